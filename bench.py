@@ -8,7 +8,9 @@ pass, inside the timed region).  Inputs are resident in HBM before the timed reg
 
 Launch:  python bench.py --gpus 1 --steps 5 --warmup 1
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps and prints the line; `--full` adds everything
+measured beside the headline (parity sample, side kernels, PyTorch-ROCm and CPU baselines, clock / power telemetry), and
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -565,6 +567,28 @@ def gpu_torch_baseline(act, sd, B, proj_steps, dev, timed_steps=5):
             "achieved_tflops": B * FLOP_PER_POSE_STEP / per_step / 1e12, "torch": torch.__version__}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays):
+    """`--dump-outputs`: the arrays a caller of the timed path receives from its last timed step, as float32
+    DIR/<name>.npy.  When they exceed DUMP_LIMIT_BYTES in all, the same fixed, seeded sample of rows is taken from every
+    array and its row indices are written beside them (sample_rows.npy, float64)."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v.detach().float().cpu().numpy()) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    total = sum(a.nbytes for a in arrays.values())
+    room = DUMP_LIMIT_BYTES - 4096                                  # (the .npy headers)
+    if total > room:
+        keep = room // (total // n + 8)                             # (+ 8 bytes per row for its index)
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: np.ascontiguousarray(a[rows]) for k, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without a launcher: re-execute under torch.distributed.run, one rank per GPU."""
     import socket
@@ -594,11 +618,16 @@ def main():
                     help="trunk arithmetic of the measured path; f16x3 and fp32 meet the 1e-4 parity gates (tests -m "
                          "gpu); f16 / bf16 are the reduced-precision comparison points of BASELINE.json configs[2], not a valid "
                          "headline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: parity_sample, the exact-fp32 / softplus / "
+                         "bf16 side runs, forward_grad_single_launch, gpu_torch_baseline, cpu_baseline, clock and power telemetry")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32; a seeded sample of rows above 64 MB)")
     ap.add_argument("--no-fp32-ref", action="store_true",
-                    help="skip the short exact-fp32 and plain-f16 runs reported beside f16x3")
-    ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU baseline work")
+                    help="--full: skip the short exact-fp32 and plain-f16 runs reported beside f16x3")
+    ap.add_argument("--cpu-budget", type=float, default=12.0, help="--full: seconds of CPU baseline work")
     ap.add_argument("--diagnostics", action="store_true",
-                    help="also emit the analysis blocks that are not part of the contract line: box (+ mem_probe, power_window), "
+                    help="implies --full, and also emits the analysis blocks: box (+ mem_probe, power_window), "
                          "regions, f16_single, fp16_checkpoint, host_twin, host_boundary, motion_denoise_config4 (~40 s more)")
     ap.add_argument("--workload", default="project", choices=["project", "denoise"],
                     help="project (default): BASELINE.json configs[2]/[3], the headline; denoise: configs[4], whole sequences "
@@ -612,8 +641,11 @@ def main():
     ap.add_argument("--no-gpu-torch-baseline", action="store_true")
     ap.add_argument("--lbs-torch-baseline", action="store_true", help="also time a PyTorch restatement of the body-model terms (4 x 300 frames)")
     ap.add_argument("--no-motion-denoise", action="store_true", help="--diagnostics: skip the configs[4] side block")
-    ap.add_argument("--no-parity-sample", action="store_true", help="skip the oracle check of a sample of the timed result")
+    ap.add_argument("--no-parity-sample", action="store_true", help="--full: skip the oracle check of a sample of the timed result")
     args = ap.parse_args()
+    full = args.full or args.diagnostics
+    if args.dump_outputs and args.steps < 1:
+        raise SystemExit("--dump-outputs needs at least one timed step")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)                                       # does not return
 
@@ -700,7 +732,7 @@ def main():
         out_shape = (T, 69)
     # receive buffer of the final gather, allocated once: equal blocks go straight into it (all_gather_into_tensor).
     # project: ONE collective carries poses AND last distances, 85 floats per pose (sharding.gather_projected)
-    from posendf_amd.sharding import ROW_FLOATS, gather_projected
+    from posendf_amd.sharding import ROW_FLOATS, gather_projected, unpack_rows
     if args.workload == "project":
         gathered = torch.empty((rows * world, ROW_FLOATS), device=dev, dtype=torch.float32) if use_dist else None
     else:
@@ -721,11 +753,12 @@ def main():
     for _ in range(args.warmup):
         one_pass()
     ev = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(3)) for _ in range(args.steps)]
-    tele = GpuTelemetry(dev_index)
+    tele = GpuTelemetry(dev_index) if full else None
     if use_dist:
         dist.barrier()
     torch.cuda.synchronize()
-    tele.start()
+    if tele is not None:
+        tele.start()
     t0 = time.perf_counter()
     for k in range(args.steps):
         ev[k][0].record()
@@ -734,13 +767,21 @@ def main():
         if use_dist:
             final_gather(qp, d)
         ev[k][2].record()
-    smi = smi_snapshot() if (tele.src is None and rank == 0 and args.steps) else None      # (launches still in flight)
+    smi = smi_snapshot() if (tele is not None and tele.src is None and rank == 0 and args.steps) else None      # (launches still in flight)
     if use_dist:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    tele.stop()
-    telemetry = tele.summary() if (tele.samples or smi is None) else smi
+    telemetry = {}
+    if tele is not None:
+        tele.stop()
+        telemetry = tele.summary() if (tele.samples or smi is None) else smi
+    if args.dump_outputs and rank == 0:
+        if args.workload == "project":
+            qa, da = unpack_rows(gathered) if use_dist else (qp, d)
+            dump_outputs(args.dump_outputs, {"projected_poses": qa, "distances": da})
+        else:
+            dump_outputs(args.dump_outputs, {"denoised_poses": gathered if use_dist else qp})
     kern_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev])) if args.steps else float("nan")
     gather_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in ev])) if (args.steps and use_dist) else 0.0
     per_rank = None
@@ -789,8 +830,10 @@ def main():
                               "sequences_total": S * world, "frames": T, "adam_steps_per_step": steps_done,
                               "parallelism": f"sequence-sharded x{world}, final all_gather" if world > 1 else "single GPU"},
                    "adam_step_ms": elapsed / max(args.steps, 1) * 1e3 / steps_done,
-                   "finite": bool(torch.isfinite(qp).all()), "telemetry": telemetry,
+                   "finite": bool(torch.isfinite(qp).all()),
                    "parity": "pose prior pinned; body model unpinned (smplx is third-party and absent; oracle/lbs_np.py)"}
+            if full:
+                out["telemetry"] = telemetry
             if dist_info is not None:
                 out["distributed"] = dist_info
             json_line = json.dumps(out)
@@ -833,7 +876,7 @@ def main():
                 "reference_fp32": {"median": float(np.median(ref)), "p95": float(np.percentile(ref, 95)), "max": float(ref.max())},
                 "tolerance": 1e-4, "within_tolerance_frac": float((mine <= 1e-4).mean())}
 
-    parity = parity_sample() if (rank == 0 and not args.no_parity_sample) else None
+    parity = parity_sample() if (full and rank == 0 and not args.no_parity_sample) else None
 
     # the exact-fp32 and the plain-fp16 kernels beside the split-precision one (same inputs, short runs, outside the
     # timed region): the three points of BASELINE.json configs[2] "fp32 vs bf16"
@@ -888,7 +931,7 @@ def main():
             ms.append((time.perf_counter() - t) * 1e3)
         return sorted(ms)[1]
 
-    side = world == 1 and not args.no_fp32_ref      # the side runs belong to the N = 1 line; scaling runs stay short
+    side = full and world == 1 and not args.no_fp32_ref      # the side runs belong to the N = 1 line; scaling runs stay short
     fwd_grad = host_ms = None
     # Where the cycles of a step go ON THIS BOX: one 3-step launch of the instrumented build of the measured kernel right
     # after the timed loop (s_memtime stamps per region; the weight ring's counted wait and barrier sampled every 16th slot),
@@ -1066,16 +1109,17 @@ def main():
             "data": "synthetic",
             # (the driver's record keeps ~120 characters of a string: what was measured comes first)
             "config": {"workload": (f"cfg[2] B={B}/GPU x{args.proj_steps} steps {args.act}: "
-                                    + {"f16x3": "f16x3 (fp32-split) timed; fp32 (exact), bf16 (not parity grade) reported",
+                                    + {"f16x3": "f16x3 (fp32-split) timed" + ("; fp32 (exact), bf16 (not parity grade) reported" if side else ""),
                                        "fp32": "fp32 (exact) timed", "f16": "f16 (NOT parity grade) timed",
                                        "bf16": "bf16 (NOT parity grade) timed"}[precision]
                                     + f"; BASELINE.json configs[2], {args.proj_steps}-step project() loop, amass.yaml arch, random-init "
                                       "weights (uniform +-2/sqrt(fan_in), lin6.bias=0.1)"),
                        "precision": precision,
                        "precisions": ("f16x3 = fp32 operands split into fp16 hi+lo, 3 MFMAs per block, fp32 accumulate (timed); "
-                                      "fp32 = exact fp32 MFMA (reported beside it: fp32_exact); bf16 = operands rounded to bfloat16, "
-                                      "1 MFMA per block (reported beside it: bf16, with its error against the fp64 oracle -- not parity "
-                                      "grade; its fp16 sibling with 3 more mantissa bits at the same rate: f16_single under --diagnostics)"),
+                                      "fp32 = exact fp32 MFMA (reported beside it under --full: fp32_exact); bf16 = operands rounded to "
+                                      "bfloat16, 1 MFMA per block (reported beside it under --full: bf16, with its error against the fp64 "
+                                      "oracle -- not parity grade; its fp16 sibling with 3 more mantissa bits at the same rate: f16_single "
+                                      "under --diagnostics)"),
                        "parity": ("NOT parity grade (operands rounded to 16 bits)" if precision in ("f16", "bf16") else
                                   "same 1e-4 gates as the fp32 kernel (tests/test_gpu_parity.py, both precisions)"),
                        "global_batch": B * world, "proj_steps": args.proj_steps,
@@ -1162,7 +1206,7 @@ def main():
             out["motion_denoise_config4"] = denoise
         if h16_ref is not None:
             out["fp16_checkpoint"] = h16_ref
-        if world == 1 and not args.no_gpu_torch_baseline:
+        if full and world == 1 and not args.no_gpu_torch_baseline:
             gt = gpu_torch_baseline(args.act, sd, B, args.proj_steps, dev)
             gt["speedup_of_value"] = out["value"] / gt["value"]
             if fp32_ref is not None:
@@ -1170,7 +1214,7 @@ def main():
             out["gpu_torch_baseline"] = gt
             rl["gpu_torch_poses_per_s"] = gt["value"]      # (scalars again: the >= 10x denominator stays with the record)
             rl["speedup_vs_gpu_torch"] = gt["speedup_of_value"]
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.act, sd, args.proj_steps, args.cpu_budget)
         if world == 1 and diag:
             # the library's own host twins (pndf_*_cpu, plain C++; what a `train.device: cpu` config runs) on the same sample:

@@ -26,11 +26,16 @@ def run_bench(*extra):
 DIAGNOSTIC_BLOCKS = {"box", "regions", "f16_single", "fp16_checkpoint", "host_twin", "host_boundary", "motion_denoise_config4"}
 
 
+# what a plain run leaves to --full
+FULL_BLOCKS = {"parity_sample", "fp32_exact", "bf16", "softplus", "roofline_softplus", "forward_grad_single_launch",
+               "gpu_torch_baseline", "cpu_baseline"}
+
+
 @pytest.mark.gpu
 def test_bench_json_line_default_precision():
-    """The DEFAULT line (what the driver runs): warm-up + timed loop + fp32_exact + softplus (with its own roofline block) +
-    gpu_torch_baseline + cpu_baseline + parity_sample -- and none of the analysis blocks."""
-    d = run_bench("--cpu-budget", "2")
+    """The --full line: warm-up + timed loop + fp32_exact + softplus (with its own roofline block) + gpu_torch_baseline +
+    cpu_baseline + parity_sample -- and none of the analysis blocks."""
+    d = run_bench("--full", "--cpu-budget", "2")
     assert REQUIRED <= set(d) and ROOFLINE <= set(d["roofline"])
     assert not (DIAGNOSTIC_BLOCKS & set(d)), DIAGNOSTIC_BLOCKS & set(d)
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["higher_is_better"] is True
@@ -80,6 +85,79 @@ def test_bench_json_line_default_precision():
     gt = d["gpu_torch_baseline"]                  # the denominator of north_star's ">= 10x", measured in the same run
     assert gt["value"] > 0 and abs(gt["speedup_of_value"] - d["value"] / gt["value"]) < 1e-9
     assert d["roofline"]["gpu_torch_poses_per_s"] == gt["value"] and d["roofline"]["speedup_vs_gpu_torch"] == gt["speedup_of_value"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run is warm-up + timed loop + the line, nothing of --full; `--dump-outputs` writes what the last timed step
+    returned, and two runs with the same arguments write the same bits (seeded inputs)."""
+    import numpy as np
+    runs = [run_bench("--dump-outputs", str(tmp_path / k)) for k in ("a", "b")]
+    for d in runs:
+        assert REQUIRED <= set(d) and ROOFLINE <= set(d["roofline"]) and not ((FULL_BLOCKS | DIAGNOSTIC_BLOCKS) & set(d))
+        assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["dtype"].startswith("f16x3") and d["unit"] == "poses/s"
+        assert d["config"]["workload"].split(": ", 1)[1].startswith("f16x3 (fp32-split) timed; BASELINE.json")
+    q, dist = (np.load(tmp_path / "a" / f"{n}.npy") for n in ("projected_poses", "distances"))
+    assert q.shape == (4096, 21, 4) and dist.shape == (4096, 1) and q.dtype == dist.dtype == np.float32
+    assert np.isfinite(q).all() and np.isfinite(dist).all()
+    assert sorted(os.listdir(tmp_path / "b")) == ["distances.npy", "projected_poses.npy"]
+    assert np.array_equal(q, np.load(tmp_path / "b" / "projected_poses.npy"))
+    assert np.array_equal(dist, np.load(tmp_path / "b" / "distances.npy"))
+    # what was dumped is the timed path's result: the 5-step projection of the seeded input batch and the distances of its
+    # last iteration (the input itself is ~1e-2 away from the projected poses, the previous iteration's d ~4e-3 away)
+    _check_projected(q, dist, [synth_poses(4096, 0)])
+
+
+def synth_poses(batch, rank):
+    """the input shard of `rank` as bench.py builds it"""
+    from posendf_amd import synth
+    return synth.make_poses(batch, seed=1234, offset=rank)
+
+
+def _check_projected(q, dist, inputs, rows=64, proj_steps=5):
+    """Dumped [sum B,21,4] poses and [sum B,1] distances against the fp64 numpy oracle's projection of the input blocks
+    (`inputs`, in rank order): a seeded sample of `rows` rows per block, the parity gate of `parity_sample`."""
+    import numpy as np
+    from conftest import d_rows, rel_err_rows
+    from oracle import posendf_np as onp
+    from posendf_amd import synth
+    sd = synth.make_weights(0, 2.0, 0.1)
+    eq, ed, lo = [], [], 0
+    for q_in in inputs:
+        idx = np.sort(np.random.default_rng(0).choice(len(q_in), min(rows, len(q_in)), replace=False))
+        q64, d64 = onp.project(q_in[idx], sd, steps=proj_steps, act="lrelu", dtype=np.float64)
+        eq.append(rel_err_rows(q[lo + idx], q64))
+        ed.append(d_rows(dist[lo + idx], d64))
+        lo += len(q_in)
+    eq, ed = np.concatenate(eq), np.concatenate(ed)
+    assert lo == len(q) and np.median(eq) < 1e-5 and (eq <= 1e-4).mean() > 0.9, (np.median(eq), eq.max())
+    assert np.median(ed) < 1e-4 and (ed <= 1e-3).mean() > 0.9, (np.median(ed), ed.max())
+
+
+def test_dump_outputs_takes_one_seeded_sample_of_rows_above_the_limit(tmp_path, monkeypatch):
+    """bench.dump_outputs: float32 files; above the size limit the same seeded rows of every array, their indices beside
+    them, and the files within the limit."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    q = torch.arange(1000 * 84, dtype=torch.float32).reshape(1000, 21, 4)
+    d = torch.arange(1000, dtype=torch.float64).reshape(1000, 1)
+    bench.dump_outputs(str(tmp_path / "all"), {"projected_poses": q, "distances": d})
+    assert sorted(os.listdir(tmp_path / "all")) == ["distances.npy", "projected_poses.npy"]
+    assert np.array_equal(np.load(tmp_path / "all" / "projected_poses.npy"), q.numpy())
+    assert np.load(tmp_path / "all" / "distances.npy").dtype == np.float32
+    limit = 4096 + 100_000
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", limit)
+    got = {}
+    for k in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / k), {"projected_poses": q, "distances": d})
+        assert sum(os.path.getsize(tmp_path / k / f) for f in os.listdir(tmp_path / k)) <= limit
+        got[k] = {n: np.load(tmp_path / k / f"{n}.npy") for n in ("projected_poses", "distances", "sample_rows")}
+    rows = got["a"]["sample_rows"].astype(np.int64)
+    assert 250 < len(rows) < 1000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(got["a"]["projected_poses"], q.numpy()[rows]) and np.array_equal(got["a"]["distances"][:, 0], rows)
+    assert all(np.array_equal(got["a"][n], got["b"][n]) for n in got["a"])
 
 
 @pytest.mark.gpu
@@ -157,19 +235,35 @@ def _one_json_line(out):
     return json.loads(lines[0])
 
 
+# Every rank is a process that holds its device open, and so is the launching bench.py, and so is this pytest process once an
+# in-process GPU test has run: N ranks on one device put N + 2 processes on it.  The shared GPU nodes the suite runs on end
+# the whole job once more than six processes hold a device open, so one device takes at most four ranks; N = 8 needs two.
+RANKS_PER_DEVICE = 4
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("world", [2, 4, 8])
-def test_bench_real_ranks_on_one_device(world):
+def test_bench_real_ranks_on_one_device(world, tmp_path):
     """The N > 1 path with REAL processes and the HIP kernel, for every world size of the driver's scaling run (N = 2, 4, 8;
-    VERDICT r3 item 3, r5 item 7): `bench.py --gpus N` launches its own N ranks under torch.distributed.run; all share the
-    one visible device (PNDF_BENCH_SHARE_DEVICE=1) and meet over gloo (RCCL refuses two ranks on one device).  Exercised:
+    VERDICT r3 item 3, r5 item 7): `bench.py --gpus N` launches its own N ranks under torch.distributed.run; they share the
+    visible devices, at most RANKS_PER_DEVICE per device (PNDF_BENCH_SHARE_DEVICE=1), and meet over gloo (RCCL refuses two
+    ranks on one device).  Exercised:
     self-launch, rank -> shard offset, ONE final collective of 85 floats per pose into the preallocated buffer with every
     rank checking its own block in it, max-over-ranks timing, whole-job value, one JSON line, and the per-rank records that
     prove the rank count."""
+    if world > RANKS_PER_DEVICE:
+        import torch
+        ndev = torch.cuda.device_count()
+        if world > RANKS_PER_DEVICE * ndev:
+            pytest.skip(f"needs {-(-world // RANKS_PER_DEVICE)} GPUs, found {ndev}: at most {RANKS_PER_DEVICE} ranks share one device")
     B = 1024
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--batch", str(B),
-           "--proj-steps", "5"]
+           "--proj-steps", "5", "--dump-outputs", str(tmp_path)]
     d = _one_json_line(subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=REPO, env=_two_rank_env(29591 + world)))
+    import numpy as np
+    q, dist = np.load(tmp_path / "projected_poses.npy"), np.load(tmp_path / "distances.npy")     # the gathered job's result
+    assert q.shape == (world * B, 21, 4) and dist.shape == (world * B, 1)
+    _check_projected(q, dist, [synth_poses(B, r) for r in range(world)], rows=16)      # every rank's block, in rank order
     assert d["n_gpus"] == world and d["scaling"] == "weak" and d["config"]["global_batch"] == world * B
     di = d["distributed"]
     assert di["world_size"] == world and di["backend"] == "gloo" and di["ranks_share_devices"] is True
@@ -186,17 +280,28 @@ def test_bench_real_ranks_on_one_device(world):
 
 
 @pytest.mark.gpu
-def test_bench_denoise_workload_two_ranks():
+def test_bench_denoise_workload_two_ranks(tmp_path):
     """BASELINE.json configs[4] has an N-rank line too: `--workload denoise` shards whole sequences over the ranks
     (experiments/motion_denoise.py:171-188 loops sequences), runs fused Adam steps of the reference's objective and gathers
     the denoised poses once.  One rank first (the N = 1 line), then two real ranks on the one device."""
     base = [sys.executable, os.path.join(REPO, "bench.py"), "--workload", "denoise", "--steps", "2", "--warmup", "1", "--seqs", "3",
             "--frames", "24", "--adam-steps", "4"]
     env1 = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    d1 = _one_json_line(subprocess.run(base + ["--gpus", "1"], capture_output=True, text=True, timeout=900, cwd=REPO, env=env1))
+    d1 = _one_json_line(subprocess.run(base + ["--gpus", "1", "--dump-outputs", str(tmp_path / "1")], capture_output=True, text=True,
+                                       timeout=900, cwd=REPO, env=env1))
     assert d1["n_gpus"] == 1 and d1["unit"] == "frame-steps/s" and d1["finite"] and d1["value"] > 0
     assert "configs[4]" in d1["config"]["workload"] and d1["config"]["sequences_total"] == 3 and "distributed" not in d1
-    d2 = _one_json_line(subprocess.run(base + ["--gpus", "2"], capture_output=True, text=True, timeout=900, cwd=REPO, env=_two_rank_env(29593)))
+    d2 = _one_json_line(subprocess.run(base + ["--gpus", "2", "--dump-outputs", str(tmp_path / "2")], capture_output=True, text=True,
+                                       timeout=900, cwd=REPO, env=_two_rank_env(29593)))
+    import numpy as np
+    th1, th2 = (np.load(tmp_path / k / "denoised_poses.npy") for k in ("1", "2"))
+    # rank 0 of the two-rank job draws the same sequences as the one-rank job, and its block comes first in the gather
+    assert th1.shape == (3, 24, 69) and th2.shape == (6, 24, 69) and np.allclose(th2[:3], th1, rtol=1e-5, atol=1e-6)
+    import torch
+    gen = torch.Generator().manual_seed(1000)      # rank 0's noisy input sequences, as bench.py draws them
+    theta = (torch.cumsum(0.02 * torch.randn(3, 24, 69, generator=gen), dim=1) + 0.3 * torch.randn(3, 1, 69, generator=gen)
+             + 0.1 * torch.randn(3, 24, 69, generator=gen)).numpy()
+    assert np.isfinite(th1).all() and np.abs(th1 - theta).max() > 1e-3      # the optimised poses, not the input
     assert d2["n_gpus"] == 2 and d2["config"]["sequences_total"] == 6 and d2["finite"]
     di = d2["distributed"]
     assert di["world_size"] == 2 and di["gathered_rows"] == 6 and all(r["own_block_in_gather"] for r in di["per_rank"])

@@ -52,7 +52,7 @@ def _worker(rank, world, port, total, steps, outdir):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("total,world", [(64, 2), (37, 2), (64, 4), (43, 4)])
+@pytest.mark.parametrize("total,world", [(64, 2), (37, 2), (64, 4), (43, 4), (64, 8)])
 def test_gloo_ranks_match_unsharded(tmp_path, total, world):
     from oracle import posendf_np as onp
     from posendf_amd import synth
