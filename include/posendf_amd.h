@@ -235,6 +235,32 @@ int64_t pndf_lbs_packed_split_bytes(int32_t V);
 int pndf_lbs_pack_split_host(int32_t V, const float* blob, void* sblob, float* scales_out);
 const char* pndf_lbs_last_error(pndf_lbs_handle h);    /* h may be NULL: last error of a failed pndf_lbs_create */
 
+/* ---- the training objective (model/posendf.py:62-99, train=True; what model/train_posendf.py:87-96 runs every step) and its
+ * weight gradients.  q [B,21,4] noisy poses, dist_gt [B] their labels, q_man [Bm,21,4] manifold poses:
+ *   dist = mean_b |d(normalize(q, dim=1)) - dist_gt|  (loss_type 0 = L1Loss; 1 = MSELoss),  man = mean_b |d(q_man)|  (no
+ *   normalisation, as in the reference),  eikonal = mean_{b,j} (|d d / d q[b,j,:]|_2 - 1)^2.
+ * The handle carries the plan: the architecture of the config, i.e. every network that pndf_create accepts with the structure
+ * encoder (an encoder-less config is PNDF_ERR_UNSUPPORTED: the reference cannot train one either); exact fp32 MFMA, `precision`
+ * is ignored.
+ * Compute calls take DEVICE pointers, enqueue on `stream` and allocate nothing: all scratch is `workspace`
+ * (pndf_train_workspace_floats(h, B, Bm, eikonal) floats, 16-byte aligned), which carries the forward's state to the backward.
+ * Weights are read in place: `weights` is a HOST array of DEVICE pointers in state-dict order (the tensors of pndf_load_weights,
+ * row-major [out,in] as torch stores them).  Deterministic: the same inputs give the same bits (fixed K splits, no atomics). */
+typedef struct pndf_train_plan* pndf_train_handle;
+int pndf_train_create(pndf_train_handle* out, const pndf_config* cfg, int device);    /* PNDF_ERR_NO_DEVICE without gfx950 */
+int pndf_train_destroy(pndf_train_handle h);
+int64_t pndf_train_workspace_floats(pndf_train_handle h, int64_t B, int64_t Bm, int32_t eikonal);
+/* The forward half: both batches, the losses and, with eikonal != 0, the input gradient and the tangent pass the eikonal term's
+ * double backward needs.  losses: device [3] = dist, man, eikonal (0 when eikonal == 0). */
+int pndf_train_forward(pndf_train_handle h, const float* const* weights, const float* q, const float* dist_gt, const float* q_man,
+                       int64_t B, int64_t Bm, int32_t loss_type, int32_t eikonal, float* losses, void* workspace, void* stream);
+/* The backward half, once per forward, on the workspace that forward filled: upstream = device [3] d(total) / d(dist, man,
+ * eikonal), read on the device (no synchronisation); grads: HOST array of DEVICE pointers in the order of `weights`, written
+ * (not added).  With eikonal == 0 only `dist` has a gradient, as in the reference's (loss, {'dist': loss}) branch. */
+int pndf_train_backward(pndf_train_handle h, const float* const* weights, const float* upstream, float* const* grads,
+                        void* workspace, void* stream);
+const char* pndf_train_last_error(pndf_train_handle h);  /* h may be NULL: last error of a failed pndf_train_create */
+
 /* ---- quaternion pose distance + k nearest candidates (data/dist_utils.py:9-50, classes euc / geo; caller
  * data/prepare_traindata.py:159).  noise [B,21,4], valid [B,K,21,4] (device, 16-byte aligned);
  * metric 0 = geo: sum_j w_j (1 - |<q_valid_j, q_noise_j>|), 1 = euc: sum_j w_j ||q_noise_j - q_valid_j||;

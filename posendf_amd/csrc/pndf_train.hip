@@ -1,0 +1,970 @@
+// PoseNDF's training objective and its weight gradients on gfx950 (model/posendf.py:62-99, the train=True branch that
+// model/train_posendf.py:87-96 runs every step).
+//
+// Layer by layer over the whole batch, activations in HBM: the weight gradients are reductions over every pose, which a
+// persistent per-pose kernel cannot hold.  Every activation matrix is [features][columns] (the pose index contiguous) with the
+// columns ordered  [ noisy primal (B) | manifold primal (Bm) | noisy tangent (B) ].
+//   forward : encoder (noisy: x = normalize(q, dim=1); manifold: raw q) -> NN GEMMs over the B + Bm primal columns, epilogue
+//             bias + sigma, stores a, sigma' and (softplus) sigma'';  the losses.
+//   eikonal : input gradient of the noisy batch (TN GEMMs, epilogue * sigma'), encoder backward, G = J_N^T g_x, the seed
+//             Gbar = (2 / 21B)(|G_j| - 1) G_j / |G_j|, xdot = J_N Gbar, tangent encoder, tangent NN GEMMs (no bias, epilogue
+//             * sigma'; softplus: sigma'' zdot kept for the reverse).
+//   backward: one reverse pass over the dual network.  Seeds on the output, then per layer  Wbar = [zbar|zdotbar][a|adot]^T
+//             (NT GEMM, K split in a fixed way, partial slabs, a second launch sums them in order), bbar = row sums over the
+//             primal columns, [abar|adotbar] = W^T [zbar|zdotbar] (TN GEMM) with zbar = abar sigma' + adotbar zdot sigma''
+//             and zdotbar = adotbar sigma' in the epilogue; the 21 bone MLPs of the encoder last, lanes owning poses, their
+//             weight gradients summed per workgroup (fixed order) and then over workgroups (fixed order).
+// Arithmetic: exact fp32 MFMA (v_mfma_f32_16x16x4_f32), fp32 accumulate.  No float atomics, no communication between
+// workgroups inside a launch: two calls with the same inputs give the same bits.
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+#include <string.h>
+
+#include <cmath>
+#include <mutex>
+#include <string>
+#include <unordered_map>
+
+#include "../../include/posendf_amd.h"
+#include "pndf_experiment.h"
+#include "pndf_host.h"
+
+PNDF_EXPORT_EXPERIMENT_WORD(train)
+
+namespace {
+
+constexpr int NJ = 21, FEAT = 6, HID = 10, BONE = 4;
+constexpr int ENC_IN = NJ * FEAT;          // 126: the encoder's output, the trunk's input
+constexpr int POSE = NJ * BONE;            // 84
+constexpr int MAX_LIN = 8;                 // 1 .. 7 hidden layers -> 2 .. 8 linear layers
+constexpr int ENC_TENSORS = 4 * NJ;        // 84
+constexpr float NORM_EPS = 1e-12f;         // F.normalize
+constexpr float LRELU_SLOPE = 0.01f;       // nn.LeakyReLU()
+constexpr float SP_THRESHOLD = 20.f;       // nn.Softplus(threshold=20)
+
+// GEMM tiling: a 128 x 128 output tile per 256-thread workgroup, K steps of 16, each wave a 64 x 64 quarter as 4 x 4 blocks of
+// the 16x16x4 fp32 MFMA.  LDS rows padded to 144 floats: the four k-rows one fragment read touches fall on distinct banks.
+constexpr int TM = 128, TN = 128, TK = 16, LDS_LD = 144;
+constexpr int SPLIT_TARGET_WGS = 1024;     // split-K target of the weight-gradient GEMM: a constant, never the device's occupancy
+constexpr int ENC_WG = 192;                // poses per workgroup of the encoder's dual reverse (>= 176, the largest bone)
+constexpr int ENC_VEC = 72;                // per-pose vectors the encoder's reduction reads from LDS
+constexpr int ENC_LDS_LD = ENC_WG + 1;
+
+enum { EPI_STORE = 0, EPI_FWD = 1, EPI_TAN = 2, EPI_MUL = 3 };
+enum { LOSS_L1 = 0, LOSS_L2 = 1 };
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+struct GemmArgs {
+    const float* A;
+    const float* B;
+    float* C;
+    int64_t lda, ldb, ldc;
+    int M, N, K, kc;          // kc: K range of one blockIdx.z (split-K)
+    int64_t slab;             // C offset per blockIdx.z
+    int epi, act, out_layer;
+    float beta;
+    const float* bias;
+    float* D1;                // sigma'(z)                     [M][ld1]
+    float* D2;                // sigma'' (then sigma'' zdot)   [M][ld2], columns < nB only
+    const float* X;           // EPI_MUL: cross term added on columns < nB
+    int64_t ld1, ld2, ldx;
+    int64_t nB;
+    int64_t np_split;         // EPI_MUL: columns >= np_split read sigma' at (column - np_split)
+};
+
+__device__ __forceinline__ void act_eval(int act, float beta, bool out, float z, float& a, float& d1, float& d2) {
+    if (act == PNDF_ACT_SOFTPLUS) {
+        const float bz = beta * z;
+        if (bz > SP_THRESHOLD) {
+            a = z; d1 = 1.f; d2 = 0.f;
+        } else {
+            const float e = expf(bz);
+            a = log1pf(e) / beta;
+            const float s = e / (e + 1.f);
+            d1 = s;
+            d2 = beta * s * (1.f - s);
+        }
+    } else if (act == PNDF_ACT_RELU || out) {
+        a = z > 0.f ? z : 0.f; d1 = z > 0.f ? 1.f : 0.f; d2 = 0.f;
+    } else {
+        a = z > 0.f ? z : LRELU_SLOPE * z; d1 = z > 0.f ? 1.f : LRELU_SLOPE; d2 = 0.f;
+    }
+}
+
+// C(m, n) = sum_k A(m, k) B(k, n).  A_KC: A(m, k) = A[m lda + k] (else A[k lda + m]);  B_KC: B(k, n) = B[n ldb + k] (else
+// B[k ldb + n]).  Every load outside [0, M) x [kbeg, kend) x [0, N) reads zero; every store is bounds checked.
+template <int A_KC, int B_KC>
+__device__ __forceinline__ void gemm_body(const GemmArgs& g) {
+    __shared__ float As[TK][LDS_LD];
+    __shared__ float Bs[TK][LDS_LD];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int wm = w & 1, wn = w >> 1;
+    const int m0 = blockIdx.y * TM, n0 = blockIdx.x * TN;
+    const int kbeg = blockIdx.z * g.kc;
+    const int kend = min(g.K, kbeg + g.kc);
+    float ra[8], rb[8];
+    auto load = [&](int k0) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int mm = A_KC ? (tid >> 4) + 16 * i : (tid & 127);
+            const int ka = A_KC ? (tid & 15) : (tid >> 7) + 2 * i;
+            const int m = m0 + mm, k = k0 + ka;
+            ra[i] = (m < g.M && k < kend) ? (A_KC ? g.A[(int64_t)m * g.lda + k] : g.A[(int64_t)k * g.lda + m]) : 0.f;
+            const int nn = B_KC ? (tid >> 4) + 16 * i : (tid & 127);
+            const int kb = B_KC ? (tid & 15) : (tid >> 7) + 2 * i;
+            const int n = n0 + nn, kk = k0 + kb;
+            rb[i] = (n < g.N && kk < kend) ? (B_KC ? g.B[(int64_t)n * g.ldb + kk] : g.B[(int64_t)kk * g.ldb + n]) : 0.f;
+        }
+    };
+    f32x4 acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (kbeg < kend) load(kbeg);
+    for (int k0 = kbeg; k0 < kend; k0 += TK) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            As[A_KC ? (tid & 15) : (tid >> 7) + 2 * i][A_KC ? (tid >> 4) + 16 * i : (tid & 127)] = ra[i];
+            Bs[B_KC ? (tid & 15) : (tid >> 7) + 2 * i][B_KC ? (tid >> 4) + 16 * i : (tid & 127)] = rb[i];
+        }
+        __syncthreads();
+        if (k0 + TK < kend) load(k0 + TK);
+#pragma unroll
+        for (int s = 0; s < TK / 4; ++s) {
+            float a[4], b[4];
+            const int kr = s * 4 + (lane >> 4);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                a[i] = As[kr][wm * 64 + i * 16 + (lane & 15)];
+                b[i] = Bs[kr][wn * 64 + i * 16 + (lane & 15)];
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    float* C = g.C + (int64_t)blockIdx.z * g.slab;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = m0 + wm * 64 + i * 16 + (lane >> 4) * 4 + r;
+                const int col = n0 + wn * 64 + j * 16 + (lane & 15);
+                if (row >= g.M || col >= g.N) continue;
+                const float v = acc[i][j][r];
+                float* out = C + (int64_t)row * g.ldc + col;
+                if (g.epi == EPI_STORE) {
+                    *out = v;
+                } else if (g.epi == EPI_FWD) {
+                    float a, d1, d2;
+                    act_eval(g.act, g.beta, g.out_layer != 0, v + g.bias[row], a, d1, d2);
+                    *out = a;
+                    g.D1[(int64_t)row * g.ld1 + col] = d1;
+                    if (g.D2 && col < g.nB) g.D2[(int64_t)row * g.ld2 + col] = d2;
+                } else if (g.epi == EPI_TAN) {      // tangent forward (v = zdot) and tangent reverse (v = adotbar)
+                    *out = v * g.D1[(int64_t)row * g.ld1 + col];
+                    if (g.D2) {
+                        float* d2 = g.D2 + (int64_t)row * g.ld2 + col;
+                        *d2 = v * *d2;
+                    }
+                } else {                            // EPI_MUL: v sigma' (+ the cross term); raw without sigma'
+                    float o = v;
+                    if (g.D1) o *= g.D1[(int64_t)row * g.ld1 + (col >= g.np_split ? col - g.np_split : col)];
+                    if (g.X && col < g.nB) o += g.X[(int64_t)row * g.ldx + col];
+                    *out = o;
+                }
+            }
+}
+
+}  // namespace
+
+extern "C" __global__ void __launch_bounds__(256) pndf_train_gemm_nn_kernel(GemmArgs g) { gemm_body<1, 0>(g); }
+extern "C" __global__ void __launch_bounds__(256) pndf_train_gemm_tn_kernel(GemmArgs g) { gemm_body<0, 0>(g); }
+extern "C" __global__ void __launch_bounds__(256) pndf_train_gemm_nt_kernel(GemmArgs g) { gemm_body<1, 1>(g); }
+
+namespace {
+
+// ---- encoder: 21 bone MLPs (4 | 10 -> 10 -> 6), the weights packed in state-dict order into one flat array
+struct EncArgs {
+    const float* wenc;        // packed encoder weights
+    const float* q;           // noisy poses [B][84]
+    const float* qm;          // manifold poses [Bm][84]
+    const float* dgt;         // labels [B]
+    float* X;                 // network input per primal column [84][np]: normalised noisy poses, raw manifold poses
+    float* dgt_copy;          // [B]
+    float* act0;              // encoder output [126][ncols]
+    float* U0;                // d dist / d act0 of the noisy columns [126][B]
+    float* Xd;                // x gradient, then Gbar, then xdot [84][B]
+    float* eikp;              // per pose: sum_j (|G_j| - 1)^2 [B]
+    float* abar;              // adjoint of act0 [126][ncols] (backward: accumulated in place)
+    float* part;              // per-workgroup encoder weight-gradient partials [wgs][n_params]
+    int64_t B, Bm, np, ncols;
+    int act, eik, n_params;
+    float beta;
+    int parent[NJ];
+    int off[NJ];
+};
+
+template <int FIN>
+__device__ __forceinline__ void bone_lin0(const float* w, const float* in, float* zh, bool bias) {
+#pragma unroll
+    for (int i = 0; i < HID; ++i) {
+        float s = bias ? w[HID * FIN + i] : 0.f;
+#pragma unroll
+        for (int k = 0; k < FIN; ++k) s = fmaf(w[i * FIN + k], in[k], s);
+        zh[i] = s;
+    }
+}
+template <int FIN>
+__device__ __forceinline__ const float* bone_w2(const float* w) { return w + HID * FIN + HID; }
+
+// one bone's primal forward: activations and derivatives of both layers
+template <int FIN>
+__device__ __forceinline__ void bone_fwd(const EncArgs& e, const float* w, const float* in, float* ah, float* d1h, float* d2h,
+                                         float* ao, float* d1o, float* d2o) {
+    float zh[HID];
+    bone_lin0<FIN>(w, in, zh, true);
+#pragma unroll
+    for (int i = 0; i < HID; ++i) act_eval(e.act, e.beta, false, zh[i], ah[i], d1h[i], d2h[i]);
+    const float* w2 = bone_w2<FIN>(w);
+#pragma unroll
+    for (int i = 0; i < FEAT; ++i) {
+        float s = w2[FEAT * HID + i];
+#pragma unroll
+        for (int k = 0; k < HID; ++k) s = fmaf(w2[i * HID + k], ah[k], s);
+        act_eval(e.act, e.beta, false, s, ao[i], d1o[i], d2o[i]);
+    }
+}
+
+// bone j's input on primal column `col`: its own quaternion (X) and its parent's feature (act0)
+template <int FIN>
+__device__ __forceinline__ void load_in(const EncArgs& e, int j, int64_t col, float* in) {
+#pragma unroll
+    for (int k = 0; k < BONE; ++k) in[k] = e.X[(int64_t)(j * BONE + k) * e.np + col];
+    if (FIN > BONE) {
+        const int p = e.parent[j];
+#pragma unroll
+        for (int i = 0; i < FIN - BONE; ++i) in[BONE + i] = e.act0[(int64_t)(p * FEAT + i) * e.ncols + col];
+    }
+}
+// the tangent of bone j's input on noisy column c: xdot and the parent's tangent feature
+template <int FIN>
+__device__ __forceinline__ void load_in_tan(const EncArgs& e, int j, int64_t c, float* ind) {
+#pragma unroll
+    for (int k = 0; k < BONE; ++k) ind[k] = e.Xd[(int64_t)(j * BONE + k) * e.B + c];
+    if (FIN > BONE) {
+        const int p = e.parent[j];
+#pragma unroll
+        for (int i = 0; i < FIN - BONE; ++i) ind[BONE + i] = e.act0[(int64_t)(p * FEAT + i) * e.ncols + e.np + c];
+    }
+}
+
+template <int FIN>
+__device__ __forceinline__ void enc_fwd_bone(const EncArgs& e, int j, int64_t c) {
+    float in[FIN], ah[HID], d1h[HID], d2h[HID], ao[FEAT], d1o[FEAT], d2o[FEAT];
+    load_in<FIN>(e, j, c, in);
+    bone_fwd<FIN>(e, e.wenc + e.off[j], in, ah, d1h, d2h, ao, d1o, d2o);
+#pragma unroll
+    for (int i = 0; i < FEAT; ++i) e.act0[(int64_t)(j * FEAT + i) * e.ncols + c] = ao[i];
+}
+
+// first-order reverse of one bone (input gradient of the noisy batch): the gradient on act0's rows of bone j (U0) -> the x
+// gradient (Xd) and the parent's feature gradient (accumulated into U0)
+template <int FIN>
+__device__ __forceinline__ void enc_grad_bone(const EncArgs& e, int j, int64_t c) {
+    const float* w = e.wenc + e.off[j];
+    const float* w2 = bone_w2<FIN>(w);
+    float in[FIN], ah[HID], d1h[HID], d2h[HID], ao[FEAT], d1o[FEAT], d2o[FEAT];
+    load_in<FIN>(e, j, c, in);
+    bone_fwd<FIN>(e, w, in, ah, d1h, d2h, ao, d1o, d2o);
+    float go[FEAT], gh[HID];
+#pragma unroll
+    for (int i = 0; i < FEAT; ++i) go[i] = e.U0[(int64_t)(j * FEAT + i) * e.B + c] * d1o[i];
+#pragma unroll
+    for (int k = 0; k < HID; ++k) {
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < FEAT; ++i) s = fmaf(w2[i * HID + k], go[i], s);
+        gh[k] = s * d1h[k];
+    }
+#pragma unroll
+    for (int m = 0; m < FIN; ++m) {
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < HID; ++k) s = fmaf(w[k * FIN + m], gh[k], s);
+        if (m < BONE) e.Xd[(int64_t)(j * BONE + m) * e.B + c] = s;
+        else e.U0[(int64_t)(e.parent[j] * FEAT + (m - BONE)) * e.B + c] += s;
+    }
+}
+
+// tangent forward of one bone along xdot
+template <int FIN>
+__device__ __forceinline__ void enc_tan_bone(const EncArgs& e, int j, int64_t c) {
+    const float* w = e.wenc + e.off[j];
+    const float* w2 = bone_w2<FIN>(w);
+    float in[FIN], ind[FIN], ah[HID], d1h[HID], d2h[HID], ao[FEAT], d1o[FEAT], d2o[FEAT];
+    load_in<FIN>(e, j, c, in);
+    load_in_tan<FIN>(e, j, c, ind);
+    bone_fwd<FIN>(e, w, in, ah, d1h, d2h, ao, d1o, d2o);
+    float hd[HID];
+    bone_lin0<FIN>(w, ind, hd, false);
+#pragma unroll
+    for (int k = 0; k < HID; ++k) hd[k] *= d1h[k];
+#pragma unroll
+    for (int i = 0; i < FEAT; ++i) {
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < HID; ++k) s = fmaf(w2[i * HID + k], hd[k], s);
+        e.act0[(int64_t)(j * FEAT + i) * e.ncols + e.np + c] = s * d1o[i];
+    }
+}
+
+// dual reverse of one bone for one pose: the primal and tangent adjoints of the bone's output (abar, in place) -> the parent's,
+// and the per-pose vectors whose outer products make the bone's weight gradient (to LDS, column `lane`)
+template <int FIN>
+__device__ __forceinline__ void enc_rev_bone(const EncArgs& e, int j, int64_t c, bool active, bool tangent,
+                                             float (*sv)[ENC_LDS_LD], int lane) {
+    float in[HID] = {}, ind[HID] = {}, zhb[HID] = {}, zhdb[HID] = {}, ah[HID] = {}, ahd[HID] = {}, zob[FEAT] = {}, zodb[FEAT] = {};
+    if (active) {
+        const float* w = e.wenc + e.off[j];
+        const float* w2 = bone_w2<FIN>(w);
+        const int64_t tc = e.np + c;
+        load_in<FIN>(e, j, c, in);
+        if (tangent) load_in_tan<FIN>(e, j, c, ind);
+        float d1h[HID], d2h[HID], ao[FEAT], d1o[FEAT], d2o[FEAT];
+        bone_fwd<FIN>(e, w, in, ah, d1h, d2h, ao, d1o, d2o);
+        float hz[HID], oz[FEAT];       // tangent pre-activations
+        bone_lin0<FIN>(w, ind, hz, false);
+#pragma unroll
+        for (int k = 0; k < HID; ++k) ahd[k] = d1h[k] * hz[k];
+#pragma unroll
+        for (int i = 0; i < FEAT; ++i) {
+            float s = 0.f;
+#pragma unroll
+            for (int k = 0; k < HID; ++k) s = fmaf(w2[i * HID + k], ahd[k], s);
+            oz[i] = s;
+        }
+#pragma unroll
+        for (int i = 0; i < FEAT; ++i) {
+            const float ab = e.abar[(int64_t)(j * FEAT + i) * e.ncols + c];
+            const float adb = tangent ? e.abar[(int64_t)(j * FEAT + i) * e.ncols + tc] : 0.f;
+            zob[i] = ab * d1o[i] + adb * oz[i] * d2o[i];
+            zodb[i] = adb * d1o[i];
+        }
+#pragma unroll
+        for (int k = 0; k < HID; ++k) {
+            float s = 0.f, sd = 0.f;
+#pragma unroll
+            for (int i = 0; i < FEAT; ++i) {
+                s = fmaf(w2[i * HID + k], zob[i], s);
+                sd = fmaf(w2[i * HID + k], zodb[i], sd);
+            }
+            zhb[k] = s * d1h[k] + sd * hz[k] * d2h[k];
+            zhdb[k] = sd * d1h[k];
+        }
+        if (FIN > BONE) {
+            const int p = e.parent[j];
+#pragma unroll
+            for (int m = BONE; m < FIN; ++m) {
+                float s = 0.f, sd = 0.f;
+#pragma unroll
+                for (int k = 0; k < HID; ++k) {
+                    s = fmaf(w[k * FIN + m], zhb[k], s);
+                    sd = fmaf(w[k * FIN + m], zhdb[k], sd);
+                }
+                e.abar[(int64_t)(p * FEAT + (m - BONE)) * e.ncols + c] += s;
+                if (tangent) e.abar[(int64_t)(p * FEAT + (m - BONE)) * e.ncols + tc] += sd;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < HID; ++k) {
+        sv[k][lane] = in[k];
+        sv[10 + k][lane] = ind[k];
+        sv[20 + k][lane] = zhb[k];
+        sv[30 + k][lane] = zhdb[k];
+        sv[40 + k][lane] = ah[k];
+        sv[50 + k][lane] = ahd[k];
+    }
+#pragma unroll
+    for (int i = 0; i < FEAT; ++i) {
+        sv[60 + i][lane] = zob[i];
+        sv[66 + i][lane] = zodb[i];
+    }
+}
+
+// parameter t of a bone (state-dict order inside the bone), summed over the workgroup's poses in order
+template <int FIN>
+__device__ __forceinline__ float enc_param_sum(float (*sv)[ENC_LDS_LD], int t) {
+    float s = 0.f;
+    if (t < HID * FIN) {
+        const int i = t / FIN, k = t % FIN;
+        for (int l = 0; l < ENC_WG; ++l) s = fmaf(sv[30 + i][l], sv[10 + k][l], fmaf(sv[20 + i][l], sv[k][l], s));
+    } else if (t < HID * FIN + HID) {
+        const int i = t - HID * FIN;
+        for (int l = 0; l < ENC_WG; ++l) s += sv[20 + i][l];
+    } else if (t < HID * FIN + HID + FEAT * HID) {
+        const int u = t - HID * FIN - HID, i = u / HID, k = u % HID;
+        for (int l = 0; l < ENC_WG; ++l) s = fmaf(sv[66 + i][l], sv[50 + k][l], fmaf(sv[60 + i][l], sv[40 + k][l], s));
+    } else {
+        const int i = t - HID * FIN - HID - FEAT * HID;
+        for (int l = 0; l < ENC_WG; ++l) s += sv[60 + i][l];
+    }
+    return s;
+}
+
+}  // namespace
+
+// encoder forward over the primal columns; the noisy ones normalised over the joint axis first (F.normalize(q, dim=1))
+extern "C" __global__ void __launch_bounds__(256) pndf_train_enc_fwd_kernel(EncArgs e) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= e.np) return;
+    if (c < e.B) {
+        const float* q = e.q + c * POSE;
+        float n2[BONE] = {0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+            for (int k = 0; k < BONE; ++k) n2[k] = fmaf(q[j * BONE + k], q[j * BONE + k], n2[k]);
+        float den[BONE];
+#pragma unroll
+        for (int k = 0; k < BONE; ++k) den[k] = fmaxf(sqrtf(n2[k]), NORM_EPS);
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+            for (int k = 0; k < BONE; ++k) e.X[(int64_t)(j * BONE + k) * e.np + c] = q[j * BONE + k] / den[k];
+        e.dgt_copy[c] = e.dgt[c];
+    } else {
+        const float* q = e.qm + (c - e.B) * POSE;
+        for (int f = 0; f < POSE; ++f) e.X[(int64_t)f * e.np + c] = q[f];
+    }
+    for (int j = 0; j < NJ; ++j) {
+        if (e.parent[j] < 0) enc_fwd_bone<BONE>(e, j, c);
+        else enc_fwd_bone<BONE + FEAT>(e, j, c);
+    }
+}
+
+// noisy columns: encoder backward of the input gradient, G = J_N^T g_x, the eikonal partial sums and seed, xdot = J_N Gbar, and
+// the tangent encoder forward into act0's tangent columns
+extern "C" __global__ void __launch_bounds__(256) pndf_train_enc_eik_kernel(EncArgs e) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= e.B) return;
+    for (int j = NJ - 1; j >= 0; --j) {
+        if (e.parent[j] < 0) enc_grad_bone<BONE>(e, j, c);
+        else enc_grad_bone<BONE + FEAT>(e, j, c);
+    }
+    const float* q = e.q + c * POSE;
+    float nrm[BONE] = {0.f, 0.f, 0.f, 0.f}, s[BONE] = {0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int k = 0; k < BONE; ++k) {
+            nrm[k] = fmaf(q[j * BONE + k], q[j * BONE + k], nrm[k]);
+            s[k] = fmaf(e.X[(int64_t)(j * BONE + k) * e.np + c], e.Xd[(int64_t)(j * BONE + k) * e.B + c], s[k]);
+        }
+#pragma unroll
+    for (int k = 0; k < BONE; ++k) nrm[k] = sqrtf(nrm[k]);
+    // J_N v = (v - x (x . v)) / |q_k| per quaternion component k (a column of 21 joints); v / eps where the norm is clamped
+    const float coef = 2.f / (21.f * (float)e.B);
+    float eik = 0.f, t[BONE] = {0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NJ; ++j) {
+        float G[BONE], x[BONE], n2 = 0.f;
+#pragma unroll
+        for (int k = 0; k < BONE; ++k) {
+            x[k] = e.X[(int64_t)(j * BONE + k) * e.np + c];
+            const float gx = e.Xd[(int64_t)(j * BONE + k) * e.B + c];
+            G[k] = nrm[k] >= NORM_EPS ? (gx - x[k] * s[k]) / nrm[k] : gx / NORM_EPS;
+            n2 = fmaf(G[k], G[k], n2);
+        }
+        const float n = sqrtf(n2);
+        eik = fmaf(n - 1.f, n - 1.f, eik);
+        const float f = n > 0.f ? coef * (n - 1.f) / n : 0.f;
+#pragma unroll
+        for (int k = 0; k < BONE; ++k) {
+            const float gb = f * G[k];
+            e.Xd[(int64_t)(j * BONE + k) * e.B + c] = gb;
+            t[k] = fmaf(x[k], gb, t[k]);
+        }
+    }
+    e.eikp[c] = eik;
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int k = 0; k < BONE; ++k) {
+            float* p = e.Xd + (int64_t)(j * BONE + k) * e.B + c;
+            const float x = e.X[(int64_t)(j * BONE + k) * e.np + c];
+            *p = nrm[k] >= NORM_EPS ? (*p - x * t[k]) / nrm[k] : *p / NORM_EPS;
+        }
+    for (int j = 0; j < NJ; ++j) {
+        if (e.parent[j] < 0) enc_tan_bone<BONE>(e, j, c);
+        else enc_tan_bone<BONE + FEAT>(e, j, c);
+    }
+}
+
+// dual reverse of the encoder: lanes own poses (the noisy ones, and the manifold ones when the eikonal term is on); per bone
+// the workgroup's weight-gradient partial sums go to `part` (one row per workgroup)
+extern "C" __global__ void __launch_bounds__(ENC_WG) pndf_train_enc_rev_kernel(EncArgs e) {
+    __shared__ float sv[ENC_VEC][ENC_LDS_LD];
+    const int lane = threadIdx.x;
+    const int64_t c = (int64_t)blockIdx.x * ENC_WG + lane;
+    const int64_t P = e.eik ? e.np : e.B;
+    const bool active = c < P, tangent = e.eik && c < e.B;
+    float* part = e.part + (int64_t)blockIdx.x * e.n_params;
+    for (int j = NJ - 1; j >= 0; --j) {
+        const bool root = e.parent[j] < 0;
+        if (root) enc_rev_bone<BONE>(e, j, c, active, tangent, sv, lane);
+        else enc_rev_bone<BONE + FEAT>(e, j, c, active, tangent, sv, lane);
+        __syncthreads();
+        const int size = root ? HID * BONE + HID + FEAT * HID + FEAT : HID * (BONE + FEAT) + HID + FEAT * HID + FEAT;
+        if (lane < size) part[e.off[j] + lane] = root ? enc_param_sum<BONE>(sv, lane) : enc_param_sum<BONE + FEAT>(sv, lane);
+        __syncthreads();
+    }
+}
+
+namespace {
+struct PtrTable {
+    float* p[ENC_TENSORS];
+    int off[ENC_TENSORS + 1];
+};
+}  // namespace
+
+// the caller's 84 encoder tensors -> one flat array
+extern "C" __global__ void __launch_bounds__(256) pndf_train_enc_pack_kernel(PtrTable t, float* dst) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= t.off[ENC_TENSORS]) return;
+    int k = 0;
+    while (t.off[k + 1] <= i) ++k;
+    dst[i] = t.p[k][i - t.off[k]];
+}
+
+// per-workgroup partials -> the caller's 84 encoder gradient tensors, summed over workgroups in order
+extern "C" __global__ void __launch_bounds__(256) pndf_train_enc_reduce_kernel(PtrTable t, const float* part, int wgs) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int n = t.off[ENC_TENSORS];
+    if (i >= n) return;
+    float s = 0.f;
+    for (int w = 0; w < wgs; ++w) s += part[(int64_t)w * n + i];
+    int k = 0;
+    while (t.off[k + 1] <= i) ++k;
+    t.p[k][i - t.off[k]] = s;
+}
+
+// split-K slabs -> the weight gradient, summed over the slabs in order
+extern "C" __global__ void __launch_bounds__(256) pndf_train_slab_reduce_kernel(const float* slab, int S, int64_t n, float* out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float s = 0.f;
+    for (int z = 0; z < S; ++z) s += slab[(int64_t)z * n + i];
+    out[i] = s;
+}
+
+// bias gradient: row sums over the primal columns, one workgroup per row, a fixed-order tree
+extern "C" __global__ void __launch_bounds__(256) pndf_train_row_sum_kernel(const float* Z, int64_t ld, int64_t ncols, float* out) {
+    __shared__ float red[256];
+    const float* z = Z + (int64_t)blockIdx.x * ld;
+    float s = 0.f;
+    for (int64_t c = threadIdx.x; c < ncols; c += 256) s += z[c];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[blockIdx.x] = red[0];
+}
+
+// the three losses: one workgroup, fp64 partial sums in a fixed order
+extern "C" __global__ void __launch_bounds__(256) pndf_train_loss_kernel(const float* d, const float* dgt, const float* eikp, int64_t B,
+                                                                         int64_t Bm, int loss_type, int eik, float* losses) {
+    __shared__ double red[3][256];
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int64_t c = threadIdx.x; c < B; c += 256) {
+        const double r = (double)d[c] - (double)dgt[c];
+        s0 += loss_type == LOSS_L2 ? r * r : fabs(r);
+        if (eik) s2 += (double)eikp[c];
+    }
+    for (int64_t c = threadIdx.x; c < Bm; c += 256) s1 += fabs((double)d[B + c]);
+    red[0][threadIdx.x] = s0;
+    red[1][threadIdx.x] = s1;
+    red[2][threadIdx.x] = s2;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h)
+            for (int k = 0; k < 3; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        losses[0] = (float)(red[0][0] / (double)B);
+        losses[1] = (float)(red[1][0] / (double)Bm);
+        losses[2] = eik ? (float)(red[2][0] / (21.0 * (double)B)) : 0.f;
+    }
+}
+
+// seeds of the reverse pass on the output layer (width 1): zbar on the primal columns, zdotbar on the tangent columns
+extern "C" __global__ void __launch_bounds__(256) pndf_train_head_kernel(const float* d, const float* dgt, const float* D1, const float* D2,
+                                                                         const float* up, int64_t B, int64_t Bm, int loss_type, int eik,
+                                                                         float* zbar) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t np = B + Bm, n = eik ? np + B : B;
+    if (c >= n) return;
+    const float g_dist = up[0], g_man = up[1], g_eik = up[2];
+    float z;
+    if (c < B) {
+        const float r = d[c] - dgt[c];
+        const float dl = loss_type == LOSS_L2 ? 2.f * r / (float)B : (float)((r > 0.f) - (r < 0.f)) / (float)B;
+        z = g_dist * dl * D1[c];
+        if (D2) z += g_eik * D2[c];
+    } else if (c < np) {
+        const float m = d[c];
+        z = g_man * ((float)((m > 0.f) - (m < 0.f)) / (float)Bm) * D1[c];
+    } else {
+        z = g_eik * D1[c - np];
+    }
+    zbar[c] = z;
+}
+
+// ------------------------------------------------------------------------------------------------------------ host side
+namespace {
+
+struct Shape {
+    int64_t B = 0, Bm = 0;
+    int loss_type = 0, eik = 0;
+};
+
+// workspace layout in floats (every region 256-byte aligned)
+struct Layout {
+    int64_t np, ncols, nrev;
+    int64_t wenc, X, dgt, act[MAX_LIN + 1], D1[MAX_LIN], D2[MAX_LIN], Xd, eikp, Z[2], slab, part;
+    int split[MAX_LIN], kc[MAX_LIN];
+    int enc_wgs;
+    int64_t total;
+};
+
+}  // namespace
+
+struct pndf_train_plan {
+    int device = 0;
+    int L = 0;                    // linear layers of the trunk
+    int dims[MAX_LIN + 1] = {};   // dims[0] = 126 ... dims[L] = 1
+    int act = 0, enc_act = 0;
+    float beta = 100.f, enc_beta = 100.f;
+    int parent[NJ] = {};
+    int enc_off[NJ] = {};         // offset of bone j in the packed encoder
+    int enc_tensor_off[ENC_TENSORS + 1] = {};
+    int enc_params = 0;
+    int maxw = 0;
+    std::mutex mu;
+    std::unordered_map<const void*, Shape> shapes;      // workspace -> the shape of the forward that filled it
+    std::string err;
+};
+
+namespace {
+
+thread_local std::string g_train_create_err;
+int train_fail(pndf_train_plan* h, int code, const std::string& msg) {
+    if (h) h->err = msg; else g_train_create_err = msg;
+    return code;
+}
+
+int64_t align64(int64_t x) { return (x + 63) / 64 * 64; }
+
+Layout make_layout(const pndf_train_plan* h, int64_t B, int64_t Bm, int eik) {
+    Layout l{};
+    l.np = B + Bm;
+    l.ncols = eik ? l.np + B : l.np;
+    l.nrev = eik ? l.ncols : B;
+    int64_t o = 0;
+    auto take = [&](int64_t n) { const int64_t at = o; o += align64(n); return at; };
+    l.wenc = take(h->enc_params);
+    l.X = take(POSE * l.np);
+    l.dgt = take(B);
+    for (int t = 0; t <= h->L; ++t) l.act[t] = take((int64_t)h->dims[t] * l.ncols);
+    for (int t = 0; t < h->L; ++t) l.D1[t] = take((int64_t)h->dims[t + 1] * l.np);
+    for (int t = 0; t < h->L; ++t) l.D2[t] = (eik && h->act == PNDF_ACT_SOFTPLUS) ? take((int64_t)h->dims[t + 1] * B) : -1;
+    l.Xd = eik ? take(POSE * B) : -1;
+    l.eikp = eik ? take(B) : -1;
+    // the two ping-pong adjoint buffers of the reverse pass; the forward's input-gradient pass uses the same memory
+    l.Z[0] = take((int64_t)h->maxw * l.ncols);
+    l.Z[1] = take((int64_t)h->maxw * l.ncols);
+    int64_t slab = 0;
+    for (int t = 0; t < h->L; ++t) {
+        // K split of the weight-gradient GEMM: a function of the shapes only, never of the device's occupancy
+        const int64_t M = h->dims[t + 1], N = h->dims[t];
+        const int64_t tiles = ((M + TM - 1) / TM) * ((N + TN - 1) / TN);
+        int64_t S = (SPLIT_TARGET_WGS + tiles - 1) / tiles;
+        const int64_t smax = (l.nrev + 255) / 256;
+        if (S > smax) S = smax;
+        if (S < 1) S = 1;
+        int64_t kc = (l.nrev + S - 1) / S;
+        kc = (kc + TK - 1) / TK * TK;
+        S = (l.nrev + kc - 1) / kc;
+        l.split[t] = (int)S;
+        l.kc[t] = (int)kc;
+        if (S * M * N > slab) slab = S * M * N;
+    }
+    l.slab = take(slab);
+    const int64_t P = eik ? l.np : B;
+    l.enc_wgs = (int)((P + ENC_WG - 1) / ENC_WG);
+    l.part = take((int64_t)l.enc_wgs * h->enc_params);
+    l.total = o;
+    return l;
+}
+
+GemmArgs gemm_args(const float* A, int64_t lda, const float* Bp, int64_t ldb, float* C, int64_t ldc, int M, int N, int K) {
+    GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.A = A; g.lda = lda; g.B = Bp; g.ldb = ldb; g.C = C; g.ldc = ldc;
+    g.M = M; g.N = N; g.K = K; g.kc = K;
+    g.np_split = INT64_MAX;
+    return g;
+}
+
+enum { GEMM_NN, GEMM_TN, GEMM_NT };
+void launch_gemm(int kind, const GemmArgs& g, int splits, hipStream_t st) {
+    if (g.M <= 0 || g.N <= 0) return;
+    const dim3 grid((g.N + TN - 1) / TN, (g.M + TM - 1) / TM, splits);
+    if (kind == GEMM_NN) hipLaunchKernelGGL(pndf_train_gemm_nn_kernel, grid, dim3(256), 0, st, g);
+    else if (kind == GEMM_TN) hipLaunchKernelGGL(pndf_train_gemm_tn_kernel, grid, dim3(256), 0, st, g);
+    else hipLaunchKernelGGL(pndf_train_gemm_nt_kernel, grid, dim3(256), 0, st, g);
+}
+
+EncArgs enc_args(const pndf_train_plan* h, const Layout& l, float* ws, int64_t B, int64_t Bm, int eik) {
+    EncArgs e;
+    memset(&e, 0, sizeof(e));
+    e.wenc = ws + l.wenc;
+    e.X = ws + l.X;
+    e.dgt_copy = ws + l.dgt;
+    e.act0 = ws + l.act[0];
+    e.U0 = ws + l.Z[0];
+    e.Xd = eik ? ws + l.Xd : nullptr;
+    e.eikp = eik ? ws + l.eikp : nullptr;
+    e.part = ws + l.part;
+    e.B = B; e.Bm = Bm; e.np = l.np; e.ncols = l.ncols;
+    e.act = h->enc_act; e.beta = h->enc_beta; e.eik = eik; e.n_params = h->enc_params;
+    for (int j = 0; j < NJ; ++j) { e.parent[j] = h->parent[j]; e.off[j] = h->enc_off[j]; }
+    return e;
+}
+
+PtrTable ptr_table(const pndf_train_plan* h, const float* const* tensors) {
+    PtrTable t;
+    for (int k = 0; k < ENC_TENSORS; ++k) t.p[k] = const_cast<float*>(tensors[k]);
+    for (int k = 0; k <= ENC_TENSORS; ++k) t.off[k] = h->enc_tensor_off[k];
+    return t;
+}
+
+unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+int check_launch(pndf_train_plan* h, const char* what) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return train_fail(h, PNDF_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    return PNDF_OK;
+}
+
+}  // namespace
+
+extern "C" const char* pndf_train_last_error(pndf_train_handle h) { return h ? h->err.c_str() : g_train_create_err.c_str(); }
+
+extern "C" int pndf_train_create(pndf_train_handle* out, const pndf_config* cfg, int device) {
+    if (!out || !cfg) return train_fail(nullptr, PNDF_ERR_BAD_ARG, "out / cfg is null");
+    *out = nullptr;
+    if (cfg->act < PNDF_ACT_RELU || cfg->act > PNDF_ACT_SOFTPLUS)
+        return train_fail(nullptr, PNDF_ERR_UNSUPPORTED, "activation: relu, lrelu or softplus");
+    if (cfg->enc_act > PNDF_ACT_SOFTPLUS) return train_fail(nullptr, PNDF_ERR_UNSUPPORTED, "encoder activation: relu, lrelu or softplus");
+    if (cfg->num_joints != NJ) return train_fail(nullptr, PNDF_ERR_UNSUPPORTED, "num_joints must be 21");
+    if (cfg->dims[0] != ENC_IN)
+        return train_fail(nullptr, PNDF_ERR_UNSUPPORTED,
+                          "training needs the structure encoder (model.StrEnc.use: True, dims[0] = 126): the reference's train=True "
+                          "branch cannot run without it either (man_pose_in is unbound)");
+    if (cfg->n_dims < 3 || cfg->n_dims > MAX_LIN + 1 || cfg->dims[cfg->n_dims - 1] != 1)
+        return train_fail(nullptr, PNDF_ERR_UNSUPPORTED, "DFNet: 1 .. 7 hidden layers and one output");
+    for (int i = 1; i < cfg->n_dims - 1; ++i)
+        if (cfg->dims[i] < 1 || cfg->dims[i] > 1024) return train_fail(nullptr, PNDF_ERR_UNSUPPORTED, "hidden widths 1 .. 1024");
+    for (int j = 0; j < NJ; ++j)
+        if (cfg->parent[j] >= j || cfg->parent[j] < -1)
+            return train_fail(nullptr, PNDF_ERR_UNSUPPORTED, "parent table: every parent before its child");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+        (void)hipGetLastError();
+        return train_fail(nullptr, PNDF_ERR_NO_DEVICE, "no HIP device " + std::to_string(device) + " (training has no CPU fallback)");
+    }
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
+        return train_fail(nullptr, PNDF_ERR_NO_DEVICE, "kernels are built for gfx950 only");
+    pndf_train_plan* h = new pndf_train_plan();
+    h->device = device;
+    h->L = cfg->n_dims - 1;
+    for (int t = 0; t <= h->L; ++t) {
+        h->dims[t] = cfg->dims[t];
+        if (cfg->dims[t] > h->maxw) h->maxw = cfg->dims[t];
+    }
+    h->act = cfg->act;
+    h->beta = cfg->beta;
+    h->enc_act = cfg->enc_act >= 0 ? cfg->enc_act : cfg->act;
+    h->enc_beta = cfg->enc_beta > 0.f ? cfg->enc_beta : cfg->beta;
+    int o = 0, k = 0;
+    for (int j = 0; j < NJ; ++j) {
+        h->parent[j] = cfg->parent[j];
+        h->enc_off[j] = o;
+        const int fin = cfg->parent[j] < 0 ? BONE : BONE + FEAT;
+        const int sizes[4] = {HID * fin, HID, FEAT * HID, FEAT};
+        for (int s = 0; s < 4; ++s) {
+            h->enc_tensor_off[k++] = o;
+            o += sizes[s];
+        }
+    }
+    h->enc_tensor_off[ENC_TENSORS] = o;
+    h->enc_params = o;
+    *out = h;
+    return PNDF_OK;
+}
+
+extern "C" int pndf_train_destroy(pndf_train_handle h) {
+    delete h;
+    return PNDF_OK;
+}
+
+extern "C" int64_t pndf_train_workspace_floats(pndf_train_handle h, int64_t B, int64_t Bm, int32_t eikonal) {
+    if (!h || B < 1 || Bm < 1) return PNDF_ERR_BAD_ARG;
+    return make_layout(h, B, Bm, eikonal ? 1 : 0).total;
+}
+
+extern "C" int pndf_train_forward(pndf_train_handle h, const float* const* weights, const float* q, const float* dist_gt,
+                                  const float* q_man, int64_t B, int64_t Bm, int32_t loss_type, int32_t eikonal, float* losses,
+                                  void* workspace, void* stream) {
+    if (!h) return PNDF_ERR_BAD_ARG;
+    if (!weights || !q || !dist_gt || !q_man || !losses || !workspace) return train_fail(h, PNDF_ERR_BAD_ARG, "null pointer");
+    if (B < 1 || Bm < 1) return train_fail(h, PNDF_ERR_BAD_ARG, "B and Bm must be >= 1");
+    if (loss_type != LOSS_L1 && loss_type != LOSS_L2) return train_fail(h, PNDF_ERR_BAD_ARG, "loss_type: 0 (l1) or 1 (l2)");
+    if (((uintptr_t)workspace & 15) != 0) return train_fail(h, PNDF_ERR_BAD_ARG, "workspace must be 16-byte aligned");
+    for (int i = 0; i < ENC_TENSORS + 2 * h->L; ++i)
+        if (!weights[i]) return train_fail(h, PNDF_ERR_BAD_ARG, "null weight tensor " + std::to_string(i));
+    PndfRange range("pndf_train_forward");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return train_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
+    const int eik = eikonal ? 1 : 0;
+    const Layout l = make_layout(h, B, Bm, eik);
+    {
+        std::lock_guard<std::mutex> lk(h->mu);
+        Shape s;
+        s.B = B; s.Bm = Bm; s.loss_type = loss_type; s.eik = eik;
+        h->shapes[workspace] = s;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    float* ws = (float*)workspace;
+    const float* const* W = weights + ENC_TENSORS;          // trunk layer t: W[2t] weight [dims[t+1]][dims[t]], W[2t+1] bias
+    const bool sp = h->act == PNDF_ACT_SOFTPLUS;
+
+    hipLaunchKernelGGL(pndf_train_enc_pack_kernel, dim3(blocks(h->enc_params)), dim3(256), 0, st, ptr_table(h, weights), ws + l.wenc);
+    EncArgs e = enc_args(h, l, ws, B, Bm, eik);
+    e.q = q; e.qm = q_man; e.dgt = dist_gt;
+    hipLaunchKernelGGL(pndf_train_enc_fwd_kernel, dim3(blocks(l.np)), dim3(256), 0, st, e);
+    // 1. forward over the primal columns
+    for (int t = 0; t < h->L; ++t) {
+        GemmArgs g = gemm_args(W[2 * t], h->dims[t], ws + l.act[t], l.ncols, ws + l.act[t + 1], l.ncols, h->dims[t + 1], (int)l.np,
+                               h->dims[t]);
+        g.epi = EPI_FWD; g.act = h->act; g.beta = h->beta; g.out_layer = t == h->L - 1; g.bias = W[2 * t + 1];
+        g.D1 = ws + l.D1[t]; g.ld1 = l.np;
+        if (l.D2[t] >= 0) { g.D2 = ws + l.D2[t]; g.ld2 = B; g.nB = B; }
+        launch_gemm(GEMM_NN, g, 1, st);
+    }
+    if (eik) {
+        // 2. input gradient of the noisy batch: u_t = (W_t^T u_{t+1}) sigma'_{t-1}, from sigma' of the output; ends in Z[0] = U0
+        const float* U = ws + l.D1[h->L - 1];
+        int64_t ldu = l.np;
+        for (int t = h->L - 1; t >= 0; --t) {
+            float* out = ws + l.Z[t & 1];
+            GemmArgs g = gemm_args(W[2 * t], h->dims[t], U, ldu, out, B, h->dims[t], (int)B, h->dims[t + 1]);
+            g.epi = EPI_MUL;
+            if (t > 0) { g.D1 = ws + l.D1[t - 1]; g.ld1 = l.np; }
+            launch_gemm(GEMM_TN, g, 1, st);
+            U = out;
+            ldu = B;
+        }
+        // 3. encoder backward, the eikonal seed, xdot and the tangent encoder
+        hipLaunchKernelGGL(pndf_train_enc_eik_kernel, dim3(blocks(B)), dim3(256), 0, st, e);
+        // 4. tangent forward
+        for (int t = 0; t < h->L; ++t) {
+            GemmArgs g = gemm_args(W[2 * t], h->dims[t], ws + l.act[t] + l.np, l.ncols, ws + l.act[t + 1] + l.np, l.ncols,
+                                   h->dims[t + 1], (int)B, h->dims[t]);
+            g.epi = EPI_TAN; g.D1 = ws + l.D1[t]; g.ld1 = l.np;
+            if (sp) { g.D2 = ws + l.D2[t]; g.ld2 = B; }
+            launch_gemm(GEMM_NN, g, 1, st);
+        }
+    }
+    hipLaunchKernelGGL(pndf_train_loss_kernel, dim3(1), dim3(256), 0, st, ws + l.act[h->L], ws + l.dgt, eik ? ws + l.eikp : nullptr,
+                       B, Bm, (int)loss_type, eik, losses);
+    return check_launch(h, "pndf_train_forward");
+}
+
+extern "C" int pndf_train_backward(pndf_train_handle h, const float* const* weights, const float* upstream, float* const* grads,
+                                   void* workspace, void* stream) {
+    if (!h) return PNDF_ERR_BAD_ARG;
+    if (!weights || !upstream || !grads || !workspace) return train_fail(h, PNDF_ERR_BAD_ARG, "null pointer");
+    Shape s;
+    {
+        std::lock_guard<std::mutex> lk(h->mu);
+        auto it = h->shapes.find(workspace);
+        if (it == h->shapes.end()) return train_fail(h, PNDF_ERR_BAD_ARG, "workspace was not filled by pndf_train_forward of this handle");
+        s = it->second;
+    }
+    for (int i = 0; i < ENC_TENSORS + 2 * h->L; ++i)
+        if (!weights[i] || !grads[i]) return train_fail(h, PNDF_ERR_BAD_ARG, "null weight / gradient tensor " + std::to_string(i));
+    PndfRange range("pndf_train_backward");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return train_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
+    const int64_t B = s.B, Bm = s.Bm;
+    const int eik = s.eik;
+    const Layout l = make_layout(h, B, Bm, eik);
+    hipStream_t st = (hipStream_t)stream;
+    float* ws = (float*)workspace;
+    const float* const* W = weights + ENC_TENSORS;
+    float* const* G = grads + ENC_TENSORS;
+    const bool cross = eik && h->act == PNDF_ACT_SOFTPLUS;
+    const int64_t npr = eik ? l.np : B;          // primal columns of the reverse pass
+
+    hipLaunchKernelGGL(pndf_train_enc_pack_kernel, dim3(blocks(h->enc_params)), dim3(256), 0, st, ptr_table(h, weights), ws + l.wenc);
+    const int L = h->L;
+    int zi = 0;
+    hipLaunchKernelGGL(pndf_train_head_kernel, dim3(blocks(l.nrev)), dim3(256), 0, st, ws + l.act[L], ws + l.dgt, ws + l.D1[L - 1],
+                       cross ? ws + l.D2[L - 1] : nullptr, upstream, B, Bm, s.loss_type, eik, ws + l.Z[zi]);
+    for (int t = L - 1; t >= 0; --t) {
+        const float* Zb = ws + l.Z[zi];
+        const int M = h->dims[t + 1], N = h->dims[t];
+        // weight gradient: [zbar|zdotbar] [a|adot]^T over every column of the reverse pass, K split, the slabs summed in order
+        GemmArgs g = gemm_args(Zb, l.ncols, ws + l.act[t], l.ncols, ws + l.slab, N, M, N, (int)l.nrev);
+        g.epi = EPI_STORE; g.kc = l.kc[t]; g.slab = (int64_t)M * N;
+        launch_gemm(GEMM_NT, g, l.split[t], st);
+        hipLaunchKernelGGL(pndf_train_slab_reduce_kernel, dim3(blocks((int64_t)M * N)), dim3(256), 0, st, ws + l.slab, l.split[t],
+                           (int64_t)M * N, G[2 * t]);
+        hipLaunchKernelGGL(pndf_train_row_sum_kernel, dim3(M), dim3(256), 0, st, Zb, l.ncols, npr, G[2 * t + 1]);
+        // adjoint of the layer's input
+        float* out = ws + l.Z[zi ^ 1];
+        if (t > 0 && cross) {
+            // softplus: the tangent columns first (adotbar sigma'' zdot replaces sigma'' zdot), then the primal ones add it
+            GemmArgs gt = gemm_args(W[2 * t], N, Zb + l.np, l.ncols, out + l.np, l.ncols, N, (int)B, M);
+            gt.epi = EPI_TAN; gt.D1 = ws + l.D1[t - 1]; gt.ld1 = l.np; gt.D2 = ws + l.D2[t - 1]; gt.ld2 = B;
+            launch_gemm(GEMM_TN, gt, 1, st);
+            GemmArgs gp = gemm_args(W[2 * t], N, Zb, l.ncols, out, l.ncols, N, (int)l.np, M);
+            gp.epi = EPI_MUL; gp.D1 = ws + l.D1[t - 1]; gp.ld1 = l.np; gp.X = ws + l.D2[t - 1]; gp.ldx = B; gp.nB = B;
+            launch_gemm(GEMM_TN, gp, 1, st);
+        } else {
+            GemmArgs gr = gemm_args(W[2 * t], N, Zb, l.ncols, out, l.ncols, N, (int)l.nrev, M);
+            gr.epi = EPI_MUL;
+            if (t > 0) { gr.D1 = ws + l.D1[t - 1]; gr.ld1 = l.np; gr.np_split = l.np; }
+            launch_gemm(GEMM_TN, gr, 1, st);
+        }
+        zi ^= 1;
+    }
+    // the encoder: dual reverse per pose, partials per workgroup, then the ordered sum into the caller's tensors
+    EncArgs e = enc_args(h, l, ws, B, Bm, eik);
+    e.abar = ws + l.Z[zi];
+    hipLaunchKernelGGL(pndf_train_enc_rev_kernel, dim3(l.enc_wgs), dim3(ENC_WG), 0, st, e);
+    PtrTable gtab;
+    for (int k = 0; k < ENC_TENSORS; ++k) gtab.p[k] = grads[k];
+    for (int k = 0; k <= ENC_TENSORS; ++k) gtab.off[k] = h->enc_tensor_off[k];
+    hipLaunchKernelGGL(pndf_train_enc_reduce_kernel, dim3(blocks(h->enc_params)), dim3(256), 0, st, gtab, ws + l.part, l.enc_wgs);
+    return check_launch(h, "pndf_train_backward");
+}

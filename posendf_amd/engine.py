@@ -151,6 +151,20 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     lib.pndf_quat_topk.argtypes = [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_void_p,
                                    c_void_p, c_void_p]
     lib.pndf_quat_topk.restype = c_int
+    TH = c_void_p
+    lib.pndf_train_create.argtypes = [POINTER(TH), POINTER(PndfConfig), c_int]
+    lib.pndf_train_create.restype = c_int
+    lib.pndf_train_destroy.argtypes = [TH]
+    lib.pndf_train_destroy.restype = c_int
+    lib.pndf_train_workspace_floats.argtypes = [TH, c_int64, c_int64, c_int32]
+    lib.pndf_train_workspace_floats.restype = c_int64
+    lib.pndf_train_forward.argtypes = [TH, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p,
+                                       c_void_p, c_void_p]
+    lib.pndf_train_forward.restype = c_int
+    lib.pndf_train_backward.argtypes = [TH, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.pndf_train_backward.restype = c_int
+    lib.pndf_train_last_error.argtypes = [TH]
+    lib.pndf_train_last_error.restype = c_char_p
     CH = c_void_p
     lib.pndf_cpu_create.argtypes = [POINTER(CH), POINTER(PndfConfig)]
     lib.pndf_cpu_destroy.argtypes = [CH]
@@ -180,7 +194,7 @@ DEBUG_EXPORTS = ("pndf_debug_bind", "pndf_debug_experiment_word", "pndf_debug_fo
                  "pndf_debug_timing_regions", "pndf_debug_timing_layout", "pndf_debug_mem_probe", "pndf_debug_ring_stream")
 # per-translation-unit experiment words (csrc/pndf_experiment.h): data symbols, all zero in a product build
 EXPERIMENT_WORDS = ("pndf_experiment_word_capi", "pndf_experiment_word_fp32", "pndf_experiment_word_split", "pndf_experiment_word_split_x2",
-                    "pndf_experiment_word_lbs", "pndf_experiment_word_generic")
+                    "pndf_experiment_word_lbs", "pndf_experiment_word_generic", "pndf_experiment_word_train")
 DEBUG_EXPERIMENT_WORDS = ("pndf_experiment_word_debug", "pndf_experiment_word_fp32_timing", "pndf_experiment_word_split_timing",
                           "pndf_experiment_word_fp32_dbg", "pndf_experiment_word_probe")
 
@@ -205,6 +219,8 @@ EXPORTS = ("pndf_default_config", "pndf_create", "pndf_destroy", "pndf_load_weig
            "pndf_lbs_create", "pndf_lbs_destroy", "pndf_lbs_set_precision", "pndf_lbs_precision", "pndf_lbs_num_joints", "pndf_lbs_num_vertices", "pndf_lbs_workspace_floats",
            "pndf_lbs_forward", "pndf_lbs_terms_grad", "pndf_lbs_backward", "pndf_lbs_packed_floats", "pndf_lbs_pack_host", "pndf_lbs_packed_split_bytes", "pndf_lbs_pack_split_host",
            "pndf_lbs_last_error", "pndf_last_error", "pndf_version", "pndf_kernel_name",
+           "pndf_train_create", "pndf_train_destroy", "pndf_train_workspace_floats", "pndf_train_forward", "pndf_train_backward",
+           "pndf_train_last_error",
            "pndf_cpu_create", "pndf_cpu_destroy", "pndf_cpu_load_weights", "pndf_forward_cpu", "pndf_forward_grad_cpu", "pndf_project_cpu",
            "pndf_cpu_last_error")
 
@@ -365,6 +381,77 @@ class Engine:
     def close(self):
         if getattr(self, "handle", None):
             self.lib.pndf_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TrainEngine:
+    """`pndf_train_*` (csrc/pndf_train.hip): the training objective of model/posendf.py:62-99 and its weight gradients on one
+    device.  Exact fp32 MFMA; the structure encoder is required (the reference cannot train without it).  All compute methods
+    take raw device pointers (the weights and gradients as lists of them, state-dict order) and a stream handle."""
+
+    def __init__(self, act: str = "lrelu", beta: float = 100.0, device: int = 0, lib=None, encoder: bool = True, hidden=None,
+                 enc_act: str | None = None, enc_beta: float | None = None):
+        self.lib = lib or load_library()
+        if act not in ACT_CODES:
+            raise PndfError(f"unknown activation {act!r}")
+        cfg = PndfConfig()
+        self.lib.pndf_default_config(ctypes.byref(cfg), ACT_CODES[act], float(beta))
+        _set_encoder_act(cfg, act, beta, enc_act, enc_beta)
+        if not encoder:
+            cfg.dims[0] = 84
+        if hidden is not None:
+            hidden = [int(w) for w in hidden]
+            if not 1 <= len(hidden) <= 7:
+                raise PndfError(f"DFNet with {len(hidden)} hidden layers: 1 .. 7 are implemented")
+            cfg.n_dims = len(hidden) + 2
+            for i in range(1, len(cfg.dims)):
+                cfg.dims[i] = 0
+            for i, w in enumerate(hidden):
+                cfg.dims[i + 1] = w
+            cfg.dims[len(hidden) + 1] = 1
+        self.n_tensors = len(state_dict_order(encoder, cfg.n_dims - 1))
+        self.handle = c_void_p()
+        rc = self.lib.pndf_train_create(ctypes.byref(self.handle), ctypes.byref(cfg), int(device))
+        if rc != 0:
+            msg = self.lib.pndf_train_last_error(None).decode()
+            self.handle = None
+            raise PndfError(f"pndf_train_create failed ({rc}): {msg}")
+        self.device = device
+        self.act = act
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise PndfError(f"{what} failed ({rc}): {self.lib.pndf_train_last_error(self.handle).decode()}")
+
+    def _table(self, ptrs):
+        if len(ptrs) != self.n_tensors:
+            raise PndfError(f"{len(ptrs)} tensors given, the network has {self.n_tensors}")
+        return (c_void_p * len(ptrs))(*ptrs)
+
+    def workspace_floats(self, B, Bm, eikonal) -> int:
+        n = int(self.lib.pndf_train_workspace_floats(self.handle, int(B), int(Bm), int(bool(eikonal))))
+        if n < 0:
+            raise PndfError(f"pndf_train_workspace_floats failed ({n})")
+        return n
+
+    def forward(self, weight_ptrs, q_ptr, gt_ptr, qm_ptr, B, Bm, loss_type, eikonal, losses_ptr, ws_ptr, stream=0):
+        self._check(self.lib.pndf_train_forward(self.handle, self._table(weight_ptrs), q_ptr, gt_ptr, qm_ptr, int(B), int(Bm),
+                                                int(loss_type), int(bool(eikonal)), losses_ptr, ws_ptr, stream),
+                    "pndf_train_forward")
+
+    def backward(self, weight_ptrs, upstream_ptr, grad_ptrs, ws_ptr, stream=0):
+        self._check(self.lib.pndf_train_backward(self.handle, self._table(weight_ptrs), upstream_ptr, self._table(grad_ptrs), ws_ptr,
+                                                 stream), "pndf_train_backward")
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.pndf_train_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

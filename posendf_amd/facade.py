@@ -10,6 +10,9 @@ There is no fallback on the inference path: a pose on a `cuda` device runs on th
 library, no gfx950 device).  A model whose config says `train.device: cpu` -- the reference's class works there too,
 posendf.py:35,64 -- runs train=False on the library's host twins (`pndf_*_cpu`, plain C++ on the host cores),
 selected by the pose's device alone, never by a failure of the device path.
+
+`forward(train=True)` runs on the stock PyTorch modules unless `opt['engine']['train'] = 'hip'`: then a cuda model's training
+objective and every weight gradient come from csrc/pndf_train.hip (posendf_amd.train.TrainObjective), again with no fallback.
 """
 from __future__ import annotations
 
@@ -21,7 +24,7 @@ import torch
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
-from .engine import CpuEngine, Engine, PndfError, state_dict_order
+from .engine import CpuEngine, Engine, PndfError, TrainEngine, state_dict_order
 from .modules import DFNet, StructureEncoder
 
 
@@ -93,6 +96,16 @@ class PoseNDF(nn.Module):
         self._enc_act = opt["model"]["StrEnc"]["act"] if self.enc is not None else None
         self._enc_beta = float(opt["model"]["StrEnc"].get("beta", self._beta)) if self.enc is not None else None
         self._hidden = list(opt["model"]["DFNet"]["dims"])       # net_modules.py:14-28; narrower than amass.yaml: zero padded
+        # engine knob (no reference counterpart): where forward(train=True) runs for a cuda model -- "torch" (default: the stock
+        # modules below) or "hip" (the objective and every weight gradient on csrc/pndf_train.hip, posendf_amd.train; no fallback:
+        # PndfError without the library or a gfx950 device).  A model whose train.device is cpu keeps the stock path either way.
+        self._train_backend = (opt.get("engine") or {}).get("train", "torch")
+        if self._train_backend not in ("torch", "hip"):
+            raise ValueError(f"opt['engine']['train'] must be 'torch' or 'hip', not {self._train_backend!r}")
+        if self._train_backend == "hip" and self.enc is None:
+            raise PndfError("opt['engine']['train'] = 'hip' needs the structure encoder (model.StrEnc.use: True): the reference's "
+                            "train=True branch cannot run without it either")
+        self._train_engines = {}    # device index -> TrainEngine
         self._engines = {}          # device index -> (Engine, weight fingerprint)
         self._param_list = None     # cached list(self.parameters()): walking the module tree costs 0.15 ms per call
 
@@ -171,6 +184,8 @@ class PoseNDF(nn.Module):
         pose = pose.to(device=self.device).reshape(-1, 21, 4)      # posendf.py:64
         if not train:
             return {"dist_pred": _Distance.apply(pose, self)}      # posendf.py:100-101
+        if self._train_backend == "hip" and pose.device.type == "cuda":
+            return self._forward_train_hip(pose, dist_gt, man_poses, eikonal)
         # ------ training objective: stock PyTorch modules (posendf.py:65-99)
         pose.requires_grad = True
         dist_gt = dist_gt.to(device=self.device).reshape(-1)
@@ -186,6 +201,24 @@ class PoseNDF(nn.Module):
         if eikonal > 0.0:
             eik = ((grad_val.norm(2, dim=-1) - 1) ** 2).mean()
             return loss, {"dist": loss, "man_loss": loss_man, "eikonal": eik}
+        return loss, {"dist": loss}
+
+    def _forward_train_hip(self, pose, dist_gt, man_poses, eikonal):
+        """posendf.py:65-99 on the HIP engine: the same (loss, loss_dict), `loss` and loss_dict['dist'] the same tensor."""
+        from .train import LOSS_CODES, TrainObjective
+        idx = pose.device.index if pose.device.index is not None else torch.cuda.current_device()
+        eng = self._train_engines.get(idx)
+        if eng is None:
+            eng = self._train_engines[idx] = TrainEngine(self._act, self._beta, idx, hidden=self._hidden, enc_act=self._enc_act,
+                                                         enc_beta=self._enc_beta)
+        named = dict(self.named_parameters())
+        params = [named[k] for k in state_dict_order(True, len(self._hidden) + 1)]
+        man = man_poses.to(device=self.device).reshape(-1, 21, 4)
+        eik = eikonal > 0.0
+        loss, loss_man, loss_eik = TrainObjective.apply(eng, pose, dist_gt.to(device=self.device).reshape(-1), man,
+                                                        LOSS_CODES[self.loss], eik, *params)
+        if eik:
+            return loss, {"dist": loss, "man_loss": loss_man, "eikonal": loss_eik}
         return loss, {"dist": loss}
 
     # ---- added surface (north_star: `.project` on the model) -------------------------------------

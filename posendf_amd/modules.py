@@ -3,8 +3,8 @@
 These exist for three reasons only: (1) reference checkpoints load unchanged -- the attribute tree
 `enc.net[i].net[0|2]`, `dfnet.lin{l}` reproduces the 98 state-dict keys of the reference
 (model/network/net_modules.py:14-28,78-107,116-128); (2) optimisers can see `parameters()`; (3) the
-train=True path (weight gradients + eikonal double backward, model/posendf.py:77-99) stays on stock
-PyTorch-ROCm, which SURVEY.md section 8 marks out of scope for the HIP kernels.
+train=True path (weight gradients + eikonal double backward, model/posendf.py:77-99) runs on them by
+default (opt['engine']['train'] = 'hip' reads their tensors in place on csrc/pndf_train.hip instead).
 The inference path (train=False) never calls these modules' forward: it goes to the HIP engine.
 """
 from __future__ import annotations
