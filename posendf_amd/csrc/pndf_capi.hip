@@ -112,7 +112,8 @@ static int check_config(pndf_engine* h, const pndf_config* cfg) {
     // depth whose hidden layers are NARROWER runs on them zero-padded (padded units have zero outgoing weights, so they
     // reach neither the distance nor its gradient, whatever the activation); any other `dims` list the reference can build
     // (net_modules.py:14-28) -- 2 .. 8 linear layers, hidden widths up to 1024 -- runs on the runtime-planned kernels of
-    // pndf_generic.hip (exact fp32 whatever precision was asked for).  Only beyond that is a configuration refused.
+    // pndf_generic.hip (the exact fp32 form for precision fp32; the split-precision form, fp16 MFMAs with fp32 accumulation, for
+    // any other precision, unless a layer's weights cannot be scaled into fp16's range).  Only beyond that is a configuration refused.
     if (cfg->n_dims < 3 || cfg->n_dims > MAXLIN + 1)
         return fail(h, PNDF_ERR_UNSUPPORTED, "DFNet depth: n_dims must be 3 .. 9 (1 .. 7 hidden layers + the output layer)");
     if ((cfg->dims[0] != DIMS[0] && cfg->dims[0] != NOENC_IN) || cfg->dims[cfg->n_dims - 1] != 1)

@@ -3,11 +3,12 @@
 
 reference model/network/net_modules.py:14-28 builds DFNet from a free list of hidden widths (`dims`); the engine runs every
 such network on its runtime-planned kernels (posendf_amd/csrc/pndf_generic.hip).  Dev-container only, like make_golden.py:
-imports /root/reference/model/posendf.py with the two arithmetic-free stubs, overrides `model.DFNet.dims` (and `StrEnc.use`) in
-the loaded configs/amass.yaml, loads the deterministic weights of posendf_amd.synth and records inputs and outputs.  The
-projection loop of experiments/sample_poses.py:67-74 is restated around the imported objects as in make_golden.py.
+imports /root/reference/model/posendf.py with the two arithmetic-free stubs, overrides `model.DFNet.dims` (and `StrEnc.use`, and the
+activations and Softplus betas of both sides) in the loaded configs/amass.yaml, loads the deterministic weights of posendf_amd.synth
+and records inputs and outputs.  The projection loop of experiments/sample_poses.py:67-74 is restated around the imported objects as
+in make_golden.py.
 
-Usage:  python tests/golden/make_golden_depth.py        (writes tests/golden/depth_<name>.npz)
+Usage:  python tests/golden/make_golden_depth.py [name ...]        (writes tests/golden/depth_<name>.npz)
 """
 import os
 import sys
@@ -19,9 +20,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import make_golden as mg      # noqa: E402  (stubs, reference imports, project_ref)
 
+from oracle.posendf_np import parse_act  # noqa: E402
 from posendf_amd import synth  # noqa: E402
 
-# name: (hidden widths, activation, structure encoder, weights seed / gain / output bias)
+AMASS_DIMS = [256, 512, 1024, 512, 256, 64]
+# name: (hidden widths, activation, structure encoder, weights seed / gain / output bias).  The activation string is
+# oracle.posendf_np.parse_act's: "trunk[@DFNet.beta]/encoder[@StrEnc.beta]", one side for both; a side without "@" has beta 100
 CASES = {
     "d1_lrelu": ([300], "lrelu", True, (42, 2.5, 0.1)),                                       # n_dims 3: one hidden layer
     "d4_lrelu": ([192, 320, 160, 48], "lrelu", True, (22, 2.0, 0.1)),                        # four hidden layers
@@ -33,6 +37,16 @@ CASES = {
     # model.StrEnc.act differs from model.DFNet.act (net_modules.py:128 reads its own key): "trunk/encoder"
     "mix_softplus_lreluenc": ([256, 512, 1024, 512, 256, 64], "softplus/lrelu", True, (28, 2.0, 0.1)),      # amass.yaml's dims
     "mix_relu_softplusenc": ([192, 320, 160, 48], "relu/softplus", True, (43, 2.0, 0.3)),
+    # the encoder's LeakyReLU slope behind a slope-0 trunk, and the reverse pair on amass.yaml's dims (which leaves the fused kernels)
+    "mix_relu_lreluenc": ([192, 320, 160, 48], "relu/lrelu", True, (44, 2.0, 0.1)),
+    "mix_lrelu_reluenc": (AMASS_DIMS, "lrelu/relu", True, (45, 2.0, 0.3)),
+    # model.StrEnc.beta != model.DFNet.beta: only the encoder's beta differs; on amass.yaml's dims too
+    "sp_b100_encb7": ([192, 320, 160, 48], "softplus@100/softplus@7", True, (46, 1.5, 0.2)),
+    "sp_b100_encb7_amass": (AMASS_DIMS, "softplus@100/softplus@7", True, (47, 2.0, 0.1)),
+    # the encoder's Softplus threshold (beta z > 20) reached at z > 0.02
+    "mix_relu_spenc_b1000": ([192, 320, 160, 48], "relu/softplus@1000", True, (49, 1.5, 0.2)),
+    # beta 10 on both sides: the runtime-planned kernels away from beta 100
+    "d4_softplus_b10": ([192, 320, 160, 48], "softplus@10", True, (49, 2.0, 0.1)),
 }
 NPOSE = 24
 
@@ -51,10 +65,12 @@ def ref_model(name, dtype):
     hidden, act, use_enc, (seed, gain, ob) = CASES[name]
     opt = mg.load_config(os.path.join(mg.REF, "configs", "amass.yaml"))
     opt["train"]["device"] = "cpu"
-    trunk_act, _, enc_act = act.partition("/")
+    trunk_act, beta, enc_act, enc_beta = parse_act(act)
     opt["model"]["DFNet"]["act"] = trunk_act
+    opt["model"]["DFNet"]["beta"] = beta
     opt["model"]["DFNet"]["dims"] = list(hidden)
-    opt["model"]["StrEnc"]["act"] = enc_act or trunk_act
+    opt["model"]["StrEnc"]["act"] = enc_act
+    opt["model"]["StrEnc"]["beta"] = enc_beta
     opt["model"]["StrEnc"]["use"] = use_enc
     if not use_enc:
         opt["model"]["DFNet"]["in_dim"] = 84

@@ -2,11 +2,13 @@
 """Fixtures of the training objective (model/posendf.py:62-99, train=True), produced with the REAL reference (dev container only).
 
 For every case of tests/train_fixtures.py -- {lrelu, relu, softplus} x configs/amass.yaml dims x the `live` synthetic weights, the
-narrow lrelu network the reference trained (trained_lrelu.npz), one `eikonal: 0` case and one `l2` case -- the imported reference
+narrow lrelu network the reference trained (trained_lrelu.npz), one `eikonal: 0` case, one `l2` case, and three whose model.StrEnc.act /
+beta or model.DFNet.beta are not configs/amass.yaml's (train_fixtures.sides) -- the imported reference
 `PoseNDF` runs the trainer's step structure (model/train_posendf.py:93-98: forward, loss weights 1/1/1, backward) on B = 509 noisy
-poses with seeded labels and Bm = 383 manifold poses, in fp32 and in fp64.  Stored: the inputs, the losses (NaN where the
-reference returns no such key) and every weight gradient -- the encoder, all biases and the last layer in full; the large
-weights lin0 .. lin5 as Frobenius norm, row sums, column sums and 1,024 seeded entries (train_fixtures.digest).
+poses with seeded labels and Bm = 383 manifold poses, in fp32 and in fp64.  Stored: the inputs, the activations and betas the
+reference's config held, the losses (NaN where the reference returns no such key) and every weight gradient -- the encoder, all
+biases and the last layer in full; the large weights lin0 .. lin5 as Frobenius norm, row sums, column sums and 1,024 seeded entries
+(train_fixtures.digest).
 
 Nothing of the reference is copied: only inputs and outputs (data).  One thread, so that a rerun gives bit-equal arrays.
 Usage:  python tests/golden/make_golden_train.py [case ...]      (writes tests/golden/train_<case>.npz)
@@ -41,14 +43,23 @@ def _import_reference():
     return load_config, PoseNDF
 
 
-def ref_step(act, hidden, loss, eikonal, sd, dtype, q, gt, qm):
-    load_config, PoseNDF = _import_reference()
+def ref_config(act, hidden, loss):
+    load_config, _ = _import_reference()
     opt = load_config(os.path.join(REF, "configs", "amass.yaml"))
     opt["train"]["device"] = "cpu"
     opt["train"]["loss_type"] = loss
-    opt["model"]["DFNet"]["act"] = act
-    opt["model"]["StrEnc"]["act"] = act
+    trunk, beta, enc_act, enc_beta = tf.sides(act)
+    opt["model"]["DFNet"]["act"] = trunk
+    opt["model"]["DFNet"]["beta"] = beta
+    opt["model"]["StrEnc"]["act"] = enc_act
+    opt["model"]["StrEnc"]["beta"] = enc_beta
     opt["model"]["DFNet"]["dims"] = list(hidden)
+    return opt
+
+
+def ref_step(act, hidden, loss, eikonal, sd, dtype, q, gt, qm):
+    _, PoseNDF = _import_reference()
+    opt = ref_config(act, hidden, loss)
     net = PoseNDF(opt).to(dtype)
     net.load_state_dict({k: torch.from_numpy(np.asarray(v)).to(dtype) for k, v in sd.items()})
     net.train()
@@ -73,6 +84,9 @@ def make(name):
     try:
         out = {"q": q, "dist_gt": gt, "q_man": qm, "act": np.array(act), "weights": np.array(weights), "loss_type": np.array(loss),
                "eikonal": np.array(eikonal), "hidden": np.array(hidden, np.int32)}
+        m = ref_config(act, hidden, loss)["model"]
+        out.update({"dfnet_act": np.array(m["DFNet"]["act"]), "dfnet_beta": np.array(float(m["DFNet"]["beta"])),
+                    "strenc_act": np.array(m["StrEnc"]["act"]), "strenc_beta": np.array(float(m["StrEnc"]["beta"]))})
         for dtype, tag in ((torch.float32, "f32"), (torch.float64, "f64")):
             losses, grads = ref_step(act, hidden, loss, eikonal, sd, dtype, q, gt, qm)
             out[f"losses_{tag}"] = losses

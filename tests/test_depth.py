@@ -1,8 +1,8 @@
 """DFNets of other depths and widths than configs/amass.yaml.
 
 reference model/network/net_modules.py:14-28 builds DFNet from a free list of hidden widths; tests/golden/make_golden_depth.py
-runs the REAL reference on seven such networks (one to seven hidden layers, widths up to 1024, with and without the structure
-encoder, all three activations) and records inputs and outputs.  Here:
+runs the REAL reference on such networks (one to seven hidden layers, widths up to 1024, with and without the structure encoder, all
+three activations, the encoder's activation and Softplus beta other than the trunk's, beta != 100) and records inputs and outputs.  Here:
   * CPU: the numpy oracle is pinned on those vectors (so it is a valid checker at these depths too), and the library's host twins
     (`train.device: cpu`) reproduce them;
   * GPU: `posendf_amd.PoseNDF` built from the same config runs on the runtime-planned HIP kernels (csrc/pndf_generic.hip) through
@@ -17,6 +17,10 @@ from conftest import GOLDEN, d_rows, escalated_noise, fp32_noise, outlier_gate, 
 
 CASES = ["d1_lrelu", "d4_lrelu", "d4_softplus", "d7_lrelu", "d7_softplus", "wide_relu", "noenc_d3_lrelu",
          "mix_softplus_lreluenc", "mix_relu_softplusenc"]      # the last two: model.StrEnc.act != model.DFNet.act ("trunk/encoder")
+# model.StrEnc.act / beta against model.DFNet.act / beta ("trunk[@beta]/encoder[@beta]", oracle.posendf_np.parse_act): relu / lrelu pairs,
+# an encoder beta of its own (also on amass.yaml's dims, which a differing pair takes off the fused kernels), beta != 100 on both sides
+BETA_CASES = ["mix_relu_lreluenc", "mix_lrelu_reluenc", "sp_b100_encb7", "sp_b100_encb7_amass", "mix_relu_spenc_b1000", "d4_softplus_b10"]
+CASES += BETA_CASES
 KERNELS = {("relu", "relu"): "pndf_generic_relu_kernel", ("softplus", "softplus"): "pndf_generic_softplus_kernel",
            ("softplus", "relu"): "pndf_generic_softplus_reluenc_kernel", ("relu", "softplus"): "pndf_generic_relu_spenc_kernel"}
 TOL = 1e-4
@@ -33,15 +37,28 @@ def load_case(name):
 
 
 def config_for(hidden, act, enc, device):
+    from oracle.posendf_np import parse_act
     from posendf_amd import amass_config
-    trunk_act, _, enc_act = act.partition("/")
+    trunk_act, beta, enc_act, enc_beta = parse_act(act)
     cfg = amass_config(trunk_act, device)
-    cfg["model"]["StrEnc"]["act"] = enc_act or trunk_act
+    cfg["model"]["DFNet"]["beta"] = beta
+    cfg["model"]["StrEnc"]["act"] = enc_act
+    cfg["model"]["StrEnc"]["beta"] = enc_beta
     cfg["model"]["DFNet"]["dims"] = list(hidden)
     cfg["model"]["StrEnc"]["use"] = enc
     if not enc:
         cfg["model"]["DFNet"]["in_dim"] = 84
     return cfg
+
+
+def generic_kernel(act, enc, precision):
+    """the runtime-planned kernel a network of activation string `act` runs on: one per (trunk, encoder) activation family, the split
+    form's own four under f16x3 (csrc/pndf_generic.hip gen_kernel)"""
+    from oracle.posendf_np import parse_act
+    fam = lambda a: "softplus" if a == "softplus" else "relu"      # noqa: E731
+    trunk_act, _, enc_act, _ = parse_act(act)
+    want = KERNELS[(fam(trunk_act), fam(enc_act) if enc else fam(trunk_act))]
+    return want.replace("pndf_generic_", "pndf_generic_split_") if precision != "fp32" else want
 
 
 def kink_exempt(q, sd, act):
@@ -65,6 +82,29 @@ def test_oracle_is_pinned_at_other_depths(name):
     pose_gate(d_rows(g["d_f32"], g["d_f64"]), np.maximum(sig_d, d_rows(d32, g["d_f64"])), f"{name} reference fp32 d")
     pose_gate(rel_err_rows(g["dq_f32"], g["dq_f64"]), np.maximum(sig_g, rel_err_rows(g32, g["dq_f64"])), f"{name} reference fp32 dq",
               exempt=kink_exempt(g["q"], sd, act))
+
+
+def mixed_up(act):
+    """the activation strings of a kernel that confuses the two sides' parameters: the encoder given the trunk's activation and beta,
+    the trunk given the encoder's, and beta 100 in place of either side's own beta"""
+    from oracle.posendf_np import parse_act
+    t, tb, e, eb = parse_act(act)
+    wrong = {(t, tb, t, tb), (e, eb, e, eb), (t, 100.0, e, eb), (t, tb, e, 100.0)} - {(t, tb, e, eb)}
+    return sorted(f"{a}@{ab}/{b}@{bb}" for a, ab, b, bb in wrong)
+
+
+@pytest.mark.parametrize("name", BETA_CASES)
+def test_beta_fixtures_tell_the_two_sides_apart(name):
+    """A fixture of a pair only tests the pair if swapping the sides' parameters moves the answer: every mixed-up evaluation of the
+    fp64 oracle misses the reference's d d/d q by a median per-pose relative error above 1e-2 (a dead encoder, or a network whose
+    units all sit in one regime, would let a kernel that mixes them up pass)."""
+    from oracle import posendf_np as onp
+    g, hidden, act, enc, sd = load_case(name)
+    assert mixed_up(act)
+    for wrong in mixed_up(act):
+        _, g_wrong = onp.forward_grad(g["q"], sd, wrong, dtype=np.float64)
+        miss = float(np.median(rel_err_rows(g_wrong, g["dq_f64"])))
+        assert miss > 1e-2, (name, wrong, miss)
 
 
 def _check_network(net, torch, g, act, sd, name, device):
@@ -121,8 +161,8 @@ def test_host_twins_at_other_depths(name):
 @pytest.mark.parametrize("precision", ["fp32", "f16x3"])
 @pytest.mark.parametrize("name", CASES)
 def test_runtime_planned_kernels(name, precision):
-    """The HIP path: every depth / width runs on pndf_generic_{relu,softplus}_kernel through the C ABI -- exact fp32 whatever
-    `precision` the config asks for -- and meets the gates of the fused kernels."""
+    """The HIP path: every depth / width runs on the runtime-planned kernels through the C ABI -- the exact fp32 form for precision
+    fp32, the split-precision form (fp16 hi + lo MFMAs, fp32 accumulate) for f16x3 -- and meets the gates of the fused kernels."""
     import torch
     from posendf_amd import PoseNDF
     assert torch.cuda.is_available(), "GPU tests need a visible MI355X (no CPU fallback exists)"
@@ -133,12 +173,7 @@ def test_runtime_planned_kernels(name, precision):
     net.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
     net.eval()
     _check_network(net, torch, g, act, sd, f"{name} {precision}", "cuda:0")
-    fam = lambda a: "softplus" if a == "softplus" else "relu"      # noqa: E731
-    trunk_act, _, enc_act = act.partition("/")
-    want = KERNELS[(fam(trunk_act), fam(enc_act or trunk_act) if enc else fam(trunk_act))]
-    if precision != "fp32":      # the trunk on split-precision fp16 MFMAs (csrc/pndf_generic.hip gen_layer_split): its own four kernels
-        want = want.replace("pndf_generic_", "pndf_generic_split_")
-    assert net._engine_for(torch.device("cuda:0")).kernel_name() == want
+    assert net._engine_for(torch.device("cuda:0")).kernel_name() == generic_kernel(act, enc, precision)
 
 
 @pytest.mark.gpu
@@ -238,19 +273,13 @@ def live_weights(dims, act):
     raise AssertionError(f"no live weight set for {dims} {act}")
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("precision", ["fp32", "f16x3"])      # the exact and the split-precision form of the runtime-planned kernels
-@pytest.mark.parametrize("hidden,act,enc", EXTREMES, ids=lambda v: "-".join(map(str, v)) if isinstance(v, list) else str(v))
-def test_runtime_planned_kernels_width_and_depth_extremes(hidden, act, enc, precision):
-    """Hidden widths 1, 15 - 17, one past a tile / a pass / 512, 1024; one to seven hidden layers; bottlenecks of a few units between
-    1024-wide layers: single step and a 3-step projection against the numpy oracle (fp64 truth, the fp32 oracle's own noise as the
-    envelope), through the per-pose gates."""
+def _check_against_oracle(hidden, act, enc, precision, sd):
+    """single step and a 3-step projection of the runtime-planned kernels against the numpy oracle (fp64 truth, the fp32 oracle's own
+    noise as the envelope), through the per-pose gates; returns the kernel that ran"""
     import torch
     from oracle import posendf_np as onp
     from posendf_amd import PoseNDF, synth
     assert torch.cuda.is_available(), "GPU tests need a visible MI355X (no CPU fallback exists)"
-    dims = (126 if enc else 84, *hidden, 1)
-    sd = live_weights(dims, act)
     cfg = config_for(hidden, act, enc, "cuda:0")
     cfg["engine"] = {"precision": precision}
     net = PoseNDF(cfg)
@@ -260,8 +289,7 @@ def test_runtime_planned_kernels_width_and_depth_extremes(hidden, act, enc, prec
     q = torch.from_numpy(q_np).cuda().requires_grad_(True)
     d = net(q, train=False)["dist_pred"]
     (dq,) = torch.autograd.grad(d.sum(), q)
-    assert net._engine_for(q.device).kernel_name().startswith("pndf_generic_split_" if precision == "f16x3" else "pndf_generic_")
-    assert ("_split_" in net._engine_for(q.device).kernel_name()) == (precision == "f16x3")
+    kernel = net._engine_for(q.device).kernel_name()
     sig_d, sig_g, d64, g64 = fp32_noise(q_np, sd, act)
     what = f"{hidden} {act} enc={enc} {precision}"
     # (`escalate`, as in the held-out sweep of tests/test_gpu_sweep.py: a pose over the cheap envelope is held to twice the reference
@@ -275,6 +303,36 @@ def test_runtime_planned_kernels_width_and_depth_extremes(hidden, act, enc, prec
     q32, _ = onp.project(q_np, sd, steps=3, act=act)
     env = traj_envelope(q_np, sd, act, 3, q64)
     outlier_gate(rel_err_rows(qp.cpu().numpy(), q64), rel_err_rows(q32, q64), TOL, what + " project 3", margin=env["margin"], sigma=env["sigma"])
+    return kernel
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("precision", ["fp32", "f16x3"])      # the exact and the split-precision form of the runtime-planned kernels
+@pytest.mark.parametrize("hidden,act,enc", EXTREMES, ids=lambda v: "-".join(map(str, v)) if isinstance(v, list) else str(v))
+def test_runtime_planned_kernels_width_and_depth_extremes(hidden, act, enc, precision):
+    """Hidden widths 1, 15 - 17, one past a tile / a pass / 512, 1024; one to seven hidden layers; bottlenecks of a few units between
+    1024-wide layers: single step and a 3-step projection against the numpy oracle (fp64 truth, the fp32 oracle's own noise as the
+    envelope), through the per-pose gates."""
+    kernel = _check_against_oracle(hidden, act, enc, precision, live_weights((126 if enc else 84, *hidden, 1), act))
+    assert kernel.startswith("pndf_generic_split_" if precision == "f16x3" else "pndf_generic_")
+    assert ("_split_" in kernel) == (precision == "f16x3")
+
+
+# model.DFNet.beta and model.StrEnc.beta away from 100 and from each other (reference net_modules.py:39-40, :103-107): the trunk's
+# beta with an equal encoder's, the encoder's own under a beta-100 trunk, a Softplus encoder near its threshold behind a ReLU trunk
+BETAS = ["softplus@1", "softplus@10", "softplus@1000", "softplus@100/softplus@1", "softplus@100/softplus@1000", "relu/softplus@1000"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("precision", ["fp32", "f16x3"])
+@pytest.mark.parametrize("act", BETAS)
+def test_runtime_planned_kernels_across_beta(act, precision):
+    """A network that is not shaped like configs/amass.yaml runs on the runtime-planned kernels whatever its betas: each side's beta
+    must reach that side's activation (ActP `ap` / `ape` in csrc/pndf_generic.hip).  Single step and a 3-step projection against
+    the numpy oracle, through the per-pose gates; the kernel is pinned, so that the f16x3 leg cannot quietly run the fp32 form."""
+    hidden = [384, 130, 48]
+    kernel = _check_against_oracle(hidden, act, True, precision, live_weights((126, *hidden, 1), act))
+    assert kernel == generic_kernel(act, True, precision)
 
 
 @pytest.mark.gpu

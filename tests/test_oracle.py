@@ -121,3 +121,38 @@ def test_gradient_finite_difference(act):
         fd = (onp.forward(q + h * v, sd, act, dtype=np.float64) - onp.forward(q - h * v, sd, act, dtype=np.float64)) / (2 * h)
         an = (dq * v).reshape(4, -1).sum(1)
         assert np.allclose(fd[:, 0], an, rtol=2e-4, atol=1e-9)
+
+
+def test_activation_string_grammar():
+    """"trunk[@beta]/encoder[@beta]" (onp.parse_act): model.DFNet.act / beta and model.StrEnc.act / beta travel in the one `act`
+    string that every oracle function and every gate helper takes; a side without "@" takes the `beta` argument, one side is both"""
+    p = onp.parse_act
+    assert p("lrelu") == ("lrelu", 100.0, "lrelu", 100.0) and p("softplus", 7.0) == ("softplus", 7.0, "softplus", 7.0)
+    assert p("softplus/lrelu") == ("softplus", 100.0, "lrelu", 100.0) and p("relu/softplus", 3.0) == ("relu", 3.0, "softplus", 3.0)
+    assert p("softplus@10") == ("softplus", 10.0, "softplus", 10.0)
+    assert p("softplus@100/softplus@7") == ("softplus", 100.0, "softplus", 7.0)
+    assert p("relu/softplus@1000", 5.0) == ("relu", 5.0, "softplus", 1000.0)
+    assert p("softplus@2.5/lrelu", 9.0) == ("softplus", 2.5, "lrelu", 9.0)
+    assert [onp.act_family(a) for a in ("softplus@10", "relu/softplus@1000", "softplus@100/softplus@7")] == \
+        ["softplus", "relu/softplus", "softplus/softplus"]
+    for bad in ("", "tanh", "relu/", "/relu", "relu/lrelu/relu", "softplus@", "softplus@x", "softplus@0", "softplus@-1",
+                "softplus@inf", "softplus@nan", "softplus@1@2", "Softplus", "relu /lrelu"):
+        with pytest.raises(ValueError):
+            p(bad)
+    # the betas reach the arithmetic: "name@b" is beta=b, a bare name is bit-identical to what it always was
+    from conftest import golden_weights
+    from posendf_amd import synth
+    sd = golden_weights("live")
+    q = synth.make_poses(16, seed=3)
+    for act, beta, same in (("softplus", 100.0, "softplus@100"), ("softplus", 7.0, "softplus@7/softplus@7"),
+                            ("softplus/lrelu", 3.0, "softplus@3/lrelu"), ("lrelu", 100.0, "lrelu/lrelu@5")):
+        for dtype in (np.float32, np.float64):
+            a, b = onp.forward_grad(q, sd, act, beta, dtype), onp.forward_grad(q, sd, same, dtype=dtype)
+            assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]), (act, beta, same)
+    # ... and each side's beta reaches its own side only
+    d_t, _ = onp.forward_grad(q, sd, "softplus@7/softplus", dtype=np.float64)
+    d_e, _ = onp.forward_grad(q, sd, "softplus/softplus@7", dtype=np.float64)
+    f = onp.encoder_forward(onp.normalize_joint_axis(q.astype(np.float64))[0], sd, "softplus", 7.0)
+    assert np.array_equal(d_e, onp.dfnet_forward(f, sd, "softplus", 100.0))
+    f = onp.encoder_forward(onp.normalize_joint_axis(q.astype(np.float64))[0], sd, "softplus", 100.0)
+    assert np.array_equal(d_t, onp.dfnet_forward(f, sd, "softplus", 7.0))

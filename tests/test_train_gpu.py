@@ -30,9 +30,9 @@ def _gate(what, mine, ref32, ref64, failures, floor=0.0):
     return err
 
 
-def _model(act, sd, hidden, loss="l1", backend="hip", dtype=torch.float32, enc_act=None):
+def _model(act, sd, hidden, loss="l1", backend="hip", dtype=torch.float32, enc_act=None, beta=None, enc_beta=None):
     from posendf_amd import PoseNDF
-    net = PoseNDF(tf.config(act, hidden, loss, DEV, train_backend=backend, enc_act=enc_act)).to(dtype)
+    net = PoseNDF(tf.config(act, hidden, loss, DEV, train_backend=backend, enc_act=enc_act, beta=beta, enc_beta=enc_beta)).to(dtype)
     net.load_state_dict({k: torch.from_numpy(np.asarray(v)).to(dtype) for k, v in sd.items()})
     return net
 
@@ -42,11 +42,12 @@ def _run(net, q, gt, qm, eikonal, dtype=torch.float32):
     return tf.run_objective(net, t(q), t(gt), t(qm), eikonal)
 
 
-def _compare_full(tag, act, sd, hidden, q, gt, qm, eikonal, loss="l1", enc_act=None):
+def _compare_full(tag, act, sd, hidden, q, gt, qm, eikonal, loss="l1", enc_act=None, beta=None, enc_beta=None):
     """HIP fp32 against the stock path in fp64 on the GPU, with the stock fp32 run as the envelope"""
-    l_h, g_h, _ = _run(_model(act, sd, hidden, loss, enc_act=enc_act), q, gt, qm, eikonal)
-    l_32, g_32, _ = _run(_model(act, sd, hidden, loss, "torch", enc_act=enc_act), q, gt, qm, eikonal)
-    l_64, g_64, _ = _run(_model(act, sd, hidden, loss, "torch", torch.float64, enc_act=enc_act), q, gt, qm, eikonal, torch.float64)
+    kw = dict(enc_act=enc_act, beta=beta, enc_beta=enc_beta)
+    l_h, g_h, _ = _run(_model(act, sd, hidden, loss, **kw), q, gt, qm, eikonal)
+    l_32, g_32, _ = _run(_model(act, sd, hidden, loss, "torch", **kw), q, gt, qm, eikonal)
+    l_64, g_64, _ = _run(_model(act, sd, hidden, loss, "torch", torch.float64, **kw), q, gt, qm, eikonal, torch.float64)
     assert set(l_h) == set(l_64)
     failures, worst = [], 0.0
     for k in l_64:
@@ -176,6 +177,21 @@ def test_other_networks(act, hidden, enc_act):
     q, qm = synth.make_poses(300, seed=41), synth.make_poses(200, seed=42)
     gt = np.random.default_rng(43).uniform(0, 0.5, 300).astype(np.float32)
     _compare_full(f"{act} {hidden} enc {enc_act}", act, sd, hidden, q, gt, qm, 1.0, enc_act=enc_act)
+
+
+@pytest.mark.parametrize("act,enc_act,beta,enc_beta", [
+    ("softplus", None, 1.0, None), ("softplus", None, 1000.0, None),          # the trunk's beta, the encoder's equal to it
+    ("softplus", "softplus", 100.0, 7.0), ("softplus", "softplus", 10.0, 1000.0),      # the encoder's own beta
+    ("relu", "softplus", None, 1000.0), ("relu", "softplus", None, 7.0),       # a Softplus encoder of its own beta behind a ReLU trunk
+    ("lrelu", "relu", None, None), ("relu", "lrelu", None, None)])             # the two slopes, both ways round
+def test_activation_pairs_and_betas(act, enc_act, beta, enc_beta):
+    """model.StrEnc.act / beta against model.DFNet.act / beta: each side's activation, slope and beta must reach that side's
+    forward, reverse and double-backward (eikonal) arithmetic.  amass.yaml's dims, ragged B / Bm, the eikonal term on."""
+    from posendf_amd import synth
+    sd, hidden = tf.case_weights("live")
+    q, qm = synth.make_poses(300, seed=51), synth.make_poses(200, seed=52)
+    gt = np.random.default_rng(53).uniform(0, 0.5, 300).astype(np.float32)
+    _compare_full(f"{act}@{beta} enc {enc_act}@{enc_beta}", act, sd, hidden, q, gt, qm, 1.0, enc_act=enc_act, beta=beta, enc_beta=enc_beta)
 
 
 def test_opt_in_path_uses_the_hip_objective():

@@ -95,6 +95,8 @@ def test_fp64_oracle_reproduces_the_fixture(name):
     z = dict(np.load(tf.fixture_path(name)))
     act, weights, loss, eikonal = tf.CASES[name]
     assert str(z["act"]) == act and str(z["weights"]) == weights and str(z["loss_type"]) == loss and float(z["eikonal"]) == eikonal
+    trunk, beta, enc_act, enc_beta = tf.sides(act)      # what the reference's config held: model.DFNet.act / beta, model.StrEnc.act / beta
+    assert (str(z["dfnet_act"]), float(z["dfnet_beta"]), str(z["strenc_act"]), float(z["strenc_beta"])) == (trunk, beta, enc_act, enc_beta)
     assert os.path.getsize(tf.fixture_path(name)) < 700 * 1024
     q, gt, qm = tf.case_inputs()
     assert np.array_equal(z["q"], q) and np.array_equal(z["dist_gt"], gt) and np.array_equal(z["q_man"], qm)

@@ -13,7 +13,8 @@ GOLDEN = os.path.join(HERE, "golden")
 
 B, BM = 509, 383                          # ragged noisy / manifold batches
 N_ENTRIES = 1024                          # seeded entries kept of each large weight gradient
-# name: (DFNet.act, weights, train.loss_type, eikonal weight)
+# name: (activation, weights, train.loss_type, eikonal weight).  The activation string is oracle.posendf_np.parse_act's:
+# "DFNet.act[@DFNet.beta]/StrEnc.act[@StrEnc.beta]", one side for both, beta 100 where no "@" says otherwise
 CASES = {
     "lrelu_live": ("lrelu", "live", "l1", 1.0),
     "relu_live": ("relu", "live", "l1", 1.0),
@@ -21,6 +22,9 @@ CASES = {
     "trained_lrelu": ("lrelu", "trained_lrelu", "l1", 1.0),
     "lrelu_noeik": ("lrelu", "live", "l1", 0.0),
     "softplus_l2": ("softplus", "live", "l2", 1.0),
+    "softplus_encb7": ("softplus@100/softplus@7", "live", "l1", 1.0),      # the encoder's beta alone differs
+    "relu_lreluenc": ("relu/lrelu", "live", "l1", 1.0),                    # the encoder's LeakyReLU slope behind a slope-0 trunk
+    "softplus_b10": ("softplus@10", "live", "l1", 1.0),                    # beta != 100 on both sides
 }
 LOSS_KEYS = ("dist", "man_loss", "eikonal")
 
@@ -67,12 +71,22 @@ def digest(key, g, hidden):
             "vals": g.reshape(-1)[entry_index(key, g.shape)]}
 
 
-def config(act, hidden, loss, device, train_backend="torch", enc_act=None):
+def sides(act, enc_act=None, beta=None, enc_beta=None):
+    """(DFNet.act, DFNet.beta, StrEnc.act, StrEnc.beta) of an activation string; `beta` stands for the beta of a side without "@",
+    `enc_act` / `enc_beta` replace the encoder's"""
+    from oracle.posendf_np import parse_act
+    trunk, tbeta, eact, ebeta = parse_act(act, 100.0 if beta is None else float(beta))
+    return trunk, tbeta, (eact if enc_act is None else enc_act), (ebeta if enc_beta is None else float(enc_beta))
+
+
+def config(act, hidden, loss, device, train_backend="torch", enc_act=None, beta=None, enc_beta=None):
     from posendf_amd import amass_config
-    cfg = amass_config(act, device)
+    trunk, tbeta, eact, ebeta = sides(act, enc_act, beta, enc_beta)
+    cfg = amass_config(trunk, device)
     cfg["model"]["DFNet"]["dims"] = list(hidden)
-    if enc_act is not None:
-        cfg["model"]["StrEnc"]["act"] = enc_act
+    cfg["model"]["DFNet"]["beta"] = tbeta
+    cfg["model"]["StrEnc"]["act"] = eact
+    cfg["model"]["StrEnc"]["beta"] = ebeta
     cfg["train"]["loss_type"] = loss
     cfg["engine"] = {"train": train_backend}
     return cfg
