@@ -269,6 +269,27 @@ const char* pndf_train_last_error(pndf_train_handle h);  /* h may be NULL: last 
 int pndf_quat_topk(const float* noise, const float* valid, int64_t B, int32_t K, int32_t metric, const float* weights,
                    int32_t k, float* vals, long long* idx, void* stream);
 
+/* ---- exact k-nearest-pose search over a pose database (the search of data/prepare_traindata.py:152-159 with the whole
+ * database as every query's candidate list: no joint-space prefilter).  Metrics and semantics of pndf_quat_topk:
+ * metric 0 = geo, 1 = euc; weights = 21 HOST floats (> 0) or NULL for the unweighted mean; vals [Q,k] ascending, idx [Q,k]
+ * int64, ties towards the lower database index, a NaN distance is never selected (missing slots: NaN / -1);
+ * 1 <= k <= min(16, N), N < 2^31.
+ * pndf_knn_create packs a copy of `poses` (device [N,21,4], 16-byte aligned) into the layout the search kernels stream and
+ * synchronises `stream`: the caller may free or overwrite `poses` when it returns (FAISS `add` semantics).  Without a gfx950
+ * device it returns PNDF_ERR_NO_DEVICE.  The index lives on the device of `poses`.
+ * pndf_knn_search: q device [Q,21,4] (16-byte aligned), `workspace` pndf_knn_workspace_bytes(h, Q, k) bytes (16-byte aligned;
+ * may be NULL when that is 0).  Allocates nothing, does not synchronise; Q = 0 is a no-op.  The plan (query blocks x
+ * database splits) depends on (Q, N, k) only, and the results do not depend on it: the same bits for any chunking of the
+ * queries. */
+typedef struct pndf_knn_index* pndf_knn_handle;
+int pndf_knn_create(pndf_knn_handle* out, const float* poses, int64_t N, int32_t metric, const float* weights, void* stream);
+int pndf_knn_destroy(pndf_knn_handle h);
+int64_t pndf_knn_size(pndf_knn_handle h);                                        /* N; -1 for a NULL handle */
+int64_t pndf_knn_workspace_bytes(pndf_knn_handle h, int64_t Q, int32_t k);       /* negative pndf_status on bad arguments */
+int pndf_knn_search(pndf_knn_handle h, const float* q, int64_t Q, int32_t k, float* vals, long long* idx, void* workspace,
+                    void* stream);
+const char* pndf_knn_last_error(pndf_knn_handle h);   /* h may be NULL: last error of a call without a handle */
+
 const char* pndf_last_error(pndf_handle h);   /* h may be NULL: last error of a failed pndf_create */
 const char* pndf_version(void);
 /* 0 in every product build: one bit per compile-time tuning / ablation macro that differed from its product default when the

@@ -10,10 +10,13 @@ def __getattr__(name):   # torch is imported lazily so that numpy-only users (or
     if name in ("PoseNDF", "gradient"):
         from . import facade
         return getattr(facade, name)
+    if name == "PoseIndex":
+        from .knn import PoseIndex
+        return PoseIndex
     if name == "BodyModel":
         from .body_model import BodyModel
         return BodyModel
     raise AttributeError(name)
 
 
-__all__ = ["PoseNDF", "gradient", "BodyModel", "amass_config", "load_config", "synth"]
+__all__ = ["PoseNDF", "gradient", "BodyModel", "PoseIndex", "amass_config", "load_config", "synth"]

@@ -165,6 +165,19 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     lib.pndf_train_backward.restype = c_int
     lib.pndf_train_last_error.argtypes = [TH]
     lib.pndf_train_last_error.restype = c_char_p
+    KH = c_void_p
+    lib.pndf_knn_create.argtypes = [POINTER(KH), c_void_p, c_int64, c_int32, c_void_p, c_void_p]
+    lib.pndf_knn_create.restype = c_int
+    lib.pndf_knn_destroy.argtypes = [KH]
+    lib.pndf_knn_destroy.restype = c_int
+    lib.pndf_knn_size.argtypes = [KH]
+    lib.pndf_knn_size.restype = c_int64
+    lib.pndf_knn_workspace_bytes.argtypes = [KH, c_int64, c_int32]
+    lib.pndf_knn_workspace_bytes.restype = c_int64
+    lib.pndf_knn_search.argtypes = [KH, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.pndf_knn_search.restype = c_int
+    lib.pndf_knn_last_error.argtypes = [KH]
+    lib.pndf_knn_last_error.restype = c_char_p
     CH = c_void_p
     lib.pndf_cpu_create.argtypes = [POINTER(CH), POINTER(PndfConfig)]
     lib.pndf_cpu_destroy.argtypes = [CH]
@@ -221,6 +234,7 @@ EXPORTS = ("pndf_default_config", "pndf_create", "pndf_destroy", "pndf_load_weig
            "pndf_lbs_last_error", "pndf_last_error", "pndf_version", "pndf_kernel_name",
            "pndf_train_create", "pndf_train_destroy", "pndf_train_workspace_floats", "pndf_train_forward", "pndf_train_backward",
            "pndf_train_last_error",
+           "pndf_knn_create", "pndf_knn_destroy", "pndf_knn_size", "pndf_knn_workspace_bytes", "pndf_knn_search", "pndf_knn_last_error",
            "pndf_cpu_create", "pndf_cpu_destroy", "pndf_cpu_load_weights", "pndf_forward_cpu", "pndf_forward_grad_cpu", "pndf_project_cpu",
            "pndf_cpu_last_error")
 
@@ -452,6 +466,57 @@ class TrainEngine:
     def close(self):
         if getattr(self, "handle", None):
             self.lib.pndf_train_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+METRIC_CODES = {"geo": 0, "euc": 1}
+
+
+class KnnIndex:
+    """`pndf_knn_*` (csrc/pndf_knn.hip): an exact k-nearest-pose index on one device.  The constructor packs a copy of the
+    poses at `poses_ptr` (device [N,21,4]); `search` takes raw device pointers and a stream handle."""
+
+    def __init__(self, poses_ptr, N, metric: str = "geo", weights=None, stream=0, lib=None):
+        self.lib = lib or load_library()
+        if metric not in METRIC_CODES:
+            raise PndfError(f"unknown metric {metric!r} (geo, euc)")
+        w = None
+        if weights is not None:
+            w = (c_float * 21)(*[float(x) for x in np.asarray(weights, dtype=np.float32).reshape(21)])
+        self.handle = c_void_p()
+        rc = self.lib.pndf_knn_create(ctypes.byref(self.handle), poses_ptr, int(N), METRIC_CODES[metric], w, stream)
+        if rc != 0:
+            msg = self.lib.pndf_knn_last_error(None).decode()
+            self.handle = None
+            raise PndfError(f"pndf_knn_create failed ({rc}): {msg}")
+        self.metric = metric
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise PndfError(f"{what} failed ({rc}): {self.lib.pndf_knn_last_error(self.handle).decode()}")
+
+    def size(self) -> int:
+        return int(self.lib.pndf_knn_size(self.handle))
+
+    def workspace_bytes(self, Q, k) -> int:
+        n = int(self.lib.pndf_knn_workspace_bytes(self.handle, int(Q), int(k)))
+        if n < 0:
+            raise PndfError(f"pndf_knn_workspace_bytes failed ({n}): Q = {Q}, k = {k}, N = {self.size()}")
+        return n
+
+    def search(self, q_ptr, Q, k, vals_ptr, idx_ptr, ws_ptr, stream=0):
+        self._check(self.lib.pndf_knn_search(self.handle, q_ptr, int(Q), int(k), vals_ptr, idx_ptr, ws_ptr, stream),
+                    "pndf_knn_search")
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.pndf_knn_destroy(self.handle)
             self.handle = None
 
     def __del__(self):
