@@ -261,6 +261,41 @@ int pndf_train_backward(pndf_train_handle h, const float* const* weights, const 
                         void* workspace, void* stream);
 const char* pndf_train_last_error(pndf_train_handle h);  /* h may be NULL: last error of a failed pndf_train_create */
 
+/* ---- the rest of a training step (model/train_posendf.py:92-99, model/load_data.py:43-71): with the two calls above,
+ *   pndf_train_batch;  pndf_train_forward;  pndf_train_backward;  pndf_adam_step
+ * is one step with no host work between the launches.  Stateless helpers (no handle; status codes as above, no error text):
+ * DEVICE pointers, work enqueued on `stream`, nothing allocated, no synchronisation; plain loads and stores, no atomics: the
+ * same inputs give the same bits. */
+/* torch.optim.Adam(lr, betas, eps, weight_decay, amsgrad=False, maximize=False).step() (train_posendf.py:30,99) over ONE flat
+ * fp32 buffer: p, g, m (exp_avg), v (exp_avg_sq) hold every tensor of the model at the same offsets (state-dict order, every
+ * tensor on a 16-byte boundary); the pad elements between tensors are zero in all four buffers and stay zero, so no tensor
+ * table is needed.  n: floats, any count (the tail is not read past).  Coupled L2 weight decay: g + weight_decay * p enters both
+ * moments.  `step` = 1, 2, ...: the bias corrections 1 - beta^step are computed on the host in double, as torch does; eps is
+ * added after the division by sqrt(1 - beta2^step).  The hyper-parameters are doubles (torch holds Python floats) and are
+ * rounded to fp32 once, where torch rounds them.  step < 1, n < 0, a beta outside [0, 1), a null or misaligned pointer:
+ * PNDF_ERR_BAD_ARG; n == 0: no-op. */
+int pndf_adam_step(float* p, const float* g, float* m, float* v, int64_t n, int32_t step, double lr, double beta1, double beta2,
+                   double eps, double weight_decay, void* stream);
+/* PoseData.__getitem__ (load_data.py:43-71) for every item of one batch, from a data set that is resident on the device:
+ *   pose_db [N,21,4] noisy poses and dist_db [N,k] their labels, the rows of F data files one after the other, file f =
+ *   rows file_off[f] .. file_off[f+1]-1 (file_off: F+1 int64, 8-byte aligned); man_db [M,21,4] manifold poses, Fm files,
+ *   man_off likewise; item_file / item_man_file [items] int32: the data file and the manifold file of every item;
+ *   words [items,2,num_pts] uint32: raw random words.
+ * Pose i of item t is row file_off[f] + ((uint64)words[t,0,i] * len_f >> 32) of its data file f (len_f rows), its manifold pose
+ * the same with words[t,1,i] in its manifold file: uniform up to a bias below len / 2^32 per row (a file has fewer than 2^32
+ * rows).  Outputs in the layout pndf_train_forward takes: q [items*num_pts,21,4], dist_gt [items*num_pts] = the mean of the
+ * row's k labels (fp32, summed in index order, then divided by k: load_data.py:53), q_man [items*num_pts,21,4].  flip != 0
+ * negates every joint quaternion whose real part is < 0 (quat_flip, load_data.py:12-16), of the noisy poses and of the manifold
+ * poses themselves (load_data.py:63 flips the noisy poses into the manifold batch instead; that is not reproduced).
+ * pose_db, man_db, q, dist_gt, q_man 16-byte aligned.  The offsets live on the device and are not read back: an item that
+ * names a file outside 0 .. F-1 (Fm-1) or an empty file gets NaN poses and a NaN label and nothing is read out of bounds;
+ * callers refuse empty files when they load the data set.  F, Fm, k < 1, a negative count, a null or misaligned pointer:
+ * PNDF_ERR_BAD_ARG; items == 0 or num_pts == 0: no-op. */
+int pndf_train_batch(const float* pose_db, const float* dist_db, const float* man_db, const int64_t* file_off,
+                     const int64_t* man_off, const int32_t* item_file, const int32_t* item_man_file, const uint32_t* words,
+                     int32_t F, int32_t Fm, int32_t k, int32_t items, int32_t num_pts, int32_t flip, float* q, float* dist_gt,
+                     float* q_man, void* stream);
+
 /* ---- quaternion pose distance + k nearest candidates (data/dist_utils.py:9-50, classes euc / geo; caller
  * data/prepare_traindata.py:159).  noise [B,21,4], valid [B,K,21,4] (device, 16-byte aligned);
  * metric 0 = geo: sum_j w_j (1 - |<q_valid_j, q_noise_j>|), 1 = euc: sum_j w_j ||q_noise_j - q_valid_j||;

@@ -13,10 +13,13 @@ def __getattr__(name):   # torch is imported lazily so that numpy-only users (or
     if name == "PoseIndex":
         from .knn import PoseIndex
         return PoseIndex
+    if name in ("Trainer", "PoseDataset"):
+        from . import trainer
+        return getattr(trainer, name)
     if name == "BodyModel":
         from .body_model import BodyModel
         return BodyModel
     raise AttributeError(name)
 
 
-__all__ = ["PoseNDF", "gradient", "BodyModel", "PoseIndex", "amass_config", "load_config", "synth"]
+__all__ = ["PoseNDF", "gradient", "BodyModel", "PoseIndex", "Trainer", "PoseDataset", "amass_config", "load_config", "synth"]

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_void_p
 
 import numpy as np
 
@@ -165,6 +165,10 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     lib.pndf_train_backward.restype = c_int
     lib.pndf_train_last_error.argtypes = [TH]
     lib.pndf_train_last_error.restype = c_char_p
+    lib.pndf_adam_step.argtypes = [c_void_p] * 4 + [c_int64, c_int32] + [c_double] * 5 + [c_void_p]
+    lib.pndf_adam_step.restype = c_int
+    lib.pndf_train_batch.argtypes = [c_void_p] * 8 + [c_int32] * 6 + [c_void_p] * 4
+    lib.pndf_train_batch.restype = c_int
     KH = c_void_p
     lib.pndf_knn_create.argtypes = [POINTER(KH), c_void_p, c_int64, c_int32, c_void_p, c_void_p]
     lib.pndf_knn_create.restype = c_int
@@ -207,7 +211,7 @@ DEBUG_EXPORTS = ("pndf_debug_bind", "pndf_debug_experiment_word", "pndf_debug_fo
                  "pndf_debug_timing_regions", "pndf_debug_timing_layout", "pndf_debug_mem_probe", "pndf_debug_ring_stream")
 # per-translation-unit experiment words (csrc/pndf_experiment.h): data symbols, all zero in a product build
 EXPERIMENT_WORDS = ("pndf_experiment_word_capi", "pndf_experiment_word_fp32", "pndf_experiment_word_split", "pndf_experiment_word_split_x2",
-                    "pndf_experiment_word_lbs", "pndf_experiment_word_generic", "pndf_experiment_word_train")
+                    "pndf_experiment_word_lbs", "pndf_experiment_word_generic", "pndf_experiment_word_train", "pndf_experiment_word_optim")
 DEBUG_EXPERIMENT_WORDS = ("pndf_experiment_word_debug", "pndf_experiment_word_fp32_timing", "pndf_experiment_word_split_timing",
                           "pndf_experiment_word_fp32_dbg", "pndf_experiment_word_probe")
 
@@ -233,7 +237,7 @@ EXPORTS = ("pndf_default_config", "pndf_create", "pndf_destroy", "pndf_load_weig
            "pndf_lbs_forward", "pndf_lbs_terms_grad", "pndf_lbs_backward", "pndf_lbs_packed_floats", "pndf_lbs_pack_host", "pndf_lbs_packed_split_bytes", "pndf_lbs_pack_split_host",
            "pndf_lbs_last_error", "pndf_last_error", "pndf_version", "pndf_kernel_name",
            "pndf_train_create", "pndf_train_destroy", "pndf_train_workspace_floats", "pndf_train_forward", "pndf_train_backward",
-           "pndf_train_last_error",
+           "pndf_train_last_error", "pndf_adam_step", "pndf_train_batch",
            "pndf_knn_create", "pndf_knn_destroy", "pndf_knn_size", "pndf_knn_workspace_bytes", "pndf_knn_search", "pndf_knn_last_error",
            "pndf_cpu_create", "pndf_cpu_destroy", "pndf_cpu_load_weights", "pndf_forward_cpu", "pndf_forward_grad_cpu", "pndf_project_cpu",
            "pndf_cpu_last_error")
@@ -444,6 +448,8 @@ class TrainEngine:
             raise PndfError(f"{what} failed ({rc}): {self.lib.pndf_train_last_error(self.handle).decode()}")
 
     def _table(self, ptrs):
+        if isinstance(ptrs, ctypes.Array):      # a table the caller built once (posendf_amd.trainer: one per trainer, not per step)
+            return ptrs
         if len(ptrs) != self.n_tensors:
             raise PndfError(f"{len(ptrs)} tensors given, the network has {self.n_tensors}")
         return (c_void_p * len(ptrs))(*ptrs)
@@ -473,6 +479,24 @@ class TrainEngine:
             self.close()
         except Exception:
             pass
+
+
+def adam_step(p_ptr, g_ptr, m_ptr, v_ptr, n, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, stream=0, lib=None):
+    """`pndf_adam_step` (csrc/pndf_optim.hip): one torch.optim.Adam step over flat fp32 device buffers of n floats"""
+    rc = (lib or load_library()).pndf_adam_step(p_ptr, g_ptr, m_ptr, v_ptr, int(n), int(step), float(lr), float(beta1), float(beta2),
+                                                float(eps), float(weight_decay), stream)
+    if rc != 0:
+        raise PndfError(f"pndf_adam_step failed ({rc}): n = {n}, step = {step}; the four buffers must be non-null and 16-byte aligned")
+
+
+def train_batch(pose_db_ptr, dist_db_ptr, man_db_ptr, file_off_ptr, man_off_ptr, item_file_ptr, item_man_file_ptr, words_ptr, F, Fm, k,
+                items, num_pts, flip, q_ptr, gt_ptr, qm_ptr, stream=0, lib=None):
+    """`pndf_train_batch` (csrc/pndf_optim.hip): one training batch gathered from a device-resident data set"""
+    rc = (lib or load_library()).pndf_train_batch(pose_db_ptr, dist_db_ptr, man_db_ptr, file_off_ptr, man_off_ptr, item_file_ptr,
+                                                  item_man_file_ptr, words_ptr, int(F), int(Fm), int(k), int(items), int(num_pts),
+                                                  int(bool(flip)), q_ptr, gt_ptr, qm_ptr, stream)
+    if rc != 0:
+        raise PndfError(f"pndf_train_batch failed ({rc}): F = {F}, Fm = {Fm}, k = {k}, items = {items}, num_pts = {num_pts}")
 
 
 METRIC_CODES = {"geo": 0, "euc": 1}

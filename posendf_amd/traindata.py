@@ -18,6 +18,9 @@ Kept from the reference's sampler, on purpose:
 Difference: the reference's labels are the top-k among 500 candidates of a FAISS search in SMPL joint space (that prefilter
 needs the SMPL model files and is out of scope); these are the exact top-k over the whole database, so per query each of our k
 distances is <= the reference's.
+Difference on the reading side (posendf_amd.trainer): with `data.flip` the reference's loader (model/load_data.py:63) flips
+the noisy poses where it means the manifold poses, so its manifold batch becomes a copy of the noisy one; the trainer here flips
+the manifold poses themselves.
 """
 from __future__ import annotations
 
