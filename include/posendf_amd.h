@@ -117,6 +117,33 @@ int pndf_forward_grad(pndf_handle h, const float* q, const float* grad_out, floa
 int pndf_project(pndf_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps,
                  void* stream);
 
+/* Options of one projection step (pndf_project_ex; DESIGN.md section 1 "The projection step").  Per pose and step, every operation
+ * rounded to fp32 on its own (no fused multiply-add), d = dist_pred(q) and g = d d / d q as in pndf_project:
+ *   tol > 0 and d < tol : the pose is left unchanged, bit for bit (a NaN d compares false and is not frozen).  The rule is
+ *                         stateless: an unchanged pose has the same d at the next step and stays frozen.  It stops the motion,
+ *                         not the work: the launch still runs every step for every pose;
+ *   otherwise             u = q - step_size * (d * g);   step_size = 1 is the step of pndf_project, bit for bit;
+ *   PNDF_RENORM_UNIT    : per joint, u <- u / clamp_min(sqrt(((u0 u0 + u1 u1) + u2 u2) + u3 u3), 1e-12) (the clamp of F.normalize: a
+ *                         zero quaternion stays zero);
+ *   PNDF_RENORM_UNIT_FLIP: the same, then u <- -u where u0 < 0 (the convention of the training data, model/load_data.py:12-16).
+ * The input of the first step is used as given: only the results of updates are normalised. */
+enum { PNDF_RENORM_NONE = 0, PNDF_RENORM_UNIT = 1, PNDF_RENORM_UNIT_FLIP = 2 };
+typedef struct {
+    uint32_t struct_size;   /* sizeof(pndf_project_options): a struct of another size (a zero-initialised one) is refused */
+    float step_size;        /* alpha, finite and > 0; default 1 */
+    int32_t renorm;         /* PNDF_RENORM_*; default PNDF_RENORM_NONE */
+    float tol;              /* >= 0; default 0 = no pose is ever frozen */
+} pndf_project_options;
+void pndf_default_project_options(pndf_project_options* opt);
+
+/* pndf_project with step options.  opt == NULL means the defaults, and with the defaults the call is pndf_project bit for
+ * bit.  PNDF_ERR_BAD_ARG (text in pndf_last_error; nothing is launched or written) for a struct_size other than
+ * sizeof(pndf_project_options), a step_size that is not finite or <= 0, a tol that is NaN or < 0, an unknown renorm mode.
+ * d_last[b] stays dist_pred of the last iteration, evaluated before its update.  Every kernel behind pndf_project honours the
+ * options (all precisions, the encoder-less model, the runtime-planned networks). */
+int pndf_project_ex(pndf_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps,
+                    const pndf_project_options* opt, void* stream);
+
 /* ---- host twins (SURVEY.md 8b `pndf_*_cpu`): the same three operations on HOST pointers, for a caller whose
  * `train.device` is "cpu" (model/posendf.py:35,64 runs wherever the config says).  A separate handle type with no device
  * behind it: plain C++ on the host cores, fp32, PyTorch's activation conventions; blocks of 32 poses are dealt to threads
@@ -131,6 +158,8 @@ int pndf_cpu_load_weights(pndf_cpu_handle h, const float* const* tensors, const 
 int pndf_forward_cpu(pndf_cpu_handle h, const float* q, float* d, int64_t B);                                       /* posendf.py:62-76 */
 int pndf_forward_grad_cpu(pndf_cpu_handle h, const float* q, const float* grad_out, float* d, float* dq, int64_t B); /* posendf.py:18-27 */
 int pndf_project_cpu(pndf_cpu_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps);      /* sample_poses.py:67-74 */
+int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps,
+                        const pndf_project_options* opt);      /* pndf_project_ex: same semantics, same validation */
 const char* pndf_cpu_last_error(pndf_cpu_handle h);   /* h may be NULL: last error of a failed pndf_cpu_create */
 
 /* Host-only weight packer (what pndf_load_weights uploads); needs no device.  Output sizes in floats come

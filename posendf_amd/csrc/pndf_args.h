@@ -7,7 +7,11 @@
 #include <stddef.h>
 #include <stdint.h>
 
-enum { MODE_FORWARD = 0, MODE_FORWARD_GRAD = 1, MODE_PROJECT = 2 };
+// MODE_PROJECT is the plain loop q <- q - d * grad and ignores the option fields; MODE_PROJECT_OPT is the same loop with the step
+// options of pndf_project_ex (include/posendf_amd.h pndf_project_options; DESIGN.md section 1 "The projection step"): renorm,
+// step_size and tol hold.  The host picks it only when an option differs from its default, so the plain loop's code is the one
+// pndf_project always ran.
+enum { MODE_FORWARD = 0, MODE_FORWARD_GRAD = 1, MODE_PROJECT = 2, MODE_PROJECT_OPT = 3 };
 
 struct PndfKernelArgs {
     const float* q_in;      // [B,84]
@@ -19,17 +23,21 @@ struct PndfKernelArgs {
     float* dbg;             // null, or DBG_TOTAL*256 floats written by workgroup 0 (first step) / timing stamps
     long long B;
     int steps;
-    int mode;               // MODE_FORWARD / MODE_FORWARD_GRAD / MODE_PROJECT (pndf_device.h)
+    int mode;               // MODE_FORWARD / MODE_FORWARD_GRAD / MODE_PROJECT / MODE_PROJECT_OPT
     float slope;            // 0 = relu, 0.01 = lrelu
     float beta;             // softplus beta
     float* scratch;         // softplus: gridDim.x * SP_WG_FLOATS floats of derivative scratch, else null
-    int reserved0;
+    int renorm;             // MODE_PROJECT_OPT: 0 none, 1 unit, 2 unit_flip (PNDF_RENORM_*)
     int noenc;              // 1 = model.StrEnc.use False: the trunk sees the normalised quaternions (in_dim 84)
+    float step_size;        // MODE_PROJECT_OPT: alpha of q <- q - alpha (d * grad)
+    float tol;              //   and the stop tolerance: a pose with d < tol is left unchanged (0 = never)
 };
-static_assert(sizeof(PndfKernelArgs) == 96, "PndfKernelArgs layout");
+static_assert(sizeof(PndfKernelArgs) == 104, "PndfKernelArgs layout");
 static_assert(offsetof(PndfKernelArgs, stream) == 32 && offsetof(PndfKernelArgs, B) == 56 &&
               offsetof(PndfKernelArgs, steps) == 64 && offsetof(PndfKernelArgs, slope) == 72 &&
-              offsetof(PndfKernelArgs, scratch) == 80 && offsetof(PndfKernelArgs, noenc) == 92, "PndfKernelArgs layout");
+              offsetof(PndfKernelArgs, scratch) == 80 && offsetof(PndfKernelArgs, renorm) == 88 &&
+              offsetof(PndfKernelArgs, noenc) == 92 && offsetof(PndfKernelArgs, step_size) == 96 &&
+              offsetof(PndfKernelArgs, tol) == 100, "PndfKernelArgs layout");
 
 // ---- runtime-planned DFNet (pndf_generic.hip): any depth / width the reference's `dims` list can describe
 constexpr int PNDF_GEN_MAXLIN = 8;         // linear layers (n_dims 3 .. 9)
@@ -67,7 +75,12 @@ struct PndfGenericArgs {
     int kb[PNDF_GEN_MAXLIN];     // contraction blocks of the forward pass = ceil(kt / 2)
     int nb[PNDF_GEN_MAXLIN];     // contraction blocks of the backward pass = ceil(nt / 2)
     float w_inv[PNDF_GEN_MAXLIN];// 1 / s_l: the stream carries s_l W, s_l = the power of two with max |W_l| s_l in [2^12, 2^13)
+    int renorm;                  // MODE_PROJECT_OPT's step options, as in PndfKernelArgs
+    float step_size, tol;
 };
+static_assert(offsetof(PndfGenericArgs, B) == 80 && offsetof(PndfGenericArgs, kt) == 120 &&
+              offsetof(PndfGenericArgs, renorm) == offsetof(PndfGenericArgs, w_inv) + 4 * PNDF_GEN_MAXLIN &&
+              offsetof(PndfGenericArgs, tol) == offsetof(PndfGenericArgs, renorm) + 8, "PndfGenericArgs layout");
 constexpr int PNDF_GEN_ENC_SECTION_TILES = 48 + 4 * 16;      // the encoder's 3 slots + what the ring fetches ahead (4 slots)
 
 struct PndfDenoiseArgs {

@@ -16,6 +16,7 @@
 #include "pndf_host.h"
 #include "pndf_pack.h"
 #include "pndf_generic.h"
+#include "pndf_project_opts.h"
 
 using namespace pndf;
 
@@ -515,7 +516,7 @@ extern "C" const char* pndf_kernel_name(pndf_handle h) {
 // launch instead of the handle's own, with the same arguments, grid and LDS -- pndf_internal_launch below; nullptr on every
 // product path.  The debug library decides which of its kernels matches the handle (pndf_internal_describe).
 static int launch(pndf_engine* h, int mode, const float* q, const float* gout, float* qo, float* d, int64_t B,
-                  int steps, float* dbg, void* stream, const void* instrumented = nullptr) {
+                  int steps, float* dbg, void* stream, const void* instrumented = nullptr, const pndf_project_options* popt = nullptr) {
     const bool timing = instrumented != nullptr;
     if (!h) return PNDF_ERR_BAD_ARG;
     if (!h->have_weights) return fail(h, PNDF_ERR_NO_WEIGHTS, "pndf_load_weights has not been called");
@@ -536,16 +537,20 @@ static int launch(pndf_engine* h, int mode, const float* q, const float* gout, f
             return PNDF_OK;
         }
         std::string why;
-        const int grc = pndf_generic_launch(h->generic, mode, q, gout, qo, d, B, steps, stream, why);
+        const int grc = pndf_generic_launch(h->generic, mode, q, gout, qo, d, B, steps, stream, why, popt);
         return grc == PNDF_OK ? PNDF_OK : fail(h, grc, why);
     }
     a.q_in = q; a.q_out = qo; a.d_out = d; a.grad_out = gout;
     a.stream = h->d_stream; a.bias = h->d_bias; a.dbg = dbg;
-    a.B = B; a.steps = steps; a.mode = mode;
+    // pndf_project_ex: the options' own mode only when one of them differs from its default (else the plain loop, bit for bit)
+    const bool plain = !popt || mode != MODE_PROJECT || pndf_project_options_plain(*popt);
+    a.B = B; a.steps = steps; a.mode = plain ? mode : MODE_PROJECT_OPT;
+    a.renorm = plain ? 0 : popt->renorm;
+    a.step_size = plain ? 1.0f : popt->step_size;
+    a.tol = plain ? 0.0f : popt->tol;
     a.slope = (h->cfg.act == PNDF_ACT_LRELU) ? 0.01f : 0.0f;   // nn.LeakyReLU() default slope, net_modules.py:31
     a.beta = h->cfg.beta;
     a.scratch = nullptr;
-    a.reserved0 = 0;
     a.noenc = (h->cfg.dims[0] == NOENC_IN) ? 1 : 0;
     DeviceGuard guard(h->device);
     if (!guard.ok) return fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
@@ -618,6 +623,22 @@ extern "C" int pndf_project(pndf_handle h, const float* q_in, float* q_out, floa
                             void* stream) {
     PndfRange range("pndf_project");
     return launch(h, MODE_PROJECT, q_in, nullptr, q_out, d_last, B, steps, nullptr, stream);
+}
+
+extern "C" void pndf_default_project_options(pndf_project_options* opt) {
+    if (!opt) return;
+    pndf_project_options def;
+    (void)pndf_check_project_options(nullptr, def);
+    *opt = def;
+}
+
+extern "C" int pndf_project_ex(pndf_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps,
+                               const pndf_project_options* opt, void* stream) {
+    PndfRange range("pndf_project_ex");
+    if (!h) return PNDF_ERR_BAD_ARG;
+    pndf_project_options o;
+    if (const char* why = pndf_check_project_options(opt, o)) return fail(h, PNDF_ERR_BAD_ARG, why);
+    return launch(h, MODE_PROJECT, q_in, nullptr, q_out, d_last, B, steps, nullptr, stream, nullptr, &o);
 }
 
 // ---- hooks for the debug library (libposendf_amd_debug.so; include/posendf_amd_debug.h).  Not declared in any installed header and

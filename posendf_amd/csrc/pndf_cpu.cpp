@@ -26,6 +26,7 @@
 
 #include "../../include/posendf_amd.h"
 #include "pndf_layout.h"
+#include "pndf_project_opts.h"
 
 using namespace pndf;
 
@@ -387,6 +388,53 @@ extern "C" int pndf_project_cpu(pndf_cpu_handle h, const float* q_in, float* q_o
                     volatile float prod = dd[p] * dqb[p * NQ + i];      // two roundings, as the reference evaluates q - d * grad
                     qb[p * NQ + i] = qb[p * NQ + i] - prod;
                 }
+        }
+        memcpy(q_out + p0 * NQ, qb, sizeof(float) * nb * NQ);
+        if (d_last) memcpy(d_last + p0, dd, sizeof(float) * nb);
+    });
+    });
+}
+
+// One step of pndf_project_ex on the host: the statement sequence of pndf_device.h's project_step, every operation rounded to fp32
+// on its own (no contraction), so that the two agree bit for bit on equal d and grad.
+static void project_step_cpu(float* q, const float* dq, float d, const pndf_project_options& o) {
+#pragma clang fp contract(off)
+    if (o.tol > 0.f && d < o.tol) return;
+    for (int j = 0; j < NJ; ++j) {
+        float u[4];
+        for (int c = 0; c < 4; ++c) {
+            const float p = d * dq[4 * j + c];
+            const float s = o.step_size * p;
+            u[c] = q[4 * j + c] - s;
+        }
+        if (o.renorm != PNDF_RENORM_NONE) {
+            const float ss = ((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]) + u[3] * u[3];
+            const float n = sqrtf(ss);
+            const float den = (n < 1e-12f) ? 1e-12f : n;
+            for (int c = 0; c < 4; ++c) u[c] = u[c] / den;
+            if (o.renorm == PNDF_RENORM_UNIT_FLIP && u[0] < 0.f)
+                for (int c = 0; c < 4; ++c) u[c] = -u[c];
+        }
+        for (int c = 0; c < 4; ++c) q[4 * j + c] = u[c];
+    }
+}
+
+extern "C" int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps,
+                                   const pndf_project_options* opt) {
+    if (!h) return PNDF_ERR_BAD_ARG;
+    pndf_project_options o;
+    if (const char* why = pndf_check_project_options(opt, o)) return cpu_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (pndf_project_options_plain(o)) return pndf_project_cpu(h, q_in, q_out, d_last, B, steps);
+    if (int rc = check(h, q_in, B)) return rc;
+    if (steps < 0 || (B > 0 && !q_out)) return cpu_fail(h, PNDF_ERR_BAD_ARG, "negative step count or null output pointer");
+    return guarded(h, [&] {
+    parallel_blocks(B, [&](int64_t p0, int nb, Scratch& S) {
+        float qb[PB * NQ], dqb[PB * NQ], dd[PB];
+        memcpy(qb, q_in + p0 * NQ, sizeof(float) * nb * NQ);
+        for (int p = 0; p < nb; ++p) dd[p] = 0.f;
+        for (int s = 0; s < steps; ++s) {
+            forward_grad_block(*h, qb, nb, nullptr, dd, dqb, true, S);
+            for (int p = 0; p < nb; ++p) project_step_cpu(qb + p * NQ, dqb + p * NQ, dd[p], o);
         }
         memcpy(q_out + p0 * NQ, qb, sizeof(float) * nb * NQ);
         if (d_last) memcpy(d_last + p0, dd, sizeof(float) * nb);

@@ -24,5 +24,5 @@ void pndf_generic_destroy(PndfGeneric* g);
 int pndf_generic_load(PndfGeneric* g, const float* const* tensors, const int64_t* numel, int n_tensors, std::string& err);
 // mode: MODE_FORWARD / MODE_FORWARD_GRAD / MODE_PROJECT (pndf_args.h); enqueues ONE kernel on `stream`
 int pndf_generic_launch(PndfGeneric* g, int mode, const float* q, const float* gout, float* qo, float* d, int64_t B, int steps,
-                        void* stream, std::string& err);
+                        void* stream, std::string& err, const pndf_project_options* popt = nullptr);      // popt: validated, or null = the plain step
 const char* pndf_generic_kernel_name(const PndfGeneric* g);

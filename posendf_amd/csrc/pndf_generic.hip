@@ -40,6 +40,7 @@
 #include "pndf_generic.h"
 #include "pndf_host.h"
 #include "pndf_pack.h"
+#include "pndf_project_opts.h"
 
 namespace {
 
@@ -667,6 +668,7 @@ __device__ __forceinline__ void pndf_generic_body(const PndfGenericArgs& args) {
     ring.st_wait = ring.st_bar = 0;
     ring.st_n = 0;
     for (int i = tid; i < BIAS_FLOATS / 4; i += WG_THREADS) ((f32x4*)lds_bias)[i] = ((const f32x4*)args.bias)[i];
+    stage_project_options(lds_bias, args, tid);
 
     const long long nblocks = (args.B + WG_POSES - 1) / WG_POSES;
     for (long long blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
@@ -685,7 +687,7 @@ __device__ __forceinline__ void pndf_generic_body(const PndfGenericArgs& args) {
         ring_wait_dma();
         __syncthreads();
 
-        const int nsteps = (args.mode == MODE_PROJECT) ? args.steps : 1;
+        const int nsteps = (args.mode >= MODE_PROJECT) ? args.steps : 1;
         float dval = 0.f;
         for (int step = 0; step < nsteps; ++step) {
             if (step) ring.fetch_off -= (uint32_t)args.w_slots * SLOT_BYTES;      // the fetch pointer has run one step's length (ring_next_step)
@@ -851,13 +853,15 @@ __device__ __forceinline__ void pndf_generic_body(const PndfGenericArgs& args) {
                 for (int j = g; j < NJ; j += 4) {
                     const f32x4 qv = *(const f32x4*)(my_q + 4 * j);
                     const f32x4 gv = *(const f32x4*)(my_gn + 4 * j);
-                    f32x4 o;
+                    f32x4 o, dqv;
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
                         const float dq = gv[c] / denom[c] - qv[c] * kk[c];
                         const float dqs = dq * gscale;
-                        o[c] = (args.mode == MODE_PROJECT) ? project_update(qv[c], dval, dqs) : dqs;
+                        o[c] = (args.mode >= MODE_PROJECT) ? project_update(qv[c], dval, dqs) : dqs;
+                        dqv[c] = dqs;
                     }
+                    if (args.mode == MODE_PROJECT_OPT) o = project_step(qv, dqv, dval, lds_bias);      // step options (wave-uniform branch)
                     *(f32x4*)(my_q + 4 * j) = o;
                 }
             }
@@ -1183,12 +1187,17 @@ const char* pndf_generic_kernel_name(const PndfGeneric* g) {
 }
 
 int pndf_generic_launch(PndfGeneric* g, int mode, const float* q, const float* gout, float* qo, float* d, int64_t B, int steps,
-                        void* stream, std::string& err) {
+                        void* stream, std::string& err, const pndf_project_options* popt) {
     if (!g->have_weights) { err = "pndf_load_weights has not been called"; return PNDF_ERR_NO_WEIGHTS; }
     PndfGenericArgs a = g->plan;
     a.q_in = q; a.q_out = qo; a.d_out = d; a.grad_out = gout;
     a.enc_stream = g->d_enc; a.bias = g->d_bias; a.wfwd = nullptr; a.wbwd = nullptr; a.lbias = g->d_lb; a.scratch = g->d_scratch;
-    a.B = B; a.steps = steps; a.mode = mode;
+    // pndf_project_ex: the options' own mode only when one of them differs from its default (else the plain loop, bit for bit)
+    const bool plain = !popt || mode != MODE_PROJECT || pndf_project_options_plain(*popt);
+    a.B = B; a.steps = steps; a.mode = plain ? mode : MODE_PROJECT_OPT;
+    a.renorm = plain ? 0 : popt->renorm;
+    a.step_size = plain ? 1.0f : popt->step_size;
+    a.tol = plain ? 0.0f : popt->tol;
     a.slope = (g->cfg.act == PNDF_ACT_LRELU) ? 0.01f : 0.0f;      // nn.LeakyReLU() default slope, net_modules.py:31
     a.beta = g->cfg.beta;
     a.enc_slope = (gen_enc_act(g->cfg) == PNDF_ACT_LRELU) ? 0.01f : 0.0f;

@@ -260,6 +260,7 @@ __device__ __forceinline__ void pndf_fused_body(const PndfKernelArgs& args) {
     // ---- stage the biases in LDS once (coalesced)
     for (int i = tid; i < BIAS_FLOATS / 4; i += WG_THREADS)
         ((f32x4*)lds_bias)[i] = ((const f32x4*)args.bias)[i];
+    stage_project_options(lds_bias, args, tid);
 
     // A workgroup owns the 64-pose blocks blockIdx.x, blockIdx.x + gridDim.x, ...: the relu-family kernels are launched
     // with one workgroup per block, the softplus kernels with at most one workgroup per CU so that the derivative scratch
@@ -283,7 +284,7 @@ __device__ __forceinline__ void pndf_fused_body(const PndfKernelArgs& args) {
     ring_wait_dma();
     __syncthreads();
 
-    const int nsteps = (args.mode == MODE_PROJECT) ? args.steps : 1;
+    const int nsteps = (args.mode >= MODE_PROJECT) ? args.steps : 1;
     float dval = 0.f;
     RegionClock rc;
     if constexpr (TIMING) {
@@ -454,14 +455,16 @@ __device__ __forceinline__ void pndf_fused_body(const PndfKernelArgs& args) {
             for (int j = g; j < NJ; j += 4) {
                 const f32x4 qv = *(const f32x4*)(my_q + 4 * j);
                 const f32x4 gv = *(const f32x4*)(my_gn + 4 * j);
-                f32x4 o;
+                f32x4 o, dqv;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     const float dq = gv[c] / denom[c] - qv[c] * kk[c];
                     if (DBG && dbg && step == 0) dbg[(size_t)(DBG_DQ + 4 * j + c) * WG_THREADS + tid] = dq;
                     // q <- q - d * grad  (experiments/sample_poses.py:74: product rounded, then subtracted)
-                    o[c] = (args.mode == MODE_PROJECT) ? project_update(qv[c], dval, dq) : dq;
+                    o[c] = (args.mode >= MODE_PROJECT) ? project_update(qv[c], dval, dq) : dq;
+                    dqv[c] = dq;
                 }
+                if (args.mode == MODE_PROJECT_OPT) o = project_step(qv, dqv, dval, lds_bias);      // step options (wave-uniform branch)
                 *(f32x4*)(my_q + 4 * j) = o;
             }
         }

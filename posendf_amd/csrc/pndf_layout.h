@@ -116,6 +116,10 @@ constexpr int SCALE_OFF = ENCB_OFF + 21 * 32;   // split stream: 1 / (weight sca
 //   [6..8] ||W_l^T||_inf (largest absolute column sum), l = 5, 3, 1 [9..11] unused
 constexpr int NORM_OFF = SCALE_OFF + 8;
 constexpr int BIAS_FLOATS = NORM_OFF + 12;
+// the LDS copy of the block only: MODE_PROJECT_OPT's step options (step size, tolerance, renorm mode as bits) in the three unused
+// floats, written once per launch by the thread that copied their vector (pndf_device.h stage_project_options)
+constexpr int POPT_OFF = NORM_OFF + 9;
+static_assert(POPT_OFF / 4 == (POPT_OFF + 2) / 4 && POPT_OFF + 3 == BIAS_FLOATS, "the options sit in one 16-byte vector of the block");
 
 constexpr int PARENT[NJ] = {-1, -1, -1, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19};
 constexpr int enc_in(int j) { return PARENT[j] < 0 ? 4 : 10; }

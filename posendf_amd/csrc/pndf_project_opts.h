@@ -1,0 +1,28 @@
+// Validation of pndf_project_options (include/posendf_amd.h), shared by pndf_project_ex (pndf_capi.hip) and its host twin
+// pndf_project_ex_cpu (pndf_cpu.cpp): the two refuse the same structs with the same text.
+#pragma once
+#include <math.h>
+
+#include "../../include/posendf_amd.h"
+
+// null = the defaults.  Returns nullptr and fills `out`, or the reason the struct is refused.
+inline const char* pndf_check_project_options(const pndf_project_options* opt, pndf_project_options& out) {
+    out.struct_size = (uint32_t)sizeof(pndf_project_options);
+    out.step_size = 1.0f;
+    out.renorm = PNDF_RENORM_NONE;
+    out.tol = 0.0f;
+    if (!opt) return nullptr;
+    if (opt->struct_size != sizeof(pndf_project_options))
+        return "pndf_project_options.struct_size is not sizeof(pndf_project_options): fill the struct with pndf_default_project_options";
+    if (!isfinite(opt->step_size) || !(opt->step_size > 0.0f)) return "pndf_project_options.step_size must be finite and positive";
+    if (!(opt->tol >= 0.0f)) return "pndf_project_options.tol must be zero or positive (and not NaN)";
+    if (opt->renorm != PNDF_RENORM_NONE && opt->renorm != PNDF_RENORM_UNIT && opt->renorm != PNDF_RENORM_UNIT_FLIP)
+        return "pndf_project_options.renorm is not a pndf_renorm mode";
+    out = *opt;
+    return nullptr;
+}
+
+// the defaults give the plain step of pndf_project, whatever else the struct says
+inline bool pndf_project_options_plain(const pndf_project_options& o) {
+    return o.step_size == 1.0f && o.renorm == PNDF_RENORM_NONE && !(o.tol > 0.0f);
+}

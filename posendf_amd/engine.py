@@ -16,11 +16,17 @@ _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "lib
 
 ACT_CODES = {"relu": 0, "lrelu": 1, "softplus": 2}
 PRECISION_CODES = {"fp32": 0, "f16x3": 1, "f16": 2, "bf16": 3}
+RENORM_CODES = {"none": 0, "unit": 1, "unit_flip": 2}      # PNDF_RENORM_*
 
 
 class PndfConfig(ctypes.Structure):
     _fields_ = [("act", c_int32), ("beta", c_float), ("num_joints", c_int32), ("n_dims", c_int32),
                 ("dims", c_int32 * 16), ("parent", c_int32 * 32), ("precision", c_int32), ("enc_act", c_int32), ("enc_beta", c_float)]
+
+
+class ProjectOptions(ctypes.Structure):
+    """pndf_project_options: step size, renormalisation and stop tolerance of pndf_project_ex"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("step_size", c_float), ("renorm", c_int32), ("tol", c_float)]
 
 
 class DenoiseWeights(ctypes.Structure):
@@ -104,6 +110,9 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     lib.pndf_forward.argtypes = [H, c_void_p, c_void_p, c_int64, c_void_p]
     lib.pndf_forward_grad.argtypes = [H, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
     lib.pndf_project.argtypes = [H, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]
+    lib.pndf_default_project_options.argtypes = [POINTER(ProjectOptions)]
+    lib.pndf_default_project_options.restype = None
+    lib.pndf_project_ex.argtypes = [H, c_void_p, c_void_p, c_void_p, c_int64, c_int, POINTER(ProjectOptions), c_void_p]
     lib.pndf_packed_sizes.argtypes = [POINTER(c_int64)] * 2
     lib.pndf_packed_sizes.restype = None
     lib.pndf_pack_host.argtypes = [POINTER(c_void_p), POINTER(c_int64), c_int, c_void_p, c_void_p]
@@ -189,10 +198,11 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     lib.pndf_forward_cpu.argtypes = [CH, c_void_p, c_void_p, c_int64]
     lib.pndf_forward_grad_cpu.argtypes = [CH, c_void_p, c_void_p, c_void_p, c_void_p, c_int64]
     lib.pndf_project_cpu.argtypes = [CH, c_void_p, c_void_p, c_void_p, c_int64, c_int]
+    lib.pndf_project_ex_cpu.argtypes = [CH, c_void_p, c_void_p, c_void_p, c_int64, c_int, POINTER(ProjectOptions)]
     lib.pndf_cpu_last_error.argtypes = [CH]
     lib.pndf_cpu_last_error.restype = c_char_p
     for name in ("pndf_cpu_create", "pndf_cpu_destroy", "pndf_cpu_load_weights", "pndf_forward_cpu", "pndf_forward_grad_cpu",
-                 "pndf_project_cpu"):
+                 "pndf_project_cpu", "pndf_project_ex_cpu"):
         getattr(lib, name).restype = c_int
     lib.pndf_last_error.argtypes = [H]
     lib.pndf_last_error.restype = c_char_p
@@ -201,7 +211,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     lib.pndf_kernel_name.argtypes = [H]
     lib.pndf_kernel_name.restype = c_char_p
     for name in ("pndf_create", "pndf_destroy", "pndf_load_weights", "pndf_forward", "pndf_forward_grad",
-                 "pndf_project", "pndf_pack_host", "pndf_pack_host_split"):
+                 "pndf_project", "pndf_project_ex", "pndf_pack_host", "pndf_pack_host_split"):
         getattr(lib, name).restype = c_int
     return lib
 
@@ -231,7 +241,7 @@ def experiment_word(lib=None) -> int:
 
 # include/posendf_amd.h, the public header
 EXPORTS = ("pndf_default_config", "pndf_create", "pndf_destroy", "pndf_load_weights", "pndf_forward",
-           "pndf_forward_grad", "pndf_project", "pndf_experiment_word",
+           "pndf_forward_grad", "pndf_project", "pndf_project_ex", "pndf_default_project_options", "pndf_experiment_word",
            "pndf_packed_sizes", "pndf_pack_host", "pndf_pack_host_split", "pndf_aa2quat", "pndf_denoise_update", "pndf_denoise_update_body", "pndf_denoise_update_w", "pndf_lbs_terms_grad_w", "pndf_quat_topk",
            "pndf_lbs_create", "pndf_lbs_destroy", "pndf_lbs_set_precision", "pndf_lbs_precision", "pndf_lbs_num_joints", "pndf_lbs_num_vertices", "pndf_lbs_workspace_floats",
            "pndf_lbs_forward", "pndf_lbs_terms_grad", "pndf_lbs_backward", "pndf_lbs_packed_floats", "pndf_lbs_pack_host", "pndf_lbs_packed_split_bytes", "pndf_lbs_pack_split_host",
@@ -240,7 +250,7 @@ EXPORTS = ("pndf_default_config", "pndf_create", "pndf_destroy", "pndf_load_weig
            "pndf_train_last_error", "pndf_adam_step", "pndf_train_batch",
            "pndf_knn_create", "pndf_knn_destroy", "pndf_knn_size", "pndf_knn_workspace_bytes", "pndf_knn_search", "pndf_knn_last_error",
            "pndf_cpu_create", "pndf_cpu_destroy", "pndf_cpu_load_weights", "pndf_forward_cpu", "pndf_forward_grad_cpu", "pndf_project_cpu",
-           "pndf_cpu_last_error")
+           "pndf_project_ex_cpu", "pndf_cpu_last_error")
 
 
 def state_dict_order(encoder: bool = True, n_lin: int = 7):
@@ -275,6 +285,21 @@ def pack_host(sd_np, lib=None, split=False):
     if rc != 0:
         raise PndfError(f"pndf_pack_host failed ({rc})")
     return stream, bias
+
+
+def project_options(lib, step_size=1.0, renorm="none", tol=0.0):
+    """pndf_project_options for the step options of `project` (include/posendf_amd.h), or None when all three are the defaults
+    (the caller then uses the plain entry point).  `renorm`: "none" / None, "unit", "unit_flip".  The values are checked by the
+    library (PNDF_ERR_BAD_ARG), only the mode's name here."""
+    renorm = "none" if renorm is None else renorm
+    if renorm not in RENORM_CODES:
+        raise PndfError(f"unknown renormalisation {renorm!r} (None, 'unit', 'unit_flip')")
+    if float(step_size) == 1.0 and renorm == "none" and float(tol) == 0.0:
+        return None
+    opt = ProjectOptions()
+    lib.pndf_default_project_options(ctypes.byref(opt))
+    opt.step_size, opt.renorm, opt.tol = float(step_size), RENORM_CODES[renorm], float(tol)
+    return opt
 
 
 def _set_encoder_act(cfg, act, beta, enc_act, enc_beta):
@@ -345,9 +370,15 @@ class Engine:
         self._check(self.lib.pndf_forward_grad(self.handle, q_ptr, gout_ptr, d_ptr, dq_ptr, B, stream),
                     "pndf_forward_grad")
 
-    def project(self, q_in_ptr, q_out_ptr, d_ptr, B, steps, stream=0):
-        self._check(self.lib.pndf_project(self.handle, q_in_ptr, q_out_ptr, d_ptr, B, int(steps), stream),
-                    "pndf_project")
+    def project(self, q_in_ptr, q_out_ptr, d_ptr, B, steps, stream=0, *, step_size=1.0, renorm="none", tol=0.0):
+        """pndf_project; with a step option that differs from its default, pndf_project_ex (include/posendf_amd.h)"""
+        opt = project_options(self.lib, step_size, renorm, tol)
+        if opt is None:
+            self._check(self.lib.pndf_project(self.handle, q_in_ptr, q_out_ptr, d_ptr, B, int(steps), stream),
+                        "pndf_project")
+        else:
+            self._check(self.lib.pndf_project_ex(self.handle, q_in_ptr, q_out_ptr, d_ptr, B, int(steps), ctypes.byref(opt), stream),
+                        "pndf_project_ex")
 
     def debug_forward_grad(self, q_ptr, d_ptr, dq_ptr, B, dump_ptr, stream=0):
         self._check(self.lib.pndf_debug_forward_grad(self.handle, q_ptr, d_ptr, dq_ptr, B, dump_ptr, stream),
@@ -602,8 +633,13 @@ class CpuEngine:
     def forward_grad(self, q_ptr, gout_ptr, d_ptr, dq_ptr, B, stream=0):
         self._check(self.lib.pndf_forward_grad_cpu(self.handle, q_ptr, gout_ptr, d_ptr, dq_ptr, B), "pndf_forward_grad_cpu")
 
-    def project(self, q_in_ptr, q_out_ptr, d_ptr, B, steps, stream=0):
-        self._check(self.lib.pndf_project_cpu(self.handle, q_in_ptr, q_out_ptr, d_ptr, B, int(steps)), "pndf_project_cpu")
+    def project(self, q_in_ptr, q_out_ptr, d_ptr, B, steps, stream=0, *, step_size=1.0, renorm="none", tol=0.0):
+        opt = project_options(self.lib, step_size, renorm, tol)
+        if opt is None:
+            self._check(self.lib.pndf_project_cpu(self.handle, q_in_ptr, q_out_ptr, d_ptr, B, int(steps)), "pndf_project_cpu")
+        else:
+            self._check(self.lib.pndf_project_ex_cpu(self.handle, q_in_ptr, q_out_ptr, d_ptr, B, int(steps), ctypes.byref(opt)),
+                        "pndf_project_ex_cpu")
 
     def close(self):
         if getattr(self, "handle", None):

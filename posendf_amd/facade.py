@@ -223,13 +223,19 @@ class PoseNDF(nn.Module):
 
     # ---- added surface (north_star: `.project` on the model) -------------------------------------
     @torch.no_grad()
-    def project(self, noisy_poses, steps=100, return_dist=True):
+    def project(self, noisy_poses, steps=100, return_dist=True, *, step_size=1.0, renormalize=None, tol=0.0):
         """experiments/sample_poses.py:67-74 as ONE persistent kernel: `steps` times
         q <- q - dist_pred(q) * d dist_pred / d q.  Returns (poses [B,21,4], dist [B,1] of the last
-        iteration)."""
+        iteration).
+
+        Step options (keyword only; the defaults are the reference's bare loop, bit for bit): `step_size` alpha scales the step,
+        q <- q - alpha (d grad); `renormalize` = "unit" divides every joint quaternion of an updated pose by its norm (clamped at
+        1e-12 like F.normalize), "unit_flip" also negates those with a negative real part; `tol` > 0 leaves a pose with
+        dist_pred < tol unchanged.  The input is used as given; `dist` stays the distance evaluated before the last update."""
         q = noisy_poses.to(device=self.device).reshape(-1, 21, 4).float().contiguous()
         out = torch.empty_like(q)
         d = torch.empty(q.shape[0], device=q.device, dtype=torch.float32)
         eng = self._engine_for(q.device)
-        eng.project(q.data_ptr(), out.data_ptr(), d.data_ptr(), q.shape[0], int(steps), _stream_of(q.device))
+        eng.project(q.data_ptr(), out.data_ptr(), d.data_ptr(), q.shape[0], int(steps), _stream_of(q.device),
+                    step_size=step_size, renorm=renormalize, tol=tol)
         return (out, d.view(-1, 1)) if return_dist else out

@@ -44,21 +44,23 @@ class SamplePose:
         return aa.view(-1, 69), out.vertices.detach(), out.Jtr.detach()
 
     @torch.no_grad()
-    def project(self, noisy_poses, steps=10):
-        """:57-83 with the ten iterations of :70 as `steps`.  Returns the projected poses [B,21,4], dist_pred of the last
+    def project(self, noisy_poses, steps=10, *, step_size=1.0, renormalize=None, tol=0.0):
+        """:57-83 with the ten iterations of :70 as `steps`; `step_size` / `renormalize` / `tol` are PoseNDF.project's step options
+        (renormalize="unit" gives the unit quaternions that `quaternion_to_axis_angle` and the body model expect).  Returns the projected poses [B,21,4], dist_pred of the last
         iteration [B,1] and, with a body model, the meshes before / after ({'pose_init', 'vertices_init', 'pose', 'vertices',
         'joints'})."""
         noisy_poses = noisy_poses.to(self.device)
         meshes = {}
         if self.body_model is not None:
             meshes["pose_init"], meshes["vertices_init"], _ = self._mesh(noisy_poses)
-        poses, dist = self.pose_prior.project(noisy_poses, steps=steps)
+        poses, dist = self.pose_prior.project(noisy_poses, steps=steps, step_size=step_size, renormalize=renormalize, tol=tol)
         if self.body_model is not None:
             meshes["pose"], meshes["vertices"], meshes["joints"] = self._mesh(poses)
         return poses, dist, meshes
 
 
-def sample_pose(net, batch_size=10, steps=10, body_model=None, device="cuda:0", generator=None):
+def sample_pose(net, batch_size=10, steps=10, body_model=None, device="cuda:0", generator=None, *, step_size=1.0, renormalize=None,
+                tol=0.0):
     """experiments/sample_poses.py:86-105 after the checkpoint is loaded: draw random poses, project them."""
     sampler = SamplePose(net, body_model=body_model, device=device)
-    return sampler.project(random_poses(batch_size, device, generator), steps=steps)
+    return sampler.project(random_poses(batch_size, device, generator), steps=steps, step_size=step_size, renormalize=renormalize, tol=tol)
