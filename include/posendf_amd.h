@@ -325,6 +325,32 @@ int pndf_train_batch(const float* pose_db, const float* dist_db, const float* ma
                      int32_t F, int32_t Fm, int32_t k, int32_t items, int32_t num_pts, int32_t flip, float* q, float* dist_gt,
                      float* q_man, void* stream);
 
+/* ---- fitting poses to 2D keypoints through a perspective camera (experiments/image_fitting.py:67-92, camera
+ * experiments/exp_utils.py:119-143; robustifier and confidence weighting of SMPLify-X, which that script copies).  Stateless
+ * helpers as the two above: no handle, DEVICE pointers, enqueued on `stream`, nothing allocated, no synchronisation, no atomics,
+ * the same inputs give the same bits; status codes only.
+ * SMPL's global orientation r is a rotation about the rest root joint J0 = joints[n,0] and is applied here, to joints computed
+ * at zero global orientation (J0 is a constant of the pose: no gradient flows into row 0 through its role as pivot):
+ *   p = Rc (R(r) (x - J0) + J0) + t,   u = fx p_x / p_z + cx,   v = fy p_y / p_z + cy       (p_z <= 0: inf / NaN propagate)
+ *   E_n = sum_j (w_j c_nj)^2 [rho(kx_nj - u_nj) + rho(ky_nj - v_nj)],   D_n = (t_z - depth_target)^2
+ * rho(e) = e^2 for rho == 0, else rho^2 e^2 / (e^2 + rho^2) per component; c_nj = the keypoint's confidence, 1 when
+ * use_conf == 0.  A joint with w_j c_nj == 0 is SKIPPED: exactly 0 in every output whatever its keypoint holds (NaN, inf).
+ * R(r): smplx batch_rodrigues including its 1e-8, the convention of the pndf_lbs_* calls. */
+typedef struct pndf_camera { float fx, fy, cx, cy; float R[9]; } pndf_camera;             /* R = Rc, row-major */
+typedef struct pndf_keypoint_opts { float data_coef, rho, depth_coef, depth_target; int32_t use_conf, reserved; } pndf_keypoint_opts;
+/* joints [N,J,3] at zero global orientation (pndf_lbs_forward), orient / transl [N,3], keypoints [N,J,3] = (x, y, conf),
+ * joint_weight [J] (NULL = ones).  Outputs, each may be NULL: terms [N,2] = (E_n, D_n) unweighted; g_joints [N,J,3] (rows of
+ * skipped joints are written as zeros), g_orient [N,3], g_transl [N,3] = d(data_coef sum_n E_n + depth_coef sum_n D_n)/d(.).
+ * `cam` and `opt` are HOST structs, read before the call returns.  N == 0: no-op; N < 0, J < 1, a null required pointer, a null
+ * cam / opt or rho < 0: PNDF_ERR_BAD_ARG. */
+int pndf_keypoint_terms_grad(const float* joints, const float* orient, const float* transl, const float* keypoints,
+                             const float* joint_weight, int64_t N, int32_t J, const pndf_camera* cam,
+                             const pndf_keypoint_opts* opt, float* terms, float* g_joints, float* g_orient, float* g_transl,
+                             void* stream);
+/* the forward alone: posed [N,J,3] camera-space points p and/or uv [N,J,2] (either may be NULL) */
+int pndf_keypoint_project(const float* joints, const float* orient, const float* transl, int64_t N, int32_t J,
+                          const pndf_camera* cam, float* posed, float* uv, void* stream);
+
 /* ---- quaternion pose distance + k nearest candidates (data/dist_utils.py:9-50, classes euc / geo; caller
  * data/prepare_traindata.py:159).  noise [B,21,4], valid [B,K,21,4] (device, 16-byte aligned);
  * metric 0 = geo: sum_j w_j (1 - |<q_valid_j, q_noise_j>|), 1 = euc: sum_j w_j ||q_noise_j - q_valid_j||;

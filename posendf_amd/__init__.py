@@ -19,7 +19,11 @@ def __getattr__(name):   # torch is imported lazily so that numpy-only users (or
     if name == "BodyModel":
         from .body_model import BodyModel
         return BodyModel
+    if name in ("ImageFit", "PerspectiveCamera", "keypoint_term"):
+        from . import image_fitting
+        return getattr(image_fitting, name)
     raise AttributeError(name)
 
 
-__all__ = ["PoseNDF", "gradient", "BodyModel", "PoseIndex", "Trainer", "PoseDataset", "amass_config", "load_config", "synth"]
+__all__ = ["PoseNDF", "gradient", "BodyModel", "PoseIndex", "Trainer", "PoseDataset", "ImageFit", "PerspectiveCamera", "keypoint_term",
+           "amass_config", "load_config", "synth"]

@@ -34,6 +34,17 @@ class DenoiseWeights(ctypes.Structure):
     _fields_ = [("prior_coef", c_float), ("prior_power", c_int32), ("temp_coef", c_float), ("data_coef", c_float)]
 
 
+class Camera(ctypes.Structure):
+    """pndf_camera: focal lengths, centre and the fixed rotation Rc (row-major) of the perspective camera"""
+    _fields_ = [("fx", c_float), ("fy", c_float), ("cx", c_float), ("cy", c_float), ("R", c_float * 9)]
+
+
+class KeypointOpts(ctypes.Structure):
+    """pndf_keypoint_opts: the weights of the keypoint and depth terms, the robustifier's rho, confidence weighting on / off"""
+    _fields_ = [("data_coef", c_float), ("rho", c_float), ("depth_coef", c_float), ("depth_target", c_float),
+                ("use_conf", c_int32), ("reserved", c_int32)]
+
+
 class PndfError(RuntimeError):
     pass
 
@@ -178,6 +189,10 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     lib.pndf_adam_step.restype = c_int
     lib.pndf_train_batch.argtypes = [c_void_p] * 8 + [c_int32] * 6 + [c_void_p] * 4
     lib.pndf_train_batch.restype = c_int
+    lib.pndf_keypoint_terms_grad.argtypes = [c_void_p] * 5 + [c_int64, c_int32, POINTER(Camera), POINTER(KeypointOpts)] + [c_void_p] * 5
+    lib.pndf_keypoint_terms_grad.restype = c_int
+    lib.pndf_keypoint_project.argtypes = [c_void_p] * 3 + [c_int64, c_int32, POINTER(Camera)] + [c_void_p] * 3
+    lib.pndf_keypoint_project.restype = c_int
     KH = c_void_p
     lib.pndf_knn_create.argtypes = [POINTER(KH), c_void_p, c_int64, c_int32, c_void_p, c_void_p]
     lib.pndf_knn_create.restype = c_int
@@ -247,7 +262,7 @@ EXPORTS = ("pndf_default_config", "pndf_create", "pndf_destroy", "pndf_load_weig
            "pndf_lbs_forward", "pndf_lbs_terms_grad", "pndf_lbs_backward", "pndf_lbs_packed_floats", "pndf_lbs_pack_host", "pndf_lbs_packed_split_bytes", "pndf_lbs_pack_split_host",
            "pndf_lbs_last_error", "pndf_last_error", "pndf_version", "pndf_kernel_name",
            "pndf_train_create", "pndf_train_destroy", "pndf_train_workspace_floats", "pndf_train_forward", "pndf_train_backward",
-           "pndf_train_last_error", "pndf_adam_step", "pndf_train_batch",
+           "pndf_train_last_error", "pndf_adam_step", "pndf_train_batch", "pndf_keypoint_terms_grad", "pndf_keypoint_project",
            "pndf_knn_create", "pndf_knn_destroy", "pndf_knn_size", "pndf_knn_workspace_bytes", "pndf_knn_search", "pndf_knn_last_error",
            "pndf_cpu_create", "pndf_cpu_destroy", "pndf_cpu_load_weights", "pndf_forward_cpu", "pndf_forward_grad_cpu", "pndf_project_cpu",
            "pndf_project_ex_cpu", "pndf_cpu_last_error")
