@@ -22,14 +22,13 @@ stream, as with the softplus engine.
 """
 from __future__ import annotations
 
-import ctypes
 from types import SimpleNamespace
 
 import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
-from .engine import PndfError, load_library
+from .engine import PndfError, _Handle, load_library, stream_handle
 
 _KEYS = ("v_template", "shapedirs", "posedirs", "J_regressor", "parents", "lbs_weights")
 
@@ -68,7 +67,8 @@ class _Lbs(torch.autograd.Function):
         return g.reshape(ctx.in_shape).to(ctx.in_dtype), None
 
 
-class BodyModel(torch.nn.Module):
+class BodyModel(_Handle, torch.nn.Module):
+    _destroy, _last_error = "pndf_lbs_destroy", "pndf_lbs_last_error"
     PRECISIONS = {"fp32": 0, "f16x3": 1}      # PNDF_LBS_FP32 / PNDF_LBS_F16X3 (include/posendf_amd.h)
 
     def __init__(self, params, num_betas=10, batch_size=1, model_type="smpl", device="cuda:0", betas=None,
@@ -110,15 +110,9 @@ class BodyModel(torch.nn.Module):
         if jr.shape != (24, V) or w.shape != (V, 24) or par.shape != (24,):
             raise PndfError("J_regressor [24,V], lbs_weights [V,24], parents [24] expected")
         self.lib = load_library()
-        self.handle = ctypes.c_void_p()
         sd_c = np.ascontiguousarray(sd)
-        rc = self.lib.pndf_lbs_create(ctypes.byref(self.handle), V, nb, vt.ctypes.data, sd_c.ctypes.data, b.ctypes.data,
-                                      pd.ctypes.data, jr.ctypes.data, par.ctypes.data, w.ctypes.data, ex.ctypes.data, len(ex),
-                                      self.device.index or 0)
-        if rc != 0:
-            msg = self.lib.pndf_lbs_last_error(None).decode()
-            self.handle = None
-            raise PndfError(f"pndf_lbs_create failed ({rc}): {msg}")
+        self._create("pndf_lbs_create", V, nb, vt.ctypes.data, sd_c.ctypes.data, b.ctypes.data, pd.ctypes.data, jr.ctypes.data,
+                     par.ctypes.data, w.ctypes.data, ex.ctypes.data, len(ex), self.device.index or 0)
         self._call("pndf_lbs_set_precision", self.PRECISIONS[precision])
         self.precision = precision
         self.num_vertices = V
@@ -145,8 +139,7 @@ class BodyModel(torch.nn.Module):
                         parents=parents, lbs_weights=lbs_weights), **kw)
 
     # ---- plumbing -------------------------------------------------------------------------------
-    def _stream(self, device):
-        return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    _stream = staticmethod(stream_handle)
 
     def _workspace(self, S, T, device):
         """scratch of the C ABI calls (caller-owned there): one cached buffer per shape class, grown on demand"""
@@ -169,20 +162,7 @@ class BodyModel(torch.nn.Module):
         return t.detach().to(self.device, torch.float32).contiguous()
 
     def _call(self, name, *args):
-        rc = getattr(self.lib, name)(self.handle, *args)
-        if rc != 0:
-            raise PndfError(f"{name} failed ({rc}): {self.lib.pndf_lbs_last_error(self.handle).decode()}")
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.pndf_lbs_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._check(getattr(self.lib, name)(self.handle, *args), name)
 
     # ---- reference API (body_model.py:33-52) -----------------------------------------------------
     def forward(self, root_orient=None, pose_body=None, betas=None, return_dict=False, **kwargs):

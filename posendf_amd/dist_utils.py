@@ -15,7 +15,7 @@ import ctypes
 import numpy as np
 import torch
 
-from .engine import PndfError, load_library
+from .engine import PndfError, _device_only, load_library, quat_topk, stream_handle
 
 JOINT_RANK = (7, 7, 7, 6, 6, 6, 5, 5, 5, 4, 4, 4, 4, 4, 3, 3, 3, 2, 2, 1, 1)      # dist_utils.py:17,40
 
@@ -33,6 +33,7 @@ class _QuatDist:
         self._lib = load_library()
 
     def dist_calc(self, noise_quats, valid_quat, k_faiss, k_dist=5):
+        _device_only(self.device, "pndf_quat_topk")
         noise = noise_quats.to(self.device, torch.float32).reshape(-1, 21, 4).contiguous()
         B = noise.shape[0]
         valid = valid_quat.to(self.device, torch.float32).reshape(B, -1, 21, 4).contiguous()
@@ -42,11 +43,8 @@ class _QuatDist:
         k = int(k_dist)
         vals = torch.empty(B, k, device=self.device, dtype=torch.float32)
         idx = torch.empty(B, k, device=self.device, dtype=torch.int64)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        rc = self._lib.pndf_quat_topk(noise.data_ptr(), valid.data_ptr(), B, K, self.metric, self._w, k,
-                                      vals.data_ptr(), idx.data_ptr(), stream)
-        if rc != 0:
-            raise PndfError(f"pndf_quat_topk failed ({rc}): B={B} K={K} k={k} (k <= min(K, 16), K <= ~1850)")
+        quat_topk(noise.data_ptr(), valid.data_ptr(), B, K, self.metric, self._w, k, vals.data_ptr(), idx.data_ptr(),
+                  stream_handle(self.device), self._lib)
         return vals, idx
 
 

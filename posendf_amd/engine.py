@@ -8,9 +8,18 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint, c_void_p
 
 import numpy as np
+
+# PyTorch is the plumbing for device memory and streams, so the library must share PyTorch's HIP runtime: torch is imported
+# FIRST, here, so that its bundled libamdhip64 is the one already mapped when the loader resolves the library's dependency (the
+# other order puts two HIP runtimes in the process and pndf_create then sees no device).  Without torch installed the system
+# runtime is used.
+try:
+    import torch
+except ImportError:
+    torch = None
 
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libposendf_amd.so")
 
@@ -49,6 +58,111 @@ class PndfError(RuntimeError):
     pass
 
 
+# ---- the C ABI, one table per library: name -> (restype, argtypes), in the header's order.  load_library() binds the tables, EXPORTS /
+# DEBUG_EXPORTS are their names, tests/test_cabi.py holds both against the declarations of the two headers.
+_H = c_void_p                          # every handle type, and every `void* stream`
+_P = c_void_p                          # any other address: tensor data (an int from data_ptr(), or None), a callback, an out value
+_TENSORS = [POINTER(c_void_p), POINTER(c_int64), c_int]      # tensors, numel, n_tensors (host pointers in state-dict order)
+_SIGNATURES = {      # include/posendf_amd.h
+    "pndf_default_config": (None, [POINTER(PndfConfig), c_int32, c_float]),
+    "pndf_create": (c_int, [POINTER(_H), POINTER(PndfConfig), c_int]),
+    "pndf_destroy": (c_int, [_H]),
+    "pndf_load_weights": (c_int, [_H] + _TENSORS),
+    "pndf_forward": (c_int, [_H, _P, _P, c_int64, _H]),
+    "pndf_forward_grad": (c_int, [_H, _P, _P, _P, _P, c_int64, _H]),
+    "pndf_project": (c_int, [_H, _P, _P, _P, c_int64, c_int, _H]),
+    "pndf_default_project_options": (None, [POINTER(ProjectOptions)]),
+    "pndf_project_ex": (c_int, [_H, _P, _P, _P, c_int64, c_int, POINTER(ProjectOptions), _H]),
+    # ---- host twins
+    "pndf_cpu_create": (c_int, [POINTER(_H), POINTER(PndfConfig)]),
+    "pndf_cpu_destroy": (c_int, [_H]),
+    "pndf_cpu_load_weights": (c_int, [_H] + _TENSORS),
+    "pndf_forward_cpu": (c_int, [_H, _P, _P, c_int64]),
+    "pndf_forward_grad_cpu": (c_int, [_H, _P, _P, _P, _P, c_int64]),
+    "pndf_project_cpu": (c_int, [_H, _P, _P, _P, c_int64, c_int]),
+    "pndf_project_ex_cpu": (c_int, [_H, _P, _P, _P, c_int64, c_int, POINTER(ProjectOptions)]),
+    "pndf_cpu_last_error": (c_char_p, [_H]),
+    # host-only weight packer
+    "pndf_packed_sizes": (None, [POINTER(c_int64)] * 2),
+    "pndf_pack_host": (c_int, _TENSORS + [_P, _P]),
+    "pndf_pack_host_split": (c_int, _TENSORS + [_P, _P]),
+    # ---- motion-denoise optimiser step
+    "pndf_aa2quat": (c_int, [_P, _P, c_int64, _H]),
+    "pndf_denoise_update": (c_int, [_P] * 8 + [c_int32] * 4 + [c_float, _H]),
+    "pndf_denoise_update_w": (c_int, [_P] * 9 + [c_int32, c_int32, POINTER(DenoiseWeights), c_int32, c_float, _H]),
+    "pndf_denoise_update_body": (c_int, [_P] * 9 + [c_int32] * 4 + [c_float, _H]),
+    # ---- SMPL-shaped body model
+    "pndf_lbs_create": (c_int, [POINTER(_H), c_int32, c_int32] + [_P] * 8 + [c_int32, c_int]),
+    "pndf_lbs_destroy": (c_int, [_H]),
+    "pndf_lbs_set_precision": (c_int, [_H, c_int32]),
+    "pndf_lbs_precision": (c_int32, [_H]),
+    "pndf_lbs_num_joints": (c_int32, [_H]),
+    "pndf_lbs_num_vertices": (c_int32, [_H]),
+    "pndf_lbs_workspace_floats": (c_int64, [_H, c_int32, c_int32]),
+    "pndf_lbs_forward": (c_int, [_H, _P, c_int64, _P, _P, _P, _H]),
+    "pndf_lbs_terms_grad": (c_int, [_H, _P, _P, c_int32, c_int32, c_int32, _P, _P, _H]),
+    "pndf_lbs_terms_grad_w": (c_int, [_H, _P, _P, c_int32, c_int32, c_float, c_float, _P, _P, _H]),
+    "pndf_lbs_backward": (c_int, [_H, _P, _P, _P, c_int64, _P, _P, _H]),
+    "pndf_lbs_packed_floats": (c_int64, [c_int32]),
+    "pndf_lbs_pack_host": (c_int, [c_int32, c_int32] + [_P] * 8 + [c_int32, _P, _P, _P]),
+    "pndf_lbs_packed_split_bytes": (c_int64, [c_int32]),
+    "pndf_lbs_pack_split_host": (c_int, [c_int32, _P, _P, _P]),
+    "pndf_lbs_last_error": (c_char_p, [_H]),
+    # ---- the training objective
+    "pndf_train_create": (c_int, [POINTER(_H), POINTER(PndfConfig), c_int]),
+    "pndf_train_destroy": (c_int, [_H]),
+    "pndf_train_workspace_floats": (c_int64, [_H, c_int64, c_int64, c_int32]),
+    "pndf_train_forward": (c_int, [_H, _P, _P, _P, _P, c_int64, c_int64, c_int32, c_int32, _P, _P, _H]),
+    "pndf_train_backward": (c_int, [_H, _P, _P, _P, _P, _H]),
+    "pndf_train_last_error": (c_char_p, [_H]),
+    # ---- the rest of a training step
+    "pndf_adam_step": (c_int, [_P] * 4 + [c_int64, c_int32] + [c_double] * 5 + [_H]),
+    "pndf_train_batch": (c_int, [_P] * 8 + [c_int32] * 6 + [_P] * 3 + [_H]),
+    # ---- fitting poses to 2D keypoints
+    "pndf_keypoint_terms_grad": (c_int, [_P] * 5 + [c_int64, c_int32, POINTER(Camera), POINTER(KeypointOpts)] + [_P] * 4 + [_H]),
+    "pndf_keypoint_project": (c_int, [_P] * 3 + [c_int64, c_int32, POINTER(Camera), _P, _P, _H]),
+    # ---- quaternion pose distance + k nearest candidates
+    "pndf_quat_topk": (c_int, [_P, _P, c_int64, c_int32, c_int32, _P, c_int32, _P, _P, _H]),
+    # ---- exact k-nearest-pose search
+    "pndf_knn_create": (c_int, [POINTER(_H), _P, c_int64, c_int32, _P, _H]),
+    "pndf_knn_destroy": (c_int, [_H]),
+    "pndf_knn_size": (c_int64, [_H]),
+    "pndf_knn_workspace_bytes": (c_int64, [_H, c_int64, c_int32]),
+    "pndf_knn_search": (c_int, [_H, _P, c_int64, c_int32, _P, _P, _P, _H]),
+    "pndf_knn_last_error": (c_char_p, [_H]),
+
+    "pndf_last_error": (c_char_p, [_H]),
+    "pndf_version": (c_char_p, []),
+    "pndf_experiment_word": (c_uint, []),
+    "pndf_kernel_name": (c_char_p, [_H]),
+}
+_DEBUG_SIGNATURES = {      # include/posendf_amd_debug.h: bring-up / profiling / measurement aids, NOT the drop-in boundary
+    "pndf_debug_bind": (c_int, [_P, _P, _P]),
+    "pndf_debug_experiment_word": (c_uint, []),
+    "pndf_debug_forward_grad": (c_int, [_H, _P, _P, _P, c_int64, _P, _H]),
+    "pndf_debug_floats": (c_int64, []),
+    "pndf_debug_project_timing": (c_int, [_H, _P, _P, c_int64, c_int, _P, _H]),
+    "pndf_debug_timing_regions": (c_int, []),
+    "pndf_debug_timing_layout": (c_int, [c_int]),
+    "pndf_debug_mem_probe": (c_int, [c_int, _P, c_int]),
+    "pndf_debug_ring_stream": (c_int, [c_int, c_int, _P]),
+}
+EXPORTS, DEBUG_EXPORTS = tuple(_SIGNATURES), tuple(_DEBUG_SIGNATURES)
+# per-translation-unit experiment words (csrc/pndf_experiment.h): data symbols, all zero in a product build
+EXPERIMENT_WORDS = ("pndf_experiment_word_capi", "pndf_experiment_word_fp32", "pndf_experiment_word_split", "pndf_experiment_word_split_x2",
+                    "pndf_experiment_word_bf16", "pndf_experiment_word_lbs", "pndf_experiment_word_generic", "pndf_experiment_word_train",
+                    "pndf_experiment_word_optim")
+DEBUG_EXPERIMENT_WORDS = ("pndf_experiment_word_debug", "pndf_experiment_word_fp32_timing", "pndf_experiment_word_split_timing",
+                          "pndf_experiment_word_fp32_dbg", "pndf_experiment_word_probe")
+
+
+def _bind(lib, signatures):
+    for name, (restype, argtypes) in signatures.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return lib
+
+
 def debug_library_path(product_path: str) -> str:
     """libposendf_amd.so -> libposendf_amd_debug.so (variant builds: lib_<name>.so -> lib_<name>_debug.so, next to it)"""
     base, ext = os.path.splitext(product_path)
@@ -73,23 +187,7 @@ class _PndfLibrary(ctypes.CDLL):
             path = debug_library_path(self._name)
             if not os.path.exists(path):
                 raise PndfError(f"{path} not found (the debug library is built with the product one: __graft_entry__.build())")
-            dbg = ctypes.CDLL(path)
-            H = c_void_p
-            dbg.pndf_debug_bind.argtypes = [c_void_p, c_void_p, c_void_p]
-            dbg.pndf_debug_bind.restype = c_int
-            dbg.pndf_debug_experiment_word.restype = ctypes.c_uint
-            dbg.pndf_debug_forward_grad.argtypes = [H, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
-            dbg.pndf_debug_forward_grad.restype = c_int
-            dbg.pndf_debug_floats.restype = c_int64
-            dbg.pndf_debug_project_timing.argtypes = [H, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]
-            dbg.pndf_debug_project_timing.restype = c_int
-            dbg.pndf_debug_timing_regions.restype = c_int
-            dbg.pndf_debug_timing_layout.argtypes = [c_int]
-            dbg.pndf_debug_timing_layout.restype = c_int
-            dbg.pndf_debug_mem_probe.argtypes = [c_int, c_void_p, c_int]
-            dbg.pndf_debug_mem_probe.restype = c_int
-            dbg.pndf_debug_ring_stream.argtypes = [c_int, c_int, c_void_p]
-            dbg.pndf_debug_ring_stream.restype = c_int
+            dbg = _bind(ctypes.CDLL(path), _DEBUG_SIGNATURES)
             hooks = [ctypes.cast(ctypes.CDLL.__getattr__(self, n), c_void_p) for n in
                      ("pndf_internal_launch", "pndf_internal_describe", "pndf_internal_fail")]
             if dbg.pndf_debug_bind(*hooks) != 0:
@@ -100,145 +198,10 @@ class _PndfLibrary(ctypes.CDLL):
 
 def load_library(path: str | None = None) -> ctypes.CDLL:
     path = path or os.environ.get("PNDF_LIBRARY") or _LIB_PATH      # PNDF_LIBRARY: A/B runs of two builds on one box
-    # PyTorch is the plumbing for device memory and streams, so the library must share PyTorch's HIP runtime:
-    # import torch FIRST so that its bundled libamdhip64 is the one already mapped when the loader resolves
-    # this library's dependency (the other order puts two HIP runtimes in the process and pndf_create then
-    # sees no device).  Without torch installed the system runtime is used.
-    try:
-        import torch  # noqa: F401
-    except ImportError:
-        pass
     if not os.path.exists(path):
         raise PndfError(f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                         "(hipcc --offload-arch=gfx950). The engine has no fallback path.")
-    lib = _PndfLibrary(path)
-    H = c_void_p
-    lib.pndf_default_config.argtypes = [POINTER(PndfConfig), c_int32, c_float]
-    lib.pndf_default_config.restype = None
-    lib.pndf_create.argtypes = [POINTER(H), POINTER(PndfConfig), c_int]
-    lib.pndf_destroy.argtypes = [H]
-    lib.pndf_load_weights.argtypes = [H, POINTER(c_void_p), POINTER(c_int64), c_int]
-    lib.pndf_forward.argtypes = [H, c_void_p, c_void_p, c_int64, c_void_p]
-    lib.pndf_forward_grad.argtypes = [H, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
-    lib.pndf_project.argtypes = [H, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]
-    lib.pndf_default_project_options.argtypes = [POINTER(ProjectOptions)]
-    lib.pndf_default_project_options.restype = None
-    lib.pndf_project_ex.argtypes = [H, c_void_p, c_void_p, c_void_p, c_int64, c_int, POINTER(ProjectOptions), c_void_p]
-    lib.pndf_packed_sizes.argtypes = [POINTER(c_int64)] * 2
-    lib.pndf_packed_sizes.restype = None
-    lib.pndf_pack_host.argtypes = [POINTER(c_void_p), POINTER(c_int64), c_int, c_void_p, c_void_p]
-    lib.pndf_pack_host_split.argtypes = [POINTER(c_void_p), POINTER(c_int64), c_int, c_void_p, c_void_p]
-    lib.pndf_aa2quat.argtypes = [c_void_p, c_void_p, c_int64, c_void_p]
-    lib.pndf_aa2quat.restype = c_int
-    lib.pndf_denoise_update.argtypes = [c_void_p] * 8 + [c_int32] * 4 + [c_float, c_void_p]
-    lib.pndf_denoise_update.restype = c_int
-    lib.pndf_denoise_update_w.argtypes = [c_void_p] * 9 + [c_int32, c_int32, POINTER(DenoiseWeights), c_int32, c_float, c_void_p]
-    lib.pndf_denoise_update_w.restype = c_int
-    lib.pndf_lbs_terms_grad_w.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_float, c_void_p, c_void_p, c_void_p]
-    lib.pndf_lbs_terms_grad_w.restype = c_int
-    lib.pndf_denoise_update_body.argtypes = [c_void_p] * 9 + [c_int32] * 4 + [c_float, c_void_p]
-    lib.pndf_denoise_update_body.restype = c_int
-    LH = c_void_p
-    lib.pndf_lbs_create.argtypes = [POINTER(LH), c_int32, c_int32] + [c_void_p] * 8 + [c_int32, c_int]
-    lib.pndf_lbs_create.restype = c_int
-    lib.pndf_lbs_destroy.argtypes = [LH]
-    lib.pndf_lbs_num_joints.argtypes = [LH]
-    lib.pndf_lbs_num_joints.restype = c_int32
-    lib.pndf_lbs_num_vertices.argtypes = [LH]
-    lib.pndf_lbs_num_vertices.restype = c_int32
-    lib.pndf_lbs_workspace_floats.argtypes = [LH, c_int32, c_int32]
-    lib.pndf_lbs_workspace_floats.restype = c_int64
-    lib.pndf_lbs_forward.argtypes = [LH, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.pndf_lbs_forward.restype = c_int
-    lib.pndf_lbs_terms_grad.argtypes = [LH, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
-    lib.pndf_lbs_terms_grad.restype = c_int
-    lib.pndf_lbs_backward.argtypes = [LH, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]
-    lib.pndf_lbs_backward.restype = c_int
-    lib.pndf_lbs_packed_floats.argtypes = [c_int32]
-    lib.pndf_lbs_packed_floats.restype = c_int64
-    lib.pndf_lbs_pack_host.argtypes = [c_int32, c_int32] + [c_void_p] * 8 + [c_int32, c_void_p, c_void_p, c_void_p]
-    lib.pndf_lbs_pack_host.restype = c_int
-    lib.pndf_lbs_packed_split_bytes.argtypes = [c_int32]
-    lib.pndf_lbs_packed_split_bytes.restype = c_int64
-    lib.pndf_lbs_pack_split_host.argtypes = [c_int32, c_void_p, c_void_p, c_void_p]
-    lib.pndf_lbs_pack_split_host.restype = c_int
-    lib.pndf_lbs_set_precision.argtypes = [LH, c_int32]
-    lib.pndf_lbs_set_precision.restype = c_int
-    lib.pndf_lbs_precision.argtypes = [LH]
-    lib.pndf_lbs_precision.restype = c_int32
-    lib.pndf_lbs_last_error.argtypes = [LH]
-    lib.pndf_lbs_last_error.restype = c_char_p
-    lib.pndf_quat_topk.argtypes = [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_void_p,
-                                   c_void_p, c_void_p]
-    lib.pndf_quat_topk.restype = c_int
-    TH = c_void_p
-    lib.pndf_train_create.argtypes = [POINTER(TH), POINTER(PndfConfig), c_int]
-    lib.pndf_train_create.restype = c_int
-    lib.pndf_train_destroy.argtypes = [TH]
-    lib.pndf_train_destroy.restype = c_int
-    lib.pndf_train_workspace_floats.argtypes = [TH, c_int64, c_int64, c_int32]
-    lib.pndf_train_workspace_floats.restype = c_int64
-    lib.pndf_train_forward.argtypes = [TH, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p,
-                                       c_void_p, c_void_p]
-    lib.pndf_train_forward.restype = c_int
-    lib.pndf_train_backward.argtypes = [TH, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.pndf_train_backward.restype = c_int
-    lib.pndf_train_last_error.argtypes = [TH]
-    lib.pndf_train_last_error.restype = c_char_p
-    lib.pndf_adam_step.argtypes = [c_void_p] * 4 + [c_int64, c_int32] + [c_double] * 5 + [c_void_p]
-    lib.pndf_adam_step.restype = c_int
-    lib.pndf_train_batch.argtypes = [c_void_p] * 8 + [c_int32] * 6 + [c_void_p] * 4
-    lib.pndf_train_batch.restype = c_int
-    lib.pndf_keypoint_terms_grad.argtypes = [c_void_p] * 5 + [c_int64, c_int32, POINTER(Camera), POINTER(KeypointOpts)] + [c_void_p] * 5
-    lib.pndf_keypoint_terms_grad.restype = c_int
-    lib.pndf_keypoint_project.argtypes = [c_void_p] * 3 + [c_int64, c_int32, POINTER(Camera)] + [c_void_p] * 3
-    lib.pndf_keypoint_project.restype = c_int
-    KH = c_void_p
-    lib.pndf_knn_create.argtypes = [POINTER(KH), c_void_p, c_int64, c_int32, c_void_p, c_void_p]
-    lib.pndf_knn_create.restype = c_int
-    lib.pndf_knn_destroy.argtypes = [KH]
-    lib.pndf_knn_destroy.restype = c_int
-    lib.pndf_knn_size.argtypes = [KH]
-    lib.pndf_knn_size.restype = c_int64
-    lib.pndf_knn_workspace_bytes.argtypes = [KH, c_int64, c_int32]
-    lib.pndf_knn_workspace_bytes.restype = c_int64
-    lib.pndf_knn_search.argtypes = [KH, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.pndf_knn_search.restype = c_int
-    lib.pndf_knn_last_error.argtypes = [KH]
-    lib.pndf_knn_last_error.restype = c_char_p
-    CH = c_void_p
-    lib.pndf_cpu_create.argtypes = [POINTER(CH), POINTER(PndfConfig)]
-    lib.pndf_cpu_destroy.argtypes = [CH]
-    lib.pndf_cpu_load_weights.argtypes = [CH, POINTER(c_void_p), POINTER(c_int64), c_int]
-    lib.pndf_forward_cpu.argtypes = [CH, c_void_p, c_void_p, c_int64]
-    lib.pndf_forward_grad_cpu.argtypes = [CH, c_void_p, c_void_p, c_void_p, c_void_p, c_int64]
-    lib.pndf_project_cpu.argtypes = [CH, c_void_p, c_void_p, c_void_p, c_int64, c_int]
-    lib.pndf_project_ex_cpu.argtypes = [CH, c_void_p, c_void_p, c_void_p, c_int64, c_int, POINTER(ProjectOptions)]
-    lib.pndf_cpu_last_error.argtypes = [CH]
-    lib.pndf_cpu_last_error.restype = c_char_p
-    for name in ("pndf_cpu_create", "pndf_cpu_destroy", "pndf_cpu_load_weights", "pndf_forward_cpu", "pndf_forward_grad_cpu",
-                 "pndf_project_cpu", "pndf_project_ex_cpu"):
-        getattr(lib, name).restype = c_int
-    lib.pndf_last_error.argtypes = [H]
-    lib.pndf_last_error.restype = c_char_p
-    lib.pndf_version.restype = c_char_p
-    lib.pndf_experiment_word.restype = ctypes.c_uint
-    lib.pndf_kernel_name.argtypes = [H]
-    lib.pndf_kernel_name.restype = c_char_p
-    for name in ("pndf_create", "pndf_destroy", "pndf_load_weights", "pndf_forward", "pndf_forward_grad",
-                 "pndf_project", "pndf_project_ex", "pndf_pack_host", "pndf_pack_host_split"):
-        getattr(lib, name).restype = c_int
-    return lib
-
-
-# bring-up / profiling / measurement aids: include/posendf_amd_debug.h, NOT the drop-in boundary
-DEBUG_EXPORTS = ("pndf_debug_bind", "pndf_debug_experiment_word", "pndf_debug_forward_grad", "pndf_debug_floats", "pndf_debug_project_timing",
-                 "pndf_debug_timing_regions", "pndf_debug_timing_layout", "pndf_debug_mem_probe", "pndf_debug_ring_stream")
-# per-translation-unit experiment words (csrc/pndf_experiment.h): data symbols, all zero in a product build
-EXPERIMENT_WORDS = ("pndf_experiment_word_capi", "pndf_experiment_word_fp32", "pndf_experiment_word_split", "pndf_experiment_word_split_x2",
-                    "pndf_experiment_word_lbs", "pndf_experiment_word_generic", "pndf_experiment_word_train", "pndf_experiment_word_optim")
-DEBUG_EXPERIMENT_WORDS = ("pndf_experiment_word_debug", "pndf_experiment_word_fp32_timing", "pndf_experiment_word_split_timing",
-                          "pndf_experiment_word_fp32_dbg", "pndf_experiment_word_probe")
+    return _bind(_PndfLibrary(path), _SIGNATURES)
 
 
 def experiment_word(lib=None) -> int:
@@ -254,18 +217,16 @@ def experiment_word(lib=None) -> int:
     return w
 
 
-# include/posendf_amd.h, the public header
-EXPORTS = ("pndf_default_config", "pndf_create", "pndf_destroy", "pndf_load_weights", "pndf_forward",
-           "pndf_forward_grad", "pndf_project", "pndf_project_ex", "pndf_default_project_options", "pndf_experiment_word",
-           "pndf_packed_sizes", "pndf_pack_host", "pndf_pack_host_split", "pndf_aa2quat", "pndf_denoise_update", "pndf_denoise_update_body", "pndf_denoise_update_w", "pndf_lbs_terms_grad_w", "pndf_quat_topk",
-           "pndf_lbs_create", "pndf_lbs_destroy", "pndf_lbs_set_precision", "pndf_lbs_precision", "pndf_lbs_num_joints", "pndf_lbs_num_vertices", "pndf_lbs_workspace_floats",
-           "pndf_lbs_forward", "pndf_lbs_terms_grad", "pndf_lbs_backward", "pndf_lbs_packed_floats", "pndf_lbs_pack_host", "pndf_lbs_packed_split_bytes", "pndf_lbs_pack_split_host",
-           "pndf_lbs_last_error", "pndf_last_error", "pndf_version", "pndf_kernel_name",
-           "pndf_train_create", "pndf_train_destroy", "pndf_train_workspace_floats", "pndf_train_forward", "pndf_train_backward",
-           "pndf_train_last_error", "pndf_adam_step", "pndf_train_batch", "pndf_keypoint_terms_grad", "pndf_keypoint_project",
-           "pndf_knn_create", "pndf_knn_destroy", "pndf_knn_size", "pndf_knn_workspace_bytes", "pndf_knn_search", "pndf_knn_last_error",
-           "pndf_cpu_create", "pndf_cpu_destroy", "pndf_cpu_load_weights", "pndf_forward_cpu", "pndf_forward_grad_cpu", "pndf_project_cpu",
-           "pndf_project_ex_cpu", "pndf_cpu_last_error")
+def stream_handle(device) -> int:
+    """The caller's current HIP stream on `device` (a torch.device) as the integer the C ABI's `void* stream` takes; 0 for a host
+    device: the host twins take none, and a caller that launches a kernel refuses a host device itself (`_device_only`)."""
+    return torch.cuda.current_stream(device).cuda_stream if device.type == "cuda" else 0
+
+
+def _device_only(device, what):
+    """the refusal of the entry points that have no host twin: their pointers must be device memory"""
+    if device.type != "cuda":
+        raise PndfError(f"{what} runs on the HIP kernel only: tensors on {device}")
 
 
 def state_dict_order(encoder: bool = True, n_lin: int = 7):
@@ -327,48 +288,79 @@ def _set_encoder_act(cfg, act, beta, enc_act, enc_beta):
         cfg.enc_beta = float(enc_beta if enc_beta is not None else beta)
 
 
-class Engine:
+def _network_config(lib, act, beta, *, precision=None, encoder=True, hidden=None, enc_act=None, enc_beta=None) -> PndfConfig:
+    """The pndf_config of a network: configs/amass.yaml's architecture (pndf_default_config) with the activation pair, the trunk's
+    arithmetic, the encoder-less input and model.DFNet.dims of the caller."""
+    if act not in ACT_CODES:
+        raise PndfError(f"unknown activation {act!r}")
+    if precision is not None and precision not in PRECISION_CODES:
+        raise PndfError(f"unknown precision {precision!r} (fp32, f16x3, f16, bf16)")
+    cfg = PndfConfig()
+    lib.pndf_default_config(ctypes.byref(cfg), ACT_CODES[act], float(beta))
+    if precision is not None:
+        cfg.precision = PRECISION_CODES[precision]
+    _set_encoder_act(cfg, act, beta, enc_act, enc_beta)
+    if not encoder:
+        cfg.dims[0] = 84          # model.StrEnc.use = False: DFNet on the 21 x 4 normalised quaternions
+    if hidden is not None:
+        # model.DFNet.dims (reference net_modules.py:14-28: a free list).  Six hidden widths within configs/amass.yaml's run on
+        # the fused kernels (narrower ones zero padded); any other list of 1 .. 7 widths up to 1024 on the runtime-planned
+        # kernels (csrc/pndf_generic.hip: exact fp32, or split-precision fp16 MFMAs for f16x3 / f16); pndf_create refuses the rest
+        hidden = [int(w) for w in hidden]
+        if not 1 <= len(hidden) <= 7:
+            raise PndfError(f"DFNet with {len(hidden)} hidden layers: 1 .. 7 are implemented")
+        cfg.n_dims = len(hidden) + 2
+        for i in range(1, len(cfg.dims)):
+            cfg.dims[i] = 0
+        for i, w in enumerate(hidden):
+            cfg.dims[i + 1] = w
+        cfg.dims[len(hidden) + 1] = 1
+    return cfg
+
+
+class _Handle:
+    """The life cycle of one C-ABI handle.  A subclass names its handle type's destroy and last-error functions and sets `lib`
+    before it calls `_create`; compute methods call the bound function themselves and pass its status to `_check`."""
+    _destroy = _last_error = None
+    handle = None
+
+    def _create(self, fn, *args):
+        """self.handle = the handle that `fn(&handle, *args)` makes"""
+        self.handle = c_void_p()
+        rc = getattr(self.lib, fn)(ctypes.byref(self.handle), *args)
+        if rc != 0:
+            msg = getattr(self.lib, self._last_error)(None).decode()
+            self.handle = None
+            raise PndfError(f"{fn} failed ({rc}): {msg}")
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise PndfError(f"{what} failed ({rc}): {getattr(self.lib, self._last_error)(self.handle).decode()}")
+
+    def close(self):
+        if self.handle:
+            getattr(self.lib, self._destroy)(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Engine(_Handle):
     """One engine per device.  All compute methods take raw device pointers and a stream handle."""
+    _destroy, _last_error = "pndf_destroy", "pndf_last_error"
 
     def __init__(self, act: str = "lrelu", beta: float = 100.0, device: int = 0, lib=None, precision: str = "fp32",
                  encoder: bool = True, hidden=None, enc_act: str | None = None, enc_beta: float | None = None):
         self.lib = lib or load_library()
-        if act not in ACT_CODES:
-            raise PndfError(f"unknown activation {act!r}")
-        if precision not in PRECISION_CODES:
-            raise PndfError(f"unknown precision {precision!r} (fp32, f16x3, f16, bf16)")
-        cfg = PndfConfig()
-        self.lib.pndf_default_config(ctypes.byref(cfg), ACT_CODES[act], float(beta))
-        cfg.precision = PRECISION_CODES[precision]
-        _set_encoder_act(cfg, act, beta, enc_act, enc_beta)
-        if not encoder:
-            cfg.dims[0] = 84          # model.StrEnc.use = False: DFNet on the 21 x 4 normalised quaternions
-        if hidden is not None:
-            # model.DFNet.dims (reference net_modules.py:14-28: a free list).  Six hidden widths within configs/amass.yaml's run on
-            # the fused kernels (narrower ones zero padded); any other list of 1 .. 7 widths up to 1024 on the runtime-planned
-            # kernels (csrc/pndf_generic.hip: exact fp32, or split-precision fp16 MFMAs for f16x3 / f16); pndf_create refuses the rest
-            hidden = [int(w) for w in hidden]
-            if not 1 <= len(hidden) <= 7:
-                raise PndfError(f"DFNet with {len(hidden)} hidden layers: 1 .. 7 are implemented")
-            cfg.n_dims = len(hidden) + 2
-            for i in range(1, len(cfg.dims)):
-                cfg.dims[i] = 0
-            for i, w in enumerate(hidden):
-                cfg.dims[i + 1] = w
-            cfg.dims[len(hidden) + 1] = 1
+        cfg = _network_config(self.lib, act, beta, precision=precision, encoder=encoder, hidden=hidden, enc_act=enc_act, enc_beta=enc_beta)
         self.precision = precision
-        self.handle = c_void_p()
-        rc = self.lib.pndf_create(ctypes.byref(self.handle), ctypes.byref(cfg), int(device))
-        if rc != 0:
-            msg = self.lib.pndf_last_error(None).decode()
-            self.handle = None
-            raise PndfError(f"pndf_create failed ({rc}): {msg}")
+        self._create("pndf_create", ctypes.byref(cfg), int(device))
         self.device = device
         self.act = act
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise PndfError(f"{what} failed ({rc}): {self.lib.pndf_last_error(self.handle).decode()}")
 
     def load_weights(self, sd_np):
         arrs, ptrs, numel = _tensor_table(sd_np)
@@ -409,13 +401,13 @@ class Engine:
         """pndf_debug_project_timing on a CUDA tensor of poses: the instrumented kernel's per-region shader cycles of one
         step (mean over waves), the effective shader clock, and the weight ring's sampled events -- how long a wave sits in
         the ring's counted wait (the slot's DMA had not landed) and in its barrier, per slot."""
-        import torch
+        _device_only(q.device, "pndf_debug_project_timing")
         B = int(q.shape[0])
         R = int(self.lib.pndf_debug_timing_regions())
         nreg, ngrp, nring, period, slots = (int(self.lib.pndf_debug_timing_layout(i)) for i in range(5))
         cyc = torch.zeros((-(-B // 64)) * 4 * R, dtype=torch.int64, device=q.device)
         out = torch.empty_like(q) if out is None else out
-        st = torch.cuda.current_stream(q.device).cuda_stream
+        st = stream_handle(q.device)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         self._check(self.lib.pndf_debug_project_timing(self.handle, q.data_ptr(), out.data_ptr(), B, int(steps), cyc.data_ptr(), st),
@@ -442,56 +434,21 @@ class Engine:
                          "wait_cycles_per_slot_p99_wave": float(np.percentile(ring[:, 0] / np.maximum(ring[:, 2], 1), 99))},
                 "spread_over_waves": [float(reg.sum(1).min() / steps), float(reg.sum(1).max() / steps)]}
 
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.pndf_destroy(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class TrainEngine:
+class TrainEngine(_Handle):
     """`pndf_train_*` (csrc/pndf_train.hip): the training objective of model/posendf.py:62-99 and its weight gradients on one
     device.  Exact fp32 MFMA; the structure encoder is required (the reference cannot train without it).  All compute methods
     take raw device pointers (the weights and gradients as lists of them, state-dict order) and a stream handle."""
+    _destroy, _last_error = "pndf_train_destroy", "pndf_train_last_error"
 
     def __init__(self, act: str = "lrelu", beta: float = 100.0, device: int = 0, lib=None, encoder: bool = True, hidden=None,
                  enc_act: str | None = None, enc_beta: float | None = None):
         self.lib = lib or load_library()
-        if act not in ACT_CODES:
-            raise PndfError(f"unknown activation {act!r}")
-        cfg = PndfConfig()
-        self.lib.pndf_default_config(ctypes.byref(cfg), ACT_CODES[act], float(beta))
-        _set_encoder_act(cfg, act, beta, enc_act, enc_beta)
-        if not encoder:
-            cfg.dims[0] = 84
-        if hidden is not None:
-            hidden = [int(w) for w in hidden]
-            if not 1 <= len(hidden) <= 7:
-                raise PndfError(f"DFNet with {len(hidden)} hidden layers: 1 .. 7 are implemented")
-            cfg.n_dims = len(hidden) + 2
-            for i in range(1, len(cfg.dims)):
-                cfg.dims[i] = 0
-            for i, w in enumerate(hidden):
-                cfg.dims[i + 1] = w
-            cfg.dims[len(hidden) + 1] = 1
+        cfg = _network_config(self.lib, act, beta, encoder=encoder, hidden=hidden, enc_act=enc_act, enc_beta=enc_beta)
         self.n_tensors = len(state_dict_order(encoder, cfg.n_dims - 1))
-        self.handle = c_void_p()
-        rc = self.lib.pndf_train_create(ctypes.byref(self.handle), ctypes.byref(cfg), int(device))
-        if rc != 0:
-            msg = self.lib.pndf_train_last_error(None).decode()
-            self.handle = None
-            raise PndfError(f"pndf_train_create failed ({rc}): {msg}")
+        self._create("pndf_train_create", ctypes.byref(cfg), int(device))
         self.device = device
         self.act = act
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise PndfError(f"{what} failed ({rc}): {self.lib.pndf_train_last_error(self.handle).decode()}")
 
     def _table(self, ptrs):
         if isinstance(ptrs, ctypes.Array):      # a table the caller built once (posendf_amd.trainer: one per trainer, not per step)
@@ -515,17 +472,6 @@ class TrainEngine:
         self._check(self.lib.pndf_train_backward(self.handle, self._table(weight_ptrs), upstream_ptr, self._table(grad_ptrs), ws_ptr,
                                                  stream), "pndf_train_backward")
 
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.pndf_train_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def adam_step(p_ptr, g_ptr, m_ptr, v_ptr, n, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, stream=0, lib=None):
     """`pndf_adam_step` (csrc/pndf_optim.hip): one torch.optim.Adam step over flat fp32 device buffers of n floats"""
@@ -545,12 +491,56 @@ def train_batch(pose_db_ptr, dist_db_ptr, man_db_ptr, file_off_ptr, man_off_ptr,
         raise PndfError(f"pndf_train_batch failed ({rc}): F = {F}, Fm = {Fm}, k = {k}, items = {items}, num_pts = {num_pts}")
 
 
+def aa2quat(theta_ptr, q_ptr, N, stream=0, lib=None):
+    """`pndf_aa2quat` (csrc/pndf_denoise.hip): device theta [N,69] axis-angle -> q [N,21,4] quaternions of the first 21 joints"""
+    rc = (lib or load_library()).pndf_aa2quat(theta_ptr, q_ptr, int(N), stream)
+    if rc != 0:
+        raise PndfError(f"pndf_aa2quat failed ({rc}): N = {N}")
+
+
+def denoise_update_w(theta_in_ptr, theta_out_ptr, theta0_ptr, d_ptr, dq_ptr, g_body_ptr, m_ptr, v_ptr, q_next_ptr, S, T, weights, step, lr,
+                     stream=0, lib=None):
+    """`pndf_denoise_update_w` (csrc/pndf_denoise.hip): one Adam step of the motion-denoise objective with the explicit loss
+    weights `weights` (a DenoiseWeights); g_body_ptr None selects the pose-space surrogates"""
+    rc = (lib or load_library()).pndf_denoise_update_w(theta_in_ptr, theta_out_ptr, theta0_ptr, d_ptr, dq_ptr, g_body_ptr, m_ptr, v_ptr,
+                                                       q_next_ptr, int(S), int(T), ctypes.byref(weights), int(step), float(lr), stream)
+    if rc != 0:
+        raise PndfError(f"pndf_denoise_update_w failed ({rc}): S = {S}, T = {T}, step = {step}, prior_power = {weights.prior_power}")
+
+
+def keypoint_terms_grad(joints_ptr, orient_ptr, transl_ptr, keypoints_ptr, joint_weight_ptr, N, J, cam, opt, terms_ptr, g_joints_ptr,
+                        g_orient_ptr, g_transl_ptr, stream=0, lib=None):
+    """`pndf_keypoint_terms_grad` (csrc/pndf_keypoints.hip): the keypoint and depth terms of N frames of J joints and their
+    gradients; `cam` a Camera, `opt` a KeypointOpts; every output pointer may be None"""
+    rc = (lib or load_library()).pndf_keypoint_terms_grad(joints_ptr, orient_ptr, transl_ptr, keypoints_ptr, joint_weight_ptr, int(N), int(J),
+                                                          ctypes.byref(cam), ctypes.byref(opt), terms_ptr, g_joints_ptr, g_orient_ptr,
+                                                          g_transl_ptr, stream)
+    if rc != 0:
+        raise PndfError(f"pndf_keypoint_terms_grad failed ({rc}): N = {N}, J = {J}, rho = {opt.rho}")
+
+
+def keypoint_project(joints_ptr, orient_ptr, transl_ptr, N, J, cam, posed_ptr, uv_ptr, stream=0, lib=None):
+    """`pndf_keypoint_project` (csrc/pndf_keypoints.hip): camera-space points [N,J,3] and / or image points [N,J,2]"""
+    rc = (lib or load_library()).pndf_keypoint_project(joints_ptr, orient_ptr, transl_ptr, int(N), int(J), ctypes.byref(cam), posed_ptr,
+                                                       uv_ptr, stream)
+    if rc != 0:
+        raise PndfError(f"pndf_keypoint_project failed ({rc}): N = {N}, J = {J}")
+
+
+def quat_topk(noise_ptr, valid_ptr, B, K, metric, weights, k, vals_ptr, idx_ptr, stream=0, lib=None):
+    """`pndf_quat_topk` (csrc/pndf_quatdist.hip): the k nearest of every pose's K candidates; `weights` 21 host floats or None"""
+    rc = (lib or load_library()).pndf_quat_topk(noise_ptr, valid_ptr, int(B), int(K), int(metric), weights, int(k), vals_ptr, idx_ptr, stream)
+    if rc != 0:
+        raise PndfError(f"pndf_quat_topk failed ({rc}): B={B} K={K} k={k} (k <= min(K, 16), K <= ~1850)")
+
+
 METRIC_CODES = {"geo": 0, "euc": 1}
 
 
-class KnnIndex:
+class KnnIndex(_Handle):
     """`pndf_knn_*` (csrc/pndf_knn.hip): an exact k-nearest-pose index on one device.  The constructor packs a copy of the
     poses at `poses_ptr` (device [N,21,4]); `search` takes raw device pointers and a stream handle."""
+    _destroy, _last_error = "pndf_knn_destroy", "pndf_knn_last_error"
 
     def __init__(self, poses_ptr, N, metric: str = "geo", weights=None, stream=0, lib=None):
         self.lib = lib or load_library()
@@ -559,17 +549,8 @@ class KnnIndex:
         w = None
         if weights is not None:
             w = (c_float * 21)(*[float(x) for x in np.asarray(weights, dtype=np.float32).reshape(21)])
-        self.handle = c_void_p()
-        rc = self.lib.pndf_knn_create(ctypes.byref(self.handle), poses_ptr, int(N), METRIC_CODES[metric], w, stream)
-        if rc != 0:
-            msg = self.lib.pndf_knn_last_error(None).decode()
-            self.handle = None
-            raise PndfError(f"pndf_knn_create failed ({rc}): {msg}")
+        self._create("pndf_knn_create", poses_ptr, int(N), METRIC_CODES[metric], w, stream)
         self.metric = metric
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise PndfError(f"{what} failed ({rc}): {self.lib.pndf_knn_last_error(self.handle).decode()}")
 
     def size(self) -> int:
         return int(self.lib.pndf_knn_size(self.handle))
@@ -584,56 +565,21 @@ class KnnIndex:
         self._check(self.lib.pndf_knn_search(self.handle, q_ptr, int(Q), int(k), vals_ptr, idx_ptr, ws_ptr, stream),
                     "pndf_knn_search")
 
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.pndf_knn_destroy(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class CpuEngine:
+class CpuEngine(_Handle):
     """The host twins `pndf_*_cpu` behind the interface of `Engine` (raw HOST pointers; `stream` is accepted and ignored):
     what `PoseNDF` runs on when its config says `train.device: cpu`, as the reference's class does (model/posendf.py:35,64).
     Plain C++ on the host cores -- not the oracle, and never a fallback of the device engine."""
+    _destroy, _last_error = "pndf_cpu_destroy", "pndf_cpu_last_error"
 
     def __init__(self, act: str = "lrelu", beta: float = 100.0, lib=None, encoder: bool = True, hidden=None,
                  enc_act: str | None = None, enc_beta: float | None = None):
         self.lib = lib or load_library()
-        if act not in ACT_CODES:
-            raise PndfError(f"unknown activation {act!r}")
-        cfg = PndfConfig()
-        self.lib.pndf_default_config(ctypes.byref(cfg), ACT_CODES[act], float(beta))
-        _set_encoder_act(cfg, act, beta, enc_act, enc_beta)
-        if not encoder:
-            cfg.dims[0] = 84
-        if hidden is not None:
-            hidden = [int(w) for w in hidden]
-            if not 1 <= len(hidden) <= 7:
-                raise PndfError(f"DFNet with {len(hidden)} hidden layers: 1 .. 7 are implemented")
-            cfg.n_dims = len(hidden) + 2
-            for i in range(1, len(cfg.dims)):
-                cfg.dims[i] = 0
-            for i, w in enumerate(hidden):
-                cfg.dims[i + 1] = w
-            cfg.dims[len(hidden) + 1] = 1
+        cfg = _network_config(self.lib, act, beta, encoder=encoder, hidden=hidden, enc_act=enc_act, enc_beta=enc_beta)
         self.precision = "fp32"
-        self.handle = c_void_p()
-        rc = self.lib.pndf_cpu_create(ctypes.byref(self.handle), ctypes.byref(cfg))
-        if rc != 0:
-            msg = self.lib.pndf_cpu_last_error(None).decode()
-            self.handle = None
-            raise PndfError(f"pndf_cpu_create failed ({rc}): {msg}")
+        self._create("pndf_cpu_create", ctypes.byref(cfg))
         self.device = "cpu"
         self.act = act
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise PndfError(f"{what} failed ({rc}): {self.lib.pndf_cpu_last_error(self.handle).decode()}")
 
     def load_weights(self, sd_np):
         arrs, ptrs, numel = _tensor_table(sd_np)
@@ -655,14 +601,3 @@ class CpuEngine:
         else:
             self._check(self.lib.pndf_project_ex_cpu(self.handle, q_in_ptr, q_out_ptr, d_ptr, B, int(steps), ctypes.byref(opt)),
                         "pndf_project_ex_cpu")
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.pndf_cpu_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

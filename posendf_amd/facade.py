@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
-from .engine import CpuEngine, Engine, PndfError, TrainEngine, state_dict_order
+from .engine import CpuEngine, Engine, PndfError, TrainEngine, state_dict_order, stream_handle
 from .modules import DFNet, StructureEncoder
 
 
@@ -33,11 +33,6 @@ def gradient(inputs, outputs):
     ones = torch.ones_like(outputs, requires_grad=False, device=outputs.device)
     return torch.autograd.grad(outputs=outputs, inputs=inputs, grad_outputs=ones, create_graph=True,
                                retain_graph=True, only_inputs=True)[0]
-
-
-def _stream_of(device):
-    """the caller's current HIP stream as an integer handle (0 for a host tensor: the host twins take none)"""
-    return torch.cuda.current_stream(device).cuda_stream if device.type == "cuda" else 0
 
 
 class _Distance(torch.autograd.Function):
@@ -52,7 +47,7 @@ class _Distance(torch.autograd.Function):
         B = q.shape[0]
         d = torch.empty(B, device=q.device, dtype=torch.float32)
         eng = owner._engine_for(q.device)
-        stream = _stream_of(q.device)
+        stream = stream_handle(q.device)
         if ctx.needs_input_grad[0]:     # one launch yields d and d d/d pose
             dq = torch.empty_like(q)
             eng.forward_grad(q.data_ptr(), None, d.data_ptr(), dq.data_ptr(), B, stream)
@@ -236,6 +231,6 @@ class PoseNDF(nn.Module):
         out = torch.empty_like(q)
         d = torch.empty(q.shape[0], device=q.device, dtype=torch.float32)
         eng = self._engine_for(q.device)
-        eng.project(q.data_ptr(), out.data_ptr(), d.data_ptr(), q.shape[0], int(steps), _stream_of(q.device),
+        eng.project(q.data_ptr(), out.data_ptr(), d.data_ptr(), q.shape[0], int(steps), stream_handle(q.device),
                     step_size=step_size, renorm=renormalize, tol=tol)
         return (out, d.view(-1, 1)) if return_dist else out

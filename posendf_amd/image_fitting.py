@@ -29,16 +29,13 @@ import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
-from .engine import Camera, KeypointOpts, PndfError, load_library
+from .engine import (Camera, DenoiseWeights, KeypointOpts, PndfError, _device_only, aa2quat, adam_step, denoise_update_w,
+                     keypoint_project, keypoint_terms_grad, load_library, stream_handle)
 from .motion_denoise import axis_angle_to_quaternion
 
 FOCAL_LENGTH = 5000.0                      # image_fitting.py:96, exp_utils.py:70
 INIT_JOINTS_IDXS = (9, 12, 2, 5)           # the torso joints of stage 1 (image_fitting.py:30)
 TRANS_ESTIMATION = 10.0                    # :32
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _f32(t, device=None):
@@ -123,14 +120,12 @@ class PerspectiveCamera(torch.nn.Module):
 def project(joints, orient, transl, camera, posed=True, uv=True):
     """`pndf_keypoint_project`: joints [N,J,3] at zero global orientation, orient / transl [N,3] (CUDA, float32, contiguous) ->
     (camera-space points [N,J,3] or None, image points [N,J,2] or None)"""
+    _device_only(joints.device, "pndf_keypoint_project")
     N, J = joints.shape[:2]
     po = torch.empty(N, J, 3, device=joints.device, dtype=torch.float32) if posed else None
     out = torch.empty(N, J, 2, device=joints.device, dtype=torch.float32) if uv else None
-    cam = camera.struct()
-    rc = load_library().pndf_keypoint_project(joints.data_ptr(), orient.data_ptr(), transl.data_ptr(), N, J, ctypes.byref(cam),
-                                              _ptr(po), _ptr(out), _stream(joints.device))
-    if rc != 0:
-        raise PndfError(f"pndf_keypoint_project failed ({rc})")
+    keypoint_project(joints.data_ptr(), orient.data_ptr(), transl.data_ptr(), N, J, camera.struct(), _ptr(po), _ptr(out),
+                     stream_handle(joints.device))
     return po, out
 
 
@@ -158,11 +153,8 @@ def terms_grad(joints, orient, transl, keypoints, camera, joint_weight=None, *, 
         outs.append(want)
     cam = cam or camera.struct()
     opt = KeypointOpts(float(data_coef), float(rho), float(depth_coef), float(depth_target), int(bool(use_conf)), 0)
-    rc = load_library().pndf_keypoint_terms_grad(joints.data_ptr(), orient.data_ptr(), transl.data_ptr(), keypoints.data_ptr(),
-                                                 _ptr(joint_weight), N, J, ctypes.byref(cam), ctypes.byref(opt),
-                                                 *[_ptr(o) for o in outs], _stream(dev))
-    if rc != 0:
-        raise PndfError(f"pndf_keypoint_terms_grad failed ({rc})")
+    keypoint_terms_grad(joints.data_ptr(), orient.data_ptr(), transl.data_ptr(), keypoints.data_ptr(), _ptr(joint_weight), N, J, cam, opt,
+                        *[_ptr(o) for o in outs], stream_handle(dev))
     return tuple(outs)
 
 
@@ -265,7 +257,7 @@ class _FusedFit:
         self.N, self.J = N, J = kp.shape[0], kp.shape[1]
         self.lib = load_library()
         self.eng = fit.pose_prior._engine_for(dev)
-        self.st = _stream(dev)
+        self.st = stream_handle(dev)
         self.cam = fit.camera.struct()
         f32 = dict(device=dev, dtype=torch.float32)
         self.theta0 = torch.zeros(S, T, 69, **f32)                                  # :102
@@ -286,7 +278,6 @@ class _FusedFit:
         terms_grad(self.joints, self.orient, self.transl, self.kp, None, w, use_conf=self.fit.use_joints_conf, cam=self.cam, **kw)
 
     def _adam(self, p, g, m, v, k):
-        from .engine import adam_step
         adam_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), k, self.fit.LR, stream=self.st, lib=self.lib)
 
     def data_term(self, w, rho):
@@ -306,26 +297,21 @@ class _FusedFit:
         """fresh optimiser state (:144) and the quaternions of the first step"""
         self.mo.zero_()
         self.vo.zero_()
-        if self.lib.pndf_aa2quat(self.bufs[0].data_ptr(), self.q.data_ptr(), self.N, self.st) != 0:
-            raise PndfError("pndf_aa2quat failed")
+        aa2quat(self.bufs[0].data_ptr(), self.q.data_ptr(), self.N, self.st, self.lib)
 
     def stage2_step(self, k, it):
         """six launches: distances and their gradient, joints, the keypoint term's gradient, the body model's reverse pass,
         the pose update (axis-angle Jacobian, Adam, next quaternions), Adam on the orientation"""
-        from .engine import DenoiseWeights
         bm, st, N = self.bm, self.st, self.N
         pc, dc = self.fit.stage2_coefs(it)
         w = DenoiseWeights(pc, 1, 0.0, 0.0)
         cur, nxt = self.bufs
-        self.eng.forward_grad(self.q.data_ptr(), None, self.d.data_ptr(), self.dq.data_ptr(), N, st.value or 0)
+        self.eng.forward_grad(self.q.data_ptr(), None, self.d.data_ptr(), self.dq.data_ptr(), N, st)
         bm._call("pndf_lbs_forward", cur.data_ptr(), N, None, self.joints.data_ptr(), self.ws, st)
         self._terms_grad(self.w2, data_coef=dc, rho=self.fit.rho, terms=False, g_joints=self.g_joints, g_orient=self.g_orient, g_transl=False)
         bm._call("pndf_lbs_backward", cur.data_ptr(), None, self.g_joints.data_ptr(), N, self.g_body.data_ptr(), self.ws, st)
-        rc = self.lib.pndf_denoise_update_w(cur.data_ptr(), nxt.data_ptr(), self.theta0.data_ptr(), self.d.data_ptr(), self.dq.data_ptr(),
-                                            self.g_body.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.q.data_ptr(), self.S, self.T,
-                                            ctypes.byref(w), k, float(self.fit.LR), st)
-        if rc != 0:
-            raise PndfError(f"pndf_denoise_update_w failed ({rc})")
+        denoise_update_w(cur.data_ptr(), nxt.data_ptr(), self.theta0.data_ptr(), self.d.data_ptr(), self.dq.data_ptr(), self.g_body.data_ptr(),
+                         self.m.data_ptr(), self.v.data_ptr(), self.q.data_ptr(), self.S, self.T, w, k, self.fit.LR, st, self.lib)
         self._adam(self.orient, self.g_orient, self.mo, self.vo, k)
         self.bufs.reverse()
 

@@ -14,7 +14,7 @@ from __future__ import annotations
 import torch
 
 from .dist_utils import JOINT_RANK
-from .engine import KnnIndex, PndfError
+from .engine import KnnIndex, PndfError, stream_handle
 
 
 class PoseIndex:
@@ -30,8 +30,7 @@ class PoseIndex:
             rank = torch.tensor(JOINT_RANK, dtype=torch.float32)
             w = torch.nn.functional.normalize(rank, dim=0).tolist()                # dist_utils.py:18,41
         with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            self._index = KnnIndex(p.data_ptr(), p.shape[0], metric, w, stream)
+            self._index = KnnIndex(p.data_ptr(), p.shape[0], metric, w, stream_handle(self.device))
 
     def __len__(self) -> int:
         return self._index.size()
@@ -46,6 +45,5 @@ class PoseIndex:
             vals = torch.empty(Q, k, dtype=torch.float32, device=self.device)
             idx = torch.empty(Q, k, dtype=torch.int64, device=self.device)
             ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self.device)
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            self._index.search(q.data_ptr(), Q, k, vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), stream)
+            self._index.search(q.data_ptr(), Q, k, vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), stream_handle(self.device))
         return vals, idx

@@ -132,8 +132,8 @@ class MotionDenoise:
     # ---- optimiser ------------------------------------------------------------------------------
     def _optimize_fused(self, pose, iterations, steps_per_iter, lr):
         """The loop of `optimize` on the engine + pndf_denoise_update, no autograd (module docstring)."""
-        import ctypes
         from .body_model import BodyModel
+        from .engine import DenoiseWeights, aa2quat, denoise_update_w, stream_handle
         bm = self.body_model
         if bm is not None and not isinstance(bm, BodyModel):
             raise ValueError("fused=True needs body_model None (pose-space surrogates) or a posendf_amd.BodyModel (HIP LBS); "
@@ -148,33 +148,29 @@ class MotionDenoise:
             raise ValueError(f"poses on {dev} but the body model lives on {bm.device}: the fused step hands raw pointers to both")
         eng = self.pose_prior._engine_for(dev)
         lib = eng.lib
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = stream_handle(dev)
         theta0 = pose.contiguous()
         bufs = [theta0.clone(), torch.empty_like(theta0)]
         m, v = torch.zeros_like(theta0), torch.zeros_like(theta0)
         q = torch.empty(N, 21, 4, device=dev, dtype=torch.float32)
         d = torch.empty(N, device=dev, dtype=torch.float32)
         dq = torch.empty(N, 21, 4, device=dev, dtype=torch.float32)
-        if lib.pndf_aa2quat(bufs[0].data_ptr(), q.data_ptr(), N, stream) != 0:
-            raise RuntimeError("pndf_aa2quat failed")
+        aa2quat(bufs[0].data_ptr(), q.data_ptr(), N, stream, lib)
         if bm is not None:
             joints0 = bm.joints_of(theta0)                  # smpl_init.Jtr of the noisy poses (motion_denoise.py:60,63)
             g_body = torch.empty_like(theta0)
         k = 0
-        from .engine import DenoiseWeights
         for it in range(iterations):
             pc, pp, tc, dc = iteration_coefs(self.schedule, it)
             w = DenoiseWeights(pc, pp, tc, dc)
             for _ in range(steps_per_iter):
                 k += 1
-                eng.forward_grad(q.data_ptr(), None, d.data_ptr(), dq.data_ptr(), N, stream.value or 0)
+                eng.forward_grad(q.data_ptr(), None, d.data_ptr(), dq.data_ptr(), N, stream)
                 if bm is not None:
                     bm.terms_grad(bufs[0], joints0, it, out=g_body, coefs=(w.temp_coef, w.data_coef))
-                rc = lib.pndf_denoise_update_w(bufs[0].data_ptr(), bufs[1].data_ptr(), theta0.data_ptr(), d.data_ptr(),
-                                               dq.data_ptr(), None if bm is None else g_body.data_ptr(), m.data_ptr(),
-                                               v.data_ptr(), q.data_ptr(), S, T, ctypes.byref(w), k, float(lr), stream)
-                if rc != 0:
-                    raise RuntimeError(f"pndf_denoise_update failed ({rc})")
+                denoise_update_w(bufs[0].data_ptr(), bufs[1].data_ptr(), theta0.data_ptr(), d.data_ptr(), dq.data_ptr(),
+                                 None if bm is None else g_body.data_ptr(), m.data_ptr(), v.data_ptr(), q.data_ptr(), S, T, w, k, lr,
+                                 stream, lib)
                 bufs.reverse()
         return bufs[0]
 

@@ -5,7 +5,7 @@ from __future__ import annotations
 import torch
 from torch.autograd.function import once_differentiable
 
-from .engine import PndfError
+from .engine import PndfError, stream_handle
 
 LOSS_CODES = {"l1": 0, "l2": 1}
 
@@ -35,9 +35,8 @@ class TrainObjective(torch.autograd.Function):
                 raise PndfError(f"the HIP training objective takes contiguous fp32 parameters on {dev} (got {p.dtype} on {p.device})")
         ws = torch.empty(engine.workspace_floats(B, Bm, eikonal), dtype=torch.float32, device=dev)
         losses = torch.empty(3, dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         engine.forward([p.data_ptr() for p in params], q.data_ptr(), gt.data_ptr(), qm.data_ptr(), B, Bm, loss_type, eikonal,
-                       losses.data_ptr(), ws.data_ptr(), stream)
+                       losses.data_ptr(), ws.data_ptr(), stream_handle(dev))
         ctx.engine, ctx.ws = engine, ws
         ctx.save_for_backward(*params)
         return losses[0].clone(), losses[1].clone(), losses[2].clone()
@@ -51,6 +50,6 @@ class TrainObjective(torch.autograd.Function):
         up = torch.stack([zero if g is None else g.reshape(()).float() for g in (g_dist, g_man, g_eik)]).contiguous()
         grads = [torch.empty_like(p) for p in params]
         ctx.engine.backward([p.data_ptr() for p in params], up.data_ptr(), [g.data_ptr() for g in grads], ctx.ws.data_ptr(),
-                            torch.cuda.current_stream(dev).cuda_stream)
+                            stream_handle(dev))
         ctx.ws = None
         return (None,) * 6 + tuple(grads)

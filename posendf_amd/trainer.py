@@ -47,7 +47,7 @@ import shutil
 import numpy as np
 import torch
 
-from .engine import PndfError, TrainEngine, adam_step, load_library, state_dict_order, train_batch
+from .engine import PndfError, TrainEngine, adam_step, load_library, state_dict_order, stream_handle, train_batch
 from .facade import PoseNDF
 from .train import LOSS_CODES
 
@@ -337,7 +337,7 @@ class Trainer:
     def _step_hip(self, i):
         ds, bs = self.dataset, self.batch_size
         self._check_homes()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = stream_handle(self.device)
         train_batch(ds.pose.data_ptr(), ds.dist.data_ptr(), ds.man.data_ptr(), ds.file_off_t.data_ptr(), ds.man_off_t.data_ptr(),
                     self._item_file.data_ptr() + 4 * i * bs, self._item_man.data_ptr() + 4 * i * bs,
                     self._words.data_ptr() + 4 * i * bs * 2 * self.num_pts, ds.F, ds.Fm, ds.k, bs, self.num_pts, self.flip,

@@ -286,3 +286,150 @@ def test_weight_fingerprint_sees_replaced_parameters_and_modules():
     f.append(net._fingerprint())
     assert len(set(f)) == len(f)
     assert len(f[-1]) == 98
+
+
+# ---- the binding's signature tables, handle base, stream helper and stateless wrappers (posendf_amd/engine.py) ----------------
+
+_DECLARATION = re.compile(r"((?:const\s+)?\b[A-Za-z_][A-Za-z0-9_]*(?:\s*\*)?)\s*\b(pndf_[a-z0-9_]+)\s*\(([^()]*)\)\s*;")
+
+
+def _prototypes(header):
+    """{name: (return type, parameter count)} of every `pndf_*(...);` declaration, comments stripped"""
+    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(REPO, "include", header)).read(), flags=re.S)
+    text = "\n".join(ln for ln in re.sub(r"//[^\n]*", " ", text).splitlines() if not ln.lstrip().startswith("#"))
+    protos = {}
+    for ret, name, params in _DECLARATION.findall(text):
+        assert name not in protos, f"{name} declared twice"
+        params = params.strip()
+        protos[name] = (" ".join(ret.replace("*", " * ").split()), 0 if params in ("", "void") else params.count(",") + 1)
+    return protos
+
+
+@pytest.mark.parametrize("header,table,count", [("posendf_amd.h", "_SIGNATURES", 61), ("posendf_amd_debug.h", "_DEBUG_SIGNATURES", 9)])
+def test_signature_table_matches_header(lib, header, table, count):
+    """Every declaration of the header has an entry of the same parameter count and return kind in the table the binding is
+    made from, in the header's order, and no entry leaves its restype to ctypes' default."""
+    from posendf_amd import engine
+    protos, sigs = _prototypes(header), getattr(engine, table)
+    assert len(protos) == count and set(protos) == _declared(header), "the declaration pattern missed one"
+    assert list(sigs) == list(protos)
+    assert tuple(sigs) == (engine.EXPORTS if table == "_SIGNATURES" else engine.DEBUG_EXPORTS)
+    kinds = {"void": (None,), "const char *": (ctypes.c_char_p,), "int64_t": (ctypes.c_int64,), "int": (ctypes.c_int, ctypes.c_int32),
+             "int32_t": (ctypes.c_int, ctypes.c_int32), "unsigned": (ctypes.c_uint,)}
+    assert ctypes.sizeof(ctypes.c_int) == 4
+    bound = lib if table == "_SIGNATURES" else lib._debug()
+    for name, (ret, n_params) in protos.items():
+        entry = sigs[name]
+        assert isinstance(entry, tuple) and len(entry) == 2, f"{name}: the entry must be (restype, argtypes)"
+        restype, argtypes = entry
+        assert len(argtypes) == n_params, f"{name}: {n_params} parameters declared, {len(argtypes)} bound"
+        assert ret in kinds and restype in kinds[ret], f"{name}: returns {ret}, bound as {restype}"
+        fn = getattr(bound, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), f"{name}: the loaded library is not bound from the table"
+
+
+def test_experiment_words_cover_every_translation_unit(lib):
+    """The gate of build() reads EXPERIMENT_WORDS / DEBUG_EXPERIMENT_WORDS: they are exactly the pndf_experiment_word_* data symbols the
+    two libraries export, so a new translation unit cannot stay outside the gate."""
+    import subprocess
+    import __graft_entry__ as ge
+    from posendf_amd import engine
+
+    def words(path):
+        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+        rows = [ln.split() for ln in out.splitlines() if ln.strip()]
+        return [r[-1] for r in rows if r[-1].startswith("pndf_experiment_word_") and r[-2] in "BbDdRrSsGg"]
+    product, debug = words(ge.LIB), words(engine.debug_library_path(ge.LIB))
+    assert len(set(product)) == len(product) and len(set(debug)) == len(debug)
+    assert set(product) == set(engine.EXPERIMENT_WORDS) and len(engine.EXPERIMENT_WORDS) == len(product)
+    assert set(debug) == set(engine.DEBUG_EXPERIMENT_WORDS) and len(engine.DEBUG_EXPERIMENT_WORDS) == len(debug)
+    assert "pndf_experiment_word_bf16" in engine.EXPERIMENT_WORDS
+
+
+def _refused_handles():
+    from posendf_amd import engine
+    return {"CpuEngine": (engine.CpuEngine, dict(hidden=[2048]), "pndf_cpu_create", False),      # wider than 1024: refused on any machine
+            "Engine": (engine.Engine, {}, "pndf_create", True),
+            "TrainEngine": (engine.TrainEngine, {}, "pndf_train_create", True),
+            "KnnIndex": (engine.KnnIndex, dict(poses_ptr=None, N=0), "pndf_knn_create", False)}  # N < 1: refused before the device is looked for
+
+
+@pytest.mark.parametrize("which", ["CpuEngine", "Engine", "TrainEngine", "KnnIndex"])
+def test_handle_life_cycle_after_a_failed_create(lib, which):
+    import torch
+    from posendf_amd.engine import PndfError
+    cls, kwargs, create, needs_no_device = _refused_handles()[which]
+    if needs_no_device and torch.cuda.is_available():
+        pytest.skip("a GPU is visible")
+    obj = cls.__new__(cls)
+    with pytest.raises(PndfError, match=rf"{create} failed \(-\d\): \S") as e:
+        obj.__init__(lib=lib, **kwargs)
+    if needs_no_device:
+        assert re.search("no HIP device|no CPU fallback|gfx950", str(e.value))
+    assert obj.handle is None
+    obj.close()
+    obj.close()
+    obj.__del__()
+    assert obj.handle is None
+
+
+def test_handle_close_is_idempotent(lib):
+    from posendf_amd.engine import CpuEngine
+    eng = CpuEngine("relu", lib=lib)
+    assert eng.handle
+    eng.close()
+    assert eng.handle is None
+    eng.close()
+    eng.__del__()
+    assert eng.handle is None
+
+
+def test_stream_handle_and_checked_wrappers(lib):
+    """stream_handle is 0 on the host; a stateless wrapper raises PndfError naming the entry point that refused.  The refusals used
+    here come from the argument checks at the top of the entry points: nothing is launched and no device is looked for."""
+    import torch
+    from posendf_amd import engine
+    assert engine.stream_handle(torch.device("cpu")) == 0
+    from posendf_amd.body_model import BodyModel
+    assert BodyModel._stream(torch.device("cpu")) == 0          # the same function under the name tests/test_image_fitting_gpu.py calls
+    w = engine.DenoiseWeights(1.0, 2, 1.0, 0.0)
+    nine = (None,) * 9
+    # S = 0 with Adam step 0: pndf_denoise_update_w checks the step before it treats S == 0 as the header's no-op
+    with pytest.raises(engine.PndfError, match=r"pndf_denoise_update_w failed \(-1\)") as e:
+        engine.denoise_update_w(*nine, 0, 3, w, 0, 0.02, 0, lib)
+    assert type(e.value) is engine.PndfError and isinstance(e.value, RuntimeError)
+    engine.denoise_update_w(*nine, 0, 3, w, 1, 0.02, 0, lib)          # S = 0 alone: a no-op, not an error
+    with pytest.raises(engine.PndfError, match=r"pndf_denoise_update_w failed \(-1\)"):
+        engine.denoise_update_w(*nine, 0, 3, engine.DenoiseWeights(1.0, 3, 1.0, 0.0), 1, 0.02, 0, lib)      # prior_power 1 or 2
+    with pytest.raises(engine.PndfError, match="pndf_aa2quat failed"):
+        engine.aa2quat(None, None, -1, 0, lib)
+    with pytest.raises(engine.PndfError, match="pndf_keypoint_project failed"):
+        engine.keypoint_project(None, None, None, -1, 1, engine.Camera(), None, None, 0, lib)
+    with pytest.raises(engine.PndfError, match="pndf_keypoint_terms_grad failed"):
+        engine.keypoint_terms_grad(None, None, None, None, None, -1, 1, engine.Camera(), engine.KeypointOpts(), None, None, None, None, 0, lib)
+    with pytest.raises(engine.PndfError, match=r"pndf_quat_topk failed .*k <= min\(K, 16\)"):
+        engine.quat_topk(None, None, 1, 4, 0, None, 17, None, None, 0, lib)
+
+
+def test_kernel_only_entry_points_refuse_host_tensors(lib, monkeypatch):
+    """pndf_quat_topk, pndf_keypoint_project and pndf_debug_project_timing have no host twin and check their pointers for null
+    and alignment only: their drivers refuse a host device themselves, before the library is reached."""
+    import torch
+    from posendf_amd import dist_utils, engine, image_fitting
+
+    def reached(*a, **k):
+        raise AssertionError("the library was reached with host pointers")
+    monkeypatch.setattr(dist_utils, "quat_topk", reached)
+    monkeypatch.setattr(image_fitting, "keypoint_project", reached)
+    q = torch.zeros(1, 21, 4)
+    q[..., 0] = 1
+    for cls in (dist_utils.geo, dist_utils.euc):
+        with pytest.raises(engine.PndfError, match="pndf_quat_topk runs on the HIP kernel only"):
+            cls(1, "cpu").dist_calc(q, q[:, None].repeat(1, 4, 1, 1), 4, 2)
+    with pytest.raises(engine.PndfError, match="pndf_keypoint_project runs on the HIP kernel only"):
+        image_fitting.project(torch.zeros(1, 24, 3), torch.zeros(1, 3), torch.zeros(1, 3), image_fitting.PerspectiveCamera())
+    eng = engine.Engine.__new__(engine.Engine)      # no device needed: the refusal comes before the handle is used
+    eng.lib = lib
+    monkeypatch.setattr(lib, "pndf_debug_timing_regions", reached, raising=False)
+    with pytest.raises(engine.PndfError, match="pndf_debug_project_timing runs on the HIP kernel only"):
+        eng.project_timing(q.reshape(1, 84))
