@@ -43,12 +43,10 @@ struct pndf_engine {
     float* d_bias = nullptr;
     // softplus: fp32 derivative scratch, one block per RESIDENT workgroup (= per CU: the kernels take a whole CU each
     // and walk the 64-pose blocks with a grid-stride loop), allocated once in pndf_create.  Launches of one handle share
-    // it, so launches on different streams are ordered with an event (sp_done recorded after each softplus launch).
+    // it, so launches on different streams are ordered with an event (sp_order, pndf_host.h).
     float* d_scratch = nullptr;
     int resident_wgs = 0;
-    hipEvent_t sp_done = nullptr;
-    void* sp_stream = nullptr;
-    bool sp_pending = false;
+    PndfScratchOrder sp_order;
     // any DFNet that is not shaped like configs/amass.yaml (another depth, wider layers): the runtime-planned path, pndf_generic.hip
     PndfGeneric* generic = nullptr;
     std::string err;
@@ -56,19 +54,26 @@ struct pndf_engine {
 
 constexpr int STREAM_PAD_SLOTS = 5;           // >= RING_SLOTS - 1 of pndf_device.h (the ring's prefetch distance; 5 covers the six-buffer experiment arm)
 
-static thread_local std::string g_create_err;
-
-static int fail(pndf_engine* h, int code, const std::string& msg) {
-    if (h) h->err = msg; else g_create_err = msg;
-    return code;
+// The fused kernels, and the one a handle launches: by precision, activation family and (f16x3) whether every lo tile is zero
+typedef void (*fused_kernel_t)(PndfKernelArgs);
+struct FusedKernel {
+    fused_kernel_t fn;
+    const char* name;
+};
+#define PNDF_FUSED(k) {k, #k}
+static const FusedKernel FUSED_KERNELS[8] = {
+    PNDF_FUSED(pndf_fused_relu_kernel),       PNDF_FUSED(pndf_fused_softplus_kernel),       PNDF_FUSED(pndf_fused_split_relu_kernel),
+    PNDF_FUSED(pndf_fused_split_softplus_kernel), PNDF_FUSED(pndf_fused_split2_relu_kernel), PNDF_FUSED(pndf_fused_split2_softplus_kernel),
+    PNDF_FUSED(pndf_fused_half_relu_kernel),  PNDF_FUSED(pndf_fused_bf16_relu_kernel)};
+#undef PNDF_FUSED
+static const FusedKernel& fused_kernel(int precision, bool softplus, bool lo_all_zero) {
+    switch (precision) {
+        case PNDF_PREC_F16X3: return FUSED_KERNELS[(lo_all_zero ? 4 : 2) + softplus];
+        case PNDF_PREC_F16: return FUSED_KERNELS[6];
+        case PNDF_PREC_BF16: return FUSED_KERNELS[7];
+        default: return FUSED_KERNELS[softplus];
+    }
 }
-
-#define HIP_TRY(h, expr)                                                                     \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return fail(h, PNDF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 // The lab is quarantined from the product (pndf_experiment.h): every translation unit exports one word with a bit per tuning /
 // ablation macro that differs from its product default; a product library reports 0.
@@ -90,7 +95,7 @@ extern "C" const char* pndf_version(void) {
     return v.c_str();
 }
 
-extern "C" const char* pndf_last_error(pndf_handle h) { return h ? h->err.c_str() : g_create_err.c_str(); }
+extern "C" const char* pndf_last_error(pndf_handle h) { return pndf_last_error_of(h); }
 
 extern "C" void pndf_default_config(pndf_config* cfg, int32_t act, float beta) {
     memset(cfg, 0, sizeof(*cfg));
@@ -106,9 +111,9 @@ extern "C" void pndf_default_config(pndf_config* cfg, int32_t act, float beta) {
 }
 
 static int check_config(pndf_engine* h, const pndf_config* cfg) {
-    if (!cfg) return fail(h, PNDF_ERR_BAD_ARG, "cfg is null");
+    if (!cfg) return pndf_fail(h, PNDF_ERR_BAD_ARG, "cfg is null");
     if (cfg->num_joints != NJ)
-        return fail(h, PNDF_ERR_UNSUPPORTED, "only the 21-joint structure of get_parent_mapping('smpl') is implemented");
+        return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "only the 21-joint structure of get_parent_mapping('smpl') is implemented");
     // The fused kernels are laid out for configs/amass.yaml (126 | 84, 256, 512, 1024, 512, 256, 64, 1).  A DFNet of the same
     // depth whose hidden layers are NARROWER runs on them zero-padded (padded units have zero outgoing weights, so they
     // reach neither the distance nor its gradient, whatever the activation); any other `dims` list the reference can build
@@ -116,63 +121,59 @@ static int check_config(pndf_engine* h, const pndf_config* cfg) {
     // pndf_generic.hip (the exact fp32 form for precision fp32; the split-precision form, fp16 MFMAs with fp32 accumulation, for
     // any other precision, unless a layer's weights cannot be scaled into fp16's range).  Only beyond that is a configuration refused.
     if (cfg->n_dims < 3 || cfg->n_dims > MAXLIN + 1)
-        return fail(h, PNDF_ERR_UNSUPPORTED, "DFNet depth: n_dims must be 3 .. 9 (1 .. 7 hidden layers + the output layer)");
+        return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "DFNet depth: n_dims must be 3 .. 9 (1 .. 7 hidden layers + the output layer)");
     if ((cfg->dims[0] != DIMS[0] && cfg->dims[0] != NOENC_IN) || cfg->dims[cfg->n_dims - 1] != 1)
-        return fail(h, PNDF_ERR_UNSUPPORTED, "DFNet in_dim must be 126 (StrEnc.use=True) or 84 (False), its output 1");
+        return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "DFNet in_dim must be 126 (StrEnc.use=True) or 84 (False), its output 1");
     for (int i = 1; i < cfg->n_dims - 1; ++i)
         if (cfg->dims[i] < 1 || cfg->dims[i] > MAX_WIDTH)
-            return fail(h, PNDF_ERR_UNSUPPORTED, "DFNet hidden widths must be 1 .. 1024");
+            return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "DFNet hidden widths must be 1 .. 1024");
     for (int i = 0; i < NJ; ++i)
-        if (cfg->parent[i] != PARENT[i]) return fail(h, PNDF_ERR_UNSUPPORTED, "parent table must be get_parent_mapping('smpl')");
+        if (cfg->parent[i] != PARENT[i]) return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "parent table must be get_parent_mapping('smpl')");
     if (cfg->act != PNDF_ACT_RELU && cfg->act != PNDF_ACT_LRELU && cfg->act != PNDF_ACT_SOFTPLUS)
-        return fail(h, PNDF_ERR_UNSUPPORTED, "unknown activation (relu, lrelu and softplus are implemented)");
+        return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "unknown activation (relu, lrelu and softplus are implemented)");
     if (cfg->act == PNDF_ACT_SOFTPLUS && !(cfg->beta > 0.f))
-        return fail(h, PNDF_ERR_BAD_ARG, "softplus beta must be positive");
+        return pndf_fail(h, PNDF_ERR_BAD_ARG, "softplus beta must be positive");
     if (cfg->enc_act != -1 && cfg->enc_act != PNDF_ACT_RELU && cfg->enc_act != PNDF_ACT_LRELU && cfg->enc_act != PNDF_ACT_SOFTPLUS)
-        return fail(h, PNDF_ERR_UNSUPPORTED, "unknown encoder activation (relu, lrelu and softplus are implemented; -1 = the trunk's)");
+        return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "unknown encoder activation (relu, lrelu and softplus are implemented; -1 = the trunk's)");
     if (cfg->enc_act == PNDF_ACT_SOFTPLUS && !(cfg->enc_beta > 0.f) && !(cfg->beta > 0.f))
-        return fail(h, PNDF_ERR_BAD_ARG, "softplus beta of the encoder must be positive");
+        return pndf_fail(h, PNDF_ERR_BAD_ARG, "softplus beta of the encoder must be positive");
     if (cfg->precision != PNDF_PREC_FP32 && cfg->precision != PNDF_PREC_F16X3 && cfg->precision != PNDF_PREC_F16 &&
         cfg->precision != PNDF_PREC_BF16)
-        return fail(h, PNDF_ERR_UNSUPPORTED, "unknown precision (fp32, f16x3, f16 and bf16 are implemented)");
+        return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "unknown precision (fp32, f16x3, f16 and bf16 are implemented)");
     if ((cfg->precision == PNDF_PREC_F16 || cfg->precision == PNDF_PREC_BF16) && cfg->act == PNDF_ACT_SOFTPLUS)
-        return fail(h, PNDF_ERR_UNSUPPORTED, "the plain-f16 / plain-bf16 comparison kernels implement relu / lrelu only");
+        return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "the plain-f16 / plain-bf16 comparison kernels implement relu / lrelu only");
     return PNDF_OK;
 }
 
 extern "C" int pndf_create(pndf_handle* out, const pndf_config* cfg, int device) {
-    if (!out) return fail(nullptr, PNDF_ERR_BAD_ARG, "out is null");
+    if (!out) return pndf_fail<pndf_engine>(nullptr, PNDF_ERR_BAD_ARG, "out is null");
     *out = nullptr;
     int rc = check_config(nullptr, cfg);
     if (rc) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev)
-        return fail(nullptr, PNDF_ERR_NO_DEVICE, "no HIP device " + std::to_string(device) + " (the engine has no CPU fallback)");
-    hipDeviceProp_t prop;
-    HIP_TRY(nullptr, hipGetDeviceProperties(&prop, device));
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
-        return fail(nullptr, PNDF_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
+    const PndfDeviceCheck dev = pndf_check_gfx950(device, "the engine", true);
+    if (dev.code != PNDF_OK) return pndf_fail<pndf_engine>(nullptr, dev.code, dev.text);
+    const hipDeviceProp_t& prop = dev.prop;
     DeviceGuard guard(device);
-    if (!guard.ok) return fail(nullptr, PNDF_ERR_HIP, "hipSetDevice failed");
+    if (!guard.ok) return pndf_fail<pndf_engine>(nullptr, PNDF_ERR_HIP, "hipSetDevice failed");
     pndf_engine* h = new pndf_engine();
     h->cfg = *cfg;
     h->device = device;
     if (prop.multiProcessorCount <= 0) {
         delete h;
-        return fail(nullptr, PNDF_ERR_HIP, "the device reports no compute units (multiProcessorCount <= 0)");
+        return pndf_fail<pndf_engine>(nullptr, PNDF_ERR_HIP, "the device reports no compute units (multiProcessorCount <= 0)");
     }
     h->resident_wgs = prop.multiProcessorCount;
     if (pndf_generic_needed(*cfg)) {
         if (cfg->precision == PNDF_PREC_BF16) {
             delete h;
-            return fail(nullptr, PNDF_ERR_UNSUPPORTED, "the plain-bf16 comparison kernel exists for amass.yaml-shaped networks only "
+            return pndf_fail<pndf_engine>(nullptr, PNDF_ERR_UNSUPPORTED, "the plain-bf16 comparison kernel exists for amass.yaml-shaped networks only "
                                                        "(the runtime-planned kernels run fp32 or split-precision fp16)");
         }
         std::string why;
         rc = pndf_generic_create(&h->generic, *cfg, h->resident_wgs, why);
         if (rc != PNDF_OK) {
             delete h;
-            return fail(nullptr, rc, why);
+            return pndf_fail<pndf_engine>(nullptr, rc, why);
         }
         *out = h;
         return PNDF_OK;
@@ -186,28 +187,14 @@ extern "C" int pndf_create(pndf_handle* out, const pndf_config* cfg, int device)
         if (mt && mt[0] == 'u') e = hipExtMallocWithFlags((void**)&h->d_scratch, sbytes, hipDeviceMallocUncached);
         else if (mt && mt[0] == 'f') e = hipExtMallocWithFlags((void**)&h->d_scratch, sbytes, hipDeviceMallocFinegrained);
         else e = hipMalloc((void**)&h->d_scratch, sbytes);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&h->sp_done, hipEventDisableTiming);
+        if (e == hipSuccess) e = h->sp_order.create();
     }
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)pndf_fused_relu_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, pndf_kernel_lds_bytes());
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)pndf_fused_split_relu_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, pndf_kernel_lds_bytes());
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)pndf_fused_split_softplus_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, pndf_kernel_lds_bytes());
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)pndf_fused_split2_relu_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, pndf_kernel_lds_bytes());
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)pndf_fused_split2_softplus_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, pndf_kernel_lds_bytes());
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)pndf_fused_half_relu_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, pndf_kernel_lds_bytes());
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)pndf_fused_bf16_relu_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, pndf_kernel_lds_bytes());
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)pndf_fused_softplus_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, pndf_kernel_lds_bytes());
+    for (const FusedKernel& k : FUSED_KERNELS)
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pndf_kernel_lds_bytes());
     if (e != hipSuccess) {
         std::string m = std::string("pndf_create: ") + hipGetErrorString(e);
         pndf_destroy(h);
-        return fail(nullptr, PNDF_ERR_HIP, m);
+        return pndf_fail<pndf_engine>(nullptr, PNDF_ERR_HIP, m);
     }
     *out = h;
     return PNDF_OK;
@@ -217,7 +204,7 @@ extern "C" int pndf_destroy(pndf_handle h) {
     if (!h) return PNDF_OK;
     DeviceGuard guard(h->device);
     pndf_generic_destroy(h->generic);
-    if (h->sp_done) (void)hipEventDestroy(h->sp_done);
+    h->sp_order.destroy();
     if (h->d_stream) (void)hipFree(h->d_stream);
     if (h->d_bias) (void)hipFree(h->d_bias);
     if (h->d_scratch) (void)hipFree(h->d_scratch);
@@ -226,11 +213,9 @@ extern "C" int pndf_destroy(pndf_handle h) {
 }
 
 // ------------------------------------------------------------------------------------------ packing
-// (Mat / emit_tile / EncMat / emit_enc_tile: pndf_pack.h, shared with pndf_generic.hip)
+// (Mat / emit_tile / emit_pair_f16 / the encoder's sections and biases / layer_scale: pndf_pack.h, shared with pndf_generic.hip)
 using pndf_pack::Mat;
 using pndf_pack::emit_tile;
-using pndf_pack::EncMat;
-using pndf_pack::emit_enc_tile;
 
 extern "C" void pndf_packed_sizes(int64_t* stream_floats, int64_t* bias_floats) {
     if (stream_floats) *stream_floats = (int64_t)STEP_TILES * TILE_FLOATS;
@@ -285,18 +270,10 @@ extern "C" int pndf_pack_host(const float* const* tensors, const int64_t* numel,
     for (int l = 0; l < NLIN - 1; ++l) memcpy(bias + BIAS_OFF[l], lin[2 * l + 1], sizeof(float) * nd.out(l));   // narrower layers: zero padded
     memcpy(bias + W6_OFF, lin[2 * (NLIN - 1)], sizeof(float) * nd.in(NLIN - 1));
     bias[BIAS_OFF[NLIN - 1]] = lin[2 * (NLIN - 1) + 1][0];
-    for (int j = 0; enc && j < NJ; ++j) {
-        memcpy(bias + ENCB_OFF + 32 * j, tensors[4 * j + 1], sizeof(float) * HID);
-        memcpy(bias + ENCB_OFF + 32 * j + 16 + ENC_FEAT_ROW, tensors[4 * j + 3], sizeof(float) * FEAT);
-    }
+    if (enc) pndf_pack::emit_encoder_biases(tensors, bias);
     // ---- stream: encoder forward tiles | trunk phases | encoder backward tiles, in consumption order
-    float* dst = stream;
     memset(stream, 0, (size_t)STEP_TILES * TILE_FLOATS * sizeof(float));
-    for (int j = 0; enc && j < NJ; ++j) {                           // forward: joint order, W1 then W2
-        for (int kind = 0; kind < 2; ++kind, dst += TILE_FLOATS)
-            emit_enc_tile(EncMat{tensors[4 * j], tensors[4 * j + 2], enc_in(j), kind}, dst);
-    }
-    dst = stream + (size_t)ENC_TILES_PADDED * TILE_FLOATS;
+    float* dst = stream + (size_t)ENC_TILES_PADDED * TILE_FLOATS;
     for (int ph = 0; ph < 6; ++ph) {
         const Phase& P = PHASES[ph];
         const Mat A{lin[2 * P.a_lin], nd.out(P.a_lin), nd.in(P.a_lin), P.transposed};
@@ -310,88 +287,27 @@ extern "C" int pndf_pack_host(const float* const* tensors, const int64_t* numel,
         }
     }
     if (dst - stream != (ptrdiff_t)(ENC_TILES_PADDED + TRUNK_FWD_TILES + TRUNK_BWD_TILES) * TILE_FLOATS) return PNDF_ERR_BAD_SHAPE;
-    for (int j = NJ - 1; enc && j >= 0; --j) {                      // backward: reverse joint order, W2^T then W1^T
-        for (int kind = 2; kind < 4; ++kind, dst += TILE_FLOATS)
-            emit_enc_tile(EncMat{tensors[4 * j], tensors[4 * j + 2], enc_in(j), kind}, dst);
-    }
+    if (enc) pndf_pack::emit_encoder_sections(tensors, stream, dst);
     return PNDF_OK;
 }
 
 // ---- split-precision stream
-// Exact power-of-two scaling (pndf_kernel_split.hip, "operand scaling"): the weights of layer l travel as s_l W with
-// s_l = the power of two that brings the layer's largest |weight| into [2^12, 2^13) -- the hi halves cannot overflow and
-// the lo halves of all weights down to 2^-14 of the largest stay in fp16's normal range; 1 / s_l goes to the bias block
+// Exact power-of-two scaling (pndf_pack::layer_scale): the weights of layer l travel as s_l W; 1 / s_l goes to the bias block
 // (SCALE_OFF + l).  Biases stay unscaled: activations and gradients are scaled PER POSE on the chip, and the packer only
 // supplies the norms (NORM_OFF) from which the kernel derives guaranteed bounds for the layers it cannot measure.
-namespace {
-inline void split_f16(float w, _Float16& hi, _Float16& lo) {
-    hi = (_Float16)w;                       // round to nearest even
-    lo = (_Float16)(w - (float)hi);
-#ifdef PNDF_EXP_LO_BITS                     // (energy experiment, profiles/r05/energy_breakdown.txt: the lo half keeps this many
-    {                                       // explicit mantissa bits -- does the matrix pipe pay for operand bits that toggle?)
-        uint16_t u = __builtin_bit_cast(uint16_t, lo);
-        const int drop = 10 - PNDF_EXP_LO_BITS;
-        u = (uint16_t)((u + (1u << (drop - 1))) & ~((1u << drop) - 1));
-        lo = __builtin_bit_cast(_Float16, u);
-    }
-#endif
-}
-// fp32 -> bfloat16 bits, round to nearest even (the packer's inputs are finite: pack_host_split refuses a layer that is not)
-inline uint16_t bf16_bits(float w) {
-    const uint32_t u = __builtin_bit_cast(uint32_t, w);
-    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-// block(M, nt, kb): hi tile then lo tile, 8 halfs per lane each; returns whether any lo half is non-zero.
-// `bf16` (precision bf16, the one-term comparison kernel): the hi tile holds bfloat16 bits, the lo tile zeros.
-bool emit_pair(const Mat& m, int nt, int kb, float* dst, float scale, bool bf16) {
-    _Float16* hi = (_Float16*)dst;
-    _Float16* lo = (_Float16*)(dst + TILE_FLOATS);
-    bool any_lo = false;
-    for (int lane = 0; lane < 64; ++lane)
-        for (int jj = 0; jj < 8; ++jj) {
-            const float w = m.at(16 * nt + (lane & 15), 16 * (2 * kb + (jj >> 2)) + 4 * (lane >> 4) + (jj & 3));
-            if (bf16) {
-                hi[lane * 8 + jj] = __builtin_bit_cast(_Float16, bf16_bits(w * scale));
-                lo[lane * 8 + jj] = (_Float16)0;
-                continue;
-            }
-            split_f16(w * scale, hi[lane * 8 + jj], lo[lane * 8 + jj]);
-            any_lo |= (lo[lane * 8 + jj] != (_Float16)0);
-        }
-    return any_lo;
-}
-}  // namespace
 
-static int pack_host_split(const float* const* tensors, const int64_t* numel, int n_tensors, float* stream, float* bias,
-                           bool* lo_all_zero, bool bf16 = false);
-extern "C" int pndf_pack_host_split(const float* const* tensors, const int64_t* numel, int n_tensors, float* stream,
-                                    float* bias) {
-    return pack_host_split(tensors, numel, n_tensors, stream, bias, nullptr);
-}
-static int pack_host_split(const float* const* tensors, const int64_t* numel, int n_tensors, float* stream, float* bias,
-                           bool* lo_all_zero, bool bf16) {
+// `nd`: the widths check_tensors found in this table
+static int pack_host_split(const float* const* tensors, const int64_t* numel, int n_tensors, const NetDims& nd, float* stream,
+                           float* bias, bool* lo_all_zero, bool bf16 = false) {
     // biases and encoder tiles are identical to the fp32 stream (the encoder stays on fp32 MFMA)
     int rc = pndf_pack_host(tensors, numel, n_tensors, stream, bias);
     if (rc != PNDF_OK) return rc;
-    NetDims nd;
-    (void)check_tensors(tensors, numel, n_tensors, &nd);
     const bool enc = table_has_encoder(n_tensors);
     const float* const* lin = tensors + (enc ? 4 * NJ : 0);
     // per-layer weight scale; a layer without a finite non-zero weight cannot be scaled: refused (-> fp32 kernel)
     float wscale[6];
     for (int l = 0; l < 6; ++l) {
-        float mx = 0.f;
-        bool nan = false;
-        const int64_t n = (int64_t)nd.out(l) * nd.in(l);
-        for (int64_t i = 0; i < n; ++i) {
-            const float a = std::fabs(lin[2 * l][i]);
-            nan |= (a != a);
-            if (a > mx) mx = a;
-        }
-        if (nan || !(mx > 0x1p-100f && mx < 0x1p100f)) return PNDF_ERR_UNSUPPORTED;
-        int e;
-        (void)std::frexp(mx, &e);                       // mx = f * 2^e, f in [0.5, 1)
-        wscale[l] = std::ldexp(1.0f, 13 - e);           // s_l * mx in [2^12, 2^13)
+        if (!pndf_pack::layer_scale(lin[2 * l], (int64_t)nd.out(l) * nd.in(l), &wscale[l])) return PNDF_ERR_UNSUPPORTED;
         bias[SCALE_OFF + l] = 1.0f / wscale[l];
     }
     // norms for the a-priori bounds of the chunked layers, rounded UP (they must stay upper bounds in fp32)
@@ -429,11 +345,11 @@ static int pack_host_split(const float* const* tensors, const int64_t* numel, in
         const Mat B{lin[2 * P.b_lin], nd.out(P.b_lin), nd.in(P.b_lin), P.transposed};
         auto partA = [&](int c) {
             for (int kb = 0; kb < P.KA / 2; ++kb)
-                for (int ci = 0; ci < P.CT; ++ci, dst += 2 * TILE_FLOATS) any_lo |= emit_pair(A, c * P.CT + ci, kb, dst, wscale[P.a_lin], bf16);
+                for (int ci = 0; ci < P.CT; ++ci, dst += 2 * TILE_FLOATS) any_lo |= pndf_pack::emit_pair_f16(A, c * P.CT + ci, kb, wscale[P.a_lin], dst, bf16);
         };
         auto partB = [&](int c) {
             for (int nb = 0; nb < P.NB; ++nb)
-                for (int b = 0; b < P.CT / 2; ++b, dst += 2 * TILE_FLOATS) any_lo |= emit_pair(B, nb, (c * P.CT) / 2 + b, dst, wscale[P.b_lin], bf16);
+                for (int b = 0; b < P.CT / 2; ++b, dst += 2 * TILE_FLOATS) any_lo |= pndf_pack::emit_pair_f16(B, nb, (c * P.CT) / 2 + b, wscale[P.b_lin], dst, bf16);
         };
         partA(0);
         for (int c = 0; c < P.NC; ++c) {
@@ -445,34 +361,40 @@ static int pack_host_split(const float* const* tensors, const int64_t* numel, in
     if (lo_all_zero) *lo_all_zero = !any_lo;
     return PNDF_OK;
 }
+extern "C" int pndf_pack_host_split(const float* const* tensors, const int64_t* numel, int n_tensors, float* stream,
+                                    float* bias) {
+    NetDims nd;
+    if (check_tensors(tensors, numel, n_tensors, &nd)) return PNDF_ERR_BAD_SHAPE;
+    return pack_host_split(tensors, numel, n_tensors, nd, stream, bias, nullptr);
+}
 
 extern "C" int pndf_load_weights(pndf_handle h, const float* const* tensors, const int64_t* numel, int n_tensors) {
     if (!h) return PNDF_ERR_BAD_ARG;
     if (h->generic) {
         DeviceGuard guard(h->device);
-        if (!guard.ok) return fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
+        if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
         std::string why;
         const int grc = pndf_generic_load(h->generic, tensors, numel, n_tensors, why);
-        if (grc != PNDF_OK) return fail(h, grc, why);
+        if (grc != PNDF_OK) return pndf_fail(h, grc, why);
         h->have_weights = true;
         return PNDF_OK;
     }
     NetDims nd;
-    if (const char* why = check_tensors(tensors, numel, n_tensors, &nd)) return fail(h, PNDF_ERR_BAD_SHAPE, why);
+    if (const char* why = check_tensors(tensors, numel, n_tensors, &nd)) return pndf_fail(h, PNDF_ERR_BAD_SHAPE, why);
     if (table_has_encoder(n_tensors) != (h->cfg.dims[0] == DIMS[0]))
-        return fail(h, PNDF_ERR_BAD_SHAPE, "tensor table does not match the configured in_dim (98 tensors for 126, 14 for 84)");
+        return pndf_fail(h, PNDF_ERR_BAD_SHAPE, "tensor table does not match the configured in_dim (98 tensors for 126, 14 for 84)");
     for (int i = 0; i <= NLIN; ++i)
-        if (nd.d[i] != h->cfg.dims[i]) return fail(h, PNDF_ERR_BAD_SHAPE, "dfnet tensor shapes do not match the configured dims");
+        if (nd.d[i] != h->cfg.dims[i]) return pndf_fail(h, PNDF_ERR_BAD_SHAPE, "dfnet tensor shapes do not match the configured dims");
     std::vector<float> stream((size_t)STEP_TILES * TILE_FLOATS), bias(BIAS_FLOATS);
     bool lo_zero = false;
     const int prc = (h->cfg.precision != PNDF_PREC_FP32)
-                        ? pack_host_split(tensors, numel, n_tensors, stream.data(), bias.data(), &lo_zero, h->cfg.precision == PNDF_PREC_BF16)
+                        ? pack_host_split(tensors, numel, n_tensors, nd, stream.data(), bias.data(), &lo_zero, h->cfg.precision == PNDF_PREC_BF16)
                         : pndf_pack_host(tensors, numel, n_tensors, stream.data(), bias.data());
     if (prc == PNDF_ERR_UNSUPPORTED)
-        return fail(h, PNDF_ERR_UNSUPPORTED, "a trunk layer has no finite non-zero weight: outside the operating "
+        return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "a trunk layer has no finite non-zero weight: outside the operating "
                                              "range of the fp16 hi/lo split -- use precision fp32 for this network");
     if (prc != PNDF_OK)
-        return fail(h, PNDF_ERR_BAD_SHAPE, "internal: packed stream length mismatch");
+        return pndf_fail(h, PNDF_ERR_BAD_SHAPE, "internal: packed stream length mismatch");
     if (h->cfg.act == PNDF_ACT_SOFTPLUS) {
         // zero-padded units of a narrower network: softplus(0) = ln 2 / beta with derivative 1/2 is harmless for the
         // result (zero outgoing weights) but would enter the per-pose operand bounds the split kernels measure (largest
@@ -482,7 +404,7 @@ extern "C" int pndf_load_weights(pndf_handle h, const float* const* tensors, con
             for (int j = nd.out(l); j < DIMS[l + 1]; ++j) bias[BIAS_OFF[l] + j] = -1.0e6f;
     }
     DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
+    if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     HIP_TRY(h, hipDeviceSynchronize());   // no launch may still be reading the old weights
     HIP_TRY(h, hipMemcpy(h->d_stream, stream.data(), stream.size() * sizeof(float), hipMemcpyHostToDevice));
     // replica of the first slots behind the stream: the ring's fetch offset never wraps inside a step
@@ -500,15 +422,7 @@ extern "C" int pndf_load_weights(pndf_handle h, const float* const* tensors, con
 extern "C" const char* pndf_kernel_name(pndf_handle h) {
     if (!h) return "";
     if (h->generic) return pndf_generic_kernel_name(h->generic);
-    const bool sp = h->cfg.act == PNDF_ACT_SOFTPLUS;
-    switch (h->cfg.precision) {
-        case PNDF_PREC_F16X3:
-            if (h->lo_all_zero) return sp ? "pndf_fused_split2_softplus_kernel" : "pndf_fused_split2_relu_kernel";
-            return sp ? "pndf_fused_split_softplus_kernel" : "pndf_fused_split_relu_kernel";
-        case PNDF_PREC_F16: return "pndf_fused_half_relu_kernel";
-        case PNDF_PREC_BF16: return "pndf_fused_bf16_relu_kernel";
-        default: return sp ? "pndf_fused_softplus_kernel" : "pndf_fused_relu_kernel";
-    }
+    return fused_kernel(h->cfg.precision, h->cfg.act == PNDF_ACT_SOFTPLUS, h->lo_all_zero).name;
 }
 
 // ------------------------------------------------------------------------------------------ launches
@@ -519,92 +433,58 @@ static int launch(pndf_engine* h, int mode, const float* q, const float* gout, f
                   int steps, float* dbg, void* stream, const void* instrumented = nullptr, const pndf_project_options* popt = nullptr) {
     const bool timing = instrumented != nullptr;
     if (!h) return PNDF_ERR_BAD_ARG;
-    if (!h->have_weights) return fail(h, PNDF_ERR_NO_WEIGHTS, "pndf_load_weights has not been called");
-    if (B < 0 || steps < 0) return fail(h, PNDF_ERR_BAD_ARG, "negative batch or step count");
+    if (!h->have_weights) return pndf_fail(h, PNDF_ERR_NO_WEIGHTS, "pndf_load_weights has not been called");
+    if (B < 0 || steps < 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative batch or step count");
     if (B == 0) return PNDF_OK;
     if (!q || (mode != MODE_FORWARD && !qo) || (mode == MODE_FORWARD && !d))
-        return fail(h, PNDF_ERR_BAD_ARG, "null pose / output pointer");
-    if (((uintptr_t)q | (uintptr_t)qo) & 15) return fail(h, PNDF_ERR_BAD_ARG, "pose buffers must be 16-byte aligned");
-    if (((uintptr_t)d | (uintptr_t)gout) & 3) return fail(h, PNDF_ERR_BAD_ARG, "misaligned distance buffer");
-    PndfKernelArgs a;
-    if (h->generic) {
-        if (dbg || timing) return fail(h, PNDF_ERR_UNSUPPORTED, "stage dumps and region timing exist for the amass.yaml-shaped kernels only");
-        DeviceGuard gguard(h->device);
-        if (!gguard.ok) return fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
-        if (mode == MODE_PROJECT && steps == 0) {      // zero iterations: the loop body never runs (sample_poses.py:70)
-            if (qo != q) HIP_TRY(h, hipMemcpyAsync(qo, q, (size_t)B * NQ * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-            if (d) HIP_TRY(h, hipMemsetAsync(d, 0, (size_t)B * sizeof(float), (hipStream_t)stream));
-            return PNDF_OK;
-        }
-        std::string why;
-        const int grc = pndf_generic_launch(h->generic, mode, q, gout, qo, d, B, steps, stream, why, popt);
-        return grc == PNDF_OK ? PNDF_OK : fail(h, grc, why);
-    }
-    a.q_in = q; a.q_out = qo; a.d_out = d; a.grad_out = gout;
-    a.stream = h->d_stream; a.bias = h->d_bias; a.dbg = dbg;
-    // pndf_project_ex: the options' own mode only when one of them differs from its default (else the plain loop, bit for bit)
-    const bool plain = !popt || mode != MODE_PROJECT || pndf_project_options_plain(*popt);
-    a.B = B; a.steps = steps; a.mode = plain ? mode : MODE_PROJECT_OPT;
-    a.renorm = plain ? 0 : popt->renorm;
-    a.step_size = plain ? 1.0f : popt->step_size;
-    a.tol = plain ? 0.0f : popt->tol;
-    a.slope = (h->cfg.act == PNDF_ACT_LRELU) ? 0.01f : 0.0f;   // nn.LeakyReLU() default slope, net_modules.py:31
-    a.beta = h->cfg.beta;
-    a.scratch = nullptr;
-    a.noenc = (h->cfg.dims[0] == NOENC_IN) ? 1 : 0;
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
+        return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose / output pointer");
+    if (((uintptr_t)q | (uintptr_t)qo) & 15) return pndf_fail(h, PNDF_ERR_BAD_ARG, "pose buffers must be 16-byte aligned");
+    if (((uintptr_t)d | (uintptr_t)gout) & 3) return pndf_fail(h, PNDF_ERR_BAD_ARG, "misaligned distance buffer");
     const bool softplus = h->cfg.act == PNDF_ACT_SOFTPLUS;
-    if (dbg && !timing) return fail(h, PNDF_ERR_BAD_ARG, "a dump buffer needs an instrumented kernel (libposendf_amd_debug.so)");
-    if (timing && softplus && B > (int64_t)WG_POSES * h->resident_wgs)
-        return fail(h, PNDF_ERR_UNSUPPORTED, "instrumented softplus kernel: at most one 64-pose block per compute unit");
+    if (h->generic && (dbg || timing))
+        return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "stage dumps and region timing exist for the amass.yaml-shaped kernels only");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
+    if (!h->generic) {
+        if (dbg && !timing) return pndf_fail(h, PNDF_ERR_BAD_ARG, "a dump buffer needs an instrumented kernel (libposendf_amd_debug.so)");
+        if (timing && softplus && B > (int64_t)WG_POSES * h->resident_wgs)
+            return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "instrumented softplus kernel: at most one 64-pose block per compute unit");
+    }
     if (mode == MODE_PROJECT && steps == 0) {
         // zero iterations: the loop body never runs (sample_poses.py:70); poses pass through
         if (qo != q) HIP_TRY(h, hipMemcpyAsync(qo, q, (size_t)B * NQ * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
         if (d) HIP_TRY(h, hipMemsetAsync(d, 0, (size_t)B * sizeof(float), (hipStream_t)stream));
         return PNDF_OK;
     }
-    const int64_t nblocks = (B + WG_POSES - 1) / WG_POSES;
-    const dim3 grid((unsigned)nblocks), block(WG_THREADS);
-    if (softplus) {
-        // Persistent grid: at most one workgroup per CU (a workgroup takes a whole CU), each walking its blocks; the
-        // derivative scratch is indexed by workgroup and was allocated in pndf_create -- nothing is allocated, freed or
-        // synchronised here.  The scratch is shared by all launches of the handle: a launch on another stream than the
-        // previous one first waits (on the device) for that one's completion event.
-        const dim3 pgrid((unsigned)(nblocks < h->resident_wgs ? nblocks : h->resident_wgs));
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing((hipStream_t)stream, &cap);
-        const bool capturing = cap != hipStreamCaptureStatusNone;
-        if (h->sp_pending && h->sp_stream != stream && !capturing)
-            HIP_TRY(h, hipStreamWaitEvent((hipStream_t)stream, h->sp_done, 0));
-        a.scratch = h->d_scratch;
-        if (timing) {   // instrumented: one workgroup per block like the relu timing kernel needs B <= 64 * resident_wgs
-            void* kargs[] = {&a};
-            HIP_TRY(h, hipLaunchKernel(instrumented, pgrid, block, kargs, pndf_kernel_lds_bytes(), (hipStream_t)stream));
-        } else if (h->cfg.precision == PNDF_PREC_F16X3 && h->lo_all_zero)
-            hipLaunchKernelGGL(pndf_fused_split2_softplus_kernel, pgrid, block, pndf_kernel_lds_bytes(), (hipStream_t)stream, a);
-        else if (h->cfg.precision == PNDF_PREC_F16X3)
-            hipLaunchKernelGGL(pndf_fused_split_softplus_kernel, pgrid, block, pndf_kernel_lds_bytes(), (hipStream_t)stream, a);
-        else
-            hipLaunchKernelGGL(pndf_fused_softplus_kernel, pgrid, block, pndf_kernel_lds_bytes(), (hipStream_t)stream, a);
-        HIP_TRY(h, hipGetLastError());
-        if (!capturing) {
-            HIP_TRY(h, hipEventRecord(h->sp_done, (hipStream_t)stream));
-            h->sp_stream = stream;
-            h->sp_pending = true;
-        }
-        return PNDF_OK;
+    if (h->generic) {
+        std::string why;
+        const int grc = pndf_generic_launch(h->generic, mode, q, gout, qo, d, B, steps, stream, why, popt);
+        return grc == PNDF_OK ? PNDF_OK : pndf_fail(h, grc, why);
     }
-    const bool split = h->cfg.precision == PNDF_PREC_F16X3, half = h->cfg.precision == PNDF_PREC_F16;
+    PndfKernelArgs a;
+    a.q_in = q; a.q_out = qo; a.d_out = d; a.grad_out = gout;
+    a.stream = h->d_stream; a.bias = h->d_bias; a.dbg = dbg;
+    a.B = B; a.steps = steps;
+    pndf_fill_step_options(a, mode, popt);
+    a.slope = (h->cfg.act == PNDF_ACT_LRELU) ? 0.01f : 0.0f;   // nn.LeakyReLU() default slope, net_modules.py:31
+    a.beta = h->cfg.beta;
+    a.scratch = softplus ? h->d_scratch : nullptr;
+    a.noenc = (h->cfg.dims[0] == NOENC_IN) ? 1 : 0;
+    // relu family: one workgroup per 64-pose block.  Softplus: a persistent grid, at most one workgroup per CU (a workgroup takes
+    // a whole CU), each walking its blocks; the derivative scratch is indexed by workgroup and was allocated in pndf_create --
+    // nothing is allocated, freed or synchronised here.  The scratch is shared by all launches of the handle: sp_order.
+    // (Instrumented softplus: one workgroup per block like the relu timing kernel, hence B <= 64 * resident_wgs above.)
+    const int64_t nblocks = (B + WG_POSES - 1) / WG_POSES;
+    const dim3 grid((unsigned)(softplus && nblocks > h->resident_wgs ? h->resident_wgs : nblocks)), block(WG_THREADS);
+    if (softplus) HIP_TRY(h, h->sp_order.wait(stream));
     if (timing) {
         void* kargs[] = {&a};
         HIP_TRY(h, hipLaunchKernel(instrumented, grid, block, kargs, pndf_kernel_lds_bytes(), (hipStream_t)stream));
-    } else if (half) hipLaunchKernelGGL(pndf_fused_half_relu_kernel, grid, block, pndf_kernel_lds_bytes(), (hipStream_t)stream, a);
-    else if (h->cfg.precision == PNDF_PREC_BF16) hipLaunchKernelGGL(pndf_fused_bf16_relu_kernel, grid, block, pndf_kernel_lds_bytes(), (hipStream_t)stream, a);
-    else if (split && h->lo_all_zero) hipLaunchKernelGGL(pndf_fused_split2_relu_kernel, grid, block, pndf_kernel_lds_bytes(), (hipStream_t)stream, a);
-    else if (split) hipLaunchKernelGGL(pndf_fused_split_relu_kernel, grid, block, pndf_kernel_lds_bytes(), (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(pndf_fused_relu_kernel, grid, block, pndf_kernel_lds_bytes(), (hipStream_t)stream, a);
+    } else {
+        hipLaunchKernelGGL(fused_kernel(h->cfg.precision, softplus, h->lo_all_zero).fn, grid, block, pndf_kernel_lds_bytes(), (hipStream_t)stream, a);
+    }
     HIP_TRY(h, hipGetLastError());
+    if (softplus) HIP_TRY(h, h->sp_order.record(stream));
     return PNDF_OK;
 }
 
@@ -637,7 +517,7 @@ extern "C" int pndf_project_ex(pndf_handle h, const float* q_in, float* q_out, f
     PndfRange range("pndf_project_ex");
     if (!h) return PNDF_ERR_BAD_ARG;
     pndf_project_options o;
-    if (const char* why = pndf_check_project_options(opt, o)) return fail(h, PNDF_ERR_BAD_ARG, why);
+    if (const char* why = pndf_check_project_options(opt, o)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     return launch(h, MODE_PROJECT, q_in, nullptr, q_out, d_last, B, steps, nullptr, stream, nullptr, &o);
 }
 
@@ -648,7 +528,7 @@ extern "C" int pndf_project_ex(pndf_handle h, const float* q_in, float* q_out, f
 // instrumented by its own debug library and never by the default one.
 extern "C" int pndf_internal_launch(pndf_handle h, int mode, const float* q, const float* gout, float* qo, float* d, int64_t B, int steps,
                                     float* dbg, void* stream, const void* kernel) {
-    if (!kernel) return fail(h, PNDF_ERR_BAD_ARG, "pndf_internal_launch: no kernel");
+    if (!kernel) return pndf_fail(h, PNDF_ERR_BAD_ARG, "pndf_internal_launch: no kernel");
     return launch(h, mode, q, gout, qo, d, B, steps, dbg, stream, kernel);
 }
 // what[0..6] = precision, act, lo_all_zero, noenc, runtime-planned, resident workgroups, LDS bytes of a fused kernel
@@ -663,4 +543,4 @@ extern "C" int pndf_internal_describe(pndf_handle h, int* what, int n) {
     what[6] = pndf_kernel_lds_bytes();
     return PNDF_OK;
 }
-extern "C" int pndf_internal_fail(pndf_handle h, int code, const char* msg) { return fail(h, code, msg ? msg : ""); }
+extern "C" int pndf_internal_fail(pndf_handle h, int code, const char* msg) { return pndf_fail(h, code, msg ? msg : ""); }

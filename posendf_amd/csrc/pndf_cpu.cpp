@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/posendf_amd.h"
+#include "pndf_error.h"
 #include "pndf_layout.h"
 #include "pndf_project_opts.h"
 
@@ -53,13 +54,6 @@ struct pndf_cpu_engine {
 };
 
 namespace {
-
-thread_local std::string g_cpu_create_err;      // (per thread, like pndf_lbs_last_error(nullptr))
-
-int cpu_fail(pndf_cpu_engine* h, int code, const std::string& msg) {
-    (h ? h->err : g_cpu_create_err) = msg;
-    return code;
-}
 
 // y[o][p] = b[o] + sum_i w[o][i] x[i][p]   (four rows of y at a time; the compiler vectorises the p loops)
 __attribute__((target_clones("avx512f", "arch=haswell", "default")))
@@ -265,9 +259,9 @@ void parallel_blocks(int64_t B, F&& body) {
 
 int check(pndf_cpu_engine* h, const void* q, int64_t B) {
     if (!h) return PNDF_ERR_BAD_ARG;
-    if (!h->have_weights) return cpu_fail(h, PNDF_ERR_NO_WEIGHTS, "pndf_cpu_load_weights has not been called");
-    if (B < 0) return cpu_fail(h, PNDF_ERR_BAD_ARG, "negative batch");
-    if (B > 0 && !q) return cpu_fail(h, PNDF_ERR_BAD_ARG, "null pose pointer");
+    if (!h->have_weights) return pndf_fail(h, PNDF_ERR_NO_WEIGHTS, "pndf_cpu_load_weights has not been called");
+    if (B < 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative batch");
+    if (B > 0 && !q) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose pointer");
     return PNDF_OK;
 }
 
@@ -278,31 +272,31 @@ int guarded(pndf_cpu_engine* h, F&& body) {
         body();
         return PNDF_OK;
     } catch (const std::exception& e) {
-        return cpu_fail(h, PNDF_ERR_HOST, std::string("host resource failure: ") + e.what());
+        return pndf_fail(h, PNDF_ERR_HOST, std::string("host resource failure: ") + e.what());
     } catch (...) {
-        return cpu_fail(h, PNDF_ERR_HOST, "host resource failure");
+        return pndf_fail(h, PNDF_ERR_HOST, "host resource failure");
     }
 }
 
 }  // namespace
 
 extern "C" int pndf_cpu_create(pndf_cpu_handle* out, const pndf_config* cfg) {
-    if (!out || !cfg) return cpu_fail(nullptr, PNDF_ERR_BAD_ARG, "null argument");
+    if (!out || !cfg) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_BAD_ARG, "null argument");
     *out = nullptr;
-    if (cfg->act < PNDF_ACT_RELU || cfg->act > PNDF_ACT_SOFTPLUS) return cpu_fail(nullptr, PNDF_ERR_UNSUPPORTED, "unknown activation");
+    if (cfg->act < PNDF_ACT_RELU || cfg->act > PNDF_ACT_SOFTPLUS) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_UNSUPPORTED, "unknown activation");
     if (cfg->num_joints != NJ || cfg->n_dims < 3 || cfg->n_dims > MAXLIN + 1)
-        return cpu_fail(nullptr, PNDF_ERR_UNSUPPORTED, "21 joints and a DFNet of 2 .. 8 linear layers (n_dims 3 .. 9)");
+        return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_UNSUPPORTED, "21 joints and a DFNet of 2 .. 8 linear layers (n_dims 3 .. 9)");
     const int nlin = cfg->n_dims - 1;
     for (int j = 0; j < NJ; ++j)
-        if (cfg->parent[j] != PARENT[j]) return cpu_fail(nullptr, PNDF_ERR_UNSUPPORTED, "parent table other than net_utils.py:46");
-    if (cfg->dims[0] != NFEAT && cfg->dims[0] != NOENC_IN) return cpu_fail(nullptr, PNDF_ERR_UNSUPPORTED, "DFNet in_dim must be 126 (encoder) or 84");
-    if (cfg->dims[nlin] != 1) return cpu_fail(nullptr, PNDF_ERR_UNSUPPORTED, "DFNet must end in one output");
+        if (cfg->parent[j] != PARENT[j]) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_UNSUPPORTED, "parent table other than net_utils.py:46");
+    if (cfg->dims[0] != NFEAT && cfg->dims[0] != NOENC_IN) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_UNSUPPORTED, "DFNet in_dim must be 126 (encoder) or 84");
+    if (cfg->dims[nlin] != 1) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_UNSUPPORTED, "DFNet must end in one output");
     for (int l = 1; l < nlin; ++l)
         if (cfg->dims[l] < 1 || cfg->dims[l] > MAX_WIDTH)      // the same architectures the device engine accepts
-            return cpu_fail(nullptr, PNDF_ERR_UNSUPPORTED, "hidden widths 1 .. 1024");
-    if (cfg->act == PNDF_ACT_SOFTPLUS && !(cfg->beta > 0.f)) return cpu_fail(nullptr, PNDF_ERR_BAD_ARG, "Softplus beta must be positive");
-    if (cfg->enc_act < -1 || cfg->enc_act > PNDF_ACT_SOFTPLUS) return cpu_fail(nullptr, PNDF_ERR_UNSUPPORTED, "unknown encoder activation");
-    if (cfg->enc_act == PNDF_ACT_SOFTPLUS && !(cfg->enc_beta > 0.f) && !(cfg->beta > 0.f)) return cpu_fail(nullptr, PNDF_ERR_BAD_ARG, "Softplus beta of the encoder must be positive");
+            return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_UNSUPPORTED, "hidden widths 1 .. 1024");
+    if (cfg->act == PNDF_ACT_SOFTPLUS && !(cfg->beta > 0.f)) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_BAD_ARG, "Softplus beta must be positive");
+    if (cfg->enc_act < -1 || cfg->enc_act > PNDF_ACT_SOFTPLUS) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_UNSUPPORTED, "unknown encoder activation");
+    if (cfg->enc_act == PNDF_ACT_SOFTPLUS && !(cfg->enc_beta > 0.f) && !(cfg->beta > 0.f)) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_BAD_ARG, "Softplus beta of the encoder must be positive");
     return guarded(nullptr, [&] {
         pndf_cpu_engine* h = new pndf_cpu_engine();
         h->cfg = *cfg;
@@ -318,12 +312,12 @@ extern "C" int pndf_cpu_destroy(pndf_cpu_handle h) {
     return PNDF_OK;
 }
 
-extern "C" const char* pndf_cpu_last_error(pndf_cpu_handle h) { return h ? h->err.c_str() : g_cpu_create_err.c_str(); }
+extern "C" const char* pndf_cpu_last_error(pndf_cpu_handle h) { return pndf_last_error_of(h); }
 
 extern "C" int pndf_cpu_load_weights(pndf_cpu_handle h, const float* const* tensors, const int64_t* numel, int n_tensors) {
     if (!h || !tensors || !numel) return PNDF_ERR_BAD_ARG;
     const int want = (h->encoder ? 4 * NJ : 0) + 2 * h->nlin;
-    if (n_tensors != want) return cpu_fail(h, PNDF_ERR_BAD_SHAPE, "tensor count: " + std::to_string(n_tensors) + ", expected " + std::to_string(want));
+    if (n_tensors != want) return pndf_fail(h, PNDF_ERR_BAD_SHAPE, "tensor count: " + std::to_string(n_tensors) + ", expected " + std::to_string(want));
     h->have_weights = false;      // a failed load leaves no half-loaded engine behind
     int rc = PNDF_OK;
     const int grc = guarded(h, [&] {
@@ -342,10 +336,10 @@ extern "C" int pndf_cpu_load_weights(pndf_cpu_handle h, const float* const* tens
         if (h->encoder)
             for (int j = 0; j < NJ && rc == PNDF_OK; ++j)
                 if (!take(h->enc[j][0], HID, enc_in(j)) || !take(h->enc[j][1], FEAT, HID))
-                    rc = cpu_fail(h, PNDF_ERR_BAD_SHAPE, "encoder tensor " + std::to_string(t) + " has the wrong size");
+                    rc = pndf_fail(h, PNDF_ERR_BAD_SHAPE, "encoder tensor " + std::to_string(t) + " has the wrong size");
         for (int l = 0; l < h->nlin && rc == PNDF_OK; ++l)
             if (!take(h->lin[l], h->dims[l + 1], h->dims[l]))
-                rc = cpu_fail(h, PNDF_ERR_BAD_SHAPE, "dfnet.lin" + std::to_string(l) + " has the wrong size");
+                rc = pndf_fail(h, PNDF_ERR_BAD_SHAPE, "dfnet.lin" + std::to_string(l) + " has the wrong size");
     });
     if (grc != PNDF_OK) return grc;
     if (rc != PNDF_OK) return rc;
@@ -355,7 +349,7 @@ extern "C" int pndf_cpu_load_weights(pndf_cpu_handle h, const float* const* tens
 
 extern "C" int pndf_forward_cpu(pndf_cpu_handle h, const float* q, float* d, int64_t B) {
     if (int rc = check(h, q, B)) return rc;
-    if (B > 0 && !d) return cpu_fail(h, PNDF_ERR_BAD_ARG, "null output pointer");
+    if (B > 0 && !d) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null output pointer");
     return guarded(h, [&] {
         parallel_blocks(B, [&](int64_t p0, int nb, Scratch& S) { forward_grad_block(*h, q + p0 * NQ, nb, nullptr, d + p0, nullptr, false, S); });
     });
@@ -363,7 +357,7 @@ extern "C" int pndf_forward_cpu(pndf_cpu_handle h, const float* q, float* d, int
 
 extern "C" int pndf_forward_grad_cpu(pndf_cpu_handle h, const float* q, const float* grad_out, float* d, float* dq, int64_t B) {
     if (int rc = check(h, q, B)) return rc;
-    if (B > 0 && !dq) return cpu_fail(h, PNDF_ERR_BAD_ARG, "null output pointer");
+    if (B > 0 && !dq) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null output pointer");
     return guarded(h, [&] {
         parallel_blocks(B, [&](int64_t p0, int nb, Scratch& S) {
             float dd[PB];
@@ -375,7 +369,7 @@ extern "C" int pndf_forward_grad_cpu(pndf_cpu_handle h, const float* q, const fl
 
 extern "C" int pndf_project_cpu(pndf_cpu_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps) {
     if (int rc = check(h, q_in, B)) return rc;
-    if (steps < 0 || (B > 0 && !q_out)) return cpu_fail(h, PNDF_ERR_BAD_ARG, "negative step count or null output pointer");
+    if (steps < 0 || (B > 0 && !q_out)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count or null output pointer");
     return guarded(h, [&] {
     parallel_blocks(B, [&](int64_t p0, int nb, Scratch& S) {
         float qb[PB * NQ], dqb[PB * NQ], dd[PB];
@@ -423,10 +417,10 @@ extern "C" int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* 
                                    const pndf_project_options* opt) {
     if (!h) return PNDF_ERR_BAD_ARG;
     pndf_project_options o;
-    if (const char* why = pndf_check_project_options(opt, o)) return cpu_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (const char* why = pndf_check_project_options(opt, o)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (pndf_project_options_plain(o)) return pndf_project_cpu(h, q_in, q_out, d_last, B, steps);
     if (int rc = check(h, q_in, B)) return rc;
-    if (steps < 0 || (B > 0 && !q_out)) return cpu_fail(h, PNDF_ERR_BAD_ARG, "negative step count or null output pointer");
+    if (steps < 0 || (B > 0 && !q_out)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count or null output pointer");
     return guarded(h, [&] {
     parallel_blocks(B, [&](int64_t p0, int nb, Scratch& S) {
         float qb[PB * NQ], dqb[PB * NQ], dd[PB];

@@ -149,26 +149,26 @@ extern "C" __global__ void __launch_bounds__(WG) pndf_denoise_update_kernel(Pndf
 // ------------------------------------------------------------------ C ABI (include/posendf_amd.h)
 extern "C" int pndf_aa2quat(const float* theta, float* q, int64_t N, void* stream) {
     PndfRange range("pndf_aa2quat");
-    if (N < 0 || (N > 0 && (!theta || !q))) return -1;
-    if (((uintptr_t)q) & 15) return -1;
-    if (N == 0) return 0;
+    if (N < 0 || (N > 0 && (!theta || !q))) return PNDF_ERR_BAD_ARG;
+    if (((uintptr_t)q) & 15) return PNDF_ERR_BAD_ARG;
+    if (N == 0) return PNDF_OK;
     DeviceGuard guard(pndf_pointer_device(q));
-    if (!guard.ok) return -3;
+    if (!guard.ok) return PNDF_ERR_HIP;
     const long long items = (long long)N * NJ;
     hipLaunchKernelGGL(pndf_aa2quat_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, theta, q,
                        (long long)N);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return hipGetLastError() == hipSuccess ? PNDF_OK : PNDF_ERR_HIP;
 }
 
 static int denoise_update(const float* theta_in, float* theta_out, const float* theta0, const float* d, const float* dq,
                           float* m, float* v, float* q_next, const float* g_extra, int32_t S, int32_t T,
                           const pndf_denoise_weights& w, int32_t adam_step, float lr, void* stream) {
-    if (S < 0 || T < 0 || adam_step < 1 || (w.prior_power != 1 && w.prior_power != 2)) return -1;
-    if (S == 0 || T == 0) return 0;
-    if (!theta_in || !theta_out || !theta0 || !d || !dq || !m || !v || !q_next || theta_in == theta_out) return -1;
-    if ((((uintptr_t)dq) | ((uintptr_t)q_next)) & 15) return -1;
+    if (S < 0 || T < 0 || adam_step < 1 || (w.prior_power != 1 && w.prior_power != 2)) return PNDF_ERR_BAD_ARG;
+    if (S == 0 || T == 0) return PNDF_OK;
+    if (!theta_in || !theta_out || !theta0 || !d || !dq || !m || !v || !q_next || theta_in == theta_out) return PNDF_ERR_BAD_ARG;
+    if ((((uintptr_t)dq) | ((uintptr_t)q_next)) & 15) return PNDF_ERR_BAD_ARG;
     DeviceGuard guard(pndf_pointer_device(q_next));
-    if (!guard.ok) return -3;
+    if (!guard.ok) return PNDF_ERR_HIP;
     PndfDenoiseArgs a;
     a.theta_in = theta_in; a.theta_out = theta_out; a.theta0 = theta0; a.d = d; a.dq = dq; a.m = m; a.v = v;
     a.q_next = q_next; a.g_extra = g_extra; a.S = S; a.T = T; a.adam_step = adam_step; a.prior_power = w.prior_power;
@@ -176,7 +176,7 @@ static int denoise_update(const float* theta_in, float* theta_out, const float* 
     a.lr = lr; a.beta1 = 0.9f; a.beta2 = 0.999f; a.eps = 1e-8f;       // motion_denoise.py:70, torch.optim.Adam defaults
     const dim3 grid((unsigned)((T + FRAMES_PER_WG - 1) / FRAMES_PER_WG), (unsigned)S);
     hipLaunchKernelGGL(pndf_denoise_update_kernel, grid, dim3(WG), 0, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return hipGetLastError() == hipSuccess ? PNDF_OK : PNDF_ERR_HIP;
 }
 
 // experiments/motion_denoise.py:29-35 at outer iteration `it`; the data term only for it > 0 (:92)
@@ -192,7 +192,7 @@ static pndf_denoise_weights motion_denoise_weights(int32_t it) {
 extern "C" int pndf_denoise_update(const float* theta_in, float* theta_out, const float* theta0, const float* d,
                                    const float* dq, float* m, float* v, float* q_next, int32_t S, int32_t T, int32_t it,
                                    int32_t adam_step, float lr, void* stream) {
-    if (it < 0) return -1;
+    if (it < 0) return PNDF_ERR_BAD_ARG;
     return denoise_update(theta_in, theta_out, theta0, d, dq, m, v, q_next, nullptr, S, T, motion_denoise_weights(it), adam_step,
                           lr, stream);
 }
@@ -201,14 +201,14 @@ extern "C" int pndf_denoise_update_w(const float* theta_in, float* theta_out, co
                                      const float* g_body, float* m, float* v, float* q_next, int32_t S, int32_t T,
                                      const pndf_denoise_weights* w, int32_t adam_step, float lr, void* stream) {
     PndfRange range("pndf_denoise_update_w");
-    if (!w) return -1;
+    if (!w) return PNDF_ERR_BAD_ARG;
     return denoise_update(theta_in, theta_out, theta0, d, dq, m, v, q_next, g_body, S, T, *w, adam_step, lr, stream);
 }
 
 extern "C" int pndf_denoise_update_body(const float* theta_in, float* theta_out, const float* theta0, const float* d,
                                         const float* dq, const float* g_body, float* m, float* v, float* q_next, int32_t S,
                                         int32_t T, int32_t it, int32_t adam_step, float lr, void* stream) {
-    if (!g_body || it < 0) return -1;
+    if (!g_body || it < 0) return PNDF_ERR_BAD_ARG;
     return denoise_update(theta_in, theta_out, theta0, d, dq, m, v, q_next, g_body, S, T, motion_denoise_weights(it), adam_step,
                           lr, stream);
 }

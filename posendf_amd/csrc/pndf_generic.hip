@@ -931,11 +931,7 @@ struct PndfGeneric {
     char* d_enc = nullptr;
     float *d_bias = nullptr, *d_wf = nullptr, *d_wb = nullptr, *d_lb = nullptr, *d_scratch = nullptr;
     bool have_weights = false;
-    // the scratch is shared by all launches of the handle: a launch on another stream than the previous one first waits
-    // (on the device) for that one's completion event, as the softplus engines do
-    hipEvent_t done = nullptr;
-    void* last_stream = nullptr;
-    bool pending = false;
+    PndfScratchOrder order;          // the scratch is shared by all launches of the handle, as the softplus engines' is
 };
 
 bool pndf_generic_needed(const pndf_config& cfg) {
@@ -1061,7 +1057,7 @@ int pndf_generic_create(PndfGeneric** out, const pndf_config& cfg, int resident_
     g->d_wf = g->d_wb = nullptr;      // (one stream: encoder and trunk tiles live in d_enc)
     if (e == hipSuccess) e = hipMalloc((void**)&g->d_lb, g->lbias_floats * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void**)&g->d_scratch, (size_t)resident_wgs * P.wg_tiles * SLOT_F4 * sizeof(f32x4));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&g->done, hipEventDisableTiming);
+    if (e == hipSuccess) e = g->order.create();
     for (const void* kfn : {(const void*)pndf_generic_relu_kernel, (const void*)pndf_generic_softplus_kernel,
                             (const void*)pndf_generic_relu_spenc_kernel, (const void*)pndf_generic_softplus_reluenc_kernel,
                             (const void*)pndf_generic_split_relu_kernel, (const void*)pndf_generic_split_softplus_kernel,
@@ -1078,7 +1074,7 @@ int pndf_generic_create(PndfGeneric** out, const pndf_config& cfg, int resident_
 
 void pndf_generic_destroy(PndfGeneric* g) {
     if (!g) return;
-    if (g->done) (void)hipEventDestroy(g->done);
+    g->order.destroy();
     for (void* p : {(void*)g->d_enc, (void*)g->d_bias, (void*)g->d_wf, (void*)g->d_wb, (void*)g->d_lb, (void*)g->d_scratch})
         if (p) (void)hipFree(p);
     delete g;
@@ -1106,25 +1102,11 @@ int pndf_generic_load(PndfGeneric* g, const float* const* tensors, const int64_t
             return PNDF_ERR_BAD_SHAPE;
         }
     }
-    // precision f16x3 / f16: the trunk on split-precision fp16 MFMAs -- the weights of layer l travel as s_l W, s_l = the power of two
-    // that brings the layer's largest |weight| into [2^12, 2^13) (pndf_capi.hip "split-precision stream").  A layer without a finite
-    // non-zero weight cannot be scaled: such a network runs the exact fp32 kernels, whatever precision was asked for.
+    // precision f16x3 / f16: the trunk on split-precision fp16 MFMAs -- the weights of layer l travel as s_l W (pndf_pack::layer_scale).
+    // A layer without a finite non-zero weight cannot be scaled: such a network runs the exact fp32 kernels, whatever precision was asked for.
     float wscale[PNDF_GEN_MAXLIN];
     bool split = g->cfg.precision != PNDF_PREC_FP32;
-    for (int l = 0; l < L && split; ++l) {
-        float mx = 0.f;
-        bool nan = false;
-        const int64_t n = (int64_t)g->cfg.dims[l] * g->cfg.dims[l + 1];
-        for (int64_t i = 0; i < n; ++i) {
-            const float a = fabsf(lin[2 * l][i]);
-            nan |= (a != a);
-            if (a > mx) mx = a;
-        }
-        if (nan || !(mx > 0x1p-100f && mx < 0x1p100f)) { split = false; break; }
-        int e;
-        (void)frexpf(mx, &e);                            // mx = f * 2^e, f in [0.5, 1)
-        wscale[l] = ldexpf(1.0f, 13 - e);                // s_l * mx in [2^12, 2^13)
-    }
+    for (int l = 0; l < L && split; ++l) split = pndf_pack::layer_scale(lin[2 * l], (int64_t)g->cfg.dims[l] * g->cfg.dims[l + 1], &wscale[l]);
     gen_plan(g, split);
     PndfGenericArgs& P = g->plan;
     const size_t step_tiles = (size_t)P.w_slots * SLOT_TILES;
@@ -1163,10 +1145,7 @@ int pndf_generic_load(PndfGeneric* g, const float* const* tensors, const int64_t
     }
     for (int l = 0; l < 8; ++l) bias[SCALE_OFF + l] = 1.0f;
     if (g->enc) {
-        for (int j = 0; j < NJ; ++j) {
-            memcpy(bias.data() + ENCB_OFF + 32 * j, tensors[4 * j + 1], sizeof(float) * HID);
-            memcpy(bias.data() + ENCB_OFF + 32 * j + 16 + ENC_FEAT_ROW, tensors[4 * j + 3], sizeof(float) * FEAT);
-        }
+        pndf_pack::emit_encoder_biases(tensors, bias.data());
         pndf_pack::emit_encoder_sections(tensors, stream.data(), stream.data() + ((size_t)ENC_TILES_PADDED + g->trunk_tiles) * TILE_FLOATS);
     }
     // replica of the first slots behind the stream: the ring's fetch offset never wraps inside a step
@@ -1192,33 +1171,21 @@ int pndf_generic_launch(PndfGeneric* g, int mode, const float* q, const float* g
     PndfGenericArgs a = g->plan;
     a.q_in = q; a.q_out = qo; a.d_out = d; a.grad_out = gout;
     a.enc_stream = g->d_enc; a.bias = g->d_bias; a.wfwd = nullptr; a.wbwd = nullptr; a.lbias = g->d_lb; a.scratch = g->d_scratch;
-    // pndf_project_ex: the options' own mode only when one of them differs from its default (else the plain loop, bit for bit)
-    const bool plain = !popt || mode != MODE_PROJECT || pndf_project_options_plain(*popt);
-    a.B = B; a.steps = steps; a.mode = plain ? mode : MODE_PROJECT_OPT;
-    a.renorm = plain ? 0 : popt->renorm;
-    a.step_size = plain ? 1.0f : popt->step_size;
-    a.tol = plain ? 0.0f : popt->tol;
+    a.B = B; a.steps = steps;
+    pndf_fill_step_options(a, mode, popt);
     a.slope = (g->cfg.act == PNDF_ACT_LRELU) ? 0.01f : 0.0f;      // nn.LeakyReLU() default slope, net_modules.py:31
     a.beta = g->cfg.beta;
     a.enc_slope = (gen_enc_act(g->cfg) == PNDF_ACT_LRELU) ? 0.01f : 0.0f;
     a.enc_beta = gen_enc_beta(g->cfg);
     const int64_t nblocks = (B + WG_POSES - 1) / WG_POSES;
     const dim3 grid((unsigned)(nblocks < g->resident ? nblocks : g->resident)), block(WG_THREADS);
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing((hipStream_t)stream, &cap);
-    const bool capturing = cap != hipStreamCaptureStatusNone;
-    hipError_t e = hipSuccess;
-    if (g->pending && g->last_stream != stream && !capturing) e = hipStreamWaitEvent((hipStream_t)stream, g->done, 0);
+    hipError_t e = g->order.wait(stream);
     if (e == hipSuccess) {
         const char* name = "";
         hipLaunchKernelGGL(gen_kernel(g->cfg, g->split, &name), grid, block, LDS_TOTAL, (hipStream_t)stream, a);
         e = hipGetLastError();
     }
-    if (e == hipSuccess && !capturing) {
-        e = hipEventRecord(g->done, (hipStream_t)stream);
-        g->last_stream = stream;
-        g->pending = true;
-    }
+    if (e == hipSuccess) e = g->order.record(stream);
     if (e != hipSuccess) { err = std::string("runtime-planned DFNet launch: ") + hipGetErrorString(e); return PNDF_ERR_HIP; }
     return PNDF_OK;
 }

@@ -2,6 +2,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <string>
+
+#include "../../include/posendf_amd.h"
+#include "pndf_error.h"
+
 // Every entry point runs on the device that owns its buffers and leaves the caller's current device as it found it
 // (torch keeps a per-thread current device; an engine for cuda:1 must not change what torch.cuda.current_device() says).
 struct DeviceGuard {
@@ -29,6 +34,82 @@ inline int pndf_pointer_device(const void* p) {
     }
     return attr.device;
 }
+
+// A failed HIP call ends the entry point with PNDF_ERR_HIP and the call's own text on the handle `h` (pndf_error.h)
+#define HIP_TRY(h, expr)                                                                          \
+    do {                                                                                          \
+        hipError_t e_ = (expr);                                                                   \
+        if (e_ != hipSuccess)                                                                     \
+            return pndf_fail(h, PNDF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+// after the launches of an entry point: PNDF_OK, or PNDF_ERR_HIP with "<what>: <the runtime's text>" on the handle
+template <class H>
+PNDF_LOCAL inline int pndf_check_launch(H* h, const char* what) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return pndf_fail(h, PNDF_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    return PNDF_OK;
+}
+
+// Is `device` a gfx950 device, and what are its properties?  `who` ("the engine", "training", ...) names the caller in the text.
+// PNDF_ANY_DEVICE asks only whether the runtime sees a device at all (the pose index learns its device from a pointer afterwards).
+// Every refusal clears the runtime's sticky error.  `verbose`: pndf_create's wording, which names the failed call and the
+// architecture it found.
+constexpr int PNDF_ANY_DEVICE = -0x7fffffff - 1;
+struct PNDF_LOCAL PndfDeviceCheck {
+    int code = PNDF_OK;
+    std::string text;
+    hipDeviceProp_t prop;
+};
+PNDF_LOCAL inline PndfDeviceCheck pndf_check_gfx950(int device, const char* who, bool verbose = false) {
+    PndfDeviceCheck r;
+    auto refuse = [&r](int code, const std::string& text) -> PndfDeviceCheck& {
+        (void)hipGetLastError();
+        r.code = code;
+        r.text = text;
+        return r;
+    };
+    const bool any = device == PNDF_ANY_DEVICE;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || (!any && (device < 0 || device >= ndev)))
+        return refuse(PNDF_ERR_NO_DEVICE, "no HIP device " + (any ? std::string() : std::to_string(device) + " ") + "(" + who + " has no CPU fallback)");
+    if (any) return r;
+    const hipError_t e = hipGetDeviceProperties(&r.prop, device);
+    if (e != hipSuccess && verbose) return refuse(PNDF_ERR_HIP, std::string("hipGetDeviceProperties(&prop, device): ") + hipGetErrorString(e));
+    if (e != hipSuccess || std::string(r.prop.gcnArchName).rfind("gfx950", 0) != 0)
+        return refuse(PNDF_ERR_NO_DEVICE, (verbose ? std::string("device is ") + r.prop.gcnArchName + ", " : std::string()) + "kernels are built for gfx950 only");
+    return r;
+}
+
+// Launches of one handle that share a scratch buffer: a launch on another stream than the previous one first waits (on the
+// device) for that one's completion event.  wait() goes before the launch, record() after it; a capturing stream is left alone
+// (a captured graph replays in the order it was captured).
+struct PNDF_LOCAL PndfScratchOrder {
+    hipEvent_t done = nullptr;
+    void* last_stream = nullptr;
+    bool pending = false, capturing = false;
+    hipError_t create() { return hipEventCreateWithFlags(&done, hipEventDisableTiming); }
+    void destroy() {
+        if (done) (void)hipEventDestroy(done);
+        done = nullptr;
+    }
+    hipError_t wait(void* stream) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        (void)hipStreamIsCapturing((hipStream_t)stream, &cap);
+        capturing = cap != hipStreamCaptureStatusNone;
+        if (pending && last_stream != stream && !capturing) return hipStreamWaitEvent((hipStream_t)stream, done, 0);
+        return hipSuccess;
+    }
+    hipError_t record(void* stream) {
+        if (capturing) return hipSuccess;
+        const hipError_t e = hipEventRecord(done, (hipStream_t)stream);
+        if (e == hipSuccess) {
+            last_stream = stream;
+            pending = true;
+        }
+        return e;
+    }
+};
 
 // roctx ranges around the C-ABI compute entry points: `rocprofv3 --marker-trace` then shows
 // pndf_forward / pndf_forward_grad / pndf_project / pndf_lbs_terms_grad ... as named host ranges next to the kernels they

@@ -264,13 +264,6 @@ __global__ void __launch_bounds__(256) pndf_knn_merge_kernel(MergeArgs a) {
 }
 
 namespace {
-thread_local std::string g_knn_err;
-
-int knn_fail(pndf_knn_index* h, int code, const std::string& msg) {
-    if (h) h->err = msg; else g_knn_err = msg;
-    return code;
-}
-
 struct Plan {
     int KM;
     int64_t qb, S, tps;
@@ -305,33 +298,29 @@ void launch(const pndf_knn_index* h, const KnnArgs& a, const MergeArgs& m, hipSt
 }
 }  // namespace
 
-extern "C" const char* pndf_knn_last_error(pndf_knn_handle h) { return h ? h->err.c_str() : g_knn_err.c_str(); }
+extern "C" const char* pndf_knn_last_error(pndf_knn_handle h) { return pndf_last_error_of(h); }
 
 extern "C" int pndf_knn_create(pndf_knn_handle* out, const float* poses, int64_t N, int32_t metric, const float* weights,
                                void* stream) {
-    if (!out) return knn_fail(nullptr, PNDF_ERR_BAD_ARG, "out is null");
+    if (!out) return pndf_fail<pndf_knn_index>(nullptr, PNDF_ERR_BAD_ARG, "out is null");
     *out = nullptr;
-    if (metric != 0 && metric != 1) return knn_fail(nullptr, PNDF_ERR_UNSUPPORTED, "metric: 0 = geo or 1 = euc");
-    if (N < 1) return knn_fail(nullptr, PNDF_ERR_BAD_ARG, "the index needs N >= 1 poses");
-    if (N >= ((int64_t)1 << 31)) return knn_fail(nullptr, PNDF_ERR_UNSUPPORTED, "N must be below 2^31");
-    if (!poses) return knn_fail(nullptr, PNDF_ERR_BAD_ARG, "poses is null");
-    if ((uintptr_t)poses & 15) return knn_fail(nullptr, PNDF_ERR_BAD_ARG, "poses must be 16-byte aligned");
+    if (metric != 0 && metric != 1) return pndf_fail<pndf_knn_index>(nullptr, PNDF_ERR_UNSUPPORTED, "metric: 0 = geo or 1 = euc");
+    if (N < 1) return pndf_fail<pndf_knn_index>(nullptr, PNDF_ERR_BAD_ARG, "the index needs N >= 1 poses");
+    if (N >= ((int64_t)1 << 31)) return pndf_fail<pndf_knn_index>(nullptr, PNDF_ERR_UNSUPPORTED, "N must be below 2^31");
+    if (!poses) return pndf_fail<pndf_knn_index>(nullptr, PNDF_ERR_BAD_ARG, "poses is null");
+    if ((uintptr_t)poses & 15) return pndf_fail<pndf_knn_index>(nullptr, PNDF_ERR_BAD_ARG, "poses must be 16-byte aligned");
     if (weights)
         for (int j = 0; j < NJ; ++j)
             if (!(weights[j] > 0.f) || !std::isfinite(weights[j]))
-                return knn_fail(nullptr, PNDF_ERR_BAD_ARG, "joint weights must be finite and > 0");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-        (void)hipGetLastError();
-        return knn_fail(nullptr, PNDF_ERR_NO_DEVICE, "no HIP device (the pose index has no CPU fallback)");
-    }
+                return pndf_fail<pndf_knn_index>(nullptr, PNDF_ERR_BAD_ARG, "joint weights must be finite and > 0");
+    const PndfDeviceCheck any = pndf_check_gfx950(PNDF_ANY_DEVICE, "the pose index");
+    if (any.code != PNDF_OK) return pndf_fail<pndf_knn_index>(nullptr, any.code, any.text);
     const int device = pndf_pointer_device(poses);
-    if (device < 0) return knn_fail(nullptr, PNDF_ERR_BAD_ARG, "poses is not device memory");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
-        return knn_fail(nullptr, PNDF_ERR_NO_DEVICE, "kernels are built for gfx950 only");
+    if (device < 0) return pndf_fail<pndf_knn_index>(nullptr, PNDF_ERR_BAD_ARG, "poses is not device memory");
+    const PndfDeviceCheck dev = pndf_check_gfx950(device, "the pose index");
+    if (dev.code != PNDF_OK) return pndf_fail<pndf_knn_index>(nullptr, dev.code, dev.text);
     DeviceGuard guard(device);
-    if (!guard.ok) return knn_fail(nullptr, PNDF_ERR_HIP, "hipSetDevice failed");
+    if (!guard.ok) return pndf_fail<pndf_knn_index>(nullptr, PNDF_ERR_HIP, "hipSetDevice failed");
     pndf_knn_index* h = new pndf_knn_index();
     h->device = device;
     h->N = N;
@@ -342,7 +331,7 @@ extern "C" int pndf_knn_create(pndf_knn_handle* out, const float* poses, int64_t
     if (hipMalloc((void**)&h->db, (size_t)n_out * sizeof(float)) != hipSuccess) {
         (void)hipGetLastError();
         delete h;
-        return knn_fail(nullptr, PNDF_ERR_HIP, "hipMalloc of the packed index (" + std::to_string(n_out * 4) + " B) failed");
+        return pndf_fail<pndf_knn_index>(nullptr, PNDF_ERR_HIP, "hipMalloc of the packed index (" + std::to_string(n_out * 4) + " B) failed");
     }
     hipLaunchKernelGGL(pndf_knn_pack_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, (hipStream_t)stream, poses,
                        h->db, N, n_out);
@@ -352,7 +341,7 @@ extern "C" int pndf_knn_create(pndf_knn_handle* out, const float* poses, int64_t
         const std::string msg = std::string("packing the index: ") + hipGetErrorString(e);
         (void)hipFree(h->db);
         delete h;
-        return knn_fail(nullptr, PNDF_ERR_HIP, msg);
+        return pndf_fail<pndf_knn_index>(nullptr, PNDF_ERR_HIP, msg);
     }
     *out = h;
     return PNDF_OK;
@@ -378,18 +367,18 @@ extern "C" int64_t pndf_knn_workspace_bytes(pndf_knn_handle h, int64_t Q, int32_
 extern "C" int pndf_knn_search(pndf_knn_handle h, const float* q, int64_t Q, int32_t k, float* vals, long long* idx,
                                void* workspace, void* stream) {
     PndfRange range("pndf_knn_search");
-    if (k < 1 || k > MAX_K) return knn_fail(h, PNDF_ERR_BAD_ARG, "k must be in 1 .. 16, got " + std::to_string(k));
-    if (Q < 0) return knn_fail(h, PNDF_ERR_BAD_ARG, "Q must be >= 0");
+    if (k < 1 || k > MAX_K) return pndf_fail(h, PNDF_ERR_BAD_ARG, "k must be in 1 .. 16, got " + std::to_string(k));
+    if (Q < 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "Q must be >= 0");
     if (((uintptr_t)q & 15) || ((uintptr_t)vals & 3) || ((uintptr_t)idx & 7) || ((uintptr_t)workspace & 15))
-        return knn_fail(h, PNDF_ERR_BAD_ARG, "misaligned pointer: q and workspace 16 B, vals 4 B, idx 8 B");
-    if (!h) return knn_fail(nullptr, PNDF_ERR_BAD_ARG, "null index handle");
+        return pndf_fail(h, PNDF_ERR_BAD_ARG, "misaligned pointer: q and workspace 16 B, vals 4 B, idx 8 B");
+    if (!h) return pndf_fail<pndf_knn_index>(nullptr, PNDF_ERR_BAD_ARG, "null index handle");
     if (k > h->N)
-        return knn_fail(h, PNDF_ERR_BAD_ARG, "k = " + std::to_string(k) + " exceeds the index size " + std::to_string(h->N));
+        return pndf_fail(h, PNDF_ERR_BAD_ARG, "k = " + std::to_string(k) + " exceeds the index size " + std::to_string(h->N));
     if (Q == 0) return PNDF_OK;
-    if (!q || !vals || !idx || !workspace) return knn_fail(h, PNDF_ERR_BAD_ARG, "q, vals, idx and workspace must be non-null");
-    if (Q >= ((int64_t)1 << 31)) return knn_fail(h, PNDF_ERR_UNSUPPORTED, "Q must be below 2^31 per call");
+    if (!q || !vals || !idx || !workspace) return pndf_fail(h, PNDF_ERR_BAD_ARG, "q, vals, idx and workspace must be non-null");
+    if (Q >= ((int64_t)1 << 31)) return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "Q must be below 2^31 per call");
     DeviceGuard guard(h->device);
-    if (!guard.ok) return knn_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
+    if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     const Plan p = make_plan(Q, h->N, k);
     KnnArgs a;
     a.db = h->db; a.q = q;
@@ -407,7 +396,5 @@ extern "C" int pndf_knn_search(pndf_knn_handle h, const float* q, int64_t Q, int
         case 8: launch<8>(h, a, m, st); break;
         default: launch<16>(h, a, m, st); break;
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return knn_fail(h, PNDF_ERR_HIP, std::string("pndf_knn_search: ") + hipGetErrorString(e));
-    return PNDF_OK;
+    return pndf_check_launch(h, "pndf_knn_search");
 }

@@ -1431,13 +1431,7 @@ static void lbs_pack_split(const float* blob, int NG, float p_scale, float w_sca
     }
 }
 
-static thread_local std::string g_lbs_create_err;
-static int lbs_fail(pndf_lbs_model* h, int code, const std::string& msg) {
-    if (h) h->err = msg; else g_lbs_create_err = msg;
-    return code;
-}
-
-extern "C" const char* pndf_lbs_last_error(pndf_lbs_handle h) { return h ? h->err.c_str() : g_lbs_create_err.c_str(); }
+extern "C" const char* pndf_lbs_last_error(pndf_lbs_handle h) { return pndf_last_error_of(h); }
 
 extern "C" int64_t pndf_lbs_packed_floats(int32_t V) { return V < 1 ? 0 : (int64_t)((V + GV - 1) / GV) * BLOB; }
 
@@ -1548,25 +1542,22 @@ extern "C" int pndf_lbs_pack_split_host(int32_t V, const float* blob, void* sblo
 extern "C" int pndf_lbs_create(pndf_lbs_handle* out, int32_t V, int32_t NB, const float* v_template, const float* shapedirs,
                                const float* betas, const float* posedirs, const float* J_regressor, const int32_t* parents,
                                const float* lbs_weights, const int32_t* extra_joint_vertex, int32_t n_extra, int device) {
-    if (!out) return lbs_fail(nullptr, PNDF_ERR_BAD_ARG, "out is null");
+    if (!out) return pndf_fail<pndf_lbs_model>(nullptr, PNDF_ERR_BAD_ARG, "out is null");
     *out = nullptr;
-    if (V < 1) return lbs_fail(nullptr, PNDF_ERR_BAD_ARG, "V < 1");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return lbs_fail(nullptr, PNDF_ERR_NO_DEVICE, "no HIP device " + std::to_string(device) + " (the body model has no CPU fallback)");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
-        return lbs_fail(nullptr, PNDF_ERR_NO_DEVICE, "kernels are built for gfx950 only");
+    if (V < 1) return pndf_fail<pndf_lbs_model>(nullptr, PNDF_ERR_BAD_ARG, "V < 1");
+    const PndfDeviceCheck dev = pndf_check_gfx950(device, "the body model");
+    if (dev.code != PNDF_OK) return pndf_fail<pndf_lbs_model>(nullptr, dev.code, dev.text);
+    const hipDeviceProp_t& prop = dev.prop;
     const int NG = (V + GV - 1) / GV;
     std::vector<float> blob((size_t)NG * BLOB);
     float J[NJ * 3], rel[NJ * 3];
     const int rc = pndf_lbs_pack_host(V, NB, v_template, shapedirs, betas, posedirs, J_regressor, parents, lbs_weights,
                                       extra_joint_vertex, n_extra, blob.data(), J, rel);
     if (rc == PNDF_ERR_UNSUPPORTED)
-        return lbs_fail(nullptr, rc, "kinematic tree: 24 joints, parents[0] = -1 and every parent before its children (SMPL)");
-    if (rc != PNDF_OK) return lbs_fail(nullptr, rc, "null pointer, or an extra-joint vertex outside [0, V) or named twice, or more than 32 of them");
+        return pndf_fail<pndf_lbs_model>(nullptr, rc, "kinematic tree: 24 joints, parents[0] = -1 and every parent before its children (SMPL)");
+    if (rc != PNDF_OK) return pndf_fail<pndf_lbs_model>(nullptr, rc, "null pointer, or an extra-joint vertex outside [0, V) or named twice, or more than 32 of them");
     DeviceGuard guard(device);
-    if (!guard.ok) return lbs_fail(nullptr, PNDF_ERR_HIP, "hipSetDevice failed");
+    if (!guard.ok) return pndf_fail<pndf_lbs_model>(nullptr, PNDF_ERR_HIP, "hipSetDevice failed");
     pndf_lbs_model* h = new pndf_lbs_model();
     h->device = device; h->V = V; h->NG = NG; h->NE = n_extra;
     h->sm_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -1591,7 +1582,7 @@ extern "C" int pndf_lbs_create(pndf_lbs_handle* out, int32_t V, int32_t NB, cons
             hipMemcpy(h->d_picked, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
             if (h->d_picked) (void)hipFree(h->d_picked);
             delete h;
-            return lbs_fail(nullptr, PNDF_ERR_HIP, "pndf_lbs_create: picked-joint table");
+            return pndf_fail<pndf_lbs_model>(nullptr, PNDF_ERR_HIP, "pndf_lbs_create: picked-joint table");
         }
     }
     h->smpl_tree = true;
@@ -1632,7 +1623,7 @@ extern "C" int pndf_lbs_create(pndf_lbs_handle* out, int32_t V, int32_t NB, cons
         if (h->d_sblob) (void)hipFree(h->d_sblob);
         if (h->d_picked) (void)hipFree(h->d_picked);
         delete h;
-        return lbs_fail(nullptr, PNDF_ERR_HIP, m);
+        return pndf_fail<pndf_lbs_model>(nullptr, PNDF_ERR_HIP, m);
     }
     *out = h;
     return PNDF_OK;
@@ -1650,7 +1641,7 @@ extern "C" int pndf_lbs_destroy(pndf_lbs_handle h) {
 
 extern "C" int pndf_lbs_set_precision(pndf_lbs_handle h, int32_t precision) {
     if (!h) return PNDF_ERR_BAD_ARG;
-    if (precision != PNDF_LBS_FP32 && precision != PNDF_LBS_F16X3) return lbs_fail(h, PNDF_ERR_BAD_ARG, "precision: PNDF_LBS_FP32 or PNDF_LBS_F16X3");
+    if (precision != PNDF_LBS_FP32 && precision != PNDF_LBS_F16X3) return pndf_fail(h, PNDF_ERR_BAD_ARG, "precision: PNDF_LBS_FP32 or PNDF_LBS_F16X3");
     h->precision = precision;
     return PNDF_OK;
 }
@@ -1712,22 +1703,20 @@ extern "C" int64_t pndf_lbs_workspace_floats(pndf_lbs_handle h, int32_t S, int32
 }
 
 static int lbs_launch(pndf_lbs_model* h, int mode, PndfLbsArgs& a, void* workspace, void* stream) {
-    if (((uintptr_t)workspace) & 15) return lbs_fail(h, PNDF_ERR_BAD_ARG, "workspace must be 16-byte aligned");
+    if (((uintptr_t)workspace) & 15) return pndf_fail(h, PNDF_ERR_BAD_ARG, "workspace must be 16-byte aligned");
     a.blob = h->d_blob; a.V = h->V; a.NG = h->NG; a.NE = h->NE; a.model = h->consts;
     const bool split = h->precision == PNDF_LBS_F16X3 && mode != 2;
     PndfLbsSplitArgs sa;
     memset(&sa, 0, sizeof(sa));
     (void)lbs_workspace(h, a.S, a.T, &a, (float*)workspace, mode, &sa);
     DeviceGuard guard(h->device);
-    if (!guard.ok) return lbs_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
+    if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     const long long N = (long long)a.S * a.T;
     const dim3 fgrid((unsigned)((N + 63) / 64)), fblock(64);
     if (mode == 0 && !a.verts && a.joints) {      // joints only: the chain + the picked vertices alone (lbs_joints_only_body)
         if (h->smpl_tree) hipLaunchKernelGGL(pndf_lbs_joints_only_smpl_kernel, fgrid, fblock, 0, (hipStream_t)stream, a, (const float*)h->d_picked);
         else hipLaunchKernelGGL(pndf_lbs_joints_only_kernel, fgrid, fblock, 0, (hipStream_t)stream, a, (const float*)h->d_picked);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return lbs_fail(h, PNDF_ERR_HIP, std::string("launch: ") + hipGetErrorString(e));
-        return PNDF_OK;
+        return pndf_check_launch(h, "launch");
     }
     const dim3 vgrid((unsigned)(((long long)a.S * a.cps + 3) / 4), (unsigned)(mode == 0 ? 1 : a.vsplit)), vblock(256);
     const int lds = 3 * BLOB * (int)sizeof(float);
@@ -1760,9 +1749,7 @@ static int lbs_launch(pndf_lbs_model* h, int mode, PndfLbsArgs& a, void* workspa
                 hipLaunchKernelGGL(pndf_lbs_rodrigues_vjp_kernel, dim3((unsigned)((N * (NJ - 1) + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
             } else hipLaunchKernelGGL(pndf_lbs_pose_backward_kernel, fgrid, fblock, 0, (hipStream_t)stream, a);
         }
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return lbs_fail(h, PNDF_ERR_HIP, std::string("launch: ") + hipGetErrorString(e));
-        return PNDF_OK;
+        return pndf_check_launch(h, "launch");
     }
     if (h->smpl_tree) hipLaunchKernelGGL(pndf_lbs_pose_smpl_kernel, fgrid, fblock, 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(pndf_lbs_pose_kernel, fgrid, fblock, 0, (hipStream_t)stream, a);
@@ -1778,9 +1765,7 @@ static int lbs_launch(pndf_lbs_model* h, int mode, PndfLbsArgs& a, void* workspa
             hipLaunchKernelGGL(pndf_lbs_rodrigues_vjp_kernel, dim3((unsigned)((N * (NJ - 1) + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
         } else hipLaunchKernelGGL(pndf_lbs_pose_backward_kernel, fgrid, fblock, 0, (hipStream_t)stream, a);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return lbs_fail(h, PNDF_ERR_HIP, std::string("launch: ") + hipGetErrorString(e));
-    return PNDF_OK;
+    return pndf_check_launch(h, "launch");
 }
 
 static void lbs_clear(PndfLbsArgs& a) { memset(&a, 0, sizeof(a)); }
@@ -1789,9 +1774,9 @@ extern "C" int pndf_lbs_forward(pndf_lbs_handle h, const float* theta, int64_t N
                                 void* stream) {
     PndfRange range("pndf_lbs_forward");
     if (!h) return PNDF_ERR_BAD_ARG;
-    if (N < 0 || N > 0x7fffffff) return lbs_fail(h, PNDF_ERR_BAD_ARG, "bad frame count");
+    if (N < 0 || N > 0x7fffffff) return pndf_fail(h, PNDF_ERR_BAD_ARG, "bad frame count");
     if (N == 0) return PNDF_OK;
-    if (!theta || !workspace || (!verts && !joints)) return lbs_fail(h, PNDF_ERR_BAD_ARG, "null pointer");
+    if (!theta || !workspace || (!verts && !joints)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pointer");
     PndfLbsArgs a;
     lbs_clear(a);
     a.theta = theta; a.verts = verts; a.joints = joints; a.S = 1; a.T = (int)N;
@@ -1802,10 +1787,10 @@ extern "C" int pndf_lbs_terms_grad_w(pndf_lbs_handle h, const float* theta, cons
                                      float temp_coef, float data_coef, float* g_theta, void* workspace, void* stream) {
     PndfRange range("pndf_lbs_terms_grad_w");
     if (!h) return PNDF_ERR_BAD_ARG;
-    if (S < 0 || T < 0) return lbs_fail(h, PNDF_ERR_BAD_ARG, "negative size");
+    if (S < 0 || T < 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative size");
     if (S == 0 || T == 0) return PNDF_OK;
     const bool data = data_coef != 0.f;
-    if (!theta || !g_theta || !workspace || (data && !joints0)) return lbs_fail(h, PNDF_ERR_BAD_ARG, "null pointer");
+    if (!theta || !g_theta || !workspace || (data && !joints0)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pointer");
     PndfLbsArgs a;
     lbs_clear(a);
     a.theta = theta; a.joints0 = joints0; a.g_theta = g_theta; a.S = S; a.T = T; a.it_gt0 = data ? 1 : 0;
@@ -1818,7 +1803,7 @@ extern "C" int pndf_lbs_terms_grad_w(pndf_lbs_handle h, const float* theta, cons
 extern "C" int pndf_lbs_terms_grad(pndf_lbs_handle h, const float* theta, const float* joints0, int32_t S, int32_t T, int32_t it,
                                    float* g_theta, void* workspace, void* stream) {
     if (!h) return PNDF_ERR_BAD_ARG;
-    if (it < 0) return lbs_fail(h, PNDF_ERR_BAD_ARG, "negative iteration");
+    if (it < 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative iteration");
     // motion_denoise.py:31-32: temp 10 (1 + it), data 100 / (1 + it) for it > 0 (:92)
     return pndf_lbs_terms_grad_w(h, theta, joints0, S, T, 10.0f * (float)(1 + it), it > 0 ? 100.0f / (float)(1 + it) : 0.0f, g_theta,
                                  workspace, stream);
@@ -1828,9 +1813,9 @@ extern "C" int pndf_lbs_backward(pndf_lbs_handle h, const float* theta, const fl
                                  float* g_theta, void* workspace, void* stream) {
     PndfRange range("pndf_lbs_backward");
     if (!h) return PNDF_ERR_BAD_ARG;
-    if (N < 0 || N > 0x7fffffff) return lbs_fail(h, PNDF_ERR_BAD_ARG, "bad frame count");
+    if (N < 0 || N > 0x7fffffff) return pndf_fail(h, PNDF_ERR_BAD_ARG, "bad frame count");
     if (N == 0) return PNDF_OK;
-    if (!theta || !g_theta || !workspace) return lbs_fail(h, PNDF_ERR_BAD_ARG, "null pointer");
+    if (!theta || !g_theta || !workspace) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pointer");
     PndfLbsArgs a;
     lbs_clear(a);
     a.theta = theta; a.g_verts = g_verts; a.g_joints = g_joints; a.g_theta = g_theta; a.S = 1; a.T = (int)N;

@@ -1,12 +1,16 @@
 // Host-side packing helpers shared by the C-ABI translation units (pndf_capi.hip: the amass.yaml streams; pndf_generic.hip:
 // runtime-planned networks): logical matrix views and the lane-linear 16 x 16 tile both kernel families read.
 #pragma once
+#include <math.h>
 #include <stddef.h>
+#include <stdint.h>
+#include <string.h>
 
 #include "pndf_layout.h"
 
 namespace pndf_pack {
 using namespace pndf;
+#define PNDF_PACK_LOCAL __attribute__((visibility("hidden")))      // (not an export of the library)
 
 struct Mat {          // logical matrix view M[r][c] of dfnet.lin{l}.weight, optionally transposed, zero padded
     const float* w;   // (out, in) row-major
@@ -24,19 +28,62 @@ inline void emit_tile(const Mat& m, int nt, int kt, float* dst) {
         for (int s = 0; s < 4; ++s) dst[lane * 4 + s] = m.at(16 * nt + (lane & 15), 16 * kt + 4 * (lane >> 4) + s);
 }
 
+// Exact power-of-two scaling of a layer's weights for the split-precision streams (pndf_kernel_split.hip, "operand scaling"): the
+// weights travel as s W with s = the power of two that brings the layer's largest |weight| into [2^12, 2^13) -- the hi halves cannot
+// overflow and the lo halves of all weights down to 2^-14 of the largest stay in fp16's normal range.  False: the layer has no
+// finite non-zero weight and cannot be scaled.
+PNDF_PACK_LOCAL inline bool layer_scale(const float* w, int64_t n, float* scale) {
+    float mx = 0.f;
+    bool nan = false;
+    for (int64_t i = 0; i < n; ++i) {
+        const float a = fabsf(w[i]);
+        nan |= (a != a);
+        if (a > mx) mx = a;
+    }
+    if (nan || !(mx > 0x1p-100f && mx < 0x1p100f)) return false;
+    int e;
+    (void)frexpf(mx, &e);                  // mx = f * 2^e, f in [0.5, 1)
+    *scale = ldexpf(1.0f, 13 - e);         // s * mx in [2^12, 2^13)
+    return true;
+}
+
+// fp32 -> bfloat16 bits, round to nearest even (the packers' inputs are finite: a layer that is not has no layer_scale)
+PNDF_PACK_LOCAL inline uint16_t bf16_bits(float w) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, w);
+    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+
 // split-precision block (pndf_layout.h "split-precision stream"): hi tile then lo tile of (16 rows x 32 k), 8 halfs per lane each,
 //   block(M, nt, kb)[lane * 8 + jj] = scale * M[16 nt + (lane & 15)][16 (2 kb + (jj >> 2)) + 4 (lane >> 4) + (jj & 3)]
-// hi = the value rounded to nearest even, lo = the remainder rounded to nearest (pndf_capi.hip emit_pair: the amass.yaml stream)
-inline void emit_pair_f16(const Mat& m, int nt, int kb, float scale, float* dst) {
+// hi = the value rounded to nearest even, lo = the remainder rounded to nearest; returns whether any lo half is non-zero.
+// `bf16` (precision bf16, the one-term comparison kernel): the hi tile holds bfloat16 bits, the lo tile zeros.
+PNDF_PACK_LOCAL inline bool emit_pair_f16(const Mat& m, int nt, int kb, float scale, float* dst, bool bf16 = false) {
     _Float16* hi = (_Float16*)dst;
     _Float16* lo = (_Float16*)(dst + TILE_FLOATS);
+    bool any_lo = false;
     for (int lane = 0; lane < 64; ++lane)
         for (int jj = 0; jj < 8; ++jj) {
             const float w = scale * m.at(16 * nt + (lane & 15), 16 * (2 * kb + (jj >> 2)) + 4 * (lane >> 4) + (jj & 3));
-            const _Float16 h = (_Float16)w;
-            hi[lane * 8 + jj] = h;
-            lo[lane * 8 + jj] = (_Float16)(w - (float)h);
+            _Float16& h = hi[lane * 8 + jj];
+            _Float16& l = lo[lane * 8 + jj];
+            if (bf16) {
+                h = __builtin_bit_cast(_Float16, bf16_bits(w));
+                l = (_Float16)0;
+                continue;
+            }
+            h = (_Float16)w;
+            l = (_Float16)(w - (float)h);
+#ifdef PNDF_EXP_LO_BITS                     // (energy experiment, profiles/r05/energy_breakdown.txt: the lo half keeps this many
+            {                               // explicit mantissa bits -- does the matrix pipe pay for operand bits that toggle?)
+                uint16_t u = __builtin_bit_cast(uint16_t, l);
+                const int drop = 10 - PNDF_EXP_LO_BITS;
+                u = (uint16_t)((u + (1u << (drop - 1))) & ~((1u << drop) - 1));
+                l = __builtin_bit_cast(_Float16, u);
+            }
+#endif
+            any_lo |= (l != (_Float16)0);
         }
+    return any_lo;
 }
 
 // 16x16 logical matrices of one encoder joint (zero padded), see pndf_layout.h "encoder on the MFMA pipe"
@@ -71,4 +118,13 @@ inline void emit_encoder_sections(const float* const* tensors, float* fwd, float
             emit_enc_tile(EncMat{tensors[4 * j], tensors[4 * j + 2], enc_in(j), kind}, bwd);
 }
 
+// the encoder's rows of the bias block: per joint b1 padded to 16, b2 on rows 4..9 of 16
+PNDF_PACK_LOCAL inline void emit_encoder_biases(const float* const* tensors, float* bias) {
+    for (int j = 0; j < NJ; ++j) {
+        memcpy(bias + ENCB_OFF + 32 * j, tensors[4 * j + 1], sizeof(float) * HID);
+        memcpy(bias + ENCB_OFF + 32 * j + 16 + ENC_FEAT_ROW, tensors[4 * j + 3], sizeof(float) * FEAT);
+    }
+}
+
+#undef PNDF_PACK_LOCAL
 }  // namespace pndf_pack

@@ -105,33 +105,33 @@ __global__ void __launch_bounds__(256, 1) probe_ring(const char* stream, int pas
 // counter rate in MHz, out[5] = hops timed per footprint; with n_out >= 8 also out[6], out[7]: the weight ring alone (below).
 // Returns 0 or a negative pndf_status.
 extern "C" int pndf_debug_mem_probe(int device, double* out, int n_out) {
-    if (!out || n_out < 6) return -1;
+    if (!out || n_out < 6) return PNDF_ERR_BAD_ARG;
     DeviceGuard guard(device);
-    if (!guard.ok) return -3;
+    if (!guard.ok) return PNDF_ERR_HIP;
     int rate_khz = 0;
     if (hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || rate_khz <= 0) rate_khz = 100000;
     const size_t bytes = (size_t)1 << 30;
     uint32_t* buf = nullptr;
     unsigned long long* ticks = nullptr;
     uint32_t* sink = nullptr;
-    if (hipMalloc((void**)&buf, bytes) != hipSuccess) return -3;
-    int rc = 0;
-    if (hipMalloc((void**)&ticks, 64) != hipSuccess || hipMalloc((void**)&sink, 64) != hipSuccess) rc = -3;
+    if (hipMalloc((void**)&buf, bytes) != hipSuccess) return PNDF_ERR_HIP;
+    int rc = PNDF_OK;
+    if (hipMalloc((void**)&ticks, 64) != hipSuccess || hipMalloc((void**)&sink, 64) != hipSuccess) rc = PNDF_ERR_HIP;
     const int hops = 4096;
     const size_t foot[3] = {(size_t)1 << 20, (size_t)64 << 20, bytes};
-    for (int f = 0; f < 3 && rc == 0; ++f) {
+    for (int f = 0; f < 3 && rc == PNDF_OK; ++f) {
         const uint32_t n = (uint32_t)(foot[f] / (LINE_WORDS * 4));
         hipLaunchKernelGGL(probe_fill, dim3((n + 255) / 256), dim3(256), 0, 0, buf, n);
         // bring the footprint into the level it fits in: two streaming passes over it (the 1 GiB one fits in none)
         for (int pass = 0; pass < 2; ++pass)
             hipLaunchKernelGGL(probe_stream, dim3(1024), dim3(256), 0, 0, (const f4*)buf, foot[f] / 16, (float*)sink);
         hipLaunchKernelGGL(probe_chase, dim3(1), dim3(64), 0, 0, buf, hops, ticks, sink);
-        if (hipGetLastError() != hipSuccess) { rc = -3; break; }
+        if (hipGetLastError() != hipSuccess) { rc = PNDF_ERR_HIP; break; }
         unsigned long long t = 0;
-        if (hipMemcpy(&t, ticks, sizeof(t), hipMemcpyDeviceToHost) != hipSuccess) { rc = -3; break; }
+        if (hipMemcpy(&t, ticks, sizeof(t), hipMemcpyDeviceToHost) != hipSuccess) { rc = PNDF_ERR_HIP; break; }
         out[f] = (double)t / hops * 1e6 / rate_khz;      // ticks per hop -> ns
     }
-    if (rc == 0) {
+    if (rc == PNDF_OK) {
         hipEvent_t e0, e1;
         (void)hipEventCreate(&e0);
         (void)hipEventCreate(&e1);
@@ -141,14 +141,14 @@ extern "C" int pndf_debug_mem_probe(int device, double* out, int n_out) {
             hipLaunchKernelGGL(probe_stream, dim3(2048), dim3(256), 0, 0, (const f4*)buf, bytes / 16, (float*)sink);
         (void)hipEventRecord(e1, 0);
         float ms = 0.f;
-        if (hipGetLastError() != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess || ms <= 0.f) rc = -3;
+        if (hipGetLastError() != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess || ms <= 0.f) rc = PNDF_ERR_HIP;
         else out[3] = 3.0 * (double)bytes / (ms * 1e-3) / 1e9;
         (void)hipEventDestroy(e0);
         (void)hipEventDestroy(e1);
     }
     out[4] = rate_khz / 1e3;
     out[5] = hops;
-    if (rc == 0 && n_out >= 8) {
+    if (rc == PNDF_OK && n_out >= 8) {
         // out[6] = GB/s that ONE compute unit pulls through its LDS ring while all of them do (the fused f16x3 kernel needs ~51),
         // out[7] = ns per 16-KiB slot.  Mean over the workgroups, one per CU.
         hipDeviceProp_t prop;
@@ -156,14 +156,14 @@ extern "C" int pndf_debug_mem_probe(int device, double* out, int n_out) {
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
         unsigned long long* tk = nullptr;
         const int passes = 8;
-        if (hipMalloc((void**)&tk, (size_t)cus * sizeof(unsigned long long)) != hipSuccess) rc = -3;
-        if (rc == 0 && hipFuncSetAttribute((const void*)probe_ring, hipFuncAttributeMaxDynamicSharedMemorySize, PR_SLOTS * PR_SLOT) != hipSuccess) rc = -3;
-        if (rc == 0) {
+        if (hipMalloc((void**)&tk, (size_t)cus * sizeof(unsigned long long)) != hipSuccess) rc = PNDF_ERR_HIP;
+        if (rc == PNDF_OK && hipFuncSetAttribute((const void*)probe_ring, hipFuncAttributeMaxDynamicSharedMemorySize, PR_SLOTS * PR_SLOT) != hipSuccess) rc = PNDF_ERR_HIP;
+        if (rc == PNDF_OK) {
             hipLaunchKernelGGL(probe_ring, dim3(cus), dim3(256), PR_SLOTS * PR_SLOT, 0, (const char*)buf, 1, tk);      // warm
             hipLaunchKernelGGL(probe_ring, dim3(cus), dim3(256), PR_SLOTS * PR_SLOT, 0, (const char*)buf, passes, tk);
             std::vector<unsigned long long> h(cus);
-            if (hipGetLastError() != hipSuccess) rc = -3;
-            else if (hipMemcpy(h.data(), tk, (size_t)cus * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) rc = -3;
+            if (hipGetLastError() != hipSuccess) rc = PNDF_ERR_HIP;
+            else if (hipMemcpy(h.data(), tk, (size_t)cus * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) rc = PNDF_ERR_HIP;
             else {
                 double sum = 0;
                 for (int i = 0; i < cus; ++i) sum += (double)h[i];
@@ -184,9 +184,9 @@ extern "C" int pndf_debug_mem_probe(int device, double* out, int n_out) {
 // compute unit, synchronous.  tools/power_window.py --ring-only reads the package power while it runs: what delivering the weight
 // stream into LDS costs in energy with nothing else going on.  Returns seconds per pass in *sec_per_pass (may be NULL).
 extern "C" int pndf_debug_ring_stream(int device, int passes, double* sec_per_pass) {
-    if (passes <= 0) return -1;
+    if (passes <= 0) return PNDF_ERR_BAD_ARG;
     DeviceGuard guard(device);
-    if (!guard.ok) return -3;
+    if (!guard.ok) return PNDF_ERR_HIP;
     int rate_khz = 0;
     if (hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || rate_khz <= 0) rate_khz = 100000;
     hipDeviceProp_t prop;
@@ -198,20 +198,20 @@ extern "C" int pndf_debug_ring_stream(int device, int passes, double* sec_per_pa
     unsigned long long* tk = nullptr;
     const size_t bytes = (size_t)(PR_STREAM_SLOTS + PR_SLOTS) * PR_SLOT;
     if (cus > 1024) cus = 1024;
-    int rc = 0;
-    if (hipMalloc((void**)&buf, bytes) != hipSuccess || hipMalloc((void**)&tk, 1024 * sizeof(unsigned long long)) != hipSuccess) rc = -3;
-    if (rc == 0) {
+    int rc = PNDF_OK;
+    if (hipMalloc((void**)&buf, bytes) != hipSuccess || hipMalloc((void**)&tk, 1024 * sizeof(unsigned long long)) != hipSuccess) rc = PNDF_ERR_HIP;
+    if (rc == PNDF_OK) {
         hipLaunchKernelGGL(probe_fill_random, dim3(1024), dim3(256), 0, 0, (uint32_t*)buf, bytes / 4);
-        if (hipGetLastError() != hipSuccess) rc = -3;
+        if (hipGetLastError() != hipSuccess) rc = PNDF_ERR_HIP;
     }
-    if (rc == 0 && hipFuncSetAttribute((const void*)probe_ring, hipFuncAttributeMaxDynamicSharedMemorySize, PR_SLOTS * PR_SLOT) != hipSuccess) rc = -3;
-    if (rc == 0) {
+    if (rc == PNDF_OK && hipFuncSetAttribute((const void*)probe_ring, hipFuncAttributeMaxDynamicSharedMemorySize, PR_SLOTS * PR_SLOT) != hipSuccess) rc = PNDF_ERR_HIP;
+    if (rc == PNDF_OK) {
         hipLaunchKernelGGL(probe_ring, dim3(cus), dim3(256), PR_SLOTS * PR_SLOT, 0, (const char*)buf, passes, tk);
-        if (hipGetLastError() != hipSuccess) rc = -3;
+        if (hipGetLastError() != hipSuccess) rc = PNDF_ERR_HIP;
     }
     unsigned long long t = 0;
-    if (rc == 0 && hipMemcpy(&t, tk, sizeof(t), hipMemcpyDeviceToHost) != hipSuccess) rc = -3;      // (synchronises: the kernel's own errors surface here)
-    if (rc == 0 && sec_per_pass) *sec_per_pass = (double)t / (rate_khz * 1e3) / passes;
+    if (rc == PNDF_OK && hipMemcpy(&t, tk, sizeof(t), hipMemcpyDeviceToHost) != hipSuccess) rc = PNDF_ERR_HIP;      // (synchronises: the kernel's own errors surface here)
+    if (rc == PNDF_OK && sec_per_pass) *sec_per_pass = (double)t / (rate_khz * 1e3) / passes;
     if (tk) (void)hipFree(tk);
     if (buf) (void)hipFree(buf);
     return rc;

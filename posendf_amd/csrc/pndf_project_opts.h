@@ -4,6 +4,7 @@
 #include <math.h>
 
 #include "../../include/posendf_amd.h"
+#include "pndf_args.h"
 
 // null = the defaults.  Returns nullptr and fills `out`, or the reason the struct is refused.
 inline const char* pndf_check_project_options(const pndf_project_options* opt, pndf_project_options& out) {
@@ -25,4 +26,16 @@ inline const char* pndf_check_project_options(const pndf_project_options* opt, p
 // the defaults give the plain step of pndf_project, whatever else the struct says
 inline bool pndf_project_options_plain(const pndf_project_options& o) {
     return o.step_size == 1.0f && o.renorm == PNDF_RENORM_NONE && !(o.tol > 0.0f);
+}
+
+// mode / renorm / step_size / tol of a kernel-argument struct (PndfKernelArgs, PndfGenericArgs) for a launch in `mode` with the
+// validated options `popt` (null = none): the options' own mode only when one of them differs from its default, else the plain
+// loop, bit for bit
+template <class Args>
+inline void pndf_fill_step_options(Args& a, int mode, const pndf_project_options* popt) {
+    const bool plain = !popt || mode != MODE_PROJECT || pndf_project_options_plain(*popt);
+    a.mode = plain ? mode : MODE_PROJECT_OPT;
+    a.renorm = plain ? 0 : popt->renorm;
+    a.step_size = plain ? 1.0f : popt->step_size;
+    a.tol = plain ? 0.0f : popt->tol;
 }

@@ -100,21 +100,21 @@ extern "C" __global__ void __launch_bounds__(WG) pndf_quat_topk_kernel(PndfQuatD
 extern "C" int pndf_quat_topk(const float* noise, const float* valid, int64_t B, int32_t K, int32_t metric,
                               const float* weights, int32_t k, float* vals, long long* idx, void* stream) {
     PndfRange range("pndf_quat_topk");
-    if (B < 0 || K < 1 || k < 1 || k > K || k > MAX_K_OUT || (metric != 0 && metric != 1)) return -1;
-    if (B == 0) return 0;
-    if (!noise || !valid || !vals || !idx) return -1;
-    if ((((uintptr_t)noise) | ((uintptr_t)valid)) & 15) return -1;
+    if (B < 0 || K < 1 || k < 1 || k > K || k > MAX_K_OUT || (metric != 0 && metric != 1)) return PNDF_ERR_BAD_ARG;
+    if (B == 0) return PNDF_OK;
+    if (!noise || !valid || !vals || !idx) return PNDF_ERR_BAD_ARG;
+    if ((((uintptr_t)noise) | ((uintptr_t)valid)) & 15) return PNDF_ERR_BAD_ARG;
     const size_t lds = ((size_t)K * NJ + ((K + 3) & ~3) + NJ * 4 + 24 + 8) * sizeof(float);
-    if (lds > 160 * 1024) return -4;                  // K <= ~1,850 candidates per query
+    if (lds > 160 * 1024) return PNDF_ERR_UNSUPPORTED;     // K <= ~1,850 candidates per query
     DeviceGuard guard(pndf_pointer_device(valid));
-    if (!guard.ok) return -3;
+    if (!guard.ok) return PNDF_ERR_HIP;
     // the dynamic-LDS limit is a per-device function attribute; setting it is a host-side table write (no device work), so
     // it is simply set on every call: no shared state between threads, no bound on the device index
     if (hipFuncSetAttribute((const void*)pndf_quat_topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-        return -3;
+        return PNDF_ERR_HIP;
     PndfQuatDistArgs a;
     a.noise = noise; a.valid = valid; a.vals = vals; a.idx = idx; a.K = K; a.k = k; a.metric = metric;
     for (int j = 0; j < NJ; ++j) a.w[j] = weights ? weights[j] : 1.0f / (float)NJ;
     hipLaunchKernelGGL(pndf_quat_topk_kernel, dim3((unsigned)B), dim3(WG), lds, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return hipGetLastError() == hipSuccess ? PNDF_OK : PNDF_ERR_HIP;
 }

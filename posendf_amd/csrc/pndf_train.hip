@@ -663,12 +663,6 @@ struct pndf_train_plan {
 
 namespace {
 
-thread_local std::string g_train_create_err;
-int train_fail(pndf_train_plan* h, int code, const std::string& msg) {
-    if (h) h->err = msg; else g_train_create_err = msg;
-    return code;
-}
-
 int64_t align64(int64_t x) { return (x + 63) / 64 * 64; }
 
 Layout make_layout(const pndf_train_plan* h, int64_t B, int64_t Bm, int eik) {
@@ -757,42 +751,30 @@ PtrTable ptr_table(const pndf_train_plan* h, const float* const* tensors) {
 
 unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
 
-int check_launch(pndf_train_plan* h, const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return train_fail(h, PNDF_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-    return PNDF_OK;
-}
-
 }  // namespace
 
-extern "C" const char* pndf_train_last_error(pndf_train_handle h) { return h ? h->err.c_str() : g_train_create_err.c_str(); }
+extern "C" const char* pndf_train_last_error(pndf_train_handle h) { return pndf_last_error_of(h); }
 
 extern "C" int pndf_train_create(pndf_train_handle* out, const pndf_config* cfg, int device) {
-    if (!out || !cfg) return train_fail(nullptr, PNDF_ERR_BAD_ARG, "out / cfg is null");
+    if (!out || !cfg) return pndf_fail<pndf_train_plan>(nullptr, PNDF_ERR_BAD_ARG, "out / cfg is null");
     *out = nullptr;
     if (cfg->act < PNDF_ACT_RELU || cfg->act > PNDF_ACT_SOFTPLUS)
-        return train_fail(nullptr, PNDF_ERR_UNSUPPORTED, "activation: relu, lrelu or softplus");
-    if (cfg->enc_act > PNDF_ACT_SOFTPLUS) return train_fail(nullptr, PNDF_ERR_UNSUPPORTED, "encoder activation: relu, lrelu or softplus");
-    if (cfg->num_joints != NJ) return train_fail(nullptr, PNDF_ERR_UNSUPPORTED, "num_joints must be 21");
+        return pndf_fail<pndf_train_plan>(nullptr, PNDF_ERR_UNSUPPORTED, "activation: relu, lrelu or softplus");
+    if (cfg->enc_act > PNDF_ACT_SOFTPLUS) return pndf_fail<pndf_train_plan>(nullptr, PNDF_ERR_UNSUPPORTED, "encoder activation: relu, lrelu or softplus");
+    if (cfg->num_joints != NJ) return pndf_fail<pndf_train_plan>(nullptr, PNDF_ERR_UNSUPPORTED, "num_joints must be 21");
     if (cfg->dims[0] != ENC_IN)
-        return train_fail(nullptr, PNDF_ERR_UNSUPPORTED,
+        return pndf_fail<pndf_train_plan>(nullptr, PNDF_ERR_UNSUPPORTED,
                           "training needs the structure encoder (model.StrEnc.use: True, dims[0] = 126): the reference's train=True "
                           "branch cannot run without it either (man_pose_in is unbound)");
     if (cfg->n_dims < 3 || cfg->n_dims > MAX_LIN + 1 || cfg->dims[cfg->n_dims - 1] != 1)
-        return train_fail(nullptr, PNDF_ERR_UNSUPPORTED, "DFNet: 1 .. 7 hidden layers and one output");
+        return pndf_fail<pndf_train_plan>(nullptr, PNDF_ERR_UNSUPPORTED, "DFNet: 1 .. 7 hidden layers and one output");
     for (int i = 1; i < cfg->n_dims - 1; ++i)
-        if (cfg->dims[i] < 1 || cfg->dims[i] > 1024) return train_fail(nullptr, PNDF_ERR_UNSUPPORTED, "hidden widths 1 .. 1024");
+        if (cfg->dims[i] < 1 || cfg->dims[i] > 1024) return pndf_fail<pndf_train_plan>(nullptr, PNDF_ERR_UNSUPPORTED, "hidden widths 1 .. 1024");
     for (int j = 0; j < NJ; ++j)
         if (cfg->parent[j] >= j || cfg->parent[j] < -1)
-            return train_fail(nullptr, PNDF_ERR_UNSUPPORTED, "parent table: every parent before its child");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        (void)hipGetLastError();
-        return train_fail(nullptr, PNDF_ERR_NO_DEVICE, "no HIP device " + std::to_string(device) + " (training has no CPU fallback)");
-    }
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
-        return train_fail(nullptr, PNDF_ERR_NO_DEVICE, "kernels are built for gfx950 only");
+            return pndf_fail<pndf_train_plan>(nullptr, PNDF_ERR_UNSUPPORTED, "parent table: every parent before its child");
+    const PndfDeviceCheck dev = pndf_check_gfx950(device, "training");
+    if (dev.code != PNDF_OK) return pndf_fail<pndf_train_plan>(nullptr, dev.code, dev.text);
     pndf_train_plan* h = new pndf_train_plan();
     h->device = device;
     h->L = cfg->n_dims - 1;
@@ -835,15 +817,15 @@ extern "C" int pndf_train_forward(pndf_train_handle h, const float* const* weigh
                                   const float* q_man, int64_t B, int64_t Bm, int32_t loss_type, int32_t eikonal, float* losses,
                                   void* workspace, void* stream) {
     if (!h) return PNDF_ERR_BAD_ARG;
-    if (!weights || !q || !dist_gt || !q_man || !losses || !workspace) return train_fail(h, PNDF_ERR_BAD_ARG, "null pointer");
-    if (B < 1 || Bm < 1) return train_fail(h, PNDF_ERR_BAD_ARG, "B and Bm must be >= 1");
-    if (loss_type != LOSS_L1 && loss_type != LOSS_L2) return train_fail(h, PNDF_ERR_BAD_ARG, "loss_type: 0 (l1) or 1 (l2)");
-    if (((uintptr_t)workspace & 15) != 0) return train_fail(h, PNDF_ERR_BAD_ARG, "workspace must be 16-byte aligned");
+    if (!weights || !q || !dist_gt || !q_man || !losses || !workspace) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pointer");
+    if (B < 1 || Bm < 1) return pndf_fail(h, PNDF_ERR_BAD_ARG, "B and Bm must be >= 1");
+    if (loss_type != LOSS_L1 && loss_type != LOSS_L2) return pndf_fail(h, PNDF_ERR_BAD_ARG, "loss_type: 0 (l1) or 1 (l2)");
+    if (((uintptr_t)workspace & 15) != 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "workspace must be 16-byte aligned");
     for (int i = 0; i < ENC_TENSORS + 2 * h->L; ++i)
-        if (!weights[i]) return train_fail(h, PNDF_ERR_BAD_ARG, "null weight tensor " + std::to_string(i));
+        if (!weights[i]) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null weight tensor " + std::to_string(i));
     PndfRange range("pndf_train_forward");
     DeviceGuard guard(h->device);
-    if (!guard.ok) return train_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
+    if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     const int eik = eikonal ? 1 : 0;
     const Layout l = make_layout(h, B, Bm, eik);
     {
@@ -896,25 +878,25 @@ extern "C" int pndf_train_forward(pndf_train_handle h, const float* const* weigh
     }
     hipLaunchKernelGGL(pndf_train_loss_kernel, dim3(1), dim3(256), 0, st, ws + l.act[h->L], ws + l.dgt, eik ? ws + l.eikp : nullptr,
                        B, Bm, (int)loss_type, eik, losses);
-    return check_launch(h, "pndf_train_forward");
+    return pndf_check_launch(h, "pndf_train_forward");
 }
 
 extern "C" int pndf_train_backward(pndf_train_handle h, const float* const* weights, const float* upstream, float* const* grads,
                                    void* workspace, void* stream) {
     if (!h) return PNDF_ERR_BAD_ARG;
-    if (!weights || !upstream || !grads || !workspace) return train_fail(h, PNDF_ERR_BAD_ARG, "null pointer");
+    if (!weights || !upstream || !grads || !workspace) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pointer");
     Shape s;
     {
         std::lock_guard<std::mutex> lk(h->mu);
         auto it = h->shapes.find(workspace);
-        if (it == h->shapes.end()) return train_fail(h, PNDF_ERR_BAD_ARG, "workspace was not filled by pndf_train_forward of this handle");
+        if (it == h->shapes.end()) return pndf_fail(h, PNDF_ERR_BAD_ARG, "workspace was not filled by pndf_train_forward of this handle");
         s = it->second;
     }
     for (int i = 0; i < ENC_TENSORS + 2 * h->L; ++i)
-        if (!weights[i] || !grads[i]) return train_fail(h, PNDF_ERR_BAD_ARG, "null weight / gradient tensor " + std::to_string(i));
+        if (!weights[i] || !grads[i]) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null weight / gradient tensor " + std::to_string(i));
     PndfRange range("pndf_train_backward");
     DeviceGuard guard(h->device);
-    if (!guard.ok) return train_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
+    if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     const int64_t B = s.B, Bm = s.Bm;
     const int eik = s.eik;
     const Layout l = make_layout(h, B, Bm, eik);
@@ -966,5 +948,5 @@ extern "C" int pndf_train_backward(pndf_train_handle h, const float* const* weig
     for (int k = 0; k < ENC_TENSORS; ++k) gtab.p[k] = grads[k];
     for (int k = 0; k <= ENC_TENSORS; ++k) gtab.off[k] = h->enc_tensor_off[k];
     hipLaunchKernelGGL(pndf_train_enc_reduce_kernel, dim3(blocks(h->enc_params)), dim3(256), 0, st, gtab, ws + l.part, l.enc_wgs);
-    return check_launch(h, "pndf_train_backward");
+    return pndf_check_launch(h, "pndf_train_backward");
 }

@@ -433,3 +433,107 @@ def test_kernel_only_entry_points_refuse_host_tensors(lib, monkeypatch):
     monkeypatch.setattr(lib, "pndf_debug_timing_regions", reached, raising=False)
     with pytest.raises(engine.PndfError, match="pndf_debug_project_timing runs on the HIP kernel only"):
         eng.project_timing(q.reshape(1, 84))
+
+
+# ---- the error channel (csrc/pndf_error.h): one slot per handle family and thread for refusals without a handle, the handle's own
+# text otherwise.  Codes and texts below are the ones the library gave before the five copies of the channel became one.
+_LAST_ERROR = {"engine": "pndf_last_error", "train": "pndf_train_last_error", "knn": "pndf_knn_last_error",
+               "lbs": "pndf_lbs_last_error", "cpu": "pndf_cpu_last_error"}
+
+
+def _refused_creates(lib):
+    """family -> [(call, code, text)]: creates refused by an argument check, before any device is looked for"""
+    from posendf_amd.engine import PndfConfig
+    h = ctypes.c_void_p()
+    cfg = PndfConfig()
+    lib.pndf_default_config(ctypes.byref(cfg), 1, 100.0)
+    shallow = PndfConfig()
+    lib.pndf_default_config(ctypes.byref(shallow), 1, 100.0)
+    shallow.n_dims = 2
+    noenc = PndfConfig()
+    lib.pndf_default_config(ctypes.byref(noenc), 1, 100.0)
+    noenc.dims[0] = 84
+    keep = (h, cfg, shallow, noenc)      # (the closures below hold the ctypes objects alive)
+    return {
+        "engine": [(lambda: lib.pndf_create(None, ctypes.byref(cfg), 0), -1, b"out is null", keep),
+                   (lambda: lib.pndf_create(ctypes.byref(h), ctypes.byref(shallow), 0), -4,
+                    b"DFNet depth: n_dims must be 3 .. 9 (1 .. 7 hidden layers + the output layer)", keep)],
+        "train": [(lambda: lib.pndf_train_create(ctypes.byref(h), ctypes.byref(noenc), 0), -4,
+                   b"training needs the structure encoder (model.StrEnc.use: True, dims[0] = 126): the reference's train=True "
+                   b"branch cannot run without it either (man_pose_in is unbound)", keep)],
+        "knn": [(lambda: lib.pndf_knn_create(ctypes.byref(h), None, 1, 2, None, None), -4, b"metric: 0 = geo or 1 = euc", keep)],
+        "lbs": [(lambda: lib.pndf_lbs_create(ctypes.byref(h), 0, 0, *([None] * 8), 0, 0), -1, b"V < 1", keep)],
+        "cpu": [(lambda: lib.pndf_cpu_create(ctypes.byref(h), None), -1, b"null argument", keep)],
+    }
+
+
+def _null_slots(lib):
+    return {fam: getattr(lib, fn)(None) for fam, fn in _LAST_ERROR.items()}
+
+
+def test_refused_creates_keep_their_codes_texts_and_slots(lib):
+    """Every family's refusal gives the pinned code and text in its OWN null-handle slot and leaves the other four slots as
+    they were (a failed pndf_knn_create does not change what pndf_last_error(NULL) returns)."""
+    cases = _refused_creates(lib)
+    assert set(cases) == set(_LAST_ERROR)
+    for fam in cases:      # give every slot a text of its own first, so "unchanged" means something
+        for call, _, _, _ in cases[fam]:
+            call()
+    for fam, calls in cases.items():
+        for call, code, text, _ in calls:
+            before = _null_slots(lib)
+            assert call() == code, fam
+            after = _null_slots(lib)
+            assert after[fam] == text, (fam, after[fam])
+            for other in _LAST_ERROR:
+                if other != fam:
+                    assert after[other] == before[other], (fam, other)
+
+
+def test_null_handle_slots_are_per_thread(lib):
+    import threading
+    cases = _refused_creates(lib)
+    for fam, calls in cases.items():
+        calls[0][0]()
+        mine = _null_slots(lib)
+        seen = {}
+
+        def other_thread():
+            seen["before"] = _null_slots(lib)[fam]
+            seen["code"] = calls[-1][0]()
+            seen["after"] = _null_slots(lib)[fam]
+        # (engine: the other thread's refusal has another text than this thread's, so a shared slot would show)
+        t = threading.Thread(target=other_thread)
+        t.start()
+        t.join()
+        assert seen["before"] == b"", (fam, seen)      # a fresh thread starts with empty slots
+        assert seen["code"] < 0 and seen["after"] != b""
+        assert _null_slots(lib) == mine, fam
+
+
+def test_handle_errors_stay_on_the_handle(lib):
+    """A compute call on a pndf_cpu handle before pndf_cpu_load_weights: the text is the handle's, the null slot is untouched."""
+    from posendf_amd.engine import PndfConfig
+    lib.pndf_cpu_create(ctypes.byref(ctypes.c_void_p()), None)
+    null_before = lib.pndf_cpu_last_error(None)
+    assert null_before == b"null argument"
+    cfg = PndfConfig()
+    lib.pndf_default_config(ctypes.byref(cfg), 1, 100.0)
+    h = ctypes.c_void_p()
+    assert lib.pndf_cpu_create(ctypes.byref(h), ctypes.byref(cfg)) == 0 and h.value
+    try:
+        assert lib.pndf_cpu_last_error(h) == b""
+        q = np.zeros((1, 84), np.float32)
+        d = np.zeros(1, np.float32)
+        assert lib.pndf_forward_cpu(h, q.ctypes.data, d.ctypes.data, 1) == -5      # PNDF_ERR_NO_WEIGHTS
+        assert lib.pndf_cpu_last_error(h) == b"pndf_cpu_load_weights has not been called"
+        assert lib.pndf_cpu_last_error(None) == null_before
+    finally:
+        lib.pndf_cpu_destroy(h)
+
+
+def test_stateless_calls_return_the_named_codes(lib):
+    """pndf_quat_topk with k > K is PNDF_ERR_BAD_ARG (-1) and pndf_aa2quat with N = 0 is PNDF_OK (0): both return before any
+    device is looked for.  (test_stream_handle_and_checked_wrappers reaches the drivers' own checks, not these.)"""
+    assert lib.pndf_quat_topk(None, None, 1, 4, 0, None, 5, None, None, None) == -1
+    assert lib.pndf_aa2quat(None, None, 0, None) == 0
