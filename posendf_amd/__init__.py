@@ -16,6 +16,9 @@ def __getattr__(name):   # torch is imported lazily so that numpy-only users (or
     if name in ("Trainer", "PoseDataset"):
         from . import trainer
         return getattr(trainer, name)
+    if name == "PoseCompletion":
+        from .pose_completion import PoseCompletion
+        return PoseCompletion
     if name == "BodyModel":
         from .body_model import BodyModel
         return BodyModel
@@ -25,5 +28,5 @@ def __getattr__(name):   # torch is imported lazily so that numpy-only users (or
     raise AttributeError(name)
 
 
-__all__ = ["PoseNDF", "gradient", "BodyModel", "PoseIndex", "Trainer", "PoseDataset", "ImageFit", "PerspectiveCamera", "keypoint_term",
+__all__ = ["PoseNDF", "gradient", "BodyModel", "PoseIndex", "Trainer", "PoseDataset", "ImageFit", "PerspectiveCamera", "keypoint_term", "PoseCompletion",
            "amass_config", "load_config", "synth"]

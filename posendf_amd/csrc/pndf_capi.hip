@@ -17,6 +17,7 @@
 #include "pndf_pack.h"
 #include "pndf_generic.h"
 #include "pndf_project_opts.h"
+#include "pndf_complete.h"
 
 using namespace pndf;
 
@@ -519,6 +520,43 @@ extern "C" int pndf_project_ex(pndf_handle h, const float* q_in, float* q_out, f
     pndf_project_options o;
     if (const char* why = pndf_check_project_options(opt, o)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     return launch(h, MODE_PROJECT, q_in, nullptr, q_out, d_last, B, steps, nullptr, stream, nullptr, &o);
+}
+
+// Pose completion (include/posendf_amd_completion.h; DESIGN.md section 2 "Pose completion"): the projection loop with the observed
+// joints held, as `steps` times { pndf_forward_grad ; the step kernel of pndf_complete.hip } on the caller's stream.  Everything is
+// validated before the first enqueue; pndf_forward_grad orders the softplus scratch across streams as for any other caller.  The
+// last iteration writes its distances straight to d_last when the caller wants them.
+extern "C" int pndf_complete(pndf_handle h, const float* q_in, const uint32_t* observed, float* q_out, float* d_last, int64_t B,
+                             int steps, const pndf_project_options* opt, void* workspace, void* stream) {
+    PndfRange range("pndf_complete");
+    if (!h) return PNDF_ERR_BAD_ARG;
+    pndf_project_options o;
+    if (const char* why = pndf_check_project_options(opt, o)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (!h->have_weights) return pndf_fail(h, PNDF_ERR_NO_WEIGHTS, "pndf_load_weights has not been called");
+    if (B < 0 || steps < 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative batch or step count");
+    if (B > PNDF_COMPLETE_MAX_B) return pndf_fail(h, PNDF_ERR_BAD_ARG, "batch too large for the step kernel's grid");
+    if (B == 0) return PNDF_OK;
+    if (!q_in || !q_out) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose / output pointer");
+    if (!workspace) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null workspace (pndf_complete_workspace_floats(B) floats of device memory)");
+    if (((uintptr_t)q_in | (uintptr_t)q_out | (uintptr_t)workspace) & 15)
+        return pndf_fail(h, PNDF_ERR_BAD_ARG, "pose buffers and the workspace must be 16-byte aligned");
+    if (((uintptr_t)d_last | (uintptr_t)observed) & 3) return pndf_fail(h, PNDF_ERR_BAD_ARG, "misaligned distance or mask buffer");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
+    if (q_out != q_in) HIP_TRY(h, hipMemcpyAsync(q_out, q_in, (size_t)B * NQ * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (steps == 0) {      // as pndf_project_ex: the poses pass through
+        if (d_last) HIP_TRY(h, hipMemsetAsync(d_last, 0, (size_t)B * sizeof(float), (hipStream_t)stream));
+        return PNDF_OK;
+    }
+    float* d_ws = (float*)workspace;
+    float* dq = d_ws + pndf_complete_d_floats(B);
+    for (int s = 0; s < steps; ++s) {
+        float* d = (s == steps - 1 && d_last) ? d_last : d_ws;
+        if (const int rc = pndf_forward_grad(h, q_out, nullptr, d, dq, B, stream)) return rc;
+        pndf_complete_step_enqueue(q_out, d, dq, observed, B, o, stream);
+        if (const int rc = pndf_check_launch(h, "pndf_complete_step_kernel")) return rc;
+    }
+    return PNDF_OK;
 }
 
 // ---- hooks for the debug library (libposendf_amd_debug.so; include/posendf_amd_debug.h).  Not declared in any installed header and

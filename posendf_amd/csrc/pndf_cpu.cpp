@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/posendf_amd.h"
+#include "../../include/posendf_amd_completion.h"
 #include "pndf_error.h"
 #include "pndf_layout.h"
 #include "pndf_project_opts.h"
@@ -390,11 +391,13 @@ extern "C" int pndf_project_cpu(pndf_cpu_handle h, const float* q_in, float* q_o
 }
 
 // One step of pndf_project_ex on the host: the statement sequence of pndf_device.h's project_step, every operation rounded to fp32
-// on its own (no contraction), so that the two agree bit for bit on equal d and grad.
-static void project_step_cpu(float* q, const float* dq, float d, const pndf_project_options& o) {
+// on its own (no contraction), so that the two agree bit for bit on equal d and grad.  `held`: bit j = joint j is observed and stays as
+// it is (pndf_complete_cpu; pndf_project_ex_cpu holds none).
+static void project_step_cpu(float* q, const float* dq, float d, const pndf_project_options& o, uint32_t held = 0) {
 #pragma clang fp contract(off)
     if (o.tol > 0.f && d < o.tol) return;
     for (int j = 0; j < NJ; ++j) {
+        if ((held >> j) & 1u) continue;
         float u[4];
         for (int c = 0; c < 4; ++c) {
             const float p = d * dq[4 * j + c];
@@ -429,6 +432,33 @@ extern "C" int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* 
         for (int s = 0; s < steps; ++s) {
             forward_grad_block(*h, qb, nb, nullptr, dd, dqb, true, S);
             for (int p = 0; p < nb; ++p) project_step_cpu(qb + p * NQ, dqb + p * NQ, dd[p], o);
+        }
+        memcpy(q_out + p0 * NQ, qb, sizeof(float) * nb * NQ);
+        if (d_last) memcpy(d_last + p0, dd, sizeof(float) * nb);
+    });
+    });
+}
+
+// Host twin of pndf_complete (include/posendf_amd_completion.h): the loop of pndf_project_ex_cpu with the observed joints held.  With
+// the default options the step is pndf_project_cpu's (step_size 1 makes its product exact), so with no joint held this is
+// pndf_project_ex_cpu bit for bit, defaults included.
+extern "C" int pndf_complete_cpu(pndf_cpu_handle h, const float* q_in, const uint32_t* observed, float* q_out, float* d_last,
+                                 int64_t B, int steps, const pndf_project_options* opt) {
+    if (!h) return PNDF_ERR_BAD_ARG;
+    pndf_project_options o;
+    if (const char* why = pndf_check_project_options(opt, o)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (int rc = check(h, q_in, B)) return rc;
+    if (steps < 0 || (B > 0 && !q_out)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count or null output pointer");
+    if (((uintptr_t)q_in | (uintptr_t)q_out | (uintptr_t)d_last | (uintptr_t)observed) & 3)
+        return pndf_fail(h, PNDF_ERR_BAD_ARG, "misaligned pose, distance or mask buffer");
+    return guarded(h, [&] {
+    parallel_blocks(B, [&](int64_t p0, int nb, Scratch& S) {
+        float qb[PB * NQ], dqb[PB * NQ], dd[PB];
+        memcpy(qb, q_in + p0 * NQ, sizeof(float) * nb * NQ);
+        for (int p = 0; p < nb; ++p) dd[p] = 0.f;
+        for (int s = 0; s < steps; ++s) {
+            forward_grad_block(*h, qb, nb, nullptr, dd, dqb, true, S);
+            for (int p = 0; p < nb; ++p) project_step_cpu(qb + p * NQ, dqb + p * NQ, dd[p], o, observed ? observed[p0 + p] : 0u);
         }
         memcpy(q_out + p0 * NQ, qb, sizeof(float) * nb * NQ);
         if (d_last) memcpy(d_last + p0, dd, sizeof(float) * nb);

@@ -58,8 +58,9 @@ class PndfError(RuntimeError):
     pass
 
 
-# ---- the C ABI, one table per library: name -> (restype, argtypes), in the header's order.  load_library() binds the tables, EXPORTS /
-# DEBUG_EXPORTS are their names, tests/test_cabi.py holds both against the declarations of the two headers.
+# ---- the C ABI, one table per header: name -> (restype, argtypes), in the header's order.  load_library() binds the tables, EXPORTS /
+# COMPLETION_EXPORTS / DEBUG_EXPORTS are their names, tests/test_cabi.py and tests/test_completion.py hold them against the
+# declarations of the headers.
 _H = c_void_p                          # every handle type, and every `void* stream`
 _P = c_void_p                          # any other address: tensor data (an int from data_ptr(), or None), a callback, an out value
 _TENSORS = [POINTER(c_void_p), POINTER(c_int64), c_int]      # tensors, numel, n_tensors (host pointers in state-dict order)
@@ -147,7 +148,14 @@ _DEBUG_SIGNATURES = {      # include/posendf_amd_debug.h: bring-up / profiling /
     "pndf_debug_mem_probe": (c_int, [c_int, _P, c_int]),
     "pndf_debug_ring_stream": (c_int, [c_int, c_int, _P]),
 }
+_COMPLETION_SIGNATURES = {      # include/posendf_amd_completion.h: pose completion, the companion header of posendf_amd.h (same library)
+    "pndf_complete_step": (c_int, [_P, _P, _P, _P, c_int64, POINTER(ProjectOptions), _H]),
+    "pndf_complete_workspace_floats": (c_int64, [c_int64]),
+    "pndf_complete": (c_int, [_H, _P, _P, _P, _P, c_int64, c_int, POINTER(ProjectOptions), _P, _H]),
+    "pndf_complete_cpu": (c_int, [_H, _P, _P, _P, _P, c_int64, c_int, POINTER(ProjectOptions)]),
+}
 EXPORTS, DEBUG_EXPORTS = tuple(_SIGNATURES), tuple(_DEBUG_SIGNATURES)
+COMPLETION_EXPORTS = tuple(_COMPLETION_SIGNATURES)
 # per-translation-unit experiment words (csrc/pndf_experiment.h): data symbols, all zero in a product build
 EXPERIMENT_WORDS = ("pndf_experiment_word_capi", "pndf_experiment_word_fp32", "pndf_experiment_word_split", "pndf_experiment_word_split_x2",
                     "pndf_experiment_word_bf16", "pndf_experiment_word_lbs", "pndf_experiment_word_generic", "pndf_experiment_word_train",
@@ -201,7 +209,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     if not os.path.exists(path):
         raise PndfError(f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                         "(hipcc --offload-arch=gfx950). The engine has no fallback path.")
-    return _bind(_PndfLibrary(path), _SIGNATURES)
+    return _bind(_bind(_PndfLibrary(path), _SIGNATURES), _COMPLETION_SIGNATURES)
 
 
 def experiment_word(lib=None) -> int:
@@ -386,6 +394,27 @@ class Engine(_Handle):
         else:
             self._check(self.lib.pndf_project_ex(self.handle, q_in_ptr, q_out_ptr, d_ptr, B, int(steps), ctypes.byref(opt), stream),
                         "pndf_project_ex")
+
+    def complete_workspace_floats(self, B) -> int:
+        n = int(self.lib.pndf_complete_workspace_floats(int(B)))
+        if n < 0:
+            raise PndfError(f"pndf_complete_workspace_floats failed ({n}): B = {B}")
+        return n
+
+    def complete(self, q_in_ptr, observed_ptr, q_out_ptr, d_ptr, B, steps, ws_ptr, stream=0, *, step_size=1.0, renorm="none", tol=0.0):
+        """pndf_complete (include/posendf_amd_completion.h): the projection loop with the joints of `observed_ptr` (one uint32 per
+        pose, bit j = joint j; None = no joint) held; `ws_ptr`: complete_workspace_floats(B) floats of device memory"""
+        opt = project_options(self.lib, step_size, renorm, tol)
+        self._check(self.lib.pndf_complete(self.handle, q_in_ptr, observed_ptr, q_out_ptr, d_ptr, B, int(steps),
+                                           None if opt is None else ctypes.byref(opt), ws_ptr, stream), "pndf_complete")
+
+    def complete_step(self, q_ptr, d_ptr, dq_ptr, observed_ptr, B, stream=0, *, step_size=1.0, renorm="none", tol=0.0):
+        """pndf_complete_step: one masked step on q in place from the d and dq of a forward_grad (a stateless helper: no text)"""
+        opt = project_options(self.lib, step_size, renorm, tol)
+        rc = self.lib.pndf_complete_step(q_ptr, d_ptr, dq_ptr, observed_ptr, B, None if opt is None else ctypes.byref(opt), stream)
+        if rc != 0:
+            raise PndfError(f"pndf_complete_step failed ({rc}): B = {B}; q and dq must be non-null and 16-byte aligned, d non-null, "
+                            "the options those of pndf_project_ex")
 
     def debug_forward_grad(self, q_ptr, d_ptr, dq_ptr, B, dump_ptr, stream=0):
         self._check(self.lib.pndf_debug_forward_grad(self.handle, q_ptr, d_ptr, dq_ptr, B, dump_ptr, stream),
@@ -601,3 +630,11 @@ class CpuEngine(_Handle):
         else:
             self._check(self.lib.pndf_project_ex_cpu(self.handle, q_in_ptr, q_out_ptr, d_ptr, B, int(steps), ctypes.byref(opt)),
                         "pndf_project_ex_cpu")
+
+    def complete_workspace_floats(self, B) -> int:
+        return 0      # the host twin needs none
+
+    def complete(self, q_in_ptr, observed_ptr, q_out_ptr, d_ptr, B, steps, ws_ptr=None, stream=0, *, step_size=1.0, renorm="none", tol=0.0):
+        opt = project_options(self.lib, step_size, renorm, tol)
+        self._check(self.lib.pndf_complete_cpu(self.handle, q_in_ptr, observed_ptr, q_out_ptr, d_ptr, B, int(steps),
+                                               None if opt is None else ctypes.byref(opt)), "pndf_complete_cpu")

@@ -234,3 +234,35 @@ class PoseNDF(nn.Module):
         eng.project(q.data_ptr(), out.data_ptr(), d.data_ptr(), q.shape[0], int(steps), stream_handle(q.device),
                     step_size=step_size, renorm=renormalize, tol=tol)
         return (out, d.view(-1, 1)) if return_dist else out
+
+    @staticmethod
+    def pack_observed(observed, B, device):
+        """bool [21] or [B,21] (True = the joint is observed and held) -> one word per pose, bit j = joint j, as an int32 tensor [B]
+        on `device` (the uint32 of include/posendf_amd_completion.h: bits 0 .. 20 only, so the sign bit is never set)"""
+        obs = torch.as_tensor(observed, device=device)
+        if obs.dtype != torch.bool:
+            raise PndfError(f"observed must be a bool tensor, not {obs.dtype}")
+        if obs.shape == (21,):
+            obs = obs.expand(B, 21)
+        if obs.shape != (B, 21):
+            raise PndfError(f"observed must have shape [21] or [{B}, 21], not {list(obs.shape)}")
+        bits = torch.ones(21, dtype=torch.int64, device=device) << torch.arange(21, device=device)
+        return (obs.to(torch.int64) * bits).sum(dim=1).to(torch.int32).contiguous()
+
+    @torch.no_grad()
+    def complete(self, poses, observed, steps=100, return_dist=True, *, step_size=1.0, renormalize=None, tol=0.0):
+        """Pose completion: `project` with the observed joints held.  `observed` is a bool tensor [21] (one mask for every pose) or
+        [B,21], True = the joint's rotation is known and stays as it is, bit for bit; None = no joint is held, which is `project`
+        bit for bit.  Each of the `steps` steps is one forward + gradient launch and one small masked update kernel on the
+        caller's stream (include/posendf_amd_completion.h); a `train.device: cpu` model runs the host twin.  Returns and step options:
+        as `project`."""
+        q = poses.to(device=self.device).reshape(-1, 21, 4).float().contiguous()
+        B = q.shape[0]
+        out = torch.empty_like(q)
+        d = torch.empty(B, device=q.device, dtype=torch.float32)
+        mask = None if observed is None else self.pack_observed(observed, B, q.device)
+        eng = self._engine_for(q.device)
+        ws = torch.empty(eng.complete_workspace_floats(B), device=q.device, dtype=torch.float32)
+        eng.complete(q.data_ptr(), None if mask is None or B == 0 else mask.data_ptr(), out.data_ptr(), d.data_ptr(), B, int(steps),
+                     ws.data_ptr() if ws.numel() else None, stream_handle(q.device), step_size=step_size, renorm=renormalize, tol=tol)
+        return (out, d.view(-1, 1)) if return_dist else out
