@@ -19,6 +19,9 @@ def __getattr__(name):   # torch is imported lazily so that numpy-only users (or
     if name == "PoseCompletion":
         from .pose_completion import PoseCompletion
         return PoseCompletion
+    if name == "PoseInterpolation":
+        from .pose_interpolation import PoseInterpolation
+        return PoseInterpolation
     if name == "BodyModel":
         from .body_model import BodyModel
         return BodyModel
@@ -28,5 +31,5 @@ def __getattr__(name):   # torch is imported lazily so that numpy-only users (or
     raise AttributeError(name)
 
 
-__all__ = ["PoseNDF", "gradient", "BodyModel", "PoseIndex", "Trainer", "PoseDataset", "ImageFit", "PerspectiveCamera", "keypoint_term", "PoseCompletion",
+__all__ = ["PoseNDF", "gradient", "BodyModel", "PoseIndex", "Trainer", "PoseDataset", "ImageFit", "PerspectiveCamera", "keypoint_term", "PoseCompletion", "PoseInterpolation",
            "amass_config", "load_config", "synth"]

@@ -18,6 +18,7 @@
 #include "pndf_generic.h"
 #include "pndf_project_opts.h"
 #include "pndf_complete.h"
+#include "pndf_interp.h"
 
 using namespace pndf;
 
@@ -555,6 +556,55 @@ extern "C" int pndf_complete(pndf_handle h, const float* q_in, const uint32_t* o
         if (const int rc = pndf_forward_grad(h, q_out, nullptr, d, dq, B, stream)) return rc;
         pndf_complete_step_enqueue(q_out, d, dq, observed, B, o, stream);
         if (const int rc = pndf_check_launch(h, "pndf_complete_step_kernel")) return rc;
+    }
+    return PNDF_OK;
+}
+
+// Pose interpolation (include/posendf_amd_interpolation.h; DESIGN.md section 2 "Pose interpolation"): the fill, then `steps` times
+// { pndf_forward_grad ; the band kernel of pndf_interp.hip } on the caller's stream.  The band step is out of place, so the track
+// alternates between track_out and the pose buffer of the workspace; the fill goes to the one that makes the last step write
+// track_out.  Everything is validated before the first enqueue.
+extern "C" int pndf_interpolate(pndf_handle h, const float* a, const float* b, const uint32_t* observed, float* track_out, float* d_last,
+                                int64_t P, int32_t T, int32_t mode, int steps, float lambda, const pndf_project_options* opt,
+                                void* workspace, void* stream) {
+    PndfRange range("pndf_interpolate");
+    if (!h) return PNDF_ERR_BAD_ARG;
+    pndf_project_options o;
+    if (const char* why = pndf_check_project_options(opt, o)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (const char* why = pndf_interp_check_mode(mode)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (const char* why = pndf_interp_check_lambda(lambda)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (!h->have_weights) return pndf_fail(h, PNDF_ERR_NO_WEIGHTS, "pndf_load_weights has not been called");
+    if (steps < 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count");
+    if (const char* why = pndf_interp_check_shape(P, T)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (P == 0) return PNDF_OK;
+    if (!a || !b || !track_out) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose / output pointer");
+    if (!workspace)
+        return pndf_fail(h, PNDF_ERR_BAD_ARG, "null workspace (pndf_interpolate_workspace_floats(P, T) floats of device memory)");
+    if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)track_out | (uintptr_t)workspace) & 15)
+        return pndf_fail(h, PNDF_ERR_BAD_ARG, "pose buffers and the workspace must be 16-byte aligned");
+    if (((uintptr_t)d_last | (uintptr_t)observed) & 3) return pndf_fail(h, PNDF_ERR_BAD_ARG, "misaligned distance or mask buffer");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
+    const int64_t B = P * T;
+    float* d_ws = (float*)workspace;
+    float* dq = d_ws + pndf_complete_d_floats(B);
+    float* other = dq + B * NQ;
+    float* cur = (steps & 1) ? other : track_out;      // `steps` swaps later the track is in track_out
+    float* nxt = (steps & 1) ? track_out : other;
+    pndf_interp_fill_enqueue(a, b, cur, P, T, mode, stream);
+    if (const int rc = pndf_check_launch(h, "pndf_interp_fill_kernel")) return rc;
+    if (steps == 0) {      // as pndf_project_ex: nothing to report
+        if (d_last) HIP_TRY(h, hipMemsetAsync(d_last, 0, (size_t)B * sizeof(float), (hipStream_t)stream));
+        return PNDF_OK;
+    }
+    for (int s = 0; s < steps; ++s) {
+        float* d = (s == steps - 1 && d_last) ? d_last : d_ws;
+        if (const int rc = pndf_forward_grad(h, cur, nullptr, d, dq, B, stream)) return rc;
+        pndf_interp_band_enqueue(cur, nxt, d, dq, observed, P, T, lambda, o, stream);
+        if (const int rc = pndf_check_launch(h, "pndf_interp_band_kernel")) return rc;
+        float* t = cur;
+        cur = nxt;
+        nxt = t;
     }
     return PNDF_OK;
 }

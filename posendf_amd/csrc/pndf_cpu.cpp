@@ -27,6 +27,7 @@
 #include "../../include/posendf_amd.h"
 #include "../../include/posendf_amd_completion.h"
 #include "pndf_error.h"
+#include "pndf_interp.h"
 #include "pndf_layout.h"
 #include "pndf_project_opts.h"
 
@@ -464,4 +465,60 @@ extern "C" int pndf_complete_cpu(pndf_cpu_handle h, const float* q_in, const uin
         if (d_last) memcpy(d_last + p0, dd, sizeof(float) * nb);
     });
     });
+}
+
+// Host twin of pndf_interpolate (include/posendf_amd_interpolation.h): the fill and the band step of pndf_interp.h -- the statements
+// the device kernels run -- around pndf_forward_grad_cpu.  A step reads the neighbour frames of the track as they were before it
+// (out of place, like the device), so the whole track takes one step at a time; with lambda == 0 this is pndf_complete_cpu on the
+// filled track with the end frames observed, bit for bit.
+extern "C" int pndf_interpolate_cpu(pndf_cpu_handle h, const float* a, const float* b, const uint32_t* observed, float* track_out,
+                                    float* d_last, int64_t P, int32_t T, int32_t mode, int steps, float lambda,
+                                    const pndf_project_options* opt) {
+    if (!h) return PNDF_ERR_BAD_ARG;
+    pndf_project_options o;
+    if (const char* why = pndf_check_project_options(opt, o)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (const char* why = pndf_interp_check_mode(mode)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (const char* why = pndf_interp_check_lambda(lambda)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (!h->have_weights) return pndf_fail(h, PNDF_ERR_NO_WEIGHTS, "pndf_cpu_load_weights has not been called");
+    if (steps < 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count");
+    if (const char* why = pndf_interp_check_shape(P, T)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (P == 0) return PNDF_OK;
+    if (!a || !b || !track_out) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose / output pointer");
+    if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)track_out | (uintptr_t)d_last | (uintptr_t)observed) & 3)
+        return pndf_fail(h, PNDF_ERR_BAD_ARG, "misaligned pose, distance or mask buffer");
+    const int64_t B = P * T;
+    int rc = PNDF_OK;
+    const int grc = guarded(h, [&] {
+        std::vector<float> other((size_t)B * NQ), dq(steps ? (size_t)B * NQ : 0), dd((size_t)B, 0.f);
+        float* cur = (steps & 1) ? other.data() : track_out;      // `steps` swaps later the track is in track_out
+        float* nxt = (steps & 1) ? track_out : other.data();
+        for (int64_t p = 0; p < P; ++p)
+            for (int j = 0; j < NJ; ++j) {
+                const float *A = a + (p * NJ + j) * 4, *Bq = b + (p * NJ + j) * 4;
+                float bp[4];
+                pndf_interp_align(A, Bq, bp);
+                memcpy(cur + ((p * T) * NJ + j) * 4, A, sizeof(float) * 4);
+                memcpy(cur + ((p * T + T - 1) * NJ + j) * 4, bp, sizeof(float) * 4);
+                for (int k = 1; k < T - 1; ++k) pndf_interp_fill_quat(A, bp, (float)k / (float)(T - 1), mode, cur + ((p * T + k) * NJ + j) * 4);
+            }
+        for (int s = 0; s < steps && rc == PNDF_OK; ++s) {
+            rc = pndf_forward_grad_cpu(h, cur, nullptr, dd.data(), dq.data(), B);
+            if (rc != PNDF_OK) break;
+            for (int64_t f = 0; f < B; ++f) {
+                const int k = (int)(f % T);
+                const uint32_t held = (k == 0 || k == T - 1) ? ~0u : (observed ? observed[f] : 0u);
+                for (int j = 0; j < NJ; ++j) {
+                    const int64_t i = (f * NJ + j) * 4;
+                    float u[4];
+                    if (((held >> j) & 1u) || pndf_interp_band_quat(cur + i, dq.data() + i, dd[f], cur + i - NQ, cur + i + NQ, lambda, o.step_size, o.tol, (int)o.renorm, u))
+                        memcpy(nxt + i, cur + i, sizeof(float) * 4);
+                    else
+                        memcpy(nxt + i, u, sizeof(float) * 4);
+                }
+            }
+            std::swap(cur, nxt);
+        }
+        if (rc == PNDF_OK && d_last) memcpy(d_last, dd.data(), sizeof(float) * B);
+    });
+    return grc != PNDF_OK ? grc : rc;
 }

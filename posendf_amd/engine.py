@@ -26,6 +26,7 @@ _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "lib
 ACT_CODES = {"relu": 0, "lrelu": 1, "softplus": 2}
 PRECISION_CODES = {"fp32": 0, "f16x3": 1, "f16": 2, "bf16": 3}
 RENORM_CODES = {"none": 0, "unit": 1, "unit_flip": 2}      # PNDF_RENORM_*
+INTERP_MODES = {"slerp": 0, "nlerp": 1}                    # PNDF_INTERP_*
 
 
 class PndfConfig(ctypes.Structure):
@@ -59,8 +60,8 @@ class PndfError(RuntimeError):
 
 
 # ---- the C ABI, one table per header: name -> (restype, argtypes), in the header's order.  load_library() binds the tables, EXPORTS /
-# COMPLETION_EXPORTS / DEBUG_EXPORTS are their names, tests/test_cabi.py and tests/test_completion.py hold them against the
-# declarations of the headers.
+# COMPLETION_EXPORTS / INTERPOLATION_EXPORTS / DEBUG_EXPORTS are their names, tests/test_cabi.py, tests/test_completion.py and
+# tests/test_interpolation.py hold them against the declarations of the headers.
 _H = c_void_p                          # every handle type, and every `void* stream`
 _P = c_void_p                          # any other address: tensor data (an int from data_ptr(), or None), a callback, an out value
 _TENSORS = [POINTER(c_void_p), POINTER(c_int64), c_int]      # tensors, numel, n_tensors (host pointers in state-dict order)
@@ -154,8 +155,16 @@ _COMPLETION_SIGNATURES = {      # include/posendf_amd_completion.h: pose complet
     "pndf_complete": (c_int, [_H, _P, _P, _P, _P, c_int64, c_int, POINTER(ProjectOptions), _P, _H]),
     "pndf_complete_cpu": (c_int, [_H, _P, _P, _P, _P, c_int64, c_int, POINTER(ProjectOptions)]),
 }
+_INTERPOLATION_SIGNATURES = {      # include/posendf_amd_interpolation.h: pose interpolation, the second companion header (same library)
+    "pndf_interp_fill": (c_int, [_P, _P, _P, c_int64, c_int32, c_int32, _H]),
+    "pndf_interp_band_step": (c_int, [_P, _P, _P, _P, _P, c_int64, c_int32, c_float, POINTER(ProjectOptions), _H]),
+    "pndf_interpolate_workspace_floats": (c_int64, [c_int64, c_int32]),
+    "pndf_interpolate": (c_int, [_H, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int, c_float, POINTER(ProjectOptions), _P, _H]),
+    "pndf_interpolate_cpu": (c_int, [_H, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int, c_float, POINTER(ProjectOptions)]),
+}
 EXPORTS, DEBUG_EXPORTS = tuple(_SIGNATURES), tuple(_DEBUG_SIGNATURES)
 COMPLETION_EXPORTS = tuple(_COMPLETION_SIGNATURES)
+INTERPOLATION_EXPORTS = tuple(_INTERPOLATION_SIGNATURES)
 # per-translation-unit experiment words (csrc/pndf_experiment.h): data symbols, all zero in a product build
 EXPERIMENT_WORDS = ("pndf_experiment_word_capi", "pndf_experiment_word_fp32", "pndf_experiment_word_split", "pndf_experiment_word_split_x2",
                     "pndf_experiment_word_bf16", "pndf_experiment_word_lbs", "pndf_experiment_word_generic", "pndf_experiment_word_train",
@@ -209,7 +218,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     if not os.path.exists(path):
         raise PndfError(f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                         "(hipcc --offload-arch=gfx950). The engine has no fallback path.")
-    return _bind(_bind(_PndfLibrary(path), _SIGNATURES), _COMPLETION_SIGNATURES)
+    return _bind(_bind(_bind(_PndfLibrary(path), _SIGNATURES), _COMPLETION_SIGNATURES), _INTERPOLATION_SIGNATURES)
 
 
 def experiment_word(lib=None) -> int:
@@ -284,6 +293,13 @@ def project_options(lib, step_size=1.0, renorm="none", tol=0.0):
     lib.pndf_default_project_options(ctypes.byref(opt))
     opt.step_size, opt.renorm, opt.tol = float(step_size), RENORM_CODES[renorm], float(tol)
     return opt
+
+
+def interp_mode(mode) -> int:
+    """PNDF_INTERP_* of a fill mode's name"""
+    if mode not in INTERP_MODES:
+        raise PndfError(f"unknown interpolation mode {mode!r} ('slerp', 'nlerp')")
+    return INTERP_MODES[mode]
 
 
 def _set_encoder_act(cfg, act, beta, enc_act, enc_beta):
@@ -415,6 +431,38 @@ class Engine(_Handle):
         if rc != 0:
             raise PndfError(f"pndf_complete_step failed ({rc}): B = {B}; q and dq must be non-null and 16-byte aligned, d non-null, "
                             "the options those of pndf_project_ex")
+
+    def interpolate_workspace(self, P, T) -> int:
+        n = int(self.lib.pndf_interpolate_workspace_floats(int(P), int(T)))
+        if n < 0:
+            raise PndfError(f"pndf_interpolate_workspace_floats failed ({n}): P = {P}, T = {T}")
+        return n
+
+    def interpolate(self, a_ptr, b_ptr, observed_ptr, track_ptr, d_ptr, P, T, steps, ws_ptr, stream=0, *, mode="slerp", smooth=0.0,
+                    step_size=1.0, renorm="none", tol=0.0):
+        """pndf_interpolate (include/posendf_amd_interpolation.h): the track [P,T,21,4] between the pairs a, b [P,21,4] -- the fill
+        in `mode`, then `steps` band steps with the neighbour coupling `smooth` (lambda); `observed_ptr`: one uint32 per pose of the
+        track or None; `ws_ptr`: interpolate_workspace(P, T) floats of device memory"""
+        opt = project_options(self.lib, step_size, renorm, tol)
+        self._check(self.lib.pndf_interpolate(self.handle, a_ptr, b_ptr, observed_ptr, track_ptr, d_ptr, int(P), int(T), interp_mode(mode),
+                                              int(steps), float(smooth), None if opt is None else ctypes.byref(opt), ws_ptr, stream),
+                    "pndf_interpolate")
+
+    def interp_fill(self, a_ptr, b_ptr, track_ptr, P, T, stream=0, *, mode="slerp"):
+        """pndf_interp_fill: the filled track alone (a stateless helper: no text)"""
+        rc = self.lib.pndf_interp_fill(a_ptr, b_ptr, track_ptr, int(P), int(T), interp_mode(mode), stream)
+        if rc != 0:
+            raise PndfError(f"pndf_interp_fill failed ({rc}): P = {P}, T = {T}; a, b and the track must be non-null and 16-byte aligned, T >= 2")
+
+    def interp_band_step(self, q_in_ptr, q_out_ptr, d_ptr, dq_ptr, observed_ptr, P, T, stream=0, *, smooth=0.0, step_size=1.0, renorm="none",
+                         tol=0.0):
+        """pndf_interp_band_step: one out-of-place band step from the d and dq of a forward_grad (a stateless helper: no text)"""
+        opt = project_options(self.lib, step_size, renorm, tol)
+        rc = self.lib.pndf_interp_band_step(q_in_ptr, q_out_ptr, d_ptr, dq_ptr, observed_ptr, int(P), int(T), float(smooth),
+                                            None if opt is None else ctypes.byref(opt), stream)
+        if rc != 0:
+            raise PndfError(f"pndf_interp_band_step failed ({rc}): P = {P}, T = {T}, lambda = {smooth}; q_in, q_out and dq must be non-null, "
+                            "distinct and 16-byte aligned, d non-null, lambda in [0, 1], the options those of pndf_project_ex")
 
     def debug_forward_grad(self, q_ptr, d_ptr, dq_ptr, B, dump_ptr, stream=0):
         self._check(self.lib.pndf_debug_forward_grad(self.handle, q_ptr, d_ptr, dq_ptr, B, dump_ptr, stream),
@@ -638,3 +686,12 @@ class CpuEngine(_Handle):
         opt = project_options(self.lib, step_size, renorm, tol)
         self._check(self.lib.pndf_complete_cpu(self.handle, q_in_ptr, observed_ptr, q_out_ptr, d_ptr, B, int(steps),
                                                None if opt is None else ctypes.byref(opt)), "pndf_complete_cpu")
+
+    def interpolate_workspace(self, P, T) -> int:
+        return 0      # the host twin needs none
+
+    def interpolate(self, a_ptr, b_ptr, observed_ptr, track_ptr, d_ptr, P, T, steps, ws_ptr=None, stream=0, *, mode="slerp", smooth=0.0,
+                    step_size=1.0, renorm="none", tol=0.0):
+        opt = project_options(self.lib, step_size, renorm, tol)
+        self._check(self.lib.pndf_interpolate_cpu(self.handle, a_ptr, b_ptr, observed_ptr, track_ptr, d_ptr, int(P), int(T), interp_mode(mode),
+                                                  int(steps), float(smooth), None if opt is None else ctypes.byref(opt)), "pndf_interpolate_cpu")

@@ -266,3 +266,40 @@ class PoseNDF(nn.Module):
         eng.complete(q.data_ptr(), None if mask is None or B == 0 else mask.data_ptr(), out.data_ptr(), d.data_ptr(), B, int(steps),
                      ws.data_ptr() if ws.numel() else None, stream_handle(q.device), step_size=step_size, renorm=renormalize, tol=tol)
         return (out, d.view(-1, 1)) if return_dist else out
+
+    @torch.no_grad()
+    def interpolate(self, pose_a, pose_b, frames, steps=100, smooth=0.0, mode="slerp", observed=None, return_dist=True, *, step_size=1.0,
+                    renormalize="unit", tol=0.0):
+        """Pose interpolation: a track of `frames` poses from every pose of `pose_a` to the matching pose of `pose_b` ([P,21,4]
+        each), relaxed onto the manifold.  Frame 0 is `pose_a`, frame frames-1 is `pose_b` with every joint quaternion negated
+        where that is the shorter way round; the frames between them start as the `mode` ("slerp" / "nlerp") interpolation of each
+        joint and take `steps` steps of `complete` -- the two end frames and the `observed` joints held, bit for bit -- with a
+        neighbour coupling of weight `smooth` in [0, 1] in the same step, which pulls every frame towards the mean of its two
+        neighbours and keeps the track evenly spaced (smooth=0: the frames descend on their own, `complete` bit for bit).
+        `observed`: bool [21], [frames,21] (one mask per frame, for every pair) or [P,frames,21].  One fill launch, then per step
+        one forward + gradient launch and one band kernel on the caller's stream (include/posendf_amd_interpolation.h); a
+        `train.device: cpu` model runs the host twin.  The inputs are not written.  Returns (track [P,frames,21,4], dist
+        [P,frames] of the last iteration); step options: as `project`, with unit quaternions as the default."""
+        a = pose_a.to(device=self.device).reshape(-1, 21, 4).float().contiguous()
+        b = pose_b.to(device=self.device).reshape(-1, 21, 4).float().contiguous()
+        P, T = a.shape[0], int(frames)
+        if b.shape[0] != P:
+            raise PndfError(f"pose_a holds {P} poses, pose_b {b.shape[0]}")
+        if T < 2:
+            raise PndfError(f"an interpolation has at least two frames, not {frames}")
+        track = torch.empty((P, T, 21, 4), device=a.device, dtype=torch.float32)
+        d = torch.empty((P, T), device=a.device, dtype=torch.float32)
+        mask = None
+        if observed is not None:
+            obs = torch.as_tensor(observed, device=a.device)
+            if obs.dtype == torch.bool and obs.shape == (T, 21):
+                obs = obs.expand(P, T, 21)
+            if obs.dtype == torch.bool and obs.shape == (P, T, 21):
+                obs = obs.reshape(P * T, 21)
+            mask = self.pack_observed(obs, P * T, a.device)
+        eng = self._engine_for(a.device)
+        ws = torch.empty(eng.interpolate_workspace(P, T), device=a.device, dtype=torch.float32)
+        eng.interpolate(a.data_ptr(), b.data_ptr(), None if mask is None or P == 0 else mask.data_ptr(), track.data_ptr(), d.data_ptr(), P, T,
+                        int(steps), ws.data_ptr() if ws.numel() else None, stream_handle(a.device), mode=mode, smooth=smooth,
+                        step_size=step_size, renorm=renormalize, tol=tol)
+        return (track, d) if return_dist else track
