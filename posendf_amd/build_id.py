@@ -9,7 +9,7 @@ import os
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FUSED_KERNEL_SOURCES = ("pndf_kernel.hip", "pndf_kernel_split.hip", "pndf_kernel_split_x2.hip", "pndf_device.h", "pndf_layout.h",
-                        "pndf_args.h", "pndf_capi.hip")
+                        "pndf_args.h", "pndf_step.h", "pndf_capi.hip")
 
 
 def source_id() -> str:

@@ -539,9 +539,7 @@ extern "C" int pndf_complete(pndf_handle h, const float* q_in, const uint32_t* o
     if (B == 0) return PNDF_OK;
     if (!q_in || !q_out) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose / output pointer");
     if (!workspace) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null workspace (pndf_complete_workspace_floats(B) floats of device memory)");
-    if (((uintptr_t)q_in | (uintptr_t)q_out | (uintptr_t)workspace) & 15)
-        return pndf_fail(h, PNDF_ERR_BAD_ARG, "pose buffers and the workspace must be 16-byte aligned");
-    if (((uintptr_t)d_last | (uintptr_t)observed) & 3) return pndf_fail(h, PNDF_ERR_BAD_ARG, "misaligned distance or mask buffer");
+    if (const char* why = pndf_check_step_alignment({q_in, q_out, workspace}, d_last, observed)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     if (q_out != q_in) HIP_TRY(h, hipMemcpyAsync(q_out, q_in, (size_t)B * NQ * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
@@ -580,9 +578,7 @@ extern "C" int pndf_interpolate(pndf_handle h, const float* a, const float* b, c
     if (!a || !b || !track_out) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose / output pointer");
     if (!workspace)
         return pndf_fail(h, PNDF_ERR_BAD_ARG, "null workspace (pndf_interpolate_workspace_floats(P, T) floats of device memory)");
-    if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)track_out | (uintptr_t)workspace) & 15)
-        return pndf_fail(h, PNDF_ERR_BAD_ARG, "pose buffers and the workspace must be 16-byte aligned");
-    if (((uintptr_t)d_last | (uintptr_t)observed) & 3) return pndf_fail(h, PNDF_ERR_BAD_ARG, "misaligned distance or mask buffer");
+    if (const char* why = pndf_check_step_alignment({a, b, track_out, workspace}, d_last, observed)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     const int64_t B = P * T;

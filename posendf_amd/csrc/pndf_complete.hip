@@ -4,74 +4,46 @@
 // behind pndf_forward_grad stay as they are, and the mask lives in this one small element-wise kernel.
 //   pndf_complete_step_kernel   one lane per joint quaternion: lane i holds joint j = i - 21 b of pose b = i / 21 (64-bit index
 //                               arithmetic, bounded by B * 21).  One 16-byte load of q and of dq, d[b] and observed[b]; a held
-//                               joint (bit j of observed[b]) is neither updated nor stored; any other joint takes the step of
-//                               pndf_device.h's project_step -- the same statements in the same order, every operation rounded to
-//                               fp32 on its own (contraction off) -- and is stored with one 16-byte store.
+//                               joint (bit j of observed[b]) is neither updated nor stored; any other joint takes pndf_step.h's
+//                               pndf_step_quat -- the one statement of the step, which the fused kernels call too -- and is
+//                               stored with one 16-byte store.
 // The step options are plain kernel arguments.  No LDS, no atomics, no communication between lanes: the same inputs give the same
 // bits, and with no joint held a step equals the one inside pndf_project_ex bit for bit (tests/test_completion_gpu.py).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <string>
-
 #include "../../include/posendf_amd_completion.h"
 #include "pndf_complete.h"
 #include "pndf_host.h"
 #include "pndf_project_opts.h"
+#include "pndf_step.h"
 
-namespace {
-
-constexpr int NJ = 21;            // joints = 16-byte quaternions per pose
-constexpr int THREADS = 256;
-
-// the stateless helper has no handle: pndf_check_launch leaves its text here and the code is returned
-struct StepStatus {
-    std::string err;
-};
-
-}  // namespace
+using pndf::NJ;
 
 extern "C" __global__ void __launch_bounds__(256) pndf_complete_step_kernel(float4* __restrict__ q, const float* __restrict__ d,
                                                                             const float4* __restrict__ dq,
                                                                             const uint32_t* __restrict__ observed, long long quats,
                                                                             float alpha, float tol, int renorm) {
-#pragma clang fp contract(off)
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= quats) return;
     const long long b = i / NJ;
     const int j = (int)(i - b * NJ);
     if (observed && ((observed[b] >> j) & 1u)) return;      // held: the joint's bits stay as they are
     const float dist = d[b];
-    const float4 Q = q[i], G = dq[i];
-    const float qv[4] = {Q.x, Q.y, Q.z, Q.w}, gv[4] = {G.x, G.y, G.z, G.w};
-    float u[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const float p = dist * gv[c];
-        const float s = alpha * p;
-        u[c] = qv[c] - s;
-    }
-    if (renorm) {
-        const float ss = ((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]) + u[3] * u[3];
-        const float n = sqrtf(ss);
-        const float den = (n < 1e-12f) ? 1e-12f : n;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) u[c] = u[c] / den;
-        const bool flip = renorm == 2 && u[0] < 0.f;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) u[c] = flip ? -u[c] : u[c];
-    }
-    const bool rest = tol > 0.f && dist < tol;      // false for a NaN d: not frozen
+    const float4 Q = q[i];
+    float qv[4], gv[4], u[4];
+    pndf_quat_unpack(Q, qv);
+    pndf_quat_unpack(dq[i], gv);
+    const bool rest = pndf_step_quat(qv, gv, dist, alpha, tol, renorm, u);
     q[i] = rest ? Q : make_float4(u[0], u[1], u[2], u[3]);
 }
 
 void pndf_complete_step_enqueue(float* q, const float* d, const float* dq, const uint32_t* observed, int64_t B,
                                 const pndf_project_options& o, void* stream) {
     const long long quats = (long long)B * NJ;
-    const unsigned blocks = (unsigned)((quats + THREADS - 1) / THREADS);
-    // (the default options give the plain step of pndf_project: alpha = 1 makes alpha * p exact)
-    hipLaunchKernelGGL(pndf_complete_step_kernel, dim3(blocks), dim3(THREADS), 0, (hipStream_t)stream, (float4*)q, d, (const float4*)dq,
-                       observed, quats, o.step_size, o.tol, (int)o.renorm);
+    // (the default options give the plain step of pndf_project: a step size of 1 makes its product exact)
+    hipLaunchKernelGGL(pndf_complete_step_kernel, dim3(pndf_step_blocks(quats)), dim3(PNDF_STEP_THREADS), 0, (hipStream_t)stream,
+                       (float4*)q, d, (const float4*)dq, observed, quats, o.step_size, o.tol, (int)o.renorm);
 }
 
 // ------------------------------------------------------------------ C ABI (include/posendf_amd_completion.h)
@@ -82,13 +54,11 @@ extern "C" int pndf_complete_step(float* q, const float* d, const float* dq, con
     if (pndf_check_project_options(opt, o)) return PNDF_ERR_BAD_ARG;
     if (B < 0 || B > PNDF_COMPLETE_MAX_B) return PNDF_ERR_BAD_ARG;
     if (B == 0) return PNDF_OK;
-    if (!q || !d || !dq) return PNDF_ERR_BAD_ARG;
-    if ((((uintptr_t)q) | ((uintptr_t)dq)) & 15) return PNDF_ERR_BAD_ARG;
-    if ((((uintptr_t)d) | ((uintptr_t)observed)) & 3) return PNDF_ERR_BAD_ARG;
+    if (!q || !d || !dq || pndf_check_step_alignment({q, dq}, d, observed)) return PNDF_ERR_BAD_ARG;
     DeviceGuard guard(pndf_pointer_device(q));
     if (!guard.ok) return PNDF_ERR_HIP;
     pndf_complete_step_enqueue(q, d, dq, observed, B, o, stream);
-    StepStatus status;
+    PndfStepStatus status;
     return pndf_check_launch(&status, "pndf_complete_step");
 }
 

@@ -391,30 +391,35 @@ extern "C" int pndf_project_cpu(pndf_cpu_handle h, const float* q_in, float* q_o
     });
 }
 
-// One step of pndf_project_ex on the host: the statement sequence of pndf_device.h's project_step, every operation rounded to fp32
-// on its own (no contraction), so that the two agree bit for bit on equal d and grad.  `held`: bit j = joint j is observed and stays as
-// it is (pndf_complete_cpu; pndf_project_ex_cpu holds none).
-static void project_step_cpu(float* q, const float* dq, float d, const pndf_project_options& o, uint32_t held = 0) {
-#pragma clang fp contract(off)
+// One step of pndf_project_ex on the host: pndf_step.h's pndf_step_quat -- the statement the device kernels run -- for every joint of
+// a pose that does not rest.  `held`: bit j = joint j is observed and stays as it is (pndf_complete_cpu; pndf_project_ex_cpu holds none).
+static void project_step_cpu(float* q, const float* dq, float d, const pndf_project_options& o, uint32_t held) {
     if (o.tol > 0.f && d < o.tol) return;
     for (int j = 0; j < NJ; ++j) {
         if ((held >> j) & 1u) continue;
         float u[4];
-        for (int c = 0; c < 4; ++c) {
-            const float p = d * dq[4 * j + c];
-            const float s = o.step_size * p;
-            u[c] = q[4 * j + c] - s;
-        }
-        if (o.renorm != PNDF_RENORM_NONE) {
-            const float ss = ((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]) + u[3] * u[3];
-            const float n = sqrtf(ss);
-            const float den = (n < 1e-12f) ? 1e-12f : n;
-            for (int c = 0; c < 4; ++c) u[c] = u[c] / den;
-            if (o.renorm == PNDF_RENORM_UNIT_FLIP && u[0] < 0.f)
-                for (int c = 0; c < 4; ++c) u[c] = -u[c];
-        }
-        for (int c = 0; c < 4; ++c) q[4 * j + c] = u[c];
+        (void)pndf_step_quat(q + 4 * j, dq + 4 * j, d, o.step_size, o.tol, (int)o.renorm, u);
+        memcpy(q + 4 * j, u, sizeof(u));
     }
+}
+
+// The loop of pndf_project_ex_cpu and pndf_complete_cpu (validated arguments): `steps` times forward + gradient and the step, block by
+// block; `observed` null = no joint held.
+static int project_loop_cpu(pndf_cpu_handle h, const float* q_in, const uint32_t* observed, float* q_out, float* d_last, int64_t B,
+                            int steps, const pndf_project_options& o) {
+    return guarded(h, [&] {
+    parallel_blocks(B, [&](int64_t p0, int nb, Scratch& S) {
+        float qb[PB * NQ], dqb[PB * NQ], dd[PB];
+        memcpy(qb, q_in + p0 * NQ, sizeof(float) * nb * NQ);
+        for (int p = 0; p < nb; ++p) dd[p] = 0.f;
+        for (int s = 0; s < steps; ++s) {
+            forward_grad_block(*h, qb, nb, nullptr, dd, dqb, true, S);
+            for (int p = 0; p < nb; ++p) project_step_cpu(qb + p * NQ, dqb + p * NQ, dd[p], o, observed ? observed[p0 + p] : 0u);
+        }
+        memcpy(q_out + p0 * NQ, qb, sizeof(float) * nb * NQ);
+        if (d_last) memcpy(d_last + p0, dd, sizeof(float) * nb);
+    });
+    });
 }
 
 extern "C" int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps,
@@ -425,19 +430,7 @@ extern "C" int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* 
     if (pndf_project_options_plain(o)) return pndf_project_cpu(h, q_in, q_out, d_last, B, steps);
     if (int rc = check(h, q_in, B)) return rc;
     if (steps < 0 || (B > 0 && !q_out)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count or null output pointer");
-    return guarded(h, [&] {
-    parallel_blocks(B, [&](int64_t p0, int nb, Scratch& S) {
-        float qb[PB * NQ], dqb[PB * NQ], dd[PB];
-        memcpy(qb, q_in + p0 * NQ, sizeof(float) * nb * NQ);
-        for (int p = 0; p < nb; ++p) dd[p] = 0.f;
-        for (int s = 0; s < steps; ++s) {
-            forward_grad_block(*h, qb, nb, nullptr, dd, dqb, true, S);
-            for (int p = 0; p < nb; ++p) project_step_cpu(qb + p * NQ, dqb + p * NQ, dd[p], o);
-        }
-        memcpy(q_out + p0 * NQ, qb, sizeof(float) * nb * NQ);
-        if (d_last) memcpy(d_last + p0, dd, sizeof(float) * nb);
-    });
-    });
+    return project_loop_cpu(h, q_in, nullptr, q_out, d_last, B, steps, o);
 }
 
 // Host twin of pndf_complete (include/posendf_amd_completion.h): the loop of pndf_project_ex_cpu with the observed joints held.  With
@@ -452,19 +445,7 @@ extern "C" int pndf_complete_cpu(pndf_cpu_handle h, const float* q_in, const uin
     if (steps < 0 || (B > 0 && !q_out)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count or null output pointer");
     if (((uintptr_t)q_in | (uintptr_t)q_out | (uintptr_t)d_last | (uintptr_t)observed) & 3)
         return pndf_fail(h, PNDF_ERR_BAD_ARG, "misaligned pose, distance or mask buffer");
-    return guarded(h, [&] {
-    parallel_blocks(B, [&](int64_t p0, int nb, Scratch& S) {
-        float qb[PB * NQ], dqb[PB * NQ], dd[PB];
-        memcpy(qb, q_in + p0 * NQ, sizeof(float) * nb * NQ);
-        for (int p = 0; p < nb; ++p) dd[p] = 0.f;
-        for (int s = 0; s < steps; ++s) {
-            forward_grad_block(*h, qb, nb, nullptr, dd, dqb, true, S);
-            for (int p = 0; p < nb; ++p) project_step_cpu(qb + p * NQ, dqb + p * NQ, dd[p], o, observed ? observed[p0 + p] : 0u);
-        }
-        memcpy(q_out + p0 * NQ, qb, sizeof(float) * nb * NQ);
-        if (d_last) memcpy(d_last + p0, dd, sizeof(float) * nb);
-    });
-    });
+    return project_loop_cpu(h, q_in, observed, q_out, d_last, B, steps, o);
 }
 
 // Host twin of pndf_interpolate (include/posendf_amd_interpolation.h): the fill and the band step of pndf_interp.h -- the statements
@@ -496,7 +477,7 @@ extern "C" int pndf_interpolate_cpu(pndf_cpu_handle h, const float* a, const flo
             for (int j = 0; j < NJ; ++j) {
                 const float *A = a + (p * NJ + j) * 4, *Bq = b + (p * NJ + j) * 4;
                 float bp[4];
-                pndf_interp_align(A, Bq, bp);
+                pndf_quat_align(A, Bq, bp);
                 memcpy(cur + ((p * T) * NJ + j) * 4, A, sizeof(float) * 4);
                 memcpy(cur + ((p * T + T - 1) * NJ + j) * 4, bp, sizeof(float) * 4);
                 for (int k = 1; k < T - 1; ++k) pndf_interp_fill_quat(A, bp, (float)k / (float)(T - 1), mode, cur + ((p * T + k) * NJ + j) * 4);

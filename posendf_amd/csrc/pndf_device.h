@@ -6,6 +6,7 @@
 
 #include "pndf_layout.h"
 #include "pndf_args.h"
+#include "pndf_step.h"
 
 using namespace pndf;
 
@@ -856,12 +857,8 @@ __device__ __forceinline__ float project_update(float q, float d, float dq) {
 }
 
 // MODE_PROJECT_OPT's step (include/posendf_amd.h pndf_project_options; DESIGN.md section 1 "The projection step"), for the one joint
-// quaternion a lane holds -- norm and sign test need no other lane.  Every operation is rounded to fp32 on its own, in the order
-// written (contraction off: the host twin and a numpy float32 replay give the same bits):
-//   d < tol (tol > 0; false for a NaN d)            the quaternion is returned as it came
-//   u = q - alpha * (d * grad)                      alpha = 1: project_update's result, 1 * p being exact
-//   renorm 1, 2: u / clamp_min(sqrt(((u0 u0 + u1 u1) + u2 u2) + u3 u3), 1e-12)   F.normalize's clamp: 0 stays 0, a NaN norm stays NaN
-//   renorm 2: -u when u0 < 0                        (the sign rule of posendf_amd.trainer.quat_flip)
+// quaternion a lane holds -- norm and sign test need no other lane.  The statement is pndf_step.h's pndf_step_quat (with alpha = 1
+// its descent is project_update's result, 1 * p being exact); a resting pose's quaternion is returned as it came.
 // The options are kernel arguments read ONCE per launch, before any step: stage_project_options parks them in the LDS copy of the
 // bias block (pndf_layout.h POPT_OFF) and the step reads them from there -- the plain loop keeps no register for them, and the step
 // loop gains no global access (the ring's vmcnt accounting sees none of this).
@@ -880,24 +877,10 @@ __device__ __forceinline__ f32x4 project_step(const f32x4 q, const f32x4 dq, flo
     auto uni = [&](int i) { return __builtin_amdgcn_readfirstlane(__float_as_int(lds_bias[POPT_OFF + i])); };
     const float alpha = __int_as_float(uni(0)), tol = __int_as_float(uni(1));
     const int renorm = uni(2);
-    f32x4 u;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const float p = d * dq[c];
-        const float s = alpha * p;
-        u[c] = q[c] - s;
-    }
-    if (renorm) {
-        const float ss = ((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]) + u[3] * u[3];
-        const float n = sqrtf(ss);
-        const float den = (n < 1e-12f) ? 1e-12f : n;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) u[c] = u[c] / den;
-        const bool flip = renorm == 2 && u[0] < 0.f;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) u[c] = flip ? -u[c] : u[c];
-    }
-    return (tol > 0.f && d < tol) ? q : u;
+    const float qv[4] = {q[0], q[1], q[2], q[3]}, gv[4] = {dq[0], dq[1], dq[2], dq[3]};
+    float u[4];
+    const bool rest = pndf_step_quat(qv, gv, d, alpha, tol, renorm, u);
+    return rest ? q : f32x4{u[0], u[1], u[2], u[3]};
 }
 
 template <int NT>

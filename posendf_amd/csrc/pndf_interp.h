@@ -1,7 +1,7 @@
 // Pose interpolation (include/posendf_amd_interpolation.h): what the kernels' translation unit (pndf_interp.hip), pndf_interpolate
 // (pndf_capi.hip, where the engine handle lives) and the host twin (pndf_cpu.cpp, compiled without a device pass) share -- the
-// arithmetic of one joint quaternion of the fill and of the band step, stated ONCE for the device and the host, the argument
-// checks, the workspace layout and the two enqueue functions.
+// arithmetic of one joint quaternion of the fill and of the band step's coupling, stated ONCE for the device and the host around the
+// projection step of pndf_step.h, the argument checks, the workspace layout and the two enqueue functions.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -9,33 +9,7 @@
 #include "../../include/posendf_amd_interpolation.h"
 #include "pndf_complete.h"
 #include "pndf_error.h"
-
-#ifdef __HIP__
-#define PNDF_HD __host__ __device__ __forceinline__
-#else
-#define PNDF_HD inline
-#endif
-
-// ((x0 y0 + x1 y1) + x2 y2) + x3 y3, every operation rounded to fp32 on its own: the sum order of the step's renormalisation
-PNDF_HD float pndf_interp_dot(const float* x, const float* y) {
-#pragma clang fp contract(off)
-    return ((x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]) + x[3] * y[3];
-}
-
-// out = <q, n> < 0 ? -n : n (a NaN dot product does not flip; the negation is exact)
-PNDF_HD void pndf_interp_align(const float* q, const float* n, float* out) {
-    const bool flip = pndf_interp_dot(q, n) < 0.f;
-    for (int c = 0; c < 4; ++c) out[c] = flip ? -n[c] : n[c];
-}
-
-// u / max(|u|, 1e-12): the unit renormalisation of pndf_complete_step_kernel, statement by statement
-PNDF_HD void pndf_interp_unit(float* u) {
-#pragma clang fp contract(off)
-    const float ss = ((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]) + u[3] * u[3];
-    const float n = sqrtf(ss);
-    const float den = (n < 1e-12f) ? 1e-12f : n;
-    for (int c = 0; c < 4; ++c) u[c] = u[c] / den;
-}
+#include "pndf_step.h"
 
 // An interior frame of the fill: `bp` is b aligned to a, t = (float)k / (float)(T-1).
 PNDF_HD void pndf_interp_fill_quat(const float* a, const float* bp, float t, int mode, float* u) {
@@ -47,8 +21,8 @@ PNDF_HD void pndf_interp_fill_quat(const float* a, const float* bp, float t, int
             dm[c] = a[c] - bp[c];
             dp[c] = a[c] + bp[c];
         }
-        const float s = sqrtf(pndf_interp_dot(dm, dm));
-        const float p = sqrtf(pndf_interp_dot(dp, dp));
+        const float s = sqrtf(pndf_quat_dot(dm, dm));
+        const float p = sqrtf(pndf_quat_dot(dp, dp));
         const float theta = 2.0f * atan2f(s, p);
         const float sn = sinf(theta);
         if (sn > 0.f) {      // false for theta == 0 (a == b') and for a NaN: the linear weights
@@ -62,7 +36,7 @@ PNDF_HD void pndf_interp_fill_quat(const float* a, const float* bp, float t, int
         const float xb = wb * bp[c];
         u[c] = xa + xb;
     }
-    pndf_interp_unit(u);
+    pndf_quat_unit(u);
 }
 
 // A free joint quaternion of the band step.  nm / np: the joint in the two neighbour frames, read only when lambda > 0.
@@ -70,15 +44,11 @@ PNDF_HD void pndf_interp_fill_quat(const float* a, const float* bp, float t, int
 PNDF_HD bool pndf_interp_band_quat(const float* Q, const float* G, float dist, const float* nm, const float* np, float lambda, float alpha,
                                    float tol, int renorm, float* u) {
 #pragma clang fp contract(off)
-    for (int c = 0; c < 4; ++c) {
-        const float p = dist * G[c];
-        const float s = alpha * p;
-        u[c] = Q[c] - s;
-    }
+    pndf_step_descend(Q, G, dist, alpha, u);
     if (lambda > 0.f) {
         float am[4], ap[4];
-        pndf_interp_align(Q, nm, am);
-        pndf_interp_align(Q, np, ap);
+        pndf_quat_align(Q, nm, am);
+        pndf_quat_align(Q, np, ap);
         for (int c = 0; c < 4; ++c) {
             const float sum = am[c] + ap[c];
             const float h = 0.5f * sum;
@@ -87,12 +57,7 @@ PNDF_HD bool pndf_interp_band_quat(const float* Q, const float* G, float dist, c
             u[c] = u[c] + lm;
         }
     }
-    if (renorm) {
-        pndf_interp_unit(u);
-        const bool flip = renorm == 2 && u[0] < 0.f;
-        for (int c = 0; c < 4; ++c) u[c] = flip ? -u[c] : u[c];
-    }
-    return tol > 0.f && dist < tol;      // false for a NaN d: not frozen
+    return pndf_step_finish(dist, tol, renorm, u);
 }
 
 // P pairs of T frames are P * T poses for the engine and the kernels: the reason a shape is refused, or nullptr
@@ -110,7 +75,7 @@ inline const char* pndf_interp_check_lambda(float lambda) {
 }
 
 // the workspace of pndf_interpolate: d [B] padded to a multiple of four floats, dq [B,21,4], the second pose buffer [B,21,4]
-inline int64_t pndf_interp_workspace_floats(int64_t B) { return pndf_complete_d_floats(B) + 2 * B * (int64_t)(21 * 4); }
+inline int64_t pndf_interp_workspace_floats(int64_t B) { return pndf_complete_d_floats(B) + 2 * B * (int64_t)pndf::NQ; }
 
 // Enqueue the kernels on `stream` and nothing else: no validation (the callers have done it), no device selection, no error check
 // -- the caller follows them with pndf_check_launch.

@@ -12,36 +12,19 @@
 //                             dq of its own quaternion, d[f] and -- only when lambda > 0 -- the same joint of frames k-1 and k+1
 //                             of ITS pair (k is interior, so both exist and neither belongs to another pair): four 16-byte loads,
 //                             the 4-byte d[f] and the mask word, then pndf_interp_band_quat and one 16-byte store.
-// The arithmetic is pndf_interp.h's, shared with the host twin: every operation rounded to fp32 on its own (contraction off).  The
+// The arithmetic is shared with the host twin, every operation rounded to fp32 on its own (contraction off): the fill and the coupling
+// are pndf_interp.h's, the projection step around the coupling is pndf_step.h's, which the fused kernels call too.  The
 // options are plain kernel arguments.  No LDS, no atomics, no communication between lanes; q_out never aliases q_in, so one step
 // is a Jacobi update and the same inputs give the same bits (tests/test_interpolation_gpu.py).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#include <string>
 
 #include "../../include/posendf_amd_interpolation.h"
 #include "pndf_host.h"
 #include "pndf_interp.h"
 #include "pndf_project_opts.h"
 
-namespace {
-
-constexpr int NJ = 21;            // joints = 16-byte quaternions per pose
-constexpr int THREADS = 256;
-
-// the stateless helpers have no handle: pndf_check_launch leaves its text here and the code is returned
-struct StepStatus {
-    std::string err;
-};
-
-__device__ __forceinline__ void unpack(const float4 v, float* x) {
-    x[0] = v.x, x[1] = v.y, x[2] = v.z, x[3] = v.w;
-}
-
-unsigned blocks_for(long long quats) { return (unsigned)((quats + THREADS - 1) / THREADS); }
-
-}  // namespace
+using pndf::NJ;
 
 extern "C" __global__ void __launch_bounds__(256) pndf_interp_fill_kernel(const float4* __restrict__ a, const float4* __restrict__ b,
                                                                           float4* __restrict__ track, long long quats, int T, int mode) {
@@ -58,9 +41,9 @@ extern "C" __global__ void __launch_bounds__(256) pndf_interp_fill_kernel(const 
         return;
     }
     float av[4], bv[4], bp[4], u[4];
-    unpack(A, av);
-    unpack(B, bv);
-    pndf_interp_align(av, bv, bp);
+    pndf_quat_unpack(A, av);
+    pndf_quat_unpack(B, bv);
+    pndf_quat_align(av, bv, bp);
     if (k < T - 1) {
         const float t = (float)k / (float)(T - 1);
         pndf_interp_fill_quat(av, bp, t, mode, u);
@@ -89,11 +72,11 @@ extern "C" __global__ void __launch_bounds__(256) pndf_interp_band_kernel(const 
     const float dist = d[f];
     const float4 G = dq[i];
     float qv[4], gv[4], nm[4] = {0.f, 0.f, 0.f, 0.f}, np[4] = {0.f, 0.f, 0.f, 0.f}, u[4];
-    unpack(Q, qv);
-    unpack(G, gv);
+    pndf_quat_unpack(Q, qv);
+    pndf_quat_unpack(G, gv);
     if (lambda > 0.f) {      // 0 < k < T-1: i - 21 and i + 21 are the same joint in frames k-1 and k+1 of the same pair
-        unpack(q_in[i - NJ], nm);
-        unpack(q_in[i + NJ], np);
+        pndf_quat_unpack(q_in[i - NJ], nm);
+        pndf_quat_unpack(q_in[i + NJ], np);
     }
     const bool rest = pndf_interp_band_quat(qv, gv, dist, nm, np, lambda, alpha, tol, renorm, u);
     q_out[i] = rest ? Q : make_float4(u[0], u[1], u[2], u[3]);
@@ -101,14 +84,14 @@ extern "C" __global__ void __launch_bounds__(256) pndf_interp_band_kernel(const 
 
 void pndf_interp_fill_enqueue(const float* a, const float* b, float* track, int64_t P, int32_t T, int32_t mode, void* stream) {
     const long long quats = (long long)P * T * NJ;
-    hipLaunchKernelGGL(pndf_interp_fill_kernel, dim3(blocks_for(quats)), dim3(THREADS), 0, (hipStream_t)stream, (const float4*)a,
+    hipLaunchKernelGGL(pndf_interp_fill_kernel, dim3(pndf_step_blocks(quats)), dim3(PNDF_STEP_THREADS), 0, (hipStream_t)stream, (const float4*)a,
                        (const float4*)b, (float4*)track, quats, (int)T, (int)mode);
 }
 
 void pndf_interp_band_enqueue(const float* q_in, float* q_out, const float* d, const float* dq, const uint32_t* observed, int64_t P,
                               int32_t T, float lambda, const pndf_project_options& o, void* stream) {
     const long long quats = (long long)P * T * NJ;
-    hipLaunchKernelGGL(pndf_interp_band_kernel, dim3(blocks_for(quats)), dim3(THREADS), 0, (hipStream_t)stream, (const float4*)q_in,
+    hipLaunchKernelGGL(pndf_interp_band_kernel, dim3(pndf_step_blocks(quats)), dim3(PNDF_STEP_THREADS), 0, (hipStream_t)stream, (const float4*)q_in,
                        (float4*)q_out, d, (const float4*)dq, observed, quats, (int)T, lambda, o.step_size, o.tol, (int)o.renorm);
 }
 
@@ -117,12 +100,11 @@ extern "C" int pndf_interp_fill(const float* a, const float* b, float* track, in
     PndfRange range("pndf_interp_fill");
     if (pndf_interp_check_shape(P, T) || pndf_interp_check_mode(mode)) return PNDF_ERR_BAD_ARG;
     if (P == 0) return PNDF_OK;
-    if (!a || !b || !track) return PNDF_ERR_BAD_ARG;
-    if ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)track)) & 15) return PNDF_ERR_BAD_ARG;
+    if (!a || !b || !track || pndf_check_step_alignment({a, b, track}, nullptr, nullptr)) return PNDF_ERR_BAD_ARG;
     DeviceGuard guard(pndf_pointer_device(track));
     if (!guard.ok) return PNDF_ERR_HIP;
     pndf_interp_fill_enqueue(a, b, track, P, T, mode, stream);
-    StepStatus status;
+    PndfStepStatus status;
     return pndf_check_launch(&status, "pndf_interp_fill");
 }
 
@@ -134,12 +116,11 @@ extern "C" int pndf_interp_band_step(const float* q_in, float* q_out, const floa
     if (pndf_interp_check_shape(P, T) || pndf_interp_check_lambda(lambda)) return PNDF_ERR_BAD_ARG;
     if (P == 0) return PNDF_OK;
     if (!q_in || !q_out || !d || !dq || q_out == q_in) return PNDF_ERR_BAD_ARG;
-    if ((((uintptr_t)q_in) | ((uintptr_t)q_out) | ((uintptr_t)dq)) & 15) return PNDF_ERR_BAD_ARG;
-    if ((((uintptr_t)d) | ((uintptr_t)observed)) & 3) return PNDF_ERR_BAD_ARG;
+    if (pndf_check_step_alignment({q_in, q_out, dq}, d, observed)) return PNDF_ERR_BAD_ARG;
     DeviceGuard guard(pndf_pointer_device(q_out));
     if (!guard.ok) return PNDF_ERR_HIP;
     pndf_interp_band_enqueue(q_in, q_out, d, dq, observed, P, T, lambda, o, stream);
-    StepStatus status;
+    PndfStepStatus status;
     return pndf_check_launch(&status, "pndf_interp_band_step");
 }
 

@@ -295,6 +295,12 @@ def project_options(lib, step_size=1.0, renorm="none", tol=0.0):
     return opt
 
 
+def _opt_ref(lib, step_size, renorm, tol):
+    """the `const pndf_project_options*` argument of the entry points that take null for the defaults"""
+    opt = project_options(lib, step_size, renorm, tol)
+    return None if opt is None else ctypes.byref(opt)
+
+
 def interp_mode(mode) -> int:
     """PNDF_INTERP_* of a fill mode's name"""
     if mode not in INTERP_MODES:
@@ -420,14 +426,12 @@ class Engine(_Handle):
     def complete(self, q_in_ptr, observed_ptr, q_out_ptr, d_ptr, B, steps, ws_ptr, stream=0, *, step_size=1.0, renorm="none", tol=0.0):
         """pndf_complete (include/posendf_amd_completion.h): the projection loop with the joints of `observed_ptr` (one uint32 per
         pose, bit j = joint j; None = no joint) held; `ws_ptr`: complete_workspace_floats(B) floats of device memory"""
-        opt = project_options(self.lib, step_size, renorm, tol)
         self._check(self.lib.pndf_complete(self.handle, q_in_ptr, observed_ptr, q_out_ptr, d_ptr, B, int(steps),
-                                           None if opt is None else ctypes.byref(opt), ws_ptr, stream), "pndf_complete")
+                                           _opt_ref(self.lib, step_size, renorm, tol), ws_ptr, stream), "pndf_complete")
 
     def complete_step(self, q_ptr, d_ptr, dq_ptr, observed_ptr, B, stream=0, *, step_size=1.0, renorm="none", tol=0.0):
         """pndf_complete_step: one masked step on q in place from the d and dq of a forward_grad (a stateless helper: no text)"""
-        opt = project_options(self.lib, step_size, renorm, tol)
-        rc = self.lib.pndf_complete_step(q_ptr, d_ptr, dq_ptr, observed_ptr, B, None if opt is None else ctypes.byref(opt), stream)
+        rc = self.lib.pndf_complete_step(q_ptr, d_ptr, dq_ptr, observed_ptr, B, _opt_ref(self.lib, step_size, renorm, tol), stream)
         if rc != 0:
             raise PndfError(f"pndf_complete_step failed ({rc}): B = {B}; q and dq must be non-null and 16-byte aligned, d non-null, "
                             "the options those of pndf_project_ex")
@@ -443,9 +447,9 @@ class Engine(_Handle):
         """pndf_interpolate (include/posendf_amd_interpolation.h): the track [P,T,21,4] between the pairs a, b [P,21,4] -- the fill
         in `mode`, then `steps` band steps with the neighbour coupling `smooth` (lambda); `observed_ptr`: one uint32 per pose of the
         track or None; `ws_ptr`: interpolate_workspace(P, T) floats of device memory"""
-        opt = project_options(self.lib, step_size, renorm, tol)
+        opt = _opt_ref(self.lib, step_size, renorm, tol)      # (refuses an unknown `renorm` before an unknown `mode`)
         self._check(self.lib.pndf_interpolate(self.handle, a_ptr, b_ptr, observed_ptr, track_ptr, d_ptr, int(P), int(T), interp_mode(mode),
-                                              int(steps), float(smooth), None if opt is None else ctypes.byref(opt), ws_ptr, stream),
+                                              int(steps), float(smooth), opt, ws_ptr, stream),
                     "pndf_interpolate")
 
     def interp_fill(self, a_ptr, b_ptr, track_ptr, P, T, stream=0, *, mode="slerp"):
@@ -457,9 +461,8 @@ class Engine(_Handle):
     def interp_band_step(self, q_in_ptr, q_out_ptr, d_ptr, dq_ptr, observed_ptr, P, T, stream=0, *, smooth=0.0, step_size=1.0, renorm="none",
                          tol=0.0):
         """pndf_interp_band_step: one out-of-place band step from the d and dq of a forward_grad (a stateless helper: no text)"""
-        opt = project_options(self.lib, step_size, renorm, tol)
         rc = self.lib.pndf_interp_band_step(q_in_ptr, q_out_ptr, d_ptr, dq_ptr, observed_ptr, int(P), int(T), float(smooth),
-                                            None if opt is None else ctypes.byref(opt), stream)
+                                            _opt_ref(self.lib, step_size, renorm, tol), stream)
         if rc != 0:
             raise PndfError(f"pndf_interp_band_step failed ({rc}): P = {P}, T = {T}, lambda = {smooth}; q_in, q_out and dq must be non-null, "
                             "distinct and 16-byte aligned, d non-null, lambda in [0, 1], the options those of pndf_project_ex")
@@ -683,15 +686,14 @@ class CpuEngine(_Handle):
         return 0      # the host twin needs none
 
     def complete(self, q_in_ptr, observed_ptr, q_out_ptr, d_ptr, B, steps, ws_ptr=None, stream=0, *, step_size=1.0, renorm="none", tol=0.0):
-        opt = project_options(self.lib, step_size, renorm, tol)
         self._check(self.lib.pndf_complete_cpu(self.handle, q_in_ptr, observed_ptr, q_out_ptr, d_ptr, B, int(steps),
-                                               None if opt is None else ctypes.byref(opt)), "pndf_complete_cpu")
+                                               _opt_ref(self.lib, step_size, renorm, tol)), "pndf_complete_cpu")
 
     def interpolate_workspace(self, P, T) -> int:
         return 0      # the host twin needs none
 
     def interpolate(self, a_ptr, b_ptr, observed_ptr, track_ptr, d_ptr, P, T, steps, ws_ptr=None, stream=0, *, mode="slerp", smooth=0.0,
                     step_size=1.0, renorm="none", tol=0.0):
-        opt = project_options(self.lib, step_size, renorm, tol)
+        opt = _opt_ref(self.lib, step_size, renorm, tol)
         self._check(self.lib.pndf_interpolate_cpu(self.handle, a_ptr, b_ptr, observed_ptr, track_ptr, d_ptr, int(P), int(T), interp_mode(mode),
-                                                  int(steps), float(smooth), None if opt is None else ctypes.byref(opt)), "pndf_interpolate_cpu")
+                                                  int(steps), float(smooth), opt), "pndf_interpolate_cpu")
