@@ -26,6 +26,7 @@
 
 #include "../../include/posendf_amd.h"
 #include "../../include/posendf_amd_completion.h"
+#include "../../include/posendf_amd_second_order.h"
 #include "pndf_error.h"
 #include "pndf_interp.h"
 #include "pndf_layout.h"
@@ -502,4 +503,208 @@ extern "C" int pndf_interpolate_cpu(pndf_cpu_handle h, const float* a, const flo
         if (rc == PNDF_OK && d_last) memcpy(d_last, dd.data(), sizeof(float) * B);
     });
     return grc != PNDF_OK ? grc : rc;
+}
+
+// ---- host twin of pndf_second_order (include/posendf_amd_second_order.h): d, g = grad_q d, t = <v, g> and w_d g + w_t H v, one pose at
+// a time through the dual-number network (csrc/pndf_second_order.hip has the derivation): primal and tangent forward with sigma'
+// and sigma'' kept, then both adjoint chains in one reverse -- the tangent's (the first-order reverse, seed 1) and the primal's
+// (seed 0, zbar = abar sigma' + adotbar zdot sigma'') --, then the normalisation with its curvature term.  Values are stored in
+// fp32; a dot product is summed in double and rounded once.
+namespace {
+
+void act3(const Act& a, bool output_layer, float z, float& y, float& d1, float& d2) {
+    if (a.kind == PNDF_ACT_SOFTPLUS) {
+        const float bz = z * a.beta;
+        if (bz > 20.0f) {
+            y = z; d1 = 1.0f; d2 = 0.0f;
+        } else {
+            const float e = expf(bz);
+            y = log1pf(e) / a.beta;
+            d1 = e / (e + 1.0f);
+            d2 = a.beta * d1 * (1.0f - d1);
+        }
+        return;
+    }
+    const float slope = (a.kind == PNDF_ACT_LRELU && !output_layer) ? 0.01f : 0.0f;
+    y = z > 0.0f ? z : z * slope;
+    d1 = z > 0.0f ? 1.0f : slope;
+    d2 = 0.0f;
+}
+
+// y = W x (+ b): w [out][in]
+void matvec(const float* w, const float* b, int out, int in, const float* x, float* y) {
+    for (int o = 0; o < out; ++o) {
+        double s = b ? (double)b[o] : 0.0;
+        for (int i = 0; i < in; ++i) s += (double)w[(size_t)o * in + i] * (double)x[i];
+        y[o] = (float)s;
+    }
+}
+
+struct SoScratch {
+    std::vector<float> a, ad, u, ub, t0, t1, d1[MAXLIN], c2[MAXLIN];
+};
+
+void second_order_pose(const pndf_cpu_engine& E, const float* q, const float* v, float wd, float wt, float* d, float* g, float* t,
+                       float* out, SoScratch& S) {
+    const Act act{E.cfg.act, E.cfg.beta};
+    const Act eact{E.cfg.enc_act == -1 ? E.cfg.act : E.cfg.enc_act, E.cfg.enc_beta > 0.f ? E.cfg.enc_beta : E.cfg.beta};
+    constexpr int FIN = 4 + FEAT;
+    // ---- normalisation: x, xdot = J_N v
+    float s[4], va[4], x[NQ], xd[NQ];
+    bool live[4];
+    for (int c = 0; c < 4; ++c) {
+        double ss = 0.0;
+        for (int j = 0; j < NJ; ++j) ss += (double)q[4 * j + c] * (double)q[4 * j + c];
+        s[c] = (float)sqrt(ss);
+        live[c] = s[c] > 1e-12f;
+        const float den = std::max(s[c], 1e-12f);
+        double a = 0.0;
+        for (int j = 0; j < NJ; ++j) {
+            x[4 * j + c] = q[4 * j + c] / den;
+            a += (double)x[4 * j + c] * (double)v[4 * j + c];
+        }
+        va[c] = (float)a;
+        for (int j = 0; j < NJ; ++j) xd[4 * j + c] = live[c] ? (v[4 * j + c] - x[4 * j + c] * va[c]) / s[c] : v[4 * j + c] / 1e-12f;
+    }
+    // ---- encoder: primal and tangent, the derivatives kept per bone
+    float feat[NFEAT], tfeat[NFEAT], d1h[NJ][HID], d2h[NJ][HID], hz[NJ][HID], d1o[NJ][FEAT], d2o[NJ][FEAT], oz[NJ][FEAT];
+    for (int j = 0; j < NJ; ++j) {
+        const int in = enc_in(j);
+        float xi[FIN], xdi[FIN], zh[HID], ah[HID], ahd[HID], zo[FEAT];
+        memcpy(xi, x + 4 * j, sizeof(float) * 4);
+        memcpy(xdi, xd + 4 * j, sizeof(float) * 4);
+        if (PARENT[j] >= 0) {
+            memcpy(xi + 4, feat + FEAT * PARENT[j], sizeof(float) * FEAT);
+            memcpy(xdi + 4, tfeat + FEAT * PARENT[j], sizeof(float) * FEAT);
+        }
+        matvec(E.enc[j][0].w.data(), E.enc[j][0].b.data(), HID, in, xi, zh);
+        matvec(E.enc[j][0].w.data(), nullptr, HID, in, xdi, hz[j]);
+        for (int k = 0; k < HID; ++k) {
+            act3(eact, false, zh[k], ah[k], d1h[j][k], d2h[j][k]);
+            ahd[k] = d1h[j][k] * hz[j][k];
+        }
+        matvec(E.enc[j][1].w.data(), E.enc[j][1].b.data(), FEAT, HID, ah, zo);
+        matvec(E.enc[j][1].w.data(), nullptr, FEAT, HID, ahd, oz[j]);
+        for (int i = 0; i < FEAT; ++i) {
+            act3(eact, false, zo[i], feat[FEAT * j + i], d1o[j][i], d2o[j][i]);
+            tfeat[FEAT * j + i] = oz[j][i] * d1o[j][i];
+        }
+    }
+    // ---- trunk: primal and tangent; c2 = sigma'' zdot
+    const int NL = E.nlin;
+    S.a.assign(feat, feat + NFEAT);
+    S.ad.assign(tfeat, tfeat + NFEAT);
+    for (int l = 0; l < NL; ++l) {
+        const Layer& L = E.lin[l];
+        S.t0.resize(L.out); S.t1.resize(L.out); S.d1[l].resize(L.out); S.c2[l].resize(L.out);
+        matvec(L.w.data(), L.b.data(), L.out, L.in, S.a.data(), S.t0.data());
+        matvec(L.w.data(), nullptr, L.out, L.in, S.ad.data(), S.t1.data());
+        for (int o = 0; o < L.out; ++o) {
+            float y, d2;
+            act3(act, l == NL - 1, S.t0[o], y, S.d1[l][o], d2);
+            S.t0[o] = y;
+            S.c2[l][o] = d2 * S.t1[o];
+            S.t1[o] = S.d1[l][o] * S.t1[o];
+        }
+        S.a.swap(S.t0);
+        S.ad.swap(S.t1);
+    }
+    if (d) *d = S.a[0];
+    // ---- reverse: u = adjoint of the tangent's pre-activation (seed 1), ub = of the primal's (seed 0)
+    S.u.assign(1, S.d1[NL - 1][0]);
+    S.ub.assign(1, S.c2[NL - 1][0]);
+    for (int l = NL - 1; l >= 0; --l) {
+        const Layer& L = E.lin[l];
+        S.t0.resize(L.in); S.t1.resize(L.in);
+        matvec(L.wt.data(), nullptr, L.in, L.out, S.u.data(), S.t0.data());
+        matvec(L.wt.data(), nullptr, L.in, L.out, S.ub.data(), S.t1.data());
+        if (l > 0)
+            for (int i = 0; i < L.in; ++i) {
+                S.t1[i] = S.t1[i] * S.d1[l - 1][i] + S.t0[i] * S.c2[l - 1][i];
+                S.t0[i] = S.t0[i] * S.d1[l - 1][i];
+            }
+        S.u.swap(S.t0);
+        S.ub.swap(S.t1);
+    }
+    // ---- encoder reverse, children before parents: gx = d d / d x, xb = hess f xdot
+    float gx[NQ], xb[NQ];
+    float* gf = S.u.data();
+    float* af = S.ub.data();
+    for (int j = NJ - 1; j >= 0; --j) {
+        const int in = enc_in(j);
+        float zob[FEAT], zodb[FEAT], sb[HID], sdb[HID], zhb[HID], zhdb[HID], gi[FIN], ai[FIN];
+        for (int i = 0; i < FEAT; ++i) {
+            zodb[i] = gf[FEAT * j + i] * d1o[j][i];
+            zob[i] = af[FEAT * j + i] * d1o[j][i] + gf[FEAT * j + i] * oz[j][i] * d2o[j][i];
+        }
+        matvec(E.enc[j][1].wt.data(), nullptr, HID, FEAT, zodb, sdb);
+        matvec(E.enc[j][1].wt.data(), nullptr, HID, FEAT, zob, sb);
+        for (int k = 0; k < HID; ++k) {
+            zhb[k] = sb[k] * d1h[j][k] + sdb[k] * hz[j][k] * d2h[j][k];
+            zhdb[k] = sdb[k] * d1h[j][k];
+        }
+        matvec(E.enc[j][0].wt.data(), nullptr, in, HID, zhdb, gi);
+        matvec(E.enc[j][0].wt.data(), nullptr, in, HID, zhb, ai);
+        memcpy(gx + 4 * j, gi, sizeof(float) * 4);
+        memcpy(xb + 4 * j, ai, sizeof(float) * 4);
+        if (PARENT[j] >= 0)
+            for (int i = 0; i < FEAT; ++i) {
+                gf[FEAT * PARENT[j] + i] += gi[4 + i];
+                af[FEAT * PARENT[j] + i] += ai[4 + i];
+            }
+    }
+    // ---- the normalisation: per component column with n = x, p = xdot, g = J g_x:  H v = J xbar - [(g_x . p) n + (n . v) g + (g_x . n) p] / s;
+    // on the clamp J = I / eps and there is no curvature
+    double tt = 0.0;
+    for (int c = 0; c < 4; ++c) {
+        double b = 0.0, e = 0.0, gp = 0.0;
+        for (int j = 0; j < NJ; ++j) {
+            b += (double)x[4 * j + c] * (double)gx[4 * j + c];
+            e += (double)x[4 * j + c] * (double)xb[4 * j + c];
+            gp += (double)gx[4 * j + c] * (double)xd[4 * j + c];
+        }
+        const float bf = (float)b, ef = (float)e, gpf = (float)gp;
+        for (int j = 0; j < NJ; ++j) {
+            const int i = 4 * j + c;
+            float gg, hv;
+            if (live[c]) {
+                gg = (gx[i] - x[i] * bf) / s[c];
+                hv = (xb[i] - x[i] * ef) / s[c] - (gpf * x[i] + va[c] * gg + bf * xd[i]) / s[c];
+            } else {
+                gg = gx[i] / 1e-12f;
+                hv = xb[i] / 1e-12f;
+            }
+            tt += (double)v[i] * (double)gg;
+            if (g) g[i] = gg;
+            if (out) out[i] = wd * gg + wt * hv;
+        }
+    }
+    if (t) *t = (float)tt;
+}
+
+}  // namespace
+
+extern "C" int pndf_second_order_cpu(pndf_cpu_handle h, const float* q, const float* v, const float* w_d, const float* w_t, float* d,
+                                     float* g, float* t, float* out, int64_t B) {
+    if (!h) return PNDF_ERR_BAD_ARG;
+    if (!h->encoder)
+        return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "the second order needs the structure encoder (model.StrEnc.use: True, dims[0] = 126)");
+    if (int rc = check(h, q, B)) return rc;
+    if (B == 0) return PNDF_OK;
+    if (!v) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null direction pointer");
+    if (((uintptr_t)q | (uintptr_t)v | (uintptr_t)w_d | (uintptr_t)w_t | (uintptr_t)d | (uintptr_t)g | (uintptr_t)t | (uintptr_t)out) & 3)
+        return pndf_fail(h, PNDF_ERR_BAD_ARG, "misaligned pose, direction, weight or output buffer");
+    auto overlaps = [B](const float* a, const float* b) {
+        return a && b && (uintptr_t)a < (uintptr_t)(b + B * NQ) && (uintptr_t)b < (uintptr_t)(a + B * NQ);
+    };
+    if (overlaps(out, q) || overlaps(out, v) || overlaps(g, q) || overlaps(g, v) || overlaps(g, out))
+        return pndf_fail(h, PNDF_ERR_BAD_ARG, "out and g must not alias q, v or each other");
+    return guarded(h, [&] {
+        parallel_blocks(B, [&](int64_t p0, int nb, Scratch&) {
+            SoScratch S;
+            for (int64_t p = p0; p < p0 + nb; ++p)
+                second_order_pose(*h, q + p * NQ, v + p * NQ, w_d ? w_d[p] : 0.0f, w_t ? w_t[p] : 1.0f, d ? d + p : nullptr,
+                                  g ? g + p * NQ : nullptr, t ? t + p : nullptr, out ? out + p * NQ : nullptr, S);
+        });
+    });
 }

@@ -1,0 +1,492 @@
+// Second order of the distance on gfx950 (include/posendf_amd_second_order.h): for poses q, directions v and per-pose weights
+// w_d, w_t one call gives  d(q),  g = grad_q d,  t = <v, g>  and  out = grad_q (w_d d + w_t <v, grad_q d>) = w_d g + w_t H v.
+// The weights of the network are constants here (the train=False path): this is the double backward of
+// model/posendf.py:18-27,62-76,100-101 with respect to the pose alone.
+//
+// With x = normalize(q, dim=1) and f the encoder plus trunk:  g = J_N g_x,  xdot = J_N v,  H v = J_N (hess f xdot) + C(q, v, g_x),
+// C the curvature of the normalisation.  hess f xdot comes from the dual-number network csrc/pndf_train.hip differentiates the
+// eikonal term through, seeded with dbar = 0, ddotbar = 1: the adjoint chain of the tangent is the first-order reverse (it gives
+// g_x), the adjoint chain of the primal carries  zbar = abar sigma' + adotbar zdot sigma''.
+//
+// Layer by layer over a chunk of SO_CHUNK poses, every activation matrix [features][columns] (the pose index contiguous) in the
+// caller's workspace; the chunk is a function of B only and bounds the workspace (0.53 GB for configs/amass.yaml with softplus):
+//   pndf_so_enc_fwd_kernel   lanes own poses: x, xdot, the encoder and its tangent
+//   trunk forward            NN GEMMs, epilogue bias + sigma, stores sigma' and (softplus) sigma''
+//   softplus trunk only      tangent forward (NN, * sigma', sigma'' zdot kept), the tangent's adjoint chain (TN, * sigma',
+//                            adotbar sigma'' zdot kept), the primal's adjoint chain (TN, * sigma' + the kept cross term)
+//   relu family trunk        sigma'' = 0: the first-order reverse alone (TN, * sigma'); the primal adjoint of the features is zero
+//   pndf_so_enc_rev_kernel   lanes own poses: both adjoint chains through the 21 bone MLPs (no weight gradient, so no
+//                            reduction), then the normalisation: g, t, J_N xbar + C, the four outputs
+// A relu-family network (trunk and encoder) has hess f = 0: H v = C, and the tangent and the primal chain are skipped everywhere.
+// Arithmetic: exact fp32 MFMA (v_mfma_f32_16x16x4_f32), fp32 accumulate.  No float atomics, no communication between workgroups
+// inside a launch: two calls with the same inputs give the same bits.
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+#include <string.h>
+
+#include <string>
+
+#include "../../include/posendf_amd_second_order.h"
+#include "pndf_experiment.h"
+#include "pndf_gemm.h"
+#include "pndf_host.h"
+
+PNDF_EXPORT_EXPERIMENT_WORD(second_order)
+
+namespace {
+
+// Poses per pass over the layers: a constant, so the chunk seams depend on B only.  Measured at B = 65,536 on amass.yaml's dims
+// (lrelu / softplus, ms per call; profiles/second_order/chunk_sweep.jsonl): 4,096 -> 20.9 / 44.2, 8,192 -> 11.4 / 24.5, 16,384 -> 7.75 / 17.6.  A 4,096-column chunk would keep its
+// 133 MB inside the last-level cache, but the 128 x 128 GEMM tile then fills half of the 256 CUs on the 512-row layers with one
+// workgroup each; 16,384 columns give every layer at least two workgroups per CU, and that outweighs the cache.
+constexpr int64_t SO_CHUNK = 16384;
+
+struct SoArgs {
+    const float* wenc;        // packed encoder weights
+    const float* q;           // the chunk's poses [n][84]
+    const float* v;           // the chunk's directions [n][84]
+    const float* w_d;         // [n] or null (0)
+    const float* w_t;         // [n] or null (1)
+    float* d_out;             // [n] or null
+    float* g_out;             // [n][84] or null
+    float* t_out;             // [n] or null
+    float* h_out;             // [n][84] or null
+    float* X;                 // normalised poses [84][ld]
+    float* Xd;                // xdot = J_N v [84][ld]                                   (dual only)
+    float* act0;              // encoder output [126][ld]
+    float* tan0;              // its tangent [126][ld]                                    (dual only)
+    float* U0;                // adjoint of the tangent features = d d / d act0 [126][ld], accumulated in place
+    float* A0;                // adjoint of the primal features [126][ld], accumulated in place  (dual only)
+    float* Gx;                // g_x [84][ld]
+    float* Xb;                // xbar = hess f xdot [84][ld]                              (dual only)
+    const float* dist;        // the trunk's output row [ld]
+    int64_t n, ld;
+    int act, dual, zero_a0;   // act / beta: the encoder's; dual: the network has a softplus; zero_a0: no trunk pass writes A0
+    float beta;
+    int parent[NJ];
+    int off[NJ];
+};
+
+// bone j's input on column c: its own normalised quaternion and its parent's feature; `tan`: the tangents of both
+template <int FIN>
+__device__ __forceinline__ void so_load_in(const SoArgs& e, int j, int64_t c, bool tan, float* in) {
+    const float* x = tan ? e.Xd : e.X;
+    const float* f = tan ? e.tan0 : e.act0;
+#pragma unroll
+    for (int k = 0; k < BONE; ++k) in[k] = x[(int64_t)(j * BONE + k) * e.ld + c];
+    if (FIN > BONE) {
+        const int p = e.parent[j];
+#pragma unroll
+        for (int i = 0; i < FIN - BONE; ++i) in[BONE + i] = f[(int64_t)(p * FEAT + i) * e.ld + c];
+    }
+}
+
+// the tangent pre-activations of one bone along `ind`: hidden (hz), the hidden tangent (ahd = sigma' hz), output (oz)
+template <int FIN>
+__device__ __forceinline__ void so_bone_tan(const float* w, const float* ind, const float* d1h, float* hz, float* ahd, float* oz) {
+    const float* w2 = bone_w2<FIN>(w);
+    bone_lin0<FIN>(w, ind, hz, false);
+#pragma unroll
+    for (int k = 0; k < HID; ++k) ahd[k] = d1h[k] * hz[k];
+#pragma unroll
+    for (int i = 0; i < FEAT; ++i) {
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < HID; ++k) s = fmaf(w2[i * HID + k], ahd[k], s);
+        oz[i] = s;
+    }
+}
+
+// primal and (dual) tangent forward of one bone
+template <int FIN>
+__device__ __forceinline__ void so_fwd_bone(const SoArgs& e, int j, int64_t c) {
+    const float* w = e.wenc + e.off[j];
+    float in[FIN], ah[HID], d1h[HID], d2h[HID], ao[FEAT], d1o[FEAT], d2o[FEAT];
+    so_load_in<FIN>(e, j, c, false, in);
+    bone_fwd<FIN>(e, w, in, ah, d1h, d2h, ao, d1o, d2o);
+#pragma unroll
+    for (int i = 0; i < FEAT; ++i) e.act0[(int64_t)(j * FEAT + i) * e.ld + c] = ao[i];
+    if (!e.dual) return;
+    float ind[FIN], hz[HID], ahd[HID], oz[FEAT];
+    so_load_in<FIN>(e, j, c, true, ind);
+    so_bone_tan<FIN>(w, ind, d1h, hz, ahd, oz);
+#pragma unroll
+    for (int i = 0; i < FEAT; ++i) e.tan0[(int64_t)(j * FEAT + i) * e.ld + c] = oz[i] * d1o[i];
+}
+
+// reverse of one bone for one pose.  The tangent's adjoint (U0 -> Gx, the parent's rows of U0) is the first-order reverse; with
+// `dual` the primal's adjoint (A0 -> Xb, the parent's rows of A0) runs next to it with the sigma'' cross terms.
+template <int FIN>
+__device__ __forceinline__ void so_rev_bone(const SoArgs& e, int j, int64_t c) {
+    const float* w = e.wenc + e.off[j];
+    const float* w2 = bone_w2<FIN>(w);
+    float in[FIN], ah[HID], d1h[HID], d2h[HID], ao[FEAT], d1o[FEAT], d2o[FEAT];
+    so_load_in<FIN>(e, j, c, false, in);
+    bone_fwd<FIN>(e, w, in, ah, d1h, d2h, ao, d1o, d2o);
+    float hz[HID], ahd[HID], oz[FEAT];
+#pragma unroll
+    for (int k = 0; k < HID; ++k) hz[k] = 0.f;
+#pragma unroll
+    for (int i = 0; i < FEAT; ++i) oz[i] = 0.f;
+    if (e.dual) {
+        float ind[FIN];
+        so_load_in<FIN>(e, j, c, true, ind);
+        so_bone_tan<FIN>(w, ind, d1h, hz, ahd, oz);
+    }
+    float zob[FEAT], zodb[FEAT], zhb[HID], zhdb[HID];
+#pragma unroll
+    for (int i = 0; i < FEAT; ++i) {
+        const float adb = e.U0[(int64_t)(j * FEAT + i) * e.ld + c];
+        const float ab = e.dual ? e.A0[(int64_t)(j * FEAT + i) * e.ld + c] : 0.f;
+        zob[i] = ab * d1o[i] + adb * oz[i] * d2o[i];
+        zodb[i] = adb * d1o[i];
+    }
+#pragma unroll
+    for (int k = 0; k < HID; ++k) {
+        float s = 0.f, sd = 0.f;
+#pragma unroll
+        for (int i = 0; i < FEAT; ++i) {
+            s = fmaf(w2[i * HID + k], zob[i], s);
+            sd = fmaf(w2[i * HID + k], zodb[i], sd);
+        }
+        zhb[k] = s * d1h[k] + sd * hz[k] * d2h[k];
+        zhdb[k] = sd * d1h[k];
+    }
+#pragma unroll
+    for (int m = 0; m < FIN; ++m) {
+        float s = 0.f, sd = 0.f;
+#pragma unroll
+        for (int k = 0; k < HID; ++k) {
+            s = fmaf(w[k * FIN + m], zhb[k], s);
+            sd = fmaf(w[k * FIN + m], zhdb[k], sd);
+        }
+        if (m < BONE) {
+            e.Gx[(int64_t)(j * BONE + m) * e.ld + c] = sd;
+            if (e.dual) e.Xb[(int64_t)(j * BONE + m) * e.ld + c] = s;
+        } else {
+            const int64_t at = (int64_t)(e.parent[j] * FEAT + (m - BONE)) * e.ld + c;
+            e.U0[at] += sd;
+            if (e.dual) e.A0[at] += s;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" __global__ void __launch_bounds__(256) pndf_so_gemm_nn_kernel(GemmArgs g) { gemm_body<1, 0>(g); }
+extern "C" __global__ void __launch_bounds__(256) pndf_so_gemm_tn_kernel(GemmArgs g) { gemm_body<0, 0>(g); }
+
+// the caller's 84 encoder tensors -> one flat array
+extern "C" __global__ void __launch_bounds__(256) pndf_so_enc_pack_kernel(PtrTable t, float* dst) { enc_pack_body(t, dst); }
+
+// x = normalize(q, dim=1) (over the joint axis, per quaternion component), xdot = J_N v, the encoder and its tangent
+extern "C" __global__ void __launch_bounds__(256) pndf_so_enc_fwd_kernel(SoArgs e) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= e.n) return;
+    const float* q = e.q + c * POSE;
+    const float* v = e.v + c * POSE;
+    float n2[BONE] = {0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int k = 0; k < BONE; ++k) n2[k] = fmaf(q[j * BONE + k], q[j * BONE + k], n2[k]);
+    float nrm[BONE], den[BONE], a[BONE] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < BONE; ++k) {
+        nrm[k] = sqrtf(n2[k]);
+        den[k] = fmaxf(nrm[k], NORM_EPS);
+    }
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int k = 0; k < BONE; ++k) {
+            const float x = q[j * BONE + k] / den[k];
+            e.X[(int64_t)(j * BONE + k) * e.ld + c] = x;
+            a[k] = fmaf(x, v[j * BONE + k], a[k]);
+        }
+    if (e.dual) {
+        // J_N v = (v - x (x . v)) / |q_k| per component k (a column of 21 joints); v / eps where the norm is clamped
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+            for (int k = 0; k < BONE; ++k) {
+                const float x = e.X[(int64_t)(j * BONE + k) * e.ld + c];
+                e.Xd[(int64_t)(j * BONE + k) * e.ld + c] = nrm[k] > NORM_EPS ? (v[j * BONE + k] - x * a[k]) / nrm[k] : v[j * BONE + k] / NORM_EPS;
+            }
+    }
+    for (int j = 0; j < NJ; ++j) {
+        if (e.parent[j] < 0) so_fwd_bone<BONE>(e, j, c);
+        else so_fwd_bone<BONE + FEAT>(e, j, c);
+    }
+    if (e.zero_a0)
+        for (int f = 0; f < ENC_IN; ++f) e.A0[(int64_t)f * e.ld + c] = 0.f;
+}
+
+// both adjoint chains through the encoder, then the normalisation and the four outputs.  Per component column k with s = |q_k|,
+// n = q_k / s, p = J v_k, g = J g_k (J = (I - n n^T) / s):   H v = J xbar_k - [(g_k . p) n + (n . v_k) g + (g_k . n) p] / s;
+// where the norm is clamped the normalisation is linear: J = I / eps and no curvature.
+extern "C" __global__ void __launch_bounds__(256) pndf_so_enc_rev_kernel(SoArgs e) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= e.n) return;
+    for (int j = NJ - 1; j >= 0; --j) {
+        if (e.parent[j] < 0) so_rev_bone<BONE>(e, j, c);
+        else so_rev_bone<BONE + FEAT>(e, j, c);
+    }
+    const float* q = e.q + c * POSE;
+    const float* v = e.v + c * POSE;
+    float n2[BONE] = {0.f, 0.f, 0.f, 0.f}, a[BONE] = {0.f, 0.f, 0.f, 0.f}, b[BONE] = {0.f, 0.f, 0.f, 0.f}, xe[BONE] = {0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int k = 0; k < BONE; ++k) {
+            const int64_t at = (int64_t)(j * BONE + k) * e.ld + c;
+            const float x = e.X[at];
+            n2[k] = fmaf(q[j * BONE + k], q[j * BONE + k], n2[k]);
+            a[k] = fmaf(x, v[j * BONE + k], a[k]);
+            b[k] = fmaf(x, e.Gx[at], b[k]);
+            if (e.dual) xe[k] = fmaf(x, e.Xb[at], xe[k]);
+        }
+    float s[BONE], gp[BONE] = {0.f, 0.f, 0.f, 0.f};
+    bool live[BONE];
+#pragma unroll
+    for (int k = 0; k < BONE; ++k) {
+        s[k] = sqrtf(n2[k]);
+        live[k] = s[k] > NORM_EPS;
+    }
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int k = 0; k < BONE; ++k) {
+            const int64_t at = (int64_t)(j * BONE + k) * e.ld + c;
+            const float p = (v[j * BONE + k] - e.X[at] * a[k]) / s[k];
+            if (live[k]) gp[k] = fmaf(e.Gx[at], p, gp[k]);
+        }
+    const float wd = e.w_d ? e.w_d[c] : 0.f, wt = e.w_t ? e.w_t[c] : 1.f;
+    float t = 0.f;
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int k = 0; k < BONE; ++k) {
+            const int64_t at = (int64_t)(j * BONE + k) * e.ld + c;
+            const float x = e.X[at], gx = e.Gx[at], vv = v[j * BONE + k];
+            const float xb = e.dual ? e.Xb[at] : 0.f;
+            float g, hv;
+            if (live[k]) {
+                const float p = (vv - x * a[k]) / s[k];
+                g = (gx - x * b[k]) / s[k];
+                hv = (xb - x * xe[k]) / s[k] - (gp[k] * x + a[k] * g + b[k] * p) / s[k];
+            } else {
+                g = gx / NORM_EPS;
+                hv = xb / NORM_EPS;
+            }
+            t = fmaf(vv, g, t);
+            if (e.g_out) e.g_out[c * POSE + j * BONE + k] = g;
+            if (e.h_out) e.h_out[c * POSE + j * BONE + k] = wd * g + wt * hv;
+        }
+    if (e.t_out) e.t_out[c] = t;
+    if (e.d_out) e.d_out[c] = e.dist[c];
+}
+
+// ------------------------------------------------------------------------------------------------------------ host side
+struct pndf_so_plan {
+    int device = 0;
+    int L = 0;                    // linear layers of the trunk
+    int dims[MAX_LIN + 1] = {};   // dims[0] = 126 ... dims[L] = 1
+    int act = 0, enc_act = 0;
+    float beta = 100.f, enc_beta = 100.f;
+    int parent[NJ] = {};
+    int enc_off[NJ] = {};         // offset of bone j in the packed encoder
+    int enc_tensor_off[ENC_TENSORS + 1] = {};
+    int enc_params = 0;
+    int maxw = 0;
+    bool dual_trunk = false, dual = false;      // softplus trunk; a softplus anywhere
+    std::string err;
+};
+
+namespace {
+
+// workspace layout in floats (every region 256-byte aligned); nc: the columns of a chunk
+struct SoLayout {
+    int64_t nc;
+    int64_t wenc, X, Xd, act0, tan0, U0, A0, Gx, Xb, dist, D1[MAX_LIN], D2[MAX_LIN], P[2];
+    int64_t total;
+};
+
+SoLayout so_layout(const pndf_so_plan* h, int64_t B) {
+    SoLayout l{};
+    l.nc = B < SO_CHUNK ? B : SO_CHUNK;
+    int64_t o = 0;
+    auto take = [&](int64_t n) { const int64_t at = o; o += align64(n); return at; };
+    l.wenc = take(h->enc_params);
+    l.X = take(POSE * l.nc);
+    l.Xd = h->dual ? take(POSE * l.nc) : -1;
+    l.act0 = take(ENC_IN * l.nc);
+    l.tan0 = h->dual ? take(ENC_IN * l.nc) : -1;
+    l.U0 = take(ENC_IN * l.nc);
+    l.A0 = h->dual ? take(ENC_IN * l.nc) : -1;
+    l.Gx = take(POSE * l.nc);
+    l.Xb = h->dual ? take(POSE * l.nc) : -1;
+    l.dist = take(l.nc);
+    for (int t = 0; t < h->L; ++t) l.D1[t] = take((int64_t)h->dims[t + 1] * l.nc);
+    for (int t = 0; t < h->L; ++t) l.D2[t] = h->dual_trunk ? take((int64_t)h->dims[t + 1] * l.nc) : -1;
+    // the two ping-pong buffers every pass over the layers runs through
+    l.P[0] = take((int64_t)h->maxw * l.nc);
+    l.P[1] = take((int64_t)h->maxw * l.nc);
+    l.total = o;
+    return l;
+}
+
+enum { SO_GEMM_NN, SO_GEMM_TN };
+void so_launch_gemm(int kind, const GemmArgs& g, hipStream_t st) {
+    const dim3 grid((g.N + TN - 1) / TN, (g.M + TM - 1) / TM, 1);
+    if (kind == SO_GEMM_NN) hipLaunchKernelGGL(pndf_so_gemm_nn_kernel, grid, dim3(256), 0, st, g);
+    else hipLaunchKernelGGL(pndf_so_gemm_tn_kernel, grid, dim3(256), 0, st, g);
+}
+
+bool overlaps(const float* a, const float* b, int64_t floats) {
+    return a && b && (uintptr_t)a < (uintptr_t)(b + floats) && (uintptr_t)b < (uintptr_t)(a + floats);
+}
+
+}  // namespace
+
+extern "C" const char* pndf_so_last_error(pndf_so_handle h) { return pndf_last_error_of(h); }
+
+extern "C" int pndf_so_create(pndf_so_handle* out, const pndf_config* cfg, int device) {
+    if (!out || !cfg) return pndf_fail<pndf_so_plan>(nullptr, PNDF_ERR_BAD_ARG, "out / cfg is null");
+    *out = nullptr;
+    if (const char* why = layer_network_refusal(cfg, "the second order needs the structure encoder (model.StrEnc.use: True, dims[0] = 126)"))
+        return pndf_fail<pndf_so_plan>(nullptr, PNDF_ERR_UNSUPPORTED, why);
+    const PndfDeviceCheck dev = pndf_check_gfx950(device, "the second order");
+    if (dev.code != PNDF_OK) return pndf_fail<pndf_so_plan>(nullptr, dev.code, dev.text);
+    pndf_so_plan* h = new pndf_so_plan();
+    h->device = device;
+    h->L = cfg->n_dims - 1;
+    for (int t = 0; t <= h->L; ++t) {
+        h->dims[t] = cfg->dims[t];
+        if (cfg->dims[t] > h->maxw) h->maxw = cfg->dims[t];
+    }
+    h->act = cfg->act;
+    h->beta = cfg->beta;
+    h->enc_act = cfg->enc_act >= 0 ? cfg->enc_act : cfg->act;
+    h->enc_beta = cfg->enc_beta > 0.f ? cfg->enc_beta : cfg->beta;
+    h->dual_trunk = h->act == PNDF_ACT_SOFTPLUS;
+    h->dual = h->dual_trunk || h->enc_act == PNDF_ACT_SOFTPLUS;
+    int o = 0, k = 0;
+    for (int j = 0; j < NJ; ++j) {
+        h->parent[j] = cfg->parent[j];
+        h->enc_off[j] = o;
+        const int fin = cfg->parent[j] < 0 ? BONE : BONE + FEAT;
+        const int sizes[4] = {HID * fin, HID, FEAT * HID, FEAT};
+        for (int s = 0; s < 4; ++s) {
+            h->enc_tensor_off[k++] = o;
+            o += sizes[s];
+        }
+    }
+    h->enc_tensor_off[ENC_TENSORS] = o;
+    h->enc_params = o;
+    *out = h;
+    return PNDF_OK;
+}
+
+extern "C" int pndf_so_destroy(pndf_so_handle h) {
+    delete h;
+    return PNDF_OK;
+}
+
+extern "C" int64_t pndf_so_workspace_floats(pndf_so_handle h, int64_t B) {
+    if (!h || B < 0) return PNDF_ERR_BAD_ARG;
+    return B == 0 ? 0 : so_layout(h, B).total;
+}
+
+extern "C" int pndf_second_order(pndf_so_handle h, const float* const* weights, const float* q, const float* v, const float* w_d,
+                                 const float* w_t, float* d, float* g, float* t, float* out, int64_t B, void* workspace,
+                                 int64_t workspace_floats, void* stream) {
+    if (!h) return PNDF_ERR_BAD_ARG;
+    if (B < 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative batch");
+    if (B == 0) return PNDF_OK;
+    if (!weights || !q || !v || !workspace) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pointer");
+    if (((uintptr_t)workspace & 15) != 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "workspace must be 16-byte aligned");
+    if (((uintptr_t)q | (uintptr_t)v | (uintptr_t)w_d | (uintptr_t)w_t | (uintptr_t)d | (uintptr_t)g | (uintptr_t)t | (uintptr_t)out) & 3)
+        return pndf_fail(h, PNDF_ERR_BAD_ARG, "misaligned pose, direction, weight or output buffer");
+    if (overlaps(out, q, B * POSE) || overlaps(out, v, B * POSE) || overlaps(g, q, B * POSE) || overlaps(g, v, B * POSE) || overlaps(g, out, B * POSE))
+        return pndf_fail(h, PNDF_ERR_BAD_ARG, "out and g must not alias q, v or each other");
+    const SoLayout l = so_layout(h, B);
+    if (workspace_floats < l.total)
+        return pndf_fail(h, PNDF_ERR_BAD_ARG, "workspace of " + std::to_string(workspace_floats) + " floats, pndf_so_workspace_floats asks for " + std::to_string(l.total));
+    for (int i = 0; i < ENC_TENSORS + 2 * h->L; ++i)
+        if (!weights[i]) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null weight tensor " + std::to_string(i));
+    PndfRange range("pndf_second_order");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    float* ws = (float*)workspace;
+    const float* const* W = weights + ENC_TENSORS;          // trunk layer t: W[2t] weight [dims[t+1]][dims[t]], W[2t+1] bias
+    const int L = h->L;
+    const int64_t ld = l.nc;
+
+    PtrTable tab;
+    for (int k = 0; k < ENC_TENSORS; ++k) tab.p[k] = const_cast<float*>(weights[k]);
+    for (int k = 0; k <= ENC_TENSORS; ++k) tab.off[k] = h->enc_tensor_off[k];
+    hipLaunchKernelGGL(pndf_so_enc_pack_kernel, dim3(blocks(h->enc_params)), dim3(256), 0, st, tab, ws + l.wenc);
+
+    SoArgs e;
+    memset(&e, 0, sizeof(e));
+    e.wenc = ws + l.wenc;
+    e.X = ws + l.X; e.act0 = ws + l.act0; e.U0 = ws + l.U0; e.Gx = ws + l.Gx; e.dist = ws + l.dist;
+    if (h->dual) { e.Xd = ws + l.Xd; e.tan0 = ws + l.tan0; e.A0 = ws + l.A0; e.Xb = ws + l.Xb; }
+    e.ld = ld;
+    e.act = h->enc_act; e.beta = h->enc_beta; e.dual = h->dual ? 1 : 0; e.zero_a0 = (h->dual && !h->dual_trunk) ? 1 : 0;
+    for (int j = 0; j < NJ; ++j) { e.parent[j] = h->parent[j]; e.off[j] = h->enc_off[j]; }
+
+    for (int64_t c0 = 0; c0 < B; c0 += l.nc) {
+        const int n = (int)(B - c0 < l.nc ? B - c0 : l.nc);
+        e.n = n;
+        e.q = q + c0 * POSE; e.v = v + c0 * POSE;
+        e.w_d = w_d ? w_d + c0 : nullptr; e.w_t = w_t ? w_t + c0 : nullptr;
+        e.d_out = d ? d + c0 : nullptr; e.g_out = g ? g + c0 * POSE : nullptr;
+        e.t_out = t ? t + c0 : nullptr; e.h_out = out ? out + c0 * POSE : nullptr;
+        hipLaunchKernelGGL(pndf_so_enc_fwd_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
+        // 1. forward: layer t reads act0 / P[(t-1)&1] and writes P[t&1]; the output row goes to `dist`
+        for (int tt = 0; tt < L; ++tt) {
+            GemmArgs a = gemm_args(W[2 * tt], h->dims[tt], tt == 0 ? ws + l.act0 : ws + l.P[(tt - 1) & 1], ld,
+                                   tt == L - 1 ? ws + l.dist : ws + l.P[tt & 1], ld, h->dims[tt + 1], n, h->dims[tt]);
+            a.epi = EPI_FWD; a.act = h->act; a.beta = h->beta; a.out_layer = tt == L - 1; a.bias = W[2 * tt + 1];
+            a.D1 = ws + l.D1[tt]; a.ld1 = ld;
+            if (h->dual_trunk) { a.D2 = ws + l.D2[tt]; a.ld2 = ld; a.nB = n; }
+            so_launch_gemm(SO_GEMM_NN, a, st);
+        }
+        if (h->dual_trunk) {
+            // 2. tangent forward: adot = sigma' zdot; sigma'' zdot replaces sigma''
+            for (int tt = 0; tt < L; ++tt) {
+                GemmArgs a = gemm_args(W[2 * tt], h->dims[tt], tt == 0 ? ws + l.tan0 : ws + l.P[(tt - 1) & 1], ld, ws + l.P[tt & 1], ld,
+                                       h->dims[tt + 1], n, h->dims[tt]);
+                a.epi = EPI_TAN; a.D1 = ws + l.D1[tt]; a.ld1 = ld; a.D2 = ws + l.D2[tt]; a.ld2 = ld;
+                so_launch_gemm(SO_GEMM_NN, a, st);
+            }
+        }
+        // 3. the tangent's adjoint chain from zdotbar = sigma' of the output (seed ddotbar = 1): the first-order reverse.  Softplus:
+        //    adotbar sigma'' zdot replaces sigma'' zdot on the way
+        const float* U = ws + l.D1[L - 1];
+        for (int tt = L - 1; tt >= 0; --tt) {
+            float* o = tt == 0 ? ws + l.U0 : ws + l.P[tt & 1];
+            GemmArgs a = gemm_args(W[2 * tt], h->dims[tt], U, ld, o, ld, h->dims[tt], n, h->dims[tt + 1]);
+            if (tt > 0 && h->dual_trunk) {
+                a.epi = EPI_TAN; a.D1 = ws + l.D1[tt - 1]; a.ld1 = ld; a.D2 = ws + l.D2[tt - 1]; a.ld2 = ld;
+            } else {
+                a.epi = EPI_MUL;
+                if (tt > 0) { a.D1 = ws + l.D1[tt - 1]; a.ld1 = ld; }
+            }
+            so_launch_gemm(SO_GEMM_TN, a, st);
+            U = o;
+        }
+        if (h->dual_trunk) {
+            // 4. the primal's adjoint chain from zbar = sigma'' zdot of the output (seed dbar = 0): abar sigma' + the kept cross term
+            const float* Z = ws + l.D2[L - 1];
+            for (int tt = L - 1; tt >= 0; --tt) {
+                float* o = tt == 0 ? ws + l.A0 : ws + l.P[tt & 1];
+                GemmArgs a = gemm_args(W[2 * tt], h->dims[tt], Z, ld, o, ld, h->dims[tt], n, h->dims[tt + 1]);
+                a.epi = EPI_MUL;
+                if (tt > 0) { a.D1 = ws + l.D1[tt - 1]; a.ld1 = ld; a.X = ws + l.D2[tt - 1]; a.ldx = ld; a.nB = n; }
+                so_launch_gemm(SO_GEMM_TN, a, st);
+                Z = o;
+            }
+        }
+        hipLaunchKernelGGL(pndf_so_enc_rev_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
+    }
+    return pndf_check_launch(h, "pndf_second_order");
+}

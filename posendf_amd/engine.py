@@ -60,8 +60,8 @@ class PndfError(RuntimeError):
 
 
 # ---- the C ABI, one table per header: name -> (restype, argtypes), in the header's order.  load_library() binds the tables, EXPORTS /
-# COMPLETION_EXPORTS / INTERPOLATION_EXPORTS / DEBUG_EXPORTS are their names, tests/test_cabi.py, tests/test_completion.py and
-# tests/test_interpolation.py hold them against the declarations of the headers.
+# COMPLETION_EXPORTS / INTERPOLATION_EXPORTS / SECOND_ORDER_EXPORTS / DEBUG_EXPORTS are their names, tests/test_cabi.py,
+# tests/test_completion.py, tests/test_interpolation.py and tests/test_second_order.py hold them against the declarations of the headers.
 _H = c_void_p                          # every handle type, and every `void* stream`
 _P = c_void_p                          # any other address: tensor data (an int from data_ptr(), or None), a callback, an out value
 _TENSORS = [POINTER(c_void_p), POINTER(c_int64), c_int]      # tensors, numel, n_tensors (host pointers in state-dict order)
@@ -162,13 +162,22 @@ _INTERPOLATION_SIGNATURES = {      # include/posendf_amd_interpolation.h: pose i
     "pndf_interpolate": (c_int, [_H, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int, c_float, POINTER(ProjectOptions), _P, _H]),
     "pndf_interpolate_cpu": (c_int, [_H, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int, c_float, POINTER(ProjectOptions)]),
 }
+_SECOND_ORDER_SIGNATURES = {      # include/posendf_amd_second_order.h: Hessian-vector products of the distance, the third companion header
+    "pndf_so_create": (c_int, [POINTER(_H), POINTER(PndfConfig), c_int]),
+    "pndf_so_destroy": (c_int, [_H]),
+    "pndf_so_last_error": (c_char_p, [_H]),
+    "pndf_so_workspace_floats": (c_int64, [_H, c_int64]),
+    "pndf_second_order": (c_int, [_H] + [_P] * 9 + [c_int64, _P, c_int64, _H]),
+    "pndf_second_order_cpu": (c_int, [_H] + [_P] * 8 + [c_int64]),
+}
 EXPORTS, DEBUG_EXPORTS = tuple(_SIGNATURES), tuple(_DEBUG_SIGNATURES)
 COMPLETION_EXPORTS = tuple(_COMPLETION_SIGNATURES)
 INTERPOLATION_EXPORTS = tuple(_INTERPOLATION_SIGNATURES)
+SECOND_ORDER_EXPORTS = tuple(_SECOND_ORDER_SIGNATURES)
 # per-translation-unit experiment words (csrc/pndf_experiment.h): data symbols, all zero in a product build
 EXPERIMENT_WORDS = ("pndf_experiment_word_capi", "pndf_experiment_word_fp32", "pndf_experiment_word_split", "pndf_experiment_word_split_x2",
                     "pndf_experiment_word_bf16", "pndf_experiment_word_lbs", "pndf_experiment_word_generic", "pndf_experiment_word_train",
-                    "pndf_experiment_word_optim")
+                    "pndf_experiment_word_optim", "pndf_experiment_word_second_order")
 DEBUG_EXPERIMENT_WORDS = ("pndf_experiment_word_debug", "pndf_experiment_word_fp32_timing", "pndf_experiment_word_split_timing",
                           "pndf_experiment_word_fp32_dbg", "pndf_experiment_word_probe")
 
@@ -218,7 +227,8 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     if not os.path.exists(path):
         raise PndfError(f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                         "(hipcc --offload-arch=gfx950). The engine has no fallback path.")
-    return _bind(_bind(_bind(_PndfLibrary(path), _SIGNATURES), _COMPLETION_SIGNATURES), _INTERPOLATION_SIGNATURES)
+    lib = _bind(_bind(_bind(_PndfLibrary(path), _SIGNATURES), _COMPLETION_SIGNATURES), _INTERPOLATION_SIGNATURES)
+    return _bind(lib, _SECOND_ORDER_SIGNATURES)
 
 
 def experiment_word(lib=None) -> int:
@@ -553,6 +563,37 @@ class TrainEngine(_Handle):
                                                  stream), "pndf_train_backward")
 
 
+class SecondOrderEngine(_Handle):
+    """`pndf_so_*` / `pndf_second_order` (csrc/pndf_second_order.hip): d, grad_q d, <v, grad_q d> and w_d grad_q d + w_t H v on one
+    device, the weights read in place.  Exact fp32 MFMA; the structure encoder is required.  Raw device pointers (the weights as
+    a list of them, state-dict order) and a stream handle."""
+    _destroy, _last_error = "pndf_so_destroy", "pndf_so_last_error"
+
+    def __init__(self, act: str = "lrelu", beta: float = 100.0, device: int = 0, lib=None, encoder: bool = True, hidden=None,
+                 enc_act: str | None = None, enc_beta: float | None = None):
+        self.lib = lib or load_library()
+        cfg = _network_config(self.lib, act, beta, encoder=encoder, hidden=hidden, enc_act=enc_act, enc_beta=enc_beta)
+        self.n_tensors = len(state_dict_order(encoder, cfg.n_dims - 1))
+        self._create("pndf_so_create", ctypes.byref(cfg), int(device))
+        self.device = device
+        self.act = act
+
+    def workspace_floats(self, B) -> int:
+        n = int(self.lib.pndf_so_workspace_floats(self.handle, int(B)))
+        if n < 0:
+            raise PndfError(f"pndf_so_workspace_floats failed ({n}): B = {B}")
+        return n
+
+    def second_order(self, weight_ptrs, q_ptr, v_ptr, wd_ptr, wt_ptr, d_ptr, g_ptr, t_ptr, out_ptr, B, ws_ptr, ws_floats, stream=0):
+        """every output pointer, wd_ptr (0) and wt_ptr (1) may be None"""
+        if not isinstance(weight_ptrs, ctypes.Array):
+            if len(weight_ptrs) != self.n_tensors:
+                raise PndfError(f"{len(weight_ptrs)} tensors given, the network has {self.n_tensors}")
+            weight_ptrs = (c_void_p * len(weight_ptrs))(*weight_ptrs)
+        self._check(self.lib.pndf_second_order(self.handle, weight_ptrs, q_ptr, v_ptr, wd_ptr, wt_ptr, d_ptr, g_ptr, t_ptr, out_ptr, int(B),
+                                               ws_ptr, int(ws_floats), stream), "pndf_second_order")
+
+
 def adam_step(p_ptr, g_ptr, m_ptr, v_ptr, n, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, stream=0, lib=None):
     """`pndf_adam_step` (csrc/pndf_optim.hip): one torch.optim.Adam step over flat fp32 device buffers of n floats"""
     rc = (lib or load_library()).pndf_adam_step(p_ptr, g_ptr, m_ptr, v_ptr, int(n), int(step), float(lr), float(beta1), float(beta2),
@@ -697,3 +738,9 @@ class CpuEngine(_Handle):
         opt = _opt_ref(self.lib, step_size, renorm, tol)
         self._check(self.lib.pndf_interpolate_cpu(self.handle, a_ptr, b_ptr, observed_ptr, track_ptr, d_ptr, int(P), int(T), interp_mode(mode),
                                                   int(steps), float(smooth), opt), "pndf_interpolate_cpu")
+
+    def second_order(self, q_ptr, v_ptr, wd_ptr, wt_ptr, d_ptr, g_ptr, t_ptr, out_ptr, B):
+        """pndf_second_order_cpu (include/posendf_amd_second_order.h) with the weights of load_weights; outputs, wd_ptr (0) and wt_ptr
+        (1) may be None"""
+        self._check(self.lib.pndf_second_order_cpu(self.handle, q_ptr, v_ptr, wd_ptr, wt_ptr, d_ptr, g_ptr, t_ptr, out_ptr, int(B)),
+                    "pndf_second_order_cpu")

@@ -13,6 +13,10 @@ selected by the pose's device alone, never by a failure of the device path.
 
 `forward(train=True)` runs on the stock PyTorch modules unless `opt['engine']['train'] = 'hip'`: then a cuda model's training
 objective and every weight gradient come from csrc/pndf_train.hip (posendf_amd.train.TrainObjective), again with no fallback.
+
+`hvp(pose, v)` gives the distance, its pose gradient and Hessian-vector products with respect to the pose
+(include/posendf_amd_second_order.h); `opt['engine']['second_order'] = 'hip'` makes the train=False gradient itself differentiable
+once more through the same entry point (default 'off': a double backward raises).
 """
 from __future__ import annotations
 
@@ -24,7 +28,7 @@ import torch
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
-from .engine import CpuEngine, Engine, PndfError, TrainEngine, state_dict_order, stream_handle
+from .engine import CpuEngine, Engine, PndfError, SecondOrderEngine, TrainEngine, state_dict_order, stream_handle
 from .modules import DFNet, StructureEncoder
 
 
@@ -35,33 +39,78 @@ def gradient(inputs, outputs):
                                retain_graph=True, only_inputs=True)[0]
 
 
+def _distance_launch(pose, owner, want_grad):
+    """dist_pred [B,1] and, when asked for, d dist / d pose [B,21,4] (else None) from ONE kernel launch"""
+    q = pose.detach()
+    if q.dtype != torch.float32 or not q.is_contiguous():
+        q = q.float().contiguous()
+    B = q.shape[0]
+    d = torch.empty(B, device=q.device, dtype=torch.float32)
+    eng = owner._engine_for(q.device)
+    stream = stream_handle(q.device)
+    dq = None
+    if want_grad:
+        dq = torch.empty_like(q)
+        eng.forward_grad(q.data_ptr(), None, d.data_ptr(), dq.data_ptr(), B, stream)
+    else:
+        eng.forward(q.data_ptr(), d.data_ptr(), B, stream)
+    return d.view(B, 1), dq
+
+
 class _Distance(torch.autograd.Function):
     """dist_pred = f(pose) with first-order autograd: backward(g) = g * d dist / d pose.
     Both come from ONE kernel launch; double backward is not provided (train=True path has it)."""
 
     @staticmethod
     def forward(ctx, pose, owner):
-        q = pose.detach()
-        if q.dtype != torch.float32 or not q.is_contiguous():
-            q = q.float().contiguous()
-        B = q.shape[0]
-        d = torch.empty(B, device=q.device, dtype=torch.float32)
-        eng = owner._engine_for(q.device)
-        stream = stream_handle(q.device)
-        if ctx.needs_input_grad[0]:     # one launch yields d and d d/d pose
-            dq = torch.empty_like(q)
-            eng.forward_grad(q.data_ptr(), None, d.data_ptr(), dq.data_ptr(), B, stream)
+        d, dq = _distance_launch(pose, owner, ctx.needs_input_grad[0])
+        if dq is not None:
             ctx.save_for_backward(dq)
-        else:
-            eng.forward(q.data_ptr(), d.data_ptr(), B, stream)
         ctx.pose_dtype = pose.dtype
-        return d.view(B, 1)
+        return d
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
         (dq,) = ctx.saved_tensors
         return (grad_out.reshape(-1, 1, 1).to(dq.dtype) * dq).to(ctx.pose_dtype), None
+
+
+class _Distance2(torch.autograd.Function):
+    """`_Distance` for opt['engine']['second_order'] = 'hip': the same launch and the same values, but the backward is itself a
+    differentiable function of (pose, grad_out)."""
+
+    @staticmethod
+    def forward(ctx, pose, owner):
+        d, dq = _distance_launch(pose, owner, ctx.needs_input_grad[0])
+        if dq is not None:
+            ctx.save_for_backward(pose, dq)
+        ctx.owner = owner
+        return d
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        pose, dq = ctx.saved_tensors
+        return _DistanceGrad.apply(pose, grad_out, dq, ctx.owner), None
+
+
+class _DistanceGrad(torch.autograd.Function):
+    """(pose, grad_out) -> grad_out * d dist / d pose, the value from the forward's launch (`dq`).  Its backward, given the incoming
+    v: grad_out * H v for the pose and <v, d dist / d pose> for grad_out, from one pndf_second_order call; a third order raises."""
+
+    @staticmethod
+    def forward(ctx, pose, grad_out, dq, owner):
+        ctx.save_for_backward(pose, grad_out)
+        ctx.owner = owner
+        return (grad_out.reshape(-1, 1, 1).to(dq.dtype) * dq).to(pose.dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, v):
+        pose, grad_out = ctx.saved_tensors
+        need_pose, need_go = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        _, _, t, out = ctx.owner._second_order(pose.detach(), v, None, grad_out.detach().reshape(-1), want=(False, False, need_go, need_pose))
+        return (out.to(pose.dtype) if need_pose else None, t.reshape(grad_out.shape).to(grad_out.dtype) if need_go else None, None, None)
 
 
 class PoseNDF(nn.Module):
@@ -100,7 +149,17 @@ class PoseNDF(nn.Module):
         if self._train_backend == "hip" and self.enc is None:
             raise PndfError("opt['engine']['train'] = 'hip' needs the structure encoder (model.StrEnc.use: True): the reference's "
                             "train=True branch cannot run without it either")
+        # engine knob (no reference counterpart): "off" (default: the train=False gradient is once differentiable, a double backward
+        # raises) or "hip" (it is differentiable once more, through pndf_second_order / its host twin; a third order raises)
+        self._second_order_mode = (opt.get("engine") or {}).get("second_order", "off")
+        if self._second_order_mode not in ("off", "hip"):
+            raise ValueError(f"opt['engine']['second_order'] must be 'off' or 'hip', not {self._second_order_mode!r}")
+        if self._second_order_mode == "hip" and self.enc is None:
+            raise PndfError("opt['engine']['second_order'] = 'hip' needs the structure encoder (model.StrEnc.use: True)")
         self._train_engines = {}    # device index -> TrainEngine
+        self._so_engines = {}       # device index -> SecondOrderEngine
+        self._so_params = None      # (the _param_list it was made from, the Parameters in state-dict order)
+        self._so_workspaces = {}    # (device index, stream) -> workspace tensor, grown on demand
         self._engines = {}          # device index -> (Engine, weight fingerprint)
         self._param_list = None     # cached list(self.parameters()): walking the module tree costs 0.15 ms per call
 
@@ -178,7 +237,8 @@ class PoseNDF(nn.Module):
     def forward(self, pose, dist_gt=None, man_poses=None, train=True, eikonal=0.0):
         pose = pose.to(device=self.device).reshape(-1, 21, 4)      # posendf.py:64
         if not train:
-            return {"dist_pred": _Distance.apply(pose, self)}      # posendf.py:100-101
+            fn = _Distance2 if self._second_order_mode == "hip" else _Distance
+            return {"dist_pred": fn.apply(pose, self)}             # posendf.py:100-101
         if self._train_backend == "hip" and pose.device.type == "cuda":
             return self._forward_train_hip(pose, dist_gt, man_poses, eikonal)
         # ------ training objective: stock PyTorch modules (posendf.py:65-99)
@@ -217,6 +277,61 @@ class PoseNDF(nn.Module):
         return loss, {"dist": loss}
 
     # ---- added surface (north_star: `.project` on the model) -------------------------------------
+    def _ordered_parameters(self):
+        """the live Parameters in state-dict order; the walk of the module tree is cached next to `_fingerprint`'s and rebuilt with it"""
+        self._fingerprint()      # validates (or rebuilds) self._param_list by identity
+        c = self._so_params
+        if c is None or c[0] is None or c[0] is not self._param_list:
+            named = dict(self.named_parameters())
+            c = self._so_params = (self._param_list, [named[k] for k in state_dict_order(True, len(self._hidden) + 1)])
+        return c[1]
+
+    def _second_order(self, q, v, w_d, w_t, want=(True, True, True, True)):
+        """pndf_second_order (cuda poses) or its host twin (cpu poses) -> (d [B], g [B,21,4], t [B], out [B,21,4]) in fp32, None
+        where `want` is False.  q, v: [B,21,4]; w_d, w_t: [B] or None (0 and 1)."""
+        def f32(x):
+            return None if x is None else x.detach().to(device=q.device, dtype=torch.float32).contiguous()
+        q = f32(q.reshape(-1, 21, 4))
+        B = q.shape[0]
+        v = f32(v.reshape(B, 21, 4))
+        w_d = f32(w_d if w_d is None else w_d.reshape(B))
+        w_t = f32(w_t if w_t is None else w_t.reshape(B))
+        shapes = ((B,), (B, 21, 4), (B,), (B, 21, 4))
+        outs = [torch.empty(s, device=q.device, dtype=torch.float32) if w else None for s, w in zip(shapes, want)]
+        ptr = [None if x is None or B == 0 else x.data_ptr() for x in (w_d, w_t, *outs)]
+        if q.device.type == "cpu":
+            self._engine_for(q.device).second_order(q.data_ptr(), v.data_ptr(), *ptr, B)
+            return outs
+        if q.device.type != "cuda":
+            raise PndfError(f"the second order runs on the HIP engine (cuda) or the host twin (cpu), not on {q.device}")
+        if self.enc is None:
+            raise PndfError("the second order needs the structure encoder (model.StrEnc.use: True)")
+        idx = q.device.index if q.device.index is not None else torch.cuda.current_device()
+        eng = self._so_engines.get(idx)
+        if eng is None:
+            eng = self._so_engines[idx] = SecondOrderEngine(self._act, self._beta, idx, hidden=self._hidden, enc_act=self._enc_act,
+                                                            enc_beta=self._enc_beta)
+        params = self._ordered_parameters()
+        if any(p.device != q.device or p.dtype != torch.float32 or not p.is_contiguous() for p in params):
+            raise PndfError("the second order reads the parameters in place: contiguous fp32 on the pose's device")
+        n = eng.workspace_floats(B)
+        stream = stream_handle(q.device)
+        ws = self._so_workspaces.get((idx, stream))      # one per stream: calls on one stream run in order, so they may share it
+        if ws is None or ws.numel() < n:
+            ws = self._so_workspaces[(idx, stream)] = torch.empty(n, device=q.device, dtype=torch.float32)
+        eng.second_order([p.data_ptr() for p in params], q.data_ptr(), v.data_ptr(), *ptr, B, ws.data_ptr() if n else None, ws.numel(), stream)
+        return outs
+
+    @torch.no_grad()
+    def hvp(self, pose, v, w_d=None, w_t=None):
+        """Distance, gradient and Hessian-vector product in one call (include/posendf_amd_second_order.h): for poses and
+        directions [B,21,4] and per-pose weights w_d (default 0), w_t (default 1) returns (d [B,1], grad [B,21,4] = d d / d pose,
+        t [B,1] = <v, grad>, out [B,21,4] = w_d grad + w_t H v) with H the Hessian of the distance in the pose, the weights of the
+        network held constant.  Exact fp32 on the HIP engine for cuda poses, the host twin for a `train.device: cpu` model."""
+        q = pose.to(device=self.device).reshape(-1, 21, 4)
+        d, g, t, out = self._second_order(q, v, w_d, w_t)
+        return d.view(-1, 1), g, t.view(-1, 1), out
+
     @torch.no_grad()
     def project(self, noisy_poses, steps=100, return_dist=True, *, step_size=1.0, renormalize=None, tol=0.0):
         """experiments/sample_poses.py:67-74 as ONE persistent kernel: `steps` times
