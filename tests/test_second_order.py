@@ -1,7 +1,8 @@
 """The second order of the distance on the host (include/posendf_amd_second_order.h): the host
 twin `pndf_second_order_cpu` against the vectors the real reference's double backward produced
 (tests/golden/make_golden_second_order.py), the relu family's H v against the closed form of the normalisation's curvature, the NULL
-outputs and B = 0, the refusals' codes, the companion header against its signature table, and the opt-in autograd path of `PoseNDF` on a
+outputs and B = 0, other betas / activation pairs / widths against the stock modules in fp64, the exact identities and the row
+isolation that need no oracle, the refusals' codes, the companion header against its signature table, and the opt-in autograd path of `PoseNDF` on a
 cpu model.  Runs without a GPU; tests/test_second_order_gpu.py holds the device to the same."""
 import ctypes
 import os
@@ -150,6 +151,43 @@ def test_zero_norm_column_is_finite(fixture, sd):
     for act in ("lrelu", "softplus"):
         outs = run_twin(cpu_engine(act, sd), q, v)
         assert all(np.isfinite(a).all() for a in outs), act
+
+
+def twin_of(net, sd):
+    """the host twin of a second_order_oracle.NETWORKS entry as `run(q, v, w_d, w_t)` -> [d, g, t, out]"""
+    act, beta, enc_act, enc_beta, hidden = net
+    eng = cpu_engine(act, sd, beta=beta, hidden=hidden, enc_act=enc_act, enc_beta=enc_beta)
+    return lambda q, v, w_d, w_t: run_twin(eng, q, v, w_d, w_t)
+
+
+@pytest.mark.parametrize("net", soo.NETWORKS, ids=soo.network_id)
+def test_host_twin_other_networks(net):
+    """betas (a factor of the result: sigma'' = beta s (1 - s)) on either side and both, activation pairs, one-unit, odd, 1024-wide
+    and 129 / 127-wide layers, at B = 129 under the gate against the stock modules in fp64, their fp32 run as the envelope"""
+    sd = soo.network_weights(net)
+    args = soo.batch_inputs(129, seed=33, kinks=soo.network_kinks(net, sd))
+    ref32, ref64 = soo.stock_reference(net, sd, args, "cpu")
+    soo.gate_all(f"host twin {soo.network_id(net)}", twin_of(net, sd)(*args), ref32, ref64)
+
+
+@pytest.mark.parametrize("net", soo.LAUNCH_SEQUENCES, ids=soo.network_id)
+def test_exact_identities(sd, net):
+    """v -> 2v, v -> -v, v = 0, w_t = 0 and power-of-two scalings of (w_d, w_t), to the bit at B = 300"""
+    soo.check_exact_identities(twin_of(net, sd), *soo.batch_inputs(300, seed=38))
+
+
+@pytest.mark.parametrize("net", soo.LAUNCH_SEQUENCES, ids=soo.network_id)
+def test_rows_are_independent(sd, net):
+    """NaN / Inf poses, a NaN direction, an infinite weight and clamped columns stay in their rows; for lrelu the clamped column of
+    `out` is w_d g: no curvature there"""
+    soo.check_rows_are_independent(twin_of(net, sd), *soo.batch_inputs(300, seed=38), clamped_column_is_w_d_g=net[0] == "lrelu")
+
+
+@pytest.mark.parametrize("act", ["lrelu", "relu"])
+def test_distance_zero_has_no_derivatives(sd, act):
+    """an output bias of -1e3 switches the output ReLU off: d, g, t and out are exactly zero at B = 129"""
+    sd = dict(sd, **{"dfnet.lin6.bias": np.full_like(sd["dfnet.lin6.bias"], -1e3)})
+    soo.check_distance_zero(twin_of((act, 100.0, None, None, None), sd), *soo.batch_inputs(129, seed=39))
 
 
 def test_refusals_return_their_codes(fixture, sd):

@@ -1,7 +1,9 @@
 """The second order of the distance on an MI355X (include/posendf_amd_second_order.h, csrc/pndf_second_order.hip):
 `pndf_second_order` against the reference's fp64 vectors and against the stock modules' double backward in fp64 on the same GPU,
-determinism and the NULL outputs, the clamp of the normalisation, and the opt-in autograd path of `PoseNDF`.  Reads only
-fixtures and synth (the reference is not here).
+determinism and the NULL outputs, the clamp of the normalisation, and the opt-in autograd path of `PoseNDF`; the betas, activation
+pairs and widths of second_order_oracle.NETWORKS, and the oracle-free properties (exact linearity in v and in the weights, rows that
+stay rows, a distance clamped to zero) that tests/test_second_order.py holds the host twin to.  Reads only fixtures and synth (the
+reference is not here).
 
 The gate, everywhere: max abs error over the batch / max abs of the fp64 output <= 4 x the same figure of the reference arithmetic's
 own fp32 run (second_order_oracle.gate).  A pose's results do not depend on the batch around it (every GEMM column and every
@@ -13,7 +15,6 @@ import pytest
 import torch
 
 import second_order_oracle as soo
-from oracle import posendf_np as onp
 from posendf_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -31,13 +32,9 @@ def sd():
     return soo.weights()
 
 
-def model(act, sd, hidden=None, enc_act=None, engine=None, device=DEV):
+def model(act, sd, hidden=None, enc_act=None, engine=None, device=DEV, beta=None, enc_beta=None):
     from posendf_amd import PoseNDF, amass_config
-    cfg = amass_config(act, device)
-    if hidden is not None:
-        cfg["model"]["DFNet"]["dims"] = list(hidden)
-    if enc_act is not None:
-        cfg["model"]["StrEnc"]["act"] = enc_act
+    cfg = soo.set_network(amass_config(act, device), hidden, enc_act, beta, enc_beta)
     if engine is not None:
         cfg["engine"] = dict(engine)
     net = PoseNDF(cfg)
@@ -47,36 +44,36 @@ def model(act, sd, hidden=None, enc_act=None, engine=None, device=DEV):
 
 
 def inputs(B, seed=31, kinks=None):
-    """B signed poses, normal directions and weights of both signs on the GPU.  `kinks` = (weights, "trunk/encoder" activations) of a
-    network with a relu-family part: only poses whose kink margin (oracle.posendf_np.kink_margin: the smallest |pre-activation|
-    relative to its layer's largest) is at least 1e-5 -- conftest.outlier_gate's kink_tol -- are taken.  Nearer to a kink two correct
-    fp32 evaluations may take different sides of it, and their derivatives then differ by O(1): such a pose measures no arithmetic."""
-    rs = np.random.RandomState(seed)
-    q = synth.make_poses(2 * B + 8, seed=seed, signed=True).astype(np.float32)
-    if kinks is not None:
-        q = q[onp.kink_margin(q, *kinks) >= 1e-5]
-    q = np.ascontiguousarray(q[:B])
-    assert len(q) == B
-    v = rs.normal(size=q.shape).astype(np.float32)
-    w_d = (rs.uniform(0.5, 1.5, B) * np.where(rs.rand(B) < 0.5, -1, 1)).astype(np.float32)
-    w_t = (rs.uniform(0.5, 1.5, B) * np.where(rs.rand(B) < 0.5, -1, 1)).astype(np.float32)
-    return tuple(torch.from_numpy(a).to(DEV) for a in (q, v, w_d, w_t))
+    """second_order_oracle.batch_inputs (B signed poses, normal directions, weights of both signs; `kinks`: its kink filter) on the GPU"""
+    return tuple(torch.from_numpy(a).to(DEV) for a in soo.batch_inputs(B, seed, kinks))
 
 
 def hvp_np(net, *args):
     return [a.cpu().numpy() for a in net.hvp(*args)]
 
 
-def stock_gate(tag, net, act, sd, args, hidden=None, enc_act=None):
+def stock_gate(tag, net, act, sd, args, hidden=None, enc_act=None, beta=None, enc_beta=None):
     """`net.hvp` against the stock modules' double backward: fp64 as the truth, their fp32 run as the envelope, on this GPU"""
     mine = hvp_np(net, *args)
-    m64 = soo.stock_model(act, sd, DEV, torch.float64, hidden, enc_act)
-    m32 = soo.stock_model(act, sd, DEV, torch.float32, hidden, enc_act)
+    m64 = soo.stock_model(act, sd, DEV, torch.float64, hidden, enc_act, beta, enc_beta)
+    m32 = soo.stock_model(act, sd, DEV, torch.float32, hidden, enc_act, beta, enc_beta)
     r64 = soo.stock_second_order(m64, *(a.double() for a in args))
     r32 = soo.stock_second_order(m32, *args)
     for name, a, b, c in zip(soo.OUTPUTS, mine, r32, r64):
         soo.gate(a, b.cpu().numpy(), c.cpu().numpy(), f"{tag} {name}")
     return mine
+
+
+def device_of(net, sd):
+    """`pndf_second_order` for a second_order_oracle.NETWORKS entry as `run(q, v, w_d, w_t)` -> [d, g, t, out] in numpy, through
+    PoseNDF._second_order on the GPU; and the model"""
+    act, beta, enc_act, enc_beta, hidden = net
+    m = model(act, sd, hidden, enc_act, beta=beta, enc_beta=enc_beta)
+
+    def run(q, v, w_d, w_t):
+        args = [None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for a in (q, v, w_d, w_t)]
+        return [a.cpu().numpy() for a in m._second_order(*args)]
+    return run, m
 
 
 @pytest.mark.parametrize("act", soo.ACTS)
@@ -231,3 +228,71 @@ def test_hvp_takes_any_layout_and_dtype(sd):
     for pose, vv in ((strided, v), (q.double(), v.double()), (q.cpu(), v.cpu())):
         got = net.hvp(pose, vv, w_d, w_t)
         assert all(torch.equal(a, b) for a, b in zip(got, want))
+
+
+@pytest.mark.parametrize("net", soo.NETWORKS, ids=soo.network_id)
+def test_networks_table(net):
+    """9. second_order_oracle.NETWORKS -- betas on either side and both (a factor of the result), activation pairs, a one-unit
+    hidden layer (M = 1 forward, K = 1 reverse), odd widths, 1024 x 1024 (eight row tiles, 64 K steps), 129 / 127 -- at B = 129
+    under the gate against the stock modules in fp64 on this GPU"""
+    act, beta, enc_act, enc_beta, hidden = net
+    sd = soo.network_weights(net)
+    args = inputs(129, seed=33, kinks=soo.network_kinks(net, sd))
+    m = model(act, sd, hidden, enc_act, beta=beta, enc_beta=enc_beta)
+    stock_gate(f"stock {soo.network_id(net)}", m, act, sd, args, hidden, enc_act, beta, enc_beta)
+
+
+@pytest.mark.parametrize("net", soo.LAUNCH_SEQUENCES, ids=soo.network_id)
+def test_exact_identities(sd, net):
+    """10. v -> 2v, v -> -v, v = 0, w_t = 0 and power-of-two scalings of (w_d, w_t), to the bit at B = 300: the kernels compute the
+    formula of their header comment, with nothing of the tangent in the primal chain"""
+    soo.check_exact_identities(device_of(net, sd)[0], *soo.batch_inputs(300, seed=38))
+
+
+@pytest.mark.parametrize("net", soo.LAUNCH_SEQUENCES, ids=soo.network_id)
+def test_rows_are_independent(sd, net):
+    """11. NaN / Inf poses, a NaN direction, an infinite weight and clamped columns (ordinary float inputs to arithmetic kernels;
+    nothing indexes with them) stay in their rows: the GEMM loads zero-fill outside the matrix, not inside it, so a NaN column stays a
+    column.  Rows 7, 130 and 257 sit in three 128-column tiles, 127 | 128 | 129 straddle a tile edge"""
+    soo.check_rows_are_independent(device_of(net, sd)[0], *soo.batch_inputs(300, seed=38), clamped_column_is_w_d_g=net[0] == "lrelu")
+
+
+@pytest.mark.parametrize("act", ["lrelu", "relu"])
+def test_distance_zero_has_no_derivatives(sd, act):
+    """12. an output bias of -1e3 switches the output ReLU off: d, g, t and out are exactly zero at B = 129"""
+    sd = dict(sd, **{"dfnet.lin6.bias": np.full_like(sd["dfnet.lin6.bias"], -1e3)})
+    soo.check_distance_zero(device_of((act, 100.0, None, None, None), sd)[0], *soo.batch_inputs(129, seed=39))
+
+
+@pytest.mark.parametrize("net", soo.LAUNCH_SEQUENCES[1:], ids=soo.network_id)
+def test_chunk_seam_other_launch_sequences(sd, net):
+    """13. the relu-family launch sequence, and `zero_a0` (the encoder kernel clears the primal adjoint of the features itself, no
+    trunk pass writes it), across a chunk seam at B = CHUNK + 129: the first 300 poses and the last 129 equal, bit for bit, separate
+    calls on those slices made afterwards on the same model -- whose per-stream workspace a smaller call then reuses.  No oracle."""
+    run, _ = device_of(net, sd)
+    args = soo.batch_inputs(CHUNK + 129, seed=32)
+    full = run(*args)
+    head = run(*(a[:300] for a in args))
+    last = run(*(a[CHUNK:] for a in args))
+    assert all(np.isfinite(a).all() for a in full)
+    for name, a, b, c in zip(soo.OUTPUTS, full, head, last):
+        assert a[:300].tobytes() == b.tobytes(), f"{name}: the chunk's head"
+        assert a[CHUNK:].tobytes() == c.tobytes(), f"{name}: behind the seam"
+
+
+@pytest.mark.parametrize("net", soo.TWIN_AND_DEVICE, ids=soo.network_id)
+def test_device_equals_host_twin_under_the_gate(net):
+    """14. the device and the host twin held to the same stock fp64 truth (this GPU's) with the same gate, side by side"""
+    from posendf_amd.engine import CpuEngine
+    act, beta, enc_act, enc_beta, hidden = net
+    sd = soo.network_weights(net)
+    args = soo.batch_inputs(129, seed=33, kinks=soo.network_kinks(net, sd))
+    ref32, ref64 = soo.stock_reference(net, sd, args, DEV)
+    dev = soo.gate_all(f"device {soo.network_id(net)}", device_of(net, sd)[0](*args), ref32, ref64)
+    eng = CpuEngine(act, beta, hidden=hidden, enc_act=enc_act, enc_beta=enc_beta)
+    eng.load_weights(sd)
+    twin = [np.empty(s, np.float32) for s in ((129,), (129, 21, 4), (129,), (129, 21, 4))]
+    eng.second_order(*(a.ctypes.data for a in (*args, *twin)), 129)
+    host = soo.gate_all(f"host twin {soo.network_id(net)}", twin, ref32, ref64)
+    for name in soo.OUTPUTS:
+        print(f"[second order] {soo.network_id(net)} {name}: device {dev[name]:.2f}  host twin {host[name]:.2f}  (err / stock fp32 err)")
