@@ -16,6 +16,9 @@ def __getattr__(name):   # torch is imported lazily so that numpy-only users (or
     if name in ("Trainer", "PoseDataset"):
         from . import trainer
         return getattr(trainer, name)
+    if name in ("OnlinePoseDataset", "OnlineOptions", "sample_noisy"):
+        from . import online
+        return getattr(online, name)
     if name == "PoseCompletion":
         from .pose_completion import PoseCompletion
         return PoseCompletion
@@ -31,5 +34,5 @@ def __getattr__(name):   # torch is imported lazily so that numpy-only users (or
     raise AttributeError(name)
 
 
-__all__ = ["PoseNDF", "gradient", "BodyModel", "PoseIndex", "Trainer", "PoseDataset", "ImageFit", "PerspectiveCamera", "keypoint_term", "PoseCompletion", "PoseInterpolation",
+__all__ = ["PoseNDF", "gradient", "BodyModel", "PoseIndex", "Trainer", "PoseDataset", "OnlinePoseDataset", "OnlineOptions", "sample_noisy", "ImageFit", "PerspectiveCamera", "keypoint_term", "PoseCompletion", "PoseInterpolation",
            "amass_config", "load_config", "synth"]

@@ -30,6 +30,7 @@
 #include "pndf_error.h"
 #include "pndf_interp.h"
 #include "pndf_layout.h"
+#include "pndf_online.h"
 #include "pndf_project_opts.h"
 
 using namespace pndf;
@@ -707,4 +708,50 @@ extern "C" int pndf_second_order_cpu(pndf_cpu_handle h, const float* q, const fl
                                   g ? g + p * NQ : nullptr, t ? t + p : nullptr, out ? out + p * NQ : nullptr, S);
         });
     });
+}
+
+// ------------------------------------------------------------------ online training data (include/posendf_amd_online.h)
+// The sampler's host side: the default options, the thresholds of a list of shares, and the host twin of pndf_online_sample --
+// pndf_online.h's expression, pose by pose on the calling thread (84 floats and 22 Philox blocks per pose: meant for small pools
+// and for holding the kernel to).  No handle: a refusal's text goes to the slot of pndf_cpu_last_error(NULL).
+namespace {
+
+int online_fail(int code, const std::string& msg) { return pndf_fail<pndf_cpu_engine>(nullptr, code, msg); }
+
+}  // namespace
+
+extern "C" int pndf_online_shares(pndf_online_opts* opt, const float* shares) {
+    if (!opt) return online_fail(PNDF_ERR_BAD_ARG, "pndf_online_shares: opt is null");
+    uint32_t cum[PNDF_ONLINE_MAX_SIGMA];
+    if (const char* why = pndf_online_thresholds(opt->n_sigma, shares, cum)) return online_fail(PNDF_ERR_BAD_ARG, std::string("pndf_online_shares: ") + why);
+    for (int g = 0; g < PNDF_ONLINE_MAX_SIGMA; ++g) opt->cum[g] = g < opt->n_sigma ? cum[g] : 0xffffffffu;
+    return PNDF_OK;
+}
+
+extern "C" int pndf_online_default_opts(pndf_online_opts* opt) {
+    if (!opt) return online_fail(PNDF_ERR_BAD_ARG, "pndf_online_default_opts: opt is null");
+    memset(opt, 0, sizeof(*opt));
+    const float sigma[5] = {0.01f, 0.05f, 0.1f, 0.25f, 0.5f}, shares[5] = {0.2f, 0.2f, 0.2f, 0.2f, 0.2f};      // create_data.py:51-52
+    opt->noise = PNDF_ONLINE_UNIFORM;
+    opt->n_sigma = 5;
+    for (int g = 0; g < 5; ++g) opt->sigma[g] = sigma[g];
+    return pndf_online_shares(opt, shares);
+}
+
+extern "C" int pndf_online_sample_cpu(const float* man_db, int64_t N, int64_t first, int64_t count, const pndf_online_opts* opt, float* q,
+                                      int64_t* src, int32_t* group) {
+    if (const char* why = pndf_online_check(man_db, N, first, count, opt, q, src, group, 4))
+        return online_fail(PNDF_ERR_BAD_ARG, std::string("pndf_online_sample_cpu: ") + why);
+    for (int64_t p = 0; p < count; ++p) {
+        const int64_t i = first + p;
+        int64_t row;
+        int32_t g;
+        float sigma;
+        pndf_online_pick(*opt, i, N, &row, &g, &sigma);
+        for (int j = 0; j < NJ; ++j)
+            pndf_online_quat(opt->seed, opt->draw, i, j, opt->noise, sigma, man_db + (row * NJ + j) * 4, q + (p * NJ + j) * 4);
+        if (src) src[p] = row;
+        if (group) group[p] = g;
+    }
+    return PNDF_OK;
 }

@@ -55,13 +55,20 @@ class KeypointOpts(ctypes.Structure):
                 ("use_conf", c_int32), ("reserved", c_int32)]
 
 
+class OnlineOpts(ctypes.Structure):
+    """pndf_online_opts: the stream (seed, draw), the noise mode and the sigma groups of the online sampler"""
+    _fields_ = [("seed", ctypes.c_uint64), ("draw", ctypes.c_uint32), ("noise", c_int32), ("n_sigma", c_int32),
+                ("sigma", c_float * 16), ("cum", ctypes.c_uint32 * 16)]
+
+
 class PndfError(RuntimeError):
     pass
 
 
 # ---- the C ABI, one table per header: name -> (restype, argtypes), in the header's order.  load_library() binds the tables, EXPORTS /
-# COMPLETION_EXPORTS / INTERPOLATION_EXPORTS / SECOND_ORDER_EXPORTS / DEBUG_EXPORTS are their names, tests/test_cabi.py,
-# tests/test_completion.py, tests/test_interpolation.py and tests/test_second_order.py hold them against the declarations of the headers.
+# COMPLETION_EXPORTS / INTERPOLATION_EXPORTS / SECOND_ORDER_EXPORTS / ONLINE_EXPORTS / DEBUG_EXPORTS are their names, tests/test_cabi.py,
+# tests/test_completion.py, tests/test_interpolation.py, tests/test_second_order.py and tests/test_online.py hold them against the
+# declarations of the headers.
 _H = c_void_p                          # every handle type, and every `void* stream`
 _P = c_void_p                          # any other address: tensor data (an int from data_ptr(), or None), a callback, an out value
 _TENSORS = [POINTER(c_void_p), POINTER(c_int64), c_int]      # tensors, numel, n_tensors (host pointers in state-dict order)
@@ -170,10 +177,17 @@ _SECOND_ORDER_SIGNATURES = {      # include/posendf_amd_second_order.h: Hessian-
     "pndf_second_order": (c_int, [_H] + [_P] * 9 + [c_int64, _P, c_int64, _H]),
     "pndf_second_order_cpu": (c_int, [_H] + [_P] * 8 + [c_int64]),
 }
+_ONLINE_SIGNATURES = {      # include/posendf_amd_online.h: the sampler of online training data, the fourth companion header
+    "pndf_online_default_opts": (c_int, [POINTER(OnlineOpts)]),
+    "pndf_online_shares": (c_int, [POINTER(OnlineOpts), POINTER(c_float)]),
+    "pndf_online_sample": (c_int, [_P, c_int64, c_int64, c_int64, POINTER(OnlineOpts), _P, _P, _P, _H]),
+    "pndf_online_sample_cpu": (c_int, [_P, c_int64, c_int64, c_int64, POINTER(OnlineOpts), _P, _P, _P]),
+}
 EXPORTS, DEBUG_EXPORTS = tuple(_SIGNATURES), tuple(_DEBUG_SIGNATURES)
 COMPLETION_EXPORTS = tuple(_COMPLETION_SIGNATURES)
 INTERPOLATION_EXPORTS = tuple(_INTERPOLATION_SIGNATURES)
 SECOND_ORDER_EXPORTS = tuple(_SECOND_ORDER_SIGNATURES)
+ONLINE_EXPORTS = tuple(_ONLINE_SIGNATURES)
 # per-translation-unit experiment words (csrc/pndf_experiment.h): data symbols, all zero in a product build
 EXPERIMENT_WORDS = ("pndf_experiment_word_capi", "pndf_experiment_word_fp32", "pndf_experiment_word_split", "pndf_experiment_word_split_x2",
                     "pndf_experiment_word_bf16", "pndf_experiment_word_lbs", "pndf_experiment_word_generic", "pndf_experiment_word_train",
@@ -228,7 +242,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         raise PndfError(f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                         "(hipcc --offload-arch=gfx950). The engine has no fallback path.")
     lib = _bind(_bind(_bind(_PndfLibrary(path), _SIGNATURES), _COMPLETION_SIGNATURES), _INTERPOLATION_SIGNATURES)
-    return _bind(lib, _SECOND_ORDER_SIGNATURES)
+    return _bind(_bind(lib, _SECOND_ORDER_SIGNATURES), _ONLINE_SIGNATURES)
 
 
 def experiment_word(lib=None) -> int:
@@ -610,6 +624,43 @@ def train_batch(pose_db_ptr, dist_db_ptr, man_db_ptr, file_off_ptr, man_off_ptr,
                                                   int(bool(flip)), q_ptr, gt_ptr, qm_ptr, stream)
     if rc != 0:
         raise PndfError(f"pndf_train_batch failed ({rc}): F = {F}, Fm = {Fm}, k = {k}, items = {items}, num_pts = {num_pts}")
+
+
+NOISE_CODES = {"uniform": 0, "symmetric": 1}               # PNDF_ONLINE_*
+
+
+def online_opts(sigmas, shares, noise="uniform", seed=0, draw=0, lib=None) -> OnlineOpts:
+    """pndf_online_opts of one pool: `sigmas` and `shares` of equal length 1 .. 16, thresholds by pndf_online_shares"""
+    lib = lib or load_library()
+    if noise not in NOISE_CODES:
+        raise PndfError(f"unknown noise {noise!r} ('uniform', 'symmetric')")
+    sigmas, shares = [float(s) for s in sigmas], [float(s) for s in shares]
+    if len(sigmas) != len(shares) or not 1 <= len(sigmas) <= 16:
+        raise PndfError(f"{len(sigmas)} sigmas and {len(shares)} shares: 1 .. 16 of each, one share per sigma")
+    opt = OnlineOpts()
+    opt.seed, opt.draw, opt.noise, opt.n_sigma = int(seed) & (2 ** 64 - 1), int(draw) & 0xffffffff, NOISE_CODES[noise], len(sigmas)
+    for g, s in enumerate(sigmas):
+        opt.sigma[g] = s
+    rc = lib.pndf_online_shares(ctypes.byref(opt), (c_float * len(shares))(*shares))
+    if rc != 0:
+        raise PndfError(f"pndf_online_shares failed ({rc}): {lib.pndf_cpu_last_error(None).decode()}")
+    return opt
+
+
+def online_sample(man_ptr, N, first, count, opt, q_ptr, src_ptr=None, group_ptr=None, stream=0, lib=None):
+    """`pndf_online_sample` (csrc/pndf_online.hip): poses first .. first + count - 1 of the pool of `opt` over the device manifold"""
+    lib = lib or load_library()
+    rc = lib.pndf_online_sample(man_ptr, int(N), int(first), int(count), ctypes.byref(opt), q_ptr, src_ptr, group_ptr, stream)
+    if rc != 0:
+        raise PndfError(f"pndf_online_sample failed ({rc}): {lib.pndf_last_error(None).decode()}")
+
+
+def online_sample_cpu(man_ptr, N, first, count, opt, q_ptr, src_ptr=None, group_ptr=None, lib=None):
+    """`pndf_online_sample_cpu` (csrc/pndf_cpu.cpp): the host twin of online_sample, HOST pointers"""
+    lib = lib or load_library()
+    rc = lib.pndf_online_sample_cpu(man_ptr, int(N), int(first), int(count), ctypes.byref(opt), q_ptr, src_ptr, group_ptr)
+    if rc != 0:
+        raise PndfError(f"pndf_online_sample_cpu failed ({rc}): {lib.pndf_cpu_last_error(None).decode()}")
 
 
 def aa2quat(theta_ptr, q_ptr, N, stream=0, lib=None):

@@ -33,7 +33,9 @@ Differences from the reference, on purpose:
   * the checkpoint's `epoch` is the epoch just trained, as in the reference, but a resume continues with the NEXT epoch; the
     reference's loop (trainer.py:21) trains the stored epoch a second time;
   * scalars go to <exp>/summary.jsonl (one JSON line per epoch), not to TensorBoard;
-  * the data set is resident in memory (device memory on cuda): one that does not fit is refused with the byte count.
+  * the data set is resident in memory (device memory on cuda): one that does not fit is refused with the byte count;
+  * `data.online` (posendf_amd.online) replaces the frozen sample files by a pool that is redrawn and relabelled on the device
+    every `refresh_every` epochs; without it every code path is the file-based one.
 """
 from __future__ import annotations
 
@@ -176,7 +178,13 @@ class Trainer:
     """`PoseNDF_trainer(opt)` (train_posendf.py:15-176).  Reads train.{device, batch_size, optimizer_param, continue_train,
     max_epoch, loss_type, man_loss, dist, eikonal}, data.{data_dir, amass_dir, flip (False), num_pts (5000)} and
     experiment.{root_dir, exp_name}; `seed` feeds the initial weights and, with the epoch, every draw of the sampler.
-    `dataset`: a PoseDataset to train on instead of the directories of `opt['data']`."""
+    `dataset`: a PoseDataset to train on instead of the directories of `opt['data']`.
+
+    Online data (posendf_amd.online): with the mapping `data.online` = {files, rows, refresh_every (epochs, default 1), sigmas,
+    shares, noise, k, metric, weighted} -- or an `OnlinePoseDataset` passed as `dataset` -- the noisy poses are a pool of files x
+    rows poses drawn from `data.amass_dir` and labelled on the device; `data.data_dir` is not read.  `begin_epoch(epoch)` makes
+    pool `epoch // refresh_every` of the trainer's seed resident when it is not; the pool is a pure function of (seed, draw,
+    manifold, options), so a resume regenerates it and continues bit for bit.  The experiment name gains the prefix `online_`."""
 
     def __init__(self, opt, seed=0, dataset=None):
         tr, data = opt["train"], opt.get("data") or {}
@@ -198,6 +206,13 @@ class Trainer:
         # train_posendf.py:58-62
         name = "{}_{}_{}_{}_dist{}_eik{}".format(opt["experiment"]["exp_name"], opt["model"]["DFNet"]["act"], self.loss,
                                                  tr["optimizer_param"], tr["dist"], tr["eikonal"])
+        online = data.get("online")
+        self.online = online is not None or hasattr(dataset, "refresh")
+        self.refresh_every = int((online or {}).get("refresh_every", 1))
+        if self.refresh_every < 1:
+            raise ValueError(f"data.online.refresh_every = {self.refresh_every}: a pool lasts one epoch or more")
+        if self.online:
+            name = "online_{}".format(name)      # the two data sources keep their checkpoints apart
         self.exp_name = "flip_{}".format(name) if self.flip else name
         self.exp_path = "{}/{}/".format(opt["experiment"]["root_dir"], self.exp_name)
         self.checkpoint_path = self.exp_path + "checkpoints/"
@@ -209,6 +224,8 @@ class Trainer:
         self.hip = self.device.type == "cuda"
         if self.hip and self.model.enc is None:
             raise PndfError("training on cuda needs the structure encoder (model.StrEnc.use: True), as opt['engine']['train'] = 'hip'")
+        if dataset is None and online is not None:
+            dataset = self._online_dataset(data, online)
         self.dataset = dataset if dataset is not None else PoseDataset(data["data_dir"], data["amass_dir"], data.get("datasets"),
                                                                         self.device)
         if self.dataset.device != self.device:
@@ -270,6 +287,29 @@ class Trainer:
         self._item_man = torch.zeros(self.items, dtype=torch.int32, device=dev)
         self._words = torch.zeros(self.items, 2, self.num_pts, dtype=torch.int32, device=dev)      # uint32 bit patterns
 
+    def _online_dataset(self, data, online):
+        """the OnlinePoseDataset of `data.online` over `data.amass_dir`"""
+        from .online import OnlineOptions, OnlinePoseDataset
+        known = {"files", "rows", "refresh_every", "sigmas", "shares", "noise", "k", "metric", "weighted", "chunk"}
+        if set(online) - known:
+            raise ValueError(f"data.online: unknown keys {sorted(set(online) - known)} (known: {sorted(known)})")
+        if "files" not in online or "rows" not in online:
+            raise ValueError("data.online needs `files` and `rows`: the pool is files x rows noisy poses")
+        kw = {k: online[k] for k in ("noise", "k", "metric", "weighted") if k in online}
+        for k in ("sigmas", "shares"):
+            if k in online:
+                kw[k] = tuple(float(x) for x in online[k])
+        extra = {"chunk": int(online["chunk"])} if "chunk" in online else {}
+        return OnlinePoseDataset(data["amass_dir"], int(online["files"]), int(online["rows"]), OnlineOptions(**kw), data.get("datasets"),
+                                 self.device, **extra)
+
+    def _ensure_pool(self, epoch):
+        """online data: the pool of `epoch` resident (a no-op when it is, and for a file-based data set)"""
+        if self.online:
+            draw = int(epoch) // self.refresh_every
+            if self.dataset.draw != draw or self.dataset.seed != self.seed:
+                self.dataset.refresh(draw, self.seed)
+
     def _check_homes(self):
         """the parameters must still be the views the kernels update"""
         for k, p, ptr in zip(self._keys, self._params, self._ptrs):
@@ -310,6 +350,7 @@ class Trainer:
     def begin_epoch(self, epoch):
         """draws the epoch on the host and (cuda) uploads it: the only host-to-device copy of the epoch"""
         perm, man, words = self._epoch_draws(epoch)
+        self._ensure_pool(epoch)
         if self.hip:
             self._item_file.copy_(torch.from_numpy(perm))
             self._item_man.copy_(torch.from_numpy(man))
@@ -327,6 +368,7 @@ class Trainer:
         epoch, i = self._cursor
         if i >= self.steps_per_epoch:
             raise IndexError(f"epoch {epoch} has {self.steps_per_epoch} steps: begin_epoch() starts the next one")
+        self._ensure_pool(epoch)      # (online data: batch() of another epoch may have swapped the pool since begin_epoch)
         if self.hip:
             self._step_hip(i)
         else:
@@ -353,6 +395,7 @@ class Trainer:
     def batch(self, epoch, step):
         """the batch of (epoch, step) with torch indexing, on the trainer's device: (pose [B,21,4], dist_gt [B], man [B,21,4])"""
         rows, man_rows = self.batch_rows(epoch, step)
+        self._ensure_pool(epoch)
         ds = self.dataset
         rows, man_rows = torch.from_numpy(rows).to(self.device), torch.from_numpy(man_rows).to(self.device)
         pose, man = ds.pose[rows], ds.man[man_rows]
