@@ -1,0 +1,242 @@
+// The structure encoder and the network plan of the layer-by-layer units (csrc/pndf_train.hip, csrc/pndf_second_order.hip), on top
+// of pndf_gemm.h.  Device side: one bone MLP as a dual number (its input gather, its forward with the tangent, its reverse with
+// the primal and the tangent adjoint: DESIGN.md section 2s, "The dual-number bone"), the pieces of normalize(q, dim=1), the table
+// of the encoder's 84 tensors.  Host side: LayerNet, what both units know about the network, and what they ask of its tensors.
+// Each unit keeps what is its own: training the LDS reduction of the weight gradient, the second order the curvature of the
+// normalisation.  Everything is in an unnamed namespace, instantiated per translation unit as in pndf_gemm.h.
+#pragma once
+#include "pndf_gemm.h"
+
+namespace {
+
+constexpr int NJ = 21, FEAT = 6, HID = 10, BONE = 4;
+constexpr int ENC_IN = NJ * FEAT;          // 126: the encoder's output, the trunk's input
+constexpr int POSE = NJ * BONE;            // 84
+constexpr int MAX_LIN = 8;                 // 1 .. 7 hidden layers -> 2 .. 8 linear layers
+constexpr int ENC_TENSORS = 4 * NJ;        // 84
+constexpr float NORM_EPS = 1e-12f;         // F.normalize
+
+// ---- encoder: 21 bone MLPs (4 | 10 -> 10 -> 6), the weights packed in state-dict order into one flat array
+template <int FIN>
+__device__ __forceinline__ void bone_lin0(const float* w, const float* in, float* zh, bool bias) {
+#pragma unroll
+    for (int i = 0; i < HID; ++i) {
+        float s = bias ? w[HID * FIN + i] : 0.f;
+#pragma unroll
+        for (int k = 0; k < FIN; ++k) s = fmaf(w[i * FIN + k], in[k], s);
+        zh[i] = s;
+    }
+}
+template <int FIN>
+__device__ __forceinline__ const float* bone_w2(const float* w) { return w + HID * FIN + HID; }
+
+// bone j's input on column `col`: its own four rows of x (row stride ldx) and its parent's six feature rows of f (row stride ldf)
+template <int FIN>
+__device__ __forceinline__ void bone_load(const float* x, int64_t ldx, const float* f, int64_t ldf, const int* parent, int j,
+                                          int64_t col, float* out) {
+#pragma unroll
+    for (int k = 0; k < BONE; ++k) out[k] = x[(int64_t)(j * BONE + k) * ldx + col];
+    if (FIN > BONE) {
+        const int p = parent[j];
+#pragma unroll
+        for (int i = 0; i < FIN - BONE; ++i) out[BONE + i] = f[(int64_t)(p * FEAT + i) * ldf + col];
+    }
+}
+
+// One bone at one pose as a dual number: the primal's activations with sigma' and sigma'' of both layers, and along the tangent
+// of the input the pre-activations hz (hidden) and oz (output) and the hidden tangent ahd = sigma'h hz.  The tangent of the bone's
+// output is oz sigma'o.
+struct BoneDual {
+    float ah[HID], d1h[HID], d2h[HID], ao[FEAT], d1o[FEAT], d2o[FEAT];
+    float hz[HID], ahd[HID], oz[FEAT];
+};
+
+// The dual forward of one bone in its two steps, so that a caller can store the primal's output before it gathers the tangent's
+// input.  The primal from `in` (E: the kernel's argument struct, for its act and beta) ...
+template <int FIN, class E>
+__device__ __forceinline__ void bone_fwd(const E& e, const float* w, const float* in, BoneDual& b) {
+    float zh[HID];
+    bone_lin0<FIN>(w, in, zh, true);
+#pragma unroll
+    for (int i = 0; i < HID; ++i) act_eval(e.act, e.beta, false, zh[i], b.ah[i], b.d1h[i], b.d2h[i]);
+    const float* w2 = bone_w2<FIN>(w);
+#pragma unroll
+    for (int i = 0; i < FEAT; ++i) {
+        float s = w2[FEAT * HID + i];
+#pragma unroll
+        for (int k = 0; k < HID; ++k) s = fmaf(w2[i * HID + k], b.ah[k], s);
+        act_eval(e.act, e.beta, false, s, b.ao[i], b.d1o[i], b.d2o[i]);
+    }
+}
+// ... then, with `tangent`, the tangent along `ind`; without it +0 and no product formed
+template <int FIN>
+__device__ __forceinline__ void bone_tan(const float* w, const float* ind, bool tangent, BoneDual& b) {
+#pragma unroll
+    for (int k = 0; k < HID; ++k) b.hz[k] = b.ahd[k] = 0.f;
+#pragma unroll
+    for (int i = 0; i < FEAT; ++i) b.oz[i] = 0.f;
+    if (!tangent) return;
+    const float* w2 = bone_w2<FIN>(w);
+    bone_lin0<FIN>(w, ind, b.hz, false);
+#pragma unroll
+    for (int k = 0; k < HID; ++k) b.ahd[k] = b.d1h[k] * b.hz[k];
+#pragma unroll
+    for (int i = 0; i < FEAT; ++i) {
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < HID; ++k) s = fmaf(w2[i * HID + k], b.ahd[k], s);
+        b.oz[i] = s;
+    }
+}
+
+// the adjoints of one bone's pre-activations, output (zo) and hidden (zh), primal (..b) and tangent (..db)
+struct BoneAdj {
+    float zob[FEAT], zodb[FEAT], zhb[HID], zhdb[HID];
+};
+
+// Dual reverse of one bone ("The dual-number bone") from the adjoints ab (primal) and adb (tangent) of its
+// six outputs.  Without PRIMAL the ab chain is compiled out (ab is not read, zob and zhb stay unwritten): what is left is the
+// first-order reverse, the chain a network without a second derivative needs.
+// The rounding of the two sums is pinned (one fma, the other product rounded first), no longer left to -ffp-contract: zhb takes
+// the cross term's last product into the fma.  For zob the two units' own copies had been compiled differently, the second order
+// like zhb in all six outputs, training in the last output only (the other five fuse ab sigma'o instead).  Bit i of FUSE_CROSS
+// keeps that choice for output i, so that both units compute the bits they did; one mask for both would move training's.
+template <int FIN, bool PRIMAL, unsigned FUSE_CROSS = 0x3f>
+__device__ __forceinline__ void bone_dual_rev(const float* w, const BoneDual& b, const float* ab, const float* adb, BoneAdj& r) {
+#pragma clang fp contract(off)
+    const float* w2 = bone_w2<FIN>(w);
+#pragma unroll
+    for (int i = 0; i < FEAT; ++i) {
+        const float cross = adb[i] * b.oz[i];
+        if (PRIMAL) r.zob[i] = (FUSE_CROSS >> i & 1) ? fmaf(cross, b.d2o[i], ab[i] * b.d1o[i]) : fmaf(ab[i], b.d1o[i], cross * b.d2o[i]);
+        r.zodb[i] = adb[i] * b.d1o[i];
+    }
+#pragma unroll
+    for (int k = 0; k < HID; ++k) {
+        float s = 0.f, sd = 0.f;
+#pragma unroll
+        for (int i = 0; i < FEAT; ++i) {
+            if (PRIMAL) s = fmaf(w2[i * HID + k], r.zob[i], s);
+            sd = fmaf(w2[i * HID + k], r.zodb[i], sd);
+        }
+        if (PRIMAL) r.zhb[k] = fmaf(sd * b.hz[k], b.d2h[k], s * b.d1h[k]);
+        r.zhdb[k] = sd * b.d1h[k];
+    }
+}
+// ... and the adjoints of input m, s the primal's and sd the tangent's: the caller's loop, which stores each pair as it comes
+template <int FIN, bool PRIMAL>
+__device__ __forceinline__ void bone_input_adj(const float* w, const BoneAdj& r, int m, float& s, float& sd) {
+    s = 0.f;
+    sd = 0.f;
+#pragma unroll
+    for (int k = 0; k < HID; ++k) {
+        if (PRIMAL) s = fmaf(w[k * FIN + m], r.zhb[k], s);
+        sd = fmaf(w[k * FIN + m], r.zhdb[k], sd);
+    }
+}
+
+// ---- x = normalize(q, dim=1): over the joint axis, per quaternion component k (a column of 21 joints)
+// the norms of a pose's four columns
+__device__ __forceinline__ void pose_col_norms(const float* q, float* nrm) {
+    float n2[BONE] = {0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int k = 0; k < BONE; ++k) n2[k] = fmaf(q[j * BONE + k], q[j * BONE + k], n2[k]);
+#pragma unroll
+    for (int k = 0; k < BONE; ++k) nrm[k] = sqrtf(n2[k]);
+}
+__device__ __forceinline__ float norm_x(float q, float nrm) { return q / fmaxf(nrm, NORM_EPS); }
+// J_N v = (v - x (x . v)) / |q_k| with a = x . v over the column; v / eps where the norm is clamped.  `live` is the caller's:
+// training tests nrm >= NORM_EPS, the second order nrm > NORM_EPS.  They part at nrm == eps exactly, where one comparison for
+// both would change the bits of one of them.
+__device__ __forceinline__ float norm_jvp(float v, float x, float a, float nrm, bool live) {
+    return live ? (v - x * a) / nrm : v / NORM_EPS;
+}
+
+// ---- the caller's 84 encoder tensors and their offsets in the flat array
+struct PtrTable {
+    float* p[ENC_TENSORS];
+    int off[ENC_TENSORS + 1];
+};
+
+__device__ __forceinline__ void enc_pack_body(const PtrTable& t, float* dst) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= t.off[ENC_TENSORS]) return;
+    int k = 0;
+    while (t.off[k + 1] <= i) ++k;
+    dst[i] = t.p[k][i - t.off[k]];
+}
+
+// ------------------------------------------------------------------------------------------------------------ host side
+// The networks the layer-by-layer translation units run: relu / lrelu / softplus, 21 joints, the structure encoder, one to seven
+// hidden layers up to 1024 wide, every parent before its child.  Null, or why `cfg` is PNDF_ERR_UNSUPPORTED; `no_encoder`: the
+// caller's text for a network without the encoder.
+inline const char* layer_network_refusal(const pndf_config* cfg, const char* no_encoder) {
+    if (cfg->act < PNDF_ACT_RELU || cfg->act > PNDF_ACT_SOFTPLUS) return "activation: relu, lrelu or softplus";
+    if (cfg->enc_act > PNDF_ACT_SOFTPLUS) return "encoder activation: relu, lrelu or softplus";
+    if (cfg->num_joints != NJ) return "num_joints must be 21";
+    if (cfg->dims[0] != ENC_IN) return no_encoder;
+    if (cfg->n_dims < 3 || cfg->n_dims > MAX_LIN + 1 || cfg->dims[cfg->n_dims - 1] != 1) return "DFNet: 1 .. 7 hidden layers and one output";
+    for (int i = 1; i < cfg->n_dims - 1; ++i)
+        if (cfg->dims[i] < 1 || cfg->dims[i] > 1024) return "hidden widths 1 .. 1024";
+    for (int j = 0; j < NJ; ++j)
+        if (cfg->parent[j] >= j || cfg->parent[j] < -1) return "parent table: every parent before its child";
+    return nullptr;
+}
+
+// what a unit's handle knows about the network (a `cfg` that layer_network_refusal passed)
+struct LayerNet {
+    int device = 0;
+    int L = 0;                    // linear layers of the trunk
+    int dims[MAX_LIN + 1] = {};   // dims[0] = 126 ... dims[L] = 1
+    int act = 0, enc_act = 0;
+    float beta = 100.f, enc_beta = 100.f;
+    int parent[NJ] = {};
+    int enc_off[NJ] = {};         // offset of bone j in the packed encoder
+    int enc_tensor_off[ENC_TENSORS + 1] = {};
+    int enc_params = 0;
+    int maxw = 0;
+};
+
+inline void layer_net_init(LayerNet& n, const pndf_config* cfg, int device) {
+    n.device = device;
+    n.L = cfg->n_dims - 1;
+    for (int t = 0; t <= n.L; ++t) {
+        n.dims[t] = cfg->dims[t];
+        if (cfg->dims[t] > n.maxw) n.maxw = cfg->dims[t];
+    }
+    n.act = cfg->act;
+    n.beta = cfg->beta;
+    n.enc_act = cfg->enc_act >= 0 ? cfg->enc_act : cfg->act;
+    n.enc_beta = cfg->enc_beta > 0.f ? cfg->enc_beta : cfg->beta;
+    int o = 0, k = 0;
+    for (int j = 0; j < NJ; ++j) {
+        n.parent[j] = cfg->parent[j];
+        n.enc_off[j] = o;
+        const int fin = cfg->parent[j] < 0 ? BONE : BONE + FEAT;
+        const int sizes[4] = {HID * fin, HID, FEAT * HID, FEAT};
+        for (int s = 0; s < 4; ++s) {
+            n.enc_tensor_off[k++] = o;
+            o += sizes[s];
+        }
+    }
+    n.enc_tensor_off[ENC_TENSORS] = o;
+    n.enc_params = o;
+}
+
+// the encoder's 84 tensors among the caller's `tensors` (weights, or gradients to write)
+inline PtrTable ptr_table(const LayerNet& n, const float* const* tensors) {
+    PtrTable t;
+    for (int k = 0; k < ENC_TENSORS; ++k) t.p[k] = const_cast<float*>(tensors[k]);
+    for (int k = 0; k <= ENC_TENSORS; ++k) t.off[k] = n.enc_tensor_off[k];
+    return t;
+}
+
+// the first of the network's 84 + 2L tensors that is null in `a` (or in `b`, when given); -1: none
+inline int null_tensor(const LayerNet& n, const float* const* a, const float* const* b = nullptr) {
+    for (int i = 0; i < ENC_TENSORS + 2 * n.L; ++i)
+        if (!a[i] || (b && !b[i])) return i;
+    return -1;
+}
+
+}  // namespace

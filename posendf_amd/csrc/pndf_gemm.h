@@ -1,7 +1,7 @@
-// The layer-by-layer fp32 pieces shared by csrc/pndf_train.hip (the training objective) and csrc/pndf_second_order.hip (Hessian-
-// vector products of the distance): the 128 x 128 fp32 MFMA GEMM with its epilogues, the activation with its two derivatives, one
-// bone MLP of the structure encoder, the table of the encoder's 84 tensors.  Device code in an unnamed namespace: every
-// translation unit that includes this header instantiates its own kernels from it under its own extern "C" names.
+// The 128 x 128 fp32 MFMA GEMM with its epilogues and the activation with its two derivatives, shared by the layer-by-layer
+// units csrc/pndf_train.hip (the training objective) and csrc/pndf_second_order.hip (Hessian-vector products of the distance).
+// The structure encoder and the network plan of those units are in pndf_bone.h, which includes this header.  Device code in an
+// unnamed namespace: every translation unit that includes it instantiates its own kernels from it under its own extern "C" names.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,12 +12,6 @@
 
 namespace {
 
-constexpr int NJ = 21, FEAT = 6, HID = 10, BONE = 4;
-constexpr int ENC_IN = NJ * FEAT;          // 126: the encoder's output, the trunk's input
-constexpr int POSE = NJ * BONE;            // 84
-constexpr int MAX_LIN = 8;                 // 1 .. 7 hidden layers -> 2 .. 8 linear layers
-constexpr int ENC_TENSORS = 4 * NJ;        // 84
-constexpr float NORM_EPS = 1e-12f;         // F.normalize
 constexpr float LRELU_SLOPE = 0.01f;       // nn.LeakyReLU()
 constexpr float SP_THRESHOLD = 20.f;       // nn.Softplus(threshold=20)
 
@@ -156,52 +150,6 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g) {
             }
 }
 
-// ---- encoder: 21 bone MLPs (4 | 10 -> 10 -> 6), the weights packed in state-dict order into one flat array
-template <int FIN>
-__device__ __forceinline__ void bone_lin0(const float* w, const float* in, float* zh, bool bias) {
-#pragma unroll
-    for (int i = 0; i < HID; ++i) {
-        float s = bias ? w[HID * FIN + i] : 0.f;
-#pragma unroll
-        for (int k = 0; k < FIN; ++k) s = fmaf(w[i * FIN + k], in[k], s);
-        zh[i] = s;
-    }
-}
-template <int FIN>
-__device__ __forceinline__ const float* bone_w2(const float* w) { return w + HID * FIN + HID; }
-
-// one bone's primal forward: activations and derivatives of both layers (E: the kernel's argument struct, for its act and beta)
-template <int FIN, class E>
-__device__ __forceinline__ void bone_fwd(const E& e, const float* w, const float* in, float* ah, float* d1h, float* d2h,
-                                         float* ao, float* d1o, float* d2o) {
-    float zh[HID];
-    bone_lin0<FIN>(w, in, zh, true);
-#pragma unroll
-    for (int i = 0; i < HID; ++i) act_eval(e.act, e.beta, false, zh[i], ah[i], d1h[i], d2h[i]);
-    const float* w2 = bone_w2<FIN>(w);
-#pragma unroll
-    for (int i = 0; i < FEAT; ++i) {
-        float s = w2[FEAT * HID + i];
-#pragma unroll
-        for (int k = 0; k < HID; ++k) s = fmaf(w2[i * HID + k], ah[k], s);
-        act_eval(e.act, e.beta, false, s, ao[i], d1o[i], d2o[i]);
-    }
-}
-
-// the caller's 84 encoder tensors and their offsets in the flat array
-struct PtrTable {
-    float* p[ENC_TENSORS];
-    int off[ENC_TENSORS + 1];
-};
-
-__device__ __forceinline__ void enc_pack_body(const PtrTable& t, float* dst) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= t.off[ENC_TENSORS]) return;
-    int k = 0;
-    while (t.off[k + 1] <= i) ++k;
-    dst[i] = t.p[k][i - t.off[k]];
-}
-
 inline GemmArgs gemm_args(const float* A, int64_t lda, const float* Bp, int64_t ldb, float* C, int64_t ldc, int M, int N, int K) {
     GemmArgs g;
     memset(&g, 0, sizeof(g));
@@ -209,22 +157,6 @@ inline GemmArgs gemm_args(const float* A, int64_t lda, const float* Bp, int64_t 
     g.M = M; g.N = N; g.K = K; g.kc = K;
     g.np_split = INT64_MAX;
     return g;
-}
-
-// The networks the layer-by-layer translation units run: relu / lrelu / softplus, 21 joints, the structure encoder, one to seven
-// hidden layers up to 1024 wide, every parent before its child.  Null, or why `cfg` is PNDF_ERR_UNSUPPORTED; `no_encoder`: the
-// caller's text for a network without the encoder.
-inline const char* layer_network_refusal(const pndf_config* cfg, const char* no_encoder) {
-    if (cfg->act < PNDF_ACT_RELU || cfg->act > PNDF_ACT_SOFTPLUS) return "activation: relu, lrelu or softplus";
-    if (cfg->enc_act > PNDF_ACT_SOFTPLUS) return "encoder activation: relu, lrelu or softplus";
-    if (cfg->num_joints != NJ) return "num_joints must be 21";
-    if (cfg->dims[0] != ENC_IN) return no_encoder;
-    if (cfg->n_dims < 3 || cfg->n_dims > MAX_LIN + 1 || cfg->dims[cfg->n_dims - 1] != 1) return "DFNet: 1 .. 7 hidden layers and one output";
-    for (int i = 1; i < cfg->n_dims - 1; ++i)
-        if (cfg->dims[i] < 1 || cfg->dims[i] > 1024) return "hidden widths 1 .. 1024";
-    for (int j = 0; j < NJ; ++j)
-        if (cfg->parent[j] >= j || cfg->parent[j] < -1) return "parent table: every parent before its child";
-    return nullptr;
 }
 
 inline int64_t align64(int64_t x) { return (x + 63) / 64 * 64; }

@@ -6,7 +6,10 @@
 // With x = normalize(q, dim=1) and f the encoder plus trunk:  g = J_N g_x,  xdot = J_N v,  H v = J_N (hess f xdot) + C(q, v, g_x),
 // C the curvature of the normalisation.  hess f xdot comes from the dual-number network csrc/pndf_train.hip differentiates the
 // eikonal term through, seeded with dbar = 0, ddotbar = 1: the adjoint chain of the tangent is the first-order reverse (it gives
-// g_x), the adjoint chain of the primal carries  zbar = abar sigma' + adotbar zdot sigma''.
+// g_x), the adjoint chain of the primal carries the sigma'' cross terms ("The dual-number bone").
+// Shared with pndf_train.hip: the GEMM with its epilogues and the activation (pndf_gemm.h); the dual-number bone, the pieces of
+// the normalisation and the host's description of the network, LayerNet (pndf_bone.h).  Here: the two encoder kernels around
+// the bone, the curvature of the normalisation with the four outputs, the chunked launch sequence.
 //
 // Layer by layer over a chunk of SO_CHUNK poses, every activation matrix [features][columns] (the pose index contiguous) in the
 // caller's workspace; the chunk is a function of B only and bounds the workspace (0.53 GB for configs/amass.yaml with softplus):
@@ -29,7 +32,7 @@
 
 #include "../../include/posendf_amd_second_order.h"
 #include "pndf_experiment.h"
-#include "pndf_gemm.h"
+#include "pndf_bone.h"
 #include "pndf_host.h"
 
 PNDF_EXPORT_EXPERIMENT_WORD(second_order)
@@ -71,103 +74,55 @@ struct SoArgs {
 // bone j's input on column c: its own normalised quaternion and its parent's feature; `tan`: the tangents of both
 template <int FIN>
 __device__ __forceinline__ void so_load_in(const SoArgs& e, int j, int64_t c, bool tan, float* in) {
-    const float* x = tan ? e.Xd : e.X;
-    const float* f = tan ? e.tan0 : e.act0;
-#pragma unroll
-    for (int k = 0; k < BONE; ++k) in[k] = x[(int64_t)(j * BONE + k) * e.ld + c];
-    if (FIN > BONE) {
-        const int p = e.parent[j];
-#pragma unroll
-        for (int i = 0; i < FIN - BONE; ++i) in[BONE + i] = f[(int64_t)(p * FEAT + i) * e.ld + c];
-    }
-}
-
-// the tangent pre-activations of one bone along `ind`: hidden (hz), the hidden tangent (ahd = sigma' hz), output (oz)
-template <int FIN>
-__device__ __forceinline__ void so_bone_tan(const float* w, const float* ind, const float* d1h, float* hz, float* ahd, float* oz) {
-    const float* w2 = bone_w2<FIN>(w);
-    bone_lin0<FIN>(w, ind, hz, false);
-#pragma unroll
-    for (int k = 0; k < HID; ++k) ahd[k] = d1h[k] * hz[k];
-#pragma unroll
-    for (int i = 0; i < FEAT; ++i) {
-        float s = 0.f;
-#pragma unroll
-        for (int k = 0; k < HID; ++k) s = fmaf(w2[i * HID + k], ahd[k], s);
-        oz[i] = s;
-    }
+    bone_load<FIN>(tan ? e.Xd : e.X, e.ld, tan ? e.tan0 : e.act0, e.ld, e.parent, j, c, in);
 }
 
 // primal and (dual) tangent forward of one bone
 template <int FIN>
 __device__ __forceinline__ void so_fwd_bone(const SoArgs& e, int j, int64_t c) {
     const float* w = e.wenc + e.off[j];
-    float in[FIN], ah[HID], d1h[HID], d2h[HID], ao[FEAT], d1o[FEAT], d2o[FEAT];
+    float in[FIN], ind[FIN];
+    BoneDual b;
     so_load_in<FIN>(e, j, c, false, in);
-    bone_fwd<FIN>(e, w, in, ah, d1h, d2h, ao, d1o, d2o);
+    bone_fwd<FIN>(e, w, in, b);
 #pragma unroll
-    for (int i = 0; i < FEAT; ++i) e.act0[(int64_t)(j * FEAT + i) * e.ld + c] = ao[i];
+    for (int i = 0; i < FEAT; ++i) e.act0[(int64_t)(j * FEAT + i) * e.ld + c] = b.ao[i];
     if (!e.dual) return;
-    float ind[FIN], hz[HID], ahd[HID], oz[FEAT];
     so_load_in<FIN>(e, j, c, true, ind);
-    so_bone_tan<FIN>(w, ind, d1h, hz, ahd, oz);
+    bone_tan<FIN>(w, ind, true, b);
 #pragma unroll
-    for (int i = 0; i < FEAT; ++i) e.tan0[(int64_t)(j * FEAT + i) * e.ld + c] = oz[i] * d1o[i];
+    for (int i = 0; i < FEAT; ++i) e.tan0[(int64_t)(j * FEAT + i) * e.ld + c] = b.oz[i] * b.d1o[i];
 }
 
 // reverse of one bone for one pose.  The tangent's adjoint (U0 -> Gx, the parent's rows of U0) is the first-order reverse; with
-// `dual` the primal's adjoint (A0 -> Xb, the parent's rows of A0) runs next to it with the sigma'' cross terms.
-template <int FIN>
+// DUAL the primal's adjoint (A0 -> Xb, the parent's rows of A0) runs next to it with the sigma'' cross terms.
+template <int FIN, bool DUAL>
 __device__ __forceinline__ void so_rev_bone(const SoArgs& e, int j, int64_t c) {
     const float* w = e.wenc + e.off[j];
-    const float* w2 = bone_w2<FIN>(w);
-    float in[FIN], ah[HID], d1h[HID], d2h[HID], ao[FEAT], d1o[FEAT], d2o[FEAT];
+    float in[FIN], ind[FIN], ab[FEAT], adb[FEAT];
+    BoneDual b;
+    BoneAdj r;
     so_load_in<FIN>(e, j, c, false, in);
-    bone_fwd<FIN>(e, w, in, ah, d1h, d2h, ao, d1o, d2o);
-    float hz[HID], ahd[HID], oz[FEAT];
-#pragma unroll
-    for (int k = 0; k < HID; ++k) hz[k] = 0.f;
-#pragma unroll
-    for (int i = 0; i < FEAT; ++i) oz[i] = 0.f;
-    if (e.dual) {
-        float ind[FIN];
-        so_load_in<FIN>(e, j, c, true, ind);
-        so_bone_tan<FIN>(w, ind, d1h, hz, ahd, oz);
-    }
-    float zob[FEAT], zodb[FEAT], zhb[HID], zhdb[HID];
+    bone_fwd<FIN>(e, w, in, b);
+    if (DUAL) so_load_in<FIN>(e, j, c, true, ind);
+    bone_tan<FIN>(w, ind, DUAL, b);
 #pragma unroll
     for (int i = 0; i < FEAT; ++i) {
-        const float adb = e.U0[(int64_t)(j * FEAT + i) * e.ld + c];
-        const float ab = e.dual ? e.A0[(int64_t)(j * FEAT + i) * e.ld + c] : 0.f;
-        zob[i] = ab * d1o[i] + adb * oz[i] * d2o[i];
-        zodb[i] = adb * d1o[i];
+        adb[i] = e.U0[(int64_t)(j * FEAT + i) * e.ld + c];
+        if (DUAL) ab[i] = e.A0[(int64_t)(j * FEAT + i) * e.ld + c];
     }
-#pragma unroll
-    for (int k = 0; k < HID; ++k) {
-        float s = 0.f, sd = 0.f;
-#pragma unroll
-        for (int i = 0; i < FEAT; ++i) {
-            s = fmaf(w2[i * HID + k], zob[i], s);
-            sd = fmaf(w2[i * HID + k], zodb[i], sd);
-        }
-        zhb[k] = s * d1h[k] + sd * hz[k] * d2h[k];
-        zhdb[k] = sd * d1h[k];
-    }
+    bone_dual_rev<FIN, DUAL>(w, b, ab, adb, r);
 #pragma unroll
     for (int m = 0; m < FIN; ++m) {
-        float s = 0.f, sd = 0.f;
-#pragma unroll
-        for (int k = 0; k < HID; ++k) {
-            s = fmaf(w[k * FIN + m], zhb[k], s);
-            sd = fmaf(w[k * FIN + m], zhdb[k], sd);
-        }
+        float s, sd;
+        bone_input_adj<FIN, DUAL>(w, r, m, s, sd);
         if (m < BONE) {
             e.Gx[(int64_t)(j * BONE + m) * e.ld + c] = sd;
-            if (e.dual) e.Xb[(int64_t)(j * BONE + m) * e.ld + c] = s;
+            if (DUAL) e.Xb[(int64_t)(j * BONE + m) * e.ld + c] = s;
         } else {
             const int64_t at = (int64_t)(e.parent[j] * FEAT + (m - BONE)) * e.ld + c;
             e.U0[at] += sd;
-            if (e.dual) e.A0[at] += s;
+            if (DUAL) e.A0[at] += s;
         }
     }
 }
@@ -186,30 +141,21 @@ extern "C" __global__ void __launch_bounds__(256) pndf_so_enc_fwd_kernel(SoArgs 
     if (c >= e.n) return;
     const float* q = e.q + c * POSE;
     const float* v = e.v + c * POSE;
-    float n2[BONE] = {0.f, 0.f, 0.f, 0.f};
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int k = 0; k < BONE; ++k) n2[k] = fmaf(q[j * BONE + k], q[j * BONE + k], n2[k]);
-    float nrm[BONE], den[BONE], a[BONE] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < BONE; ++k) {
-        nrm[k] = sqrtf(n2[k]);
-        den[k] = fmaxf(nrm[k], NORM_EPS);
-    }
+    float nrm[BONE], a[BONE] = {0.f, 0.f, 0.f, 0.f};
+    pose_col_norms(q, nrm);
     for (int j = 0; j < NJ; ++j)
 #pragma unroll
         for (int k = 0; k < BONE; ++k) {
-            const float x = q[j * BONE + k] / den[k];
+            const float x = norm_x(q[j * BONE + k], nrm[k]);
             e.X[(int64_t)(j * BONE + k) * e.ld + c] = x;
             a[k] = fmaf(x, v[j * BONE + k], a[k]);
         }
     if (e.dual) {
-        // J_N v = (v - x (x . v)) / |q_k| per component k (a column of 21 joints); v / eps where the norm is clamped
         for (int j = 0; j < NJ; ++j)
 #pragma unroll
             for (int k = 0; k < BONE; ++k) {
                 const float x = e.X[(int64_t)(j * BONE + k) * e.ld + c];
-                e.Xd[(int64_t)(j * BONE + k) * e.ld + c] = nrm[k] > NORM_EPS ? (v[j * BONE + k] - x * a[k]) / nrm[k] : v[j * BONE + k] / NORM_EPS;
+                e.Xd[(int64_t)(j * BONE + k) * e.ld + c] = norm_jvp(v[j * BONE + k], x, a[k], nrm[k], nrm[k] > NORM_EPS);
             }
     }
     for (int j = 0; j < NJ; ++j) {
@@ -227,29 +173,27 @@ extern "C" __global__ void __launch_bounds__(256) pndf_so_enc_rev_kernel(SoArgs 
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= e.n) return;
     for (int j = NJ - 1; j >= 0; --j) {
-        if (e.parent[j] < 0) so_rev_bone<BONE>(e, j, c);
-        else so_rev_bone<BONE + FEAT>(e, j, c);
+        const bool root = e.parent[j] < 0;      // without a softplus the primal chain is compiled out, not run on zeros
+        if (e.dual) root ? so_rev_bone<BONE, true>(e, j, c) : so_rev_bone<BONE + FEAT, true>(e, j, c);
+        else root ? so_rev_bone<BONE, false>(e, j, c) : so_rev_bone<BONE + FEAT, false>(e, j, c);
     }
     const float* q = e.q + c * POSE;
     const float* v = e.v + c * POSE;
-    float n2[BONE] = {0.f, 0.f, 0.f, 0.f}, a[BONE] = {0.f, 0.f, 0.f, 0.f}, b[BONE] = {0.f, 0.f, 0.f, 0.f}, xe[BONE] = {0.f, 0.f, 0.f, 0.f};
+    float s[BONE], a[BONE] = {0.f, 0.f, 0.f, 0.f}, b[BONE] = {0.f, 0.f, 0.f, 0.f}, xe[BONE] = {0.f, 0.f, 0.f, 0.f};
+    pose_col_norms(q, s);
     for (int j = 0; j < NJ; ++j)
 #pragma unroll
         for (int k = 0; k < BONE; ++k) {
             const int64_t at = (int64_t)(j * BONE + k) * e.ld + c;
             const float x = e.X[at];
-            n2[k] = fmaf(q[j * BONE + k], q[j * BONE + k], n2[k]);
             a[k] = fmaf(x, v[j * BONE + k], a[k]);
             b[k] = fmaf(x, e.Gx[at], b[k]);
             if (e.dual) xe[k] = fmaf(x, e.Xb[at], xe[k]);
         }
-    float s[BONE], gp[BONE] = {0.f, 0.f, 0.f, 0.f};
+    float gp[BONE] = {0.f, 0.f, 0.f, 0.f};
     bool live[BONE];
 #pragma unroll
-    for (int k = 0; k < BONE; ++k) {
-        s[k] = sqrtf(n2[k]);
-        live[k] = s[k] > NORM_EPS;
-    }
+    for (int k = 0; k < BONE; ++k) live[k] = s[k] > NORM_EPS;
     for (int j = 0; j < NJ; ++j)
 #pragma unroll
         for (int k = 0; k < BONE; ++k) {
@@ -283,17 +227,7 @@ extern "C" __global__ void __launch_bounds__(256) pndf_so_enc_rev_kernel(SoArgs 
 }
 
 // ------------------------------------------------------------------------------------------------------------ host side
-struct pndf_so_plan {
-    int device = 0;
-    int L = 0;                    // linear layers of the trunk
-    int dims[MAX_LIN + 1] = {};   // dims[0] = 126 ... dims[L] = 1
-    int act = 0, enc_act = 0;
-    float beta = 100.f, enc_beta = 100.f;
-    int parent[NJ] = {};
-    int enc_off[NJ] = {};         // offset of bone j in the packed encoder
-    int enc_tensor_off[ENC_TENSORS + 1] = {};
-    int enc_params = 0;
-    int maxw = 0;
+struct pndf_so_plan : LayerNet {
     bool dual_trunk = false, dual = false;      // softplus trunk; a softplus anywhere
     std::string err;
 };
@@ -354,31 +288,9 @@ extern "C" int pndf_so_create(pndf_so_handle* out, const pndf_config* cfg, int d
     const PndfDeviceCheck dev = pndf_check_gfx950(device, "the second order");
     if (dev.code != PNDF_OK) return pndf_fail<pndf_so_plan>(nullptr, dev.code, dev.text);
     pndf_so_plan* h = new pndf_so_plan();
-    h->device = device;
-    h->L = cfg->n_dims - 1;
-    for (int t = 0; t <= h->L; ++t) {
-        h->dims[t] = cfg->dims[t];
-        if (cfg->dims[t] > h->maxw) h->maxw = cfg->dims[t];
-    }
-    h->act = cfg->act;
-    h->beta = cfg->beta;
-    h->enc_act = cfg->enc_act >= 0 ? cfg->enc_act : cfg->act;
-    h->enc_beta = cfg->enc_beta > 0.f ? cfg->enc_beta : cfg->beta;
+    layer_net_init(*h, cfg, device);
     h->dual_trunk = h->act == PNDF_ACT_SOFTPLUS;
     h->dual = h->dual_trunk || h->enc_act == PNDF_ACT_SOFTPLUS;
-    int o = 0, k = 0;
-    for (int j = 0; j < NJ; ++j) {
-        h->parent[j] = cfg->parent[j];
-        h->enc_off[j] = o;
-        const int fin = cfg->parent[j] < 0 ? BONE : BONE + FEAT;
-        const int sizes[4] = {HID * fin, HID, FEAT * HID, FEAT};
-        for (int s = 0; s < 4; ++s) {
-            h->enc_tensor_off[k++] = o;
-            o += sizes[s];
-        }
-    }
-    h->enc_tensor_off[ENC_TENSORS] = o;
-    h->enc_params = o;
     *out = h;
     return PNDF_OK;
 }
@@ -408,8 +320,7 @@ extern "C" int pndf_second_order(pndf_so_handle h, const float* const* weights, 
     const SoLayout l = so_layout(h, B);
     if (workspace_floats < l.total)
         return pndf_fail(h, PNDF_ERR_BAD_ARG, "workspace of " + std::to_string(workspace_floats) + " floats, pndf_so_workspace_floats asks for " + std::to_string(l.total));
-    for (int i = 0; i < ENC_TENSORS + 2 * h->L; ++i)
-        if (!weights[i]) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null weight tensor " + std::to_string(i));
+    if (const int i = null_tensor(*h, weights); i >= 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null weight tensor " + std::to_string(i));
     PndfRange range("pndf_second_order");
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
@@ -419,10 +330,7 @@ extern "C" int pndf_second_order(pndf_so_handle h, const float* const* weights, 
     const int L = h->L;
     const int64_t ld = l.nc;
 
-    PtrTable tab;
-    for (int k = 0; k < ENC_TENSORS; ++k) tab.p[k] = const_cast<float*>(weights[k]);
-    for (int k = 0; k <= ENC_TENSORS; ++k) tab.off[k] = h->enc_tensor_off[k];
-    hipLaunchKernelGGL(pndf_so_enc_pack_kernel, dim3(blocks(h->enc_params)), dim3(256), 0, st, tab, ws + l.wenc);
+    hipLaunchKernelGGL(pndf_so_enc_pack_kernel, dim3(blocks(h->enc_params)), dim3(256), 0, st, ptr_table(*h, weights), ws + l.wenc);
 
     SoArgs e;
     memset(&e, 0, sizeof(e));

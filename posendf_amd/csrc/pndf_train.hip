@@ -14,7 +14,11 @@
 //             primal columns, [abar|adotbar] = W^T [zbar|zdotbar] (TN GEMM) with zbar = abar sigma' + adotbar zdot sigma''
 //             and zdotbar = adotbar sigma' in the epilogue; the 21 bone MLPs of the encoder last, lanes owning poses, their
 //             weight gradients summed per workgroup (fixed order) and then over workgroups (fixed order).
-// The GEMM with its epilogues, the activation and the bone MLP live in pndf_gemm.h (shared with pndf_second_order.hip).
+// Shared with pndf_second_order.hip: the GEMM with its epilogues and the activation (pndf_gemm.h); the dual-number bone (gather,
+// forward with tangent, reverse with both adjoints: the formulas are in DESIGN.md section 2s, "The dual-number bone"), the pieces
+// of the normalisation and the host's description of the network, LayerNet (pndf_bone.h).  Here: the encoder's kernels around
+// the bone with the LDS reduction of its weight gradient, the eikonal seed, the losses, the reverse's seeds and sums, the launch
+// sequences.
 // Arithmetic: exact fp32 MFMA (v_mfma_f32_16x16x4_f32), fp32 accumulate.  No float atomics, no communication between
 // workgroups inside a launch: two calls with the same inputs give the same bits.
 #include <hip/hip_runtime.h>
@@ -29,7 +33,7 @@
 
 #include "../../include/posendf_amd.h"
 #include "pndf_experiment.h"
-#include "pndf_gemm.h"
+#include "pndf_bone.h"
 #include "pndf_host.h"
 
 PNDF_EXPORT_EXPERIMENT_WORD(train)
@@ -51,7 +55,7 @@ extern "C" __global__ void __launch_bounds__(256) pndf_train_gemm_nt_kernel(Gemm
 
 namespace {
 
-// ---- encoder: 21 bone MLPs (pndf_gemm.h: bone_fwd), the weights packed in state-dict order into one flat array
+// ---- encoder: 21 bone MLPs (pndf_bone.h), the weights packed in state-dict order into one flat array
 struct EncArgs {
     const float* wenc;        // packed encoder weights
     const float* q;           // noisy poses [B][84]
@@ -72,64 +76,46 @@ struct EncArgs {
     int off[NJ];
 };
 
-// bone j's input on primal column `col`: its own quaternion (X) and its parent's feature (act0)
+// bone j's input on primal column c (X and the parent's rows of act0), and its tangent on noisy column c (xdot in Xd and the
+// parent's rows of act0's tangent columns)
 template <int FIN>
-__device__ __forceinline__ void load_in(const EncArgs& e, int j, int64_t col, float* in) {
-#pragma unroll
-    for (int k = 0; k < BONE; ++k) in[k] = e.X[(int64_t)(j * BONE + k) * e.np + col];
-    if (FIN > BONE) {
-        const int p = e.parent[j];
-#pragma unroll
-        for (int i = 0; i < FIN - BONE; ++i) in[BONE + i] = e.act0[(int64_t)(p * FEAT + i) * e.ncols + col];
-    }
+__device__ __forceinline__ void load_in(const EncArgs& e, int j, int64_t c, float* in) {
+    bone_load<FIN>(e.X, e.np, e.act0, e.ncols, e.parent, j, c, in);
 }
-// the tangent of bone j's input on noisy column c: xdot and the parent's tangent feature
 template <int FIN>
 __device__ __forceinline__ void load_in_tan(const EncArgs& e, int j, int64_t c, float* ind) {
-#pragma unroll
-    for (int k = 0; k < BONE; ++k) ind[k] = e.Xd[(int64_t)(j * BONE + k) * e.B + c];
-    if (FIN > BONE) {
-        const int p = e.parent[j];
-#pragma unroll
-        for (int i = 0; i < FIN - BONE; ++i) ind[BONE + i] = e.act0[(int64_t)(p * FEAT + i) * e.ncols + e.np + c];
-    }
+    bone_load<FIN>(e.Xd, e.B, e.act0 + e.np, e.ncols, e.parent, j, c, ind);
 }
 
 template <int FIN>
 __device__ __forceinline__ void enc_fwd_bone(const EncArgs& e, int j, int64_t c) {
-    float in[FIN], ah[HID], d1h[HID], d2h[HID], ao[FEAT], d1o[FEAT], d2o[FEAT];
+    float in[FIN];
+    BoneDual b;
     load_in<FIN>(e, j, c, in);
-    bone_fwd<FIN>(e, e.wenc + e.off[j], in, ah, d1h, d2h, ao, d1o, d2o);
+    bone_fwd<FIN>(e, e.wenc + e.off[j], in, b);
 #pragma unroll
-    for (int i = 0; i < FEAT; ++i) e.act0[(int64_t)(j * FEAT + i) * e.ncols + c] = ao[i];
+    for (int i = 0; i < FEAT; ++i) e.act0[(int64_t)(j * FEAT + i) * e.ncols + c] = b.ao[i];
 }
 
 // first-order reverse of one bone (input gradient of the noisy batch): the gradient on act0's rows of bone j (U0) -> the x
-// gradient (Xd) and the parent's feature gradient (accumulated into U0)
+// gradient (Xd) and the parent's feature gradient (accumulated into U0).  The dual reverse without its primal chain.
 template <int FIN>
 __device__ __forceinline__ void enc_grad_bone(const EncArgs& e, int j, int64_t c) {
     const float* w = e.wenc + e.off[j];
-    const float* w2 = bone_w2<FIN>(w);
-    float in[FIN], ah[HID], d1h[HID], d2h[HID], ao[FEAT], d1o[FEAT], d2o[FEAT];
+    float in[FIN], adb[FEAT];
+    BoneDual b;
+    BoneAdj r;
     load_in<FIN>(e, j, c, in);
-    bone_fwd<FIN>(e, w, in, ah, d1h, d2h, ao, d1o, d2o);
-    float go[FEAT], gh[HID];
+    bone_fwd<FIN>(e, w, in, b);
 #pragma unroll
-    for (int i = 0; i < FEAT; ++i) go[i] = e.U0[(int64_t)(j * FEAT + i) * e.B + c] * d1o[i];
-#pragma unroll
-    for (int k = 0; k < HID; ++k) {
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < FEAT; ++i) s = fmaf(w2[i * HID + k], go[i], s);
-        gh[k] = s * d1h[k];
-    }
+    for (int i = 0; i < FEAT; ++i) adb[i] = e.U0[(int64_t)(j * FEAT + i) * e.B + c];
+    bone_dual_rev<FIN, false>(w, b, nullptr, adb, r);
 #pragma unroll
     for (int m = 0; m < FIN; ++m) {
-        float s = 0.f;
-#pragma unroll
-        for (int k = 0; k < HID; ++k) s = fmaf(w[k * FIN + m], gh[k], s);
-        if (m < BONE) e.Xd[(int64_t)(j * BONE + m) * e.B + c] = s;
-        else e.U0[(int64_t)(e.parent[j] * FEAT + (m - BONE)) * e.B + c] += s;
+        float s, sd;
+        bone_input_adj<FIN, false>(w, r, m, s, sd);
+        if (m < BONE) e.Xd[(int64_t)(j * BONE + m) * e.B + c] = sd;
+        else e.U0[(int64_t)(e.parent[j] * FEAT + (m - BONE)) * e.B + c] += sd;
     }
 }
 
@@ -137,77 +123,44 @@ __device__ __forceinline__ void enc_grad_bone(const EncArgs& e, int j, int64_t c
 template <int FIN>
 __device__ __forceinline__ void enc_tan_bone(const EncArgs& e, int j, int64_t c) {
     const float* w = e.wenc + e.off[j];
-    const float* w2 = bone_w2<FIN>(w);
-    float in[FIN], ind[FIN], ah[HID], d1h[HID], d2h[HID], ao[FEAT], d1o[FEAT], d2o[FEAT];
+    float in[FIN], ind[FIN];
+    BoneDual b;
     load_in<FIN>(e, j, c, in);
     load_in_tan<FIN>(e, j, c, ind);
-    bone_fwd<FIN>(e, w, in, ah, d1h, d2h, ao, d1o, d2o);
-    float hd[HID];
-    bone_lin0<FIN>(w, ind, hd, false);
+    bone_fwd<FIN>(e, w, in, b);
+    bone_tan<FIN>(w, ind, true, b);
 #pragma unroll
-    for (int k = 0; k < HID; ++k) hd[k] *= d1h[k];
-#pragma unroll
-    for (int i = 0; i < FEAT; ++i) {
-        float s = 0.f;
-#pragma unroll
-        for (int k = 0; k < HID; ++k) s = fmaf(w2[i * HID + k], hd[k], s);
-        e.act0[(int64_t)(j * FEAT + i) * e.ncols + e.np + c] = s * d1o[i];
-    }
+    for (int i = 0; i < FEAT; ++i) e.act0[(int64_t)(j * FEAT + i) * e.ncols + e.np + c] = b.oz[i] * b.d1o[i];
 }
 
 // dual reverse of one bone for one pose: the primal and tangent adjoints of the bone's output (abar, in place) -> the parent's,
-// and the per-pose vectors whose outer products make the bone's weight gradient (to LDS, column `lane`)
+// and the per-pose vectors whose outer products make the bone's weight gradient (to LDS, column `lane`; zeros on an idle lane)
 template <int FIN>
 __device__ __forceinline__ void enc_rev_bone(const EncArgs& e, int j, int64_t c, bool active, bool tangent,
                                              float (*sv)[ENC_LDS_LD], int lane) {
-    float in[HID] = {}, ind[HID] = {}, zhb[HID] = {}, zhdb[HID] = {}, ah[HID] = {}, ahd[HID] = {}, zob[FEAT] = {}, zodb[FEAT] = {};
+    float in[HID] = {}, ind[HID] = {};
+    BoneDual b = {};
+    BoneAdj r = {};
     if (active) {
         const float* w = e.wenc + e.off[j];
-        const float* w2 = bone_w2<FIN>(w);
         const int64_t tc = e.np + c;
         load_in<FIN>(e, j, c, in);
         if (tangent) load_in_tan<FIN>(e, j, c, ind);
-        float d1h[HID], d2h[HID], ao[FEAT], d1o[FEAT], d2o[FEAT];
-        bone_fwd<FIN>(e, w, in, ah, d1h, d2h, ao, d1o, d2o);
-        float hz[HID], oz[FEAT];       // tangent pre-activations
-        bone_lin0<FIN>(w, ind, hz, false);
-#pragma unroll
-        for (int k = 0; k < HID; ++k) ahd[k] = d1h[k] * hz[k];
+        bone_fwd<FIN>(e, w, in, b);
+        bone_tan<FIN>(w, ind, true, b);      // a lane without a tangent runs it on ind = 0: a per-lane branch here spills 42 VGPRs
+        float ab[FEAT], adb[FEAT];
 #pragma unroll
         for (int i = 0; i < FEAT; ++i) {
-            float s = 0.f;
-#pragma unroll
-            for (int k = 0; k < HID; ++k) s = fmaf(w2[i * HID + k], ahd[k], s);
-            oz[i] = s;
+            ab[i] = e.abar[(int64_t)(j * FEAT + i) * e.ncols + c];
+            adb[i] = tangent ? e.abar[(int64_t)(j * FEAT + i) * e.ncols + tc] : 0.f;
         }
-#pragma unroll
-        for (int i = 0; i < FEAT; ++i) {
-            const float ab = e.abar[(int64_t)(j * FEAT + i) * e.ncols + c];
-            const float adb = tangent ? e.abar[(int64_t)(j * FEAT + i) * e.ncols + tc] : 0.f;
-            zob[i] = ab * d1o[i] + adb * oz[i] * d2o[i];
-            zodb[i] = adb * d1o[i];
-        }
-#pragma unroll
-        for (int k = 0; k < HID; ++k) {
-            float s = 0.f, sd = 0.f;
-#pragma unroll
-            for (int i = 0; i < FEAT; ++i) {
-                s = fmaf(w2[i * HID + k], zob[i], s);
-                sd = fmaf(w2[i * HID + k], zodb[i], sd);
-            }
-            zhb[k] = s * d1h[k] + sd * hz[k] * d2h[k];
-            zhdb[k] = sd * d1h[k];
-        }
+        bone_dual_rev<FIN, true, 0x20>(w, b, ab, adb, r);      // 0x20: this unit's rounding of zob (pndf_bone.h)
         if (FIN > BONE) {
             const int p = e.parent[j];
 #pragma unroll
-            for (int m = BONE; m < FIN; ++m) {
-                float s = 0.f, sd = 0.f;
-#pragma unroll
-                for (int k = 0; k < HID; ++k) {
-                    s = fmaf(w[k * FIN + m], zhb[k], s);
-                    sd = fmaf(w[k * FIN + m], zhdb[k], sd);
-                }
+            for (int m = BONE; m < FIN; ++m) {      // the parent's adjoints; the weight gradient does not need those of x
+                float s, sd;
+                bone_input_adj<FIN, true>(w, r, m, s, sd);
                 e.abar[(int64_t)(p * FEAT + (m - BONE)) * e.ncols + c] += s;
                 if (tangent) e.abar[(int64_t)(p * FEAT + (m - BONE)) * e.ncols + tc] += sd;
             }
@@ -217,15 +170,15 @@ __device__ __forceinline__ void enc_rev_bone(const EncArgs& e, int j, int64_t c,
     for (int k = 0; k < HID; ++k) {
         sv[k][lane] = in[k];
         sv[10 + k][lane] = ind[k];
-        sv[20 + k][lane] = zhb[k];
-        sv[30 + k][lane] = zhdb[k];
-        sv[40 + k][lane] = ah[k];
-        sv[50 + k][lane] = ahd[k];
+        sv[20 + k][lane] = r.zhb[k];
+        sv[30 + k][lane] = r.zhdb[k];
+        sv[40 + k][lane] = b.ah[k];
+        sv[50 + k][lane] = b.ahd[k];
     }
 #pragma unroll
     for (int i = 0; i < FEAT; ++i) {
-        sv[60 + i][lane] = zob[i];
-        sv[66 + i][lane] = zodb[i];
+        sv[60 + i][lane] = r.zob[i];
+        sv[66 + i][lane] = r.zodb[i];
     }
 }
 
@@ -257,16 +210,11 @@ extern "C" __global__ void __launch_bounds__(256) pndf_train_enc_fwd_kernel(EncA
     if (c >= e.np) return;
     if (c < e.B) {
         const float* q = e.q + c * POSE;
-        float n2[BONE] = {0.f, 0.f, 0.f, 0.f};
+        float nrm[BONE];
+        pose_col_norms(q, nrm);
         for (int j = 0; j < NJ; ++j)
 #pragma unroll
-            for (int k = 0; k < BONE; ++k) n2[k] = fmaf(q[j * BONE + k], q[j * BONE + k], n2[k]);
-        float den[BONE];
-#pragma unroll
-        for (int k = 0; k < BONE; ++k) den[k] = fmaxf(sqrtf(n2[k]), NORM_EPS);
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int k = 0; k < BONE; ++k) e.X[(int64_t)(j * BONE + k) * e.np + c] = q[j * BONE + k] / den[k];
+            for (int k = 0; k < BONE; ++k) e.X[(int64_t)(j * BONE + k) * e.np + c] = norm_x(q[j * BONE + k], nrm[k]);
         e.dgt_copy[c] = e.dgt[c];
     } else {
         const float* q = e.qm + (c - e.B) * POSE;
@@ -288,16 +236,14 @@ extern "C" __global__ void __launch_bounds__(256) pndf_train_enc_eik_kernel(EncA
         else enc_grad_bone<BONE + FEAT>(e, j, c);
     }
     const float* q = e.q + c * POSE;
-    float nrm[BONE] = {0.f, 0.f, 0.f, 0.f}, s[BONE] = {0.f, 0.f, 0.f, 0.f};
+    float nrm[BONE], s[BONE] = {0.f, 0.f, 0.f, 0.f};
+    bool live[BONE];
+    pose_col_norms(q, nrm);
+#pragma unroll
+    for (int k = 0; k < BONE; ++k) live[k] = nrm[k] >= NORM_EPS;
     for (int j = 0; j < NJ; ++j)
 #pragma unroll
-        for (int k = 0; k < BONE; ++k) {
-            nrm[k] = fmaf(q[j * BONE + k], q[j * BONE + k], nrm[k]);
-            s[k] = fmaf(e.X[(int64_t)(j * BONE + k) * e.np + c], e.Xd[(int64_t)(j * BONE + k) * e.B + c], s[k]);
-        }
-#pragma unroll
-    for (int k = 0; k < BONE; ++k) nrm[k] = sqrtf(nrm[k]);
-    // J_N v = (v - x (x . v)) / |q_k| per quaternion component k (a column of 21 joints); v / eps where the norm is clamped
+        for (int k = 0; k < BONE; ++k) s[k] = fmaf(e.X[(int64_t)(j * BONE + k) * e.np + c], e.Xd[(int64_t)(j * BONE + k) * e.B + c], s[k]);
     const float coef = 2.f / (21.f * (float)e.B);
     float eik = 0.f, t[BONE] = {0.f, 0.f, 0.f, 0.f};
     for (int j = 0; j < NJ; ++j) {
@@ -306,7 +252,7 @@ extern "C" __global__ void __launch_bounds__(256) pndf_train_enc_eik_kernel(EncA
         for (int k = 0; k < BONE; ++k) {
             x[k] = e.X[(int64_t)(j * BONE + k) * e.np + c];
             const float gx = e.Xd[(int64_t)(j * BONE + k) * e.B + c];
-            G[k] = nrm[k] >= NORM_EPS ? (gx - x[k] * s[k]) / nrm[k] : gx / NORM_EPS;
+            G[k] = norm_jvp(gx, x[k], s[k], nrm[k], live[k]);
             n2 = fmaf(G[k], G[k], n2);
         }
         const float n = sqrtf(n2);
@@ -325,7 +271,7 @@ extern "C" __global__ void __launch_bounds__(256) pndf_train_enc_eik_kernel(EncA
         for (int k = 0; k < BONE; ++k) {
             float* p = e.Xd + (int64_t)(j * BONE + k) * e.B + c;
             const float x = e.X[(int64_t)(j * BONE + k) * e.np + c];
-            *p = nrm[k] >= NORM_EPS ? (*p - x * t[k]) / nrm[k] : *p / NORM_EPS;
+            *p = norm_jvp(*p, x, t[k], nrm[k], live[k]);
         }
     for (int j = 0; j < NJ; ++j) {
         if (e.parent[j] < 0) enc_tan_bone<BONE>(e, j, c);
@@ -463,17 +409,7 @@ struct Layout {
 
 }  // namespace
 
-struct pndf_train_plan {
-    int device = 0;
-    int L = 0;                    // linear layers of the trunk
-    int dims[MAX_LIN + 1] = {};   // dims[0] = 126 ... dims[L] = 1
-    int act = 0, enc_act = 0;
-    float beta = 100.f, enc_beta = 100.f;
-    int parent[NJ] = {};
-    int enc_off[NJ] = {};         // offset of bone j in the packed encoder
-    int enc_tensor_off[ENC_TENSORS + 1] = {};
-    int enc_params = 0;
-    int maxw = 0;
+struct pndf_train_plan : LayerNet {
     std::mutex mu;
     std::unordered_map<const void*, Shape> shapes;      // workspace -> the shape of the forward that filled it
     std::string err;
@@ -549,13 +485,6 @@ EncArgs enc_args(const pndf_train_plan* h, const Layout& l, float* ws, int64_t B
     return e;
 }
 
-PtrTable ptr_table(const pndf_train_plan* h, const float* const* tensors) {
-    PtrTable t;
-    for (int k = 0; k < ENC_TENSORS; ++k) t.p[k] = const_cast<float*>(tensors[k]);
-    for (int k = 0; k <= ENC_TENSORS; ++k) t.off[k] = h->enc_tensor_off[k];
-    return t;
-}
-
 }  // namespace
 
 extern "C" const char* pndf_train_last_error(pndf_train_handle h) { return pndf_last_error_of(h); }
@@ -569,29 +498,7 @@ extern "C" int pndf_train_create(pndf_train_handle* out, const pndf_config* cfg,
     const PndfDeviceCheck dev = pndf_check_gfx950(device, "training");
     if (dev.code != PNDF_OK) return pndf_fail<pndf_train_plan>(nullptr, dev.code, dev.text);
     pndf_train_plan* h = new pndf_train_plan();
-    h->device = device;
-    h->L = cfg->n_dims - 1;
-    for (int t = 0; t <= h->L; ++t) {
-        h->dims[t] = cfg->dims[t];
-        if (cfg->dims[t] > h->maxw) h->maxw = cfg->dims[t];
-    }
-    h->act = cfg->act;
-    h->beta = cfg->beta;
-    h->enc_act = cfg->enc_act >= 0 ? cfg->enc_act : cfg->act;
-    h->enc_beta = cfg->enc_beta > 0.f ? cfg->enc_beta : cfg->beta;
-    int o = 0, k = 0;
-    for (int j = 0; j < NJ; ++j) {
-        h->parent[j] = cfg->parent[j];
-        h->enc_off[j] = o;
-        const int fin = cfg->parent[j] < 0 ? BONE : BONE + FEAT;
-        const int sizes[4] = {HID * fin, HID, FEAT * HID, FEAT};
-        for (int s = 0; s < 4; ++s) {
-            h->enc_tensor_off[k++] = o;
-            o += sizes[s];
-        }
-    }
-    h->enc_tensor_off[ENC_TENSORS] = o;
-    h->enc_params = o;
+    layer_net_init(*h, cfg, device);
     *out = h;
     return PNDF_OK;
 }
@@ -614,8 +521,7 @@ extern "C" int pndf_train_forward(pndf_train_handle h, const float* const* weigh
     if (B < 1 || Bm < 1) return pndf_fail(h, PNDF_ERR_BAD_ARG, "B and Bm must be >= 1");
     if (loss_type != LOSS_L1 && loss_type != LOSS_L2) return pndf_fail(h, PNDF_ERR_BAD_ARG, "loss_type: 0 (l1) or 1 (l2)");
     if (((uintptr_t)workspace & 15) != 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "workspace must be 16-byte aligned");
-    for (int i = 0; i < ENC_TENSORS + 2 * h->L; ++i)
-        if (!weights[i]) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null weight tensor " + std::to_string(i));
+    if (const int i = null_tensor(*h, weights); i >= 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null weight tensor " + std::to_string(i));
     PndfRange range("pndf_train_forward");
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
@@ -632,7 +538,7 @@ extern "C" int pndf_train_forward(pndf_train_handle h, const float* const* weigh
     const float* const* W = weights + ENC_TENSORS;          // trunk layer t: W[2t] weight [dims[t+1]][dims[t]], W[2t+1] bias
     const bool sp = h->act == PNDF_ACT_SOFTPLUS;
 
-    hipLaunchKernelGGL(pndf_train_enc_pack_kernel, dim3(blocks(h->enc_params)), dim3(256), 0, st, ptr_table(h, weights), ws + l.wenc);
+    hipLaunchKernelGGL(pndf_train_enc_pack_kernel, dim3(blocks(h->enc_params)), dim3(256), 0, st, ptr_table(*h, weights), ws + l.wenc);
     EncArgs e = enc_args(h, l, ws, B, Bm, eik);
     e.q = q; e.qm = q_man; e.dgt = dist_gt;
     hipLaunchKernelGGL(pndf_train_enc_fwd_kernel, dim3(blocks(l.np)), dim3(256), 0, st, e);
@@ -685,8 +591,8 @@ extern "C" int pndf_train_backward(pndf_train_handle h, const float* const* weig
         if (it == h->shapes.end()) return pndf_fail(h, PNDF_ERR_BAD_ARG, "workspace was not filled by pndf_train_forward of this handle");
         s = it->second;
     }
-    for (int i = 0; i < ENC_TENSORS + 2 * h->L; ++i)
-        if (!weights[i] || !grads[i]) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null weight / gradient tensor " + std::to_string(i));
+    if (const int i = null_tensor(*h, weights, grads); i >= 0)
+        return pndf_fail(h, PNDF_ERR_BAD_ARG, "null weight / gradient tensor " + std::to_string(i));
     PndfRange range("pndf_train_backward");
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
@@ -700,7 +606,7 @@ extern "C" int pndf_train_backward(pndf_train_handle h, const float* const* weig
     const bool cross = eik && h->act == PNDF_ACT_SOFTPLUS;
     const int64_t npr = eik ? l.np : B;          // primal columns of the reverse pass
 
-    hipLaunchKernelGGL(pndf_train_enc_pack_kernel, dim3(blocks(h->enc_params)), dim3(256), 0, st, ptr_table(h, weights), ws + l.wenc);
+    hipLaunchKernelGGL(pndf_train_enc_pack_kernel, dim3(blocks(h->enc_params)), dim3(256), 0, st, ptr_table(*h, weights), ws + l.wenc);
     const int L = h->L;
     int zi = 0;
     hipLaunchKernelGGL(pndf_train_head_kernel, dim3(blocks(l.nrev)), dim3(256), 0, st, ws + l.act[L], ws + l.dgt, ws + l.D1[L - 1],
@@ -737,9 +643,7 @@ extern "C" int pndf_train_backward(pndf_train_handle h, const float* const* weig
     EncArgs e = enc_args(h, l, ws, B, Bm, eik);
     e.abar = ws + l.Z[zi];
     hipLaunchKernelGGL(pndf_train_enc_rev_kernel, dim3(l.enc_wgs), dim3(ENC_WG), 0, st, e);
-    PtrTable gtab;
-    for (int k = 0; k < ENC_TENSORS; ++k) gtab.p[k] = grads[k];
-    for (int k = 0; k <= ENC_TENSORS; ++k) gtab.off[k] = h->enc_tensor_off[k];
-    hipLaunchKernelGGL(pndf_train_enc_reduce_kernel, dim3(blocks(h->enc_params)), dim3(256), 0, st, gtab, ws + l.part, l.enc_wgs);
+    hipLaunchKernelGGL(pndf_train_enc_reduce_kernel, dim3(blocks(h->enc_params)), dim3(256), 0, st, ptr_table(*h, grads), ws + l.part,
+                       l.enc_wgs);
     return pndf_check_launch(h, "pndf_train_backward");
 }
