@@ -148,7 +148,9 @@ int pndf_project_ex(pndf_handle h, const float* q_in, float* q_out, float* d_las
  * `train.device` is "cpu" (model/posendf.py:35,64 runs wherever the config says).  A separate handle type with no device
  * behind it: plain C++ on the host cores, fp32, PyTorch's activation conventions; blocks of 32 poses are dealt to threads
  * (PNDF_CPU_THREADS, default: all hardware threads).  Same configurations as pndf_create (all three activations, the
- * encoder-less model, narrower hidden layers; `precision` is ignored), same status codes; no stream argument: the calls
+ * encoder-less model, narrower hidden layers; `precision` is ignored) and, for the six first-order calls below, any joint tree
+ * that pndf_skel_create takes (posendf_amd_skeleton.h: 1 .. 32 joints, parent[j] in -1 .. j-1, dims[0] = 6 J or 4 J, poses
+ * [B, J, 4]); same status codes; no stream argument: the calls
  * return when the result is in memory.  Never used as a fallback: the device entry points above fail when there is no
  * gfx950 device. */
 typedef struct pndf_cpu_engine* pndf_cpu_handle;

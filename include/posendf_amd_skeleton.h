@@ -1,0 +1,77 @@
+/* posendf_amd_skeleton.h -- distance, gradient and projection for any joint tree.
+ *
+ * Companion of posendf_amd.h (same library).  The model has nothing SMPL-specific in it: a chain of bone MLPs along a parent
+ * table in front of an MLP (model/network/net_modules.py:140-170, :46-72).  pndf_create runs the 21-joint table of
+ * get_parent_mapping('smpl') on persistent kernels; this unit runs ANY table -- a hand, a body with a jaw, an animal rig -- layer
+ * by layer: two encoder kernels around exact-fp32 MFMA GEMMs, 2 + 2 L launches per evaluation for L linear layers.  DESIGN.md
+ * section 2j.
+ *
+ * The networks: pndf_config as pndf_create reads it, with
+ *   num_joints J  1 .. 32;   parent[j] in -1 .. j-1, -1 = a root, any number of roots;
+ *   dims[0] = 6 J (structure encoder) or 4 J (model.StrEnc.use = False);  1 .. 7 hidden layers of width 1 .. 1024;  dims[last] = 1;
+ *   act / enc_act relu, lrelu or softplus (enc_act -1, enc_beta <= 0: the trunk's);  precision PNDF_PREC_FP32 only.
+ * Anything else is PNDF_ERR_UNSUPPORTED with a text that names the field, decided before a device is looked for.
+ *
+ * Arithmetic: the reference's, for a pose [J,4]: x = F.normalize(pose, dim=1) (over the JOINT axis, per quaternion component), the
+ * bones in index order on cat(x_j, feature of the parent), the trunk on the concatenated features; the gradient is the analytic
+ * reverse.  Exact fp32 MFMA, fp32 accumulate; no float atomics, poses are processed in chunks whose seams depend on B alone: the
+ * same inputs give the same bits, and a pose's result does not depend on the other poses of the batch.
+ *
+ * Conventions: those of posendf_amd.h -- contiguous fp32, poses [B, J, 4], distances [B]; DEVICE pointers, 4-byte aligned, the
+ * workspace 16-byte aligned; work is enqueued on `stream` (a hipStream_t passed as void*; NULL = the default stream) and the call
+ * returns without synchronising, allocating or freeing anything (pndf_skel_create and pndf_skel_load_weights allocate /
+ * synchronise); every entry point runs on the device of its handle and restores the caller's current device; 0 on success, a
+ * negative pndf_status otherwise, its text in pndf_skel_last_error (of the calling thread's slot when there is no handle).
+ * B == 0 succeeds without a launch.  PNDF_ERR_BAD_ARG with nothing launched or written for a null handle, a negative B or step
+ * count, a null or misaligned pointer that is not optional, a workspace that is too small; PNDF_ERR_NO_WEIGHTS before
+ * pndf_skel_load_weights.
+ *
+ * The host twins pndf_cpu_create / pndf_cpu_load_weights / pndf_forward_cpu / pndf_forward_grad_cpu / pndf_project_cpu /
+ * pndf_project_ex_cpu (posendf_amd.h) accept the same skeletons.
+ */
+#ifndef POSENDF_AMD_SKELETON_H
+#define POSENDF_AMD_SKELETON_H
+
+#include "posendf_amd.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct pndf_skel_plan* pndf_skel_handle;
+
+/* A plan for the network of `cfg` on `device` (a gfx950 device: PNDF_ERR_NO_DEVICE otherwise). */
+int pndf_skel_create(pndf_skel_handle* out, const pndf_config* cfg, int device);
+int pndf_skel_destroy(pndf_skel_handle h);
+
+/* load_state_dict.  `tensors` are HOST pointers in state-dict order: with the encoder, for j in 0 .. J-1 enc.net.j.net.0.weight
+ * [10, 4 | 10], .bias [10], enc.net.j.net.2.weight [6, 10], .bias [6] (4 J tensors; a root's first layer is 4 wide); then weight
+ * [out, in] and bias [out] of every dfnet.lin.  `numel[i]` is checked against the architecture (PNDF_ERR_BAD_SHAPE).  The call
+ * uploads a copy and synchronises. */
+int pndf_skel_load_weights(pndf_skel_handle h, const float* const* tensors, const int64_t* numel, int n_tensors);
+
+/* Bytes of the workspace of the three compute calls for B poses: a function of the plan and B only, bounded (the batch is
+ * processed in chunks); 0 for B == 0; PNDF_ERR_BAD_ARG for a null handle or a negative B. */
+int64_t pndf_skel_workspace_bytes(pndf_skel_handle h, int64_t B);
+
+/* forward(pose, train=False)['dist_pred']: q [B,J,4] -> d [B]. */
+int pndf_skel_forward(pndf_skel_handle h, const float* q, float* d, int64_t B, void* workspace, int64_t workspace_bytes,
+                      void* stream);
+
+/* forward + torch.autograd.grad(d, q, grad_out): dq[b] = grad_out[b] * d d_b / d q_b; grad_out == NULL means ones; d may be
+ * NULL and is then not written.  dq must not overlap q. */
+int pndf_skel_forward_grad(pndf_skel_handle h, const float* q, const float* grad_out, float* d, float* dq, int64_t B,
+                           void* workspace, int64_t workspace_bytes, void* stream);
+
+/* `steps` projection steps with the options of pndf_project_ex (opt == NULL: the plain step q <- q - d * grad d); the step runs
+ * inside the gradient's last kernel.  q_out may be q_in itself (no other overlap).  d_last (may be NULL) is dist_pred of the last
+ * iteration, evaluated before its update; with steps == 0 q_out is a copy of q_in and d_last is zero. */
+int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps,
+                      const pndf_project_options* opt, void* workspace, int64_t workspace_bytes, void* stream);
+
+const char* pndf_skel_last_error(pndf_skel_handle h);   /* h may be NULL: last error of a failed pndf_skel_create */
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* POSENDF_AMD_SKELETON_H */

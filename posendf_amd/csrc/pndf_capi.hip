@@ -115,7 +115,7 @@ extern "C" void pndf_default_config(pndf_config* cfg, int32_t act, float beta) {
 static int check_config(pndf_engine* h, const pndf_config* cfg) {
     if (!cfg) return pndf_fail(h, PNDF_ERR_BAD_ARG, "cfg is null");
     if (cfg->num_joints != NJ)
-        return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "only the 21-joint structure of get_parent_mapping('smpl') is implemented");
+        return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "num_joints: the persistent engine runs the 21-joint table of get_parent_mapping('smpl') only; pndf_skel_create (posendf_amd_skeleton.h) takes any joint tree");
     // The fused kernels are laid out for configs/amass.yaml (126 | 84, 256, 512, 1024, 512, 256, 64, 1).  A DFNet of the same
     // depth whose hidden layers are NARROWER runs on them zero-padded (padded units have zero outgoing weights, so they
     // reach neither the distance nor its gradient, whatever the activation); any other `dims` list the reference can build
@@ -130,7 +130,7 @@ static int check_config(pndf_engine* h, const pndf_config* cfg) {
         if (cfg->dims[i] < 1 || cfg->dims[i] > MAX_WIDTH)
             return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "DFNet hidden widths must be 1 .. 1024");
     for (int i = 0; i < NJ; ++i)
-        if (cfg->parent[i] != PARENT[i]) return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "parent table must be get_parent_mapping('smpl')");
+        if (cfg->parent[i] != PARENT[i]) return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "parent: the persistent engine runs the table of get_parent_mapping('smpl') only; pndf_skel_create (posendf_amd_skeleton.h) takes any joint tree");
     if (cfg->act != PNDF_ACT_RELU && cfg->act != PNDF_ACT_LRELU && cfg->act != PNDF_ACT_SOFTPLUS)
         return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "unknown activation (relu, lrelu and softplus are implemented)");
     if (cfg->act == PNDF_ACT_SOFTPLUS && !(cfg->beta > 0.f))

@@ -2,7 +2,9 @@
 // pndf_forward_grad / pndf_project (include/posendf_amd.h) on HOST pointers, for a caller whose `train.device` is "cpu"
 // (reference model/posendf.py:35,64 moves the pose to whatever device the config names).  Written from scratch in plain
 // C++ for the host cores -- NOT the oracle (oracle/ is test infrastructure and is imported by nothing here) and NOT a
-// fallback: the device entry points never route here, a missing GPU still fails loudly there.
+// fallback: the device entry points never route here, a missing GPU still fails loudly there.  The first-order twins take the joint
+// count and the parent table from the handle's config (any joint tree of include/posendf_amd_skeleton.h, pndf_skel_plan.h); on the
+// SMPL table they compute what they did with the table fixed.  Completion, interpolation, second order and online stay 21-joint.
 //
 // Layout: poses are processed in blocks of PB = 32; inside a block every activation tensor is [feature][pose] so that the
 // inner loop of a layer runs over the 32 poses of the block (contiguous floats: one or two AVX-512 / four AVX2 registers)
@@ -32,12 +34,14 @@
 #include "pndf_layout.h"
 #include "pndf_online.h"
 #include "pndf_project_opts.h"
+#include "pndf_skel_plan.h"
 
 using namespace pndf;
 
 namespace {
 
 constexpr int PB = 32;
+constexpr int MAXJ = PNDF_SKEL_MAX_JOINTS;      // the first-order twins take any joint tree (pndf_skel_plan.h); the others stay 21-joint
 
 struct Layer {
     int in = 0, out = 0;
@@ -50,7 +54,11 @@ struct pndf_cpu_engine {
     pndf_config cfg;
     bool encoder = true;
     bool have_weights = false;
-    Layer enc[NJ][2];
+    bool smpl = true;       // 21 joints along get_parent_mapping('smpl'): what completion, interpolation and the second order need
+    int nj = NJ;            // joints, quaternion components (4 nj) and parent table of the skeleton
+    int nq = NQ;
+    int parent[MAXJ];
+    Layer enc[MAXJ][2];
     Layer lin[MAXLIN];      // any DFNet depth the reference can build (net_modules.py:14-28: `dims` is a free list): 2 .. 8 linear layers
     int dims[MAXLIN + 1];
     int nlin = NLIN;
@@ -122,12 +130,15 @@ void activate(const Act& a, float* z, float* der, int n, bool output_layer) {
 }
 
 struct Scratch {      // per thread
-    std::vector<float> n, x[MAXLIN + 1], dx[MAXLIN + 1], g, g2, eh[NJ], ehd[NJ], ef[NJ], efd[NJ], ein[NJ], gf, gh, gin;
+    std::vector<float> n, x[MAXLIN + 1], dx[MAXLIN + 1], g, g2, eh[MAXJ], ehd[MAXJ], ef[MAXJ], efd[MAXJ], ein[MAXJ], gf, gh, gin;
     float inv[4][PB], nrm[4][PB];
 };
 
-void forward_grad_block(const pndf_cpu_engine& E, const float* q /*[nb][84]*/, int nb, const float* gout, float* d, float* dq,
+void forward_grad_block(const pndf_cpu_engine& E, const float* q /*[nb][4 nj]*/, int nb, const float* gout, float* d, float* dq,
                         bool want_grad, Scratch& S) {
+    const int NJ = E.nj, NQ = E.nq, NFEAT = FEAT * E.nj;      // the skeleton of the handle (shadowing pndf_layout.h's SMPL constants)
+    const int* PARENT = E.parent;
+    auto enc_in = [PARENT](int j) { return PARENT[j] < 0 ? 4 : 10; };
     const Act act{E.cfg.act, E.cfg.beta};
     // model.StrEnc.act / beta are read on their own (net_modules.py:128); -1 / <= 0: the trunk's
     const Act eact{E.cfg.enc_act == -1 ? E.cfg.act : E.cfg.enc_act, E.cfg.enc_beta > 0.f ? E.cfg.enc_beta : E.cfg.beta};
@@ -288,12 +299,11 @@ extern "C" int pndf_cpu_create(pndf_cpu_handle* out, const pndf_config* cfg) {
     if (!out || !cfg) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_BAD_ARG, "null argument");
     *out = nullptr;
     if (cfg->act < PNDF_ACT_RELU || cfg->act > PNDF_ACT_SOFTPLUS) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_UNSUPPORTED, "unknown activation");
-    if (cfg->num_joints != NJ || cfg->n_dims < 3 || cfg->n_dims > MAXLIN + 1)
-        return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_UNSUPPORTED, "21 joints and a DFNet of 2 .. 8 linear layers (n_dims 3 .. 9)");
+    // any joint tree (include/posendf_amd_skeleton.h): 1 .. 32 joints, every parent before its child, dims[0] = 6 J or 4 J
+    if (const char* why = pndf_skeleton_refusal(cfg)) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_UNSUPPORTED, why);
+    if (cfg->n_dims < 3 || cfg->n_dims > MAXLIN + 1)
+        return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_UNSUPPORTED, "n_dims: a DFNet of 2 .. 8 linear layers (n_dims 3 .. 9)");
     const int nlin = cfg->n_dims - 1;
-    for (int j = 0; j < NJ; ++j)
-        if (cfg->parent[j] != PARENT[j]) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_UNSUPPORTED, "parent table other than net_utils.py:46");
-    if (cfg->dims[0] != NFEAT && cfg->dims[0] != NOENC_IN) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_UNSUPPORTED, "DFNet in_dim must be 126 (encoder) or 84");
     if (cfg->dims[nlin] != 1) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_UNSUPPORTED, "DFNet must end in one output");
     for (int l = 1; l < nlin; ++l)
         if (cfg->dims[l] < 1 || cfg->dims[l] > MAX_WIDTH)      // the same architectures the device engine accepts
@@ -304,7 +314,11 @@ extern "C" int pndf_cpu_create(pndf_cpu_handle* out, const pndf_config* cfg) {
     return guarded(nullptr, [&] {
         pndf_cpu_engine* h = new pndf_cpu_engine();
         h->cfg = *cfg;
-        h->encoder = cfg->dims[0] == NFEAT;
+        h->smpl = pndf_skeleton_is_smpl(cfg);
+        h->nj = cfg->num_joints;
+        h->nq = 4 * h->nj;
+        for (int j = 0; j < MAXJ; ++j) h->parent[j] = j < h->nj ? cfg->parent[j] : -1;
+        h->encoder = cfg->dims[0] == FEAT * h->nj;
         h->nlin = nlin;
         for (int l = 0; l <= nlin; ++l) h->dims[l] = cfg->dims[l];
         *out = h;
@@ -320,7 +334,7 @@ extern "C" const char* pndf_cpu_last_error(pndf_cpu_handle h) { return pndf_last
 
 extern "C" int pndf_cpu_load_weights(pndf_cpu_handle h, const float* const* tensors, const int64_t* numel, int n_tensors) {
     if (!h || !tensors || !numel) return PNDF_ERR_BAD_ARG;
-    const int want = (h->encoder ? 4 * NJ : 0) + 2 * h->nlin;
+    const int want = (h->encoder ? 4 * h->nj : 0) + 2 * h->nlin;
     if (n_tensors != want) return pndf_fail(h, PNDF_ERR_BAD_SHAPE, "tensor count: " + std::to_string(n_tensors) + ", expected " + std::to_string(want));
     h->have_weights = false;      // a failed load leaves no half-loaded engine behind
     int rc = PNDF_OK;
@@ -338,8 +352,8 @@ extern "C" int pndf_cpu_load_weights(pndf_cpu_handle h, const float* const* tens
             return true;
         };
         if (h->encoder)
-            for (int j = 0; j < NJ && rc == PNDF_OK; ++j)
-                if (!take(h->enc[j][0], HID, enc_in(j)) || !take(h->enc[j][1], FEAT, HID))
+            for (int j = 0; j < h->nj && rc == PNDF_OK; ++j)
+                if (!take(h->enc[j][0], HID, h->parent[j] < 0 ? 4 : 10) || !take(h->enc[j][1], FEAT, HID))
                     rc = pndf_fail(h, PNDF_ERR_BAD_SHAPE, "encoder tensor " + std::to_string(t) + " has the wrong size");
         for (int l = 0; l < h->nlin && rc == PNDF_OK; ++l)
             if (!take(h->lin[l], h->dims[l + 1], h->dims[l]))
@@ -355,7 +369,7 @@ extern "C" int pndf_forward_cpu(pndf_cpu_handle h, const float* q, float* d, int
     if (int rc = check(h, q, B)) return rc;
     if (B > 0 && !d) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null output pointer");
     return guarded(h, [&] {
-        parallel_blocks(B, [&](int64_t p0, int nb, Scratch& S) { forward_grad_block(*h, q + p0 * NQ, nb, nullptr, d + p0, nullptr, false, S); });
+        parallel_blocks(B, [&](int64_t p0, int nb, Scratch& S) { forward_grad_block(*h, q + p0 * h->nq, nb, nullptr, d + p0, nullptr, false, S); });
     });
 }
 
@@ -365,7 +379,7 @@ extern "C" int pndf_forward_grad_cpu(pndf_cpu_handle h, const float* q, const fl
     return guarded(h, [&] {
         parallel_blocks(B, [&](int64_t p0, int nb, Scratch& S) {
             float dd[PB];
-            forward_grad_block(*h, q + p0 * NQ, nb, grad_out ? grad_out + p0 : nullptr, dd, dq + p0 * NQ, true, S);
+            forward_grad_block(*h, q + p0 * h->nq, nb, grad_out ? grad_out + p0 : nullptr, dd, dq + p0 * h->nq, true, S);
             if (d) memcpy(d + p0, dd, sizeof(float) * nb);
         });
     });
@@ -374,9 +388,10 @@ extern "C" int pndf_forward_grad_cpu(pndf_cpu_handle h, const float* q, const fl
 extern "C" int pndf_project_cpu(pndf_cpu_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps) {
     if (int rc = check(h, q_in, B)) return rc;
     if (steps < 0 || (B > 0 && !q_out)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count or null output pointer");
+    const int NQ = h->nq;
     return guarded(h, [&] {
     parallel_blocks(B, [&](int64_t p0, int nb, Scratch& S) {
-        float qb[PB * NQ], dqb[PB * NQ], dd[PB];
+        float qb[PB * 4 * MAXJ], dqb[PB * 4 * MAXJ], dd[PB];
         memcpy(qb, q_in + p0 * NQ, sizeof(float) * nb * NQ);
         for (int p = 0; p < nb; ++p) dd[p] = 0.f;
         for (int s = 0; s < steps; ++s) {
@@ -393,11 +408,15 @@ extern "C" int pndf_project_cpu(pndf_cpu_handle h, const float* q_in, float* q_o
     });
 }
 
+// completion, interpolation and the second order stay 21-joint
+static const char* const SMPL_ONLY = "this entry point runs the 21-joint table of get_parent_mapping('smpl') only; a handle of another skeleton "
+                                     "has pndf_forward_cpu, pndf_forward_grad_cpu, pndf_project_cpu and pndf_project_ex_cpu";
+
 // One step of pndf_project_ex on the host: pndf_step.h's pndf_step_quat -- the statement the device kernels run -- for every joint of
 // a pose that does not rest.  `held`: bit j = joint j is observed and stays as it is (pndf_complete_cpu; pndf_project_ex_cpu holds none).
-static void project_step_cpu(float* q, const float* dq, float d, const pndf_project_options& o, uint32_t held) {
+static void project_step_cpu(float* q, const float* dq, float d, const pndf_project_options& o, uint32_t held, int nj) {
     if (o.tol > 0.f && d < o.tol) return;
-    for (int j = 0; j < NJ; ++j) {
+    for (int j = 0; j < nj; ++j) {
         if ((held >> j) & 1u) continue;
         float u[4];
         (void)pndf_step_quat(q + 4 * j, dq + 4 * j, d, o.step_size, o.tol, (int)o.renorm, u);
@@ -409,14 +428,15 @@ static void project_step_cpu(float* q, const float* dq, float d, const pndf_proj
 // block; `observed` null = no joint held.
 static int project_loop_cpu(pndf_cpu_handle h, const float* q_in, const uint32_t* observed, float* q_out, float* d_last, int64_t B,
                             int steps, const pndf_project_options& o) {
+    const int NQ = h->nq;
     return guarded(h, [&] {
     parallel_blocks(B, [&](int64_t p0, int nb, Scratch& S) {
-        float qb[PB * NQ], dqb[PB * NQ], dd[PB];
+        float qb[PB * 4 * MAXJ], dqb[PB * 4 * MAXJ], dd[PB];
         memcpy(qb, q_in + p0 * NQ, sizeof(float) * nb * NQ);
         for (int p = 0; p < nb; ++p) dd[p] = 0.f;
         for (int s = 0; s < steps; ++s) {
             forward_grad_block(*h, qb, nb, nullptr, dd, dqb, true, S);
-            for (int p = 0; p < nb; ++p) project_step_cpu(qb + p * NQ, dqb + p * NQ, dd[p], o, observed ? observed[p0 + p] : 0u);
+            for (int p = 0; p < nb; ++p) project_step_cpu(qb + p * NQ, dqb + p * NQ, dd[p], o, observed ? observed[p0 + p] : 0u, h->nj);
         }
         memcpy(q_out + p0 * NQ, qb, sizeof(float) * nb * NQ);
         if (d_last) memcpy(d_last + p0, dd, sizeof(float) * nb);
@@ -441,6 +461,7 @@ extern "C" int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* 
 extern "C" int pndf_complete_cpu(pndf_cpu_handle h, const float* q_in, const uint32_t* observed, float* q_out, float* d_last,
                                  int64_t B, int steps, const pndf_project_options* opt) {
     if (!h) return PNDF_ERR_BAD_ARG;
+    if (!h->smpl) return pndf_fail(h, PNDF_ERR_UNSUPPORTED, SMPL_ONLY);
     pndf_project_options o;
     if (const char* why = pndf_check_project_options(opt, o)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (int rc = check(h, q_in, B)) return rc;
@@ -458,6 +479,7 @@ extern "C" int pndf_interpolate_cpu(pndf_cpu_handle h, const float* a, const flo
                                     float* d_last, int64_t P, int32_t T, int32_t mode, int steps, float lambda,
                                     const pndf_project_options* opt) {
     if (!h) return PNDF_ERR_BAD_ARG;
+    if (!h->smpl) return pndf_fail(h, PNDF_ERR_UNSUPPORTED, SMPL_ONLY);
     pndf_project_options o;
     if (const char* why = pndf_check_project_options(opt, o)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (const char* why = pndf_interp_check_mode(mode)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
@@ -688,6 +710,7 @@ void second_order_pose(const pndf_cpu_engine& E, const float* q, const float* v,
 extern "C" int pndf_second_order_cpu(pndf_cpu_handle h, const float* q, const float* v, const float* w_d, const float* w_t, float* d,
                                      float* g, float* t, float* out, int64_t B) {
     if (!h) return PNDF_ERR_BAD_ARG;
+    if (!h->smpl) return pndf_fail(h, PNDF_ERR_UNSUPPORTED, SMPL_ONLY);
     if (!h->encoder)
         return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "the second order needs the structure encoder (model.StrEnc.use: True, dims[0] = 126)");
     if (int rc = check(h, q, B)) return rc;

@@ -1,0 +1,521 @@
+// Distance, gradient and projection for any joint tree on gfx950 (include/posendf_amd_skeleton.h): the
+// first-order path of model/posendf.py:62-76 / experiments/sample_poses.py:67-74 with the skeleton as a run-time value -- up to 32
+// joints, every parent before its child, any number of roots.  The fused and runtime-planned persistent kernels keep the 21-joint
+// table (their MFMA encoder indexes registers by a compile-time parent); this unit is assembled layer by layer, in the style of
+// csrc/pndf_second_order.hip, from the shared pieces:
+//   pndf_gemm.h   the 128 x 128 exact-fp32 MFMA GEMM, its bias + sigma epilogue that keeps sigma', its * sigma' epilogue
+//   pndf_bone.h   one bone MLP (bone_load / bone_fwd / bone_dual_rev without the primal chain / bone_input_adj), norm_x
+//   pndf_step.h   the projection step of one joint quaternion
+// Here: the two encoder kernels with the joint count and the parent table as kernel arguments, the plan, the launch sequence.
+//
+// Over a chunk of SK_CHUNK poses, every activation matrix [features][columns] (the pose index contiguous) in the caller's workspace:
+//   pndf_skel_enc_fwd_kernel   lanes own poses: x = normalize(q, dim=1), the bones in index order (a uniform branch on the
+//                              parent selects the 4- or 10-input bone), features and sigma' of both bone layers stored
+//   trunk forward              L NN GEMMs, epilogue bias + sigma, sigma' kept
+//   trunk reverse              L TN GEMMs, epilogue * sigma'
+//   pndf_skel_enc_rev_kernel   lanes own poses: joints nj-1 .. 0 (children before parents), rows 4..9 of a bone's input adjoint
+//                              added to the parent's feature adjoint, the reverse of the normalisation, grad_out; in project mode
+//                              the step of pndf_step.h in the same kernel
+// 2 + 2 L launches per evaluation.  No float atomics, no communication between workgroups, every column of a GEMM summed in the
+// same order wherever it sits: the same inputs give the same bits and a pose's result does not depend on its batch.
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/posendf_amd_skeleton.h"
+#include "pndf_experiment.h"
+#include "pndf_bone.h"
+#include "pndf_host.h"
+#include "pndf_project_opts.h"
+#include "pndf_skel_plan.h"
+#include "pndf_step.h"
+
+PNDF_EXPORT_EXPERIMENT_WORD(skeleton)
+
+namespace {
+
+// Poses per pass over the layers: a constant, so the chunk seams depend on B only (the value of the second order's SO_CHUNK,
+// whose sweep found two workgroups per compute unit on every layer worth more than a chunk inside the last-level cache).
+constexpr int64_t SK_CHUNK = 16384;
+constexpr int MAXJ = PNDF_SKEL_MAX_JOINTS;
+
+enum { SK_FORWARD = 0, SK_GRAD = 1, SK_PROJECT = 2 };
+
+struct SkArgs {
+    const float* wenc;        // packed encoder weights
+    const float* q;           // the chunk's poses [n][4 nj]
+    const float* grad_out;    // [n] or null (ones)                            (SK_GRAD)
+    float* d_out;             // [n] or null
+    float* out;               // dq (SK_GRAD) or the stepped poses (SK_PROJECT) [n][4 nj]
+    float* X;                 // normalised poses [4 nj][ld]; without the encoder this is the trunk's input
+    float* act0;              // encoder output [6 nj][ld]
+    float* S1;                // sigma' of the bones' hidden layers [10 nj][ld]
+    float* S2;                // sigma' of the bones' output layers [6 nj][ld]
+    float* U0;                // adjoint of the trunk's input, accumulated in place [6 nj][ld] (without the encoder: g_x [4 nj][ld])
+    float* Gx;                // g_x = d d / d x [4 nj][ld]
+    const float* dist;        // the trunk's output row [ld]
+    int64_t n, ld;
+    int nj, encoder, mode;
+    int act;                  // act / beta: the encoder's
+    float beta;
+    float step_size, tol;     // SK_PROJECT
+    int renorm;
+    int parent[MAXJ];
+    int off[MAXJ];
+};
+
+// the norms of a pose's four component columns over its nj joints (pose_col_norms of pndf_bone.h with the joint count at run time)
+__device__ __forceinline__ void skel_col_norms(const float* q, int nj, float* nrm) {
+    float n2[BONE] = {0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < nj; ++j)
+#pragma unroll
+        for (int k = 0; k < BONE; ++k) n2[k] = fmaf(q[j * BONE + k], q[j * BONE + k], n2[k]);
+#pragma unroll
+    for (int k = 0; k < BONE; ++k) nrm[k] = sqrtf(n2[k]);
+}
+
+// bone j forward on column c: the parent's features are read back from act0 (a per-thread feature array indexed by a run-time
+// parent would live in scratch memory)
+template <int FIN>
+__device__ __forceinline__ void skel_fwd_bone(const SkArgs& e, int j, int64_t c) {
+    float in[FIN];
+    BoneDual b;
+    bone_load<FIN>(e.X, e.ld, e.act0, e.ld, e.parent, j, c, in);
+    bone_fwd<FIN>(e, e.wenc + e.off[j], in, b);
+#pragma unroll
+    for (int i = 0; i < HID; ++i) e.S1[(int64_t)(j * HID + i) * e.ld + c] = b.d1h[i];
+#pragma unroll
+    for (int i = 0; i < FEAT; ++i) {
+        e.act0[(int64_t)(j * FEAT + i) * e.ld + c] = b.ao[i];
+        e.S2[(int64_t)(j * FEAT + i) * e.ld + c] = b.d1o[i];
+    }
+}
+
+// bone j reverse on column c: U0 rows of j -> Gx rows of j, and (FIN = 10) added to the U0 rows of the parent
+template <int FIN>
+__device__ __forceinline__ void skel_rev_bone(const SkArgs& e, int j, int64_t c) {
+    const float* w = e.wenc + e.off[j];
+    float adb[FEAT];
+    BoneDual b;
+    BoneAdj r;
+#pragma unroll
+    for (int i = 0; i < HID; ++i) {
+        b.d1h[i] = e.S1[(int64_t)(j * HID + i) * e.ld + c];
+        b.hz[i] = 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < FEAT; ++i) {
+        b.d1o[i] = e.S2[(int64_t)(j * FEAT + i) * e.ld + c];
+        b.oz[i] = 0.f;
+        adb[i] = e.U0[(int64_t)(j * FEAT + i) * e.ld + c];
+    }
+    bone_dual_rev<FIN, false>(w, b, nullptr, adb, r);
+#pragma unroll
+    for (int m = 0; m < FIN; ++m) {
+        float s, sd;
+        bone_input_adj<FIN, false>(w, r, m, s, sd);
+        if (m < BONE) e.Gx[(int64_t)(j * BONE + m) * e.ld + c] = sd;
+        else e.U0[(int64_t)(e.parent[j] * FEAT + (m - BONE)) * e.ld + c] += sd;
+    }
+}
+
+}  // namespace
+
+extern "C" __global__ void __launch_bounds__(256) pndf_skel_gemm_nn_kernel(GemmArgs g) { gemm_body<1, 0>(g); }
+extern "C" __global__ void __launch_bounds__(256) pndf_skel_gemm_tn_kernel(GemmArgs g) { gemm_body<0, 0>(g); }
+
+// x = normalize(q, dim=1) (over the joint axis, per quaternion component) and the encoder
+extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_fwd_kernel(SkArgs e) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= e.n) return;
+    const float* q = e.q + c * (e.nj * BONE);
+    float nrm[BONE];
+    skel_col_norms(q, e.nj, nrm);
+    for (int j = 0; j < e.nj; ++j)
+#pragma unroll
+        for (int k = 0; k < BONE; ++k) e.X[(int64_t)(j * BONE + k) * e.ld + c] = norm_x(q[j * BONE + k], nrm[k]);
+    if (!e.encoder) return;
+    for (int j = 0; j < e.nj; ++j) {
+        if (e.parent[j] < 0) skel_fwd_bone<BONE>(e, j, c);
+        else skel_fwd_bone<BONE + FEAT>(e, j, c);
+    }
+}
+
+// The reverse of the encoder and of the normalisation: per component column k with s = |q_k| and x = q_k / s,
+// d d / d q = (g_x - x (x . g_x)) / s; where the norm is clamped the normalisation is linear, g_x / eps.  Then grad_out, or the step.
+extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_kernel(SkArgs e) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= e.n) return;
+    if (e.encoder)
+        for (int j = e.nj - 1; j >= 0; --j) {
+            if (e.parent[j] < 0) skel_rev_bone<BONE>(e, j, c);
+            else skel_rev_bone<BONE + FEAT>(e, j, c);
+        }
+    const int nq = e.nj * BONE;
+    const float* q = e.q + c * nq;
+    float* out = e.out + c * nq;
+    float s[BONE], b[BONE] = {0.f, 0.f, 0.f, 0.f};
+    skel_col_norms(q, e.nj, s);      // before the first store: in project mode `out` may be `q`
+    for (int j = 0; j < e.nj; ++j)
+#pragma unroll
+        for (int k = 0; k < BONE; ++k) {
+            const int64_t at = (int64_t)(j * BONE + k) * e.ld + c;
+            b[k] = fmaf(e.X[at], e.Gx[at], b[k]);
+        }
+    const float dist = e.dist[c];
+    const float go = (e.mode == SK_GRAD && e.grad_out) ? e.grad_out[c] : 1.f;
+    for (int j = 0; j < e.nj; ++j) {
+        float g[BONE];
+#pragma unroll
+        for (int k = 0; k < BONE; ++k) {
+            const int64_t at = (int64_t)(j * BONE + k) * e.ld + c;
+            const float x = e.X[at], gx = e.Gx[at];
+            g[k] = s[k] > NORM_EPS ? (gx - x * b[k]) / s[k] : gx / NORM_EPS;
+        }
+        if (e.mode == SK_PROJECT) {
+            float Q[BONE], u[BONE];
+#pragma unroll
+            for (int k = 0; k < BONE; ++k) Q[k] = q[j * BONE + k];
+            const bool rest = pndf_step_quat(Q, g, dist, e.step_size, e.tol, e.renorm, u);
+#pragma unroll
+            for (int k = 0; k < BONE; ++k) out[j * BONE + k] = rest ? Q[k] : u[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < BONE; ++k) out[j * BONE + k] = g[k] * go;
+        }
+    }
+    if (e.d_out) e.d_out[c] = dist;
+}
+
+// the forward alone ends here: the trunk's output row -> d
+extern "C" __global__ void __launch_bounds__(256) pndf_skel_copy_kernel(const float* src, float* dst, int64_t n) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < n) dst[c] = src[c];
+}
+
+// ------------------------------------------------------------------------------------------------------------ host side
+struct pndf_skel_plan {
+    int device = 0;
+    int nj = 0, L = 0;
+    bool encoder = true, have_weights = false;
+    int dims[MAX_LIN + 1] = {};
+    int act = 0, enc_act = 0;
+    float beta = 100.f, enc_beta = 100.f;
+    int parent[MAXJ] = {};
+    int enc_off[MAXJ] = {};           // offset of bone j in the packed encoder
+    int enc_params = 0, maxw = 0;
+    std::vector<int64_t> numel;       // of every tensor pndf_skel_load_weights takes, in its order
+    int64_t w_off[MAX_LIN] = {}, b_off[MAX_LIN] = {}, blob_floats = 0;      // the device copy: the packed encoder, then W and b of every layer
+    float* d_blob = nullptr;
+    std::string err;
+};
+
+namespace {
+
+// workspace layout in floats (every region 256-byte aligned); nc: the columns of a chunk
+struct SkLayout {
+    int64_t nc;
+    int64_t X, act0, S1, S2, U0, Gx, dist, D1[MAX_LIN], P[2];
+    int64_t total;
+};
+
+SkLayout sk_layout(const pndf_skel_plan* h, int64_t B) {
+    SkLayout l{};
+    l.nc = B < SK_CHUNK ? B : SK_CHUNK;
+    int64_t o = 0;
+    auto take = [&](int64_t n) { const int64_t at = o; o += align64(n); return at; };
+    const int64_t nq = (int64_t)h->nj * BONE, nf = (int64_t)h->nj * FEAT;
+    l.X = take(nq * l.nc);
+    if (h->encoder) {
+        l.act0 = take(nf * l.nc);
+        l.S1 = take((int64_t)h->nj * HID * l.nc);
+        l.S2 = take(nf * l.nc);
+        l.U0 = take(nf * l.nc);
+        l.Gx = take(nq * l.nc);
+    } else {      // the trunk reads x and its reverse ends in g_x
+        l.act0 = l.X;
+        l.S1 = l.S2 = -1;
+        l.U0 = l.Gx = take(nq * l.nc);
+    }
+    l.dist = take(l.nc);
+    for (int t = 0; t < h->L; ++t) l.D1[t] = take((int64_t)h->dims[t + 1] * l.nc);
+    l.P[0] = take((int64_t)h->maxw * l.nc);
+    l.P[1] = take((int64_t)h->maxw * l.nc);
+    l.total = o;
+    return l;
+}
+
+enum { SK_GEMM_NN, SK_GEMM_TN };
+void sk_launch_gemm(int kind, const GemmArgs& g, hipStream_t st) {
+    const dim3 grid((g.N + TN - 1) / TN, (g.M + TM - 1) / TM, 1);
+    if (kind == SK_GEMM_NN) hipLaunchKernelGGL(pndf_skel_gemm_nn_kernel, grid, dim3(256), 0, st, g);
+    else hipLaunchKernelGGL(pndf_skel_gemm_tn_kernel, grid, dim3(256), 0, st, g);
+}
+
+bool sk_overlaps(const float* a, const float* b, int64_t floats) {
+    return a && b && (uintptr_t)a < (uintptr_t)(b + floats) && (uintptr_t)b < (uintptr_t)(a + floats);
+}
+
+// One evaluation of a chunk of n poses at `q`: the 2 + 2 L launches (the forward alone: 1 + L and the copy of the output row)
+void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, SkArgs e, hipStream_t st) {
+    const int L = h->L;
+    const int n = (int)e.n;
+    const int64_t ld = l.nc;
+    hipLaunchKernelGGL(pndf_skel_enc_fwd_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
+    // forward: layer t reads act0 / P[(t-1)&1] and writes P[t&1]; the output row goes to `dist`
+    for (int t = 0; t < L; ++t) {
+        GemmArgs a = gemm_args(h->d_blob + h->w_off[t], h->dims[t], t == 0 ? ws + l.act0 : ws + l.P[(t - 1) & 1], ld,
+                               t == L - 1 ? ws + l.dist : ws + l.P[t & 1], ld, h->dims[t + 1], n, h->dims[t]);
+        a.epi = EPI_FWD; a.act = h->act; a.beta = h->beta; a.out_layer = t == L - 1; a.bias = h->d_blob + h->b_off[t];
+        a.D1 = ws + l.D1[t]; a.ld1 = ld;
+        sk_launch_gemm(SK_GEMM_NN, a, st);
+    }
+    if (e.mode == SK_FORWARD) {
+        hipLaunchKernelGGL(pndf_skel_copy_kernel, dim3(blocks(n)), dim3(256), 0, st, ws + l.dist, e.d_out, (int64_t)n);
+        return;
+    }
+    // reverse from sigma' of the output (the seed 1; grad_out scales the result): layer t's input adjoint, * sigma' of layer t-1
+    const float* U = ws + l.D1[L - 1];
+    for (int t = L - 1; t >= 0; --t) {
+        float* o = t == 0 ? ws + l.U0 : ws + l.P[t & 1];
+        GemmArgs a = gemm_args(h->d_blob + h->w_off[t], h->dims[t], U, ld, o, ld, h->dims[t], n, h->dims[t + 1]);
+        a.epi = EPI_MUL;
+        if (t > 0) { a.D1 = ws + l.D1[t - 1]; a.ld1 = ld; }
+        sk_launch_gemm(SK_GEMM_TN, a, st);
+        U = o;
+    }
+    hipLaunchKernelGGL(pndf_skel_enc_rev_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
+}
+
+SkArgs sk_args(const pndf_skel_plan* h, const SkLayout& l, float* ws, int mode) {
+    SkArgs e;
+    memset(&e, 0, sizeof(e));
+    e.wenc = h->d_blob;
+    e.X = ws + l.X; e.act0 = ws + l.act0; e.U0 = ws + l.U0; e.Gx = ws + l.Gx; e.dist = ws + l.dist;
+    if (h->encoder) { e.S1 = ws + l.S1; e.S2 = ws + l.S2; }
+    e.ld = l.nc;
+    e.nj = h->nj; e.encoder = h->encoder ? 1 : 0; e.mode = mode;
+    e.act = h->enc_act; e.beta = h->enc_beta;
+    e.step_size = 1.f;
+    for (int j = 0; j < h->nj; ++j) { e.parent[j] = h->parent[j]; e.off[j] = h->enc_off[j]; }
+    return e;
+}
+
+// what the three compute calls check alike; PNDF_OK with *go = false: nothing to do
+int sk_check(pndf_skel_plan* h, int64_t B, const void* workspace, int64_t workspace_bytes, SkLayout& l, bool* go) {
+    *go = false;
+    if (B < 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative batch");
+    if (!h->have_weights) return pndf_fail(h, PNDF_ERR_NO_WEIGHTS, "pndf_skel_load_weights has not been called");
+    if (B == 0) return PNDF_OK;
+    if (!workspace) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null workspace");
+    if (((uintptr_t)workspace & 15) != 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "workspace must be 16-byte aligned");
+    l = sk_layout(h, B);
+    const int64_t need = l.total * (int64_t)sizeof(float);
+    if (workspace_bytes < need)
+        return pndf_fail(h, PNDF_ERR_BAD_ARG, "workspace of " + std::to_string(workspace_bytes) + " bytes, pndf_skel_workspace_bytes asks for " + std::to_string(need));
+    *go = true;
+    return PNDF_OK;
+}
+
+}  // namespace
+
+extern "C" const char* pndf_skel_last_error(pndf_skel_handle h) { return pndf_last_error_of(h); }
+
+extern "C" int pndf_skel_create(pndf_skel_handle* out, const pndf_config* cfg, int device) {
+    auto refuse = [](int code, const std::string& why) { return pndf_fail<pndf_skel_plan>(nullptr, code, why); };
+    if (!out || !cfg) return refuse(PNDF_ERR_BAD_ARG, "out / cfg is null");
+    *out = nullptr;
+    if (const char* why = pndf_skeleton_refusal(cfg)) return refuse(PNDF_ERR_UNSUPPORTED, why);
+    if (cfg->n_dims < 3 || cfg->n_dims > MAX_LIN + 1 || cfg->dims[cfg->n_dims - 1] != 1)
+        return refuse(PNDF_ERR_UNSUPPORTED, "n_dims / dims: 1 .. 7 hidden layers and one output");
+    for (int i = 1; i < cfg->n_dims - 1; ++i)
+        if (cfg->dims[i] < 1 || cfg->dims[i] > 1024) return refuse(PNDF_ERR_UNSUPPORTED, "dims: hidden widths 1 .. 1024");
+    if (cfg->act < PNDF_ACT_RELU || cfg->act > PNDF_ACT_SOFTPLUS) return refuse(PNDF_ERR_UNSUPPORTED, "act: relu, lrelu or softplus");
+    if (cfg->enc_act < -1 || cfg->enc_act > PNDF_ACT_SOFTPLUS) return refuse(PNDF_ERR_UNSUPPORTED, "enc_act: relu, lrelu, softplus or -1 (the trunk's)");
+    if (cfg->precision != PNDF_PREC_FP32) return refuse(PNDF_ERR_UNSUPPORTED, "precision: this unit runs exact fp32 (PNDF_PREC_FP32) only");
+    if (cfg->act == PNDF_ACT_SOFTPLUS && !(cfg->beta > 0.f)) return refuse(PNDF_ERR_UNSUPPORTED, "beta: Softplus beta must be positive");
+    if ((cfg->enc_act >= 0 ? cfg->enc_act : cfg->act) == PNDF_ACT_SOFTPLUS && !(cfg->enc_beta > 0.f) && !(cfg->beta > 0.f))
+        return refuse(PNDF_ERR_UNSUPPORTED, "enc_beta: Softplus beta of the encoder must be positive");
+    const PndfDeviceCheck dev = pndf_check_gfx950(device, "the skeleton unit");
+    if (dev.code != PNDF_OK) return refuse(dev.code, dev.text);
+    pndf_skel_plan* h = new pndf_skel_plan();
+    h->device = device;
+    h->nj = cfg->num_joints;
+    h->L = cfg->n_dims - 1;
+    h->encoder = cfg->dims[0] == FEAT * h->nj;
+    for (int t = 0; t <= h->L; ++t) {
+        h->dims[t] = cfg->dims[t];
+        if (cfg->dims[t] > h->maxw) h->maxw = cfg->dims[t];
+    }
+    h->act = cfg->act;
+    h->beta = cfg->beta;
+    h->enc_act = cfg->enc_act >= 0 ? cfg->enc_act : cfg->act;              // as layer_net_init (pndf_bone.h) reads them
+    h->enc_beta = cfg->enc_beta > 0.f ? cfg->enc_beta : cfg->beta;
+    int64_t o = 0;
+    for (int j = 0; j < h->nj; ++j) {
+        h->parent[j] = cfg->parent[j];
+        h->enc_off[j] = (int)o;
+        if (!h->encoder) continue;
+        int sizes[4];
+        pndf_skeleton_bone_sizes(pndf_skeleton_fin(cfg, j), sizes);
+        for (int s = 0; s < 4; ++s) {
+            h->numel.push_back(sizes[s]);
+            o += sizes[s];
+        }
+    }
+    h->enc_params = (int)o;
+    o = align64(o);
+    for (int t = 0; t < h->L; ++t) {
+        h->w_off[t] = o;
+        o += align64((int64_t)h->dims[t + 1] * h->dims[t]);
+        h->b_off[t] = o;
+        o += align64(h->dims[t + 1]);
+        h->numel.push_back((int64_t)h->dims[t + 1] * h->dims[t]);
+        h->numel.push_back(h->dims[t + 1]);
+    }
+    h->blob_floats = o;
+    DeviceGuard guard(device);
+    const hipError_t e = guard.ok ? hipMalloc((void**)&h->d_blob, (size_t)o * sizeof(float)) : hipErrorInvalidDevice;
+    if (e != hipSuccess) {
+        delete h;
+        (void)hipGetLastError();
+        return refuse(PNDF_ERR_HIP, std::string("hipMalloc of the weights: ") + hipGetErrorString(e));
+    }
+    *out = h;
+    return PNDF_OK;
+}
+
+extern "C" int pndf_skel_destroy(pndf_skel_handle h) {
+    if (!h) return PNDF_OK;
+    if (h->d_blob) {
+        DeviceGuard guard(h->device);
+        (void)hipFree(h->d_blob);
+    }
+    delete h;
+    return PNDF_OK;
+}
+
+extern "C" int pndf_skel_load_weights(pndf_skel_handle h, const float* const* tensors, const int64_t* numel, int n_tensors) {
+    if (!h) return PNDF_ERR_BAD_ARG;
+    if (!tensors || !numel) return pndf_fail(h, PNDF_ERR_BAD_ARG, "tensors / numel is null");
+    if (n_tensors != (int)h->numel.size())
+        return pndf_fail(h, PNDF_ERR_BAD_SHAPE, "tensor count: " + std::to_string(n_tensors) + ", expected " + std::to_string(h->numel.size()));
+    for (int i = 0; i < n_tensors; ++i) {
+        if (!tensors[i]) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null tensor " + std::to_string(i));
+        if (numel[i] != h->numel[i])
+            return pndf_fail(h, PNDF_ERR_BAD_SHAPE, "tensor " + std::to_string(i) + " has " + std::to_string(numel[i]) + " elements, expected " + std::to_string(h->numel[i]));
+    }
+    h->have_weights = false;      // a failed load leaves no half-loaded plan behind
+    std::vector<float> blob((size_t)h->blob_floats, 0.f);
+    int i = 0;
+    int64_t o = 0;
+    for (; i < (h->encoder ? 4 * h->nj : 0); ++i) {      // the packed encoder: the tensors one after the other
+        memcpy(blob.data() + o, tensors[i], sizeof(float) * (size_t)numel[i]);
+        o += numel[i];
+    }
+    for (int t = 0; t < h->L; ++t, i += 2) {
+        memcpy(blob.data() + h->w_off[t], tensors[i], sizeof(float) * (size_t)numel[i]);
+        memcpy(blob.data() + h->b_off[t], tensors[i + 1], sizeof(float) * (size_t)numel[i + 1]);
+    }
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
+    HIP_TRY(h, hipDeviceSynchronize());      // launches that still read the previous weights
+    HIP_TRY(h, hipMemcpy(h->d_blob, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice));
+    h->have_weights = true;
+    return PNDF_OK;
+}
+
+extern "C" int64_t pndf_skel_workspace_bytes(pndf_skel_handle h, int64_t B) {
+    if (!h || B < 0) return PNDF_ERR_BAD_ARG;
+    return B == 0 ? 0 : sk_layout(h, B).total * (int64_t)sizeof(float);
+}
+
+extern "C" int pndf_skel_forward(pndf_skel_handle h, const float* q, float* d, int64_t B, void* workspace, int64_t workspace_bytes,
+                                 void* stream) {
+    if (!h) return PNDF_ERR_BAD_ARG;
+    SkLayout l;
+    bool go;
+    if (B > 0 && (!q || !d)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose / distance pointer");
+    if (((uintptr_t)q | (uintptr_t)d) & 3) return pndf_fail(h, PNDF_ERR_BAD_ARG, "misaligned pose or distance buffer");
+    if (const int rc = sk_check(h, B, workspace, workspace_bytes, l, &go); rc != PNDF_OK || !go) return rc;
+    PndfRange range("pndf_skel_forward");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
+    float* ws = (float*)workspace;
+    SkArgs e = sk_args(h, l, ws, SK_FORWARD);
+    for (int64_t c0 = 0; c0 < B; c0 += l.nc) {
+        e.n = B - c0 < l.nc ? B - c0 : l.nc;
+        e.q = q + c0 * h->nj * BONE;
+        e.d_out = d + c0;
+        sk_run_chunk(h, l, ws, e, (hipStream_t)stream);
+    }
+    return pndf_check_launch(h, "pndf_skel_forward");
+}
+
+extern "C" int pndf_skel_forward_grad(pndf_skel_handle h, const float* q, const float* grad_out, float* d, float* dq, int64_t B,
+                                      void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!h) return PNDF_ERR_BAD_ARG;
+    SkLayout l;
+    bool go;
+    if (B > 0 && (!q || !dq)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose / gradient pointer");
+    if (((uintptr_t)q | (uintptr_t)grad_out | (uintptr_t)d | (uintptr_t)dq) & 3)
+        return pndf_fail(h, PNDF_ERR_BAD_ARG, "misaligned pose, grad_out, distance or gradient buffer");
+    if (B > 0 && sk_overlaps(q, dq, B * h->nj * BONE)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "dq must not overlap q");
+    if (const int rc = sk_check(h, B, workspace, workspace_bytes, l, &go); rc != PNDF_OK || !go) return rc;
+    PndfRange range("pndf_skel_forward_grad");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
+    float* ws = (float*)workspace;
+    SkArgs e = sk_args(h, l, ws, SK_GRAD);
+    for (int64_t c0 = 0; c0 < B; c0 += l.nc) {
+        e.n = B - c0 < l.nc ? B - c0 : l.nc;
+        e.q = q + c0 * h->nj * BONE;
+        e.grad_out = grad_out ? grad_out + c0 : nullptr;
+        e.d_out = d ? d + c0 : nullptr;
+        e.out = dq + c0 * h->nj * BONE;
+        sk_run_chunk(h, l, ws, e, (hipStream_t)stream);
+    }
+    return pndf_check_launch(h, "pndf_skel_forward_grad");
+}
+
+extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps,
+                                 const pndf_project_options* opt, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!h) return PNDF_ERR_BAD_ARG;
+    pndf_project_options o;
+    if (const char* why = pndf_check_project_options(opt, o)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (steps < 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count");
+    SkLayout l;
+    bool go;
+    if (B > 0 && (!q_in || !q_out)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose pointer");
+    if (((uintptr_t)q_in | (uintptr_t)q_out | (uintptr_t)d_last) & 3) return pndf_fail(h, PNDF_ERR_BAD_ARG, "misaligned pose or distance buffer");
+    if (B > 0 && q_in != q_out && sk_overlaps(q_in, q_out, B * h->nj * BONE))
+        return pndf_fail(h, PNDF_ERR_BAD_ARG, "q_out may be q_in itself, but must not overlap it otherwise");
+    if (const int rc = sk_check(h, B, workspace, workspace_bytes, l, &go); rc != PNDF_OK || !go) return rc;
+    PndfRange range("pndf_skel_project");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t nq = (int64_t)h->nj * BONE;
+    if (steps == 0) {
+        if (q_in != q_out) HIP_TRY(h, hipMemcpyAsync(q_out, q_in, sizeof(float) * (size_t)(B * nq), hipMemcpyDeviceToDevice, st));
+        if (d_last) HIP_TRY(h, hipMemsetAsync(d_last, 0, sizeof(float) * (size_t)B, st));
+        return PNDF_OK;
+    }
+    float* ws = (float*)workspace;
+    SkArgs e = sk_args(h, l, ws, SK_PROJECT);
+    e.step_size = o.step_size; e.tol = o.tol; e.renorm = (int)o.renorm;
+    for (int64_t c0 = 0; c0 < B; c0 += l.nc) {
+        e.n = B - c0 < l.nc ? B - c0 : l.nc;
+        e.out = q_out + c0 * nq;
+        for (int s = 0; s < steps; ++s) {      // from the second step on the iterate is in q_out: a lane reads its pose before it writes it
+            e.q = s == 0 ? q_in + c0 * nq : q_out + c0 * nq;
+            e.d_out = (d_last && s == steps - 1) ? d_last + c0 : nullptr;
+            sk_run_chunk(h, l, ws, e, st);
+        }
+    }
+    return pndf_check_launch(h, "pndf_skel_project");
+}

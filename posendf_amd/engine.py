@@ -66,9 +66,9 @@ class PndfError(RuntimeError):
 
 
 # ---- the C ABI, one table per header: name -> (restype, argtypes), in the header's order.  load_library() binds the tables, EXPORTS /
-# COMPLETION_EXPORTS / INTERPOLATION_EXPORTS / SECOND_ORDER_EXPORTS / ONLINE_EXPORTS / DEBUG_EXPORTS are their names, tests/test_cabi.py,
-# tests/test_completion.py, tests/test_interpolation.py, tests/test_second_order.py and tests/test_online.py hold them against the
-# declarations of the headers.
+# COMPLETION_EXPORTS / INTERPOLATION_EXPORTS / SECOND_ORDER_EXPORTS / ONLINE_EXPORTS / SKELETON_EXPORTS / DEBUG_EXPORTS are their names,
+# tests/test_cabi.py, tests/test_completion.py, tests/test_interpolation.py, tests/test_second_order.py, tests/test_online.py and
+# tests/test_skeleton.py hold them against the declarations of the headers.
 _H = c_void_p                          # every handle type, and every `void* stream`
 _P = c_void_p                          # any other address: tensor data (an int from data_ptr(), or None), a callback, an out value
 _TENSORS = [POINTER(c_void_p), POINTER(c_int64), c_int]      # tensors, numel, n_tensors (host pointers in state-dict order)
@@ -183,15 +183,26 @@ _ONLINE_SIGNATURES = {      # include/posendf_amd_online.h: the sampler of onlin
     "pndf_online_sample": (c_int, [_P, c_int64, c_int64, c_int64, POINTER(OnlineOpts), _P, _P, _P, _H]),
     "pndf_online_sample_cpu": (c_int, [_P, c_int64, c_int64, c_int64, POINTER(OnlineOpts), _P, _P, _P]),
 }
+_SKELETON_SIGNATURES = {      # include/posendf_amd_skeleton.h: distance, gradient and projection for any joint tree, the fifth companion header
+    "pndf_skel_create": (c_int, [POINTER(_H), POINTER(PndfConfig), c_int]),
+    "pndf_skel_destroy": (c_int, [_H]),
+    "pndf_skel_load_weights": (c_int, [_H] + _TENSORS),
+    "pndf_skel_workspace_bytes": (c_int64, [_H, c_int64]),
+    "pndf_skel_forward": (c_int, [_H, _P, _P, c_int64, _P, c_int64, _H]),
+    "pndf_skel_forward_grad": (c_int, [_H, _P, _P, _P, _P, c_int64, _P, c_int64, _H]),
+    "pndf_skel_project": (c_int, [_H, _P, _P, _P, c_int64, c_int, POINTER(ProjectOptions), _P, c_int64, _H]),
+    "pndf_skel_last_error": (c_char_p, [_H]),
+}
 EXPORTS, DEBUG_EXPORTS = tuple(_SIGNATURES), tuple(_DEBUG_SIGNATURES)
 COMPLETION_EXPORTS = tuple(_COMPLETION_SIGNATURES)
 INTERPOLATION_EXPORTS = tuple(_INTERPOLATION_SIGNATURES)
 SECOND_ORDER_EXPORTS = tuple(_SECOND_ORDER_SIGNATURES)
 ONLINE_EXPORTS = tuple(_ONLINE_SIGNATURES)
+SKELETON_EXPORTS = tuple(_SKELETON_SIGNATURES)
 # per-translation-unit experiment words (csrc/pndf_experiment.h): data symbols, all zero in a product build
 EXPERIMENT_WORDS = ("pndf_experiment_word_capi", "pndf_experiment_word_fp32", "pndf_experiment_word_split", "pndf_experiment_word_split_x2",
                     "pndf_experiment_word_bf16", "pndf_experiment_word_lbs", "pndf_experiment_word_generic", "pndf_experiment_word_train",
-                    "pndf_experiment_word_optim", "pndf_experiment_word_second_order")
+                    "pndf_experiment_word_optim", "pndf_experiment_word_second_order", "pndf_experiment_word_skeleton")
 DEBUG_EXPERIMENT_WORDS = ("pndf_experiment_word_debug", "pndf_experiment_word_fp32_timing", "pndf_experiment_word_split_timing",
                           "pndf_experiment_word_fp32_dbg", "pndf_experiment_word_probe")
 
@@ -242,7 +253,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         raise PndfError(f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                         "(hipcc --offload-arch=gfx950). The engine has no fallback path.")
     lib = _bind(_bind(_bind(_PndfLibrary(path), _SIGNATURES), _COMPLETION_SIGNATURES), _INTERPOLATION_SIGNATURES)
-    return _bind(_bind(lib, _SECOND_ORDER_SIGNATURES), _ONLINE_SIGNATURES)
+    return _bind(_bind(_bind(lib, _SECOND_ORDER_SIGNATURES), _ONLINE_SIGNATURES), _SKELETON_SIGNATURES)
 
 
 def experiment_word(lib=None) -> int:
@@ -270,18 +281,20 @@ def _device_only(device, what):
         raise PndfError(f"{what} runs on the HIP kernel only: tensors on {device}")
 
 
-def state_dict_order(encoder: bool = True, n_lin: int = 7):
+def state_dict_order(encoder: bool = True, n_lin: int = 7, parents=None):
     """Keys in the order pndf_load_weights expects (== reference state_dict order): the 84 encoder tensors (with the
     structure encoder; without it -- model.StrEnc.use = False, in_dim 84 -- none), then weight and bias of every
-    dfnet.lin{l}: 98 / 14 tensors for configs/amass.yaml's seven linear layers."""
-    from .synth import DFNET_DIMS, DFNET_DIMS_NOENC, state_dict_shapes
-    first = (DFNET_DIMS if encoder else DFNET_DIMS_NOENC)[0]
-    return list(state_dict_shapes((first,) + (1,) * n_lin).keys())
+    dfnet.lin{l}: 98 / 14 tensors for configs/amass.yaml's seven linear layers.  `parents`: another skeleton's parent table
+    (four encoder tensors per joint); None = the SMPL table."""
+    from .synth import BONE_DIM, FEAT, PARENT, state_dict_shapes
+    parents = PARENT if parents is None else tuple(parents)
+    first = len(parents) * (FEAT if encoder else BONE_DIM)
+    return list(state_dict_shapes((first,) + (1,) * n_lin, parents=parents).keys())
 
 
-def _tensor_table(sd_np):
+def _tensor_table(sd_np, parents=None):
     n_lin = sum(1 for k in sd_np if k.startswith("dfnet.lin") and k.endswith(".weight"))
-    keys = state_dict_order(encoder=any(k.startswith("enc.") for k in sd_np), n_lin=n_lin)
+    keys = state_dict_order(encoder=any(k.startswith("enc.") for k in sd_np), n_lin=n_lin, parents=parents)
     arrs = [np.ascontiguousarray(np.asarray(sd_np[k], dtype=np.float32)) for k in keys]
     ptrs = (c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
     numel = (c_int64 * len(arrs))(*[a.size for a in arrs])
@@ -342,9 +355,10 @@ def _set_encoder_act(cfg, act, beta, enc_act, enc_beta):
         cfg.enc_beta = float(enc_beta if enc_beta is not None else beta)
 
 
-def _network_config(lib, act, beta, *, precision=None, encoder=True, hidden=None, enc_act=None, enc_beta=None) -> PndfConfig:
+def _network_config(lib, act, beta, *, precision=None, encoder=True, hidden=None, enc_act=None, enc_beta=None, parents=None) -> PndfConfig:
     """The pndf_config of a network: configs/amass.yaml's architecture (pndf_default_config) with the activation pair, the trunk's
-    arithmetic, the encoder-less input and model.DFNet.dims of the caller."""
+    arithmetic, the encoder-less input and model.DFNet.dims of the caller.  `parents`: the parent table of another skeleton (1 .. 32
+    joints, -1 = a root; pndf_skel_create and the first-order host twins take it, the values are checked by the library); None = SMPL."""
     if act not in ACT_CODES:
         raise PndfError(f"unknown activation {act!r}")
     if precision is not None and precision not in PRECISION_CODES:
@@ -354,8 +368,16 @@ def _network_config(lib, act, beta, *, precision=None, encoder=True, hidden=None
     if precision is not None:
         cfg.precision = PRECISION_CODES[precision]
     _set_encoder_act(cfg, act, beta, enc_act, enc_beta)
+    if parents is not None:
+        parents = [int(p) for p in parents]
+        if len(parents) > len(cfg.parent):
+            raise PndfError(f"a skeleton of {len(parents)} joints: pndf_config.parent holds {len(cfg.parent)}")
+        cfg.num_joints = len(parents)
+        for j in range(len(cfg.parent)):
+            cfg.parent[j] = parents[j] if j < len(parents) else 0
+        cfg.dims[0] = 6 * len(parents)
     if not encoder:
-        cfg.dims[0] = 84          # model.StrEnc.use = False: DFNet on the 21 x 4 normalised quaternions
+        cfg.dims[0] = 4 * cfg.num_joints      # model.StrEnc.use = False: DFNet on the J x 4 normalised quaternions (84 for SMPL)
     if hidden is not None:
         # model.DFNet.dims (reference net_modules.py:14-28: a free list).  Six hidden widths within configs/amass.yaml's run on
         # the fused kernels (narrower ones zero padded); any other list of 1 .. 7 widths up to 1024 on the runtime-planned
@@ -608,6 +630,49 @@ class SecondOrderEngine(_Handle):
                                                ws_ptr, int(ws_floats), stream), "pndf_second_order")
 
 
+class SkeletonEngine(_Handle):
+    """`pndf_skel_*` (csrc/pndf_skeleton.hip): distance, gradient and projection for the joint tree `parents` (1 .. 32 joints, -1 = a
+    root, every parent before its child; None = SMPL) on one device, layer by layer in exact fp32.  Raw device pointers, a workspace
+    of `workspace_bytes(B)` bytes from the caller and a stream handle."""
+    _destroy, _last_error = "pndf_skel_destroy", "pndf_skel_last_error"
+
+    def __init__(self, parents=None, act: str = "lrelu", beta: float = 100.0, device: int = 0, lib=None, encoder: bool = True, hidden=None,
+                 enc_act: str | None = None, enc_beta: float | None = None):
+        self.lib = lib or load_library()
+        cfg = _network_config(self.lib, act, beta, encoder=encoder, hidden=hidden, enc_act=enc_act, enc_beta=enc_beta, parents=parents)
+        self.parents = None if parents is None else tuple(int(p) for p in parents)
+        self.num_joints = int(cfg.num_joints)
+        self.precision = "fp32"
+        self._create("pndf_skel_create", ctypes.byref(cfg), int(device))
+        self.device = device
+        self.act = act
+
+    def load_weights(self, sd_np):
+        arrs, ptrs, numel = _tensor_table(sd_np, self.parents)
+        self._check(self.lib.pndf_skel_load_weights(self.handle, ptrs, numel, len(arrs)), "pndf_skel_load_weights")
+
+    def kernel_name(self) -> str:
+        return "pndf_skel_enc_fwd_kernel"
+
+    def workspace_bytes(self, B) -> int:
+        n = int(self.lib.pndf_skel_workspace_bytes(self.handle, int(B)))
+        if n < 0:
+            raise PndfError(f"pndf_skel_workspace_bytes failed ({n}): B = {B}")
+        return n
+
+    def forward(self, q_ptr, d_ptr, B, ws_ptr, ws_bytes, stream=0):
+        self._check(self.lib.pndf_skel_forward(self.handle, q_ptr, d_ptr, int(B), ws_ptr, int(ws_bytes), stream), "pndf_skel_forward")
+
+    def forward_grad(self, q_ptr, gout_ptr, d_ptr, dq_ptr, B, ws_ptr, ws_bytes, stream=0):
+        """gout_ptr None = ones; d_ptr may be None"""
+        self._check(self.lib.pndf_skel_forward_grad(self.handle, q_ptr, gout_ptr, d_ptr, dq_ptr, int(B), ws_ptr, int(ws_bytes), stream),
+                    "pndf_skel_forward_grad")
+
+    def project(self, q_in_ptr, q_out_ptr, d_ptr, B, steps, ws_ptr, ws_bytes, stream=0, *, step_size=1.0, renorm="none", tol=0.0):
+        self._check(self.lib.pndf_skel_project(self.handle, q_in_ptr, q_out_ptr, d_ptr, int(B), int(steps),
+                                               _opt_ref(self.lib, step_size, renorm, tol), ws_ptr, int(ws_bytes), stream), "pndf_skel_project")
+
+
 def adam_step(p_ptr, g_ptr, m_ptr, v_ptr, n, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, stream=0, lib=None):
     """`pndf_adam_step` (csrc/pndf_optim.hip): one torch.optim.Adam step over flat fp32 device buffers of n floats"""
     rc = (lib or load_library()).pndf_adam_step(p_ptr, g_ptr, m_ptr, v_ptr, int(n), int(step), float(lr), float(beta1), float(beta2),
@@ -745,16 +810,17 @@ class CpuEngine(_Handle):
     _destroy, _last_error = "pndf_cpu_destroy", "pndf_cpu_last_error"
 
     def __init__(self, act: str = "lrelu", beta: float = 100.0, lib=None, encoder: bool = True, hidden=None,
-                 enc_act: str | None = None, enc_beta: float | None = None):
+                 enc_act: str | None = None, enc_beta: float | None = None, parents=None):
         self.lib = lib or load_library()
-        cfg = _network_config(self.lib, act, beta, encoder=encoder, hidden=hidden, enc_act=enc_act, enc_beta=enc_beta)
+        cfg = _network_config(self.lib, act, beta, encoder=encoder, hidden=hidden, enc_act=enc_act, enc_beta=enc_beta, parents=parents)
         self.precision = "fp32"
+        self.parents = None if parents is None else tuple(int(p) for p in parents)      # another skeleton: the first-order calls only
         self._create("pndf_cpu_create", ctypes.byref(cfg))
         self.device = "cpu"
         self.act = act
 
     def load_weights(self, sd_np):
-        arrs, ptrs, numel = _tensor_table(sd_np)
+        arrs, ptrs, numel = _tensor_table(sd_np, self.parents)
         self._check(self.lib.pndf_cpu_load_weights(self.handle, ptrs, numel, len(arrs)), "pndf_cpu_load_weights")
 
     def kernel_name(self) -> str:

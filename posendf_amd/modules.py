@@ -42,11 +42,16 @@ class BoneMLP(nn.Module):
 
 
 class StructureEncoder(nn.Module):
-    """21 BoneMLPs chained along the SMPL parent table (net_modules.py:114-170)."""
+    """One BoneMLP per joint chained along a parent table (net_modules.py:114-170): the SMPL table, 21 joints, unless the config
+    names another one under `parent_mapping` (model.StrEnc.parent_mapping, the key of the reference's own from_cfg): a list with -1
+    for a root and every parent before its child."""
 
     def __init__(self, opt):
         super().__init__()
-        self.parent_mapping = list(PARENT)
+        mapping = opt.get("parent_mapping") if hasattr(opt, "get") else None
+        self.parent_mapping = list(PARENT) if mapping is None else [int(p) for p in mapping]
+        if any(not -1 <= p < j for j, p in enumerate(self.parent_mapping)) or not self.parent_mapping:
+            raise ValueError(f"parent_mapping {self.parent_mapping}: at least one joint, -1 for a root, every parent before its child")
         self.num_joints = len(self.parent_mapping)
         self.out_dim = self.num_joints * FEAT
         self.net = nn.ModuleList(BoneMLP(p != -1, opt["act"], opt["beta"]) for p in self.parent_mapping)

@@ -23,11 +23,17 @@ DFNET_DIMS = (126, 256, 512, 1024, 512, 256, 64, 1)   # configs/amass.yaml:26,30
 DFNET_DIMS_NOENC = (84,) + DFNET_DIMS[1:]              # model.StrEnc.use = False: DFNet on the 21 x 4 quaternions
 
 
-def state_dict_shapes(dims=DFNET_DIMS):
+def skeleton_dims(parents, hidden, encoder=True):
+    """(in_dim, *hidden, 1) of a DFNet behind the skeleton `parents`: 6 features per joint with the encoder, 4 without"""
+    return (len(parents) * (FEAT if encoder else BONE_DIM), *[int(w) for w in hidden], 1)
+
+
+def state_dict_shapes(dims=DFNET_DIMS, parents=PARENT):
     """Ordered {key: shape} of the reference state dict.  dims[0] == 84 is the
-    encoder-less variant (reference model/posendf.py:40-42,73-74): 14 DFNet tensors only."""
+    encoder-less variant (reference model/posendf.py:40-42,73-74): 14 DFNet tensors only.  `parents`: the parent table of the
+    skeleton (-1 = a root; the SMPL table by default), dims[0] == 4 * len(parents) its encoder-less variant."""
     shapes = {}
-    for i, p in (enumerate(PARENT) if dims[0] != NUM_JOINTS * BONE_DIM else ()):
+    for i, p in (enumerate(parents) if dims[0] != len(parents) * BONE_DIM else ()):
         fin = BONE_DIM if p == -1 else BONE_DIM + FEAT
         shapes[f"enc.net.{i}.net.0.weight"] = (HID, fin)
         shapes[f"enc.net.{i}.net.0.bias"] = (HID,)
@@ -39,13 +45,14 @@ def state_dict_shapes(dims=DFNET_DIMS):
     return shapes
 
 
-def make_weights(seed: int = 0, gain: float = 2.0, out_bias: float = 0.1, dims=DFNET_DIMS):
-    """Deterministic fp32 weights keyed like the reference state dict."""
+def make_weights(seed: int = 0, gain: float = 2.0, out_bias: float = 0.1, dims=DFNET_DIMS, parents=PARENT):
+    """Deterministic fp32 weights keyed like the reference state dict (of the skeleton `parents`; dims[0] = 6 or 4 per joint)."""
     rng = np.random.default_rng(seed)
     sd = {}
-    for key, shape in state_dict_shapes(dims).items():
+    shapes = state_dict_shapes(dims, parents)
+    for key, shape in shapes.items():
         layer = key.rsplit(".", 1)[0]
-        fan_in = state_dict_shapes(dims)[layer + ".weight"][1]
+        fan_in = shapes[layer + ".weight"][1]
         bound = gain / np.sqrt(fan_in)
         sd[key] = rng.uniform(-bound, bound, size=shape).astype(np.float32)
     last = f"dfnet.lin{len(dims) - 2}.bias"
@@ -53,13 +60,14 @@ def make_weights(seed: int = 0, gain: float = 2.0, out_bias: float = 0.1, dims=D
     return sd
 
 
-def make_poses(batch: int, seed: int = 1234, signed: bool = False, offset: int = 0):
+def make_poses(batch: int, seed: int = 1234, signed: bool = False, offset: int = 0, num_joints: int = NUM_JOINTS):
     """Synthetic input poses, reference experiments/sample_poses.py:96-97:
     normalize(torch.rand(B,21,4), dim=2) -- components U[0,1) then per-quaternion unit norm.
     signed=True draws U(-1,1) instead (full-sphere quaternions).  `offset` selects a window of a
-    conceptually infinite stream so that shards of one global batch are reproducible per rank."""
+    conceptually infinite stream so that shards of one global batch are reproducible per rank.
+    `num_joints`: the joints of another skeleton."""
     rng = np.random.default_rng([seed, offset])
-    q = rng.random((batch, NUM_JOINTS, 4), dtype=np.float32)
+    q = rng.random((batch, num_joints, 4), dtype=np.float32)
     if signed:
         q = q * 2.0 - 1.0
     n = np.sqrt((q.astype(np.float64) ** 2).sum(-1, keepdims=True))
