@@ -1,18 +1,20 @@
-// The structure encoder and the network plan of the layer-by-layer units (csrc/pndf_train.hip, csrc/pndf_second_order.hip), on top
-// of pndf_gemm.h.  Device side: one bone MLP as a dual number (its input gather, its forward with the tangent, its reverse with
+// The structure encoder of the layer-by-layer units (csrc/pndf_train.hip, csrc/pndf_second_order.hip, csrc/pndf_skeleton.hip), on
+// top of pndf_gemm.h.  Device side: one bone MLP as a dual number (its input gather, its forward with the tangent, its reverse with
 // the primal and the tangent adjoint: DESIGN.md section 2s, "The dual-number bone"), the pieces of normalize(q, dim=1), the table
-// of the encoder's 84 tensors.  Host side: LayerNet, what both units know about the network, and what they ask of its tensors.
-// Each unit keeps what is its own: training the LDS reduction of the weight gradient, the second order the curvature of the
-// normalisation.  Everything is in an unnamed namespace, instantiated per translation unit as in pndf_gemm.h.
+// of the encoder's 84 tensors.  Host side: what the two 21-joint units refuse of a network and ask of its tensors; the plan
+// itself, LayerNet, is pndf_net_plan.h's.  Each unit keeps what is its own: training the LDS reduction of the weight gradient,
+// the second order the curvature of the normalisation, the skeleton unit the joint count at run time.  Everything is in an
+// unnamed namespace, instantiated per translation unit as in pndf_gemm.h.
 #pragma once
 #include "pndf_gemm.h"
+#include "pndf_net_plan.h"
 
 namespace {
 
 constexpr int NJ = 21, FEAT = 6, HID = 10, BONE = 4;
 constexpr int ENC_IN = NJ * FEAT;          // 126: the encoder's output, the trunk's input
 constexpr int POSE = NJ * BONE;            // 84
-constexpr int MAX_LIN = 8;                 // 1 .. 7 hidden layers -> 2 .. 8 linear layers
+constexpr int MAX_LIN = PNDF_NET_MAX_LIN;  // 1 .. 7 hidden layers -> 2 .. 8 linear layers
 constexpr int ENC_TENSORS = 4 * NJ;        // 84
 constexpr float NORM_EPS = 1e-12f;         // F.normalize
 
@@ -168,60 +170,13 @@ __device__ __forceinline__ void enc_pack_body(const PtrTable& t, float* dst) {
 }
 
 // ------------------------------------------------------------------------------------------------------------ host side
-// The networks the layer-by-layer translation units run: relu / lrelu / softplus, 21 joints, the structure encoder, one to seven
-// hidden layers up to 1024 wide, every parent before its child.  Null, or why `cfg` is PNDF_ERR_UNSUPPORTED; `no_encoder`: the
-// caller's text for a network without the encoder.
+// The networks training and the second order run: what pndf_net_plan.h accepts, with the 21 joints and the structure encoder their
+// kernels are compiled for.  Null, or why `cfg` is PNDF_ERR_UNSUPPORTED; `no_encoder`: the caller's text for a network without it.
 inline const char* layer_network_refusal(const pndf_config* cfg, const char* no_encoder) {
-    if (cfg->act < PNDF_ACT_RELU || cfg->act > PNDF_ACT_SOFTPLUS) return "activation: relu, lrelu or softplus";
-    if (cfg->enc_act > PNDF_ACT_SOFTPLUS) return "encoder activation: relu, lrelu or softplus";
-    if (cfg->num_joints != NJ) return "num_joints must be 21";
+    if (const char* why = pndf_skeleton_refusal(cfg)) return why;
+    if (cfg->num_joints != NJ) return "num_joints must be 21 (pndf_skel_create of posendf_amd_skeleton.h takes any joint tree)";
     if (cfg->dims[0] != ENC_IN) return no_encoder;
-    if (cfg->n_dims < 3 || cfg->n_dims > MAX_LIN + 1 || cfg->dims[cfg->n_dims - 1] != 1) return "DFNet: 1 .. 7 hidden layers and one output";
-    for (int i = 1; i < cfg->n_dims - 1; ++i)
-        if (cfg->dims[i] < 1 || cfg->dims[i] > 1024) return "hidden widths 1 .. 1024";
-    for (int j = 0; j < NJ; ++j)
-        if (cfg->parent[j] >= j || cfg->parent[j] < -1) return "parent table: every parent before its child";
-    return nullptr;
-}
-
-// what a unit's handle knows about the network (a `cfg` that layer_network_refusal passed)
-struct LayerNet {
-    int device = 0;
-    int L = 0;                    // linear layers of the trunk
-    int dims[MAX_LIN + 1] = {};   // dims[0] = 126 ... dims[L] = 1
-    int act = 0, enc_act = 0;
-    float beta = 100.f, enc_beta = 100.f;
-    int parent[NJ] = {};
-    int enc_off[NJ] = {};         // offset of bone j in the packed encoder
-    int enc_tensor_off[ENC_TENSORS + 1] = {};
-    int enc_params = 0;
-    int maxw = 0;
-};
-
-inline void layer_net_init(LayerNet& n, const pndf_config* cfg, int device) {
-    n.device = device;
-    n.L = cfg->n_dims - 1;
-    for (int t = 0; t <= n.L; ++t) {
-        n.dims[t] = cfg->dims[t];
-        if (cfg->dims[t] > n.maxw) n.maxw = cfg->dims[t];
-    }
-    n.act = cfg->act;
-    n.beta = cfg->beta;
-    n.enc_act = cfg->enc_act >= 0 ? cfg->enc_act : cfg->act;
-    n.enc_beta = cfg->enc_beta > 0.f ? cfg->enc_beta : cfg->beta;
-    int o = 0, k = 0;
-    for (int j = 0; j < NJ; ++j) {
-        n.parent[j] = cfg->parent[j];
-        n.enc_off[j] = o;
-        const int fin = cfg->parent[j] < 0 ? BONE : BONE + FEAT;
-        const int sizes[4] = {HID * fin, HID, FEAT * HID, FEAT};
-        for (int s = 0; s < 4; ++s) {
-            n.enc_tensor_off[k++] = o;
-            o += sizes[s];
-        }
-    }
-    n.enc_tensor_off[ENC_TENSORS] = o;
-    n.enc_params = o;
+    return pndf_dfnet_refusal(cfg);
 }
 
 // the encoder's 84 tensors among the caller's `tensors` (weights, or gradients to write)

@@ -3,7 +3,7 @@
 // (reference model/posendf.py:35,64 moves the pose to whatever device the config names).  Written from scratch in plain
 // C++ for the host cores -- NOT the oracle (oracle/ is test infrastructure and is imported by nothing here) and NOT a
 // fallback: the device entry points never route here, a missing GPU still fails loudly there.  The first-order twins take the joint
-// count and the parent table from the handle's config (any joint tree of include/posendf_amd_skeleton.h, pndf_skel_plan.h); on the
+// count and the parent table from the handle's config (any joint tree of include/posendf_amd_skeleton.h, pndf_net_plan.h); on the
 // SMPL table they compute what they did with the table fixed.  Completion, interpolation, second order and online stay 21-joint.
 //
 // Layout: poses are processed in blocks of PB = 32; inside a block every activation tensor is [feature][pose] so that the
@@ -34,14 +34,14 @@
 #include "pndf_layout.h"
 #include "pndf_online.h"
 #include "pndf_project_opts.h"
-#include "pndf_skel_plan.h"
+#include "pndf_net_plan.h"
 
 using namespace pndf;
 
 namespace {
 
 constexpr int PB = 32;
-constexpr int MAXJ = PNDF_SKEL_MAX_JOINTS;      // the first-order twins take any joint tree (pndf_skel_plan.h); the others stay 21-joint
+constexpr int MAXJ = PNDF_SKEL_MAX_JOINTS;      // the first-order twins take any joint tree (pndf_net_plan.h); the others stay 21-joint
 
 struct Layer {
     int in = 0, out = 0;
@@ -141,7 +141,7 @@ void forward_grad_block(const pndf_cpu_engine& E, const float* q /*[nb][4 nj]*/,
     auto enc_in = [PARENT](int j) { return PARENT[j] < 0 ? 4 : 10; };
     const Act act{E.cfg.act, E.cfg.beta};
     // model.StrEnc.act / beta are read on their own (net_modules.py:128); -1 / <= 0: the trunk's
-    const Act eact{E.cfg.enc_act == -1 ? E.cfg.act : E.cfg.enc_act, E.cfg.enc_beta > 0.f ? E.cfg.enc_beta : E.cfg.beta};
+    const Act eact{pndf_enc_act(E.cfg), pndf_enc_beta(E.cfg)};
     // ---- normalise over joints per component (posendf.py:71), poses of the block as the inner index
     S.n.assign((size_t)NQ * PB, 0.f);
     for (int c = 0; c < 4; ++c)
@@ -298,18 +298,12 @@ int guarded(pndf_cpu_engine* h, F&& body) {
 extern "C" int pndf_cpu_create(pndf_cpu_handle* out, const pndf_config* cfg) {
     if (!out || !cfg) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_BAD_ARG, "null argument");
     *out = nullptr;
-    if (cfg->act < PNDF_ACT_RELU || cfg->act > PNDF_ACT_SOFTPLUS) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_UNSUPPORTED, "unknown activation");
-    // any joint tree (include/posendf_amd_skeleton.h): 1 .. 32 joints, every parent before its child, dims[0] = 6 J or 4 J
+    // any joint tree (include/posendf_amd_skeleton.h): 1 .. 32 joints, every parent before its child, dims[0] = 6 J or 4 J; the
+    // same DFNets the device units accept
     if (const char* why = pndf_skeleton_refusal(cfg)) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_UNSUPPORTED, why);
-    if (cfg->n_dims < 3 || cfg->n_dims > MAXLIN + 1)
-        return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_UNSUPPORTED, "n_dims: a DFNet of 2 .. 8 linear layers (n_dims 3 .. 9)");
+    if (const char* why = pndf_dfnet_refusal(cfg)) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_UNSUPPORTED, why);
     const int nlin = cfg->n_dims - 1;
-    if (cfg->dims[nlin] != 1) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_UNSUPPORTED, "DFNet must end in one output");
-    for (int l = 1; l < nlin; ++l)
-        if (cfg->dims[l] < 1 || cfg->dims[l] > MAX_WIDTH)      // the same architectures the device engine accepts
-            return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_UNSUPPORTED, "hidden widths 1 .. 1024");
     if (cfg->act == PNDF_ACT_SOFTPLUS && !(cfg->beta > 0.f)) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_BAD_ARG, "Softplus beta must be positive");
-    if (cfg->enc_act < -1 || cfg->enc_act > PNDF_ACT_SOFTPLUS) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_UNSUPPORTED, "unknown encoder activation");
     if (cfg->enc_act == PNDF_ACT_SOFTPLUS && !(cfg->enc_beta > 0.f) && !(cfg->beta > 0.f)) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_BAD_ARG, "Softplus beta of the encoder must be positive");
     return guarded(nullptr, [&] {
         pndf_cpu_engine* h = new pndf_cpu_engine();
@@ -570,7 +564,7 @@ struct SoScratch {
 void second_order_pose(const pndf_cpu_engine& E, const float* q, const float* v, float wd, float wt, float* d, float* g, float* t,
                        float* out, SoScratch& S) {
     const Act act{E.cfg.act, E.cfg.beta};
-    const Act eact{E.cfg.enc_act == -1 ? E.cfg.act : E.cfg.enc_act, E.cfg.enc_beta > 0.f ? E.cfg.enc_beta : E.cfg.beta};
+    const Act eact{pndf_enc_act(E.cfg), pndf_enc_beta(E.cfg)};
     constexpr int FIN = 4 + FEAT;
     // ---- normalisation: x, xdot = J_N v
     float s[4], va[4], x[NQ], xd[NQ];

@@ -1,7 +1,9 @@
 // The 128 x 128 fp32 MFMA GEMM with its epilogues and the activation with its two derivatives, shared by the layer-by-layer
-// units csrc/pndf_train.hip (the training objective) and csrc/pndf_second_order.hip (Hessian-vector products of the distance).
-// The structure encoder and the network plan of those units are in pndf_bone.h, which includes this header.  Device code in an
-// unnamed namespace: every translation unit that includes it instantiates its own kernels from it under its own extern "C" names.
+// units csrc/pndf_train.hip (the training objective), csrc/pndf_second_order.hip (Hessian-vector products of the distance) and
+// csrc/pndf_skeleton.hip (the first order for any joint tree).  Device code in an unnamed namespace: every translation unit that
+// includes it instantiates its own kernels from it under its own extern "C" names.  Host side, at the end: the one GEMM launcher
+// over a unit's kernels, and the trunk's forward and first-order reverse as launch sequences over the plan of pndf_net_plan.h.
+// The structure encoder of those units is in pndf_bone.h, which includes this header.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +11,7 @@
 #include <string.h>
 
 #include "../../include/posendf_amd.h"
+#include "pndf_net_plan.h"
 
 namespace {
 
@@ -161,5 +164,78 @@ inline GemmArgs gemm_args(const float* A, int64_t lda, const float* Bp, int64_t 
 
 inline int64_t align64(int64_t x) { return (x + 63) / 64 * 64; }
 inline unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+// ------------------------------------------------------------------------------------------------------------ host side
+// a workspace or a weight blob carved into regions of floats, every region 256-byte aligned
+struct Carver {
+    int64_t o = 0;
+    int64_t take(int64_t n) { const int64_t at = o; o += align64(n); return at; }
+};
+
+// A unit's own instances of gemm_body under its own extern "C" names (the profiles name them); nt: training alone has one.
+struct GemmKernels {
+    void (*nn)(GemmArgs);
+    void (*tn)(GemmArgs);
+    void (*nt)(GemmArgs);
+};
+enum { GEMM_NN, GEMM_TN, GEMM_NT };
+inline void launch_gemm(const GemmKernels& k, int kind, const GemmArgs& g, int splits, hipStream_t st) {
+    if (g.M <= 0 || g.N <= 0) return;
+    const dim3 grid((g.N + TN - 1) / TN, (g.M + TM - 1) / TM, splits);
+    void (*kernel)(GemmArgs) = kind == GEMM_NN ? k.nn : kind == GEMM_TN ? k.tn : k.nt;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, g);
+}
+
+// trunk layer t: W[t] weight [dims[t+1]][dims[t]], b[t] bias
+struct TrunkWeights {
+    const float* W[PNDF_NET_MAX_LIN];
+    const float* b[PNDF_NET_MAX_LIN];
+};
+// ... from a caller's tensor table, the trunk's 2 L tensors in state-dict order
+inline TrunkWeights trunk_weights(const LayerNet& net, const float* const* tensors) {
+    TrunkWeights w{};
+    for (int t = 0; t < net.L; ++t) { w.W[t] = tensors[2 * t]; w.b[t] = tensors[2 * t + 1]; }
+    return w;
+}
+
+// The buffers of one pass over the trunk for a chunk of n columns, every matrix [features][ld]
+struct TrunkBuffers {
+    const float* in;                   // the trunk's input [dims[0]][ld]
+    float* P[2];                       // the ping-pong buffers every pass over the layers runs through [maxw][ld]
+    float* D1[PNDF_NET_MAX_LIN];       // sigma' of layer t [dims[t+1]][ld]
+    float* D2[PNDF_NET_MAX_LIN];       // null, or sigma'' of layer t, then what the tangent passes leave there (a dual trunk)
+    float *out, *din;                  // the output row [ld]; the reverse's result, the adjoint of the input [dims[0]][ld]
+    int64_t ld;
+    int n;
+};
+
+// forward: layer t reads in / P[(t-1)&1] and writes P[t&1], epilogue bias + sigma with sigma' (and sigma'') kept; the output row
+// goes to `out`
+inline void trunk_forward(const GemmKernels& k, const LayerNet& net, const TrunkWeights& w, const TrunkBuffers& b, hipStream_t st) {
+    const int L = net.L;
+    for (int t = 0; t < L; ++t) {
+        GemmArgs a = gemm_args(w.W[t], net.dims[t], t == 0 ? b.in : b.P[(t - 1) & 1], b.ld, t == L - 1 ? b.out : b.P[t & 1], b.ld,
+                               net.dims[t + 1], b.n, net.dims[t]);
+        a.epi = EPI_FWD; a.act = net.act; a.beta = net.beta; a.out_layer = t == L - 1; a.bias = w.b[t];
+        a.D1 = b.D1[t]; a.ld1 = b.ld;
+        if (b.D2[t]) { a.D2 = b.D2[t]; a.ld2 = b.ld; a.nB = b.n; }
+        launch_gemm(k, GEMM_NN, a, 1, st);
+    }
+}
+
+// The first-order reverse from sigma' of the output (the seed 1): layer t's input adjoint, * sigma' of layer t-1, down to `din`.
+// In a dual trunk this is the adjoint chain of the tangent, and adotbar sigma'' zdot replaces sigma'' zdot in D2 on the way.
+inline void trunk_reverse(const GemmKernels& k, const LayerNet& net, const TrunkWeights& w, const TrunkBuffers& b, hipStream_t st) {
+    const float* U = b.D1[net.L - 1];
+    for (int t = net.L - 1; t >= 0; --t) {
+        float* o = t == 0 ? b.din : b.P[t & 1];
+        GemmArgs a = gemm_args(w.W[t], net.dims[t], U, b.ld, o, b.ld, net.dims[t], b.n, net.dims[t + 1]);
+        a.epi = (t > 0 && b.D2[t - 1]) ? EPI_TAN : EPI_MUL;
+        if (t > 0) { a.D1 = b.D1[t - 1]; a.ld1 = b.ld; }
+        if (a.epi == EPI_TAN) { a.D2 = b.D2[t - 1]; a.ld2 = b.ld; }
+        launch_gemm(k, GEMM_TN, a, 1, st);
+        U = o;
+    }
+}
 
 }  // namespace

@@ -39,6 +39,7 @@
 
 #include "pndf_generic.h"
 #include "pndf_host.h"
+#include "pndf_net_plan.h"
 #include "pndf_pack.h"
 #include "pndf_project_opts.h"
 
@@ -959,11 +960,9 @@ bool pndf_generic_needed(const pndf_config& cfg) {
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int round_up_int(int a, int b) { return ceil_div(a, b) * b; }
 constexpr int GEN_STREAM_PAD_SLOTS = 5;      // >= RING_SLOTS - 1: the replica of the stream's first slots behind it (the ring never wraps)
-static inline int gen_enc_act(const pndf_config& cfg) { return cfg.enc_act == -1 ? cfg.act : cfg.enc_act; }
-static inline float gen_enc_beta(const pndf_config& cfg) { return cfg.enc_beta > 0.f ? cfg.enc_beta : cfg.beta; }
 typedef void (*gen_kernel_t)(PndfGenericArgs);
 static gen_kernel_t gen_kernel(const pndf_config& cfg, bool split, const char** name) {
-    const bool sp = cfg.act == PNDF_ACT_SOFTPLUS, esp = (cfg.dims[0] == DIMS[0]) ? gen_enc_act(cfg) == PNDF_ACT_SOFTPLUS : sp;
+    const bool sp = cfg.act == PNDF_ACT_SOFTPLUS, esp = (cfg.dims[0] == DIMS[0]) ? pndf_enc_act(cfg) == PNDF_ACT_SOFTPLUS : sp;
     if (split) {
         if (sp && esp) { *name = "pndf_generic_split_softplus_kernel"; return pndf_generic_split_softplus_kernel; }
         if (!sp && !esp) { *name = "pndf_generic_split_relu_kernel"; return pndf_generic_split_relu_kernel; }
@@ -1021,7 +1020,7 @@ static void gen_plan(PndfGeneric* g, bool split) {
     }
     g->wb_tiles = wb;
     P.enc_d_off = slot;
-    if (gen_enc_act(cfg) == PNDF_ACT_SOFTPLUS && g->enc) slot += 2 * NJ;
+    if (pndf_enc_act(cfg) == PNDF_ACT_SOFTPLUS && g->enc) slot += 2 * NJ;
     P.wg_tiles = slot;
     // the step's stream: encoder forward (3 slots) | trunk (whole groups of NTB tiles, padded to whole slots) | encoder backward (3 slots)
     // Every group of the trunk runs the ring events and the tile reads of the group BEHIND it (gen_layer has no "last group" case), so
@@ -1175,8 +1174,8 @@ int pndf_generic_launch(PndfGeneric* g, int mode, const float* q, const float* g
     pndf_fill_step_options(a, mode, popt);
     a.slope = (g->cfg.act == PNDF_ACT_LRELU) ? 0.01f : 0.0f;      // nn.LeakyReLU() default slope, net_modules.py:31
     a.beta = g->cfg.beta;
-    a.enc_slope = (gen_enc_act(g->cfg) == PNDF_ACT_LRELU) ? 0.01f : 0.0f;
-    a.enc_beta = gen_enc_beta(g->cfg);
+    a.enc_slope = (pndf_enc_act(g->cfg) == PNDF_ACT_LRELU) ? 0.01f : 0.0f;
+    a.enc_beta = pndf_enc_beta(g->cfg);
     const int64_t nblocks = (B + WG_POSES - 1) / WG_POSES;
     const dim3 grid((unsigned)(nblocks < g->resident ? nblocks : g->resident)), block(WG_THREADS);
     hipError_t e = g->order.wait(stream);

@@ -51,6 +51,22 @@ PNDF_LOCAL inline int pndf_check_launch(H* h, const char* what) {
     return PNDF_OK;
 }
 
+// do two buffers of `floats` floats each share memory?  (a null one shares none)
+PNDF_LOCAL inline bool overlaps(const float* a, const float* b, int64_t floats) {
+    return a && b && (uintptr_t)a < (uintptr_t)(b + floats) && (uintptr_t)b < (uintptr_t)(a + floats);
+}
+
+// The caller's workspace of `have` units ("floats", "bytes") against the `need` that `asks` (the unit's own query) returns:
+// PNDF_OK, or PNDF_ERR_BAD_ARG with the text on the handle
+template <class H>
+PNDF_LOCAL inline int pndf_check_workspace(H* h, const void* workspace, int64_t have, int64_t need, const char* unit, const char* asks) {
+    if (!workspace) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null workspace");
+    if (((uintptr_t)workspace & 15) != 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "workspace must be 16-byte aligned");
+    if (have < need)
+        return pndf_fail(h, PNDF_ERR_BAD_ARG, "workspace of " + std::to_string(have) + " " + unit + ", " + asks + " asks for " + std::to_string(need));
+    return PNDF_OK;
+}
+
 // Is `device` a gfx950 device, and what are its properties?  `who` ("the engine", "training", ...) names the caller in the text.
 // PNDF_ANY_DEVICE asks only whether the runtime sees a device at all (the pose index learns its device from a pointer afterwards).
 // Every refusal clears the runtime's sticky error.  `verbose`: pndf_create's wording, which names the failed call and the

@@ -7,9 +7,11 @@
 // C the curvature of the normalisation.  hess f xdot comes from the dual-number network csrc/pndf_train.hip differentiates the
 // eikonal term through, seeded with dbar = 0, ddotbar = 1: the adjoint chain of the tangent is the first-order reverse (it gives
 // g_x), the adjoint chain of the primal carries the sigma'' cross terms ("The dual-number bone").
-// Shared with pndf_train.hip: the GEMM with its epilogues and the activation (pndf_gemm.h); the dual-number bone, the pieces of
-// the normalisation and the host's description of the network, LayerNet (pndf_bone.h).  Here: the two encoder kernels around
-// the bone, the curvature of the normalisation with the four outputs, the chunked launch sequence.
+// Shared with pndf_train.hip and pndf_skeleton.hip: the GEMM with its epilogues and the activation, the GEMM launcher and the
+// trunk's forward and first-order reverse as launch sequences (pndf_gemm.h); the dual-number bone and the pieces of the
+// normalisation (pndf_bone.h); the host's description of the network, LayerNet (pndf_net_plan.h).  Here: the two encoder kernels
+// around the bone, the curvature of the normalisation with the four outputs, the tangent forward and the primal adjoint chain of
+// a softplus trunk, the chunked call.
 //
 // Layer by layer over a chunk of SO_CHUNK poses, every activation matrix [features][columns] (the pose index contiguous) in the
 // caller's workspace; the chunk is a function of B only and bounds the workspace (0.53 GB for configs/amass.yaml with softplus):
@@ -244,37 +246,27 @@ struct SoLayout {
 SoLayout so_layout(const pndf_so_plan* h, int64_t B) {
     SoLayout l{};
     l.nc = B < SO_CHUNK ? B : SO_CHUNK;
-    int64_t o = 0;
-    auto take = [&](int64_t n) { const int64_t at = o; o += align64(n); return at; };
-    l.wenc = take(h->enc_params);
-    l.X = take(POSE * l.nc);
-    l.Xd = h->dual ? take(POSE * l.nc) : -1;
-    l.act0 = take(ENC_IN * l.nc);
-    l.tan0 = h->dual ? take(ENC_IN * l.nc) : -1;
-    l.U0 = take(ENC_IN * l.nc);
-    l.A0 = h->dual ? take(ENC_IN * l.nc) : -1;
-    l.Gx = take(POSE * l.nc);
-    l.Xb = h->dual ? take(POSE * l.nc) : -1;
-    l.dist = take(l.nc);
-    for (int t = 0; t < h->L; ++t) l.D1[t] = take((int64_t)h->dims[t + 1] * l.nc);
-    for (int t = 0; t < h->L; ++t) l.D2[t] = h->dual_trunk ? take((int64_t)h->dims[t + 1] * l.nc) : -1;
+    Carver c;
+    l.wenc = c.take(h->enc_params);
+    l.X = c.take(POSE * l.nc);
+    l.Xd = h->dual ? c.take(POSE * l.nc) : -1;
+    l.act0 = c.take(ENC_IN * l.nc);
+    l.tan0 = h->dual ? c.take(ENC_IN * l.nc) : -1;
+    l.U0 = c.take(ENC_IN * l.nc);
+    l.A0 = h->dual ? c.take(ENC_IN * l.nc) : -1;
+    l.Gx = c.take(POSE * l.nc);
+    l.Xb = h->dual ? c.take(POSE * l.nc) : -1;
+    l.dist = c.take(l.nc);
+    for (int t = 0; t < h->L; ++t) l.D1[t] = c.take((int64_t)h->dims[t + 1] * l.nc);
+    for (int t = 0; t < h->L; ++t) l.D2[t] = h->dual_trunk ? c.take((int64_t)h->dims[t + 1] * l.nc) : -1;
     // the two ping-pong buffers every pass over the layers runs through
-    l.P[0] = take((int64_t)h->maxw * l.nc);
-    l.P[1] = take((int64_t)h->maxw * l.nc);
-    l.total = o;
+    l.P[0] = c.take((int64_t)h->maxw * l.nc);
+    l.P[1] = c.take((int64_t)h->maxw * l.nc);
+    l.total = c.o;
     return l;
 }
 
-enum { SO_GEMM_NN, SO_GEMM_TN };
-void so_launch_gemm(int kind, const GemmArgs& g, hipStream_t st) {
-    const dim3 grid((g.N + TN - 1) / TN, (g.M + TM - 1) / TM, 1);
-    if (kind == SO_GEMM_NN) hipLaunchKernelGGL(pndf_so_gemm_nn_kernel, grid, dim3(256), 0, st, g);
-    else hipLaunchKernelGGL(pndf_so_gemm_tn_kernel, grid, dim3(256), 0, st, g);
-}
-
-bool overlaps(const float* a, const float* b, int64_t floats) {
-    return a && b && (uintptr_t)a < (uintptr_t)(b + floats) && (uintptr_t)b < (uintptr_t)(a + floats);
-}
+const GemmKernels SO_GEMM = {pndf_so_gemm_nn_kernel, pndf_so_gemm_tn_kernel, nullptr};
 
 }  // namespace
 
@@ -311,24 +303,26 @@ extern "C" int pndf_second_order(pndf_so_handle h, const float* const* weights, 
     if (!h) return PNDF_ERR_BAD_ARG;
     if (B < 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative batch");
     if (B == 0) return PNDF_OK;
-    if (!weights || !q || !v || !workspace) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pointer");
-    if (((uintptr_t)workspace & 15) != 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "workspace must be 16-byte aligned");
+    if (!weights || !q || !v) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pointer");
     if (((uintptr_t)q | (uintptr_t)v | (uintptr_t)w_d | (uintptr_t)w_t | (uintptr_t)d | (uintptr_t)g | (uintptr_t)t | (uintptr_t)out) & 3)
         return pndf_fail(h, PNDF_ERR_BAD_ARG, "misaligned pose, direction, weight or output buffer");
     if (overlaps(out, q, B * POSE) || overlaps(out, v, B * POSE) || overlaps(g, q, B * POSE) || overlaps(g, v, B * POSE) || overlaps(g, out, B * POSE))
         return pndf_fail(h, PNDF_ERR_BAD_ARG, "out and g must not alias q, v or each other");
     const SoLayout l = so_layout(h, B);
-    if (workspace_floats < l.total)
-        return pndf_fail(h, PNDF_ERR_BAD_ARG, "workspace of " + std::to_string(workspace_floats) + " floats, pndf_so_workspace_floats asks for " + std::to_string(l.total));
+    if (const int rc = pndf_check_workspace(h, workspace, workspace_floats, l.total, "floats", "pndf_so_workspace_floats"); rc != PNDF_OK) return rc;
     if (const int i = null_tensor(*h, weights); i >= 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null weight tensor " + std::to_string(i));
     PndfRange range("pndf_second_order");
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
-    const float* const* W = weights + ENC_TENSORS;          // trunk layer t: W[2t] weight [dims[t+1]][dims[t]], W[2t+1] bias
+    const TrunkWeights w = trunk_weights(*h, weights + ENC_TENSORS);
     const int L = h->L;
     const int64_t ld = l.nc;
+    TrunkBuffers b{};
+    b.in = ws + l.act0; b.P[0] = ws + l.P[0]; b.P[1] = ws + l.P[1]; b.out = ws + l.dist; b.din = ws + l.U0;
+    b.ld = ld;
+    for (int tt = 0; tt < L; ++tt) { b.D1[tt] = ws + l.D1[tt]; b.D2[tt] = h->dual_trunk ? ws + l.D2[tt] : nullptr; }
 
     hipLaunchKernelGGL(pndf_so_enc_pack_kernel, dim3(blocks(h->enc_params)), dim3(256), 0, st, ptr_table(*h, weights), ws + l.wenc);
 
@@ -349,48 +343,29 @@ extern "C" int pndf_second_order(pndf_so_handle h, const float* const* weights, 
         e.d_out = d ? d + c0 : nullptr; e.g_out = g ? g + c0 * POSE : nullptr;
         e.t_out = t ? t + c0 : nullptr; e.h_out = out ? out + c0 * POSE : nullptr;
         hipLaunchKernelGGL(pndf_so_enc_fwd_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
-        // 1. forward: layer t reads act0 / P[(t-1)&1] and writes P[t&1]; the output row goes to `dist`
-        for (int tt = 0; tt < L; ++tt) {
-            GemmArgs a = gemm_args(W[2 * tt], h->dims[tt], tt == 0 ? ws + l.act0 : ws + l.P[(tt - 1) & 1], ld,
-                                   tt == L - 1 ? ws + l.dist : ws + l.P[tt & 1], ld, h->dims[tt + 1], n, h->dims[tt]);
-            a.epi = EPI_FWD; a.act = h->act; a.beta = h->beta; a.out_layer = tt == L - 1; a.bias = W[2 * tt + 1];
-            a.D1 = ws + l.D1[tt]; a.ld1 = ld;
-            if (h->dual_trunk) { a.D2 = ws + l.D2[tt]; a.ld2 = ld; a.nB = n; }
-            so_launch_gemm(SO_GEMM_NN, a, st);
-        }
+        b.n = n;
+        trunk_forward(SO_GEMM, *h, w, b, st);      // 1. sigma' kept, and (softplus) sigma''
         if (h->dual_trunk) {
             // 2. tangent forward: adot = sigma' zdot; sigma'' zdot replaces sigma''
             for (int tt = 0; tt < L; ++tt) {
-                GemmArgs a = gemm_args(W[2 * tt], h->dims[tt], tt == 0 ? ws + l.tan0 : ws + l.P[(tt - 1) & 1], ld, ws + l.P[tt & 1], ld,
+                GemmArgs a = gemm_args(w.W[tt], h->dims[tt], tt == 0 ? ws + l.tan0 : ws + l.P[(tt - 1) & 1], ld, ws + l.P[tt & 1], ld,
                                        h->dims[tt + 1], n, h->dims[tt]);
                 a.epi = EPI_TAN; a.D1 = ws + l.D1[tt]; a.ld1 = ld; a.D2 = ws + l.D2[tt]; a.ld2 = ld;
-                so_launch_gemm(SO_GEMM_NN, a, st);
+                launch_gemm(SO_GEMM, GEMM_NN, a, 1, st);
             }
         }
         // 3. the tangent's adjoint chain from zdotbar = sigma' of the output (seed ddotbar = 1): the first-order reverse.  Softplus:
         //    adotbar sigma'' zdot replaces sigma'' zdot on the way
-        const float* U = ws + l.D1[L - 1];
-        for (int tt = L - 1; tt >= 0; --tt) {
-            float* o = tt == 0 ? ws + l.U0 : ws + l.P[tt & 1];
-            GemmArgs a = gemm_args(W[2 * tt], h->dims[tt], U, ld, o, ld, h->dims[tt], n, h->dims[tt + 1]);
-            if (tt > 0 && h->dual_trunk) {
-                a.epi = EPI_TAN; a.D1 = ws + l.D1[tt - 1]; a.ld1 = ld; a.D2 = ws + l.D2[tt - 1]; a.ld2 = ld;
-            } else {
-                a.epi = EPI_MUL;
-                if (tt > 0) { a.D1 = ws + l.D1[tt - 1]; a.ld1 = ld; }
-            }
-            so_launch_gemm(SO_GEMM_TN, a, st);
-            U = o;
-        }
+        trunk_reverse(SO_GEMM, *h, w, b, st);
         if (h->dual_trunk) {
             // 4. the primal's adjoint chain from zbar = sigma'' zdot of the output (seed dbar = 0): abar sigma' + the kept cross term
             const float* Z = ws + l.D2[L - 1];
             for (int tt = L - 1; tt >= 0; --tt) {
                 float* o = tt == 0 ? ws + l.A0 : ws + l.P[tt & 1];
-                GemmArgs a = gemm_args(W[2 * tt], h->dims[tt], Z, ld, o, ld, h->dims[tt], n, h->dims[tt + 1]);
+                GemmArgs a = gemm_args(w.W[tt], h->dims[tt], Z, ld, o, ld, h->dims[tt], n, h->dims[tt + 1]);
                 a.epi = EPI_MUL;
                 if (tt > 0) { a.D1 = ws + l.D1[tt - 1]; a.ld1 = ld; a.X = ws + l.D2[tt - 1]; a.ldx = ld; a.nB = n; }
-                so_launch_gemm(SO_GEMM_TN, a, st);
+                launch_gemm(SO_GEMM, GEMM_TN, a, 1, st);
                 Z = o;
             }
         }

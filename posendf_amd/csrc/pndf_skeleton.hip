@@ -1,12 +1,12 @@
 // Distance, gradient and projection for any joint tree on gfx950 (include/posendf_amd_skeleton.h): the
 // first-order path of model/posendf.py:62-76 / experiments/sample_poses.py:67-74 with the skeleton as a run-time value -- up to 32
 // joints, every parent before its child, any number of roots.  The fused and runtime-planned persistent kernels keep the 21-joint
-// table (their MFMA encoder indexes registers by a compile-time parent); this unit is assembled layer by layer, in the style of
-// csrc/pndf_second_order.hip, from the shared pieces:
-//   pndf_gemm.h   the 128 x 128 exact-fp32 MFMA GEMM, its bias + sigma epilogue that keeps sigma', its * sigma' epilogue
-//   pndf_bone.h   one bone MLP (bone_load / bone_fwd / bone_dual_rev without the primal chain / bone_input_adj), norm_x
-//   pndf_step.h   the projection step of one joint quaternion
-// Here: the two encoder kernels with the joint count and the parent table as kernel arguments, the plan, the launch sequence.
+// table (their MFMA encoder indexes registers by a compile-time parent); this unit is assembled layer by layer from shared pieces:
+//   pndf_net_plan.h   what is accepted of a skeleton and of a DFNet, and the plan (LayerNet) the handle derives from
+//   pndf_gemm.h       the 128 x 128 exact-fp32 MFMA GEMM and its epilogues; on the host trunk_forward / trunk_reverse
+//   pndf_bone.h       one bone MLP (bone_load / bone_fwd / bone_dual_rev without the primal chain / bone_input_adj), norm_x
+//   pndf_step.h       the projection step of one joint quaternion
+// Here: the two encoder kernels with the joint count and the parent table as kernel arguments, the weights' device copy, the calls.
 //
 // Over a chunk of SK_CHUNK poses, every activation matrix [features][columns] (the pose index contiguous) in the caller's workspace:
 //   pndf_skel_enc_fwd_kernel   lanes own poses: x = normalize(q, dim=1), the bones in index order (a uniform branch on the
@@ -31,7 +31,6 @@
 #include "pndf_bone.h"
 #include "pndf_host.h"
 #include "pndf_project_opts.h"
-#include "pndf_skel_plan.h"
 #include "pndf_step.h"
 
 PNDF_EXPORT_EXPERIMENT_WORD(skeleton)
@@ -198,23 +197,16 @@ extern "C" __global__ void __launch_bounds__(256) pndf_skel_copy_kernel(const fl
 }
 
 // ------------------------------------------------------------------------------------------------------------ host side
-struct pndf_skel_plan {
-    int device = 0;
-    int nj = 0, L = 0;
-    bool encoder = true, have_weights = false;
-    int dims[MAX_LIN + 1] = {};
-    int act = 0, enc_act = 0;
-    float beta = 100.f, enc_beta = 100.f;
-    int parent[MAXJ] = {};
-    int enc_off[MAXJ] = {};           // offset of bone j in the packed encoder
-    int enc_params = 0, maxw = 0;
-    std::vector<int64_t> numel;       // of every tensor pndf_skel_load_weights takes, in its order
+struct pndf_skel_plan : LayerNet {
+    bool have_weights = false;
     int64_t w_off[MAX_LIN] = {}, b_off[MAX_LIN] = {}, blob_floats = 0;      // the device copy: the packed encoder, then W and b of every layer
     float* d_blob = nullptr;
     std::string err;
 };
 
 namespace {
+
+const GemmKernels SK_GEMM = {pndf_skel_gemm_nn_kernel, pndf_skel_gemm_tn_kernel, nullptr};
 
 // workspace layout in floats (every region 256-byte aligned); nc: the columns of a chunk
 struct SkLayout {
@@ -226,68 +218,43 @@ struct SkLayout {
 SkLayout sk_layout(const pndf_skel_plan* h, int64_t B) {
     SkLayout l{};
     l.nc = B < SK_CHUNK ? B : SK_CHUNK;
-    int64_t o = 0;
-    auto take = [&](int64_t n) { const int64_t at = o; o += align64(n); return at; };
+    Carver c;
     const int64_t nq = (int64_t)h->nj * BONE, nf = (int64_t)h->nj * FEAT;
-    l.X = take(nq * l.nc);
+    l.X = c.take(nq * l.nc);
     if (h->encoder) {
-        l.act0 = take(nf * l.nc);
-        l.S1 = take((int64_t)h->nj * HID * l.nc);
-        l.S2 = take(nf * l.nc);
-        l.U0 = take(nf * l.nc);
-        l.Gx = take(nq * l.nc);
+        l.act0 = c.take(nf * l.nc);
+        l.S1 = c.take((int64_t)h->nj * HID * l.nc);
+        l.S2 = c.take(nf * l.nc);
+        l.U0 = c.take(nf * l.nc);
+        l.Gx = c.take(nq * l.nc);
     } else {      // the trunk reads x and its reverse ends in g_x
         l.act0 = l.X;
         l.S1 = l.S2 = -1;
-        l.U0 = l.Gx = take(nq * l.nc);
+        l.U0 = l.Gx = c.take(nq * l.nc);
     }
-    l.dist = take(l.nc);
-    for (int t = 0; t < h->L; ++t) l.D1[t] = take((int64_t)h->dims[t + 1] * l.nc);
-    l.P[0] = take((int64_t)h->maxw * l.nc);
-    l.P[1] = take((int64_t)h->maxw * l.nc);
-    l.total = o;
+    l.dist = c.take(l.nc);
+    for (int t = 0; t < h->L; ++t) l.D1[t] = c.take((int64_t)h->dims[t + 1] * l.nc);
+    l.P[0] = c.take((int64_t)h->maxw * l.nc);
+    l.P[1] = c.take((int64_t)h->maxw * l.nc);
+    l.total = c.o;
     return l;
-}
-
-enum { SK_GEMM_NN, SK_GEMM_TN };
-void sk_launch_gemm(int kind, const GemmArgs& g, hipStream_t st) {
-    const dim3 grid((g.N + TN - 1) / TN, (g.M + TM - 1) / TM, 1);
-    if (kind == SK_GEMM_NN) hipLaunchKernelGGL(pndf_skel_gemm_nn_kernel, grid, dim3(256), 0, st, g);
-    else hipLaunchKernelGGL(pndf_skel_gemm_tn_kernel, grid, dim3(256), 0, st, g);
-}
-
-bool sk_overlaps(const float* a, const float* b, int64_t floats) {
-    return a && b && (uintptr_t)a < (uintptr_t)(b + floats) && (uintptr_t)b < (uintptr_t)(a + floats);
 }
 
 // One evaluation of a chunk of n poses at `q`: the 2 + 2 L launches (the forward alone: 1 + L and the copy of the output row)
 void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, SkArgs e, hipStream_t st) {
-    const int L = h->L;
     const int n = (int)e.n;
-    const int64_t ld = l.nc;
+    TrunkWeights w{};
+    TrunkBuffers b{};
+    for (int t = 0; t < h->L; ++t) { w.W[t] = h->d_blob + h->w_off[t]; w.b[t] = h->d_blob + h->b_off[t]; b.D1[t] = ws + l.D1[t]; }
+    b.in = ws + l.act0; b.P[0] = ws + l.P[0]; b.P[1] = ws + l.P[1]; b.out = ws + l.dist; b.din = ws + l.U0;
+    b.ld = l.nc; b.n = n;
     hipLaunchKernelGGL(pndf_skel_enc_fwd_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
-    // forward: layer t reads act0 / P[(t-1)&1] and writes P[t&1]; the output row goes to `dist`
-    for (int t = 0; t < L; ++t) {
-        GemmArgs a = gemm_args(h->d_blob + h->w_off[t], h->dims[t], t == 0 ? ws + l.act0 : ws + l.P[(t - 1) & 1], ld,
-                               t == L - 1 ? ws + l.dist : ws + l.P[t & 1], ld, h->dims[t + 1], n, h->dims[t]);
-        a.epi = EPI_FWD; a.act = h->act; a.beta = h->beta; a.out_layer = t == L - 1; a.bias = h->d_blob + h->b_off[t];
-        a.D1 = ws + l.D1[t]; a.ld1 = ld;
-        sk_launch_gemm(SK_GEMM_NN, a, st);
-    }
+    trunk_forward(SK_GEMM, *h, w, b, st);
     if (e.mode == SK_FORWARD) {
         hipLaunchKernelGGL(pndf_skel_copy_kernel, dim3(blocks(n)), dim3(256), 0, st, ws + l.dist, e.d_out, (int64_t)n);
         return;
     }
-    // reverse from sigma' of the output (the seed 1; grad_out scales the result): layer t's input adjoint, * sigma' of layer t-1
-    const float* U = ws + l.D1[L - 1];
-    for (int t = L - 1; t >= 0; --t) {
-        float* o = t == 0 ? ws + l.U0 : ws + l.P[t & 1];
-        GemmArgs a = gemm_args(h->d_blob + h->w_off[t], h->dims[t], U, ld, o, ld, h->dims[t], n, h->dims[t + 1]);
-        a.epi = EPI_MUL;
-        if (t > 0) { a.D1 = ws + l.D1[t - 1]; a.ld1 = ld; }
-        sk_launch_gemm(SK_GEMM_TN, a, st);
-        U = o;
-    }
+    trunk_reverse(SK_GEMM, *h, w, b, st);      // grad_out scales the result in the encoder's reverse
     hipLaunchKernelGGL(pndf_skel_enc_rev_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
 }
 
@@ -305,20 +272,13 @@ SkArgs sk_args(const pndf_skel_plan* h, const SkLayout& l, float* ws, int mode) 
     return e;
 }
 
-// what the three compute calls check alike; PNDF_OK with *go = false: nothing to do
-int sk_check(pndf_skel_plan* h, int64_t B, const void* workspace, int64_t workspace_bytes, SkLayout& l, bool* go) {
-    *go = false;
+// what the three compute calls check alike, and the layout for B > 0 poses (PNDF_OK with B == 0: nothing to do)
+int sk_check(pndf_skel_plan* h, int64_t B, const void* workspace, int64_t workspace_bytes, SkLayout& l) {
     if (B < 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative batch");
     if (!h->have_weights) return pndf_fail(h, PNDF_ERR_NO_WEIGHTS, "pndf_skel_load_weights has not been called");
     if (B == 0) return PNDF_OK;
-    if (!workspace) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null workspace");
-    if (((uintptr_t)workspace & 15) != 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "workspace must be 16-byte aligned");
     l = sk_layout(h, B);
-    const int64_t need = l.total * (int64_t)sizeof(float);
-    if (workspace_bytes < need)
-        return pndf_fail(h, PNDF_ERR_BAD_ARG, "workspace of " + std::to_string(workspace_bytes) + " bytes, pndf_skel_workspace_bytes asks for " + std::to_string(need));
-    *go = true;
-    return PNDF_OK;
+    return pndf_check_workspace(h, workspace, workspace_bytes, l.total * (int64_t)sizeof(float), "bytes", "pndf_skel_workspace_bytes");
 }
 
 }  // namespace
@@ -330,56 +290,24 @@ extern "C" int pndf_skel_create(pndf_skel_handle* out, const pndf_config* cfg, i
     if (!out || !cfg) return refuse(PNDF_ERR_BAD_ARG, "out / cfg is null");
     *out = nullptr;
     if (const char* why = pndf_skeleton_refusal(cfg)) return refuse(PNDF_ERR_UNSUPPORTED, why);
-    if (cfg->n_dims < 3 || cfg->n_dims > MAX_LIN + 1 || cfg->dims[cfg->n_dims - 1] != 1)
-        return refuse(PNDF_ERR_UNSUPPORTED, "n_dims / dims: 1 .. 7 hidden layers and one output");
-    for (int i = 1; i < cfg->n_dims - 1; ++i)
-        if (cfg->dims[i] < 1 || cfg->dims[i] > 1024) return refuse(PNDF_ERR_UNSUPPORTED, "dims: hidden widths 1 .. 1024");
-    if (cfg->act < PNDF_ACT_RELU || cfg->act > PNDF_ACT_SOFTPLUS) return refuse(PNDF_ERR_UNSUPPORTED, "act: relu, lrelu or softplus");
-    if (cfg->enc_act < -1 || cfg->enc_act > PNDF_ACT_SOFTPLUS) return refuse(PNDF_ERR_UNSUPPORTED, "enc_act: relu, lrelu, softplus or -1 (the trunk's)");
+    if (const char* why = pndf_dfnet_refusal(cfg)) return refuse(PNDF_ERR_UNSUPPORTED, why);
     if (cfg->precision != PNDF_PREC_FP32) return refuse(PNDF_ERR_UNSUPPORTED, "precision: this unit runs exact fp32 (PNDF_PREC_FP32) only");
     if (cfg->act == PNDF_ACT_SOFTPLUS && !(cfg->beta > 0.f)) return refuse(PNDF_ERR_UNSUPPORTED, "beta: Softplus beta must be positive");
-    if ((cfg->enc_act >= 0 ? cfg->enc_act : cfg->act) == PNDF_ACT_SOFTPLUS && !(cfg->enc_beta > 0.f) && !(cfg->beta > 0.f))
+    if (pndf_enc_act(*cfg) == PNDF_ACT_SOFTPLUS && !(pndf_enc_beta(*cfg) > 0.f))
         return refuse(PNDF_ERR_UNSUPPORTED, "enc_beta: Softplus beta of the encoder must be positive");
     const PndfDeviceCheck dev = pndf_check_gfx950(device, "the skeleton unit");
     if (dev.code != PNDF_OK) return refuse(dev.code, dev.text);
     pndf_skel_plan* h = new pndf_skel_plan();
-    h->device = device;
-    h->nj = cfg->num_joints;
-    h->L = cfg->n_dims - 1;
-    h->encoder = cfg->dims[0] == FEAT * h->nj;
-    for (int t = 0; t <= h->L; ++t) {
-        h->dims[t] = cfg->dims[t];
-        if (cfg->dims[t] > h->maxw) h->maxw = cfg->dims[t];
-    }
-    h->act = cfg->act;
-    h->beta = cfg->beta;
-    h->enc_act = cfg->enc_act >= 0 ? cfg->enc_act : cfg->act;              // as layer_net_init (pndf_bone.h) reads them
-    h->enc_beta = cfg->enc_beta > 0.f ? cfg->enc_beta : cfg->beta;
-    int64_t o = 0;
-    for (int j = 0; j < h->nj; ++j) {
-        h->parent[j] = cfg->parent[j];
-        h->enc_off[j] = (int)o;
-        if (!h->encoder) continue;
-        int sizes[4];
-        pndf_skeleton_bone_sizes(pndf_skeleton_fin(cfg, j), sizes);
-        for (int s = 0; s < 4; ++s) {
-            h->numel.push_back(sizes[s]);
-            o += sizes[s];
-        }
-    }
-    h->enc_params = (int)o;
-    o = align64(o);
+    layer_net_init(*h, cfg, device);
+    Carver blob;
+    blob.take(h->enc_params);
     for (int t = 0; t < h->L; ++t) {
-        h->w_off[t] = o;
-        o += align64((int64_t)h->dims[t + 1] * h->dims[t]);
-        h->b_off[t] = o;
-        o += align64(h->dims[t + 1]);
-        h->numel.push_back((int64_t)h->dims[t + 1] * h->dims[t]);
-        h->numel.push_back(h->dims[t + 1]);
+        h->w_off[t] = blob.take((int64_t)h->dims[t + 1] * h->dims[t]);
+        h->b_off[t] = blob.take(h->dims[t + 1]);
     }
-    h->blob_floats = o;
+    h->blob_floats = blob.o;
     DeviceGuard guard(device);
-    const hipError_t e = guard.ok ? hipMalloc((void**)&h->d_blob, (size_t)o * sizeof(float)) : hipErrorInvalidDevice;
+    const hipError_t e = guard.ok ? hipMalloc((void**)&h->d_blob, (size_t)h->blob_floats * sizeof(float)) : hipErrorInvalidDevice;
     if (e != hipSuccess) {
         delete h;
         (void)hipGetLastError();
@@ -438,10 +366,9 @@ extern "C" int pndf_skel_forward(pndf_skel_handle h, const float* q, float* d, i
                                  void* stream) {
     if (!h) return PNDF_ERR_BAD_ARG;
     SkLayout l;
-    bool go;
     if (B > 0 && (!q || !d)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose / distance pointer");
     if (((uintptr_t)q | (uintptr_t)d) & 3) return pndf_fail(h, PNDF_ERR_BAD_ARG, "misaligned pose or distance buffer");
-    if (const int rc = sk_check(h, B, workspace, workspace_bytes, l, &go); rc != PNDF_OK || !go) return rc;
+    if (const int rc = sk_check(h, B, workspace, workspace_bytes, l); rc != PNDF_OK || B == 0) return rc;
     PndfRange range("pndf_skel_forward");
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
@@ -460,12 +387,11 @@ extern "C" int pndf_skel_forward_grad(pndf_skel_handle h, const float* q, const 
                                       void* workspace, int64_t workspace_bytes, void* stream) {
     if (!h) return PNDF_ERR_BAD_ARG;
     SkLayout l;
-    bool go;
     if (B > 0 && (!q || !dq)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose / gradient pointer");
     if (((uintptr_t)q | (uintptr_t)grad_out | (uintptr_t)d | (uintptr_t)dq) & 3)
         return pndf_fail(h, PNDF_ERR_BAD_ARG, "misaligned pose, grad_out, distance or gradient buffer");
-    if (B > 0 && sk_overlaps(q, dq, B * h->nj * BONE)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "dq must not overlap q");
-    if (const int rc = sk_check(h, B, workspace, workspace_bytes, l, &go); rc != PNDF_OK || !go) return rc;
+    if (B > 0 && overlaps(q, dq, B * h->nj * BONE)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "dq must not overlap q");
+    if (const int rc = sk_check(h, B, workspace, workspace_bytes, l); rc != PNDF_OK || B == 0) return rc;
     PndfRange range("pndf_skel_forward_grad");
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
@@ -489,12 +415,11 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
     if (const char* why = pndf_check_project_options(opt, o)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (steps < 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count");
     SkLayout l;
-    bool go;
     if (B > 0 && (!q_in || !q_out)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose pointer");
     if (((uintptr_t)q_in | (uintptr_t)q_out | (uintptr_t)d_last) & 3) return pndf_fail(h, PNDF_ERR_BAD_ARG, "misaligned pose or distance buffer");
-    if (B > 0 && q_in != q_out && sk_overlaps(q_in, q_out, B * h->nj * BONE))
+    if (B > 0 && q_in != q_out && overlaps(q_in, q_out, B * h->nj * BONE))
         return pndf_fail(h, PNDF_ERR_BAD_ARG, "q_out may be q_in itself, but must not overlap it otherwise");
-    if (const int rc = sk_check(h, B, workspace, workspace_bytes, l, &go); rc != PNDF_OK || !go) return rc;
+    if (const int rc = sk_check(h, B, workspace, workspace_bytes, l); rc != PNDF_OK || B == 0) return rc;
     PndfRange range("pndf_skel_project");
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");

@@ -14,11 +14,11 @@
 //             primal columns, [abar|adotbar] = W^T [zbar|zdotbar] (TN GEMM) with zbar = abar sigma' + adotbar zdot sigma''
 //             and zdotbar = adotbar sigma' in the epilogue; the 21 bone MLPs of the encoder last, lanes owning poses, their
 //             weight gradients summed per workgroup (fixed order) and then over workgroups (fixed order).
-// Shared with pndf_second_order.hip: the GEMM with its epilogues and the activation (pndf_gemm.h); the dual-number bone (gather,
-// forward with tangent, reverse with both adjoints: the formulas are in DESIGN.md section 2s, "The dual-number bone"), the pieces
-// of the normalisation and the host's description of the network, LayerNet (pndf_bone.h).  Here: the encoder's kernels around
-// the bone with the LDS reduction of its weight gradient, the eikonal seed, the losses, the reverse's seeds and sums, the launch
-// sequences.
+// Shared with pndf_second_order.hip and pndf_skeleton.hip: the GEMM, its epilogues, the activation and the launcher (pndf_gemm.h);
+// the dual-number bone ("The dual-number bone") and the pieces of the normalisation (pndf_bone.h); the
+// host's description of the network, LayerNet (pndf_net_plan.h).  Here: the encoder's kernels around the bone with the LDS
+// reduction of its weight gradient, the eikonal seed, the losses, the reverse's seeds and sums, and this unit's own launch
+// sequences: column ranges of one [primal | tangent] matrix per layer, two leading dimensions, no ping-pong.
 // Arithmetic: exact fp32 MFMA (v_mfma_f32_16x16x4_f32), fp32 accumulate.  No float atomics, no communication between
 // workgroups inside a launch: two calls with the same inputs give the same bits.
 #include <hip/hip_runtime.h>
@@ -422,19 +422,18 @@ Layout make_layout(const pndf_train_plan* h, int64_t B, int64_t Bm, int eik) {
     l.np = B + Bm;
     l.ncols = eik ? l.np + B : l.np;
     l.nrev = eik ? l.ncols : B;
-    int64_t o = 0;
-    auto take = [&](int64_t n) { const int64_t at = o; o += align64(n); return at; };
-    l.wenc = take(h->enc_params);
-    l.X = take(POSE * l.np);
-    l.dgt = take(B);
-    for (int t = 0; t <= h->L; ++t) l.act[t] = take((int64_t)h->dims[t] * l.ncols);
-    for (int t = 0; t < h->L; ++t) l.D1[t] = take((int64_t)h->dims[t + 1] * l.np);
-    for (int t = 0; t < h->L; ++t) l.D2[t] = (eik && h->act == PNDF_ACT_SOFTPLUS) ? take((int64_t)h->dims[t + 1] * B) : -1;
-    l.Xd = eik ? take(POSE * B) : -1;
-    l.eikp = eik ? take(B) : -1;
+    Carver c;
+    l.wenc = c.take(h->enc_params);
+    l.X = c.take(POSE * l.np);
+    l.dgt = c.take(B);
+    for (int t = 0; t <= h->L; ++t) l.act[t] = c.take((int64_t)h->dims[t] * l.ncols);
+    for (int t = 0; t < h->L; ++t) l.D1[t] = c.take((int64_t)h->dims[t + 1] * l.np);
+    for (int t = 0; t < h->L; ++t) l.D2[t] = (eik && h->act == PNDF_ACT_SOFTPLUS) ? c.take((int64_t)h->dims[t + 1] * B) : -1;
+    l.Xd = eik ? c.take(POSE * B) : -1;
+    l.eikp = eik ? c.take(B) : -1;
     // the two ping-pong adjoint buffers of the reverse pass; the forward's input-gradient pass uses the same memory
-    l.Z[0] = take((int64_t)h->maxw * l.ncols);
-    l.Z[1] = take((int64_t)h->maxw * l.ncols);
+    l.Z[0] = c.take((int64_t)h->maxw * l.ncols);
+    l.Z[1] = c.take((int64_t)h->maxw * l.ncols);
     int64_t slab = 0;
     for (int t = 0; t < h->L; ++t) {
         // K split of the weight-gradient GEMM: a function of the shapes only, never of the device's occupancy
@@ -451,22 +450,15 @@ Layout make_layout(const pndf_train_plan* h, int64_t B, int64_t Bm, int eik) {
         l.kc[t] = (int)kc;
         if (S * M * N > slab) slab = S * M * N;
     }
-    l.slab = take(slab);
+    l.slab = c.take(slab);
     const int64_t P = eik ? l.np : B;
     l.enc_wgs = (int)((P + ENC_WG - 1) / ENC_WG);
-    l.part = take((int64_t)l.enc_wgs * h->enc_params);
-    l.total = o;
+    l.part = c.take((int64_t)l.enc_wgs * h->enc_params);
+    l.total = c.o;
     return l;
 }
 
-enum { GEMM_NN, GEMM_TN, GEMM_NT };
-void launch_gemm(int kind, const GemmArgs& g, int splits, hipStream_t st) {
-    if (g.M <= 0 || g.N <= 0) return;
-    const dim3 grid((g.N + TN - 1) / TN, (g.M + TM - 1) / TM, splits);
-    if (kind == GEMM_NN) hipLaunchKernelGGL(pndf_train_gemm_nn_kernel, grid, dim3(256), 0, st, g);
-    else if (kind == GEMM_TN) hipLaunchKernelGGL(pndf_train_gemm_tn_kernel, grid, dim3(256), 0, st, g);
-    else hipLaunchKernelGGL(pndf_train_gemm_nt_kernel, grid, dim3(256), 0, st, g);
-}
+const GemmKernels TRAIN_GEMM = {pndf_train_gemm_nn_kernel, pndf_train_gemm_tn_kernel, pndf_train_gemm_nt_kernel};
 
 EncArgs enc_args(const pndf_train_plan* h, const Layout& l, float* ws, int64_t B, int64_t Bm, int eik) {
     EncArgs e;
@@ -535,7 +527,7 @@ extern "C" int pndf_train_forward(pndf_train_handle h, const float* const* weigh
     }
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
-    const float* const* W = weights + ENC_TENSORS;          // trunk layer t: W[2t] weight [dims[t+1]][dims[t]], W[2t+1] bias
+    const TrunkWeights w = trunk_weights(*h, weights + ENC_TENSORS);
     const bool sp = h->act == PNDF_ACT_SOFTPLUS;
 
     hipLaunchKernelGGL(pndf_train_enc_pack_kernel, dim3(blocks(h->enc_params)), dim3(256), 0, st, ptr_table(*h, weights), ws + l.wenc);
@@ -544,12 +536,12 @@ extern "C" int pndf_train_forward(pndf_train_handle h, const float* const* weigh
     hipLaunchKernelGGL(pndf_train_enc_fwd_kernel, dim3(blocks(l.np)), dim3(256), 0, st, e);
     // 1. forward over the primal columns
     for (int t = 0; t < h->L; ++t) {
-        GemmArgs g = gemm_args(W[2 * t], h->dims[t], ws + l.act[t], l.ncols, ws + l.act[t + 1], l.ncols, h->dims[t + 1], (int)l.np,
+        GemmArgs g = gemm_args(w.W[t], h->dims[t], ws + l.act[t], l.ncols, ws + l.act[t + 1], l.ncols, h->dims[t + 1], (int)l.np,
                                h->dims[t]);
-        g.epi = EPI_FWD; g.act = h->act; g.beta = h->beta; g.out_layer = t == h->L - 1; g.bias = W[2 * t + 1];
+        g.epi = EPI_FWD; g.act = h->act; g.beta = h->beta; g.out_layer = t == h->L - 1; g.bias = w.b[t];
         g.D1 = ws + l.D1[t]; g.ld1 = l.np;
         if (l.D2[t] >= 0) { g.D2 = ws + l.D2[t]; g.ld2 = B; g.nB = B; }
-        launch_gemm(GEMM_NN, g, 1, st);
+        launch_gemm(TRAIN_GEMM, GEMM_NN, g, 1, st);
     }
     if (eik) {
         // 2. input gradient of the noisy batch: u_t = (W_t^T u_{t+1}) sigma'_{t-1}, from sigma' of the output; ends in Z[0] = U0
@@ -557,10 +549,10 @@ extern "C" int pndf_train_forward(pndf_train_handle h, const float* const* weigh
         int64_t ldu = l.np;
         for (int t = h->L - 1; t >= 0; --t) {
             float* out = ws + l.Z[t & 1];
-            GemmArgs g = gemm_args(W[2 * t], h->dims[t], U, ldu, out, B, h->dims[t], (int)B, h->dims[t + 1]);
+            GemmArgs g = gemm_args(w.W[t], h->dims[t], U, ldu, out, B, h->dims[t], (int)B, h->dims[t + 1]);
             g.epi = EPI_MUL;
             if (t > 0) { g.D1 = ws + l.D1[t - 1]; g.ld1 = l.np; }
-            launch_gemm(GEMM_TN, g, 1, st);
+            launch_gemm(TRAIN_GEMM, GEMM_TN, g, 1, st);
             U = out;
             ldu = B;
         }
@@ -568,11 +560,11 @@ extern "C" int pndf_train_forward(pndf_train_handle h, const float* const* weigh
         hipLaunchKernelGGL(pndf_train_enc_eik_kernel, dim3(blocks(B)), dim3(256), 0, st, e);
         // 4. tangent forward
         for (int t = 0; t < h->L; ++t) {
-            GemmArgs g = gemm_args(W[2 * t], h->dims[t], ws + l.act[t] + l.np, l.ncols, ws + l.act[t + 1] + l.np, l.ncols,
+            GemmArgs g = gemm_args(w.W[t], h->dims[t], ws + l.act[t] + l.np, l.ncols, ws + l.act[t + 1] + l.np, l.ncols,
                                    h->dims[t + 1], (int)B, h->dims[t]);
             g.epi = EPI_TAN; g.D1 = ws + l.D1[t]; g.ld1 = l.np;
             if (sp) { g.D2 = ws + l.D2[t]; g.ld2 = B; }
-            launch_gemm(GEMM_NN, g, 1, st);
+            launch_gemm(TRAIN_GEMM, GEMM_NN, g, 1, st);
         }
     }
     hipLaunchKernelGGL(pndf_train_loss_kernel, dim3(1), dim3(256), 0, st, ws + l.act[h->L], ws + l.dgt, eik ? ws + l.eikp : nullptr,
@@ -601,7 +593,7 @@ extern "C" int pndf_train_backward(pndf_train_handle h, const float* const* weig
     const Layout l = make_layout(h, B, Bm, eik);
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
-    const float* const* W = weights + ENC_TENSORS;
+    const TrunkWeights w = trunk_weights(*h, weights + ENC_TENSORS);
     float* const* G = grads + ENC_TENSORS;
     const bool cross = eik && h->act == PNDF_ACT_SOFTPLUS;
     const int64_t npr = eik ? l.np : B;          // primal columns of the reverse pass
@@ -617,7 +609,7 @@ extern "C" int pndf_train_backward(pndf_train_handle h, const float* const* weig
         // weight gradient: [zbar|zdotbar] [a|adot]^T over every column of the reverse pass, K split, the slabs summed in order
         GemmArgs g = gemm_args(Zb, l.ncols, ws + l.act[t], l.ncols, ws + l.slab, N, M, N, (int)l.nrev);
         g.epi = EPI_STORE; g.kc = l.kc[t]; g.slab = (int64_t)M * N;
-        launch_gemm(GEMM_NT, g, l.split[t], st);
+        launch_gemm(TRAIN_GEMM, GEMM_NT, g, l.split[t], st);
         hipLaunchKernelGGL(pndf_train_slab_reduce_kernel, dim3(blocks((int64_t)M * N)), dim3(256), 0, st, ws + l.slab, l.split[t],
                            (int64_t)M * N, G[2 * t]);
         hipLaunchKernelGGL(pndf_train_row_sum_kernel, dim3(M), dim3(256), 0, st, Zb, l.ncols, npr, G[2 * t + 1]);
@@ -625,17 +617,17 @@ extern "C" int pndf_train_backward(pndf_train_handle h, const float* const* weig
         float* out = ws + l.Z[zi ^ 1];
         if (t > 0 && cross) {
             // softplus: the tangent columns first (adotbar sigma'' zdot replaces sigma'' zdot), then the primal ones add it
-            GemmArgs gt = gemm_args(W[2 * t], N, Zb + l.np, l.ncols, out + l.np, l.ncols, N, (int)B, M);
+            GemmArgs gt = gemm_args(w.W[t], N, Zb + l.np, l.ncols, out + l.np, l.ncols, N, (int)B, M);
             gt.epi = EPI_TAN; gt.D1 = ws + l.D1[t - 1]; gt.ld1 = l.np; gt.D2 = ws + l.D2[t - 1]; gt.ld2 = B;
-            launch_gemm(GEMM_TN, gt, 1, st);
-            GemmArgs gp = gemm_args(W[2 * t], N, Zb, l.ncols, out, l.ncols, N, (int)l.np, M);
+            launch_gemm(TRAIN_GEMM, GEMM_TN, gt, 1, st);
+            GemmArgs gp = gemm_args(w.W[t], N, Zb, l.ncols, out, l.ncols, N, (int)l.np, M);
             gp.epi = EPI_MUL; gp.D1 = ws + l.D1[t - 1]; gp.ld1 = l.np; gp.X = ws + l.D2[t - 1]; gp.ldx = B; gp.nB = B;
-            launch_gemm(GEMM_TN, gp, 1, st);
+            launch_gemm(TRAIN_GEMM, GEMM_TN, gp, 1, st);
         } else {
-            GemmArgs gr = gemm_args(W[2 * t], N, Zb, l.ncols, out, l.ncols, N, (int)l.nrev, M);
+            GemmArgs gr = gemm_args(w.W[t], N, Zb, l.ncols, out, l.ncols, N, (int)l.nrev, M);
             gr.epi = EPI_MUL;
             if (t > 0) { gr.D1 = ws + l.D1[t - 1]; gr.ld1 = l.np; gr.np_split = l.np; }
-            launch_gemm(GEMM_TN, gr, 1, st);
+            launch_gemm(TRAIN_GEMM, GEMM_TN, gr, 1, st);
         }
         zi ^= 1;
     }

@@ -28,7 +28,7 @@ import torch
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
-from .engine import CpuEngine, Engine, PndfError, SecondOrderEngine, TrainEngine, state_dict_order, stream_handle
+from .engine import CpuEngine, Engine, PndfError, SecondOrderEngine, StreamWorkspaces, TrainEngine, state_dict_order, stream_handle
 from .modules import DFNet, StructureEncoder
 
 
@@ -159,7 +159,7 @@ class PoseNDF(nn.Module):
         self._train_engines = {}    # device index -> TrainEngine
         self._so_engines = {}       # device index -> SecondOrderEngine
         self._so_params = None      # (the _param_list it was made from, the Parameters in state-dict order)
-        self._so_workspaces = {}    # (device index, stream) -> workspace tensor, grown on demand
+        self._so_workspaces = StreamWorkspaces(torch.float32)
         self._engines = {}          # device index -> (Engine, weight fingerprint)
         self._param_list = None     # cached list(self.parameters()): walking the module tree costs 0.15 ms per call
 
@@ -315,11 +315,9 @@ class PoseNDF(nn.Module):
         if any(p.device != q.device or p.dtype != torch.float32 or not p.is_contiguous() for p in params):
             raise PndfError("the second order reads the parameters in place: contiguous fp32 on the pose's device")
         n = eng.workspace_floats(B)
-        stream = stream_handle(q.device)
-        ws = self._so_workspaces.get((idx, stream))      # one per stream: calls on one stream run in order, so they may share it
-        if ws is None or ws.numel() < n:
-            ws = self._so_workspaces[(idx, stream)] = torch.empty(n, device=q.device, dtype=torch.float32)
-        eng.second_order([p.data_ptr() for p in params], q.data_ptr(), v.data_ptr(), *ptr, B, ws.data_ptr() if n else None, ws.numel(), stream)
+        ws = self._so_workspaces.get(q.device, n)
+        eng.second_order([p.data_ptr() for p in params], q.data_ptr(), v.data_ptr(), *ptr, B, ws.data_ptr() if n else None, ws.numel(),
+                         stream_handle(q.device))
         return outs
 
     @torch.no_grad()

@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
-from .engine import CpuEngine, PndfError, SkeletonEngine, state_dict_order, stream_handle
+from .engine import CpuEngine, PndfError, SkeletonEngine, StreamWorkspaces, state_dict_order, stream_handle
 from .facade import gradient
 from .modules import DFNet, StructureEncoder
 from .synth import BONE_DIM, FEAT, PARENT
@@ -106,7 +106,7 @@ class SkeletonPoseNDF(nn.Module):
         self._enc_beta = float(strenc.get("beta", self._beta)) if self.enc is not None else None
         self._hidden = list(dfnet["dims"])
         self._engines = {}        # device index or "cpu" -> [engine, weight fingerprint]
-        self._workspaces = {}     # (device index, stream) -> workspace tensor, grown on demand
+        self._workspaces = StreamWorkspaces(torch.uint8)
 
     def train(self, mode=True):
         super().train(mode)
@@ -137,11 +137,7 @@ class SkeletonPoseNDF(nn.Module):
 
     def _workspace(self, eng, q, B):
         """(pointer, bytes) of this stream's workspace on q's device for B poses"""
-        n = eng.workspace_bytes(B)
-        key = (q.device.index if q.device.index is not None else torch.cuda.current_device(), stream_handle(q.device))
-        ws = self._workspaces.get(key)
-        if ws is None or ws.numel() < n:
-            ws = self._workspaces[key] = torch.empty(max(n, 16), device=q.device, dtype=torch.uint8)
+        ws = self._workspaces.get(q.device, max(eng.workspace_bytes(B), 16))
         return ws.data_ptr(), ws.numel()
 
     def _poses(self, pose):
