@@ -275,6 +275,11 @@ def stream_handle(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream if device.type == "cuda" else 0
 
 
+def device_index(device) -> int:
+    """the index of a cuda torch.device, the current device's for a bare "cuda": the key of every per-device cache"""
+    return device.index if device.index is not None else torch.cuda.current_device()
+
+
 class StreamWorkspaces:
     """A unit's workspace tensors, one per (device index, stream) and grown on demand: calls on one stream run in order, so they
     may share one.  `dtype` is the unit the entry point counts the workspace in (float32, or uint8 for bytes)."""
@@ -285,7 +290,7 @@ class StreamWorkspaces:
 
     def get(self, device, n):
         """a tensor of at least `n` elements on `device` (a cuda torch.device) for the caller's current stream"""
-        key = (device.index if device.index is not None else torch.cuda.current_device(), stream_handle(device))
+        key = (device_index(device), stream_handle(device))
         ws = self._tensors.get(key)
         if ws is None or ws.numel() < n:
             ws = self._tensors[key] = torch.empty(n, device=device, dtype=self.dtype)

@@ -1,15 +1,9 @@
 """`PoseNDF` -- drop-in for the reference class of the same name (reference model/posendf.py:30-101).
 
-Same constructor (`PoseNDF(opt)` reading the keys of configs/amass.yaml that the reference reads),
-same `forward(pose, dist_gt=None, man_poses=None, train=True, eikonal=0.0)` signature and return
-values, same parameter tree / state-dict keys.  With train=False the distance and its input gradient
-come from the fused HIP kernel through the C ABI (include/posendf_amd.h); `project()` runs the whole
-projection loop of experiments/sample_poses.py:67-74 in one persistent launch.
-
-There is no fallback on the inference path: a pose on a `cuda` device runs on the HIP engine or raises (no built
-library, no gfx950 device).  A model whose config says `train.device: cpu` -- the reference's class works there too,
-posendf.py:35,64 -- runs train=False on the library's host twins (`pndf_*_cpu`, plain C++ on the host cores),
-selected by the pose's device alone, never by a failure of the device path.
+Same constructor (`PoseNDF(opt)` reading the keys of configs/amass.yaml that the reference reads) and the same
+`forward(pose, dist_gt=None, man_poses=None, train=True, eikonal=0.0)` signature and return values, on the 21-joint table of
+get_parent_mapping('smpl'); the model layer it shares with `SkeletonPoseNDF` is posendf_amd.model_base.PoseModel.  A cuda model's
+train=False and `project()` run on the fused persistent kernels (include/posendf_amd.h).
 
 `forward(train=True)` runs on the stock PyTorch modules unless `opt['engine']['train'] = 'hip'`: then a cuda model's training
 objective and every weight gradient come from csrc/pndf_train.hip (posendf_amd.train.TrainObjective), again with no fallback.
@@ -25,55 +19,11 @@ import os
 import warnings
 
 import torch
-import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
-from .engine import CpuEngine, Engine, PndfError, SecondOrderEngine, StreamWorkspaces, TrainEngine, state_dict_order, stream_handle
-from .modules import DFNet, StructureEncoder
-
-
-def gradient(inputs, outputs):
-    """reference model/posendf.py:18-27: d(sum outputs)/d inputs with create_graph/retain_graph."""
-    ones = torch.ones_like(outputs, requires_grad=False, device=outputs.device)
-    return torch.autograd.grad(outputs=outputs, inputs=inputs, grad_outputs=ones, create_graph=True,
-                               retain_graph=True, only_inputs=True)[0]
-
-
-def _distance_launch(pose, owner, want_grad):
-    """dist_pred [B,1] and, when asked for, d dist / d pose [B,21,4] (else None) from ONE kernel launch"""
-    q = pose.detach()
-    if q.dtype != torch.float32 or not q.is_contiguous():
-        q = q.float().contiguous()
-    B = q.shape[0]
-    d = torch.empty(B, device=q.device, dtype=torch.float32)
-    eng = owner._engine_for(q.device)
-    stream = stream_handle(q.device)
-    dq = None
-    if want_grad:
-        dq = torch.empty_like(q)
-        eng.forward_grad(q.data_ptr(), None, d.data_ptr(), dq.data_ptr(), B, stream)
-    else:
-        eng.forward(q.data_ptr(), d.data_ptr(), B, stream)
-    return d.view(B, 1), dq
-
-
-class _Distance(torch.autograd.Function):
-    """dist_pred = f(pose) with first-order autograd: backward(g) = g * d dist / d pose.
-    Both come from ONE kernel launch; double backward is not provided (train=True path has it)."""
-
-    @staticmethod
-    def forward(ctx, pose, owner):
-        d, dq = _distance_launch(pose, owner, ctx.needs_input_grad[0])
-        if dq is not None:
-            ctx.save_for_backward(dq)
-        ctx.pose_dtype = pose.dtype
-        return d
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_out):
-        (dq,) = ctx.saved_tensors
-        return (grad_out.reshape(-1, 1, 1).to(dq.dtype) * dq).to(ctx.pose_dtype), None
+from .engine import Engine, PndfError, SecondOrderEngine, StreamWorkspaces, TrainEngine, device_index, state_dict_order, stream_handle
+from .model_base import PoseModel, _Distance, cached, gradient  # noqa: F401  (`gradient` is part of this module's surface)
+from .synth import PARENT
 
 
 class _Distance2(torch.autograd.Function):
@@ -82,7 +32,7 @@ class _Distance2(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pose, owner):
-        d, dq = _distance_launch(pose, owner, ctx.needs_input_grad[0])
+        d, dq = owner._launch(pose, ctx.needs_input_grad[0])
         if dq is not None:
             ctx.save_for_backward(pose, dq)
         ctx.owner = owner
@@ -113,33 +63,16 @@ class _DistanceGrad(torch.autograd.Function):
         return (out.to(pose.dtype) if need_pose else None, t.reshape(grad_out.shape).to(grad_out.dtype) if need_go else None, None, None)
 
 
-class PoseNDF(nn.Module):
+class PoseNDF(PoseModel):
     def __init__(self, opt):
-        super().__init__()
-        self.device = opt["train"]["device"]                       # posendf.py:35
-        self.enc = None
-        if opt["model"]["StrEnc"]["use"]:                          # posendf.py:41-42
-            self.enc = StructureEncoder(opt["model"]["StrEnc"]).to(self.device)
-        self.dfnet = DFNet(opt["model"]["DFNet"]).to(self.device)  # posendf.py:44
-        self.loss = opt["train"]["loss_type"]
+        super().__init__(opt, PARENT)
         self.batch_size = opt["train"]["batch_size"]
-        if self.loss == "l1":
-            self.loss_l1 = nn.L1Loss()
-        elif self.loss == "l2":
-            self.loss_l1 = nn.MSELoss()
         # engine knob (no reference counterpart): arithmetic of the trunk -- "fp32" (exact fp32 MFMA), "f16x3" (fp16
         # hi/lo split, fp32 accumulate: fp32-class accuracy, same parity gates, ~3x the throughput), "auto" (default:
         # f16x3, or fp32 with a warning when a layer's weights are outside the split's operating range), "f16"
         # / "bf16" (reduced precision, ONE MFMA per product block: the measured comparison points of BASELINE.json configs[2] "fp32 vs
         # bf16", outside the 1e-4 parity bar, relu family only); opt["engine"]["precision"] or $PNDF_PRECISION
         self._precision = (opt.get("engine") or {}).get("precision") or os.environ.get("PNDF_PRECISION", "auto")
-        self._act = opt["model"]["DFNet"]["act"]
-        self._beta = float(opt["model"]["DFNet"].get("beta", 100.0))
-        # model.StrEnc.act / beta are read on their own (net_modules.py:128, :116-128); every config of the reference sets them equal
-        # to DFNet's.  A mixed pair runs on the runtime-planned kernels (csrc/pndf_generic.hip).
-        self._enc_act = opt["model"]["StrEnc"]["act"] if self.enc is not None else None
-        self._enc_beta = float(opt["model"]["StrEnc"].get("beta", self._beta)) if self.enc is not None else None
-        self._hidden = list(opt["model"]["DFNet"]["dims"])       # net_modules.py:14-28; narrower than amass.yaml: zero padded
         # engine knob (no reference counterpart): where forward(train=True) runs for a cuda model -- "torch" (default: the stock
         # modules below) or "hip" (the objective and every weight gradient on csrc/pndf_train.hip, posendf_amd.train; no fallback:
         # PndfError without the library or a gfx950 device).  A model whose train.device is cpu keeps the stock path either way.
@@ -160,115 +93,47 @@ class PoseNDF(nn.Module):
         self._so_engines = {}       # device index -> SecondOrderEngine
         self._so_params = None      # (the _param_list it was made from, the Parameters in state-dict order)
         self._so_workspaces = StreamWorkspaces(torch.float32)
-        self._engines = {}          # device index -> (Engine, weight fingerprint)
-        self._param_list = None     # cached list(self.parameters()): walking the module tree costs 0.15 ms per call
-
-    # ---- nn.Module conveniences the reference callers rely on -----------------------------------
-    def train(self, mode=True):     # the reference override returns None (posendf.py:58-59); returning
-        super().train(mode)         # self keeps statement-style callers working and fixes chaining
-        return self
 
     # ---- engine plumbing -----------------------------------------------------------------------
-    def _fingerprint(self):
-        """(storage, version) of every parameter.  Walking the module tree costs 0.15 ms per call, so the walk is cached as
-        (owner module, name, Parameter) triples plus the (parent, name, child) links of the tree -- and VALIDATED by identity
-        on every call (~140 dict lookups): a Parameter or submodule replaced by attribute assignment
-        (`net.dfnet.lin0.weight = nn.Parameter(...)`, `net.dfnet = DFNet(...)`) rebuilds the cache and so re-packs."""
-        c = self._param_list
-        if c is not None:
-            links, leaves = c
-            if not (all(par._modules.get(n) is ch for par, n, ch in links)
-                    and all(m._parameters.get(n) is p for m, n, p in leaves)):
-                c = None
-        if c is None:
-            links = [(par, n, ch) for par in self.modules() for n, ch in par._modules.items()]
-            leaves = [(m, n, p) for m in self.modules() for n, p in m._parameters.items() if p is not None]
-            if len(leaves) != len(list(self.parameters())):      # shared / parametrised tensors: no cache, full walk
-                return tuple((p.data_ptr(), p._version) for p in self.parameters())
-            c = self._param_list = (links, leaves)
-        return tuple((p.data_ptr(), p._version) for _, _, p in c[1])
+    def _new_engine(self, idx):
+        # the plain-f16 / plain-bf16 comparison kernels are relu-family only; fp32 and f16x3 implement all three activations
+        prec = "fp32" if (self._act == "softplus" and self._precision in ("f16", "bf16")) else self._precision
+        eng = Engine(device=idx, precision="f16x3" if prec == "auto" else prec, **self._net_kw)
+        if prec == "auto":      # a drop-in of an fp32 model picks an arithmetic on the caller's behalf: say so, once per engine
+            logging.getLogger("posendf_amd").info(
+                "PoseNDF on cuda:%s: precision 'auto' runs the split-precision kernels (f16x3: fp32 operands as fp16 hi + lo, "
+                "three fp16 MFMAs per product block, fp32 accumulate; same parity gates as the exact kernel); "
+                "opt['engine'] = {'precision': 'fp32'} or PNDF_PRECISION=fp32 selects the exact fp32 MFMA kernel", idx)
+        return eng
 
-    def _apply(self, fn, *args, **kwargs):          # .to() / .float() / .cuda(): parameters may be replaced
-        self._param_list = None
-        return super()._apply(fn, *args, **kwargs)
+    def _engine_after_refusal(self, eng, err):
+        if self._precision != "auto" or eng.precision != "f16x3" or "operating" not in str(err):
+            return None
+        # both are HIP kernels: this is a choice of arithmetic, not a fallback off the engine
+        warnings.warn(f"posendf_amd: {err}; precision 'auto' selects the exact fp32 kernel for this network")
+        return Engine(device=eng.device, precision="fp32", **self._net_kw)
 
-    def load_state_dict(self, *args, **kwargs):     # assign=True replaces the Parameter objects
-        self._param_list = None
-        return super().load_state_dict(*args, **kwargs)
-
-    def _engine_for(self, device):
-        if device.type not in ("cuda", "cpu"):
-            raise PndfError(f"PoseNDF inference runs on the HIP engine (cuda) or the host twins (cpu), not on {device}")
-        host = device.type == "cpu"
-        idx = "cpu" if host else (device.index if device.index is not None else torch.cuda.current_device())
-        fp = self._fingerprint()
-        entry = self._engines.get(idx)
-        if entry is None and host:
-            entry = self._engines[idx] = [CpuEngine(self._act, self._beta, encoder=self.enc is not None, hidden=self._hidden,
-                                                    enc_act=self._enc_act, enc_beta=self._enc_beta), None]
-        if entry is None:
-            # the plain-f16 / plain-bf16 comparison kernels are relu-family only; fp32 and f16x3 implement all three activations
-            prec = "fp32" if (self._act == "softplus" and self._precision in ("f16", "bf16")) else self._precision
-            entry = [Engine(self._act, self._beta, idx, precision="f16x3" if prec == "auto" else prec,
-                            encoder=self.enc is not None, hidden=self._hidden, enc_act=self._enc_act, enc_beta=self._enc_beta), None]
-            self._engines[idx] = entry
-            if prec == "auto":      # a drop-in of an fp32 model picks an arithmetic on the caller's behalf: say so, once per engine
-                logging.getLogger("posendf_amd").info(
-                    "PoseNDF on cuda:%s: precision 'auto' runs the split-precision kernels (f16x3: fp32 operands as fp16 hi + lo, "
-                    "three fp16 MFMAs per product block, fp32 accumulate; same parity gates as the exact kernel); "
-                    "opt['engine'] = {'precision': 'fp32'} or PNDF_PRECISION=fp32 selects the exact fp32 MFMA kernel", idx)
-        if entry[1] != fp:          # first use, load_state_dict, optimiser step, .to(): re-pack the weights
-            sd = self.state_dict()
-            weights = {k: sd[k].detach().float().cpu().numpy() for k in state_dict_order(self.enc is not None, len(self._hidden) + 1)}
-            try:
-                entry[0].load_weights(weights)
-            except PndfError as e:
-                if self._precision != "auto" or entry[0].precision != "f16x3" or "operating" not in str(e):
-                    raise
-                # both are HIP kernels: this is a choice of arithmetic, not a fallback off the engine
-                warnings.warn(f"posendf_amd: {e}; precision 'auto' selects the exact fp32 kernel for this network")
-                entry[0] = Engine(self._act, self._beta, idx, precision="fp32", encoder=self.enc is not None,
-                                  hidden=self._hidden, enc_act=self._enc_act, enc_beta=self._enc_beta)
-                entry[0].load_weights(weights)
-            entry[1] = fp
-        return entry[0]
+    def _engine_args(self, eng, device, B):
+        return (stream_handle(device),)
 
     # ---- reference API -------------------------------------------------------------------------
     def forward(self, pose, dist_gt=None, man_poses=None, train=True, eikonal=0.0):
-        pose = pose.to(device=self.device).reshape(-1, 21, 4)      # posendf.py:64
+        pose = pose.to(device=self.device).reshape(-1, self.num_joints, 4)      # posendf.py:64
         if not train:
             fn = _Distance2 if self._second_order_mode == "hip" else _Distance
             return {"dist_pred": fn.apply(pose, self)}             # posendf.py:100-101
         if self._train_backend == "hip" and pose.device.type == "cuda":
             return self._forward_train_hip(pose, dist_gt, man_poses, eikonal)
-        # ------ training objective: stock PyTorch modules (posendf.py:65-99)
-        pose.requires_grad = True
-        dist_gt = dist_gt.to(device=self.device).reshape(-1)
-        x = torch.nn.functional.normalize(pose, dim=1)             # joint-axis normalisation, posendf.py:71
-        if self.enc:
-            x = self.enc(x)
-        dist_pred = self.dfnet(x)
-        man = man_poses.to(device=self.device).reshape(-1, 21, 4)
-        dist_man = self.dfnet(self.enc(man) if self.enc else man)
-        loss = self.loss_l1(dist_pred[:, 0], dist_gt)
-        loss_man = dist_man.abs().mean()
-        grad_val = gradient(pose, dist_pred)
-        if eikonal > 0.0:
-            eik = ((grad_val.norm(2, dim=-1) - 1) ** 2).mean()
-            return loss, {"dist": loss, "man_loss": loss_man, "eikonal": eik}
-        return loss, {"dist": loss}
+        return self._objective(pose, dist_gt, man_poses, eikonal)
 
     def _forward_train_hip(self, pose, dist_gt, man_poses, eikonal):
         """posendf.py:65-99 on the HIP engine: the same (loss, loss_dict), `loss` and loss_dict['dist'] the same tensor."""
         from .train import LOSS_CODES, TrainObjective
-        idx = pose.device.index if pose.device.index is not None else torch.cuda.current_device()
-        eng = self._train_engines.get(idx)
-        if eng is None:
-            eng = self._train_engines[idx] = TrainEngine(self._act, self._beta, idx, hidden=self._hidden, enc_act=self._enc_act,
-                                                         enc_beta=self._enc_beta)
+        idx = device_index(pose.device)
+        eng = cached(self._train_engines, idx, lambda: TrainEngine(device=idx, **self._net_kw))
         named = dict(self.named_parameters())
         params = [named[k] for k in state_dict_order(True, len(self._hidden) + 1)]
-        man = man_poses.to(device=self.device).reshape(-1, 21, 4)
+        man = man_poses.to(device=self.device).reshape(-1, self.num_joints, 4)
         eik = eikonal > 0.0
         loss, loss_man, loss_eik = TrainObjective.apply(eng, pose, dist_gt.to(device=self.device).reshape(-1), man,
                                                         LOSS_CODES[self.loss], eik, *params)
@@ -291,12 +156,12 @@ class PoseNDF(nn.Module):
         where `want` is False.  q, v: [B,21,4]; w_d, w_t: [B] or None (0 and 1)."""
         def f32(x):
             return None if x is None else x.detach().to(device=q.device, dtype=torch.float32).contiguous()
-        q = f32(q.reshape(-1, 21, 4))
+        q = f32(q.reshape(-1, self.num_joints, 4))
         B = q.shape[0]
-        v = f32(v.reshape(B, 21, 4))
+        v = f32(v.reshape(q.shape))
         w_d = f32(w_d if w_d is None else w_d.reshape(B))
         w_t = f32(w_t if w_t is None else w_t.reshape(B))
-        shapes = ((B,), (B, 21, 4), (B,), (B, 21, 4))
+        shapes = ((B,), q.shape, (B,), q.shape)
         outs = [torch.empty(s, device=q.device, dtype=torch.float32) if w else None for s, w in zip(shapes, want)]
         ptr = [None if x is None or B == 0 else x.data_ptr() for x in (w_d, w_t, *outs)]
         if q.device.type == "cpu":
@@ -306,11 +171,8 @@ class PoseNDF(nn.Module):
             raise PndfError(f"the second order runs on the HIP engine (cuda) or the host twin (cpu), not on {q.device}")
         if self.enc is None:
             raise PndfError("the second order needs the structure encoder (model.StrEnc.use: True)")
-        idx = q.device.index if q.device.index is not None else torch.cuda.current_device()
-        eng = self._so_engines.get(idx)
-        if eng is None:
-            eng = self._so_engines[idx] = SecondOrderEngine(self._act, self._beta, idx, hidden=self._hidden, enc_act=self._enc_act,
-                                                            enc_beta=self._enc_beta)
+        idx = device_index(q.device)
+        eng = cached(self._so_engines, idx, lambda: SecondOrderEngine(device=idx, **self._net_kw))
         params = self._ordered_parameters()
         if any(p.device != q.device or p.dtype != torch.float32 or not p.is_contiguous() for p in params):
             raise PndfError("the second order reads the parameters in place: contiguous fp32 on the pose's device")
@@ -326,40 +188,23 @@ class PoseNDF(nn.Module):
         directions [B,21,4] and per-pose weights w_d (default 0), w_t (default 1) returns (d [B,1], grad [B,21,4] = d d / d pose,
         t [B,1] = <v, grad>, out [B,21,4] = w_d grad + w_t H v) with H the Hessian of the distance in the pose, the weights of the
         network held constant.  Exact fp32 on the HIP engine for cuda poses, the host twin for a `train.device: cpu` model."""
-        q = pose.to(device=self.device).reshape(-1, 21, 4)
+        q = pose.to(device=self.device).reshape(-1, self.num_joints, 4)
         d, g, t, out = self._second_order(q, v, w_d, w_t)
         return d.view(-1, 1), g, t.view(-1, 1), out
 
-    @torch.no_grad()
-    def project(self, noisy_poses, steps=100, return_dist=True, *, step_size=1.0, renormalize=None, tol=0.0):
-        """experiments/sample_poses.py:67-74 as ONE persistent kernel: `steps` times
-        q <- q - dist_pred(q) * d dist_pred / d q.  Returns (poses [B,21,4], dist [B,1] of the last
-        iteration).
-
-        Step options (keyword only; the defaults are the reference's bare loop, bit for bit): `step_size` alpha scales the step,
-        q <- q - alpha (d grad); `renormalize` = "unit" divides every joint quaternion of an updated pose by its norm (clamped at
-        1e-12 like F.normalize), "unit_flip" also negates those with a negative real part; `tol` > 0 leaves a pose with
-        dist_pred < tol unchanged.  The input is used as given; `dist` stays the distance evaluated before the last update."""
-        q = noisy_poses.to(device=self.device).reshape(-1, 21, 4).float().contiguous()
-        out = torch.empty_like(q)
-        d = torch.empty(q.shape[0], device=q.device, dtype=torch.float32)
-        eng = self._engine_for(q.device)
-        eng.project(q.data_ptr(), out.data_ptr(), d.data_ptr(), q.shape[0], int(steps), stream_handle(q.device),
-                    step_size=step_size, renorm=renormalize, tol=tol)
-        return (out, d.view(-1, 1)) if return_dist else out
-
     @staticmethod
-    def pack_observed(observed, B, device):
+    def pack_observed(observed, B, device, num_joints=len(PARENT)):
         """bool [21] or [B,21] (True = the joint is observed and held) -> one word per pose, bit j = joint j, as an int32 tensor [B]
         on `device` (the uint32 of include/posendf_amd_completion.h: bits 0 .. 20 only, so the sign bit is never set)"""
         obs = torch.as_tensor(observed, device=device)
         if obs.dtype != torch.bool:
             raise PndfError(f"observed must be a bool tensor, not {obs.dtype}")
-        if obs.shape == (21,):
-            obs = obs.expand(B, 21)
-        if obs.shape != (B, 21):
-            raise PndfError(f"observed must have shape [21] or [{B}, 21], not {list(obs.shape)}")
-        bits = torch.ones(21, dtype=torch.int64, device=device) << torch.arange(21, device=device)
+        J = num_joints
+        if obs.shape == (J,):
+            obs = obs.expand(B, J)
+        if obs.shape != (B, J):
+            raise PndfError(f"observed must have shape [{J}] or [{B}, {J}], not {list(obs.shape)}")
+        bits = torch.ones(J, dtype=torch.int64, device=device) << torch.arange(J, device=device)
         return (obs.to(torch.int64) * bits).sum(dim=1).to(torch.int32).contiguous()
 
     @torch.no_grad()
@@ -369,11 +214,11 @@ class PoseNDF(nn.Module):
         bit for bit.  Each of the `steps` steps is one forward + gradient launch and one small masked update kernel on the
         caller's stream (include/posendf_amd_completion.h); a `train.device: cpu` model runs the host twin.  Returns and step options:
         as `project`."""
-        q = poses.to(device=self.device).reshape(-1, 21, 4).float().contiguous()
+        q = poses.to(device=self.device).reshape(-1, self.num_joints, 4).float().contiguous()
         B = q.shape[0]
         out = torch.empty_like(q)
         d = torch.empty(B, device=q.device, dtype=torch.float32)
-        mask = None if observed is None else self.pack_observed(observed, B, q.device)
+        mask = None if observed is None else self.pack_observed(observed, B, q.device, self.num_joints)
         eng = self._engine_for(q.device)
         ws = torch.empty(eng.complete_workspace_floats(B), device=q.device, dtype=torch.float32)
         eng.complete(q.data_ptr(), None if mask is None or B == 0 else mask.data_ptr(), out.data_ptr(), d.data_ptr(), B, int(steps),
@@ -393,23 +238,24 @@ class PoseNDF(nn.Module):
         one forward + gradient launch and one band kernel on the caller's stream (include/posendf_amd_interpolation.h); a
         `train.device: cpu` model runs the host twin.  The inputs are not written.  Returns (track [P,frames,21,4], dist
         [P,frames] of the last iteration); step options: as `project`, with unit quaternions as the default."""
-        a = pose_a.to(device=self.device).reshape(-1, 21, 4).float().contiguous()
-        b = pose_b.to(device=self.device).reshape(-1, 21, 4).float().contiguous()
+        J = self.num_joints
+        a = pose_a.to(device=self.device).reshape(-1, J, 4).float().contiguous()
+        b = pose_b.to(device=self.device).reshape(-1, J, 4).float().contiguous()
         P, T = a.shape[0], int(frames)
         if b.shape[0] != P:
             raise PndfError(f"pose_a holds {P} poses, pose_b {b.shape[0]}")
         if T < 2:
             raise PndfError(f"an interpolation has at least two frames, not {frames}")
-        track = torch.empty((P, T, 21, 4), device=a.device, dtype=torch.float32)
+        track = torch.empty((P, T, J, 4), device=a.device, dtype=torch.float32)
         d = torch.empty((P, T), device=a.device, dtype=torch.float32)
         mask = None
         if observed is not None:
             obs = torch.as_tensor(observed, device=a.device)
-            if obs.dtype == torch.bool and obs.shape == (T, 21):
-                obs = obs.expand(P, T, 21)
-            if obs.dtype == torch.bool and obs.shape == (P, T, 21):
-                obs = obs.reshape(P * T, 21)
-            mask = self.pack_observed(obs, P * T, a.device)
+            if obs.dtype == torch.bool and obs.shape == (T, J):
+                obs = obs.expand(P, T, J)
+            if obs.dtype == torch.bool and obs.shape == (P, T, J):
+                obs = obs.reshape(P * T, J)
+            mask = self.pack_observed(obs, P * T, a.device, J)
         eng = self._engine_for(a.device)
         ws = torch.empty(eng.interpolate_workspace(P, T), device=a.device, dtype=torch.float32)
         eng.interpolate(a.data_ptr(), b.data_ptr(), None if mask is None or P == 0 else mask.data_ptr(), track.data_ptr(), d.data_ptr(), P, T,

@@ -50,25 +50,26 @@ class PoseCompletion(SamplePose):
         K = int(hypotheses)
         if K < 1:
             raise ValueError(f"hypotheses must be at least 1, not {hypotheses}")
-        q = poses.to(self.device).reshape(-1, 21, 4).float()
+        J = self.pose_prior.num_joints
+        q = poses.to(self.device).reshape(-1, J, 4).float()
         B = q.shape[0]
-        obs = torch.zeros(B, 21, dtype=torch.bool, device=q.device) if observed is None else torch.as_tensor(observed, device=q.device)
-        if obs.dtype != torch.bool or obs.shape not in ((21,), (B, 21)):
-            raise ValueError(f"observed must be a bool tensor of shape [21] or [{B}, 21]")
-        obs = obs.expand(B, 21)
-        start = q[:, None].expand(B, K, 21, 4)
+        obs = torch.zeros(B, J, dtype=torch.bool, device=q.device) if observed is None else torch.as_tensor(observed, device=q.device)
+        if obs.dtype != torch.bool or obs.shape not in ((J,), (B, J)):
+            raise ValueError(f"observed must be a bool tensor of shape [{J}] or [{B}, {J}]")
+        obs = obs.expand(B, J)
+        start = q[:, None].expand(B, K, J, 4)
         if fill == "random":
-            rand = torch.nn.functional.normalize(torch.rand((B, K, 21, 4), generator=generator), dim=-1).to(q.device)
+            rand = torch.nn.functional.normalize(torch.rand((B, K, J, 4), generator=generator), dim=-1).to(q.device)
             start = torch.where(obs[:, None, :, None], start, rand)
-        start = start.reshape(B * K, 21, 4).contiguous()
-        mask = obs[:, None].expand(B, K, 21).reshape(B * K, 21)
+        start = start.reshape(B * K, J, 4).contiguous()
+        mask = obs[:, None].expand(B, K, J).reshape(B * K, J)
         out, dist = self.pose_prior.complete(start, mask, steps=steps, step_size=step_size, renormalize=renormalize, tol=tol)
-        out, dist = out.view(B, K, 21, 4), dist.view(B, K)
-        start = start.view(B, K, 21, 4)
+        out, dist = out.view(B, K, J, 4), dist.view(B, K)
+        start = start.view(B, K, J, 4)
         best = best_hypothesis(dist) if select == "best" else None
         meshes = {}
         if self.body_model is not None:
-            pick = (lambda x: x.reshape(B * K, 21, 4)) if best is None else (lambda x: x[torch.arange(B, device=x.device), best])
+            pick = (lambda x: x.reshape(B * K, J, 4)) if best is None else (lambda x: x[torch.arange(B, device=x.device), best])
             meshes["pose_init"], meshes["vertices_init"], _ = self._mesh(pick(start))
             meshes["pose"], meshes["vertices"], meshes["joints"] = self._mesh(pick(out))
         return (out, dist, meshes) if best is None else (out, dist, best, meshes)

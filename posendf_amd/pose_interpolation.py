@@ -33,15 +33,16 @@ class PoseInterpolation(SamplePose):
         a track even).  Returns (track [P,frames,21,4], dist [P,frames] of the last iteration, meshes).  With a body model, meshes
         holds 'pose_init' / 'vertices_init' of the filled track (steps = 0) and 'pose' / 'vertices' / 'joints' of the relaxed one,
         P * frames rows each; without one it is empty."""
-        a = pose_a.to(self.device).reshape(-1, 21, 4).float()
-        b = pose_b.to(self.device).reshape(-1, 21, 4).float()
+        J = self.pose_prior.num_joints
+        a = pose_a.to(self.device).reshape(-1, J, 4).float()
+        b = pose_b.to(self.device).reshape(-1, J, 4).float()
         kw = dict(mode=mode, observed=observed, step_size=step_size, renormalize=renormalize, tol=tol)
         track, dist = self.pose_prior.interpolate(a, b, frames, steps=steps, smooth=smooth, **kw)
         meshes = {}
         if self.body_model is not None:
             start = self.pose_prior.interpolate(a, b, frames, steps=0, smooth=smooth, return_dist=False, **kw)
-            meshes["pose_init"], meshes["vertices_init"], _ = self._mesh(start.reshape(-1, 21, 4))
-            meshes["pose"], meshes["vertices"], meshes["joints"] = self._mesh(track.reshape(-1, 21, 4))
+            meshes["pose_init"], meshes["vertices_init"], _ = self._mesh(start.reshape(-1, J, 4))
+            meshes["pose"], meshes["vertices"], meshes["joints"] = self._mesh(track.reshape(-1, J, 4))
         return track, dist, meshes
 
 

@@ -2,7 +2,7 @@
 """The reference's OWN loop, statement by statement, around the drop-in class (experiments/sample_poses.py:67-74:
 `net(q, train=False)` -> `gradient(q, dist_pred)` -> `q = q - dist_pred * grad`): wall time per iteration at the reference's batch
 sizes, beside the fused `project()` and the same loop around the PyTorch-ROCm restatement.  What a user who switches the import and
-changes nothing else gets.  One JSON line per batch size.  usage: python tools/bench_dropin_loop.py [act]"""
+changes nothing else gets.  One JSON line per batch size.  usage: python tools/bench_dropin_loop.py [act [batch ...]]"""
 import json
 import os
 import sys
@@ -17,6 +17,7 @@ from posendf_amd.facade import gradient  # noqa: E402
 from oracle.posendf_torch import RefNet  # noqa: E402  (the comparator, never the product path)
 
 ACT = sys.argv[1] if len(sys.argv) > 1 else "lrelu"
+BATCHES = [int(b) for b in sys.argv[2:]] or [1, 10, 300, 4096, 65536]
 ITERS = 10
 dev = torch.device("cuda:0")
 sd = synth.make_weights(0, 2.0, 0.1)
@@ -50,7 +51,7 @@ def timed(fn, reps=7):
     return best
 
 
-for B in (1, 10, 300, 4096, 65536):
+for B in BATCHES:
     q0 = torch.from_numpy(synth.make_poses(B, seed=1234)).to(dev)
     t_loop = timed(lambda: loop(net, q0, lambda m, q: m(q, train=False)["dist_pred"]))
     t_proj = timed(lambda: net.project(q0, steps=ITERS))
