@@ -272,7 +272,8 @@ const char* pndf_lbs_last_error(pndf_lbs_handle h);    /* h may be NULL: last er
  *   normalisation, as in the reference),  eikonal = mean_{b,j} (|d d / d q[b,j,:]|_2 - 1)^2.
  * The handle carries the plan: the architecture of the config, i.e. every network that pndf_create accepts with the structure
  * encoder (an encoder-less config is PNDF_ERR_UNSUPPORTED: the reference cannot train one either); exact fp32 MFMA, `precision`
- * is ignored.
+ * is ignored.  A handle of posendf_amd_skeleton_train.h's pndf_skel_train_create plans any joint tree of J = 1 .. 32 joints: for it
+ * read [B,J,4] / [Bm,J,4] for the poses, 4 J encoder tensors in front of the trunk's, and the eikonal mean over b and the J joints.
  * Compute calls take DEVICE pointers, enqueue on `stream` and allocate nothing: all scratch is `workspace`
  * (pndf_train_workspace_floats(h, B, Bm, eikonal) floats, 16-byte aligned), which carries the forward's state to the backward.
  * Weights are read in place: `weights` is a HOST array of DEVICE pointers in state-dict order (the tensors of pndf_load_weights,
@@ -320,7 +321,8 @@ int pndf_adam_step(float* p, const float* g, float* m, float* v, int64_t n, int3
  * poses themselves (load_data.py:63 flips the noisy poses into the manifold batch instead; that is not reproduced).
  * pose_db, man_db, q, dist_gt, q_man 16-byte aligned.  The offsets live on the device and are not read back: an item that
  * names a file outside 0 .. F-1 (Fm-1) or an empty file gets NaN poses and a NaN label and nothing is read out of bounds;
- * callers refuse empty files when they load the data set.  F, Fm, k < 1, a negative count, a null or misaligned pointer:
+ * callers refuse empty files when they load the data set.  posendf_amd_skeleton_train.h's pndf_skel_train_batch is this call for
+ * poses [.,J,4] of any joint count.  F, Fm, k < 1, a negative count, a null or misaligned pointer:
  * PNDF_ERR_BAD_ARG; items == 0 or num_pts == 0: no-op. */
 int pndf_train_batch(const float* pose_db, const float* dist_db, const float* man_db, const int64_t* file_off,
                      const int64_t* man_off, const int32_t* item_file, const int32_t* item_man_file, const uint32_t* words,

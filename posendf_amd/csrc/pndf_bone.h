@@ -1,24 +1,27 @@
 // The structure encoder of the layer-by-layer units (csrc/pndf_train.hip, csrc/pndf_second_order.hip, csrc/pndf_skeleton.hip), on
 // top of pndf_gemm.h.  Device side: one bone MLP as a dual number (its input gather, its forward with the tangent, its reverse with
 // the primal and the tangent adjoint: DESIGN.md section 2s, "The dual-number bone"), the pieces of normalize(q, dim=1), the table
-// of the encoder's 84 tensors.  Host side: what the two 21-joint units refuse of a network and ask of its tensors; the plan
-// itself, LayerNet, is pndf_net_plan.h's.  Each unit keeps what is its own: training the LDS reduction of the weight gradient,
-// the second order the curvature of the normalisation, the skeleton unit the joint count at run time.  Everything is in an
-// unnamed namespace, instantiated per translation unit as in pndf_gemm.h.
+// of the encoder's 4 J tensors.  Host side: what training and the second order refuse of a network and ask of its tensors; the
+// plan itself, LayerNet, is pndf_net_plan.h's.  Each unit keeps what is its own: training the LDS reduction of the weight
+// gradient, the second order the curvature of the normalisation and the 21 joints its kernels are compiled for; training and the
+// skeleton unit take the joint count at run time.  Everything is in an unnamed namespace, instantiated per translation unit as in
+// pndf_gemm.h.
 #pragma once
 #include "pndf_gemm.h"
 #include "pndf_net_plan.h"
 
 namespace {
 
-constexpr int NJ = 21, FEAT = 6, HID = 10, BONE = 4;
+constexpr int NJ = 21, FEAT = 6, HID = 10, BONE = 4;      // NJ and what follows from it: the SMPL table, for the second order
 constexpr int ENC_IN = NJ * FEAT;          // 126: the encoder's output, the trunk's input
 constexpr int POSE = NJ * BONE;            // 84
 constexpr int MAX_LIN = PNDF_NET_MAX_LIN;  // 1 .. 7 hidden layers -> 2 .. 8 linear layers
 constexpr int ENC_TENSORS = 4 * NJ;        // 84
+constexpr int MAXJ = PNDF_SKEL_MAX_JOINTS; // the units that take the joint count at run time: 1 .. 32 joints
+constexpr int MAX_ENC_TENSORS = 4 * MAXJ;  // 128
 constexpr float NORM_EPS = 1e-12f;         // F.normalize
 
-// ---- encoder: 21 bone MLPs (4 | 10 -> 10 -> 6), the weights packed in state-dict order into one flat array
+// ---- encoder: one bone MLP per joint (4 | 10 -> 10 -> 6), the weights packed in state-dict order into one flat array
 template <int FIN>
 __device__ __forceinline__ void bone_lin0(const float* w, const float* in, float* zh, bool bias) {
 #pragma unroll
@@ -137,11 +140,11 @@ __device__ __forceinline__ void bone_input_adj(const float* w, const BoneAdj& r,
     }
 }
 
-// ---- x = normalize(q, dim=1): over the joint axis, per quaternion component k (a column of 21 joints)
-// the norms of a pose's four columns
-__device__ __forceinline__ void pose_col_norms(const float* q, float* nrm) {
+// ---- x = normalize(q, dim=1): over the joint axis, per quaternion component k (a column of nj joints)
+// the norms of a pose's four columns, the joints summed in index order
+__device__ __forceinline__ void pose_col_norms(const float* q, int nj, float* nrm) {
     float n2[BONE] = {0.f, 0.f, 0.f, 0.f};
-    for (int j = 0; j < NJ; ++j)
+    for (int j = 0; j < nj; ++j)
 #pragma unroll
         for (int k = 0; k < BONE; ++k) n2[k] = fmaf(q[j * BONE + k], q[j * BONE + k], n2[k]);
 #pragma unroll
@@ -155,41 +158,51 @@ __device__ __forceinline__ float norm_jvp(float v, float x, float a, float nrm, 
     return live ? (v - x * a) / nrm : v / NORM_EPS;
 }
 
-// ---- the caller's 84 encoder tensors and their offsets in the flat array
-struct PtrTable {
-    float* p[ENC_TENSORS];
-    int off[ENC_TENSORS + 1];
+// ---- the caller's encoder tensors and their offsets in the flat array: a table of NT entries of which the first n are live
+// (n = NT = 84 in the second order; training sizes it for 32 joints and takes n = 4 J from the plan)
+template <int NT>
+struct PtrTableOf {
+    float* p[NT];
+    int off[NT + 1];
 };
+using PtrTable = PtrTableOf<ENC_TENSORS>;
 
-__device__ __forceinline__ void enc_pack_body(const PtrTable& t, float* dst) {
+template <int NT>
+__device__ __forceinline__ void enc_pack_body(const PtrTableOf<NT>& t, int n, float* dst) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= t.off[ENC_TENSORS]) return;
+    if (i >= t.off[n]) return;
     int k = 0;
     while (t.off[k + 1] <= i) ++k;
     dst[i] = t.p[k][i - t.off[k]];
 }
 
 // ------------------------------------------------------------------------------------------------------------ host side
-// The networks training and the second order run: what pndf_net_plan.h accepts, with the 21 joints and the structure encoder their
-// kernels are compiled for.  Null, or why `cfg` is PNDF_ERR_UNSUPPORTED; `no_encoder`: the caller's text for a network without it.
-inline const char* layer_network_refusal(const pndf_config* cfg, const char* no_encoder) {
+// The networks training and the second order run: what pndf_net_plan.h accepts, with the structure encoder and -- unless
+// `any_tree`, the training plans of posendf_amd_skeleton_train.h -- the 21 joints the second order's kernels are compiled for.
+// Null, or why `cfg` is PNDF_ERR_UNSUPPORTED; `no_encoder`: the caller's text for a network without it.
+inline const char* layer_network_refusal(const pndf_config* cfg, const char* no_encoder, bool any_tree = false) {
     if (const char* why = pndf_skeleton_refusal(cfg)) return why;
-    if (cfg->num_joints != NJ) return "num_joints must be 21 (pndf_skel_create of posendf_amd_skeleton.h takes any joint tree)";
-    if (cfg->dims[0] != ENC_IN) return no_encoder;
+    if (!any_tree && cfg->num_joints != NJ)
+        return "num_joints must be 21 (pndf_skel_create of posendf_amd_skeleton.h and pndf_skel_train_create of "
+               "posendf_amd_skeleton_train.h take any joint tree)";
+    if (cfg->dims[0] != FEAT * cfg->num_joints) return no_encoder;
     return pndf_dfnet_refusal(cfg);
 }
 
-// the encoder's 84 tensors among the caller's `tensors` (weights, or gradients to write)
-inline PtrTable ptr_table(const LayerNet& n, const float* const* tensors) {
-    PtrTable t;
-    for (int k = 0; k < ENC_TENSORS; ++k) t.p[k] = const_cast<float*>(tensors[k]);
-    for (int k = 0; k <= ENC_TENSORS; ++k) t.off[k] = n.enc_tensor_off[k];
+// the encoder's 4 J tensors among the caller's `tensors` (weights, or gradients to write); the entries past them are null and
+// their offsets the end of the packed encoder
+template <int NT = ENC_TENSORS>
+inline PtrTableOf<NT> ptr_table(const LayerNet& n, const float* const* tensors) {
+    PtrTableOf<NT> t;
+    const int live = 4 * n.nj;
+    for (int k = 0; k < NT; ++k) t.p[k] = k < live ? const_cast<float*>(tensors[k]) : nullptr;
+    for (int k = 0; k <= NT; ++k) t.off[k] = n.enc_tensor_off[k < live ? k : live];
     return t;
 }
 
-// the first of the network's 84 + 2L tensors that is null in `a` (or in `b`, when given); -1: none
+// the first of the network's 4 J + 2L tensors that is null in `a` (or in `b`, when given); -1: none
 inline int null_tensor(const LayerNet& n, const float* const* a, const float* const* b = nullptr) {
-    for (int i = 0; i < ENC_TENSORS + 2 * n.L; ++i)
+    for (int i = 0; i < 4 * n.nj + 2 * n.L; ++i)
         if (!a[i] || (b && !b[i])) return i;
     return -1;
 }

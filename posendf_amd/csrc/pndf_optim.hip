@@ -3,6 +3,7 @@
 // host work, allocation or copy in between.
 //   pndf_train_batch_kernel   gathers the step's noisy poses, their labels' mean and the manifold poses out of a data set that
 //                             is resident on the device, from raw 32-bit random words: row = off[f] + (word * len_f >> 32).
+//                             The joint count is an argument (pndf_skel_train_batch; pndf_train_batch is 21 joints).
 //                             One thread per joint quaternion (one 16-byte load, one 16-byte store); the thread of joint 0 of a
 //                             noisy pose also reduces the pose's k labels, in index order.
 //   pndf_adam_step_kernel     torch.optim.Adam (coupled L2 weight decay, no amsgrad) over ONE flat buffer that holds every
@@ -14,7 +15,7 @@
 
 #include <cmath>
 
-#include "../../include/posendf_amd.h"
+#include "../../include/posendf_amd_skeleton_train.h"
 #include "pndf_experiment.h"
 #include "pndf_host.h"
 
@@ -22,7 +23,8 @@ PNDF_EXPORT_EXPERIMENT_WORD(optim)
 
 namespace {
 
-constexpr int NJ = 21;                 // joints = 16-byte quaternions per pose
+constexpr int SMPL_JOINTS = 21;        // pndf_train_batch: joints = 16-byte quaternions per pose
+constexpr int MAX_JOINTS = 32;         // pndf_config.parent[32]
 constexpr int MAX_BLOCKS = 2048;       // 256 CUs x 8 blocks of 256 threads; the rest of the buffer by grid stride
 
 struct AdamScalars {
@@ -81,8 +83,8 @@ struct BatchArgs {
     float4* q;
     float* dist_gt;
     float4* q_man;
-    long long quats;          // items * num_pts * 21: 16-byte elements per side
-    int F, Fm, k, num_pts, flip;
+    long long quats;          // items * num_pts * nj: 16-byte elements per side
+    int F, Fm, k, num_pts, flip, nj;
 };
 
 // Grid: the noisy side's quaternions, then the manifold side's.  A file index outside the table or an empty file cannot be
@@ -92,8 +94,8 @@ extern "C" __global__ void __launch_bounds__(256) pndf_train_batch_kernel(BatchA
     if (id >= 2 * a.quats) return;
     const int side = id >= a.quats;
     const long long e = side ? id - a.quats : id;
-    const long long pose = e / NJ;
-    const int j = (int)(e - pose * NJ);
+    const long long pose = e / a.nj;
+    const int j = (int)(e - pose * a.nj);
     const long long item = pose / a.num_pts;
     const int i = (int)(pose - item * a.num_pts);
     const int f = side ? a.item_man_file[item] : a.item_file[item];
@@ -113,7 +115,7 @@ extern "C" __global__ void __launch_bounds__(256) pndf_train_batch_kernel(BatchA
     }
     const unsigned w = a.words[(item * 2 + side) * a.num_pts + i];
     const long long row = first + (long long)(((unsigned long long)w * (unsigned long long)len) >> 32);
-    float4 x = (side ? a.man_db : a.pose_db)[row * NJ + j];
+    float4 x = (side ? a.man_db : a.pose_db)[row * a.nj + j];
     if (a.flip && x.x < 0.0f) x = make_float4(-x.x, -x.y, -x.z, -x.w);     // quat_flip, load_data.py:12-16
     out[e] = x;
     if (!side && j == 0) {
@@ -153,11 +155,12 @@ extern "C" int pndf_adam_step(float* p, const float* g, float* m, float* v, int6
     return hipGetLastError() == hipSuccess ? PNDF_OK : PNDF_ERR_HIP;
 }
 
-extern "C" int pndf_train_batch(const float* pose_db, const float* dist_db, const float* man_db, const int64_t* file_off,
-                                const int64_t* man_off, const int32_t* item_file, const int32_t* item_man_file,
-                                const uint32_t* words, int32_t F, int32_t Fm, int32_t k, int32_t items, int32_t num_pts,
-                                int32_t flip, float* q, float* dist_gt, float* q_man, void* stream) {
+extern "C" int pndf_skel_train_batch(const float* pose_db, const float* dist_db, const float* man_db, const int64_t* file_off,
+                                     const int64_t* man_off, const int32_t* item_file, const int32_t* item_man_file,
+                                     const uint32_t* words, int32_t F, int32_t Fm, int32_t k, int32_t items, int32_t num_pts,
+                                     int32_t flip, int32_t num_joints, float* q, float* dist_gt, float* q_man, void* stream) {
     PndfRange range("pndf_train_batch");
+    if (num_joints < 1 || num_joints > MAX_JOINTS) return PNDF_ERR_BAD_ARG;
     if (F < 1 || Fm < 1 || k < 1 || items < 0 || num_pts < 0) return PNDF_ERR_BAD_ARG;
     if (items == 0 || num_pts == 0) return PNDF_OK;
     if (!pose_db || !dist_db || !man_db || !file_off || !man_off || !item_file || !item_man_file || !words || !q || !dist_gt || !q_man)
@@ -165,7 +168,7 @@ extern "C" int pndf_train_batch(const float* pose_db, const float* dist_db, cons
     if ((((uintptr_t)pose_db) | ((uintptr_t)man_db) | ((uintptr_t)q) | ((uintptr_t)q_man) | ((uintptr_t)dist_gt)) & 15) return PNDF_ERR_BAD_ARG;
     if ((((uintptr_t)file_off) | ((uintptr_t)man_off)) & 7) return PNDF_ERR_BAD_ARG;
     if ((((uintptr_t)dist_db) | ((uintptr_t)item_file) | ((uintptr_t)item_man_file) | ((uintptr_t)words)) & 3) return PNDF_ERR_BAD_ARG;
-    const long long quats = (long long)items * num_pts * NJ;
+    const long long quats = (long long)items * num_pts * num_joints;
     const long long blocks = (2 * quats + 255) / 256;
     if (blocks > 0x7fffffffll) return PNDF_ERR_BAD_ARG;
     DeviceGuard guard(pndf_pointer_device(q));
@@ -183,7 +186,15 @@ extern "C" int pndf_train_batch(const float* pose_db, const float* dist_db, cons
     a.dist_gt = dist_gt;
     a.q_man = reinterpret_cast<float4*>(q_man);
     a.quats = quats;
-    a.F = F; a.Fm = Fm; a.k = k; a.num_pts = num_pts; a.flip = flip ? 1 : 0;
+    a.F = F; a.Fm = Fm; a.k = k; a.num_pts = num_pts; a.flip = flip ? 1 : 0; a.nj = num_joints;
     hipLaunchKernelGGL(pndf_train_batch_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? PNDF_OK : PNDF_ERR_HIP;
+}
+
+extern "C" int pndf_train_batch(const float* pose_db, const float* dist_db, const float* man_db, const int64_t* file_off,
+                                const int64_t* man_off, const int32_t* item_file, const int32_t* item_man_file,
+                                const uint32_t* words, int32_t F, int32_t Fm, int32_t k, int32_t items, int32_t num_pts,
+                                int32_t flip, float* q, float* dist_gt, float* q_man, void* stream) {
+    return pndf_skel_train_batch(pose_db, dist_db, man_db, file_off, man_off, item_file, item_man_file, words, F, Fm, k, items, num_pts,
+                                 flip, SMPL_JOINTS, q, dist_gt, q_man, stream);
 }

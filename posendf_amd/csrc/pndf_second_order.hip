@@ -135,7 +135,7 @@ extern "C" __global__ void __launch_bounds__(256) pndf_so_gemm_nn_kernel(GemmArg
 extern "C" __global__ void __launch_bounds__(256) pndf_so_gemm_tn_kernel(GemmArgs g) { gemm_body<0, 0>(g); }
 
 // the caller's 84 encoder tensors -> one flat array
-extern "C" __global__ void __launch_bounds__(256) pndf_so_enc_pack_kernel(PtrTable t, float* dst) { enc_pack_body(t, dst); }
+extern "C" __global__ void __launch_bounds__(256) pndf_so_enc_pack_kernel(PtrTable t, float* dst) { enc_pack_body(t, ENC_TENSORS, dst); }
 
 // x = normalize(q, dim=1) (over the joint axis, per quaternion component), xdot = J_N v, the encoder and its tangent
 extern "C" __global__ void __launch_bounds__(256) pndf_so_enc_fwd_kernel(SoArgs e) {
@@ -144,7 +144,7 @@ extern "C" __global__ void __launch_bounds__(256) pndf_so_enc_fwd_kernel(SoArgs 
     const float* q = e.q + c * POSE;
     const float* v = e.v + c * POSE;
     float nrm[BONE], a[BONE] = {0.f, 0.f, 0.f, 0.f};
-    pose_col_norms(q, nrm);
+    pose_col_norms(q, NJ, nrm);
     for (int j = 0; j < NJ; ++j)
 #pragma unroll
         for (int k = 0; k < BONE; ++k) {
@@ -182,7 +182,7 @@ extern "C" __global__ void __launch_bounds__(256) pndf_so_enc_rev_kernel(SoArgs 
     const float* q = e.q + c * POSE;
     const float* v = e.v + c * POSE;
     float s[BONE], a[BONE] = {0.f, 0.f, 0.f, 0.f}, b[BONE] = {0.f, 0.f, 0.f, 0.f}, xe[BONE] = {0.f, 0.f, 0.f, 0.f};
-    pose_col_norms(q, s);
+    pose_col_norms(q, NJ, s);
     for (int j = 0; j < NJ; ++j)
 #pragma unroll
         for (int k = 0; k < BONE; ++k) {

@@ -4,7 +4,7 @@
 // table (their MFMA encoder indexes registers by a compile-time parent); this unit is assembled layer by layer from shared pieces:
 //   pndf_net_plan.h   what is accepted of a skeleton and of a DFNet, and the plan (LayerNet) the handle derives from
 //   pndf_gemm.h       the 128 x 128 exact-fp32 MFMA GEMM and its epilogues; on the host trunk_forward / trunk_reverse
-//   pndf_bone.h       one bone MLP (bone_load / bone_fwd / bone_dual_rev without the primal chain / bone_input_adj), norm_x
+//   pndf_bone.h       one bone MLP (bone_load / bone_fwd / bone_dual_rev without the primal chain / bone_input_adj), pose_col_norms, norm_x
 //   pndf_step.h       the projection step of one joint quaternion
 // Here: the two encoder kernels with the joint count and the parent table as kernel arguments, the weights' device copy, the calls.
 //
@@ -40,7 +40,6 @@ namespace {
 // Poses per pass over the layers: a constant, so the chunk seams depend on B only (the value of the second order's SO_CHUNK,
 // whose sweep found two workgroups per compute unit on every layer worth more than a chunk inside the last-level cache).
 constexpr int64_t SK_CHUNK = 16384;
-constexpr int MAXJ = PNDF_SKEL_MAX_JOINTS;
 
 enum { SK_FORWARD = 0, SK_GRAD = 1, SK_PROJECT = 2 };
 
@@ -66,16 +65,6 @@ struct SkArgs {
     int parent[MAXJ];
     int off[MAXJ];
 };
-
-// the norms of a pose's four component columns over its nj joints (pose_col_norms of pndf_bone.h with the joint count at run time)
-__device__ __forceinline__ void skel_col_norms(const float* q, int nj, float* nrm) {
-    float n2[BONE] = {0.f, 0.f, 0.f, 0.f};
-    for (int j = 0; j < nj; ++j)
-#pragma unroll
-        for (int k = 0; k < BONE; ++k) n2[k] = fmaf(q[j * BONE + k], q[j * BONE + k], n2[k]);
-#pragma unroll
-    for (int k = 0; k < BONE; ++k) nrm[k] = sqrtf(n2[k]);
-}
 
 // bone j forward on column c: the parent's features are read back from act0 (a per-thread feature array indexed by a run-time
 // parent would live in scratch memory)
@@ -133,7 +122,7 @@ extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_fwd_kernel(SkArg
     if (c >= e.n) return;
     const float* q = e.q + c * (e.nj * BONE);
     float nrm[BONE];
-    skel_col_norms(q, e.nj, nrm);
+    pose_col_norms(q, e.nj, nrm);
     for (int j = 0; j < e.nj; ++j)
 #pragma unroll
         for (int k = 0; k < BONE; ++k) e.X[(int64_t)(j * BONE + k) * e.ld + c] = norm_x(q[j * BONE + k], nrm[k]);
@@ -158,7 +147,7 @@ extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_kernel(SkArg
     const float* q = e.q + c * nq;
     float* out = e.out + c * nq;
     float s[BONE], b[BONE] = {0.f, 0.f, 0.f, 0.f};
-    skel_col_norms(q, e.nj, s);      // before the first store: in project mode `out` may be `q`
+    pose_col_norms(q, e.nj, s);      // before the first store: in project mode `out` may be `q`
     for (int j = 0; j < e.nj; ++j)
 #pragma unroll
         for (int k = 0; k < BONE; ++k) {

@@ -7,12 +7,12 @@
 //   forward : encoder (noisy: x = normalize(q, dim=1); manifold: raw q) -> NN GEMMs over the B + Bm primal columns, epilogue
 //             bias + sigma, stores a, sigma' and (softplus) sigma'';  the losses.
 //   eikonal : input gradient of the noisy batch (TN GEMMs, epilogue * sigma'), encoder backward, G = J_N^T g_x, the seed
-//             Gbar = (2 / 21B)(|G_j| - 1) G_j / |G_j|, xdot = J_N Gbar, tangent encoder, tangent NN GEMMs (no bias, epilogue
+//             Gbar = (2 / JB)(|G_j| - 1) G_j / |G_j|, xdot = J_N Gbar, tangent encoder, tangent NN GEMMs (no bias, epilogue
 //             * sigma'; softplus: sigma'' zdot kept for the reverse).
 //   backward: one reverse pass over the dual network.  Seeds on the output, then per layer  Wbar = [zbar|zdotbar][a|adot]^T
 //             (NT GEMM, K split in a fixed way, partial slabs, a second launch sums them in order), bbar = row sums over the
 //             primal columns, [abar|adotbar] = W^T [zbar|zdotbar] (TN GEMM) with zbar = abar sigma' + adotbar zdot sigma''
-//             and zdotbar = adotbar sigma' in the epilogue; the 21 bone MLPs of the encoder last, lanes owning poses, their
+//             and zdotbar = adotbar sigma' in the epilogue; the J bone MLPs of the encoder last, lanes owning poses, their
 //             weight gradients summed per workgroup (fixed order) and then over workgroups (fixed order).
 // Shared with pndf_second_order.hip and pndf_skeleton.hip: the GEMM, its epilogues, the activation and the launcher (pndf_gemm.h);
 // the dual-number bone ("The dual-number bone") and the pieces of the normalisation (pndf_bone.h); the
@@ -21,6 +21,9 @@
 // sequences: column ranges of one [primal | tangent] matrix per layer, two leading dimensions, no ping-pong.
 // Arithmetic: exact fp32 MFMA (v_mfma_f32_16x16x4_f32), fp32 accumulate.  No float atomics, no communication between
 // workgroups inside a launch: two calls with the same inputs give the same bits.
+// The skeleton is a run-time value (include/posendf_amd_skeleton_train.h): J = 1 .. 32 joints, the parent table and every bone's
+// offset in the packed encoder from the plan.  A parent's features and adjoints are read back from the [6 J][ld] matrices, never
+// from a per-thread array indexed by the parent, so the encoder kernels use no scratch memory.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -31,7 +34,7 @@
 #include <string>
 #include <unordered_map>
 
-#include "../../include/posendf_amd.h"
+#include "../../include/posendf_amd_skeleton_train.h"
 #include "pndf_experiment.h"
 #include "pndf_bone.h"
 #include "pndf_host.h"
@@ -47,6 +50,8 @@ constexpr int ENC_LDS_LD = ENC_WG + 1;
 
 enum { LOSS_L1 = 0, LOSS_L2 = 1 };
 
+using EncTable = PtrTableOf<MAX_ENC_TENSORS>;      // the encoder's tensors of up to 32 joints; 4 J of them live
+
 }  // namespace
 
 extern "C" __global__ void __launch_bounds__(256) pndf_train_gemm_nn_kernel(GemmArgs g) { gemm_body<1, 0>(g); }
@@ -55,25 +60,25 @@ extern "C" __global__ void __launch_bounds__(256) pndf_train_gemm_nt_kernel(Gemm
 
 namespace {
 
-// ---- encoder: 21 bone MLPs (pndf_bone.h), the weights packed in state-dict order into one flat array
+// ---- encoder: J bone MLPs (pndf_bone.h), the weights packed in state-dict order into one flat array
 struct EncArgs {
     const float* wenc;        // packed encoder weights
-    const float* q;           // noisy poses [B][84]
-    const float* qm;          // manifold poses [Bm][84]
+    const float* q;           // noisy poses [B][4 J]
+    const float* qm;          // manifold poses [Bm][4 J]
     const float* dgt;         // labels [B]
-    float* X;                 // network input per primal column [84][np]: normalised noisy poses, raw manifold poses
+    float* X;                 // network input per primal column [4 J][np]: normalised noisy poses, raw manifold poses
     float* dgt_copy;          // [B]
-    float* act0;              // encoder output [126][ncols]
-    float* U0;                // d dist / d act0 of the noisy columns [126][B]
-    float* Xd;                // x gradient, then Gbar, then xdot [84][B]
+    float* act0;              // encoder output [6 J][ncols]
+    float* U0;                // d dist / d act0 of the noisy columns [6 J][B]
+    float* Xd;                // x gradient, then Gbar, then xdot [4 J][B]
     float* eikp;              // per pose: sum_j (|G_j| - 1)^2 [B]
-    float* abar;              // adjoint of act0 [126][ncols] (backward: accumulated in place)
+    float* abar;              // adjoint of act0 [6 J][ncols] (backward: accumulated in place)
     float* part;              // per-workgroup encoder weight-gradient partials [wgs][n_params]
     int64_t B, Bm, np, ncols;
-    int act, eik, n_params;
+    int act, eik, n_params, nj;
     float beta;
-    int parent[NJ];
-    int off[NJ];
+    int parent[MAXJ];
+    int off[MAXJ];
 };
 
 // bone j's input on primal column c (X and the parent's rows of act0), and its tangent on noisy column c (xdot in Xd and the
@@ -208,19 +213,20 @@ __device__ __forceinline__ float enc_param_sum(float (*sv)[ENC_LDS_LD], int t) {
 extern "C" __global__ void __launch_bounds__(256) pndf_train_enc_fwd_kernel(EncArgs e) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= e.np) return;
+    const int nq = e.nj * BONE;
     if (c < e.B) {
-        const float* q = e.q + c * POSE;
+        const float* q = e.q + c * nq;
         float nrm[BONE];
-        pose_col_norms(q, nrm);
-        for (int j = 0; j < NJ; ++j)
+        pose_col_norms(q, e.nj, nrm);
+        for (int j = 0; j < e.nj; ++j)
 #pragma unroll
             for (int k = 0; k < BONE; ++k) e.X[(int64_t)(j * BONE + k) * e.np + c] = norm_x(q[j * BONE + k], nrm[k]);
         e.dgt_copy[c] = e.dgt[c];
     } else {
-        const float* q = e.qm + (c - e.B) * POSE;
-        for (int f = 0; f < POSE; ++f) e.X[(int64_t)f * e.np + c] = q[f];
+        const float* q = e.qm + (c - e.B) * nq;
+        for (int f = 0; f < nq; ++f) e.X[(int64_t)f * e.np + c] = q[f];
     }
-    for (int j = 0; j < NJ; ++j) {
+    for (int j = 0; j < e.nj; ++j) {
         if (e.parent[j] < 0) enc_fwd_bone<BONE>(e, j, c);
         else enc_fwd_bone<BONE + FEAT>(e, j, c);
     }
@@ -231,22 +237,22 @@ extern "C" __global__ void __launch_bounds__(256) pndf_train_enc_fwd_kernel(EncA
 extern "C" __global__ void __launch_bounds__(256) pndf_train_enc_eik_kernel(EncArgs e) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= e.B) return;
-    for (int j = NJ - 1; j >= 0; --j) {
+    for (int j = e.nj - 1; j >= 0; --j) {
         if (e.parent[j] < 0) enc_grad_bone<BONE>(e, j, c);
         else enc_grad_bone<BONE + FEAT>(e, j, c);
     }
-    const float* q = e.q + c * POSE;
+    const float* q = e.q + c * (e.nj * BONE);
     float nrm[BONE], s[BONE] = {0.f, 0.f, 0.f, 0.f};
     bool live[BONE];
-    pose_col_norms(q, nrm);
+    pose_col_norms(q, e.nj, nrm);
 #pragma unroll
     for (int k = 0; k < BONE; ++k) live[k] = nrm[k] >= NORM_EPS;
-    for (int j = 0; j < NJ; ++j)
+    for (int j = 0; j < e.nj; ++j)
 #pragma unroll
         for (int k = 0; k < BONE; ++k) s[k] = fmaf(e.X[(int64_t)(j * BONE + k) * e.np + c], e.Xd[(int64_t)(j * BONE + k) * e.B + c], s[k]);
-    const float coef = 2.f / (21.f * (float)e.B);
+    const float coef = 2.f / ((float)e.nj * (float)e.B);
     float eik = 0.f, t[BONE] = {0.f, 0.f, 0.f, 0.f};
-    for (int j = 0; j < NJ; ++j) {
+    for (int j = 0; j < e.nj; ++j) {
         float G[BONE], x[BONE], n2 = 0.f;
 #pragma unroll
         for (int k = 0; k < BONE; ++k) {
@@ -266,14 +272,14 @@ extern "C" __global__ void __launch_bounds__(256) pndf_train_enc_eik_kernel(EncA
         }
     }
     e.eikp[c] = eik;
-    for (int j = 0; j < NJ; ++j)
+    for (int j = 0; j < e.nj; ++j)
 #pragma unroll
         for (int k = 0; k < BONE; ++k) {
             float* p = e.Xd + (int64_t)(j * BONE + k) * e.B + c;
             const float x = e.X[(int64_t)(j * BONE + k) * e.np + c];
             *p = norm_jvp(*p, x, t[k], nrm[k], live[k]);
         }
-    for (int j = 0; j < NJ; ++j) {
+    for (int j = 0; j < e.nj; ++j) {
         if (e.parent[j] < 0) enc_tan_bone<BONE>(e, j, c);
         else enc_tan_bone<BONE + FEAT>(e, j, c);
     }
@@ -288,7 +294,7 @@ extern "C" __global__ void __launch_bounds__(ENC_WG) pndf_train_enc_rev_kernel(E
     const int64_t P = e.eik ? e.np : e.B;
     const bool active = c < P, tangent = e.eik && c < e.B;
     float* part = e.part + (int64_t)blockIdx.x * e.n_params;
-    for (int j = NJ - 1; j >= 0; --j) {
+    for (int j = e.nj - 1; j >= 0; --j) {
         const bool root = e.parent[j] < 0;
         if (root) enc_rev_bone<BONE>(e, j, c, active, tangent, sv, lane);
         else enc_rev_bone<BONE + FEAT>(e, j, c, active, tangent, sv, lane);
@@ -299,15 +305,15 @@ extern "C" __global__ void __launch_bounds__(ENC_WG) pndf_train_enc_rev_kernel(E
     }
 }
 
-// the caller's 84 encoder tensors -> one flat array
-extern "C" __global__ void __launch_bounds__(256) pndf_train_enc_pack_kernel(PtrTable t, float* dst) {
-    enc_pack_body(t, dst);
+// the caller's 4 J encoder tensors (nt of them) -> one flat array
+extern "C" __global__ void __launch_bounds__(256) pndf_train_enc_pack_kernel(EncTable t, int nt, float* dst) {
+    enc_pack_body(t, nt, dst);
 }
 
-// per-workgroup partials -> the caller's 84 encoder gradient tensors, summed over workgroups in order
-extern "C" __global__ void __launch_bounds__(256) pndf_train_enc_reduce_kernel(PtrTable t, const float* part, int wgs) {
+// per-workgroup partials -> the caller's 4 J encoder gradient tensors, summed over workgroups in order
+extern "C" __global__ void __launch_bounds__(256) pndf_train_enc_reduce_kernel(EncTable t, int nt, const float* part, int wgs) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int n = t.off[ENC_TENSORS];
+    const int n = t.off[nt];
     if (i >= n) return;
     float s = 0.f;
     for (int w = 0; w < wgs; ++w) s += part[(int64_t)w * n + i];
@@ -342,7 +348,7 @@ extern "C" __global__ void __launch_bounds__(256) pndf_train_row_sum_kernel(cons
 
 // the three losses: one workgroup, fp64 partial sums in a fixed order
 extern "C" __global__ void __launch_bounds__(256) pndf_train_loss_kernel(const float* d, const float* dgt, const float* eikp, int64_t B,
-                                                                         int64_t Bm, int loss_type, int eik, float* losses) {
+                                                                         int64_t Bm, int nj, int loss_type, int eik, float* losses) {
     __shared__ double red[3][256];
     double s0 = 0.0, s1 = 0.0, s2 = 0.0;
     for (int64_t c = threadIdx.x; c < B; c += 256) {
@@ -363,7 +369,7 @@ extern "C" __global__ void __launch_bounds__(256) pndf_train_loss_kernel(const f
     if (threadIdx.x == 0) {
         losses[0] = (float)(red[0][0] / (double)B);
         losses[1] = (float)(red[1][0] / (double)Bm);
-        losses[2] = eik ? (float)(red[2][0] / (21.0 * (double)B)) : 0.f;
+        losses[2] = eik ? (float)(red[2][0] / ((double)nj * (double)B)) : 0.f;
     }
 }
 
@@ -424,12 +430,12 @@ Layout make_layout(const pndf_train_plan* h, int64_t B, int64_t Bm, int eik) {
     l.nrev = eik ? l.ncols : B;
     Carver c;
     l.wenc = c.take(h->enc_params);
-    l.X = c.take(POSE * l.np);
+    l.X = c.take((int64_t)h->nj * BONE * l.np);
     l.dgt = c.take(B);
     for (int t = 0; t <= h->L; ++t) l.act[t] = c.take((int64_t)h->dims[t] * l.ncols);
     for (int t = 0; t < h->L; ++t) l.D1[t] = c.take((int64_t)h->dims[t + 1] * l.np);
     for (int t = 0; t < h->L; ++t) l.D2[t] = (eik && h->act == PNDF_ACT_SOFTPLUS) ? c.take((int64_t)h->dims[t + 1] * B) : -1;
-    l.Xd = eik ? c.take(POSE * B) : -1;
+    l.Xd = eik ? c.take((int64_t)h->nj * BONE * B) : -1;
     l.eikp = eik ? c.take(B) : -1;
     // the two ping-pong adjoint buffers of the reverse pass; the forward's input-gradient pass uses the same memory
     l.Z[0] = c.take((int64_t)h->maxw * l.ncols);
@@ -472,8 +478,8 @@ EncArgs enc_args(const pndf_train_plan* h, const Layout& l, float* ws, int64_t B
     e.eikp = eik ? ws + l.eikp : nullptr;
     e.part = ws + l.part;
     e.B = B; e.Bm = Bm; e.np = l.np; e.ncols = l.ncols;
-    e.act = h->enc_act; e.beta = h->enc_beta; e.eik = eik; e.n_params = h->enc_params;
-    for (int j = 0; j < NJ; ++j) { e.parent[j] = h->parent[j]; e.off[j] = h->enc_off[j]; }
+    e.act = h->enc_act; e.beta = h->enc_beta; e.eik = eik; e.n_params = h->enc_params; e.nj = h->nj;
+    for (int j = 0; j < h->nj; ++j) { e.parent[j] = h->parent[j]; e.off[j] = h->enc_off[j]; }
     return e;
 }
 
@@ -481,12 +487,16 @@ EncArgs enc_args(const pndf_train_plan* h, const Layout& l, float* ws, int64_t B
 
 extern "C" const char* pndf_train_last_error(pndf_train_handle h) { return pndf_last_error_of(h); }
 
-extern "C" int pndf_train_create(pndf_train_handle* out, const pndf_config* cfg, int device) {
+namespace {
+
+const char* const NO_ENCODER = "training needs the structure encoder (model.StrEnc.use: True, dims[0] = 126): the reference's train=True "
+                               "branch cannot run without it either (man_pose_in is unbound)";
+
+// the two creates: one plan, refusals before a device is looked for; `any_tree`: every joint tree of pndf_net_plan.h, not SMPL's 21 alone
+int train_create(pndf_train_handle* out, const pndf_config* cfg, int device, bool any_tree) {
     if (!out || !cfg) return pndf_fail<pndf_train_plan>(nullptr, PNDF_ERR_BAD_ARG, "out / cfg is null");
     *out = nullptr;
-    if (const char* why = layer_network_refusal(cfg, "training needs the structure encoder (model.StrEnc.use: True, dims[0] = 126): the reference's train=True "
-                                                     "branch cannot run without it either (man_pose_in is unbound)"))
-        return pndf_fail<pndf_train_plan>(nullptr, PNDF_ERR_UNSUPPORTED, why);
+    if (const char* why = layer_network_refusal(cfg, NO_ENCODER, any_tree)) return pndf_fail<pndf_train_plan>(nullptr, PNDF_ERR_UNSUPPORTED, why);
     const PndfDeviceCheck dev = pndf_check_gfx950(device, "training");
     if (dev.code != PNDF_OK) return pndf_fail<pndf_train_plan>(nullptr, dev.code, dev.text);
     pndf_train_plan* h = new pndf_train_plan();
@@ -494,6 +504,12 @@ extern "C" int pndf_train_create(pndf_train_handle* out, const pndf_config* cfg,
     *out = h;
     return PNDF_OK;
 }
+
+}  // namespace
+
+extern "C" int pndf_train_create(pndf_train_handle* out, const pndf_config* cfg, int device) { return train_create(out, cfg, device, false); }
+
+extern "C" int pndf_skel_train_create(pndf_train_handle* out, const pndf_config* cfg, int device) { return train_create(out, cfg, device, true); }
 
 extern "C" int pndf_train_destroy(pndf_train_handle h) {
     delete h;
@@ -527,10 +543,11 @@ extern "C" int pndf_train_forward(pndf_train_handle h, const float* const* weigh
     }
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
-    const TrunkWeights w = trunk_weights(*h, weights + ENC_TENSORS);
+    const int nt = 4 * h->nj;      // the encoder's tensors, in front of the trunk's
+    const TrunkWeights w = trunk_weights(*h, weights + nt);
     const bool sp = h->act == PNDF_ACT_SOFTPLUS;
 
-    hipLaunchKernelGGL(pndf_train_enc_pack_kernel, dim3(blocks(h->enc_params)), dim3(256), 0, st, ptr_table(*h, weights), ws + l.wenc);
+    hipLaunchKernelGGL(pndf_train_enc_pack_kernel, dim3(blocks(h->enc_params)), dim3(256), 0, st, ptr_table<MAX_ENC_TENSORS>(*h, weights), nt, ws + l.wenc);
     EncArgs e = enc_args(h, l, ws, B, Bm, eik);
     e.q = q; e.qm = q_man; e.dgt = dist_gt;
     hipLaunchKernelGGL(pndf_train_enc_fwd_kernel, dim3(blocks(l.np)), dim3(256), 0, st, e);
@@ -568,7 +585,7 @@ extern "C" int pndf_train_forward(pndf_train_handle h, const float* const* weigh
         }
     }
     hipLaunchKernelGGL(pndf_train_loss_kernel, dim3(1), dim3(256), 0, st, ws + l.act[h->L], ws + l.dgt, eik ? ws + l.eikp : nullptr,
-                       B, Bm, (int)loss_type, eik, losses);
+                       B, Bm, h->nj, (int)loss_type, eik, losses);
     return pndf_check_launch(h, "pndf_train_forward");
 }
 
@@ -593,12 +610,13 @@ extern "C" int pndf_train_backward(pndf_train_handle h, const float* const* weig
     const Layout l = make_layout(h, B, Bm, eik);
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
-    const TrunkWeights w = trunk_weights(*h, weights + ENC_TENSORS);
-    float* const* G = grads + ENC_TENSORS;
+    const int nt = 4 * h->nj;      // the encoder's tensors, in front of the trunk's
+    const TrunkWeights w = trunk_weights(*h, weights + nt);
+    float* const* G = grads + nt;
     const bool cross = eik && h->act == PNDF_ACT_SOFTPLUS;
     const int64_t npr = eik ? l.np : B;          // primal columns of the reverse pass
 
-    hipLaunchKernelGGL(pndf_train_enc_pack_kernel, dim3(blocks(h->enc_params)), dim3(256), 0, st, ptr_table(*h, weights), ws + l.wenc);
+    hipLaunchKernelGGL(pndf_train_enc_pack_kernel, dim3(blocks(h->enc_params)), dim3(256), 0, st, ptr_table<MAX_ENC_TENSORS>(*h, weights), nt, ws + l.wenc);
     const int L = h->L;
     int zi = 0;
     hipLaunchKernelGGL(pndf_train_head_kernel, dim3(blocks(l.nrev)), dim3(256), 0, st, ws + l.act[L], ws + l.dgt, ws + l.D1[L - 1],
@@ -635,7 +653,7 @@ extern "C" int pndf_train_backward(pndf_train_handle h, const float* const* weig
     EncArgs e = enc_args(h, l, ws, B, Bm, eik);
     e.abar = ws + l.Z[zi];
     hipLaunchKernelGGL(pndf_train_enc_rev_kernel, dim3(l.enc_wgs), dim3(ENC_WG), 0, st, e);
-    hipLaunchKernelGGL(pndf_train_enc_reduce_kernel, dim3(blocks(h->enc_params)), dim3(256), 0, st, ptr_table(*h, grads), ws + l.part,
+    hipLaunchKernelGGL(pndf_train_enc_reduce_kernel, dim3(blocks(h->enc_params)), dim3(256), 0, st, ptr_table<MAX_ENC_TENSORS>(*h, grads), nt, ws + l.part,
                        l.enc_wgs);
     return pndf_check_launch(h, "pndf_train_backward");
 }

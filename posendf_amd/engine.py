@@ -66,9 +66,10 @@ class PndfError(RuntimeError):
 
 
 # ---- the C ABI, one table per header: name -> (restype, argtypes), in the header's order.  load_library() binds the tables, EXPORTS /
-# COMPLETION_EXPORTS / INTERPOLATION_EXPORTS / SECOND_ORDER_EXPORTS / ONLINE_EXPORTS / SKELETON_EXPORTS / DEBUG_EXPORTS are their names,
+# COMPLETION_EXPORTS / INTERPOLATION_EXPORTS / SECOND_ORDER_EXPORTS / ONLINE_EXPORTS / SKELETON_EXPORTS / SKELETON_TRAIN_EXPORTS /
+# DEBUG_EXPORTS are their names,
 # tests/test_cabi.py, tests/test_completion.py, tests/test_interpolation.py, tests/test_second_order.py, tests/test_online.py and
-# tests/test_skeleton.py hold them against the declarations of the headers.
+# tests/test_skeleton.py and tests/test_skeleton_train.py hold them against the declarations of the headers.
 _H = c_void_p                          # every handle type, and every `void* stream`
 _P = c_void_p                          # any other address: tensor data (an int from data_ptr(), or None), a callback, an out value
 _TENSORS = [POINTER(c_void_p), POINTER(c_int64), c_int]      # tensors, numel, n_tensors (host pointers in state-dict order)
@@ -193,12 +194,17 @@ _SKELETON_SIGNATURES = {      # include/posendf_amd_skeleton.h: distance, gradie
     "pndf_skel_project": (c_int, [_H, _P, _P, _P, c_int64, c_int, POINTER(ProjectOptions), _P, c_int64, _H]),
     "pndf_skel_last_error": (c_char_p, [_H]),
 }
+_SKELETON_TRAIN_SIGNATURES = {      # include/posendf_amd_skeleton_train.h: training any joint tree, the sixth companion header
+    "pndf_skel_train_create": (c_int, [POINTER(_H), POINTER(PndfConfig), c_int]),
+    "pndf_skel_train_batch": (c_int, [_P] * 8 + [c_int32] * 7 + [_P] * 3 + [_H]),
+}
 EXPORTS, DEBUG_EXPORTS = tuple(_SIGNATURES), tuple(_DEBUG_SIGNATURES)
 COMPLETION_EXPORTS = tuple(_COMPLETION_SIGNATURES)
 INTERPOLATION_EXPORTS = tuple(_INTERPOLATION_SIGNATURES)
 SECOND_ORDER_EXPORTS = tuple(_SECOND_ORDER_SIGNATURES)
 ONLINE_EXPORTS = tuple(_ONLINE_SIGNATURES)
 SKELETON_EXPORTS = tuple(_SKELETON_SIGNATURES)
+SKELETON_TRAIN_EXPORTS = tuple(_SKELETON_TRAIN_SIGNATURES)
 # per-translation-unit experiment words (csrc/pndf_experiment.h): data symbols, all zero in a product build
 EXPERIMENT_WORDS = ("pndf_experiment_word_capi", "pndf_experiment_word_fp32", "pndf_experiment_word_split", "pndf_experiment_word_split_x2",
                     "pndf_experiment_word_bf16", "pndf_experiment_word_lbs", "pndf_experiment_word_generic", "pndf_experiment_word_train",
@@ -253,7 +259,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         raise PndfError(f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                         "(hipcc --offload-arch=gfx950). The engine has no fallback path.")
     lib = _bind(_bind(_bind(_PndfLibrary(path), _SIGNATURES), _COMPLETION_SIGNATURES), _INTERPOLATION_SIGNATURES)
-    return _bind(_bind(_bind(lib, _SECOND_ORDER_SIGNATURES), _ONLINE_SIGNATURES), _SKELETON_SIGNATURES)
+    return _bind(_bind(_bind(_bind(lib, _SECOND_ORDER_SIGNATURES), _ONLINE_SIGNATURES), _SKELETON_SIGNATURES), _SKELETON_TRAIN_SIGNATURES)
 
 
 def experiment_word(lib=None) -> int:
@@ -585,16 +591,20 @@ class Engine(_Handle):
 
 class TrainEngine(_Handle):
     """`pndf_train_*` (csrc/pndf_train.hip): the training objective of model/posendf.py:62-99 and its weight gradients on one
-    device.  Exact fp32 MFMA; the structure encoder is required (the reference cannot train without it).  All compute methods
-    take raw device pointers (the weights and gradients as lists of them, state-dict order) and a stream handle."""
+    device.  Exact fp32 MFMA; the structure encoder is required (the reference cannot train without it).  `parents`: the parent
+    table of another skeleton (1 .. 32 joints), planned by pndf_skel_train_create of include/posendf_amd_skeleton_train.h; None =
+    the SMPL table through pndf_train_create.  All compute methods take raw device pointers (the weights and gradients as lists
+    of them, state-dict order; poses [B, num_joints, 4]) and a stream handle."""
     _destroy, _last_error = "pndf_train_destroy", "pndf_train_last_error"
 
     def __init__(self, act: str = "lrelu", beta: float = 100.0, device: int = 0, lib=None, encoder: bool = True, hidden=None,
-                 enc_act: str | None = None, enc_beta: float | None = None):
+                 enc_act: str | None = None, enc_beta: float | None = None, parents=None):
         self.lib = lib or load_library()
-        cfg = _network_config(self.lib, act, beta, encoder=encoder, hidden=hidden, enc_act=enc_act, enc_beta=enc_beta)
-        self.n_tensors = len(state_dict_order(encoder, cfg.n_dims - 1))
-        self._create("pndf_train_create", ctypes.byref(cfg), int(device))
+        cfg = _network_config(self.lib, act, beta, encoder=encoder, hidden=hidden, enc_act=enc_act, enc_beta=enc_beta, parents=parents)
+        self.parents = None if parents is None else tuple(int(p) for p in parents)
+        self.num_joints = int(cfg.num_joints)
+        self.n_tensors = len(state_dict_order(encoder, cfg.n_dims - 1, parents=self.parents))
+        self._create("pndf_train_create" if parents is None else "pndf_skel_train_create", ctypes.byref(cfg), int(device))
         self.device = device
         self.act = act
 
@@ -711,6 +721,17 @@ def train_batch(pose_db_ptr, dist_db_ptr, man_db_ptr, file_off_ptr, man_off_ptr,
                                                   int(bool(flip)), q_ptr, gt_ptr, qm_ptr, stream)
     if rc != 0:
         raise PndfError(f"pndf_train_batch failed ({rc}): F = {F}, Fm = {Fm}, k = {k}, items = {items}, num_pts = {num_pts}")
+
+
+def skel_train_batch(pose_db_ptr, dist_db_ptr, man_db_ptr, file_off_ptr, man_off_ptr, item_file_ptr, item_man_file_ptr, words_ptr, F, Fm, k,
+                     items, num_pts, flip, num_joints, q_ptr, gt_ptr, qm_ptr, stream=0, lib=None):
+    """`pndf_skel_train_batch` (csrc/pndf_optim.hip): `train_batch` for poses of `num_joints` joints"""
+    rc = (lib or load_library()).pndf_skel_train_batch(pose_db_ptr, dist_db_ptr, man_db_ptr, file_off_ptr, man_off_ptr, item_file_ptr,
+                                                       item_man_file_ptr, words_ptr, int(F), int(Fm), int(k), int(items), int(num_pts),
+                                                       int(bool(flip)), int(num_joints), q_ptr, gt_ptr, qm_ptr, stream)
+    if rc != 0:
+        raise PndfError(f"pndf_skel_train_batch failed ({rc}): F = {F}, Fm = {Fm}, k = {k}, items = {items}, num_pts = {num_pts}, "
+                        f"num_joints = {num_joints}")
 
 
 NOISE_CODES = {"uniform": 0, "symmetric": 1}               # PNDF_ONLINE_*

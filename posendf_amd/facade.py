@@ -6,7 +6,8 @@ get_parent_mapping('smpl'); the model layer it shares with `SkeletonPoseNDF` is 
 train=False and `project()` run on the fused persistent kernels (include/posendf_amd.h).
 
 `forward(train=True)` runs on the stock PyTorch modules unless `opt['engine']['train'] = 'hip'`: then a cuda model's training
-objective and every weight gradient come from csrc/pndf_train.hip (posendf_amd.train.TrainObjective), again with no fallback.
+objective and every weight gradient come from csrc/pndf_train.hip (posendf_amd.train.TrainObjective), again with no fallback; the
+knob is the model base's.
 
 `hvp(pose, v)` gives the distance, its pose gradient and Hessian-vector products with respect to the pose
 (include/posendf_amd_second_order.h); `opt['engine']['second_order'] = 'hip'` makes the train=False gradient itself differentiable
@@ -21,7 +22,7 @@ import warnings
 import torch
 from torch.autograd.function import once_differentiable
 
-from .engine import Engine, PndfError, SecondOrderEngine, StreamWorkspaces, TrainEngine, device_index, state_dict_order, stream_handle
+from .engine import Engine, PndfError, SecondOrderEngine, StreamWorkspaces, device_index, state_dict_order, stream_handle
 from .model_base import PoseModel, _Distance, cached, gradient  # noqa: F401  (`gradient` is part of this module's surface)
 from .synth import PARENT
 
@@ -73,15 +74,6 @@ class PoseNDF(PoseModel):
         # / "bf16" (reduced precision, ONE MFMA per product block: the measured comparison points of BASELINE.json configs[2] "fp32 vs
         # bf16", outside the 1e-4 parity bar, relu family only); opt["engine"]["precision"] or $PNDF_PRECISION
         self._precision = (opt.get("engine") or {}).get("precision") or os.environ.get("PNDF_PRECISION", "auto")
-        # engine knob (no reference counterpart): where forward(train=True) runs for a cuda model -- "torch" (default: the stock
-        # modules below) or "hip" (the objective and every weight gradient on csrc/pndf_train.hip, posendf_amd.train; no fallback:
-        # PndfError without the library or a gfx950 device).  A model whose train.device is cpu keeps the stock path either way.
-        self._train_backend = (opt.get("engine") or {}).get("train", "torch")
-        if self._train_backend not in ("torch", "hip"):
-            raise ValueError(f"opt['engine']['train'] must be 'torch' or 'hip', not {self._train_backend!r}")
-        if self._train_backend == "hip" and self.enc is None:
-            raise PndfError("opt['engine']['train'] = 'hip' needs the structure encoder (model.StrEnc.use: True): the reference's "
-                            "train=True branch cannot run without it either")
         # engine knob (no reference counterpart): "off" (default: the train=False gradient is once differentiable, a double backward
         # raises) or "hip" (it is differentiable once more, through pndf_second_order / its host twin; a third order raises)
         self._second_order_mode = (opt.get("engine") or {}).get("second_order", "off")
@@ -89,7 +81,6 @@ class PoseNDF(PoseModel):
             raise ValueError(f"opt['engine']['second_order'] must be 'off' or 'hip', not {self._second_order_mode!r}")
         if self._second_order_mode == "hip" and self.enc is None:
             raise PndfError("opt['engine']['second_order'] = 'hip' needs the structure encoder (model.StrEnc.use: True)")
-        self._train_engines = {}    # device index -> TrainEngine
         self._so_engines = {}       # device index -> SecondOrderEngine
         self._so_params = None      # (the _param_list it was made from, the Parameters in state-dict order)
         self._so_workspaces = StreamWorkspaces(torch.float32)
@@ -122,24 +113,7 @@ class PoseNDF(PoseModel):
         if not train:
             fn = _Distance2 if self._second_order_mode == "hip" else _Distance
             return {"dist_pred": fn.apply(pose, self)}             # posendf.py:100-101
-        if self._train_backend == "hip" and pose.device.type == "cuda":
-            return self._forward_train_hip(pose, dist_gt, man_poses, eikonal)
-        return self._objective(pose, dist_gt, man_poses, eikonal)
-
-    def _forward_train_hip(self, pose, dist_gt, man_poses, eikonal):
-        """posendf.py:65-99 on the HIP engine: the same (loss, loss_dict), `loss` and loss_dict['dist'] the same tensor."""
-        from .train import LOSS_CODES, TrainObjective
-        idx = device_index(pose.device)
-        eng = cached(self._train_engines, idx, lambda: TrainEngine(device=idx, **self._net_kw))
-        named = dict(self.named_parameters())
-        params = [named[k] for k in state_dict_order(True, len(self._hidden) + 1)]
-        man = man_poses.to(device=self.device).reshape(-1, self.num_joints, 4)
-        eik = eikonal > 0.0
-        loss, loss_man, loss_eik = TrainObjective.apply(eng, pose, dist_gt.to(device=self.device).reshape(-1), man,
-                                                        LOSS_CODES[self.loss], eik, *params)
-        if eik:
-            return loss, {"dist": loss, "man_loss": loss_man, "eikonal": loss_eik}
-        return loss, {"dist": loss}
+        return self._forward_train(pose, dist_gt, man_poses, eikonal)
 
     # ---- added surface (north_star: `.project` on the model) -------------------------------------
     def _ordered_parameters(self):

@@ -6,7 +6,11 @@ its input gradient come from ONE launch of the subclass's engine through the C A
 experiments/sample_poses.py:67-74 in one call.  There is no fallback on that path: a pose on a `cuda` device runs on the HIP engine or
 raises (no built library, no gfx950 device).  A model whose config says `train.device: cpu` -- the reference's class works there too,
 posendf.py:35,64 -- runs on the library's host twins (`pndf_*_cpu`, plain C++ on the host cores), selected by the
-pose's device alone, never by a failure of the device path.  `forward(train=True)` runs on the stock PyTorch modules.
+pose's device alone, never by a failure of the device path.
+
+`forward(train=True)` runs on the stock PyTorch modules unless `opt['engine']['train'] = 'hip'`: then a cuda model's training
+objective and every weight gradient come from csrc/pndf_train.hip (posendf_amd.train.TrainObjective) for the model's joint tree,
+again with no fallback.
 
 A subclass fills in `_new_engine` (which engine a cuda device gets), `_engine_args` (the trailing arguments of that engine's compute
 calls) and, where it has one, `_engine_after_refusal` (another engine for weights the first one refused).
@@ -17,7 +21,7 @@ import torch
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
-from .engine import CpuEngine, PndfError, device_index, state_dict_order
+from .engine import CpuEngine, PndfError, TrainEngine, device_index, state_dict_order
 from .modules import DFNet, StructureEncoder
 
 
@@ -84,6 +88,16 @@ class PoseModel(nn.Module):
         self._net_kw = dict(act=self._act, beta=self._beta, encoder=self.enc is not None, hidden=self._hidden, enc_act=self._enc_act,
                             enc_beta=self._enc_beta)
         self._engines = {}          # device index or "cpu" -> [engine, weight fingerprint]
+        # engine knob (no reference counterpart): where forward(train=True) runs for a cuda model -- "torch" (default: the stock
+        # modules below) or "hip" (the objective and every weight gradient on csrc/pndf_train.hip, posendf_amd.train; no fallback:
+        # PndfError without the library or a gfx950 device).  A model whose train.device is cpu keeps the stock path either way.
+        self._train_backend = (opt.get("engine") or {}).get("train", "torch")
+        if self._train_backend not in ("torch", "hip"):
+            raise ValueError(f"opt['engine']['train'] must be 'torch' or 'hip', not {self._train_backend!r}")
+        if self._train_backend == "hip" and self.enc is None:
+            raise PndfError("opt['engine']['train'] = 'hip' needs the structure encoder (model.StrEnc.use: True): the reference's "
+                            "train=True branch cannot run without it either")
+        self._train_engines = {}    # device index -> TrainEngine
         self._param_list = None     # the cached walk of the module tree, see _fingerprint
 
     # ---- nn.Module conveniences the reference callers rely on -----------------------------------
@@ -173,6 +187,28 @@ class PoseModel(nn.Module):
         return d.view(B, 1), dq
 
     # ---- reference API -------------------------------------------------------------------------
+    def _forward_train(self, pose, dist_gt, man_poses, eikonal):
+        """forward(train=True) for `pose` [B,J,4] on the model's device: the HIP objective for a cuda pose of a model whose
+        opt['engine']['train'] is 'hip', the stock modules otherwise"""
+        if self._train_backend == "hip" and pose.device.type == "cuda":
+            return self._forward_train_hip(pose, dist_gt, man_poses, eikonal)
+        return self._objective(pose, dist_gt, man_poses, eikonal)
+
+    def _forward_train_hip(self, pose, dist_gt, man_poses, eikonal):
+        """posendf.py:65-99 on the HIP engine: the same (loss, loss_dict), `loss` and loss_dict['dist'] the same tensor."""
+        from .train import LOSS_CODES, TrainObjective
+        idx = device_index(pose.device)
+        eng = cached(self._train_engines, idx, lambda: TrainEngine(device=idx, **self._net_kw))
+        named = dict(self.named_parameters())
+        params = [named[k] for k in state_dict_order(True, len(self._hidden) + 1, parents=self.parents)]
+        man = man_poses.to(device=self.device).reshape(-1, self.num_joints, 4)
+        eik = eikonal > 0.0
+        loss, loss_man, loss_eik = TrainObjective.apply(eng, pose, dist_gt.to(device=self.device).reshape(-1), man,
+                                                        LOSS_CODES[self.loss], eik, *params)
+        if eik:
+            return loss, {"dist": loss, "man_loss": loss_man, "eikonal": loss_eik}
+        return loss, {"dist": loss}
+
     def _objective(self, pose, dist_gt, man_poses, eikonal):
         """the training objective of model/posendf.py:65-99 on the stock PyTorch modules"""
         pose.requires_grad = True

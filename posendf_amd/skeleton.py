@@ -7,8 +7,10 @@ get_parent_mapping('smpl') on the persistent kernels; this class takes the table
 before its child, 1 .. 32 joints) or as a name of `SKELETONS`, and runs train=False on include/posendf_amd_skeleton.h: the
 layer-by-layer HIP unit for a cuda model, the first-order host twins for `train.device: cpu` (posendf_amd.model_base.PoseModel).
 
-`forward(train=True)` runs the stock PyTorch modules, so another skeleton trains through PyTorch autograd; the HIP training path,
-completion, interpolation and the second order stay 21-joint.
+`forward(train=True)` runs the stock PyTorch modules unless `opt['engine']['train'] = 'hip'`: then a cuda model's training objective
+and every weight gradient come from csrc/pndf_train.hip on a plan of include/posendf_amd_skeleton_train.h for this class's parent
+table, with no fallback, and `posendf_amd.trainer.Trainer` trains the skeleton end to end.  The second order,
+completion, interpolation, the k-NN index and the online sampler stay 21-joint.
 """
 from __future__ import annotations
 
@@ -88,4 +90,4 @@ class SkeletonPoseNDF(PoseModel):
         pose = pose.to(device=self.device).reshape(-1, self.num_joints, 4)
         if not train:
             return {"dist_pred": _Distance.apply(pose, self)}
-        return self._objective(pose, dist_gt, man_poses, eikonal)
+        return self._forward_train(pose, dist_gt, man_poses, eikonal)

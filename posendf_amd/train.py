@@ -1,5 +1,6 @@
-"""The training objective of `PoseNDF.forward(train=True)` on the HIP engine (csrc/pndf_train.hip, `pndf_train_*` of
-include/posendf_amd.h): what `opt['engine']['train'] = 'hip'` routes a cuda model's training step to."""
+"""The training objective of `PoseNDF.forward(train=True)` / `SkeletonPoseNDF.forward(train=True)` on the HIP engine
+(csrc/pndf_train.hip, `pndf_train_*` of include/posendf_amd.h, for another skeleton on a plan of
+include/posendf_amd_skeleton_train.h): what `opt['engine']['train'] = 'hip'` routes a cuda model's training step to."""
 from __future__ import annotations
 
 import torch
@@ -24,9 +25,10 @@ class TrainObjective(torch.autograd.Function):
     @staticmethod
     def forward(ctx, engine, pose, dist_gt, man_poses, loss_type, eikonal, *params):
         dev = pose.device
-        q = pose.detach().reshape(-1, 84).float().contiguous()
+        nq = 4 * engine.num_joints
+        q = pose.detach().reshape(-1, nq).float().contiguous()
         gt = dist_gt.detach().reshape(-1).float().contiguous()
-        qm = man_poses.detach().reshape(-1, 84).float().contiguous()
+        qm = man_poses.detach().reshape(-1, nq).float().contiguous()
         B, Bm = q.shape[0], qm.shape[0]
         if gt.numel() != B:
             raise PndfError(f"{gt.numel()} labels for {B} poses")

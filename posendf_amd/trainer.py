@@ -35,7 +35,11 @@ Differences from the reference, on purpose:
   * scalars go to <exp>/summary.jsonl (one JSON line per epoch), not to TensorBoard;
   * the data set is resident in memory (device memory on cuda): one that does not fit is refused with the byte count;
   * `data.online` (posendf_amd.online) replaces the frozen sample files by a pool that is redrawn and relabelled on the device
-    every `refresh_every` epochs; without it every code path is the file-based one.
+    every `refresh_every` epochs; without it every code path is the file-based one;
+  * another skeleton: when `model.StrEnc.parent_mapping` is set (a list or a name of posendf_amd.SKELETONS) the model is
+    `SkeletonPoseNDF(opt)`, the files hold `pose` [n,J,4] for its J joints and the cuda backend runs the same four calls on a plan
+    of include/posendf_amd_skeleton_train.h.  The k-NN index and the sampler of `data.online` are 21-joint: online data with
+    another table than SMPL's is refused.
 """
 from __future__ import annotations
 
@@ -49,8 +53,9 @@ import shutil
 import numpy as np
 import torch
 
-from .engine import PndfError, TrainEngine, adam_step, load_library, state_dict_order, stream_handle, train_batch
+from .engine import PndfError, TrainEngine, adam_step, load_library, skel_train_batch, state_dict_order, stream_handle
 from .facade import PoseNDF
+from .synth import PARENT as SMPL_PARENT
 from .train import LOSS_CODES
 
 LOSS_KEYS = ("dist", "man_loss", "eikonal")
@@ -70,13 +75,15 @@ def _subdirs(root, datasets):
 
 
 class PoseDataset:
-    """Every `<data_dir>/<dataset>/*.npz` (keys `pose` [n,21,4], `dist` [n,k]) and `<amass_dir>/<dataset>/*.npz` (key `pose`),
-    concatenated once and kept on `device`: pose [N,21,4], dist [N,k], man [M,21,4] fp32, file_off [F+1], man_off [Fm+1] int64.
-    `datasets` defaults to every subdirectory (as traindata.database_files).  Files are refused by name when `pose` is not
-    [n,21,4], when `dist` does not have one row per pose or has another k than the first file, and when they are empty (the
-    sampler cannot draw from them)."""
+    """Every `<data_dir>/<dataset>/*.npz` (keys `pose` [n,J,4], `dist` [n,k]) and `<amass_dir>/<dataset>/*.npz` (key `pose`),
+    concatenated once and kept on `device`: pose [N,J,4], dist [N,k], man [M,J,4] fp32, file_off [F+1], man_off [Fm+1] int64, for
+    poses of J = `num_joints` joints (21: SMPL).  `datasets` defaults to every subdirectory (as traindata.database_files).  Files are
+    refused by name when `pose` is not [n,J,4], when `dist` does not have one row per pose or has another k than the first file,
+    and when they are empty (the sampler cannot draw from them)."""
+    num_joints = 21      # (of the online data set, which sets none)
 
-    def __init__(self, data_dir, amass_dir, datasets=None, device="cpu"):
+    def __init__(self, data_dir, amass_dir, datasets=None, device="cpu", num_joints=21):
+        self.num_joints = int(num_joints)
         files, man_files = [], []
         for ds in _subdirs(data_dir, datasets):
             files += sorted(glob.glob(os.path.join(data_dir, ds, "*.npz")))
@@ -91,7 +98,7 @@ class PoseDataset:
             with np.load(f) as z:
                 if "pose" not in z.files or "dist" not in z.files:
                     raise ValueError(f"{f}: a data file holds `pose` and `dist`, this one {sorted(z.files)}")
-                poses.append(self._pose(f, z["pose"]))
+                poses.append(self._pose(f, z["pose"], self.num_joints))
                 d = np.asarray(z["dist"])
                 if d.ndim != 2 or len(d) != len(poses[-1]) or d.shape[1] < 1:
                     raise ValueError(f"{f}: dist is {d.shape}, expected [{len(poses[-1])}, k]")
@@ -102,17 +109,18 @@ class PoseDataset:
             with np.load(f) as z:
                 if "pose" not in z.files:
                     raise ValueError(f"{f}: a manifold file holds `pose`, this one {sorted(z.files)}")
-                mans.append(self._pose(f, z["pose"]))
+                mans.append(self._pose(f, z["pose"], self.num_joints))
         self._init(poses, dists, mans, device, files, man_files)
 
     @classmethod
-    def from_arrays(cls, poses, dists, mans, device="cpu"):
+    def from_arrays(cls, poses, dists, mans, device="cpu", num_joints=21):
         """the same from lists of arrays, one entry per file (tests, benchmarks)"""
         self = cls.__new__(cls)
+        self.num_joints = int(num_joints)
         names = [f"<data {i}>" for i in range(len(poses))]
         mnames = [f"<manifold {i}>" for i in range(len(mans))]
-        poses = [cls._pose(n, p) for n, p in zip(names, poses)]
-        mans = [cls._pose(n, p) for n, p in zip(mnames, mans)]
+        poses = [cls._pose(n, p, self.num_joints) for n, p in zip(names, poses)]
+        mans = [cls._pose(n, p, self.num_joints) for n, p in zip(mnames, mans)]
         dists = [np.ascontiguousarray(d, dtype=np.float32) for d in dists]
         for n, p, d in zip(names, poses, dists):
             if d.ndim != 2 or len(d) != len(p) or d.shape[1] != dists[0].shape[1] or d.shape[1] < 1:
@@ -121,10 +129,10 @@ class PoseDataset:
         return self
 
     @staticmethod
-    def _pose(name, p):
+    def _pose(name, p, num_joints=21):
         p = np.asarray(p)
-        if p.ndim != 3 or p.shape[1:] != (21, 4):
-            raise ValueError(f"{name}: pose is {p.shape}, expected [n, 21, 4]")
+        if p.ndim != 3 or p.shape[1:] != (num_joints, 4):
+            raise ValueError(f"{name}: pose is {p.shape}, expected [n, {num_joints}, 4]")
         if len(p) == 0:
             raise ValueError(f"{name}: an empty file cannot be sampled")
         if len(p) >= 2 ** 32:
@@ -140,7 +148,8 @@ class PoseDataset:
         self.file_off = np.concatenate([[0], np.cumsum([len(p) for p in poses])]).astype(np.int64)
         self.man_off = np.concatenate([[0], np.cumsum([len(p) for p in mans])]).astype(np.int64)
         N, M = int(self.file_off[-1]), int(self.man_off[-1])
-        self.nbytes = 4 * (N * 84 + N * self.k + M * 84) + 8 * (len(self.file_off) + len(self.man_off))
+        nq = 4 * self.num_joints
+        self.nbytes = 4 * (N * nq + N * self.k + M * nq) + 8 * (len(self.file_off) + len(self.man_off))
         if self.device.type == "cuda":
             free, _ = torch.cuda.mem_get_info(self.device)
             if self.nbytes > free:
@@ -179,6 +188,9 @@ class Trainer:
     max_epoch, loss_type, man_loss, dist, eikonal}, data.{data_dir, amass_dir, flip (False), num_pts (5000)} and
     experiment.{root_dir, exp_name}; `seed` feeds the initial weights and, with the epoch, every draw of the sampler.
     `dataset`: a PoseDataset to train on instead of the directories of `opt['data']`.
+
+    Another skeleton: with `model.StrEnc.parent_mapping` (a list, or a name of posendf_amd.SKELETONS) the model is
+    `SkeletonPoseNDF(opt)` and the data set holds poses of its J joints; without the key nothing changes.
 
     Online data (posendf_amd.online): with the mapping `data.online` = {files, rows, refresh_every (epochs, default 1), sigmas,
     shares, noise, k, metric, weighted} -- or an `OnlinePoseDataset` passed as `dataset` -- the noisy poses are a pool of files x
@@ -220,14 +232,24 @@ class Trainer:
 
         with torch.random.fork_rng(devices=[]):        # the initial weights: a function of `seed`, the global stream untouched
             torch.manual_seed(self.seed)
-            self.model = PoseNDF(opt).to(self.device)
+            if "parent_mapping" in opt["model"]["StrEnc"]:
+                from .skeleton import SkeletonPoseNDF
+                self.model = SkeletonPoseNDF(opt).to(self.device)
+            else:
+                self.model = PoseNDF(opt).to(self.device)
+        self.num_joints = self.model.num_joints
+        if self.online and tuple(self.model.parents) != tuple(SMPL_PARENT):
+            raise PndfError(f"online training data needs the SMPL table: the k-NN index and the sampler are 21-joint, this model has "
+                            f"the {self.num_joints}-joint table {list(self.model.parents)}")
         self.hip = self.device.type == "cuda"
         if self.hip and self.model.enc is None:
             raise PndfError("training on cuda needs the structure encoder (model.StrEnc.use: True), as opt['engine']['train'] = 'hip'")
         if dataset is None and online is not None:
             dataset = self._online_dataset(data, online)
         self.dataset = dataset if dataset is not None else PoseDataset(data["data_dir"], data["amass_dir"], data.get("datasets"),
-                                                                        self.device)
+                                                                        self.device, self.num_joints)
+        if self.dataset.num_joints != self.num_joints:
+            raise ValueError(f"the data set holds poses of {self.dataset.num_joints} joints, the model has {self.num_joints}")
         if self.dataset.device != self.device:
             raise ValueError(f"the data set is on {self.dataset.device}, the trainer on {self.device}")
         if self.dataset.F < self.batch_size:
@@ -253,7 +275,8 @@ class Trainer:
         m, dev = self.model, self.device
         self.lib = load_library()
         named = dict(m.named_parameters())
-        self._keys = state_dict_order(True, len(m._hidden) + 1)
+        skel = m._net_kw.get("parents")      # SkeletonPoseNDF: its table; PoseNDF: None, the SMPL plan of pndf_train_create
+        self._keys = state_dict_order(True, len(m._hidden) + 1, parents=skel)
         if set(self._keys) != set(named):
             raise PndfError("the model's parameters are not the reference's state dict")
         self._offsets, n = [], 0
@@ -275,10 +298,11 @@ class Trainer:
         tab = ctypes.c_void_p * len(self._keys)
         self._wtab = tab(*self._ptrs)
         self._gtab = tab(*[self.flat_g.data_ptr() + 4 * o for o in self._offsets])
-        self._engine = TrainEngine(m._act, m._beta, dev.index, lib=self.lib, hidden=m._hidden, enc_act=m._enc_act, enc_beta=m._enc_beta)
+        self._engine = TrainEngine(m._act, m._beta, dev.index, lib=self.lib, hidden=m._hidden, enc_act=m._enc_act, enc_beta=m._enc_beta,
+                                   parents=skel)
         self._ws = torch.empty(self._engine.workspace_floats(self.B, self.B, self.eikonal), dtype=torch.float32, device=dev)
-        self._q = torch.empty(self.B, 21, 4, dtype=torch.float32, device=dev)
-        self._qm = torch.empty(self.B, 21, 4, dtype=torch.float32, device=dev)
+        self._q = torch.empty(self.B, self.num_joints, 4, dtype=torch.float32, device=dev)
+        self._qm = torch.empty(self.B, self.num_joints, 4, dtype=torch.float32, device=dev)
         self._gt = torch.empty(self.B, dtype=torch.float32, device=dev)
         self._upstream = torch.tensor([self.loss_weight[k] for k in LOSS_KEYS], dtype=torch.float32, device=dev)
         self._log_dev = torch.zeros(self.steps_per_epoch, 3, dtype=torch.float32, device=dev)
@@ -380,10 +404,10 @@ class Trainer:
         ds, bs = self.dataset, self.batch_size
         self._check_homes()
         stream = stream_handle(self.device)
-        train_batch(ds.pose.data_ptr(), ds.dist.data_ptr(), ds.man.data_ptr(), ds.file_off_t.data_ptr(), ds.man_off_t.data_ptr(),
-                    self._item_file.data_ptr() + 4 * i * bs, self._item_man.data_ptr() + 4 * i * bs,
-                    self._words.data_ptr() + 4 * i * bs * 2 * self.num_pts, ds.F, ds.Fm, ds.k, bs, self.num_pts, self.flip,
-                    self._q.data_ptr(), self._gt.data_ptr(), self._qm.data_ptr(), stream, self.lib)
+        skel_train_batch(ds.pose.data_ptr(), ds.dist.data_ptr(), ds.man.data_ptr(), ds.file_off_t.data_ptr(), ds.man_off_t.data_ptr(),
+                         self._item_file.data_ptr() + 4 * i * bs, self._item_man.data_ptr() + 4 * i * bs,
+                         self._words.data_ptr() + 4 * i * bs * 2 * self.num_pts, ds.F, ds.Fm, ds.k, bs, self.num_pts, self.flip,
+                         self.num_joints, self._q.data_ptr(), self._gt.data_ptr(), self._qm.data_ptr(), stream, self.lib)
         ws = self._ws.data_ptr()
         self._engine.forward(self._wtab, self._q.data_ptr(), self._gt.data_ptr(), self._qm.data_ptr(), self.B, self.B,
                              LOSS_CODES[self.loss], self.eikonal, self._log_dev.data_ptr() + 12 * i, ws, stream)
@@ -393,7 +417,7 @@ class Trainer:
         self._stale_inference()
 
     def batch(self, epoch, step):
-        """the batch of (epoch, step) with torch indexing, on the trainer's device: (pose [B,21,4], dist_gt [B], man [B,21,4])"""
+        """the batch of (epoch, step) with torch indexing, on the trainer's device: (pose [B,J,4], dist_gt [B], man [B,J,4])"""
         rows, man_rows = self.batch_rows(epoch, step)
         self._ensure_pool(epoch)
         ds = self.dataset
@@ -407,7 +431,7 @@ class Trainer:
         pose, gt, man = self.batch(epoch, i)
         self.model.train()
         self.optimizer.zero_grad()
-        _, ld = self.model(pose, gt, man, eikonal=self.loss_weight["eikonal"])
+        _, ld = self.model(pose, gt, man, train=True, eikonal=self.loss_weight["eikonal"])
         loss = 0.0
         for k in ld.keys():
             loss += self.loss_weight[k] * ld[k]
