@@ -374,7 +374,8 @@ int pndf_quat_topk(const float* noise, const float* valid, int64_t B, int32_t K,
  * pndf_knn_search: q device [Q,21,4] (16-byte aligned), `workspace` pndf_knn_workspace_bytes(h, Q, k) bytes (16-byte aligned;
  * may be NULL when that is 0).  Allocates nothing, does not synchronise; Q = 0 is a no-op.  The plan (query blocks x
  * database splits) depends on (Q, N, k) only, and the results do not depend on it: the same bits for any chunking of the
- * queries. */
+ * queries.
+ * An index over poses of another joint count J (q then [Q,J,4]): pndf_skel_knn_create of posendf_amd_skeleton_data.h. */
 typedef struct pndf_knn_index* pndf_knn_handle;
 int pndf_knn_create(pndf_knn_handle* out, const float* poses, int64_t N, int32_t metric, const float* weights, void* stream);
 int pndf_knn_destroy(pndf_knn_handle h);

@@ -22,6 +22,8 @@
  * runs on the device of `q` and restores the caller's current device; return value 0 on success, a negative pndf_status
  * otherwise.  There is no handle: the text of a refusal is left in the calling thread's slot, pndf_last_error(NULL) for
  * pndf_online_sample and pndf_cpu_last_error(NULL) for the three host functions.
+ *
+ * Poses of another joint count than 21: pndf_skel_online_sample / pndf_skel_online_sample_cpu of posendf_amd_skeleton_data.h.
  */
 #ifndef POSENDF_AMD_ONLINE_H
 #define POSENDF_AMD_ONLINE_H

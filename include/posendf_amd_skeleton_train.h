@@ -10,7 +10,8 @@
  * float atomics, the same inputs give the same bits).  On the SMPL table pndf_skel_train_create builds the plan pndf_train_create
  * builds, and the compute calls return the same bits.
  *
- * Still 21-joint: the second order (posendf_amd_second_order.h), completion, interpolation, the k-NN index and the online sampler.
+ * Still 21-joint: the second order (posendf_amd_second_order.h), completion and interpolation.  The k-NN index and the online
+ * sampler for J joints, which make this trainer's data: posendf_amd_skeleton_data.h.
  */
 #ifndef POSENDF_AMD_SKELETON_TRAIN_H
 #define POSENDF_AMD_SKELETON_TRAIN_H

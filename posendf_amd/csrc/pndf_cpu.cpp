@@ -4,7 +4,7 @@
 // C++ for the host cores -- NOT the oracle (oracle/ is test infrastructure and is imported by nothing here) and NOT a
 // fallback: the device entry points never route here, a missing GPU still fails loudly there.  The first-order twins take the joint
 // count and the parent table from the handle's config (any joint tree of include/posendf_amd_skeleton.h, pndf_net_plan.h); on the
-// SMPL table they compute what they did with the table fixed.  Completion, interpolation, second order and online stay 21-joint.
+// SMPL table they compute what they did with the table fixed.  Completion, interpolation and second order stay 21-joint.
 //
 // Layout: poses are processed in blocks of PB = 32; inside a block every activation tensor is [feature][pose] so that the
 // inner loop of a layer runs over the 32 poses of the block (contiguous floats: one or two AVX-512 / four AVX2 registers)
@@ -33,6 +33,7 @@
 #include "pndf_interp.h"
 #include "pndf_layout.h"
 #include "pndf_online.h"
+#include "../../include/posendf_amd_skeleton_data.h"
 #include "pndf_project_opts.h"
 #include "pndf_net_plan.h"
 
@@ -729,7 +730,7 @@ extern "C" int pndf_second_order_cpu(pndf_cpu_handle h, const float* q, const fl
 
 // ------------------------------------------------------------------ online training data (include/posendf_amd_online.h)
 // The sampler's host side: the default options, the thresholds of a list of shares, and the host twin of pndf_online_sample --
-// pndf_online.h's expression, pose by pose on the calling thread (84 floats and 22 Philox blocks per pose: meant for small pools
+// pndf_online.h's expression, pose by pose on the calling thread (84 floats and 22 Philox blocks per 21-joint pose: meant for small pools
 // and for holding the kernel to).  No handle: a refusal's text goes to the slot of pndf_cpu_last_error(NULL).
 namespace {
 
@@ -755,20 +756,32 @@ extern "C" int pndf_online_default_opts(pndf_online_opts* opt) {
     return pndf_online_shares(opt, shares);
 }
 
-extern "C" int pndf_online_sample_cpu(const float* man_db, int64_t N, int64_t first, int64_t count, const pndf_online_opts* opt, float* q,
-                                      int64_t* src, int32_t* group) {
-    if (const char* why = pndf_online_check(man_db, N, first, count, opt, q, src, group, 4))
-        return online_fail(PNDF_ERR_BAD_ARG, std::string("pndf_online_sample_cpu: ") + why);
+// `name`: the entry point, for the texts; J floats x 4 and 1 + J Philox blocks per pose
+static int online_sample_cpu(const char* name, const float* man_db, int64_t N, int J, int64_t first, int64_t count, const pndf_online_opts* opt,
+                             float* q, int64_t* src, int32_t* group) {
+    if (const char* why = pndf_online_check(man_db, N, J, first, count, opt, q, src, group, 4))
+        return online_fail(PNDF_ERR_BAD_ARG, std::string(name) + ": " + why);
     for (int64_t p = 0; p < count; ++p) {
         const int64_t i = first + p;
         int64_t row;
         int32_t g;
         float sigma;
         pndf_online_pick(*opt, i, N, &row, &g, &sigma);
-        for (int j = 0; j < NJ; ++j)
-            pndf_online_quat(opt->seed, opt->draw, i, j, opt->noise, sigma, man_db + (row * NJ + j) * 4, q + (p * NJ + j) * 4);
+        for (int j = 0; j < J; ++j)
+            pndf_online_quat(opt->seed, opt->draw, i, j, opt->noise, sigma, man_db + (row * J + j) * 4, q + (p * J + j) * 4);
         if (src) src[p] = row;
         if (group) group[p] = g;
     }
     return PNDF_OK;
+}
+
+extern "C" int pndf_online_sample_cpu(const float* man_db, int64_t N, int64_t first, int64_t count, const pndf_online_opts* opt, float* q,
+                                      int64_t* src, int32_t* group) {
+    return online_sample_cpu("pndf_online_sample_cpu", man_db, N, NJ, first, count, opt, q, src, group);
+}
+
+// include/posendf_amd_skeleton_data.h
+extern "C" int pndf_skel_online_sample_cpu(const float* man_db, int64_t N, int32_t num_joints, int64_t first, int64_t count,
+                                           const pndf_online_opts* opt, float* q, int64_t* src, int32_t* group) {
+    return online_sample_cpu("pndf_skel_online_sample_cpu", man_db, N, num_joints, first, count, opt, q, src, group);
 }

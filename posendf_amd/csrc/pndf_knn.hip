@@ -1,17 +1,23 @@
 // Exact k-nearest-pose search over a pose database (the search stage of the reference's data/prepare_traindata.py:152-159,
-// with the whole database as every query's candidate list): for Q query poses [Q,21,4] and an index of N poses, the k
-// smallest of
+// with the whole database as every query's candidate list): for Q query poses [Q,J,4] and an index of N poses of J joints
+// (1 .. 32, a property of the index: 21 for pndf_knn_create, any for pndf_skel_knn_create of
+// include/posendf_amd_skeleton_data.h), the k smallest of
 //   geo: sum_j w_j (1 - |<q_j, p_j>|)        euc: sum_j w_j ||q_j - p_j||_2
-// (w_j = 1/21, or the L2-normalised joint ranks), the metric and semantics of pndf_quat_topk.
+// (w_j = 1/J, or the caller's: the L2-normalised joint ranks of SMPL), the metric and semantics of pndf_quat_topk.
 //
-// Layout.  pndf_knn_create packs the database once into joint-major 16-pose tiles: tile t = 21 joints x 4 components x 16
-// poses (5,376 B), element [t][j][c][m] = pose 16t+m, joint j, component c.  Poses past N are NaN, so their distance is NaN
-// and never selected.  One joint of one tile is 64 consecutive floats: lane l of a wave loads element l, which is exactly
-// the A operand A[m = l&15][c = l>>4] of v_mfma_f32_16x16x4_f32.
+// Layout.  The index packs the database once into joint-major 16-pose tiles: tile t = J joints x 4 components x 16 poses
+// (256 J bytes; 5,376 B at 21), element [t][j][c][m] = pose 16t+m, joint j, component c.  Poses past N are NaN, so their
+// distance is NaN and never selected.  One joint of one tile is 64 consecutive floats: lane l of a wave loads element l, which
+// is exactly the A operand A[m = l&15][c = l>>4] of v_mfma_f32_16x16x4_f32.
+//
+// The joint count in the kernels.  Every per-joint register array is sized by a compile-time bound JP and indexed by unrolled
+// loops only; the kernels are instantiated for the width classes JP = 8, 16, 24, 32, where joint j of the unrolled sequence runs
+// under the wave-uniform guard j < J (J a kernel argument), and for JP = 21, where J is the constant 21 and the guard folds
+// away: the 21-joint instantiation is the expression sequence it was before the other joint counts existed.
 //
 // geo (MFMA).  A = 16 database poses (rows), B = 16 queries (columns) with w_j folded in; one MFMA per joint and query group
 // gives the 16x16 block of w_j <q_j, p_j>.  Lane l holds column l&15 (one query) and rows 4(l>>4)+r (four poses), adds
-// w_j - |d| per joint in joint order 0..20: a pair gets the same bits wherever it lands in the plan.  A wave owns 2 groups
+// w_j - |d| per joint in joint order 0..J-1: a pair gets the same bits wherever it lands in the plan.  A wave owns 2 groups
 // (32 queries), a workgroup of 4 waves 128 queries; the 4 waves read the same tile (L1 hits after the first).
 // euc (VALU).  The direct-difference form sqrt(sum_c (q_c - p_c)^2), never the expansion |q|^2 + |p|^2 - 2<q,p> (which
 // cancels for near-identical joints).  A lane owns one query; a workgroup of 128 stages 4 tiles in LDS and reads each pose
@@ -32,20 +38,21 @@
 #include <string>
 
 #include "../../include/posendf_amd.h"
+#include "../../include/posendf_amd_skeleton_data.h"
 #include "pndf_host.h"
 
 struct pndf_knn_index {
     int device = -1;
     int64_t N = 0, T = 0;
     int32_t metric = 0;
-    float w[21];
+    int32_t J = 21;
+    float w[32];
     float* db = nullptr;
     std::string err;
 };
 
 namespace {
-constexpr int NJ = 21, TILE = 16, QPB = 128, MAX_K = 16, EUC_CHUNK = 4;
-constexpr int TILE_FLOATS = NJ * 4 * TILE;            // 1344 floats = 5,376 B
+constexpr int MAX_J = 32, EXACT_J = 21, TILE = 16, QPB = 128, MAX_K = 16, EUC_CHUNK = 4;
 constexpr int SENT = 0x7fffffff;                     // empty slot: sorts after every real index (N < 2^31)
 constexpr int TARGET_WGS = 2048;                     // 8 workgroups per CU of a 256-CU part
 constexpr int64_t MIN_TILES_PER_SPLIT = 16;
@@ -53,12 +60,17 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 
 struct KnnArgs {
     const float* db;     // packed tiles
-    const float* q;      // [Q,21,4]
+    const float* q;      // [Q,J,4]
     float* pv;           // partial lists [S][Q][KM]
     int* pi;
     int64_t Q, T, tps, S, qb;
-    float w[NJ];
+    int32_t J;
+    float w[MAX_J];
 };
+
+// the joint count of an instantiation: the constant 21 in the exact one, the argument (<= JP) in a width class
+template <int JP>
+__device__ __forceinline__ int joint_count(const KnnArgs& a) { return JP == EXACT_J ? EXACT_J : a.J; }
 
 struct MergeArgs {
     const float* pv;
@@ -124,27 +136,29 @@ __device__ __forceinline__ void merge_lanes(float (&lv)[KM], int (&li)[KM], int 
 }  // namespace
 
 extern "C" __global__ void __launch_bounds__(256) pndf_knn_pack_kernel(const float* __restrict__ src, float* __restrict__ dst,
-                                                                        int64_t N, int64_t n_out) {
+                                                                        int64_t N, int J, int64_t n_out) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= n_out) return;
-    const int64_t t = e / TILE_FLOATS;
-    const int r = (int)(e - t * TILE_FLOATS);
+    const int tile_floats = J * 4 * TILE;
+    const int64_t t = e / tile_floats;
+    const int r = (int)(e - t * tile_floats);
     const int j = r >> 6, c = (r >> 4) & 3, m = r & 15;
     const int64_t n = t * TILE + m;
-    dst[e] = n < N ? src[(n * NJ + j) * 4 + c] : __builtin_nanf("");
+    dst[e] = n < N ? src[(n * J + j) * 4 + c] : __builtin_nanf("");
 }
 
-template <int KM>
+template <int JP, int KM>
 __global__ void __launch_bounds__(256) pndf_knn_geo_kernel(KnnArgs a) {
     constexpr int G = 2;                              // query groups of 16 per wave
+    const int J = joint_count<JP>(a), tile_floats = J * 4 * TILE;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, kq = lane >> 4;
     const int64_t split = blockIdx.x / a.qb, qblock = blockIdx.x - split * a.qb;
-    float bq[G][NJ];
+    float bq[G][JP];
 #pragma unroll
     for (int g = 0; g < G; ++g) {
         const int64_t qi = qblock * QPB + wave * (16 * G) + g * 16 + col;
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) bq[g][j] = qi < a.Q ? a.w[j] * a.q[(qi * NJ + j) * 4 + kq] : 0.f;
+        for (int j = 0; j < JP; ++j) bq[g][j] = (j < J && qi < a.Q) ? a.w[j] * a.q[(qi * J + j) * 4 + kq] : 0.f;
     }
     float lv[G][KM];
     int li[G][KM];
@@ -152,24 +166,26 @@ __global__ void __launch_bounds__(256) pndf_knn_geo_kernel(KnnArgs a) {
     for (int g = 0; g < G; ++g) init_list<KM>(lv[g], li[g]);
     const int64_t t0 = split * a.tps, t1 = min(t0 + a.tps, a.T);
     const float* db = a.db + lane;
-    float pa[NJ];
+    float pa[JP];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) pa[j] = db[t0 * TILE_FLOATS + j * 64];
+    for (int j = 0; j < JP; ++j) pa[j] = j < J ? db[t0 * tile_floats + j * 64] : 0.f;
     for (int64_t t = t0; t < t1; ++t) {
         const int64_t tn = t + 1 < t1 ? t + 1 : t;   // the next tile's loads go out before this tile's MFMAs
-        float pn[NJ];
+        float pn[JP];
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) pn[j] = db[tn * TILE_FLOATS + j * 64];
+        for (int j = 0; j < JP; ++j) pn[j] = j < J ? db[tn * tile_floats + j * 64] : 0.f;
         f4 s[G];
 #pragma unroll
         for (int g = 0; g < G; ++g) s[g] = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) {
+        for (int j = 0; j < JP; ++j) {
+            if (j < J) {                              // (wave-uniform; constant in the 21-joint instantiation)
 #pragma unroll
-            for (int g = 0; g < G; ++g) {
-                const f4 d = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[j], bq[g][j], f4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+                for (int g = 0; g < G; ++g) {
+                    const f4 d = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[j], bq[g][j], f4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) s[g][r] += a.w[j] - fabsf(d[r]);
+                    for (int r = 0; r < 4; ++r) s[g][r] += a.w[j] - fabsf(d[r]);
+                }
             }
         }
         const int64_t base = t * TILE + 4 * kq;      // (padding poses are NaN: never taken)
@@ -179,7 +195,7 @@ __global__ void __launch_bounds__(256) pndf_knn_geo_kernel(KnnArgs a) {
             for (int r = 0; r < 4; ++r) offer<KM>(lv[g], li[g], s[g][r], (int)(base + r));
         }
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) pa[j] = pn[j];
+        for (int j = 0; j < JP; ++j) pa[j] = pn[j];
     }
 #pragma unroll
     for (int g = 0; g < G; ++g) {
@@ -193,15 +209,16 @@ __global__ void __launch_bounds__(256) pndf_knn_geo_kernel(KnnArgs a) {
     }
 }
 
-template <int KM>
+template <int JP, int KM>
 __global__ void __launch_bounds__(QPB) pndf_knn_euc_kernel(KnnArgs a) {
-    __shared__ f4 sp[EUC_CHUNK * TILE][NJ];           // 21,504 B
+    __shared__ f4 sp[EUC_CHUNK * TILE][JP];           // 21,504 B at 21, 32 KB at 32
     const int tid = threadIdx.x;
+    const int J = joint_count<JP>(a), tile_floats = J * 4 * TILE;
     const int64_t split = blockIdx.x / a.qb, qblock = blockIdx.x - split * a.qb;
     const int64_t qi = qblock * QPB + tid;
-    f4 qq[NJ];
+    f4 qq[JP];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) qq[j] = qi < a.Q ? ((const f4*)a.q)[qi * NJ + j] : f4{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < JP; ++j) qq[j] = (j < J && qi < a.Q) ? ((const f4*)a.q)[qi * J + j] : f4{0.f, 0.f, 0.f, 0.f};
     float lv[KM];
     int li[KM];
     init_list<KM>(lv, li);
@@ -209,9 +226,9 @@ __global__ void __launch_bounds__(QPB) pndf_knn_euc_kernel(KnnArgs a) {
     for (int64_t t = t0; t < t1; t += EUC_CHUNK) {
         const int nt = (int)min((int64_t)EUC_CHUNK, t1 - t);
         __syncthreads();
-        const float* src = a.db + t * TILE_FLOATS;
-        for (int e = tid; e < nt * TILE_FLOATS; e += QPB) {
-            const int tt = e / TILE_FLOATS, r = e - tt * TILE_FLOATS;
+        const float* src = a.db + t * tile_floats;
+        for (int e = tid; e < nt * tile_floats; e += QPB) {
+            const int tt = e / tile_floats, r = e - tt * tile_floats;
             const int j = r >> 6, c = (r >> 4) & 3, m = r & 15;
             ((float*)&sp[tt * TILE + m][j])[c] = src[e];
         }
@@ -220,10 +237,12 @@ __global__ void __launch_bounds__(QPB) pndf_knn_euc_kernel(KnnArgs a) {
         for (int p = 0; p < nt * TILE; ++p) {
             float s = 0.f;
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const f4 v = sp[p][j], q = qq[j];
-                const float dx = q.x - v.x, dy = q.y - v.y, dz = q.z - v.z, dw = q.w - v.w;
-                s += sqrtf(dx * dx + dy * dy + dz * dz + dw * dw) * a.w[j];
+            for (int j = 0; j < JP; ++j) {
+                if (j < J) {
+                    const f4 v = sp[p][j], q = qq[j];
+                    const float dx = q.x - v.x, dy = q.y - v.y, dz = q.z - v.z, dw = q.w - v.w;
+                    s += sqrtf(dx * dx + dy * dy + dz * dz + dw * dw) * a.w[j];
+                }
             }
             offer<KM>(lv, li, s, (int)(base + p));
         }
@@ -289,19 +308,28 @@ int64_t workspace_bytes(int64_t Q, int64_t N, int k) {
     return p.S * Q * p.KM * 8;
 }
 
+template <int JP, int KM>
+void launch_search(const pndf_knn_index* h, const KnnArgs& a, hipStream_t st) {
+    const unsigned grid = (unsigned)(a.S * a.qb);
+    if (h->metric == 0) hipLaunchKernelGGL((pndf_knn_geo_kernel<JP, KM>), dim3(grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((pndf_knn_euc_kernel<JP, KM>), dim3(grid), dim3(QPB), 0, st, a);
+}
+
+// the instantiation of a joint count: 21 has its own, every other one the smallest width class that holds it
 template <int KM>
 void launch(const pndf_knn_index* h, const KnnArgs& a, const MergeArgs& m, hipStream_t st) {
-    const unsigned grid = (unsigned)(a.S * a.qb);
-    if (h->metric == 0) hipLaunchKernelGGL(pndf_knn_geo_kernel<KM>, dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(pndf_knn_euc_kernel<KM>, dim3(grid), dim3(QPB), 0, st, a);
+    if (h->J == EXACT_J) launch_search<EXACT_J, KM>(h, a, st);
+    else if (h->J <= 8) launch_search<8, KM>(h, a, st);
+    else if (h->J <= 16) launch_search<16, KM>(h, a, st);
+    else if (h->J <= 24) launch_search<24, KM>(h, a, st);
+    else launch_search<MAX_J, KM>(h, a, st);
     hipLaunchKernelGGL(pndf_knn_merge_kernel<KM>, dim3((unsigned)((m.Q + 3) / 4)), dim3(256), 0, st, m);
 }
 }  // namespace
 
 extern "C" const char* pndf_knn_last_error(pndf_knn_handle h) { return pndf_last_error_of(h); }
 
-extern "C" int pndf_knn_create(pndf_knn_handle* out, const float* poses, int64_t N, int32_t metric, const float* weights,
-                               void* stream) {
+static int knn_create(pndf_knn_handle* out, const float* poses, int64_t N, int J, int32_t metric, const float* weights, void* stream) {
     if (!out) return pndf_fail<pndf_knn_index>(nullptr, PNDF_ERR_BAD_ARG, "out is null");
     *out = nullptr;
     if (metric != 0 && metric != 1) return pndf_fail<pndf_knn_index>(nullptr, PNDF_ERR_UNSUPPORTED, "metric: 0 = geo or 1 = euc");
@@ -310,7 +338,7 @@ extern "C" int pndf_knn_create(pndf_knn_handle* out, const float* poses, int64_t
     if (!poses) return pndf_fail<pndf_knn_index>(nullptr, PNDF_ERR_BAD_ARG, "poses is null");
     if ((uintptr_t)poses & 15) return pndf_fail<pndf_knn_index>(nullptr, PNDF_ERR_BAD_ARG, "poses must be 16-byte aligned");
     if (weights)
-        for (int j = 0; j < NJ; ++j)
+        for (int j = 0; j < J; ++j)
             if (!(weights[j] > 0.f) || !std::isfinite(weights[j]))
                 return pndf_fail<pndf_knn_index>(nullptr, PNDF_ERR_BAD_ARG, "joint weights must be finite and > 0");
     const PndfDeviceCheck any = pndf_check_gfx950(PNDF_ANY_DEVICE, "the pose index");
@@ -326,15 +354,16 @@ extern "C" int pndf_knn_create(pndf_knn_handle* out, const float* poses, int64_t
     h->N = N;
     h->T = (N + TILE - 1) / TILE;
     h->metric = metric;
-    for (int j = 0; j < NJ; ++j) h->w[j] = weights ? weights[j] : 1.0f / (float)NJ;
-    const int64_t n_out = h->T * TILE_FLOATS;
+    h->J = J;
+    for (int j = 0; j < MAX_J; ++j) h->w[j] = j >= J ? 0.f : weights ? weights[j] : 1.0f / (float)J;
+    const int64_t n_out = h->T * (J * 4 * TILE);
     if (hipMalloc((void**)&h->db, (size_t)n_out * sizeof(float)) != hipSuccess) {
         (void)hipGetLastError();
         delete h;
         return pndf_fail<pndf_knn_index>(nullptr, PNDF_ERR_HIP, "hipMalloc of the packed index (" + std::to_string(n_out * 4) + " B) failed");
     }
     hipLaunchKernelGGL(pndf_knn_pack_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, (hipStream_t)stream, poses,
-                       h->db, N, n_out);
+                       h->db, N, J, n_out);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);      // the caller may free or overwrite `poses` next
     if (e != hipSuccess) {
@@ -345,6 +374,19 @@ extern "C" int pndf_knn_create(pndf_knn_handle* out, const float* poses, int64_t
     }
     *out = h;
     return PNDF_OK;
+}
+
+extern "C" int pndf_knn_create(pndf_knn_handle* out, const float* poses, int64_t N, int32_t metric, const float* weights,
+                               void* stream) {
+    return knn_create(out, poses, N, EXACT_J, metric, weights, stream);
+}
+
+// include/posendf_amd_skeleton_data.h
+extern "C" int pndf_skel_knn_create(pndf_knn_handle* out, const float* poses, int64_t N, int32_t num_joints, int32_t metric,
+                                    const float* weights, void* stream) {
+    if (num_joints < 1 || num_joints > MAX_J)         // (before any pointer is looked at, `out` among them)
+        return pndf_fail<pndf_knn_index>(nullptr, PNDF_ERR_BAD_ARG, "num_joints must be in 1 .. 32, got " + std::to_string(num_joints));
+    return knn_create(out, poses, N, num_joints, metric, weights, stream);
 }
 
 extern "C" int pndf_knn_destroy(pndf_knn_handle h) {
@@ -385,7 +427,8 @@ extern "C" int pndf_knn_search(pndf_knn_handle h, const float* q, int64_t Q, int
     a.pv = (float*)workspace;
     a.pi = (int*)((char*)workspace + p.S * Q * p.KM * 4);
     a.Q = Q; a.T = h->T; a.tps = p.tps; a.S = p.S; a.qb = p.qb;
-    for (int j = 0; j < NJ; ++j) a.w[j] = h->w[j];
+    a.J = h->J;
+    for (int j = 0; j < MAX_J; ++j) a.w[j] = h->w[j];
     MergeArgs m;
     m.pv = a.pv; m.pi = a.pi; m.vals = vals; m.idx = idx; m.Q = Q; m.S = p.S; m.k = k;
     const hipStream_t st = (hipStream_t)stream;

@@ -73,15 +73,18 @@ PNDF_HD void pndf_online_quat(uint64_t seed, uint32_t draw, int64_t i, int j, in
 // ------------------------------------------------------------------ host only: the refusals, the thresholds
 // (plain inline functions: host code in every translation unit)
 // the grid of the kernel: one lane per joint quaternion, 256 lanes per block
-constexpr int64_t PNDF_ONLINE_MAX_COUNT = ((int64_t)0x7fffffff * 256) / 21;
+constexpr int PNDF_ONLINE_MAX_JOINTS = 32;
+inline int64_t pndf_online_max_count(int num_joints) { return ((int64_t)0x7fffffff * 256) / num_joints; }
 
-// why a call of pndf_online_sample / pndf_online_sample_cpu is refused, or nullptr; `vec_align`: the alignment of q and man_db
-inline const char* pndf_online_check(const float* man_db, int64_t N, int64_t first, int64_t count, const pndf_online_opts* o, const float* q,
+// why a call of pndf_online_sample / pndf_online_sample_cpu (num_joints 21) or of their pndf_skel_ forms is refused, or nullptr;
+// `vec_align`: the alignment of q and man_db.  The joint count is looked at before any pointer.
+inline const char* pndf_online_check(const float* man_db, int64_t N, int num_joints, int64_t first, int64_t count, const pndf_online_opts* o, const float* q,
                                      const int64_t* src, const int32_t* group, uintptr_t vec_align) {
+    if (num_joints < 1 || num_joints > PNDF_ONLINE_MAX_JOINTS) return "num_joints must be in 1 .. 32";
     if (N < 1 || N >= ((int64_t)1 << 31)) return "the manifold needs 1 <= N < 2^31 poses";
     if (count < 0 || first < 0) return "negative count or first";
     if (first > INT64_MAX - count) return "first + count is beyond int64";
-    if (count > PNDF_ONLINE_MAX_COUNT) return "count is beyond the grid of the kernel";
+    if (count > pndf_online_max_count(num_joints)) return "count is beyond the grid of the kernel";
     if (!o) return "opt is null";
     if (o->n_sigma < 1 || o->n_sigma > PNDF_ONLINE_MAX_SIGMA) return "n_sigma must be in 1 .. 16";
     for (int g = 0; g < o->n_sigma; ++g) {

@@ -67,9 +67,9 @@ class PndfError(RuntimeError):
 
 # ---- the C ABI, one table per header: name -> (restype, argtypes), in the header's order.  load_library() binds the tables, EXPORTS /
 # COMPLETION_EXPORTS / INTERPOLATION_EXPORTS / SECOND_ORDER_EXPORTS / ONLINE_EXPORTS / SKELETON_EXPORTS / SKELETON_TRAIN_EXPORTS /
-# DEBUG_EXPORTS are their names,
+# SKELETON_DATA_EXPORTS / DEBUG_EXPORTS are their names,
 # tests/test_cabi.py, tests/test_completion.py, tests/test_interpolation.py, tests/test_second_order.py, tests/test_online.py and
-# tests/test_skeleton.py and tests/test_skeleton_train.py hold them against the declarations of the headers.
+# tests/test_skeleton.py, tests/test_skeleton_train.py and tests/test_skeleton_data.py hold them against the declarations of the headers.
 _H = c_void_p                          # every handle type, and every `void* stream`
 _P = c_void_p                          # any other address: tensor data (an int from data_ptr(), or None), a callback, an out value
 _TENSORS = [POINTER(c_void_p), POINTER(c_int64), c_int]      # tensors, numel, n_tensors (host pointers in state-dict order)
@@ -198,6 +198,11 @@ _SKELETON_TRAIN_SIGNATURES = {      # include/posendf_amd_skeleton_train.h: trai
     "pndf_skel_train_create": (c_int, [POINTER(_H), POINTER(PndfConfig), c_int]),
     "pndf_skel_train_batch": (c_int, [_P] * 8 + [c_int32] * 7 + [_P] * 3 + [_H]),
 }
+_SKELETON_DATA_SIGNATURES = {      # include/posendf_amd_skeleton_data.h: the k-NN index and the online sampler for any J, the seventh companion header
+    "pndf_skel_knn_create": (c_int, [POINTER(_H), _P, c_int64, c_int32, c_int32, _P, _H]),
+    "pndf_skel_online_sample": (c_int, [_P, c_int64, c_int32, c_int64, c_int64, POINTER(OnlineOpts), _P, _P, _P, _H]),
+    "pndf_skel_online_sample_cpu": (c_int, [_P, c_int64, c_int32, c_int64, c_int64, POINTER(OnlineOpts), _P, _P, _P]),
+}
 EXPORTS, DEBUG_EXPORTS = tuple(_SIGNATURES), tuple(_DEBUG_SIGNATURES)
 COMPLETION_EXPORTS = tuple(_COMPLETION_SIGNATURES)
 INTERPOLATION_EXPORTS = tuple(_INTERPOLATION_SIGNATURES)
@@ -205,6 +210,7 @@ SECOND_ORDER_EXPORTS = tuple(_SECOND_ORDER_SIGNATURES)
 ONLINE_EXPORTS = tuple(_ONLINE_SIGNATURES)
 SKELETON_EXPORTS = tuple(_SKELETON_SIGNATURES)
 SKELETON_TRAIN_EXPORTS = tuple(_SKELETON_TRAIN_SIGNATURES)
+SKELETON_DATA_EXPORTS = tuple(_SKELETON_DATA_SIGNATURES)
 # per-translation-unit experiment words (csrc/pndf_experiment.h): data symbols, all zero in a product build
 EXPERIMENT_WORDS = ("pndf_experiment_word_capi", "pndf_experiment_word_fp32", "pndf_experiment_word_split", "pndf_experiment_word_split_x2",
                     "pndf_experiment_word_bf16", "pndf_experiment_word_lbs", "pndf_experiment_word_generic", "pndf_experiment_word_train",
@@ -259,7 +265,8 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         raise PndfError(f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                         "(hipcc --offload-arch=gfx950). The engine has no fallback path.")
     lib = _bind(_bind(_bind(_PndfLibrary(path), _SIGNATURES), _COMPLETION_SIGNATURES), _INTERPOLATION_SIGNATURES)
-    return _bind(_bind(_bind(_bind(lib, _SECOND_ORDER_SIGNATURES), _ONLINE_SIGNATURES), _SKELETON_SIGNATURES), _SKELETON_TRAIN_SIGNATURES)
+    lib = _bind(_bind(_bind(_bind(lib, _SECOND_ORDER_SIGNATURES), _ONLINE_SIGNATURES), _SKELETON_SIGNATURES), _SKELETON_TRAIN_SIGNATURES)
+    return _bind(lib, _SKELETON_DATA_SIGNATURES)
 
 
 def experiment_word(lib=None) -> int:
@@ -755,20 +762,29 @@ def online_opts(sigmas, shares, noise="uniform", seed=0, draw=0, lib=None) -> On
     return opt
 
 
-def online_sample(man_ptr, N, first, count, opt, q_ptr, src_ptr=None, group_ptr=None, stream=0, lib=None):
-    """`pndf_online_sample` (csrc/pndf_online.hip): poses first .. first + count - 1 of the pool of `opt` over the device manifold"""
+def online_sample(man_ptr, N, first, count, opt, q_ptr, src_ptr=None, group_ptr=None, stream=0, lib=None, num_joints=21):
+    """`pndf_online_sample` (csrc/pndf_online.hip): poses first .. first + count - 1 of the pool of `opt` over the device manifold;
+    another `num_joints` than 21: `pndf_skel_online_sample`"""
     lib = lib or load_library()
-    rc = lib.pndf_online_sample(man_ptr, int(N), int(first), int(count), ctypes.byref(opt), q_ptr, src_ptr, group_ptr, stream)
+    if int(num_joints) == 21:
+        fn, rc = "pndf_online_sample", lib.pndf_online_sample(man_ptr, int(N), int(first), int(count), ctypes.byref(opt), q_ptr, src_ptr, group_ptr, stream)
+    else:
+        fn, rc = "pndf_skel_online_sample", lib.pndf_skel_online_sample(man_ptr, int(N), int(num_joints), int(first), int(count), ctypes.byref(opt),
+                                                                        q_ptr, src_ptr, group_ptr, stream)
     if rc != 0:
-        raise PndfError(f"pndf_online_sample failed ({rc}): {lib.pndf_last_error(None).decode()}")
+        raise PndfError(f"{fn} failed ({rc}): {lib.pndf_last_error(None).decode()}")
 
 
-def online_sample_cpu(man_ptr, N, first, count, opt, q_ptr, src_ptr=None, group_ptr=None, lib=None):
+def online_sample_cpu(man_ptr, N, first, count, opt, q_ptr, src_ptr=None, group_ptr=None, lib=None, num_joints=21):
     """`pndf_online_sample_cpu` (csrc/pndf_cpu.cpp): the host twin of online_sample, HOST pointers"""
     lib = lib or load_library()
-    rc = lib.pndf_online_sample_cpu(man_ptr, int(N), int(first), int(count), ctypes.byref(opt), q_ptr, src_ptr, group_ptr)
+    if int(num_joints) == 21:
+        fn, rc = "pndf_online_sample_cpu", lib.pndf_online_sample_cpu(man_ptr, int(N), int(first), int(count), ctypes.byref(opt), q_ptr, src_ptr, group_ptr)
+    else:
+        fn, rc = "pndf_skel_online_sample_cpu", lib.pndf_skel_online_sample_cpu(man_ptr, int(N), int(num_joints), int(first), int(count),
+                                                                                ctypes.byref(opt), q_ptr, src_ptr, group_ptr)
     if rc != 0:
-        raise PndfError(f"pndf_online_sample_cpu failed ({rc}): {lib.pndf_cpu_last_error(None).decode()}")
+        raise PndfError(f"{fn} failed ({rc}): {lib.pndf_cpu_last_error(None).decode()}")
 
 
 def aa2quat(theta_ptr, q_ptr, N, stream=0, lib=None):
@@ -819,18 +835,25 @@ METRIC_CODES = {"geo": 0, "euc": 1}
 
 class KnnIndex(_Handle):
     """`pndf_knn_*` (csrc/pndf_knn.hip): an exact k-nearest-pose index on one device.  The constructor packs a copy of the
-    poses at `poses_ptr` (device [N,21,4]); `search` takes raw device pointers and a stream handle."""
+    poses at `poses_ptr` (device [N,J,4], J = `num_joints`; another J than 21: `pndf_skel_knn_create`); `search` takes raw device
+    pointers and a stream handle."""
     _destroy, _last_error = "pndf_knn_destroy", "pndf_knn_last_error"
 
-    def __init__(self, poses_ptr, N, metric: str = "geo", weights=None, stream=0, lib=None):
+    def __init__(self, poses_ptr, N, metric: str = "geo", weights=None, stream=0, lib=None, num_joints=21):
         self.lib = lib or load_library()
         if metric not in METRIC_CODES:
             raise PndfError(f"unknown metric {metric!r} (geo, euc)")
+        J = int(num_joints)
+        if not 1 <= J <= 32:
+            raise PndfError(f"num_joints = {J}: the index takes 1 .. 32 joints")
         w = None
         if weights is not None:
-            w = (c_float * 21)(*[float(x) for x in np.asarray(weights, dtype=np.float32).reshape(21)])
-        self._create("pndf_knn_create", poses_ptr, int(N), METRIC_CODES[metric], w, stream)
-        self.metric = metric
+            w = (c_float * J)(*[float(x) for x in np.asarray(weights, dtype=np.float32).reshape(J)])
+        if J == 21:
+            self._create("pndf_knn_create", poses_ptr, int(N), METRIC_CODES[metric], w, stream)
+        else:
+            self._create("pndf_skel_knn_create", poses_ptr, int(N), J, METRIC_CODES[metric], w, stream)
+        self.metric, self.num_joints = metric, J
 
     def size(self) -> int:
         return int(self.lib.pndf_knn_size(self.handle))

@@ -6,6 +6,9 @@ it -- what the reference sketches in model/load_data.py:89-135 (`PoseData_online
     ds.refresh(draw=3, seed=0)                                              # pose <- the sampler, dist <- pndf_knn_search
     Trainer(opt, dataset=ds)        # or `data.online: {files, rows, refresh_every, ...}` in the config (posendf_amd.trainer)
 
+Another skeleton: `num_joints=J` (1 .. 32) on sample_noisy, OnlinePoseDataset and .from_manifold draws and labels poses [.., J, 4]
+(include/posendf_amd_skeleton_data.h); a J-joint data set goes to the trainer as `dataset=`.
+
 A pool is a pure function of (seed, draw, options, manifold): pose i takes the manifold row, the sigma group and the noise that
 the Philox4x32-10 blocks with counter (i, block, draw) and key `seed` give it (include/posendf_amd_online.h), so any chunking
 produces the same bits and a pool is regenerated, not stored.  `OnlinePoseDataset` holds the pool in the buffers `Trainer` and
@@ -31,7 +34,21 @@ from .engine import PndfError, load_library, online_opts, online_sample, online_
 from .traindata import SAMPLE_DISTRIBUTION, SIGMA
 from .trainer import PoseDataset, _subdirs
 
-KNN_TILE_BYTES, KNN_TILE = 5376, 16      # csrc/pndf_knn.hip: the packed index is whole tiles of 16 poses
+KNN_TILE_BYTES, KNN_TILE = 5376, 16      # csrc/pndf_knn.hip: the packed index is whole tiles of 16 poses (21 joints)
+
+
+def knn_tile_bytes(num_joints=21):
+    """one packed tile of the index: J joints x 4 components x 16 poses, fp32"""
+    return 256 * int(num_joints)
+
+
+def _check_joints(num_joints, weighted=False):
+    J = int(num_joints)
+    if not 1 <= J <= 32:
+        raise ValueError(f"num_joints = {J}: the sampler and the index take 1 .. 32 joints")
+    if weighted and J != 21:
+        raise ValueError(f"OnlineOptions.weighted is the joint-rank vector of the 21 SMPL joints, not of {J}")
+    return J
 
 
 @dataclass(frozen=True)
@@ -51,25 +68,28 @@ class OnlineOptions:
 
 
 def _sample_into(man, first, count, opt, q, src, group, lib=None):
-    """pool poses first .. first + count - 1 into q (and src, group: tensors or None) on man's device, on the current stream"""
+    """pool poses first .. first + count - 1 into q (and src, group: tensors or None) on man's device, on the current stream;
+    man [N,J,4] gives the joint count"""
     ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+    J = man.shape[1]
     if man.device.type == "cuda":
         with torch.cuda.device(man.device):
-            online_sample(man.data_ptr(), man.shape[0], first, count, opt, q.data_ptr(), ptr(src), ptr(group), stream_handle(man.device), lib)
+            online_sample(man.data_ptr(), man.shape[0], first, count, opt, q.data_ptr(), ptr(src), ptr(group), stream_handle(man.device), lib, J)
     else:
-        online_sample_cpu(man.data_ptr(), man.shape[0], first, count, opt, q.data_ptr(), ptr(src), ptr(group), lib)
+        online_sample_cpu(man.data_ptr(), man.shape[0], first, count, opt, q.data_ptr(), ptr(src), ptr(group), lib, J)
 
 
-def sample_noisy(man, count, *, first=0, seed=0, draw=0, options=None):
-    """-> (q float32 [count,21,4], src int64 [count], group int32 [count]) on `man`'s device: poses first .. first + count - 1
-    of pool (seed, draw) over the manifold man [N,21,4].  On cuda this is pndf_online_sample on the current stream (no
-    synchronisation); on cpu the host twin, the same bits."""
+def sample_noisy(man, count, *, first=0, seed=0, draw=0, options=None, num_joints=21):
+    """-> (q float32 [count,J,4], src int64 [count], group int32 [count]) on `man`'s device: poses first .. first + count - 1
+    of pool (seed, draw) over the manifold man [N,J,4], J = `num_joints`.  On cuda this is pndf_online_sample (J = 21) or
+    pndf_skel_online_sample on the current stream (no synchronisation); on cpu the host twin, the same bits."""
     options = options or OnlineOptions()
-    man = torch.as_tensor(man).to(torch.float32).reshape(-1, 21, 4).contiguous()
+    J = _check_joints(num_joints)
+    man = torch.as_tensor(man).to(torch.float32).reshape(-1, J, 4).contiguous()
     count = int(count)
     if count < 0:
         raise PndfError(f"count = {count}")
-    q = torch.empty(count, 21, 4, dtype=torch.float32, device=man.device)
+    q = torch.empty(count, J, 4, dtype=torch.float32, device=man.device)
     src = torch.empty(count, dtype=torch.int64, device=man.device)
     group = torch.empty(count, dtype=torch.int32, device=man.device)
     if count:
@@ -86,13 +106,15 @@ def _joint_weights(weighted, device, dtype):
 
 def host_labels(queries, man, k, metric, weighted, vals, idx, budget=2 ** 18):
     """dist_utils.geo / euc over the whole manifold and the k smallest, restated with torch on the host in fp64 (rounded to fp32
-    at the end), about `budget` pairs at a time: ascending, ties to the lower row, a NaN distance last.  Slow -- a [chunk, M, 21]
-    intermediate and a full sort per chunk -- and meant for small sets."""
+    at the end), about `budget` pairs at a time: ascending, ties to the lower row, a NaN distance last.  Slow -- a [chunk, M, J]
+    intermediate and a full sort per chunk -- and meant for small sets.  Any joint count J = man.shape[1]; `weighted` (the SMPL
+    joint ranks) with 21 only."""
+    _check_joints(man.shape[1], weighted)
     m = man.to(torch.float64)
     w = _joint_weights(weighted, man.device, torch.float64)
     step = max(1, budget // max(len(m), 1))
     for s in range(0, len(queries), step):
-        n = queries[s:s + step].to(torch.float64)[:, None]                             # [c,1,21,4]
+        n = queries[s:s + step].to(torch.float64)[:, None]                             # [c,1,J,4]
         if metric == "geo":
             per_joint = 1.0 - torch.einsum("cjd,mjd->cmj", n[:, 0], m).abs()
         elif metric == "euc":
@@ -108,9 +130,9 @@ def host_labels(queries, man, k, metric, weighted, vals, idx, budget=2 ** 18):
 
 class OnlinePoseDataset(PoseDataset):
     """A `PoseDataset` whose noisy poses and labels are generated, not loaded: built from the manifold files alone
-    (`<amass_dir>/<dataset>/*.npz`, key `pose`), it exposes what `Trainer` and pndf_train_batch read -- pose [F*R,21,4], dist
-    [F*R,k], man [M,21,4], file_off, man_off (and their device copies file_off_t, man_off_t), k, F, Fm, nbytes, device -- with
-    `files` virtual data files of `rows` poses each.  `refresh(draw, seed)` rewrites pose, src, group (the manifold row and the
+    (`<amass_dir>/<dataset>/*.npz`, key `pose`), it exposes what `Trainer` and pndf_train_batch read -- pose [F*R,J,4], dist
+    [F*R,k], man [M,J,4], file_off, man_off (and their device copies file_off_t, man_off_t), k, F, Fm, nbytes, device, num_joints
+    -- with `files` virtual data files of `rows` poses each and J = `num_joints` joints (21: SMPL; any of 1 .. 32).  `refresh(draw, seed)` rewrites pose, src, group (the manifold row and the
     sigma group every pose came from) and dist, nn_idx (the exact k nearest manifold rows) in place; `draw` and `seed` record
     which pool is resident (None before the first refresh).
 
@@ -120,7 +142,8 @@ class OnlinePoseDataset(PoseDataset):
     meant for small sets.  Refused: k > min(16, M), rows >= 2^32, and on cuda a pool + manifold + index + workspace larger than the
     free device memory (the message gives the byte count)."""
 
-    def __init__(self, amass_dir, files, rows, options=None, datasets=None, device="cpu", chunk=65536):
+    def __init__(self, amass_dir, files, rows, options=None, datasets=None, device="cpu", chunk=65536, num_joints=21):
+        J = _check_joints(num_joints)
         man_files = []
         for ds in _subdirs(amass_dir, datasets):
             man_files += sorted(glob.glob(os.path.join(amass_dir, ds, "*.npz")))
@@ -131,19 +154,21 @@ class OnlinePoseDataset(PoseDataset):
             with np.load(f) as z:
                 if "pose" not in z.files:
                     raise ValueError(f"{f}: a manifold file holds `pose`, this one {sorted(z.files)}")
-                mans.append(self._pose(f, z["pose"]))
-        self._init_online(mans, man_files, files, rows, options, device, chunk)
+                mans.append(self._pose(f, z["pose"], J))
+        self._init_online(mans, man_files, files, rows, options, device, chunk, J)
 
     @classmethod
-    def from_manifold(cls, mans, files, rows, options=None, device="cpu", chunk=65536):
-        """the same from a list of arrays [n,21,4], one entry per manifold file (tests, benchmarks)"""
+    def from_manifold(cls, mans, files, rows, options=None, device="cpu", chunk=65536, num_joints=21):
+        """the same from a list of arrays [n,J,4], one entry per manifold file (tests, benchmarks)"""
         self = cls.__new__(cls)
+        J = _check_joints(num_joints)
         names = [f"<manifold {i}>" for i in range(len(mans))]
-        self._init_online([cls._pose(n, p) for n, p in zip(names, mans)], names, files, rows, options, device, chunk)
+        self._init_online([cls._pose(n, p, J) for n, p in zip(names, mans)], names, files, rows, options, device, chunk, J)
         return self
 
-    def _init_online(self, mans, man_files, files, rows, options, device, chunk):
+    def _init_online(self, mans, man_files, files, rows, options, device, chunk, num_joints=21):
         self.options = options or OnlineOptions()
+        J = self.num_joints = _check_joints(num_joints, self.options.weighted)
         F, R, k = int(files), int(rows), int(self.options.k)
         if F < 1 or R < 1:
             raise ValueError(f"an online pool needs files >= 1 and rows >= 1, got {F} x {R}")
@@ -168,12 +193,12 @@ class OnlinePoseDataset(PoseDataset):
         self.chunk = max(1, min(int(chunk), P))
         self._lib = load_library()
         self.options.opts(0, 0, self._lib)                       # refuses bad sigmas / shares / noise here, not at the first refresh
-        self.nbytes = 4 * (P * 84 + P * k + M * 84) + 8 * (P * k + P) + 4 * P + 8 * (len(self.file_off) + len(self.man_off))
+        self.nbytes = 4 * (P * 4 * J + P * k + M * 4 * J) + 8 * (P * k + P) + 4 * P + 8 * (len(self.file_off) + len(self.man_off))
         hip = self.device.type == "cuda"
         if hip:
             # the plan of a search depends on its query count: the workspace must hold a full chunk and the last, shorter one
             sizes = sorted({self.chunk, P % self.chunk} - {0})
-            index_bytes = -(-M // KNN_TILE) * KNN_TILE_BYTES
+            index_bytes = -(-M // KNN_TILE) * knn_tile_bytes(J)
             ws_bound = max(self._plan_bytes(Q, M, k) for Q in sizes)
             need = self.nbytes + index_bytes + ws_bound
             free, _ = torch.cuda.mem_get_info(self.device)
@@ -182,7 +207,7 @@ class OnlinePoseDataset(PoseDataset):
                                   f"{free} are free: a data set larger than device memory is not supported")
         dev = self.device
         self.man = torch.from_numpy(np.concatenate(mans)).to(dev)
-        self.pose = torch.zeros(P, 21, 4, dtype=torch.float32, device=dev)
+        self.pose = torch.zeros(P, J, 4, dtype=torch.float32, device=dev)
         self.dist = torch.zeros(P, k, dtype=torch.float32, device=dev)
         self.nn_idx = torch.zeros(P, k, dtype=torch.int64, device=dev)
         self.src = torch.zeros(P, dtype=torch.int64, device=dev)
@@ -193,7 +218,7 @@ class OnlinePoseDataset(PoseDataset):
         self._index = self._ws = None
         if hip:
             from .knn import PoseIndex
-            self._index = PoseIndex(self.man, metric=self.options.metric, weighted=self.options.weighted, device=dev)._index
+            self._index = PoseIndex(self.man, metric=self.options.metric, weighted=self.options.weighted, device=dev, num_joints=J)._index
             ws = max(self._index.workspace_bytes(Q, k) for Q in sizes)
             self._ws = torch.empty(max(ws, 16), dtype=torch.uint8, device=dev)
             self.nbytes += index_bytes + ws
@@ -216,7 +241,7 @@ class OnlinePoseDataset(PoseDataset):
                 stream = stream_handle(self.device)
                 for s in range(0, P, self.chunk):
                     c = min(self.chunk, P - s)
-                    self._index.search(self.pose.data_ptr() + 336 * s, c, self.k, self.dist.data_ptr() + 4 * self.k * s,
+                    self._index.search(self.pose.data_ptr() + 16 * self.num_joints * s, c, self.k, self.dist.data_ptr() + 4 * self.k * s,
                                        self.nn_idx.data_ptr() + 8 * self.k * s, self._ws.data_ptr(), stream)
         else:
             host_labels(self.pose, self.man, self.k, self.options.metric, self.options.weighted, self.dist, self.nn_idx)

@@ -10,6 +10,10 @@ Labels: the exact k nearest database poses of every query under the reference's 
 neighbours' axis-angle, as the reference stores it), plus `nn_idx` [n,k] int64.  `--manifold_dir` also writes every database
 file's quaternions under key `pose` (`man_poses` of load_data.py:57-61).
 
+Another skeleton: `--num_joints J` (1 .. 32) reads the first 3 J columns of `pose_body` as J axis-angle joints and writes `pose`
+[n,J,4], `nn_pose` [n,k,J,3]: the files `PoseDataset(num_joints=J)` loads.  With 21 the numpy stream and the output are what they
+were.
+
 Kept from the reference's sampler, on purpose:
   * one `rand(21, 4)` draw per sigma group is added to every pose of the group: the noise is shared within a group;
   * the noise is U[0, 1) (`np.random.rand`), not zero-mean;
@@ -45,29 +49,35 @@ def group_sizes(num_samples: int) -> np.ndarray:
 
 
 def sample_queries(quat_pose: np.ndarray, num_samples: int, rng: np.random.RandomState) -> np.ndarray:
-    """One item of create_data.py:PoseData.__getitem__ in mode 'query' (:82-94): quat_pose float32 [n,21,4] -> float64
-    [num_samples,21,4], consuming `rng` in the reference's order."""
+    """One item of create_data.py:PoseData.__getitem__ in mode 'query' (:82-94): quat_pose float32 [n,J,4] -> float64
+    [num_samples,J,4], consuming `rng` in the reference's order (one rand(J, 4) per sigma group; J = 21 there)."""
     out = []
     for i, num in enumerate(group_sizes(num_samples)):
         indices = rng.randint(0, len(quat_pose), num)
-        sampled = quat_pose[indices] + SIGMA[i] * rng.rand(21, 4)
+        sampled = quat_pose[indices] + SIGMA[i] * rng.rand(quat_pose.shape[1], 4)
         sampled = sampled / np.linalg.norm(sampled, axis=2, keepdims=True)
         out.extend(sampled)
     return np.array(out)
 
 
 def aa_to_quat(aa: np.ndarray):
-    """axis-angle [n,21,3] -> quaternions [n,21,4] (real part first) with the engine's conversion (motion_denoise), on the
+    """axis-angle [n,J,3] -> quaternions [n,J,4] (real part first) with the engine's conversion (motion_denoise), on the
     host in float32 as the reference converts (create_data.py:33-37)"""
     import torch
     from .motion_denoise import axis_angle_to_quaternion
     return axis_angle_to_quaternion(torch.from_numpy(np.ascontiguousarray(aa, dtype=np.float32)))
 
 
-def load_pose_body(path: str) -> np.ndarray:
-    """`pose_body` of a VPoser-style file -> float32 [n,21,3] (the first 63 values: create_data.py:72-73)"""
-    p = np.load(path)["pose_body"].astype(np.float32)[:, :63]
-    return p.reshape(len(p), 21, 3)
+def load_pose_body(path: str, num_joints: int = 21) -> np.ndarray:
+    """`pose_body` of a VPoser-style file -> float32 [n,J,3] (the first 3 J values; 63 for the 21 joints of create_data.py:72-73)"""
+    J = int(num_joints)
+    if not 1 <= J <= 32:
+        raise ValueError(f"num_joints = {J}: 1 .. 32 joints")
+    p = np.load(path)["pose_body"].astype(np.float32)
+    if p.ndim != 2 or p.shape[1] < 3 * J:
+        raise ValueError(f"{path}: pose_body is {p.shape}, {J} joints need [n, >= {3 * J}]")
+    p = p[:, :3 * J]
+    return p.reshape(len(p), J, 3)
 
 
 def database_files(raw_data: str, datasets=None):
@@ -79,27 +89,28 @@ def database_files(raw_data: str, datasets=None):
     return files
 
 
-def make_queries(seq_file: str, num_samples: int, runs: int, seed: int) -> np.ndarray:
-    """`runs` items of the reference's sampler from one seeded stream -> float64 [runs * num_samples, 21, 4]"""
+def make_queries(seq_file: str, num_samples: int, runs: int, seed: int, num_joints: int = 21) -> np.ndarray:
+    """`runs` items of the reference's sampler from one seeded stream -> float64 [runs * num_samples, J, 4]"""
     group_sizes(num_samples)
-    quat = aa_to_quat(load_pose_body(seq_file)).numpy()
+    quat = aa_to_quat(load_pose_body(seq_file, num_joints)).numpy()
     rng = np.random.RandomState(seed)
     return np.concatenate([sample_queries(quat, num_samples, rng) for _ in range(runs)], axis=0)
 
 
 def generate(raw_data, out_dir, seq_file, metric="geo", num_samples=100, k_dist=5, batch_size=65536, runs=1000, seed=0,
-             weighted=False, datasets=None, manifold_dir=None, device="cuda:0"):
+             weighted=False, datasets=None, manifold_dir=None, device="cuda:0", num_joints=21):
     """Writes <out_dir>/<seq_file> (and, with manifold_dir, the database's quaternions); returns the output path."""
     import torch
-    from .knn import PoseIndex
+    from .knn import PoseIndex, joint_weights
+    joint_weights(num_joints, weighted)      # refuses --weighted with another joint count than 21 before anything is read
     seq_path = os.path.join(raw_data, seq_file)
     if not os.path.exists(seq_path):
         raise FileNotFoundError(f"missing sequence file {seq_path}")
-    queries = make_queries(seq_path, num_samples, runs, seed)
+    queries = make_queries(seq_path, num_samples, runs, seed, num_joints)
     files = database_files(raw_data, datasets)
     if not files:
         raise FileNotFoundError(f"no database files <dataset>/*.npz under {raw_data}")
-    aa = [load_pose_body(f) for f in files]
+    aa = [load_pose_body(f, num_joints) for f in files]
     db_aa = np.concatenate(aa, axis=0)
     db_q = aa_to_quat(db_aa).numpy()
     if manifold_dir:
@@ -109,7 +120,7 @@ def generate(raw_data, out_dir, seq_file, metric="geo", num_samples=100, k_dist=
             os.makedirs(os.path.dirname(dst), exist_ok=True)
             np.savez(dst, pose=db_q[o:o + len(a)])
             o += len(a)
-    index = PoseIndex(db_q, metric=metric, weighted=weighted, device=device)
+    index = PoseIndex(db_q, metric=metric, weighted=weighted, device=device, num_joints=num_joints)
     del db_q
     pose = queries.astype(np.float32)
     dist = np.empty((len(pose), k_dist), np.float32)
@@ -141,9 +152,10 @@ def main(argv=None):
     ap.add_argument("--datasets", nargs="*", default=None, help="database subdirectories of --raw_data (default: all)")
     ap.add_argument("--manifold_dir", default=None, help="also write each database file's quaternions (key pose) here")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--num_joints", type=int, default=21, help="joints per pose (1 .. 32): the first 3 J columns of pose_body")
     a = ap.parse_args(argv)
     out = generate(a.raw_data, a.out_dir, a.seq_file, a.metric, a.num_samples, a.k_dist, a.batch_size, a.runs, a.seed,
-                   a.weighted, a.datasets, a.manifold_dir, a.device)
+                   a.weighted, a.datasets, a.manifold_dir, a.device, a.num_joints)
     print("wrote", out)
 
 

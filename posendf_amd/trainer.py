@@ -38,8 +38,9 @@ Differences from the reference, on purpose:
     every `refresh_every` epochs; without it every code path is the file-based one;
   * another skeleton: when `model.StrEnc.parent_mapping` is set (a list or a name of posendf_amd.SKELETONS) the model is
     `SkeletonPoseNDF(opt)`, the files hold `pose` [n,J,4] for its J joints and the cuda backend runs the same four calls on a plan
-    of include/posendf_amd_skeleton_train.h.  The k-NN index and the sampler of `data.online` are 21-joint: online data with
-    another table than SMPL's is refused.
+    of include/posendf_amd_skeleton_train.h.  Online data for it is passed as `dataset=OnlinePoseDataset(..., num_joints=J)`
+    (include/posendf_amd_skeleton_data.h); the config mapping `data.online` builds the 21-joint pool only and is refused on
+    another table than SMPL's.
 """
 from __future__ import annotations
 
@@ -80,7 +81,7 @@ class PoseDataset:
     poses of J = `num_joints` joints (21: SMPL).  `datasets` defaults to every subdirectory (as traindata.database_files).  Files are
     refused by name when `pose` is not [n,J,4], when `dist` does not have one row per pose or has another k than the first file,
     and when they are empty (the sampler cannot draw from them)."""
-    num_joints = 21      # (of the online data set, which sets none)
+    num_joints = 21      # (of a data set that sets none)
 
     def __init__(self, data_dir, amass_dir, datasets=None, device="cpu", num_joints=21):
         self.num_joints = int(num_joints)
@@ -238,9 +239,9 @@ class Trainer:
             else:
                 self.model = PoseNDF(opt).to(self.device)
         self.num_joints = self.model.num_joints
-        if self.online and tuple(self.model.parents) != tuple(SMPL_PARENT):
-            raise PndfError(f"online training data needs the SMPL table: the k-NN index and the sampler are 21-joint, this model has "
-                            f"the {self.num_joints}-joint table {list(self.model.parents)}")
+        if online is not None and tuple(self.model.parents) != tuple(SMPL_PARENT):
+            raise PndfError(f"`data.online` in a config builds the 21-joint pool only, this model has the {self.num_joints}-joint table "
+                            f"{list(self.model.parents)}: pass its pool as dataset=OnlinePoseDataset(..., num_joints={self.num_joints})")
         self.hip = self.device.type == "cuda"
         if self.hip and self.model.enc is None:
             raise PndfError("training on cuda needs the structure encoder (model.StrEnc.use: True), as opt['engine']['train'] = 'hip'")

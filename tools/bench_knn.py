@@ -4,7 +4,8 @@ unweighted, k = 5, at Q = 65,536 x N = 1,048,576 and the reference's per-file sh
 chunked PyTorch-ROCm restatement (einsum / broadcast difference + topk) on the same GPU and the same inputs.  HIP events, one
 warm-up, median of --reps timed calls.  The PyTorch comparator materialises [q, n, 21] blocks and is timed on the first
 --torch_queries queries against the whole database (its time scales with the number of pairs); the two must agree on those
-queries.  One JSON line per case.   usage: python tools/bench_knn.py [--reps 3] [--shapes 65536x1048576 100000x4194304]"""
+queries.  One JSON line per case.  --num_joints J (1 .. 32) measures the J-joint index (include/posendf_amd_skeleton_data.h), unweighted
+only: the joint ranks are SMPL's.   usage: python tools/bench_knn.py [--reps 3] [--shapes 65536x1048576 100000x4194304] [--num_joints 21]"""
 import argparse
 import json
 import os
@@ -18,18 +19,18 @@ from posendf_amd.dist_utils import JOINT_RANK  # noqa: E402
 from posendf_amd.knn import PoseIndex  # noqa: E402
 
 PEAK_FP32_MFMA = 157.3e12
-FLOP_PER_PAIR = 168          # 21 joints x (4 multiply-adds + |.| + weight + sum)
+FLOP_PER_JOINT = 8           # per pair and joint: 4 multiply-adds + |.| + weight + sum (168 per pair at 21 joints)
 
 
-def weights(weighted):
+def weights(weighted, J=21):
     if weighted:
         return torch.nn.functional.normalize(torch.tensor(JOINT_RANK, dtype=torch.float32), dim=0).cuda()
-    return torch.full((21,), 1.0 / 21, device="cuda")
+    return torch.full((J,), 1.0 / J, device="cuda")
 
 
 def torch_knn(db, q, k, metric, weighted, cq=512, cn=131072):
-    """the PyTorch-ROCm restatement: per block [cq, cn, 21] of per-joint terms, weighted sum, running topk"""
-    w = weights(weighted)
+    """the PyTorch-ROCm restatement: per block [cq, cn, J] of per-joint terms, weighted sum, running topk"""
+    w = weights(weighted, db.shape[1])
     vals, idx = [], []
     for s in range(0, len(q), cq):
         qc = q[s:s + cq]
@@ -71,17 +72,19 @@ def main():
     ap.add_argument("--metrics", nargs="*", default=["geo", "euc"])
     ap.add_argument("--torch_queries", type=int, default=1024)
     ap.add_argument("--out", default=None, help="append the JSON lines to this file")
+    ap.add_argument("--num_joints", type=int, default=21)
     a = ap.parse_args()
+    J = a.num_joints
     g = torch.Generator(device="cuda").manual_seed(0)
     for shape in a.shapes:
         Q, N = (int(x) for x in shape.split("x"))
-        db = torch.rand(N, 21, 4, device="cuda", generator=g) * 2 - 1
+        db = torch.rand(N, J, 4, device="cuda", generator=g) * 2 - 1
         db /= db.norm(dim=2, keepdim=True)
-        q = db[torch.randint(0, N, (Q,), device="cuda", generator=g)] + 0.05 * torch.randn(Q, 21, 4, device="cuda", generator=g)
+        q = db[torch.randint(0, N, (Q,), device="cuda", generator=g)] + 0.05 * torch.randn(Q, J, 4, device="cuda", generator=g)
         q /= q.norm(dim=2, keepdim=True)
         for metric in a.metrics:
-            for weighted in (False, True):
-                index = PoseIndex(db, metric=metric, weighted=weighted)
+            for weighted in ((False, True) if J == 21 else (False,)):
+                index = PoseIndex(db, metric=metric, weighted=weighted, num_joints=J)
                 k = 5
                 out = {}
                 t, ts = timed(lambda: out.update(r=index.search(q, k)), a.reps)
@@ -92,11 +95,11 @@ def main():
                 dv = float((tv - vals[:nq]).abs().max())
                 same = float((ti == idx[:nq]).all(1).float().mean())
                 pairs = Q * N
-                rec = {"tool": "bench_knn", "metric": metric, "weighted": weighted, "Q": Q, "N": N, "k": k, "seconds": t,
+                rec = {"tool": "bench_knn", "metric": metric, "weighted": weighted, "num_joints": J, "Q": Q, "N": N, "k": k, "seconds": t,
                        "seconds_all": ts, "pairs_per_s": pairs / t}
                 if metric == "geo":
-                    rec["flop_per_s"] = pairs * FLOP_PER_PAIR / t
-                    rec["fraction_of_fp32_mfma_peak"] = pairs * FLOP_PER_PAIR / t / PEAK_FP32_MFMA
+                    rec["flop_per_s"] = pairs * FLOP_PER_JOINT * J / t
+                    rec["fraction_of_fp32_mfma_peak"] = pairs * FLOP_PER_JOINT * J / t / PEAK_FP32_MFMA
                 rec.update({"torch_queries": nq, "torch_seconds": tt, "torch_pairs_per_s": nq * N / tt,
                             "speedup_vs_torch": (nq * N / tt) and (pairs / t) / (nq * N / tt),
                             "torch_max_abs_diff": dv, "torch_rows_same_idx": same})

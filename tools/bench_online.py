@@ -10,8 +10,10 @@
             refresh amortised over the steps it serves: a pool of 40 files is 10 steps per epoch, times refresh_every = 1 and 10.
 
 Every window is timed with device events around a loop that ends in a synchronise, after a warm-up of the same shape; three
-windows each, median and spread reported.  One JSON document, printed and written to --out.
-usage: python tools/bench_online.py [--out profiles/online/bench.json] [--steps 100] [--warmup 10]"""
+windows each, median and spread reported.  One JSON document, printed and written to --out.  --num_joints J (1 .. 32) measures the
+sampler (32 J bytes per pose) and the refresh for poses of J joints (include/posendf_amd_skeleton_data.h); with another J than 21 the
+step rows, which are the 21-joint trainer's, are left out.
+usage: python tools/bench_online.py [--out profiles/online/bench.json] [--steps 100] [--warmup 10] [--num_joints 21]"""
 import argparse
 import json
 import os
@@ -34,10 +36,10 @@ POOL_FILES, POOL_ROWS = 40, 5000
 WINDOWS = 3
 
 
-def unit_poses(n, seed):
-    """seeded unit quaternions [n,21,4] made on the device (a million poses from the host generator take longer than the bench)"""
+def unit_poses(n, seed, J=21):
+    """seeded unit quaternions [n,J,4] made on the device (a million poses from the host generator take longer than the bench)"""
     g = torch.Generator(device=DEV).manual_seed(seed)
-    q = torch.randn(n, 21, 4, device=DEV, generator=g)
+    q = torch.randn(n, J, 4, device=DEV, generator=g)
     return q / q.norm(dim=2, keepdim=True)
 
 
@@ -64,12 +66,13 @@ def bench_sampler(man, lib):
     out = []
     opt = OnlineOptions().opts(seed=1, draw=0, lib=lib)
     st = torch.cuda.current_stream().cuda_stream
+    J = man.shape[1]
     for P in (1 << 16, 1 << 20):
-        q = torch.empty(P, 21, 4, device=DEV)
-        fn = lambda: engine.online_sample(man.data_ptr(), man.shape[0], 0, P, opt, q.data_ptr(), None, None, st, lib)      # noqa: E731
+        q = torch.empty(P, J, 4, device=DEV)
+        fn = lambda: engine.online_sample(man.data_ptr(), man.shape[0], 0, P, opt, q.data_ptr(), None, None, st, lib, J)      # noqa: E731
         med, ms, reps = windows(fn)
-        nbytes = 672 * P
-        out.append({"what": "pndf_online_sample alone", "P": P, "N": man.shape[0], "launch_us_median": 1e3 * med,
+        nbytes = 32 * J * P
+        out.append({"what": "pndf_online_sample alone" if J == 21 else "pndf_skel_online_sample alone", "num_joints": J, "P": P, "N": man.shape[0], "launch_us_median": 1e3 * med,
                     "launch_us_windows": [1e3 * m for m in ms], "launches_per_window": reps, "counted_bytes": nbytes,
                     "counted_bytes_per_s": nbytes / (med * 1e-3), "fraction_of_hbm_roof": nbytes / (med * 1e-3) / HBM_ROOF,
                     "hbm_roof_bytes_per_s": HBM_ROOF, "bound": "bytes (HBM); the gather's sector waste is not counted"})
@@ -78,7 +81,8 @@ def bench_sampler(man, lib):
 
 
 def bench_refresh(man):
-    ds = OnlinePoseDataset.from_manifold([man.cpu().numpy()], POOL_FILES, POOL_ROWS, OnlineOptions(k=K, metric="geo"), device=DEV)
+    ds = OnlinePoseDataset.from_manifold([man.cpu().numpy()], POOL_FILES, POOL_ROWS, OnlineOptions(k=K, metric="geo"), device=DEV,
+                                         num_joints=man.shape[1])
     draw = [0]
 
     def fn():
@@ -87,8 +91,8 @@ def bench_refresh(man):
     med, ms, reps = windows(fn, target_s=2.0, least=2, most=20)
     P = POOL_FILES * POOL_ROWS
     assert bool(torch.isfinite(ds.dist).all()) and bool((ds.nn_idx >= 0).all())
-    return {"what": "OnlinePoseDataset.refresh: sampler + pndf_knn_search", "P": P, "N": man.shape[0], "k": K, "metric": "geo",
-            "chunk": ds.chunk, "refresh_ms_median": med, "refresh_ms_windows": ms, "refreshes_per_window": reps,
+    return {"what": "OnlinePoseDataset.refresh: sampler + pndf_knn_search", "num_joints": ds.num_joints, "P": P, "N": man.shape[0], "k": K,
+            "metric": "geo", "chunk": ds.chunk, "refresh_ms_median": med, "refresh_ms_windows": ms, "refreshes_per_window": reps,
             "pairs_per_s": P * man.shape[0] / (med * 1e-3), "resident_bytes": ds.nbytes}
 
 
@@ -122,21 +126,23 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--root", default=os.path.join(REPO, "build", "bench_online"), help="experiment directory of the trainer")
+    ap.add_argument("--num_joints", type=int, default=21)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_online.py measures on the GPU"
     lib = engine.load_library()
-    man = unit_poses(N_MAN, seed=2)
+    man = unit_poses(N_MAN, seed=2, J=a.num_joints)
     doc = {"device": torch.cuda.get_device_name(0), "library": lib.pndf_version().decode(), "sampler": bench_sampler(man, lib),
            "refresh": bench_refresh(man)}
     del man
     torch.cuda.empty_cache()
-    doc["step"] = bench_step(a.steps, a.warmup, a.root)
-    steps_per_epoch = POOL_FILES // ITEMS
-    doc["amortised"] = [{"refresh_every": r, "steps_per_pool": steps_per_epoch * r,
-                         "refresh_ms_per_step": doc["refresh"]["refresh_ms_median"] / (steps_per_epoch * r),
-                         "step_ms": doc["step"]["step_ms_median"],
-                         "refresh_over_step": doc["refresh"]["refresh_ms_median"] / (steps_per_epoch * r) / doc["step"]["step_ms_median"]}
-                        for r in (1, 10)]
+    if a.num_joints == 21:
+        doc["step"] = bench_step(a.steps, a.warmup, a.root)
+        steps_per_epoch = POOL_FILES // ITEMS
+        doc["amortised"] = [{"refresh_every": r, "steps_per_pool": steps_per_epoch * r,
+                             "refresh_ms_per_step": doc["refresh"]["refresh_ms_median"] / (steps_per_epoch * r),
+                             "step_ms": doc["step"]["step_ms_median"],
+                             "refresh_over_step": doc["refresh"]["refresh_ms_median"] / (steps_per_epoch * r) / doc["step"]["step_ms_median"]}
+                            for r in (1, 10)]
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(doc, f, indent=1)
