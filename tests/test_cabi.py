@@ -7,7 +7,13 @@ import re
 import numpy as np
 import pytest
 
+import cabi_headers as ch
 from conftest import REPO
+
+# the headers of include/ in the order of posendf_amd/abi.py: HEADERS, each with the number of entry points it declares
+HEADER_COUNTS = {"posendf_amd.h": 61, "posendf_amd_debug.h": 9, "posendf_amd_completion.h": 4, "posendf_amd_interpolation.h": 5,
+                 "posendf_amd_second_order.h": 6, "posendf_amd_online.h": 4, "posendf_amd_skeleton.h": 8, "posendf_amd_skeleton_train.h": 2,
+                 "posendf_amd_skeleton_data.h": 3}
 
 
 @pytest.fixture(scope="module")
@@ -19,7 +25,7 @@ def lib():
 
 
 def _declared(header):
-    return set(re.findall(r"\b(pndf_[a-z0-9_]+)\s*\(", open(os.path.join(REPO, "include", header)).read()))
+    return ch.called(ch.header_text(header))
 
 
 def test_exports_match_header(lib):
@@ -43,15 +49,12 @@ def test_debug_entry_points_live_in_their_own_header(lib):
     for name in dbg:
         assert hasattr(lib, name), f"{name} declared in the debug header but not exported"      # (answered by the debug library, lazily)
     # ... and the PRODUCT library carries none of it: no pndf_debug_* symbol, no instrumented / stage-dump kernel, no probe
-    import subprocess
     import __graft_entry__ as ge
-    syms = subprocess.run(["nm", "-D", "--defined-only", ge.LIB], capture_output=True, text=True, check=True).stdout
-    names = [ln.split()[-1] for ln in syms.splitlines() if ln.strip()]
-    assert any(n == "pndf_project" for n in names) and any(n == "pndf_fused_split_relu_kernel" for n in names)
-    leaked = [n for n in names if "debug" in n or "timing" in n or n.endswith("_dbg") or "probe" in n]
+    names = ch.exported_symbols(ge.LIB)
+    assert "pndf_project" in names and "pndf_fused_split_relu_kernel" in names
+    leaked = sorted(n for n in names if "debug" in n or "timing" in n or n.endswith("_dbg") or "probe" in n)
     assert not leaked, leaked
-    dsyms = subprocess.run(["nm", "-D", "--defined-only", engine.debug_library_path(ge.LIB)], capture_output=True, text=True, check=True).stdout
-    assert all(any(ln.split()[-1] == n for ln in dsyms.splitlines() if ln.strip()) for n in dbg)
+    assert dbg <= ch.exported_symbols(engine.debug_library_path(ge.LIB))
 
 
 def test_product_library_carries_no_experiment(lib, tmp_path):
@@ -244,22 +247,18 @@ def test_reference_checkpoint_interchange(tmp_path):
     assert np.array_equal(s1, s2) and np.array_equal(b1, b2)
 
 
-def test_header_is_plain_c(tmp_path):
-    """The drop-in boundary is a C ABI: include/posendf_amd.h must compile as C99 (no C++-isms, no torch / HIP types in
-    the signatures) and a C translation unit must be able to name every entry point."""
+@pytest.mark.parametrize("header", list(HEADER_COUNTS))
+def test_header_is_plain_c(tmp_path, header):
+    """The drop-in boundary is a C ABI: every header of include/, included alone, must compile as C99 (no C++-isms, no torch / HIP
+    types in the signatures) and a C translation unit must be able to name every entry point: its own and, through it, posendf_amd.h's."""
     import shutil
-    import subprocess
-    from conftest import REPO
-    from posendf_amd import engine
-    gcc = shutil.which("gcc")
-    if gcc is None:
+    from posendf_amd import abi
+    if shutil.which("gcc") is None:
         pytest.skip("no gcc")
-    src = tmp_path / "use_header.c"
-    refs = "\n".join(f"    (void)&{name};" for name in engine.EXPORTS + engine.DEBUG_EXPORTS)
-    src.write_text('#include "posendf_amd.h"\n#include "posendf_amd_debug.h"\nint main(void) {\n' + refs + "\n    return sizeof(pndf_config) > 0 ? 0 : 1;\n}\n")
-    r = subprocess.run([gcc, "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(REPO, "include"),
-                        str(src)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    refs = "\n".join(f"    (void)&{name};" for name in dict.fromkeys(abi.exports(header) + abi.EXPORTS))
+    ok, diagnostics = ch.compiles_as_c99(tmp_path, f'#include "{header}"\nint main(void) {{\n{refs}\n'
+                                         "    return sizeof(pndf_config) > 0 && sizeof(pndf_project_options) > 0 ? 0 : 1;\n}\n")
+    assert ok, diagnostics
 
 
 def test_weight_fingerprint_sees_replaced_parameters_and_modules():
@@ -288,36 +287,41 @@ def test_weight_fingerprint_sees_replaced_parameters_and_modules():
     assert len(f[-1]) == 98
 
 
-# ---- the binding's signature tables, handle base, stream helper and stateless wrappers (posendf_amd/engine.py) ----------------
+# ---- the header registry (posendf_amd/abi.py: HEADERS), the handle base, stream helper and stateless wrappers (posendf_amd/engine.py) ----
 
-_DECLARATION = re.compile(r"((?:const\s+)?\b[A-Za-z_][A-Za-z0-9_]*(?:\s*\*)?)\s*\b(pndf_[a-z0-9_]+)\s*\(([^()]*)\)\s*;")
+def test_header_registry():
+    """abi.HEADERS is the header set: the files of include/, in the order they were added, no name in two tables; the export
+    tuples are read from it."""
+    from posendf_amd import abi, engine
+    assert list(abi.HEADERS) == list(HEADER_COUNTS)
+    assert set(abi.HEADERS) == {name for name in os.listdir(os.path.join(REPO, "include")) if name.endswith(".h")}
+    tables = list(abi.HEADERS.items())
+    for i, (header, table) in enumerate(tables):
+        for other, other_table in tables[i + 1:]:
+            assert not set(table) & set(other_table), (header, other, sorted(set(table) & set(other_table)))
+    assert abi.DEBUG_HEADER in abi.HEADERS
+    assert abi.PRODUCT_EXPORTS == sum((abi.exports(h) for h in abi.HEADERS if h != abi.DEBUG_HEADER), ())
+    assert engine.EXPORTS == abi.EXPORTS == abi.exports("posendf_amd.h") and engine.DEBUG_EXPORTS == abi.DEBUG_EXPORTS == abi.exports(abi.DEBUG_HEADER)
 
 
-def _prototypes(header):
-    """{name: (return type, parameter count)} of every `pndf_*(...);` declaration, comments stripped"""
-    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(REPO, "include", header)).read(), flags=re.S)
-    text = "\n".join(ln for ln in re.sub(r"//[^\n]*", " ", text).splitlines() if not ln.lstrip().startswith("#"))
-    protos = {}
-    for ret, name, params in _DECLARATION.findall(text):
-        assert name not in protos, f"{name} declared twice"
-        params = params.strip()
-        protos[name] = (" ".join(ret.replace("*", " * ").split()), 0 if params in ("", "void") else params.count(",") + 1)
-    return protos
-
-
-@pytest.mark.parametrize("header,table,count", [("posendf_amd.h", "_SIGNATURES", 61), ("posendf_amd_debug.h", "_DEBUG_SIGNATURES", 9)])
-def test_signature_table_matches_header(lib, header, table, count):
+@pytest.mark.parametrize("header,count", list(HEADER_COUNTS.items()))
+def test_signature_table_matches_header(lib, header, count):
     """Every declaration of the header has an entry of the same parameter count and return kind in the table the binding is
-    made from, in the header's order, and no entry leaves its restype to ctypes' default."""
-    from posendf_amd import engine
-    protos, sigs = _prototypes(header), getattr(engine, table)
-    assert len(protos) == count and set(protos) == _declared(header), "the declaration pattern missed one"
-    assert list(sigs) == list(protos)
-    assert tuple(sigs) == (engine.EXPORTS if table == "_SIGNATURES" else engine.DEBUG_EXPORTS)
+    made from, in the header's order, no entry leaves its restype to ctypes' default, the loaded library is bound from the table and
+    the binary the header belongs to defines every name."""
+    import __graft_entry__ as ge
+    from posendf_amd import abi
+    protos, sigs = ch.prototypes(header), abi.HEADERS[header]
+    assert len(protos) == count and set(protos) == ch.called(ch.header_text(header, comments=False)), "the declaration pattern missed one"
+    if header in ("posendf_amd.h", abi.DEBUG_HEADER):      # (the companion headers' comments name other headers' functions)
+        assert set(protos) == _declared(header), "the declaration pattern missed one"
+    assert list(sigs) == list(protos) and tuple(sigs) == abi.exports(header)
     kinds = {"void": (None,), "const char *": (ctypes.c_char_p,), "int64_t": (ctypes.c_int64,), "int": (ctypes.c_int, ctypes.c_int32),
              "int32_t": (ctypes.c_int, ctypes.c_int32), "unsigned": (ctypes.c_uint,)}
     assert ctypes.sizeof(ctypes.c_int) == 4
-    bound = lib if table == "_SIGNATURES" else lib._debug()
+    debug = header == abi.DEBUG_HEADER
+    bound = lib._debug() if debug else lib
+    defined = ch.exported_symbols(abi.debug_library_path(ge.LIB) if debug else ge.LIB)
     for name, (ret, n_params) in protos.items():
         entry = sigs[name]
         assert isinstance(entry, tuple) and len(entry) == 2, f"{name}: the entry must be (restype, argtypes)"
@@ -326,6 +330,7 @@ def test_signature_table_matches_header(lib, header, table, count):
         assert ret in kinds and restype in kinds[ret], f"{name}: returns {ret}, bound as {restype}"
         fn = getattr(bound, name)
         assert fn.restype is restype and list(fn.argtypes) == list(argtypes), f"{name}: the loaded library is not bound from the table"
+        assert name in defined, f"{name}: not a defined dynamic symbol of its library"
 
 
 def test_experiment_words_cover_every_translation_unit(lib):

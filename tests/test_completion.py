@@ -5,15 +5,14 @@
 signature table, and the `PoseCompletion` driver.  Runs without a GPU; tests/test_completion_gpu.py holds the device to the same."""
 import ctypes
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import cabi_headers as ch
 import completion_oracle as co
-from conftest import REPO, outlier_gate, rel_err_rows
+from conftest import outlier_gate, rel_err_rows
 
 TOL = 1e-4
 SETS = list(co.OPTION_SETS)
@@ -253,55 +252,17 @@ def test_a_nan_distance_is_not_frozen(sd):
     assert out[2][m[2]].tobytes() == q0[2][m[2]].tobytes() and out[[0, 1, 3]].tobytes() == q0[[0, 1, 3]].tobytes()
 
 
-# ---- 7. the companion header against its signature table, in the style of tests/test_cabi.py:test_signature_table_matches_header
-_DECLARATION = re.compile(r"((?:const\s+)?\b[A-Za-z_][A-Za-z0-9_]*(?:\s*\*)?)\s*\b(pndf_[a-z0-9_]+)\s*\(([^()]*)\)\s*;")
+# ---- 7. the companion header: what is its own (its table, binding, symbols and C99 build: tests/test_cabi.py, for every header alike)
 HEADER = "posendf_amd_completion.h"
 
 
-def _prototypes(header):
-    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(REPO, "include", header)).read(), flags=re.S)
-    text = "\n".join(ln for ln in re.sub(r"//[^\n]*", " ", text).splitlines() if not ln.lstrip().startswith("#"))
-    protos = {}
-    for ret, name, params in _DECLARATION.findall(text):
-        assert name not in protos, f"{name} declared twice"
-        params = params.strip()
-        protos[name] = (" ".join(ret.replace("*", " * ").split()), 0 if params in ("", "void") else params.count(",") + 1)
-    return protos
-
-
-def test_completion_table_matches_its_header(tmp_path):
-    import shutil
-    import subprocess
+def test_completion_table_matches_its_header():
     import __graft_entry__ as ge
     ge.build()
-    from posendf_amd import engine
-    lib = engine.load_library()
-    protos, sigs = _prototypes(HEADER), engine._COMPLETION_SIGNATURES
-    assert list(protos) == ["pndf_complete_step", "pndf_complete_workspace_floats", "pndf_complete", "pndf_complete_cpu"]
-    assert list(sigs) == list(protos) and tuple(sigs) == engine.COMPLETION_EXPORTS
-    assert not set(engine.COMPLETION_EXPORTS) & set(engine.EXPORTS) and not set(engine.COMPLETION_EXPORTS) & set(engine.DEBUG_EXPORTS)
-    assert not set(protos) & set(_prototypes("posendf_amd.h"))
-    kinds = {"int64_t": (ctypes.c_int64,), "int": (ctypes.c_int, ctypes.c_int32)}
-    for name, (ret, n_params) in protos.items():
-        restype, argtypes = sigs[name]
-        assert len(argtypes) == n_params, f"{name}: {n_params} parameters declared, {len(argtypes)} bound"
-        assert ret in kinds and restype in kinds[ret], f"{name}: returns {ret}, bound as {restype}"
-        fn = getattr(lib, name)
-        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), f"{name}: the loaded library is not bound from the table"
-    syms = subprocess.run(["nm", "-D", "--defined-only", ge.LIB], capture_output=True, text=True, check=True).stdout
-    names = {ln.split()[-1] for ln in syms.splitlines() if ln.strip()}
-    assert set(protos) <= names and "pndf_complete_step_kernel" in names
-    public = open(os.path.join(REPO, "include", HEADER)).read()
+    assert list(ch.prototypes(HEADER)) == ["pndf_complete_step", "pndf_complete_workspace_floats", "pndf_complete", "pndf_complete_cpu"]
+    assert "pndf_complete_step_kernel" in ch.exported_symbols(ge.LIB)
+    public = ch.header_text(HEADER)
     assert "debug" not in public.lower() and '#include "posendf_amd.h"' in public
-    gcc = shutil.which("gcc")
-    if gcc is None:
-        pytest.skip("no gcc")
-    src = tmp_path / "use_header.c"
-    refs = "\n".join(f"    (void)&{name};" for name in engine.COMPLETION_EXPORTS + engine.EXPORTS)
-    src.write_text(f'#include "{HEADER}"\nint main(void) {{\n{refs}\n    return sizeof(pndf_project_options) > 0 ? 0 : 1;\n}}\n')
-    r = subprocess.run([gcc, "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(REPO, "include"), str(src)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
 
 
 # ---- 8. the driver

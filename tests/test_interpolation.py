@@ -6,15 +6,15 @@ against its signature table, and the `PoseInterpolation` driver.  Runs without a
 device to the same."""
 import ctypes
 import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
+import cabi_headers as ch
 import interpolation_oracle as io
-from conftest import REPO, outlier_gate, rel_err_rows
-from test_completion import _prototypes, cpu_engine, cpu_net
+from conftest import outlier_gate, rel_err_rows
+from test_completion import cpu_engine, cpu_net
 
 TOL = 1e-4
 SETS = list(io.OPTION_SETS)
@@ -278,45 +278,22 @@ def test_crafted_joints_on_the_host(sd):
             assert np.abs(got[ok].astype(np.float64) - want[ok]).max() <= 16 * 2.0 ** -24
 
 
-# ---- 7. the companion header against its signature table, in the manner of tests/test_completion.py check 7
+# ---- 7. the companion header: what is its own (its table, binding, symbols and C99 build: tests/test_cabi.py, for every header alike)
 def test_interpolation_table_matches_its_header(tmp_path):
-    import shutil
-    import subprocess
     import __graft_entry__ as ge
     ge.build()
-    from posendf_amd import engine
-    lib = engine.load_library()
-    protos, sigs = _prototypes(HEADER), engine._INTERPOLATION_SIGNATURES
+    from posendf_amd import abi, engine
+    protos = ch.prototypes(HEADER)
     assert list(protos) == ["pndf_interp_fill", "pndf_interp_band_step", "pndf_interpolate_workspace_floats", "pndf_interpolate",
                             "pndf_interpolate_cpu"]
-    assert list(sigs) == list(protos) and tuple(sigs) == engine.INTERPOLATION_EXPORTS
-    others = set(engine.EXPORTS) | set(engine.COMPLETION_EXPORTS) | set(engine.DEBUG_EXPORTS)
-    assert not set(engine.INTERPOLATION_EXPORTS) & others
-    assert not set(protos) & (set(_prototypes("posendf_amd.h")) | set(_prototypes("posendf_amd_completion.h")))
-    assert [len(sigs[n][1]) for n in protos] == [7, 10, 2, 14, 12]
-    kinds = {"int64_t": (ctypes.c_int64,), "int": (ctypes.c_int, ctypes.c_int32)}
-    for name, (ret, n_params) in protos.items():
-        restype, argtypes = sigs[name]
-        assert len(argtypes) == n_params, f"{name}: {n_params} parameters declared, {len(argtypes)} bound"
-        assert ret in kinds and restype in kinds[ret], f"{name}: returns {ret}, bound as {restype}"
-        fn = getattr(lib, name)
-        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), f"{name}: the loaded library is not bound from the table"
-    syms = subprocess.run(["nm", "-D", "--defined-only", ge.LIB], capture_output=True, text=True, check=True).stdout
-    names = {ln.split()[-1] for ln in syms.splitlines() if ln.strip()}
-    assert set(protos) <= names and {"pndf_interp_fill_kernel", "pndf_interp_band_kernel"} <= names
+    assert [len(abi.HEADERS[HEADER][n][1]) for n in protos] == [7, 10, 2, 14, 12]
+    assert {"pndf_interp_fill_kernel", "pndf_interp_band_kernel"} <= ch.exported_symbols(ge.LIB)
     assert engine.INTERP_MODES == {"slerp": 0, "nlerp": 1}
-    public = open(os.path.join(REPO, "include", HEADER)).read()
+    public = ch.header_text(HEADER)
     assert "debug" not in public.lower() and '#include "posendf_amd.h"' in public
     assert "PNDF_INTERP_SLERP = 0" in public and "PNDF_INTERP_NLERP = 1" in public
-    gcc = shutil.which("gcc")
-    if gcc is None:
-        pytest.skip("no gcc")
-    src = tmp_path / "use_header.c"
-    refs = "\n".join(f"    (void)&{name};" for name in engine.INTERPOLATION_EXPORTS + engine.EXPORTS)
-    src.write_text(f'#include "{HEADER}"\nint main(void) {{\n{refs}\n    return sizeof(pndf_project_options) > 0 && PNDF_INTERP_NLERP == 1 ? 0 : 1;\n}}\n')
-    r = subprocess.run([gcc, "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(REPO, "include"), str(src)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    ok, diagnostics = ch.compiles_as_c99(tmp_path, f'#include "{HEADER}"\nint main(void) {{ return PNDF_INTERP_NLERP == 1 ? 0 : 1; }}\n')
+    assert ok, diagnostics
 
 
 # ---- 8. the driver

@@ -5,17 +5,15 @@ distribution of rows and groups, the companion header against its signature tabl
 tests/test_online_gpu.py holds the kernel and the device data set to the same."""
 import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import cabi_headers as ch
 import knn_oracle as ko
 import online_oracle as oo
 import trainer_fixtures as trf
-from conftest import REPO
 
 BAD_ARG, NO_DEVICE = -1, -6
 
@@ -163,34 +161,22 @@ def test_shares_make_the_thresholds(lib):
 
 # ---- 5. ABI ------------------------------------------------------------------------------------------------------------------------
 def test_header_matches_the_signature_table(lib):
-    """every declaration of the companion header is bound from _ONLINE_SIGNATURES, in the header's order, with its parameter count
-    and return kind; posendf_amd.h declares none of them"""
+    """what is the online header's own (its table, binding and symbols: tests/test_cabi.py, for every header alike): every entry point
+    returns a status, posendf_amd.h names none of them, the build knows the sources, the options structure has the header's size"""
     import __graft_entry__ as ge
-    from posendf_amd import engine
-    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(REPO, "include", "posendf_amd_online.h")).read(), flags=re.S)
-    protos = re.findall(r"\b(\w+)\s+(pndf_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text)
-    assert [n for _, n, _ in protos] == list(engine._ONLINE_SIGNATURES) == list(engine.ONLINE_EXPORTS)
-    assert len(protos) == 4
-    for ret, name, params in protos:
-        restype, argtypes = engine._ONLINE_SIGNATURES[name]
-        assert len(argtypes) == params.count(",") + 1, name
-        assert ret == "int" and restype is ctypes.c_int, name
-        fn = getattr(lib, name)
-        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
-    assert not set(engine.ONLINE_EXPORTS) & set(engine.EXPORTS)
-    main = open(os.path.join(REPO, "include", "posendf_amd.h")).read()
-    assert not any(n in main for n in engine.ONLINE_EXPORTS)
+    from posendf_amd import abi, engine
+    header = "posendf_amd_online.h"
+    assert all(ret == "int" and abi.HEADERS[header][name][0] is ctypes.c_int for name, (ret, _) in ch.prototypes(header).items())
+    main = ch.header_text("posendf_amd.h")
+    assert not any(n in main for n in abi.exports(header))
     assert "pndf_online.hip" in ge.PRODUCT_SOURCES and "pndf_online.h" in ge.HIP_DEPS
     assert ctypes.sizeof(engine.OnlineOpts) == 152      # 8 + 4 + 4 + 4 + 64 + 64, padded to the struct's 8-byte alignment
 
 
 def test_header_compiles_as_plain_c(tmp_path):
-    src = tmp_path / "online_header.c"
-    src.write_text('#include "posendf_amd_online.h"\n'
-                   "int use(void) { pndf_online_opts o; o.n_sigma = PNDF_ONLINE_MAX_SIGMA; return (int)sizeof(o) + o.n_sigma + PNDF_ONLINE_SYMMETRIC; }\n")
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(REPO, "include"), str(src)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    ok, diagnostics = ch.compiles_as_c99(tmp_path, '#include "posendf_amd_online.h"\nint use(void) { pndf_online_opts o; '
+                                         "o.n_sigma = PNDF_ONLINE_MAX_SIGMA; return (int)sizeof(o) + o.n_sigma + PNDF_ONLINE_SYMMETRIC; }\n")
+    assert ok, diagnostics
 
 
 def _refusals(opt_of):

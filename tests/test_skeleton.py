@@ -5,15 +5,14 @@ against oracle.posendf_np (SMPL) and against the reference's own autograd on a h
 tests/test_skeleton_gpu.py holds the HIP unit to the same gates."""
 import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import cabi_headers as ch
 import skeleton_oracle as sko
-from conftest import REPO, d_rows, golden_weights, pose_gate, rel_err_rows
+from conftest import d_rows, golden_weights, pose_gate, rel_err_rows
 from oracle import posendf_np as onp
 from posendf_amd import synth
 
@@ -239,22 +238,10 @@ def test_create_refusals_name_the_field():
 
 # ------------------------------------------------------------------------------------------ 5. the header
 def test_header_matches_the_signature_table(tmp_path):
+    """what the skeleton unit adds to the build, and its handle type in a C call; its header against its table is tests/test_cabi.py's"""
     import __graft_entry__ as ge
-    ge.build()
     from posendf_amd import engine
-    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(REPO, "include", "posendf_amd_skeleton.h")).read(), flags=re.S)
-    protos = re.findall(r"\b(pndf_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text)
-    assert [n for n, _ in protos] == list(engine._SKELETON_SIGNATURES) == list(engine.SKELETON_EXPORTS)
-    lib = engine.load_library()
-    for name, params in protos:
-        restype, argtypes = engine._SKELETON_SIGNATURES[name]
-        assert len(argtypes) == params.count(",") + 1, name
-        fn = getattr(lib, name)
-        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
-    assert not set(engine.SKELETON_EXPORTS) & set(engine.EXPORTS)
     assert "pndf_experiment_word_skeleton" in engine.EXPERIMENT_WORDS and "pndf_skeleton.hip" in ge.PRODUCT_SOURCES
-    src = tmp_path / "use.c"
-    src.write_text('#include "posendf_amd_skeleton.h"\nint main(void) { pndf_skel_handle h = 0; return pndf_skel_destroy(h) + (int)sizeof(pndf_config) * 0; }\n')
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(REPO, "include"), str(src)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    ok, diagnostics = ch.compiles_as_c99(tmp_path, '#include "posendf_amd_skeleton.h"\nint main(void) { pndf_skel_handle h = 0; '
+                                         "return pndf_skel_destroy(h) + (int)sizeof(pndf_config) * 0; }\n")
+    assert ok, diagnostics

@@ -4,19 +4,16 @@ bit for bit, against the fp64 restatement of tests/skeleton_data_oracle.py for o
 `OnlinePoseDataset(num_joints=15)` and the trainer on it, the traindata helpers and what `PoseIndex` refuses before it touches a
 device.  tests/test_skeleton_data_gpu.py holds the kernels to the same."""
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import cabi_headers as ch
 import knn_oracle as ko
 import online_oracle as oo
 import skeleton_data_oracle as sdo
 import trainer_fixtures as trf
-from conftest import REPO
 
 BAD_ARG = sdo.BAD_ARG
 
@@ -30,38 +27,23 @@ def lib():
 
 
 # ------------------------------------------------------------------------------------------ 1. the header
-def test_header_matches_the_signature_table(lib, tmp_path):
+def test_header_matches_the_signature_table(tmp_path):
+    """each call takes its 21-joint form's parameters with num_joints after N, the build watches the header, and the calls in C; the
+    header against its table is tests/test_cabi.py's"""
     import __graft_entry__ as ge
-    from posendf_amd import engine
-    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(REPO, "include", "posendf_amd_skeleton_data.h")).read(), flags=re.S)
-    protos = re.findall(r"\b(pndf_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text)
-    assert [n for n, _ in protos] == list(engine._SKELETON_DATA_SIGNATURES) == list(engine.SKELETON_DATA_EXPORTS)
-    assert len(protos) == 3
-    for name, params in protos:
-        restype, argtypes = engine._SKELETON_DATA_SIGNATURES[name]
-        assert len(argtypes) == params.count(",") + 1, name
-        fn = getattr(lib, name)
-        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
-    others = (engine.EXPORTS, engine.COMPLETION_EXPORTS, engine.INTERPOLATION_EXPORTS, engine.SECOND_ORDER_EXPORTS, engine.ONLINE_EXPORTS,
-              engine.SKELETON_EXPORTS, engine.SKELETON_TRAIN_EXPORTS, engine.DEBUG_EXPORTS)
-    assert all(not set(engine.SKELETON_DATA_EXPORTS) & set(t) for t in others)
-    syms = subprocess.run(["nm", "-D", "--defined-only", ge.LIB], capture_output=True, text=True, check=True).stdout
-    names = {ln.split()[-1] for ln in syms.splitlines() if ln.strip()}
-    assert set(engine.SKELETON_DATA_EXPORTS) <= names
-    # each call takes its 21-joint form's parameters with num_joints after N
-    for skel, smpl, table in (("pndf_skel_knn_create", "pndf_knn_create", engine._SIGNATURES),
-                              ("pndf_skel_online_sample", "pndf_online_sample", engine._ONLINE_SIGNATURES),
-                              ("pndf_skel_online_sample_cpu", "pndf_online_sample_cpu", engine._ONLINE_SIGNATURES)):
-        at = table[smpl][1].index(ctypes.c_int64) + 1
-        assert list(engine._SKELETON_DATA_SIGNATURES[skel][1]) == list(table[smpl][1][:at]) + [ctypes.c_int32] + list(table[smpl][1][at:])
+    from posendf_amd import abi
+    mine = abi.HEADERS["posendf_amd_skeleton_data.h"]
+    for skel, smpl, header in (("pndf_skel_knn_create", "pndf_knn_create", "posendf_amd.h"),
+                               ("pndf_skel_online_sample", "pndf_online_sample", "posendf_amd_online.h"),
+                               ("pndf_skel_online_sample_cpu", "pndf_online_sample_cpu", "posendf_amd_online.h")):
+        smpl_args = abi.HEADERS[header][smpl][1]
+        at = smpl_args.index(ctypes.c_int64) + 1
+        assert list(mine[skel][1]) == list(smpl_args[:at]) + [ctypes.c_int32] + list(smpl_args[at:])
     assert "posendf_amd_skeleton_data.h" in " ".join(ge.HIP_DEPS)
-    src = tmp_path / "use.c"
-    src.write_text('#include "posendf_amd_skeleton_data.h"\nint main(void) { pndf_knn_handle h = 0; pndf_online_opts o; '
-                   'return pndf_skel_knn_create(&h, 0, 1, 15, 0, 0, 0) + pndf_skel_online_sample(0, 1, 15, 0, 0, &o, 0, 0, 0, 0) + '
-                   'pndf_skel_online_sample_cpu(0, 1, 15, 0, 0, &o, 0, 0, 0); }\n')
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(REPO, "include"), str(src)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    ok, diagnostics = ch.compiles_as_c99(tmp_path, '#include "posendf_amd_skeleton_data.h"\nint main(void) { pndf_knn_handle h = 0; pndf_online_opts o; '
+                                         'return pndf_skel_knn_create(&h, 0, 1, 15, 0, 0, 0) + pndf_skel_online_sample(0, 1, 15, 0, 0, &o, 0, 0, 0, 0) + '
+                                         'pndf_skel_online_sample_cpu(0, 1, 15, 0, 0, &o, 0, 0, 0); }\n')
+    assert ok, diagnostics
 
 
 # ------------------------------------------------------------------------------------------ 2. refusals

@@ -3,17 +3,15 @@ pinned against the reference's own classes, the header against the signature tab
 the data set's shapes, the model's knob and the trainer's cpu backend on the 15-joint hand."""
 import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import cabi_headers as ch
 import skeleton_oracle as sko
 import skeleton_train_fixtures as stf
 import test_net_plan as tnp
-from conftest import REPO
 
 OK, BAD_ARG, UNSUPPORTED, NO_DEVICE = 0, -1, -4, -6
 ACCEPTED = OK if torch.cuda.is_available() else NO_DEVICE
@@ -48,33 +46,16 @@ def test_stock_fp64_path_equals_the_reference(skel, act):
 
 
 # ------------------------------------------------------------------------------------------ 2. the header
-def test_header_matches_the_signature_table(lib, tmp_path):
-    import __graft_entry__ as ge
-    from posendf_amd import engine
-    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(REPO, "include", "posendf_amd_skeleton_train.h")).read(), flags=re.S)
-    protos = re.findall(r"\b(pndf_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text)
-    assert [n for n, _ in protos] == list(engine._SKELETON_TRAIN_SIGNATURES) == list(engine.SKELETON_TRAIN_EXPORTS)
-    assert len(protos) == 2
-    for name, params in protos:
-        restype, argtypes = engine._SKELETON_TRAIN_SIGNATURES[name]
-        assert len(argtypes) == params.count(",") + 1, name
-        fn = getattr(lib, name)
-        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
-    others = (engine.EXPORTS, engine.COMPLETION_EXPORTS, engine.INTERPOLATION_EXPORTS, engine.SECOND_ORDER_EXPORTS, engine.ONLINE_EXPORTS,
-              engine.SKELETON_EXPORTS, engine.DEBUG_EXPORTS)
-    assert all(not set(engine.SKELETON_TRAIN_EXPORTS) & set(t) for t in others)
-    syms = subprocess.run(["nm", "-D", "--defined-only", ge.LIB], capture_output=True, text=True, check=True).stdout
-    names = {ln.split()[-1] for ln in syms.splitlines() if ln.strip()}
-    assert set(engine.SKELETON_TRAIN_EXPORTS) <= names
-    # pndf_skel_train_batch takes pndf_train_batch's parameters with num_joints after `flip`
-    batch, skel_batch = engine._SIGNATURES["pndf_train_batch"][1], engine._SKELETON_TRAIN_SIGNATURES["pndf_skel_train_batch"][1]
+def test_header_matches_the_signature_table(tmp_path):
+    """pndf_skel_train_batch takes pndf_train_batch's parameters with num_joints after `flip`, and the header's types in a C call; the
+    header against its table is tests/test_cabi.py's"""
+    from posendf_amd import abi
+    batch = abi.HEADERS["posendf_amd.h"]["pndf_train_batch"][1]
+    skel_batch = abi.HEADERS["posendf_amd_skeleton_train.h"]["pndf_skel_train_batch"][1]
     assert list(skel_batch) == list(batch[:14]) + [ctypes.c_int32] + list(batch[14:])
-    src = tmp_path / "use.c"
-    src.write_text('#include "posendf_amd_skeleton_train.h"\nint main(void) { pndf_train_handle h = 0; pndf_config c; '
-                   'return pndf_skel_train_create(&h, &c, 0) + (int)sizeof(pndf_config) * 0; }\n')
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(REPO, "include"), str(src)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    ok, diagnostics = ch.compiles_as_c99(tmp_path, '#include "posendf_amd_skeleton_train.h"\nint main(void) { pndf_train_handle h = 0; pndf_config c; '
+                                         "return pndf_skel_train_create(&h, &c, 0) + (int)sizeof(pndf_config) * 0; }\n")
+    assert ok, diagnostics
 
 
 # ------------------------------------------------------------------------------------------ 3. refusals
