@@ -136,6 +136,24 @@ typedef struct {
 } pndf_project_options;
 void pndf_default_project_options(pndf_project_options* opt);
 
+/* The options with a joint mask: pose completion inside the projection step, for any joint tree (J = 1 .. 32 joints).  A joint whose
+ * bit is set in its pose's word is HELD: it keeps the bits it came with in q_out, whatever they are (a NaN, a zero quaternion),
+ * and still enters the distance and the gradient of the other joints; the other joints take the step above.  Bits J .. 31 of a
+ * word are ignored; `tol` rests a whole pose as before, d_last keeps its meaning, q_out == q_in stays allowed.  With observed ==
+ * NULL or all words zero the call is the one with the 16-byte struct, bit for bit.  Fill it with
+ *   pndf_project_options2 o;  pndf_default_project_options(&o.base);  o.base.struct_size = sizeof o;  o.observed = mask;  o.reserved = 0;
+ * and pass (const pndf_project_options*)&o.  Exactly two entry points take it: pndf_skel_project of posendf_amd_skeleton.h (any
+ * handle) and pndf_project_ex_cpu below (any handle: the 21-joint table and the encoder-less model too).  Every other function
+ * with a pndf_project_options parameter keeps refusing a struct_size other than sizeof(pndf_project_options).  PNDF_ERR_BAD_ARG with
+ * a text that names the field, before anything is launched or written: a struct_size that is neither of the two sizes, reserved
+ * != 0, a misaligned observed, and what is refused in `base`. */
+typedef struct {
+    pndf_project_options base;   /* base.struct_size = sizeof(pndf_project_options2); the rest as pndf_project_options */
+    const uint32_t* observed;    /* one word per pose, bit j set = joint j is held; NULL = no joint is held.
+                                    DEVICE memory for the device entry point, HOST memory for the host twin; 4-byte aligned */
+    uint64_t reserved;           /* must be 0 */
+} pndf_project_options2;         /* 32 bytes */
+
 /* pndf_project with step options.  opt == NULL means the defaults, and with the defaults the call is pndf_project bit for
  * bit.  PNDF_ERR_BAD_ARG (text in pndf_last_error; nothing is launched or written) for a struct_size other than
  * sizeof(pndf_project_options), a step_size that is not finite or <= 0, a tol that is NaN or < 0, an unknown renorm mode.
@@ -161,7 +179,8 @@ int pndf_forward_cpu(pndf_cpu_handle h, const float* q, float* d, int64_t B);   
 int pndf_forward_grad_cpu(pndf_cpu_handle h, const float* q, const float* grad_out, float* d, float* dq, int64_t B); /* posendf.py:18-27 */
 int pndf_project_cpu(pndf_cpu_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps);      /* sample_poses.py:67-74 */
 int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps,
-                        const pndf_project_options* opt);      /* pndf_project_ex: same semantics, same validation */
+                        const pndf_project_options* opt);      /* pndf_project_ex: same semantics, same validation; also takes a
+                                                                  pndf_project_options2, its `observed` in HOST memory */
 const char* pndf_cpu_last_error(pndf_cpu_handle h);   /* h may be NULL: last error of a failed pndf_cpu_create */
 
 /* Host-only weight packer (what pndf_load_weights uploads); needs no device.  Output sizes in floats come

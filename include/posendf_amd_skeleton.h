@@ -28,6 +28,11 @@
  *
  * The host twins pndf_cpu_create / pndf_cpu_load_weights / pndf_forward_cpu / pndf_forward_grad_cpu / pndf_project_cpu /
  * pndf_project_ex_cpu (posendf_amd.h) accept the same skeletons.
+ *
+ * Pose completion -- some joints observed and held, the others pulled onto the manifold -- is pndf_skel_project (the host twin:
+ * pndf_project_ex_cpu) with a pndf_project_options2 (posendf_amd.h) in place of the options: one mask word per pose, the select
+ * inside the step of the gradient's last kernel, no launch more than an unmasked projection.  Still 21-joint: the second order
+ * (posendf_amd_second_order.h) and interpolation; pndf_complete and its host twin keep the SMPL table.
  */
 #ifndef POSENDF_AMD_SKELETON_H
 #define POSENDF_AMD_SKELETON_H
@@ -65,7 +70,9 @@ int pndf_skel_forward_grad(pndf_skel_handle h, const float* q, const float* grad
 
 /* `steps` projection steps with the options of pndf_project_ex (opt == NULL: the plain step q <- q - d * grad d); the step runs
  * inside the gradient's last kernel.  q_out may be q_in itself (no other overlap).  d_last (may be NULL) is dist_pred of the last
- * iteration, evaluated before its update; with steps == 0 q_out is a copy of q_in and d_last is zero. */
+ * iteration, evaluated before its update; with steps == 0 q_out is a copy of q_in and d_last is zero.  `opt` may point to a
+ * pndf_project_options2 (posendf_amd.h; observed: DEVICE memory, one word per pose, read by the kernels of this call): the joints
+ * of its mask are held, bit for bit, and the call is otherwise the same -- with no mask or all words zero the same bits. */
 int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps,
                       const pndf_project_options* opt, void* workspace, int64_t workspace_bytes, void* stream);
 

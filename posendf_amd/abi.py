@@ -37,6 +37,12 @@ class ProjectOptions(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("step_size", c_float), ("renorm", c_int32), ("tol", c_float)]
 
 
+class ProjectOptions2(ctypes.Structure):
+    """pndf_project_options2: the options (`base`, with struct_size = 32) and a joint mask, one uint32 per pose, bit j = joint j is
+    held; taken by pndf_skel_project (device memory) and pndf_project_ex_cpu (host memory) through the options pointer"""
+    _fields_ = [("base", ProjectOptions), ("observed", c_void_p), ("reserved", ctypes.c_uint64)]
+
+
 class DenoiseWeights(ctypes.Structure):
     """pndf_denoise_weights: the loss weights of one outer iteration, evaluated"""
     _fields_ = [("prior_coef", c_float), ("prior_power", c_int32), ("temp_coef", c_float), ("data_coef", c_float)]
@@ -66,6 +72,7 @@ class PndfError(RuntimeError):
 _H = c_void_p                          # every handle type, and every `void* stream`
 _P = c_void_p                          # any other address: tensor data (an int from data_ptr(), or None), a callback, an out value
 _TENSORS = [POINTER(c_void_p), POINTER(c_int64), c_int]      # tensors, numel, n_tensors (host pointers in state-dict order)
+_OPT2 = c_void_p                       # `const pndf_project_options*` where it may point to a ProjectOptions or a ProjectOptions2 (byref of either)
 # ---- the header set, stated once: header of include/ -> {name: (restype, argtypes)} in the header's order; the headers in the order
 # they were added.  A new header is a file in include/, a table here and its declaration count in tests/test_cabi.py.
 DEBUG_HEADER = "posendf_amd_debug.h"      # the one header that lives in libposendf_amd_debug.so; every other one in the product library
@@ -87,7 +94,7 @@ HEADERS = {
         "pndf_forward_cpu": (c_int, [_H, _P, _P, c_int64]),
         "pndf_forward_grad_cpu": (c_int, [_H, _P, _P, _P, _P, c_int64]),
         "pndf_project_cpu": (c_int, [_H, _P, _P, _P, c_int64, c_int]),
-        "pndf_project_ex_cpu": (c_int, [_H, _P, _P, _P, c_int64, c_int, POINTER(ProjectOptions)]),
+        "pndf_project_ex_cpu": (c_int, [_H, _P, _P, _P, c_int64, c_int, _OPT2]),
         "pndf_cpu_last_error": (c_char_p, [_H]),
         # host-only weight packer
         "pndf_packed_sizes": (None, [POINTER(c_int64)] * 2),
@@ -188,7 +195,7 @@ HEADERS = {
         "pndf_skel_workspace_bytes": (c_int64, [_H, c_int64]),
         "pndf_skel_forward": (c_int, [_H, _P, _P, c_int64, _P, c_int64, _H]),
         "pndf_skel_forward_grad": (c_int, [_H, _P, _P, _P, _P, c_int64, _P, c_int64, _H]),
-        "pndf_skel_project": (c_int, [_H, _P, _P, _P, c_int64, c_int, POINTER(ProjectOptions), _P, c_int64, _H]),
+        "pndf_skel_project": (c_int, [_H, _P, _P, _P, c_int64, c_int, _OPT2, _P, c_int64, _H]),
         "pndf_skel_last_error": (c_char_p, [_H]),
     },
     "posendf_amd_skeleton_train.h": {      # training any joint tree

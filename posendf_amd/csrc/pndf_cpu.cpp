@@ -403,12 +403,15 @@ extern "C" int pndf_project_cpu(pndf_cpu_handle h, const float* q_in, float* q_o
     });
 }
 
-// completion, interpolation and the second order stay 21-joint
+// interpolation, the second order and pndf_complete_cpu itself stay 21-joint; another skeleton completes poses
+// through pndf_project_ex_cpu with a pndf_project_options2
 static const char* const SMPL_ONLY = "this entry point runs the 21-joint table of get_parent_mapping('smpl') only; a handle of another skeleton "
-                                     "has pndf_forward_cpu, pndf_forward_grad_cpu, pndf_project_cpu and pndf_project_ex_cpu";
+                                     "has pndf_forward_cpu, pndf_forward_grad_cpu, pndf_project_cpu and pndf_project_ex_cpu (which holds "
+                                     "observed joints when it is given a pndf_project_options2)";
 
 // One step of pndf_project_ex on the host: pndf_step.h's pndf_step_quat -- the statement the device kernels run -- for every joint of
-// a pose that does not rest.  `held`: bit j = joint j is observed and stays as it is (pndf_complete_cpu; pndf_project_ex_cpu holds none).
+// a pose that does not rest.  `held`: bit j = joint j is observed and stays as it is (pndf_complete_cpu, and pndf_project_ex_cpu with the
+// mask of a pndf_project_options2; without one it holds none).
 static void project_step_cpu(float* q, const float* dq, float d, const pndf_project_options& o, uint32_t held, int nj) {
     if (o.tol > 0.f && d < o.tol) return;
     for (int j = 0; j < nj; ++j) {
@@ -443,11 +446,12 @@ extern "C" int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* 
                                    const pndf_project_options* opt) {
     if (!h) return PNDF_ERR_BAD_ARG;
     pndf_project_options o;
-    if (const char* why = pndf_check_project_options(opt, o)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
-    if (pndf_project_options_plain(o)) return pndf_project_cpu(h, q_in, q_out, d_last, B, steps);
+    const uint32_t* observed;      // a pndf_project_options2 brings the joint mask (host memory): completion for any joint tree
+    if (const char* why = pndf_check_project_options2(opt, o, observed)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (!observed && pndf_project_options_plain(o)) return pndf_project_cpu(h, q_in, q_out, d_last, B, steps);
     if (int rc = check(h, q_in, B)) return rc;
     if (steps < 0 || (B > 0 && !q_out)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count or null output pointer");
-    return project_loop_cpu(h, q_in, nullptr, q_out, d_last, B, steps, o);
+    return project_loop_cpu(h, q_in, observed, q_out, d_last, B, steps, o);
 }
 
 // Host twin of pndf_complete (include/posendf_amd_completion.h): the loop of pndf_project_ex_cpu with the observed joints held.  With

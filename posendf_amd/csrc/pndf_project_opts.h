@@ -1,5 +1,6 @@
 // Validation of pndf_project_options (include/posendf_amd.h), shared by pndf_project_ex (pndf_capi.hip) and its host twin
-// pndf_project_ex_cpu (pndf_cpu.cpp): the two refuse the same structs with the same text.
+// pndf_project_ex_cpu (pndf_cpu.cpp): the two refuse the same structs with the same text.  And of pndf_project_options2, the options with
+// a joint mask, which pndf_skel_project (pndf_skeleton.hip) and pndf_project_ex_cpu take besides.
 #pragma once
 #include <math.h>
 
@@ -20,6 +21,27 @@ inline const char* pndf_check_project_options(const pndf_project_options* opt, p
     if (opt->renorm != PNDF_RENORM_NONE && opt->renorm != PNDF_RENORM_UNIT && opt->renorm != PNDF_RENORM_UNIT_FLIP)
         return "pndf_project_options.renorm is not a pndf_renorm mode";
     out = *opt;
+    return nullptr;
+}
+
+// The checker of the two entry points that also take a pndf_project_options2 (pndf_skel_project, pndf_project_ex_cpu): struct_size
+// says which of the two structs `opt` points to.  Returns nullptr, fills `out` from the struct (or its `base`) and sets `observed` to
+// the mask (null: no joint is held), or the reason the struct is refused; nothing the mask points to is read here.
+inline const char* pndf_check_project_options2(const pndf_project_options* opt, pndf_project_options& out, const uint32_t*& observed) {
+    observed = nullptr;
+    if (!opt || opt->struct_size == sizeof(pndf_project_options)) return pndf_check_project_options(opt, out);
+    if (opt->struct_size != sizeof(pndf_project_options2)) {
+        (void)pndf_check_project_options(nullptr, out);
+        return "pndf_project_options.struct_size is neither sizeof(pndf_project_options) nor sizeof(pndf_project_options2): fill the "
+               "struct with pndf_default_project_options";
+    }
+    const pndf_project_options2* o2 = (const pndf_project_options2*)opt;
+    pndf_project_options base = o2->base;
+    base.struct_size = (uint32_t)sizeof(pndf_project_options);
+    if (const char* why = pndf_check_project_options(&base, out)) return why;
+    if (o2->reserved != 0) return "pndf_project_options2.reserved must be 0";
+    if ((uintptr_t)o2->observed & 3) return "pndf_project_options2.observed must be 4-byte aligned";
+    observed = o2->observed;
     return nullptr;
 }
 

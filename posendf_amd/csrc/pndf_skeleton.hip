@@ -15,7 +15,8 @@
 //   trunk reverse              L TN GEMMs, epilogue * sigma'
 //   pndf_skel_enc_rev_kernel   lanes own poses: joints nj-1 .. 0 (children before parents), rows 4..9 of a bone's input adjoint
 //                              added to the parent's feature adjoint, the reverse of the normalisation, grad_out; in project mode
-//                              the step of pndf_step.h in the same kernel
+//                              the step of pndf_step.h in the same kernel, and with the joint mask of a pndf_project_options2 (pose
+//                              completion: one word per pose) a held joint stores the bits it read instead
 // 2 + 2 L launches per evaluation.  No float atomics, no communication between workgroups, every column of a GEMM summed in the
 // same order wherever it sits: the same inputs give the same bits and a pose's result does not depend on its batch.
 #include <hip/hip_runtime.h>
@@ -56,6 +57,7 @@ struct SkArgs {
     float* U0;                // adjoint of the trunk's input, accumulated in place [6 nj][ld] (without the encoder: g_x [4 nj][ld])
     float* Gx;                // g_x = d d / d x [4 nj][ld]
     const float* dist;        // the trunk's output row [ld]
+    const uint32_t* observed; // the chunk's mask words [n], bit j = joint j is held, or null (no joint is held)   (SK_PROJECT)
     int64_t n, ld;
     int nj, encoder, mode;
     int act;                  // act / beta: the encoder's
@@ -156,6 +158,7 @@ extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_kernel(SkArg
         }
     const float dist = e.dist[c];
     const float go = (e.mode == SK_GRAD && e.grad_out) ? e.grad_out[c] : 1.f;
+    const uint32_t held = (e.mode == SK_PROJECT && e.observed) ? e.observed[c] : 0u;
     for (int j = 0; j < e.nj; ++j) {
         float g[BONE];
 #pragma unroll
@@ -170,7 +173,10 @@ extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_kernel(SkArg
             for (int k = 0; k < BONE; ++k) Q[k] = q[j * BONE + k];
             const bool rest = pndf_step_quat(Q, g, dist, e.step_size, e.tol, e.renorm, u);
 #pragma unroll
-            for (int k = 0; k < BONE; ++k) out[j * BONE + k] = rest ? Q[k] : u[k];
+            for (int k = 0; k < BONE; ++k) {      // a held joint keeps the bits it came with: an integer select, no arithmetic on them
+                const uint32_t kept = __float_as_uint(Q[k]), stepped = __float_as_uint(rest ? Q[k] : u[k]);
+                out[j * BONE + k] = __uint_as_float(((held >> j) & 1u) ? kept : stepped);
+            }
         } else {
 #pragma unroll
             for (int k = 0; k < BONE; ++k) out[j * BONE + k] = g[k] * go;
@@ -401,7 +407,8 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
                                  const pndf_project_options* opt, void* workspace, int64_t workspace_bytes, void* stream) {
     if (!h) return PNDF_ERR_BAD_ARG;
     pndf_project_options o;
-    if (const char* why = pndf_check_project_options(opt, o)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    const uint32_t* observed;      // a pndf_project_options2 brings the joint mask: one word per pose, device memory
+    if (const char* why = pndf_check_project_options2(opt, o, observed)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (steps < 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count");
     SkLayout l;
     if (B > 0 && (!q_in || !q_out)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose pointer");
@@ -425,6 +432,7 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
     for (int64_t c0 = 0; c0 < B; c0 += l.nc) {
         e.n = B - c0 < l.nc ? B - c0 : l.nc;
         e.out = q_out + c0 * nq;
+        e.observed = observed ? observed + c0 : nullptr;
         for (int s = 0; s < steps; ++s) {      // from the second step on the iterate is in q_out: a lane reads its pose before it writes it
             e.q = s == 0 ? q_in + c0 * nq : q_out + c0 * nq;
             e.d_out = (d_last && s == steps - 1) ? d_last + c0 : nullptr;

@@ -15,7 +15,7 @@ import numpy as np
 # public names stay importable from here.  `torch` comes from there too: abi imports it before the library is loaded (None without it).
 from .abi import (ACT_CODES, DEBUG_EXPERIMENT_WORDS, DEBUG_EXPORTS, EXPERIMENT_WORDS, EXPORTS, INTERP_MODES, METRIC_CODES,  # noqa: F401
                   NOISE_CODES, PRECISION_CODES, RENORM_CODES, Camera, DenoiseWeights, KeypointOpts, OnlineOpts, PndfConfig, PndfError,
-                  ProjectOptions, debug_library_path, experiment_word, load_library, torch)
+                  ProjectOptions, ProjectOptions2, debug_library_path, experiment_word, load_library, torch)
 
 
 def stream_handle(device) -> int:
@@ -107,6 +107,19 @@ def _opt_ref(lib, step_size, renorm, tol):
     """the `const pndf_project_options*` argument of the entry points that take null for the defaults"""
     opt = project_options(lib, step_size, renorm, tol)
     return None if opt is None else ctypes.byref(opt)
+
+
+def project_options2(lib, observed_ptr, step_size=1.0, renorm="none", tol=0.0):
+    """pndf_project_options2 (include/posendf_amd.h): the step options and the joint mask at `observed_ptr` -- one uint32 per pose, bit j
+    = joint j is held; device memory for pndf_skel_project, host memory for pndf_project_ex_cpu"""
+    opt = ProjectOptions2()
+    lib.pndf_default_project_options(ctypes.byref(opt.base))
+    base = project_options(lib, step_size, renorm, tol)
+    if base is not None:
+        opt.base = base
+    opt.base.struct_size = ctypes.sizeof(opt)
+    opt.observed, opt.reserved = observed_ptr, 0
+    return opt
 
 
 def interp_mode(mode) -> int:
@@ -443,9 +456,16 @@ class SkeletonEngine(_Handle):
         self._check(self.lib.pndf_skel_forward_grad(self.handle, q_ptr, gout_ptr, d_ptr, dq_ptr, int(B), ws_ptr, int(ws_bytes), stream),
                     "pndf_skel_forward_grad")
 
-    def project(self, q_in_ptr, q_out_ptr, d_ptr, B, steps, ws_ptr, ws_bytes, stream=0, *, step_size=1.0, renorm="none", tol=0.0):
-        self._check(self.lib.pndf_skel_project(self.handle, q_in_ptr, q_out_ptr, d_ptr, int(B), int(steps),
-                                               _opt_ref(self.lib, step_size, renorm, tol), ws_ptr, int(ws_bytes), stream), "pndf_skel_project")
+    def project(self, q_in_ptr, q_out_ptr, d_ptr, B, steps, ws_ptr, ws_bytes, stream=0, *, step_size=1.0, renorm="none", tol=0.0,
+                observed_ptr=None):
+        """pndf_skel_project; `observed_ptr`: one uint32 per pose in device memory, bit j = joint j is held (pose completion, through a
+        pndf_project_options2); None: no joint is held and the call is the one without a mask"""
+        if observed_ptr is None:
+            opt = _opt_ref(self.lib, step_size, renorm, tol)
+        else:
+            opt = ctypes.byref(project_options2(self.lib, observed_ptr, step_size, renorm, tol))
+        self._check(self.lib.pndf_skel_project(self.handle, q_in_ptr, q_out_ptr, d_ptr, int(B), int(steps), opt, ws_ptr, int(ws_bytes), stream),
+                    "pndf_skel_project")
 
 
 def adam_step(p_ptr, g_ptr, m_ptr, v_ptr, n, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, stream=0, lib=None):
@@ -628,7 +648,14 @@ class CpuEngine(_Handle):
     def forward_grad(self, q_ptr, gout_ptr, d_ptr, dq_ptr, B, stream=0):
         self._check(self.lib.pndf_forward_grad_cpu(self.handle, q_ptr, gout_ptr, d_ptr, dq_ptr, B), "pndf_forward_grad_cpu")
 
-    def project(self, q_in_ptr, q_out_ptr, d_ptr, B, steps, stream=0, *, step_size=1.0, renorm="none", tol=0.0):
+    def project(self, q_in_ptr, q_out_ptr, d_ptr, B, steps, stream=0, *, step_size=1.0, renorm="none", tol=0.0, observed_ptr=None):
+        """`observed_ptr`: one uint32 per pose in host memory, bit j = joint j is held (pndf_project_ex_cpu with a pndf_project_options2:
+        any joint tree); None: the call without a mask"""
+        if observed_ptr is not None:
+            opt2 = project_options2(self.lib, observed_ptr, step_size, renorm, tol)
+            self._check(self.lib.pndf_project_ex_cpu(self.handle, q_in_ptr, q_out_ptr, d_ptr, B, int(steps), ctypes.byref(opt2)),
+                        "pndf_project_ex_cpu")
+            return
         opt = project_options(self.lib, step_size, renorm, tol)
         if opt is None:
             self._check(self.lib.pndf_project_cpu(self.handle, q_in_ptr, q_out_ptr, d_ptr, B, int(steps)), "pndf_project_cpu")

@@ -23,7 +23,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from .engine import Engine, PndfError, SecondOrderEngine, StreamWorkspaces, device_index, state_dict_order, stream_handle
-from .model_base import PoseModel, _Distance, cached, gradient  # noqa: F401  (`gradient` is part of this module's surface)
+from .model_base import PoseModel, _Distance, cached, gradient, pack_observed  # noqa: F401  (`gradient` is part of this module's surface)
 from .synth import PARENT
 
 
@@ -166,20 +166,7 @@ class PoseNDF(PoseModel):
         d, g, t, out = self._second_order(q, v, w_d, w_t)
         return d.view(-1, 1), g, t.view(-1, 1), out
 
-    @staticmethod
-    def pack_observed(observed, B, device, num_joints=len(PARENT)):
-        """bool [21] or [B,21] (True = the joint is observed and held) -> one word per pose, bit j = joint j, as an int32 tensor [B]
-        on `device` (the uint32 of include/posendf_amd_completion.h: bits 0 .. 20 only, so the sign bit is never set)"""
-        obs = torch.as_tensor(observed, device=device)
-        if obs.dtype != torch.bool:
-            raise PndfError(f"observed must be a bool tensor, not {obs.dtype}")
-        J = num_joints
-        if obs.shape == (J,):
-            obs = obs.expand(B, J)
-        if obs.shape != (B, J):
-            raise PndfError(f"observed must have shape [{J}] or [{B}, {J}], not {list(obs.shape)}")
-        bits = torch.ones(J, dtype=torch.int64, device=device) << torch.arange(J, device=device)
-        return (obs.to(torch.int64) * bits).sum(dim=1).to(torch.int32).contiguous()
+    pack_observed = staticmethod(pack_observed)      # the model base's, shared with SkeletonPoseNDF.complete; num_joints defaults to 21
 
     @torch.no_grad()
     def complete(self, poses, observed, steps=100, return_dist=True, *, step_size=1.0, renormalize=None, tol=0.0):

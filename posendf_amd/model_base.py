@@ -40,6 +40,27 @@ def cached(cache, key, make):
     return value
 
 
+def pack_observed(observed, B, device, num_joints=21):
+    """bool [J] or [B,J] (True = the joint is observed and held) -> one word per pose, bit j = joint j, as an int32 tensor [B] on
+    `device`: the bits of the uint32 of include/posendf_amd_completion.h and of pndf_project_options2.  J = `num_joints` is 1 .. 32; with
+    32 joints joint 31 is the sign bit of the int32 (torch has no arithmetic on uint32): the word is put together in int64 and
+    brought into the int32 range before the cast, so the 32 bits are exact."""
+    obs = torch.as_tensor(observed, device=device)
+    if obs.dtype != torch.bool:
+        raise PndfError(f"observed must be a bool tensor, not {obs.dtype}")
+    J = int(num_joints)
+    if not 1 <= J <= 32:
+        raise PndfError(f"a mask of {J} joints: one word holds 1 .. 32")
+    if obs.shape == (J,):
+        obs = obs.expand(B, J)
+    if obs.shape != (B, J):
+        raise PndfError(f"observed must have shape [{J}] or [{B}, {J}], not {list(obs.shape)}")
+    bits = torch.ones(J, dtype=torch.int64, device=device) << torch.arange(J, device=device)
+    word = (obs.to(torch.int64) * bits).sum(dim=1)
+    word = torch.where(word >= 2 ** 31, word - 2 ** 32, word)
+    return word.to(torch.int32).contiguous()
+
+
 class _Distance(torch.autograd.Function):
     """dist_pred = f(pose) with first-order autograd: backward(g) = g * d dist / d pose.
     Both come from ONE engine call; double backward is not provided (train=True path has it)."""

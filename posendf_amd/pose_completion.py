@@ -1,13 +1,15 @@
-"""Pose completion -- the application of the paper that follows pose generation: some of a pose's 21 joint rotations are observed,
-the others are occluded or missing, and plausible values for them are found by descending the distance field while the observed
-joints stay put.  Modelled on `SamplePose` (posendf_amd/sample_poses.py): the loop is `PoseNDF.complete` (per step one forward +
-gradient launch and one masked update kernel, include/posendf_amd_completion.h), and with a body model the poses before / after are
-turned into meshes for inspection.
+"""Pose completion -- the application of the paper that follows pose generation: some of a pose's joint rotations are observed, the
+others are occluded or missing, and plausible values for them are found by descending the distance field while the observed joints
+stay put.  Modelled on `SamplePose` (posendf_amd/sample_poses.py): the loop is the model's `complete` -- `PoseNDF.complete` for the 21
+SMPL joints (per step one forward + gradient launch and one masked update kernel, include/posendf_amd_completion.h),
+`SkeletonPoseNDF.complete` for any other joint tree of 1 .. 32 joints, a hand or a rig (the mask inside the projection step,
+pndf_project_options2 of include/posendf_amd.h) -- and with a body model the poses before / after are turned into meshes for
+inspection.  The body model is SMPL's: a model of another joint count completes poses without one.
 
 The distance field has many local minima around a partial observation, so the usual recipe is several hypotheses per pose: the
 unobserved joints are filled with random unit quaternions (the convention of `random_poses`), every hypothesis is completed, and
 the one that ends nearest to the manifold is kept.  The fill and the selection happen once per call and are torch ops; all
-B * K poses go through ONE `PoseNDF.complete` call.
+B * K poses go through ONE `complete` call of the model.
 """
 from __future__ import annotations
 
@@ -34,12 +36,13 @@ class PoseCompletion(SamplePose):
     @torch.no_grad()
     def complete(self, poses, observed, hypotheses=1, fill="random", select="all", generator=None, steps=100, *, step_size=1.0,
                  renormalize=None, tol=0.0):
-        """poses [B,21,4]; observed: bool [21] or [B,21], True = the joint is known (None: no joint is).  `hypotheses` = K starts
-        per pose.  fill="random": the unobserved joints of every hypothesis are normalize(torch.rand(B,K,21,4), dim=-1), drawn on
-        the host from `generator` -- whatever the input holds there (NaN included) is ignored; fill="given": every hypothesis
-        starts from the input as it is.  `steps` and the step options are PoseNDF.complete's.
+        """poses [B,J,4] with J = the model's num_joints (21 for PoseNDF); observed: bool [J] or [B,J], True = the joint is known
+        (None: no joint is).  `hypotheses` = K starts per pose.  fill="random": the unobserved joints of every hypothesis are
+        normalize(torch.rand(B,K,J,4), dim=-1), drawn on the host from `generator` -- whatever the input holds there (NaN
+        included) is ignored; fill="given": every hypothesis starts from the input as it is.  `steps` and the step options are
+        those of the model's `complete`.
 
-        Returns (poses [B,K,21,4], dist [B,K] of the last iteration, meshes); with select="best" (poses, dist, best [B], meshes),
+        Returns (poses [B,K,J,4], dist [B,K] of the last iteration, meshes); with select="best" (poses, dist, best [B], meshes),
         where best[b] is the hypothesis with the smallest distance (`best_hypothesis`).  With a body model, meshes holds
         'pose_init' / 'vertices_init' and 'pose' / 'vertices' / 'joints' of the B * K poses before and after (of the B best ones
         with select="best"); without one it is empty."""
@@ -51,6 +54,8 @@ class PoseCompletion(SamplePose):
         if K < 1:
             raise ValueError(f"hypotheses must be at least 1, not {hypotheses}")
         J = self.pose_prior.num_joints
+        if self.body_model is not None and J != 21:
+            raise ValueError(f"the body model takes SMPL's 21 joints; a model of {J} joints completes poses without one (body_model=None)")
         q = poses.to(self.device).reshape(-1, J, 4).float()
         B = q.shape[0]
         obs = torch.zeros(B, J, dtype=torch.bool, device=q.device) if observed is None else torch.as_tensor(observed, device=q.device)

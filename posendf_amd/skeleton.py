@@ -9,8 +9,12 @@ layer-by-layer HIP unit for a cuda model, the first-order host twins for `train.
 
 `forward(train=True)` runs the stock PyTorch modules unless `opt['engine']['train'] = 'hip'`: then a cuda model's training objective
 and every weight gradient come from csrc/pndf_train.hip on a plan of include/posendf_amd_skeleton_train.h for this class's parent
-table, with no fallback, and `posendf_amd.trainer.Trainer` trains the skeleton end to end.  The second order,
-completion, interpolation, the k-NN index and the online sampler stay 21-joint.
+table, with no fallback, and `posendf_amd.trainer.Trainer` trains the skeleton end to end.
+
+`complete(poses, observed)` is pose completion for the model's tree: `project` with the observed joints held, the joint mask inside
+the projection step of the unit's last kernel (or of the host twin), handed over in a pndf_project_options2 (include/posendf_amd.h);
+`posendf_amd.pose_completion.PoseCompletion` drives it with several hypotheses per pose.  The second order and interpolation stay
+21-joint.
 """
 from __future__ import annotations
 
@@ -20,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from .engine import PndfError, SkeletonEngine, StreamWorkspaces, stream_handle
-from .model_base import PoseModel, _Distance
+from .model_base import PoseModel, _Distance, pack_observed
 from .synth import BONE_DIM, FEAT, PARENT
 
 # named parent tables: get_parent_mapping('smpl') of the reference, and a 15-joint hand -- five fingers of three joints each, every
@@ -91,3 +95,23 @@ class SkeletonPoseNDF(PoseModel):
         if not train:
             return {"dist_pred": _Distance.apply(pose, self)}
         return self._forward_train(pose, dist_gt, man_poses, eikonal)
+
+    @torch.no_grad()
+    def complete(self, poses, observed, steps=100, return_dist=True, *, step_size=1.0, renormalize=None, tol=0.0):
+        """Pose completion with the contract of `PoseNDF.complete`: `project` with the observed joints held.  `observed` is a bool
+        tensor [J] (one mask for every pose) or [B,J], True = the joint's rotation is known and stays as it is, bit for bit (it still
+        enters the distance and the gradient of the others); None = no joint is held, which is `project` bit for bit.  The mask rides
+        in the projection call itself (pndf_project_options2, include/posendf_amd.h): the unit's last kernel of every step selects
+        per joint, so a masked step costs no launch more than an unmasked one; a `train.device: cpu` model runs the host twin.
+        Returns and step options: as `project`."""
+        q = poses.to(device=self.device).reshape(-1, self.num_joints, 4).float().contiguous()
+        B = q.shape[0]
+        out = torch.empty_like(q)
+        d = torch.empty(B, device=q.device, dtype=torch.float32)
+        mask = None if observed is None else pack_observed(observed, B, q.device, self.num_joints)
+        eng = self._engine_for(q.device)
+        host = q.device.type == "cpu"
+        if B or host:       # as `project`
+            eng.project(q.data_ptr(), out.data_ptr(), d.data_ptr(), B, int(steps), *(() if host else self._engine_args(eng, q.device, B)),
+                        step_size=step_size, renorm=renormalize, tol=tol, observed_ptr=None if mask is None or B == 0 else mask.data_ptr())
+        return (out, d.view(-1, 1)) if return_dist else out
