@@ -196,7 +196,8 @@ int pndf_pack_host_split(const float* const* tensors, const int64_t* numel, int 
  * Stateless helpers (no handle; status codes as above, no error text).  One Adam step =
  *   pndf_forward_grad(h, q, NULL, d, dq, S*T, stream);  pndf_denoise_update(...)   -- q for the first step from
  * pndf_aa2quat.  Terms: pose prior 1e7 c_s^2 / (1+it), c_s = mean_t d (:81-83,33) and the pose-space surrogates of the
- * SMPL temporal / data terms (:31-32,88-94; the body model itself is out of scope).  Adam(lr, 0.9, 0.999, 1e-8) (:70). */
+ * SMPL temporal / data terms (:31-32,88-94; the body model itself is out of scope).  Adam(lr, 0.9, 0.999, 1e-8) (:70): the
+ * arithmetic of pndf_adam_step with weight decay 0 -- `float lr` is widened and the step's scalars are formed in double. */
 /* theta [N,69] axis-angle (SMPL body pose) -> q [N,21,4] real-part-first quaternions of the first 21 joints
  * (pytorch3d.transforms.axis_angle_to_quaternion, :81). */
 int pndf_aa2quat(const float* theta, float* q, int64_t N, void* stream);

@@ -13,6 +13,9 @@ documented convention) and the SMPL vertex / joint terms, which ar
   temp    : 10 (1 + it) mean_{t, j} ||th_{t, j} - th_{t+1, j}||    (:88-89 on the surrogate "vertices")
   data    : 100 / (1 + it) mean_{t, j} ||th_{t, j} - th0_{t, j}||  (:92-94, only for it > 0)
   Adam(lr = 0.02, betas = (0.9, 0.999), eps = 1e-8), torch.optim.Adam semantics  (:70, :98-99)
+
+update_step is ONE launch of the update kernel with the network's outputs given (tests/test_denoise_update_gpu.py); it is tied to
+optimize, step for step, in tests/test_denoise_oracle.py.
 """
 from __future__ import annotations
 
@@ -84,6 +87,44 @@ def step_gradient(theta, theta0, sd, it, act="lrelu", beta=100.0, dtype=np.float
         terms["data"] = w_data * nrm.mean(dtype=dtype)
         g[:, :NJ] += w_data / dtype(T * NJ) * diff / nrm
     return g.reshape(T, 69), terms
+
+
+def update_step(theta, theta0, d, dq, m, v, weights, k, lr, g_body=None, dtype=np.float64):
+    """The arithmetic of ONE launch of pndf_denoise_update_kernel, with the distances d [S,T] and their gradient dq [S,T,21,4]
+    GIVEN instead of computed by a network: theta, theta0, m, v [S,T,69]; weights = (prior_coef, prior_power, temp_coef,
+    data_coef) already evaluated for the outer iteration (data_coef 0 = no data term); k = the Adam step (1 = zero moments
+    expected); g_body [S,T,69] = the weighted gradient of the body-model terms over all 23 joints, which replaces the pose-space
+    surrogates.  Returns (g, theta_out, m_out, v_out, q_next [S,T,21,4]); without g_body the hand joints (63:69) have g = 0
+    and take the Adam update of their moments all the same.  The formulas are step_gradient's and optimize's."""
+    theta = np.asarray(theta, dtype)
+    S, T = theta.shape[:2]
+    a = theta.reshape(S, T, 23, 3)[:, :, :NJ]
+    pc, pp, w_temp, w_data = dtype(weights[0]), int(weights[1]), dtype(weights[2]), dtype(weights[3])
+    c = np.asarray(d, dtype).reshape(S, T).mean(axis=1, dtype=dtype)
+    wp = (dtype(2) * pc * c if pp == 2 else pc * np.ones_like(c)) / dtype(T)
+    g = np.zeros((S, T, 23, 3), dtype)
+    g[:, :, :NJ] = aa2quat_vjp(a, np.asarray(dq, dtype).reshape(S, T, NJ, 4) * wp[:, None, None, None])
+    if g_body is not None:
+        g = g + np.asarray(g_body, dtype).reshape(S, T, 23, 3)
+    else:
+        if T > 1:
+            diff = a[:, :-1] - a[:, 1:]
+            nrm = np.sqrt((diff * diff).sum(-1, keepdims=True) + dtype(SURROGATE_EPS))
+            w = w_temp / dtype((T - 1) * NJ)
+            g[:, :-1, :NJ] += w * diff / nrm
+            g[:, 1:, :NJ] -= w * diff / nrm
+        if w_data != 0:
+            diff = a - np.asarray(theta0, dtype).reshape(S, T, 23, 3)[:, :, :NJ]
+            nrm = np.sqrt((diff * diff).sum(-1, keepdims=True) + dtype(SURROGATE_EPS))
+            g[:, :, :NJ] += w_data / dtype(T * NJ) * diff / nrm
+    g = g.reshape(S, T, 69)
+    b1, b2, eps = dtype(0.9), dtype(0.999), dtype(1e-8)
+    m = b1 * np.asarray(m, dtype) + (1 - b1) * g
+    v = b2 * np.asarray(v, dtype) + (1 - b2) * g * g
+    bc1, bc2 = 1 - b1 ** k, 1 - b2 ** k
+    out = theta - (dtype(lr) / bc1) * m / (np.sqrt(v) / np.sqrt(bc2) + eps)        # torch.optim.Adam (no amsgrad)
+    q_next = axis_angle_to_quaternion(out.reshape(S, T, 23, 3)[:, :, :NJ])[0]
+    return g, out, m, v, q_next
 
 
 def optimize(theta0, sd, iterations=10, steps_per_iter=50, lr=0.02, act="lrelu", beta=100.0, dtype=np.float64,

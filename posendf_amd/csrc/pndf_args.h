@@ -3,6 +3,7 @@
 // another translation unit: both sides include this header, and the static_asserts pin the layout the kernels were
 // written against (a silent mismatch between two copies would corrupt every launch).
 #pragma once
+#include "pndf_adam.h"
 #include "pndf_experiment.h"
 #include <stddef.h>
 #include <stdint.h>
@@ -94,16 +95,15 @@ struct PndfDenoiseArgs {
     float* q_next;         // [S*T,84] quaternions of the UPDATED theta
     const float* g_extra;  // null, or [S,T,69]: gradient of the body-model terms (pndf_lbs_terms_grad), already weighted;
                            //   when given, the pose-space surrogate terms are NOT added
-    int S, T, adam_step, prior_power;
-    float lr, beta1, beta2, eps;
+    int S, T, prior_power, reserved0;
+    AdamScalars adam;      // this step's Adam scalars, formed in double on the host (pndf_adam.h); weight decay 0
     // loss weights of this outer iteration, already evaluated (include/posendf_amd.h pndf_denoise_weights):
     //   pose prior  prior_coef c^prior_power  (c = mean_t d),   temporal  temp_coef mean ||..||,   data  data_coef mean ||..||
     float prior_coef, temp_coef, data_coef;
-    int reserved0;
 };
-static_assert(sizeof(PndfDenoiseArgs) == 120 && offsetof(PndfDenoiseArgs, g_extra) == 64 &&
-              offsetof(PndfDenoiseArgs, S) == 72 && offsetof(PndfDenoiseArgs, lr) == 88 &&
-              offsetof(PndfDenoiseArgs, prior_coef) == 104, "PndfDenoiseArgs layout");
+static_assert(sizeof(PndfDenoiseArgs) == 128 && offsetof(PndfDenoiseArgs, g_extra) == 64 &&
+              offsetof(PndfDenoiseArgs, S) == 72 && offsetof(PndfDenoiseArgs, adam) == 88 &&
+              offsetof(PndfDenoiseArgs, prior_coef) == 116, "PndfDenoiseArgs layout");
 
 struct PndfQuatDistArgs {
     const float* noise;    // [B,21,4]

@@ -119,23 +119,18 @@ extern "C" __global__ void __launch_bounds__(WG) pndf_denoise_update_kernel(Pndf
             gx += r * dx; gy += r * dy; gz += r * dz;
         }
     }
-    // ---- Adam (torch.optim.Adam defaults: no amsgrad, no weight decay).  The two hand joints have a zero gradient
-    // without a body model: m = v = 0 and the step is exactly 0, as in torch.
-    const float bc1 = 1.0f - powf(a.beta1, (float)a.adam_step);
-    const float bc2 = 1.0f - powf(a.beta2, (float)a.adam_step);
-    const float step = a.lr / bc1, rs = 1.0f / sqrtf(bc2);
+    // ---- Adam (torch.optim.Adam defaults: no amsgrad, no weight decay), the library's one Adam (pndf_adam.h).  The two hand
+    // joints have a zero gradient without a body model: m = v = 0 and the step is exactly 0, as in torch.
     float* mm = a.m + n * TH + 3 * j;
     float* vv = a.v + n * TH + 3 * j;
     const float g[3] = {gx, gy, gz};
-    float nw[3];
-    const float cur[3] = {x, y, z};
+    float nw[3] = {x, y, z};
 #pragma unroll
     for (int e = 0; e < 3; ++e) {
-        const float m1 = a.beta1 * mm[e] + (1.0f - a.beta1) * g[e];
-        const float v1 = a.beta2 * vv[e] + (1.0f - a.beta2) * g[e] * g[e];
+        float m1 = mm[e], v1 = vv[e];
+        adam_one(nw[e], g[e], m1, v1, a.adam);
         mm[e] = m1;
         vv[e] = v1;
-        nw[e] = cur[e] - step * m1 / (sqrtf(v1) * rs + a.eps);
     }
     if (j < NJ) {
         float k2, ang2, q2[4];
@@ -171,9 +166,10 @@ static int denoise_update(const float* theta_in, float* theta_out, const float* 
     if (!guard.ok) return PNDF_ERR_HIP;
     PndfDenoiseArgs a;
     a.theta_in = theta_in; a.theta_out = theta_out; a.theta0 = theta0; a.d = d; a.dq = dq; a.m = m; a.v = v;
-    a.q_next = q_next; a.g_extra = g_extra; a.S = S; a.T = T; a.adam_step = adam_step; a.prior_power = w.prior_power;
-    a.prior_coef = w.prior_coef; a.temp_coef = w.temp_coef; a.data_coef = w.data_coef; a.reserved0 = 0;
-    a.lr = lr; a.beta1 = 0.9f; a.beta2 = 0.999f; a.eps = 1e-8f;       // motion_denoise.py:70, torch.optim.Adam defaults
+    a.q_next = q_next; a.g_extra = g_extra; a.S = S; a.T = T; a.prior_power = w.prior_power; a.reserved0 = 0;
+    a.prior_coef = w.prior_coef; a.temp_coef = w.temp_coef; a.data_coef = w.data_coef;
+    // motion_denoise.py:70, torch.optim.Adam defaults; the fp32 lr of the C ABI is widened before the division by 1 - beta1^step
+    a.adam = pndf_adam_scalars(adam_step, (double)lr, 0.9, 0.999, 1e-8, 0.0);
     const dim3 grid((unsigned)((T + FRAMES_PER_WG - 1) / FRAMES_PER_WG), (unsigned)S);
     hipLaunchKernelGGL(pndf_denoise_update_kernel, grid, dim3(WG), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? PNDF_OK : PNDF_ERR_HIP;

@@ -6,7 +6,7 @@
 //                             The joint count is an argument (pndf_skel_train_batch; pndf_train_batch is 21 joints).
 //                             One thread per joint quaternion (one 16-byte load, one 16-byte store); the thread of joint 0 of a
 //                             noisy pose also reduces the pose's k labels, in index order.
-//   pndf_adam_step_kernel     torch.optim.Adam (coupled L2 weight decay, no amsgrad) over ONE flat buffer that holds every
+//   pndf_adam_step_kernel     torch.optim.Adam (pndf_adam.h; coupled L2 weight decay, no amsgrad) over ONE flat buffer that holds every
 //                             parameter: four 16-byte streams in, three out, no tensor table (the pads between tensors are
 //                             zero and stay zero).  Element-wise: the result does not depend on the launch shape.
 // Plain vector loads and stores, no atomics, no communication between threads: the same inputs give the same bits.
@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "../../include/posendf_amd_skeleton_train.h"
+#include "pndf_adam.h"
 #include "pndf_experiment.h"
 #include "pndf_host.h"
 
@@ -26,19 +27,6 @@ namespace {
 constexpr int SMPL_JOINTS = 21;        // pndf_train_batch: joints = 16-byte quaternions per pose
 constexpr int MAX_JOINTS = 32;         // pndf_config.parent[32]
 constexpr int MAX_BLOCKS = 2048;       // 256 CUs x 8 blocks of 256 threads; the rest of the buffer by grid stride
-
-struct AdamScalars {
-    float one_minus_beta1, beta2, one_minus_beta2, step_size, bc2_sqrt, eps, weight_decay;
-};
-
-// one element of torch's _single_tensor_adam, in its order of operations
-__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, const AdamScalars& s) {
-    g = g + s.weight_decay * p;                        // grad.add(param, alpha=weight_decay)
-    m = m + s.one_minus_beta1 * (g - m);               // exp_avg.lerp_(grad, 1 - beta1)
-    v = v * s.beta2 + s.one_minus_beta2 * (g * g);     // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
-    const float denom = sqrtf(v) / s.bc2_sqrt + s.eps; // (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
-    p = p - s.step_size * (m / denom);                 // param.addcdiv_(exp_avg, denom, value=-step_size)
-}
 
 }  // namespace
 
@@ -136,17 +124,7 @@ extern "C" int pndf_adam_step(float* p, const float* g, float* m, float* v, int6
     if ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) return PNDF_ERR_BAD_ARG;
     DeviceGuard guard(pndf_pointer_device(p));
     if (!guard.ok) return PNDF_ERR_HIP;
-    // the scalars as torch forms them: Python floats (double), each rounded once to fp32 where it meets the tensors
-    const double bc1 = 1.0 - std::pow(beta1, (double)step);
-    const double bc2 = 1.0 - std::pow(beta2, (double)step);
-    AdamScalars s;
-    s.one_minus_beta1 = (float)(1.0 - beta1);
-    s.beta2 = (float)beta2;
-    s.one_minus_beta2 = (float)(1.0 - beta2);
-    s.step_size = (float)(lr / bc1);
-    s.bc2_sqrt = (float)std::sqrt(bc2);
-    s.eps = (float)eps;
-    s.weight_decay = (float)weight_decay;
+    const AdamScalars s = pndf_adam_scalars(step, lr, beta1, beta2, eps, weight_decay);      // as torch forms them (pndf_adam.h)
     const long long n4 = (long long)(n >> 2);
     long long blocks = (n4 + 255) / 256;
     if (blocks < 1) blocks = 1;

@@ -1,5 +1,8 @@
 """Motion-denoise driver: CPU checks of the host logic, GPU parity of the optimisation loop
-against the same loop around the PyTorch-CPU oracle network."""
+against the same loop around the PyTorch-CPU oracle network.  These are LOOP tests: they see the update kernel through Adam, which
+hides the gradient's scale, and compare final poses only.  The kernel-level checks -- one launch of pndf_denoise_update_kernel on
+buffers of the test's own making: gradient, moments, update and next quaternions against oracle/denoise_np.update_step and
+torch.optim.Adam, the three C entry points, the kernel's edges -- are in tests/test_denoise_update_gpu.py."""
 import numpy as np
 import pytest
 import torch

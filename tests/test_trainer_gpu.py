@@ -68,19 +68,6 @@ def _adam_inputs(n, step, pad=None, seed=0):
     return out
 
 
-def _torch_adam(p, g, m, v, step, dtype, lr, wd):
-    P = torch.from_numpy(p).to(DEV, dtype).requires_grad_(True)
-    opt = torch.optim.Adam([P], lr=lr, weight_decay=wd)
-    if step > 1:                                                           # the state a loop would hold before this step
-        opt.state[P] = {"step": torch.tensor(float(step - 1)), "exp_avg": torch.from_numpy(m).to(DEV, dtype),
-                        "exp_avg_sq": torch.from_numpy(v).to(DEV, dtype)}
-    P.grad = torch.from_numpy(g).to(DEV, dtype)
-    opt.step()
-    st = opt.state[P]
-    assert float(st["step"]) == step
-    return [x.detach().double().cpu().numpy() for x in (P, st["exp_avg"], st["exp_avg_sq"])]
-
-
 @pytest.mark.parametrize("step", [1, 2, 1000])
 @pytest.mark.parametrize("size", [1000, 1003, "model"])
 def test_adam_step_against_torch(lib, size, step):
@@ -88,8 +75,8 @@ def test_adam_step_against_torch(lib, size, step):
     lr, wd = 1e-5, 1e-4                                                    # train_posendf.py:30
     n, pad = _model_layout() if size == "model" else (size, None)
     p, g, m, v = _adam_inputs(n, step, pad)
-    t32 = _torch_adam(p, g, m, v, step, torch.float32, lr, wd)
-    t64 = _torch_adam(p, g, m, v, step, torch.float64, lr, wd)
+    t32 = trf.torch_adam(p, g, m, v, step, torch.float32, lr, wd, DEV)
+    t64 = trf.torch_adam(p, g, m, v, step, torch.float64, lr, wd, DEV)
     guard = 8                                                              # floats behind the buffer that no call may touch
     runs = []
     for _ in range(2):

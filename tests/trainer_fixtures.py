@@ -90,6 +90,23 @@ def state_digest(key, x, hidden, full=True):
     return d
 
 
+def torch_adam(p, g, m, v, step, dtype, lr, wd, device):
+    """ONE step of torch.optim.Adam on `device` in `dtype` from the numpy buffers p, g, m, v (m, v: the state a loop would hold
+    before step `step`; ignored at step 1): [p, exp_avg, exp_avg_sq] as fp64 numpy arrays.  The yardstick of both optimiser
+    kernels (tests/test_trainer_gpu.py, tests/test_denoise_update_gpu.py)."""
+    import torch
+    P = torch.from_numpy(p).to(device, dtype).requires_grad_(True)
+    opt = torch.optim.Adam([P], lr=lr, weight_decay=wd)
+    if step > 1:
+        opt.state[P] = {"step": torch.tensor(float(step - 1)), "exp_avg": torch.from_numpy(m).to(device, dtype),
+                        "exp_avg_sq": torch.from_numpy(v).to(device, dtype)}
+    P.grad = torch.from_numpy(g).to(device, dtype)
+    opt.step()
+    st = opt.state[P]
+    assert float(st["step"]) == step
+    return [x.detach().double().cpu().numpy() for x in (P, st["exp_avg"], st["exp_avg_sq"])]
+
+
 def adam_state(trainer):
     """{state-dict key: (exp_avg, exp_avg_sq)} as numpy arrays, from optimizer_state_dict()"""
     st = trainer.optimizer_state_dict()["state"]
