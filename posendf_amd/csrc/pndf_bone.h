@@ -200,11 +200,4 @@ inline PtrTableOf<NT> ptr_table(const LayerNet& n, const float* const* tensors) 
     return t;
 }
 
-// the first of the network's 4 J + 2L tensors that is null in `a` (or in `b`, when given); -1: none
-inline int null_tensor(const LayerNet& n, const float* const* a, const float* const* b = nullptr) {
-    for (int i = 0; i < 4 * n.nj + 2 * n.L; ++i)
-        if (!a[i] || (b && !b[i])) return i;
-    return -1;
-}
-
 }  // namespace

@@ -14,6 +14,7 @@
 #include "pndf_layout.h"
 #include "pndf_args.h"
 #include "pndf_host.h"
+#include "pndf_net_plan.h"
 #include "pndf_pack.h"
 #include "pndf_generic.h"
 #include "pndf_project_opts.h"
@@ -34,9 +35,22 @@ extern "C" long long pndf_kernel_softplus_scratch_floats_per_wg();
 extern "C" int pndf_kernel_lds_bytes();
 
 
+// The limits and the SMPL table are written down where each reader needs them -- pndf_layout.h for the fused kernels, pndf_args.h for the
+// runtime-planned kernels' arguments, pndf_net_plan.h for what the library accepts; this translation unit sees all three.
+static_assert(MAXLIN == PNDF_NET_MAX_LIN && PNDF_GEN_MAXLIN == PNDF_NET_MAX_LIN && MAX_WIDTH == PNDF_NET_MAX_WIDTH, "one depth and one width limit");
+static_assert(NJ == PNDF_SMPL_JOINTS && FEAT == PNDF_SKEL_FEAT && HID == PNDF_SKEL_HID && NQ == PNDF_SKEL_BONE * NJ && NFEAT == DIMS[0] &&
+                  DIMS[0] == PNDF_SKEL_FEAT * NJ && NOENC_IN == PNDF_SKEL_BONE * NJ && NJ <= PNDF_SKEL_MAX_JOINTS,
+              "one bone: 4 | 10 -> 10 -> 6, 21 of them");
+constexpr bool smpl_tables_agree() {
+    for (int j = 0; j < NJ; ++j)
+        if (PARENT[j] != PNDF_SMPL_PARENT[j]) return false;
+    return true;
+}
+static_assert(smpl_tables_agree(), "pndf_layout.h's PARENT is pndf_skeleton_is_smpl's table");
+
 struct pndf_engine {
-    pndf_config cfg;
-    int device = 0;
+    LayerNet net;               // the network and the device (pndf_net_plan.h): SMPL's 21 joints, dims[0] 126 | 84
+    int precision = PNDF_PREC_FP32;
     bool have_weights = false;
     // f16x3 only: every lo tile of the packed trunk is zero (weights exactly representable in fp16 at their layer scale),
     // so the lo hi term vanishes identically and the two-term kernels give bit-identical results with 2/3 of the MFMAs
@@ -54,7 +68,7 @@ struct pndf_engine {
     std::string err;
 };
 
-constexpr int STREAM_PAD_SLOTS = 5;           // >= RING_SLOTS - 1 of pndf_device.h (the ring's prefetch distance; 5 covers the six-buffer experiment arm)
+using pndf_pack::STREAM_PAD_SLOTS;
 
 // The fused kernels, and the one a handle launches: by precision, activation family and (f16x3) whether every lo tile is zero
 typedef void (*fused_kernel_t)(PndfKernelArgs);
@@ -114,29 +128,15 @@ extern "C" void pndf_default_config(pndf_config* cfg, int32_t act, float beta) {
 
 static int check_config(pndf_engine* h, const pndf_config* cfg) {
     if (!cfg) return pndf_fail(h, PNDF_ERR_BAD_ARG, "cfg is null");
-    if (cfg->num_joints != NJ)
-        return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "num_joints: the persistent engine runs the 21-joint table of get_parent_mapping('smpl') only; pndf_skel_create (posendf_amd_skeleton.h) takes any joint tree");
-    // The fused kernels are laid out for configs/amass.yaml (126 | 84, 256, 512, 1024, 512, 256, 64, 1).  A DFNet of the same
-    // depth whose hidden layers are NARROWER runs on them zero-padded (padded units have zero outgoing weights, so they
-    // reach neither the distance nor its gradient, whatever the activation); any other `dims` list the reference can build
-    // (net_modules.py:14-28) -- 2 .. 8 linear layers, hidden widths up to 1024 -- runs on the runtime-planned kernels of
-    // pndf_generic.hip (the exact fp32 form for precision fp32; the split-precision form, fp16 MFMAs with fp32 accumulation, for
-    // any other precision, unless a layer's weights cannot be scaled into fp16's range).  Only beyond that is a configuration refused.
-    if (cfg->n_dims < 3 || cfg->n_dims > MAXLIN + 1)
-        return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "DFNet depth: n_dims must be 3 .. 9 (1 .. 7 hidden layers + the output layer)");
-    if ((cfg->dims[0] != DIMS[0] && cfg->dims[0] != NOENC_IN) || cfg->dims[cfg->n_dims - 1] != 1)
-        return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "DFNet in_dim must be 126 (StrEnc.use=True) or 84 (False), its output 1");
-    for (int i = 1; i < cfg->n_dims - 1; ++i)
-        if (cfg->dims[i] < 1 || cfg->dims[i] > MAX_WIDTH)
-            return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "DFNet hidden widths must be 1 .. 1024");
-    for (int i = 0; i < NJ; ++i)
-        if (cfg->parent[i] != PARENT[i]) return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "parent: the persistent engine runs the table of get_parent_mapping('smpl') only; pndf_skel_create (posendf_amd_skeleton.h) takes any joint tree");
-    if (cfg->act != PNDF_ACT_RELU && cfg->act != PNDF_ACT_LRELU && cfg->act != PNDF_ACT_SOFTPLUS)
-        return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "unknown activation (relu, lrelu and softplus are implemented)");
+    // What the library accepts of a DFNet and its activations is pndf_net_plan.h's; the engine's own rules are the SMPL table, an input
+    // of 126 | 84, the precisions and the Softplus betas.  Which kernels run an accepted network is pndf_generic_needed's decision.
+    if (!pndf_skeleton_is_smpl(cfg))
+        return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "num_joints / parent: the persistent engine runs the 21-joint table of get_parent_mapping('smpl') only; pndf_skel_create (posendf_amd_skeleton.h) takes any joint tree");
+    if (const char* why = pndf_dfnet_refusal(cfg)) return pndf_fail(h, PNDF_ERR_UNSUPPORTED, why);
+    if (cfg->dims[0] != DIMS[0] && cfg->dims[0] != NOENC_IN)
+        return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "DFNet in_dim (dims[0]) must be 126 (StrEnc.use=True) or 84 (False)");
     if (cfg->act == PNDF_ACT_SOFTPLUS && !(cfg->beta > 0.f))
         return pndf_fail(h, PNDF_ERR_BAD_ARG, "softplus beta must be positive");
-    if (cfg->enc_act != -1 && cfg->enc_act != PNDF_ACT_RELU && cfg->enc_act != PNDF_ACT_LRELU && cfg->enc_act != PNDF_ACT_SOFTPLUS)
-        return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "unknown encoder activation (relu, lrelu and softplus are implemented; -1 = the trunk's)");
     if (cfg->enc_act == PNDF_ACT_SOFTPLUS && !(cfg->enc_beta > 0.f) && !(cfg->beta > 0.f))
         return pndf_fail(h, PNDF_ERR_BAD_ARG, "softplus beta of the encoder must be positive");
     if (cfg->precision != PNDF_PREC_FP32 && cfg->precision != PNDF_PREC_F16X3 && cfg->precision != PNDF_PREC_F16 &&
@@ -158,8 +158,8 @@ extern "C" int pndf_create(pndf_handle* out, const pndf_config* cfg, int device)
     DeviceGuard guard(device);
     if (!guard.ok) return pndf_fail<pndf_engine>(nullptr, PNDF_ERR_HIP, "hipSetDevice failed");
     pndf_engine* h = new pndf_engine();
-    h->cfg = *cfg;
-    h->device = device;
+    layer_net_init(h->net, cfg, device);
+    h->precision = cfg->precision;
     if (prop.multiProcessorCount <= 0) {
         delete h;
         return pndf_fail<pndf_engine>(nullptr, PNDF_ERR_HIP, "the device reports no compute units (multiProcessorCount <= 0)");
@@ -172,7 +172,7 @@ extern "C" int pndf_create(pndf_handle* out, const pndf_config* cfg, int device)
                                                        "(the runtime-planned kernels run fp32 or split-precision fp16)");
         }
         std::string why;
-        rc = pndf_generic_create(&h->generic, *cfg, h->resident_wgs, why);
+        rc = pndf_generic_create(&h->generic, h->net, h->precision, h->resident_wgs, why);
         if (rc != PNDF_OK) {
             delete h;
             return pndf_fail<pndf_engine>(nullptr, rc, why);
@@ -183,12 +183,7 @@ extern "C" int pndf_create(pndf_handle* out, const pndf_config* cfg, int device)
     hipError_t e = hipMalloc((void**)&h->d_stream, (size_t)(STEP_TILES + STREAM_PAD_SLOTS * SLOT_TILES) * TILE_BYTES);
     if (e == hipSuccess) e = hipMalloc((void**)&h->d_bias, BIAS_FLOATS * sizeof(float));
     if (e == hipSuccess && cfg->act == PNDF_ACT_SOFTPLUS) {
-        const size_t sbytes = (size_t)h->resident_wgs * pndf_kernel_softplus_scratch_floats_per_wg() * sizeof(float);
-        // PNDF_SP_SCRATCH=uncached|finegrained: memory-type experiments on the derivative scratch (profiles/r04/sp_forward_diag.txt)
-        const char* mt = getenv("PNDF_SP_SCRATCH");
-        if (mt && mt[0] == 'u') e = hipExtMallocWithFlags((void**)&h->d_scratch, sbytes, hipDeviceMallocUncached);
-        else if (mt && mt[0] == 'f') e = hipExtMallocWithFlags((void**)&h->d_scratch, sbytes, hipDeviceMallocFinegrained);
-        else e = hipMalloc((void**)&h->d_scratch, sbytes);
+        e = hipMalloc((void**)&h->d_scratch, (size_t)h->resident_wgs * pndf_kernel_softplus_scratch_floats_per_wg() * sizeof(float));
         if (e == hipSuccess) e = h->sp_order.create();
     }
     for (const FusedKernel& k : FUSED_KERNELS)
@@ -204,7 +199,7 @@ extern "C" int pndf_create(pndf_handle* out, const pndf_config* cfg, int device)
 
 extern "C" int pndf_destroy(pndf_handle h) {
     if (!h) return PNDF_OK;
-    DeviceGuard guard(h->device);
+    DeviceGuard guard(h->net.device);
     pndf_generic_destroy(h->generic);
     h->sp_order.destroy();
     if (h->d_stream) (void)hipFree(h->d_stream);
@@ -224,50 +219,30 @@ extern "C" void pndf_packed_sizes(int64_t* stream_floats, int64_t* bias_floats) 
     if (bias_floats) *bias_floats = BIAS_FLOATS;
 }
 
-// in_dim of the trunk: 126 with the structure encoder, 84 = 21 x 4 without it (model.StrEnc.use = False, reference
-// model/posendf.py:40-42,73-74: DFNet sees the normalised quaternions, `p.reshape(len(p), -1)` net_modules.py:49)
-static bool table_has_encoder(int n) { return n == 4 * NJ + 2 * NLIN; }
-
-// widths of the DFNet in a state-dict table: dims[0] = in_dim (126 | 84), dims[l + 1] = rows of dfnet.lin{l}
-struct NetDims {
-    int d[NLIN + 1];
-    int in(int l) const { return d[l]; }
-    int out(int l) const { return d[l + 1]; }
-};
-
-static const char* check_tensors(const float* const* tensors, const int64_t* numel, int n, NetDims* dims_out = nullptr) {
-    if (!tensors || !numel) return "tensors / numel is null";
-    if (n != 4 * NJ + 2 * NLIN && n != 2 * NLIN)
-        return "expected 98 tensors (encoder + dfnet) or 14 (dfnet only, StrEnc.use = False) in state-dict order";
-    const bool enc = table_has_encoder(n);
-    int t = 0;
-    for (int j = 0; enc && j < NJ; ++j) {
-        const int64_t want[4] = {HID * enc_in(j), HID, FEAT * HID, FEAT};
-        for (int k = 0; k < 4; ++k, ++t)
-            if (!tensors[t] || numel[t] != want[k]) return "encoder tensor missing or of the wrong size";
+// The stateless packers have no handle, so the table brings its own plan: 98 tensors come with the structure encoder (in_dim 126), 14
+// without it (84 = 21 x 4, model.StrEnc.use = False: DFNet sees the normalised quaternions, reference model/posendf.py:40-42,73-74),
+// and the bias lengths are the layer widths -- at most configs/amass.yaml's, narrower layers travel zero padded.  Against that plan
+// the table is checked like any other.  Does it fit?
+static bool table_plan(const float* const* tensors, const int64_t* numel, int n, LayerNet& net) {
+    if (!tensors || !numel || (n != 4 * NJ + 2 * NLIN && n != 2 * NLIN)) return false;
+    pndf_config cfg;
+    pndf_default_config(&cfg, PNDF_ACT_RELU, 0.f);
+    cfg.dims[0] = n == 2 * NLIN ? NOENC_IN : DIMS[0];
+    for (int l = 0; l < NLIN; ++l) {
+        const int64_t out = numel[n - 2 * (NLIN - l) + 1];
+        if (out < 1 || out > DIMS[l + 1] || (l == NLIN - 1 && out != 1)) return false;
+        cfg.dims[l + 1] = (int)out;
     }
-    NetDims nd;
-    nd.d[0] = enc ? DIMS[0] : NOENC_IN;
-    for (int l = 0; l < NLIN; ++l) {             // the bias lengths are the layer widths
-        const int64_t out = numel[t + 2 * l + 1];
-        if (!tensors[t + 2 * l] || !tensors[t + 2 * l + 1] || out < 1 || out > DIMS[l + 1] || (l == NLIN - 1 && out != 1))
-            return "dfnet tensor missing, or a layer wider than the configs/amass.yaml architecture (256,512,1024,512,256,64,1)";
-        nd.d[l + 1] = (int)out;
-    }
-    for (int l = 0; l < NLIN; ++l)
-        if (numel[t + 2 * l] != (int64_t)nd.out(l) * nd.in(l)) return "dfnet weight of the wrong size";
-    if (dims_out) *dims_out = nd;
-    return nullptr;
+    layer_net_init(net, &cfg, -1);
+    return !pndf_table_fault(net, tensors, numel, n);
 }
 
-extern "C" int pndf_pack_host(const float* const* tensors, const int64_t* numel, int n_tensors, float* stream,
-                              float* bias) {
-    NetDims nd;
-    if (check_tensors(tensors, numel, n_tensors, &nd) || !stream || !bias) return PNDF_ERR_BAD_SHAPE;
+// a table that fits `net` (SMPL, amass.yaml's depth, no layer wider than amass.yaml's) -> the fp32 stream and the bias block
+static int pack_fp32(const float* const* tensors, const LayerNet& nd, float* stream, float* bias) {
     // ---- bias block: b0..b5 | w6 | b6 | per joint: b1 padded to 16, b2 on rows 4..9 of 16
     memset(bias, 0, BIAS_FLOATS * sizeof(float));
     for (int l = 0; l < 8; ++l) bias[SCALE_OFF + l] = 1.0f;
-    const bool enc = table_has_encoder(n_tensors);     // without the encoder its tiles / biases stay zero (skipped on chip)
+    const bool enc = nd.encoder;      // without the encoder its tiles / biases stay zero (skipped on chip)
     const float* const* lin = tensors + (enc ? 4 * NJ : 0);
     for (int l = 0; l < NLIN - 1; ++l) memcpy(bias + BIAS_OFF[l], lin[2 * l + 1], sizeof(float) * nd.out(l));   // narrower layers: zero padded
     memcpy(bias + W6_OFF, lin[2 * (NLIN - 1)], sizeof(float) * nd.in(NLIN - 1));
@@ -292,20 +267,22 @@ extern "C" int pndf_pack_host(const float* const* tensors, const int64_t* numel,
     if (enc) pndf_pack::emit_encoder_sections(tensors, stream, dst);
     return PNDF_OK;
 }
+extern "C" int pndf_pack_host(const float* const* tensors, const int64_t* numel, int n_tensors, float* stream, float* bias) {
+    LayerNet nd;
+    if (!table_plan(tensors, numel, n_tensors, nd) || !stream || !bias) return PNDF_ERR_BAD_SHAPE;
+    return pack_fp32(tensors, nd, stream, bias);
+}
 
 // ---- split-precision stream
 // Exact power-of-two scaling (pndf_pack::layer_scale): the weights of layer l travel as s_l W; 1 / s_l goes to the bias block
 // (SCALE_OFF + l).  Biases stay unscaled: activations and gradients are scaled PER POSE on the chip, and the packer only
 // supplies the norms (NORM_OFF) from which the kernel derives guaranteed bounds for the layers it cannot measure.
 
-// `nd`: the widths check_tensors found in this table
-static int pack_host_split(const float* const* tensors, const int64_t* numel, int n_tensors, const NetDims& nd, float* stream,
-                           float* bias, bool* lo_all_zero, bool bf16 = false) {
+static int pack_split(const float* const* tensors, const LayerNet& nd, float* stream, float* bias, bool* lo_all_zero, bool bf16 = false) {
     // biases and encoder tiles are identical to the fp32 stream (the encoder stays on fp32 MFMA)
-    int rc = pndf_pack_host(tensors, numel, n_tensors, stream, bias);
+    int rc = pack_fp32(tensors, nd, stream, bias);
     if (rc != PNDF_OK) return rc;
-    const bool enc = table_has_encoder(n_tensors);
-    const float* const* lin = tensors + (enc ? 4 * NJ : 0);
+    const float* const* lin = tensors + (nd.encoder ? 4 * NJ : 0);
     // per-layer weight scale; a layer without a finite non-zero weight cannot be scaled: refused (-> fp32 kernel)
     float wscale[6];
     for (int l = 0; l < 6; ++l) {
@@ -365,39 +342,38 @@ static int pack_host_split(const float* const* tensors, const int64_t* numel, in
 }
 extern "C" int pndf_pack_host_split(const float* const* tensors, const int64_t* numel, int n_tensors, float* stream,
                                     float* bias) {
-    NetDims nd;
-    if (check_tensors(tensors, numel, n_tensors, &nd)) return PNDF_ERR_BAD_SHAPE;
-    return pack_host_split(tensors, numel, n_tensors, nd, stream, bias, nullptr);
+    LayerNet nd;
+    if (!table_plan(tensors, numel, n_tensors, nd) || !stream || !bias) return PNDF_ERR_BAD_SHAPE;
+    return pack_split(tensors, nd, stream, bias, nullptr);
 }
 
 extern "C" int pndf_load_weights(pndf_handle h, const float* const* tensors, const int64_t* numel, int n_tensors) {
     if (!h) return PNDF_ERR_BAD_ARG;
-    if (h->generic) {
-        DeviceGuard guard(h->device);
-        if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
+    // One order for both kernel families: validate (a refused table leaves the previous weights serving), stage on the host, clear
+    // the flag, synchronise, copy, commit.
+    const LayerNet& nd = h->net;
+    if (const PndfTableFault f = pndf_table_fault(nd, tensors, numel, n_tensors))
+        return pndf_fail(h, PNDF_ERR_BAD_SHAPE, "the weight table does not fit the configured network (the encoder's 84 tensors for in_dim 126, then weight and bias of every dfnet.lin): " + f.text());
+    DeviceGuard guard(nd.device);
+    if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
+    if (h->generic) {      // stages under a plan of its own and commits it after its copies
+        h->have_weights = false;
         std::string why;
-        const int grc = pndf_generic_load(h->generic, tensors, numel, n_tensors, why);
+        const int grc = pndf_generic_load(h->generic, tensors, why);
         if (grc != PNDF_OK) return pndf_fail(h, grc, why);
         h->have_weights = true;
         return PNDF_OK;
     }
-    NetDims nd;
-    if (const char* why = check_tensors(tensors, numel, n_tensors, &nd)) return pndf_fail(h, PNDF_ERR_BAD_SHAPE, why);
-    if (table_has_encoder(n_tensors) != (h->cfg.dims[0] == DIMS[0]))
-        return pndf_fail(h, PNDF_ERR_BAD_SHAPE, "tensor table does not match the configured in_dim (98 tensors for 126, 14 for 84)");
-    for (int i = 0; i <= NLIN; ++i)
-        if (nd.d[i] != h->cfg.dims[i]) return pndf_fail(h, PNDF_ERR_BAD_SHAPE, "dfnet tensor shapes do not match the configured dims");
     std::vector<float> stream((size_t)STEP_TILES * TILE_FLOATS), bias(BIAS_FLOATS);
     bool lo_zero = false;
-    const int prc = (h->cfg.precision != PNDF_PREC_FP32)
-                        ? pack_host_split(tensors, numel, n_tensors, nd, stream.data(), bias.data(), &lo_zero, h->cfg.precision == PNDF_PREC_BF16)
-                        : pndf_pack_host(tensors, numel, n_tensors, stream.data(), bias.data());
+    const int prc = (h->precision != PNDF_PREC_FP32) ? pack_split(tensors, nd, stream.data(), bias.data(), &lo_zero, h->precision == PNDF_PREC_BF16)
+                                                     : pack_fp32(tensors, nd, stream.data(), bias.data());
     if (prc == PNDF_ERR_UNSUPPORTED)
         return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "a trunk layer has no finite non-zero weight: outside the operating "
                                              "range of the fp16 hi/lo split -- use precision fp32 for this network");
     if (prc != PNDF_OK)
         return pndf_fail(h, PNDF_ERR_BAD_SHAPE, "internal: packed stream length mismatch");
-    if (h->cfg.act == PNDF_ACT_SOFTPLUS) {
+    if (nd.act == PNDF_ACT_SOFTPLUS) {
         // zero-padded units of a narrower network: softplus(0) = ln 2 / beta with derivative 1/2 is harmless for the
         // result (zero outgoing weights) but would enter the per-pose operand bounds the split kernels measure (largest
         // activation, largest derivative of a layer).  A bias of -1e6 makes both exactly zero; relu-family units are
@@ -405,18 +381,17 @@ extern "C" int pndf_load_weights(pndf_handle h, const float* const* tensors, con
         for (int l = 0; l < NLIN - 1; ++l)
             for (int j = nd.out(l); j < DIMS[l + 1]; ++j) bias[BIAS_OFF[l] + j] = -1.0e6f;
     }
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
+    h->have_weights = false;              // from here on a failure leaves no half-loaded engine behind
     HIP_TRY(h, hipDeviceSynchronize());   // no launch may still be reading the old weights
     HIP_TRY(h, hipMemcpy(h->d_stream, stream.data(), stream.size() * sizeof(float), hipMemcpyHostToDevice));
     // replica of the first slots behind the stream: the ring's fetch offset never wraps inside a step
     HIP_TRY(h, hipMemcpy(h->d_stream + (size_t)STEP_TILES * TILE_BYTES, stream.data(),
                          (size_t)STREAM_PAD_SLOTS * SLOT_TILES * TILE_BYTES, hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->d_bias, bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice));
-    h->have_weights = true;
     // PNDF_THREE_TERMS=1 keeps the three-term kernels (same-box A/B runs and the bit-identity test)
     const char* keep3 = getenv("PNDF_THREE_TERMS");
-    h->lo_all_zero = lo_zero && h->cfg.precision == PNDF_PREC_F16X3 && !(keep3 && keep3[0] == '1');
+    h->lo_all_zero = lo_zero && h->precision == PNDF_PREC_F16X3 && !(keep3 && keep3[0] == '1');
+    h->have_weights = true;
     return PNDF_OK;
 }
 
@@ -424,7 +399,7 @@ extern "C" int pndf_load_weights(pndf_handle h, const float* const* tensors, con
 extern "C" const char* pndf_kernel_name(pndf_handle h) {
     if (!h) return "";
     if (h->generic) return pndf_generic_kernel_name(h->generic);
-    return fused_kernel(h->cfg.precision, h->cfg.act == PNDF_ACT_SOFTPLUS, h->lo_all_zero).name;
+    return fused_kernel(h->precision, h->net.act == PNDF_ACT_SOFTPLUS, h->lo_all_zero).name;
 }
 
 // ------------------------------------------------------------------------------------------ launches
@@ -442,10 +417,10 @@ static int launch(pndf_engine* h, int mode, const float* q, const float* gout, f
         return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose / output pointer");
     if (((uintptr_t)q | (uintptr_t)qo) & 15) return pndf_fail(h, PNDF_ERR_BAD_ARG, "pose buffers must be 16-byte aligned");
     if (((uintptr_t)d | (uintptr_t)gout) & 3) return pndf_fail(h, PNDF_ERR_BAD_ARG, "misaligned distance buffer");
-    const bool softplus = h->cfg.act == PNDF_ACT_SOFTPLUS;
+    const bool softplus = h->net.act == PNDF_ACT_SOFTPLUS;
     if (h->generic && (dbg || timing))
         return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "stage dumps and region timing exist for the amass.yaml-shaped kernels only");
-    DeviceGuard guard(h->device);
+    DeviceGuard guard(h->net.device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     if (!h->generic) {
         if (dbg && !timing) return pndf_fail(h, PNDF_ERR_BAD_ARG, "a dump buffer needs an instrumented kernel (libposendf_amd_debug.so)");
@@ -468,10 +443,10 @@ static int launch(pndf_engine* h, int mode, const float* q, const float* gout, f
     a.stream = h->d_stream; a.bias = h->d_bias; a.dbg = dbg;
     a.B = B; a.steps = steps;
     pndf_fill_step_options(a, mode, popt);
-    a.slope = (h->cfg.act == PNDF_ACT_LRELU) ? 0.01f : 0.0f;   // nn.LeakyReLU() default slope, net_modules.py:31
-    a.beta = h->cfg.beta;
+    a.slope = (h->net.act == PNDF_ACT_LRELU) ? 0.01f : 0.0f;   // nn.LeakyReLU() default slope, net_modules.py:31
+    a.beta = h->net.beta;
     a.scratch = softplus ? h->d_scratch : nullptr;
-    a.noenc = (h->cfg.dims[0] == NOENC_IN) ? 1 : 0;
+    a.noenc = h->net.encoder ? 0 : 1;
     // relu family: one workgroup per 64-pose block.  Softplus: a persistent grid, at most one workgroup per CU (a workgroup takes
     // a whole CU), each walking its blocks; the derivative scratch is indexed by workgroup and was allocated in pndf_create --
     // nothing is allocated, freed or synchronised here.  The scratch is shared by all launches of the handle: sp_order.
@@ -483,7 +458,7 @@ static int launch(pndf_engine* h, int mode, const float* q, const float* gout, f
         void* kargs[] = {&a};
         HIP_TRY(h, hipLaunchKernel(instrumented, grid, block, kargs, pndf_kernel_lds_bytes(), (hipStream_t)stream));
     } else {
-        hipLaunchKernelGGL(fused_kernel(h->cfg.precision, softplus, h->lo_all_zero).fn, grid, block, pndf_kernel_lds_bytes(), (hipStream_t)stream, a);
+        hipLaunchKernelGGL(fused_kernel(h->precision, softplus, h->lo_all_zero).fn, grid, block, pndf_kernel_lds_bytes(), (hipStream_t)stream, a);
     }
     HIP_TRY(h, hipGetLastError());
     if (softplus) HIP_TRY(h, h->sp_order.record(stream));
@@ -540,7 +515,7 @@ extern "C" int pndf_complete(pndf_handle h, const float* q_in, const uint32_t* o
     if (!q_in || !q_out) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose / output pointer");
     if (!workspace) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null workspace (pndf_complete_workspace_floats(B) floats of device memory)");
     if (const char* why = pndf_check_step_alignment({q_in, q_out, workspace}, d_last, observed)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
-    DeviceGuard guard(h->device);
+    DeviceGuard guard(h->net.device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     if (q_out != q_in) HIP_TRY(h, hipMemcpyAsync(q_out, q_in, (size_t)B * NQ * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     if (steps == 0) {      // as pndf_project_ex: the poses pass through
@@ -579,7 +554,7 @@ extern "C" int pndf_interpolate(pndf_handle h, const float* a, const float* b, c
     if (!workspace)
         return pndf_fail(h, PNDF_ERR_BAD_ARG, "null workspace (pndf_interpolate_workspace_floats(P, T) floats of device memory)");
     if (const char* why = pndf_check_step_alignment({a, b, track_out, workspace}, d_last, observed)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
-    DeviceGuard guard(h->device);
+    DeviceGuard guard(h->net.device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     const int64_t B = P * T;
     float* d_ws = (float*)workspace;
@@ -618,10 +593,10 @@ extern "C" int pndf_internal_launch(pndf_handle h, int mode, const float* q, con
 // what[0..6] = precision, act, lo_all_zero, noenc, runtime-planned, resident workgroups, LDS bytes of a fused kernel
 extern "C" int pndf_internal_describe(pndf_handle h, int* what, int n) {
     if (!h || !what || n < 7) return PNDF_ERR_BAD_ARG;
-    what[0] = h->cfg.precision;
-    what[1] = h->cfg.act;
+    what[0] = h->precision;
+    what[1] = h->net.act;
     what[2] = h->lo_all_zero ? 1 : 0;
-    what[3] = (h->cfg.dims[0] == NOENC_IN) ? 1 : 0;
+    what[3] = h->net.encoder ? 0 : 1;
     what[4] = h->generic ? 1 : 0;
     what[5] = h->resident_wgs;
     what[6] = pndf_kernel_lds_bytes();

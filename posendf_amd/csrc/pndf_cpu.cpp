@@ -52,18 +52,13 @@ struct Layer {
 }  // namespace
 
 struct pndf_cpu_engine {
-    pndf_config cfg;
-    bool encoder = true;
+    LayerNet net;           // the skeleton, the widths, the activations and the size of every tensor (pndf_net_plan.h)
     bool have_weights = false;
     bool smpl = true;       // 21 joints along get_parent_mapping('smpl'): what completion, interpolation and the second order need
-    int nj = NJ;            // joints, quaternion components (4 nj) and parent table of the skeleton
-    int nq = NQ;
-    int parent[MAXJ];
     Layer enc[MAXJ][2];
     Layer lin[MAXLIN];      // any DFNet depth the reference can build (net_modules.py:14-28: `dims` is a free list): 2 .. 8 linear layers
-    int dims[MAXLIN + 1];
-    int nlin = NLIN;
     std::string err;
+    int nq() const { return 4 * net.nj; }      // quaternion components of a pose
 };
 
 namespace {
@@ -137,12 +132,11 @@ struct Scratch {      // per thread
 
 void forward_grad_block(const pndf_cpu_engine& E, const float* q /*[nb][4 nj]*/, int nb, const float* gout, float* d, float* dq,
                         bool want_grad, Scratch& S) {
-    const int NJ = E.nj, NQ = E.nq, NFEAT = FEAT * E.nj;      // the skeleton of the handle (shadowing pndf_layout.h's SMPL constants)
-    const int* PARENT = E.parent;
+    const int NJ = E.net.nj, NQ = E.nq(), NFEAT = FEAT * NJ;      // the skeleton of the handle (shadowing pndf_layout.h's SMPL constants)
+    const int* PARENT = E.net.parent;
     auto enc_in = [PARENT](int j) { return PARENT[j] < 0 ? 4 : 10; };
-    const Act act{E.cfg.act, E.cfg.beta};
-    // model.StrEnc.act / beta are read on their own (net_modules.py:128); -1 / <= 0: the trunk's
-    const Act eact{pndf_enc_act(E.cfg), pndf_enc_beta(E.cfg)};
+    const Act act{E.net.act, E.net.beta};
+    const Act eact{E.net.enc_act, E.net.enc_beta};      // model.StrEnc.act / beta, read on their own (net_modules.py:128)
     // ---- normalise over joints per component (posendf.py:71), poses of the block as the inner index
     S.n.assign((size_t)NQ * PB, 0.f);
     for (int c = 0; c < 4; ++c)
@@ -158,9 +152,9 @@ void forward_grad_block(const pndf_cpu_engine& E, const float* q /*[nb][4 nj]*/,
         for (int c = 0; c < 4; ++c)
             for (int p = 0; p < nb; ++p) S.n[(size_t)(4 * j + c) * PB + p] = q[(size_t)p * NQ + 4 * j + c] * S.inv[c][p];
     // ---- structure encoder (net_modules.py:140-170) or the normalised pose itself
-    const int d0 = E.dims[0];
+    const int d0 = E.net.dims[0];
     S.x[0].assign((size_t)d0 * PB, 0.f);
-    if (E.encoder) {
+    if (E.net.encoder) {
         for (int j = 0; j < NJ; ++j) {
             const int in = enc_in(j);
             S.ein[j].assign((size_t)in * PB, 0.f);
@@ -178,7 +172,7 @@ void forward_grad_block(const pndf_cpu_engine& E, const float* q /*[nb][4 nj]*/,
         memcpy(S.x[0].data(), S.n.data(), sizeof(float) * NQ * PB);
     }
     // ---- DFNet (net_modules.py:46-72)
-    const int NL = E.nlin;
+    const int NL = E.net.L;
     for (int l = 0; l < NL; ++l) {
         const Layer& L = E.lin[l];
         S.x[l + 1].resize((size_t)L.out * PB);
@@ -202,7 +196,7 @@ void forward_grad_block(const pndf_cpu_engine& E, const float* q /*[nb][4 nj]*/,
     // S.g = d / d x0  [d0][PB]
     std::vector<float>& gn = S.g2;
     gn.assign((size_t)NQ * PB, 0.f);
-    if (E.encoder) {
+    if (E.net.encoder) {
         // children before parents: joints in decreasing index order (every parent has a smaller index)
         std::vector<float>& gfeat = S.gf;
         gfeat.assign(S.g.begin(), S.g.begin() + (size_t)NFEAT * PB);      // accumulates the children's contributions
@@ -303,19 +297,12 @@ extern "C" int pndf_cpu_create(pndf_cpu_handle* out, const pndf_config* cfg) {
     // same DFNets the device units accept
     if (const char* why = pndf_skeleton_refusal(cfg)) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_UNSUPPORTED, why);
     if (const char* why = pndf_dfnet_refusal(cfg)) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_UNSUPPORTED, why);
-    const int nlin = cfg->n_dims - 1;
     if (cfg->act == PNDF_ACT_SOFTPLUS && !(cfg->beta > 0.f)) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_BAD_ARG, "Softplus beta must be positive");
     if (cfg->enc_act == PNDF_ACT_SOFTPLUS && !(cfg->enc_beta > 0.f) && !(cfg->beta > 0.f)) return pndf_fail<pndf_cpu_engine>(nullptr, PNDF_ERR_BAD_ARG, "Softplus beta of the encoder must be positive");
     return guarded(nullptr, [&] {
         pndf_cpu_engine* h = new pndf_cpu_engine();
-        h->cfg = *cfg;
+        layer_net_init(h->net, cfg, -1);      // (no device)
         h->smpl = pndf_skeleton_is_smpl(cfg);
-        h->nj = cfg->num_joints;
-        h->nq = 4 * h->nj;
-        for (int j = 0; j < MAXJ; ++j) h->parent[j] = j < h->nj ? cfg->parent[j] : -1;
-        h->encoder = cfg->dims[0] == FEAT * h->nj;
-        h->nlin = nlin;
-        for (int l = 0; l <= nlin; ++l) h->dims[l] = cfg->dims[l];
         *out = h;
     });
 }
@@ -328,15 +315,15 @@ extern "C" int pndf_cpu_destroy(pndf_cpu_handle h) {
 extern "C" const char* pndf_cpu_last_error(pndf_cpu_handle h) { return pndf_last_error_of(h); }
 
 extern "C" int pndf_cpu_load_weights(pndf_cpu_handle h, const float* const* tensors, const int64_t* numel, int n_tensors) {
-    if (!h || !tensors || !numel) return PNDF_ERR_BAD_ARG;
-    const int want = (h->encoder ? 4 * h->nj : 0) + 2 * h->nlin;
-    if (n_tensors != want) return pndf_fail(h, PNDF_ERR_BAD_SHAPE, "tensor count: " + std::to_string(n_tensors) + ", expected " + std::to_string(want));
-    h->have_weights = false;      // a failed load leaves no half-loaded engine behind
-    int rc = PNDF_OK;
+    if (!h) return PNDF_ERR_BAD_ARG;
+    const PndfTableFault f = pndf_table_fault(h->net, tensors, numel, n_tensors);
+    if (f.kind == PndfTableFault::NULL_TABLE) return PNDF_ERR_BAD_ARG;
+    if (f.kind == PndfTableFault::COUNT) return pndf_fail(h, PNDF_ERR_BAD_SHAPE, f.text());
+    h->have_weights = false;      // a table of the right length that does not fit leaves the handle without weights, as a failed copy does
+    if (f) return pndf_fail(h, PNDF_ERR_BAD_SHAPE, f.text());
     const int grc = guarded(h, [&] {
         int t = 0;
-        auto take = [&](Layer& L, int out, int in) -> bool {
-            if (!tensors[t] || !tensors[t + 1] || numel[t] != (int64_t)out * in || numel[t + 1] != out) return false;
+        auto take = [&](Layer& L, int out, int in) {
             L.in = in; L.out = out;
             L.w.assign(tensors[t], tensors[t] + (size_t)out * in);
             L.b.assign(tensors[t + 1], tensors[t + 1] + out);
@@ -344,18 +331,14 @@ extern "C" int pndf_cpu_load_weights(pndf_cpu_handle h, const float* const* tens
             for (int o = 0; o < out; ++o)
                 for (int i = 0; i < in; ++i) L.wt[(size_t)i * out + o] = L.w[(size_t)o * in + i];
             t += 2;
-            return true;
         };
-        if (h->encoder)
-            for (int j = 0; j < h->nj && rc == PNDF_OK; ++j)
-                if (!take(h->enc[j][0], HID, h->parent[j] < 0 ? 4 : 10) || !take(h->enc[j][1], FEAT, HID))
-                    rc = pndf_fail(h, PNDF_ERR_BAD_SHAPE, "encoder tensor " + std::to_string(t) + " has the wrong size");
-        for (int l = 0; l < h->nlin && rc == PNDF_OK; ++l)
-            if (!take(h->lin[l], h->dims[l + 1], h->dims[l]))
-                rc = pndf_fail(h, PNDF_ERR_BAD_SHAPE, "dfnet.lin" + std::to_string(l) + " has the wrong size");
+        for (int j = 0; h->net.encoder && j < h->net.nj; ++j) {
+            take(h->enc[j][0], HID, h->net.parent[j] < 0 ? 4 : 10);
+            take(h->enc[j][1], FEAT, HID);
+        }
+        for (int l = 0; l < h->net.L; ++l) take(h->lin[l], h->net.dims[l + 1], h->net.dims[l]);
     });
     if (grc != PNDF_OK) return grc;
-    if (rc != PNDF_OK) return rc;
     h->have_weights = true;
     return PNDF_OK;
 }
@@ -364,7 +347,7 @@ extern "C" int pndf_forward_cpu(pndf_cpu_handle h, const float* q, float* d, int
     if (int rc = check(h, q, B)) return rc;
     if (B > 0 && !d) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null output pointer");
     return guarded(h, [&] {
-        parallel_blocks(B, [&](int64_t p0, int nb, Scratch& S) { forward_grad_block(*h, q + p0 * h->nq, nb, nullptr, d + p0, nullptr, false, S); });
+        parallel_blocks(B, [&](int64_t p0, int nb, Scratch& S) { forward_grad_block(*h, q + p0 * h->nq(), nb, nullptr, d + p0, nullptr, false, S); });
     });
 }
 
@@ -374,7 +357,7 @@ extern "C" int pndf_forward_grad_cpu(pndf_cpu_handle h, const float* q, const fl
     return guarded(h, [&] {
         parallel_blocks(B, [&](int64_t p0, int nb, Scratch& S) {
             float dd[PB];
-            forward_grad_block(*h, q + p0 * h->nq, nb, grad_out ? grad_out + p0 : nullptr, dd, dq + p0 * h->nq, true, S);
+            forward_grad_block(*h, q + p0 * h->nq(), nb, grad_out ? grad_out + p0 : nullptr, dd, dq + p0 * h->nq(), true, S);
             if (d) memcpy(d + p0, dd, sizeof(float) * nb);
         });
     });
@@ -383,7 +366,7 @@ extern "C" int pndf_forward_grad_cpu(pndf_cpu_handle h, const float* q, const fl
 extern "C" int pndf_project_cpu(pndf_cpu_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps) {
     if (int rc = check(h, q_in, B)) return rc;
     if (steps < 0 || (B > 0 && !q_out)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count or null output pointer");
-    const int NQ = h->nq;
+    const int NQ = h->nq();
     return guarded(h, [&] {
     parallel_blocks(B, [&](int64_t p0, int nb, Scratch& S) {
         float qb[PB * 4 * MAXJ], dqb[PB * 4 * MAXJ], dd[PB];
@@ -426,7 +409,7 @@ static void project_step_cpu(float* q, const float* dq, float d, const pndf_proj
 // block; `observed` null = no joint held.
 static int project_loop_cpu(pndf_cpu_handle h, const float* q_in, const uint32_t* observed, float* q_out, float* d_last, int64_t B,
                             int steps, const pndf_project_options& o) {
-    const int NQ = h->nq;
+    const int NQ = h->nq();
     return guarded(h, [&] {
     parallel_blocks(B, [&](int64_t p0, int nb, Scratch& S) {
         float qb[PB * 4 * MAXJ], dqb[PB * 4 * MAXJ], dd[PB];
@@ -434,7 +417,7 @@ static int project_loop_cpu(pndf_cpu_handle h, const float* q_in, const uint32_t
         for (int p = 0; p < nb; ++p) dd[p] = 0.f;
         for (int s = 0; s < steps; ++s) {
             forward_grad_block(*h, qb, nb, nullptr, dd, dqb, true, S);
-            for (int p = 0; p < nb; ++p) project_step_cpu(qb + p * NQ, dqb + p * NQ, dd[p], o, observed ? observed[p0 + p] : 0u, h->nj);
+            for (int p = 0; p < nb; ++p) project_step_cpu(qb + p * NQ, dqb + p * NQ, dd[p], o, observed ? observed[p0 + p] : 0u, h->net.nj);
         }
         memcpy(q_out + p0 * NQ, qb, sizeof(float) * nb * NQ);
         if (d_last) memcpy(d_last + p0, dd, sizeof(float) * nb);
@@ -568,8 +551,8 @@ struct SoScratch {
 
 void second_order_pose(const pndf_cpu_engine& E, const float* q, const float* v, float wd, float wt, float* d, float* g, float* t,
                        float* out, SoScratch& S) {
-    const Act act{E.cfg.act, E.cfg.beta};
-    const Act eact{pndf_enc_act(E.cfg), pndf_enc_beta(E.cfg)};
+    const Act act{E.net.act, E.net.beta};
+    const Act eact{E.net.enc_act, E.net.enc_beta};
     constexpr int FIN = 4 + FEAT;
     // ---- normalisation: x, xdot = J_N v
     float s[4], va[4], x[NQ], xd[NQ];
@@ -613,7 +596,7 @@ void second_order_pose(const pndf_cpu_engine& E, const float* q, const float* v,
         }
     }
     // ---- trunk: primal and tangent; c2 = sigma'' zdot
-    const int NL = E.nlin;
+    const int NL = E.net.L;
     S.a.assign(feat, feat + NFEAT);
     S.ad.assign(tfeat, tfeat + NFEAT);
     for (int l = 0; l < NL; ++l) {
@@ -710,7 +693,7 @@ extern "C" int pndf_second_order_cpu(pndf_cpu_handle h, const float* q, const fl
                                      float* g, float* t, float* out, int64_t B) {
     if (!h) return PNDF_ERR_BAD_ARG;
     if (!h->smpl) return pndf_fail(h, PNDF_ERR_UNSUPPORTED, SMPL_ONLY);
-    if (!h->encoder)
+    if (!h->net.encoder)
         return pndf_fail(h, PNDF_ERR_UNSUPPORTED, "the second order needs the structure encoder (model.StrEnc.use: True, dims[0] = 126)");
     if (int rc = check(h, q, B)) return rc;
     if (B == 0) return PNDF_OK;

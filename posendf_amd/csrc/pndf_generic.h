@@ -11,18 +11,20 @@
 #include <string>
 
 #include "../../include/posendf_amd.h"
+#include "pndf_net_plan.h"
 
-struct PndfGeneric;      // plan + device buffers of one engine
+struct PndfGeneric;      // launch plan + device buffers of one engine
 
 // does `cfg` need this path?  (false: the amass.yaml-shaped kernels take it; unsupported configurations are refused by
 // pndf_create before this is asked)
 bool pndf_generic_needed(const pndf_config& cfg);
-// 0 or a negative pndf_status with `err` set
-int pndf_generic_create(PndfGeneric** out, const pndf_config& cfg, int resident_wgs, std::string& err);
+// 0 or a negative pndf_status with `err` set.  `net`: the engine's plan, which outlives the PndfGeneric; `precision`: fp32 or a split one
+int pndf_generic_create(PndfGeneric** out, const LayerNet& net, int precision, int resident_wgs, std::string& err);
 void pndf_generic_destroy(PndfGeneric* g);
-// tensors in state-dict order: 84 encoder tensors (with the encoder) + 2 per linear layer
-int pndf_generic_load(PndfGeneric* g, const float* const* tensors, const int64_t* numel, int n_tensors, std::string& err);
-// mode: MODE_FORWARD / MODE_FORWARD_GRAD / MODE_PROJECT (pndf_args.h); enqueues ONE kernel on `stream`
+// tensors in state-dict order, a table the caller has checked against `net` (pndf_table_fault).  After a failure the device holds
+// neither the old nor the new weights whole: the caller must not launch until a load succeeds.
+int pndf_generic_load(PndfGeneric* g, const float* const* tensors, std::string& err);
+// mode: MODE_FORWARD / MODE_FORWARD_GRAD / MODE_PROJECT (pndf_args.h); enqueues ONE kernel on `stream`.  For a handle whose last load succeeded.
 int pndf_generic_launch(PndfGeneric* g, int mode, const float* q, const float* gout, float* qo, float* d, int64_t B, int steps,
                         void* stream, std::string& err, const pndf_project_options* popt = nullptr);      // popt: validated, or null = the plain step
 const char* pndf_generic_kernel_name(const PndfGeneric* g);

@@ -919,19 +919,40 @@ extern "C" __global__ void __launch_bounds__(WG_THREADS, 1) pndf_generic_split_s
 // ------------------------------------------------------------------------------------------ host side
 using namespace pndf;
 
+// The eight kernels: [form: exact fp32 | split][trunk family: relu | softplus][encoder family: relu | softplus]
+typedef void (*gen_kernel_t)(PndfGenericArgs);
+struct GenKernel {
+    gen_kernel_t fn;
+    const char* name;
+};
+#define PNDF_GEN(k) {k, #k}
+static const GenKernel GEN_KERNELS[2][2][2] = {
+    {{PNDF_GEN(pndf_generic_relu_kernel), PNDF_GEN(pndf_generic_relu_spenc_kernel)},
+     {PNDF_GEN(pndf_generic_softplus_reluenc_kernel), PNDF_GEN(pndf_generic_softplus_kernel)}},
+    {{PNDF_GEN(pndf_generic_split_relu_kernel), PNDF_GEN(pndf_generic_split_relu_spenc_kernel)},
+     {PNDF_GEN(pndf_generic_split_softplus_reluenc_kernel), PNDF_GEN(pndf_generic_split_softplus_kernel)}}};
+#undef PNDF_GEN
+static const GenKernel& gen_kernel(const LayerNet& n, bool split) {
+    const bool sp = n.act == PNDF_ACT_SOFTPLUS, esp = n.encoder ? n.enc_act == PNDF_ACT_SOFTPLUS : sp;      // (no encoder: the trunk's family)
+    return GEN_KERNELS[split][sp][esp];
+}
+
+// what a launch needs of a loaded weight table
+struct GenPlan {
+    PndfGenericArgs args;            // tile counts, offsets and weight scales (pointers filled per launch)
+    size_t lbias_floats = 0;
+    int trunk_tiles = 0;             // the trunk's tiles rounded up to whole ring slots
+    bool split = false;              // the trunk on split-precision fp16 MFMAs -- decided at pndf_generic_load
+};
+
 struct PndfGeneric {
-    pndf_config cfg;
-    int L = 0;
-    bool enc = true;
+    const LayerNet* net = nullptr;   // the engine's: depth, widths, the encoder and both activations
+    int precision = PNDF_PREC_FP32;  // fp32: the exact form; f16x3 and f16 alike: the three-term split form (there is no two-term or plain-f16 form here)
     int resident = 0;
-    PndfGenericArgs plan;            // tile counts and offsets (pointers filled per launch)
-    size_t wf_tiles = 0, wb_tiles = 0, lbias_floats = 0;
-    int trunk_tiles = 0;             // wf_tiles + wb_tiles rounded up to whole ring slots
-    bool split = false;              // the trunk on split-precision fp16 MFMAs (precision f16x3 / f16) -- decided at pndf_generic_load
+    GenPlan plan;                    // of the weights on the device: written by a load whose copies succeeded
     size_t enc_alloc_tiles = 0;      // tiles allocated for the step's stream (the larger of the two plans)
     char* d_enc = nullptr;
-    float *d_bias = nullptr, *d_wf = nullptr, *d_wb = nullptr, *d_lb = nullptr, *d_scratch = nullptr;
-    bool have_weights = false;
+    float *d_bias = nullptr, *d_lb = nullptr, *d_scratch = nullptr;
     PndfScratchOrder order;          // the scratch is shared by all launches of the handle, as the softplus engines' is
 };
 
@@ -959,23 +980,6 @@ bool pndf_generic_needed(const pndf_config& cfg) {
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int round_up_int(int a, int b) { return ceil_div(a, b) * b; }
-constexpr int GEN_STREAM_PAD_SLOTS = 5;      // >= RING_SLOTS - 1: the replica of the stream's first slots behind it (the ring never wraps)
-typedef void (*gen_kernel_t)(PndfGenericArgs);
-static gen_kernel_t gen_kernel(const pndf_config& cfg, bool split, const char** name) {
-    const bool sp = cfg.act == PNDF_ACT_SOFTPLUS, esp = (cfg.dims[0] == DIMS[0]) ? pndf_enc_act(cfg) == PNDF_ACT_SOFTPLUS : sp;
-    if (split) {
-        if (sp && esp) { *name = "pndf_generic_split_softplus_kernel"; return pndf_generic_split_softplus_kernel; }
-        if (!sp && !esp) { *name = "pndf_generic_split_relu_kernel"; return pndf_generic_split_relu_kernel; }
-        if (sp) { *name = "pndf_generic_split_softplus_reluenc_kernel"; return pndf_generic_split_softplus_reluenc_kernel; }
-        *name = "pndf_generic_split_relu_spenc_kernel";
-        return pndf_generic_split_relu_spenc_kernel;
-    }
-    if (sp && esp) { *name = "pndf_generic_softplus_kernel"; return pndf_generic_softplus_kernel; }
-    if (!sp && !esp) { *name = "pndf_generic_relu_kernel"; return pndf_generic_relu_kernel; }
-    if (sp) { *name = "pndf_generic_softplus_reluenc_kernel"; return pndf_generic_softplus_reluenc_kernel; }
-    *name = "pndf_generic_relu_spenc_kernel";
-    return pndf_generic_relu_spenc_kernel;
-}
 // tiles -> tiles rounded up to a group count the layer code exists for (PNDF_GEN_GROUP_CASES)
 static inline int gen_round_tiles(int tiles) {
     const int groups = ceil_div(tiles, NTB);
@@ -984,17 +988,17 @@ static inline int gen_round_tiles(int tiles) {
 }
 
 // tile counts and offsets of the step's stream and of the workgroup's scratch, for the fp32 or the split-precision trunk
-static void gen_plan(PndfGeneric* g, bool split) {
-    const pndf_config& cfg = g->cfg;
-    const int L = g->L;
-    PndfGenericArgs& P = g->plan;
+static GenPlan gen_plan(const LayerNet& n, bool split) {
+    GenPlan plan;
+    const int L = n.L;
+    PndfGenericArgs& P = plan.args;
     memset(&P, 0, sizeof(P));
     P.nlayers = L;
-    P.noenc = g->enc ? 0 : 1;
+    P.noenc = n.encoder ? 0 : 1;
     int bo = 0, slot = 2 * PNDF_GEN_XTILES;
     for (int l = 0; l < L; ++l) {
-        const int in = (l == 0) ? 128 : cfg.dims[l];      // x0 is the pose's 128-row feature buffer (126 | 84 rows used, the rest zero)
-        const int outw = cfg.dims[l + 1];
+        const int in = (l == 0) ? 128 : n.dims[l];      // x0 is the pose's 128-row feature buffer (126 | 84 rows used, the rest zero)
+        const int outw = n.dims[l + 1];
         P.kt[l] = ceil_div(in, 16);
         P.nt[l] = ceil_div(outw, 16);
         P.kb[l] = ceil_div(P.kt[l], 2);
@@ -1013,55 +1017,48 @@ static void gen_plan(PndfGeneric* g, bool split) {
         P.wf_off[l] = wf;
         wf += split ? 2 * P.ntp[l] * P.kb[l] : P.ntp[l] * P.kt[l];
     }
-    g->wf_tiles = wf;                 // the backward matrices follow the forward ones in ONE stream, in the order the backward pass walks them
-    for (int l = L - 1; l >= 0; --l) {
+    for (int l = L - 1; l >= 0; --l) {      // the backward matrices follow the forward ones in ONE stream, in the order the backward pass walks them
         P.wb_off[l] = wf + wb;
         wb += split ? 2 * P.ktp[l] * P.nb[l] : P.ktp[l] * P.nt[l];
     }
-    g->wb_tiles = wb;
     P.enc_d_off = slot;
-    if (pndf_enc_act(cfg) == PNDF_ACT_SOFTPLUS && g->enc) slot += 2 * NJ;
+    if (n.enc_act == PNDF_ACT_SOFTPLUS && n.encoder) slot += 2 * NJ;
     P.wg_tiles = slot;
     // the step's stream: encoder forward (3 slots) | trunk (whole groups of NTB tiles, padded to whole slots) | encoder backward (3 slots)
     // Every group of the trunk runs the ring events and the tile reads of the group BEHIND it (gen_layer has no "last group" case), so
     // the last one needs padding behind it: fp32 the other half of its slot, or -- when the trunk fills its last slot -- a slot of its
     // own; split (a group = a slot) always a slot.
-    g->trunk_tiles = split ? (wf + wb) + SLOT_TILES : round_up_int((wf + wb) + NTB, SLOT_TILES);
-    P.w_slots = (2 * ENC_TILES_PADDED + g->trunk_tiles) / SLOT_TILES;
-    g->lbias_floats = bo;
-    g->split = split;
+    plan.trunk_tiles = split ? (wf + wb) + SLOT_TILES : round_up_int((wf + wb) + NTB, SLOT_TILES);
+    P.w_slots = (2 * ENC_TILES_PADDED + plan.trunk_tiles) / SLOT_TILES;
+    plan.lbias_floats = bo;
+    plan.split = split;
+    return plan;
 }
 
-int pndf_generic_create(PndfGeneric** out, const pndf_config& cfg, int resident_wgs, std::string& err) {
+int pndf_generic_create(PndfGeneric** out, const LayerNet& net, int precision, int resident_wgs, std::string& err) {
     *out = nullptr;
-    const int L = cfg.n_dims - 1;
-    if (L < 2 || L > PNDF_GEN_MAXLIN) { err = "DFNet depth: 2 .. 8 linear layers (n_dims 3 .. 9)"; return PNDF_ERR_UNSUPPORTED; }
     PndfGeneric* g = new PndfGeneric();
-    g->cfg = cfg;
-    g->L = L;
-    g->enc = cfg.dims[0] == DIMS[0];
+    g->net = &net;
+    g->precision = precision;
     g->resident = resident_wgs;
     // the stream is allocated for the larger of the two plans: pndf_generic_load falls back to the fp32 trunk when a layer cannot be
     // scaled into the fp16 range (scratch and biases have the same layout in both)
-    gen_plan(g, false);
-    size_t alloc_slots = (size_t)g->plan.w_slots;
-    if (cfg.precision != PNDF_PREC_FP32) {
-        gen_plan(g, true);
-        if ((size_t)g->plan.w_slots > alloc_slots) alloc_slots = (size_t)g->plan.w_slots;
+    g->plan = gen_plan(net, false);
+    size_t alloc_slots = (size_t)g->plan.args.w_slots;
+    if (precision != PNDF_PREC_FP32) {
+        g->plan = gen_plan(net, true);
+        if ((size_t)g->plan.args.w_slots > alloc_slots) alloc_slots = (size_t)g->plan.args.w_slots;
     }
-    g->enc_alloc_tiles = (alloc_slots + GEN_STREAM_PAD_SLOTS) * SLOT_TILES;
-    PndfGenericArgs& P = g->plan;
+    g->enc_alloc_tiles = (alloc_slots + pndf_pack::STREAM_PAD_SLOTS) * SLOT_TILES;
     hipError_t e = hipMalloc((void**)&g->d_bias, BIAS_FLOATS * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&g->d_enc, g->enc_alloc_tiles * TILE_BYTES);
-    g->d_wf = g->d_wb = nullptr;      // (one stream: encoder and trunk tiles live in d_enc)
-    if (e == hipSuccess) e = hipMalloc((void**)&g->d_lb, g->lbias_floats * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&g->d_scratch, (size_t)resident_wgs * P.wg_tiles * SLOT_F4 * sizeof(f32x4));
+    if (e == hipSuccess) e = hipMalloc((void**)&g->d_enc, g->enc_alloc_tiles * TILE_BYTES);      // (one stream: encoder and trunk tiles)
+    if (e == hipSuccess) e = hipMalloc((void**)&g->d_lb, g->plan.lbias_floats * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&g->d_scratch, (size_t)resident_wgs * g->plan.args.wg_tiles * SLOT_F4 * sizeof(f32x4));
     if (e == hipSuccess) e = g->order.create();
-    for (const void* kfn : {(const void*)pndf_generic_relu_kernel, (const void*)pndf_generic_softplus_kernel,
-                            (const void*)pndf_generic_relu_spenc_kernel, (const void*)pndf_generic_softplus_reluenc_kernel,
-                            (const void*)pndf_generic_split_relu_kernel, (const void*)pndf_generic_split_softplus_kernel,
-                            (const void*)pndf_generic_split_relu_spenc_kernel, (const void*)pndf_generic_split_softplus_reluenc_kernel})
-        if (e == hipSuccess) e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
+    for (const auto& form : GEN_KERNELS)
+        for (const auto& trunk : form)
+            for (const GenKernel& k : trunk)
+                if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
     if (e != hipSuccess) {
         err = std::string("pndf_create (runtime-planned DFNet): ") + hipGetErrorString(e);
         pndf_generic_destroy(g);
@@ -1074,47 +1071,33 @@ int pndf_generic_create(PndfGeneric** out, const pndf_config& cfg, int resident_
 void pndf_generic_destroy(PndfGeneric* g) {
     if (!g) return;
     g->order.destroy();
-    for (void* p : {(void*)g->d_enc, (void*)g->d_bias, (void*)g->d_wf, (void*)g->d_wb, (void*)g->d_lb, (void*)g->d_scratch})
+    for (void* p : {(void*)g->d_enc, (void*)g->d_bias, (void*)g->d_lb, (void*)g->d_scratch})
         if (p) (void)hipFree(p);
     delete g;
 }
 
-int pndf_generic_load(PndfGeneric* g, const float* const* tensors, const int64_t* numel, int n_tensors, std::string& err) {
-    const int L = g->L;
-    const int want = (g->enc ? 4 * NJ : 0) + 2 * L;
-    if (!tensors || !numel || n_tensors != want) {
-        err = "expected " + std::to_string(want) + " tensors in state-dict order (encoder: 84, then weight and bias of every dfnet.lin)";
-        return PNDF_ERR_BAD_SHAPE;
-    }
-    int t = 0;
-    for (int j = 0; g->enc && j < NJ; ++j) {
-        const int64_t sz[4] = {HID * enc_in(j), HID, FEAT * HID, FEAT};
-        for (int k = 0; k < 4; ++k, ++t)
-            if (!tensors[t] || numel[t] != sz[k]) { err = "encoder tensor missing or of the wrong size"; return PNDF_ERR_BAD_SHAPE; }
-    }
-    const float* const* lin = tensors + t;
-    const int64_t* ln = numel + t;
-    for (int l = 0; l < L; ++l) {
-        const int64_t in = g->cfg.dims[l], outw = g->cfg.dims[l + 1];
-        if (!lin[2 * l] || !lin[2 * l + 1] || ln[2 * l] != in * outw || ln[2 * l + 1] != outw) {
-            err = "dfnet.lin" + std::to_string(l) + " does not match the configured dims";
-            return PNDF_ERR_BAD_SHAPE;
-        }
-    }
+// `tensors`: a table that fits the network (pndf_table_fault of pndf_net_plan.h: pndf_load_weights has asked).  Stages the stream on the
+// host under a plan of its own, and writes that plan to the handle only after the copies succeeded; the caller keeps the handle
+// from launching in between.
+int pndf_generic_load(PndfGeneric* g, const float* const* tensors, std::string& err) {
+    const LayerNet& n = *g->net;
+    const int L = n.L;
+    const float* const* lin = tensors + (n.encoder ? 4 * NJ : 0);
     // precision f16x3 / f16: the trunk on split-precision fp16 MFMAs -- the weights of layer l travel as s_l W (pndf_pack::layer_scale).
-    // A layer without a finite non-zero weight cannot be scaled: such a network runs the exact fp32 kernels, whatever precision was asked for.
+    // A layer without a finite non-zero weight cannot be scaled: such a table runs on the exact fp32 kernels whatever precision was
+    // asked for, until a table that can be scaled is loaded (tests/test_depth.py, the all-zero layer).
     float wscale[PNDF_GEN_MAXLIN];
-    bool split = g->cfg.precision != PNDF_PREC_FP32;
-    for (int l = 0; l < L && split; ++l) split = pndf_pack::layer_scale(lin[2 * l], (int64_t)g->cfg.dims[l] * g->cfg.dims[l + 1], &wscale[l]);
-    gen_plan(g, split);
-    PndfGenericArgs& P = g->plan;
-    const size_t step_tiles = (size_t)P.w_slots * SLOT_TILES;
-    if (step_tiles + (size_t)GEN_STREAM_PAD_SLOTS * SLOT_TILES > g->enc_alloc_tiles) { err = "internal: stream larger than its allocation"; return PNDF_ERR_BAD_SHAPE; }
-    std::vector<float> stream((step_tiles + (size_t)GEN_STREAM_PAD_SLOTS * SLOT_TILES) * TILE_FLOATS, 0.f), lb(g->lbias_floats, 0.f), bias(BIAS_FLOATS, 0.f);
+    bool split = g->precision != PNDF_PREC_FP32;
+    for (int l = 0; l < L && split; ++l) split = pndf_pack::layer_scale(lin[2 * l], (int64_t)n.dims[l] * n.dims[l + 1], &wscale[l]);
+    GenPlan plan = gen_plan(n, split);
+    PndfGenericArgs& P = plan.args;
+    const size_t step_tiles = (size_t)P.w_slots * SLOT_TILES, pad_tiles = (size_t)pndf_pack::STREAM_PAD_SLOTS * SLOT_TILES;
+    if (step_tiles + pad_tiles > g->enc_alloc_tiles) { err = "internal: stream larger than its allocation"; return PNDF_ERR_BAD_SHAPE; }
+    std::vector<float> stream((step_tiles + pad_tiles) * TILE_FLOATS, 0.f), lb(plan.lbias_floats, 0.f), bias(BIAS_FLOATS, 0.f);
     float* const trunk = stream.data() + (size_t)ENC_TILES_PADDED * TILE_FLOATS;      // wf_off / wb_off count tiles from here
-    const bool sp_trunk = g->cfg.act == PNDF_ACT_SOFTPLUS;
+    const bool sp_trunk = n.act == PNDF_ACT_SOFTPLUS;
     for (int l = 0; l < L; ++l) {
-        const int in = g->cfg.dims[l], outw = g->cfg.dims[l + 1];
+        const int in = n.dims[l], outw = n.dims[l + 1];
         const pndf_pack::Mat F{lin[2 * l], outw, in, false}, T{lin[2 * l], outw, in, true};
         float* dst = trunk + (size_t)P.wf_off[l] * TILE_FLOATS;
         const int PT = GEN_PASS_GROUPS * NTB;                  // consumption order: [pass of <= 32 output tiles][k tile][tile of the pass]
@@ -1143,45 +1126,41 @@ int pndf_generic_load(PndfGeneric* g, const float* const* tensors, const int64_t
             for (int j = outw; j < 16 * P.ntp[l]; ++j) lb[P.b_off[l] + j] = -1.0e6f;
     }
     for (int l = 0; l < 8; ++l) bias[SCALE_OFF + l] = 1.0f;
-    if (g->enc) {
+    if (n.encoder) {
         pndf_pack::emit_encoder_biases(tensors, bias.data());
-        pndf_pack::emit_encoder_sections(tensors, stream.data(), stream.data() + ((size_t)ENC_TILES_PADDED + g->trunk_tiles) * TILE_FLOATS);
+        pndf_pack::emit_encoder_sections(tensors, stream.data(), stream.data() + ((size_t)ENC_TILES_PADDED + plan.trunk_tiles) * TILE_FLOATS);
     }
     // replica of the first slots behind the stream: the ring's fetch offset never wraps inside a step
-    memcpy(stream.data() + step_tiles * TILE_FLOATS, stream.data(), (size_t)GEN_STREAM_PAD_SLOTS * SLOT_TILES * TILE_FLOATS * sizeof(float));
+    memcpy(stream.data() + step_tiles * TILE_FLOATS, stream.data(), pad_tiles * TILE_FLOATS * sizeof(float));
     hipError_t e = hipDeviceSynchronize();      // no launch may still be reading the old weights
     if (e == hipSuccess) e = hipMemcpy(g->d_lb, lb.data(), lb.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(g->d_bias, bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(g->d_enc, stream.data(), stream.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e != hipSuccess) { err = std::string("pndf_load_weights (runtime-planned DFNet): ") + hipGetErrorString(e); return PNDF_ERR_HIP; }
-    g->have_weights = true;
+    g->plan = plan;
     return PNDF_OK;
 }
 
-const char* pndf_generic_kernel_name(const PndfGeneric* g) {
-    const char* name = "";
-    (void)gen_kernel(g->cfg, g->split, &name);
-    return name;
-}
+const char* pndf_generic_kernel_name(const PndfGeneric* g) { return gen_kernel(*g->net, g->plan.split).name; }
 
+// (the caller has checked that weights are loaded)
 int pndf_generic_launch(PndfGeneric* g, int mode, const float* q, const float* gout, float* qo, float* d, int64_t B, int steps,
                         void* stream, std::string& err, const pndf_project_options* popt) {
-    if (!g->have_weights) { err = "pndf_load_weights has not been called"; return PNDF_ERR_NO_WEIGHTS; }
-    PndfGenericArgs a = g->plan;
+    const LayerNet& n = *g->net;
+    PndfGenericArgs a = g->plan.args;
     a.q_in = q; a.q_out = qo; a.d_out = d; a.grad_out = gout;
     a.enc_stream = g->d_enc; a.bias = g->d_bias; a.wfwd = nullptr; a.wbwd = nullptr; a.lbias = g->d_lb; a.scratch = g->d_scratch;
     a.B = B; a.steps = steps;
     pndf_fill_step_options(a, mode, popt);
-    a.slope = (g->cfg.act == PNDF_ACT_LRELU) ? 0.01f : 0.0f;      // nn.LeakyReLU() default slope, net_modules.py:31
-    a.beta = g->cfg.beta;
-    a.enc_slope = (pndf_enc_act(g->cfg) == PNDF_ACT_LRELU) ? 0.01f : 0.0f;
-    a.enc_beta = pndf_enc_beta(g->cfg);
+    a.slope = (n.act == PNDF_ACT_LRELU) ? 0.01f : 0.0f;      // nn.LeakyReLU() default slope, net_modules.py:31
+    a.beta = n.beta;
+    a.enc_slope = (n.enc_act == PNDF_ACT_LRELU) ? 0.01f : 0.0f;
+    a.enc_beta = n.enc_beta;
     const int64_t nblocks = (B + WG_POSES - 1) / WG_POSES;
     const dim3 grid((unsigned)(nblocks < g->resident ? nblocks : g->resident)), block(WG_THREADS);
     hipError_t e = g->order.wait(stream);
     if (e == hipSuccess) {
-        const char* name = "";
-        hipLaunchKernelGGL(gen_kernel(g->cfg, g->split, &name), grid, block, LDS_TOTAL, (hipStream_t)stream, a);
+        hipLaunchKernelGGL(gen_kernel(n, g->plan.split).fn, grid, block, LDS_TOTAL, (hipStream_t)stream, a);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = g->order.record(stream);

@@ -1,13 +1,16 @@
-// The network as the host describes it, once for every unit that is assembled layer by layer (csrc/pndf_train.hip,
-// csrc/pndf_second_order.hip, csrc/pndf_skeleton.hip) and for the host twins of csrc/pndf_cpu.cpp: what a unit accepts of
-// pndf_config's num_joints / parent / dims / act / enc_act, how the encoder's activation and beta default to the trunk's, and
-// LayerNet, the plan a handle keeps -- the joint count and the parent table as run-time values, where bone j's tensors sit in the
-// packed encoder, the size of every tensor in state-dict order.  The units that stay 21-joint add that on top
-// (layer_network_refusal of pndf_bone.h); the fused kernels have the compile-time layout of pndf_layout.h.
+// The network as the host describes it, once for every handle that holds one -- the units assembled layer by layer
+// (csrc/pndf_train.hip, csrc/pndf_second_order.hip, csrc/pndf_skeleton.hip), the persistent engine (csrc/pndf_capi.hip and its
+// runtime-planned side, csrc/pndf_generic.hip) and the host twins of csrc/pndf_cpu.cpp: what the library accepts of pndf_config's
+// num_joints / parent / dims / act / enc_act, how the encoder's activation and beta default to the trunk's, LayerNet, the plan a
+// handle keeps -- the joint count and the parent table as run-time values, where bone j's tensors sit in the packed encoder, the
+// size of every tensor in state-dict order --, and pndf_table_fault, whether a weight table fits that plan.  The units that stay
+// 21-joint add that on top (layer_network_refusal of pndf_bone.h, pndf_skeleton_is_smpl); the fused kernels have the compile-time
+// layout of pndf_layout.h, which csrc/pndf_capi.hip holds to the limits below with static_asserts.
 // Plain C++: pndf_cpu.cpp is compiled without a device pass.
 #pragma once
 #include <stdint.h>
 
+#include <string>
 #include <vector>
 
 #include "../../include/posendf_amd.h"
@@ -30,11 +33,12 @@ inline const char* pndf_skeleton_refusal(const pndf_config* cfg) {
 }
 
 // is this the table of get_parent_mapping('smpl')?  (the units that stay 21-joint ask)
+constexpr int PNDF_SMPL_JOINTS = 21;
+constexpr int PNDF_SMPL_PARENT[PNDF_SMPL_JOINTS] = {-1, -1, -1, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19};
 inline bool pndf_skeleton_is_smpl(const pndf_config* cfg) {
-    constexpr int SMPL[21] = {-1, -1, -1, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19};
-    if (cfg->num_joints != 21) return false;
-    for (int j = 0; j < 21; ++j)
-        if (cfg->parent[j] != SMPL[j]) return false;
+    if (cfg->num_joints != PNDF_SMPL_JOINTS) return false;
+    for (int j = 0; j < PNDF_SMPL_JOINTS; ++j)
+        if (cfg->parent[j] != PNDF_SMPL_PARENT[j]) return false;
     return true;
 }
 
@@ -51,8 +55,8 @@ inline void pndf_skeleton_bone_sizes(int fin, int sizes[4]) {
 // output, relu / lrelu / softplus in the trunk and in the encoder (-1: the trunk's).  The text names the field.  Softplus betas
 // are each unit's own check.
 inline const char* pndf_dfnet_refusal(const pndf_config* cfg) {
-    if (cfg->n_dims < 3 || cfg->n_dims > PNDF_NET_MAX_LIN + 1) return "n_dims: a DFNet of 1 .. 7 hidden layers and the output layer (n_dims 3 .. 9)";
-    if (cfg->dims[cfg->n_dims - 1] != 1) return "dims: the DFNet must end in one output";
+    if (cfg->n_dims < 3 || cfg->n_dims > PNDF_NET_MAX_LIN + 1) return "DFNet depth: n_dims must be 3 .. 9 (1 .. 7 hidden layers + the output layer)";
+    if (cfg->dims[cfg->n_dims - 1] != 1) return "dims: in_dim, the hidden widths, then 1 -- the DFNet must end in one output";
     for (int i = 1; i < cfg->n_dims - 1; ++i)
         if (cfg->dims[i] < 1 || cfg->dims[i] > PNDF_NET_MAX_WIDTH) return "dims: hidden widths 1 .. 1024";
     if (cfg->act < PNDF_ACT_RELU || cfg->act > PNDF_ACT_SOFTPLUS) return "act: unknown activation (relu, lrelu or softplus)";
@@ -71,6 +75,8 @@ struct LayerNet {
     bool encoder = true;          // dims[0] = 6 nj; without it the trunk reads the 4 nj normalised components
     int L = 0;                    // linear layers of the trunk
     int dims[PNDF_NET_MAX_LIN + 1] = {};
+    int in(int l) const { return dims[l]; }          // dfnet.lin{l}: weight [out][in], bias [out]
+    int out(int l) const { return dims[l + 1]; }
     int act = 0, enc_act = 0;
     float beta = 100.f, enc_beta = 100.f;
     int parent[PNDF_SKEL_MAX_JOINTS] = {};
@@ -112,4 +118,37 @@ inline void layer_net_init(LayerNet& n, const pndf_config* cfg, int device) {
         n.numel.push_back((int64_t)n.dims[t + 1] * n.dims[t]);
         n.numel.push_back(n.dims[t + 1]);
     }
+}
+
+// Does a weight table -- `n_tensors` host tensors in state-dict order, tensor i of numel[i] floats -- fit the network?  The first
+// thing that is wrong, in the order below and then by tensor index, or FITS.  Every loader asks here and maps the answer to its
+// family's status code; a caller that has no sizes of its own (training, the second order) passes the plan's, and can only hear
+// NULL_TABLE or NULL_TENSOR.
+struct PndfTableFault {
+    enum Kind { FITS = 0, NULL_TABLE, COUNT, NULL_TENSOR, SIZE } kind = FITS;
+    int index = -1;                 // NULL_TENSOR, SIZE: the tensor
+    int64_t have = 0, want = 0;     // COUNT: tensors; SIZE: elements
+    explicit operator bool() const { return kind != FITS; }
+    std::string text() const {
+        switch (kind) {
+            case NULL_TABLE: return "tensors / numel is null";
+            case COUNT: return "tensor count: " + std::to_string(have) + ", expected " + std::to_string(want) + " in state-dict order";
+            case NULL_TENSOR: return "null tensor " + std::to_string(index);
+            case SIZE: return "tensor " + std::to_string(index) + " has " + std::to_string(have) + " elements, expected " + std::to_string(want);
+            default: return "";
+        }
+    }
+};
+inline PndfTableFault pndf_table_fault(const LayerNet& n, const float* const* tensors, const int64_t* numel, int n_tensors) {
+    if (!tensors || !numel) return {PndfTableFault::NULL_TABLE};
+    if (n_tensors != (int)n.numel.size()) return {PndfTableFault::COUNT, -1, n_tensors, (int64_t)n.numel.size()};
+    for (int i = 0; i < n_tensors; ++i) {
+        if (!tensors[i]) return {PndfTableFault::NULL_TENSOR, i};
+        if (numel[i] != n.numel[i]) return {PndfTableFault::SIZE, i, numel[i], n.numel[i]};
+    }
+    return {};
+}
+// a table that comes without sizes: 4 J + 2 L pointers, each taken to be of the plan's size
+inline PndfTableFault pndf_table_fault(const LayerNet& n, const float* const* tensors) {
+    return pndf_table_fault(n, tensors, n.numel.data(), (int)n.numel.size());
 }

@@ -12,6 +12,11 @@ namespace pndf_pack {
 using namespace pndf;
 #define PNDF_PACK_LOCAL __attribute__((visibility("hidden")))      // (not an export of the library)
 
+// Behind a step's stream sits a replica of its first slots, so that the ring's fetch offset never wraps inside a step: as many
+// slots as the ring fetches ahead (pndf_device.h: RING_SLOTS - 1; 5 covers the six-buffer experiment arm as well).
+constexpr int STREAM_PAD_SLOTS = 5;
+static_assert(STREAM_PAD_SLOTS >= PNDF_RING_SLOTS - 1, "the replica covers the ring's prefetch distance");
+
 struct Mat {          // logical matrix view M[r][c] of dfnet.lin{l}.weight, optionally transposed, zero padded
     const float* w;   // (out, in) row-major
     int out, in;

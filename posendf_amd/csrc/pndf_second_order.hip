@@ -310,7 +310,7 @@ extern "C" int pndf_second_order(pndf_so_handle h, const float* const* weights, 
         return pndf_fail(h, PNDF_ERR_BAD_ARG, "out and g must not alias q, v or each other");
     const SoLayout l = so_layout(h, B);
     if (const int rc = pndf_check_workspace(h, workspace, workspace_floats, l.total, "floats", "pndf_so_workspace_floats"); rc != PNDF_OK) return rc;
-    if (const int i = null_tensor(*h, weights); i >= 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null weight tensor " + std::to_string(i));
+    if (const PndfTableFault f = pndf_table_fault(*h, weights)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "weights: " + f.text());
     PndfRange range("pndf_second_order");
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");

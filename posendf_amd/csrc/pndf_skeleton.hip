@@ -324,15 +324,10 @@ extern "C" int pndf_skel_destroy(pndf_skel_handle h) {
 
 extern "C" int pndf_skel_load_weights(pndf_skel_handle h, const float* const* tensors, const int64_t* numel, int n_tensors) {
     if (!h) return PNDF_ERR_BAD_ARG;
-    if (!tensors || !numel) return pndf_fail(h, PNDF_ERR_BAD_ARG, "tensors / numel is null");
-    if (n_tensors != (int)h->numel.size())
-        return pndf_fail(h, PNDF_ERR_BAD_SHAPE, "tensor count: " + std::to_string(n_tensors) + ", expected " + std::to_string(h->numel.size()));
-    for (int i = 0; i < n_tensors; ++i) {
-        if (!tensors[i]) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null tensor " + std::to_string(i));
-        if (numel[i] != h->numel[i])
-            return pndf_fail(h, PNDF_ERR_BAD_SHAPE, "tensor " + std::to_string(i) + " has " + std::to_string(numel[i]) + " elements, expected " + std::to_string(h->numel[i]));
+    if (const PndfTableFault f = pndf_table_fault(*h, tensors, numel, n_tensors)) {      // a null pointer is an argument's fault here
+        const bool null = f.kind == PndfTableFault::NULL_TABLE || f.kind == PndfTableFault::NULL_TENSOR;
+        return pndf_fail(h, null ? PNDF_ERR_BAD_ARG : PNDF_ERR_BAD_SHAPE, f.text());
     }
-    h->have_weights = false;      // a failed load leaves no half-loaded plan behind
     std::vector<float> blob((size_t)h->blob_floats, 0.f);
     int i = 0;
     int64_t o = 0;
@@ -344,6 +339,7 @@ extern "C" int pndf_skel_load_weights(pndf_skel_handle h, const float* const* te
         memcpy(blob.data() + h->w_off[t], tensors[i], sizeof(float) * (size_t)numel[i]);
         memcpy(blob.data() + h->b_off[t], tensors[i + 1], sizeof(float) * (size_t)numel[i + 1]);
     }
+    h->have_weights = false;      // from here on a failure leaves no half-loaded plan behind
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     HIP_TRY(h, hipDeviceSynchronize());      // launches that still read the previous weights

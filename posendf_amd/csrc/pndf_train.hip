@@ -529,7 +529,7 @@ extern "C" int pndf_train_forward(pndf_train_handle h, const float* const* weigh
     if (B < 1 || Bm < 1) return pndf_fail(h, PNDF_ERR_BAD_ARG, "B and Bm must be >= 1");
     if (loss_type != LOSS_L1 && loss_type != LOSS_L2) return pndf_fail(h, PNDF_ERR_BAD_ARG, "loss_type: 0 (l1) or 1 (l2)");
     if (((uintptr_t)workspace & 15) != 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "workspace must be 16-byte aligned");
-    if (const int i = null_tensor(*h, weights); i >= 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null weight tensor " + std::to_string(i));
+    if (const PndfTableFault f = pndf_table_fault(*h, weights)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "weights: " + f.text());
     PndfRange range("pndf_train_forward");
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
@@ -600,8 +600,8 @@ extern "C" int pndf_train_backward(pndf_train_handle h, const float* const* weig
         if (it == h->shapes.end()) return pndf_fail(h, PNDF_ERR_BAD_ARG, "workspace was not filled by pndf_train_forward of this handle");
         s = it->second;
     }
-    if (const int i = null_tensor(*h, weights, grads); i >= 0)
-        return pndf_fail(h, PNDF_ERR_BAD_ARG, "null weight / gradient tensor " + std::to_string(i));
+    if (const PndfTableFault f = pndf_table_fault(*h, weights)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "weights: " + f.text());
+    if (const PndfTableFault f = pndf_table_fault(*h, grads)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "grads: " + f.text());
     PndfRange range("pndf_train_backward");
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");

@@ -1,7 +1,7 @@
-"""What the four creates that share csrc/pndf_net_plan.h refuse of a pndf_config (DESIGN.md sections 2s and 2j): pndf_train_create,
-pndf_so_create, pndf_skel_create and pndf_cpu_create against one table of configurations with a single fault each.  The status codes
-are literals, recorded from the library before the four checks were merged into pndf_skeleton_refusal / pndf_dfnet_refusal; a
-refusal leaves a text in the family's slot.  Runs without a GPU: a configuration is refused before the device is looked for, and a
+"""What the five creates that share csrc/pndf_net_plan.h refuse of a pndf_config (DESIGN.md sections 2s and 2j): pndf_train_create,
+pndf_so_create, pndf_skel_create, pndf_cpu_create and pndf_create against one table of configurations with a single fault each.  The
+status codes are literals, recorded from the library before each create's own checks were merged into pndf_skeleton_refusal /
+pndf_dfnet_refusal; a refusal leaves a text in the family's slot.  Runs without a GPU: a configuration is refused before the device is looked for, and a
 configuration a device unit accepts ends in PNDF_ERR_NO_DEVICE there."""
 import ctypes
 
@@ -11,7 +11,7 @@ import torch
 OK, BAD_ARG, UNSUPPORTED, NO_DEVICE = 0, -1, -4, -6
 ACCEPT = "accepted"      # the configuration passes: the device decides (a device unit), PNDF_OK (the host twin)
 
-CREATES = ("pndf_train_create", "pndf_so_create", "pndf_skel_create", "pndf_cpu_create")
+CREATES = ("pndf_train_create", "pndf_so_create", "pndf_skel_create", "pndf_cpu_create", "pndf_create")
 
 
 def _set(field, value):
@@ -39,24 +39,48 @@ def _softplus_beta_0(c):
     c.beta = 0.0
 
 
-# fault on configs/amass.yaml's lrelu network (21 joints, the encoder, eight linear layers) -> train, so, skel, cpu
+def _softplus_at(precision):
+    def fault(c):
+        c.act = 2
+        c.precision = precision
+    return fault
+
+
+def _softplus_encoder(beta):
+    """the trunk stays lrelu; the encoder's Softplus has no beta of its own and falls back to the trunk's"""
+    def fault(c):
+        c.enc_act = 2
+        c.enc_beta = 0.0
+        c.beta = beta
+    return fault
+
+
+# fault on configs/amass.yaml's lrelu network (21 joints, the encoder, eight linear layers) -> train, so, skel, cpu, the engine
 TABLE = (
-    ("n_dims 2", _set("n_dims", 2), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
-    ("n_dims 10", _ten_dims, (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
-    ("hidden width 0", _item("dims", 2, 0), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
-    ("hidden width 1025", _item("dims", 2, 1025), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
-    ("last dim 2", _item("dims", 7, 2), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
-    ("act -1", _set("act", -1), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
-    ("act 3", _set("act", 3), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
-    ("enc_act 3", _set("enc_act", 3), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
-    ("num_joints 0", _set("num_joints", 0), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
-    ("num_joints 33", _set("num_joints", 33), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
-    ("parent[4] = 4", _item("parent", 4, 4), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
-    ("parent[2] = -2", _item("parent", 2, -2), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
-    ("dims[0] = 100", _item("dims", 0, 100), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
-    ("no encoder", _item("dims", 0, 84), (UNSUPPORTED, UNSUPPORTED, ACCEPT, ACCEPT)),
-    ("20 joints", _twenty_joints, (UNSUPPORTED, UNSUPPORTED, ACCEPT, ACCEPT)),
-    ("softplus, beta 0", _softplus_beta_0, (ACCEPT, ACCEPT, UNSUPPORTED, BAD_ARG)),
+    ("n_dims 2", _set("n_dims", 2), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
+    ("n_dims 10", _ten_dims, (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
+    ("hidden width 0", _item("dims", 2, 0), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
+    ("hidden width 1025", _item("dims", 2, 1025), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
+    ("last dim 2", _item("dims", 7, 2), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
+    ("act -1", _set("act", -1), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
+    ("act 3", _set("act", 3), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
+    ("enc_act 3", _set("enc_act", 3), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
+    ("num_joints 0", _set("num_joints", 0), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
+    ("num_joints 33", _set("num_joints", 33), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
+    ("parent[4] = 4", _item("parent", 4, 4), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
+    ("parent[2] = -2", _item("parent", 2, -2), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
+    ("dims[0] = 100", _item("dims", 0, 100), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
+    ("no encoder", _item("dims", 0, 84), (UNSUPPORTED, UNSUPPORTED, ACCEPT, ACCEPT, ACCEPT)),
+    ("20 joints", _twenty_joints, (UNSUPPORTED, UNSUPPORTED, ACCEPT, ACCEPT, UNSUPPORTED)),
+    ("softplus, beta 0", _softplus_beta_0, (ACCEPT, ACCEPT, UNSUPPORTED, BAD_ARG, BAD_ARG)),
+    # precisions and the encoder's own activation: each unit's own rules on top of the shared ones
+    ("precision 7", _set("precision", 7), (ACCEPT, ACCEPT, UNSUPPORTED, ACCEPT, UNSUPPORTED)),
+    ("precision f16x3", _set("precision", 1), (ACCEPT, ACCEPT, UNSUPPORTED, ACCEPT, ACCEPT)),
+    ("softplus + precision f16", _softplus_at(2), (ACCEPT, ACCEPT, UNSUPPORTED, ACCEPT, UNSUPPORTED)),
+    ("softplus + precision bf16", _softplus_at(3), (ACCEPT, ACCEPT, UNSUPPORTED, ACCEPT, UNSUPPORTED)),
+    ("enc_act softplus, enc_beta 0, beta 0", _softplus_encoder(0.0), (ACCEPT, ACCEPT, UNSUPPORTED, BAD_ARG, BAD_ARG)),
+    ("enc_act softplus, enc_beta 0, beta 100", _softplus_encoder(100.0), (ACCEPT, ACCEPT, ACCEPT, ACCEPT, ACCEPT)),
+    ("enc_act -2", _set("enc_act", -2), (UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED, UNSUPPORTED)),
 )
 
 
