@@ -55,6 +55,14 @@ int pndf_debug_mem_probe(int device, double* out, int n_out);
  * seconds per pass in *sec_per_pass, may be NULL): tools/power_window.py --ring-only reads the package power under it. */
 int pndf_debug_ring_stream(int device, int passes, double* sec_per_pass);
 
+/* Test aid, host only (no device, no handle, no pndf_debug_bind): the operand scales the split-precision body-model kernels
+ * (PNDF_LBS_F16X3) would run with, from the one function that pndf_lbs_create and every launch call.  `blob`, `J`, `rel` as
+ * pndf_lbs_pack_host wrote them for `V` vertices; w_temp, w_data = the weights over the means of the two terms, i.e.
+ * temp_coef / ((T - 1) V) and data_coef / (T num_joints) of pndf_lbs_terms_grad_w.  out[13]: the power-of-two scales p_scale,
+ * w_scale, a_scale, g_scale, x_scale, then the bounds they come from: max |P|, max |W|, max_v sum_j |W|, the bound of |v_posed|,
+ * of |A|, of |T_R^T d L / d verts| and of |d L / d verts (x) [v_posed, 1]|, then the pose feature's constant scale. */
+int pndf_debug_lbs_scales(int32_t V, const float* blob, const float* J, const float* rel, float w_temp, float w_data, float* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,12 +136,13 @@ def lbs_vjp(model, cache, g_verts, g_joints, dtype=np.float64):
 
 
 # ---------------------------------------------------------------- experiments/motion_denoise.py:86-94, restated
-def body_terms(theta, joints0, model, it, dtype=np.float64, coefs=None):
+def body_terms(theta, joints0, model, it, dtype=np.float64, coefs=None, keep=False):
     """ONE sequence theta [T,69]: the unweighted temporal and data terms and the gradient of their WEIGHTED sum
     10 (1 + it) temp + [it > 0] 100 / (1 + it) data  with respect to theta (motion_denoise.py:29-45,86-94).
     `coefs` = (temp weight, data weight) replaces that schedule (experiments/partial_observation.py:31-32).  Like the
     reference there is no epsilon under the square roots: two identical consecutive vertices (or a joint that has not
-    moved, which is why the reference skips the data term at it = 0, :92) give a NaN gradient."""
+    moved, which is why the reference skips the data term at it = 0, :92) give a NaN gradient.
+    keep=True also returns the intermediates: lbs()'s cache with `gV`, `gJ` (d L / d verts, d L / d joints of the two terms)."""
     theta = np.asarray(theta, dtype).reshape(-1, 69)
     T = theta.shape[0]
     verts, joints, cache = lbs(theta, model, dtype, keep=True)
@@ -162,4 +163,6 @@ def body_terms(theta, joints0, model, it, dtype=np.float64, coefs=None):
         terms["data"] = nrm.mean(dtype=dtype)
         with np.errstate(divide="ignore", invalid="ignore"):
             gJ += diff / nrm * (dtype(100.0 / (1 + it) if coefs is None else coefs[1]) / dtype(nrm.size))
+    if keep:
+        return lbs_vjp(model, cache, gV, gJ, dtype), terms, dict(cache, gV=gV, gJ=gJ)
     return lbs_vjp(model, cache, gV, gJ, dtype), terms

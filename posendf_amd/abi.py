@@ -160,6 +160,7 @@ HEADERS = {
         "pndf_debug_timing_layout": (c_int, [c_int]),
         "pndf_debug_mem_probe": (c_int, [c_int, _P, c_int]),
         "pndf_debug_ring_stream": (c_int, [c_int, c_int, _P]),
+        "pndf_debug_lbs_scales": (c_int, [c_int32, _P, _P, _P, c_float, c_float, _P]),
     },
     "posendf_amd_completion.h": {      # pose completion
         "pndf_complete_step": (c_int, [_P, _P, _P, _P, c_int64, POINTER(ProjectOptions), _H]),

@@ -10,7 +10,11 @@ takes the dict, `from_arrays` keyword arguments, `from_npz` a converted model fi
 
 `precision` selects the arithmetic of the forward and fused-terms passes: "f16x3" (default; fp16 MFMAs on operands split
 into hi + lo halves, fp32 accumulate: the distance engine's split arithmetic, fp32-class accuracy) or "fp32" (fp32 MFMAs);
-the general reverse pass behind autograd always runs on fp32.
+the general reverse pass behind autograd always runs on fp32.  "f16x3" scales its operands by powers of two chosen from
+a-priori bounds of the model and the term weights (csrc/pndf_lbs_scales.h); they are tested for SMPL-like models whose
+length unit is anything from kilometres to millimetres (template x 1e-3 .. 1e3, tests/test_lbs_range*.py).  Rotation and
+translation entries of the joint transforms share one scale, so a model far outside that range (extent below ~1e-2 or above
+~1e4 length units) should use "fp32".
 
 `forward` is differentiable with respect to `pose_body` (first order, through `pndf_lbs_backward`); the betas and the global
 orientation are constants, as in the reference's optimisation (motion_denoise.py:27,67; root_orient=None).  There is no CPU

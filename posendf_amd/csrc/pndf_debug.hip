@@ -12,6 +12,7 @@
 #include "../../include/posendf_amd_debug.h"
 #include "pndf_args.h"
 #include "pndf_layout.h"
+#include "pndf_lbs_scales.h"
 
 extern "C" __global__ void pndf_fused_split_relu_kernel_timing(PndfKernelArgs args);
 extern "C" __global__ void pndf_fused_split_softplus_kernel_timing(PndfKernelArgs args);
@@ -101,6 +102,19 @@ extern "C" int pndf_debug_project_timing(pndf_handle h, const float* q_in, float
                                                      : (const void*)pndf_fused_relu_kernel_timing;
     if ((rc = allow_lds(h, k, ds.lds)) != PNDF_OK) return rc;
     return g_launch(h, MODE_PROJECT, q_in, nullptr, q_out, nullptr, B, steps, (float*)cycles, stream, k);
+}
+
+// Host only: the operand scales the split-precision body-model kernels would run with (csrc/pndf_lbs_scales.h: the function
+// pndf_lbs_create and every launch call) and the bounds behind them.
+extern "C" int pndf_debug_lbs_scales(int32_t V, const float* blob, const float* J, const float* rel, float w_temp, float w_data, float* out) {
+    if (V < 1 || !blob || !J || !rel || !out) return PNDF_ERR_BAD_ARG;
+    PndfLbsScales s;
+    pndf_lbs_select_scales(s, blob, (V + PNDF_LBS_GV - 1) / PNDF_LBS_GV, J, rel, 0.f, 0.f);      // as pndf_lbs_create
+    pndf_lbs_select_scales(s, nullptr, 0, nullptr, nullptr, w_temp, w_data);                     // as a launch
+    const float v[PNDF_LBS_SCALES_FLOATS] = {s.p_scale, s.w_scale, s.a_scale, s.g_scale, s.x_scale, s.max_p, s.max_w,
+                                             s.w_rowsum, s.vp_bound, s.a_bound, s.g_bound, s.x_bound, s.pf_scale};
+    for (int i = 0; i < PNDF_LBS_SCALES_FLOATS; ++i) out[i] = v[i];
+    return PNDF_OK;
 }
 
 // the experiment words of this library's translation units (csrc/pndf_experiment.h): 0 in a product build

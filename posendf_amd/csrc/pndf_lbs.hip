@@ -49,6 +49,7 @@
 #include "../../include/posendf_amd.h"
 #include "pndf_args.h"
 #include "pndf_host.h"
+#include "pndf_lbs_scales.h"
 #include "pndf_lbs_split.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -769,7 +770,8 @@ extern "C" __global__ void __launch_bounds__(256) pndf_lbs_rodrigues_vjp_kernel(
 // engine's f16x3 kernels (pndf_kernel_split.hip).  Operands are scaled by powers of two so that they sit high in the fp16
 // range without leaving it: the model's by the packer (p_scale, w_scale from the largest |entry|), the pose feature by 2^12
 // (|R - I| <= 2), the joint transforms by a_scale (from the skeleton's extent), the reverse operands by g_scale / x_scale
-// from a-priori bounds the host derives from the term weights (|d L / d verts| <= 2 w_temp + w_data) and the model.
+// from a-priori bounds the host derives from the term weights (|d L / d verts| <= 2 w_temp + w_data) and the model: all of
+// them in pndf_lbs_scales.h (pndf_lbs_select_scales), held against the fp64 oracle's operands by tests/test_lbs_range.py.
 // Per (16 vertex x 16 frame) tile: 63 + 36 MFMAs forward, 65 + 48 reverse = 3,392 matrix-pipe cycles against 15,360.
 //   * ONE copy of the model in LDS serves both contractions (pndf_lbs_split.h): planes [row][16 v] of halfs; the reverse
 //     pass (contraction over vertices) reads 4 v of a row per lane, the forward pass (contraction over rows) gets its
@@ -1366,9 +1368,7 @@ struct pndf_lbs_model {
     void* d_sblob = nullptr;          // the model for the split-precision kernels (pndf_lbs_split.h)
     float* d_picked = nullptr;        // [NE][PICK_FLOATS]: the vertex-picked joints' own rows of the model (joints-only forward)
     int precision = PNDF_LBS_F16X3;   // forward and fused-terms passes; the general reverse pass is always fp32
-    float p_scale = 1.f, w_scale = 1.f, a_scale = 1.f;      // powers of two: model and joint-transform operands
-    float w_rowsum = 1.f;             // max_v sum_j |W[v, j]|                        (bounds |T_R^T g|)
-    float vp_bound = 1.f;             // max_v,c |v_shaped| + 2 sum_k |posedirs|      (bounds |v_posed|)
+    PndfLbsScales scales;             // operand scales of the split-precision kernels and their bounds (pndf_lbs_scales.h)
     bool smpl_tree = false;           // the kinematic tree is SMPL's own: per-frame kernels with the tree as a compile-time table
     PndfLbsModel consts;
     int sm_count = 256;
@@ -1397,13 +1397,6 @@ static float f16_to_f32(uint16_t h) {
     const int e = (h >> 10) & 31, m = h & 1023;
     const float v = (e == 0) ? std::ldexp((float)m, -24) : std::ldexp((float)(m | 1024), e - 25);
     return (h & 0x8000u) ? -v : v;
-}
-// power of two s with bound * s in [2^13, 2^14): the operand's hi half cannot overflow (65504), and values down to 2^-16 of
-// the bound keep a normal lo half.  Clamped: a zero bound must not turn into an infinite factor.
-static float lbs_scale_for(float bound) {
-    if (!(bound > 1e-30f)) bound = 1e-30f;
-    if (bound > 1e30f) bound = 1e30f;
-    return std::ldexp(1.0f, 13 - std::ilogb(bound));
 }
 
 // the split-precision model from the fp32 one (same [row][16 v] order inside a plane)
@@ -1497,35 +1490,6 @@ extern "C" int pndf_lbs_pack_host(int32_t V, int32_t NB, const float* v_template
     return PNDF_OK;
 }
 
-// operand scales of the split-precision model (powers of two, from the largest |entry|: [2^12, 2^13)) and the bounds the
-// host derives the reverse operand scales from
-struct LbsSplitScales { float p_scale, w_scale, w_rowsum, vp_bound; };
-static LbsSplitScales lbs_split_scales(const float* blob, int NG) {
-    float maxP = 0.f, maxW = 0.f, rowsum = 0.f, vpb = 0.f;
-    for (int grp = 0; grp < NG; ++grp) {
-        const float* b = blob + (size_t)grp * BLOB;
-        for (int vi = 0; vi < GV; ++vi) {
-            float ws = 0.f;
-            for (int j = 0; j < NJ; ++j) {
-                const float w = std::fabs(b[PNDF_LBS_BLOB_W + j * GV + vi]);
-                ws += w;
-                maxW = std::fmax(maxW, w);
-            }
-            rowsum = std::fmax(rowsum, ws);
-            for (int c = 0; c < 3; ++c) {
-                float ps = 0.f;
-                for (int k = 0; k < PF; ++k) {
-                    const float pv = std::fabs(b[PNDF_LBS_BLOB_P + c * C_STRIDE + k * GV + vi]);
-                    ps += pv;
-                    maxP = std::fmax(maxP, pv);
-                }
-                vpb = std::fmax(vpb, std::fabs(b[PNDF_LBS_BLOB_VS + c * GV + vi]) + 2.0f * ps);      // |R - I| <= 2
-            }
-        }
-    }
-    return LbsSplitScales{lbs_scale_for(maxP) * 0.5f, lbs_scale_for(maxW) * 0.5f, std::fmax(rowsum, 1e-6f), std::fmax(vpb, 1.0f)};
-}
-
 extern "C" int64_t pndf_lbs_packed_split_bytes(int32_t V) { return V < 1 ? 0 : (int64_t)((V + GV - 1) / GV) * PNDF_LBS_SB_BYTES; }
 
 // Host-only: the split-precision model (what pndf_lbs_create uploads for PNDF_LBS_F16X3) from the fp32 one of
@@ -1533,7 +1497,9 @@ extern "C" int64_t pndf_lbs_packed_split_bytes(int32_t V) { return V < 1 ? 0 : (
 extern "C" int pndf_lbs_pack_split_host(int32_t V, const float* blob, void* sblob, float* scales_out) {
     if (V < 1 || !blob || !sblob) return PNDF_ERR_BAD_ARG;
     const int NG = (V + GV - 1) / GV;
-    const LbsSplitScales sc = lbs_split_scales(blob, NG);
+    PndfLbsScales sc;      // (p_scale and w_scale depend on the blob alone: no rest joints needed)
+    const float no_joints[NJ * 3] = {};
+    pndf_lbs_select_scales(sc, blob, NG, no_joints, no_joints, 0.f, 0.f);
     lbs_pack_split(blob, NG, sc.p_scale, sc.w_scale, (uint8_t*)sblob);
     if (scales_out) { scales_out[0] = sc.p_scale; scales_out[1] = sc.w_scale; }
     return PNDF_OK;
@@ -1593,20 +1559,10 @@ extern "C" int pndf_lbs_create(pndf_lbs_handle* out, int32_t V, int32_t NB, cons
     hipError_t e = hipMalloc((void**)&h->d_blob, blob.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(h->d_blob, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice);
     {
-        // operand scales and bounds of the split-precision kernels, from the packed model
-        const LbsSplitScales sc = lbs_split_scales(blob.data(), NG);
-        float extent = 0.f, maxJ = 0.f;      // |G_t[j]| <= sum of the bone lengths, |A_t| <= |G_t| + |J|
-        for (int j = 0; j < NJ; ++j) {
-            extent += std::sqrt(rel[3 * j] * rel[3 * j] + rel[3 * j + 1] * rel[3 * j + 1] + rel[3 * j + 2] * rel[3 * j + 2]);
-            maxJ = std::fmax(maxJ, std::sqrt(J[3 * j] * J[3 * j] + J[3 * j + 1] * J[3 * j + 1] + J[3 * j + 2] * J[3 * j + 2]));
-        }
-        h->p_scale = sc.p_scale;
-        h->w_scale = sc.w_scale;
-        h->a_scale = lbs_scale_for(std::fmax(1.0f, extent + maxJ)) * 0.5f;
-        h->w_rowsum = sc.w_rowsum;
-        h->vp_bound = sc.vp_bound;
+        // operand scales and bounds of the split-precision kernels, from the packed model (the model's part: pndf_lbs_scales.h)
+        pndf_lbs_select_scales(h->scales, blob.data(), NG, J, rel, 0.f, 0.f);
         std::vector<uint8_t> sblob((size_t)NG * PNDF_LBS_SB_BYTES);
-        lbs_pack_split(blob.data(), NG, h->p_scale, h->w_scale, sblob.data());
+        lbs_pack_split(blob.data(), NG, h->scales.p_scale, h->scales.w_scale, sblob.data());
         if (e == hipSuccess) e = hipMalloc(&h->d_sblob, sblob.size());
         if (e == hipSuccess) e = hipMemcpy(h->d_sblob, sblob.data(), sblob.size(), hipMemcpyHostToDevice);
         const int lds_s = 3 * PNDF_LBS_SB_BYTES;
@@ -1723,18 +1679,18 @@ static int lbs_launch(pndf_lbs_model* h, int mode, PndfLbsArgs& a, void* workspa
     if (mode == 0) a.vsplit = split ? (h->NG < 8 ? h->NG : 8) : 1;      // (forward: the vertex ranges are independent outputs)
     if (split) {
         const dim3 sgrid((unsigned)(vgrid.x * (unsigned)a.vsplit));
-        // operand scales (powers of two) from a-priori bounds: |d L / d verts| <= 2 w_temp + w_data per component (two pairs
-        // share a vertex; the data term touches the picked vertices), |T_R^T g| <= 3 max_v sum_j |W| |g|, |v_posed| <= vp_bound
-        const float gb = 2.0f * std::fabs(a.w_temp) + std::fabs(a.w_data);
+        // the reverse operands' scales from this launch's term weights (the weights' part: pndf_lbs_scales.h)
+        PndfLbsScales sc = h->scales;
+        pndf_lbs_select_scales(sc, nullptr, h->NG, nullptr, nullptr, a.w_temp, a.w_data);
         sa.base = a;
         sa.sblob = h->d_sblob;
-        sa.a_scale = h->a_scale;
-        sa.off_true = 1.0f / (h->p_scale * PNDF_LBS_PF_SCALE);
-        sa.tm_true = 1.0f / (h->w_scale * h->a_scale);
-        sa.g_scale = lbs_scale_for(3.0f * h->w_rowsum * gb);
-        sa.x_scale = lbs_scale_for(gb * h->vp_bound);
-        sa.gpf_true = (1.0f / h->p_scale) / sa.g_scale;
-        sa.gA_true = (1.0f / h->w_scale) / sa.x_scale;
+        sa.a_scale = sc.a_scale;
+        sa.off_true = 1.0f / (sc.p_scale * PNDF_LBS_PF_SCALE);
+        sa.tm_true = 1.0f / (sc.w_scale * sc.a_scale);
+        sa.g_scale = sc.g_scale;
+        sa.x_scale = sc.x_scale;
+        sa.gpf_true = (1.0f / sc.p_scale) / sa.g_scale;
+        sa.gA_true = (1.0f / sc.w_scale) / sa.x_scale;
         const int lds_s = 3 * PNDF_LBS_SB_BYTES;
         if (h->smpl_tree) hipLaunchKernelGGL(pndf_lbs_pose_split_smpl_kernel, fgrid, fblock, 0, (hipStream_t)stream, sa);
         else hipLaunchKernelGGL(pndf_lbs_pose_split_kernel, fgrid, fblock, 0, (hipStream_t)stream, sa);
