@@ -21,26 +21,27 @@
 // forward and fused-terms passes -- fp16 MFMAs on operands split into hi + lo halves (PNDF_LBS_F16X3, "split precision" below:
 // 212 MFMAs of 16 cycles per tile instead of 480 of 32).
 //
-// Three stages (fp32 form; the split-precision vertex kernels are described at their section):
+// Four stages (fp32 form; the split-precision vertex kernels are described at their section):
 //   pndf_lbs_pose_kernel            one thread per frame: Rodrigues, transform chain -> pose feature, A, posed joints
 //                                   (_smpl_: SMPL's own tree as a compile-time table -- arrays in registers, no scratch)
-//   pndf_lbs_vertex_kernel<MODE>    one wave per chunk of 16 frames, four chunks per workgroup sharing the model stream:
+//   pndf_lbs_vertex_{forward,terms,reverse}_kernel (lbs_vertex_body<MODE>)
+//                                   one wave per chunk of 16 frames, four chunks per workgroup sharing the model stream:
 //       the packed model ("blob": 42 KiB per 16 vertices, lane-linear MFMA tiles) is streamed global -> LDS by DMA into
 //       three buffers (the loop is software-pipelined one group deep), and read TWICE from LDS: as A operand of the forward pose-blend contraction (rows = vertices) and,
 //       with a transposed conflict-free ds_read_b128, as A operand of the reverse contraction (rows = pose-feature entries).
 //       MODE 0: vertices / vertex-picked joints out.  MODE 1: the two weighted terms of motion_denoise.py:86-94 formed in
 //       registers (neighbouring frames are neighbouring lanes) and pushed straight back: d L / d pose_feature and
 //       d L / d A accumulate in registers over all vertices.  MODE 2: general reverse pass for given d L / d verts.
+//   pndf_lbs_reduce_partials_kernel sums the partial results of MODE 1 / 2 in a fixed order, value-major for the last stage
 //   pndf_lbs_pose_backward_kernel   one thread per frame: reverse of the transform chain and of Rodrigues -> d L / d theta
 //                                   (SMPL's tree: pndf_lbs_pose_backward_smpl_kernel + pndf_lbs_rodrigues_vjp_kernel)
 // In MODE 1 a chunk is 16 frames = 15 pairs; consecutive chunks share a frame, whose two partial results ("halo") are summed
-// by the last kernel.  Small problems split the vertex range over blockIdx.y (`vsplit`) and sum the partials there too, in
-// a fixed order: results are deterministic.
+// by the reduce kernel.  Small problems split the vertex range over blockIdx.y (`vsplit`); their partials are summed there
+// too, in a fixed order: results are deterministic.  (Joints alone: pndf_lbs_joints_only_kernel, one launch.)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 
-#include <cmath>
 #include <string>
 #include <type_traits>
 #include <utility>
@@ -49,18 +50,17 @@
 #include "../../include/posendf_amd.h"
 #include "pndf_args.h"
 #include "pndf_host.h"
-#include "pndf_lbs_scales.h"
-#include "pndf_lbs_split.h"
+#include "pndf_lbs_pack.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
+using namespace pndf_lbs;      // NJ, PF, GV, BLOB, C_STRIDE, PICK_FLOATS and the host packers (pndf_lbs_pack.h)
+
 namespace {
 
-constexpr int NJ = PNDF_LBS_J, PF = PNDF_LBS_PF, GV = PNDF_LBS_GV, BLOB = PNDF_LBS_BLOB_FLOATS;
 constexpr int KS = PF / 4;                 // 52 k-steps of the pose-blend contraction
 constexpr int KT = PF / 16;                // 13 row tiles of d L / d pose_feature
-constexpr int C_STRIDE = PF * GV;          // floats per component of P in a blob (3328)
 constexpr int A_FLOATS = 12 * 32;          // d L / d A per frame: [12 entries][32 joints (24 used)]
 
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
@@ -226,7 +226,6 @@ extern "C" __global__ void __launch_bounds__(64) pndf_lbs_pose_smpl_kernel(PndfL
 // groups through the vertex kernel, 6.6 ms for 153,600 frames -- to read 21 of them is waste: one thread per frame does the
 // kinematic chain and then skins the picked vertices alone, from a small table made at create time (per picked vertex:
 // shaped template [3] | skinning weights [24] | pose blend shapes [207][3]; uniform addresses: scalar loads).  fp32 on the VALU.
-constexpr int PICK_FLOATS = 3 + NJ + 3 * 9 * (NJ - 1);
 template <class Tree>
 __device__ __forceinline__ void lbs_joints_only_body(const PndfLbsArgs& a, const float* __restrict__ picked) {
     // v_posed of the picked vertices between the two passes: [x * 3 + c][thread] (one column per thread: conflict-free)
@@ -587,13 +586,9 @@ __device__ __forceinline__ void lbs_pose_backward_body(const PndfLbsArgs& a) {
     const long long N = (long long)a.S * a.T;
     const long long n = (long long)blockIdx.x * 64 + threadIdx.x;
     if (n >= N) return;
-    const int T = a.T, s = (int)(n / T), t = (int)(n - (long long)s * T), njt = NJ + a.NE;
-    const int nch = a.S * a.cps;
+    const int njt = NJ + a.NE;
     float R[NJ][9], GR[NJ][9], Gt[NJ][3];
     frame_transforms<Tree>(a.theta + n * 69, a.model, R, GR, Gt);
-    // the frame a chunk of pairs shares with the next chunk got a second partial result there
-    const bool halo = a.halo_pf && t > 0 && t % 15 == 0 && t / 15 < a.cps;
-    const long long hidx = (long long)s * a.cps + t / 15 - 1;
     // (summed over vertex ranges and halos by pndf_lbs_reduce_partials_kernel: value-major, one line per wave and load)
     auto sum_pf = [&](int k) __attribute__((always_inline)) { return a.red[(size_t)k * N + n]; };
     auto sum_A = [&](int e, int j) __attribute__((always_inline)) { return a.red[(size_t)(RED_PF + e * NJ + j) * N + n]; };
@@ -667,16 +662,13 @@ extern "C" __global__ void __launch_bounds__(64) pndf_lbs_pose_backward_smpl_ker
     const long long N = (long long)a.S * a.T;
     const long long n = (long long)blockIdx.x * 64 + threadIdx.x;
     if (n >= N) return;
-    const int T = a.T, s = (int)(n / T), t = (int)(n - (long long)s * T), njt = NJ + a.NE;
-    const int nch = a.S * a.cps;
+    const int njt = NJ + a.NE;
     float GR[NJ][9], Gt[NJ][3];
     {
         float R[NJ][9];
         frame_transforms<SmplTree>(a.theta + n * 69, a.model, R, GR, Gt);
     }
-    const bool halo = a.halo_pf && t > 0 && t % 15 == 0 && t / 15 < a.cps;
-    const long long hidx = (long long)s * a.cps + t / 15 - 1;
-    // partial results of joint i, summed over the vertex ranges (and the chunk that shares this frame) in a fixed order
+    // partial results of joint i, as pndf_lbs_reduce_partials_kernel summed them over the vertex ranges and halos
     auto gather = [&](int i, float (&sA)[12], float (&sP)[9]) __attribute__((always_inline)) {
 #pragma unroll
         for (int e = 0; e < 12; ++e) sA[e] = a.red[(size_t)(RED_PF + e * NJ + i) * N + n];
@@ -784,7 +776,6 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
@@ -806,13 +797,6 @@ __device__ __forceinline__ void lbs_split2(float a, float b, unsigned& hi, unsig
     asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t"
         "v_fma_mixhi_f16 %0, %1, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=&v"(l) : "v"(hp), "v"(a), "v"(b));
     lo = l;
-}
-__device__ __forceinline__ void lbs_split4(const f32x4& v, f16x4& hi, f16x4& lo) {
-    unsigned h0, l0, h1, l1;
-    lbs_split2(v[0], v[1], h0, l0);
-    lbs_split2(v[2], v[3], h1, l1);
-    hi = __builtin_bit_cast(f16x4, u32x2{h0, h1});
-    lo = __builtin_bit_cast(f16x4, u32x2{l0, l1});
 }
 __device__ __forceinline__ f16x8 cat(f16x4 a, f16x4 b) { return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7); }
 // (static_for: see the top of the file -- `#pragma unroll` leaves the 99-trip loop over the forward MFMAs rolled)
@@ -1360,7 +1344,7 @@ __device__ __forceinline__ void lbs_vertex_split_body(const PndfLbsSplitArgs& sa
 extern "C" __global__ void __launch_bounds__(256, 1) pndf_lbs_vertex_split_forward_kernel(PndfLbsSplitArgs a) { lbs_vertex_split_body<0>(a); }
 extern "C" __global__ void __launch_bounds__(256, 1) pndf_lbs_vertex_split_terms_kernel(PndfLbsSplitArgs a) { lbs_vertex_split_body<1>(a); }
 
-// ------------------------------------------------------------------------------------------ host: handle, packing, launches
+// ------------------------------------------------------------------------------------------ host: handle, launch table, launches
 struct pndf_lbs_model {
     int device = 0;
     int V = 0, NG = 0, NE = 0;
@@ -1373,136 +1357,49 @@ struct pndf_lbs_model {
     PndfLbsModel consts;
     int sm_count = 256;
     std::string err;
+    ~pndf_lbs_model() {               // the one owner of the device buffers: a failed create and pndf_lbs_destroy end here
+        DeviceGuard guard(device);
+        for (void* p : {(void*)d_blob, d_sblob, (void*)d_picked}) (void)hipFree(p);      // (a null pointer: no-op)
+    }
 };
 
-// fp32 -> fp16 bits, round to nearest even (host side of the split: any hi + lo = x decomposition serves the kernels)
-static uint16_t f32_to_f16(float f) {
-    uint32_t x;
-    memcpy(&x, &f, 4);
-    const uint16_t sign = (uint16_t)((x >> 16) & 0x8000u);
-    x &= 0x7fffffffu;
-    if (x > 0x7f800000u) return (uint16_t)(sign | 0x7e00u);
-    if (x >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);                          // >= 65520: inf
-    if (x < 0x38800000u) {                                                            // below 2^-14: subnormal, units of 2^-24
-        float af;
-        memcpy(&af, &x, 4);
-        return (uint16_t)(sign | (uint16_t)std::nearbyint((double)af * 16777216.0));
-    }
-    uint32_t h = (((x >> 23) - 112u) << 10) | ((x & 0x7fffffu) >> 13);
-    const uint32_t rem = x & 0x1fffu;
-    if (rem > 0x1000u || (rem == 0x1000u && (h & 1u))) ++h;                           // (a carry runs into the exponent)
-    return (uint16_t)(sign | h);
-}
-static float f16_to_f32(uint16_t h) {
-    const int e = (h >> 10) & 31, m = h & 1023;
-    const float v = (e == 0) ? std::ldexp((float)m, -24) : std::ldexp((float)(m | 1024), e - 25);
-    return (h & 0x8000u) ? -v : v;
-}
-
-// the split-precision model from the fp32 one (same [row][16 v] order inside a plane)
-static void lbs_pack_split(const float* blob, int NG, float p_scale, float w_scale, uint8_t* out) {
-    memset(out, 0, (size_t)NG * PNDF_LBS_SB_BYTES);
-    for (int grp = 0; grp < NG; ++grp) {
-        const float* b = blob + (size_t)grp * BLOB;
-        uint8_t* o = out + (size_t)grp * PNDF_LBS_SB_BYTES;
-        auto put = [&](int hi_off, int lo_off, int row, int vi, float x) {
-            const uint16_t h = f32_to_f16(x);
-            const uint16_t l = f32_to_f16(x - f16_to_f32(h));
-            memcpy(o + hi_off + pndf_lbs_sb_at(row, vi), &h, 2);
-            memcpy(o + lo_off + pndf_lbs_sb_at(row, vi), &l, 2);
-        };
-        for (int c = 0; c < 3; ++c)
-            for (int k = 0; k < PF; ++k)
-                for (int vi = 0; vi < GV; ++vi)
-                    put(PNDF_LBS_SB_PH + c * PNDF_LBS_SB_PLANE, PNDF_LBS_SB_PL + c * PNDF_LBS_SB_PLANE, k, vi,
-                        b[PNDF_LBS_BLOB_P + c * C_STRIDE + k * GV + vi] * p_scale);
-        for (int j = 0; j < 32; ++j)
-            for (int vi = 0; vi < GV; ++vi)
-                put(PNDF_LBS_SB_WH, PNDF_LBS_SB_WL, j, vi, b[PNDF_LBS_BLOB_W + j * GV + vi] * w_scale);
-        memcpy(o + PNDF_LBS_SB_VS, b + PNDF_LBS_BLOB_VS, 3 * GV * 4);
-        memcpy(o + PNDF_LBS_SB_FL, b + PNDF_LBS_BLOB_FL, GV * 4);
-    }
+// What a launch does.  The arithmetic is the handle's precision, except that the general reverse pass always runs on fp32.
+enum LbsMode { LBS_FORWARD = 0, LBS_TERMS = 1, LBS_REVERSE = 2 };
+struct LbsArith {
+    const void* pose[2];       // per-frame forward kernel: [generic tree, SMPL tree]
+    const void* vertex[3];     // vertex kernel by LbsMode; null: the arithmetic has none
+    int lds;                   // dynamic LDS bytes of the vertex kernels (three buffers of one vertex group)
+    bool flat;                 // vertex grid: quads x vsplit on x (the kernel takes them apart), or (quads, vsplit)
+};
+static const LbsArith LBS_ARITH[2] = {      // [PNDF_LBS_FP32, PNDF_LBS_F16X3]
+    {{(const void*)pndf_lbs_pose_kernel, (const void*)pndf_lbs_pose_smpl_kernel},
+     {(const void*)pndf_lbs_vertex_forward_kernel, (const void*)pndf_lbs_vertex_terms_kernel, (const void*)pndf_lbs_vertex_reverse_kernel},
+     3 * BLOB * (int)sizeof(float), false},
+    {{(const void*)pndf_lbs_pose_split_kernel, (const void*)pndf_lbs_pose_split_smpl_kernel},
+     {(const void*)pndf_lbs_vertex_split_forward_kernel, (const void*)pndf_lbs_vertex_split_terms_kernel, nullptr},
+     3 * PNDF_LBS_SB_BYTES, true}};
+// one kernel on the one argument struct its arithmetic takes (a failure stays with the runtime for pndf_check_launch)
+static void lbs_run(const void* kernel, dim3 grid, dim3 block, int lds, void* arg, void* stream) {
+    void* args[] = {arg};
+    (void)hipLaunchKernel(kernel, grid, block, args, (size_t)lds, (hipStream_t)stream);
 }
 
 extern "C" const char* pndf_lbs_last_error(pndf_lbs_handle h) { return pndf_last_error_of(h); }
 
 extern "C" int64_t pndf_lbs_packed_floats(int32_t V) { return V < 1 ? 0 : (int64_t)((V + GV - 1) / GV) * BLOB; }
 
-// Host-only packer (needs no device): the model in MFMA tile order + the rest joints.  `J_out` (72 floats) and `rel_out`
-// (72 floats) may be null.  Returns 0 or a negative pndf_status.
 extern "C" int pndf_lbs_pack_host(int32_t V, int32_t NB, const float* v_template, const float* shapedirs, const float* betas,
                                   const float* posedirs, const float* J_regressor, const int32_t* parents,
                                   const float* lbs_weights, const int32_t* extra_joint_vertex, int32_t n_extra, float* blob,
                                   float* J_out, float* rel_out) {
-    if (V < 1 || NB < 0 || !v_template || !posedirs || !J_regressor || !parents || !lbs_weights || !blob) return PNDF_ERR_BAD_ARG;
-    if (NB > 0 && (!shapedirs || !betas)) return PNDF_ERR_BAD_ARG;
-    if (n_extra < 0 || n_extra > PNDF_LBS_MAX_EXTRA || (n_extra > 0 && !extra_joint_vertex)) return PNDF_ERR_BAD_ARG;
-    if (parents[0] >= 0) return PNDF_ERR_UNSUPPORTED;
-    for (int j = 1; j < NJ; ++j)
-        if (parents[j] < 0 || parents[j] >= j) return PNDF_ERR_UNSUPPORTED;      // parents precede their children (SMPL)
-    for (int e = 0; e < n_extra; ++e)
-        if (extra_joint_vertex[e] < 0 || extra_joint_vertex[e] >= V) return PNDF_ERR_BAD_ARG;
-    // v_shaped = v_template + blend_shapes(betas, shapedirs); J = J_regressor v_shaped   (smplx lbs(), first two steps)
-    std::vector<float> vsh((size_t)V * 3);
-    for (int i = 0; i < V * 3; ++i) {
-        double acc = v_template[i];
-        for (int l = 0; l < NB; ++l) acc += (double)shapedirs[(size_t)i * NB + l] * betas[l];
-        vsh[i] = (float)acc;
-    }
-    float J[NJ][3];
-    for (int j = 0; j < NJ; ++j)
-        for (int e = 0; e < 3; ++e) {
-            double acc = 0.0;
-            for (int v = 0; v < V; ++v) acc += (double)J_regressor[(size_t)j * V + v] * vsh[(size_t)v * 3 + e];
-            J[j][e] = (float)acc;
-        }
-    for (int j = 0; j < NJ; ++j)
-        for (int e = 0; e < 3; ++e) {
-            if (J_out) J_out[3 * j + e] = J[j][e];
-            if (rel_out) rel_out[3 * j + e] = (j == 0) ? J[j][e] : J[j][e] - J[parents[j]][e];
-        }
-    const int NG = (V + GV - 1) / GV;
-    std::vector<int> flag((size_t)NG * GV, -2);
-    for (int v = 0; v < V; ++v) flag[v] = -1;
-    // The vertex kernels find a vertex-picked joint through this per-vertex flag, i.e. one joint per vertex: a vertex named
-    // twice would leave the earlier joint's row unwritten (smplx's VertexJointSelector is an index_select and would serve
-    // both).  SMPL's own table has no duplicates; anything else is refused rather than half served.
-    for (int e = 0; e < n_extra; ++e) {
-        if (flag[extra_joint_vertex[e]] >= 0) return PNDF_ERR_BAD_ARG;
-        flag[extra_joint_vertex[e]] = e;
-    }
-    memset(blob, 0, (size_t)NG * BLOB * sizeof(float));
-    const int npf = 9 * (NJ - 1);
-    for (int grp = 0; grp < NG; ++grp) {
-        float* b = blob + (size_t)grp * BLOB;
-        for (int vi = 0; vi < GV; ++vi) {
-            const int v = grp * GV + vi;
-            ((int*)(b + PNDF_LBS_BLOB_FL))[vi] = flag[(size_t)grp * GV + vi];
-            if (v >= V) continue;
-            for (int c = 0; c < 3; ++c) {
-                for (int k = 0; k < npf; ++k)
-                    b[PNDF_LBS_BLOB_P + c * C_STRIDE + k * GV + vi] = posedirs[(size_t)k * V * 3 + (size_t)v * 3 + c];
-                b[PNDF_LBS_BLOB_VS + c * GV + vi] = vsh[(size_t)v * 3 + c];
-            }
-            for (int j = 0; j < NJ; ++j) b[PNDF_LBS_BLOB_W + j * GV + vi] = lbs_weights[(size_t)v * NJ + j];
-        }
-    }
-    return PNDF_OK;
+    return lbs_pack(V, NB, v_template, shapedirs, betas, posedirs, J_regressor, parents, lbs_weights, extra_joint_vertex, n_extra,
+                    blob, J_out, rel_out);
 }
 
 extern "C" int64_t pndf_lbs_packed_split_bytes(int32_t V) { return V < 1 ? 0 : (int64_t)((V + GV - 1) / GV) * PNDF_LBS_SB_BYTES; }
 
-// Host-only: the split-precision model (what pndf_lbs_create uploads for PNDF_LBS_F16X3) from the fp32 one of
-// pndf_lbs_pack_host.  scales_out (may be null): p_scale, w_scale.
 extern "C" int pndf_lbs_pack_split_host(int32_t V, const float* blob, void* sblob, float* scales_out) {
-    if (V < 1 || !blob || !sblob) return PNDF_ERR_BAD_ARG;
-    const int NG = (V + GV - 1) / GV;
-    PndfLbsScales sc;      // (p_scale and w_scale depend on the blob alone: no rest joints needed)
-    const float no_joints[NJ * 3] = {};
-    pndf_lbs_select_scales(sc, blob, NG, no_joints, no_joints, 0.f, 0.f);
-    lbs_pack_split(blob, NG, sc.p_scale, sc.w_scale, (uint8_t*)sblob);
-    if (scales_out) { scales_out[0] = sc.p_scale; scales_out[1] = sc.w_scale; }
-    return PNDF_OK;
+    return lbs_pack_split_host(V, blob, sblob, scales_out);
 }
 
 extern "C" int pndf_lbs_create(pndf_lbs_handle* out, int32_t V, int32_t NB, const float* v_template, const float* shapedirs,
@@ -1513,87 +1410,54 @@ extern "C" int pndf_lbs_create(pndf_lbs_handle* out, int32_t V, int32_t NB, cons
     if (V < 1) return pndf_fail<pndf_lbs_model>(nullptr, PNDF_ERR_BAD_ARG, "V < 1");
     const PndfDeviceCheck dev = pndf_check_gfx950(device, "the body model");
     if (dev.code != PNDF_OK) return pndf_fail<pndf_lbs_model>(nullptr, dev.code, dev.text);
-    const hipDeviceProp_t& prop = dev.prop;
+    // all host work before the first device call: packed model, its picked rows, the model's part of the scales, split model
     const int NG = (V + GV - 1) / GV;
     std::vector<float> blob((size_t)NG * BLOB);
     float J[NJ * 3], rel[NJ * 3];
-    const int rc = pndf_lbs_pack_host(V, NB, v_template, shapedirs, betas, posedirs, J_regressor, parents, lbs_weights,
-                                      extra_joint_vertex, n_extra, blob.data(), J, rel);
+    const int rc = lbs_pack(V, NB, v_template, shapedirs, betas, posedirs, J_regressor, parents, lbs_weights, extra_joint_vertex,
+                            n_extra, blob.data(), J, rel);
     if (rc == PNDF_ERR_UNSUPPORTED)
         return pndf_fail<pndf_lbs_model>(nullptr, rc, "kinematic tree: 24 joints, parents[0] = -1 and every parent before its children (SMPL)");
     if (rc != PNDF_OK) return pndf_fail<pndf_lbs_model>(nullptr, rc, "null pointer, or an extra-joint vertex outside [0, V) or named twice, or more than 32 of them");
+    std::vector<float> pk((size_t)n_extra * PICK_FLOATS);      // (n_extra: 0 .. 32 from here on)
+    lbs_picked_table(blob.data(), extra_joint_vertex, n_extra, pk.data());
+    PndfLbsScales scales;
+    pndf_lbs_select_scales(scales, blob.data(), NG, J, rel, 0.f, 0.f);
+    std::vector<uint8_t> sblob((size_t)NG * PNDF_LBS_SB_BYTES);
+    lbs_pack_split(blob.data(), NG, scales.p_scale, scales.w_scale, sblob.data());
     DeviceGuard guard(device);
     if (!guard.ok) return pndf_fail<pndf_lbs_model>(nullptr, PNDF_ERR_HIP, "hipSetDevice failed");
     pndf_lbs_model* h = new pndf_lbs_model();
     h->device = device; h->V = V; h->NG = NG; h->NE = n_extra;
-    h->sm_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    h->sm_count = dev.prop.multiProcessorCount > 0 ? dev.prop.multiProcessorCount : 256;
+    h->scales = scales;
     memcpy(h->consts.J, J, sizeof(J));
     memcpy(h->consts.rel, rel, sizeof(rel));
-    if (n_extra > 0) {
-        std::vector<float> pk((size_t)n_extra * PICK_FLOATS);
-        const int npf = 9 * (NJ - 1);
-        for (int x = 0; x < n_extra; ++x) {
-            const int v = extra_joint_vertex[x];
-            float* P = pk.data() + (size_t)x * PICK_FLOATS;
-            for (int c = 0; c < 3; ++c) {
-                double acc = v_template[(size_t)v * 3 + c];
-                for (int l = 0; l < NB; ++l) acc += (double)shapedirs[((size_t)v * 3 + c) * NB + l] * betas[l];
-                P[c] = (float)acc;
-            }
-            for (int j = 0; j < NJ; ++j) P[3 + j] = lbs_weights[(size_t)v * NJ + j];
-            for (int k = 0; k < npf; ++k)
-                for (int c = 0; c < 3; ++c) P[3 + NJ + 3 * k + c] = posedirs[(size_t)k * V * 3 + (size_t)v * 3 + c];
-        }
-        if (hipMalloc((void**)&h->d_picked, pk.size() * sizeof(float)) != hipSuccess ||
-            hipMemcpy(h->d_picked, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-            if (h->d_picked) (void)hipFree(h->d_picked);
-            delete h;
-            return pndf_fail<pndf_lbs_model>(nullptr, PNDF_ERR_HIP, "pndf_lbs_create: picked-joint table");
-        }
-    }
     h->smpl_tree = true;
     for (int j = 0; j < NJ; ++j) {
         h->consts.parent[j] = parents[j];
         h->smpl_tree = h->smpl_tree && (j == 0 || parents[j] == SmplTree::tab[j]);
     }
-    hipError_t e = hipMalloc((void**)&h->d_blob, blob.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(h->d_blob, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice);
-    {
-        // operand scales and bounds of the split-precision kernels, from the packed model (the model's part: pndf_lbs_scales.h)
-        pndf_lbs_select_scales(h->scales, blob.data(), NG, J, rel, 0.f, 0.f);
-        std::vector<uint8_t> sblob((size_t)NG * PNDF_LBS_SB_BYTES);
-        lbs_pack_split(blob.data(), NG, h->scales.p_scale, h->scales.w_scale, sblob.data());
-        if (e == hipSuccess) e = hipMalloc(&h->d_sblob, sblob.size());
-        if (e == hipSuccess) e = hipMemcpy(h->d_sblob, sblob.data(), sblob.size(), hipMemcpyHostToDevice);
-        const int lds_s = 3 * PNDF_LBS_SB_BYTES;
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)pndf_lbs_vertex_split_forward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_s);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)pndf_lbs_vertex_split_terms_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_s);
-    }
-    const int lds = 3 * BLOB * (int)sizeof(float);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)pndf_lbs_vertex_forward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)pndf_lbs_vertex_terms_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)pndf_lbs_vertex_reverse_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipError_t e = hipSuccess;
+    auto upload = [&e](auto** dst, const void* src, size_t bytes) {      // (no picked vertex: no table)
+        if (e == hipSuccess && bytes) e = hipMalloc((void**)dst, bytes);
+        if (e == hipSuccess && bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+    };
+    upload(&h->d_picked, pk.data(), pk.size() * sizeof(float));
+    upload(&h->d_blob, blob.data(), blob.size() * sizeof(float));
+    upload(&h->d_sblob, sblob.data(), sblob.size());
+    for (const LbsArith& ar : LBS_ARITH)
+        for (const void* k : ar.vertex)
+            if (k && e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, ar.lds);
     if (e != hipSuccess) {
-        const std::string m = std::string("pndf_lbs_create: ") + hipGetErrorString(e);
-        if (h->d_blob) (void)hipFree(h->d_blob);
-        if (h->d_sblob) (void)hipFree(h->d_sblob);
-        if (h->d_picked) (void)hipFree(h->d_picked);
         delete h;
-        return pndf_fail<pndf_lbs_model>(nullptr, PNDF_ERR_HIP, m);
+        return pndf_fail<pndf_lbs_model>(nullptr, PNDF_ERR_HIP, std::string("pndf_lbs_create: ") + hipGetErrorString(e));
     }
     *out = h;
     return PNDF_OK;
 }
 
-extern "C" int pndf_lbs_destroy(pndf_lbs_handle h) {
-    if (!h) return PNDF_OK;
-    DeviceGuard guard(h->device);
-    if (h->d_blob) (void)hipFree(h->d_blob);
-    if (h->d_sblob) (void)hipFree(h->d_sblob);
-    if (h->d_picked) (void)hipFree(h->d_picked);
-    delete h;
-    return PNDF_OK;
-}
+extern "C" int pndf_lbs_destroy(pndf_lbs_handle h) { delete h; return PNDF_OK; }
 
 extern "C" int pndf_lbs_set_precision(pndf_lbs_handle h, int32_t precision) {
     if (!h) return PNDF_ERR_BAD_ARG;
@@ -1625,10 +1489,10 @@ static int lbs_vsplit(const pndf_lbs_model* h, int nch) {
 }
 
 // workspace layout (floats): pfp | Ap | Gt | gpf | gA | halo_pf | halo_A   (sized for the fused-terms mode, the largest)
-static int64_t lbs_workspace(const pndf_lbs_model* h, int64_t S, int64_t T, PndfLbsArgs* a, float* base, int mode,
+static int64_t lbs_workspace(const pndf_lbs_model* h, int64_t S, int64_t T, PndfLbsArgs* a, float* base, LbsMode mode,
                              PndfLbsSplitArgs* sa = nullptr) {
     const int64_t N = S * T;
-    const int cps = (mode == 1) ? chunks_pairs((int)T) : chunks_fwd((int)T);
+    const int cps = (mode == LBS_TERMS) ? chunks_pairs((int)T) : chunks_fwd((int)T);
     const int64_t nch = S * cps;
     const int vsplit = lbs_vsplit(h, (int)nch);
     int64_t off = 0;
@@ -1645,7 +1509,7 @@ static int64_t lbs_workspace(const pndf_lbs_model* h, int64_t S, int64_t T, Pndf
     float* Aps = take(N * (PNDF_LBS_APS_HALFS / 2));
     if (a) {
         a->pfp = pfp; a->Ap = Ap; a->Gt = Gt; a->gpf = gpf; a->gA = gA; a->red = red;
-        a->halo_pf = (mode == 1) ? hpf : nullptr; a->halo_A = (mode == 1) ? hA : nullptr;
+        a->halo_pf = (mode == LBS_TERMS) ? hpf : nullptr; a->halo_A = (mode == LBS_TERMS) ? hA : nullptr;
         a->cps = cps; a->vsplit = vsplit;
     }
     if (sa) { sa->pfs = pfs; sa->Aps = Aps; }
@@ -1654,31 +1518,31 @@ static int64_t lbs_workspace(const pndf_lbs_model* h, int64_t S, int64_t T, Pndf
 
 extern "C" int64_t pndf_lbs_workspace_floats(pndf_lbs_handle h, int32_t S, int32_t T) {
     if (!h || S < 1 || T < 1) return 0;
-    const int64_t a = lbs_workspace(h, S, T, nullptr, nullptr, 1), b = lbs_workspace(h, S, T, nullptr, nullptr, 2);
+    const int64_t a = lbs_workspace(h, S, T, nullptr, nullptr, LBS_TERMS), b = lbs_workspace(h, S, T, nullptr, nullptr, LBS_REVERSE);
     return a > b ? a : b;
 }
 
-static int lbs_launch(pndf_lbs_model* h, int mode, PndfLbsArgs& a, void* workspace, void* stream) {
+static int lbs_launch(pndf_lbs_model* h, LbsMode mode, PndfLbsArgs& a, void* workspace, void* stream) {
     if (((uintptr_t)workspace) & 15) return pndf_fail(h, PNDF_ERR_BAD_ARG, "workspace must be 16-byte aligned");
     a.blob = h->d_blob; a.V = h->V; a.NG = h->NG; a.NE = h->NE; a.model = h->consts;
-    const bool split = h->precision == PNDF_LBS_F16X3 && mode != 2;
-    PndfLbsSplitArgs sa;
-    memset(&sa, 0, sizeof(sa));
+    const bool split = h->precision == PNDF_LBS_F16X3 && mode != LBS_REVERSE;
+    const LbsArith& ar = LBS_ARITH[split];
+    PndfLbsSplitArgs sa = {};
     (void)lbs_workspace(h, a.S, a.T, &a, (float*)workspace, mode, &sa);
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     const long long N = (long long)a.S * a.T;
     const dim3 fgrid((unsigned)((N + 63) / 64)), fblock(64);
-    if (mode == 0 && !a.verts && a.joints) {      // joints only: the chain + the picked vertices alone (lbs_joints_only_body)
+    if (mode == LBS_FORWARD && !a.verts && a.joints) {      // joints only: the chain + the picked vertices alone (lbs_joints_only_body)
         if (h->smpl_tree) hipLaunchKernelGGL(pndf_lbs_joints_only_smpl_kernel, fgrid, fblock, 0, (hipStream_t)stream, a, (const float*)h->d_picked);
         else hipLaunchKernelGGL(pndf_lbs_joints_only_kernel, fgrid, fblock, 0, (hipStream_t)stream, a, (const float*)h->d_picked);
         return pndf_check_launch(h, "launch");
     }
-    const dim3 vgrid((unsigned)(((long long)a.S * a.cps + 3) / 4), (unsigned)(mode == 0 ? 1 : a.vsplit)), vblock(256);
-    const int lds = 3 * BLOB * (int)sizeof(float);
-    if (mode == 0) a.vsplit = split ? (h->NG < 8 ? h->NG : 8) : 1;      // (forward: the vertex ranges are independent outputs)
+    if (mode == LBS_FORWARD) a.vsplit = split ? (h->NG < 8 ? h->NG : 8) : 1;      // (forward: the vertex ranges are independent outputs)
+    const unsigned quads = (unsigned)(((long long)a.S * a.cps + 3) / 4);
+    const dim3 vgrid = ar.flat ? dim3(quads * (unsigned)a.vsplit) : dim3(quads, (unsigned)a.vsplit), vblock(256);
+    void* arg = &a;
     if (split) {
-        const dim3 sgrid((unsigned)(vgrid.x * (unsigned)a.vsplit));
         // the reverse operands' scales from this launch's term weights (the weights' part: pndf_lbs_scales.h)
         PndfLbsScales sc = h->scales;
         pndf_lbs_select_scales(sc, nullptr, h->NG, nullptr, nullptr, a.w_temp, a.w_data);
@@ -1691,40 +1555,19 @@ static int lbs_launch(pndf_lbs_model* h, int mode, PndfLbsArgs& a, void* workspa
         sa.x_scale = sc.x_scale;
         sa.gpf_true = (1.0f / sc.p_scale) / sa.g_scale;
         sa.gA_true = (1.0f / sc.w_scale) / sa.x_scale;
-        const int lds_s = 3 * PNDF_LBS_SB_BYTES;
-        if (h->smpl_tree) hipLaunchKernelGGL(pndf_lbs_pose_split_smpl_kernel, fgrid, fblock, 0, (hipStream_t)stream, sa);
-        else hipLaunchKernelGGL(pndf_lbs_pose_split_kernel, fgrid, fblock, 0, (hipStream_t)stream, sa);
-        if (mode == 0) {
-            if (a.verts || (a.joints && a.NE > 0))
-                hipLaunchKernelGGL(pndf_lbs_vertex_split_forward_kernel, sgrid, vblock, lds_s, (hipStream_t)stream, sa);
-        } else {
-            hipLaunchKernelGGL(pndf_lbs_vertex_split_terms_kernel, sgrid, vblock, lds_s, (hipStream_t)stream, sa);
-            hipLaunchKernelGGL(pndf_lbs_reduce_partials_kernel, dim3((unsigned)((N + 63) / 64), (unsigned)((RED_ROWS + 63) / 64)), dim3(256), 0, (hipStream_t)stream, a);
-            if (h->smpl_tree) {
-                hipLaunchKernelGGL(pndf_lbs_pose_backward_smpl_kernel, fgrid, fblock, 0, (hipStream_t)stream, a);
-                hipLaunchKernelGGL(pndf_lbs_rodrigues_vjp_kernel, dim3((unsigned)((N * (NJ - 1) + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-            } else hipLaunchKernelGGL(pndf_lbs_pose_backward_kernel, fgrid, fblock, 0, (hipStream_t)stream, a);
-        }
-        return pndf_check_launch(h, "launch");
+        arg = &sa;
     }
-    if (h->smpl_tree) hipLaunchKernelGGL(pndf_lbs_pose_smpl_kernel, fgrid, fblock, 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(pndf_lbs_pose_kernel, fgrid, fblock, 0, (hipStream_t)stream, a);
-    if (mode == 0) {
-        if (a.verts || (a.joints && a.NE > 0))
-            hipLaunchKernelGGL(pndf_lbs_vertex_forward_kernel, vgrid, vblock, lds, (hipStream_t)stream, a);
-    } else {
-        if (mode == 1) hipLaunchKernelGGL(pndf_lbs_vertex_terms_kernel, vgrid, vblock, lds, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL(pndf_lbs_vertex_reverse_kernel, vgrid, vblock, lds, (hipStream_t)stream, a);
-        hipLaunchKernelGGL(pndf_lbs_reduce_partials_kernel, dim3((unsigned)((N + 63) / 64), (unsigned)((RED_ROWS + 63) / 64)), dim3(256), 0, (hipStream_t)stream, a);
+    lbs_run(ar.pose[h->smpl_tree], fgrid, fblock, 0, arg, stream);
+    if (mode != LBS_FORWARD || a.verts || (a.joints && a.NE > 0)) lbs_run(ar.vertex[mode], vgrid, vblock, ar.lds, arg, stream);
+    if (mode != LBS_FORWARD) {      // the reverse tail, on fp32 partial results whatever the arithmetic
+        lbs_run((const void*)pndf_lbs_reduce_partials_kernel, dim3((unsigned)((N + 63) / 64), (unsigned)((RED_ROWS + 63) / 64)), dim3(256), 0, &a, stream);
         if (h->smpl_tree) {
-            hipLaunchKernelGGL(pndf_lbs_pose_backward_smpl_kernel, fgrid, fblock, 0, (hipStream_t)stream, a);
-            hipLaunchKernelGGL(pndf_lbs_rodrigues_vjp_kernel, dim3((unsigned)((N * (NJ - 1) + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-        } else hipLaunchKernelGGL(pndf_lbs_pose_backward_kernel, fgrid, fblock, 0, (hipStream_t)stream, a);
+            lbs_run((const void*)pndf_lbs_pose_backward_smpl_kernel, fgrid, fblock, 0, &a, stream);
+            lbs_run((const void*)pndf_lbs_rodrigues_vjp_kernel, dim3((unsigned)((N * (NJ - 1) + 255) / 256)), dim3(256), 0, &a, stream);
+        } else lbs_run((const void*)pndf_lbs_pose_backward_kernel, fgrid, fblock, 0, &a, stream);
     }
     return pndf_check_launch(h, "launch");
 }
-
-static void lbs_clear(PndfLbsArgs& a) { memset(&a, 0, sizeof(a)); }
 
 extern "C" int pndf_lbs_forward(pndf_lbs_handle h, const float* theta, int64_t N, float* verts, float* joints, void* workspace,
                                 void* stream) {
@@ -1733,10 +1576,9 @@ extern "C" int pndf_lbs_forward(pndf_lbs_handle h, const float* theta, int64_t N
     if (N < 0 || N > 0x7fffffff) return pndf_fail(h, PNDF_ERR_BAD_ARG, "bad frame count");
     if (N == 0) return PNDF_OK;
     if (!theta || !workspace || (!verts && !joints)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pointer");
-    PndfLbsArgs a;
-    lbs_clear(a);
+    PndfLbsArgs a = {};
     a.theta = theta; a.verts = verts; a.joints = joints; a.S = 1; a.T = (int)N;
-    return lbs_launch(h, 0, a, workspace, stream);
+    return lbs_launch(h, LBS_FORWARD, a, workspace, stream);
 }
 
 extern "C" int pndf_lbs_terms_grad_w(pndf_lbs_handle h, const float* theta, const float* joints0, int32_t S, int32_t T,
@@ -1747,13 +1589,12 @@ extern "C" int pndf_lbs_terms_grad_w(pndf_lbs_handle h, const float* theta, cons
     if (S == 0 || T == 0) return PNDF_OK;
     const bool data = data_coef != 0.f;
     if (!theta || !g_theta || !workspace || (data && !joints0)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pointer");
-    PndfLbsArgs a;
-    lbs_clear(a);
+    PndfLbsArgs a = {};
     a.theta = theta; a.joints0 = joints0; a.g_theta = g_theta; a.S = S; a.T = T; a.it_gt0 = data ? 1 : 0;
     // the weights over the means of motion_denoise.py:89,94
     a.w_temp = T > 1 ? temp_coef / ((float)(T - 1) * (float)h->V) : 0.f;
     a.w_data = data ? data_coef / ((float)T * (float)(NJ + h->NE)) : 0.f;
-    return lbs_launch(h, 1, a, workspace, stream);
+    return lbs_launch(h, LBS_TERMS, a, workspace, stream);
 }
 
 extern "C" int pndf_lbs_terms_grad(pndf_lbs_handle h, const float* theta, const float* joints0, int32_t S, int32_t T, int32_t it,
@@ -1772,10 +1613,9 @@ extern "C" int pndf_lbs_backward(pndf_lbs_handle h, const float* theta, const fl
     if (N < 0 || N > 0x7fffffff) return pndf_fail(h, PNDF_ERR_BAD_ARG, "bad frame count");
     if (N == 0) return PNDF_OK;
     if (!theta || !g_theta || !workspace) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pointer");
-    PndfLbsArgs a;
-    lbs_clear(a);
+    PndfLbsArgs a = {};
     a.theta = theta; a.g_verts = g_verts; a.g_joints = g_joints; a.g_theta = g_theta; a.S = 1; a.T = (int)N;
-    return lbs_launch(h, 2, a, workspace, stream);
+    return lbs_launch(h, LBS_REVERSE, a, workspace, stream);
 }
 
 PNDF_EXPORT_EXPERIMENT_WORD(lbs)

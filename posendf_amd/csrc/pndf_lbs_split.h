@@ -17,9 +17,10 @@
 // (g, p) -> row p, quad g: rows 0 .. 15 x quads {0, 1} | {2, 3}) and the transposed reads (lane m of lane group g -> row
 // 4 g + m / 4, quad m % 4: rows 0 .. 7 | 8 .. 15 x all quads).  With the plain row-major order the row reads of rows r and
 // r + 8 collide: 7 conflict cycles per LDS instruction measured (SQ_LDS_BANK_CONFLICT 4.3e9 -> 5e7 per launch).
-__host__ __device__ constexpr int pndf_lbs_sb_unit(int r, int q) { return 32 * (r / 8) + 4 * (r % 8) + (q ^ (2 * (r / 8))); }
+// (constexpr: callable from host and device code alike, and from a plain C++ compiler -- pndf_lbs_pack.h)
+constexpr int pndf_lbs_sb_unit(int r, int q) { return 32 * (r / 8) + 4 * (r % 8) + (q ^ (2 * (r / 8))); }
 // byte offset of (row, vertex) inside a plane
-__host__ __device__ constexpr int pndf_lbs_sb_at(int row, int v) {
+constexpr int pndf_lbs_sb_at(int row, int v) {
     return (row / 16) * 512 + 8 * pndf_lbs_sb_unit(row % 16, v / 4) + 2 * (v % 4);
 }
 constexpr int PNDF_LBS_KP = 224;                                               // 7 k-blocks of 32
