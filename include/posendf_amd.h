@@ -154,6 +154,36 @@ typedef struct {
     uint64_t reserved;           /* must be 0 */
 } pndf_project_options2;         /* 32 bytes */
 
+/* The options with tracks: pose interpolation inside the projection step, for any joint tree.  With frames = T >= 2 the B poses are
+ * B / T tracks of T consecutive frames (include/posendf_amd_interpolation.h states the semantics for the 21 joints; here J joints):
+ *   fill PNDF_TRACK_GIVEN : q_in is the track; frames 0 and T-1 of every track are copied bit for bit;
+ *   fill PNDF_TRACK_SLERP / _NLERP: only frames 0 (a) and T-1 (b) of every track are read from q_in; frame T-1 of the result is b with
+ *                           every joint quaternion negated where <a, b> < 0, the frames between them the interpolation of each joint;
+ *   step                  : the end frames and the joints of `observed` keep their bits (the integer select of the mask); every other
+ *                           joint quaternion descends as above, then takes lambda (0.5 (N- + N+) - Q) with N-, N+ the joint in the two
+ *                           neighbour frames of the step's INPUT iterate, each negated where its dot product with Q is negative, then
+ *                           renorm / flip / tol as above.  A step is out of place (a Jacobi update): q_out must not overlap q_in.
+ * steps == 0 returns the fill (or the copy) and zeroes d_last; d_last keeps its meaning.  With frames == 0 (then lambda must be 0 and
+ * fill PNDF_TRACK_GIVEN) the call is the one with the 32-byte struct, bit for bit; with lambda == 0 and PNDF_TRACK_GIVEN it is that call
+ * with all ones in the words of the end frames, bit for bit.  Fill it with
+ *   pndf_project_options3 o;  pndf_default_project_options(&o.base2.base);  o.base2.base.struct_size = sizeof o;  o.base2.observed = mask;
+ *   o.base2.reserved = 0;  o.frames = T;  o.lambda = 0.5f;  o.fill = PNDF_TRACK_SLERP;  o.reserved2 = 0;
+ * and pass (const pndf_project_options*)&o.  Exactly two entry points take it, the two that take a pndf_project_options2:
+ * pndf_skel_project of posendf_amd_skeleton.h and pndf_project_ex_cpu below (any handle: the 21-joint table and the encoder-less
+ * model too); every other function with a pndf_project_options parameter keeps refusing a struct_size other than sizeof(pndf_project_options).
+ * PNDF_ERR_BAD_ARG with a text that names the field, before anything is launched or written: a struct_size that is none of the
+ * three sizes, reserved2 != 0, frames of 1, negative or above 16,384, B % frames != 0, a lambda outside [0, 1] or NaN, an unknown
+ * fill, frames == 0 with a non-zero lambda or another fill than PNDF_TRACK_GIVEN, frames > 0 with q_out overlapping q_in, and what is
+ * refused in `base2`. */
+enum { PNDF_TRACK_GIVEN = 0, PNDF_TRACK_SLERP = 1, PNDF_TRACK_NLERP = 2 };
+typedef struct {
+    pndf_project_options2 base2; /* base2.base.struct_size = sizeof(pndf_project_options3); mask and reserved as before */
+    int32_t frames;              /* T: 0 = no tracks; else 2 .. 16384 and B % T == 0 */
+    float   lambda;              /* neighbour coupling, in [0, 1] */
+    int32_t fill;                /* PNDF_TRACK_* */
+    int32_t reserved2;           /* must be 0 */
+} pndf_project_options3;         /* 48 bytes */
+
 /* pndf_project with step options.  opt == NULL means the defaults, and with the defaults the call is pndf_project bit for
  * bit.  PNDF_ERR_BAD_ARG (text in pndf_last_error; nothing is launched or written) for a struct_size other than
  * sizeof(pndf_project_options), a step_size that is not finite or <= 0, a tol that is NaN or < 0, an unknown renorm mode.
@@ -180,7 +210,8 @@ int pndf_forward_grad_cpu(pndf_cpu_handle h, const float* q, const float* grad_o
 int pndf_project_cpu(pndf_cpu_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps);      /* sample_poses.py:67-74 */
 int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps,
                         const pndf_project_options* opt);      /* pndf_project_ex: same semantics, same validation; also takes a
-                                                                  pndf_project_options2, its `observed` in HOST memory */
+                                                                  pndf_project_options2 or a pndf_project_options3, `observed` in
+                                                                  HOST memory */
 const char* pndf_cpu_last_error(pndf_cpu_handle h);   /* h may be NULL: last error of a failed pndf_cpu_create */
 
 /* Host-only weight packer (what pndf_load_weights uploads); needs no device.  Output sizes in floats come

@@ -31,8 +31,15 @@
  *
  * Pose completion -- some joints observed and held, the others pulled onto the manifold -- is pndf_skel_project (the host twin:
  * pndf_project_ex_cpu) with a pndf_project_options2 (posendf_amd.h) in place of the options: one mask word per pose, the select
- * inside the step of the gradient's last kernel, no launch more than an unmasked projection.  Still 21-joint: the second order
- * (posendf_amd_second_order.h) and interpolation; pndf_complete and its host twin keep the SMPL table.
+ * inside the step of the gradient's last kernel, no launch more than an unmasked projection.
+ *
+ * Pose interpolation -- tracks of T frames between two key poses, relaxed onto the manifold with their end frames held and a coupling
+ * between neighbouring frames -- is the same two entry points with a pndf_project_options3 (posendf_amd.h) in place of the options:
+ * the B poses are B / T tracks, one small kernel fills a chunk of tracks from their end frames, and the coupling sits in the step of the
+ * gradient's last kernel (its second instantiation), so a step costs no launch more than a projection step.
+ *
+ * Still 21-joint: the second order (posendf_amd_second_order.h) only; pndf_complete, pndf_interpolate and their host twins keep the
+ * SMPL table.
  */
 #ifndef POSENDF_AMD_SKELETON_H
 #define POSENDF_AMD_SKELETON_H
@@ -55,8 +62,10 @@ int pndf_skel_destroy(pndf_skel_handle h);
  * uploads a copy and synchronises. */
 int pndf_skel_load_weights(pndf_skel_handle h, const float* const* tensors, const int64_t* numel, int n_tensors);
 
-/* Bytes of the workspace of the three compute calls for B poses: a function of the plan and B only, bounded (the batch is
- * processed in chunks); 0 for B == 0; PNDF_ERR_BAD_ARG for a null handle or a negative B. */
+/* Bytes of the workspace of the three compute calls for B poses: a function of the plan and B only -- not of the options of a call --,
+ * bounded (the batch is processed in chunks of at most 16,384 poses); 0 for B == 0; PNDF_ERR_BAD_ARG for a null handle or a negative B.
+ * It includes, for every caller, one pose buffer [chunk][4 J] for the out-of-place steps of a projection with tracks: at most
+ * 16,384 x 128 x 4 B = 8 MB. */
 int64_t pndf_skel_workspace_bytes(pndf_skel_handle h, int64_t B);
 
 /* forward(pose, train=False)['dist_pred']: q [B,J,4] -> d [B]. */
@@ -72,7 +81,10 @@ int pndf_skel_forward_grad(pndf_skel_handle h, const float* q, const float* grad
  * inside the gradient's last kernel.  q_out may be q_in itself (no other overlap).  d_last (may be NULL) is dist_pred of the last
  * iteration, evaluated before its update; with steps == 0 q_out is a copy of q_in and d_last is zero.  `opt` may point to a
  * pndf_project_options2 (posendf_amd.h; observed: DEVICE memory, one word per pose, read by the kernels of this call): the joints
- * of its mask are held, bit for bit, and the call is otherwise the same -- with no mask or all words zero the same bits. */
+ * of its mask are held, bit for bit, and the call is otherwise the same -- with no mask or all words zero the same bits.  Or to a
+ * pndf_project_options3: with frames = T >= 2 the poses are B / T tracks of T consecutive frames (B % T == 0, T <= 16,384), filled
+ * from their end frames or given, the end frames held, the interior frames coupled to their neighbours with weight lambda; the batch is
+ * then processed in chunks of whole tracks, every step is out of place and q_out must not overlap q_in. */
 int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps,
                       const pndf_project_options* opt, void* workspace, int64_t workspace_bytes, void* stream);
 

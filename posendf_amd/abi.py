@@ -23,6 +23,7 @@ ACT_CODES = {"relu": 0, "lrelu": 1, "softplus": 2}
 PRECISION_CODES = {"fp32": 0, "f16x3": 1, "f16": 2, "bf16": 3}
 RENORM_CODES = {"none": 0, "unit": 1, "unit_flip": 2}      # PNDF_RENORM_*
 INTERP_MODES = {"slerp": 0, "nlerp": 1}                    # PNDF_INTERP_*
+TRACK_FILLS = {"given": 0, "slerp": 1, "nlerp": 2}         # PNDF_TRACK_*
 NOISE_CODES = {"uniform": 0, "symmetric": 1}               # PNDF_ONLINE_*
 METRIC_CODES = {"geo": 0, "euc": 1}
 
@@ -41,6 +42,13 @@ class ProjectOptions2(ctypes.Structure):
     """pndf_project_options2: the options (`base`, with struct_size = 32) and a joint mask, one uint32 per pose, bit j = joint j is
     held; taken by pndf_skel_project (device memory) and pndf_project_ex_cpu (host memory) through the options pointer"""
     _fields_ = [("base", ProjectOptions), ("observed", c_void_p), ("reserved", ctypes.c_uint64)]
+
+
+class ProjectOptions3(ctypes.Structure):
+    """pndf_project_options3: the options with a mask (`base2`, with base2.base.struct_size = 48) and tracks -- the poses are B / frames
+    tracks of `frames` consecutive frames, the end frames held, `lambda_` the neighbour coupling of the interior ones, `fill` a
+    PNDF_TRACK_* code; taken by the two entry points that take a ProjectOptions2"""
+    _fields_ = [("base2", ProjectOptions2), ("frames", c_int32), ("lambda_", c_float), ("fill", c_int32), ("reserved2", c_int32)]
 
 
 class DenoiseWeights(ctypes.Structure):
@@ -72,7 +80,7 @@ class PndfError(RuntimeError):
 _H = c_void_p                          # every handle type, and every `void* stream`
 _P = c_void_p                          # any other address: tensor data (an int from data_ptr(), or None), a callback, an out value
 _TENSORS = [POINTER(c_void_p), POINTER(c_int64), c_int]      # tensors, numel, n_tensors (host pointers in state-dict order)
-_OPT2 = c_void_p                       # `const pndf_project_options*` where it may point to a ProjectOptions or a ProjectOptions2 (byref of either)
+_OPT2 = c_void_p                       # `const pndf_project_options*` where it may point to a ProjectOptions, a ProjectOptions2 or a ProjectOptions3 (byref of any)
 # ---- the header set, stated once: header of include/ -> {name: (restype, argtypes)} in the header's order; the headers in the order
 # they were added.  A new header is a file in include/, a table here and its declaration count in tests/test_cabi.py.
 DEBUG_HEADER = "posendf_amd_debug.h"      # the one header that lives in libposendf_amd_debug.so; every other one in the product library

@@ -4,7 +4,8 @@
 // C++ for the host cores -- NOT the oracle (oracle/ is test infrastructure and is imported by nothing here) and NOT a
 // fallback: the device entry points never route here, a missing GPU still fails loudly there.  The first-order twins take the joint
 // count and the parent table from the handle's config (any joint tree of include/posendf_amd_skeleton.h, pndf_net_plan.h); on the
-// SMPL table they compute what they did with the table fixed.  Completion, interpolation and second order stay 21-joint.
+// SMPL table they compute what they did with the table fixed.  pndf_complete_cpu, pndf_interpolate_cpu and the second order stay 21-joint;
+// pndf_project_ex_cpu completes and interpolates for any joint tree (pndf_project_options2 / pndf_project_options3).
 //
 // Layout: poses are processed in blocks of PB = 32; inside a block every activation tensor is [feature][pose] so that the
 // inner loop of a layer runs over the 32 poses of the block (contiguous floats: one or two AVX-512 / four AVX2 registers)
@@ -386,11 +387,12 @@ extern "C" int pndf_project_cpu(pndf_cpu_handle h, const float* q_in, float* q_o
     });
 }
 
-// interpolation, the second order and pndf_complete_cpu itself stay 21-joint; another skeleton completes poses
-// through pndf_project_ex_cpu with a pndf_project_options2
+// pndf_interpolate_cpu, the second order and pndf_complete_cpu themselves stay 21-joint; another skeleton completes
+// poses through pndf_project_ex_cpu with a pndf_project_options2 and interpolates through it with a pndf_project_options3
 static const char* const SMPL_ONLY = "this entry point runs the 21-joint table of get_parent_mapping('smpl') only; a handle of another skeleton "
                                      "has pndf_forward_cpu, pndf_forward_grad_cpu, pndf_project_cpu and pndf_project_ex_cpu (which holds "
-                                     "observed joints when it is given a pndf_project_options2)";
+                                     "observed joints when it is given a pndf_project_options2 and interpolates tracks when it is given a "
+                                     "pndf_project_options3)";
 
 // One step of pndf_project_ex on the host: pndf_step.h's pndf_step_quat -- the statement the device kernels run -- for every joint of
 // a pose that does not rest.  `held`: bit j = joint j is observed and stays as it is (pndf_complete_cpu, and pndf_project_ex_cpu with the
@@ -425,18 +427,6 @@ static int project_loop_cpu(pndf_cpu_handle h, const float* q_in, const uint32_t
     });
 }
 
-extern "C" int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps,
-                                   const pndf_project_options* opt) {
-    if (!h) return PNDF_ERR_BAD_ARG;
-    pndf_project_options o;
-    const uint32_t* observed;      // a pndf_project_options2 brings the joint mask (host memory): completion for any joint tree
-    if (const char* why = pndf_check_project_options2(opt, o, observed)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
-    if (!observed && pndf_project_options_plain(o)) return pndf_project_cpu(h, q_in, q_out, d_last, B, steps);
-    if (int rc = check(h, q_in, B)) return rc;
-    if (steps < 0 || (B > 0 && !q_out)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count or null output pointer");
-    return project_loop_cpu(h, q_in, observed, q_out, d_last, B, steps, o);
-}
-
 // Host twin of pndf_complete (include/posendf_amd_completion.h): the loop of pndf_project_ex_cpu with the observed joints held.  With
 // the default options the step is pndf_project_cpu's (step_size 1 makes its product exact), so with no joint held this is
 // pndf_project_ex_cpu bit for bit, defaults included.
@@ -453,10 +443,80 @@ extern "C" int pndf_complete_cpu(pndf_cpu_handle h, const float* q_in, const uin
     return project_loop_cpu(h, q_in, observed, q_out, d_last, B, steps, o);
 }
 
-// Host twin of pndf_interpolate (include/posendf_amd_interpolation.h): the fill and the band step of pndf_interp.h -- the statements
-// the device kernels run -- around pndf_forward_grad_cpu.  A step reads the neighbour frames of the track as they were before it
-// (out of place, like the device), so the whole track takes one step at a time; with lambda == 0 this is pndf_complete_cpu on the
-// filled track with the end frames observed, bit for bit.
+// The whole-track loop of pndf_interpolate_cpu and of pndf_project_ex_cpu with the tracks of a pndf_project_options3 (validated
+// arguments), for the handle's joint count: the fill and the band step of pndf_interp.h -- the statements the device kernels run --
+// around pndf_forward_grad_cpu.  A step reads the neighbour frames of the track as they were before it (out of place, like the
+// device), so the whole track takes one step at a time.  `fill` PNDF_TRACK_GIVEN: `a` is the track [P*T] itself (`b` is not read);
+// otherwise pair p is the poses a + p * a_stride and b + p * b_stride.  With lambda == 0 this is project_loop_cpu on the filled
+// track with the end frames held, bit for bit.
+static int track_loop_cpu(pndf_cpu_handle h, const float* a, int64_t a_stride, const float* b, int64_t b_stride, int fill,
+                          const uint32_t* observed, float* track_out, float* d_last, int64_t P, int32_t T, int steps, float lambda,
+                          const pndf_project_options& o) {
+    const int nj = h->net.nj;
+    const int64_t nq = h->nq(), B = P * T;
+    int rc = PNDF_OK;
+    const int grc = guarded(h, [&] {
+        std::vector<float> other((size_t)(B * nq)), dq(steps ? (size_t)(B * nq) : 0), dd((size_t)B, 0.f);
+        float* cur = (steps & 1) ? other.data() : track_out;      // `steps` swaps later the track is in track_out
+        float* nxt = (steps & 1) ? track_out : other.data();
+        if (fill == PNDF_TRACK_GIVEN) memcpy(cur, a, sizeof(float) * (size_t)(B * nq));
+        else
+            for (int64_t p = 0; p < P; ++p)
+                for (int j = 0; j < nj; ++j) {
+                    const float *A = a + p * a_stride + j * 4, *Bq = b + p * b_stride + j * 4;
+                    float bp[4];
+                    pndf_quat_align(A, Bq, bp);
+                    memcpy(cur + ((p * T) * nj + j) * 4, A, sizeof(float) * 4);
+                    memcpy(cur + ((p * T + T - 1) * nj + j) * 4, bp, sizeof(float) * 4);
+                    for (int k = 1; k < T - 1; ++k)
+                        pndf_interp_fill_quat(A, bp, (float)k / (float)(T - 1), fill == PNDF_TRACK_SLERP ? PNDF_INTERP_SLERP : PNDF_INTERP_NLERP,
+                                              cur + ((p * T + k) * nj + j) * 4);
+                }
+        for (int s = 0; s < steps && rc == PNDF_OK; ++s) {
+            rc = pndf_forward_grad_cpu(h, cur, nullptr, dd.data(), dq.data(), B);
+            if (rc != PNDF_OK) break;
+            for (int64_t f = 0; f < B; ++f) {
+                const int k = (int)(f % T);
+                const uint32_t held = (k == 0 || k == T - 1) ? ~0u : (observed ? observed[f] : 0u);
+                for (int j = 0; j < nj; ++j) {
+                    const int64_t i = (f * nj + j) * 4;
+                    float u[4];
+                    if (((held >> j) & 1u) || pndf_interp_band_quat(cur + i, dq.data() + i, dd[f], cur + i - nq, cur + i + nq, lambda, o.step_size, o.tol, (int)o.renorm, u))
+                        memcpy(nxt + i, cur + i, sizeof(float) * 4);
+                    else
+                        memcpy(nxt + i, u, sizeof(float) * 4);
+                }
+            }
+            std::swap(cur, nxt);
+        }
+        if (rc == PNDF_OK && d_last) memcpy(d_last, dd.data(), sizeof(float) * B);
+    });
+    return grc != PNDF_OK ? grc : rc;
+}
+
+extern "C" int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps,
+                                   const pndf_project_options* opt) {
+    if (!h) return PNDF_ERR_BAD_ARG;
+    pndf_project_options o;
+    const uint32_t* observed;      // a pndf_project_options2 brings the joint mask (host memory): completion for any joint tree
+    PndfTracks tracks;             // a pndf_project_options3 the tracks besides: interpolation for any joint tree
+    if (const char* why = pndf_check_project_options3(opt, B, o, observed, tracks)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (!tracks.frames && !observed && pndf_project_options_plain(o)) return pndf_project_cpu(h, q_in, q_out, d_last, B, steps);
+    if (int rc = check(h, q_in, B)) return rc;
+    if (steps < 0 || (B > 0 && !q_out)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count or null output pointer");
+    if (!tracks.frames) return project_loop_cpu(h, q_in, observed, q_out, d_last, B, steps, o);
+    if (B == 0) return PNDF_OK;
+    const int64_t nq = h->nq(), T = tracks.frames;
+    if ((uintptr_t)q_in < (uintptr_t)(q_out + B * nq) && (uintptr_t)q_out < (uintptr_t)(q_in + B * nq))
+        return pndf_fail(h, PNDF_ERR_BAD_ARG, "q_out must not overlap q_in when pndf_project_options3.frames > 0: a step reads the neighbour "
+                                              "frames of its input");
+    return track_loop_cpu(h, q_in, T * nq, q_in + (T - 1) * nq, T * nq, tracks.fill, observed, q_out, d_last, B / T, (int32_t)T, steps,
+                          tracks.lambda, o);
+}
+
+// Host twin of pndf_interpolate (include/posendf_amd_interpolation.h): track_loop_cpu on the 21-joint table; with lambda == 0 this is
+// pndf_complete_cpu on the filled track with the end frames observed, bit for bit.  Another skeleton interpolates through
+// pndf_project_ex_cpu with a pndf_project_options3.
 extern "C" int pndf_interpolate_cpu(pndf_cpu_handle h, const float* a, const float* b, const uint32_t* observed, float* track_out,
                                     float* d_last, int64_t P, int32_t T, int32_t mode, int steps, float lambda,
                                     const pndf_project_options* opt) {
@@ -473,41 +533,8 @@ extern "C" int pndf_interpolate_cpu(pndf_cpu_handle h, const float* a, const flo
     if (!a || !b || !track_out) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose / output pointer");
     if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)track_out | (uintptr_t)d_last | (uintptr_t)observed) & 3)
         return pndf_fail(h, PNDF_ERR_BAD_ARG, "misaligned pose, distance or mask buffer");
-    const int64_t B = P * T;
-    int rc = PNDF_OK;
-    const int grc = guarded(h, [&] {
-        std::vector<float> other((size_t)B * NQ), dq(steps ? (size_t)B * NQ : 0), dd((size_t)B, 0.f);
-        float* cur = (steps & 1) ? other.data() : track_out;      // `steps` swaps later the track is in track_out
-        float* nxt = (steps & 1) ? track_out : other.data();
-        for (int64_t p = 0; p < P; ++p)
-            for (int j = 0; j < NJ; ++j) {
-                const float *A = a + (p * NJ + j) * 4, *Bq = b + (p * NJ + j) * 4;
-                float bp[4];
-                pndf_quat_align(A, Bq, bp);
-                memcpy(cur + ((p * T) * NJ + j) * 4, A, sizeof(float) * 4);
-                memcpy(cur + ((p * T + T - 1) * NJ + j) * 4, bp, sizeof(float) * 4);
-                for (int k = 1; k < T - 1; ++k) pndf_interp_fill_quat(A, bp, (float)k / (float)(T - 1), mode, cur + ((p * T + k) * NJ + j) * 4);
-            }
-        for (int s = 0; s < steps && rc == PNDF_OK; ++s) {
-            rc = pndf_forward_grad_cpu(h, cur, nullptr, dd.data(), dq.data(), B);
-            if (rc != PNDF_OK) break;
-            for (int64_t f = 0; f < B; ++f) {
-                const int k = (int)(f % T);
-                const uint32_t held = (k == 0 || k == T - 1) ? ~0u : (observed ? observed[f] : 0u);
-                for (int j = 0; j < NJ; ++j) {
-                    const int64_t i = (f * NJ + j) * 4;
-                    float u[4];
-                    if (((held >> j) & 1u) || pndf_interp_band_quat(cur + i, dq.data() + i, dd[f], cur + i - NQ, cur + i + NQ, lambda, o.step_size, o.tol, (int)o.renorm, u))
-                        memcpy(nxt + i, cur + i, sizeof(float) * 4);
-                    else
-                        memcpy(nxt + i, u, sizeof(float) * 4);
-                }
-            }
-            std::swap(cur, nxt);
-        }
-        if (rc == PNDF_OK && d_last) memcpy(d_last, dd.data(), sizeof(float) * B);
-    });
-    return grc != PNDF_OK ? grc : rc;
+    return track_loop_cpu(h, a, NQ, b, NQ, mode == PNDF_INTERP_SLERP ? PNDF_TRACK_SLERP : PNDF_TRACK_NLERP, observed, track_out, d_last, P, T,
+                          steps, lambda, o);
 }
 
 // ---- host twin of pndf_second_order (include/posendf_amd_second_order.h): d, g = grad_q d, t = <v, g> and w_d g + w_t H v, one pose at

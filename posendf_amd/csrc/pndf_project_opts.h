@@ -1,6 +1,7 @@
 // Validation of pndf_project_options (include/posendf_amd.h), shared by pndf_project_ex (pndf_capi.hip) and its host twin
 // pndf_project_ex_cpu (pndf_cpu.cpp): the two refuse the same structs with the same text.  And of pndf_project_options2, the options with
-// a joint mask, which pndf_skel_project (pndf_skeleton.hip) and pndf_project_ex_cpu take besides.
+// a joint mask, which pndf_skel_project (pndf_skeleton.hip) and pndf_project_ex_cpu take besides, and of pndf_project_options3, the
+// options with tracks (pose interpolation inside the step), which the same two take.
 #pragma once
 #include <math.h>
 
@@ -42,6 +43,52 @@ inline const char* pndf_check_project_options2(const pndf_project_options* opt, 
     if (o2->reserved != 0) return "pndf_project_options2.reserved must be 0";
     if ((uintptr_t)o2->observed & 3) return "pndf_project_options2.observed must be 4-byte aligned";
     observed = o2->observed;
+    return nullptr;
+}
+
+// the longest track: the poses of one chunk of the skeleton unit (SK_CHUNK of pndf_skeleton.hip), so a track never straddles a seam
+constexpr int32_t PNDF_TRACK_MAX_FRAMES = 16384;
+
+// The tracks of a pndf_project_options3, validated: frames 0 = none (then lambda 0 and PNDF_TRACK_GIVEN)
+struct PndfTracks {
+    int32_t frames = 0;
+    float lambda = 0.f;
+    int32_t fill = PNDF_TRACK_GIVEN;
+};
+
+// The checker of the same two entry points for all three structs: a pndf_project_options3 brings the tracks of B poses besides.
+// Returns nullptr and fills `out`, `observed` and `tracks`, or the reason the struct is refused.  That q_out does not overlap q_in
+// when there are tracks is the caller's to check: it knows the size of a pose.
+inline const char* pndf_check_project_options3(const pndf_project_options* opt, int64_t B, pndf_project_options& out,
+                                               const uint32_t*& observed, PndfTracks& tracks) {
+    tracks = PndfTracks();
+    if (!opt || opt->struct_size != sizeof(pndf_project_options3)) {
+        const char* why = pndf_check_project_options2(opt, out, observed);
+        if (why && opt && opt->struct_size != sizeof(pndf_project_options) && opt->struct_size != sizeof(pndf_project_options2))
+            return "pndf_project_options.struct_size is none of sizeof(pndf_project_options), sizeof(pndf_project_options2) and "
+                   "sizeof(pndf_project_options3): fill the struct with pndf_default_project_options";
+        return why;
+    }
+    const pndf_project_options3* o3 = (const pndf_project_options3*)opt;
+    pndf_project_options2 base2 = o3->base2;
+    base2.base.struct_size = (uint32_t)sizeof(pndf_project_options2);
+    if (const char* why = pndf_check_project_options2(&base2.base, out, observed)) return why;
+    observed = nullptr;      // (set again below: a refusal leaves no mask behind)
+    if (o3->reserved2 != 0) return "pndf_project_options3.reserved2 must be 0";
+    if (o3->fill != PNDF_TRACK_GIVEN && o3->fill != PNDF_TRACK_SLERP && o3->fill != PNDF_TRACK_NLERP)
+        return "pndf_project_options3.fill is not a PNDF_TRACK_* mode";
+    if (!(o3->lambda >= 0.f && o3->lambda <= 1.f)) return "pndf_project_options3.lambda must lie in [0, 1] (and not be NaN)";
+    if (o3->frames == 0) {
+        if (o3->lambda != 0.f) return "pndf_project_options3.lambda must be 0 when frames is 0 (no tracks)";
+        if (o3->fill != PNDF_TRACK_GIVEN) return "pndf_project_options3.fill must be PNDF_TRACK_GIVEN when frames is 0 (no tracks)";
+    } else {
+        if (o3->frames < 2 || o3->frames > PNDF_TRACK_MAX_FRAMES) return "pndf_project_options3.frames must be 0 (no tracks) or 2 .. 16384";
+        if (B > 0 && B % o3->frames != 0) return "pndf_project_options3.frames does not divide B: the poses are B / frames whole tracks";
+    }
+    observed = base2.observed;
+    tracks.frames = o3->frames;
+    tracks.lambda = o3->lambda;
+    tracks.fill = o3->fill;
     return nullptr;
 }
 

@@ -16,7 +16,12 @@
 //   pndf_skel_enc_rev_kernel   lanes own poses: joints nj-1 .. 0 (children before parents), rows 4..9 of a bone's input adjoint
 //                              added to the parent's feature adjoint, the reverse of the normalisation, grad_out; in project mode
 //                              the step of pndf_step.h in the same kernel, and with the joint mask of a pndf_project_options2 (pose
-//                              completion: one word per pose) a held joint stores the bits it read instead
+//                              completion: one word per pose) a held joint stores the bits it read instead; with the tracks of a
+//                              pndf_project_options3 (pose interpolation: lane c is frame c % T of its track) its second
+//                              instantiation pndf_skel_enc_rev_track_kernel: the end frames are held and a free joint of an
+//                              interior frame takes the neighbour coupling of pndf_interp.h between the descent and the
+//                              renormalisation, out of place
+//   pndf_skel_fill_kernel      the fill of a track from its two end frames, once per chunk in front of the steps
 // 2 + 2 L launches per evaluation.  No float atomics, no communication between workgroups, every column of a GEMM summed in the
 // same order wherever it sits: the same inputs give the same bits and a pose's result does not depend on its batch.
 #include <hip/hip_runtime.h>
@@ -31,6 +36,7 @@
 #include "pndf_experiment.h"
 #include "pndf_bone.h"
 #include "pndf_host.h"
+#include "pndf_interp.h"
 #include "pndf_project_opts.h"
 #include "pndf_step.h"
 
@@ -64,6 +70,8 @@ struct SkArgs {
     float beta;
     float step_size, tol;     // SK_PROJECT
     int renorm;
+    int frames;               // T of a pndf_project_options3: the chunk is n / T whole tracks, lane c is frame c % T; 0 = no tracks  (SK_PROJECT)
+    float lambda;             // the neighbour coupling of an interior frame
     int parent[MAXJ];
     int off[MAXJ];
 };
@@ -137,7 +145,10 @@ extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_fwd_kernel(SkArg
 
 // The reverse of the encoder and of the normalisation: per component column k with s = |q_k| and x = q_k / s,
 // d d / d q = (g_x - x (x . g_x)) / s; where the norm is clamped the normalisation is linear, g_x / eps.  Then grad_out, or the step.
-extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_kernel(SkArgs e) {
+// TRACKS: the instantiation of a projection with tracks (e.frames >= 2); every other call runs the one without, which has no branch on
+// the tracks and no neighbour registers (as a branch in one kernel the tracks cost the call without them up to 0.2 %).
+template <bool TRACKS>
+__device__ __forceinline__ void skel_enc_rev(const SkArgs& e) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= e.n) return;
     if (e.encoder)
@@ -158,7 +169,13 @@ extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_kernel(SkArg
         }
     const float dist = e.dist[c];
     const float go = (e.mode == SK_GRAD && e.grad_out) ? e.grad_out[c] : 1.f;
-    const uint32_t held = (e.mode == SK_PROJECT && e.observed) ? e.observed[c] : 0u;
+    uint32_t held = (e.mode == SK_PROJECT && e.observed) ? e.observed[c] : 0u;
+    float lambda = 0.f;      // > 0: an interior frame of a track, whose neighbours c - 1 and c + 1 are frames of the same track and chunk
+    if (TRACKS) {            // (SK_PROJECT, e.frames >= 2)
+        const int k = (int)(c % e.frames);
+        if (k == 0 || k == e.frames - 1) held = ~0u;
+        else lambda = e.lambda;
+    }
     for (int j = 0; j < e.nj; ++j) {
         float g[BONE];
 #pragma unroll
@@ -171,7 +188,19 @@ extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_kernel(SkArg
             float Q[BONE], u[BONE];
 #pragma unroll
             for (int k = 0; k < BONE; ++k) Q[k] = q[j * BONE + k];
-            const bool rest = pndf_step_quat(Q, g, dist, e.step_size, e.tol, e.renorm, u);
+            bool rest;
+            if (TRACKS) {
+                float nm[BONE] = {0.f, 0.f, 0.f, 0.f}, np[BONE] = {0.f, 0.f, 0.f, 0.f};
+                if (lambda > 0.f)
+#pragma unroll
+                    for (int k = 0; k < BONE; ++k) {
+                        nm[k] = q[j * BONE + k - nq];
+                        np[k] = q[j * BONE + k + nq];
+                    }
+                rest = pndf_interp_band_quat(Q, g, dist, nm, np, lambda, e.step_size, e.tol, e.renorm, u);      // lambda 0: pndf_step_quat
+            } else {
+                rest = pndf_step_quat(Q, g, dist, e.step_size, e.tol, e.renorm, u);
+            }
 #pragma unroll
             for (int k = 0; k < BONE; ++k) {      // a held joint keeps the bits it came with: an integer select, no arithmetic on them
                 const uint32_t kept = __float_as_uint(Q[k]), stepped = __float_as_uint(rest ? Q[k] : u[k]);
@@ -183,6 +212,41 @@ extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_kernel(SkArg
         }
     }
     if (e.d_out) e.d_out[c] = dist;
+}
+
+extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_kernel(SkArgs e) { skel_enc_rev<false>(e); }
+extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_track_kernel(SkArgs e) { skel_enc_rev<true>(e); }
+
+// The fill of a chunk of whole tracks (pndf_project_options3, PNDF_TRACK_SLERP / _NLERP): one lane per joint quaternion.  Of every track
+// only frames 0 (a) and T-1 (b) of `src` are read; frame 0 of `dst` takes the bits of a, frame T-1 b aligned to a, the frames between
+// them pndf_interp_fill_quat -- the statements of pndf_interp_fill_kernel for a run-time joint count.  dst does not overlap src.
+extern "C" __global__ void __launch_bounds__(256) pndf_skel_fill_kernel(const float* __restrict__ src, float* __restrict__ dst, int64_t quats,
+                                                                        int nj, int T, int mode) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= quats) return;
+    const int64_t f = i / nj;
+    const int j = (int)(i - f * nj);
+    const int k = (int)(f % T);
+    const float* a = src + ((f - k) * nj + j) * BONE;
+    const float* b = a + (int64_t)(T - 1) * nj * BONE;
+    float av[BONE], bv[BONE], u[BONE];
+#pragma unroll
+    for (int c = 0; c < BONE; ++c) av[c] = a[c];
+    if (k > 0) {
+#pragma unroll
+        for (int c = 0; c < BONE; ++c) bv[c] = b[c];
+        float bp[BONE];
+        pndf_quat_align(av, bv, bp);
+        if (k < T - 1) pndf_interp_fill_quat(av, bp, (float)k / (float)(T - 1), mode, u);
+        else
+#pragma unroll
+            for (int c = 0; c < BONE; ++c) u[c] = bp[c];
+    } else {
+#pragma unroll
+        for (int c = 0; c < BONE; ++c) u[c] = av[c];
+    }
+#pragma unroll
+    for (int c = 0; c < BONE; ++c) dst[i * BONE + c] = u[c];
 }
 
 // the forward alone ends here: the trunk's output row -> d
@@ -207,6 +271,7 @@ const GemmKernels SK_GEMM = {pndf_skel_gemm_nn_kernel, pndf_skel_gemm_tn_kernel,
 struct SkLayout {
     int64_t nc;
     int64_t X, act0, S1, S2, U0, Gx, dist, D1[MAX_LIN], P[2];
+    int64_t Q2;      // the second pose buffer [nc][4 J] of the out-of-place steps of a pndf_project_options3
     int64_t total;
 };
 
@@ -231,6 +296,7 @@ SkLayout sk_layout(const pndf_skel_plan* h, int64_t B) {
     for (int t = 0; t < h->L; ++t) l.D1[t] = c.take((int64_t)h->dims[t + 1] * l.nc);
     l.P[0] = c.take((int64_t)h->maxw * l.nc);
     l.P[1] = c.take((int64_t)h->maxw * l.nc);
+    l.Q2 = c.take(nq * l.nc);
     l.total = c.o;
     return l;
 }
@@ -250,7 +316,8 @@ void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, SkArgs 
         return;
     }
     trunk_reverse(SK_GEMM, *h, w, b, st);      // grad_out scales the result in the encoder's reverse
-    hipLaunchKernelGGL(pndf_skel_enc_rev_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
+    if (e.mode == SK_PROJECT && e.frames) hipLaunchKernelGGL(pndf_skel_enc_rev_track_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
+    else hipLaunchKernelGGL(pndf_skel_enc_rev_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
 }
 
 SkArgs sk_args(const pndf_skel_plan* h, const SkLayout& l, float* ws, int mode) {
@@ -404,20 +471,25 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
     if (!h) return PNDF_ERR_BAD_ARG;
     pndf_project_options o;
     const uint32_t* observed;      // a pndf_project_options2 brings the joint mask: one word per pose, device memory
-    if (const char* why = pndf_check_project_options2(opt, o, observed)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    PndfTracks tracks;             // a pndf_project_options3 the tracks besides: B / frames of them
+    if (const char* why = pndf_check_project_options3(opt, B, o, observed, tracks)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (steps < 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count");
     SkLayout l;
     if (B > 0 && (!q_in || !q_out)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose pointer");
     if (((uintptr_t)q_in | (uintptr_t)q_out | (uintptr_t)d_last) & 3) return pndf_fail(h, PNDF_ERR_BAD_ARG, "misaligned pose or distance buffer");
     if (B > 0 && q_in != q_out && overlaps(q_in, q_out, B * h->nj * BONE))
         return pndf_fail(h, PNDF_ERR_BAD_ARG, "q_out may be q_in itself, but must not overlap it otherwise");
+    if (B > 0 && tracks.frames && q_in == q_out)
+        return pndf_fail(h, PNDF_ERR_BAD_ARG, "q_out must not overlap q_in when pndf_project_options3.frames > 0: a step reads the neighbour "
+                                              "frames of its input");
     if (const int rc = sk_check(h, B, workspace, workspace_bytes, l); rc != PNDF_OK || B == 0) return rc;
     PndfRange range("pndf_skel_project");
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     hipStream_t st = (hipStream_t)stream;
     const int64_t nq = (int64_t)h->nj * BONE;
-    if (steps == 0) {
+    const bool filled = tracks.fill != PNDF_TRACK_GIVEN;
+    if (steps == 0 && !filled) {
         if (q_in != q_out) HIP_TRY(h, hipMemcpyAsync(q_out, q_in, sizeof(float) * (size_t)(B * nq), hipMemcpyDeviceToDevice, st));
         if (d_last) HIP_TRY(h, hipMemsetAsync(d_last, 0, sizeof(float) * (size_t)B, st));
         return PNDF_OK;
@@ -425,14 +497,30 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
     float* ws = (float*)workspace;
     SkArgs e = sk_args(h, l, ws, SK_PROJECT);
     e.step_size = o.step_size; e.tol = o.tol; e.renorm = (int)o.renorm;
-    for (int64_t c0 = 0; c0 < B; c0 += l.nc) {
-        e.n = B - c0 < l.nc ? B - c0 : l.nc;
-        e.out = q_out + c0 * nq;
+    e.frames = tracks.frames; e.lambda = tracks.lambda;
+    // with tracks a chunk holds whole tracks, so no track straddles a seam and lane c of a chunk is frame c % T
+    const int64_t nc = tracks.frames ? (l.nc / tracks.frames) * tracks.frames : l.nc;
+    if (steps == 0 && d_last) HIP_TRY(h, hipMemsetAsync(d_last, 0, sizeof(float) * (size_t)B, st));
+    for (int64_t c0 = 0; c0 < B; c0 += nc) {
+        e.n = B - c0 < nc ? B - c0 : nc;
         e.observed = observed ? observed + c0 : nullptr;
-        for (int s = 0; s < steps; ++s) {      // from the second step on the iterate is in q_out: a lane reads its pose before it writes it
-            e.q = s == 0 ? q_in + c0 * nq : q_out + c0 * nq;
+        // Without tracks the iterate is in q_out from the second step on: a lane reads its pose before it writes it.  With tracks a
+        // step is out of place: the steps alternate between the chunk of q_out and the second pose buffer, the last one writes
+        // q_out; step 0 reads q_in, or the buffer the fill wrote.
+        float* buf[2] = {q_out + c0 * nq, tracks.frames ? ws + l.Q2 : q_out + c0 * nq};
+        const float* cur = q_in + c0 * nq;
+        if (filled) {
+            float* dst = buf[steps & 1];      // what step 0 does not write; q_out itself when there is no step
+            hipLaunchKernelGGL(pndf_skel_fill_kernel, dim3(blocks(e.n * h->nj)), dim3(256), 0, st, cur, dst, e.n * (int64_t)h->nj, h->nj,
+                               tracks.frames, tracks.fill == PNDF_TRACK_SLERP ? PNDF_INTERP_SLERP : PNDF_INTERP_NLERP);
+            cur = dst;
+        }
+        for (int s = 0; s < steps; ++s) {
+            e.q = cur;
+            e.out = buf[(steps - 1 - s) & 1];
             e.d_out = (d_last && s == steps - 1) ? d_last + c0 : nullptr;
             sk_run_chunk(h, l, ws, e, st);
+            cur = e.out;
         }
     }
     return pndf_check_launch(h, "pndf_skel_project");

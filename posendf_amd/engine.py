@@ -15,7 +15,7 @@ import numpy as np
 # public names stay importable from here.  `torch` comes from there too: abi imports it before the library is loaded (None without it).
 from .abi import (ACT_CODES, DEBUG_EXPERIMENT_WORDS, DEBUG_EXPORTS, EXPERIMENT_WORDS, EXPORTS, INTERP_MODES, METRIC_CODES,  # noqa: F401
                   NOISE_CODES, PRECISION_CODES, RENORM_CODES, Camera, DenoiseWeights, KeypointOpts, OnlineOpts, PndfConfig, PndfError,
-                  ProjectOptions, ProjectOptions2, debug_library_path, experiment_word, load_library, torch)
+                  ProjectOptions, ProjectOptions2, ProjectOptions3, TRACK_FILLS, debug_library_path, experiment_word, load_library, torch)
 
 
 def stream_handle(device) -> int:
@@ -120,6 +120,25 @@ def project_options2(lib, observed_ptr, step_size=1.0, renorm="none", tol=0.0):
     opt.base.struct_size = ctypes.sizeof(opt)
     opt.observed, opt.reserved = observed_ptr, 0
     return opt
+
+
+def project_options3(lib, observed_ptr, frames, smooth=0.0, fill=None, step_size=1.0, renorm="none", tol=0.0):
+    """pndf_project_options3 (include/posendf_amd.h): the options, the mask and the tracks -- the poses are tracks of `frames` frames with the
+    end frames held, `smooth` the neighbour coupling lambda, `fill` "given" / None (the poses are the track), "slerp" or "nlerp" (the
+    frames between the end frames are interpolated).  The values are checked by the library, only the fill's name here."""
+    fill = "given" if fill is None else fill
+    if fill not in TRACK_FILLS:
+        raise PndfError(f"unknown track fill {fill!r} (None / 'given', 'slerp', 'nlerp')")
+    opt = ProjectOptions3()
+    opt.base2 = project_options2(lib, observed_ptr, step_size, renorm, tol)
+    opt.base2.base.struct_size = ctypes.sizeof(opt)
+    opt.frames, opt.lambda_, opt.fill, opt.reserved2 = int(frames), float(smooth), TRACK_FILLS[fill], 0
+    return opt
+
+
+def _tracked(frames, smooth, fill) -> bool:
+    """whether a `project` call names tracks at all: only then is the 48-byte struct built"""
+    return bool(frames) or float(smooth) != 0.0 or fill not in (None, "given")
 
 
 def interp_mode(mode) -> int:
@@ -457,10 +476,13 @@ class SkeletonEngine(_Handle):
                     "pndf_skel_forward_grad")
 
     def project(self, q_in_ptr, q_out_ptr, d_ptr, B, steps, ws_ptr, ws_bytes, stream=0, *, step_size=1.0, renorm="none", tol=0.0,
-                observed_ptr=None):
+                observed_ptr=None, frames=0, smooth=0.0, fill=None):
         """pndf_skel_project; `observed_ptr`: one uint32 per pose in device memory, bit j = joint j is held (pose completion, through a
-        pndf_project_options2); None: no joint is held and the call is the one without a mask"""
-        if observed_ptr is None:
+        pndf_project_options2); None: no joint is held and the call is the one without a mask.  `frames` = T >= 2: the poses are B / T
+        tracks (pose interpolation, through a pndf_project_options3: `project_options3`), q_out apart from q_in"""
+        if _tracked(frames, smooth, fill):
+            opt = ctypes.byref(project_options3(self.lib, observed_ptr, frames, smooth, fill, step_size, renorm, tol))
+        elif observed_ptr is None:
             opt = _opt_ref(self.lib, step_size, renorm, tol)
         else:
             opt = ctypes.byref(project_options2(self.lib, observed_ptr, step_size, renorm, tol))
@@ -648,9 +670,16 @@ class CpuEngine(_Handle):
     def forward_grad(self, q_ptr, gout_ptr, d_ptr, dq_ptr, B, stream=0):
         self._check(self.lib.pndf_forward_grad_cpu(self.handle, q_ptr, gout_ptr, d_ptr, dq_ptr, B), "pndf_forward_grad_cpu")
 
-    def project(self, q_in_ptr, q_out_ptr, d_ptr, B, steps, stream=0, *, step_size=1.0, renorm="none", tol=0.0, observed_ptr=None):
+    def project(self, q_in_ptr, q_out_ptr, d_ptr, B, steps, stream=0, *, step_size=1.0, renorm="none", tol=0.0, observed_ptr=None,
+                frames=0, smooth=0.0, fill=None):
         """`observed_ptr`: one uint32 per pose in host memory, bit j = joint j is held (pndf_project_ex_cpu with a pndf_project_options2:
-        any joint tree); None: the call without a mask"""
+        any joint tree); None: the call without a mask.  `frames` = T >= 2: the poses are B / T tracks (pndf_project_ex_cpu with a
+        pndf_project_options3: `project_options3`)"""
+        if _tracked(frames, smooth, fill):
+            opt3 = project_options3(self.lib, observed_ptr, frames, smooth, fill, step_size, renorm, tol)
+            self._check(self.lib.pndf_project_ex_cpu(self.handle, q_in_ptr, q_out_ptr, d_ptr, B, int(steps), ctypes.byref(opt3)),
+                        "pndf_project_ex_cpu")
+            return
         if observed_ptr is not None:
             opt2 = project_options2(self.lib, observed_ptr, step_size, renorm, tol)
             self._check(self.lib.pndf_project_ex_cpu(self.handle, q_in_ptr, q_out_ptr, d_ptr, B, int(steps), ctypes.byref(opt2)),

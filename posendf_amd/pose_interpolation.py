@@ -17,7 +17,7 @@ from .sample_poses import SamplePose
 
 
 def segment_lengths(track: torch.Tensor) -> torch.Tensor:
-    """track [P,T,21,4] -> [P,T-1]: the length of every segment of the track in radians, the sum over the joints of the rotation
+    """track [P,T,J,4] (any joint count) -> [P,T-1]: the length of every segment of the track in radians, the sum over the joints of the rotation
     angle between consecutive frames, 2 acos(min(|<q_k, q_k+1>|, 1)) (the sign of a quaternion does not matter)."""
     dots = (track[:, :-1] * track[:, 1:]).sum(dim=-1).abs().clamp(max=1.0)
     return (2.0 * torch.acos(dots)).sum(dim=-1)
@@ -29,11 +29,14 @@ class PoseInterpolation(SamplePose):
     @torch.no_grad()
     def interpolate(self, pose_a, pose_b, frames, steps=100, smooth=0.5, mode="slerp", observed=None, *, step_size=1.0, renormalize="unit",
                     tol=0.0):
-        """pose_a, pose_b: [21,4] or [P,21,4]; every argument is PoseNDF.interpolate's (smooth defaults to the coupling that keeps
-        a track even).  Returns (track [P,frames,21,4], dist [P,frames] of the last iteration, meshes).  With a body model, meshes
+        """pose_a, pose_b: [J,4] or [P,J,4] for the model's J joints (21 for a PoseNDF, the tree's for a SkeletonPoseNDF, which has no
+        body model: its meshes are empty); every argument is the model's `interpolate`'s (smooth defaults to the coupling that keeps
+        a track even).  Returns (track [P,frames,J,4], dist [P,frames] of the last iteration, meshes).  With a body model, meshes
         holds 'pose_init' / 'vertices_init' of the filled track (steps = 0) and 'pose' / 'vertices' / 'joints' of the relaxed one,
         P * frames rows each; without one it is empty."""
         J = self.pose_prior.num_joints
+        if self.body_model is not None and J != 21:
+            raise ValueError(f"the body model takes SMPL's 21 joints; a model of {J} joints interpolates without one (body_model=None)")
         a = pose_a.to(self.device).reshape(-1, J, 4).float()
         b = pose_b.to(self.device).reshape(-1, J, 4).float()
         kw = dict(mode=mode, observed=observed, step_size=step_size, renormalize=renormalize, tol=tol)

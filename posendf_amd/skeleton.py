@@ -13,8 +13,10 @@ table, with no fallback, and `posendf_amd.trainer.Trainer` trains the skeleton e
 
 `complete(poses, observed)` is pose completion for the model's tree: `project` with the observed joints held, the joint mask inside
 the projection step of the unit's last kernel (or of the host twin), handed over in a pndf_project_options2 (include/posendf_amd.h);
-`posendf_amd.pose_completion.PoseCompletion` drives it with several hypotheses per pose.  The second order and interpolation stay
-21-joint.
+`posendf_amd.pose_completion.PoseCompletion` drives it with several hypotheses per pose.  `interpolate(pose_a, pose_b, frames)` is pose
+interpolation for the model's tree the same way: the tracks ride in a pndf_project_options3, the fill is one small kernel and the
+neighbour coupling sits in the step; `posendf_amd.pose_interpolation.PoseInterpolation` drives it.  The second order stays 21-joint
+(DESIGN.md section 8).
 """
 from __future__ import annotations
 
@@ -115,3 +117,48 @@ class SkeletonPoseNDF(PoseModel):
             eng.project(q.data_ptr(), out.data_ptr(), d.data_ptr(), B, int(steps), *(() if host else self._engine_args(eng, q.device, B)),
                         step_size=step_size, renorm=renormalize, tol=tol, observed_ptr=None if mask is None or B == 0 else mask.data_ptr())
         return (out, d.view(-1, 1)) if return_dist else out
+
+    @torch.no_grad()
+    def interpolate(self, pose_a, pose_b, frames, steps=100, smooth=0.0, mode="slerp", observed=None, return_dist=True, *, step_size=1.0,
+                    renormalize="unit", tol=0.0):
+        """Pose interpolation with the contract of `PoseNDF.interpolate`: a track of `frames` poses from every pose of `pose_a` to the
+        matching pose of `pose_b` ([P,J,4] each), relaxed onto the manifold.  Frame 0 is `pose_a`, frame frames-1 is `pose_b` with every
+        joint quaternion negated where that is the shorter way round; the frames between them start as the `mode` ("slerp" / "nlerp")
+        interpolation of each joint and take `steps` steps of `complete` -- the two end frames and the `observed` joints held, bit for
+        bit -- with a neighbour coupling of weight `smooth` in [0, 1] inside the same step.  `observed`: bool [J], [frames,J] (one mask
+        per frame, for every pair) or [P,frames,J].  The whole interpolation is ONE engine call: the tracks ride in the projection call
+        itself (pndf_project_options3, include/posendf_amd.h), the unit fills a chunk of tracks with one small kernel and couples the
+        neighbours in its last kernel of every step, so a step costs no launch more than a projection step; a `train.device: cpu` model
+        runs the host twin.  The inputs are not written.  Returns (track [P,frames,J,4], dist [P,frames] of the last iteration); step
+        options: as `project`, with unit quaternions as the default."""
+        if mode not in ("slerp", "nlerp"):
+            raise PndfError(f"unknown interpolation mode {mode!r} ('slerp', 'nlerp')")
+        J = self.num_joints
+        a = pose_a.to(device=self.device).reshape(-1, J, 4).float()
+        b = pose_b.to(device=self.device).reshape(-1, J, 4).float()
+        P, T = a.shape[0], int(frames)
+        if b.shape[0] != P:
+            raise PndfError(f"pose_a holds {P} poses, pose_b {b.shape[0]}")
+        if T < 2:
+            raise PndfError(f"an interpolation has at least two frames, not {frames}")
+        # the call reads frames 0 and T-1 of every track of its input and nothing else of it
+        ends = torch.zeros((P, T, J, 4), device=a.device, dtype=torch.float32)
+        ends[:, 0], ends[:, T - 1] = a, b
+        track = torch.empty_like(ends)
+        d = torch.empty((P, T), device=a.device, dtype=torch.float32)
+        mask = None
+        if observed is not None:
+            obs = torch.as_tensor(observed, device=a.device)
+            if obs.dtype == torch.bool and obs.shape == (T, J):
+                obs = obs.expand(P, T, J)
+            if obs.dtype == torch.bool and obs.shape == (P, T, J):
+                obs = obs.reshape(P * T, J)
+            mask = pack_observed(obs, P * T, a.device, J)
+        eng = self._engine_for(a.device)
+        host = a.device.type == "cpu"
+        B = P * T
+        if B or host:       # as `project`
+            eng.project(ends.data_ptr(), track.data_ptr(), d.data_ptr(), B, int(steps), *(() if host else self._engine_args(eng, a.device, B)),
+                        step_size=step_size, renorm=renormalize, tol=tol, observed_ptr=None if mask is None or B == 0 else mask.data_ptr(),
+                        frames=T, smooth=smooth, fill=mode)
+        return (track, d) if return_dist else track
