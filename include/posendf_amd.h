@@ -184,6 +184,38 @@ typedef struct {
     int32_t reserved2;           /* must be 0 */
 } pndf_project_options3;         /* 48 bytes */
 
+/* The options with an observation: motion denoising inside the projection step, for any joint tree -- a pose prior (the descent), a
+ * temporal term (the tracks' coupling) and a data term that ties the result to the noisy observation, all in quaternion space.  Per
+ * free joint quaternion Q of a pose, every operation rounded on its own, between the descent and renorm / flip / tol:
+ *   coupling : an interior frame of a track as in pndf_project_options3.  With PNDF_TRACK_FREE_ENDS the two end frames of a track are
+ *              no longer held: they descend like every frame, and with lambda > 0 take lambda (0.5 (N - Q)) with N the joint in their
+ *              one neighbour frame, negated where <Q, N> < 0 (the gradient of sum_k |q_k - q_k+1|^2, which for an interior frame is
+ *              lambda (mean - Q)); the joints of `observed` stay held in every frame.  Without the flag the end frames are held;
+ *   data term: w = mu * conf[pose][j] (w = mu when conf is NULL); when w > 0, u <- u + w (A - Q) with A the joint of `anchor`, negated
+ *              where <Q, A> < 0.  When w > 0 is false -- a zero, negative or NaN confidence -- the joint takes no data term and its
+ *              anchor is NOT READ: a missing detection may hold anything, a NaN included.
+ * anchor [B,J,4] and conf [B,J] are laid out as the poses are (DEVICE memory for the device entry point, HOST memory for the host twin);
+ * they may be q_in itself or overlap it, and must not overlap q_out.  Without tracks (frames == 0) the call may still run in place.
+ * With anchor == NULL and flags == 0 the call is the one with the 48-byte struct, bit for bit; with mu == 0 it is that call too and
+ * the anchors are never read.  Fill it with
+ *   pndf_project_options4 o;  pndf_default_project_options(&o.base3.base2.base);  o.base3.base2.base.struct_size = sizeof o;
+ *   o.base3.base2.observed = NULL;  o.base3.base2.reserved = 0;  o.base3.frames = T;  o.base3.lambda = 0.5f;
+ *   o.base3.fill = PNDF_TRACK_GIVEN;  o.base3.reserved2 = 0;  o.anchor = noisy;  o.conf = NULL;  o.mu = 0.25f;  o.flags = PNDF_TRACK_FREE_ENDS;
+ * and pass (const pndf_project_options*)&o.  Exactly the two entry points that take a pndf_project_options3 take it: pndf_skel_project
+ * and pndf_project_ex_cpu; every other function with a pndf_project_options parameter keeps refusing a struct_size other than
+ * sizeof(pndf_project_options).  PNDF_ERR_BAD_ARG with a text that names the field, before anything is launched or written: a
+ * struct_size that is none of the four sizes, a mu outside [0, 1] or NaN, an unknown bit in flags, anchor == NULL with mu != 0 or
+ * conf != NULL, a misaligned anchor or conf, PNDF_TRACK_FREE_ENDS with frames == 0 or with a fill other than PNDF_TRACK_GIVEN, anchor
+ * or conf overlapping q_out, and what is refused in `base3`. */
+enum { PNDF_TRACK_FREE_ENDS = 1 };
+typedef struct {
+    pndf_project_options3 base3;  /* base3.base2.base.struct_size = sizeof(pndf_project_options4); mask and tracks as before */
+    const float* anchor;          /* [B,J,4] the observation, or NULL (no data term); 4-byte aligned */
+    const float* conf;            /* [B,J] per-joint confidence, or NULL (ones); 4-byte aligned */
+    float mu;                     /* weight of the data term, in [0, 1] */
+    uint32_t flags;               /* 0 or PNDF_TRACK_FREE_ENDS */
+} pndf_project_options4;          /* 72 bytes */
+
 /* pndf_project with step options.  opt == NULL means the defaults, and with the defaults the call is pndf_project bit for
  * bit.  PNDF_ERR_BAD_ARG (text in pndf_last_error; nothing is launched or written) for a struct_size other than
  * sizeof(pndf_project_options), a step_size that is not finite or <= 0, a tol that is NaN or < 0, an unknown renorm mode.
@@ -210,8 +242,9 @@ int pndf_forward_grad_cpu(pndf_cpu_handle h, const float* q, const float* grad_o
 int pndf_project_cpu(pndf_cpu_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps);      /* sample_poses.py:67-74 */
 int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps,
                         const pndf_project_options* opt);      /* pndf_project_ex: same semantics, same validation; also takes a
-                                                                  pndf_project_options2 or a pndf_project_options3, `observed` in
-                                                                  HOST memory */
+                                                                  pndf_project_options2, a pndf_project_options3 or a
+                                                                  pndf_project_options4, `observed` / `anchor` / `conf`
+                                                                  in HOST memory */
 const char* pndf_cpu_last_error(pndf_cpu_handle h);   /* h may be NULL: last error of a failed pndf_cpu_create */
 
 /* Host-only weight packer (what pndf_load_weights uploads); needs no device.  Output sizes in floats come

@@ -38,6 +38,11 @@
  * the B poses are B / T tracks, one small kernel fills a chunk of tracks from their end frames, and the coupling sits in the step of the
  * gradient's last kernel (its second instantiation), so a step costs no launch more than a projection step.
  *
+ * Motion denoising -- a noisy clip pulled onto the manifold by the descent (the pose prior), the coupling between neighbouring frames
+ * (the temporal term) and a data term towards the observation, the end frames free -- is the same two entry points with a
+ * pndf_project_options4 (posendf_amd.h): anchor [B,J,4] and conf [B,J] in device memory beside the poses, mu and PNDF_TRACK_FREE_ENDS; the
+ * terms sit in the step of the gradient's last kernel (its third instantiation), so a denoising step costs no launch more either.
+ *
  * Still 21-joint: the second order (posendf_amd_second_order.h) only; pndf_complete, pndf_interpolate and their host twins keep the
  * SMPL table.
  */
@@ -84,7 +89,10 @@ int pndf_skel_forward_grad(pndf_skel_handle h, const float* q, const float* grad
  * of its mask are held, bit for bit, and the call is otherwise the same -- with no mask or all words zero the same bits.  Or to a
  * pndf_project_options3: with frames = T >= 2 the poses are B / T tracks of T consecutive frames (B % T == 0, T <= 16,384), filled
  * from their end frames or given, the end frames held, the interior frames coupled to their neighbours with weight lambda; the batch is
- * then processed in chunks of whole tracks, every step is out of place and q_out must not overlap q_in. */
+ * then processed in chunks of whole tracks, every step is out of place and q_out must not overlap q_in.  Or to a
+ * pndf_project_options4: besides, `anchor` [B,J,4] and `conf` [B,J] (DEVICE memory, read by the kernels of this call; neither may overlap
+ * q_out, both may be q_in) add the data term of weight mu * conf to every free joint, and PNDF_TRACK_FREE_ENDS frees the end frames of
+ * every track; without tracks such a call may still run in place. */
 int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps,
                       const pndf_project_options* opt, void* workspace, int64_t workspace_bytes, void* stream);
 

@@ -25,6 +25,9 @@ def __getattr__(name):   # torch is imported lazily so that numpy-only users (or
     if name == "PoseInterpolation":
         from .pose_interpolation import PoseInterpolation
         return PoseInterpolation
+    if name in ("PoseDenoising", "denoise_track_file"):
+        from . import pose_denoising
+        return getattr(pose_denoising, name)
     if name in ("SkeletonPoseNDF", "SKELETONS", "skeleton_config"):
         from . import skeleton
         return getattr(skeleton, name)
@@ -38,5 +41,6 @@ def __getattr__(name):   # torch is imported lazily so that numpy-only users (or
 
 
 __all__ = ["PoseNDF", "gradient", "BodyModel", "PoseIndex", "Trainer", "PoseDataset", "OnlinePoseDataset", "OnlineOptions", "sample_noisy", "ImageFit", "PerspectiveCamera", "keypoint_term", "PoseCompletion", "PoseInterpolation",
+           "PoseDenoising", "denoise_track_file",
            "SkeletonPoseNDF", "SKELETONS", "skeleton_config",
            "amass_config", "load_config", "synth"]

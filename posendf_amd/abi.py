@@ -24,6 +24,7 @@ PRECISION_CODES = {"fp32": 0, "f16x3": 1, "f16": 2, "bf16": 3}
 RENORM_CODES = {"none": 0, "unit": 1, "unit_flip": 2}      # PNDF_RENORM_*
 INTERP_MODES = {"slerp": 0, "nlerp": 1}                    # PNDF_INTERP_*
 TRACK_FILLS = {"given": 0, "slerp": 1, "nlerp": 2}         # PNDF_TRACK_*
+TRACK_FREE_ENDS = 1                                        # PNDF_TRACK_FREE_ENDS (pndf_project_options4.flags)
 NOISE_CODES = {"uniform": 0, "symmetric": 1}               # PNDF_ONLINE_*
 METRIC_CODES = {"geo": 0, "euc": 1}
 
@@ -49,6 +50,13 @@ class ProjectOptions3(ctypes.Structure):
     tracks of `frames` consecutive frames, the end frames held, `lambda_` the neighbour coupling of the interior ones, `fill` a
     PNDF_TRACK_* code; taken by the two entry points that take a ProjectOptions2"""
     _fields_ = [("base2", ProjectOptions2), ("frames", c_int32), ("lambda_", c_float), ("fill", c_int32), ("reserved2", c_int32)]
+
+
+class ProjectOptions4(ctypes.Structure):
+    """pndf_project_options4: the options with a mask and tracks (`base3`, with base3.base2.base.struct_size = 72) and an observation --
+    `anchor` [B,J,4] the noisy poses the data term pulls towards (None: no data term), `conf` [B,J] per-joint confidences (None: ones),
+    `mu` the data term's weight, `flags` 0 or TRACK_FREE_ENDS; taken by the two entry points that take a ProjectOptions3"""
+    _fields_ = [("base3", ProjectOptions3), ("anchor", c_void_p), ("conf", c_void_p), ("mu", c_float), ("flags", ctypes.c_uint32)]
 
 
 class DenoiseWeights(ctypes.Structure):
@@ -80,7 +88,7 @@ class PndfError(RuntimeError):
 _H = c_void_p                          # every handle type, and every `void* stream`
 _P = c_void_p                          # any other address: tensor data (an int from data_ptr(), or None), a callback, an out value
 _TENSORS = [POINTER(c_void_p), POINTER(c_int64), c_int]      # tensors, numel, n_tensors (host pointers in state-dict order)
-_OPT2 = c_void_p                       # `const pndf_project_options*` where it may point to a ProjectOptions, a ProjectOptions2 or a ProjectOptions3 (byref of any)
+_OPT2 = c_void_p                       # `const pndf_project_options*` where it may point to a ProjectOptions, a ProjectOptions2, a ProjectOptions3 or a ProjectOptions4 (byref of any)
 # ---- the header set, stated once: header of include/ -> {name: (restype, argtypes)} in the header's order; the headers in the order
 # they were added.  A new header is a file in include/, a table here and its declaration count in tests/test_cabi.py.
 DEBUG_HEADER = "posendf_amd_debug.h"      # the one header that lives in libposendf_amd_debug.so; every other one in the product library

@@ -5,7 +5,8 @@
 // fallback: the device entry points never route here, a missing GPU still fails loudly there.  The first-order twins take the joint
 // count and the parent table from the handle's config (any joint tree of include/posendf_amd_skeleton.h, pndf_net_plan.h); on the
 // SMPL table they compute what they did with the table fixed.  pndf_complete_cpu, pndf_interpolate_cpu and the second order stay 21-joint;
-// pndf_project_ex_cpu completes and interpolates for any joint tree (pndf_project_options2 / pndf_project_options3).
+// pndf_project_ex_cpu completes, interpolates and denoises for any joint tree (pndf_project_options2 / pndf_project_options3 /
+// pndf_project_options4).
 //
 // Layout: poses are processed in blocks of PB = 32; inside a block every activation tensor is [feature][pose] so that the
 // inner loop of a layer runs over the 32 poses of the block (contiguous floats: one or two AVX-512 / four AVX2 registers)
@@ -396,21 +397,28 @@ static const char* const SMPL_ONLY = "this entry point runs the 21-joint table o
 
 // One step of pndf_project_ex on the host: pndf_step.h's pndf_step_quat -- the statement the device kernels run -- for every joint of
 // a pose that does not rest.  `held`: bit j = joint j is observed and stays as it is (pndf_complete_cpu, and pndf_project_ex_cpu with the
-// mask of a pndf_project_options2; without one it holds none).
-static void project_step_cpu(float* q, const float* dq, float d, const pndf_project_options& o, uint32_t held, int nj) {
+// mask of a pndf_project_options2; without one it holds none).  `anchor` / `conf`: the pose's rows of the observation of a
+// pndf_project_options4 (null: none): then the step is pndf_interp.h's pndf_denoise_quat without neighbours, the data term alone.
+static void project_step_cpu(float* q, const float* dq, float d, const pndf_project_options& o, uint32_t held, int nj,
+                             const float* anchor = nullptr, const float* conf = nullptr, float mu = 0.f) {
     if (o.tol > 0.f && d < o.tol) return;
     for (int j = 0; j < nj; ++j) {
         if ((held >> j) & 1u) continue;
         float u[4];
-        (void)pndf_step_quat(q + 4 * j, dq + 4 * j, d, o.step_size, o.tol, (int)o.renorm, u);
+        if (anchor) {
+            const float w = conf ? mu * conf[j] : mu;
+            (void)pndf_denoise_quat(q + 4 * j, dq + 4 * j, d, nullptr, nullptr, 0, 0.f, anchor + 4 * j, w, o.step_size, o.tol, (int)o.renorm, u);
+        } else {
+            (void)pndf_step_quat(q + 4 * j, dq + 4 * j, d, o.step_size, o.tol, (int)o.renorm, u);
+        }
         memcpy(q + 4 * j, u, sizeof(u));
     }
 }
 
 // The loop of pndf_project_ex_cpu and pndf_complete_cpu (validated arguments): `steps` times forward + gradient and the step, block by
-// block; `observed` null = no joint held.
+// block; `observed` null = no joint held; `data`: the observation of a pndf_project_options4 (none: the step without a data term).
 static int project_loop_cpu(pndf_cpu_handle h, const float* q_in, const uint32_t* observed, float* q_out, float* d_last, int64_t B,
-                            int steps, const pndf_project_options& o) {
+                            int steps, const pndf_project_options& o, const PndfData& data = PndfData()) {
     const int NQ = h->nq();
     return guarded(h, [&] {
     parallel_blocks(B, [&](int64_t p0, int nb, Scratch& S) {
@@ -419,7 +427,9 @@ static int project_loop_cpu(pndf_cpu_handle h, const float* q_in, const uint32_t
         for (int p = 0; p < nb; ++p) dd[p] = 0.f;
         for (int s = 0; s < steps; ++s) {
             forward_grad_block(*h, qb, nb, nullptr, dd, dqb, true, S);
-            for (int p = 0; p < nb; ++p) project_step_cpu(qb + p * NQ, dqb + p * NQ, dd[p], o, observed ? observed[p0 + p] : 0u, h->net.nj);
+            for (int p = 0; p < nb; ++p)
+                project_step_cpu(qb + p * NQ, dqb + p * NQ, dd[p], o, observed ? observed[p0 + p] : 0u, h->net.nj,
+                                 data.anchor ? data.anchor + (p0 + p) * NQ : nullptr, data.conf ? data.conf + (p0 + p) * h->net.nj : nullptr, data.mu);
         }
         memcpy(q_out + p0 * NQ, qb, sizeof(float) * nb * NQ);
         if (d_last) memcpy(d_last + p0, dd, sizeof(float) * nb);
@@ -448,10 +458,11 @@ extern "C" int pndf_complete_cpu(pndf_cpu_handle h, const float* q_in, const uin
 // around pndf_forward_grad_cpu.  A step reads the neighbour frames of the track as they were before it (out of place, like the
 // device), so the whole track takes one step at a time.  `fill` PNDF_TRACK_GIVEN: `a` is the track [P*T] itself (`b` is not read);
 // otherwise pair p is the poses a + p * a_stride and b + p * b_stride.  With lambda == 0 this is project_loop_cpu on the filled
-// track with the end frames held, bit for bit.
+// track with the end frames held, bit for bit.  `data`: the observation and the free end frames of a pndf_project_options4 (motion
+// denoising; none: the band step, which pndf_denoise_quat is for an interior frame without a data term).
 static int track_loop_cpu(pndf_cpu_handle h, const float* a, int64_t a_stride, const float* b, int64_t b_stride, int fill,
                           const uint32_t* observed, float* track_out, float* d_last, int64_t P, int32_t T, int steps, float lambda,
-                          const pndf_project_options& o) {
+                          const pndf_project_options& o, const PndfData& data = PndfData()) {
     const int nj = h->net.nj;
     const int64_t nq = h->nq(), B = P * T;
     int rc = PNDF_OK;
@@ -477,11 +488,15 @@ static int track_loop_cpu(pndf_cpu_handle h, const float* a, int64_t a_stride, c
             if (rc != PNDF_OK) break;
             for (int64_t f = 0; f < B; ++f) {
                 const int k = (int)(f % T);
-                const uint32_t held = (k == 0 || k == T - 1) ? ~0u : (observed ? observed[f] : 0u);
+                const int nbr = (k > 0 ? 1 : 0) | (k < T - 1 ? 2 : 0);
+                const uint32_t held = (nbr != 3 && !data.free_ends) ? ~0u : (observed ? observed[f] : 0u);
                 for (int j = 0; j < nj; ++j) {
                     const int64_t i = (f * nj + j) * 4;
                     float u[4];
-                    if (((held >> j) & 1u) || pndf_interp_band_quat(cur + i, dq.data() + i, dd[f], cur + i - nq, cur + i + nq, lambda, o.step_size, o.tol, (int)o.renorm, u))
+                    const float w = !data.anchor ? 0.f : data.conf ? data.mu * data.conf[f * nj + j] : data.mu;
+                    if (((held >> j) & 1u) ||
+                        pndf_denoise_quat(cur + i, dq.data() + i, dd[f], (nbr & 1) ? cur + i - nq : nullptr, (nbr & 2) ? cur + i + nq : nullptr, nbr, lambda,
+                                          data.anchor ? data.anchor + i : nullptr, w, o.step_size, o.tol, (int)o.renorm, u))
                         memcpy(nxt + i, cur + i, sizeof(float) * 4);
                     else
                         memcpy(nxt + i, u, sizeof(float) * 4);
@@ -500,18 +515,20 @@ extern "C" int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* 
     pndf_project_options o;
     const uint32_t* observed;      // a pndf_project_options2 brings the joint mask (host memory): completion for any joint tree
     PndfTracks tracks;             // a pndf_project_options3 the tracks besides: interpolation for any joint tree
-    if (const char* why = pndf_check_project_options3(opt, B, o, observed, tracks)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
-    if (!tracks.frames && !observed && pndf_project_options_plain(o)) return pndf_project_cpu(h, q_in, q_out, d_last, B, steps);
+    PndfData data;                 // a pndf_project_options4 the observation besides (host memory): motion denoising for any joint tree
+    if (const char* why = pndf_check_project_options4(opt, B, o, observed, tracks, data)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (!tracks.frames && !observed && !data.any() && pndf_project_options_plain(o)) return pndf_project_cpu(h, q_in, q_out, d_last, B, steps);
     if (int rc = check(h, q_in, B)) return rc;
     if (steps < 0 || (B > 0 && !q_out)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count or null output pointer");
-    if (!tracks.frames) return project_loop_cpu(h, q_in, observed, q_out, d_last, B, steps, o);
+    if (const char* why = pndf_check_observation_apart(data, q_out, B, h->net.nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (!tracks.frames) return project_loop_cpu(h, q_in, observed, q_out, d_last, B, steps, o, data);
     if (B == 0) return PNDF_OK;
     const int64_t nq = h->nq(), T = tracks.frames;
     if ((uintptr_t)q_in < (uintptr_t)(q_out + B * nq) && (uintptr_t)q_out < (uintptr_t)(q_in + B * nq))
         return pndf_fail(h, PNDF_ERR_BAD_ARG, "q_out must not overlap q_in when pndf_project_options3.frames > 0: a step reads the neighbour "
                                               "frames of its input");
     return track_loop_cpu(h, q_in, T * nq, q_in + (T - 1) * nq, T * nq, tracks.fill, observed, q_out, d_last, B / T, (int32_t)T, steps,
-                          tracks.lambda, o);
+                          tracks.lambda, o, data);
 }
 
 // Host twin of pndf_interpolate (include/posendf_amd_interpolation.h): track_loop_cpu on the 21-joint table; with lambda == 0 this is

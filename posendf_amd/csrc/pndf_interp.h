@@ -60,6 +60,49 @@ PNDF_HD bool pndf_interp_band_quat(const float* Q, const float* G, float dist, c
     return pndf_step_finish(dist, tol, renorm, u);
 }
 
+// A free joint quaternion of the denoising step (pndf_project_options4; DESIGN.md section 2j "Motion denoising"): the band step with
+// end frames that may be free and a data term towards the observation.  `nbr`: which neighbour frames the joint has, bit 0 = nm, bit
+// 1 = np -- 3 an interior frame (exactly pndf_interp_band_quat's coupling), 1 or 2 a free end frame with its one neighbour, 0 none (no
+// tracks); a neighbour is read only when its bit is set and lambda > 0.  w = mu * conf, rounded once by the caller; `A`, the joint of
+// the observation, is read only when w > 0 (false for a zero, negative or NaN weight).  Returns the rest flag of pndf_step_finish.
+PNDF_HD bool pndf_denoise_quat(const float* Q, const float* G, float dist, const float* nm, const float* np, int nbr, float lambda,
+                               const float* A, float w, float alpha, float tol, int renorm, float* u) {
+#pragma clang fp contract(off)
+    pndf_step_descend(Q, G, dist, alpha, u);
+    if (lambda > 0.f && nbr == 3) {
+        float am[4], ap[4];
+        pndf_quat_align(Q, nm, am);
+        pndf_quat_align(Q, np, ap);
+        for (int c = 0; c < 4; ++c) {
+            const float sum = am[c] + ap[c];
+            const float h = 0.5f * sum;
+            const float m = h - Q[c];
+            const float lm = lambda * m;
+            u[c] = u[c] + lm;
+        }
+    } else if (lambda > 0.f && nbr != 0) {
+        float n[4], an[4];
+        for (int c = 0; c < 4; ++c) n[c] = nbr == 1 ? nm[c] : np[c];
+        pndf_quat_align(Q, n, an);
+        for (int c = 0; c < 4; ++c) {
+            const float m = an[c] - Q[c];
+            const float h = 0.5f * m;
+            const float lm = lambda * h;
+            u[c] = u[c] + lm;
+        }
+    }
+    if (w > 0.f) {
+        float aa[4];
+        pndf_quat_align(Q, A, aa);
+        for (int c = 0; c < 4; ++c) {
+            const float m = aa[c] - Q[c];
+            const float wm = w * m;
+            u[c] = u[c] + wm;
+        }
+    }
+    return pndf_step_finish(dist, tol, renorm, u);
+}
+
 // P pairs of T frames are P * T poses for the engine and the kernels: the reason a shape is refused, or nullptr
 inline const char* pndf_interp_check_shape(int64_t P, int32_t T) {
     if (T < 2) return "an interpolation has at least two frames (T >= 2)";

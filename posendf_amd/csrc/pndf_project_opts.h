@@ -1,7 +1,8 @@
 // Validation of pndf_project_options (include/posendf_amd.h), shared by pndf_project_ex (pndf_capi.hip) and its host twin
 // pndf_project_ex_cpu (pndf_cpu.cpp): the two refuse the same structs with the same text.  And of pndf_project_options2, the options with
 // a joint mask, which pndf_skel_project (pndf_skeleton.hip) and pndf_project_ex_cpu take besides, and of pndf_project_options3, the
-// options with tracks (pose interpolation inside the step), which the same two take.
+// options with tracks (pose interpolation inside the step), and of pndf_project_options4, the options with an observation (motion
+// denoising inside the step), which the same two take.
 #pragma once
 #include <math.h>
 
@@ -89,6 +90,74 @@ inline const char* pndf_check_project_options3(const pndf_project_options* opt, 
     tracks.frames = o3->frames;
     tracks.lambda = o3->lambda;
     tracks.fill = o3->fill;
+    return nullptr;
+}
+
+// The observation of a pndf_project_options4, validated: anchor null = no data term (then conf null and mu 0; a struct with mu == 0
+// arrives here like that too, so its anchors are never read)
+struct PndfData {
+    const float* anchor = nullptr;
+    const float* conf = nullptr;
+    float mu = 0.f;
+    bool free_ends = false;
+    // whether a call needs the denoising form of the step at all: without either it is the call of the 48-byte struct
+    bool any() const { return anchor || free_ends; }
+};
+
+// The checker of the same two entry points for all four structs: a pndf_project_options4 brings the observation of motion denoising
+// besides.  Returns nullptr and fills `out`, `observed`, `tracks` and `data`, or the reason the struct is refused.  That anchor and
+// conf do not overlap q_out is the caller's to check: it knows the size of a pose.
+inline const char* pndf_check_project_options4(const pndf_project_options* opt, int64_t B, pndf_project_options& out,
+                                               const uint32_t*& observed, PndfTracks& tracks, PndfData& data) {
+    data = PndfData();
+    if (!opt || opt->struct_size != sizeof(pndf_project_options4)) {
+        const char* why = pndf_check_project_options3(opt, B, out, observed, tracks);
+        if (why && opt && opt->struct_size != sizeof(pndf_project_options) && opt->struct_size != sizeof(pndf_project_options2) &&
+            opt->struct_size != sizeof(pndf_project_options3))
+            return "pndf_project_options.struct_size is none of sizeof(pndf_project_options), sizeof(pndf_project_options2), "
+                   "sizeof(pndf_project_options3) and sizeof(pndf_project_options4): fill the struct with pndf_default_project_options";
+        return why;
+    }
+    const pndf_project_options4* o4 = (const pndf_project_options4*)opt;
+    pndf_project_options3 base3 = o4->base3;
+    base3.base2.base.struct_size = (uint32_t)sizeof(pndf_project_options3);
+    if (const char* why = pndf_check_project_options3(&base3.base2.base, B, out, observed, tracks)) return why;
+    const uint32_t* mask = observed;
+    const PndfTracks tr = tracks;
+    observed = nullptr;      // (set again below: a refusal leaves no mask and no tracks behind)
+    tracks = PndfTracks();
+    if (!(o4->mu >= 0.f && o4->mu <= 1.f)) return "pndf_project_options4.mu must lie in [0, 1] (and not be NaN)";
+    if (o4->flags & ~(uint32_t)PNDF_TRACK_FREE_ENDS) return "pndf_project_options4.flags has a bit other than PNDF_TRACK_FREE_ENDS";
+    if (!o4->anchor && o4->mu != 0.f) return "pndf_project_options4.mu must be 0 when anchor is NULL (no data term)";
+    if (!o4->anchor && o4->conf) return "pndf_project_options4.conf must be NULL when anchor is NULL (no data term)";
+    if ((uintptr_t)o4->anchor & 3) return "pndf_project_options4.anchor must be 4-byte aligned";
+    if ((uintptr_t)o4->conf & 3) return "pndf_project_options4.conf must be 4-byte aligned";
+    if (o4->flags & PNDF_TRACK_FREE_ENDS) {
+        if (tr.frames == 0) return "pndf_project_options4.flags: PNDF_TRACK_FREE_ENDS needs tracks (pndf_project_options3.frames >= 2)";
+        if (tr.fill != PNDF_TRACK_GIVEN)
+            return "pndf_project_options4.flags: PNDF_TRACK_FREE_ENDS needs pndf_project_options3.fill == PNDF_TRACK_GIVEN (a fill reads "
+                   "only the end frames)";
+    }
+    observed = mask;
+    tracks = tr;
+    if (o4->mu != 0.f) {
+        data.anchor = o4->anchor;
+        data.conf = o4->conf;
+        data.mu = o4->mu;
+    }
+    data.free_ends = (o4->flags & PNDF_TRACK_FREE_ENDS) != 0;
+    return nullptr;
+}
+
+// What the entry point adds to the checker, knowing the size of a pose: every step reads the observation, so neither anchor [B,J,4]
+// nor conf [B,J] may share memory with q_out [B,J,4] (q_in may: the observation is usually the start).  nullptr, or the reason.
+inline const char* pndf_check_observation_apart(const PndfData& data, const float* q_out, int64_t B, int nj) {
+    if (B <= 0 || !q_out) return nullptr;
+    const uintptr_t o0 = (uintptr_t)q_out, o1 = (uintptr_t)(q_out + B * nj * 4);
+    if (data.anchor && (uintptr_t)data.anchor < o1 && o0 < (uintptr_t)(data.anchor + B * nj * 4))
+        return "pndf_project_options4.anchor must not overlap q_out: every step reads the observation";
+    if (data.conf && (uintptr_t)data.conf < o1 && o0 < (uintptr_t)(data.conf + B * nj))
+        return "pndf_project_options4.conf must not overlap q_out: every step reads the confidences";
     return nullptr;
 }
 

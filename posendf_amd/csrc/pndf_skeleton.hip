@@ -20,7 +20,9 @@
 //                              pndf_project_options3 (pose interpolation: lane c is frame c % T of its track) its second
 //                              instantiation pndf_skel_enc_rev_track_kernel: the end frames are held and a free joint of an
 //                              interior frame takes the neighbour coupling of pndf_interp.h between the descent and the
-//                              renormalisation, out of place
+//                              renormalisation, out of place; with the observation or the free end frames of a
+//                              pndf_project_options4 (motion denoising) its third instantiation pndf_skel_enc_rev_denoise_kernel:
+//                              pndf_denoise_quat of pndf_interp.h, with tracks (out of place) or without (in place allowed)
 //   pndf_skel_fill_kernel      the fill of a track from its two end frames, once per chunk in front of the steps
 // 2 + 2 L launches per evaluation.  No float atomics, no communication between workgroups, every column of a GEMM summed in the
 // same order wherever it sits: the same inputs give the same bits and a pose's result does not depend on its batch.
@@ -74,6 +76,16 @@ struct SkArgs {
     float lambda;             // the neighbour coupling of an interior frame
     int parent[MAXJ];
     int off[MAXJ];
+};
+
+// SkArgs with the observation of a pndf_project_options4 (SK_PROJECT), which the host side carries and pndf_skel_enc_rev_denoise_kernel
+// alone takes: every other kernel takes the SkArgs part as it was, so its hidden kernel arguments -- which follow the struct -- keep
+// their offsets and its code stays what it was to the byte.
+struct SkDenoiseArgs : SkArgs {
+    const float* anchor;      // the chunk's observation [n][4 nj], or null (no data term)
+    const float* conf;        // the chunk's confidences [n][nj], or null (ones)
+    float mu;                 // the weight of the data term
+    uint32_t flags;           // PNDF_TRACK_FREE_ENDS: the end frames of a track are not held
 };
 
 // bone j forward on column c: the parent's features are read back from act0 (a per-thread feature array indexed by a run-time
@@ -145,10 +157,15 @@ extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_fwd_kernel(SkArg
 
 // The reverse of the encoder and of the normalisation: per component column k with s = |q_k| and x = q_k / s,
 // d d / d q = (g_x - x (x . g_x)) / s; where the norm is clamped the normalisation is linear, g_x / eps.  Then grad_out, or the step.
-// TRACKS: the instantiation of a projection with tracks (e.frames >= 2); every other call runs the one without, which has no branch on
-// the tracks and no neighbour registers (as a branch in one kernel the tracks cost the call without them up to 0.2 %).
-template <bool TRACKS>
-__device__ __forceinline__ void skel_enc_rev(const SkArgs& e) {
+// KIND: SK_REV_TRACKS is the instantiation of a projection with tracks (e.frames >= 2); SK_REV_PLAIN runs every other call that brings no
+// observation and no free ends, with no branch on the tracks and no neighbour registers (as a branch in one kernel the tracks cost the
+// call without them up to 0.2 %).  SK_REV_DENOISE is the instantiation of a pndf_project_options4 with an anchor and / or
+// free end frames, with tracks (e.frames >= 2) or without (e.frames == 0): pndf_denoise_quat of pndf_interp.h in place of the step.
+enum { SK_REV_PLAIN = 0, SK_REV_TRACKS = 1, SK_REV_DENOISE = 2 };
+template <int KIND, class Args>
+__device__ __forceinline__ void skel_enc_rev(const Args& e) {
+    constexpr bool TRACKS = KIND == SK_REV_TRACKS;
+    constexpr bool DENOISE = KIND == SK_REV_DENOISE;
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= e.n) return;
     if (e.encoder)
@@ -176,6 +193,15 @@ __device__ __forceinline__ void skel_enc_rev(const SkArgs& e) {
         if (k == 0 || k == e.frames - 1) held = ~0u;
         else lambda = e.lambda;
     }
+    int nbr = 0;             // DENOISE: bit 0 = frame c - 1, bit 1 = frame c + 1 is a frame of the same track (and chunk)
+    if constexpr (DENOISE) {
+        if (e.frames) {
+            const int k = (int)(c % e.frames);
+            nbr = (k > 0 ? 1 : 0) | (k < e.frames - 1 ? 2 : 0);
+            if (nbr != 3 && !(e.flags & PNDF_TRACK_FREE_ENDS)) held = ~0u;
+            lambda = e.lambda;
+        }
+    }
     for (int j = 0; j < e.nj; ++j) {
         float g[BONE];
 #pragma unroll
@@ -198,6 +224,20 @@ __device__ __forceinline__ void skel_enc_rev(const SkArgs& e) {
                         np[k] = q[j * BONE + k + nq];
                     }
                 rest = pndf_interp_band_quat(Q, g, dist, nm, np, lambda, e.step_size, e.tol, e.renorm, u);      // lambda 0: pndf_step_quat
+            } else if constexpr (DENOISE) {
+                float nm[BONE] = {0.f, 0.f, 0.f, 0.f}, np[BONE] = {0.f, 0.f, 0.f, 0.f}, A[BONE] = {0.f, 0.f, 0.f, 0.f};
+                if (lambda > 0.f && (nbr & 1))
+#pragma unroll
+                    for (int k = 0; k < BONE; ++k) nm[k] = q[j * BONE + k - nq];
+                if (lambda > 0.f && (nbr & 2))
+#pragma unroll
+                    for (int k = 0; k < BONE; ++k) np[k] = q[j * BONE + k + nq];
+                float w = 0.f;      // the weight of the data term: mu * conf, rounded once; the anchor is read only when it is positive
+                if (e.anchor) w = e.conf ? e.mu * e.conf[c * e.nj + j] : e.mu;
+                if (w > 0.f)
+#pragma unroll
+                    for (int k = 0; k < BONE; ++k) A[k] = e.anchor[c * nq + j * BONE + k];
+                rest = pndf_denoise_quat(Q, g, dist, nm, np, nbr, lambda, A, w, e.step_size, e.tol, e.renorm, u);
             } else {
                 rest = pndf_step_quat(Q, g, dist, e.step_size, e.tol, e.renorm, u);
             }
@@ -214,8 +254,9 @@ __device__ __forceinline__ void skel_enc_rev(const SkArgs& e) {
     if (e.d_out) e.d_out[c] = dist;
 }
 
-extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_kernel(SkArgs e) { skel_enc_rev<false>(e); }
-extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_track_kernel(SkArgs e) { skel_enc_rev<true>(e); }
+extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_kernel(SkArgs e) { skel_enc_rev<SK_REV_PLAIN>(e); }
+extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_track_kernel(SkArgs e) { skel_enc_rev<SK_REV_TRACKS>(e); }
+extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_denoise_kernel(SkDenoiseArgs e) { skel_enc_rev<SK_REV_DENOISE>(e); }
 
 // The fill of a chunk of whole tracks (pndf_project_options3, PNDF_TRACK_SLERP / _NLERP): one lane per joint quaternion.  Of every track
 // only frames 0 (a) and T-1 (b) of `src` are read; frame 0 of `dst` takes the bits of a, frame T-1 b aligned to a, the frames between
@@ -302,26 +343,28 @@ SkLayout sk_layout(const pndf_skel_plan* h, int64_t B) {
 }
 
 // One evaluation of a chunk of n poses at `q`: the 2 + 2 L launches (the forward alone: 1 + L and the copy of the output row)
-void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, SkArgs e, hipStream_t st) {
+void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const SkDenoiseArgs& e, hipStream_t st) {
     const int n = (int)e.n;
     TrunkWeights w{};
     TrunkBuffers b{};
     for (int t = 0; t < h->L; ++t) { w.W[t] = h->d_blob + h->w_off[t]; w.b[t] = h->d_blob + h->b_off[t]; b.D1[t] = ws + l.D1[t]; }
     b.in = ws + l.act0; b.P[0] = ws + l.P[0]; b.P[1] = ws + l.P[1]; b.out = ws + l.dist; b.din = ws + l.U0;
     b.ld = l.nc; b.n = n;
-    hipLaunchKernelGGL(pndf_skel_enc_fwd_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
+    const SkArgs& plain = e;      // what every kernel but the denoising one takes
+    hipLaunchKernelGGL(pndf_skel_enc_fwd_kernel, dim3(blocks(n)), dim3(256), 0, st, plain);
     trunk_forward(SK_GEMM, *h, w, b, st);
     if (e.mode == SK_FORWARD) {
         hipLaunchKernelGGL(pndf_skel_copy_kernel, dim3(blocks(n)), dim3(256), 0, st, ws + l.dist, e.d_out, (int64_t)n);
         return;
     }
     trunk_reverse(SK_GEMM, *h, w, b, st);      // grad_out scales the result in the encoder's reverse
-    if (e.mode == SK_PROJECT && e.frames) hipLaunchKernelGGL(pndf_skel_enc_rev_track_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
-    else hipLaunchKernelGGL(pndf_skel_enc_rev_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
+    if (e.mode == SK_PROJECT && (e.anchor || e.flags)) hipLaunchKernelGGL(pndf_skel_enc_rev_denoise_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
+    else if (e.mode == SK_PROJECT && e.frames) hipLaunchKernelGGL(pndf_skel_enc_rev_track_kernel, dim3(blocks(n)), dim3(256), 0, st, plain);
+    else hipLaunchKernelGGL(pndf_skel_enc_rev_kernel, dim3(blocks(n)), dim3(256), 0, st, plain);
 }
 
-SkArgs sk_args(const pndf_skel_plan* h, const SkLayout& l, float* ws, int mode) {
-    SkArgs e;
+SkDenoiseArgs sk_args(const pndf_skel_plan* h, const SkLayout& l, float* ws, int mode) {
+    SkDenoiseArgs e;
     memset(&e, 0, sizeof(e));
     e.wenc = h->d_blob;
     e.X = ws + l.X; e.act0 = ws + l.act0; e.U0 = ws + l.U0; e.Gx = ws + l.Gx; e.dist = ws + l.dist;
@@ -431,7 +474,7 @@ extern "C" int pndf_skel_forward(pndf_skel_handle h, const float* q, float* d, i
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     float* ws = (float*)workspace;
-    SkArgs e = sk_args(h, l, ws, SK_FORWARD);
+    SkDenoiseArgs e = sk_args(h, l, ws, SK_FORWARD);
     for (int64_t c0 = 0; c0 < B; c0 += l.nc) {
         e.n = B - c0 < l.nc ? B - c0 : l.nc;
         e.q = q + c0 * h->nj * BONE;
@@ -454,7 +497,7 @@ extern "C" int pndf_skel_forward_grad(pndf_skel_handle h, const float* q, const 
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     float* ws = (float*)workspace;
-    SkArgs e = sk_args(h, l, ws, SK_GRAD);
+    SkDenoiseArgs e = sk_args(h, l, ws, SK_GRAD);
     for (int64_t c0 = 0; c0 < B; c0 += l.nc) {
         e.n = B - c0 < l.nc ? B - c0 : l.nc;
         e.q = q + c0 * h->nj * BONE;
@@ -472,7 +515,8 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
     pndf_project_options o;
     const uint32_t* observed;      // a pndf_project_options2 brings the joint mask: one word per pose, device memory
     PndfTracks tracks;             // a pndf_project_options3 the tracks besides: B / frames of them
-    if (const char* why = pndf_check_project_options3(opt, B, o, observed, tracks)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    PndfData data;                 // a pndf_project_options4 the observation besides (motion denoising): device memory, as the poses
+    if (const char* why = pndf_check_project_options4(opt, B, o, observed, tracks, data)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (steps < 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count");
     SkLayout l;
     if (B > 0 && (!q_in || !q_out)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose pointer");
@@ -482,6 +526,7 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
     if (B > 0 && tracks.frames && q_in == q_out)
         return pndf_fail(h, PNDF_ERR_BAD_ARG, "q_out must not overlap q_in when pndf_project_options3.frames > 0: a step reads the neighbour "
                                               "frames of its input");
+    if (const char* why = pndf_check_observation_apart(data, q_out, B, h->nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (const int rc = sk_check(h, B, workspace, workspace_bytes, l); rc != PNDF_OK || B == 0) return rc;
     PndfRange range("pndf_skel_project");
     DeviceGuard guard(h->device);
@@ -495,15 +540,18 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
         return PNDF_OK;
     }
     float* ws = (float*)workspace;
-    SkArgs e = sk_args(h, l, ws, SK_PROJECT);
+    SkDenoiseArgs e = sk_args(h, l, ws, SK_PROJECT);
     e.step_size = o.step_size; e.tol = o.tol; e.renorm = (int)o.renorm;
     e.frames = tracks.frames; e.lambda = tracks.lambda;
+    e.mu = data.mu; e.flags = data.free_ends ? (uint32_t)PNDF_TRACK_FREE_ENDS : 0u;
     // with tracks a chunk holds whole tracks, so no track straddles a seam and lane c of a chunk is frame c % T
     const int64_t nc = tracks.frames ? (l.nc / tracks.frames) * tracks.frames : l.nc;
     if (steps == 0 && d_last) HIP_TRY(h, hipMemsetAsync(d_last, 0, sizeof(float) * (size_t)B, st));
     for (int64_t c0 = 0; c0 < B; c0 += nc) {
         e.n = B - c0 < nc ? B - c0 : nc;
         e.observed = observed ? observed + c0 : nullptr;
+        e.anchor = data.anchor ? data.anchor + c0 * nq : nullptr;
+        e.conf = data.conf ? data.conf + c0 * h->nj : nullptr;
         // Without tracks the iterate is in q_out from the second step on: a lane reads its pose before it writes it.  With tracks a
         // step is out of place: the steps alternate between the chunk of q_out and the second pose buffer, the last one writes
         // q_out; step 0 reads q_in, or the buffer the fill wrote.

@@ -15,7 +15,7 @@ import numpy as np
 # public names stay importable from here.  `torch` comes from there too: abi imports it before the library is loaded (None without it).
 from .abi import (ACT_CODES, DEBUG_EXPERIMENT_WORDS, DEBUG_EXPORTS, EXPERIMENT_WORDS, EXPORTS, INTERP_MODES, METRIC_CODES,  # noqa: F401
                   NOISE_CODES, PRECISION_CODES, RENORM_CODES, Camera, DenoiseWeights, KeypointOpts, OnlineOpts, PndfConfig, PndfError,
-                  ProjectOptions, ProjectOptions2, ProjectOptions3, TRACK_FILLS, debug_library_path, experiment_word, load_library, torch)
+                  ProjectOptions, ProjectOptions2, ProjectOptions3, ProjectOptions4, TRACK_FILLS, TRACK_FREE_ENDS, debug_library_path, experiment_word, load_library, torch)
 
 
 def stream_handle(device) -> int:
@@ -134,6 +134,23 @@ def project_options3(lib, observed_ptr, frames, smooth=0.0, fill=None, step_size
     opt.base2.base.struct_size = ctypes.sizeof(opt)
     opt.frames, opt.lambda_, opt.fill, opt.reserved2 = int(frames), float(smooth), TRACK_FILLS[fill], 0
     return opt
+
+
+def project_options4(lib, observed_ptr, frames, smooth=0.0, fill=None, anchor_ptr=None, conf_ptr=None, data=0.0, free_ends=False,
+                     step_size=1.0, renorm="none", tol=0.0):
+    """pndf_project_options4 (include/posendf_amd.h): the options, the mask, the tracks and the observation of motion denoising --
+    `anchor_ptr` [B,J,4] the noisy poses (None: no data term), `conf_ptr` [B,J] per-joint confidences (None: ones), `data` the data term's
+    weight mu, `free_ends`: the end frames of a track are not held.  The values are checked by the library."""
+    opt = ProjectOptions4()
+    opt.base3 = project_options3(lib, observed_ptr, frames, smooth, fill, step_size, renorm, tol)
+    opt.base3.base2.base.struct_size = ctypes.sizeof(opt)
+    opt.anchor, opt.conf, opt.mu, opt.flags = anchor_ptr, conf_ptr, float(data), TRACK_FREE_ENDS if free_ends else 0
+    return opt
+
+
+def _anchored(anchor_ptr, conf_ptr, data, free_ends) -> bool:
+    """whether a `project` call names an observation or free end frames at all: only then is the 72-byte struct built"""
+    return anchor_ptr is not None or conf_ptr is not None or float(data) != 0.0 or bool(free_ends)
 
 
 def _tracked(frames, smooth, fill) -> bool:
@@ -476,11 +493,15 @@ class SkeletonEngine(_Handle):
                     "pndf_skel_forward_grad")
 
     def project(self, q_in_ptr, q_out_ptr, d_ptr, B, steps, ws_ptr, ws_bytes, stream=0, *, step_size=1.0, renorm="none", tol=0.0,
-                observed_ptr=None, frames=0, smooth=0.0, fill=None):
+                observed_ptr=None, frames=0, smooth=0.0, fill=None, anchor_ptr=None, conf_ptr=None, data=0.0, free_ends=False):
         """pndf_skel_project; `observed_ptr`: one uint32 per pose in device memory, bit j = joint j is held (pose completion, through a
         pndf_project_options2); None: no joint is held and the call is the one without a mask.  `frames` = T >= 2: the poses are B / T
-        tracks (pose interpolation, through a pndf_project_options3: `project_options3`), q_out apart from q_in"""
-        if _tracked(frames, smooth, fill):
+        tracks (pose interpolation, through a pndf_project_options3: `project_options3`), q_out apart from q_in.  `anchor_ptr` [B,J,4] /
+        `conf_ptr` [B,J] in device memory, `data` and `free_ends`: the observation of motion denoising (through a
+        pndf_project_options4: `project_options4`), apart from q_out"""
+        if _anchored(anchor_ptr, conf_ptr, data, free_ends):
+            opt = ctypes.byref(project_options4(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends, step_size, renorm, tol))
+        elif _tracked(frames, smooth, fill):
             opt = ctypes.byref(project_options3(self.lib, observed_ptr, frames, smooth, fill, step_size, renorm, tol))
         elif observed_ptr is None:
             opt = _opt_ref(self.lib, step_size, renorm, tol)
@@ -671,10 +692,16 @@ class CpuEngine(_Handle):
         self._check(self.lib.pndf_forward_grad_cpu(self.handle, q_ptr, gout_ptr, d_ptr, dq_ptr, B), "pndf_forward_grad_cpu")
 
     def project(self, q_in_ptr, q_out_ptr, d_ptr, B, steps, stream=0, *, step_size=1.0, renorm="none", tol=0.0, observed_ptr=None,
-                frames=0, smooth=0.0, fill=None):
+                frames=0, smooth=0.0, fill=None, anchor_ptr=None, conf_ptr=None, data=0.0, free_ends=False):
         """`observed_ptr`: one uint32 per pose in host memory, bit j = joint j is held (pndf_project_ex_cpu with a pndf_project_options2:
         any joint tree); None: the call without a mask.  `frames` = T >= 2: the poses are B / T tracks (pndf_project_ex_cpu with a
-        pndf_project_options3: `project_options3`)"""
+        pndf_project_options3: `project_options3`).  `anchor_ptr` [B,J,4] / `conf_ptr` [B,J] in host memory, `data` and `free_ends`: the
+        observation of motion denoising (pndf_project_ex_cpu with a pndf_project_options4: `project_options4`)"""
+        if _anchored(anchor_ptr, conf_ptr, data, free_ends):
+            opt4 = project_options4(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends, step_size, renorm, tol)
+            self._check(self.lib.pndf_project_ex_cpu(self.handle, q_in_ptr, q_out_ptr, d_ptr, B, int(steps), ctypes.byref(opt4)),
+                        "pndf_project_ex_cpu")
+            return
         if _tracked(frames, smooth, fill):
             opt3 = project_options3(self.lib, observed_ptr, frames, smooth, fill, step_size, renorm, tol)
             self._check(self.lib.pndf_project_ex_cpu(self.handle, q_in_ptr, q_out_ptr, d_ptr, B, int(steps), ctypes.byref(opt3)),

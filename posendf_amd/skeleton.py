@@ -15,7 +15,9 @@ table, with no fallback, and `posendf_amd.trainer.Trainer` trains the skeleton e
 the projection step of the unit's last kernel (or of the host twin), handed over in a pndf_project_options2 (include/posendf_amd.h);
 `posendf_amd.pose_completion.PoseCompletion` drives it with several hypotheses per pose.  `interpolate(pose_a, pose_b, frames)` is pose
 interpolation for the model's tree the same way: the tracks ride in a pndf_project_options3, the fill is one small kernel and the
-neighbour coupling sits in the step; `posendf_amd.pose_interpolation.PoseInterpolation` drives it.  The second order stays 21-joint
+neighbour coupling sits in the step; `posendf_amd.pose_interpolation.PoseInterpolation` drives it.  `denoise(track)` is motion
+denoising in quaternion space -- the pose prior, the neighbour coupling with free end frames and a data term towards the noisy
+observation, in a pndf_project_options4 --, which `posendf_amd.pose_denoising.PoseDenoising` drives.  The second order stays 21-joint
 (DESIGN.md section 8).
 """
 from __future__ import annotations
@@ -162,3 +164,61 @@ class SkeletonPoseNDF(PoseModel):
                         step_size=step_size, renorm=renormalize, tol=tol, observed_ptr=None if mask is None or B == 0 else mask.data_ptr(),
                         frames=T, smooth=smooth, fill=mode)
         return (track, d) if return_dist else track
+
+    @torch.no_grad()
+    def denoise(self, track, steps=100, smooth=0.25, data=0.25, conf=None, observed=None, free_ends=True, return_dist=True, *, step_size=1.0,
+                renormalize="unit", tol=0.0, anchor=None):
+        """Motion denoising for the model's tree, in quaternion space: `track` [P,T,J,4] (or [T,J,4], one clip) is the noisy observation,
+        which is both the start and the anchor.  Every step descends the distance field (the pose prior), couples every frame to its
+        neighbour frames with weight `smooth` in [0, 1] (the temporal term) and pulls every joint towards its observation with weight
+        `data` * conf in [0, 1] (the data term), all inside the projection step of the unit's last kernel (or of the host twin):
+        pndf_project_options4, include/posendf_amd.h.  `conf`: per-joint confidences [J], [T,J] or [P,T,J] (None: ones); a joint whose
+        confidence is zero, negative or NaN takes no data term and its observation is not read, so a missing detection may hold NaN --
+        but it is still the start of that joint, so give it a finite guess.  `observed`: bool [J], [T,J] or [P,T,J], joints held bit for
+        bit.  `free_ends` (default): the first and the last frame are as noisy as the rest and move; False holds them as `interpolate`
+        does.  T = 1 runs without tracks, with the data term only.  The whole clip is ONE engine call of 2 + 2 L launches per step and
+        the input is not written; a `train.device: cpu` model runs the host twin.  The defaults of `smooth` and `data` are untuned.
+        `anchor` (same shape as `track`): the observation where it is not the start -- the later iterations of `PoseDenoising` start
+        from the result of the iteration before and stay anchored to the original clip.
+        Returns (track [P,T,J,4], dist [P,T] of the last iteration) with the leading axis as given; step options: as `project`, with
+        unit quaternions as the default."""
+        J = self.num_joints
+        x = track.to(device=self.device).float()
+        if x.dim() not in (3, 4) or tuple(x.shape[-2:]) != (J, 4):
+            raise PndfError(f"a clip is [P,T,{J},4] or [T,{J},4], not {tuple(track.shape)}")
+        single = x.dim() == 3
+        q = x.reshape((-1,) + tuple(x.shape[-3:])).contiguous()
+        P, T = q.shape[0], q.shape[1]
+        if T < 1:
+            raise PndfError("a clip has at least one frame")
+        B = P * T
+        if anchor is None:
+            seen = q
+        else:
+            if tuple(anchor.shape) != tuple(track.shape):
+                raise PndfError(f"anchor has the clip's shape {tuple(track.shape)}, not {tuple(anchor.shape)}")
+            seen = anchor.to(device=self.device).float().reshape(q.shape).contiguous()
+        out = torch.empty_like(q)
+        d = torch.empty((P, T), device=q.device, dtype=torch.float32)
+
+        def per_joint(value, dtype, what):
+            v = torch.as_tensor(value, device=q.device)
+            if (dtype == torch.bool) != (v.dtype == torch.bool) or (dtype != torch.bool and not v.is_floating_point()):
+                raise PndfError(f"{what} is a {'bool' if dtype == torch.bool else 'floating-point'} tensor, not {v.dtype}")
+            if tuple(v.shape) not in ((J,), (T, J), (P, T, J)):
+                raise PndfError(f"{what} is [{J}], [{T},{J}] or [{P},{T},{J}], not {tuple(v.shape)}")
+            return v.to(dtype).expand(P, T, J).reshape(B, J).contiguous()
+
+        weights = None if conf is None else per_joint(conf, torch.float32, "conf")
+        mask = None if observed is None else pack_observed(per_joint(observed, torch.bool, "observed"), B, q.device, J)
+        eng = self._engine_for(q.device)
+        host = q.device.type == "cpu"
+        if B or host:       # as `project`
+            tracks = dict(frames=T, smooth=smooth, free_ends=bool(free_ends)) if T >= 2 else {}
+            eng.project(q.data_ptr(), out.data_ptr(), d.data_ptr(), B, int(steps), *(() if host else self._engine_args(eng, q.device, B)),
+                        step_size=step_size, renorm=renormalize, tol=tol, observed_ptr=None if mask is None or B == 0 else mask.data_ptr(),
+                        anchor_ptr=seen.data_ptr() if B else None, conf_ptr=None if weights is None or B == 0 else weights.data_ptr(), data=data if B else 0.0,
+                        **tracks)
+        if single:
+            out, d = out[0], d[0]
+        return (out, d) if return_dist else out
