@@ -216,6 +216,40 @@ typedef struct {
     uint32_t flags;               /* 0 or PNDF_TRACK_FREE_ENDS */
 } pndf_project_options4;          /* 72 bytes */
 
+/* The options with 3D keypoints: inverse kinematics under the learned prior inside the projection step, for any joint tree.  The joint
+ * tree with its rest offsets is the body model: rest[j] is joint j relative to its parent in the rest pose (the position of a root), and
+ * keypoint k is rigidly attached to joint kp_joint[k] at the local offset kp_offset[k] (zero: the joint itself; an end effector is a
+ * keypoint with an offset on a leaf).  For one pose Q [J,4], real part first:
+ *   r_j = Q_j / max(|Q_j|, 1e-12), R_j its rotation matrix;  root: G_j = R_j, p_j = t_j;  else: G_j = G_parent R_j, p_j = p_parent + G_parent t_j
+ *   P_k = p_a(k) + G_a(k) o_k        E(Q) = 1/2 sum_k w_k |P_k - Y_k|^2        w_k = kp_conf[pose][k] (1 when kp_conf is NULL)
+ * A keypoint whose w_k > 0 is false -- zero, negative or NaN -- takes no part and its target is NOT READ (the rule of anchor / conf).
+ * The step of a free joint quaternion is that of pndf_project_options4 with one more term, taken at the step's input iterate: the
+ * descent, the neighbour coupling, the data term w (A - Q), then u <- u - nu * dE/dQ_j, then renorm / flip / tol.  dE/dQ_j is the exact
+ * gradient with respect to the raw quaternion, through R(r) and through r = Q / |Q| (linear where the norm is clamped).  Held joints keep
+ * their bits and still rotate their subtree; a pose that rests under tol stays as it is; a joint without a keypoint in its subtree takes a
+ * gradient of exactly zero.  Targets are in the roots' frame.
+ * kp_target [B,K,3], kp_conf [B,K] and kp_energy [B] are DEVICE memory for pndf_skel_project and HOST memory for pndf_project_ex_cpu; rest,
+ * kp_joint and kp_offset are HOST memory in both and are read during the call.  With kp_target == NULL or nu == 0 the call is the one
+ * with the 72-byte struct, bit for bit, no keypoint array is read, and kp_energy (when given) is zeroed.  Fill it with
+ *   pndf_project_options5 o;  memset(&o, 0, sizeof o);  pndf_default_project_options(&o.base4.base3.base2.base);
+ *   o.base4.base3.base2.base.struct_size = sizeof o;  o.kp_target = detections;  o.rest = offsets;  o.n_keypoints = J;  o.nu = 0.02f;
+ * and pass (const pndf_project_options*)&o.  Exactly the two entry points that take a pndf_project_options4 take it.  PNDF_ERR_BAD_ARG
+ * with a text that names the field, before anything is launched or written: a struct_size that is none of the five sizes, a nu that is
+ * negative or not finite, with kp_target != NULL an n_keypoints outside 1 .. 64, rest == NULL, kp_joint == NULL with n_keypoints != J, a
+ * kp_joint entry outside 0 .. J-1, a rest or kp_offset value that is not finite; a misaligned pointer; kp_target, kp_conf or kp_energy
+ * overlapping q_out; and what is refused in `base4`. */
+typedef struct {
+    pndf_project_options4 base4;   /* base4.base3.base2.base.struct_size = sizeof(pndf_project_options5); mask, tracks, observation as before */
+    const float*   kp_target;      /* [B,K,3] or NULL (no keypoint term); DEVICE (pndf_skel_project) / HOST (pndf_project_ex_cpu) */
+    const float*   kp_conf;        /* [B,K] or NULL (ones); the same memory space */
+    float*         kp_energy;      /* [B] or NULL: E of the last iteration, evaluated before its update (as d_last); 0 when steps == 0 */
+    const float*   rest;           /* [J,3]; HOST memory in both entry points, read during the call */
+    const int32_t* kp_joint;       /* [K] in 0 .. J-1, HOST memory; NULL: K must equal J and keypoint k is joint k */
+    const float*   kp_offset;      /* [K,3], HOST memory; NULL: zeros */
+    int32_t        n_keypoints;    /* K, 1 .. 64 */
+    float          nu;             /* weight of the keypoint term, finite and >= 0 */
+} pndf_project_options5;           /* 128 bytes */
+
 /* pndf_project with step options.  opt == NULL means the defaults, and with the defaults the call is pndf_project bit for
  * bit.  PNDF_ERR_BAD_ARG (text in pndf_last_error; nothing is launched or written) for a struct_size other than
  * sizeof(pndf_project_options), a step_size that is not finite or <= 0, a tol that is NaN or < 0, an unknown renorm mode.
@@ -242,9 +276,9 @@ int pndf_forward_grad_cpu(pndf_cpu_handle h, const float* q, const float* grad_o
 int pndf_project_cpu(pndf_cpu_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps);      /* sample_poses.py:67-74 */
 int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps,
                         const pndf_project_options* opt);      /* pndf_project_ex: same semantics, same validation; also takes a
-                                                                  pndf_project_options2, a pndf_project_options3 or a
-                                                                  pndf_project_options4, `observed` / `anchor` / `conf`
-                                                                  in HOST memory */
+                                                                  pndf_project_options2, a pndf_project_options3, a
+                                                                  pndf_project_options4 or a pndf_project_options5,
+                                                                  `observed` / `anchor` / `conf` / `kp_*` in HOST memory */
 const char* pndf_cpu_last_error(pndf_cpu_handle h);   /* h may be NULL: last error of a failed pndf_cpu_create */
 
 /* Host-only weight packer (what pndf_load_weights uploads); needs no device.  Output sizes in floats come

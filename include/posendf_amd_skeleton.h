@@ -43,7 +43,15 @@
  * pndf_project_options4 (posendf_amd.h): anchor [B,J,4] and conf [B,J] in device memory beside the poses, mu and PNDF_TRACK_FREE_ENDS; the
  * terms sit in the step of the gradient's last kernel (its third instantiation), so a denoising step costs no launch more either.
  *
- * Still 21-joint: the second order (posendf_amd_second_order.h) only; pndf_complete, pndf_interpolate and their host twins keep the
+ * Keypoint fitting -- inverse kinematics under the learned prior: 3D detections of K keypoints attached to the joints, the joint tree
+ * with its rest offsets as the body model -- is the same two entry points with a pndf_project_options5 (posendf_amd.h): kp_target [B,K,3],
+ * kp_conf [B,K] and kp_energy [B] in device memory, the small tables rest [J,3], kp_joint [K] and kp_offset [K,3] in host memory (validated
+ * without a synchronisation, handed to the kernel as arguments).  The forward kinematics, its reverse and the term nu * dE/dQ sit in the
+ * step of the gradient's last kernel (its fourth instantiation), so a fitting step costs no launch more; the 72-byte struct's mask, tracks
+ * and observation come along unchanged.
+ *
+ * Still 21-joint: the second order (posendf_amd_second_order.h) only; 2D keypoints with a camera (pndf_keypoint_terms_grad, pndf_lbs_*) need
+ * the SMPL body model; pndf_complete, pndf_interpolate and their host twins keep the
  * SMPL table.
  */
 #ifndef POSENDF_AMD_SKELETON_H
@@ -69,8 +77,9 @@ int pndf_skel_load_weights(pndf_skel_handle h, const float* const* tensors, cons
 
 /* Bytes of the workspace of the three compute calls for B poses: a function of the plan and B only -- not of the options of a call --,
  * bounded (the batch is processed in chunks of at most 16,384 poses); 0 for B == 0; PNDF_ERR_BAD_ARG for a null handle or a negative B.
- * It includes, for every caller, one pose buffer [chunk][4 J] for the out-of-place steps of a projection with tracks: at most
- * 16,384 x 128 x 4 B = 8 MB. */
+ * It includes, for every caller, one pose buffer [chunk][4 J] for the out-of-place steps of a projection with tracks (at most
+ * 16,384 x 128 x 4 B = 8 MB) and the rows [24 J][chunk] of the forward kinematics and its adjoints of a pndf_project_options5 (at most
+ * 16,384 x 768 x 4 B = 48 MB). */
 int64_t pndf_skel_workspace_bytes(pndf_skel_handle h, int64_t B);
 
 /* forward(pose, train=False)['dist_pred']: q [B,J,4] -> d [B]. */
@@ -92,7 +101,9 @@ int pndf_skel_forward_grad(pndf_skel_handle h, const float* q, const float* grad
  * then processed in chunks of whole tracks, every step is out of place and q_out must not overlap q_in.  Or to a
  * pndf_project_options4: besides, `anchor` [B,J,4] and `conf` [B,J] (DEVICE memory, read by the kernels of this call; neither may overlap
  * q_out, both may be q_in) add the data term of weight mu * conf to every free joint, and PNDF_TRACK_FREE_ENDS frees the end frames of
- * every track; without tracks such a call may still run in place. */
+ * every track; without tracks such a call may still run in place.  Or to a pndf_project_options5: besides, kp_target [B,K,3], kp_conf [B,K]
+ * and kp_energy [B] (DEVICE memory; none may overlap q_out) and the HOST tables rest, kp_joint and kp_offset (read during the call) add the
+ * keypoint term of weight nu to every free joint; kp_energy is E of the last iteration, evaluated before its update, as d_last is. */
 int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps,
                       const pndf_project_options* opt, void* workspace, int64_t workspace_bytes, void* stream);
 

@@ -28,7 +28,10 @@ def __getattr__(name):   # torch is imported lazily so that numpy-only users (or
     if name in ("PoseDenoising", "denoise_track_file"):
         from . import pose_denoising
         return getattr(pose_denoising, name)
-    if name in ("SkeletonPoseNDF", "SKELETONS", "skeleton_config"):
+    if name in ("KeypointFitting", "fit_keypoint_file"):
+        from . import keypoint_fitting
+        return getattr(keypoint_fitting, name)
+    if name in ("SkeletonPoseNDF", "SKELETONS", "skeleton_config", "forward_kinematics"):
         from . import skeleton
         return getattr(skeleton, name)
     if name == "BodyModel":
@@ -42,5 +45,6 @@ def __getattr__(name):   # torch is imported lazily so that numpy-only users (or
 
 __all__ = ["PoseNDF", "gradient", "BodyModel", "PoseIndex", "Trainer", "PoseDataset", "OnlinePoseDataset", "OnlineOptions", "sample_noisy", "ImageFit", "PerspectiveCamera", "keypoint_term", "PoseCompletion", "PoseInterpolation",
            "PoseDenoising", "denoise_track_file",
-           "SkeletonPoseNDF", "SKELETONS", "skeleton_config",
+           "KeypointFitting", "fit_keypoint_file",
+           "SkeletonPoseNDF", "SKELETONS", "skeleton_config", "forward_kinematics",
            "amass_config", "load_config", "synth"]

@@ -59,6 +59,15 @@ class ProjectOptions4(ctypes.Structure):
     _fields_ = [("base3", ProjectOptions3), ("anchor", c_void_p), ("conf", c_void_p), ("mu", c_float), ("flags", ctypes.c_uint32)]
 
 
+class ProjectOptions5(ctypes.Structure):
+    """pndf_project_options5: the options with a mask, tracks and an observation (`base4`, with base4.base3.base2.base.struct_size = 128)
+    and 3D keypoints -- `kp_target` [B,K,3] the detections (None: no keypoint term), `kp_conf` [B,K] (None: ones), `kp_energy` [B] out (or
+    None), in the memory space of the poses; `rest` [J,3], `kp_joint` [K] (None: keypoint k is joint k) and `kp_offset` [K,3] (None: zeros)
+    in HOST memory; `n_keypoints` K, `nu` the term's weight; taken by the two entry points that take a ProjectOptions4"""
+    _fields_ = [("base4", ProjectOptions4), ("kp_target", c_void_p), ("kp_conf", c_void_p), ("kp_energy", c_void_p), ("rest", c_void_p),
+                ("kp_joint", c_void_p), ("kp_offset", c_void_p), ("n_keypoints", c_int32), ("nu", c_float)]
+
+
 class DenoiseWeights(ctypes.Structure):
     """pndf_denoise_weights: the loss weights of one outer iteration, evaluated"""
     _fields_ = [("prior_coef", c_float), ("prior_power", c_int32), ("temp_coef", c_float), ("data_coef", c_float)]
@@ -88,7 +97,7 @@ class PndfError(RuntimeError):
 _H = c_void_p                          # every handle type, and every `void* stream`
 _P = c_void_p                          # any other address: tensor data (an int from data_ptr(), or None), a callback, an out value
 _TENSORS = [POINTER(c_void_p), POINTER(c_int64), c_int]      # tensors, numel, n_tensors (host pointers in state-dict order)
-_OPT2 = c_void_p                       # `const pndf_project_options*` where it may point to a ProjectOptions, a ProjectOptions2, a ProjectOptions3 or a ProjectOptions4 (byref of any)
+_OPT2 = c_void_p                       # `const pndf_project_options*` where it may point to a ProjectOptions, a ProjectOptions2 .. a ProjectOptions5 (byref of any)
 # ---- the header set, stated once: header of include/ -> {name: (restype, argtypes)} in the header's order; the headers in the order
 # they were added.  A new header is a file in include/, a table here and its declaration count in tests/test_cabi.py.
 DEBUG_HEADER = "posendf_amd_debug.h"      # the one header that lives in libposendf_amd_debug.so; every other one in the product library

@@ -5,8 +5,8 @@
 // fallback: the device entry points never route here, a missing GPU still fails loudly there.  The first-order twins take the joint
 // count and the parent table from the handle's config (any joint tree of include/posendf_amd_skeleton.h, pndf_net_plan.h); on the
 // SMPL table they compute what they did with the table fixed.  pndf_complete_cpu, pndf_interpolate_cpu and the second order stay 21-joint;
-// pndf_project_ex_cpu completes, interpolates and denoises for any joint tree (pndf_project_options2 / pndf_project_options3 /
-// pndf_project_options4).
+// pndf_project_ex_cpu completes, interpolates, denoises and fits 3D keypoints for any joint tree (pndf_project_options2 /
+// pndf_project_options3 / pndf_project_options4 / pndf_project_options5).
 //
 // Layout: poses are processed in blocks of PB = 32; inside a block every activation tensor is [feature][pose] so that the
 // inner loop of a layer runs over the 32 poses of the block (contiguous floats: one or two AVX-512 / four AVX2 registers)
@@ -32,6 +32,7 @@
 #include "../../include/posendf_amd_completion.h"
 #include "../../include/posendf_amd_second_order.h"
 #include "pndf_error.h"
+#include "pndf_fk.h"
 #include "pndf_interp.h"
 #include "pndf_layout.h"
 #include "pndf_online.h"
@@ -399,13 +400,39 @@ static const char* const SMPL_ONLY = "this entry point runs the 21-joint table o
 // a pose that does not rest.  `held`: bit j = joint j is observed and stays as it is (pndf_complete_cpu, and pndf_project_ex_cpu with the
 // mask of a pndf_project_options2; without one it holds none).  `anchor` / `conf`: the pose's rows of the observation of a
 // pndf_project_options4 (null: none): then the step is pndf_interp.h's pndf_denoise_quat without neighbours, the data term alone.
+// The host tables of a pndf_project_options5 with their defaults filled in (pndf_fill_keypoint_tables), as the kernel's arguments hold them
+struct KeypointTables {
+    float rest[3 * MAXJ];
+    int32_t kpj[PNDF_FK_MAX_KEYPOINTS];
+    float kpo[3 * PNDF_FK_MAX_KEYPOINTS];
+};
+
+// The keypoint term of pose number `pose` at the iterate q: pndf_fk.h's pndf_fk_energy_grad -- the statement the device kernel runs -- on
+// a local array of rows (ld = 1).  gk [nj][4] = d E / d Q; returns E.
+static float keypoint_grad_cpu(const PndfKeypoints& kp, const KeypointTables& tb, const int* parent, int nj, const float* q, int64_t pose,
+                               float* gk) {
+    float W[PNDF_FK_ROWS * MAXJ];
+    const float E = pndf_fk_energy_grad(q, nj, parent, tb.rest, kp.K, tb.kpj, tb.kpo, kp.target + pose * kp.K * 3,
+                                        kp.conf ? kp.conf + pose * kp.K : nullptr, W, 1);
+    for (int j = 0; j < nj; ++j)
+        for (int c = 0; c < 4; ++c) gk[4 * j + c] = W[pndf_fk_grad_row(nj, j) + c];
+    return E;
+}
+
+// `gk` (null: none): d E / d Q of the pose's keypoint term of a pndf_project_options5, `nu` its weight: then the step is pndf_fk.h's
+// pndf_fit_quat.
 static void project_step_cpu(float* q, const float* dq, float d, const pndf_project_options& o, uint32_t held, int nj,
-                             const float* anchor = nullptr, const float* conf = nullptr, float mu = 0.f) {
+                             const float* anchor = nullptr, const float* conf = nullptr, float mu = 0.f, const float* gk = nullptr,
+                             float nu = 0.f) {
     if (o.tol > 0.f && d < o.tol) return;
     for (int j = 0; j < nj; ++j) {
         if ((held >> j) & 1u) continue;
         float u[4];
-        if (anchor) {
+        if (gk) {
+            const float w = !anchor ? 0.f : conf ? mu * conf[j] : mu;
+            (void)pndf_fit_quat(q + 4 * j, dq + 4 * j, d, nullptr, nullptr, 0, 0.f, anchor ? anchor + 4 * j : nullptr, w, gk + 4 * j, nu, o.step_size,
+                                o.tol, (int)o.renorm, u);
+        } else if (anchor) {
             const float w = conf ? mu * conf[j] : mu;
             (void)pndf_denoise_quat(q + 4 * j, dq + 4 * j, d, nullptr, nullptr, 0, 0.f, anchor + 4 * j, w, o.step_size, o.tol, (int)o.renorm, u);
         } else {
@@ -418,21 +445,28 @@ static void project_step_cpu(float* q, const float* dq, float d, const pndf_proj
 // The loop of pndf_project_ex_cpu and pndf_complete_cpu (validated arguments): `steps` times forward + gradient and the step, block by
 // block; `observed` null = no joint held; `data`: the observation of a pndf_project_options4 (none: the step without a data term).
 static int project_loop_cpu(pndf_cpu_handle h, const float* q_in, const uint32_t* observed, float* q_out, float* d_last, int64_t B,
-                            int steps, const pndf_project_options& o, const PndfData& data = PndfData()) {
+                            int steps, const pndf_project_options& o, const PndfData& data = PndfData(),
+                            const PndfKeypoints& kp = PndfKeypoints()) {
     const int NQ = h->nq();
+    KeypointTables tb;
+    if (kp.any()) pndf_fill_keypoint_tables(tb, kp, h->net.nj);
     return guarded(h, [&] {
     parallel_blocks(B, [&](int64_t p0, int nb, Scratch& S) {
-        float qb[PB * 4 * MAXJ], dqb[PB * 4 * MAXJ], dd[PB];
+        float qb[PB * 4 * MAXJ], dqb[PB * 4 * MAXJ], dd[PB], ee[PB], gk[4 * MAXJ];
         memcpy(qb, q_in + p0 * NQ, sizeof(float) * nb * NQ);
-        for (int p = 0; p < nb; ++p) dd[p] = 0.f;
+        for (int p = 0; p < nb; ++p) dd[p] = ee[p] = 0.f;
         for (int s = 0; s < steps; ++s) {
             forward_grad_block(*h, qb, nb, nullptr, dd, dqb, true, S);
-            for (int p = 0; p < nb; ++p)
+            for (int p = 0; p < nb; ++p) {
+                if (kp.any()) ee[p] = keypoint_grad_cpu(kp, tb, h->net.parent, h->net.nj, qb + p * NQ, p0 + p, gk);
                 project_step_cpu(qb + p * NQ, dqb + p * NQ, dd[p], o, observed ? observed[p0 + p] : 0u, h->net.nj,
-                                 data.anchor ? data.anchor + (p0 + p) * NQ : nullptr, data.conf ? data.conf + (p0 + p) * h->net.nj : nullptr, data.mu);
+                                 data.anchor ? data.anchor + (p0 + p) * NQ : nullptr, data.conf ? data.conf + (p0 + p) * h->net.nj : nullptr, data.mu,
+                                 kp.any() ? gk : nullptr, kp.nu);
+            }
         }
         memcpy(q_out + p0 * NQ, qb, sizeof(float) * nb * NQ);
         if (d_last) memcpy(d_last + p0, dd, sizeof(float) * nb);
+        if (kp.energy) memcpy(kp.energy + p0, ee, sizeof(float) * nb);
     });
     });
 }
@@ -462,12 +496,14 @@ extern "C" int pndf_complete_cpu(pndf_cpu_handle h, const float* q_in, const uin
 // denoising; none: the band step, which pndf_denoise_quat is for an interior frame without a data term).
 static int track_loop_cpu(pndf_cpu_handle h, const float* a, int64_t a_stride, const float* b, int64_t b_stride, int fill,
                           const uint32_t* observed, float* track_out, float* d_last, int64_t P, int32_t T, int steps, float lambda,
-                          const pndf_project_options& o, const PndfData& data = PndfData()) {
+                          const pndf_project_options& o, const PndfData& data = PndfData(), const PndfKeypoints& kp = PndfKeypoints()) {
     const int nj = h->net.nj;
     const int64_t nq = h->nq(), B = P * T;
     int rc = PNDF_OK;
+    KeypointTables tb;
+    if (kp.any()) pndf_fill_keypoint_tables(tb, kp, nj);
     const int grc = guarded(h, [&] {
-        std::vector<float> other((size_t)(B * nq)), dq(steps ? (size_t)(B * nq) : 0), dd((size_t)B, 0.f);
+        std::vector<float> other((size_t)(B * nq)), dq(steps ? (size_t)(B * nq) : 0), dd((size_t)B, 0.f), ee((size_t)B, 0.f);
         float* cur = (steps & 1) ? other.data() : track_out;      // `steps` swaps later the track is in track_out
         float* nxt = (steps & 1) ? track_out : other.data();
         if (fill == PNDF_TRACK_GIVEN) memcpy(cur, a, sizeof(float) * (size_t)(B * nq));
@@ -490,13 +526,17 @@ static int track_loop_cpu(pndf_cpu_handle h, const float* a, int64_t a_stride, c
                 const int k = (int)(f % T);
                 const int nbr = (k > 0 ? 1 : 0) | (k < T - 1 ? 2 : 0);
                 const uint32_t held = (nbr != 3 && !data.free_ends) ? ~0u : (observed ? observed[f] : 0u);
+                float gk[4 * MAXJ];
+                if (kp.any()) ee[f] = keypoint_grad_cpu(kp, tb, h->net.parent, nj, cur + f * nq, f, gk);
                 for (int j = 0; j < nj; ++j) {
                     const int64_t i = (f * nj + j) * 4;
                     float u[4];
                     const float w = !data.anchor ? 0.f : data.conf ? data.mu * data.conf[f * nj + j] : data.mu;
+                    const float *nm = (nbr & 1) ? cur + i - nq : nullptr, *np = (nbr & 2) ? cur + i + nq : nullptr;
+                    const float* A = data.anchor ? data.anchor + i : nullptr;
                     if (((held >> j) & 1u) ||
-                        pndf_denoise_quat(cur + i, dq.data() + i, dd[f], (nbr & 1) ? cur + i - nq : nullptr, (nbr & 2) ? cur + i + nq : nullptr, nbr, lambda,
-                                          data.anchor ? data.anchor + i : nullptr, w, o.step_size, o.tol, (int)o.renorm, u))
+                        (kp.any() ? pndf_fit_quat(cur + i, dq.data() + i, dd[f], nm, np, nbr, lambda, A, w, gk + 4 * j, kp.nu, o.step_size, o.tol, (int)o.renorm, u)
+                                  : pndf_denoise_quat(cur + i, dq.data() + i, dd[f], nm, np, nbr, lambda, A, w, o.step_size, o.tol, (int)o.renorm, u)))
                         memcpy(nxt + i, cur + i, sizeof(float) * 4);
                     else
                         memcpy(nxt + i, u, sizeof(float) * 4);
@@ -505,6 +545,7 @@ static int track_loop_cpu(pndf_cpu_handle h, const float* a, int64_t a_stride, c
             std::swap(cur, nxt);
         }
         if (rc == PNDF_OK && d_last) memcpy(d_last, dd.data(), sizeof(float) * B);
+        if (rc == PNDF_OK && kp.energy) memcpy(kp.energy, ee.data(), sizeof(float) * B);
     });
     return grc != PNDF_OK ? grc : rc;
 }
@@ -516,19 +557,22 @@ extern "C" int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* 
     const uint32_t* observed;      // a pndf_project_options2 brings the joint mask (host memory): completion for any joint tree
     PndfTracks tracks;             // a pndf_project_options3 the tracks besides: interpolation for any joint tree
     PndfData data;                 // a pndf_project_options4 the observation besides (host memory): motion denoising for any joint tree
-    if (const char* why = pndf_check_project_options4(opt, B, o, observed, tracks, data)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
-    if (!tracks.frames && !observed && !data.any() && pndf_project_options_plain(o)) return pndf_project_cpu(h, q_in, q_out, d_last, B, steps);
+    PndfKeypoints kp;              // a pndf_project_options5 the 3D keypoints besides (host memory): keypoint fitting for any joint tree
+    if (const char* why = pndf_check_project_options5(opt, B, h->net.nj, o, observed, tracks, data, kp)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (!tracks.frames && !observed && !data.any() && !kp.any() && !kp.energy && pndf_project_options_plain(o))
+        return pndf_project_cpu(h, q_in, q_out, d_last, B, steps);
     if (int rc = check(h, q_in, B)) return rc;
     if (steps < 0 || (B > 0 && !q_out)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count or null output pointer");
     if (const char* why = pndf_check_observation_apart(data, q_out, B, h->net.nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
-    if (!tracks.frames) return project_loop_cpu(h, q_in, observed, q_out, d_last, B, steps, o, data);
+    if (const char* why = pndf_check_keypoints_apart(kp, q_out, B, h->net.nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (!tracks.frames) return project_loop_cpu(h, q_in, observed, q_out, d_last, B, steps, o, data, kp);
     if (B == 0) return PNDF_OK;
     const int64_t nq = h->nq(), T = tracks.frames;
     if ((uintptr_t)q_in < (uintptr_t)(q_out + B * nq) && (uintptr_t)q_out < (uintptr_t)(q_in + B * nq))
         return pndf_fail(h, PNDF_ERR_BAD_ARG, "q_out must not overlap q_in when pndf_project_options3.frames > 0: a step reads the neighbour "
                                               "frames of its input");
     return track_loop_cpu(h, q_in, T * nq, q_in + (T - 1) * nq, T * nq, tracks.fill, observed, q_out, d_last, B / T, (int32_t)T, steps,
-                          tracks.lambda, o, data);
+                          tracks.lambda, o, data, kp);
 }
 
 // Host twin of pndf_interpolate (include/posendf_amd_interpolation.h): track_loop_cpu on the 21-joint table; with lambda == 0 this is

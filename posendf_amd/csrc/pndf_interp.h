@@ -65,8 +65,10 @@ PNDF_HD bool pndf_interp_band_quat(const float* Q, const float* G, float dist, c
 // 1 = np -- 3 an interior frame (exactly pndf_interp_band_quat's coupling), 1 or 2 a free end frame with its one neighbour, 0 none (no
 // tracks); a neighbour is read only when its bit is set and lambda > 0.  w = mu * conf, rounded once by the caller; `A`, the joint of
 // the observation, is read only when w > 0 (false for a zero, negative or NaN weight).  Returns the rest flag of pndf_step_finish.
-PNDF_HD bool pndf_denoise_quat(const float* Q, const float* G, float dist, const float* nm, const float* np, int nbr, float lambda,
-                               const float* A, float w, float alpha, float tol, int renorm, float* u) {
+// pndf_fit_quat is that step with one more term in front of the finish, the keypoint term of a pndf_project_options5 (pndf_fk.h): with
+// gk, the gradient d E / d Q of the joint, not null, u <- u - nu * gk.
+PNDF_HD bool pndf_fit_quat(const float* Q, const float* G, float dist, const float* nm, const float* np, int nbr, float lambda, const float* A,
+                           float w, const float* gk, float nu, float alpha, float tol, int renorm, float* u) {
 #pragma clang fp contract(off)
     pndf_step_descend(Q, G, dist, alpha, u);
     if (lambda > 0.f && nbr == 3) {
@@ -100,7 +102,17 @@ PNDF_HD bool pndf_denoise_quat(const float* Q, const float* G, float dist, const
             u[c] = u[c] + wm;
         }
     }
+    if (gk)
+        for (int c = 0; c < 4; ++c) {
+            const float s = nu * gk[c];
+            u[c] = u[c] - s;
+        }
     return pndf_step_finish(dist, tol, renorm, u);
+}
+
+PNDF_HD bool pndf_denoise_quat(const float* Q, const float* G, float dist, const float* nm, const float* np, int nbr, float lambda,
+                               const float* A, float w, float alpha, float tol, int renorm, float* u) {
+    return pndf_fit_quat(Q, G, dist, nm, np, nbr, lambda, A, w, nullptr, 0.f, alpha, tol, renorm, u);
 }
 
 // P pairs of T frames are P * T poses for the engine and the kernels: the reason a shape is refused, or nullptr

@@ -2,7 +2,8 @@
 // pndf_project_ex_cpu (pndf_cpu.cpp): the two refuse the same structs with the same text.  And of pndf_project_options2, the options with
 // a joint mask, which pndf_skel_project (pndf_skeleton.hip) and pndf_project_ex_cpu take besides, and of pndf_project_options3, the
 // options with tracks (pose interpolation inside the step), and of pndf_project_options4, the options with an observation (motion
-// denoising inside the step), which the same two take.
+// denoising inside the step), and of pndf_project_options5, the options with 3D keypoints (keypoint fitting inside the step), which the
+// same two take.
 #pragma once
 #include <math.h>
 
@@ -159,6 +160,120 @@ inline const char* pndf_check_observation_apart(const PndfData& data, const floa
     if (data.conf && (uintptr_t)data.conf < o1 && o0 < (uintptr_t)(data.conf + B * nj))
         return "pndf_project_options4.conf must not overlap q_out: every step reads the confidences";
     return nullptr;
+}
+
+// The keypoints of a pndf_project_options5, validated: target null = no keypoint term (a struct with nu == 0 arrives here like that
+// too, so none of its keypoint arrays is read); `energy` stays, and without a term it is zeroed
+constexpr int32_t PNDF_MAX_KEYPOINTS = 64;
+struct PndfKeypoints {
+    const float* target = nullptr;
+    const float* conf = nullptr;
+    float* energy = nullptr;
+    const float* rest = nullptr;
+    const int32_t* joint = nullptr;       // null: keypoint k is joint k
+    const float* offset = nullptr;        // null: zeros
+    int32_t K = 0;
+    float nu = 0.f;
+    // what the struct names whether or not there is a term (nu == 0 leaves `target` null): pndf_check_keypoints_apart refuses their
+    // overlap with q_out either way, as the header says, though nothing reads them without a term
+    const float* named_target = nullptr;
+    const float* named_conf = nullptr;
+    int32_t named_K = 0;
+    bool any() const { return target != nullptr; }
+};
+
+// The checker of the same two entry points for all five structs: a pndf_project_options5 brings the 3D keypoints of a fit besides.
+// `nj`: the joint count of the handle, which sizes the host tables rest [nj,3], kp_joint [K] and kp_offset [K,3]; they are read here
+// (and only when there is a term: kp_target != NULL and nu != 0).  Returns nullptr and fills `out`, `observed`, `tracks`, `data` and
+// `kp`, or the reason the struct is refused.  That the device arrays do not overlap q_out is the caller's to check.
+inline const char* pndf_check_project_options5(const pndf_project_options* opt, int64_t B, int nj, pndf_project_options& out,
+                                               const uint32_t*& observed, PndfTracks& tracks, PndfData& data, PndfKeypoints& kp) {
+    kp = PndfKeypoints();
+    if (!opt || opt->struct_size != sizeof(pndf_project_options5)) {
+        const char* why = pndf_check_project_options4(opt, B, out, observed, tracks, data);
+        if (why && opt && opt->struct_size != sizeof(pndf_project_options) && opt->struct_size != sizeof(pndf_project_options2) &&
+            opt->struct_size != sizeof(pndf_project_options3) && opt->struct_size != sizeof(pndf_project_options4))
+            return "pndf_project_options.struct_size is none of sizeof(pndf_project_options), sizeof(pndf_project_options2), "
+                   "sizeof(pndf_project_options3), sizeof(pndf_project_options4) and sizeof(pndf_project_options5): fill the struct with "
+                   "pndf_default_project_options";
+        return why;
+    }
+    const pndf_project_options5* o5 = (const pndf_project_options5*)opt;
+    pndf_project_options4 base4 = o5->base4;
+    base4.base3.base2.base.struct_size = (uint32_t)sizeof(pndf_project_options4);
+    if (const char* why = pndf_check_project_options4(&base4.base3.base2.base, B, out, observed, tracks, data)) return why;
+    const uint32_t* mask = observed;
+    const PndfTracks tr = tracks;
+    const PndfData da = data;
+    observed = nullptr;      // (set again below: a refusal leaves no mask, no tracks and no observation behind)
+    tracks = PndfTracks();
+    data = PndfData();
+    if (!isfinite(o5->nu) || !(o5->nu >= 0.f)) return "pndf_project_options5.nu must be finite and zero or positive";
+    if ((uintptr_t)o5->kp_target & 3) return "pndf_project_options5.kp_target must be 4-byte aligned";
+    if ((uintptr_t)o5->kp_conf & 3) return "pndf_project_options5.kp_conf must be 4-byte aligned";
+    if ((uintptr_t)o5->kp_energy & 3) return "pndf_project_options5.kp_energy must be 4-byte aligned";
+    if ((uintptr_t)o5->rest & 3) return "pndf_project_options5.rest must be 4-byte aligned";
+    if ((uintptr_t)o5->kp_joint & 3) return "pndf_project_options5.kp_joint must be 4-byte aligned";
+    if ((uintptr_t)o5->kp_offset & 3) return "pndf_project_options5.kp_offset must be 4-byte aligned";
+    if (o5->kp_target) {
+        const int32_t K = o5->n_keypoints;
+        if (K < 1 || K > PNDF_MAX_KEYPOINTS) return "pndf_project_options5.n_keypoints must lie in 1 .. 64 when kp_target is not NULL";
+        if (!o5->rest) return "pndf_project_options5.rest must not be NULL when kp_target is not NULL: the rest offsets [J,3] of the joint tree";
+        if (!o5->kp_joint && K != nj)
+            return "pndf_project_options5.kp_joint is NULL (keypoint k is joint k), so n_keypoints must equal the joint count";
+        kp.named_target = o5->kp_target;
+        kp.named_conf = o5->kp_conf;
+        kp.named_K = K;
+        if (o5->nu != 0.f) {      // the tables are read only when there is a term
+            if (o5->kp_joint)
+                for (int32_t k = 0; k < K; ++k)
+                    if (o5->kp_joint[k] < 0 || o5->kp_joint[k] >= nj) return "pndf_project_options5.kp_joint has an entry outside 0 .. J-1";
+            for (int i = 0; i < 3 * nj; ++i)
+                if (!isfinite(o5->rest[i])) return "pndf_project_options5.rest has a value that is not finite";
+            if (o5->kp_offset)
+                for (int32_t i = 0; i < 3 * K; ++i)
+                    if (!isfinite(o5->kp_offset[i])) return "pndf_project_options5.kp_offset has a value that is not finite";
+            kp.target = o5->kp_target;
+            kp.conf = o5->kp_conf;
+            kp.rest = o5->rest;
+            kp.joint = o5->kp_joint;
+            kp.offset = o5->kp_offset;
+            kp.K = K;
+            kp.nu = o5->nu;
+        }
+    }
+    kp.energy = o5->kp_energy;
+    observed = mask;
+    tracks = tr;
+    data = da;
+    return nullptr;
+}
+
+// What the entry point adds to that checker, knowing B: every step reads the targets and the confidences and the last one writes the
+// energies, so none of kp_target [B,K,3], kp_conf [B,K] and kp_energy [B] may share memory with q_out [B,J,4].  nullptr, or the reason.
+// The arrays are compared as the struct names them, with a term (nu != 0) or without.
+inline const char* pndf_check_keypoints_apart(const PndfKeypoints& kp, const float* q_out, int64_t B, int nj) {
+    if (B <= 0 || !q_out) return nullptr;
+    const uintptr_t o0 = (uintptr_t)q_out, o1 = (uintptr_t)(q_out + B * nj * 4);
+    if (kp.named_target && (uintptr_t)kp.named_target < o1 && o0 < (uintptr_t)(kp.named_target + B * kp.named_K * 3))
+        return "pndf_project_options5.kp_target must not overlap q_out: every step reads the targets";
+    if (kp.named_conf && (uintptr_t)kp.named_conf < o1 && o0 < (uintptr_t)(kp.named_conf + B * kp.named_K))
+        return "pndf_project_options5.kp_conf must not overlap q_out: every step reads the confidences";
+    if (kp.energy && (uintptr_t)kp.energy < o1 && o0 < (uintptr_t)(kp.energy + B))
+        return "pndf_project_options5.kp_energy must not overlap q_out";
+    return nullptr;
+}
+
+// The host tables of validated keypoints as the step functions of pndf_fk.h take them: kp_joint and kp_offset with their defaults
+// filled in (keypoint k is joint k; zeros).  T: anything with rest [96], kpj [64] and kpo [192] -- the kernel's argument struct, the
+// host twin's local copy.
+template <class T>
+inline void pndf_fill_keypoint_tables(T& t, const PndfKeypoints& kp, int nj) {
+    for (int i = 0; i < 3 * nj; ++i) t.rest[i] = kp.rest[i];
+    for (int k = 0; k < kp.K; ++k) {
+        t.kpj[k] = kp.joint ? kp.joint[k] : k;
+        for (int a = 0; a < 3; ++a) t.kpo[3 * k + a] = kp.offset ? kp.offset[3 * k + a] : 0.f;
+    }
 }
 
 // the defaults give the plain step of pndf_project, whatever else the struct says

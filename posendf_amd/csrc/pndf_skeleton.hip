@@ -22,7 +22,11 @@
 //                              interior frame takes the neighbour coupling of pndf_interp.h between the descent and the
 //                              renormalisation, out of place; with the observation or the free end frames of a
 //                              pndf_project_options4 (motion denoising) its third instantiation pndf_skel_enc_rev_denoise_kernel:
-//                              pndf_denoise_quat of pndf_interp.h, with tracks (out of place) or without (in place allowed)
+//                              pndf_denoise_quat of pndf_interp.h, with tracks (out of place) or without (in place allowed); with the
+//                              3D keypoints of a pndf_project_options5 (keypoint fitting) its fourth instantiation
+//                              pndf_skel_enc_rev_fit_kernel: in front of the steps of the joints the forward kinematics of the
+//                              lane's pose, the keypoint residuals and the reverse of pndf_fk.h in workspace rows [24 J][ld], then
+//                              pndf_fit_quat -- the denoising step with nu * dE/dQ_j in front of its finish
 //   pndf_skel_fill_kernel      the fill of a track from its two end frames, once per chunk in front of the steps
 // 2 + 2 L launches per evaluation.  No float atomics, no communication between workgroups, every column of a GEMM summed in the
 // same order wherever it sits: the same inputs give the same bits and a pose's result does not depend on its batch.
@@ -37,6 +41,7 @@
 #include "../../include/posendf_amd_skeleton.h"
 #include "pndf_experiment.h"
 #include "pndf_bone.h"
+#include "pndf_fk.h"
 #include "pndf_host.h"
 #include "pndf_interp.h"
 #include "pndf_project_opts.h"
@@ -86,6 +91,20 @@ struct SkDenoiseArgs : SkArgs {
     const float* conf;        // the chunk's confidences [n][nj], or null (ones)
     float mu;                 // the weight of the data term
     uint32_t flags;           // PNDF_TRACK_FREE_ENDS: the end frames of a track are not held
+};
+
+// SkDenoiseArgs with the keypoints of a pndf_project_options5 (SK_PROJECT), which pndf_skel_enc_rev_fit_kernel alone takes, derived for the
+// same reason.  The small tables are values of the argument struct: wave-uniform, read with scalar loads, validated on the host.
+struct SkFitArgs : SkDenoiseArgs {
+    const float* kp_target;   // the chunk's targets [n][K][3], or null (no keypoint term)
+    const float* kp_conf;     // the chunk's confidences [n][K], or null (ones)
+    float* kp_energy;         // [n] or null: E at the step's input iterate
+    float* fk;                // the rows [24 nj][ld] of pndf_fk.h
+    int K;                    // keypoints, 1 .. 64
+    float nu;                 // the weight of the keypoint term
+    int kpj[PNDF_FK_MAX_KEYPOINTS];            // the joint of keypoint k
+    float kpo[3 * PNDF_FK_MAX_KEYPOINTS];      // its local offset
+    float rest[3 * MAXJ];                      // the rest offsets of the joints
 };
 
 // bone j forward on column c: the parent's features are read back from act0 (a per-thread feature array indexed by a run-time
@@ -161,11 +180,14 @@ extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_fwd_kernel(SkArg
 // observation and no free ends, with no branch on the tracks and no neighbour registers (as a branch in one kernel the tracks cost the
 // call without them up to 0.2 %).  SK_REV_DENOISE is the instantiation of a pndf_project_options4 with an anchor and / or
 // free end frames, with tracks (e.frames >= 2) or without (e.frames == 0): pndf_denoise_quat of pndf_interp.h in place of the step.
-enum { SK_REV_PLAIN = 0, SK_REV_TRACKS = 1, SK_REV_DENOISE = 2 };
+// SK_REV_FIT is the instantiation of a pndf_project_options5 with a keypoint term: everything SK_REV_DENOISE does, and pndf_fk.h's
+// energy and gradient of the lane's pose at the step's input iterate -- all of it before the first store to `out`, which may be `q`.
+enum { SK_REV_PLAIN = 0, SK_REV_TRACKS = 1, SK_REV_DENOISE = 2, SK_REV_FIT = 3 };
 template <int KIND, class Args>
 __device__ __forceinline__ void skel_enc_rev(const Args& e) {
     constexpr bool TRACKS = KIND == SK_REV_TRACKS;
-    constexpr bool DENOISE = KIND == SK_REV_DENOISE;
+    constexpr bool FIT = KIND == SK_REV_FIT;
+    constexpr bool DENOISE = KIND == SK_REV_DENOISE || FIT;
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= e.n) return;
     if (e.encoder)
@@ -202,6 +224,10 @@ __device__ __forceinline__ void skel_enc_rev(const Args& e) {
             lambda = e.lambda;
         }
     }
+    float energy = 0.f;      // FIT: E of the pose; d E / d Q_j is left in the rows pndf_fk_grad_row of e.fk
+    if constexpr (FIT)
+        energy = pndf_fk_energy_grad(q, e.nj, e.parent, e.rest, e.K, e.kpj, e.kpo, e.kp_target + c * (e.K * 3),
+                                     e.kp_conf ? e.kp_conf + c * e.K : nullptr, e.fk + c, e.ld);
     for (int j = 0; j < e.nj; ++j) {
         float g[BONE];
 #pragma unroll
@@ -237,7 +263,14 @@ __device__ __forceinline__ void skel_enc_rev(const Args& e) {
                 if (w > 0.f)
 #pragma unroll
                     for (int k = 0; k < BONE; ++k) A[k] = e.anchor[c * nq + j * BONE + k];
-                rest = pndf_denoise_quat(Q, g, dist, nm, np, nbr, lambda, A, w, e.step_size, e.tol, e.renorm, u);
+                if constexpr (FIT) {
+                    float gk[BONE];
+#pragma unroll
+                    for (int k = 0; k < BONE; ++k) gk[k] = e.fk[(int64_t)(pndf_fk_grad_row(e.nj, j) + k) * e.ld + c];
+                    rest = pndf_fit_quat(Q, g, dist, nm, np, nbr, lambda, A, w, gk, e.nu, e.step_size, e.tol, e.renorm, u);
+                } else {
+                    rest = pndf_denoise_quat(Q, g, dist, nm, np, nbr, lambda, A, w, e.step_size, e.tol, e.renorm, u);
+                }
             } else {
                 rest = pndf_step_quat(Q, g, dist, e.step_size, e.tol, e.renorm, u);
             }
@@ -252,11 +285,14 @@ __device__ __forceinline__ void skel_enc_rev(const Args& e) {
         }
     }
     if (e.d_out) e.d_out[c] = dist;
+    if constexpr (FIT)
+        if (e.kp_energy) e.kp_energy[c] = energy;
 }
 
 extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_kernel(SkArgs e) { skel_enc_rev<SK_REV_PLAIN>(e); }
 extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_track_kernel(SkArgs e) { skel_enc_rev<SK_REV_TRACKS>(e); }
 extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_denoise_kernel(SkDenoiseArgs e) { skel_enc_rev<SK_REV_DENOISE>(e); }
+extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_fit_kernel(SkFitArgs e) { skel_enc_rev<SK_REV_FIT>(e); }
 
 // The fill of a chunk of whole tracks (pndf_project_options3, PNDF_TRACK_SLERP / _NLERP): one lane per joint quaternion.  Of every track
 // only frames 0 (a) and T-1 (b) of `src` are read; frame 0 of `dst` takes the bits of a, frame T-1 b aligned to a, the frames between
@@ -313,6 +349,7 @@ struct SkLayout {
     int64_t nc;
     int64_t X, act0, S1, S2, U0, Gx, dist, D1[MAX_LIN], P[2];
     int64_t Q2;      // the second pose buffer [nc][4 J] of the out-of-place steps of a pndf_project_options3
+    int64_t FK;      // the rows [24 J][nc] of the forward kinematics and its adjoints of a pndf_project_options5 (pndf_fk.h)
     int64_t total;
 };
 
@@ -338,19 +375,21 @@ SkLayout sk_layout(const pndf_skel_plan* h, int64_t B) {
     l.P[0] = c.take((int64_t)h->maxw * l.nc);
     l.P[1] = c.take((int64_t)h->maxw * l.nc);
     l.Q2 = c.take(nq * l.nc);
+    l.FK = c.take((int64_t)PNDF_FK_ROWS * h->nj * l.nc);
     l.total = c.o;
     return l;
 }
 
 // One evaluation of a chunk of n poses at `q`: the 2 + 2 L launches (the forward alone: 1 + L and the copy of the output row)
-void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const SkDenoiseArgs& e, hipStream_t st) {
+void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const SkFitArgs& e, hipStream_t st) {
     const int n = (int)e.n;
     TrunkWeights w{};
     TrunkBuffers b{};
     for (int t = 0; t < h->L; ++t) { w.W[t] = h->d_blob + h->w_off[t]; w.b[t] = h->d_blob + h->b_off[t]; b.D1[t] = ws + l.D1[t]; }
     b.in = ws + l.act0; b.P[0] = ws + l.P[0]; b.P[1] = ws + l.P[1]; b.out = ws + l.dist; b.din = ws + l.U0;
     b.ld = l.nc; b.n = n;
-    const SkArgs& plain = e;      // what every kernel but the denoising one takes
+    const SkArgs& plain = e;      // what every kernel but the denoising and the fitting one takes
+    const SkDenoiseArgs& denoise = e;
     hipLaunchKernelGGL(pndf_skel_enc_fwd_kernel, dim3(blocks(n)), dim3(256), 0, st, plain);
     trunk_forward(SK_GEMM, *h, w, b, st);
     if (e.mode == SK_FORWARD) {
@@ -358,16 +397,17 @@ void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const S
         return;
     }
     trunk_reverse(SK_GEMM, *h, w, b, st);      // grad_out scales the result in the encoder's reverse
-    if (e.mode == SK_PROJECT && (e.anchor || e.flags)) hipLaunchKernelGGL(pndf_skel_enc_rev_denoise_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
+    if (e.mode == SK_PROJECT && e.kp_target) hipLaunchKernelGGL(pndf_skel_enc_rev_fit_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
+    else if (e.mode == SK_PROJECT && (e.anchor || e.flags)) hipLaunchKernelGGL(pndf_skel_enc_rev_denoise_kernel, dim3(blocks(n)), dim3(256), 0, st, denoise);
     else if (e.mode == SK_PROJECT && e.frames) hipLaunchKernelGGL(pndf_skel_enc_rev_track_kernel, dim3(blocks(n)), dim3(256), 0, st, plain);
     else hipLaunchKernelGGL(pndf_skel_enc_rev_kernel, dim3(blocks(n)), dim3(256), 0, st, plain);
 }
 
-SkDenoiseArgs sk_args(const pndf_skel_plan* h, const SkLayout& l, float* ws, int mode) {
-    SkDenoiseArgs e;
+SkFitArgs sk_args(const pndf_skel_plan* h, const SkLayout& l, float* ws, int mode) {
+    SkFitArgs e;
     memset(&e, 0, sizeof(e));
     e.wenc = h->d_blob;
-    e.X = ws + l.X; e.act0 = ws + l.act0; e.U0 = ws + l.U0; e.Gx = ws + l.Gx; e.dist = ws + l.dist;
+    e.X = ws + l.X; e.act0 = ws + l.act0; e.U0 = ws + l.U0; e.Gx = ws + l.Gx; e.dist = ws + l.dist; e.fk = ws + l.FK;
     if (h->encoder) { e.S1 = ws + l.S1; e.S2 = ws + l.S2; }
     e.ld = l.nc;
     e.nj = h->nj; e.encoder = h->encoder ? 1 : 0; e.mode = mode;
@@ -474,7 +514,7 @@ extern "C" int pndf_skel_forward(pndf_skel_handle h, const float* q, float* d, i
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     float* ws = (float*)workspace;
-    SkDenoiseArgs e = sk_args(h, l, ws, SK_FORWARD);
+    SkFitArgs e = sk_args(h, l, ws, SK_FORWARD);
     for (int64_t c0 = 0; c0 < B; c0 += l.nc) {
         e.n = B - c0 < l.nc ? B - c0 : l.nc;
         e.q = q + c0 * h->nj * BONE;
@@ -497,7 +537,7 @@ extern "C" int pndf_skel_forward_grad(pndf_skel_handle h, const float* q, const 
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     float* ws = (float*)workspace;
-    SkDenoiseArgs e = sk_args(h, l, ws, SK_GRAD);
+    SkFitArgs e = sk_args(h, l, ws, SK_GRAD);
     for (int64_t c0 = 0; c0 < B; c0 += l.nc) {
         e.n = B - c0 < l.nc ? B - c0 : l.nc;
         e.q = q + c0 * h->nj * BONE;
@@ -516,7 +556,8 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
     const uint32_t* observed;      // a pndf_project_options2 brings the joint mask: one word per pose, device memory
     PndfTracks tracks;             // a pndf_project_options3 the tracks besides: B / frames of them
     PndfData data;                 // a pndf_project_options4 the observation besides (motion denoising): device memory, as the poses
-    if (const char* why = pndf_check_project_options4(opt, B, o, observed, tracks, data)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    PndfKeypoints kp;              // a pndf_project_options5 the 3D keypoints besides (keypoint fitting): the arrays per pose in device memory, the small tables in host memory
+    if (const char* why = pndf_check_project_options5(opt, B, h->nj, o, observed, tracks, data, kp)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (steps < 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count");
     SkLayout l;
     if (B > 0 && (!q_in || !q_out)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose pointer");
@@ -527,6 +568,7 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
         return pndf_fail(h, PNDF_ERR_BAD_ARG, "q_out must not overlap q_in when pndf_project_options3.frames > 0: a step reads the neighbour "
                                               "frames of its input");
     if (const char* why = pndf_check_observation_apart(data, q_out, B, h->nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (const char* why = pndf_check_keypoints_apart(kp, q_out, B, h->nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (const int rc = sk_check(h, B, workspace, workspace_bytes, l); rc != PNDF_OK || B == 0) return rc;
     PndfRange range("pndf_skel_project");
     DeviceGuard guard(h->device);
@@ -537,21 +579,29 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
     if (steps == 0 && !filled) {
         if (q_in != q_out) HIP_TRY(h, hipMemcpyAsync(q_out, q_in, sizeof(float) * (size_t)(B * nq), hipMemcpyDeviceToDevice, st));
         if (d_last) HIP_TRY(h, hipMemsetAsync(d_last, 0, sizeof(float) * (size_t)B, st));
+        if (kp.energy) HIP_TRY(h, hipMemsetAsync(kp.energy, 0, sizeof(float) * (size_t)B, st));
         return PNDF_OK;
     }
     float* ws = (float*)workspace;
-    SkDenoiseArgs e = sk_args(h, l, ws, SK_PROJECT);
+    SkFitArgs e = sk_args(h, l, ws, SK_PROJECT);
     e.step_size = o.step_size; e.tol = o.tol; e.renorm = (int)o.renorm;
     e.frames = tracks.frames; e.lambda = tracks.lambda;
     e.mu = data.mu; e.flags = data.free_ends ? (uint32_t)PNDF_TRACK_FREE_ENDS : 0u;
+    if (kp.any()) {
+        e.K = kp.K; e.nu = kp.nu;
+        pndf_fill_keypoint_tables(e, kp, h->nj);
+    }
     // with tracks a chunk holds whole tracks, so no track straddles a seam and lane c of a chunk is frame c % T
     const int64_t nc = tracks.frames ? (l.nc / tracks.frames) * tracks.frames : l.nc;
     if (steps == 0 && d_last) HIP_TRY(h, hipMemsetAsync(d_last, 0, sizeof(float) * (size_t)B, st));
+    if ((steps == 0 || !kp.any()) && kp.energy) HIP_TRY(h, hipMemsetAsync(kp.energy, 0, sizeof(float) * (size_t)B, st));
     for (int64_t c0 = 0; c0 < B; c0 += nc) {
         e.n = B - c0 < nc ? B - c0 : nc;
         e.observed = observed ? observed + c0 : nullptr;
         e.anchor = data.anchor ? data.anchor + c0 * nq : nullptr;
         e.conf = data.conf ? data.conf + c0 * h->nj : nullptr;
+        e.kp_target = kp.target ? kp.target + c0 * kp.K * 3 : nullptr;
+        e.kp_conf = kp.conf ? kp.conf + c0 * kp.K : nullptr;
         // Without tracks the iterate is in q_out from the second step on: a lane reads its pose before it writes it.  With tracks a
         // step is out of place: the steps alternate between the chunk of q_out and the second pose buffer, the last one writes
         // q_out; step 0 reads q_in, or the buffer the fill wrote.
@@ -567,6 +617,7 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
             e.q = cur;
             e.out = buf[(steps - 1 - s) & 1];
             e.d_out = (d_last && s == steps - 1) ? d_last + c0 : nullptr;
+            e.kp_energy = (kp.any() && kp.energy && s == steps - 1) ? kp.energy + c0 : nullptr;
             sk_run_chunk(h, l, ws, e, st);
             cur = e.out;
         }

@@ -15,7 +15,7 @@ import numpy as np
 # public names stay importable from here.  `torch` comes from there too: abi imports it before the library is loaded (None without it).
 from .abi import (ACT_CODES, DEBUG_EXPERIMENT_WORDS, DEBUG_EXPORTS, EXPERIMENT_WORDS, EXPORTS, INTERP_MODES, METRIC_CODES,  # noqa: F401
                   NOISE_CODES, PRECISION_CODES, RENORM_CODES, Camera, DenoiseWeights, KeypointOpts, OnlineOpts, PndfConfig, PndfError,
-                  ProjectOptions, ProjectOptions2, ProjectOptions3, ProjectOptions4, TRACK_FILLS, TRACK_FREE_ENDS, debug_library_path, experiment_word, load_library, torch)
+                  ProjectOptions, ProjectOptions2, ProjectOptions3, ProjectOptions4, ProjectOptions5, TRACK_FILLS, TRACK_FREE_ENDS, debug_library_path, experiment_word, load_library, torch)
 
 
 def stream_handle(device) -> int:
@@ -146,6 +146,33 @@ def project_options4(lib, observed_ptr, frames, smooth=0.0, fill=None, anchor_pt
     opt.base3.base2.base.struct_size = ctypes.sizeof(opt)
     opt.anchor, opt.conf, opt.mu, opt.flags = anchor_ptr, conf_ptr, float(data), TRACK_FREE_ENDS if free_ends else 0
     return opt
+
+
+def project_options5(lib, observed_ptr, frames, smooth=0.0, fill=None, anchor_ptr=None, conf_ptr=None, data=0.0, free_ends=False,
+                     kp_target_ptr=None, kp_conf_ptr=None, kp_energy_ptr=None, rest_ptr=None, kp_joint_ptr=None, kp_offset_ptr=None,
+                     n_keypoints=0, kp_weight=0.0, step_size=1.0, renorm="none", tol=0.0):
+    """pndf_project_options5 (include/posendf_amd.h): the options, the mask, the tracks, the observation and the 3D keypoints of a fit --
+    `kp_target_ptr` [B,K,3] (None: no keypoint term), `kp_conf_ptr` [B,K] (None: ones) and `kp_energy_ptr` [B] (out, or None) in the memory
+    space of the poses; `rest_ptr` [J,3], `kp_joint_ptr` [K] int32 (None: keypoint k is joint k) and `kp_offset_ptr` [K,3] (None: zeros) in
+    HOST memory; `n_keypoints` K and `kp_weight` the term's weight nu.  The values are checked by the library."""
+    opt = ProjectOptions5()
+    opt.base4 = project_options4(lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends, step_size, renorm, tol)
+    opt.base4.base3.base2.base.struct_size = ctypes.sizeof(opt)
+    opt.kp_target, opt.kp_conf, opt.kp_energy = kp_target_ptr, kp_conf_ptr, kp_energy_ptr
+    opt.rest, opt.kp_joint, opt.kp_offset = rest_ptr, kp_joint_ptr, kp_offset_ptr
+    opt.n_keypoints, opt.nu = int(n_keypoints), float(kp_weight)
+    return opt
+
+
+_KEYPOINT_KEYS = ("kp_target_ptr", "kp_conf_ptr", "kp_energy_ptr", "rest_ptr", "kp_joint_ptr", "kp_offset_ptr", "n_keypoints", "kp_weight")
+
+
+def _keypointed(kw) -> bool:
+    """whether a `project` call names keypoints at all: only then is the 128-byte struct built"""
+    unknown = sorted(set(kw) - set(_KEYPOINT_KEYS))
+    if unknown:
+        raise TypeError(f"project() got unexpected keyword arguments {unknown}")
+    return any(kw.get(k) is not None for k in _KEYPOINT_KEYS[:6]) or bool(kw.get("n_keypoints")) or float(kw.get("kp_weight") or 0.0) != 0.0
 
 
 def _anchored(anchor_ptr, conf_ptr, data, free_ends) -> bool:
@@ -493,13 +520,18 @@ class SkeletonEngine(_Handle):
                     "pndf_skel_forward_grad")
 
     def project(self, q_in_ptr, q_out_ptr, d_ptr, B, steps, ws_ptr, ws_bytes, stream=0, *, step_size=1.0, renorm="none", tol=0.0,
-                observed_ptr=None, frames=0, smooth=0.0, fill=None, anchor_ptr=None, conf_ptr=None, data=0.0, free_ends=False):
+                observed_ptr=None, frames=0, smooth=0.0, fill=None, anchor_ptr=None, conf_ptr=None, data=0.0, free_ends=False, **keypoints):
         """pndf_skel_project; `observed_ptr`: one uint32 per pose in device memory, bit j = joint j is held (pose completion, through a
         pndf_project_options2); None: no joint is held and the call is the one without a mask.  `frames` = T >= 2: the poses are B / T
         tracks (pose interpolation, through a pndf_project_options3: `project_options3`), q_out apart from q_in.  `anchor_ptr` [B,J,4] /
         `conf_ptr` [B,J] in device memory, `data` and `free_ends`: the observation of motion denoising (through a
-        pndf_project_options4: `project_options4`), apart from q_out"""
-        if _anchored(anchor_ptr, conf_ptr, data, free_ends):
+        pndf_project_options4: `project_options4`), apart from q_out.  `**keypoints`: kp_target_ptr [B,K,3] / kp_conf_ptr [B,K] / kp_energy_ptr
+        [B] in device memory, rest_ptr / kp_joint_ptr / kp_offset_ptr in HOST memory, n_keypoints, kp_weight: the 3D keypoints of a fit
+        (through a pndf_project_options5: `project_options5`)"""
+        if _keypointed(keypoints):
+            opt = ctypes.byref(project_options5(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends,
+                                                step_size=step_size, renorm=renorm, tol=tol, **keypoints))
+        elif _anchored(anchor_ptr, conf_ptr, data, free_ends):
             opt = ctypes.byref(project_options4(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends, step_size, renorm, tol))
         elif _tracked(frames, smooth, fill):
             opt = ctypes.byref(project_options3(self.lib, observed_ptr, frames, smooth, fill, step_size, renorm, tol))
@@ -692,11 +724,18 @@ class CpuEngine(_Handle):
         self._check(self.lib.pndf_forward_grad_cpu(self.handle, q_ptr, gout_ptr, d_ptr, dq_ptr, B), "pndf_forward_grad_cpu")
 
     def project(self, q_in_ptr, q_out_ptr, d_ptr, B, steps, stream=0, *, step_size=1.0, renorm="none", tol=0.0, observed_ptr=None,
-                frames=0, smooth=0.0, fill=None, anchor_ptr=None, conf_ptr=None, data=0.0, free_ends=False):
+                frames=0, smooth=0.0, fill=None, anchor_ptr=None, conf_ptr=None, data=0.0, free_ends=False, **keypoints):
         """`observed_ptr`: one uint32 per pose in host memory, bit j = joint j is held (pndf_project_ex_cpu with a pndf_project_options2:
         any joint tree); None: the call without a mask.  `frames` = T >= 2: the poses are B / T tracks (pndf_project_ex_cpu with a
         pndf_project_options3: `project_options3`).  `anchor_ptr` [B,J,4] / `conf_ptr` [B,J] in host memory, `data` and `free_ends`: the
-        observation of motion denoising (pndf_project_ex_cpu with a pndf_project_options4: `project_options4`)"""
+        observation of motion denoising (pndf_project_ex_cpu with a pndf_project_options4: `project_options4`).  `**keypoints`: as
+        SkeletonEngine.project, every pointer in host memory (pndf_project_ex_cpu with a pndf_project_options5: `project_options5`)"""
+        if _keypointed(keypoints):
+            opt5 = project_options5(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends,
+                                    step_size=step_size, renorm=renorm, tol=tol, **keypoints)
+            self._check(self.lib.pndf_project_ex_cpu(self.handle, q_in_ptr, q_out_ptr, d_ptr, B, int(steps), ctypes.byref(opt5)),
+                        "pndf_project_ex_cpu")
+            return
         if _anchored(anchor_ptr, conf_ptr, data, free_ends):
             opt4 = project_options4(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends, step_size, renorm, tol)
             self._check(self.lib.pndf_project_ex_cpu(self.handle, q_in_ptr, q_out_ptr, d_ptr, B, int(steps), ctypes.byref(opt4)),

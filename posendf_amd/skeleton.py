@@ -17,7 +17,10 @@ the projection step of the unit's last kernel (or of the host twin), handed over
 interpolation for the model's tree the same way: the tracks ride in a pndf_project_options3, the fill is one small kernel and the
 neighbour coupling sits in the step; `posendf_amd.pose_interpolation.PoseInterpolation` drives it.  `denoise(track)` is motion
 denoising in quaternion space -- the pose prior, the neighbour coupling with free end frames and a data term towards the noisy
-observation, in a pndf_project_options4 --, which `posendf_amd.pose_denoising.PoseDenoising` drives.  The second order stays 21-joint
+observation, in a pndf_project_options4 --, which `posendf_amd.pose_denoising.PoseDenoising` drives.  `fit_keypoints(poses, targets,
+rest)` is inverse kinematics under the prior -- 3D detections of keypoints attached to the joints, the tree with its rest offsets as the
+body model, in a pndf_project_options5 --, which `posendf_amd.keypoint_fitting.KeypointFitting` drives; `forward_kinematics` is the
+differentiable torch statement of its kinematics.  The second order stays 21-joint
 (DESIGN.md section 8).
 """
 from __future__ import annotations
@@ -222,3 +225,131 @@ class SkeletonPoseNDF(PoseModel):
         if single:
             out, d = out[0], d[0]
         return (out, d) if return_dist else out
+
+    @torch.no_grad()
+    def fit_keypoints(self, poses, targets, rest, steps=100, weight=0.02, conf=None, keypoint_joints=None, keypoint_offsets=None, observed=None,
+                      frames=None, smooth=0.0, anchor=None, data=0.0, free_ends=False, return_dist=True, return_energy=False, *, step_size=1.0,
+                      renormalize=None, tol=0.0):
+        """Inverse kinematics under the learned prior, for the model's tree: from the start `poses` [B,J,4], `steps` projection steps that
+        also descend E = 1/2 sum_k conf_k |P_k(pose) - targets_k|^2 with weight `weight` (nu), P_k = `forward_kinematics` of the pose.
+        `targets` [B,K,3] are 3D detections in the roots' frame; `rest` [J,3] the offsets of the joints from their parents in the rest
+        pose; `keypoint_joints` [K] (None: K = J, keypoint k is joint k) and `keypoint_offsets` [K,3] (None: zeros) attach the keypoints;
+        `conf` [K] or [B,K]: a keypoint whose confidence is zero, negative or NaN takes no part and its target is not read, so a missing
+        detection may hold NaN.  `observed` (bool [J] or [B,J]) joints are held bit for bit and still move their subtree.  `frames` = T >= 2
+        reads the poses as B / T clips and couples neighbouring frames with weight `smooth`, the end frames held unless `free_ends`;
+        `anchor` [B,J,4] with `data` adds the quaternion data term of `denoise`.  Everything rides in ONE engine call of 2 + 2 L launches
+        per step (pndf_project_options5, include/posendf_amd.h): kinematics, residuals and their reverse run inside the unit's last kernel;
+        a `train.device: cpu` model runs the host twin.  The inputs are not written.  The default `weight` is untuned: it is the largest of
+        the values tried (0.02, 0.05) at which the energy of a 15-joint hand with rest offsets within [-0.75, 0.75]^3 fell at every step of
+        pure inverse kinematics; the term is a plain gradient step whose length grows with the square of the bone lengths, and already
+        with offsets within [-1, 1]^3 one start of 48 oscillates at 0.02 -- scale `weight` down by the square of the rig's size.
+        Where tensors may live: the per-pose tensors `poses`, `targets`, `conf`, `anchor` and `observed` are accepted on the model's device
+        and on the cpu (host data is copied to the model's device); a tensor on any other device -- a cuda tensor handed to a
+        `train.device: cpu` model, or one on another GPU than the model's -- raises PndfError, since it would mean a silent copy of a whole
+        batch off its device.  The small tables `rest`, `keypoint_joints` and `keypoint_offsets` are host tables of the call and are
+        accepted from any device.
+        Returns poses [B,J,4], then dist [B,1] of the last iteration (`return_dist`), then the energy [B] of the last iteration, evaluated
+        before its update (`return_energy`); step options: as `project`."""
+        J = self.num_joints
+        home = torch.device(self.device)
+
+        def on_device(value, what):
+            # host data and data on the model's device are taken; anything else would be a silent copy of a batch off its device
+            t = torch.as_tensor(value)
+            there = t.device
+            if there.type != "cpu" and (there.type != home.type or (home.index is not None and there.index != home.index)):
+                raise PndfError(f"{what} lives on {there}, the model on {home}: per-pose tensors are taken from the model's device or from the cpu")
+            return t.to(device=home)
+
+        q = on_device(poses, "poses").float()
+        if q.dim() < 2 or tuple(q.shape[-2:]) != (J, 4):
+            raise PndfError(f"poses are [B,{J},4], not {tuple(poses.shape)}")
+        q = q.reshape(-1, J, 4).contiguous()
+        B, dev = q.shape[0], q.device
+
+        def table(value, shape, dtype, what):
+            t = torch.as_tensor(value).detach().to("cpu")
+            if tuple(t.shape) != shape:
+                raise PndfError(f"{what} is {list(shape)}, not {list(t.shape)}")
+            return t.to(dtype).contiguous()
+
+        kpj = None if keypoint_joints is None else torch.as_tensor(keypoint_joints).detach().to("cpu")
+        if kpj is not None and (kpj.dim() != 1 or kpj.dtype in (torch.bool, torch.float16, torch.float32, torch.float64)):
+            raise PndfError(f"keypoint_joints is an integer tensor [K], not {kpj.dtype} {list(kpj.shape)}")
+        K = J if kpj is None else int(kpj.shape[0])
+        kpj = None if kpj is None else kpj.to(torch.int32).contiguous()
+        rest_t = table(rest, (J, 3), torch.float32, "rest")
+        kpo = None if keypoint_offsets is None else table(keypoint_offsets, (K, 3), torch.float32, "keypoint_offsets")
+        y = on_device(targets, "targets").float()
+        if y.dim() < 2 or tuple(y.shape[-2:]) != (K, 3) or y.numel() != B * K * 3:
+            raise PndfError(f"targets are [{B},{K},3], not {list(y.shape)}")
+        y = y.reshape(B, K, 3).contiguous()
+        c = None
+        if conf is not None:
+            c = on_device(conf, "conf")
+            if not c.is_floating_point() or tuple(c.shape) not in ((K,), (B, K)):
+                raise PndfError(f"conf is a floating-point tensor [{K}] or [{B},{K}], not {c.dtype} {list(c.shape)}")
+            c = c.float().expand(B, K).contiguous()
+        seen = None
+        if anchor is not None:
+            seen = on_device(anchor, "anchor").float()
+            if seen.numel() != q.numel() or tuple(seen.shape[-2:]) != (J, 4):
+                raise PndfError(f"anchor has the poses' shape {list(q.shape)}, not {list(seen.shape)}")
+            seen = seen.reshape(q.shape).contiguous()
+        T = int(frames or 0)
+        if T == 1:
+            T = 0
+        out = torch.empty_like(q)
+        d = torch.empty(B, device=dev, dtype=torch.float32)
+        energy = torch.zeros(B, device=dev, dtype=torch.float32)
+        mask = None if observed is None else pack_observed(on_device(observed, "observed"), B, dev, J)
+        eng = self._engine_for(dev)
+        host = dev.type == "cpu"
+        if B or host:       # as `project`
+            tracks = dict(frames=T, smooth=smooth, free_ends=bool(free_ends)) if T else {}
+            eng.project(q.data_ptr(), out.data_ptr(), d.data_ptr(), B, int(steps), *(() if host else self._engine_args(eng, dev, B)),
+                        step_size=step_size, renorm=renormalize, tol=tol, observed_ptr=None if mask is None or B == 0 else mask.data_ptr(),
+                        anchor_ptr=None if seen is None or B == 0 else seen.data_ptr(), data=data if seen is not None and B else 0.0,
+                        kp_target_ptr=y.data_ptr() if B else None, kp_conf_ptr=None if c is None or B == 0 else c.data_ptr(),
+                        kp_energy_ptr=energy.data_ptr() if B else None, rest_ptr=rest_t.data_ptr(),
+                        kp_joint_ptr=None if kpj is None else kpj.data_ptr(), kp_offset_ptr=None if kpo is None else kpo.data_ptr(),
+                        n_keypoints=K, kp_weight=weight, **tracks)
+        result = (out,) + ((d.view(-1, 1),) if return_dist else ()) + ((energy,) if return_energy else ())
+        return result if len(result) > 1 else out
+
+
+def forward_kinematics(pose, parents, rest, keypoint_joints=None, keypoint_offsets=None):
+    """The keypoints of poses on a joint tree, differentiable: pose [...,J,4] (joint quaternions, real part first; each is normalised,
+    r = Q / max(|Q|, 1e-12)) -> [...,K,3].  `parents`: the parent table (-1: a root; every parent before its child); `rest` [J,3]: joint j
+    relative to its parent in the rest pose (the position of a root); keypoint k sits on joint `keypoint_joints[k]` at the local offset
+    `keypoint_offsets[k]` (None: K = J, the joints themselves).  With G_j the global rotation and p_j the position of joint j:
+    root G_j = R_j, p_j = t_j; else G_j = G_parent R_j, p_j = p_parent + G_parent t_j; P_k = p_a(k) + G_a(k) o_k.  This is the statement
+    `SkeletonPoseNDF.fit_keypoints` (csrc/pndf_fk.h) descends; use it to make targets and to read residuals."""
+    parents = parent_table(parents)
+    J = len(parents)
+    if tuple(pose.shape[-2:]) != (J, 4):
+        raise PndfError(f"pose is [...,{J},4], not {tuple(pose.shape)}")
+    rest = torch.as_tensor(rest, dtype=pose.dtype, device=pose.device)
+    if tuple(rest.shape) != (J, 3):
+        raise PndfError(f"rest is [{J},3], not {tuple(rest.shape)}")
+    joints = list(range(J)) if keypoint_joints is None else [int(a) for a in torch.as_tensor(keypoint_joints).reshape(-1).tolist()]
+    if any(a < 0 or a >= J for a in joints):
+        raise PndfError(f"keypoint_joints lie in 0 .. {J - 1}")
+    offsets = None if keypoint_offsets is None else torch.as_tensor(keypoint_offsets, dtype=pose.dtype, device=pose.device)
+    if offsets is not None and tuple(offsets.shape) != (len(joints), 3):
+        raise PndfError(f"keypoint_offsets is [{len(joints)},3], not {tuple(offsets.shape)}")
+    r = pose / pose.pow(2).sum(-1, keepdim=True).sqrt().clamp_min(1e-12)
+    w, x, y, z = r.unbind(-1)
+    R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                     2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                     2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], dim=-1).reshape(pose.shape[:-1] + (3, 3))
+    G, p = [], []
+    for j, pa in enumerate(parents):
+        if pa < 0:
+            G.append(R[..., j, :, :])
+            p.append(rest[j].expand(pose.shape[:-2] + (3,)))
+        else:
+            G.append(G[pa] @ R[..., j, :, :])
+            p.append(p[pa] + (G[pa] @ rest[j].unsqueeze(-1)).squeeze(-1))
+    out = [p[a] if offsets is None else p[a] + (G[a] @ offsets[k].unsqueeze(-1)).squeeze(-1) for k, a in enumerate(joints)]
+    return torch.stack(out, dim=-2)
