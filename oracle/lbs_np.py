@@ -74,10 +74,12 @@ def rest_shape(model, dtype=np.float64):
     return v_shaped, J
 
 
-def lbs(theta, model, dtype=np.float64, global_orient=None, keep=False):
+def lbs(theta, model, dtype=np.float64, global_orient=None, keep=False, contract=None):
     """SMPL.forward(betas, body_pose=theta, global_orient) of smplx (create_transl default: a zero translation).
     theta [N,69] axis-angle of the 23 body joints; the root orientation defaults to SMPL's zero-initialised
     `global_orient` parameter (the reference passes root_orient=None, body_model.py:35-40).
+    `contract`: None = the einsums below; a hook `contract(name, spec, a, b)` (split_contractions) takes over "pose blend" and
+    "skinning" in the operand form of the split kernels, everything else stays in `dtype`.
     Returns vertices [N,V,3] and joints [N, 24 + n_extra, 3]."""
     theta = np.asarray(theta, dtype).reshape(-1, 69)
     N = theta.shape[0]
@@ -88,7 +90,10 @@ def lbs(theta, model, dtype=np.float64, global_orient=None, keep=False):
     full = np.concatenate([go, theta], 1).reshape(N, nJ, 3)
     R = batch_rodrigues(full.reshape(-1, 3)).reshape(N, nJ, 3, 3)
     pf = (R[:, 1:] - np.eye(3, dtype=dtype)).reshape(N, -1)                      # pose_feature [N, 207]
-    v_posed = v_shaped[None] + (pf @ np.asarray(model["posedirs"], dtype)).reshape(N, -1, 3)
+    if contract is None:
+        v_posed = v_shaped[None] + (pf @ np.asarray(model["posedirs"], dtype)).reshape(N, -1, 3)
+    else:
+        v_posed = v_shaped[None] + contract("pose blend", "kvc,nk->nvc", np.asarray(model["posedirs"], dtype).reshape(pf.shape[1], -1, 3), pf)
     rel = J.copy()
     rel[1:] -= J[parents[1:]]
     G_R = np.empty((N, nJ, 3, 3), dtype)
@@ -100,8 +105,12 @@ def lbs(theta, model, dtype=np.float64, global_orient=None, keep=False):
         G_t[:, i] = (G_R[:, p] @ rel[i]) + G_t[:, p]
     A_t = G_t - (G_R @ J[None, :, :, None])[..., 0]                             # rel_transforms: remove the rest pose
     W = np.asarray(model["lbs_weights"], dtype)
-    T_R = np.einsum("vj,njab->nvab", W, G_R)
-    T_t = np.einsum("vj,nja->nva", W, A_t)
+    if contract is None:
+        T_R = np.einsum("vj,njab->nvab", W, G_R)
+        T_t = np.einsum("vj,nja->nva", W, A_t)
+    else:                                                                       # A = [G_R | A_t]: one operand, one scale
+        Tm = contract("skinning", "vj,nje->nve", W, np.concatenate([G_R.reshape(N, nJ, 9), A_t], -1))
+        T_R, T_t = Tm[..., :9].reshape(N, -1, 3, 3), Tm[..., 9:]
     verts = np.einsum("nvab,nvb->nva", T_R, v_posed) + T_t
     joints = np.concatenate([G_t, verts[:, np.asarray(model["extra_joint_vertex"])]], 1)
     if keep:
@@ -109,8 +118,9 @@ def lbs(theta, model, dtype=np.float64, global_orient=None, keep=False):
     return verts, joints
 
 
-def lbs_vjp(model, cache, g_verts, g_joints, dtype=np.float64):
-    """reverse pass of lbs(): d (<g_verts, verts> + <g_joints, joints>) / d theta -> [N,69]."""
+def lbs_vjp(model, cache, g_verts, g_joints, dtype=np.float64, contract=None):
+    """reverse pass of lbs(): d (<g_verts, verts> + <g_joints, joints>) / d theta -> [N,69].
+    `contract` as in lbs(): the hook takes over "d/d pose feature" and "d/d A" (operand d L / d verts (x) [v_posed, 1])."""
     parents = np.asarray(model["parents"])
     nJ = len(parents)
     R, G_R, T_R, v_posed, rel, J, W = (cache[k] for k in ("R", "G_R", "T_R", "v_posed", "rel", "J", "W"))
@@ -119,9 +129,15 @@ def lbs_vjp(model, cache, g_verts, g_joints, dtype=np.float64):
     ex = np.asarray(model["extra_joint_vertex"])
     np.add.at(gV, (slice(None), ex), np.asarray(g_joints, dtype)[:, nJ:])       # joints[:, 24:] = verts[:, extra]
     g_vposed = np.einsum("nvab,nva->nvb", T_R, gV)
-    gA_R = np.einsum("vj,nva,nvb->njab", W, gV, v_posed)
-    gA_t = np.einsum("vj,nva->nja", W, gV)
-    g_pf = g_vposed.reshape(N, -1) @ np.asarray(model["posedirs"], dtype).T      # [N,207]
+    if contract is None:
+        gA_R = np.einsum("vj,nva,nvb->njab", W, gV, v_posed)
+        gA_t = np.einsum("vj,nva->nja", W, gV)
+        g_pf = g_vposed.reshape(N, -1) @ np.asarray(model["posedirs"], dtype).T      # [N,207]
+    else:
+        x = gV[..., :, None] * np.concatenate([v_posed, np.ones(v_posed.shape[:2] + (1,), dtype)], -1)[..., None, :]
+        gA = contract("d/d A", "vj,nve->nje", W, x.reshape(N, -1, 12)).reshape(N, nJ, 3, 4)
+        gA_R, gA_t = gA[..., :3], gA[..., 3]
+        g_pf = contract("d/d pose feature", "kvc,nvc->nk", np.asarray(model["posedirs"], dtype).reshape(9 * (nJ - 1), -1, 3), g_vposed)
     gR = np.zeros((N, nJ, 3, 3), dtype)
     gR[:, 1:] += g_pf.reshape(N, nJ - 1, 3, 3)
     gG_R = gA_R - gA_t[..., :, None] * J[None, :, None, :]                      # A_t = G_t - G_R J
@@ -135,17 +151,66 @@ def lbs_vjp(model, cache, g_verts, g_joints, dtype=np.float64):
     return g_full[:, 1:].reshape(N, 69)
 
 
+# ---------------------------------------------------------------- the split kernels' stated arithmetic (csrc/pndf_lbs.hip)
+# contraction -> (scale of the model operand a, scale of the per-frame operand b): the names pndf_debug_lbs_scales reads out
+CONTRACTIONS = {"pose blend": ("p_scale", "pf_scale"), "skinning": ("w_scale", "a_scale"),
+                "d/d pose feature": ("p_scale", "g_scale"), "d/d A": ("w_scale", "x_scale")}
+PRODUCTS = ("hh", "hl", "lh")      # model hi x frame hi, model hi x frame lo, model lo x frame hi (lo lo is dropped: 2^-22)
+
+
+def split_halves(x, toward_zero=False):
+    """x -> (hi, lo), both fp16 values carried in float64.  toward_zero=False: hi = rne(x), lo = rne(x - hi), what the host
+    packer stores for the model (tests/test_lbs_split_layout.split).  toward_zero=True: hi = rtz(x) (v_cvt_pkrtz: saturates at
+    65504), lo = rne(x - hi), what the kernels do to their own operands (lbs_split2)."""
+    x = np.asarray(x, np.float64)
+    with np.errstate(over="ignore"):
+        hi = x.astype(np.float16)
+        if toward_zero:
+            over = np.abs(hi.astype(np.float64)) > np.abs(x)
+            hi = np.where(over, np.nextafter(hi, np.float16(0)), hi)
+        hi = hi.astype(np.float64)
+        lo = (x - hi).astype(np.float16).astype(np.float64)
+    return hi, lo
+
+
+def split_contractions(scales, products=None, device_rounding=True, acc=np.float32):
+    """The `contract` hook of lbs() / lbs_vjp() / body_terms() in the split kernels' arithmetic: both operands times their
+    power-of-two scale (`scales`: the dict pndf_debug_lbs_scales fills), split into fp16 hi + lo -- the model operand rounded to
+    nearest as the host packer does, the per-frame operand toward zero as the device does (device_rounding=False: both to
+    nearest) -- the kept products summed with `acc` accumulation and the sum unscaled (acc=np.float64: the exact-arithmetic model
+    of tests/test_lbs_range.contraction_errors).
+    `products`: {contraction: subset of PRODUCTS}; a contraction it does not name keeps all three."""
+    products = dict(products or {})
+    assert set(products) <= set(CONTRACTIONS) and all(set(p) <= set(PRODUCTS) for p in products.values())
+
+    def contract(name, spec, a, b):
+        sa, sb = (acc(scales[k]) for k in CONTRACTIONS[name])
+        out = np.result_type(a, b)
+        with np.errstate(over="ignore", invalid="ignore"):
+            a = np.asarray(a, acc) * sa                  # (operands in the working precision: float32 on the device)
+            b = np.asarray(b, acc) * sb
+            (ah, al), (bh, bl) = split_halves(a), split_halves(b, device_rounding)
+            terms = [np.einsum(spec, u.astype(acc), v.astype(acc), optimize=True)
+                     for key, u, v in (("hh", ah, bh), ("hl", ah, bl), ("lh", al, bh)) if key in products.get(name, PRODUCTS)]
+            total = terms[0] if terms else np.zeros(np.einsum(spec, a, b).shape, acc)
+            for t in terms[1:]:
+                total = total + t
+            return (total * ((acc(1) / sa) / sb)).astype(out)      # gpf_true = (1 / p_scale) / g_scale, in this order
+    return contract
+
+
 # ---------------------------------------------------------------- experiments/motion_denoise.py:86-94, restated
-def body_terms(theta, joints0, model, it, dtype=np.float64, coefs=None, keep=False):
+def body_terms(theta, joints0, model, it, dtype=np.float64, coefs=None, keep=False, contract=None):
     """ONE sequence theta [T,69]: the unweighted temporal and data terms and the gradient of their WEIGHTED sum
     10 (1 + it) temp + [it > 0] 100 / (1 + it) data  with respect to theta (motion_denoise.py:29-45,86-94).
     `coefs` = (temp weight, data weight) replaces that schedule (experiments/partial_observation.py:31-32).  Like the
     reference there is no epsilon under the square roots: two identical consecutive vertices (or a joint that has not
     moved, which is why the reference skips the data term at it = 0, :92) give a NaN gradient.
-    keep=True also returns the intermediates: lbs()'s cache with `gV`, `gJ` (d L / d verts, d L / d joints of the two terms)."""
+    keep=True also returns the intermediates: lbs()'s cache with `gV`, `gJ` (d L / d verts, d L / d joints of the two terms).
+    `contract`: handed to lbs() and lbs_vjp()."""
     theta = np.asarray(theta, dtype).reshape(-1, 69)
     T = theta.shape[0]
-    verts, joints, cache = lbs(theta, model, dtype, keep=True)
+    verts, joints, cache = lbs(theta, model, dtype, keep=True, contract=contract)
     gV = np.zeros_like(verts)
     gJ = np.zeros_like(joints)
     terms = {}
@@ -164,5 +229,5 @@ def body_terms(theta, joints0, model, it, dtype=np.float64, coefs=None, keep=Fal
         with np.errstate(divide="ignore", invalid="ignore"):
             gJ += diff / nrm * (dtype(100.0 / (1 + it) if coefs is None else coefs[1]) / dtype(nrm.size))
     if keep:
-        return lbs_vjp(model, cache, gV, gJ, dtype), terms, dict(cache, gV=gV, gJ=gJ)
-    return lbs_vjp(model, cache, gV, gJ, dtype), terms
+        return lbs_vjp(model, cache, gV, gJ, dtype, contract), terms, dict(cache, gV=gV, gJ=gJ)
+    return lbs_vjp(model, cache, gV, gJ, dtype, contract), terms

@@ -3,16 +3,25 @@ the numpy oracle oracle/lbs_np.py -- parity UNPINNED (smplx and the SMPL files a
 restates the published algorithm, model parameters are synthetic with SMPL's shapes (6,890 vertices, 24 joints, 21 picked
 joints).  Both arithmetics of the forward / fused-terms passes run every test: "f16x3" (the default: fp16 MFMAs on operands
 split into hi + lo halves, fp32 accumulate) and "fp32" (fp32 MFMAs).  Tolerances are the same for both: errors are measured
-against the fp64 oracle and held to 1e-4 relative (north_star's bar) and to a multiple of the fp32 oracle's own error."""
+against the fp64 oracle and held to 1e-4 relative (north_star's bar) and to a multiple of the fp32 oracle's own error.
+The forward, fused-terms and general-reverse tests also hold every vertex, joint and frame on its own (tests/lbs_gates.py)."""
 import numpy as np
 import pytest
 import torch
 
+import lbs_gates
 from conftest import golden_weights
 from oracle import denoise_np, lbs_np
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
+_ONCE = {}      # fp64 results and envelopes of the marginal gates (tests/lbs_gates.py), shared by the two arithmetics' runs
+
+
+def once(key, fn):
+    if key not in _ONCE:
+        _ONCE[key] = fn()
+    return _ONCE[key]
 
 
 @pytest.fixture(scope="module", params=["f16x3", "fp32"])
@@ -53,6 +62,15 @@ def test_forward_vertices_and_joints(smpl_like, N):
     # another arithmetic than the vertex kernels' MFMAs -- equal to rounding, and held to the fp64 oracle by itself
     jo = bm.joints_of(torch.from_numpy(th)).cpu().numpy()
     assert jo.shape == (N, 45, 3) and _rel(jo, J64) < 1e-5 and _rel(jo, out.Jtr.cpu().numpy().astype(np.float64)) < 2e-6
+    # every vertex, joint and frame on its own, against eight draws of the kernel's reference arithmetic (joints_of: fp32 VALU)
+
+    def envelope(precision):
+        return lambda: lbs_gates.envelope(lbs_gates.forward_ref(m, lbs_gates.arithmetic(precision, m)), [th], (V64, J64))
+    env_v, env_j = once(("fwd env", bm.precision, N), envelope(bm.precision))
+    env_o = once(("fwd env", "fp32", N), envelope("fp32"))[1]
+    lbs_gates.gate(f"forward {bm.precision} N={N} verts", out.vertices.cpu().numpy(), V64, env_v, lbs_gates.VERTICES)
+    lbs_gates.gate(f"forward {bm.precision} N={N} Jtr", out.Jtr.cpu().numpy(), J64, env_j, lbs_gates.JOINTS)
+    lbs_gates.gate(f"forward {bm.precision} N={N} joints_of", jo, J64, env_o, lbs_gates.JOINTS)
 
 
 @pytest.mark.parametrize("S,T,it", [(1, 1, 2), (2, 16, 0), (3, 33, 0), (3, 33, 2), (1, 31, 3), (2, 46, 1)])
@@ -75,6 +93,14 @@ def test_fused_terms_gradient(smpl_like, S, T, it):
             assert np.all(g[s] == 0)
         else:
             assert np.isfinite(g[s]).all() and err < max(TOL, 8 * ref)
+    if (S, T, it) in ((2, 16, 0), (1, 31, 3)):      # every (sequence, joint) and (sequence, frame) on its own, at SMPL size
+        def truth():
+            J0 = np.stack([lbs_np.lbs(th0[s], m)[1] for s in range(S)]).astype(np.float32)
+            return J0, lbs_gates.terms_ref(m, it, dtype=np.float64)(th, J0)
+        J0, x64 = once(("grad", S, T, it), truth)
+        hook = lbs_gates.arithmetic(bm.precision, m, T, lbs_gates.schedule_coefs(it))
+        env = once(("grad env", bm.precision, S, T, it), lambda: lbs_gates.envelope(lbs_gates.terms_ref(m, it, None, hook), [th, J0], x64))
+        lbs_gates.gate(f"terms grad {bm.precision} S={S} T={T} it={it}", g.reshape(x64.shape), x64, env, lbs_gates.GRADIENT)
 
 
 def test_general_reverse_pass_through_autograd(smpl_like):
@@ -93,7 +119,13 @@ def test_general_reverse_pass_through_autograd(smpl_like):
     # vertices only / joints only
     t2 = torch.from_numpy(th).cuda().requires_grad_(True)
     (bm(pose_body=t2).Jtr * torch.from_numpy(gj).cuda()).sum().backward()
-    assert _rel(t2.grad.cpu().numpy(), lbs_np.lbs_vjp(m, cache, np.zeros_like(gv), gj)) < 1e-5
+    g64_j = lbs_np.lbs_vjp(m, cache, np.zeros_like(gv), gj)
+    assert _rel(t2.grad.cpu().numpy(), g64_j) < 1e-5
+    # every joint and every frame on its own; pndf_lbs_backward is fp32 under either setting
+    for what, got, x64, gvs in (("verts + joints", t.grad, g64, gv), ("joints", t2.grad, g64_j, np.zeros_like(gv))):
+        x64 = x64.reshape(1, 21, 23, 3)
+        env = once(("vjp env", what), lambda: lbs_gates.envelope(lbs_gates.vjp_ref(m), [th, gvs, gj], x64))
+        lbs_gates.gate(f"general reverse {bm.precision} {what}", got.cpu().numpy().reshape(x64.shape), x64, env, lbs_gates.GRADIENT)
 
 
 def test_large_batch_matches_small_batch(smpl_like):

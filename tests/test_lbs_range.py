@@ -8,7 +8,11 @@ up to |R - I| = 2 and term weights six decades apart (tests/lbs_stress.py).
   arithmetic model  the four contractions from fp16 hi / lo halves with the three kept products, in float64, against the exact
                     contraction: the split arithmetic's predicted error per length unit, below the gates of the GPU tests
                     (tests/test_lbs_range_gpu.py).  The halves are rounded to nearest (test_lbs_split_layout.split, as the host
-                    packer does); the device splits its own operands toward zero, which costs up to 2^-21 more per operand."""
+                    packer does); the device splits its own operands toward zero, which costs up to 2^-21 more per operand.
+  marginal gates    tests/lbs_gates.py, the per-joint / per-frame / per-vertex gates of the GPU tests, held here against the
+                    oracle's two reference arithmetics (float32, and oracle/lbs_np.split_contractions = the split kernels'
+                    stated arithmetic): sound (a ninth draw passes the gate of the other eight) and sharp (a cross product
+                    dropped from one contraction leaves it; the older whole-sequence gates let "d/d A" mutants through)."""
 import numpy as np
 import pytest
 
@@ -123,8 +127,9 @@ def test_every_operand_stays_below_its_bound(lib):
     assert not failures, "\n".join(failures)
 
 
-def contraction_errors(lib, unit, motion, coefs, products=("hh", "hl", "lh"), V=137):
-    """{contraction: error of the split arithmetic relative to the largest exact output entry} at the library's scales"""
+def contraction_errors(lib, unit, motion, coefs, products=("hh", "hl", "lh"), V=137, full=False):
+    """{contraction: error of the split arithmetic relative to the largest exact output entry} at the library's scales;
+    full=True: {contraction: (einsum spec, model operand, per-frame operand, its result in scaled units)} and the scales"""
     from test_lbs_oracle import _pack
     m = stress_model(V, 9, unit=unit)
     sc = read_scales(lib, _pack(m), *term_weights(m, T, coefs))
@@ -140,14 +145,15 @@ def contraction_errors(lib, unit, motion, coefs, products=("hh", "hl", "lh"), V=
             "skinning": ("vj,nje->nve", W * sc["w_scale"], A * sc["a_scale"]),
             "d/d pose feature": ("kvc,nvc->nk", P * sc["p_scale"], op["g"][keep] * sc["g_scale"]),
             "d/d A": ("vj,nve->nje", W * sc["w_scale"], x * sc["x_scale"])}
-    errs = {}
+    errs, everything = {}, {}
     for name, (spec, a, b) in jobs.items():
         (ah, al), (bh, bl) = split(a), split(b)
         assert np.isfinite(ah).all() and np.isfinite(bh).all(), name      # (fp16 overflow would show as inf here)
         got = sum(np.einsum(spec, u, v) for key, u, v in (("hh", ah, bh), ("hl", ah, bl), ("lh", al, bh)) if key in products)
         want = np.einsum(spec, a, b)
         errs[name] = float(np.abs(got - want).max() / max(np.abs(want).max(), 1e-300))
-    return errs
+        everything[name] = (spec, a, b, got)
+    return (everything, sc) if full else errs
 
 
 GATES = {"pose blend": FORWARD_GATE, "skinning": FORWARD_GATE, "d/d pose feature": GRADIENT_GATE, "d/d A": GRADIENT_GATE}
@@ -172,3 +178,159 @@ def test_arithmetic_model_sees_a_dropped_product(lib):
     e = contraction_errors(lib, 1.0, "ordinary", COEFS[3], products=("hh", "hl"))
     print("split arithmetic without lo hi: " + "  ".join(f"{k} {v:.2e}" for k, v in e.items()))
     assert e["pose blend"] > FORWARD_GATE and e["skinning"] > FORWARD_GATE
+
+
+# ---------------------------------------------------------------- the marginal gates (tests/lbs_gates.py), held on the host
+def test_split_halves_follow_the_two_rounding_rules():
+    """to nearest = test_lbs_split_layout.split bit for bit; toward zero: |hi| <= |x| always, saturating at 65504, and hi + lo
+    within 2^-21 |x| (hi leaves up to 2^-10, lo keeps 11 bits of that)"""
+    rng = np.random.default_rng(3)
+    x = np.concatenate([rng.normal(size=4000) * 10.0 ** rng.uniform(-3, 4, 4000), [0.0, 65504.0, -65519.9, 70000.0, 2.0 ** -14, -1e-7]])
+    for mine, theirs in zip(lbs_np.split_halves(x), split(x[np.abs(x) < 65520])):
+        assert np.array_equal(mine[np.abs(x) < 65520], theirs)
+    hi, lo = lbs_np.split_halves(x, toward_zero=True)
+    assert (np.abs(hi) <= np.abs(x)).all() and np.abs(hi).max() == 65504.0 and (hi * x >= 0).all()
+    inside = np.abs(x) <= 65504
+    assert (np.abs(hi + lo - x)[inside] <= 2.0 ** -21 * np.abs(x)[inside] + 2.0 ** -25).all()      # (+ half an fp16 subnormal)
+
+
+@pytest.mark.parametrize("products", [lbs_np.PRODUCTS, ("hh", "hl"), ("hh", "lh")])
+def test_split_mode_oracle_reproduces_the_arithmetic_model(lib, products):
+    """each of the four contractions of lbs_np.split_contractions, taken alone with both operands rounded to nearest and float64
+    accumulation, is contraction_errors' `got` for the same operands and scales (to the summation order); in the device's form
+    (float32 operands, per-frame operand split toward zero, float32 accumulation) the full product set stays inside
+    (2^-19 + K 2^-24) sum |a| |b|, K the contraction length"""
+    jobs, sc = contraction_errors(lib, 1.0, "ordinary", COEFS[3], products=products, full=True)
+    assert list(jobs) == list(lbs_np.CONTRACTIONS)
+    for name, (spec, a, b, got) in jobs.items():
+        sa, sb = (sc[k] for k in lbs_np.CONTRACTIONS[name])
+        model64 = lbs_np.split_contractions(sc, {name: products}, device_rounding=False, acc=np.float64)
+        mine = model64(name, spec, a / sa, b / sb) * (sa * sb)
+        assert np.abs(mine - got).max() <= 1e-12 * np.abs(got).max(), (name, products)
+        if products == lbs_np.PRODUCTS:
+            K = {"pose blend": 207, "skinning": 24, "d/d pose feature": 3 * 137, "d/d A": 137}[name]
+            dev = lbs_np.split_contractions(sc)(name, spec, (a / sa).astype(np.float32), (b / sb).astype(np.float32)).astype(np.float64) * (sa * sb)
+            assert dev.dtype == np.float64 and (np.abs(dev - np.einsum(spec, a, b)) <= (2.0 ** -19 + K * 2.0 ** -24) * np.einsum(spec, np.abs(a), np.abs(b))).all(), name
+
+
+_GATE_CASES = {}
+
+
+def gate_case(lib, V, unit, motion, coefs=COEFS[3]):
+    """model, inputs, fp64 truth and the two reference arithmetics' envelopes (forward and gradient) of one case, made once"""
+    import lbs_gates
+    key = (V, unit, motion, coefs)
+    if key not in _GATE_CASES:
+        from test_lbs_oracle import _pack
+        m = stress_model(V, 9, unit=unit)
+        th = stress_theta(S, T, 4, motion)
+        th0 = th + np.random.default_rng(1).normal(size=th.shape).astype(np.float32) * 0.05
+        j0 = lbs_np.lbs(th0.reshape(-1, 69), m)[1].astype(np.float32).reshape(S, T, -1, 3)
+        flat = th.reshape(-1, 69)
+        hooks = {"fp32": None, "f16x3": lbs_np.split_contractions(read_scales(lib, _pack(m), *term_weights(m, T, coefs)))}
+        fwd64 = lbs_np.lbs(flat, m)
+        grad64 = lbs_gates.terms_ref(m, 1, coefs, dtype=np.float64)(th, j0)
+        env = {p: (lbs_gates.envelope(lbs_gates.forward_ref(m, h), [flat], fwd64),
+                   lbs_gates.envelope(lbs_gates.terms_ref(m, 1, coefs, h), [th, j0], grad64)) for p, h in hooks.items()}
+        _GATE_CASES[key] = dict(m=m, th=th, j0=j0, flat=flat, hooks=hooks, fwd64=fwd64, grad64=grad64, env=env,
+                                scales=read_scales(lib, _pack(m), *term_weights(m, T, coefs)))
+    return _GATE_CASES[key]
+
+
+@pytest.mark.parametrize("motion", ["ordinary", "wide", "slow"])
+@pytest.mark.parametrize("unit", UNITS)
+@pytest.mark.parametrize("V", [41, 137])
+def test_marginal_gate_is_sound(lib, V, unit, motion):
+    """a ninth draw of each reference arithmetic passes the gate built from the other eight: forward (vertices, joints) and
+    gradient, float32 and split.  A reference that fails its own gate would mean the gate is wrong."""
+    import lbs_gates
+    c = gate_case(lib, V, unit, motion)
+    for p, hook in c["hooks"].items():
+        (env_v, env_j), env_g = c["env"][p]
+        v9, j9 = lbs_gates.forward_ref(c["m"], hook)(*lbs_gates.perturbed([c["flat"]], lbs_gates.DRAWS))
+        g9 = lbs_gates.terms_ref(c["m"], 1, COEFS[3], hook)(*lbs_gates.perturbed([c["th"], c["j0"]], lbs_gates.DRAWS))
+        tag = f"ninth draw {p} V={V} unit={unit:g} {motion}"
+        lbs_gates.gate(tag + " verts", v9, c["fwd64"][0], env_v, lbs_gates.VERTICES)
+        lbs_gates.gate(tag + " joints", j9, c["fwd64"][1], env_j, lbs_gates.JOINTS)
+        lbs_gates.gate(tag + " grad", g9, c["grad64"], env_g, lbs_gates.GRADIENT)
+
+
+MUTANTS = [(name, kept) for name in lbs_np.CONTRACTIONS for kept in (("hh", "hl"), ("hh", "lh"))]
+MUTANT_NAMES = {("hh", "hl"): "lo hi", ("hh", "lh"): "hi lo"}      # kept products -> the product left out (model x per-frame operand)
+
+
+def mutant_table(lib, device_rounding):
+    """{mutant: worst error / bound per result over the marginals, and the whole-sequence error against the older gradient gate
+    max(1e-4, 8 ref) of tests/test_lbs_range_gpu.check_gradient}: unit 1, ordinary, COEFS[3], V = 137, T = 17"""
+    import lbs_gates
+    c = gate_case(lib, 137, 1.0, "ordinary")
+    (env_v, env_j), env_g = c["env"]["f16x3"]
+    ref32 = lbs_gates.terms_ref(c["m"], 1, COEFS[3])(c["th"], c["j0"])
+    table = {}
+    for name, kept in MUTANTS:
+        hook = lbs_np.split_contractions(c["scales"], {name: kept}, device_rounding=device_rounding)
+        worst = {}
+        if name in ("pose blend", "skinning"):
+            v, j = lbs_gates.forward_ref(c["m"], hook)(c["flat"])
+            worst["verts"] = max(lbs_gates.marginal_ratios(v, c["fwd64"][0], env_v, lbs_gates.VERTICES).values())
+            worst["joints"] = max(lbs_gates.marginal_ratios(j, c["fwd64"][1], env_j, lbs_gates.JOINTS).values())
+        g = lbs_gates.terms_ref(c["m"], 1, COEFS[3], hook)(c["th"], c["j0"])
+        worst["grad"] = max(lbs_gates.marginal_ratios(g, c["grad64"], env_g, lbs_gates.GRADIENT).values())
+        old = []
+        for s in range(S):
+            scale = np.abs(c["grad64"][s]).max()
+            old.append(np.abs(g[s] - c["grad64"][s]).max() / scale / max(GRADIENT_GATE, 8 * np.abs(ref32[s] - c["grad64"][s]).max() / scale))
+        worst["old gradient gate"] = float(max(old))
+        table[f"{name} without {MUTANT_NAMES[kept]}"] = worst
+        print(f"[lbs_gate mutant, halves {'toward zero' if device_rounding else 'to nearest'}] {name:17s} without {MUTANT_NAMES[kept]}: "
+              + "  ".join(f"{k} {v:.3g}" for k, v in worst.items()))
+    return table
+
+
+ESCAPES = ("d/d pose feature without lo hi", "d/d pose feature without hi lo")
+
+
+def test_marginal_gate_is_sharp(lib):
+    """The split-mode oracle with lo hi or hi lo left out of ONE contraction -- eight mutants; unit 1, ordinary, COEFS[3],
+    V = 137, S = 2, T = 17 -- against the gate the GPU tests hold the f16x3 kernels to (envelope: the split arithmetic with the
+    device's halves).  Worst error / bound over the marginals (> 1: caught), and the whole-sequence error over the older gradient
+    gate max(1e-4, 8 ref) (< 1: that gate lets it through):
+
+                                       per-frame halves toward zero (the device)      both halves to nearest (contraction_errors)
+                                       verts   joints  grad    older gradient gate    verts   joints  grad    older gradient gate
+      pose blend        without lo hi  2.01    0.593   0.325   0.031                  2.03    0.575   0.328   0.031
+      pose blend        without hi lo  4.9     1.08    0.856   0.066                  2.5     0.971   0.962   0.031
+      skinning          without lo hi  151     32.3    16.9    1.97                   151     32.3    16.9    1.98
+      skinning          without hi lo  335     274     161     9.25                   168     221     190     9.8
+      d/d pose feature  without lo hi                  0.124   0.016                                  0.113   0.015
+      d/d pose feature  without hi lo                  0.303   0.016                                  0.367   0.016
+      d/d A             without lo hi                  3.57    0.205                                  3.57    0.205
+      d/d A             without hi lo                  51      2.97                                   7.37    0.407
+
+    Asserted.  Six of the eight mutants leave the gate on at least one marginal, under either rounding of the halves.  The
+    acceptance case: "d/d A" without lo hi passes the older gate (0.2 of it) and is 3.6 times over the new one -- a reverse pass
+    that had lost a third of its products passed the suite.  "d/d A" without hi lo does the same when the halves are rounded to
+    nearest, the arithmetic of contraction_errors; with the device's halves (hi toward zero: the lo half is one-sided and up
+    to twice as large) its error is 3e-4 of the largest entry and the older gate caught it as well (2.97), the new one at 51.
+    ESCAPES: the two "d/d pose feature" mutants stay inside every marginal (0.11 to 0.37 of the bound).  The pose blend shapes of
+    this model reach 1 cm on a skeleton of metres, so what the gradient receives through d/d pose feature is 9e-4 of its
+    largest entry and at most 3 % of any joint's, and 2^-11 of that is below the float32 noise of the sum: a gate on
+    d L / d theta alone cannot see it at this model.  Recorded in profiles/lbs_gates/ratios.json; nothing is loosened for it."""
+    device, nearest = mutant_table(lib, True), mutant_table(lib, False)
+    for table in (device, nearest):
+        for key, worst in table.items():
+            caught = max(v for k, v in worst.items() if k != "old gradient gate") > 1.0
+            assert caught == (key not in ESCAPES), (key, worst)
+    assert device["d/d A without lo hi"]["old gradient gate"] < 1.0 < device["d/d A without lo hi"]["grad"]
+    for key in ("d/d A without lo hi", "d/d A without hi lo"):
+        assert nearest[key]["old gradient gate"] < 1.0 < nearest[key]["grad"], (key, nearest[key])
+    assert device["d/d A without hi lo"]["grad"] > 1.0 and device["d/d A without hi lo"]["old gradient gate"] > 1.0
+    # the unmutated split arithmetic itself is inside every gate
+    import lbs_gates
+    c = gate_case(lib, 137, 1.0, "ordinary")
+    (env_v, env_j), env_g = c["env"]["f16x3"]
+    v, j = lbs_gates.forward_ref(c["m"], c["hooks"]["f16x3"])(c["flat"])
+    g = lbs_gates.terms_ref(c["m"], 1, COEFS[3], c["hooks"]["f16x3"])(c["th"], c["j0"])
+    lbs_gates.gate("split oracle verts", v, c["fwd64"][0], env_v, lbs_gates.VERTICES)
+    lbs_gates.gate("split oracle joints", j, c["fwd64"][1], env_j, lbs_gates.JOINTS)
+    lbs_gates.gate("split oracle grad", g, c["grad64"], env_g, lbs_gates.GRADIENT)

@@ -7,12 +7,15 @@ Oracle: oracle/lbs_np.py in fp64 (parity unpinned, as in tests/test_lbs_gpu.py).
 arithmetics ("f16x3" and "fp32"):
   forward   vertices, Jtr, joints_of: error relative to the largest fp64 entry < 1e-5
   gradient  per sequence err < max(1e-4, 8 ref), ref = the fp32 oracle's own error against fp64 on the same input (printed)
+and next to them the marginal gates of tests/lbs_gates.py: every vertex, joint and frame on its own against eight draws of the
+kernel's reference arithmetic (float32; for "f16x3" the split arithmetic at the library's scales), made once per case.
 Shapes: V = 41 (three vertex groups, the last one padded) and 137; S = 2, T = 17 (a chunk boundary with a shared frame, two
 sequences in one workgroup quad)."""
 import numpy as np
 import pytest
 import torch
 
+import lbs_gates
 from lbs_stress import COEFS, SATURATING_TWINS, UNITS, stress_model, stress_theta
 from oracle import lbs_np
 
@@ -66,6 +69,14 @@ def check_forward(tag, key, m, bm, th):
     ev, ej, eo = (float(np.abs(a[ok] - b[ok]).max() / np.abs(b[ok]).max()) for a, b in ((v, V64), (j, J64), (jo, J64)))
     print(f"LBS range forward {tag}: verts {ev:.2e}  Jtr {ej:.2e}  joints_of {eo:.2e}")
     assert ev < 1e-5 and ej < 1e-5 and eo < 1e-5, tag
+
+    def envelope(precision):
+        return lambda: lbs_gates.envelope(lbs_gates.forward_ref(m, lbs_gates.arithmetic(precision, m)), [flat], (V64, J64))
+    env_v, env_j = once(("fwd env", bm.precision) + key, envelope(bm.precision))
+    env_o = once(("fwd env", "fp32") + key, envelope("fp32"))[1]      # joints_of runs on the fp32 VALU under either setting
+    lbs_gates.gate(f"range forward {tag} verts", v, V64, env_v, lbs_gates.VERTICES, ok)
+    lbs_gates.gate(f"range forward {tag} Jtr", j, J64, env_j, lbs_gates.JOINTS, ok)
+    lbs_gates.gate(f"range forward {tag} joints_of", jo, J64, env_o, lbs_gates.JOINTS, ok)
     return ok.reshape(th.shape[:2])
 
 
@@ -85,8 +96,19 @@ def check_gradient(tag, key, m, bm, th, it=0, coefs=None, data=True):
                 g32, _ = lbs_np.body_terms(th[s], None if J0 is None else J0.astype(np.float32), m, it, np.float32, coefs=coefs)
             rows.append((g64, g32))
         return rows
+    rows = once(("grad", it, coefs, data) + key, oracle)
+
+    def envelope():
+        weights = coefs if coefs is not None else lbs_gates.schedule_coefs(it)
+        hook = lbs_gates.arithmetic(bm.precision, m, th.shape[1], weights if data else (weights[0], 0.0))
+        with np.errstate(invalid="ignore"):
+            J0 = np.stack([lbs_np.lbs(th0[s], m)[1] for s in range(th.shape[0])]).astype(np.float32) if data else None
+        x64 = np.stack([g64 for g64, _ in rows]).reshape(th.shape[:2] + (23, 3))
+        return x64, lbs_gates.envelope(lbs_gates.terms_ref(m, it, coefs, hook), [th, J0], x64)
+    x64, env = once(("grad env", bm.precision, it, coefs, data) + key, envelope)
+    lbs_gates.gate(f"range grad {tag}", g.reshape(x64.shape), x64, env, lbs_gates.GRADIENT, np.isfinite(x64).all((2, 3)))
     bad_rows = []
-    for s, (g64, g32) in enumerate(once(("grad", it, coefs, data) + key, oracle)):
+    for s, (g64, g32) in enumerate(rows):
         good = np.isfinite(g64).all(1)
         assert not np.isfinite(g64[~good]).any()                     # (the oracle's non-finite rows are non-finite throughout)
         assert np.isfinite(g[s][good]).all() and not np.isfinite(g[s][~good]).any(), (tag, s, np.flatnonzero(~good))
