@@ -250,6 +250,44 @@ typedef struct {
     float          nu;             /* weight of the keypoint term, finite and >= 0 */
 } pndf_project_options5;           /* 128 bytes */
 
+/* The options with a camera: the keypoint term of pndf_project_options5 on 2D detections, and a placement of the joint tree in the
+ * target's frame (the "root": a rotation and a translation per pose) that the step may move.  For one pose, at the step's input iterate,
+ * every operation rounded to fp32 on its own in the order written:
+ *   c^ = c / max(|c|, 1e-12), R_c its rotation matrix;  C_k = R_c P_k + s  (P_k as above, in the roots' frame); root == NULL: C_k = P_k
+ *   kp_flags == 0:     kp_target [B,K,3],  e_k = C_k - Y_k,  E = 1/2 sum_k w_k |e_k|^2,  a_k = dE/dC_k = w_k e_k
+ *   PNDF_KP_IMAGE:     kp_target [B,K,2] in pixels.  A keypoint for which C_kz > 0 is false (behind the camera, in its plane, NaN) takes
+ *                      no part in that step, as one whose w_k > 0 is false.  Otherwise n = (C_x / C_z, C_y / C_z),
+ *                      y' = ((Y_u - cx) / fx, (Y_v - cy) / fy), e = n - y' (normalised image coordinates: E does not depend on the
+ *                      resolution), E = 1/2 sum_k w_k [rho(e_u) + rho(e_v)] with rho(e) = e^2 for rho == 0, else
+ *                      rho^2 e^2 / (e^2 + rho^2); with psi(e) = e for rho == 0, else e rho^4 / (e^2 + rho^2)^2:
+ *                      a_k = w_k (psi_u / C_z, psi_v / C_z, -(psi_u n_u + psi_v n_v) / C_z)
+ *   into the tree:     dE/dP_k = R_c^T a_k takes the place of w_k (P_k - Y_k); the joints then step as with the 128-byte struct
+ *   into the root:     dE/ds = sum_k a_k;  the adjoint of R_c is sum_k a_k P_k^T, and dE/dc goes through R(c^) and c^ = c / |c| as a
+ *                      joint's does.  Unless the pose rests under tol: s <- s - nu_trans * dE/ds, and when nu_rot > 0
+ *                      c <- unit(c - nu_rot * dE/dc); with nu_rot == 0 c keeps its bits.  The root is not a joint: neither the joint
+ *                      mask nor the held end frames of tracks hold it.
+ * root [B,7] (c real part first, then s) is DEVICE memory for pndf_skel_project and HOST memory for pndf_project_ex_cpu; it is READ by
+ * every step and WRITTEN by every step when a root weight is positive.  With root == NULL, kp_flags == 0 and both root weights 0 the
+ * call is the one with the 128-byte struct, bit for bit; with kp_target == NULL or nu == 0, and both root weights 0, it is the one with
+ * the 72-byte struct and root is neither read nor written.  (Without a keypoint term there is no energy for the root to descend, so it is
+ * left as it is whatever its weights; to move the root alone, hold every joint with the mask.)  Fill it as a pndf_project_options5 with
+ *   o.base5.base4.base3.base2.base.struct_size = sizeof o;  o.root = placement;  o.fx = o.fy = 500.f;  o.cx = 320.f;  o.cy = 240.f;
+ *   o.nu_rot = 0.02f;  o.nu_trans = 0.02f;  o.kp_flags = PNDF_KP_IMAGE;
+ * Exactly the two entry points that take a pndf_project_options5 take it.  PNDF_ERR_BAD_ARG with a text that names the field, before
+ * anything is launched or written: a struct_size that is none of the six sizes, an unknown bit in kp_flags, a rho, nu_rot or nu_trans
+ * that is negative or not finite, rho != 0 without PNDF_KP_IMAGE, with PNDF_KP_IMAGE an fx or fy that is not finite or <= 0 or a cx or
+ * cy that is not finite, root == NULL with a positive root weight, a misaligned root, root overlapping q_out, with a positive root
+ * weight root overlapping q_in, anchor, conf, kp_target, kp_conf or kp_energy; and what is refused in `base5`. */
+enum { PNDF_KP_IMAGE = 1 };
+typedef struct {
+    pndf_project_options5 base5;  /* base5.base4.base3.base2.base.struct_size = sizeof(pndf_project_options6) */
+    float*   root;                /* [B,7] (c: quaternion, real part first; s: translation), or NULL = identity; DEVICE / HOST as the poses */
+    float    fx, fy, cx, cy;      /* pinhole intrinsics; read only with PNDF_KP_IMAGE */
+    float    rho;                 /* robustifier of the image residual, >= 0, 0 = squared error */
+    float    nu_rot, nu_trans;    /* weights of the root's own step, finite and >= 0; 0 = that part of the root is held */
+    uint32_t kp_flags;            /* 0 or PNDF_KP_IMAGE */
+} pndf_project_options6;          /* 168 bytes */
+
 /* pndf_project with step options.  opt == NULL means the defaults, and with the defaults the call is pndf_project bit for
  * bit.  PNDF_ERR_BAD_ARG (text in pndf_last_error; nothing is launched or written) for a struct_size other than
  * sizeof(pndf_project_options), a step_size that is not finite or <= 0, a tol that is NaN or < 0, an unknown renorm mode.
@@ -277,8 +315,9 @@ int pndf_project_cpu(pndf_cpu_handle h, const float* q_in, float* q_out, float* 
 int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps,
                         const pndf_project_options* opt);      /* pndf_project_ex: same semantics, same validation; also takes a
                                                                   pndf_project_options2, a pndf_project_options3, a
-                                                                  pndf_project_options4 or a pndf_project_options5,
-                                                                  `observed` / `anchor` / `conf` / `kp_*` in HOST memory */
+                                                                  pndf_project_options4, a pndf_project_options5 or a
+                                                                  pndf_project_options6, `observed` / `anchor` / `conf` /
+                                                                  `kp_*` / `root` in HOST memory */
 const char* pndf_cpu_last_error(pndf_cpu_handle h);   /* h may be NULL: last error of a failed pndf_cpu_create */
 
 /* Host-only weight packer (what pndf_load_weights uploads); needs no device.  Output sizes in floats come

@@ -50,9 +50,18 @@
  * step of the gradient's last kernel (its fourth instantiation), so a fitting step costs no launch more; the 72-byte struct's mask, tracks
  * and observation come along unchanged.
  *
- * Still 21-joint: the second order (posendf_amd_second_order.h) only; 2D keypoints with a camera (pndf_keypoint_terms_grad, pndf_lbs_*) need
- * the SMPL body model; pndf_complete, pndf_interpolate and their host twins keep the
- * SMPL table.
+ * Image fitting -- the same inverse kinematics on what a tracker of another joint tree delivers: 2D detections, and a placement of the tree
+ * in the camera that nobody knows in advance -- is the same two entry points with a pndf_project_options6 (posendf_amd.h): root [B,7] in
+ * device memory (a quaternion and a translation per pose, C_k = R(c) P_k + s, read and -- with nu_rot or nu_trans positive -- written by
+ * every step), the pinhole intrinsics, rho and PNDF_KP_IMAGE (kp_target is [B,K,2] pixels; the residual in normalised image coordinates,
+ * a keypoint not in front of the camera skipped).  The camera, both residual kinds, the adjoint into the tree, the root's adjoints and
+ * the root's step sit in the step of the gradient's last kernel (its fifth instantiation), so an image step costs no launch more and the
+ * workspace is what it was; the 128-byte struct's keypoints, mask, tracks and observation come along unchanged.
+ *
+ * Still 21-joint: the second order (posendf_amd_second_order.h) only -- pndf_so_create refuses another joint count and
+ * pndf_second_order_cpu a handle of another tree, and that is pinned.  2D keypoints with a camera run for any joint tree through
+ * pndf_skel_project (above); pndf_keypoint_terms_grad and pndf_lbs_* are the SMPL body model's (vertices, shape, lens of ImageFit).
+ * pndf_complete, pndf_interpolate and their host twins keep the SMPL table.
  */
 #ifndef POSENDF_AMD_SKELETON_H
 #define POSENDF_AMD_SKELETON_H

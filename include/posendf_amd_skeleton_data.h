@@ -9,8 +9,8 @@
  * [.., 21, 4].  num_joints outside 1 .. 32 is PNDF_ERR_BAD_ARG, decided before any pointer is looked at (the rule of
  * pndf_skel_train_batch).
  *
- * Still 21-joint: pndf_quat_topk (dist_utils.geo / euc) and the second order (completion, interpolation, motion denoising and 3D keypoint
- * fitting for J joints: pndf_skel_project with a pndf_project_options2 / 3 / 4 / 5, posendf_amd_skeleton.h).
+ * Still 21-joint: pndf_quat_topk (dist_utils.geo / euc) and the second order (completion, interpolation, motion denoising and 3D / 2D keypoint
+ * fitting for J joints: pndf_skel_project with a pndf_project_options2 / 3 / 4 / 5 / 6, posendf_amd_skeleton.h).
  */
 #ifndef POSENDF_AMD_SKELETON_DATA_H
 #define POSENDF_AMD_SKELETON_DATA_H

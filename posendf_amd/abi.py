@@ -24,6 +24,7 @@ PRECISION_CODES = {"fp32": 0, "f16x3": 1, "f16": 2, "bf16": 3}
 RENORM_CODES = {"none": 0, "unit": 1, "unit_flip": 2}      # PNDF_RENORM_*
 INTERP_MODES = {"slerp": 0, "nlerp": 1}                    # PNDF_INTERP_*
 TRACK_FILLS = {"given": 0, "slerp": 1, "nlerp": 2}         # PNDF_TRACK_*
+KP_IMAGE = 1                                               # PNDF_KP_IMAGE (pndf_project_options6.kp_flags)
 TRACK_FREE_ENDS = 1                                        # PNDF_TRACK_FREE_ENDS (pndf_project_options4.flags)
 NOISE_CODES = {"uniform": 0, "symmetric": 1}               # PNDF_ONLINE_*
 METRIC_CODES = {"geo": 0, "euc": 1}
@@ -68,6 +69,16 @@ class ProjectOptions5(ctypes.Structure):
                 ("kp_joint", c_void_p), ("kp_offset", c_void_p), ("n_keypoints", c_int32), ("nu", c_float)]
 
 
+class ProjectOptions6(ctypes.Structure):
+    """pndf_project_options6: the options with a mask, tracks, an observation and keypoints (`base5`, with
+    base5.base4.base3.base2.base.struct_size = 168) and a camera -- `root` [B,7] (quaternion, real part first, then translation; None:
+    identity) in the memory space of the poses, read and (with a positive root weight) written by every step; `fx`, `fy`, `cx`, `cy` the
+    pinhole intrinsics and `rho` the robustifier of the image residual; `nu_rot`, `nu_trans` the weights of the root's own step;
+    `kp_flags` 0 or KP_IMAGE (kp_target is [B,K,2] pixels); taken by the two entry points that take a ProjectOptions5"""
+    _fields_ = [("base5", ProjectOptions5), ("root", c_void_p), ("fx", c_float), ("fy", c_float), ("cx", c_float), ("cy", c_float),
+                ("rho", c_float), ("nu_rot", c_float), ("nu_trans", c_float), ("kp_flags", ctypes.c_uint32)]
+
+
 class DenoiseWeights(ctypes.Structure):
     """pndf_denoise_weights: the loss weights of one outer iteration, evaluated"""
     _fields_ = [("prior_coef", c_float), ("prior_power", c_int32), ("temp_coef", c_float), ("data_coef", c_float)]
@@ -97,7 +108,7 @@ class PndfError(RuntimeError):
 _H = c_void_p                          # every handle type, and every `void* stream`
 _P = c_void_p                          # any other address: tensor data (an int from data_ptr(), or None), a callback, an out value
 _TENSORS = [POINTER(c_void_p), POINTER(c_int64), c_int]      # tensors, numel, n_tensors (host pointers in state-dict order)
-_OPT2 = c_void_p                       # `const pndf_project_options*` where it may point to a ProjectOptions, a ProjectOptions2 .. a ProjectOptions5 (byref of any)
+_OPT2 = c_void_p                       # `const pndf_project_options*` where it may point to a ProjectOptions, a ProjectOptions2 .. a ProjectOptions6 (byref of any)
 # ---- the header set, stated once: header of include/ -> {name: (restype, argtypes)} in the header's order; the headers in the order
 # they were added.  A new header is a file in include/, a table here and its declaration count in tests/test_cabi.py.
 DEBUG_HEADER = "posendf_amd_debug.h"      # the one header that lives in libposendf_amd_debug.so; every other one in the product library

@@ -5,8 +5,8 @@
 // fallback: the device entry points never route here, a missing GPU still fails loudly there.  The first-order twins take the joint
 // count and the parent table from the handle's config (any joint tree of include/posendf_amd_skeleton.h, pndf_net_plan.h); on the
 // SMPL table they compute what they did with the table fixed.  pndf_complete_cpu, pndf_interpolate_cpu and the second order stay 21-joint;
-// pndf_project_ex_cpu completes, interpolates, denoises and fits 3D keypoints for any joint tree (pndf_project_options2 /
-// pndf_project_options3 / pndf_project_options4 / pndf_project_options5).
+// pndf_project_ex_cpu completes, interpolates, denoises and fits 3D or 2D keypoints for any joint tree (pndf_project_options2 /
+// pndf_project_options3 / pndf_project_options4 / pndf_project_options5 / pndf_project_options6).
 //
 // Layout: poses are processed in blocks of PB = 32; inside a block every activation tensor is [feature][pose] so that the
 // inner loop of a layer runs over the 32 poses of the block (contiguous floats: one or two AVX-512 / four AVX2 registers)
@@ -408,12 +408,28 @@ struct KeypointTables {
 };
 
 // The keypoint term of pose number `pose` at the iterate q: pndf_fk.h's pndf_fk_energy_grad -- the statement the device kernel runs -- on
-// a local array of rows (ld = 1).  gk [nj][4] = d E / d Q; returns E.
+// a local array of rows (ld = 1).  gk [nj][4] = d E / d Q; returns E.  With the camera or the root of a pndf_project_options6 (`cam`) the
+// term is pndf_fk_camera_energy_grad, and the pose's root row takes its own step here (pndf_fk_root_step; `dist` and `tol` say whether
+// the pose rests): it is read before the term and nothing else of the step reads it.
 static float keypoint_grad_cpu(const PndfKeypoints& kp, const KeypointTables& tb, const int* parent, int nj, const float* q, int64_t pose,
-                               float* gk) {
+                               float* gk, const PndfCameraTerm& cam = PndfCameraTerm(), float dist = 0.f, float tol = 0.f) {
     float W[PNDF_FK_ROWS * MAXJ];
-    const float E = pndf_fk_energy_grad(q, nj, parent, tb.rest, kp.K, tb.kpj, tb.kpo, kp.target + pose * kp.K * 3,
-                                        kp.conf ? kp.conf + pose * kp.K : nullptr, W, 1);
+    float E;
+    if (cam.any()) {
+        const PndfFkCamera fc{cam.fx, cam.fy, cam.cx, cam.cy, cam.rho, cam.image ? 1 : 0};
+        float root[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, groot[7], stepped[7];
+        float* rt = cam.root ? cam.root + pose * 7 : nullptr;
+        if (rt) memcpy(root, rt, sizeof(root));
+        E = pndf_fk_camera_energy_grad(q, nj, parent, tb.rest, kp.K, tb.kpj, tb.kpo, kp.target + pose * kp.K * kp.dims,
+                                       kp.conf ? kp.conf + pose * kp.K : nullptr, rt != nullptr, root, fc, groot, W, 1);
+        if (cam.moves()) {
+            pndf_fk_root_step(root, groot, cam.nu_rot, cam.nu_trans, dist, tol, stepped);
+            memcpy(rt, stepped, sizeof(stepped));
+        }
+    } else {
+        E = pndf_fk_energy_grad(q, nj, parent, tb.rest, kp.K, tb.kpj, tb.kpo, kp.target + pose * kp.K * 3,
+                                kp.conf ? kp.conf + pose * kp.K : nullptr, W, 1);
+    }
     for (int j = 0; j < nj; ++j)
         for (int c = 0; c < 4; ++c) gk[4 * j + c] = W[pndf_fk_grad_row(nj, j) + c];
     return E;
@@ -446,7 +462,7 @@ static void project_step_cpu(float* q, const float* dq, float d, const pndf_proj
 // block; `observed` null = no joint held; `data`: the observation of a pndf_project_options4 (none: the step without a data term).
 static int project_loop_cpu(pndf_cpu_handle h, const float* q_in, const uint32_t* observed, float* q_out, float* d_last, int64_t B,
                             int steps, const pndf_project_options& o, const PndfData& data = PndfData(),
-                            const PndfKeypoints& kp = PndfKeypoints()) {
+                            const PndfKeypoints& kp = PndfKeypoints(), const PndfCameraTerm& cam = PndfCameraTerm()) {
     const int NQ = h->nq();
     KeypointTables tb;
     if (kp.any()) pndf_fill_keypoint_tables(tb, kp, h->net.nj);
@@ -458,7 +474,7 @@ static int project_loop_cpu(pndf_cpu_handle h, const float* q_in, const uint32_t
         for (int s = 0; s < steps; ++s) {
             forward_grad_block(*h, qb, nb, nullptr, dd, dqb, true, S);
             for (int p = 0; p < nb; ++p) {
-                if (kp.any()) ee[p] = keypoint_grad_cpu(kp, tb, h->net.parent, h->net.nj, qb + p * NQ, p0 + p, gk);
+                if (kp.any()) ee[p] = keypoint_grad_cpu(kp, tb, h->net.parent, h->net.nj, qb + p * NQ, p0 + p, gk, cam, dd[p], o.tol);
                 project_step_cpu(qb + p * NQ, dqb + p * NQ, dd[p], o, observed ? observed[p0 + p] : 0u, h->net.nj,
                                  data.anchor ? data.anchor + (p0 + p) * NQ : nullptr, data.conf ? data.conf + (p0 + p) * h->net.nj : nullptr, data.mu,
                                  kp.any() ? gk : nullptr, kp.nu);
@@ -496,7 +512,8 @@ extern "C" int pndf_complete_cpu(pndf_cpu_handle h, const float* q_in, const uin
 // denoising; none: the band step, which pndf_denoise_quat is for an interior frame without a data term).
 static int track_loop_cpu(pndf_cpu_handle h, const float* a, int64_t a_stride, const float* b, int64_t b_stride, int fill,
                           const uint32_t* observed, float* track_out, float* d_last, int64_t P, int32_t T, int steps, float lambda,
-                          const pndf_project_options& o, const PndfData& data = PndfData(), const PndfKeypoints& kp = PndfKeypoints()) {
+                          const pndf_project_options& o, const PndfData& data = PndfData(), const PndfKeypoints& kp = PndfKeypoints(),
+                          const PndfCameraTerm& cam = PndfCameraTerm()) {
     const int nj = h->net.nj;
     const int64_t nq = h->nq(), B = P * T;
     int rc = PNDF_OK;
@@ -527,7 +544,7 @@ static int track_loop_cpu(pndf_cpu_handle h, const float* a, int64_t a_stride, c
                 const int nbr = (k > 0 ? 1 : 0) | (k < T - 1 ? 2 : 0);
                 const uint32_t held = (nbr != 3 && !data.free_ends) ? ~0u : (observed ? observed[f] : 0u);
                 float gk[4 * MAXJ];
-                if (kp.any()) ee[f] = keypoint_grad_cpu(kp, tb, h->net.parent, nj, cur + f * nq, f, gk);
+                if (kp.any()) ee[f] = keypoint_grad_cpu(kp, tb, h->net.parent, nj, cur + f * nq, f, gk, cam, dd[f], o.tol);
                 for (int j = 0; j < nj; ++j) {
                     const int64_t i = (f * nj + j) * 4;
                     float u[4];
@@ -558,21 +575,23 @@ extern "C" int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* 
     PndfTracks tracks;             // a pndf_project_options3 the tracks besides: interpolation for any joint tree
     PndfData data;                 // a pndf_project_options4 the observation besides (host memory): motion denoising for any joint tree
     PndfKeypoints kp;              // a pndf_project_options5 the 3D keypoints besides (host memory): keypoint fitting for any joint tree
-    if (const char* why = pndf_check_project_options5(opt, B, h->net.nj, o, observed, tracks, data, kp)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    PndfCameraTerm cam;            // a pndf_project_options6 the camera and the root besides (host memory): image fitting for any joint tree
+    if (const char* why = pndf_check_project_options6(opt, B, h->net.nj, o, observed, tracks, data, kp, cam)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (!tracks.frames && !observed && !data.any() && !kp.any() && !kp.energy && pndf_project_options_plain(o))
         return pndf_project_cpu(h, q_in, q_out, d_last, B, steps);
     if (int rc = check(h, q_in, B)) return rc;
     if (steps < 0 || (B > 0 && !q_out)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count or null output pointer");
     if (const char* why = pndf_check_observation_apart(data, q_out, B, h->net.nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (const char* why = pndf_check_keypoints_apart(kp, q_out, B, h->net.nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
-    if (!tracks.frames) return project_loop_cpu(h, q_in, observed, q_out, d_last, B, steps, o, data, kp);
+    if (const char* why = pndf_check_root_apart(cam, data, kp, q_in, q_out, B, h->net.nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (!tracks.frames) return project_loop_cpu(h, q_in, observed, q_out, d_last, B, steps, o, data, kp, cam);
     if (B == 0) return PNDF_OK;
     const int64_t nq = h->nq(), T = tracks.frames;
     if ((uintptr_t)q_in < (uintptr_t)(q_out + B * nq) && (uintptr_t)q_out < (uintptr_t)(q_in + B * nq))
         return pndf_fail(h, PNDF_ERR_BAD_ARG, "q_out must not overlap q_in when pndf_project_options3.frames > 0: a step reads the neighbour "
                                               "frames of its input");
     return track_loop_cpu(h, q_in, T * nq, q_in + (T - 1) * nq, T * nq, tracks.fill, observed, q_out, d_last, B / T, (int32_t)T, steps,
-                          tracks.lambda, o, data, kp);
+                          tracks.lambda, o, data, kp, cam);
 }
 
 // Host twin of pndf_interpolate (include/posendf_amd_interpolation.h): track_loop_cpu on the 21-joint table; with lambda == 0 this is

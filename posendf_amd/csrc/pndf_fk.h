@@ -21,7 +21,7 @@
 // transforms indexed by a run-time parent would live in scratch memory), on the host a local array with ld = 1.  A child's adjoints
 // are added to its parent's rows in place.  Rows: G_j 9 j .., p_j 9 J + 3 j .., M_j 12 J + 9 j .., ap_j 21 J + 3 j ..; once joint j
 // is reversed the first four rows of M_j hold d E / d Q_j (pndf_fk_grad_row).  The step that takes nu * d E / d Q_j is pndf_fit_quat of
-// pndf_interp.h.
+// pndf_interp.h.  The camera term of a pndf_project_options6 -- a root per pose, a pinhole residual -- is a second entry further down.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -201,4 +201,161 @@ PNDF_HD float pndf_fk_energy_grad(const float* q, int nj, const int* parent, con
     }
     for (int j = nj - 1; j >= 0; --j) pndf_fk_joint_rev(q + 4 * j, parent[j], rest + 3 * j, W, ld, nj, j);
     return 0.5f * acc;
+}
+
+// ---- The camera term of a pndf_project_options6 (DESIGN.md section 2j "Image fitting"): the same tree, with a placement of it in the
+// target's frame (the "root" of a pose: c [4] a raw quaternion, real part first, s [3] a translation) and, with PNDF_KP_IMAGE, a pinhole
+// camera in front of the residual.  Stated once beside the 3D term, whose functions above stay as they are (their bits are pinned):
+//   c^ = pndf_fk_unit(c), R_c = pndf_fk_rot(c^);  C_k = R_c P_k + s, rows as pndf_fk_dot3;  without a root C_k = P_k, no arithmetic
+//   3D:     e = C - Y,  E = 1/2 sum_k w_k |e|^2,  a_k = w_k e
+//   image:  a keypoint for which C_z > 0 is false takes no part;  n = (C_x / C_z, C_y / C_z),  y' = ((Y_u - cx) / fx, (Y_v - cy) / fy),
+//           e = n - y',  E = 1/2 sum_k w_k [rho(e_u) + rho(e_v)],  a_k = w_k (psi_u / C_z, psi_v / C_z, -(psi_u n_u + psi_v n_v) / C_z)
+//           rho(e) = e^2 and psi(e) = e for rho == 0, else with r2 = rho rho, d = e e + r2:  (r2 (e e)) / d  and  (e (r2 r2)) / (d d)
+//   d E / d P_k = R_c^T a_k goes into ap and M as w_k (P_k - Y_k) does above;  d E / d s = sum_k a_k;  the adjoint of R_c is
+//   sum_k a_k P_k^T and d E / d c = pndf_fk_quat_adj of it.  The root's adjoints are 3 + 9 accumulators with fixed indices: registers.
+struct PndfFkCamera {
+    float fx, fy, cx, cy;      // read only with `image`
+    float rho;                 // the robustifier of the image residual; 0 = squared error
+    int image;                 // PNDF_KP_IMAGE: targets are [K][2] pixels
+};
+
+// rho(e) and psi(e) = 1/2 rho'(e)
+PNDF_HD float pndf_fk_robust(float e, float rho, float* psi) {
+#pragma clang fp contract(off)
+    const float ee = e * e;
+    if (rho == 0.f) {
+        *psi = e;
+        return ee;
+    }
+    const float r2 = rho * rho;
+    const float d = ee + r2;
+    const float num = r2 * ee;
+    const float r4 = r2 * r2;
+    const float en = e * r4;
+    const float dd = d * d;
+    *psi = en / dd;
+    return num / d;
+}
+
+// Keypoint on joint `a` at offset o with weight w > 0 under the camera: Y its target ([3], or [2] pixels), Rc / s the root (read only when
+// has_root: a flag and not a null pointer, so that on the device the arrays stay registers).
+// Its adjoint goes to ap_a and M_a and to the root's accumulators as [3] and AR [9]; returns acc + its energy (twice E's share).
+PNDF_HD float pndf_fk_camera_keypoint(int a, const float* o, const float* Y, float w, float acc, const PndfFkCamera& cam, bool has_root,
+                                      const float* Rc, const float* s, float* as, float* AR, float* W, int64_t ld, int nj) {
+#pragma clang fp contract(off)
+    const float* Ga = W + (int64_t)pndf_fk_G(nj, a) * ld;
+    const float* pa = W + (int64_t)pndf_fk_p(nj, a) * ld;
+    float* Ma = W + (int64_t)pndf_fk_M(nj, a) * ld;
+    float* aa = W + (int64_t)pndf_fk_ap(nj, a) * ld;
+    float P[3], C[3], adj[3];
+    for (int x = 0; x < 3; ++x) {
+        const float v = pndf_fk_dot3(Ga[(3 * x) * ld], o[0], Ga[(3 * x + 1) * ld], o[1], Ga[(3 * x + 2) * ld], o[2]);
+        P[x] = pa[x * ld] + v;
+    }
+    if (has_root) {
+        for (int x = 0; x < 3; ++x) {
+            const float v = pndf_fk_dot3(Rc[3 * x], P[0], Rc[3 * x + 1], P[1], Rc[3 * x + 2], P[2]);
+            C[x] = v + s[x];
+        }
+    } else {
+        for (int x = 0; x < 3; ++x) C[x] = P[x];
+    }
+    float e;
+    if (cam.image) {
+        if (!(C[2] > 0.f)) return acc;      // behind the camera, in its plane, or NaN: no energy, no gradient
+        const float nu = C[0] / C[2], nv = C[1] / C[2];
+        const float du = Y[0] - cam.cx, dv = Y[1] - cam.cy;
+        const float yu = du / cam.fx, yv = dv / cam.fy;
+        const float eu = nu - yu, ev = nv - yv;
+        float pu, pv;
+        const float ru = pndf_fk_robust(eu, cam.rho, &pu);
+        const float rv = pndf_fk_robust(ev, cam.rho, &pv);
+        const float rs = ru + rv;
+        e = w * rs;
+        const float tu = pu / C[2], tv = pv / C[2];
+        const float un = pu * nu, vn = pv * nv;
+        const float sn = un + vn;
+        const float tz = -(sn / C[2]);
+        adj[0] = w * tu;
+        adj[1] = w * tv;
+        adj[2] = w * tz;
+    } else {
+        float res[3];
+        for (int x = 0; x < 3; ++x) res[x] = C[x] - Y[x];
+        const float ss = pndf_fk_dot3(res[0], res[0], res[1], res[1], res[2], res[2]);
+        e = w * ss;
+        for (int x = 0; x < 3; ++x) adj[x] = w * res[x];
+    }
+    if (has_root)
+        for (int x = 0; x < 3; ++x) {
+            as[x] = as[x] + adj[x];
+            for (int y = 0; y < 3; ++y) {
+                const float m = adj[x] * P[y];
+                AR[3 * x + y] = AR[3 * x + y] + m;
+            }
+        }
+    for (int x = 0; x < 3; ++x) {
+        const float wr = has_root ? pndf_fk_dot3(Rc[x], adj[0], Rc[3 + x], adj[1], Rc[6 + x], adj[2]) : adj[x];      // R_c^T a
+        aa[x * ld] = aa[x * ld] + wr;
+        for (int y = 0; y < 3; ++y) {
+            const float m = wr * o[y];
+            Ma[(3 * x + y) * ld] = Ma[(3 * x + y) * ld] + m;
+        }
+    }
+    return acc + e;
+}
+
+// The whole term of one pose under the camera: pndf_fk_energy_grad's arguments, Y [K][3] or [K][2], and root [7] = (c, s), read only when
+// has_root (else groot is not written).  Leaves d E / d Q_j in the rows pndf_fk_grad_row(nj, j), d E / d c in groot [0..3] and d E / d s in groot [4..6],
+// and returns E.  Without a root and without cam.image it computes pndf_fk_energy_grad's bits.
+PNDF_HD float pndf_fk_camera_energy_grad(const float* q, int nj, const int* parent, const float* rest, int K, const int32_t* kp_joint,
+                                         const float* kp_offset, const float* Y, const float* conf, bool has_root,
+                                         const float* root, const PndfFkCamera& cam, float* groot, float* W, int64_t ld) {
+#pragma clang fp contract(off)
+    for (int j = 0; j < nj; ++j) pndf_fk_joint(q + 4 * j, parent[j], rest + 3 * j, W, ld, nj, j);
+    float ch[4] = {0.f, 0.f, 0.f, 0.f}, Rc[9], s[3] = {0.f, 0.f, 0.f}, n = 0.f;
+    float as[3] = {0.f, 0.f, 0.f}, AR[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < 9; ++i) Rc[i] = 0.f;
+    if (has_root) {
+        float c[4];
+        for (int i = 0; i < 4; ++i) c[i] = root[i];
+        for (int x = 0; x < 3; ++x) s[x] = root[4 + x];
+        n = pndf_fk_unit(c, ch);
+        pndf_fk_rot(ch, Rc);
+    }
+    const int dims = cam.image ? 2 : 3;
+    float acc = 0.f;
+    for (int k = 0; k < K; ++k) {
+        const float w = conf ? conf[k] : 1.0f;
+        if (w > 0.f)
+            acc = pndf_fk_camera_keypoint(kp_joint[k], kp_offset + 3 * k, Y + dims * k, w, acc, cam, has_root, Rc, s, as, AR, W, ld, nj);
+    }
+    for (int j = nj - 1; j >= 0; --j) pndf_fk_joint_rev(q + 4 * j, parent[j], rest + 3 * j, W, ld, nj, j);
+    if (has_root) {
+        pndf_fk_quat_adj(AR, ch, n, groot);
+        for (int x = 0; x < 3; ++x) groot[4 + x] = as[x];
+    }
+    return 0.5f * acc;
+}
+
+// The root's own step: root [7] at the step's input, groot of pndf_fk_camera_energy_grad -> out [7].  A pose that rests under tol keeps
+// its root; s <- s - nu_trans * dE/ds when nu_trans > 0, c <- pndf_fk_unit(c - nu_rot * dE/dc) when nu_rot > 0; a part whose weight is
+// zero keeps its bits.
+PNDF_HD void pndf_fk_root_step(const float* root, const float* groot, float nu_rot, float nu_trans, float dist, float tol, float* out) {
+#pragma clang fp contract(off)
+    for (int i = 0; i < 7; ++i) out[i] = root[i];
+    if (tol > 0.f && dist < tol) return;
+    if (nu_rot > 0.f) {
+        float u[4];
+        for (int i = 0; i < 4; ++i) {
+            const float t = nu_rot * groot[i];
+            u[i] = root[i] - t;
+        }
+        (void)pndf_fk_unit(u, out);
+    }
+    if (nu_trans > 0.f)
+        for (int x = 0; x < 3; ++x) {
+            const float t = nu_trans * groot[4 + x];
+            out[4 + x] = root[4 + x] - t;
+        }
 }

@@ -2,8 +2,8 @@
 // pndf_project_ex_cpu (pndf_cpu.cpp): the two refuse the same structs with the same text.  And of pndf_project_options2, the options with
 // a joint mask, which pndf_skel_project (pndf_skeleton.hip) and pndf_project_ex_cpu take besides, and of pndf_project_options3, the
 // options with tracks (pose interpolation inside the step), and of pndf_project_options4, the options with an observation (motion
-// denoising inside the step), and of pndf_project_options5, the options with 3D keypoints (keypoint fitting inside the step), which the
-// same two take.
+// denoising inside the step), and of pndf_project_options5, the options with 3D keypoints (keypoint fitting inside the step), and of
+// pndf_project_options6, the options with a camera and a root (image fitting inside the step), which the same two take.
 #pragma once
 #include <math.h>
 
@@ -179,6 +179,7 @@ struct PndfKeypoints {
     const float* named_target = nullptr;
     const float* named_conf = nullptr;
     int32_t named_K = 0;
+    int32_t dims = 3;                     // floats per target: 2 with the PNDF_KP_IMAGE of a pndf_project_options6
     bool any() const { return target != nullptr; }
 };
 
@@ -255,12 +256,107 @@ inline const char* pndf_check_project_options5(const pndf_project_options* opt, 
 inline const char* pndf_check_keypoints_apart(const PndfKeypoints& kp, const float* q_out, int64_t B, int nj) {
     if (B <= 0 || !q_out) return nullptr;
     const uintptr_t o0 = (uintptr_t)q_out, o1 = (uintptr_t)(q_out + B * nj * 4);
-    if (kp.named_target && (uintptr_t)kp.named_target < o1 && o0 < (uintptr_t)(kp.named_target + B * kp.named_K * 3))
+    if (kp.named_target && (uintptr_t)kp.named_target < o1 && o0 < (uintptr_t)(kp.named_target + B * kp.named_K * kp.dims))
         return "pndf_project_options5.kp_target must not overlap q_out: every step reads the targets";
     if (kp.named_conf && (uintptr_t)kp.named_conf < o1 && o0 < (uintptr_t)(kp.named_conf + B * kp.named_K))
         return "pndf_project_options5.kp_conf must not overlap q_out: every step reads the confidences";
     if (kp.energy && (uintptr_t)kp.energy < o1 && o0 < (uintptr_t)(kp.energy + B))
         return "pndf_project_options5.kp_energy must not overlap q_out";
+    return nullptr;
+}
+
+// The camera and the root of a pndf_project_options6, validated: without a keypoint term (kp_target NULL or nu == 0) there is no energy
+// for the root to descend, `root` stays null and nothing of it is read or written, whatever its weights; `named_root` is what the struct
+// names either way (pndf_check_root_apart refuses its overlap with q_out as the header says)
+struct PndfCameraTerm {
+    float* root = nullptr;      // null: identity, C_k = P_k without arithmetic
+    float* named_root = nullptr;
+    float fx = 1.f, fy = 1.f, cx = 0.f, cy = 0.f, rho = 0.f;
+    float nu_rot = 0.f, nu_trans = 0.f;
+    bool image = false;
+    bool moves() const { return root && (nu_rot > 0.f || nu_trans > 0.f); }
+    // whether a call needs the camera form of the fitting step at all: without either it is the call of the 128-byte struct
+    bool any() const { return root || image; }
+};
+
+// The checker of the same two entry points for all six structs: a pndf_project_options6 brings the camera and the root of a fit to 2D
+// keypoints besides.  Returns nullptr and fills `out`, `observed`, `tracks`, `data`, `kp` and `cam`, or the reason the struct is refused.
+// That root does not overlap the other arrays is the caller's to check (pndf_check_root_apart).
+inline const char* pndf_check_project_options6(const pndf_project_options* opt, int64_t B, int nj, pndf_project_options& out,
+                                               const uint32_t*& observed, PndfTracks& tracks, PndfData& data, PndfKeypoints& kp,
+                                               PndfCameraTerm& cam) {
+    cam = PndfCameraTerm();
+    if (!opt || opt->struct_size != sizeof(pndf_project_options6)) {
+        const char* why = pndf_check_project_options5(opt, B, nj, out, observed, tracks, data, kp);
+        if (why && opt && opt->struct_size != sizeof(pndf_project_options) && opt->struct_size != sizeof(pndf_project_options2) &&
+            opt->struct_size != sizeof(pndf_project_options3) && opt->struct_size != sizeof(pndf_project_options4) &&
+            opt->struct_size != sizeof(pndf_project_options5))
+            return "pndf_project_options.struct_size is none of sizeof(pndf_project_options), sizeof(pndf_project_options2), "
+                   "sizeof(pndf_project_options3), sizeof(pndf_project_options4), sizeof(pndf_project_options5) and "
+                   "sizeof(pndf_project_options6): fill the struct with pndf_default_project_options";
+        return why;
+    }
+    const pndf_project_options6* o6 = (const pndf_project_options6*)opt;
+    pndf_project_options5 base5 = o6->base5;
+    base5.base4.base3.base2.base.struct_size = (uint32_t)sizeof(pndf_project_options5);
+    if (const char* why = pndf_check_project_options5(&base5.base4.base3.base2.base, B, nj, out, observed, tracks, data, kp)) return why;
+    const uint32_t* mask = observed;
+    const PndfTracks tr = tracks;
+    const PndfData da = data;
+    const PndfKeypoints k5 = kp;
+    observed = nullptr;      // (set again below: a refusal leaves nothing behind)
+    tracks = PndfTracks();
+    data = PndfData();
+    kp = PndfKeypoints();
+    if (o6->kp_flags & ~(uint32_t)PNDF_KP_IMAGE) return "pndf_project_options6.kp_flags has a bit other than PNDF_KP_IMAGE";
+    const bool image = (o6->kp_flags & PNDF_KP_IMAGE) != 0;
+    if (!isfinite(o6->rho) || !(o6->rho >= 0.f)) return "pndf_project_options6.rho must be finite and zero or positive";
+    if (!isfinite(o6->nu_rot) || !(o6->nu_rot >= 0.f)) return "pndf_project_options6.nu_rot must be finite and zero or positive";
+    if (!isfinite(o6->nu_trans) || !(o6->nu_trans >= 0.f)) return "pndf_project_options6.nu_trans must be finite and zero or positive";
+    if (o6->rho != 0.f && !image) return "pndf_project_options6.rho must be 0 without PNDF_KP_IMAGE: it is the robustifier of the image residual";
+    if (image) {
+        if (!isfinite(o6->fx) || !(o6->fx > 0.f)) return "pndf_project_options6.fx must be finite and positive with PNDF_KP_IMAGE";
+        if (!isfinite(o6->fy) || !(o6->fy > 0.f)) return "pndf_project_options6.fy must be finite and positive with PNDF_KP_IMAGE";
+        if (!isfinite(o6->cx)) return "pndf_project_options6.cx must be finite with PNDF_KP_IMAGE";
+        if (!isfinite(o6->cy)) return "pndf_project_options6.cy must be finite with PNDF_KP_IMAGE";
+    }
+    if (!o6->root && (o6->nu_rot > 0.f || o6->nu_trans > 0.f))
+        return "pndf_project_options6.root must not be NULL when nu_rot or nu_trans is positive";
+    if ((uintptr_t)o6->root & 3) return "pndf_project_options6.root must be 4-byte aligned";
+    observed = mask;
+    tracks = tr;
+    data = da;
+    kp = k5;
+    cam.named_root = o6->root;
+    cam.nu_rot = o6->nu_rot;
+    cam.nu_trans = o6->nu_trans;
+    if (image) kp.dims = 2;
+    if (kp.any()) {
+        cam.root = o6->root;
+        cam.image = image;
+        cam.rho = o6->rho;
+        if (image) { cam.fx = o6->fx; cam.fy = o6->fy; cam.cx = o6->cx; cam.cy = o6->cy; }
+    }
+    return nullptr;
+}
+
+// What the entry point adds to that checker, knowing B and the poses: root [B,7] is read by every step, so it may not share memory with
+// q_out [B,J,4]; and it is written by every step when a root weight is positive, so then it may not share memory with anything the
+// steps read or the call writes: q_in, anchor, conf, kp_target, kp_conf, kp_energy.  nullptr, or the reason.  The keypoint arrays are
+// compared as the struct names them, the observation as it is read (none with mu == 0).
+inline const char* pndf_check_root_apart(const PndfCameraTerm& cam, const PndfData& data, const PndfKeypoints& kp, const float* q_in,
+                                         const float* q_out, int64_t B, int nj) {
+    if (B <= 0 || !cam.named_root) return nullptr;
+    const uintptr_t r0 = (uintptr_t)cam.named_root, r1 = (uintptr_t)(cam.named_root + B * 7);
+    auto meets = [&](const float* p, int64_t floats) { return p && (uintptr_t)p < r1 && r0 < (uintptr_t)(p + floats); };
+    if (meets(q_out, B * nj * 4)) return "pndf_project_options6.root must not overlap q_out: every step reads the root";
+    if (!(cam.nu_rot > 0.f || cam.nu_trans > 0.f)) return nullptr;
+    if (meets(q_in, B * nj * 4)) return "pndf_project_options6.root must not overlap q_in when nu_rot or nu_trans is positive: every step writes the root";
+    if (meets(data.anchor, B * nj * 4)) return "pndf_project_options6.root must not overlap pndf_project_options4.anchor when nu_rot or nu_trans is positive";
+    if (meets(data.conf, (int64_t)B * nj)) return "pndf_project_options6.root must not overlap pndf_project_options4.conf when nu_rot or nu_trans is positive";
+    if (meets(kp.named_target, B * kp.named_K * kp.dims)) return "pndf_project_options6.root must not overlap kp_target when nu_rot or nu_trans is positive";
+    if (meets(kp.named_conf, (int64_t)B * kp.named_K)) return "pndf_project_options6.root must not overlap kp_conf when nu_rot or nu_trans is positive";
+    if (meets(kp.energy, B)) return "pndf_project_options6.root must not overlap kp_energy when nu_rot or nu_trans is positive";
     return nullptr;
 }
 

@@ -26,7 +26,9 @@
 //                              3D keypoints of a pndf_project_options5 (keypoint fitting) its fourth instantiation
 //                              pndf_skel_enc_rev_fit_kernel: in front of the steps of the joints the forward kinematics of the
 //                              lane's pose, the keypoint residuals and the reverse of pndf_fk.h in workspace rows [24 J][ld], then
-//                              pndf_fit_quat -- the denoising step with nu * dE/dQ_j in front of its finish
+//                              pndf_fit_quat -- the denoising step with nu * dE/dQ_j in front of its finish; with the camera or the
+//                              root of a pndf_project_options6 (image fitting) its fifth instantiation
+//                              pndf_skel_enc_rev_image_kernel: pndf_fk.h's camera term in place of the 3D term and the root's own step
 //   pndf_skel_fill_kernel      the fill of a track from its two end frames, once per chunk in front of the steps
 // 2 + 2 L launches per evaluation.  No float atomics, no communication between workgroups, every column of a GEMM summed in the
 // same order wherever it sits: the same inputs give the same bits and a pose's result does not depend on its batch.
@@ -107,6 +109,14 @@ struct SkFitArgs : SkDenoiseArgs {
     float rest[3 * MAXJ];                      // the rest offsets of the joints
 };
 
+// SkFitArgs with the camera and the root of a pndf_project_options6 (SK_PROJECT), which pndf_skel_enc_rev_image_kernel alone takes, derived
+// for the same reason.  The intrinsics and the flag are values of the argument struct: wave-uniform scalar loads.
+struct SkImageArgs : SkFitArgs {
+    float* root;              // the chunk's roots [n][7] (c, s), or null (identity)
+    PndfFkCamera cam;         // fx, fy, cx, cy, rho, image
+    float nu_rot, nu_trans;   // the weights of the root's own step; both 0: the root is not written
+};
+
 // bone j forward on column c: the parent's features are read back from act0 (a per-thread feature array indexed by a run-time
 // parent would live in scratch memory)
 template <int FIN>
@@ -182,11 +192,14 @@ extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_fwd_kernel(SkArg
 // free end frames, with tracks (e.frames >= 2) or without (e.frames == 0): pndf_denoise_quat of pndf_interp.h in place of the step.
 // SK_REV_FIT is the instantiation of a pndf_project_options5 with a keypoint term: everything SK_REV_DENOISE does, and pndf_fk.h's
 // energy and gradient of the lane's pose at the step's input iterate -- all of it before the first store to `out`, which may be `q`.
-enum { SK_REV_PLAIN = 0, SK_REV_TRACKS = 1, SK_REV_DENOISE = 2, SK_REV_FIT = 3 };
+// SK_REV_IMAGE is the instantiation of a pndf_project_options6 with a root or PNDF_KP_IMAGE: SK_REV_FIT with pndf_fk.h's camera term in
+// place of the 3D term, and the root's own step -- a lane reads its root row before the term and writes it after the joints.
+enum { SK_REV_PLAIN = 0, SK_REV_TRACKS = 1, SK_REV_DENOISE = 2, SK_REV_FIT = 3, SK_REV_IMAGE = 4 };
 template <int KIND, class Args>
 __device__ __forceinline__ void skel_enc_rev(const Args& e) {
     constexpr bool TRACKS = KIND == SK_REV_TRACKS;
-    constexpr bool FIT = KIND == SK_REV_FIT;
+    constexpr bool IMAGE = KIND == SK_REV_IMAGE;
+    constexpr bool FIT = KIND == SK_REV_FIT || IMAGE;
     constexpr bool DENOISE = KIND == SK_REV_DENOISE || FIT;
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= e.n) return;
@@ -225,7 +238,14 @@ __device__ __forceinline__ void skel_enc_rev(const Args& e) {
         }
     }
     float energy = 0.f;      // FIT: E of the pose; d E / d Q_j is left in the rows pndf_fk_grad_row of e.fk
-    if constexpr (FIT)
+    float root[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, groot[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // IMAGE: the lane's root at the step's input and d E / d (c, s)
+    if constexpr (IMAGE) {
+        if (e.root)
+#pragma unroll
+            for (int i = 0; i < 7; ++i) root[i] = e.root[c * 7 + i];
+        energy = pndf_fk_camera_energy_grad(q, e.nj, e.parent, e.rest, e.K, e.kpj, e.kpo, e.kp_target + c * (e.K * (e.cam.image ? 2 : 3)),
+                                            e.kp_conf ? e.kp_conf + c * e.K : nullptr, e.root != nullptr, root, e.cam, groot, e.fk + c, e.ld);
+    } else if constexpr (FIT)
         energy = pndf_fk_energy_grad(q, e.nj, e.parent, e.rest, e.K, e.kpj, e.kpo, e.kp_target + c * (e.K * 3),
                                      e.kp_conf ? e.kp_conf + c * e.K : nullptr, e.fk + c, e.ld);
     for (int j = 0; j < e.nj; ++j) {
@@ -287,12 +307,20 @@ __device__ __forceinline__ void skel_enc_rev(const Args& e) {
     if (e.d_out) e.d_out[c] = dist;
     if constexpr (FIT)
         if (e.kp_energy) e.kp_energy[c] = energy;
+    if constexpr (IMAGE)
+        if (e.root && (e.nu_rot > 0.f || e.nu_trans > 0.f)) {
+            float stepped[7];
+            pndf_fk_root_step(root, groot, e.nu_rot, e.nu_trans, dist, e.tol, stepped);
+#pragma unroll
+            for (int i = 0; i < 7; ++i) e.root[c * 7 + i] = stepped[i];
+        }
 }
 
 extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_kernel(SkArgs e) { skel_enc_rev<SK_REV_PLAIN>(e); }
 extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_track_kernel(SkArgs e) { skel_enc_rev<SK_REV_TRACKS>(e); }
 extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_denoise_kernel(SkDenoiseArgs e) { skel_enc_rev<SK_REV_DENOISE>(e); }
 extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_fit_kernel(SkFitArgs e) { skel_enc_rev<SK_REV_FIT>(e); }
+extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_image_kernel(SkImageArgs e) { skel_enc_rev<SK_REV_IMAGE>(e); }
 
 // The fill of a chunk of whole tracks (pndf_project_options3, PNDF_TRACK_SLERP / _NLERP): one lane per joint quaternion.  Of every track
 // only frames 0 (a) and T-1 (b) of `src` are read; frame 0 of `dst` takes the bits of a, frame T-1 b aligned to a, the frames between
@@ -381,7 +409,7 @@ SkLayout sk_layout(const pndf_skel_plan* h, int64_t B) {
 }
 
 // One evaluation of a chunk of n poses at `q`: the 2 + 2 L launches (the forward alone: 1 + L and the copy of the output row)
-void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const SkFitArgs& e, hipStream_t st) {
+void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const SkImageArgs& e, hipStream_t st) {
     const int n = (int)e.n;
     TrunkWeights w{};
     TrunkBuffers b{};
@@ -390,6 +418,7 @@ void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const S
     b.ld = l.nc; b.n = n;
     const SkArgs& plain = e;      // what every kernel but the denoising and the fitting one takes
     const SkDenoiseArgs& denoise = e;
+    const SkFitArgs& fit = e;
     hipLaunchKernelGGL(pndf_skel_enc_fwd_kernel, dim3(blocks(n)), dim3(256), 0, st, plain);
     trunk_forward(SK_GEMM, *h, w, b, st);
     if (e.mode == SK_FORWARD) {
@@ -397,14 +426,15 @@ void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const S
         return;
     }
     trunk_reverse(SK_GEMM, *h, w, b, st);      // grad_out scales the result in the encoder's reverse
-    if (e.mode == SK_PROJECT && e.kp_target) hipLaunchKernelGGL(pndf_skel_enc_rev_fit_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
+    if (e.mode == SK_PROJECT && e.kp_target && (e.root || e.cam.image)) hipLaunchKernelGGL(pndf_skel_enc_rev_image_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
+    else if (e.mode == SK_PROJECT && e.kp_target) hipLaunchKernelGGL(pndf_skel_enc_rev_fit_kernel, dim3(blocks(n)), dim3(256), 0, st, fit);
     else if (e.mode == SK_PROJECT && (e.anchor || e.flags)) hipLaunchKernelGGL(pndf_skel_enc_rev_denoise_kernel, dim3(blocks(n)), dim3(256), 0, st, denoise);
     else if (e.mode == SK_PROJECT && e.frames) hipLaunchKernelGGL(pndf_skel_enc_rev_track_kernel, dim3(blocks(n)), dim3(256), 0, st, plain);
     else hipLaunchKernelGGL(pndf_skel_enc_rev_kernel, dim3(blocks(n)), dim3(256), 0, st, plain);
 }
 
-SkFitArgs sk_args(const pndf_skel_plan* h, const SkLayout& l, float* ws, int mode) {
-    SkFitArgs e;
+SkImageArgs sk_args(const pndf_skel_plan* h, const SkLayout& l, float* ws, int mode) {
+    SkImageArgs e;
     memset(&e, 0, sizeof(e));
     e.wenc = h->d_blob;
     e.X = ws + l.X; e.act0 = ws + l.act0; e.U0 = ws + l.U0; e.Gx = ws + l.Gx; e.dist = ws + l.dist; e.fk = ws + l.FK;
@@ -514,7 +544,7 @@ extern "C" int pndf_skel_forward(pndf_skel_handle h, const float* q, float* d, i
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     float* ws = (float*)workspace;
-    SkFitArgs e = sk_args(h, l, ws, SK_FORWARD);
+    SkImageArgs e = sk_args(h, l, ws, SK_FORWARD);
     for (int64_t c0 = 0; c0 < B; c0 += l.nc) {
         e.n = B - c0 < l.nc ? B - c0 : l.nc;
         e.q = q + c0 * h->nj * BONE;
@@ -537,7 +567,7 @@ extern "C" int pndf_skel_forward_grad(pndf_skel_handle h, const float* q, const 
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     float* ws = (float*)workspace;
-    SkFitArgs e = sk_args(h, l, ws, SK_GRAD);
+    SkImageArgs e = sk_args(h, l, ws, SK_GRAD);
     for (int64_t c0 = 0; c0 < B; c0 += l.nc) {
         e.n = B - c0 < l.nc ? B - c0 : l.nc;
         e.q = q + c0 * h->nj * BONE;
@@ -557,7 +587,8 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
     PndfTracks tracks;             // a pndf_project_options3 the tracks besides: B / frames of them
     PndfData data;                 // a pndf_project_options4 the observation besides (motion denoising): device memory, as the poses
     PndfKeypoints kp;              // a pndf_project_options5 the 3D keypoints besides (keypoint fitting): the arrays per pose in device memory, the small tables in host memory
-    if (const char* why = pndf_check_project_options5(opt, B, h->nj, o, observed, tracks, data, kp)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    PndfCameraTerm cam;            // a pndf_project_options6 the camera and the root besides (image fitting): the roots per pose in device memory
+    if (const char* why = pndf_check_project_options6(opt, B, h->nj, o, observed, tracks, data, kp, cam)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (steps < 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count");
     SkLayout l;
     if (B > 0 && (!q_in || !q_out)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose pointer");
@@ -569,6 +600,7 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
                                               "frames of its input");
     if (const char* why = pndf_check_observation_apart(data, q_out, B, h->nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (const char* why = pndf_check_keypoints_apart(kp, q_out, B, h->nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (const char* why = pndf_check_root_apart(cam, data, kp, q_in, q_out, B, h->nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (const int rc = sk_check(h, B, workspace, workspace_bytes, l); rc != PNDF_OK || B == 0) return rc;
     PndfRange range("pndf_skel_project");
     DeviceGuard guard(h->device);
@@ -583,13 +615,15 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
         return PNDF_OK;
     }
     float* ws = (float*)workspace;
-    SkFitArgs e = sk_args(h, l, ws, SK_PROJECT);
+    SkImageArgs e = sk_args(h, l, ws, SK_PROJECT);
     e.step_size = o.step_size; e.tol = o.tol; e.renorm = (int)o.renorm;
     e.frames = tracks.frames; e.lambda = tracks.lambda;
     e.mu = data.mu; e.flags = data.free_ends ? (uint32_t)PNDF_TRACK_FREE_ENDS : 0u;
     if (kp.any()) {
         e.K = kp.K; e.nu = kp.nu;
         pndf_fill_keypoint_tables(e, kp, h->nj);
+        e.cam.fx = cam.fx; e.cam.fy = cam.fy; e.cam.cx = cam.cx; e.cam.cy = cam.cy; e.cam.rho = cam.rho; e.cam.image = cam.image ? 1 : 0;
+        e.nu_rot = cam.nu_rot; e.nu_trans = cam.nu_trans;
     }
     // with tracks a chunk holds whole tracks, so no track straddles a seam and lane c of a chunk is frame c % T
     const int64_t nc = tracks.frames ? (l.nc / tracks.frames) * tracks.frames : l.nc;
@@ -600,7 +634,8 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
         e.observed = observed ? observed + c0 : nullptr;
         e.anchor = data.anchor ? data.anchor + c0 * nq : nullptr;
         e.conf = data.conf ? data.conf + c0 * h->nj : nullptr;
-        e.kp_target = kp.target ? kp.target + c0 * kp.K * 3 : nullptr;
+        e.kp_target = kp.target ? kp.target + c0 * kp.K * kp.dims : nullptr;
+        e.root = cam.root ? cam.root + c0 * 7 : nullptr;
         e.kp_conf = kp.conf ? kp.conf + c0 * kp.K : nullptr;
         // Without tracks the iterate is in q_out from the second step on: a lane reads its pose before it writes it.  With tracks a
         // step is out of place: the steps alternate between the chunk of q_out and the second pose buffer, the last one writes

@@ -15,7 +15,7 @@ import numpy as np
 # public names stay importable from here.  `torch` comes from there too: abi imports it before the library is loaded (None without it).
 from .abi import (ACT_CODES, DEBUG_EXPERIMENT_WORDS, DEBUG_EXPORTS, EXPERIMENT_WORDS, EXPORTS, INTERP_MODES, METRIC_CODES,  # noqa: F401
                   NOISE_CODES, PRECISION_CODES, RENORM_CODES, Camera, DenoiseWeights, KeypointOpts, OnlineOpts, PndfConfig, PndfError,
-                  ProjectOptions, ProjectOptions2, ProjectOptions3, ProjectOptions4, ProjectOptions5, TRACK_FILLS, TRACK_FREE_ENDS, debug_library_path, experiment_word, load_library, torch)
+                  ProjectOptions, ProjectOptions2, ProjectOptions3, ProjectOptions4, ProjectOptions5, ProjectOptions6, KP_IMAGE, TRACK_FILLS, TRACK_FREE_ENDS, debug_library_path, experiment_word, load_library, torch)
 
 
 def stream_handle(device) -> int:
@@ -162,6 +162,35 @@ def project_options5(lib, observed_ptr, frames, smooth=0.0, fill=None, anchor_pt
     opt.rest, opt.kp_joint, opt.kp_offset = rest_ptr, kp_joint_ptr, kp_offset_ptr
     opt.n_keypoints, opt.nu = int(n_keypoints), float(kp_weight)
     return opt
+
+
+def project_options6(lib, *args, root_ptr=None, root_weights=(0.0, 0.0), camera=None, rho=0.0, image=None, **kw):
+    """pndf_project_options6 (include/posendf_amd.h): `project_options5`'s arguments, and the camera and the root of a fit to 2D keypoints --
+    `root_ptr` [B,7] (quaternion, real part first, then translation; None: identity) in the memory space of the poses, read and, with a
+    positive weight, written by every step; `root_weights` (nu_rot, nu_trans); `camera` (fx, fy, cx, cy); `rho` the robustifier; `image`:
+    whether kp_target is [B,K,2] pixels (PNDF_KP_IMAGE; None: whenever a camera is given).  The values are checked by the library."""
+    opt = ProjectOptions6()
+    opt.base5 = project_options5(lib, *args, **kw)
+    opt.base5.base4.base3.base2.base.struct_size = ctypes.sizeof(opt)
+    opt.root = root_ptr
+    if camera is not None:
+        opt.fx, opt.fy, opt.cx, opt.cy = (float(v) for v in camera)
+    opt.rho = float(rho)
+    opt.nu_rot, opt.nu_trans = (float(v) for v in root_weights)
+    opt.kp_flags = KP_IMAGE if (camera is not None if image is None else image) else 0
+    return opt
+
+
+_IMAGE_KEYS = ("root_ptr", "root_weights", "camera", "rho", "image")
+
+
+def _imaged(kw):
+    """(the camera / root keywords of a `project` call, the rest): only when one of them says something is the 168-byte struct built"""
+    mine = {k: kw[k] for k in _IMAGE_KEYS if k in kw}
+    rest = {k: v for k, v in kw.items() if k not in _IMAGE_KEYS}
+    named = (mine.get("root_ptr") is not None or mine.get("camera") is not None or bool(mine.get("image")) or float(mine.get("rho") or 0.0) != 0.0
+             or any(float(v) != 0.0 for v in (mine.get("root_weights") or ())))
+    return (mine if named else None), rest
 
 
 _KEYPOINT_KEYS = ("kp_target_ptr", "kp_conf_ptr", "kp_energy_ptr", "rest_ptr", "kp_joint_ptr", "kp_offset_ptr", "n_keypoints", "kp_weight")
@@ -527,8 +556,14 @@ class SkeletonEngine(_Handle):
         `conf_ptr` [B,J] in device memory, `data` and `free_ends`: the observation of motion denoising (through a
         pndf_project_options4: `project_options4`), apart from q_out.  `**keypoints`: kp_target_ptr [B,K,3] / kp_conf_ptr [B,K] / kp_energy_ptr
         [B] in device memory, rest_ptr / kp_joint_ptr / kp_offset_ptr in HOST memory, n_keypoints, kp_weight: the 3D keypoints of a fit
-        (through a pndf_project_options5: `project_options5`)"""
-        if _keypointed(keypoints):
+        (through a pndf_project_options5: `project_options5`); root_ptr [B,7] in device memory, root_weights, camera, rho, image: the root and
+        the camera of a fit to 2D keypoints (through a pndf_project_options6: `project_options6`)"""
+        imaged, keypoints = _imaged(keypoints)
+        named = _keypointed(keypoints)      # (refuses an unknown keyword)
+        if imaged is not None:
+            opt = ctypes.byref(project_options6(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends,
+                                                step_size=step_size, renorm=renorm, tol=tol, **keypoints, **imaged))
+        elif named:
             opt = ctypes.byref(project_options5(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends,
                                                 step_size=step_size, renorm=renorm, tol=tol, **keypoints))
         elif _anchored(anchor_ptr, conf_ptr, data, free_ends):
@@ -729,8 +764,17 @@ class CpuEngine(_Handle):
         any joint tree); None: the call without a mask.  `frames` = T >= 2: the poses are B / T tracks (pndf_project_ex_cpu with a
         pndf_project_options3: `project_options3`).  `anchor_ptr` [B,J,4] / `conf_ptr` [B,J] in host memory, `data` and `free_ends`: the
         observation of motion denoising (pndf_project_ex_cpu with a pndf_project_options4: `project_options4`).  `**keypoints`: as
-        SkeletonEngine.project, every pointer in host memory (pndf_project_ex_cpu with a pndf_project_options5: `project_options5`)"""
-        if _keypointed(keypoints):
+        SkeletonEngine.project, every pointer in host memory (pndf_project_ex_cpu with a pndf_project_options5: `project_options5`, or with
+        root_ptr / root_weights / camera / rho / image a pndf_project_options6: `project_options6`)"""
+        imaged, keypoints = _imaged(keypoints)
+        named = _keypointed(keypoints)      # (refuses an unknown keyword)
+        if imaged is not None:
+            opt6 = project_options6(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends,
+                                    step_size=step_size, renorm=renorm, tol=tol, **keypoints, **imaged)
+            self._check(self.lib.pndf_project_ex_cpu(self.handle, q_in_ptr, q_out_ptr, d_ptr, B, int(steps), ctypes.byref(opt6)),
+                        "pndf_project_ex_cpu")
+            return
+        if named:
             opt5 = project_options5(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends,
                                     step_size=step_size, renorm=renorm, tol=tol, **keypoints)
             self._check(self.lib.pndf_project_ex_cpu(self.handle, q_in_ptr, q_out_ptr, d_ptr, B, int(steps), ctypes.byref(opt5)),

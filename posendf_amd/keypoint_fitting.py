@@ -7,6 +7,9 @@ joint tree with its rest offsets is the body model; the detections are 3D points
 Inverse kinematics from one start can end in a local minimum (a finger folded the wrong way), so `KeypointFitting.fit` runs several random
 starts per target and returns, per target, the hypothesis of the lowest `energy + lam * dist`.
 
+With a `camera` the detections are pixels [N,K,2], and with a `root` the tree is placed in the target's frame by a rotation and a
+translation per pose that the steps move as well (pndf_project_options6; DESIGN.md section 2j "Image fitting"): a hand tracker's output.
+
 `python -m posendf_amd.keypoint_fitting` reads an .npz of targets and writes the fitted poses.
 """
 from __future__ import annotations
@@ -16,12 +19,24 @@ import torch
 from .sample_poses import SamplePose
 
 
-def keypoint_energy(pose, targets, parents, rest, conf=None, keypoint_joints=None, keypoint_offsets=None):
-    """1/2 sum_k w_k |P_k(pose) - targets_k|^2 per pose [...], with `forward_kinematics`; a keypoint whose confidence is not positive (zero,
-    negative, NaN) takes no part, whatever its target holds"""
-    from .skeleton import forward_kinematics
-    res = forward_kinematics(pose, parents, rest, keypoint_joints, keypoint_offsets) - targets
-    sq = (res * res).sum(-1)
+def keypoint_energy(pose, targets, parents, rest, conf=None, keypoint_joints=None, keypoint_offsets=None, root=None, camera=None, rho=0.0):
+    """1/2 sum_k w_k |C_k(pose, root) - targets_k|^2 per pose [...], with `forward_kinematics` and `camera_project`; a keypoint whose
+    confidence is not positive (zero, negative, NaN) takes no part, whatever its target holds.  With a `camera` the targets are pixels and
+    the residual e is taken in normalised image coordinates, rho(e) = e^2 or (rho > 0) rho^2 e^2 / (e^2 + rho^2) summed over both axes; a
+    keypoint that is not in front of the camera takes no part"""
+    from .skeleton import camera_project, forward_kinematics
+    C = camera_project(forward_kinematics(pose, parents, rest, keypoint_joints, keypoint_offsets), root)
+    if camera is None:
+        res = C - targets
+        sq = (res * res).sum(-1)
+    else:
+        fx, fy, cx, cy = (float(v) for v in camera)
+        front = C[..., 2] > 0
+        z = torch.where(front, C[..., 2], torch.ones_like(C[..., 2]))
+        e = torch.stack([C[..., 0] / z - (targets[..., 0] - cx) / fx, C[..., 1] / z - (targets[..., 1] - cy) / fy], dim=-1)
+        ee = e * e
+        cost = ee if not rho else float(rho) ** 2 * ee / (ee + float(rho) ** 2)
+        sq = torch.where(front, cost.sum(-1), torch.zeros_like(z))
     if conf is not None:
         on = conf > 0
         sq = torch.where(on, conf * torch.where(on, sq, torch.zeros_like(sq)), torch.zeros_like(sq))
@@ -34,7 +49,7 @@ class KeypointFitting(SamplePose):
 
     @torch.no_grad()
     def fit(self, targets, rest, conf=None, keypoint_joints=None, keypoint_offsets=None, hypotheses=8, iterations=3, steps_per_iter=30, weight=0.02,
-            lam=1.0, seed=None, *, step_size=1.0, renormalize="unit", tol=0.0):
+            lam=1.0, seed=None, *, step_size=1.0, renormalize="unit", tol=0.0, camera=None, root=None, root_weights=(0.0, 0.0), rho=0.0):
         """targets: [N,K,3] detections (one set of K keypoints per target pose); rest / keypoint_joints / keypoint_offsets / conf: as
         `SkeletonPoseNDF.fit_keypoints` (conf [K] or [N,K]).  Every target gets `hypotheses` random starts (unit quaternions, seeded by
         `seed`); `iterations` engine calls of `steps_per_iter` steps each run all N * hypotheses poses at once, iteration `it` with the
@@ -42,22 +57,36 @@ class KeypointFitting(SamplePose):
         lam 1) is UNTUNED: no trained skeleton model exists to tune it on, and the weight is only known to lower the energy of a
         15-joint hand with rest offsets within [-0.75, 0.75]^3 at every step (with offsets within [-1, 1]^3 one start of 48 already
         oscillates: scale it down by the square of the rig's size, `SkeletonPoseNDF.fit_keypoints`).  Returns (pose [N,J,4], energy [N], dist [N], start_energy [N,hypotheses]): per target the
-        hypothesis of the lowest energy + lam * dist, its keypoint energy and distance, and the energies of its random starts."""
+        hypothesis of the lowest energy + lam * dist, its keypoint energy and distance, and the energies of its random starts.
+        `camera` = (fx, fy, cx, cy): targets are [N,K,2] pixels; `root` [7] or [N,7]: the placement of the tree in the target's frame, from
+        which EVERY hypothesis of a target starts; `root_weights` = (nu_rot, nu_trans) let the steps move it; `rho`: the robustifier of the
+        image residual -- all as `SkeletonPoseNDF.fit_keypoints`.  With a camera or a root the result has a fifth entry, the root [N,7] of
+        the chosen hypothesis.  The image term's weights are UNTUNED as well and default to a held root: its residual is in normalised
+        image coordinates, smaller than the 3D term's by the depth of the rig, so useful weights are larger.  Tried on a 15-joint hand with
+        rest offsets within [-0.75, 0.75]^3 about 6 units in front of the camera, pure inverse kinematics, as (weight; nu_rot, nu_trans):
+        (2.0; 0.5, 2.0), (1.0; 0.2, 1.0) and (0.5; 0.1, 0.5) make the energy of 45, 19 and 5 starts of 48 rise at some step; (0.3; 0.05, 0.3)
+        and (0.1; 0.02, 0.1) lower it at every step for every start."""
         net = self.pose_prior
         if not hasattr(net, "fit_keypoints"):
             raise TypeError(f"{type(net).__name__} has no fit_keypoints(): fitting to 3D keypoints is SkeletonPoseNDF's; a PoseNDF fits 2D "
                             "keypoints through posendf_amd.image_fit.ImageFit and its body model")
         J, H = net.num_joints, int(hypotheses)
         y = targets.to(self.device).float()
-        if y.dim() != 3 or y.shape[-1] != 3:
-            raise ValueError(f"targets are [N,K,3], not {tuple(targets.shape)}")
+        D = 3 if camera is None else 2
+        if y.dim() != 3 or y.shape[-1] != D:
+            raise ValueError(f"targets are [N,K,{D}], not {tuple(targets.shape)}")
         N, K = y.shape[0], y.shape[1]
         if H < 1:
             raise ValueError("at least one hypothesis per target")
         gen = torch.Generator().manual_seed(int(seed)) if seed is not None else None
         start = torch.randn((N, H, J, 4), generator=gen)
         start = (start / start.norm(dim=-1, keepdim=True).clamp_min(1e-12)).to(self.device)
-        yy = y[:, None].expand(N, H, K, 3).reshape(N * H, K, 3)
+        yy = y[:, None].expand(N, H, K, D).reshape(N * H, K, D)
+        placed = camera is not None or root is not None
+        rt = None
+        if root is not None:
+            rt = torch.as_tensor(root).to(self.device).float().expand(N, 7)[:, None].expand(N, H, 7).reshape(N * H, 7).contiguous()
+        image = dict(camera=camera, rho=rho, root_weights=tuple(root_weights)) if placed else {}
         c = None
         if conf is not None:
             c = torch.as_tensor(conf).to(self.device).float()
@@ -66,24 +95,33 @@ class KeypointFitting(SamplePose):
         rest_d = torch.as_tensor(rest).to(self.device).float()
         off_d = None if keypoint_offsets is None else torch.as_tensor(keypoint_offsets).to(self.device).float()
 
-        def energy_of(q):
-            return keypoint_energy(q, yy, net.parents, rest_d, c, keypoint_joints, off_d)
+        def energy_of(q, r):
+            return keypoint_energy(q, yy, net.parents, rest_d, c, keypoint_joints, off_d, r, camera, rho)
 
         cur = start.reshape(N * H, J, 4)
-        start_energy = energy_of(cur).reshape(N, H)
+        start_energy = energy_of(cur, rt).reshape(N, H)
         for _ in range(int(iterations)):
             cur = net.fit_keypoints(cur, yy, rest, steps=int(steps_per_iter), weight=weight, conf=c, return_dist=False, step_size=step_size,
-                                    renormalize=renormalize, tol=tol, **tables)
-        energy = energy_of(cur).reshape(N, H)
+                                    renormalize=renormalize, tol=tol, **tables, **image, **(dict(root=rt, return_root=True) if rt is not None else {}))
+            if rt is not None:
+                cur, rt = cur
+        energy = energy_of(cur, rt).reshape(N, H)
         dist = net.project(cur, steps=1)[1].reshape(N, H) if N else energy      # dist_pred at `cur`: evaluated before the update
         best = (energy + float(lam) * dist).argmin(dim=1)
         pick = torch.arange(N, device=best.device)
-        return cur.reshape(N, H, J, 4)[pick, best], energy[pick, best], dist[pick, best], start_energy
+        result = (cur.reshape(N, H, J, 4)[pick, best], energy[pick, best], dist[pick, best], start_energy)
+        if placed:
+            if rt is None:
+                rt = torch.zeros(N * H, 7, device=cur.device)
+                rt[:, 0] = 1.0
+            result += (rt.reshape(N, H, 7)[pick, best],)
+        return result
 
 
 def fit_keypoint_file(posendf, keypoint_file, device="cuda:0", key="keypoints", **kwargs):
-    """The targets of an .npz -- `key` [N,K,3], `rest` [J,3], and, if the file has them, `conf` [K] or [N,K], `keypoint_joints` [K] and
-    `keypoint_offsets` [K,3] -> what KeypointFitting.fit returns for them."""
+    """The targets of an .npz -- `key` [N,K,3], `rest` [J,3], and, if the file has them, `conf` [K] or [N,K], `keypoint_joints` [K],
+    `keypoint_offsets` [K,3], `camera` [4] = (fx, fy, cx, cy) (then `key` is [N,K,2] pixels) and `root` [7] or [N,7] -> what
+    KeypointFitting.fit returns for them."""
     import numpy as np
     with np.load(keypoint_file) as f:
         y = torch.from_numpy(np.ascontiguousarray(f[key], dtype=np.float32))
@@ -95,6 +133,10 @@ def fit_keypoint_file(posendf, keypoint_file, device="cuda:0", key="keypoints", 
             opt["keypoint_joints"] = torch.from_numpy(np.ascontiguousarray(f["keypoint_joints"], dtype=np.int32))
         if "keypoint_offsets" in f.files:
             opt["keypoint_offsets"] = torch.from_numpy(np.ascontiguousarray(f["keypoint_offsets"], dtype=np.float32))
+        if "camera" in f.files:
+            opt["camera"] = tuple(float(v) for v in np.asarray(f["camera"]).reshape(-1))
+        if "root" in f.files:
+            opt["root"] = torch.from_numpy(np.ascontiguousarray(f["root"], dtype=np.float32))
     return KeypointFitting(posendf, body_model=None, device=device).fit(y, rest, **opt, **kwargs)
 
 
@@ -103,14 +145,18 @@ def main(argv=None):
 
     from .config import load_config
     from .skeleton import SkeletonPoseNDF
-    ap = argparse.ArgumentParser(description="Fit poses of any joint tree to 3D keypoints with a SkeletonPoseNDF (schedule untuned).")
+    ap = argparse.ArgumentParser(description="Fit poses of any joint tree to 3D or 2D keypoints with a SkeletonPoseNDF (schedule untuned).")
     ap.add_argument("--config", "-c", required=True, help="path to the config file (configs/amass.yaml's keys, model.StrEnc.parent_mapping the tree)")
     ap.add_argument("--ckpt_path", "-ckpt", required=True, help="checkpoint of the trained model (key model_state_dict)")
-    ap.add_argument("--keypoint_file", "-kf", required=True, help=".npz with keys keypoints [N,K,3], rest [J,3] and optionally conf, keypoint_joints, keypoint_offsets")
+    ap.add_argument("--keypoint_file", "-kf", required=True, help=".npz with keys keypoints [N,K,3], rest [J,3] and optionally conf, keypoint_joints, keypoint_offsets, camera [4] "
+                                                                    "(fx, fy, cx, cy: keypoints are [N,K,2] pixels) and root [7] or [N,7]")
     ap.add_argument("--hypotheses", type=int, default=8)
     ap.add_argument("--iterations", type=int, default=3)
     ap.add_argument("--steps_per_iter", type=int, default=30)
     ap.add_argument("--weight", type=float, default=0.02, help="weight of the keypoint term (nu)")
+    ap.add_argument("--root_weights", type=float, nargs=2, default=(0.0, 0.0), metavar=("NU_ROT", "NU_TRANS"),
+                    help="weights of the root's own step (needs a root in the file); 0 holds that part")
+    ap.add_argument("--rho", type=float, default=0.0, help="robustifier of the image residual (needs a camera in the file); 0 = squared error")
     ap.add_argument("--lam", type=float, default=1.0, help="weight of the distance in the choice between hypotheses")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None, help="write the fitted poses (key pose), their energies (energy) and distances (dist) to this .npz")
@@ -119,13 +165,18 @@ def main(argv=None):
     net = SkeletonPoseNDF(opt)
     net.load_state_dict(torch.load(a.ckpt_path, map_location="cpu")["model_state_dict"])
     net.eval()
-    pose, energy, dist, start = fit_keypoint_file(net, a.keypoint_file, device=opt["train"]["device"], hypotheses=a.hypotheses, iterations=a.iterations,
-                                                  steps_per_iter=a.steps_per_iter, weight=a.weight, lam=a.lam, seed=a.seed)
+    extra = {}
+    if any(a.root_weights):
+        extra["root_weights"] = tuple(a.root_weights)
+    if a.rho:
+        extra["rho"] = a.rho
+    pose, energy, dist, start, *root = fit_keypoint_file(net, a.keypoint_file, device=opt["train"]["device"], hypotheses=a.hypotheses, iterations=a.iterations,
+                                                         steps_per_iter=a.steps_per_iter, weight=a.weight, lam=a.lam, seed=a.seed, **extra)
     if energy.numel():
         print(f"median keypoint energy {float(energy.median()):.5f} (random starts: {float(start.median()):.5f}), mean dist {float(dist.mean()):.4f}")
     if a.out:
         import numpy as np
-        np.savez(a.out, pose=pose.cpu().numpy(), energy=energy.cpu().numpy(), dist=dist.cpu().numpy())
+        np.savez(a.out, pose=pose.cpu().numpy(), energy=energy.cpu().numpy(), dist=dist.cpu().numpy(), **({"root": root[0].cpu().numpy()} if root else {}))
     return pose, energy
 
 

@@ -20,8 +20,9 @@ denoising in quaternion space -- the pose prior, the neighbour coupling with fre
 observation, in a pndf_project_options4 --, which `posendf_amd.pose_denoising.PoseDenoising` drives.  `fit_keypoints(poses, targets,
 rest)` is inverse kinematics under the prior -- 3D detections of keypoints attached to the joints, the tree with its rest offsets as the
 body model, in a pndf_project_options5 --, which `posendf_amd.keypoint_fitting.KeypointFitting` drives; `forward_kinematics` is the
-differentiable torch statement of its kinematics.  The second order stays 21-joint
-(DESIGN.md section 8).
+differentiable torch statement of its kinematics.  With `camera=` the detections are pixels, and with `root=` / `root_weights=` the tree
+has a placement in the target's frame that the steps move (a pndf_project_options6; `camera_project` is the torch statement of both).
+Only the second order stays 21-joint: its C ABI refuses another joint count, and that refusal is pinned.
 """
 from __future__ import annotations
 
@@ -229,7 +230,7 @@ class SkeletonPoseNDF(PoseModel):
     @torch.no_grad()
     def fit_keypoints(self, poses, targets, rest, steps=100, weight=0.02, conf=None, keypoint_joints=None, keypoint_offsets=None, observed=None,
                       frames=None, smooth=0.0, anchor=None, data=0.0, free_ends=False, return_dist=True, return_energy=False, *, step_size=1.0,
-                      renormalize=None, tol=0.0):
+                      renormalize=None, tol=0.0, root=None, root_weights=(0.0, 0.0), camera=None, rho=0.0, return_root=False):
         """Inverse kinematics under the learned prior, for the model's tree: from the start `poses` [B,J,4], `steps` projection steps that
         also descend E = 1/2 sum_k conf_k |P_k(pose) - targets_k|^2 with weight `weight` (nu), P_k = `forward_kinematics` of the pose.
         `targets` [B,K,3] are 3D detections in the roots' frame; `rest` [J,3] the offsets of the joints from their parents in the rest
@@ -248,8 +249,19 @@ class SkeletonPoseNDF(PoseModel):
         `train.device: cpu` model, or one on another GPU than the model's -- raises PndfError, since it would mean a silent copy of a whole
         batch off its device.  The small tables `rest`, `keypoint_joints` and `keypoint_offsets` are host tables of the call and are
         accepted from any device.
+        Image fitting (pndf_project_options6; DESIGN.md section 2j "Image fitting"): `camera` = (fx, fy, cx, cy) makes `targets` [B,K,2] pixel
+        detections of a pinhole camera -- the residual is taken in normalised image coordinates, (C_x / C_z, C_y / C_z) against
+        ((u - cx) / fx, (v - cy) / fy), so the energy and `weight` do not depend on the resolution; a keypoint that is not in front of the
+        camera takes no part in that step; `rho` > 0 replaces the squared residual by rho^2 e^2 / (e^2 + rho^2).  `root` [B,7] or [7] places
+        the tree in the target's frame, C_k = R(c) P_k + s with c = root[:4] (a quaternion, real part first, normalised) and s = root[4:];
+        it is per pose, lives where `poses` may live and is cloned.  `root_weights` = (nu_rot, nu_trans) let every step move it along the
+        energy's gradient (0: that part is held); the root is not a joint, so neither `observed` nor held end frames hold it.  Without a
+        keypoint term (`weight` 0) the root is left as it is.  The default weights are zero; those tried are listed in
+        `posendf_amd.keypoint_fitting`.  `camera_project` is the torch statement of C_k and of the pixels.  The defaults are the call
+        without a camera, bit for bit.
         Returns poses [B,J,4], then dist [B,1] of the last iteration (`return_dist`), then the energy [B] of the last iteration, evaluated
-        before its update (`return_energy`); step options: as `project`."""
+        before its update (`return_energy`), then the final root [B,7] (`return_root`; the identity placement when none was given);
+        step options: as `project`."""
         J = self.num_joints
         home = torch.device(self.device)
 
@@ -280,10 +292,21 @@ class SkeletonPoseNDF(PoseModel):
         kpj = None if kpj is None else kpj.to(torch.int32).contiguous()
         rest_t = table(rest, (J, 3), torch.float32, "rest")
         kpo = None if keypoint_offsets is None else table(keypoint_offsets, (K, 3), torch.float32, "keypoint_offsets")
+        D = 3 if camera is None else 2
+        if camera is not None and len(tuple(camera)) != 4:
+            raise PndfError("camera is (fx, fy, cx, cy)")
         y = on_device(targets, "targets").float()
-        if y.dim() < 2 or tuple(y.shape[-2:]) != (K, 3) or y.numel() != B * K * 3:
-            raise PndfError(f"targets are [{B},{K},3], not {list(y.shape)}")
-        y = y.reshape(B, K, 3).contiguous()
+        if y.dim() < 2 or tuple(y.shape[-2:]) != (K, D) or y.numel() != B * K * D:
+            raise PndfError(f"targets are [{B},{K},{D}], not {list(y.shape)}")
+        y = y.reshape(B, K, D).contiguous()
+        place = None
+        if root is not None:
+            place = on_device(root, "root")
+            if not place.is_floating_point() or tuple(place.shape) not in ((7,), (B, 7)):
+                raise PndfError(f"root is a floating-point tensor [7] or [{B},7], not {place.dtype} {list(place.shape)}")
+            place = place.float().expand(B, 7).contiguous().clone()
+        if len(tuple(root_weights)) != 2:
+            raise PndfError("root_weights is (nu_rot, nu_trans)")
         c = None
         if conf is not None:
             c = on_device(conf, "conf")
@@ -313,8 +336,13 @@ class SkeletonPoseNDF(PoseModel):
                         kp_target_ptr=y.data_ptr() if B else None, kp_conf_ptr=None if c is None or B == 0 else c.data_ptr(),
                         kp_energy_ptr=energy.data_ptr() if B else None, rest_ptr=rest_t.data_ptr(),
                         kp_joint_ptr=None if kpj is None else kpj.data_ptr(), kp_offset_ptr=None if kpo is None else kpo.data_ptr(),
-                        n_keypoints=K, kp_weight=weight, **tracks)
-        result = (out,) + ((d.view(-1, 1),) if return_dist else ()) + ((energy,) if return_energy else ())
+                        n_keypoints=K, kp_weight=weight, **tracks,
+                        **(dict(root_ptr=place.data_ptr() if place is not None and B else None, root_weights=tuple(root_weights) if B else (0.0, 0.0), camera=camera, rho=rho)
+                           if place is not None or camera is not None or rho or any(root_weights) else {}))
+        if return_root and place is None:
+            place = torch.zeros(B, 7, device=dev, dtype=torch.float32)
+            place[:, 0] = 1.0
+        result = (out,) + ((d.view(-1, 1),) if return_dist else ()) + ((energy,) if return_energy else ()) + ((place,) if return_root else ())
         return result if len(result) > 1 else out
 
 
@@ -353,3 +381,29 @@ def forward_kinematics(pose, parents, rest, keypoint_joints=None, keypoint_offse
             p.append(p[pa] + (G[pa] @ rest[j].unsqueeze(-1)).squeeze(-1))
     out = [p[a] if offsets is None else p[a] + (G[a] @ offsets[k].unsqueeze(-1)).squeeze(-1) for k, a in enumerate(joints)]
     return torch.stack(out, dim=-2)
+
+
+def camera_project(points, root=None, camera=None):
+    """Keypoints in the target's frame, and their pixels, differentiable: points [...,K,3] (`forward_kinematics`, the roots' frame) ->
+    C_k = R(c) P_k + s with `root` [...,7] or [7] = (c: a quaternion, real part first, normalised c / max(|c|, 1e-12); s: a translation),
+    or the points themselves when root is None; with `camera` = (fx, fy, cx, cy) the pixels (fx C_x / C_z + cx, fy C_y / C_z + cy)
+    [...,K,2] of a pinhole camera that looks along +z.  This is the statement `SkeletonPoseNDF.fit_keypoints(camera=..., root=...)`
+    (csrc/pndf_fk.h) descends; use it to make targets and to read residuals."""
+    if points.shape[-1] != 3:
+        raise PndfError(f"points are [...,K,3], not {tuple(points.shape)}")
+    C = points
+    if root is not None:
+        root = torch.as_tensor(root, dtype=points.dtype, device=points.device)
+        if root.shape[-1] != 7:
+            raise PndfError(f"root is [...,7], not {tuple(root.shape)}")
+        c, s = root[..., :4], root[..., 4:]
+        r = c / c.pow(2).sum(-1, keepdim=True).sqrt().clamp_min(1e-12)
+        w, x, y, z = r.unbind(-1)
+        R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                         2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                         2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], dim=-1).reshape(r.shape[:-1] + (3, 3))
+        C = (R.unsqueeze(-3) @ points.unsqueeze(-1)).squeeze(-1) + s.unsqueeze(-2)
+    if camera is None:
+        return C
+    fx, fy, cx, cy = (float(v) for v in camera)
+    return torch.stack([fx * C[..., 0] / C[..., 2] + cx, fy * C[..., 1] / C[..., 2] + cy], dim=-1)
