@@ -274,7 +274,7 @@ typedef struct {
  *   o.base5.base4.base3.base2.base.struct_size = sizeof o;  o.root = placement;  o.fx = o.fy = 500.f;  o.cx = 320.f;  o.cy = 240.f;
  *   o.nu_rot = 0.02f;  o.nu_trans = 0.02f;  o.kp_flags = PNDF_KP_IMAGE;
  * Exactly the two entry points that take a pndf_project_options5 take it.  PNDF_ERR_BAD_ARG with a text that names the field, before
- * anything is launched or written: a struct_size that is none of the six sizes, an unknown bit in kp_flags, a rho, nu_rot or nu_trans
+ * anything is launched or written: a struct_size that is none of the seven sizes, an unknown bit in kp_flags, a rho, nu_rot or nu_trans
  * that is negative or not finite, rho != 0 without PNDF_KP_IMAGE, with PNDF_KP_IMAGE an fx or fy that is not finite or <= 0 or a cx or
  * cy that is not finite, root == NULL with a positive root weight, a misaligned root, root overlapping q_out, with a positive root
  * weight root overlapping q_in, anchor, conf, kp_target, kp_conf or kp_energy; and what is refused in `base5`. */
@@ -287,6 +287,43 @@ typedef struct {
     float    nu_rot, nu_trans;    /* weights of the root's own step, finite and >= 0; 0 = that part of the root is held */
     uint32_t kp_flags;            /* 0 or PNDF_KP_IMAGE */
 } pndf_project_options6;          /* 168 bytes */
+
+/* The options with bone lengths: the fit of pndf_project_options6 on a joint tree whose segment lengths are unknowns too, one set per
+ * track.  S = J + K scales: sigma_j (j < J) scales joint j's rest offset, t'_j = sigma_j t_j per component, sigma_{J+k} keypoint k's local
+ * offset, o'_k = sigma_{J+k} o_k; forward kinematics, keypoints, camera and root are those of the 168-byte struct on t' and o'.  With
+ * base3.frames = T >= 2 and without PNDF_LEN_PER_POSE there are G = B / T groups: track g owns row g of bone_scale and all its frames read
+ * it; otherwise G = B, one row per pose (PNDF_LEN_PER_POSE with frames == 0 is accepted and says what holds there anyway).  For one step,
+ * every operation rounded to fp32 on its own in the order written:
+ *   per frame  h_j = <ap_j, v_j> for a joint (ap_j the complete adjoint of p_j: its own keypoints and all its children; v_j = G_pi(j) t_j
+ *              on the unscaled t_j, t_j itself for a root), h_{J+k} = <dE/dP_k, G_a(k) o_k> for a keypoint (exactly 0 for one that is
+ *              skipped); the term ap_c t_c^T of a parent's M uses the scaled t'_c.  Held end frames and masked joints contribute: like
+ *              the root, the scales are not joints.
+ *   per group  H_i = the sum of h_i over the group's n frames: the partial of every block of 64 consecutive frames accumulated in frame
+ *              order from 0.0f (the last block may be shorter), the partials then added in block order from 0.0f
+ *   the step   w_i = nu_len * len_rate_i; if w_i > 0 is false the scale keeps its bits; if tol > 0 and every frame of the group rests
+ *              (d < tol) the group keeps its bits; else m = H_i / (float)n, pr = kappa * (sigma_i - 1.0f), gsum = m + pr,
+ *              v = sigma_i - w_i * gsum, and with a clamp sigma_i <- v < len_min ? len_min : (v > len_max ? len_max : v) (a NaN stays).
+ * The update is Jacobi: every frame of a step reads the scales as the step before left them; kp_energy is E at the step's input scales.
+ * bone_scale [G,S] is DEVICE memory for pndf_skel_project and HOST memory for pndf_project_ex_cpu, READ by every step and WRITTEN by every
+ * step when nu_len > 0.  With bone_scale == NULL (then nu_len must be 0), or with every scale 1.0f and nu_len == 0, the call is the one with
+ * the 168-byte struct bit for bit and bone_scale is not written; with kp_target == NULL or nu == 0 it is the one with the 72-byte struct
+ * and bone_scale is neither read nor written; steps == 0 leaves it untouched.  Exactly the two entry points that take a
+ * pndf_project_options6 take it.  PNDF_ERR_BAD_ARG with a text that names the field, before anything is launched or written: a
+ * struct_size that is none of the seven sizes, reserved3 != 0, an unknown bit in len_flags, a nu_len or kappa that is negative or not
+ * finite, a clamp that is not 0 < len_min <= len_max finite (both 0: none), a len_rate entry that is negative or not finite, bone_scale
+ * == NULL with nu_len > 0, a misaligned bone_scale or len_rate, bone_scale overlapping q_out, q_in, root, anchor, conf, kp_target, kp_conf
+ * or kp_energy; and what is refused in `base6`. */
+enum { PNDF_LEN_PER_POSE = 1 };
+typedef struct {
+    pndf_project_options6 base6;   /* base6.base5.base4.base3.base2.base.struct_size = sizeof(pndf_project_options7) */
+    float*       bone_scale;       /* [G,S], S = J + K; DEVICE (pndf_skel_project) / HOST (pndf_project_ex_cpu); NULL: all ones, no fitting */
+    const float* len_rate;         /* [S], HOST memory, finite and >= 0; NULL: ones.  0 = that scale keeps its bits */
+    float        nu_len;           /* weight of the scales' own step, finite and >= 0 */
+    float        kappa;            /* weight of the prior 1/2 kappa (sigma - 1)^2, finite and >= 0 */
+    float        len_min, len_max; /* both 0: no clamp; else 0 < len_min <= len_max, finite */
+    uint32_t     len_flags;        /* 0 or PNDF_LEN_PER_POSE */
+    uint32_t     reserved3;        /* 0 */
+} pndf_project_options7;           /* 208 bytes */
 
 /* pndf_project with step options.  opt == NULL means the defaults, and with the defaults the call is pndf_project bit for
  * bit.  PNDF_ERR_BAD_ARG (text in pndf_last_error; nothing is launched or written) for a struct_size other than
@@ -315,9 +352,10 @@ int pndf_project_cpu(pndf_cpu_handle h, const float* q_in, float* q_out, float* 
 int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps,
                         const pndf_project_options* opt);      /* pndf_project_ex: same semantics, same validation; also takes a
                                                                   pndf_project_options2, a pndf_project_options3, a
-                                                                  pndf_project_options4, a pndf_project_options5 or a
-                                                                  pndf_project_options6, `observed` / `anchor` / `conf` /
-                                                                  `kp_*` / `root` in HOST memory */
+                                                                  pndf_project_options4, a pndf_project_options5, a
+                                                                  pndf_project_options6 or a pndf_project_options7,
+                                                                  `observed` / `anchor` / `conf` / `kp_*` / `root` /
+                                                                  `bone_scale` in HOST memory */
 const char* pndf_cpu_last_error(pndf_cpu_handle h);   /* h may be NULL: last error of a failed pndf_cpu_create */
 
 /* Host-only weight packer (what pndf_load_weights uploads); needs no device.  Output sizes in floats come

@@ -58,6 +58,13 @@
  * the root's step sit in the step of the gradient's last kernel (its fifth instantiation), so an image step costs no launch more and the
  * workspace is what it was; the 128-byte struct's keypoints, mask, tracks and observation come along unchanged.
  *
+ * Bone lengths -- the segment lengths of the subject as unknowns of the same fit, one set per track -- are the same two entry points with a
+ * pndf_project_options7 (posendf_amd.h): bone_scale [G,S] in device memory (S = J + K scales of the rest offsets and of the keypoints'
+ * local offsets; one row per track of base3.frames frames, or per pose), read and -- with nu_len positive -- written by every step.  The
+ * scaled tree and the per-frame gradient of the scales sit in the gradient's last kernel (its sixth instantiation,
+ * pndf_skel_enc_rev_len_kernel), which leaves them in S workspace rows; pndf_skel_len_step_kernel then sums them over the frames of every
+ * group in a fixed order and steps the scales: one launch more per step and chunk than an image step, and only when nu_len > 0.
+ *
  * Still 21-joint: the second order (posendf_amd_second_order.h) only -- pndf_so_create refuses another joint count and
  * pndf_second_order_cpu a handle of another tree, and that is pinned.  2D keypoints with a camera run for any joint tree through
  * pndf_skel_project (above); pndf_keypoint_terms_grad and pndf_lbs_* are the SMPL body model's (vertices, shape, lens of ImageFit).
@@ -88,7 +95,8 @@ int pndf_skel_load_weights(pndf_skel_handle h, const float* const* tensors, cons
  * bounded (the batch is processed in chunks of at most 16,384 poses); 0 for B == 0; PNDF_ERR_BAD_ARG for a null handle or a negative B.
  * It includes, for every caller, one pose buffer [chunk][4 J] for the out-of-place steps of a projection with tracks (at most
  * 16,384 x 128 x 4 B = 8 MB) and the rows [24 J][chunk] of the forward kinematics and its adjoints of a pndf_project_options5 (at most
- * 16,384 x 768 x 4 B = 48 MB). */
+ * 16,384 x 768 x 4 B = 48 MB), followed by the 96 rows [96][chunk] of the per-frame gradient of the scales of a pndf_project_options7 (at
+ * most 16,384 x 96 x 4 B = 6 MB). */
 int64_t pndf_skel_workspace_bytes(pndf_skel_handle h, int64_t B);
 
 /* forward(pose, train=False)['dist_pred']: q [B,J,4] -> d [B]. */
@@ -112,7 +120,9 @@ int pndf_skel_forward_grad(pndf_skel_handle h, const float* q, const float* grad
  * q_out, both may be q_in) add the data term of weight mu * conf to every free joint, and PNDF_TRACK_FREE_ENDS frees the end frames of
  * every track; without tracks such a call may still run in place.  Or to a pndf_project_options5: besides, kp_target [B,K,3], kp_conf [B,K]
  * and kp_energy [B] (DEVICE memory; none may overlap q_out) and the HOST tables rest, kp_joint and kp_offset (read during the call) add the
- * keypoint term of weight nu to every free joint; kp_energy is E of the last iteration, evaluated before its update, as d_last is. */
+ * keypoint term of weight nu to every free joint; kp_energy is E of the last iteration, evaluated before its update, as d_last is.  Or to
+ * a pndf_project_options6 (root [B,7]: DEVICE memory) or a pndf_project_options7 (bone_scale [G,S]: DEVICE memory, len_rate [S]: HOST
+ * memory, read during the call): seven sizes in all, every other one is refused. */
 int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps,
                       const pndf_project_options* opt, void* workspace, int64_t workspace_bytes, void* stream);
 

@@ -25,6 +25,7 @@ RENORM_CODES = {"none": 0, "unit": 1, "unit_flip": 2}      # PNDF_RENORM_*
 INTERP_MODES = {"slerp": 0, "nlerp": 1}                    # PNDF_INTERP_*
 TRACK_FILLS = {"given": 0, "slerp": 1, "nlerp": 2}         # PNDF_TRACK_*
 KP_IMAGE = 1                                               # PNDF_KP_IMAGE (pndf_project_options6.kp_flags)
+LEN_PER_POSE = 1                                           # PNDF_LEN_PER_POSE (pndf_project_options7.len_flags)
 TRACK_FREE_ENDS = 1                                        # PNDF_TRACK_FREE_ENDS (pndf_project_options4.flags)
 NOISE_CODES = {"uniform": 0, "symmetric": 1}               # PNDF_ONLINE_*
 METRIC_CODES = {"geo": 0, "euc": 1}
@@ -79,6 +80,17 @@ class ProjectOptions6(ctypes.Structure):
                 ("rho", c_float), ("nu_rot", c_float), ("nu_trans", c_float), ("kp_flags", ctypes.c_uint32)]
 
 
+class ProjectOptions7(ctypes.Structure):
+    """pndf_project_options7: the options with a mask, tracks, an observation, keypoints and a camera (`base6`, with
+    base6.base5.base4.base3.base2.base.struct_size = 208) and bone lengths -- `bone_scale` [G,S] (S = J + K scales of the rest offsets and
+    of the keypoints' offsets; one row per track, or per pose with LEN_PER_POSE or without tracks; None: all ones) in the memory space of
+    the poses, read and (with nu_len > 0) written by every step; `len_rate` [S] in HOST memory (None: ones; 0 holds that scale);
+    `nu_len` the weight of the scales' step, `kappa` of the prior 1/2 kappa (sigma - 1)^2; `len_min`, `len_max` a clamp (both 0: none);
+    `len_flags` 0 or LEN_PER_POSE; taken by the two entry points that take a ProjectOptions6"""
+    _fields_ = [("base6", ProjectOptions6), ("bone_scale", c_void_p), ("len_rate", c_void_p), ("nu_len", c_float), ("kappa", c_float),
+                ("len_min", c_float), ("len_max", c_float), ("len_flags", ctypes.c_uint32), ("reserved3", ctypes.c_uint32)]
+
+
 class DenoiseWeights(ctypes.Structure):
     """pndf_denoise_weights: the loss weights of one outer iteration, evaluated"""
     _fields_ = [("prior_coef", c_float), ("prior_power", c_int32), ("temp_coef", c_float), ("data_coef", c_float)]
@@ -108,7 +120,7 @@ class PndfError(RuntimeError):
 _H = c_void_p                          # every handle type, and every `void* stream`
 _P = c_void_p                          # any other address: tensor data (an int from data_ptr(), or None), a callback, an out value
 _TENSORS = [POINTER(c_void_p), POINTER(c_int64), c_int]      # tensors, numel, n_tensors (host pointers in state-dict order)
-_OPT2 = c_void_p                       # `const pndf_project_options*` where it may point to a ProjectOptions, a ProjectOptions2 .. a ProjectOptions6 (byref of any)
+_OPT2 = c_void_p                       # `const pndf_project_options*` where it may point to a ProjectOptions, a ProjectOptions2 .. a ProjectOptions7 (byref of any)
 # ---- the header set, stated once: header of include/ -> {name: (restype, argtypes)} in the header's order; the headers in the order
 # they were added.  A new header is a file in include/, a table here and its declaration count in tests/test_cabi.py.
 DEBUG_HEADER = "posendf_amd_debug.h"      # the one header that lives in libposendf_amd_debug.so; every other one in the product library

@@ -6,7 +6,8 @@
 // count and the parent table from the handle's config (any joint tree of include/posendf_amd_skeleton.h, pndf_net_plan.h); on the
 // SMPL table they compute what they did with the table fixed.  pndf_complete_cpu, pndf_interpolate_cpu and the second order stay 21-joint;
 // pndf_project_ex_cpu completes, interpolates, denoises and fits 3D or 2D keypoints for any joint tree (pndf_project_options2 /
-// pndf_project_options3 / pndf_project_options4 / pndf_project_options5 / pndf_project_options6).
+// pndf_project_options3 / pndf_project_options4 / pndf_project_options5 / pndf_project_options6), with the bone lengths as unknowns too
+// (pndf_project_options7).
 //
 // Layout: poses are processed in blocks of PB = 32; inside a block every activation tensor is [feature][pose] so that the
 // inner loop of a layer runs over the 32 poses of the block (contiguous floats: one or two AVX-512 / four AVX2 registers)
@@ -411,11 +412,27 @@ struct KeypointTables {
 // a local array of rows (ld = 1).  gk [nj][4] = d E / d Q; returns E.  With the camera or the root of a pndf_project_options6 (`cam`) the
 // term is pndf_fk_camera_energy_grad, and the pose's root row takes its own step here (pndf_fk_root_step; `dist` and `tol` say whether
 // the pose rests): it is read before the term and nothing else of the step reads it.
+// With the scales of a pndf_project_options7 (`len`) the term is pndf_fk_len_energy_grad on the row of the pose's group, and `hs` [S] takes
+// d E / d sigma of this frame; the scales step in len_step_cpu once every frame of the step has read them.
 static float keypoint_grad_cpu(const PndfKeypoints& kp, const KeypointTables& tb, const int* parent, int nj, const float* q, int64_t pose,
-                               float* gk, const PndfCameraTerm& cam = PndfCameraTerm(), float dist = 0.f, float tol = 0.f) {
-    float W[PNDF_FK_ROWS * MAXJ];
+                               float* gk, const PndfCameraTerm& cam = PndfCameraTerm(), float dist = 0.f, float tol = 0.f,
+                               const PndfLengths& len = PndfLengths(), float* hs = nullptr) {
+    float W[PNDF_FK_ROWS * MAXJ + PNDF_MAX_SCALES];
     float E;
-    if (cam.any()) {
+    if (len.any()) {
+        const PndfFkCamera fc{cam.fx, cam.fy, cam.cx, cam.cy, cam.rho, cam.image ? 1 : 0};
+        float root[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, groot[7], stepped[7];
+        float* rt = cam.root ? cam.root + pose * 7 : nullptr;
+        if (rt) memcpy(root, rt, sizeof(root));
+        E = pndf_fk_len_energy_grad(q, nj, parent, tb.rest, kp.K, tb.kpj, tb.kpo, kp.target + pose * kp.K * kp.dims,
+                                    kp.conf ? kp.conf + pose * kp.K : nullptr, rt != nullptr, root, fc,
+                                    len.scale + (pose / len.group) * len.S, groot, W, 1);
+        if (cam.moves()) {
+            pndf_fk_root_step(root, groot, cam.nu_rot, cam.nu_trans, dist, tol, stepped);
+            memcpy(rt, stepped, sizeof(stepped));
+        }
+        for (int i = 0; i < len.S; ++i) hs[i] = W[pndf_fk_len_row(nj, i)];
+    } else if (cam.any()) {
         const PndfFkCamera fc{cam.fx, cam.fy, cam.cx, cam.cy, cam.rho, cam.image ? 1 : 0};
         float root[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, groot[7], stepped[7];
         float* rt = cam.root ? cam.root + pose * 7 : nullptr;
@@ -433,6 +450,21 @@ static float keypoint_grad_cpu(const PndfKeypoints& kp, const KeypointTables& tb
     for (int j = 0; j < nj; ++j)
         for (int c = 0; c < 4; ++c) gk[4 * j + c] = W[pndf_fk_grad_row(nj, j) + c];
     return E;
+}
+
+// The step of the scales of group g (pndf_fk.h: pndf_fk_len_group_sum, pndf_fk_len_step): hs [n][S] the rows its n frames left, dd [n]
+// their distances
+static void len_step_cpu(const PndfLengths& len, int64_t g, const float* hs, const float* dd, float tol) {
+    const int64_t n = len.group;
+    bool rests = tol > 0.f;
+    for (int64_t f = 0; f < n && rests; ++f) rests = dd[f] < tol;
+    float* row = len.scale + g * len.S;
+    for (int i = 0; i < len.S; ++i) {
+        const float w = len.nu_len * len.rate[i];
+        const float H = pndf_fk_len_group_sum(hs + i, len.S, n);
+        const float v = pndf_fk_len_step(row[i], H, n, w, len.kappa, len.len_min, len.len_max, rests);
+        if (w > 0.f && !rests) row[i] = v;
+    }
 }
 
 // `gk` (null: none): d E / d Q of the pose's keypoint term of a pndf_project_options5, `nu` its weight: then the step is pndf_fk.h's
@@ -462,19 +494,21 @@ static void project_step_cpu(float* q, const float* dq, float d, const pndf_proj
 // block; `observed` null = no joint held; `data`: the observation of a pndf_project_options4 (none: the step without a data term).
 static int project_loop_cpu(pndf_cpu_handle h, const float* q_in, const uint32_t* observed, float* q_out, float* d_last, int64_t B,
                             int steps, const pndf_project_options& o, const PndfData& data = PndfData(),
-                            const PndfKeypoints& kp = PndfKeypoints(), const PndfCameraTerm& cam = PndfCameraTerm()) {
+                            const PndfKeypoints& kp = PndfKeypoints(), const PndfCameraTerm& cam = PndfCameraTerm(),
+                            const PndfLengths& len = PndfLengths()) {
     const int NQ = h->nq();
     KeypointTables tb;
     if (kp.any()) pndf_fill_keypoint_tables(tb, kp, h->net.nj);
     return guarded(h, [&] {
     parallel_blocks(B, [&](int64_t p0, int nb, Scratch& S) {
-        float qb[PB * 4 * MAXJ], dqb[PB * 4 * MAXJ], dd[PB], ee[PB], gk[4 * MAXJ];
+        float qb[PB * 4 * MAXJ], dqb[PB * 4 * MAXJ], dd[PB], ee[PB], gk[4 * MAXJ], hs[PNDF_MAX_SCALES];
         memcpy(qb, q_in + p0 * NQ, sizeof(float) * nb * NQ);
         for (int p = 0; p < nb; ++p) dd[p] = ee[p] = 0.f;
         for (int s = 0; s < steps; ++s) {
             forward_grad_block(*h, qb, nb, nullptr, dd, dqb, true, S);
             for (int p = 0; p < nb; ++p) {
-                if (kp.any()) ee[p] = keypoint_grad_cpu(kp, tb, h->net.parent, h->net.nj, qb + p * NQ, p0 + p, gk, cam, dd[p], o.tol);
+                if (kp.any()) ee[p] = keypoint_grad_cpu(kp, tb, h->net.parent, h->net.nj, qb + p * NQ, p0 + p, gk, cam, dd[p], o.tol, len, hs);
+                if (len.moves()) len_step_cpu(len, p0 + p, hs, dd + p, o.tol);      // (without tracks every pose is its own group)
                 project_step_cpu(qb + p * NQ, dqb + p * NQ, dd[p], o, observed ? observed[p0 + p] : 0u, h->net.nj,
                                  data.anchor ? data.anchor + (p0 + p) * NQ : nullptr, data.conf ? data.conf + (p0 + p) * h->net.nj : nullptr, data.mu,
                                  kp.any() ? gk : nullptr, kp.nu);
@@ -513,7 +547,7 @@ extern "C" int pndf_complete_cpu(pndf_cpu_handle h, const float* q_in, const uin
 static int track_loop_cpu(pndf_cpu_handle h, const float* a, int64_t a_stride, const float* b, int64_t b_stride, int fill,
                           const uint32_t* observed, float* track_out, float* d_last, int64_t P, int32_t T, int steps, float lambda,
                           const pndf_project_options& o, const PndfData& data = PndfData(), const PndfKeypoints& kp = PndfKeypoints(),
-                          const PndfCameraTerm& cam = PndfCameraTerm()) {
+                          const PndfCameraTerm& cam = PndfCameraTerm(), const PndfLengths& len = PndfLengths()) {
     const int nj = h->net.nj;
     const int64_t nq = h->nq(), B = P * T;
     int rc = PNDF_OK;
@@ -521,6 +555,7 @@ static int track_loop_cpu(pndf_cpu_handle h, const float* a, int64_t a_stride, c
     if (kp.any()) pndf_fill_keypoint_tables(tb, kp, nj);
     const int grc = guarded(h, [&] {
         std::vector<float> other((size_t)(B * nq)), dq(steps ? (size_t)(B * nq) : 0), dd((size_t)B, 0.f), ee((size_t)B, 0.f);
+        std::vector<float> hs(len.any() ? (size_t)(B * len.S) : 0);      // d E / d sigma of every frame of the step
         float* cur = (steps & 1) ? other.data() : track_out;      // `steps` swaps later the track is in track_out
         float* nxt = (steps & 1) ? track_out : other.data();
         if (fill == PNDF_TRACK_GIVEN) memcpy(cur, a, sizeof(float) * (size_t)(B * nq));
@@ -544,7 +579,8 @@ static int track_loop_cpu(pndf_cpu_handle h, const float* a, int64_t a_stride, c
                 const int nbr = (k > 0 ? 1 : 0) | (k < T - 1 ? 2 : 0);
                 const uint32_t held = (nbr != 3 && !data.free_ends) ? ~0u : (observed ? observed[f] : 0u);
                 float gk[4 * MAXJ];
-                if (kp.any()) ee[f] = keypoint_grad_cpu(kp, tb, h->net.parent, nj, cur + f * nq, f, gk, cam, dd[f], o.tol);
+                if (kp.any()) ee[f] = keypoint_grad_cpu(kp, tb, h->net.parent, nj, cur + f * nq, f, gk, cam, dd[f], o.tol, len,
+                                                        len.any() ? hs.data() + f * len.S : nullptr);
                 for (int j = 0; j < nj; ++j) {
                     const int64_t i = (f * nj + j) * 4;
                     float u[4];
@@ -559,6 +595,9 @@ static int track_loop_cpu(pndf_cpu_handle h, const float* a, int64_t a_stride, c
                         memcpy(nxt + i, u, sizeof(float) * 4);
                 }
             }
+            if (len.moves())      // Jacobi: every frame of this step has read the scales as the step before left them
+                for (int64_t g = 0; g < B / len.group; ++g)
+                    len_step_cpu(len, g, hs.data() + g * len.group * len.S, dd.data() + g * len.group, o.tol);
             std::swap(cur, nxt);
         }
         if (rc == PNDF_OK && d_last) memcpy(d_last, dd.data(), sizeof(float) * B);
@@ -576,7 +615,8 @@ extern "C" int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* 
     PndfData data;                 // a pndf_project_options4 the observation besides (host memory): motion denoising for any joint tree
     PndfKeypoints kp;              // a pndf_project_options5 the 3D keypoints besides (host memory): keypoint fitting for any joint tree
     PndfCameraTerm cam;            // a pndf_project_options6 the camera and the root besides (host memory): image fitting for any joint tree
-    if (const char* why = pndf_check_project_options6(opt, B, h->net.nj, o, observed, tracks, data, kp, cam)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    PndfLengths len;               // a pndf_project_options7 the bone lengths besides (host memory): one row of scales per track or per pose
+    if (const char* why = pndf_check_project_options7(opt, B, h->net.nj, o, observed, tracks, data, kp, cam, len)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (!tracks.frames && !observed && !data.any() && !kp.any() && !kp.energy && pndf_project_options_plain(o))
         return pndf_project_cpu(h, q_in, q_out, d_last, B, steps);
     if (int rc = check(h, q_in, B)) return rc;
@@ -584,14 +624,15 @@ extern "C" int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* 
     if (const char* why = pndf_check_observation_apart(data, q_out, B, h->net.nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (const char* why = pndf_check_keypoints_apart(kp, q_out, B, h->net.nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (const char* why = pndf_check_root_apart(cam, data, kp, q_in, q_out, B, h->net.nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
-    if (!tracks.frames) return project_loop_cpu(h, q_in, observed, q_out, d_last, B, steps, o, data, kp, cam);
+    if (const char* why = pndf_check_lengths_apart(len, cam, data, kp, q_in, q_out, B, h->net.nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (!tracks.frames) return project_loop_cpu(h, q_in, observed, q_out, d_last, B, steps, o, data, kp, cam, len);
     if (B == 0) return PNDF_OK;
     const int64_t nq = h->nq(), T = tracks.frames;
     if ((uintptr_t)q_in < (uintptr_t)(q_out + B * nq) && (uintptr_t)q_out < (uintptr_t)(q_in + B * nq))
         return pndf_fail(h, PNDF_ERR_BAD_ARG, "q_out must not overlap q_in when pndf_project_options3.frames > 0: a step reads the neighbour "
                                               "frames of its input");
     return track_loop_cpu(h, q_in, T * nq, q_in + (T - 1) * nq, T * nq, tracks.fill, observed, q_out, d_last, B / T, (int32_t)T, steps,
-                          tracks.lambda, o, data, kp, cam);
+                          tracks.lambda, o, data, kp, cam, len);
 }
 
 // Host twin of pndf_interpolate (include/posendf_amd_interpolation.h): track_loop_cpu on the 21-joint table; with lambda == 0 this is

@@ -359,3 +359,178 @@ PNDF_HD void pndf_fk_root_step(const float* root, const float* groot, float nu_r
             out[4 + x] = root[4 + x] - t;
         }
 }
+
+// ---- Bone lengths of a pndf_project_options7 (DESIGN.md section 2j "Bone lengths"): the camera term above on a tree whose rest offsets and
+// keypoint offsets are scaled, t'_j = sigma_j t_j and o'_k = sigma_{J+k} o_k per component, and the gradient of E with respect to the
+// S = J + K scales.  Stated once beside the other terms, whose functions above stay as they are (their bits are pinned); with every scale
+// 1.0f the products are exact and the term computes pndf_fk_camera_energy_grad's bits.
+//   joint j:     h_j = <ap_j, v_j> with ap_j complete (its own keypoints and all its children: joint j is about to be reversed) and
+//                v_j = G_pi(j) t_j, three pndf_fk_dot3 rows on the unscaled t_j; v_j = t_j for a root; the product a pndf_fk_dot3
+//   keypoint k:  h_{J+k} = <dE/dP_k, G_a(k) o_k>, dE/dP_k what goes into ap; a skipped keypoint gives exactly 0
+// h is left in the S rows pndf_fk_len_row(nj, i) of W, behind the 24 J rows of the tree.  The scales are read through a pointer with a
+// run-time index (on the device: the group's row in global memory, not a per-thread array); t' and o' are three values at a time.
+PNDF_HD int pndf_fk_len_row(int nj, int i) { return PNDF_FK_ROWS * nj + i; }
+constexpr int PNDF_FK_LEN_BLOCK = 64;      // frames per partial sum of pndf_fk_len_group_sum
+
+// pndf_fk_camera_keypoint on the scaled offset sg * o; *h = <R_c^T a, G_a o> (0 when the keypoint is skipped behind the camera)
+PNDF_HD float pndf_fk_len_keypoint(int a, const float* o, float sg, const float* Y, float w, float acc, const PndfFkCamera& cam, bool has_root,
+                                   const float* Rc, const float* s, float* as, float* AR, float* W, int64_t ld, int nj, float* h) {
+#pragma clang fp contract(off)
+    const float* Ga = W + (int64_t)pndf_fk_G(nj, a) * ld;
+    const float* pa = W + (int64_t)pndf_fk_p(nj, a) * ld;
+    float* Ma = W + (int64_t)pndf_fk_M(nj, a) * ld;
+    float* aa = W + (int64_t)pndf_fk_ap(nj, a) * ld;
+    float os[3], P[3], C[3], adj[3], vu[3];
+    *h = 0.f;
+    for (int x = 0; x < 3; ++x) os[x] = sg * o[x];
+    for (int x = 0; x < 3; ++x) {
+        const float v = pndf_fk_dot3(Ga[(3 * x) * ld], os[0], Ga[(3 * x + 1) * ld], os[1], Ga[(3 * x + 2) * ld], os[2]);
+        P[x] = pa[x * ld] + v;
+        vu[x] = pndf_fk_dot3(Ga[(3 * x) * ld], o[0], Ga[(3 * x + 1) * ld], o[1], Ga[(3 * x + 2) * ld], o[2]);
+    }
+    if (has_root) {
+        for (int x = 0; x < 3; ++x) {
+            const float v = pndf_fk_dot3(Rc[3 * x], P[0], Rc[3 * x + 1], P[1], Rc[3 * x + 2], P[2]);
+            C[x] = v + s[x];
+        }
+    } else {
+        for (int x = 0; x < 3; ++x) C[x] = P[x];
+    }
+    float e;
+    if (cam.image) {
+        if (!(C[2] > 0.f)) return acc;      // behind the camera, in its plane, or NaN: no energy, no gradient
+        const float nu = C[0] / C[2], nv = C[1] / C[2];
+        const float du = Y[0] - cam.cx, dv = Y[1] - cam.cy;
+        const float yu = du / cam.fx, yv = dv / cam.fy;
+        const float eu = nu - yu, ev = nv - yv;
+        float pu, pv;
+        const float ru = pndf_fk_robust(eu, cam.rho, &pu);
+        const float rv = pndf_fk_robust(ev, cam.rho, &pv);
+        const float rs = ru + rv;
+        e = w * rs;
+        const float tu = pu / C[2], tv = pv / C[2];
+        const float un = pu * nu, vn = pv * nv;
+        const float sn = un + vn;
+        const float tz = -(sn / C[2]);
+        adj[0] = w * tu;
+        adj[1] = w * tv;
+        adj[2] = w * tz;
+    } else {
+        float res[3];
+        for (int x = 0; x < 3; ++x) res[x] = C[x] - Y[x];
+        const float ss = pndf_fk_dot3(res[0], res[0], res[1], res[1], res[2], res[2]);
+        e = w * ss;
+        for (int x = 0; x < 3; ++x) adj[x] = w * res[x];
+    }
+    if (has_root)
+        for (int x = 0; x < 3; ++x) {
+            as[x] = as[x] + adj[x];
+            for (int y = 0; y < 3; ++y) {
+                const float m = adj[x] * P[y];
+                AR[3 * x + y] = AR[3 * x + y] + m;
+            }
+        }
+    float wr[3];
+    for (int x = 0; x < 3; ++x) {
+        wr[x] = has_root ? pndf_fk_dot3(Rc[x], adj[0], Rc[3 + x], adj[1], Rc[6 + x], adj[2]) : adj[x];      // R_c^T a
+        aa[x * ld] = aa[x * ld] + wr[x];
+        for (int y = 0; y < 3; ++y) {
+            const float m = wr[x] * os[y];
+            Ma[(3 * x + y) * ld] = Ma[(3 * x + y) * ld] + m;
+        }
+    }
+    *h = pndf_fk_dot3(wr[0], vu[0], wr[1], vu[1], wr[2], vu[2]);
+    return acc + e;
+}
+
+// The whole term of one pose on the scaled tree: pndf_fk_camera_energy_grad's arguments and sigma [nj + K], the scales of the pose's
+// group at the step's input.  Leaves d E / d Q_j in the rows pndf_fk_grad_row(nj, j), d E / d sigma_i in the rows pndf_fk_len_row(nj, i),
+// d E / d (c, s) in groot, and returns E.
+PNDF_HD float pndf_fk_len_energy_grad(const float* q, int nj, const int* parent, const float* rest, int K, const int32_t* kp_joint,
+                                      const float* kp_offset, const float* Y, const float* conf, bool has_root, const float* root,
+                                      const PndfFkCamera& cam, const float* sigma, float* groot, float* W, int64_t ld) {
+#pragma clang fp contract(off)
+    for (int j = 0; j < nj; ++j) {
+        const float sg = sigma[j];
+        float ts[3];
+        for (int x = 0; x < 3; ++x) ts[x] = sg * rest[3 * j + x];
+        pndf_fk_joint(q + 4 * j, parent[j], ts, W, ld, nj, j);
+    }
+    float ch[4] = {0.f, 0.f, 0.f, 0.f}, Rc[9], s[3] = {0.f, 0.f, 0.f}, n = 0.f;
+    float as[3] = {0.f, 0.f, 0.f}, AR[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < 9; ++i) Rc[i] = 0.f;
+    if (has_root) {
+        float c[4];
+        for (int i = 0; i < 4; ++i) c[i] = root[i];
+        for (int x = 0; x < 3; ++x) s[x] = root[4 + x];
+        n = pndf_fk_unit(c, ch);
+        pndf_fk_rot(ch, Rc);
+    }
+    const int dims = cam.image ? 2 : 3;
+    float acc = 0.f;
+    for (int k = 0; k < K; ++k) {
+        const float w = conf ? conf[k] : 1.0f;
+        float h = 0.f;
+        if (w > 0.f)
+            acc = pndf_fk_len_keypoint(kp_joint[k], kp_offset + 3 * k, sigma[nj + k], Y + dims * k, w, acc, cam, has_root, Rc, s, as, AR, W, ld,
+                                       nj, &h);
+        W[(int64_t)pndf_fk_len_row(nj, nj + k) * ld] = h;
+    }
+    for (int j = nj - 1; j >= 0; --j) {
+        const float* t = rest + 3 * j;
+        const float* aj = W + (int64_t)pndf_fk_ap(nj, j) * ld;
+        const float sg = sigma[j];
+        float ts[3], v[3];
+        for (int x = 0; x < 3; ++x) ts[x] = sg * t[x];
+        if (parent[j] < 0) {
+            for (int x = 0; x < 3; ++x) v[x] = t[x];
+        } else {
+            const float* Gp = W + (int64_t)pndf_fk_G(nj, parent[j]) * ld;
+            for (int x = 0; x < 3; ++x) v[x] = pndf_fk_dot3(Gp[(3 * x) * ld], t[0], Gp[(3 * x + 1) * ld], t[1], Gp[(3 * x + 2) * ld], t[2]);
+        }
+        W[(int64_t)pndf_fk_len_row(nj, j) * ld] = pndf_fk_dot3(aj[0], v[0], aj[ld], v[1], aj[2 * ld], v[2]);
+        pndf_fk_joint_rev(q + 4 * j, parent[j], ts, W, ld, nj, j);
+    }
+    if (has_root) {
+        pndf_fk_quat_adj(AR, ch, n, groot);
+        for (int x = 0; x < 3; ++x) groot[4 + x] = as[x];
+    }
+    return 0.5f * acc;
+}
+
+// The sum of a group: h of frame f at h[f * stride], n >= 1 frames.  The partial of every block of PNDF_FK_LEN_BLOCK consecutive frames is
+// accumulated in frame order from 0.0f (the last block may be shorter); the partials are added in block order from 0.0f.
+PNDF_HD float pndf_fk_len_add(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+PNDF_HD float pndf_fk_len_block_sum(const float* h, int64_t stride, int64_t f0, int64_t f1) {
+#pragma clang fp contract(off)
+    float acc = 0.f;
+    for (int64_t f = f0; f < f1; ++f) acc = acc + h[f * stride];
+    return acc;
+}
+PNDF_HD float pndf_fk_len_group_sum(const float* h, int64_t stride, int64_t n) {
+#pragma clang fp contract(off)
+    float total = 0.f;
+    for (int64_t f0 = 0; f0 < n; f0 += PNDF_FK_LEN_BLOCK) {
+        const int64_t f1 = f0 + PNDF_FK_LEN_BLOCK < n ? f0 + PNDF_FK_LEN_BLOCK : n;
+        total = pndf_fk_len_add(total, pndf_fk_len_block_sum(h, stride, f0, f1));
+    }
+    return total;
+}
+
+// The step of one scale: sigma at the step's input, H the group's sum over its n frames, w = nu_len * rate (formed by the caller, rounded
+// once), `rests`: tol > 0 and every frame of the group rests.  Returns the new scale; where it returns sigma the scale keeps its bits.
+PNDF_HD float pndf_fk_len_step(float sigma, float H, int64_t n, float w, float kappa, float len_min, float len_max, bool rests) {
+#pragma clang fp contract(off)
+    if (!(w > 0.f) || rests) return sigma;
+    const float m = H / (float)n;
+    const float d1 = sigma - 1.0f;
+    const float pr = kappa * d1;
+    const float gsum = m + pr;
+    const float t = w * gsum;
+    const float v = sigma - t;
+    if (len_min == 0.f && len_max == 0.f) return v;
+    return v < len_min ? len_min : (v > len_max ? len_max : v);
+}

@@ -360,6 +360,112 @@ inline const char* pndf_check_root_apart(const PndfCameraTerm& cam, const PndfDa
     return nullptr;
 }
 
+// The bone lengths of a pndf_project_options7, validated: without a keypoint term (kp_target NULL or nu == 0) `scale` stays null and
+// nothing of it is read or written; `named_scale` is what the struct names either way (pndf_check_lengths_apart refuses its overlaps).
+// S = J + K scales per row; G rows: one per track of `frames` frames, or one per pose.
+constexpr int32_t PNDF_MAX_SCALES = 96;      // 32 joints + 64 keypoints
+struct PndfLengths {
+    float* scale = nullptr;
+    float* named_scale = nullptr;
+    int64_t named_floats = 0;      // G * S of the struct as it names its keypoints
+    int32_t S = 0;
+    int32_t group = 1;             // frames per group: T, or 1
+    float nu_len = 0.f, kappa = 0.f, len_min = 0.f, len_max = 0.f;
+    float rate[PNDF_MAX_SCALES];
+    bool any() const { return scale != nullptr; }
+    bool moves() const { return scale && nu_len > 0.f; }
+};
+
+// The checker of the same two entry points for all seven structs: a pndf_project_options7 brings the bone lengths besides.  Returns nullptr
+// and fills `out`, `observed`, `tracks`, `data`, `kp`, `cam` and `len`, or the reason the struct is refused.  That bone_scale does not
+// overlap the other arrays is the caller's to check (pndf_check_lengths_apart).  PNDF_LEN_PER_POSE with frames == 0 is accepted: there
+// every pose is its own group anyway.
+inline const char* pndf_check_project_options7(const pndf_project_options* opt, int64_t B, int nj, pndf_project_options& out,
+                                               const uint32_t*& observed, PndfTracks& tracks, PndfData& data, PndfKeypoints& kp,
+                                               PndfCameraTerm& cam, PndfLengths& len) {
+    len = PndfLengths();
+    for (int i = 0; i < PNDF_MAX_SCALES; ++i) len.rate[i] = 1.0f;
+    if (!opt || opt->struct_size != sizeof(pndf_project_options7)) {
+        const char* why = pndf_check_project_options6(opt, B, nj, out, observed, tracks, data, kp, cam);
+        if (why && opt && opt->struct_size != sizeof(pndf_project_options) && opt->struct_size != sizeof(pndf_project_options2) &&
+            opt->struct_size != sizeof(pndf_project_options3) && opt->struct_size != sizeof(pndf_project_options4) &&
+            opt->struct_size != sizeof(pndf_project_options5) && opt->struct_size != sizeof(pndf_project_options6))
+            return "pndf_project_options.struct_size is none of sizeof(pndf_project_options), sizeof(pndf_project_options2), "
+                   "sizeof(pndf_project_options3), sizeof(pndf_project_options4), sizeof(pndf_project_options5), "
+                   "sizeof(pndf_project_options6) and sizeof(pndf_project_options7): fill the struct with pndf_default_project_options";
+        return why;
+    }
+    const pndf_project_options7* o7 = (const pndf_project_options7*)opt;
+    pndf_project_options6 base6 = o7->base6;
+    base6.base5.base4.base3.base2.base.struct_size = (uint32_t)sizeof(pndf_project_options6);
+    if (const char* why = pndf_check_project_options6(&base6.base5.base4.base3.base2.base, B, nj, out, observed, tracks, data, kp, cam)) return why;
+    const uint32_t* mask = observed;
+    const PndfTracks tr = tracks;
+    const PndfData da = data;
+    const PndfKeypoints k6 = kp;
+    const PndfCameraTerm c6 = cam;
+    observed = nullptr;      // (set again below: a refusal leaves nothing behind)
+    tracks = PndfTracks();
+    data = PndfData();
+    kp = PndfKeypoints();
+    cam = PndfCameraTerm();
+    if (o7->reserved3 != 0u) return "pndf_project_options7.reserved3 must be 0";
+    if (o7->len_flags & ~(uint32_t)PNDF_LEN_PER_POSE) return "pndf_project_options7.len_flags has a bit other than PNDF_LEN_PER_POSE";
+    if (!isfinite(o7->nu_len) || !(o7->nu_len >= 0.f)) return "pndf_project_options7.nu_len must be finite and zero or positive";
+    if (!isfinite(o7->kappa) || !(o7->kappa >= 0.f)) return "pndf_project_options7.kappa must be finite and zero or positive";
+    if (!(o7->len_min == 0.f && o7->len_max == 0.f)) {
+        if (!isfinite(o7->len_min) || !(o7->len_min > 0.f))
+            return "pndf_project_options7.len_min must be finite and positive when a clamp is given (len_min and len_max both 0: none)";
+        if (!isfinite(o7->len_max) || !(o7->len_max >= o7->len_min))
+            return "pndf_project_options7.len_max must be finite and not below len_min when a clamp is given";
+    }
+    if ((uintptr_t)o7->len_rate & 3) return "pndf_project_options7.len_rate must be 4-byte aligned";
+    if ((uintptr_t)o7->bone_scale & 3) return "pndf_project_options7.bone_scale must be 4-byte aligned";
+    if (!o7->bone_scale && o7->nu_len > 0.f) return "pndf_project_options7.bone_scale must not be NULL when nu_len is positive";
+    const int32_t S = nj + k6.named_K;      // without kp_target there are no keypoints and no term: len_rate is not read
+    if (o7->len_rate && k6.named_target)
+        for (int32_t i = 0; i < S; ++i)
+            if (!isfinite(o7->len_rate[i]) || !(o7->len_rate[i] >= 0.f))
+                return "pndf_project_options7.len_rate has an entry that is negative or not finite";
+    observed = mask;
+    tracks = tr;
+    data = da;
+    kp = k6;
+    cam = c6;
+    const bool per_pose = (o7->len_flags & PNDF_LEN_PER_POSE) != 0 || tr.frames < 2;
+    len.S = S;
+    len.group = per_pose ? 1 : tr.frames;
+    len.named_scale = o7->bone_scale;
+    len.named_floats = (B > 0 ? B / len.group : 0) * (int64_t)S;
+    len.nu_len = o7->nu_len;
+    len.kappa = o7->kappa;
+    len.len_min = o7->len_min;
+    len.len_max = o7->len_max;
+    if (o7->len_rate && k6.named_target)
+        for (int32_t i = 0; i < S; ++i) len.rate[i] = o7->len_rate[i];
+    if (kp.any()) len.scale = o7->bone_scale;
+    return nullptr;
+}
+
+// What the entry point adds to that checker, knowing B and the poses: bone_scale [G,S] is read by every step and written by every step
+// with nu_len > 0, so it may share memory with nothing the steps read or the call writes: q_out, q_in, root, anchor, conf, kp_target,
+// kp_conf, kp_energy.  nullptr, or the reason.  The arrays are compared as the struct names them.
+inline const char* pndf_check_lengths_apart(const PndfLengths& len, const PndfCameraTerm& cam, const PndfData& data, const PndfKeypoints& kp,
+                                            const float* q_in, const float* q_out, int64_t B, int nj) {
+    if (B <= 0 || !len.named_scale) return nullptr;
+    const uintptr_t r0 = (uintptr_t)len.named_scale, r1 = (uintptr_t)(len.named_scale + len.named_floats);
+    auto meets = [&](const float* p, int64_t floats) { return p && (uintptr_t)p < r1 && r0 < (uintptr_t)(p + floats); };
+    if (meets(q_out, B * nj * 4)) return "pndf_project_options7.bone_scale must not overlap q_out";
+    if (meets(q_in, B * nj * 4)) return "pndf_project_options7.bone_scale must not overlap q_in";
+    if (meets(cam.named_root, B * 7)) return "pndf_project_options7.bone_scale must not overlap pndf_project_options6.root";
+    if (meets(data.anchor, B * nj * 4)) return "pndf_project_options7.bone_scale must not overlap pndf_project_options4.anchor";
+    if (meets(data.conf, (int64_t)B * nj)) return "pndf_project_options7.bone_scale must not overlap pndf_project_options4.conf";
+    if (meets(kp.named_target, B * kp.named_K * kp.dims)) return "pndf_project_options7.bone_scale must not overlap kp_target";
+    if (meets(kp.named_conf, (int64_t)B * kp.named_K)) return "pndf_project_options7.bone_scale must not overlap kp_conf";
+    if (meets(kp.energy, B)) return "pndf_project_options7.bone_scale must not overlap kp_energy";
+    return nullptr;
+}
+
 // The host tables of validated keypoints as the step functions of pndf_fk.h take them: kp_joint and kp_offset with their defaults
 // filled in (keypoint k is joint k; zeros).  T: anything with rest [96], kpj [64] and kpo [192] -- the kernel's argument struct, the
 // host twin's local copy.

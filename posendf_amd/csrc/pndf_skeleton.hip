@@ -28,7 +28,12 @@
 //                              lane's pose, the keypoint residuals and the reverse of pndf_fk.h in workspace rows [24 J][ld], then
 //                              pndf_fit_quat -- the denoising step with nu * dE/dQ_j in front of its finish; with the camera or the
 //                              root of a pndf_project_options6 (image fitting) its fifth instantiation
-//                              pndf_skel_enc_rev_image_kernel: pndf_fk.h's camera term in place of the 3D term and the root's own step
+//                              pndf_skel_enc_rev_image_kernel: pndf_fk.h's camera term in place of the 3D term and the root's own step;
+//                              with the bone lengths of a pndf_project_options7 its sixth instantiation pndf_skel_enc_rev_len_kernel:
+//                              the camera term on the tree scaled by the row of the lane's group, d E / d sigma of the frame left in
+//                              S workspace rows
+//   pndf_skel_len_step_kernel  once per chunk and step behind that kernel (only when nu_len > 0): the sum of those rows over the frames
+//                              of every group in pndf_fk.h's order and the step of the scales in place
 //   pndf_skel_fill_kernel      the fill of a track from its two end frames, once per chunk in front of the steps
 // 2 + 2 L launches per evaluation.  No float atomics, no communication between workgroups, every column of a GEMM summed in the
 // same order wherever it sits: the same inputs give the same bits and a pose's result does not depend on its batch.
@@ -117,6 +122,25 @@ struct SkImageArgs : SkFitArgs {
     float nu_rot, nu_trans;   // the weights of the root's own step; both 0: the root is not written
 };
 
+// SkImageArgs with the bone lengths of a pndf_project_options7 (SK_PROJECT), which pndf_skel_enc_rev_len_kernel alone takes, derived for the
+// same reason.
+struct SkLenArgs : SkImageArgs {
+    const float* bone_scale;  // the rows [groups of the chunk][S] of the scales, or null (no lengths)
+    int S;                    // nj + K
+    int group;                // frames per group: lane c reads row c / group
+};
+
+// What pndf_skel_len_step_kernel takes: the rows h [S][ld] the reverse left, the chunk's distance row and the scales to step in place
+struct SkLenStepArgs {
+    float* bone_scale;        // [G][S]
+    const float* h;           // row i of frame c at h[i * ld + c]
+    const float* dist;        // [ld]
+    int64_t ld;
+    int G, S, n;              // groups of the chunk, scales per group, frames per group
+    float nu_len, kappa, len_min, len_max, tol;
+    float rate[PNDF_MAX_SCALES];
+};
+
 // bone j forward on column c: the parent's features are read back from act0 (a per-thread feature array indexed by a run-time
 // parent would live in scratch memory)
 template <int FIN>
@@ -194,11 +218,14 @@ extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_fwd_kernel(SkArg
 // energy and gradient of the lane's pose at the step's input iterate -- all of it before the first store to `out`, which may be `q`.
 // SK_REV_IMAGE is the instantiation of a pndf_project_options6 with a root or PNDF_KP_IMAGE: SK_REV_FIT with pndf_fk.h's camera term in
 // place of the 3D term, and the root's own step -- a lane reads its root row before the term and writes it after the joints.
-enum { SK_REV_PLAIN = 0, SK_REV_TRACKS = 1, SK_REV_DENOISE = 2, SK_REV_FIT = 3, SK_REV_IMAGE = 4 };
+// SK_REV_LEN is the instantiation of a pndf_project_options7 with scales: SK_REV_IMAGE with pndf_fk.h's scaled term, which reads the row
+// of the lane's group and leaves d E / d sigma of the lane's frame in the rows behind the tree's; the scales step in their own kernel.
+enum { SK_REV_PLAIN = 0, SK_REV_TRACKS = 1, SK_REV_DENOISE = 2, SK_REV_FIT = 3, SK_REV_IMAGE = 4, SK_REV_LEN = 5 };
 template <int KIND, class Args>
 __device__ __forceinline__ void skel_enc_rev(const Args& e) {
     constexpr bool TRACKS = KIND == SK_REV_TRACKS;
-    constexpr bool IMAGE = KIND == SK_REV_IMAGE;
+    constexpr bool LEN = KIND == SK_REV_LEN;
+    constexpr bool IMAGE = KIND == SK_REV_IMAGE || LEN;
     constexpr bool FIT = KIND == SK_REV_FIT || IMAGE;
     constexpr bool DENOISE = KIND == SK_REV_DENOISE || FIT;
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -243,6 +270,11 @@ __device__ __forceinline__ void skel_enc_rev(const Args& e) {
         if (e.root)
 #pragma unroll
             for (int i = 0; i < 7; ++i) root[i] = e.root[c * 7 + i];
+        if constexpr (LEN)
+            energy = pndf_fk_len_energy_grad(q, e.nj, e.parent, e.rest, e.K, e.kpj, e.kpo, e.kp_target + c * (e.K * (e.cam.image ? 2 : 3)),
+                                             e.kp_conf ? e.kp_conf + c * e.K : nullptr, e.root != nullptr, root, e.cam,
+                                             e.bone_scale + (c / e.group) * e.S, groot, e.fk + c, e.ld);
+        else
         energy = pndf_fk_camera_energy_grad(q, e.nj, e.parent, e.rest, e.K, e.kpj, e.kpo, e.kp_target + c * (e.K * (e.cam.image ? 2 : 3)),
                                             e.kp_conf ? e.kp_conf + c * e.K : nullptr, e.root != nullptr, root, e.cam, groot, e.fk + c, e.ld);
     } else if constexpr (FIT)
@@ -321,6 +353,56 @@ extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_track_kernel
 extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_denoise_kernel(SkDenoiseArgs e) { skel_enc_rev<SK_REV_DENOISE>(e); }
 extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_fit_kernel(SkFitArgs e) { skel_enc_rev<SK_REV_FIT>(e); }
 extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_image_kernel(SkImageArgs e) { skel_enc_rev<SK_REV_IMAGE>(e); }
+extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_len_kernel(SkLenArgs e) { skel_enc_rev<SK_REV_LEN>(e); }
+
+// The step of the scales of a chunk (pndf_fk.h: pndf_fk_len_group_sum's order, pndf_fk_len_step).  Frames per group n <= 64: lanes own
+// (group, scale) pairs and sum their frames in order.  n > 64: one workgroup per (group, scale), lane b sums block b of 64 frames, lane 0
+// adds the partials in block order (a chunk has at most 16,384 frames, so at most 256 blocks); whether every frame rests goes the same way.
+extern "C" __global__ void __launch_bounds__(256) pndf_skel_len_step_kernel(SkLenStepArgs a) {
+    __shared__ float part[256];
+    __shared__ int moving[256];
+    if (a.n <= PNDF_FK_LEN_BLOCK) {
+        const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        if (t >= (int64_t)a.G * a.S) return;
+        const int g = (int)(t / a.S), i = (int)(t - (int64_t)g * a.S);
+        const float w = a.nu_len * a.rate[i];
+        if (!(w > 0.f)) return;
+        const int64_t f0 = (int64_t)g * a.n;
+        bool rests = a.tol > 0.f;
+        if (rests)
+            for (int f = 0; f < a.n; ++f) rests = rests && (a.dist[f0 + f] < a.tol);
+        if (rests) return;
+        const float H = pndf_fk_len_group_sum(a.h + (int64_t)i * a.ld + f0, 1, a.n);
+        float* sg = a.bone_scale + (int64_t)g * a.S + i;
+        *sg = pndf_fk_len_step(*sg, H, a.n, w, a.kappa, a.len_min, a.len_max, false);
+        return;
+    }
+    const int g = (int)(blockIdx.x / a.S), i = (int)(blockIdx.x - (unsigned)g * a.S);      // uniform over the workgroup
+    const float w = a.nu_len * a.rate[i];
+    if (!(w > 0.f)) return;
+    const int nb = (a.n + PNDF_FK_LEN_BLOCK - 1) / PNDF_FK_LEN_BLOCK;
+    const int b = threadIdx.x;
+    const int64_t f0 = (int64_t)g * a.n;
+    float p = 0.f;
+    int mv = 0;
+    if (b < nb) {
+        const int64_t b0 = (int64_t)b * PNDF_FK_LEN_BLOCK, b1 = b0 + PNDF_FK_LEN_BLOCK < a.n ? b0 + PNDF_FK_LEN_BLOCK : a.n;
+        p = pndf_fk_len_block_sum(a.h + (int64_t)i * a.ld + f0, 1, b0, b1);
+        for (int64_t f = b0; f < b1; ++f) mv |= (a.dist[f0 + f] < a.tol) ? 0 : 1;
+    }
+    part[b] = p;
+    moving[b] = mv;
+    __syncthreads();
+    if (b != 0) return;
+    int any = 0;
+    float H = 0.f;
+    for (int k = 0; k < nb; ++k) {
+        any |= moving[k];
+        H = pndf_fk_len_add(H, part[k]);
+    }
+    float* sg = a.bone_scale + (int64_t)g * a.S + i;
+    *sg = pndf_fk_len_step(*sg, H, a.n, w, a.kappa, a.len_min, a.len_max, a.tol > 0.f && !any);
+}
 
 // The fill of a chunk of whole tracks (pndf_project_options3, PNDF_TRACK_SLERP / _NLERP): one lane per joint quaternion.  Of every track
 // only frames 0 (a) and T-1 (b) of `src` are read; frame 0 of `dst` takes the bits of a, frame T-1 b aligned to a, the frames between
@@ -377,7 +459,8 @@ struct SkLayout {
     int64_t nc;
     int64_t X, act0, S1, S2, U0, Gx, dist, D1[MAX_LIN], P[2];
     int64_t Q2;      // the second pose buffer [nc][4 J] of the out-of-place steps of a pndf_project_options3
-    int64_t FK;      // the rows [24 J][nc] of the forward kinematics and its adjoints of a pndf_project_options5 (pndf_fk.h)
+    int64_t FK;      // the rows [24 J][nc] of the forward kinematics and its adjoints of a pndf_project_options5 (pndf_fk.h), and behind
+                     // them the rows [96][nc] of d E / d sigma of a pndf_project_options7
     int64_t total;
 };
 
@@ -403,13 +486,13 @@ SkLayout sk_layout(const pndf_skel_plan* h, int64_t B) {
     l.P[0] = c.take((int64_t)h->maxw * l.nc);
     l.P[1] = c.take((int64_t)h->maxw * l.nc);
     l.Q2 = c.take(nq * l.nc);
-    l.FK = c.take((int64_t)PNDF_FK_ROWS * h->nj * l.nc);
+    l.FK = c.take(((int64_t)PNDF_FK_ROWS * h->nj + PNDF_MAX_SCALES) * l.nc);      // the tree's rows, then pndf_fk_len_row's
     l.total = c.o;
     return l;
 }
 
 // One evaluation of a chunk of n poses at `q`: the 2 + 2 L launches (the forward alone: 1 + L and the copy of the output row)
-void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const SkImageArgs& e, hipStream_t st) {
+void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const SkLenArgs& e, hipStream_t st) {
     const int n = (int)e.n;
     TrunkWeights w{};
     TrunkBuffers b{};
@@ -419,6 +502,7 @@ void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const S
     const SkArgs& plain = e;      // what every kernel but the denoising and the fitting one takes
     const SkDenoiseArgs& denoise = e;
     const SkFitArgs& fit = e;
+    const SkImageArgs& image = e;
     hipLaunchKernelGGL(pndf_skel_enc_fwd_kernel, dim3(blocks(n)), dim3(256), 0, st, plain);
     trunk_forward(SK_GEMM, *h, w, b, st);
     if (e.mode == SK_FORWARD) {
@@ -426,15 +510,16 @@ void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const S
         return;
     }
     trunk_reverse(SK_GEMM, *h, w, b, st);      // grad_out scales the result in the encoder's reverse
-    if (e.mode == SK_PROJECT && e.kp_target && (e.root || e.cam.image)) hipLaunchKernelGGL(pndf_skel_enc_rev_image_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
+    if (e.mode == SK_PROJECT && e.kp_target && e.bone_scale) hipLaunchKernelGGL(pndf_skel_enc_rev_len_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
+    else if (e.mode == SK_PROJECT && e.kp_target && (e.root || e.cam.image)) hipLaunchKernelGGL(pndf_skel_enc_rev_image_kernel, dim3(blocks(n)), dim3(256), 0, st, image);
     else if (e.mode == SK_PROJECT && e.kp_target) hipLaunchKernelGGL(pndf_skel_enc_rev_fit_kernel, dim3(blocks(n)), dim3(256), 0, st, fit);
     else if (e.mode == SK_PROJECT && (e.anchor || e.flags)) hipLaunchKernelGGL(pndf_skel_enc_rev_denoise_kernel, dim3(blocks(n)), dim3(256), 0, st, denoise);
     else if (e.mode == SK_PROJECT && e.frames) hipLaunchKernelGGL(pndf_skel_enc_rev_track_kernel, dim3(blocks(n)), dim3(256), 0, st, plain);
     else hipLaunchKernelGGL(pndf_skel_enc_rev_kernel, dim3(blocks(n)), dim3(256), 0, st, plain);
 }
 
-SkImageArgs sk_args(const pndf_skel_plan* h, const SkLayout& l, float* ws, int mode) {
-    SkImageArgs e;
+SkLenArgs sk_args(const pndf_skel_plan* h, const SkLayout& l, float* ws, int mode) {
+    SkLenArgs e;
     memset(&e, 0, sizeof(e));
     e.wenc = h->d_blob;
     e.X = ws + l.X; e.act0 = ws + l.act0; e.U0 = ws + l.U0; e.Gx = ws + l.Gx; e.dist = ws + l.dist; e.fk = ws + l.FK;
@@ -544,7 +629,7 @@ extern "C" int pndf_skel_forward(pndf_skel_handle h, const float* q, float* d, i
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     float* ws = (float*)workspace;
-    SkImageArgs e = sk_args(h, l, ws, SK_FORWARD);
+    SkLenArgs e = sk_args(h, l, ws, SK_FORWARD);
     for (int64_t c0 = 0; c0 < B; c0 += l.nc) {
         e.n = B - c0 < l.nc ? B - c0 : l.nc;
         e.q = q + c0 * h->nj * BONE;
@@ -567,7 +652,7 @@ extern "C" int pndf_skel_forward_grad(pndf_skel_handle h, const float* q, const 
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     float* ws = (float*)workspace;
-    SkImageArgs e = sk_args(h, l, ws, SK_GRAD);
+    SkLenArgs e = sk_args(h, l, ws, SK_GRAD);
     for (int64_t c0 = 0; c0 < B; c0 += l.nc) {
         e.n = B - c0 < l.nc ? B - c0 : l.nc;
         e.q = q + c0 * h->nj * BONE;
@@ -588,7 +673,8 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
     PndfData data;                 // a pndf_project_options4 the observation besides (motion denoising): device memory, as the poses
     PndfKeypoints kp;              // a pndf_project_options5 the 3D keypoints besides (keypoint fitting): the arrays per pose in device memory, the small tables in host memory
     PndfCameraTerm cam;            // a pndf_project_options6 the camera and the root besides (image fitting): the roots per pose in device memory
-    if (const char* why = pndf_check_project_options6(opt, B, h->nj, o, observed, tracks, data, kp, cam)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    PndfLengths len;               // a pndf_project_options7 the bone lengths besides: the scales per group in device memory, the rates in host memory
+    if (const char* why = pndf_check_project_options7(opt, B, h->nj, o, observed, tracks, data, kp, cam, len)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (steps < 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count");
     SkLayout l;
     if (B > 0 && (!q_in || !q_out)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose pointer");
@@ -601,6 +687,7 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
     if (const char* why = pndf_check_observation_apart(data, q_out, B, h->nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (const char* why = pndf_check_keypoints_apart(kp, q_out, B, h->nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (const char* why = pndf_check_root_apart(cam, data, kp, q_in, q_out, B, h->nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (const char* why = pndf_check_lengths_apart(len, cam, data, kp, q_in, q_out, B, h->nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (const int rc = sk_check(h, B, workspace, workspace_bytes, l); rc != PNDF_OK || B == 0) return rc;
     PndfRange range("pndf_skel_project");
     DeviceGuard guard(h->device);
@@ -615,7 +702,7 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
         return PNDF_OK;
     }
     float* ws = (float*)workspace;
-    SkImageArgs e = sk_args(h, l, ws, SK_PROJECT);
+    SkLenArgs e = sk_args(h, l, ws, SK_PROJECT);
     e.step_size = o.step_size; e.tol = o.tol; e.renorm = (int)o.renorm;
     e.frames = tracks.frames; e.lambda = tracks.lambda;
     e.mu = data.mu; e.flags = data.free_ends ? (uint32_t)PNDF_TRACK_FREE_ENDS : 0u;
@@ -624,6 +711,15 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
         pndf_fill_keypoint_tables(e, kp, h->nj);
         e.cam.fx = cam.fx; e.cam.fy = cam.fy; e.cam.cx = cam.cx; e.cam.cy = cam.cy; e.cam.rho = cam.rho; e.cam.image = cam.image ? 1 : 0;
         e.nu_rot = cam.nu_rot; e.nu_trans = cam.nu_trans;
+    }
+    SkLenStepArgs ls;
+    memset(&ls, 0, sizeof(ls));
+    if (len.any()) {
+        e.S = len.S; e.group = len.group;
+        ls.h = ws + l.FK + (int64_t)pndf_fk_len_row(h->nj, 0) * l.nc; ls.dist = ws + l.dist; ls.ld = l.nc;
+        ls.S = len.S; ls.n = len.group;
+        ls.nu_len = len.nu_len; ls.kappa = len.kappa; ls.len_min = len.len_min; ls.len_max = len.len_max; ls.tol = o.tol;
+        for (int i = 0; i < PNDF_MAX_SCALES; ++i) ls.rate[i] = len.rate[i];
     }
     // with tracks a chunk holds whole tracks, so no track straddles a seam and lane c of a chunk is frame c % T
     const int64_t nc = tracks.frames ? (l.nc / tracks.frames) * tracks.frames : l.nc;
@@ -636,6 +732,7 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
         e.conf = data.conf ? data.conf + c0 * h->nj : nullptr;
         e.kp_target = kp.target ? kp.target + c0 * kp.K * kp.dims : nullptr;
         e.root = cam.root ? cam.root + c0 * 7 : nullptr;
+        e.bone_scale = len.any() ? len.scale + (c0 / len.group) * len.S : nullptr;      // a chunk is whole groups: with tracks it is whole tracks
         e.kp_conf = kp.conf ? kp.conf + c0 * kp.K : nullptr;
         // Without tracks the iterate is in q_out from the second step on: a lane reads its pose before it writes it.  With tracks a
         // step is out of place: the steps alternate between the chunk of q_out and the second pose buffer, the last one writes
@@ -654,6 +751,13 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
             e.d_out = (d_last && s == steps - 1) ? d_last + c0 : nullptr;
             e.kp_energy = (kp.any() && kp.energy && s == steps - 1) ? kp.energy + c0 : nullptr;
             sk_run_chunk(h, l, ws, e, st);
+            if (len.moves()) {      // behind the reverse on the same stream: the frames of this step have read the scales
+                ls.bone_scale = len.scale + (c0 / len.group) * len.S;
+                ls.G = (int)(e.n / len.group);
+                const int64_t lanes = (int64_t)ls.G * ls.S;
+                const unsigned grid = ls.n <= PNDF_FK_LEN_BLOCK ? (unsigned)blocks(lanes) : (unsigned)lanes;
+                hipLaunchKernelGGL(pndf_skel_len_step_kernel, dim3(grid), dim3(256), 0, st, ls);
+            }
             cur = e.out;
         }
     }

@@ -15,7 +15,7 @@ import numpy as np
 # public names stay importable from here.  `torch` comes from there too: abi imports it before the library is loaded (None without it).
 from .abi import (ACT_CODES, DEBUG_EXPERIMENT_WORDS, DEBUG_EXPORTS, EXPERIMENT_WORDS, EXPORTS, INTERP_MODES, METRIC_CODES,  # noqa: F401
                   NOISE_CODES, PRECISION_CODES, RENORM_CODES, Camera, DenoiseWeights, KeypointOpts, OnlineOpts, PndfConfig, PndfError,
-                  ProjectOptions, ProjectOptions2, ProjectOptions3, ProjectOptions4, ProjectOptions5, ProjectOptions6, KP_IMAGE, TRACK_FILLS, TRACK_FREE_ENDS, debug_library_path, experiment_word, load_library, torch)
+                  ProjectOptions, ProjectOptions2, ProjectOptions3, ProjectOptions4, ProjectOptions5, ProjectOptions6, ProjectOptions7, KP_IMAGE, LEN_PER_POSE, TRACK_FILLS, TRACK_FREE_ENDS, debug_library_path, experiment_word, load_library, torch)
 
 
 def stream_handle(device) -> int:
@@ -179,6 +179,39 @@ def project_options6(lib, *args, root_ptr=None, root_weights=(0.0, 0.0), camera=
     opt.nu_rot, opt.nu_trans = (float(v) for v in root_weights)
     opt.kp_flags = KP_IMAGE if (camera is not None if image is None else image) else 0
     return opt
+
+
+def project_options7(lib, *args, bone_scale_ptr=None, len_rate=None, len_weight=0.0, len_prior=0.0, len_range=None, per_pose_lengths=False, **kw):
+    """pndf_project_options7 (include/posendf_amd.h): `project_options6`'s arguments, and the bone lengths of a fit -- `bone_scale_ptr` [G,S]
+    (S = J + K; one row per track, or per pose with `per_pose_lengths` or without tracks; None: all ones) in the memory space of the poses,
+    read and, with a positive `len_weight` (nu_len), written by every step; `len_rate`: S floats (a sequence; None: ones; 0 holds that
+    scale), kept alive on the returned struct; `len_prior` kappa; `len_range` (len_min, len_max) or None.  The values are checked by the
+    library."""
+    opt = ProjectOptions7()
+    opt.base6 = project_options6(lib, *args, **kw)
+    opt.base6.base5.base4.base3.base2.base.struct_size = ctypes.sizeof(opt)
+    opt.bone_scale = bone_scale_ptr
+    if len_rate is not None:
+        rates = [float(v) for v in len_rate]
+        opt._rates = (ctypes.c_float * max(len(rates), 1))(*rates)      # host memory that lives as long as the struct
+        opt.len_rate = ctypes.cast(opt._rates, ctypes.c_void_p).value
+    opt.nu_len, opt.kappa = float(len_weight), float(len_prior)
+    if len_range is not None:
+        opt.len_min, opt.len_max = (float(v) for v in len_range)
+    opt.len_flags = LEN_PER_POSE if per_pose_lengths else 0
+    return opt
+
+
+_LENGTH_KEYS = ("bone_scale_ptr", "len_rate", "len_weight", "len_prior", "len_range", "per_pose_lengths")
+
+
+def _lengthed(kw):
+    """(the bone-length keywords of a `project` call, the rest): only when one of them is given is the 208-byte struct built"""
+    mine = {k: kw[k] for k in _LENGTH_KEYS if k in kw}
+    rest = {k: v for k, v in kw.items() if k not in _LENGTH_KEYS}
+    named = (mine.get("bone_scale_ptr") is not None or mine.get("len_rate") is not None or mine.get("len_range") is not None
+             or bool(mine.get("per_pose_lengths")) or float(mine.get("len_weight") or 0.0) != 0.0 or float(mine.get("len_prior") or 0.0) != 0.0)
+    return (mine if named else None), rest
 
 
 _IMAGE_KEYS = ("root_ptr", "root_weights", "camera", "rho", "image")
@@ -557,10 +590,17 @@ class SkeletonEngine(_Handle):
         pndf_project_options4: `project_options4`), apart from q_out.  `**keypoints`: kp_target_ptr [B,K,3] / kp_conf_ptr [B,K] / kp_energy_ptr
         [B] in device memory, rest_ptr / kp_joint_ptr / kp_offset_ptr in HOST memory, n_keypoints, kp_weight: the 3D keypoints of a fit
         (through a pndf_project_options5: `project_options5`); root_ptr [B,7] in device memory, root_weights, camera, rho, image: the root and
-        the camera of a fit to 2D keypoints (through a pndf_project_options6: `project_options6`)"""
+        the camera of a fit to 2D keypoints (through a pndf_project_options6: `project_options6`); bone_scale_ptr [G,S] in device memory,
+        len_rate, len_weight, len_prior, len_range, per_pose_lengths: the bone lengths of a fit (through a pndf_project_options7:
+        `project_options7`)"""
+        lengthed, keypoints = _lengthed(keypoints)
         imaged, keypoints = _imaged(keypoints)
         named = _keypointed(keypoints)      # (refuses an unknown keyword)
-        if imaged is not None:
+        if lengthed is not None:
+            opt7 = project_options7(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends,
+                                    step_size=step_size, renorm=renorm, tol=tol, **keypoints, **(imaged or {}), **lengthed)
+            opt = ctypes.byref(opt7)
+        elif imaged is not None:
             opt = ctypes.byref(project_options6(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends,
                                                 step_size=step_size, renorm=renorm, tol=tol, **keypoints, **imaged))
         elif named:
@@ -765,9 +805,17 @@ class CpuEngine(_Handle):
         pndf_project_options3: `project_options3`).  `anchor_ptr` [B,J,4] / `conf_ptr` [B,J] in host memory, `data` and `free_ends`: the
         observation of motion denoising (pndf_project_ex_cpu with a pndf_project_options4: `project_options4`).  `**keypoints`: as
         SkeletonEngine.project, every pointer in host memory (pndf_project_ex_cpu with a pndf_project_options5: `project_options5`, or with
-        root_ptr / root_weights / camera / rho / image a pndf_project_options6: `project_options6`)"""
+        root_ptr / root_weights / camera / rho / image a pndf_project_options6: `project_options6`, or with bone_scale_ptr / len_rate /
+        len_weight / len_prior / len_range / per_pose_lengths a pndf_project_options7: `project_options7`)"""
+        lengthed, keypoints = _lengthed(keypoints)
         imaged, keypoints = _imaged(keypoints)
         named = _keypointed(keypoints)      # (refuses an unknown keyword)
+        if lengthed is not None:
+            opt7 = project_options7(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends,
+                                    step_size=step_size, renorm=renorm, tol=tol, **keypoints, **(imaged or {}), **lengthed)
+            self._check(self.lib.pndf_project_ex_cpu(self.handle, q_in_ptr, q_out_ptr, d_ptr, B, int(steps), ctypes.byref(opt7)),
+                        "pndf_project_ex_cpu")
+            return
         if imaged is not None:
             opt6 = project_options6(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends,
                                     step_size=step_size, renorm=renorm, tol=tol, **keypoints, **imaged)

@@ -9,6 +9,8 @@ starts per target and returns, per target, the hypothesis of the lowest `energy 
 
 With a `camera` the detections are pixels [N,K,2], and with a `root` the tree is placed in the target's frame by a rotation and a
 translation per pose that the steps move as well (pndf_project_options6; DESIGN.md section 2j "Image fitting"): a hand tracker's output.
+With `fit_lengths=True` the segment lengths of the subject are unknowns too: a scale per rest offset and per keypoint offset
+(pndf_project_options7; DESIGN.md section 2j "Bone lengths").
 
 `python -m posendf_amd.keypoint_fitting` reads an .npz of targets and writes the fitted poses.
 """
@@ -19,13 +21,14 @@ import torch
 from .sample_poses import SamplePose
 
 
-def keypoint_energy(pose, targets, parents, rest, conf=None, keypoint_joints=None, keypoint_offsets=None, root=None, camera=None, rho=0.0):
+def keypoint_energy(pose, targets, parents, rest, conf=None, keypoint_joints=None, keypoint_offsets=None, root=None, camera=None, rho=0.0,
+                    bone_scale=None):
     """1/2 sum_k w_k |C_k(pose, root) - targets_k|^2 per pose [...], with `forward_kinematics` and `camera_project`; a keypoint whose
     confidence is not positive (zero, negative, NaN) takes no part, whatever its target holds.  With a `camera` the targets are pixels and
     the residual e is taken in normalised image coordinates, rho(e) = e^2 or (rho > 0) rho^2 e^2 / (e^2 + rho^2) summed over both axes; a
     keypoint that is not in front of the camera takes no part"""
     from .skeleton import camera_project, forward_kinematics
-    C = camera_project(forward_kinematics(pose, parents, rest, keypoint_joints, keypoint_offsets), root)
+    C = camera_project(forward_kinematics(pose, parents, rest, keypoint_joints, keypoint_offsets, bone_scale), root)
     if camera is None:
         res = C - targets
         sq = (res * res).sum(-1)
@@ -49,7 +52,8 @@ class KeypointFitting(SamplePose):
 
     @torch.no_grad()
     def fit(self, targets, rest, conf=None, keypoint_joints=None, keypoint_offsets=None, hypotheses=8, iterations=3, steps_per_iter=30, weight=0.02,
-            lam=1.0, seed=None, *, step_size=1.0, renormalize="unit", tol=0.0, camera=None, root=None, root_weights=(0.0, 0.0), rho=0.0):
+            lam=1.0, seed=None, *, step_size=1.0, renormalize="unit", tol=0.0, camera=None, root=None, root_weights=(0.0, 0.0), rho=0.0,
+            fit_lengths=False, length_weight=0.02, length_prior=0.1, length_range=(0.5, 2.0)):
         """targets: [N,K,3] detections (one set of K keypoints per target pose); rest / keypoint_joints / keypoint_offsets / conf: as
         `SkeletonPoseNDF.fit_keypoints` (conf [K] or [N,K]).  Every target gets `hypotheses` random starts (unit quaternions, seeded by
         `seed`); `iterations` engine calls of `steps_per_iter` steps each run all N * hypotheses poses at once, iteration `it` with the
@@ -65,7 +69,13 @@ class KeypointFitting(SamplePose):
         image coordinates, smaller than the 3D term's by the depth of the rig, so useful weights are larger.  Tried on a 15-joint hand with
         rest offsets within [-0.75, 0.75]^3 about 6 units in front of the camera, pure inverse kinematics, as (weight; nu_rot, nu_trans):
         (2.0; 0.5, 2.0), (1.0; 0.2, 1.0) and (0.5; 0.1, 0.5) make the energy of 45, 19 and 5 starts of 48 rise at some step; (0.3; 0.05, 0.3)
-        and (0.1; 0.02, 0.1) lower it at every step for every start."""
+        and (0.1; 0.02, 0.1) lower it at every step for every start.
+        `fit_lengths=True` makes the bone lengths unknowns of the fit: every hypothesis carries its own scales [S] (S = J + K, one per rest
+        offset and per keypoint offset, `SkeletonPoseNDF.fit_keypoints(bone_scale=, per_pose_scale=True)`), started at ones, stepped with
+        `length_weight` under the prior `length_prior` (sigma - 1)^2 / 2 and clamped to `length_range`; the result gains a last entry, the
+        scales [N,S] of the chosen hypothesis.  These defaults (0.02, 0.1, (0.5, 2.0)) are UNTUNED: no trained model of another skeleton
+        exists to tune them on.  With a camera and a free root translation the overall scale trades against depth and only the prior holds
+        it."""
         net = self.pose_prior
         if not hasattr(net, "fit_keypoints"):
             raise TypeError(f"{type(net).__name__} has no fit_keypoints(): fitting to 3D keypoints is SkeletonPoseNDF's; a PoseNDF fits 2D "
@@ -95,14 +105,20 @@ class KeypointFitting(SamplePose):
         rest_d = torch.as_tensor(rest).to(self.device).float()
         off_d = None if keypoint_offsets is None else torch.as_tensor(keypoint_offsets).to(self.device).float()
 
+        sg = torch.ones(N * H, J + K, device=self.device) if fit_lengths else None
+        lengths = dict(scale_weight=length_weight, scale_prior=length_prior, scale_range=length_range, per_pose_scale=True, return_scale=True) if fit_lengths else {}
+
         def energy_of(q, r):
-            return keypoint_energy(q, yy, net.parents, rest_d, c, keypoint_joints, off_d, r, camera, rho)
+            return keypoint_energy(q, yy, net.parents, rest_d, c, keypoint_joints, off_d, r, camera, rho, sg)
 
         cur = start.reshape(N * H, J, 4)
         start_energy = energy_of(cur, rt).reshape(N, H)
         for _ in range(int(iterations)):
             cur = net.fit_keypoints(cur, yy, rest, steps=int(steps_per_iter), weight=weight, conf=c, return_dist=False, step_size=step_size,
-                                    renormalize=renormalize, tol=tol, **tables, **image, **(dict(root=rt, return_root=True) if rt is not None else {}))
+                                    renormalize=renormalize, tol=tol, **tables, **image, **(dict(root=rt, return_root=True) if rt is not None else {}),
+                                    **(dict(bone_scale=sg, **lengths) if fit_lengths else {}))
+            if fit_lengths:
+                cur, sg = cur[:-1] if rt is not None else cur[0], cur[-1]
             if rt is not None:
                 cur, rt = cur
         energy = energy_of(cur, rt).reshape(N, H)
@@ -115,6 +131,8 @@ class KeypointFitting(SamplePose):
                 rt = torch.zeros(N * H, 7, device=cur.device)
                 rt[:, 0] = 1.0
             result += (rt.reshape(N, H, 7)[pick, best],)
+        if fit_lengths:
+            result += (sg.reshape(N, H, J + K)[pick, best],)
         return result
 
 
@@ -157,6 +175,8 @@ def main(argv=None):
     ap.add_argument("--root_weights", type=float, nargs=2, default=(0.0, 0.0), metavar=("NU_ROT", "NU_TRANS"),
                     help="weights of the root's own step (needs a root in the file); 0 holds that part")
     ap.add_argument("--rho", type=float, default=0.0, help="robustifier of the image residual (needs a camera in the file); 0 = squared error")
+    ap.add_argument("--fit-lengths", "--fit_lengths", dest="fit_lengths", action="store_true",
+                    help="fit a scale per rest offset and per keypoint offset besides (weights untuned); written to the key scale")
     ap.add_argument("--lam", type=float, default=1.0, help="weight of the distance in the choice between hypotheses")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None, help="write the fitted poses (key pose), their energies (energy) and distances (dist) to this .npz")
@@ -170,13 +190,17 @@ def main(argv=None):
         extra["root_weights"] = tuple(a.root_weights)
     if a.rho:
         extra["rho"] = a.rho
+    if a.fit_lengths:
+        extra["fit_lengths"] = True
     pose, energy, dist, start, *root = fit_keypoint_file(net, a.keypoint_file, device=opt["train"]["device"], hypotheses=a.hypotheses, iterations=a.iterations,
                                                          steps_per_iter=a.steps_per_iter, weight=a.weight, lam=a.lam, seed=a.seed, **extra)
     if energy.numel():
         print(f"median keypoint energy {float(energy.median()):.5f} (random starts: {float(start.median()):.5f}), mean dist {float(dist.mean()):.4f}")
+    scale = [root.pop()] if a.fit_lengths else []
     if a.out:
         import numpy as np
-        np.savez(a.out, pose=pose.cpu().numpy(), energy=energy.cpu().numpy(), dist=dist.cpu().numpy(), **({"root": root[0].cpu().numpy()} if root else {}))
+        np.savez(a.out, pose=pose.cpu().numpy(), energy=energy.cpu().numpy(), dist=dist.cpu().numpy(), **({"root": root[0].cpu().numpy()} if root else {}),
+                 **({"scale": scale[0].cpu().numpy()} if scale else {}))
     return pose, energy
 
 

@@ -22,6 +22,8 @@ rest)` is inverse kinematics under the prior -- 3D detections of keypoints attac
 body model, in a pndf_project_options5 --, which `posendf_amd.keypoint_fitting.KeypointFitting` drives; `forward_kinematics` is the
 differentiable torch statement of its kinematics.  With `camera=` the detections are pixels, and with `root=` / `root_weights=` the tree
 has a placement in the target's frame that the steps move (a pndf_project_options6; `camera_project` is the torch statement of both).
+With `bone_scale=` / `scale_weight=` the segment lengths of the subject are unknowns of the same fit, one set of scales per clip (a
+pndf_project_options7; `forward_kinematics(..., bone_scale=)` is the torch statement of the scaled tree).
 Only the second order stays 21-joint: its C ABI refuses another joint count, and that refusal is pinned.
 """
 from __future__ import annotations
@@ -230,7 +232,8 @@ class SkeletonPoseNDF(PoseModel):
     @torch.no_grad()
     def fit_keypoints(self, poses, targets, rest, steps=100, weight=0.02, conf=None, keypoint_joints=None, keypoint_offsets=None, observed=None,
                       frames=None, smooth=0.0, anchor=None, data=0.0, free_ends=False, return_dist=True, return_energy=False, *, step_size=1.0,
-                      renormalize=None, tol=0.0, root=None, root_weights=(0.0, 0.0), camera=None, rho=0.0, return_root=False):
+                      renormalize=None, tol=0.0, root=None, root_weights=(0.0, 0.0), camera=None, rho=0.0, return_root=False, bone_scale=None,
+                      scale_weight=0.0, scale_prior=0.0, scale_range=None, scale_rates=None, per_pose_scale=False, return_scale=False):
         """Inverse kinematics under the learned prior, for the model's tree: from the start `poses` [B,J,4], `steps` projection steps that
         also descend E = 1/2 sum_k conf_k |P_k(pose) - targets_k|^2 with weight `weight` (nu), P_k = `forward_kinematics` of the pose.
         `targets` [B,K,3] are 3D detections in the roots' frame; `rest` [J,3] the offsets of the joints from their parents in the rest
@@ -259,9 +262,17 @@ class SkeletonPoseNDF(PoseModel):
         keypoint term (`weight` 0) the root is left as it is.  The default weights are zero; those tried are listed in
         `posendf_amd.keypoint_fitting`.  `camera_project` is the torch statement of C_k and of the pixels.  The defaults are the call
         without a camera, bit for bit.
+        Bone lengths (pndf_project_options7; DESIGN.md section 2j "Bone lengths"): `bone_scale` [G,S] or [S], S = J + K, scales the rest
+        offset of joint j by bone_scale[..., j] and the local offset of keypoint k by bone_scale[..., J + k]; with `frames` = T >= 2 and
+        without `per_pose_scale` there is one row per clip (G = B / T) which all its frames read, otherwise one per pose (G = B).  It lives
+        where `poses` may live and is cloned.  `scale_weight` (nu_len) > 0 lets every step move the scales along the gradient of the
+        clip's mean energy plus the prior 1/2 `scale_prior` (sigma - 1)^2 (then a missing `bone_scale` starts at ones); `scale_rates` [S]
+        multiplies the weight per scale (0 holds that scale); `scale_range` = (lo, hi) clamps them.  Like the root the scales are not
+        joints: held joints and held end frames still contribute to their gradient.  With 2D targets and a free root translation the
+        overall scale trades against depth and is not observable: use a prior.  The default weights are zero and UNTUNED.
         Returns poses [B,J,4], then dist [B,1] of the last iteration (`return_dist`), then the energy [B] of the last iteration, evaluated
-        before its update (`return_energy`), then the final root [B,7] (`return_root`; the identity placement when none was given);
-        step options: as `project`."""
+        before its update (`return_energy`), then the final root [B,7] (`return_root`; the identity placement when none was given), then
+        the final scales [G,S] (`return_scale`; ones when none were given); step options: as `project`."""
         J = self.num_joints
         home = torch.device(self.device)
 
@@ -307,6 +318,25 @@ class SkeletonPoseNDF(PoseModel):
             place = place.float().expand(B, 7).contiguous().clone()
         if len(tuple(root_weights)) != 2:
             raise PndfError("root_weights is (nu_rot, nu_trans)")
+        T = int(frames or 0)
+        if T == 1:
+            T = 0
+        S = J + K
+        G = B if (per_pose_scale or T < 2) else (B // T if B % T == 0 else -1)
+        lengthed = bone_scale is not None or bool(scale_weight) or bool(scale_prior) or scale_range is not None or scale_rates is not None or bool(per_pose_scale)
+        scales = None
+        if bone_scale is not None:
+            scales = on_device(bone_scale, "bone_scale")
+            if not scales.is_floating_point() or tuple(scales.shape) not in ((S,), (G, S)):
+                raise PndfError(f"bone_scale is a floating-point tensor [{S}] or [{G},{S}], not {scales.dtype} {list(scales.shape)}")
+            scales = scales.float().expand(max(G, 0), S).contiguous().clone()
+        elif scale_weight and G >= 0:
+            scales = torch.ones(G, S, device=home, dtype=torch.float32)
+        if scale_range is not None and len(tuple(scale_range)) != 2:
+            raise PndfError("scale_range is (lo, hi)")
+        rates = None
+        if scale_rates is not None:
+            rates = table(scale_rates, (S,), torch.float32, "scale_rates").tolist()
         c = None
         if conf is not None:
             c = on_device(conf, "conf")
@@ -319,9 +349,6 @@ class SkeletonPoseNDF(PoseModel):
             if seen.numel() != q.numel() or tuple(seen.shape[-2:]) != (J, 4):
                 raise PndfError(f"anchor has the poses' shape {list(q.shape)}, not {list(seen.shape)}")
             seen = seen.reshape(q.shape).contiguous()
-        T = int(frames or 0)
-        if T == 1:
-            T = 0
         out = torch.empty_like(q)
         d = torch.empty(B, device=dev, dtype=torch.float32)
         energy = torch.zeros(B, device=dev, dtype=torch.float32)
@@ -338,21 +365,28 @@ class SkeletonPoseNDF(PoseModel):
                         kp_joint_ptr=None if kpj is None else kpj.data_ptr(), kp_offset_ptr=None if kpo is None else kpo.data_ptr(),
                         n_keypoints=K, kp_weight=weight, **tracks,
                         **(dict(root_ptr=place.data_ptr() if place is not None and B else None, root_weights=tuple(root_weights) if B else (0.0, 0.0), camera=camera, rho=rho)
-                           if place is not None or camera is not None or rho or any(root_weights) else {}))
+                           if place is not None or camera is not None or rho or any(root_weights) else {}),
+                        **(dict(bone_scale_ptr=scales.data_ptr() if scales is not None and B else None, len_rate=rates, len_weight=scale_weight if B else 0.0,
+                                len_prior=scale_prior, len_range=None if scale_range is None else tuple(scale_range), per_pose_lengths=bool(per_pose_scale))
+                           if lengthed else {}))
+        if return_scale and scales is None:
+            scales = torch.ones(max(G, 0), S, device=dev, dtype=torch.float32)
         if return_root and place is None:
             place = torch.zeros(B, 7, device=dev, dtype=torch.float32)
             place[:, 0] = 1.0
-        result = (out,) + ((d.view(-1, 1),) if return_dist else ()) + ((energy,) if return_energy else ()) + ((place,) if return_root else ())
+        result = (out,) + ((d.view(-1, 1),) if return_dist else ()) + ((energy,) if return_energy else ()) + ((place,) if return_root else ()) + ((scales,) if return_scale else ())
         return result if len(result) > 1 else out
 
 
-def forward_kinematics(pose, parents, rest, keypoint_joints=None, keypoint_offsets=None):
+def forward_kinematics(pose, parents, rest, keypoint_joints=None, keypoint_offsets=None, bone_scale=None):
     """The keypoints of poses on a joint tree, differentiable: pose [...,J,4] (joint quaternions, real part first; each is normalised,
     r = Q / max(|Q|, 1e-12)) -> [...,K,3].  `parents`: the parent table (-1: a root; every parent before its child); `rest` [J,3]: joint j
     relative to its parent in the rest pose (the position of a root); keypoint k sits on joint `keypoint_joints[k]` at the local offset
     `keypoint_offsets[k]` (None: K = J, the joints themselves).  With G_j the global rotation and p_j the position of joint j:
     root G_j = R_j, p_j = t_j; else G_j = G_parent R_j, p_j = p_parent + G_parent t_j; P_k = p_a(k) + G_a(k) o_k.  This is the statement
-    `SkeletonPoseNDF.fit_keypoints` (csrc/pndf_fk.h) descends; use it to make targets and to read residuals."""
+    `SkeletonPoseNDF.fit_keypoints` (csrc/pndf_fk.h) descends; use it to make targets and to read residuals.  `bone_scale` [...,J+K] or
+    [J+K] (None: no scaling, the same bits): joint j's rest offset is scaled by bone_scale[..., j], keypoint k's local offset by
+    bone_scale[..., J + k] -- the tree of `fit_keypoints(bone_scale=)`; its leading dimensions broadcast against the pose's."""
     parents = parent_table(parents)
     J = len(parents)
     if tuple(pose.shape[-2:]) != (J, 4):
@@ -371,15 +405,28 @@ def forward_kinematics(pose, parents, rest, keypoint_joints=None, keypoint_offse
     R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
                      2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
                      2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], dim=-1).reshape(pose.shape[:-1] + (3, 3))
+    sg = None
+    if bone_scale is not None:      # a scale commutes with the rotation: sigma (G t) is G (sigma t), and with sigma = 1 the same bits as without
+        sg = torch.as_tensor(bone_scale, dtype=pose.dtype, device=pose.device)
+        if sg.shape[-1] != J + len(joints):
+            raise PndfError(f"bone_scale is [...,{J + len(joints)}], not {tuple(sg.shape)}")
     G, p = [], []
     for j, pa in enumerate(parents):
         if pa < 0:
             G.append(R[..., j, :, :])
-            p.append(rest[j].expand(pose.shape[:-2] + (3,)))
+            t = rest[j] if sg is None else sg[..., j, None] * rest[j]
+            p.append(t.expand(pose.shape[:-2] + (3,)))
         else:
             G.append(G[pa] @ R[..., j, :, :])
-            p.append(p[pa] + (G[pa] @ rest[j].unsqueeze(-1)).squeeze(-1))
-    out = [p[a] if offsets is None else p[a] + (G[a] @ offsets[k].unsqueeze(-1)).squeeze(-1) for k, a in enumerate(joints)]
+            v = (G[pa] @ rest[j].unsqueeze(-1)).squeeze(-1)
+            p.append(p[pa] + (v if sg is None else sg[..., j, None] * v))
+    out = []
+    for k, a in enumerate(joints):
+        if offsets is None:
+            out.append(p[a])
+        else:
+            v = (G[a] @ offsets[k].unsqueeze(-1)).squeeze(-1)
+            out.append(p[a] + (v if sg is None else sg[..., J + k, None] * v))
     return torch.stack(out, dim=-2)
 
 
