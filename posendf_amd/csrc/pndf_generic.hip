@@ -355,8 +355,13 @@ __device__ __forceinline__ void gen_backward(Ring& ring, GenW& W, const char* gi
 // Operand scaling (exact: every factor is a power of two), simpler than the fused kernels' because a layer is complete before the
 // next one starts: the stream carries s_l W (s_l: the largest |weight| of the layer in [2^12, 2^13), chosen by the packer), and every
 // pose scales the operand tensor of a layer by its own sigma(p) with max_i |x_i(p)| sigma in [2^13, 2^14) -- the bound is MEASURED for
-// every layer (running maximum over the epilogues of the producing layer + two cross-lane steps); the hi halves cannot overflow for
-// any finite weights and poses, and the lo half of every value down to 2^-10 of the pose's largest stays a NORMAL fp16.  The fp32
+// every layer (running maximum over the epilogues of the producing layer + two cross-lane steps); while no clamp of sigma engages the
+// hi halves cannot overflow and the lo half of every value down to 2^-10 of the pose's largest stays a NORMAL fp16.  The clamps bound
+// that: a pose's largest activation of a layer in [2^-27, 2^54), its largest adjoint in [2^-80, 2^54) (gen_pose_scale,
+// gen_pose_scale_grad; layer_scale takes any layer whose largest |weight| lies in (2^-100, 2^100)).  Below a floor the operands slide
+// down the fp16 range and lose their low bits binade by binade; above a ceiling they climb it: two binades are left, a third as long as
+// the lo half holds what the saturated hi half (rtz) cannot, then the pose comes back NaN (DESIGN.md 2c "Magnitude range",
+// tests/test_depth_range_gpu.py).  The fp32
 // accumulators hold s_l sigma x the true value (they start from b s_l sigma); one multiply per value in the epilogue (`to_true`)
 // brings it back, and the scratch holds TRUE fp32 values exactly as on the fp32 path.
 typedef _Float16 gf16x8 __attribute__((ext_vector_type(8)));

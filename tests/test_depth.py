@@ -260,17 +260,17 @@ EXTREMES = [([1], "lrelu", True), ([16], "relu", True), ([17], "softplus", True)
             ([65, 347, 385, 256, 81, 1, 2], "softplus", True)]
 
 
-def live_weights(dims, act):
+def live_weights(dims, act, gain=2.5, out_bias=0.3):
     """the first seed (deterministic) whose network is not clipped to d = 0 on most poses: a dead network tests nothing"""
     from oracle import posendf_np as onp
     from posendf_amd import synth
     probe = synth.make_poses(48, seed=60)
     for seed in range(50, 90):
-        sd = synth.make_weights(seed, 2.5, 0.3, dims=dims)
+        sd = synth.make_weights(seed, gain, out_bias, dims=dims)
         d = onp.forward(probe, sd, act)
         if (d > 1e-3).mean() > 0.8:
             return sd
-    raise AssertionError(f"no live weight set for {dims} {act}")
+    raise AssertionError(f"no live weight set for {dims} {act} gain {gain} bias {out_bias}")
 
 
 def _check_against_oracle(hidden, act, enc, precision, sd):

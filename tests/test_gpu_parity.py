@@ -680,6 +680,28 @@ def test_layer_scale_extremes(torch_cuda, act, precision, scales):
     pose_gate(rel_err_rows(dq.cpu().numpy(), g64), sig_g, "dq", exempt=kink_exempt(qn, sd, act))
 
 
+@pytest.mark.parametrize("scales", [(2.0 ** 16,) * 6, (2.0 ** -16,) * 6, (2.0 ** 16, 2.0 ** -16) * 3, (2.0 ** -16, 2.0 ** 16) * 3],
+                         ids=["up", "down", "zigzag", "zagzig"])
+@pytest.mark.parametrize("act,precision", cases(["lrelu", "relu"]))
+def test_layer_scale_power_of_two_changes_no_bit(torch_cuda, act, precision, scales):
+    """layer outputs rescaled by POWERS OF TWO (far inside the per-pose scale's 2^-40 .. 2^40): every weight and operand scale is an
+    exact power of two read off the data or off the packer's norms, so d and d d/d q of every pose are the unrescaled network's, word
+    for word (tests/test_depth_range_gpu.py asks the same of the runtime-planned kernels)"""
+    torch = torch_cuda
+    from posendf_amd import synth
+    base = synth.make_weights(0, 2.0, 0.1)
+    qn = synth.make_poses(256, seed=47, signed=True)
+    out = []
+    for sd in (base, _rescaled(base, scales)):
+        net = make_net(torch, act, sd=sd, precision=precision)
+        q = torch.from_numpy(qn).cuda().requires_grad_(True)
+        d = net(q, train=False)["dist_pred"]
+        (dq,) = torch.autograd.grad(d.sum(), q)
+        out.append((d.detach().view(torch.int32), dq.view(torch.int32)))
+    same = (out[0][0] == out[1][0]).all(dim=1) & (out[0][1] == out[1][1]).flatten(1).all(dim=1)
+    assert float(out[0][0].view(torch.float32).abs().max()) > 0 and bool(same.all()), (int((~same).sum()), torch.nonzero(~same).flatten()[:8].tolist())
+
+
 @pytest.mark.parametrize("beta", [1.0, 10.0, 1000.0])
 @pytest.mark.parametrize("precision", PRECISIONS)
 def test_softplus_beta_range(torch_cuda, precision, beta):
