@@ -274,7 +274,7 @@ typedef struct {
  *   o.base5.base4.base3.base2.base.struct_size = sizeof o;  o.root = placement;  o.fx = o.fy = 500.f;  o.cx = 320.f;  o.cy = 240.f;
  *   o.nu_rot = 0.02f;  o.nu_trans = 0.02f;  o.kp_flags = PNDF_KP_IMAGE;
  * Exactly the two entry points that take a pndf_project_options5 take it.  PNDF_ERR_BAD_ARG with a text that names the field, before
- * anything is launched or written: a struct_size that is none of the seven sizes, an unknown bit in kp_flags, a rho, nu_rot or nu_trans
+ * anything is launched or written: a struct_size that is none of the eight sizes, an unknown bit in kp_flags, a rho, nu_rot or nu_trans
  * that is negative or not finite, rho != 0 without PNDF_KP_IMAGE, with PNDF_KP_IMAGE an fx or fy that is not finite or <= 0 or a cx or
  * cy that is not finite, root == NULL with a positive root weight, a misaligned root, root overlapping q_out, with a positive root
  * weight root overlapping q_in, anchor, conf, kp_target, kp_conf or kp_energy; and what is refused in `base5`. */
@@ -309,7 +309,7 @@ typedef struct {
  * the 168-byte struct bit for bit and bone_scale is not written; with kp_target == NULL or nu == 0 it is the one with the 72-byte struct
  * and bone_scale is neither read nor written; steps == 0 leaves it untouched.  Exactly the two entry points that take a
  * pndf_project_options6 take it.  PNDF_ERR_BAD_ARG with a text that names the field, before anything is launched or written: a
- * struct_size that is none of the seven sizes, reserved3 != 0, an unknown bit in len_flags, a nu_len or kappa that is negative or not
+ * struct_size that is none of the eight sizes, reserved3 != 0, an unknown bit in len_flags, a nu_len or kappa that is negative or not
  * finite, a clamp that is not 0 < len_min <= len_max finite (both 0: none), a len_rate entry that is negative or not finite, bone_scale
  * == NULL with nu_len > 0, a misaligned bone_scale or len_rate, bone_scale overlapping q_out, q_in, root, anchor, conf, kp_target, kp_conf
  * or kp_energy; and what is refused in `base6`. */
@@ -324,6 +324,34 @@ typedef struct {
     uint32_t     len_flags;        /* 0 or PNDF_LEN_PER_POSE */
     uint32_t     reserved3;        /* 0 */
 } pndf_project_options7;           /* 208 bytes */
+
+/* The options with several cameras: the fit of pndf_project_options7 to pixels seen by V calibrated views of the same frame.  The root
+ * (c, s) places the tree in a WORLD frame, W_k = R_c P_k + s (root == NULL: W_k = P_k); view v is a row of 16 floats of `views`:
+ * fx, fy, cx, cy, then R_v [9] row-major (world -> camera), then t_v [3].  R_v need not be orthonormal: the gradient is exact for any
+ * matrix.  For one step, every operation rounded to fp32 on its own in the order written, keypoints in the outer loop and views
+ * 0 .. V-1 in the inner one:
+ *   C_vk = R_v W_k + t_v, every row (a0 b0 + a1 b1) + a2 b2, then the add.  View v takes no part for keypoint k when w_vk > 0 is false
+ *   (w_vk = kp_conf[b][v][k], or 1 when kp_conf == NULL) or when C_z > 0 is false; its target is then NOT READ and may hold anything.
+ *   A view that takes part: n, y', e, rho, psi and a_vk as PNDF_KP_IMAGE of the 168-byte struct states them, with view v's intrinsics;
+ *   its share w_vk [rho(e_u) + rho(e_v)] is added to the energy in that order, and aW_k = sum_v R_v^T a_vk is accumulated in view order
+ *   from 0.0f.  After the views aW_k takes the place of a_k in dE/ds, in the adjoint of R_c (with P_k), as R_c^T aW_k in the tree and in
+ *   h_{J+k} of the scales -- only when at least one view took part; otherwise the keypoint adds nothing anywhere.
+ * Joints, root, scales, masks, tracks, anchor and tol are those of the 208-byte struct.  With n_views = V > 0: kp_target is [B,V,K,2] in
+ * pixels, kp_conf [B,V,K]; kp_energy, root and bone_scale keep their shapes; kp_flags must have PNDF_KP_IMAGE; the intrinsics of `base6`
+ * are not read.  `views` is HOST memory in both entry points, read during the call.  With views == NULL and n_views == 0 the call is the
+ * one with the 208-byte struct bit for bit; with kp_target's term absent (nu == 0) it is the one with the 72-byte struct and neither the
+ * targets nor the confidences are read.  Exactly the two entry points that take a pndf_project_options7 take it.  PNDF_ERR_BAD_ARG with a
+ * text that names the field, before anything is launched or written: a struct_size that is none of the eight sizes, reserved4 != 0,
+ * n_views outside 0 .. PNDF_FK_MAX_VIEWS, exactly one of views == NULL and n_views == 0, n_views > 0 without PNDF_KP_IMAGE or without
+ * kp_target, a view whose fx or fy is not finite or <= 0, any other view entry that is not finite, a misaligned views; and what is
+ * refused in `base7` (the overlap checks of kp_target and kp_conf with their extents [B,V,K,2] and [B,V,K]). */
+enum { PNDF_FK_MAX_VIEWS = 8 };
+typedef struct {
+    pndf_project_options7 base7;   /* base7.base6.base5.base4.base3.base2.base.struct_size = sizeof(pndf_project_options8) */
+    const float* views;            /* [V,16] HOST memory in both entry points: fx, fy, cx, cy, R_v[9] row-major, t_v[3]; NULL: no views */
+    int32_t      n_views;          /* V, 0 or 1 .. PNDF_FK_MAX_VIEWS */
+    uint32_t     reserved4;        /* 0 */
+} pndf_project_options8;           /* 224 bytes */
 
 /* pndf_project with step options.  opt == NULL means the defaults, and with the defaults the call is pndf_project bit for
  * bit.  PNDF_ERR_BAD_ARG (text in pndf_last_error; nothing is launched or written) for a struct_size other than
@@ -353,9 +381,9 @@ int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* q_out, floa
                         const pndf_project_options* opt);      /* pndf_project_ex: same semantics, same validation; also takes a
                                                                   pndf_project_options2, a pndf_project_options3, a
                                                                   pndf_project_options4, a pndf_project_options5, a
-                                                                  pndf_project_options6 or a pndf_project_options7,
-                                                                  `observed` / `anchor` / `conf` / `kp_*` / `root` /
-                                                                  `bone_scale` in HOST memory */
+                                                                  pndf_project_options6, a pndf_project_options7 or a
+                                                                  pndf_project_options8, `observed` / `anchor` / `conf` /
+                                                                  `kp_*` / `root` / `bone_scale` in HOST memory */
 const char* pndf_cpu_last_error(pndf_cpu_handle h);   /* h may be NULL: last error of a failed pndf_cpu_create */
 
 /* Host-only weight packer (what pndf_load_weights uploads); needs no device.  Output sizes in floats come

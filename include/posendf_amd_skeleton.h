@@ -65,6 +65,12 @@
  * pndf_skel_enc_rev_len_kernel), which leaves them in S workspace rows; pndf_skel_len_step_kernel then sums them over the frames of every
  * group in a fixed order and steps the scales: one launch more per step and chunk than an image step, and only when nu_len > 0.
  *
+ * Several cameras -- pixels of the same frame in V calibrated views -- are the same two entry points with a pndf_project_options8
+ * (posendf_amd.h): views [V,16] in HOST memory (intrinsics, world -> camera rotation and translation per view), kp_target [B,V,K,2] and
+ * kp_conf [B,V,K] in device memory; the root places the tree in the world frame.  The view loop sits in the gradient's last kernel (its
+ * seventh instantiation, pndf_skel_enc_rev_views_kernel), which takes the view table by value; no launch more than a length-fitting
+ * step, and the workspace is what it was.
+ *
  * Still 21-joint: the second order (posendf_amd_second_order.h) only -- pndf_so_create refuses another joint count and
  * pndf_second_order_cpu a handle of another tree, and that is pinned.  2D keypoints with a camera run for any joint tree through
  * pndf_skel_project (above); pndf_keypoint_terms_grad and pndf_lbs_* are the SMPL body model's (vertices, shape, lens of ImageFit).
@@ -122,7 +128,8 @@ int pndf_skel_forward_grad(pndf_skel_handle h, const float* q, const float* grad
  * and kp_energy [B] (DEVICE memory; none may overlap q_out) and the HOST tables rest, kp_joint and kp_offset (read during the call) add the
  * keypoint term of weight nu to every free joint; kp_energy is E of the last iteration, evaluated before its update, as d_last is.  Or to
  * a pndf_project_options6 (root [B,7]: DEVICE memory) or a pndf_project_options7 (bone_scale [G,S]: DEVICE memory, len_rate [S]: HOST
- * memory, read during the call): seven sizes in all, every other one is refused. */
+ * memory, read during the call) or a pndf_project_options8 (views [V,16]: HOST memory, read during the call; kp_target [B,V,K,2] and
+ * kp_conf [B,V,K]: DEVICE memory): eight sizes in all, every other one is refused. */
 int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps,
                       const pndf_project_options* opt, void* workspace, int64_t workspace_bytes, void* stream);
 

@@ -31,7 +31,7 @@ def __getattr__(name):   # torch is imported lazily so that numpy-only users (or
     if name in ("KeypointFitting", "fit_keypoint_file"):
         from . import keypoint_fitting
         return getattr(keypoint_fitting, name)
-    if name in ("SkeletonPoseNDF", "SKELETONS", "skeleton_config", "forward_kinematics", "camera_project"):
+    if name in ("SkeletonPoseNDF", "SKELETONS", "skeleton_config", "forward_kinematics", "camera_project", "view_table"):
         from . import skeleton
         return getattr(skeleton, name)
     if name == "BodyModel":
@@ -46,5 +46,5 @@ def __getattr__(name):   # torch is imported lazily so that numpy-only users (or
 __all__ = ["PoseNDF", "gradient", "BodyModel", "PoseIndex", "Trainer", "PoseDataset", "OnlinePoseDataset", "OnlineOptions", "sample_noisy", "ImageFit", "PerspectiveCamera", "keypoint_term", "PoseCompletion", "PoseInterpolation",
            "PoseDenoising", "denoise_track_file",
            "KeypointFitting", "fit_keypoint_file",
-           "SkeletonPoseNDF", "SKELETONS", "skeleton_config", "forward_kinematics", "camera_project",
+           "SkeletonPoseNDF", "SKELETONS", "skeleton_config", "forward_kinematics", "camera_project", "view_table",
            "amass_config", "load_config", "synth"]

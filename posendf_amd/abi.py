@@ -91,6 +91,18 @@ class ProjectOptions7(ctypes.Structure):
                 ("len_min", c_float), ("len_max", c_float), ("len_flags", ctypes.c_uint32), ("reserved3", ctypes.c_uint32)]
 
 
+MAX_VIEWS = 8                                              # PNDF_FK_MAX_VIEWS (pndf_project_options8.n_views)
+
+
+class ProjectOptions8(ctypes.Structure):
+    """pndf_project_options8: the options with a mask, tracks, an observation, keypoints, a camera and bone lengths (`base7`, with
+    base7.base6.base5.base4.base3.base2.base.struct_size = 224) and several cameras -- `views` [V,16] in HOST memory (per view fx, fy, cx,
+    cy, the world -> camera rotation R_v [9] row-major and translation t_v [3]; None: no views), `n_views` V in 0 .. MAX_VIEWS.  With views
+    kp_target is [B,V,K,2] pixels and kp_conf [B,V,K], the root places the tree in the world frame and kp_flags must have KP_IMAGE;
+    taken by the two entry points that take a ProjectOptions7"""
+    _fields_ = [("base7", ProjectOptions7), ("views", c_void_p), ("n_views", c_int32), ("reserved4", ctypes.c_uint32)]
+
+
 class DenoiseWeights(ctypes.Structure):
     """pndf_denoise_weights: the loss weights of one outer iteration, evaluated"""
     _fields_ = [("prior_coef", c_float), ("prior_power", c_int32), ("temp_coef", c_float), ("data_coef", c_float)]
@@ -120,7 +132,7 @@ class PndfError(RuntimeError):
 _H = c_void_p                          # every handle type, and every `void* stream`
 _P = c_void_p                          # any other address: tensor data (an int from data_ptr(), or None), a callback, an out value
 _TENSORS = [POINTER(c_void_p), POINTER(c_int64), c_int]      # tensors, numel, n_tensors (host pointers in state-dict order)
-_OPT2 = c_void_p                       # `const pndf_project_options*` where it may point to a ProjectOptions, a ProjectOptions2 .. a ProjectOptions7 (byref of any)
+_OPT2 = c_void_p                       # `const pndf_project_options*` where it may point to a ProjectOptions, a ProjectOptions2 .. a ProjectOptions8 (byref of any)
 # ---- the header set, stated once: header of include/ -> {name: (restype, argtypes)} in the header's order; the headers in the order
 # they were added.  A new header is a file in include/, a table here and its declaration count in tests/test_cabi.py.
 DEBUG_HEADER = "posendf_amd_debug.h"      # the one header that lives in libposendf_amd_debug.so; every other one in the product library

@@ -7,7 +7,7 @@
 // SMPL table they compute what they did with the table fixed.  pndf_complete_cpu, pndf_interpolate_cpu and the second order stay 21-joint;
 // pndf_project_ex_cpu completes, interpolates, denoises and fits 3D or 2D keypoints for any joint tree (pndf_project_options2 /
 // pndf_project_options3 / pndf_project_options4 / pndf_project_options5 / pndf_project_options6), with the bone lengths as unknowns too
-// (pndf_project_options7).
+// (pndf_project_options7) and the pixels seen by several calibrated cameras (pndf_project_options8).
 //
 // Layout: poses are processed in blocks of PB = 32; inside a block every activation tensor is [feature][pose] so that the
 // inner loop of a layer runs over the 32 poses of the block (contiguous floats: one or two AVX-512 / four AVX2 registers)
@@ -414,12 +414,27 @@ struct KeypointTables {
 // the pose rests): it is read before the term and nothing else of the step reads it.
 // With the scales of a pndf_project_options7 (`len`) the term is pndf_fk_len_energy_grad on the row of the pose's group, and `hs` [S] takes
 // d E / d sigma of this frame; the scales step in len_step_cpu once every frame of the step has read them.
+// With the views of a pndf_project_options8 (`vw`) the term is pndf_fk_views_energy_grad: targets [V][K][2] and confidences [V][K] per pose,
+// with the scales or without.
 static float keypoint_grad_cpu(const PndfKeypoints& kp, const KeypointTables& tb, const int* parent, int nj, const float* q, int64_t pose,
                                float* gk, const PndfCameraTerm& cam = PndfCameraTerm(), float dist = 0.f, float tol = 0.f,
-                               const PndfLengths& len = PndfLengths(), float* hs = nullptr) {
+                               const PndfLengths& len = PndfLengths(), float* hs = nullptr, const PndfViews& vw = PndfViews()) {
     float W[PNDF_FK_ROWS * MAXJ + PNDF_MAX_SCALES];
     float E;
-    if (len.any()) {
+    if (vw.any()) {
+        float root[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, groot[7], stepped[7];
+        float* rt = cam.root ? cam.root + pose * 7 : nullptr;
+        if (rt) memcpy(root, rt, sizeof(root));
+        E = pndf_fk_views_energy_grad(q, nj, parent, tb.rest, kp.K, tb.kpj, tb.kpo, kp.target + pose * vw.V * kp.K * 2,
+                                      kp.conf ? kp.conf + pose * vw.V * kp.K : nullptr, rt != nullptr, root, cam.rho, vw.V, vw.table,
+                                      len.any() ? len.scale + (pose / len.group) * len.S : nullptr, groot, W, 1);
+        if (cam.moves()) {
+            pndf_fk_root_step(root, groot, cam.nu_rot, cam.nu_trans, dist, tol, stepped);
+            memcpy(rt, stepped, sizeof(stepped));
+        }
+        if (len.any())
+            for (int i = 0; i < len.S; ++i) hs[i] = W[pndf_fk_len_row(nj, i)];
+    } else if (len.any()) {
         const PndfFkCamera fc{cam.fx, cam.fy, cam.cx, cam.cy, cam.rho, cam.image ? 1 : 0};
         float root[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, groot[7], stepped[7];
         float* rt = cam.root ? cam.root + pose * 7 : nullptr;
@@ -495,7 +510,7 @@ static void project_step_cpu(float* q, const float* dq, float d, const pndf_proj
 static int project_loop_cpu(pndf_cpu_handle h, const float* q_in, const uint32_t* observed, float* q_out, float* d_last, int64_t B,
                             int steps, const pndf_project_options& o, const PndfData& data = PndfData(),
                             const PndfKeypoints& kp = PndfKeypoints(), const PndfCameraTerm& cam = PndfCameraTerm(),
-                            const PndfLengths& len = PndfLengths()) {
+                            const PndfLengths& len = PndfLengths(), const PndfViews& vw = PndfViews()) {
     const int NQ = h->nq();
     KeypointTables tb;
     if (kp.any()) pndf_fill_keypoint_tables(tb, kp, h->net.nj);
@@ -507,7 +522,7 @@ static int project_loop_cpu(pndf_cpu_handle h, const float* q_in, const uint32_t
         for (int s = 0; s < steps; ++s) {
             forward_grad_block(*h, qb, nb, nullptr, dd, dqb, true, S);
             for (int p = 0; p < nb; ++p) {
-                if (kp.any()) ee[p] = keypoint_grad_cpu(kp, tb, h->net.parent, h->net.nj, qb + p * NQ, p0 + p, gk, cam, dd[p], o.tol, len, hs);
+                if (kp.any()) ee[p] = keypoint_grad_cpu(kp, tb, h->net.parent, h->net.nj, qb + p * NQ, p0 + p, gk, cam, dd[p], o.tol, len, hs, vw);
                 if (len.moves()) len_step_cpu(len, p0 + p, hs, dd + p, o.tol);      // (without tracks every pose is its own group)
                 project_step_cpu(qb + p * NQ, dqb + p * NQ, dd[p], o, observed ? observed[p0 + p] : 0u, h->net.nj,
                                  data.anchor ? data.anchor + (p0 + p) * NQ : nullptr, data.conf ? data.conf + (p0 + p) * h->net.nj : nullptr, data.mu,
@@ -547,7 +562,8 @@ extern "C" int pndf_complete_cpu(pndf_cpu_handle h, const float* q_in, const uin
 static int track_loop_cpu(pndf_cpu_handle h, const float* a, int64_t a_stride, const float* b, int64_t b_stride, int fill,
                           const uint32_t* observed, float* track_out, float* d_last, int64_t P, int32_t T, int steps, float lambda,
                           const pndf_project_options& o, const PndfData& data = PndfData(), const PndfKeypoints& kp = PndfKeypoints(),
-                          const PndfCameraTerm& cam = PndfCameraTerm(), const PndfLengths& len = PndfLengths()) {
+                          const PndfCameraTerm& cam = PndfCameraTerm(), const PndfLengths& len = PndfLengths(),
+                          const PndfViews& vw = PndfViews()) {
     const int nj = h->net.nj;
     const int64_t nq = h->nq(), B = P * T;
     int rc = PNDF_OK;
@@ -580,7 +596,7 @@ static int track_loop_cpu(pndf_cpu_handle h, const float* a, int64_t a_stride, c
                 const uint32_t held = (nbr != 3 && !data.free_ends) ? ~0u : (observed ? observed[f] : 0u);
                 float gk[4 * MAXJ];
                 if (kp.any()) ee[f] = keypoint_grad_cpu(kp, tb, h->net.parent, nj, cur + f * nq, f, gk, cam, dd[f], o.tol, len,
-                                                        len.any() ? hs.data() + f * len.S : nullptr);
+                                                        len.any() ? hs.data() + f * len.S : nullptr, vw);
                 for (int j = 0; j < nj; ++j) {
                     const int64_t i = (f * nj + j) * 4;
                     float u[4];
@@ -616,7 +632,8 @@ extern "C" int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* 
     PndfKeypoints kp;              // a pndf_project_options5 the 3D keypoints besides (host memory): keypoint fitting for any joint tree
     PndfCameraTerm cam;            // a pndf_project_options6 the camera and the root besides (host memory): image fitting for any joint tree
     PndfLengths len;               // a pndf_project_options7 the bone lengths besides (host memory): one row of scales per track or per pose
-    if (const char* why = pndf_check_project_options7(opt, B, h->net.nj, o, observed, tracks, data, kp, cam, len)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    PndfViews vw;                  // a pndf_project_options8 the views besides (host memory): pixels of the same frame in several cameras
+    if (const char* why = pndf_check_project_options8(opt, B, h->net.nj, o, observed, tracks, data, kp, cam, len, vw)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (!tracks.frames && !observed && !data.any() && !kp.any() && !kp.energy && pndf_project_options_plain(o))
         return pndf_project_cpu(h, q_in, q_out, d_last, B, steps);
     if (int rc = check(h, q_in, B)) return rc;
@@ -625,14 +642,14 @@ extern "C" int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* 
     if (const char* why = pndf_check_keypoints_apart(kp, q_out, B, h->net.nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (const char* why = pndf_check_root_apart(cam, data, kp, q_in, q_out, B, h->net.nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (const char* why = pndf_check_lengths_apart(len, cam, data, kp, q_in, q_out, B, h->net.nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
-    if (!tracks.frames) return project_loop_cpu(h, q_in, observed, q_out, d_last, B, steps, o, data, kp, cam, len);
+    if (!tracks.frames) return project_loop_cpu(h, q_in, observed, q_out, d_last, B, steps, o, data, kp, cam, len, vw);
     if (B == 0) return PNDF_OK;
     const int64_t nq = h->nq(), T = tracks.frames;
     if ((uintptr_t)q_in < (uintptr_t)(q_out + B * nq) && (uintptr_t)q_out < (uintptr_t)(q_in + B * nq))
         return pndf_fail(h, PNDF_ERR_BAD_ARG, "q_out must not overlap q_in when pndf_project_options3.frames > 0: a step reads the neighbour "
                                               "frames of its input");
     return track_loop_cpu(h, q_in, T * nq, q_in + (T - 1) * nq, T * nq, tracks.fill, observed, q_out, d_last, B / T, (int32_t)T, steps,
-                          tracks.lambda, o, data, kp, cam, len);
+                          tracks.lambda, o, data, kp, cam, len, vw);
 }
 
 // Host twin of pndf_interpolate (include/posendf_amd_interpolation.h): track_loop_cpu on the 21-joint table; with lambda == 0 this is

@@ -534,3 +534,151 @@ PNDF_HD float pndf_fk_len_step(float sigma, float H, int64_t n, float w, float k
     if (len_min == 0.f && len_max == 0.f) return v;
     return v < len_min ? len_min : (v > len_max ? len_max : v);
 }
+
+// ---- Several cameras of a pndf_project_options8 (DESIGN.md section 2j "Several cameras"): the image term above seen by V calibrated
+// views of the same frame.  Stated once beside the other terms, whose functions above stay as they are (their bits are pinned).  The
+// root places the tree in a WORLD frame, W_k = R_c P_k + s (without a root W_k = P_k, no arithmetic: what pndf_fk_len_keypoint computes
+// as C); view v is a row of 16 floats, fx fy cx cy, R_v [9] row-major (world -> camera), t_v [3], and C_vk = R_v W_k + t_v, rows as
+// pndf_fk_dot3, then the add.  Keypoints in the outer loop, views 0 .. V-1 in the inner one:
+//   a view takes no part for a keypoint when w_vk > 0 is false (w_vk = conf [v][k], or 1) or when C_z > 0 is false; its target
+//   Y [v][k][2] is then not read.  A view that takes part gives e, rho, psi and a_vk as pndf_fk_camera_keypoint does with its own
+//   intrinsics; its energy share is added to the accumulator in view order, and aW_k = sum_v R_v^T a_vk is accumulated in view order
+//   from 0.0f.  After the views aW_k takes the place of a_k: in as and AR (with P_k), as R_c^T aW_k in ap and M, and in h_{J+k} -- only
+//   when at least one view took part; otherwise the keypoint adds nothing anywhere (h_{J+k} = 0).
+// The view table is uniform over the poses (on the device: values of the kernel's argument struct, read with scalar loads; the view
+// loop has a uniform trip count and nothing per lane is indexed by the view).  sigma may be null: every scale 1.0f, no product.
+constexpr int PNDF_FK_VIEW_FLOATS = 16;      // (at most PNDF_FK_MAX_VIEWS rows: include/posendf_amd.h)
+
+PNDF_HD float pndf_fk_views_keypoint(int a, const float* o, bool scaled, float sg, int k, int K, const float* Y, const float* conf, float acc,
+                                     float rho, int V, const float* views, bool has_root, const float* Rc, const float* s, float* as,
+                                     float* AR, float* W, int64_t ld, int nj, float* h) {
+#pragma clang fp contract(off)
+    const float* Ga = W + (int64_t)pndf_fk_G(nj, a) * ld;
+    const float* pa = W + (int64_t)pndf_fk_p(nj, a) * ld;
+    float* Ma = W + (int64_t)pndf_fk_M(nj, a) * ld;
+    float* aa = W + (int64_t)pndf_fk_ap(nj, a) * ld;
+    float os[3], P[3], Wd[3], vu[3];
+    *h = 0.f;
+    for (int x = 0; x < 3; ++x) os[x] = scaled ? sg * o[x] : o[x];
+    for (int x = 0; x < 3; ++x) {
+        const float v = pndf_fk_dot3(Ga[(3 * x) * ld], os[0], Ga[(3 * x + 1) * ld], os[1], Ga[(3 * x + 2) * ld], os[2]);
+        P[x] = pa[x * ld] + v;
+        vu[x] = pndf_fk_dot3(Ga[(3 * x) * ld], o[0], Ga[(3 * x + 1) * ld], o[1], Ga[(3 * x + 2) * ld], o[2]);
+    }
+    if (has_root) {
+        for (int x = 0; x < 3; ++x) {
+            const float v = pndf_fk_dot3(Rc[3 * x], P[0], Rc[3 * x + 1], P[1], Rc[3 * x + 2], P[2]);
+            Wd[x] = v + s[x];
+        }
+    } else {
+        for (int x = 0; x < 3; ++x) Wd[x] = P[x];
+    }
+    float aW[3] = {0.f, 0.f, 0.f};
+    bool seen = false;
+    for (int v = 0; v < V; ++v) {
+        const float* vw = views + PNDF_FK_VIEW_FLOATS * v;
+        const float w = conf ? conf[v * K + k] : 1.0f;
+        if (!(w > 0.f)) continue;
+        float C[3];
+        for (int x = 0; x < 3; ++x) {
+            const float d = pndf_fk_dot3(vw[4 + 3 * x], Wd[0], vw[5 + 3 * x], Wd[1], vw[6 + 3 * x], Wd[2]);
+            C[x] = d + vw[13 + x];
+        }
+        if (!(C[2] > 0.f)) continue;      // behind this camera, in its plane, or NaN: no energy, no gradient from this view
+        const float* y = Y + 2 * (v * K + k);
+        const float nu = C[0] / C[2], nv = C[1] / C[2];
+        const float du = y[0] - vw[2], dv = y[1] - vw[3];
+        const float yu = du / vw[0], yv = dv / vw[1];
+        const float eu = nu - yu, ev = nv - yv;
+        float pu, pv;
+        const float ru = pndf_fk_robust(eu, rho, &pu);
+        const float rv = pndf_fk_robust(ev, rho, &pv);
+        const float rs = ru + rv;
+        const float e = w * rs;
+        acc = acc + e;
+        const float tu = pu / C[2], tv = pv / C[2];
+        const float un = pu * nu, vn = pv * nv;
+        const float sn = un + vn;
+        const float tz = -(sn / C[2]);
+        const float a0 = w * tu, a1 = w * tv, a2 = w * tz;
+        for (int x = 0; x < 3; ++x) {      // R_v^T a
+            const float d = pndf_fk_dot3(vw[4 + x], a0, vw[7 + x], a1, vw[10 + x], a2);
+            aW[x] = aW[x] + d;
+        }
+        seen = true;
+    }
+    if (!seen) return acc;
+    if (has_root)
+        for (int x = 0; x < 3; ++x) {
+            as[x] = as[x] + aW[x];
+            for (int y = 0; y < 3; ++y) {
+                const float m = aW[x] * P[y];
+                AR[3 * x + y] = AR[3 * x + y] + m;
+            }
+        }
+    float wr[3];
+    for (int x = 0; x < 3; ++x) {
+        wr[x] = has_root ? pndf_fk_dot3(Rc[x], aW[0], Rc[3 + x], aW[1], Rc[6 + x], aW[2]) : aW[x];      // R_c^T aW
+        aa[x * ld] = aa[x * ld] + wr[x];
+        for (int y = 0; y < 3; ++y) {
+            const float m = wr[x] * os[y];
+            Ma[(3 * x + y) * ld] = Ma[(3 * x + y) * ld] + m;
+        }
+    }
+    *h = pndf_fk_dot3(wr[0], vu[0], wr[1], vu[1], wr[2], vu[2]);
+    return acc;
+}
+
+// The whole term of one pose under V views: pndf_fk_len_energy_grad's arguments with Y [V][K][2] pixels, conf [V][K] or null (ones),
+// views [V][16] and sigma [nj + K] or null (all ones).  Leaves d E / d Q_j in the rows pndf_fk_grad_row(nj, j), d E / d sigma_i in the rows
+// pndf_fk_len_row(nj, i) (only with sigma: without scales those rows are neither computed for the joints nor written), d E / d (c, s) in
+// groot, and returns E.
+PNDF_HD float pndf_fk_views_energy_grad(const float* q, int nj, const int* parent, const float* rest, int K, const int32_t* kp_joint,
+                                        const float* kp_offset, const float* Y, const float* conf, bool has_root, const float* root,
+                                        float rho, int V, const float* views, const float* sigma, float* groot, float* W, int64_t ld) {
+#pragma clang fp contract(off)
+    const bool scaled = sigma != nullptr;
+    for (int j = 0; j < nj; ++j) {
+        float ts[3];
+        for (int x = 0; x < 3; ++x) ts[x] = scaled ? sigma[j] * rest[3 * j + x] : rest[3 * j + x];
+        pndf_fk_joint(q + 4 * j, parent[j], ts, W, ld, nj, j);
+    }
+    float ch[4] = {0.f, 0.f, 0.f, 0.f}, Rc[9], s[3] = {0.f, 0.f, 0.f}, n = 0.f;
+    float as[3] = {0.f, 0.f, 0.f}, AR[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < 9; ++i) Rc[i] = 0.f;
+    if (has_root) {
+        float c[4];
+        for (int i = 0; i < 4; ++i) c[i] = root[i];
+        for (int x = 0; x < 3; ++x) s[x] = root[4 + x];
+        n = pndf_fk_unit(c, ch);
+        pndf_fk_rot(ch, Rc);
+    }
+    float acc = 0.f;
+    for (int k = 0; k < K; ++k) {
+        float h = 0.f;
+        acc = pndf_fk_views_keypoint(kp_joint[k], kp_offset + 3 * k, scaled, scaled ? sigma[nj + k] : 1.0f, k, K, Y, conf, acc, rho, V, views,
+                                     has_root, Rc, s, as, AR, W, ld, nj, &h);
+        if (scaled) W[(int64_t)pndf_fk_len_row(nj, nj + k) * ld] = h;      // (without scales nobody reads the rows of h: they are not written)
+    }
+    for (int j = nj - 1; j >= 0; --j) {
+        const float* t = rest + 3 * j;
+        const float* aj = W + (int64_t)pndf_fk_ap(nj, j) * ld;
+        float ts[3], v[3] = {0.f, 0.f, 0.f};
+        for (int x = 0; x < 3; ++x) ts[x] = scaled ? sigma[j] * t[x] : t[x];
+        if (scaled) {
+            if (parent[j] < 0) {
+                for (int x = 0; x < 3; ++x) v[x] = t[x];
+            } else {
+                const float* Gp = W + (int64_t)pndf_fk_G(nj, parent[j]) * ld;
+                for (int x = 0; x < 3; ++x) v[x] = pndf_fk_dot3(Gp[(3 * x) * ld], t[0], Gp[(3 * x + 1) * ld], t[1], Gp[(3 * x + 2) * ld], t[2]);
+            }
+            W[(int64_t)pndf_fk_len_row(nj, j) * ld] = pndf_fk_dot3(aj[0], v[0], aj[ld], v[1], aj[2 * ld], v[2]);
+        }
+        pndf_fk_joint_rev(q + 4 * j, parent[j], ts, W, ld, nj, j);
+    }
+    if (has_root) {
+        pndf_fk_quat_adj(AR, ch, n, groot);
+        for (int x = 0; x < 3; ++x) groot[4 + x] = as[x];
+    }
+    return 0.5f * acc;
+}

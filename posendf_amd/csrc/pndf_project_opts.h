@@ -180,6 +180,7 @@ struct PndfKeypoints {
     const float* named_conf = nullptr;
     int32_t named_K = 0;
     int32_t dims = 3;                     // floats per target: 2 with the PNDF_KP_IMAGE of a pndf_project_options6
+    int32_t views = 1;                    // V of a pndf_project_options8: the targets are [B,V,K,dims], the confidences [B,V,K]
     bool any() const { return target != nullptr; }
 };
 
@@ -256,9 +257,9 @@ inline const char* pndf_check_project_options5(const pndf_project_options* opt, 
 inline const char* pndf_check_keypoints_apart(const PndfKeypoints& kp, const float* q_out, int64_t B, int nj) {
     if (B <= 0 || !q_out) return nullptr;
     const uintptr_t o0 = (uintptr_t)q_out, o1 = (uintptr_t)(q_out + B * nj * 4);
-    if (kp.named_target && (uintptr_t)kp.named_target < o1 && o0 < (uintptr_t)(kp.named_target + B * kp.named_K * kp.dims))
+    if (kp.named_target && (uintptr_t)kp.named_target < o1 && o0 < (uintptr_t)(kp.named_target + B * kp.views * kp.named_K * kp.dims))
         return "pndf_project_options5.kp_target must not overlap q_out: every step reads the targets";
-    if (kp.named_conf && (uintptr_t)kp.named_conf < o1 && o0 < (uintptr_t)(kp.named_conf + B * kp.named_K))
+    if (kp.named_conf && (uintptr_t)kp.named_conf < o1 && o0 < (uintptr_t)(kp.named_conf + B * kp.views * kp.named_K))
         return "pndf_project_options5.kp_conf must not overlap q_out: every step reads the confidences";
     if (kp.energy && (uintptr_t)kp.energy < o1 && o0 < (uintptr_t)(kp.energy + B))
         return "pndf_project_options5.kp_energy must not overlap q_out";
@@ -354,8 +355,8 @@ inline const char* pndf_check_root_apart(const PndfCameraTerm& cam, const PndfDa
     if (meets(q_in, B * nj * 4)) return "pndf_project_options6.root must not overlap q_in when nu_rot or nu_trans is positive: every step writes the root";
     if (meets(data.anchor, B * nj * 4)) return "pndf_project_options6.root must not overlap pndf_project_options4.anchor when nu_rot or nu_trans is positive";
     if (meets(data.conf, (int64_t)B * nj)) return "pndf_project_options6.root must not overlap pndf_project_options4.conf when nu_rot or nu_trans is positive";
-    if (meets(kp.named_target, B * kp.named_K * kp.dims)) return "pndf_project_options6.root must not overlap kp_target when nu_rot or nu_trans is positive";
-    if (meets(kp.named_conf, (int64_t)B * kp.named_K)) return "pndf_project_options6.root must not overlap kp_conf when nu_rot or nu_trans is positive";
+    if (meets(kp.named_target, B * kp.views * kp.named_K * kp.dims)) return "pndf_project_options6.root must not overlap kp_target when nu_rot or nu_trans is positive";
+    if (meets(kp.named_conf, (int64_t)B * kp.views * kp.named_K)) return "pndf_project_options6.root must not overlap kp_conf when nu_rot or nu_trans is positive";
     if (meets(kp.energy, B)) return "pndf_project_options6.root must not overlap kp_energy when nu_rot or nu_trans is positive";
     return nullptr;
 }
@@ -460,9 +461,78 @@ inline const char* pndf_check_lengths_apart(const PndfLengths& len, const PndfCa
     if (meets(cam.named_root, B * 7)) return "pndf_project_options7.bone_scale must not overlap pndf_project_options6.root";
     if (meets(data.anchor, B * nj * 4)) return "pndf_project_options7.bone_scale must not overlap pndf_project_options4.anchor";
     if (meets(data.conf, (int64_t)B * nj)) return "pndf_project_options7.bone_scale must not overlap pndf_project_options4.conf";
-    if (meets(kp.named_target, B * kp.named_K * kp.dims)) return "pndf_project_options7.bone_scale must not overlap kp_target";
-    if (meets(kp.named_conf, (int64_t)B * kp.named_K)) return "pndf_project_options7.bone_scale must not overlap kp_conf";
+    if (meets(kp.named_target, B * kp.views * kp.named_K * kp.dims)) return "pndf_project_options7.bone_scale must not overlap kp_target";
+    if (meets(kp.named_conf, (int64_t)B * kp.views * kp.named_K)) return "pndf_project_options7.bone_scale must not overlap kp_conf";
     if (meets(kp.energy, B)) return "pndf_project_options7.bone_scale must not overlap kp_energy";
+    return nullptr;
+}
+
+// The views of a pndf_project_options8, validated and copied (the table is host memory that is read during the call only): without a
+// keypoint term (nu == 0) V stays 0 and the call is the one without views.
+struct PndfViews {
+    int32_t V = 0;
+    float table[PNDF_FK_MAX_VIEWS * 16];      // row v: fx, fy, cx, cy, R_v [9] row-major, t_v [3]
+    bool any() const { return V > 0; }
+};
+
+// The checker of the same two entry points for all eight structs: a pndf_project_options8 brings the views besides.  Returns nullptr and
+// fills `out`, `observed`, `tracks`, `data`, `kp` (with the views' count in kp.views, which sizes kp_target and kp_conf in the overlap
+// checks that follow), `cam`, `len` and `vw`, or the reason the struct is refused.
+inline const char* pndf_check_project_options8(const pndf_project_options* opt, int64_t B, int nj, pndf_project_options& out,
+                                               const uint32_t*& observed, PndfTracks& tracks, PndfData& data, PndfKeypoints& kp,
+                                               PndfCameraTerm& cam, PndfLengths& len, PndfViews& vw) {
+    vw.V = 0;
+    for (int i = 0; i < PNDF_FK_MAX_VIEWS * 16; ++i) vw.table[i] = 0.f;
+    if (!opt || opt->struct_size != sizeof(pndf_project_options8)) {
+        const char* why = pndf_check_project_options7(opt, B, nj, out, observed, tracks, data, kp, cam, len);
+        if (why && opt && opt->struct_size != sizeof(pndf_project_options) && opt->struct_size != sizeof(pndf_project_options2) &&
+            opt->struct_size != sizeof(pndf_project_options3) && opt->struct_size != sizeof(pndf_project_options4) &&
+            opt->struct_size != sizeof(pndf_project_options5) && opt->struct_size != sizeof(pndf_project_options6) &&
+            opt->struct_size != sizeof(pndf_project_options7))
+            return "pndf_project_options.struct_size is none of sizeof(pndf_project_options), sizeof(pndf_project_options2), "
+                   "sizeof(pndf_project_options3), sizeof(pndf_project_options4), sizeof(pndf_project_options5), "
+                   "sizeof(pndf_project_options6), sizeof(pndf_project_options7) and sizeof(pndf_project_options8): fill the struct with "
+                   "pndf_default_project_options";
+        return why;
+    }
+    const pndf_project_options8* o8 = (const pndf_project_options8*)opt;
+    // what the struct says of itself first: a refusal here has filled nothing
+    out = pndf_project_options();
+    observed = nullptr;
+    tracks = PndfTracks();
+    data = PndfData();
+    kp = PndfKeypoints();
+    cam = PndfCameraTerm();
+    if (o8->reserved4 != 0u) return "pndf_project_options8.reserved4 must be 0";
+    if (o8->n_views < 0 || o8->n_views > PNDF_FK_MAX_VIEWS) return "pndf_project_options8.n_views must lie in 0 .. 8";
+    if ((uintptr_t)o8->views & 3) return "pndf_project_options8.views must be 4-byte aligned";
+    if (!o8->views && o8->n_views != 0) return "pndf_project_options8.views must not be NULL when n_views is positive";
+    if (o8->views && o8->n_views == 0) return "pndf_project_options8.n_views must be positive when views is not NULL";
+    if (o8->n_views > 0) {
+        if (!(o8->base7.base6.kp_flags & PNDF_KP_IMAGE)) return "pndf_project_options8.n_views is positive, so pndf_project_options6.kp_flags must have PNDF_KP_IMAGE";
+        if (!o8->base7.base6.base5.kp_target) return "pndf_project_options8.n_views is positive, so pndf_project_options5.kp_target must not be NULL";
+        for (int32_t v = 0; v < o8->n_views; ++v) {
+            const float* r = o8->views + 16 * v;
+            if (!isfinite(r[0]) || !(r[0] > 0.f)) return "pndf_project_options8.views has a view whose fx is not finite and positive";
+            if (!isfinite(r[1]) || !(r[1] > 0.f)) return "pndf_project_options8.views has a view whose fy is not finite and positive";
+            for (int i = 2; i < 16; ++i)
+                if (!isfinite(r[i])) return "pndf_project_options8.views has an entry that is not finite";
+        }
+    }
+    pndf_project_options7 base7 = o8->base7;
+    base7.base6.base5.base4.base3.base2.base.struct_size = (uint32_t)sizeof(pndf_project_options7);
+    if (o8->n_views > 0) {      // the intrinsics of base6 are not read: whatever they hold is not refused
+        base7.base6.fx = base7.base6.fy = 1.f;
+        base7.base6.cx = base7.base6.cy = 0.f;
+    }
+    if (const char* why = pndf_check_project_options7(&base7.base6.base5.base4.base3.base2.base, B, nj, out, observed, tracks, data, kp, cam, len)) return why;
+    if (o8->n_views > 0) {
+        kp.views = o8->n_views;
+        if (kp.any()) {
+            vw.V = o8->n_views;
+            for (int i = 0; i < 16 * o8->n_views; ++i) vw.table[i] = o8->views[i];
+        }
+    }
     return nullptr;
 }
 

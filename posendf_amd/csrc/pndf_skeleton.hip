@@ -31,7 +31,8 @@
 //                              pndf_skel_enc_rev_image_kernel: pndf_fk.h's camera term in place of the 3D term and the root's own step;
 //                              with the bone lengths of a pndf_project_options7 its sixth instantiation pndf_skel_enc_rev_len_kernel:
 //                              the camera term on the tree scaled by the row of the lane's group, d E / d sigma of the frame left in
-//                              S workspace rows
+//                              S workspace rows; with the views of a pndf_project_options8 its seventh instantiation
+//                              pndf_skel_enc_rev_views_kernel: the same, with the pixels of V cameras in front of the root's frame
 //   pndf_skel_len_step_kernel  once per chunk and step behind that kernel (only when nu_len > 0): the sum of those rows over the frames
 //                              of every group in pndf_fk.h's order and the step of the scales in place
 //   pndf_skel_fill_kernel      the fill of a track from its two end frames, once per chunk in front of the steps
@@ -130,6 +131,14 @@ struct SkLenArgs : SkImageArgs {
     int group;                // frames per group: lane c reads row c / group
 };
 
+// SkLenArgs with the views of a pndf_project_options8 (SK_PROJECT), which pndf_skel_enc_rev_views_kernel alone takes, derived for the same
+// reason.  The table is a value of the argument struct: wave-uniform, read with scalar loads in a loop of uniform trip count.
+struct SkViewsArgs : SkLenArgs {
+    int V;                                                     // views, 1 .. PNDF_FK_MAX_VIEWS; 0: none
+    float views[PNDF_FK_MAX_VIEWS * PNDF_FK_VIEW_FLOATS];      // row v: fx, fy, cx, cy, R_v [9] row-major, t_v [3]
+};
+static_assert(sizeof(SkViewsArgs) <= 4096, "a kernel's arguments are at most 4,096 bytes");
+
 // What pndf_skel_len_step_kernel takes: the rows h [S][ld] the reverse left, the chunk's distance row and the scales to step in place
 struct SkLenStepArgs {
     float* bone_scale;        // [G][S]
@@ -220,12 +229,15 @@ extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_fwd_kernel(SkArg
 // place of the 3D term, and the root's own step -- a lane reads its root row before the term and writes it after the joints.
 // SK_REV_LEN is the instantiation of a pndf_project_options7 with scales: SK_REV_IMAGE with pndf_fk.h's scaled term, which reads the row
 // of the lane's group and leaves d E / d sigma of the lane's frame in the rows behind the tree's; the scales step in their own kernel.
-enum { SK_REV_PLAIN = 0, SK_REV_TRACKS = 1, SK_REV_DENOISE = 2, SK_REV_FIT = 3, SK_REV_IMAGE = 4, SK_REV_LEN = 5 };
+// SK_REV_VIEWS is the instantiation of a pndf_project_options8 with views: SK_REV_LEN with pndf_fk.h's several-camera term (targets
+// [V][K][2] and confidences [V][K] per lane); the group's row of scales may be missing (all ones).
+enum { SK_REV_PLAIN = 0, SK_REV_TRACKS = 1, SK_REV_DENOISE = 2, SK_REV_FIT = 3, SK_REV_IMAGE = 4, SK_REV_LEN = 5, SK_REV_VIEWS = 6 };
 template <int KIND, class Args>
 __device__ __forceinline__ void skel_enc_rev(const Args& e) {
     constexpr bool TRACKS = KIND == SK_REV_TRACKS;
     constexpr bool LEN = KIND == SK_REV_LEN;
-    constexpr bool IMAGE = KIND == SK_REV_IMAGE || LEN;
+    constexpr bool VIEWS = KIND == SK_REV_VIEWS;
+    constexpr bool IMAGE = KIND == SK_REV_IMAGE || LEN || VIEWS;
     constexpr bool FIT = KIND == SK_REV_FIT || IMAGE;
     constexpr bool DENOISE = KIND == SK_REV_DENOISE || FIT;
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -270,7 +282,11 @@ __device__ __forceinline__ void skel_enc_rev(const Args& e) {
         if (e.root)
 #pragma unroll
             for (int i = 0; i < 7; ++i) root[i] = e.root[c * 7 + i];
-        if constexpr (LEN)
+        if constexpr (VIEWS)
+            energy = pndf_fk_views_energy_grad(q, e.nj, e.parent, e.rest, e.K, e.kpj, e.kpo, e.kp_target + c * (e.V * e.K * 2),
+                                               e.kp_conf ? e.kp_conf + c * (e.V * e.K) : nullptr, e.root != nullptr, root, e.cam.rho, e.V,
+                                               e.views, e.bone_scale ? e.bone_scale + (c / e.group) * e.S : nullptr, groot, e.fk + c, e.ld);
+        else if constexpr (LEN)
             energy = pndf_fk_len_energy_grad(q, e.nj, e.parent, e.rest, e.K, e.kpj, e.kpo, e.kp_target + c * (e.K * (e.cam.image ? 2 : 3)),
                                              e.kp_conf ? e.kp_conf + c * e.K : nullptr, e.root != nullptr, root, e.cam,
                                              e.bone_scale + (c / e.group) * e.S, groot, e.fk + c, e.ld);
@@ -354,6 +370,7 @@ extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_denoise_kern
 extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_fit_kernel(SkFitArgs e) { skel_enc_rev<SK_REV_FIT>(e); }
 extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_image_kernel(SkImageArgs e) { skel_enc_rev<SK_REV_IMAGE>(e); }
 extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_len_kernel(SkLenArgs e) { skel_enc_rev<SK_REV_LEN>(e); }
+extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_views_kernel(SkViewsArgs e) { skel_enc_rev<SK_REV_VIEWS>(e); }
 
 // The step of the scales of a chunk (pndf_fk.h: pndf_fk_len_group_sum's order, pndf_fk_len_step).  Frames per group n <= 64: lanes own
 // (group, scale) pairs and sum their frames in order.  n > 64: one workgroup per (group, scale), lane b sums block b of 64 frames, lane 0
@@ -492,7 +509,7 @@ SkLayout sk_layout(const pndf_skel_plan* h, int64_t B) {
 }
 
 // One evaluation of a chunk of n poses at `q`: the 2 + 2 L launches (the forward alone: 1 + L and the copy of the output row)
-void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const SkLenArgs& e, hipStream_t st) {
+void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const SkViewsArgs& e, hipStream_t st) {
     const int n = (int)e.n;
     TrunkWeights w{};
     TrunkBuffers b{};
@@ -503,6 +520,7 @@ void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const S
     const SkDenoiseArgs& denoise = e;
     const SkFitArgs& fit = e;
     const SkImageArgs& image = e;
+    const SkLenArgs& lengths = e;
     hipLaunchKernelGGL(pndf_skel_enc_fwd_kernel, dim3(blocks(n)), dim3(256), 0, st, plain);
     trunk_forward(SK_GEMM, *h, w, b, st);
     if (e.mode == SK_FORWARD) {
@@ -510,7 +528,8 @@ void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const S
         return;
     }
     trunk_reverse(SK_GEMM, *h, w, b, st);      // grad_out scales the result in the encoder's reverse
-    if (e.mode == SK_PROJECT && e.kp_target && e.bone_scale) hipLaunchKernelGGL(pndf_skel_enc_rev_len_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
+    if (e.mode == SK_PROJECT && e.kp_target && e.V > 0) hipLaunchKernelGGL(pndf_skel_enc_rev_views_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
+    else if (e.mode == SK_PROJECT && e.kp_target && e.bone_scale) hipLaunchKernelGGL(pndf_skel_enc_rev_len_kernel, dim3(blocks(n)), dim3(256), 0, st, lengths);
     else if (e.mode == SK_PROJECT && e.kp_target && (e.root || e.cam.image)) hipLaunchKernelGGL(pndf_skel_enc_rev_image_kernel, dim3(blocks(n)), dim3(256), 0, st, image);
     else if (e.mode == SK_PROJECT && e.kp_target) hipLaunchKernelGGL(pndf_skel_enc_rev_fit_kernel, dim3(blocks(n)), dim3(256), 0, st, fit);
     else if (e.mode == SK_PROJECT && (e.anchor || e.flags)) hipLaunchKernelGGL(pndf_skel_enc_rev_denoise_kernel, dim3(blocks(n)), dim3(256), 0, st, denoise);
@@ -518,8 +537,8 @@ void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const S
     else hipLaunchKernelGGL(pndf_skel_enc_rev_kernel, dim3(blocks(n)), dim3(256), 0, st, plain);
 }
 
-SkLenArgs sk_args(const pndf_skel_plan* h, const SkLayout& l, float* ws, int mode) {
-    SkLenArgs e;
+SkViewsArgs sk_args(const pndf_skel_plan* h, const SkLayout& l, float* ws, int mode) {
+    SkViewsArgs e;
     memset(&e, 0, sizeof(e));
     e.wenc = h->d_blob;
     e.X = ws + l.X; e.act0 = ws + l.act0; e.U0 = ws + l.U0; e.Gx = ws + l.Gx; e.dist = ws + l.dist; e.fk = ws + l.FK;
@@ -629,7 +648,7 @@ extern "C" int pndf_skel_forward(pndf_skel_handle h, const float* q, float* d, i
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     float* ws = (float*)workspace;
-    SkLenArgs e = sk_args(h, l, ws, SK_FORWARD);
+    SkViewsArgs e = sk_args(h, l, ws, SK_FORWARD);
     for (int64_t c0 = 0; c0 < B; c0 += l.nc) {
         e.n = B - c0 < l.nc ? B - c0 : l.nc;
         e.q = q + c0 * h->nj * BONE;
@@ -652,7 +671,7 @@ extern "C" int pndf_skel_forward_grad(pndf_skel_handle h, const float* q, const 
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     float* ws = (float*)workspace;
-    SkLenArgs e = sk_args(h, l, ws, SK_GRAD);
+    SkViewsArgs e = sk_args(h, l, ws, SK_GRAD);
     for (int64_t c0 = 0; c0 < B; c0 += l.nc) {
         e.n = B - c0 < l.nc ? B - c0 : l.nc;
         e.q = q + c0 * h->nj * BONE;
@@ -674,7 +693,8 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
     PndfKeypoints kp;              // a pndf_project_options5 the 3D keypoints besides (keypoint fitting): the arrays per pose in device memory, the small tables in host memory
     PndfCameraTerm cam;            // a pndf_project_options6 the camera and the root besides (image fitting): the roots per pose in device memory
     PndfLengths len;               // a pndf_project_options7 the bone lengths besides: the scales per group in device memory, the rates in host memory
-    if (const char* why = pndf_check_project_options7(opt, B, h->nj, o, observed, tracks, data, kp, cam, len)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    PndfViews vw;                  // a pndf_project_options8 the views besides: the table in host memory, targets [B,V,K,2] and confidences [B,V,K] in device memory
+    if (const char* why = pndf_check_project_options8(opt, B, h->nj, o, observed, tracks, data, kp, cam, len, vw)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (steps < 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count");
     SkLayout l;
     if (B > 0 && (!q_in || !q_out)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose pointer");
@@ -702,7 +722,7 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
         return PNDF_OK;
     }
     float* ws = (float*)workspace;
-    SkLenArgs e = sk_args(h, l, ws, SK_PROJECT);
+    SkViewsArgs e = sk_args(h, l, ws, SK_PROJECT);
     e.step_size = o.step_size; e.tol = o.tol; e.renorm = (int)o.renorm;
     e.frames = tracks.frames; e.lambda = tracks.lambda;
     e.mu = data.mu; e.flags = data.free_ends ? (uint32_t)PNDF_TRACK_FREE_ENDS : 0u;
@@ -711,6 +731,10 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
         pndf_fill_keypoint_tables(e, kp, h->nj);
         e.cam.fx = cam.fx; e.cam.fy = cam.fy; e.cam.cx = cam.cx; e.cam.cy = cam.cy; e.cam.rho = cam.rho; e.cam.image = cam.image ? 1 : 0;
         e.nu_rot = cam.nu_rot; e.nu_trans = cam.nu_trans;
+    }
+    if (vw.any()) {
+        e.V = vw.V;
+        for (int i = 0; i < PNDF_FK_MAX_VIEWS * PNDF_FK_VIEW_FLOATS; ++i) e.views[i] = vw.table[i];
     }
     SkLenStepArgs ls;
     memset(&ls, 0, sizeof(ls));
@@ -730,10 +754,10 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
         e.observed = observed ? observed + c0 : nullptr;
         e.anchor = data.anchor ? data.anchor + c0 * nq : nullptr;
         e.conf = data.conf ? data.conf + c0 * h->nj : nullptr;
-        e.kp_target = kp.target ? kp.target + c0 * kp.K * kp.dims : nullptr;
+        e.kp_target = kp.target ? kp.target + c0 * kp.views * kp.K * kp.dims : nullptr;
         e.root = cam.root ? cam.root + c0 * 7 : nullptr;
         e.bone_scale = len.any() ? len.scale + (c0 / len.group) * len.S : nullptr;      // a chunk is whole groups: with tracks it is whole tracks
-        e.kp_conf = kp.conf ? kp.conf + c0 * kp.K : nullptr;
+        e.kp_conf = kp.conf ? kp.conf + c0 * kp.views * kp.K : nullptr;
         // Without tracks the iterate is in q_out from the second step on: a lane reads its pose before it writes it.  With tracks a
         // step is out of place: the steps alternate between the chunk of q_out and the second pose buffer, the last one writes
         // q_out; step 0 reads q_in, or the buffer the fill wrote.

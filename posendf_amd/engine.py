@@ -15,7 +15,7 @@ import numpy as np
 # public names stay importable from here.  `torch` comes from there too: abi imports it before the library is loaded (None without it).
 from .abi import (ACT_CODES, DEBUG_EXPERIMENT_WORDS, DEBUG_EXPORTS, EXPERIMENT_WORDS, EXPORTS, INTERP_MODES, METRIC_CODES,  # noqa: F401
                   NOISE_CODES, PRECISION_CODES, RENORM_CODES, Camera, DenoiseWeights, KeypointOpts, OnlineOpts, PndfConfig, PndfError,
-                  ProjectOptions, ProjectOptions2, ProjectOptions3, ProjectOptions4, ProjectOptions5, ProjectOptions6, ProjectOptions7, KP_IMAGE, LEN_PER_POSE, TRACK_FILLS, TRACK_FREE_ENDS, debug_library_path, experiment_word, load_library, torch)
+                  ProjectOptions, ProjectOptions2, ProjectOptions3, ProjectOptions4, ProjectOptions5, ProjectOptions6, ProjectOptions7, ProjectOptions8, KP_IMAGE, LEN_PER_POSE, MAX_VIEWS, TRACK_FILLS, TRACK_FREE_ENDS, debug_library_path, experiment_word, load_library, torch)
 
 
 def stream_handle(device) -> int:
@@ -199,6 +199,45 @@ def project_options7(lib, *args, bone_scale_ptr=None, len_rate=None, len_weight=
     if len_range is not None:
         opt.len_min, opt.len_max = (float(v) for v in len_range)
     opt.len_flags = LEN_PER_POSE if per_pose_lengths else 0
+    return opt
+
+
+def view_table(views):
+    """The [V,16] float32 table of a pndf_project_options8 (per view fx, fy, cx, cy, R row-major, t) as a C-contiguous numpy array, from
+    such an array (or tensor) or from a sequence of (K [3,3] or (fx, fy, cx, cy), R [3,3], t [3]).  The values are checked by the library."""
+    if torch is not None and isinstance(views, torch.Tensor):
+        views = views.detach().cpu().numpy()
+    if isinstance(views, np.ndarray) and views.ndim == 2:
+        if views.shape[1] != 16:
+            raise PndfError(f"views is [V,16], not {list(views.shape)}")
+        return np.ascontiguousarray(views, dtype=np.float32)
+    rows = []
+    for view in views:
+        if len(view) != 3:
+            raise PndfError("a view is (K [3,3] or (fx, fy, cx, cy), R [3,3], t [3])")
+        K, R, t = (np.asarray(v.detach().cpu() if torch is not None and isinstance(v, torch.Tensor) else v, dtype=np.float64) for v in view)
+        if K.shape == (3, 3):
+            K = np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]])
+        if K.shape != (4,) or R.shape != (3, 3) or t.shape != (3,):
+            raise PndfError(f"a view is (K [3,3] or (fx, fy, cx, cy), R [3,3], t [3]), not {K.shape}, {R.shape}, {t.shape}")
+        rows.append(np.concatenate([K, R.reshape(9), t]))
+    return np.ascontiguousarray(np.stack(rows) if rows else np.zeros((0, 16)), dtype=np.float32)
+
+
+def project_options8(lib, *args, views=None, **kw):
+    """pndf_project_options8 (include/posendf_amd.h): `project_options7`'s arguments, and the cameras of a fit to pixels seen by several
+    views -- `views`: what `view_table` takes (HOST memory, kept alive on the returned struct; None: no views).  With views kp_target_ptr is
+    [B,V,K,2], kp_conf_ptr [B,V,K], and the image flag is set (the `camera` of project_options6 is not read).  The values are checked by
+    the library."""
+    opt = ProjectOptions8()
+    if views is not None and kw.get("image") is None:
+        kw = dict(kw, image=True)
+    opt.base7 = project_options7(lib, *args, **kw)
+    opt.base7.base6.base5.base4.base3.base2.base.struct_size = ctypes.sizeof(opt)
+    if views is not None:
+        opt._views = view_table(views)      # host memory that lives as long as the struct
+        opt.views = opt._views.ctypes.data if opt._views.size else None
+        opt.n_views = int(opt._views.shape[0])
     return opt
 
 
@@ -592,11 +631,17 @@ class SkeletonEngine(_Handle):
         (through a pndf_project_options5: `project_options5`); root_ptr [B,7] in device memory, root_weights, camera, rho, image: the root and
         the camera of a fit to 2D keypoints (through a pndf_project_options6: `project_options6`); bone_scale_ptr [G,S] in device memory,
         len_rate, len_weight, len_prior, len_range, per_pose_lengths: the bone lengths of a fit (through a pndf_project_options7:
-        `project_options7`)"""
+        `project_options7`); views: the cameras of a fit to pixels seen by several views, kp_target_ptr then [B,V,K,2] and kp_conf_ptr
+        [B,V,K] (through a pndf_project_options8: `project_options8`, built only when views are given)"""
+        views = keypoints.pop("views", None)
         lengthed, keypoints = _lengthed(keypoints)
         imaged, keypoints = _imaged(keypoints)
         named = _keypointed(keypoints)      # (refuses an unknown keyword)
-        if lengthed is not None:
+        if views is not None:
+            opt8 = project_options8(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends, views=views,
+                                    step_size=step_size, renorm=renorm, tol=tol, **keypoints, **(imaged or {}), **(lengthed or {}))
+            opt = ctypes.byref(opt8)
+        elif lengthed is not None:
             opt7 = project_options7(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends,
                                     step_size=step_size, renorm=renorm, tol=tol, **keypoints, **(imaged or {}), **lengthed)
             opt = ctypes.byref(opt7)
@@ -806,10 +851,18 @@ class CpuEngine(_Handle):
         observation of motion denoising (pndf_project_ex_cpu with a pndf_project_options4: `project_options4`).  `**keypoints`: as
         SkeletonEngine.project, every pointer in host memory (pndf_project_ex_cpu with a pndf_project_options5: `project_options5`, or with
         root_ptr / root_weights / camera / rho / image a pndf_project_options6: `project_options6`, or with bone_scale_ptr / len_rate /
-        len_weight / len_prior / len_range / per_pose_lengths a pndf_project_options7: `project_options7`)"""
+        len_weight / len_prior / len_range / per_pose_lengths a pndf_project_options7: `project_options7`, or with views a
+        pndf_project_options8: `project_options8`)"""
+        views = keypoints.pop("views", None)
         lengthed, keypoints = _lengthed(keypoints)
         imaged, keypoints = _imaged(keypoints)
         named = _keypointed(keypoints)      # (refuses an unknown keyword)
+        if views is not None:
+            opt8 = project_options8(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends, views=views,
+                                    step_size=step_size, renorm=renorm, tol=tol, **keypoints, **(imaged or {}), **(lengthed or {}))
+            self._check(self.lib.pndf_project_ex_cpu(self.handle, q_in_ptr, q_out_ptr, d_ptr, B, int(steps), ctypes.byref(opt8)),
+                        "pndf_project_ex_cpu")
+            return
         if lengthed is not None:
             opt7 = project_options7(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends,
                                     step_size=step_size, renorm=renorm, tol=tol, **keypoints, **(imaged or {}), **lengthed)

@@ -9,6 +9,8 @@ starts per target and returns, per target, the hypothesis of the lowest `energy 
 
 With a `camera` the detections are pixels [N,K,2], and with a `root` the tree is placed in the target's frame by a rotation and a
 translation per pose that the steps move as well (pndf_project_options6; DESIGN.md section 2j "Image fitting"): a hand tracker's output.
+With `views` the detections are pixels [N,V,K,2] of the same frame in V calibrated cameras (pndf_project_options8; DESIGN.md section 2j
+"Several cameras"); `--views FILE.npz` on the command line.
 With `fit_lengths=True` the segment lengths of the subject are unknowns too: a scale per rest offset and per keypoint offset
 (pndf_project_options7; DESIGN.md section 2j "Bone lengths").
 
@@ -22,14 +24,25 @@ from .sample_poses import SamplePose
 
 
 def keypoint_energy(pose, targets, parents, rest, conf=None, keypoint_joints=None, keypoint_offsets=None, root=None, camera=None, rho=0.0,
-                    bone_scale=None):
+                    bone_scale=None, views=None):
     """1/2 sum_k w_k |C_k(pose, root) - targets_k|^2 per pose [...], with `forward_kinematics` and `camera_project`; a keypoint whose
     confidence is not positive (zero, negative, NaN) takes no part, whatever its target holds.  With a `camera` the targets are pixels and
     the residual e is taken in normalised image coordinates, rho(e) = e^2 or (rho > 0) rho^2 e^2 / (e^2 + rho^2) summed over both axes; a
-    keypoint that is not in front of the camera takes no part"""
+    keypoint that is not in front of the camera takes no part.  With `views` (`SkeletonPoseNDF.fit_keypoints(views=)`) the targets are
+    [...,V,K,2], the confidences [...,V,K] and the sum runs over views and keypoints"""
+    from .engine import view_table
     from .skeleton import camera_project, forward_kinematics
     C = camera_project(forward_kinematics(pose, parents, rest, keypoint_joints, keypoint_offsets, bone_scale), root)
-    if camera is None:
+    if views is not None:
+        vt = torch.as_tensor(view_table(views), dtype=C.dtype, device=C.device)
+        C = (vt[:, 4:13].reshape(-1, 1, 3, 3) @ C.unsqueeze(-3).unsqueeze(-1)).squeeze(-1) + vt[:, 13:16].unsqueeze(-2)      # [...,V,K,3]
+        front = C[..., 2] > 0
+        z = torch.where(front, C[..., 2], torch.ones_like(C[..., 2]))
+        e = C[..., :2] / z.unsqueeze(-1) - (targets - vt[:, 2:4].unsqueeze(-2)) / vt[:, 0:2].unsqueeze(-2)
+        ee = e * e
+        cost = ee if not rho else float(rho) ** 2 * ee / (ee + float(rho) ** 2)
+        sq = torch.where(front, cost.sum(-1), torch.zeros_like(z))
+    elif camera is None:
         res = C - targets
         sq = (res * res).sum(-1)
     else:
@@ -43,7 +56,7 @@ def keypoint_energy(pose, targets, parents, rest, conf=None, keypoint_joints=Non
     if conf is not None:
         on = conf > 0
         sq = torch.where(on, conf * torch.where(on, sq, torch.zeros_like(sq)), torch.zeros_like(sq))
-    return 0.5 * sq.sum(-1)
+    return 0.5 * (sq.sum((-2, -1)) if views is not None else sq.sum(-1))
 
 
 class KeypointFitting(SamplePose):
@@ -53,7 +66,7 @@ class KeypointFitting(SamplePose):
     @torch.no_grad()
     def fit(self, targets, rest, conf=None, keypoint_joints=None, keypoint_offsets=None, hypotheses=8, iterations=3, steps_per_iter=30, weight=0.02,
             lam=1.0, seed=None, *, step_size=1.0, renormalize="unit", tol=0.0, camera=None, root=None, root_weights=(0.0, 0.0), rho=0.0,
-            fit_lengths=False, length_weight=0.02, length_prior=0.1, length_range=(0.5, 2.0)):
+            fit_lengths=False, length_weight=0.02, length_prior=0.1, length_range=(0.5, 2.0), views=None):
         """targets: [N,K,3] detections (one set of K keypoints per target pose); rest / keypoint_joints / keypoint_offsets / conf: as
         `SkeletonPoseNDF.fit_keypoints` (conf [K] or [N,K]).  Every target gets `hypotheses` random starts (unit quaternions, seeded by
         `seed`); `iterations` engine calls of `steps_per_iter` steps each run all N * hypotheses poses at once, iteration `it` with the
@@ -75,32 +88,38 @@ class KeypointFitting(SamplePose):
         `length_weight` under the prior `length_prior` (sigma - 1)^2 / 2 and clamped to `length_range`; the result gains a last entry, the
         scales [N,S] of the chosen hypothesis.  These defaults (0.02, 0.1, (0.5, 2.0)) are UNTUNED: no trained model of another skeleton
         exists to tune them on.  With a camera and a free root translation the overall scale trades against depth and only the prior holds
-        it."""
+        it.
+        `views` (a [V,16] array or a sequence of (K, R, t): `SkeletonPoseNDF.fit_keypoints(views=)`): targets are [N,V,K,2] pixels of the
+        same frame in V calibrated cameras and conf [K], [V,K] or [N,V,K]; the root places the tree in the world frame.  Not with
+        `camera`.  The weights tried for one camera are the only ones known; several views add their gradients, so start lower."""
         net = self.pose_prior
         if not hasattr(net, "fit_keypoints"):
             raise TypeError(f"{type(net).__name__} has no fit_keypoints(): fitting to 3D keypoints is SkeletonPoseNDF's; a PoseNDF fits 2D "
                             "keypoints through posendf_amd.image_fit.ImageFit and its body model")
         J, H = net.num_joints, int(hypotheses)
         y = targets.to(self.device).float()
-        D = 3 if camera is None else 2
-        if y.dim() != 3 or y.shape[-1] != D:
-            raise ValueError(f"targets are [N,K,{D}], not {tuple(targets.shape)}")
-        N, K = y.shape[0], y.shape[1]
+        D = 3 if camera is None and views is None else 2
+        if camera is not None and views is not None:
+            raise ValueError("camera= is the one camera of a fit and views= the several: give one of them")
+        if y.dim() != (3 if views is None else 4) or y.shape[-1] != D:
+            raise ValueError(f"targets are [N,K,{D}] (with views [N,V,K,2]), not {tuple(targets.shape)}")
+        N, K = y.shape[0], y.shape[-2]
+        lead = () if views is None else (y.shape[1],)
         if H < 1:
             raise ValueError("at least one hypothesis per target")
         gen = torch.Generator().manual_seed(int(seed)) if seed is not None else None
         start = torch.randn((N, H, J, 4), generator=gen)
         start = (start / start.norm(dim=-1, keepdim=True).clamp_min(1e-12)).to(self.device)
-        yy = y[:, None].expand(N, H, K, D).reshape(N * H, K, D)
-        placed = camera is not None or root is not None
+        yy = y[:, None].expand(N, H, *lead, K, D).reshape(N * H, *lead, K, D)
+        placed = camera is not None or root is not None or views is not None
         rt = None
         if root is not None:
             rt = torch.as_tensor(root).to(self.device).float().expand(N, 7)[:, None].expand(N, H, 7).reshape(N * H, 7).contiguous()
-        image = dict(camera=camera, rho=rho, root_weights=tuple(root_weights)) if placed else {}
+        image = dict(camera=camera, rho=rho, root_weights=tuple(root_weights), **({} if views is None else dict(views=views))) if placed else {}
         c = None
         if conf is not None:
             c = torch.as_tensor(conf).to(self.device).float()
-            c = c.expand(N, K)[:, None].expand(N, H, K).reshape(N * H, K).contiguous()
+            c = c.expand(N, *lead, K)[:, None].expand(N, H, *lead, K).reshape(N * H, *lead, K).contiguous()
         tables = dict(keypoint_joints=keypoint_joints, keypoint_offsets=keypoint_offsets)
         rest_d = torch.as_tensor(rest).to(self.device).float()
         off_d = None if keypoint_offsets is None else torch.as_tensor(keypoint_offsets).to(self.device).float()
@@ -109,7 +128,7 @@ class KeypointFitting(SamplePose):
         lengths = dict(scale_weight=length_weight, scale_prior=length_prior, scale_range=length_range, per_pose_scale=True, return_scale=True) if fit_lengths else {}
 
         def energy_of(q, r):
-            return keypoint_energy(q, yy, net.parents, rest_d, c, keypoint_joints, off_d, r, camera, rho, sg)
+            return keypoint_energy(q, yy, net.parents, rest_d, c, keypoint_joints, off_d, r, camera, rho, sg, views)
 
         cur = start.reshape(N * H, J, 4)
         start_energy = energy_of(cur, rt).reshape(N, H)
@@ -139,7 +158,7 @@ class KeypointFitting(SamplePose):
 def fit_keypoint_file(posendf, keypoint_file, device="cuda:0", key="keypoints", **kwargs):
     """The targets of an .npz -- `key` [N,K,3], `rest` [J,3], and, if the file has them, `conf` [K] or [N,K], `keypoint_joints` [K],
     `keypoint_offsets` [K,3], `camera` [4] = (fx, fy, cx, cy) (then `key` is [N,K,2] pixels) and `root` [7] or [N,7] -> what
-    KeypointFitting.fit returns for them."""
+    KeypointFitting.fit returns for them.  With `views=` among the keyword arguments `key` is [N,V,K,2]."""
     import numpy as np
     with np.load(keypoint_file) as f:
         y = torch.from_numpy(np.ascontiguousarray(f[key], dtype=np.float32))
@@ -177,6 +196,9 @@ def main(argv=None):
     ap.add_argument("--rho", type=float, default=0.0, help="robustifier of the image residual (needs a camera in the file); 0 = squared error")
     ap.add_argument("--fit-lengths", "--fit_lengths", dest="fit_lengths", action="store_true",
                     help="fit a scale per rest offset and per keypoint offset besides (weights untuned); written to the key scale")
+    ap.add_argument("--views", default=None, metavar="FILE.npz",
+                    help="calibration of several cameras: arrays K [V,3,3] (or [V,4] = fx, fy, cx, cy), R [V,3,3] and t [V,3], world -> camera; "
+                         "keypoints are then [N,V,K,2] pixels (not with a camera in the keypoint file)")
     ap.add_argument("--lam", type=float, default=1.0, help="weight of the distance in the choice between hypotheses")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None, help="write the fitted poses (key pose), their energies (energy) and distances (dist) to this .npz")
@@ -192,6 +214,10 @@ def main(argv=None):
         extra["rho"] = a.rho
     if a.fit_lengths:
         extra["fit_lengths"] = True
+    if a.views:
+        import numpy as np
+        with np.load(a.views) as f:
+            extra["views"] = [(f["K"][v], f["R"][v], f["t"][v]) for v in range(f["R"].shape[0])]
     pose, energy, dist, start, *root = fit_keypoint_file(net, a.keypoint_file, device=opt["train"]["device"], hypotheses=a.hypotheses, iterations=a.iterations,
                                                          steps_per_iter=a.steps_per_iter, weight=a.weight, lam=a.lam, seed=a.seed, **extra)
     if energy.numel():

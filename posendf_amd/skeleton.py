@@ -24,6 +24,8 @@ differentiable torch statement of its kinematics.  With `camera=` the detections
 has a placement in the target's frame that the steps move (a pndf_project_options6; `camera_project` is the torch statement of both).
 With `bone_scale=` / `scale_weight=` the segment lengths of the subject are unknowns of the same fit, one set of scales per clip (a
 pndf_project_options7; `forward_kinematics(..., bone_scale=)` is the torch statement of the scaled tree).
+With `views=` the detections are pixels of the same frame in several calibrated cameras (a pndf_project_options8;
+`camera_project(..., views=)` is the torch statement of the pixels).
 Only the second order stays 21-joint: its C ABI refuses another joint count, and that refusal is pinned.
 """
 from __future__ import annotations
@@ -33,7 +35,7 @@ import copy
 import torch
 import torch.nn as nn
 
-from .engine import PndfError, SkeletonEngine, StreamWorkspaces, stream_handle
+from .engine import MAX_VIEWS, PndfError, SkeletonEngine, StreamWorkspaces, stream_handle, view_table
 from .model_base import PoseModel, _Distance, pack_observed
 from .synth import BONE_DIM, FEAT, PARENT
 
@@ -233,7 +235,8 @@ class SkeletonPoseNDF(PoseModel):
     def fit_keypoints(self, poses, targets, rest, steps=100, weight=0.02, conf=None, keypoint_joints=None, keypoint_offsets=None, observed=None,
                       frames=None, smooth=0.0, anchor=None, data=0.0, free_ends=False, return_dist=True, return_energy=False, *, step_size=1.0,
                       renormalize=None, tol=0.0, root=None, root_weights=(0.0, 0.0), camera=None, rho=0.0, return_root=False, bone_scale=None,
-                      scale_weight=0.0, scale_prior=0.0, scale_range=None, scale_rates=None, per_pose_scale=False, return_scale=False):
+                      scale_weight=0.0, scale_prior=0.0, scale_range=None, scale_rates=None, per_pose_scale=False, return_scale=False,
+                      views=None):
         """Inverse kinematics under the learned prior, for the model's tree: from the start `poses` [B,J,4], `steps` projection steps that
         also descend E = 1/2 sum_k conf_k |P_k(pose) - targets_k|^2 with weight `weight` (nu), P_k = `forward_kinematics` of the pose.
         `targets` [B,K,3] are 3D detections in the roots' frame; `rest` [J,3] the offsets of the joints from their parents in the rest
@@ -270,6 +273,12 @@ class SkeletonPoseNDF(PoseModel):
         multiplies the weight per scale (0 holds that scale); `scale_range` = (lo, hi) clamps them.  Like the root the scales are not
         joints: held joints and held end frames still contribute to their gradient.  With 2D targets and a free root translation the
         overall scale trades against depth and is not observable: use a prior.  The default weights are zero and UNTUNED.
+        Several cameras (pndf_project_options8; DESIGN.md section 2j "Several cameras"): `views` -- a [V,16] array (per view fx, fy, cx,
+        cy, R row-major, t) or a sequence of (K [3,3] or (fx, fy, cx, cy), R [3,3], t [3]), V <= 8 -- makes `targets` [B,V,K,2] the pixels
+        of the same frame in V calibrated cameras and `conf` [K], [V,K] or [B,V,K]; R and t map the world frame, in which `root` places
+        the tree, to the camera's (C = R W + t).  A view whose confidence for a keypoint is not positive, or behind which the keypoint
+        lies, takes no part for it and its target is not read.  `camera=` together with `views=` is an error.  `camera_project(views=)` is
+        the torch statement of the pixels.
         Returns poses [B,J,4], then dist [B,1] of the last iteration (`return_dist`), then the energy [B] of the last iteration, evaluated
         before its update (`return_energy`), then the final root [B,7] (`return_root`; the identity placement when none was given), then
         the final scales [G,S] (`return_scale`; ones when none were given); step options: as `project`."""
@@ -303,13 +312,24 @@ class SkeletonPoseNDF(PoseModel):
         kpj = None if kpj is None else kpj.to(torch.int32).contiguous()
         rest_t = table(rest, (J, 3), torch.float32, "rest")
         kpo = None if keypoint_offsets is None else table(keypoint_offsets, (K, 3), torch.float32, "keypoint_offsets")
-        D = 3 if camera is None else 2
+        D = 3 if camera is None and views is None else 2
+        if camera is not None and views is not None:
+            raise PndfError("camera= is the one camera of a fit and views= the several: give one of them")
         if camera is not None and len(tuple(camera)) != 4:
             raise PndfError("camera is (fx, fy, cx, cy)")
+        vt = None if views is None else view_table(views)
+        V = 1 if vt is None else int(vt.shape[0])
+        if vt is not None and not 1 <= V <= MAX_VIEWS:
+            raise PndfError(f"views are 1 .. {MAX_VIEWS} rows, not {V}")
         y = on_device(targets, "targets").float()
-        if y.dim() < 2 or tuple(y.shape[-2:]) != (K, D) or y.numel() != B * K * D:
-            raise PndfError(f"targets are [{B},{K},{D}], not {list(y.shape)}")
-        y = y.reshape(B, K, D).contiguous()
+        if vt is not None:
+            if y.dim() < 3 or tuple(y.shape[-3:]) != (V, K, 2) or y.numel() != B * V * K * 2:
+                raise PndfError(f"targets are [{B},{V},{K},2] with views, not {list(y.shape)}")
+            y = y.reshape(B, V, K, 2).contiguous()
+        else:
+            if y.dim() < 2 or tuple(y.shape[-2:]) != (K, D) or y.numel() != B * K * D:
+                raise PndfError(f"targets are [{B},{K},{D}], not {list(y.shape)}")
+            y = y.reshape(B, K, D).contiguous()
         place = None
         if root is not None:
             place = on_device(root, "root")
@@ -340,9 +360,14 @@ class SkeletonPoseNDF(PoseModel):
         c = None
         if conf is not None:
             c = on_device(conf, "conf")
-            if not c.is_floating_point() or tuple(c.shape) not in ((K,), (B, K)):
-                raise PndfError(f"conf is a floating-point tensor [{K}] or [{B},{K}], not {c.dtype} {list(c.shape)}")
-            c = c.float().expand(B, K).contiguous()
+            if vt is not None:
+                if not c.is_floating_point() or tuple(c.shape) not in ((K,), (V, K), (B, V, K)):
+                    raise PndfError(f"conf is a floating-point tensor [{K}], [{V},{K}] or [{B},{V},{K}] with views, not {c.dtype} {list(c.shape)}")
+                c = c.float().expand(B, V, K).contiguous()
+            else:
+                if not c.is_floating_point() or tuple(c.shape) not in ((K,), (B, K)):
+                    raise PndfError(f"conf is a floating-point tensor [{K}] or [{B},{K}], not {c.dtype} {list(c.shape)}")
+                c = c.float().expand(B, K).contiguous()
         seen = None
         if anchor is not None:
             seen = on_device(anchor, "anchor").float()
@@ -366,6 +391,7 @@ class SkeletonPoseNDF(PoseModel):
                         n_keypoints=K, kp_weight=weight, **tracks,
                         **(dict(root_ptr=place.data_ptr() if place is not None and B else None, root_weights=tuple(root_weights) if B else (0.0, 0.0), camera=camera, rho=rho)
                            if place is not None or camera is not None or rho or any(root_weights) else {}),
+                        **(dict(views=vt) if vt is not None and B else {}),      # (without poses there are no targets for the views to size)
                         **(dict(bone_scale_ptr=scales.data_ptr() if scales is not None and B else None, len_rate=rates, len_weight=scale_weight if B else 0.0,
                                 len_prior=scale_prior, len_range=None if scale_range is None else tuple(scale_range), per_pose_lengths=bool(per_pose_scale))
                            if lengthed else {}))
@@ -430,12 +456,16 @@ def forward_kinematics(pose, parents, rest, keypoint_joints=None, keypoint_offse
     return torch.stack(out, dim=-2)
 
 
-def camera_project(points, root=None, camera=None):
+def camera_project(points, root=None, camera=None, views=None):
     """Keypoints in the target's frame, and their pixels, differentiable: points [...,K,3] (`forward_kinematics`, the roots' frame) ->
     C_k = R(c) P_k + s with `root` [...,7] or [7] = (c: a quaternion, real part first, normalised c / max(|c|, 1e-12); s: a translation),
     or the points themselves when root is None; with `camera` = (fx, fy, cx, cy) the pixels (fx C_x / C_z + cx, fy C_y / C_z + cy)
     [...,K,2] of a pinhole camera that looks along +z.  This is the statement `SkeletonPoseNDF.fit_keypoints(camera=..., root=...)`
-    (csrc/pndf_fk.h) descends; use it to make targets and to read residuals."""
+    (csrc/pndf_fk.h) descends; use it to make targets and to read residuals.  With `views` ([V,16], or a sequence of (K or (fx, fy, cx, cy),
+    R, t): `fit_keypoints(views=)`) the root places the tree in the world frame and the result is [...,V,K,2]: the pixels
+    (fx C_x / C_z + cx, fy C_y / C_z + cy) of C = R_v W + t_v in every view."""
+    if camera is not None and views is not None:
+        raise PndfError("camera= is the one camera and views= the several: give one of them")
     if points.shape[-1] != 3:
         raise PndfError(f"points are [...,K,3], not {tuple(points.shape)}")
     C = points
@@ -450,6 +480,11 @@ def camera_project(points, root=None, camera=None):
                          2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
                          2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], dim=-1).reshape(r.shape[:-1] + (3, 3))
         C = (R.unsqueeze(-3) @ points.unsqueeze(-1)).squeeze(-1) + s.unsqueeze(-2)
+    if views is not None:
+        vt = torch.as_tensor(view_table(views), dtype=points.dtype, device=points.device)      # [V,16]
+        Cv = (vt[:, 4:13].reshape(-1, 1, 3, 3) @ C.unsqueeze(-3).unsqueeze(-1)).squeeze(-1) + vt[:, 13:16].unsqueeze(-2)      # [...,V,K,3]
+        f, pp = vt[:, 0:2].unsqueeze(-2), vt[:, 2:4].unsqueeze(-2)
+        return f * Cv[..., :2] / Cv[..., 2:3] + pp
     if camera is None:
         return C
     fx, fy, cx, cy = (float(v) for v in camera)
