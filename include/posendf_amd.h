@@ -274,7 +274,7 @@ typedef struct {
  *   o.base5.base4.base3.base2.base.struct_size = sizeof o;  o.root = placement;  o.fx = o.fy = 500.f;  o.cx = 320.f;  o.cy = 240.f;
  *   o.nu_rot = 0.02f;  o.nu_trans = 0.02f;  o.kp_flags = PNDF_KP_IMAGE;
  * Exactly the two entry points that take a pndf_project_options5 take it.  PNDF_ERR_BAD_ARG with a text that names the field, before
- * anything is launched or written: a struct_size that is none of the eight sizes, an unknown bit in kp_flags, a rho, nu_rot or nu_trans
+ * anything is launched or written: a struct_size that is none of the nine sizes, an unknown bit in kp_flags, a rho, nu_rot or nu_trans
  * that is negative or not finite, rho != 0 without PNDF_KP_IMAGE, with PNDF_KP_IMAGE an fx or fy that is not finite or <= 0 or a cx or
  * cy that is not finite, root == NULL with a positive root weight, a misaligned root, root overlapping q_out, with a positive root
  * weight root overlapping q_in, anchor, conf, kp_target, kp_conf or kp_energy; and what is refused in `base5`. */
@@ -309,7 +309,7 @@ typedef struct {
  * the 168-byte struct bit for bit and bone_scale is not written; with kp_target == NULL or nu == 0 it is the one with the 72-byte struct
  * and bone_scale is neither read nor written; steps == 0 leaves it untouched.  Exactly the two entry points that take a
  * pndf_project_options6 take it.  PNDF_ERR_BAD_ARG with a text that names the field, before anything is launched or written: a
- * struct_size that is none of the eight sizes, reserved3 != 0, an unknown bit in len_flags, a nu_len or kappa that is negative or not
+ * struct_size that is none of the nine sizes, reserved3 != 0, an unknown bit in len_flags, a nu_len or kappa that is negative or not
  * finite, a clamp that is not 0 < len_min <= len_max finite (both 0: none), a len_rate entry that is negative or not finite, bone_scale
  * == NULL with nu_len > 0, a misaligned bone_scale or len_rate, bone_scale overlapping q_out, q_in, root, anchor, conf, kp_target, kp_conf
  * or kp_energy; and what is refused in `base6`. */
@@ -341,7 +341,7 @@ typedef struct {
  * are not read.  `views` is HOST memory in both entry points, read during the call.  With views == NULL and n_views == 0 the call is the
  * one with the 208-byte struct bit for bit; with kp_target's term absent (nu == 0) it is the one with the 72-byte struct and neither the
  * targets nor the confidences are read.  Exactly the two entry points that take a pndf_project_options7 take it.  PNDF_ERR_BAD_ARG with a
- * text that names the field, before anything is launched or written: a struct_size that is none of the eight sizes, reserved4 != 0,
+ * text that names the field, before anything is launched or written: a struct_size that is none of the nine sizes, reserved4 != 0,
  * n_views outside 0 .. PNDF_FK_MAX_VIEWS, exactly one of views == NULL and n_views == 0, n_views > 0 without PNDF_KP_IMAGE or without
  * kp_target, a view whose fx or fy is not finite or <= 0, any other view entry that is not finite, a misaligned views; and what is
  * refused in `base7` (the overlap checks of kp_target and kp_conf with their extents [B,V,K,2] and [B,V,K]). */
@@ -352,6 +352,37 @@ typedef struct {
     int32_t      n_views;          /* V, 0 or 1 .. PNDF_FK_MAX_VIEWS */
     uint32_t     reserved4;        /* 0 */
 } pndf_project_options8;           /* 224 bytes */
+
+/* The options with a root trajectory: the fit of pndf_project_options8 with the root (c, s) of every frame coupled to the roots of its
+ * neighbour frames in the track and, optionally, drawn towards an observed or earlier trajectory `root_anchor` [B,7].  For one pose the
+ * joints, scales, energy, views, mask, tracks and tol are those of the 224-byte struct; only the root's own step changes
+ * (pndf_fk_root_smooth_step of csrc/pndf_fk.h).  Every operation rounded to fp32 on its own in the order written; c, s: the root at the
+ * step's input, g_c, g_s: d E / d (c, s), frame k = pose % frames.  A pose that rests under tol keeps its root bits.
+ *   rotation, when nu_rot > 0:   u = c - nu_rot g_c
+ *     lambda_rot > 0:  N-, N+ the root rotations of frames k-1 and k+1 of the same track at the step's INPUT (the step is Jacobi), each
+ *                      negated where its dot product with c is negative; an interior frame  u <- u + lambda_rot ((0.5 (N- + N+)) - c),
+ *                      an end frame with its one neighbour N  u <- u + lambda_rot (0.5 (N - c))
+ *     mu_rot > 0:      A the anchor's rotation, aligned to c the same way;  u <- u + mu_rot (A - c)
+ *     c <- u / max(|u|, 1e-12)
+ *   translation, when nu_trans > 0: the same three parts on the three components of s with lambda_trans and mu_trans, without alignment
+ *     and without normalisation.
+ * A part whose nu is 0 keeps its bits and reads neither neighbours nor anchor; the anchor of a part is not read when its mu is 0.  The
+ * root is not a joint: the end frames take the one-neighbour term whether or not PNDF_TRACK_FREE_ENDS is set, and the mask does not hold
+ * the root.  With lambda_rot = lambda_trans = 0 and root_anchor == NULL the call is the one with the 224-byte struct bit for bit; with
+ * kp_target == NULL or nu == 0 it is the one with the 72-byte struct and neither root nor root_anchor is read or written; steps == 0
+ * leaves root untouched.  After the call the result is in `root`, whatever the parity of steps.  Exactly the two entry points that take a
+ * pndf_project_options8 take it.  PNDF_ERR_BAD_ARG with a text that names the field, before anything is launched or written: a
+ * struct_size that is none of the nine sizes, reserved5 != 0, a lambda or mu outside [0, 1] or NaN, a positive lambda with frames == 0, a
+ * positive lambda_rot or mu_rot with nu_rot == 0 (likewise the translation), a positive lambda or mu with root == NULL, a positive mu with
+ * root_anchor == NULL, root_anchor != NULL with both mu 0, a misaligned root_anchor, root_anchor overlapping root or q_out; and what is
+ * refused in `base8`. */
+typedef struct {
+    pndf_project_options8 base8;   /* base8.base7.base6.base5.base4.base3.base2.base.struct_size = sizeof(pndf_project_options9) */
+    const float* root_anchor;      /* [B,7] an observed / earlier root trajectory, or NULL; DEVICE (pndf_skel_project) / HOST (pndf_project_ex_cpu) */
+    float lambda_rot, lambda_trans;/* neighbour coupling of the root's rotation / translation, each in [0, 1] */
+    float mu_rot, mu_trans;        /* weight of the root's data term towards root_anchor, each in [0, 1] */
+    uint64_t reserved5;            /* must be 0 */
+} pndf_project_options9;           /* 256 bytes */
 
 /* pndf_project with step options.  opt == NULL means the defaults, and with the defaults the call is pndf_project bit for
  * bit.  PNDF_ERR_BAD_ARG (text in pndf_last_error; nothing is launched or written) for a struct_size other than
@@ -381,9 +412,10 @@ int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* q_out, floa
                         const pndf_project_options* opt);      /* pndf_project_ex: same semantics, same validation; also takes a
                                                                   pndf_project_options2, a pndf_project_options3, a
                                                                   pndf_project_options4, a pndf_project_options5, a
-                                                                  pndf_project_options6, a pndf_project_options7 or a
-                                                                  pndf_project_options8, `observed` / `anchor` / `conf` /
-                                                                  `kp_*` / `root` / `bone_scale` in HOST memory */
+                                                                  pndf_project_options6, a pndf_project_options7, a
+                                                                  pndf_project_options8 or a pndf_project_options9,
+                                                                  `observed` / `anchor` / `conf` / `kp_*` / `root` /
+                                                                  `bone_scale` / `root_anchor` in HOST memory */
 const char* pndf_cpu_last_error(pndf_cpu_handle h);   /* h may be NULL: last error of a failed pndf_cpu_create */
 
 /* Host-only weight packer (what pndf_load_weights uploads); needs no device.  Output sizes in floats come

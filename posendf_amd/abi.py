@@ -103,6 +103,16 @@ class ProjectOptions8(ctypes.Structure):
     _fields_ = [("base7", ProjectOptions7), ("views", c_void_p), ("n_views", c_int32), ("reserved4", ctypes.c_uint32)]
 
 
+class ProjectOptions9(ctypes.Structure):
+    """pndf_project_options9: the options with a mask, tracks, an observation, keypoints, a camera, bone lengths and several cameras
+    (`base8`, with base8.base7.base6.base5.base4.base3.base2.base.struct_size = 256) and the root's trajectory -- `root_anchor` [B,7] an
+    observed or earlier trajectory of the roots (device memory for the skeleton unit, host memory for the twin; None: none),
+    `lambda_rot` / `lambda_trans` the coupling of a frame's root rotation / translation to its neighbour frames' in the track, `mu_rot` /
+    `mu_trans` the weights of the data term towards root_anchor, each in [0, 1]; taken by the two entry points that take a ProjectOptions8"""
+    _fields_ = [("base8", ProjectOptions8), ("root_anchor", c_void_p), ("lambda_rot", c_float), ("lambda_trans", c_float),
+                ("mu_rot", c_float), ("mu_trans", c_float), ("reserved5", ctypes.c_uint64)]
+
+
 class DenoiseWeights(ctypes.Structure):
     """pndf_denoise_weights: the loss weights of one outer iteration, evaluated"""
     _fields_ = [("prior_coef", c_float), ("prior_power", c_int32), ("temp_coef", c_float), ("data_coef", c_float)]
@@ -132,7 +142,7 @@ class PndfError(RuntimeError):
 _H = c_void_p                          # every handle type, and every `void* stream`
 _P = c_void_p                          # any other address: tensor data (an int from data_ptr(), or None), a callback, an out value
 _TENSORS = [POINTER(c_void_p), POINTER(c_int64), c_int]      # tensors, numel, n_tensors (host pointers in state-dict order)
-_OPT2 = c_void_p                       # `const pndf_project_options*` where it may point to a ProjectOptions, a ProjectOptions2 .. a ProjectOptions8 (byref of any)
+_OPT2 = c_void_p                       # `const pndf_project_options*` where it may point to a ProjectOptions, a ProjectOptions2 .. a ProjectOptions9 (byref of any)
 # ---- the header set, stated once: header of include/ -> {name: (restype, argtypes)} in the header's order; the headers in the order
 # they were added.  A new header is a file in include/, a table here and its declaration count in tests/test_cabi.py.
 DEBUG_HEADER = "posendf_amd_debug.h"      # the one header that lives in libposendf_amd_debug.so; every other one in the product library

@@ -7,7 +7,8 @@
 // SMPL table they compute what they did with the table fixed.  pndf_complete_cpu, pndf_interpolate_cpu and the second order stay 21-joint;
 // pndf_project_ex_cpu completes, interpolates, denoises and fits 3D or 2D keypoints for any joint tree (pndf_project_options2 /
 // pndf_project_options3 / pndf_project_options4 / pndf_project_options5 / pndf_project_options6), with the bone lengths as unknowns too
-// (pndf_project_options7) and the pixels seen by several calibrated cameras (pndf_project_options8).
+// (pndf_project_options7), the pixels seen by several calibrated cameras (pndf_project_options8) and the root's trajectory over the
+// frames of a track (pndf_project_options9).
 //
 // Layout: poses are processed in blocks of PB = 32; inside a block every activation tensor is [feature][pose] so that the
 // inner loop of a layer runs over the 32 poses of the block (contiguous floats: one or two AVX-512 / four AVX2 registers)
@@ -408,6 +409,35 @@ struct KeypointTables {
     float kpo[3 * PNDF_FK_MAX_KEYPOINTS];
 };
 
+// The root buffers of a step with the trajectory of a pndf_project_options9: every frame reads its own and its neighbours' rows in `src`
+// and writes its row of `dst` (the same array only without tracks, where no frame reads another's row); frames: T, or 0
+struct RootTrack {
+    const PndfRootSmooth* rs;
+    const float* src;
+    float* dst;
+    int32_t frames;
+};
+
+// The root's own step of pose number `pose`: pndf_fk_root_step in place, or with a pndf_project_options9 (`tr`) pndf_fk_root_smooth_step
+// from tr->src to tr->dst.  root: the row at the step's input, as the term read it.
+static void root_step_cpu(const PndfCameraTerm& cam, float* rt, const float* root, const float* groot, float dist, float tol, int64_t pose,
+                          const RootTrack* tr) {
+    float stepped[7];
+    if (!tr) {
+        if (!cam.moves()) return;
+        pndf_fk_root_step(root, groot, cam.nu_rot, cam.nu_trans, dist, tol, stepped);
+        memcpy(rt, stepped, sizeof(stepped));
+        return;
+    }
+    const int k = tr->frames ? (int)(pose % tr->frames) : 0;
+    const int nbr = tr->frames ? ((k > 0 ? 1 : 0) | (k < tr->frames - 1 ? 2 : 0)) : 0;
+    const float* row = tr->src + pose * 7;
+    const PndfRootSmooth& rs = *tr->rs;
+    pndf_fk_root_smooth_step(root, groot, cam.nu_rot, cam.nu_trans, dist, tol, (nbr & 1) ? row - 7 : nullptr, (nbr & 2) ? row + 7 : nullptr, nbr,
+                             rs.lambda_rot, rs.lambda_trans, rs.anchor ? rs.anchor + pose * 7 : nullptr, rs.mu_rot, rs.mu_trans, stepped);
+    memcpy(tr->dst + pose * 7, stepped, sizeof(stepped));
+}
+
 // The keypoint term of pose number `pose` at the iterate q: pndf_fk.h's pndf_fk_energy_grad -- the statement the device kernel runs -- on
 // a local array of rows (ld = 1).  gk [nj][4] = d E / d Q; returns E.  With the camera or the root of a pndf_project_options6 (`cam`) the
 // term is pndf_fk_camera_energy_grad, and the pose's root row takes its own step here (pndf_fk_root_step; `dist` and `tol` say whether
@@ -415,49 +445,42 @@ struct KeypointTables {
 // With the scales of a pndf_project_options7 (`len`) the term is pndf_fk_len_energy_grad on the row of the pose's group, and `hs` [S] takes
 // d E / d sigma of this frame; the scales step in len_step_cpu once every frame of the step has read them.
 // With the views of a pndf_project_options8 (`vw`) the term is pndf_fk_views_energy_grad: targets [V][K][2] and confidences [V][K] per pose,
-// with the scales or without.
+// with the scales or without.  With the trajectory of a pndf_project_options9 (`tr`) the root is read from tr->src and its step
+// (pndf_fk_root_smooth_step) goes to tr->dst.
 static float keypoint_grad_cpu(const PndfKeypoints& kp, const KeypointTables& tb, const int* parent, int nj, const float* q, int64_t pose,
                                float* gk, const PndfCameraTerm& cam = PndfCameraTerm(), float dist = 0.f, float tol = 0.f,
-                               const PndfLengths& len = PndfLengths(), float* hs = nullptr, const PndfViews& vw = PndfViews()) {
+                               const PndfLengths& len = PndfLengths(), float* hs = nullptr, const PndfViews& vw = PndfViews(),
+                               const RootTrack* tr = nullptr) {
     float W[PNDF_FK_ROWS * MAXJ + PNDF_MAX_SCALES];
     float E;
     if (vw.any()) {
-        float root[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, groot[7], stepped[7];
+        float root[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, groot[7];
         float* rt = cam.root ? cam.root + pose * 7 : nullptr;
-        if (rt) memcpy(root, rt, sizeof(root));
+        if (rt) memcpy(root, tr ? tr->src + pose * 7 : rt, sizeof(root));
         E = pndf_fk_views_energy_grad(q, nj, parent, tb.rest, kp.K, tb.kpj, tb.kpo, kp.target + pose * vw.V * kp.K * 2,
                                       kp.conf ? kp.conf + pose * vw.V * kp.K : nullptr, rt != nullptr, root, cam.rho, vw.V, vw.table,
                                       len.any() ? len.scale + (pose / len.group) * len.S : nullptr, groot, W, 1);
-        if (cam.moves()) {
-            pndf_fk_root_step(root, groot, cam.nu_rot, cam.nu_trans, dist, tol, stepped);
-            memcpy(rt, stepped, sizeof(stepped));
-        }
+        root_step_cpu(cam, rt, root, groot, dist, tol, pose, tr);
         if (len.any())
             for (int i = 0; i < len.S; ++i) hs[i] = W[pndf_fk_len_row(nj, i)];
     } else if (len.any()) {
         const PndfFkCamera fc{cam.fx, cam.fy, cam.cx, cam.cy, cam.rho, cam.image ? 1 : 0};
-        float root[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, groot[7], stepped[7];
+        float root[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, groot[7];
         float* rt = cam.root ? cam.root + pose * 7 : nullptr;
-        if (rt) memcpy(root, rt, sizeof(root));
+        if (rt) memcpy(root, tr ? tr->src + pose * 7 : rt, sizeof(root));
         E = pndf_fk_len_energy_grad(q, nj, parent, tb.rest, kp.K, tb.kpj, tb.kpo, kp.target + pose * kp.K * kp.dims,
                                     kp.conf ? kp.conf + pose * kp.K : nullptr, rt != nullptr, root, fc,
                                     len.scale + (pose / len.group) * len.S, groot, W, 1);
-        if (cam.moves()) {
-            pndf_fk_root_step(root, groot, cam.nu_rot, cam.nu_trans, dist, tol, stepped);
-            memcpy(rt, stepped, sizeof(stepped));
-        }
+        root_step_cpu(cam, rt, root, groot, dist, tol, pose, tr);
         for (int i = 0; i < len.S; ++i) hs[i] = W[pndf_fk_len_row(nj, i)];
     } else if (cam.any()) {
         const PndfFkCamera fc{cam.fx, cam.fy, cam.cx, cam.cy, cam.rho, cam.image ? 1 : 0};
-        float root[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, groot[7], stepped[7];
+        float root[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, groot[7];
         float* rt = cam.root ? cam.root + pose * 7 : nullptr;
-        if (rt) memcpy(root, rt, sizeof(root));
+        if (rt) memcpy(root, tr ? tr->src + pose * 7 : rt, sizeof(root));
         E = pndf_fk_camera_energy_grad(q, nj, parent, tb.rest, kp.K, tb.kpj, tb.kpo, kp.target + pose * kp.K * kp.dims,
                                        kp.conf ? kp.conf + pose * kp.K : nullptr, rt != nullptr, root, fc, groot, W, 1);
-        if (cam.moves()) {
-            pndf_fk_root_step(root, groot, cam.nu_rot, cam.nu_trans, dist, tol, stepped);
-            memcpy(rt, stepped, sizeof(stepped));
-        }
+        root_step_cpu(cam, rt, root, groot, dist, tol, pose, tr);
     } else {
         E = pndf_fk_energy_grad(q, nj, parent, tb.rest, kp.K, tb.kpj, tb.kpo, kp.target + pose * kp.K * 3,
                                 kp.conf ? kp.conf + pose * kp.K : nullptr, W, 1);
@@ -510,8 +533,12 @@ static void project_step_cpu(float* q, const float* dq, float d, const pndf_proj
 static int project_loop_cpu(pndf_cpu_handle h, const float* q_in, const uint32_t* observed, float* q_out, float* d_last, int64_t B,
                             int steps, const pndf_project_options& o, const PndfData& data = PndfData(),
                             const PndfKeypoints& kp = PndfKeypoints(), const PndfCameraTerm& cam = PndfCameraTerm(),
-                            const PndfLengths& len = PndfLengths(), const PndfViews& vw = PndfViews()) {
+                            const PndfLengths& len = PndfLengths(), const PndfViews& vw = PndfViews(),
+                            const PndfRootSmooth& rs = PndfRootSmooth()) {
     const int NQ = h->nq();
+    // without tracks no pose reads another's root (only the data term of a pndf_project_options9 is possible): its step is in place
+    const RootTrack rtk{&rs, cam.root, cam.root, 0};
+    const RootTrack* tr = rs.any() ? &rtk : nullptr;
     KeypointTables tb;
     if (kp.any()) pndf_fill_keypoint_tables(tb, kp, h->net.nj);
     return guarded(h, [&] {
@@ -522,7 +549,7 @@ static int project_loop_cpu(pndf_cpu_handle h, const float* q_in, const uint32_t
         for (int s = 0; s < steps; ++s) {
             forward_grad_block(*h, qb, nb, nullptr, dd, dqb, true, S);
             for (int p = 0; p < nb; ++p) {
-                if (kp.any()) ee[p] = keypoint_grad_cpu(kp, tb, h->net.parent, h->net.nj, qb + p * NQ, p0 + p, gk, cam, dd[p], o.tol, len, hs, vw);
+                if (kp.any()) ee[p] = keypoint_grad_cpu(kp, tb, h->net.parent, h->net.nj, qb + p * NQ, p0 + p, gk, cam, dd[p], o.tol, len, hs, vw, tr);
                 if (len.moves()) len_step_cpu(len, p0 + p, hs, dd + p, o.tol);      // (without tracks every pose is its own group)
                 project_step_cpu(qb + p * NQ, dqb + p * NQ, dd[p], o, observed ? observed[p0 + p] : 0u, h->net.nj,
                                  data.anchor ? data.anchor + (p0 + p) * NQ : nullptr, data.conf ? data.conf + (p0 + p) * h->net.nj : nullptr, data.mu,
@@ -563,7 +590,7 @@ static int track_loop_cpu(pndf_cpu_handle h, const float* a, int64_t a_stride, c
                           const uint32_t* observed, float* track_out, float* d_last, int64_t P, int32_t T, int steps, float lambda,
                           const pndf_project_options& o, const PndfData& data = PndfData(), const PndfKeypoints& kp = PndfKeypoints(),
                           const PndfCameraTerm& cam = PndfCameraTerm(), const PndfLengths& len = PndfLengths(),
-                          const PndfViews& vw = PndfViews()) {
+                          const PndfViews& vw = PndfViews(), const PndfRootSmooth& rs = PndfRootSmooth()) {
     const int nj = h->net.nj;
     const int64_t nq = h->nq(), B = P * T;
     int rc = PNDF_OK;
@@ -572,6 +599,8 @@ static int track_loop_cpu(pndf_cpu_handle h, const float* a, int64_t a_stride, c
     const int grc = guarded(h, [&] {
         std::vector<float> other((size_t)(B * nq)), dq(steps ? (size_t)(B * nq) : 0), dd((size_t)B, 0.f), ee((size_t)B, 0.f);
         std::vector<float> hs(len.any() ? (size_t)(B * len.S) : 0);      // d E / d sigma of every frame of the step
+        std::vector<float> root2(rs.any() ? (size_t)(B * 7) : 0);      // the second root buffer of a pndf_project_options9: the step is Jacobi
+        RootTrack rtk{&rs, cam.root, root2.data(), T};                 // step s reads the caller's root when s is even
         float* cur = (steps & 1) ? other.data() : track_out;      // `steps` swaps later the track is in track_out
         float* nxt = (steps & 1) ? track_out : other.data();
         if (fill == PNDF_TRACK_GIVEN) memcpy(cur, a, sizeof(float) * (size_t)(B * nq));
@@ -596,7 +625,7 @@ static int track_loop_cpu(pndf_cpu_handle h, const float* a, int64_t a_stride, c
                 const uint32_t held = (nbr != 3 && !data.free_ends) ? ~0u : (observed ? observed[f] : 0u);
                 float gk[4 * MAXJ];
                 if (kp.any()) ee[f] = keypoint_grad_cpu(kp, tb, h->net.parent, nj, cur + f * nq, f, gk, cam, dd[f], o.tol, len,
-                                                        len.any() ? hs.data() + f * len.S : nullptr, vw);
+                                                        len.any() ? hs.data() + f * len.S : nullptr, vw, rs.any() ? &rtk : nullptr);
                 for (int j = 0; j < nj; ++j) {
                     const int64_t i = (f * nj + j) * 4;
                     float u[4];
@@ -615,7 +644,13 @@ static int track_loop_cpu(pndf_cpu_handle h, const float* a, int64_t a_stride, c
                 for (int64_t g = 0; g < B / len.group; ++g)
                     len_step_cpu(len, g, hs.data() + g * len.group * len.S, dd.data() + g * len.group, o.tol);
             std::swap(cur, nxt);
+            if (rs.any()) {
+                const float* was = rtk.src;
+                rtk.src = rtk.dst;
+                rtk.dst = const_cast<float*>(was);
+            }
         }
+        if (rc == PNDF_OK && rs.any() && rtk.src != cam.root) memcpy(cam.root, rtk.src, sizeof(float) * (size_t)(B * 7));      // an odd step count
         if (rc == PNDF_OK && d_last) memcpy(d_last, dd.data(), sizeof(float) * B);
         if (rc == PNDF_OK && kp.energy) memcpy(kp.energy, ee.data(), sizeof(float) * B);
     });
@@ -633,7 +668,8 @@ extern "C" int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* 
     PndfCameraTerm cam;            // a pndf_project_options6 the camera and the root besides (host memory): image fitting for any joint tree
     PndfLengths len;               // a pndf_project_options7 the bone lengths besides (host memory): one row of scales per track or per pose
     PndfViews vw;                  // a pndf_project_options8 the views besides (host memory): pixels of the same frame in several cameras
-    if (const char* why = pndf_check_project_options8(opt, B, h->net.nj, o, observed, tracks, data, kp, cam, len, vw)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    PndfRootSmooth rs;             // a pndf_project_options9 the root's trajectory besides (host memory): the roots of a track coupled, an anchor
+    if (const char* why = pndf_check_project_options9(opt, B, h->net.nj, o, observed, tracks, data, kp, cam, len, vw, rs)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (!tracks.frames && !observed && !data.any() && !kp.any() && !kp.energy && pndf_project_options_plain(o))
         return pndf_project_cpu(h, q_in, q_out, d_last, B, steps);
     if (int rc = check(h, q_in, B)) return rc;
@@ -642,14 +678,15 @@ extern "C" int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* 
     if (const char* why = pndf_check_keypoints_apart(kp, q_out, B, h->net.nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (const char* why = pndf_check_root_apart(cam, data, kp, q_in, q_out, B, h->net.nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (const char* why = pndf_check_lengths_apart(len, cam, data, kp, q_in, q_out, B, h->net.nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
-    if (!tracks.frames) return project_loop_cpu(h, q_in, observed, q_out, d_last, B, steps, o, data, kp, cam, len, vw);
+    if (const char* why = pndf_check_root_anchor_apart(rs, cam, q_out, B, h->net.nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (!tracks.frames) return project_loop_cpu(h, q_in, observed, q_out, d_last, B, steps, o, data, kp, cam, len, vw, rs);
     if (B == 0) return PNDF_OK;
     const int64_t nq = h->nq(), T = tracks.frames;
     if ((uintptr_t)q_in < (uintptr_t)(q_out + B * nq) && (uintptr_t)q_out < (uintptr_t)(q_in + B * nq))
         return pndf_fail(h, PNDF_ERR_BAD_ARG, "q_out must not overlap q_in when pndf_project_options3.frames > 0: a step reads the neighbour "
                                               "frames of its input");
     return track_loop_cpu(h, q_in, T * nq, q_in + (T - 1) * nq, T * nq, tracks.fill, observed, q_out, d_last, B / T, (int32_t)T, steps,
-                          tracks.lambda, o, data, kp, cam, len, vw);
+                          tracks.lambda, o, data, kp, cam, len, vw, rs);
 }
 
 // Host twin of pndf_interpolate (include/posendf_amd_interpolation.h): track_loop_cpu on the 21-joint table; with lambda == 0 this is

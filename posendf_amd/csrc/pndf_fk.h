@@ -360,6 +360,91 @@ PNDF_HD void pndf_fk_root_step(const float* root, const float* groot, float nu_r
         }
 }
 
+// The root's step of a pndf_project_options9 (DESIGN.md section 2j "Root trajectory"): pndf_fk_root_step above -- which stays as it is, its
+// bits are pinned -- with the root coupled to the roots of the neighbour frames of its track and drawn towards an anchor.  root [7] at the
+// step's input, groot as above -> out [7], which must not be `root` or a neighbour's row: the step is Jacobi, every frame reads its
+// neighbours as the step before left them.  nm / np: the root rows of frames k - 1 / k + 1, read only where `nbr` has bit 0 / bit 1 and
+// the part's lambda and nu are positive; A: the anchor's row, a part of it read only when that part's mu and nu are positive.  nbr 3: an
+// interior frame, 1 or 2: an end frame with its one neighbour, 0: none.  The coupling and the data term MIRROR pndf_fit_quat of
+// pndf_interp.h under PNDF_TRACK_FREE_ENDS, operation for operation: that function's coupling sits between a descent along dist * G and
+// a renorm mode, neither of which the root has, so it does not separate.  The translation takes the same three parts per component
+// without alignment or normalisation.  A pose that rests under tol keeps its root; a part whose nu is zero keeps its bits.
+PNDF_HD void pndf_fk_root_smooth_step(const float* root, const float* groot, float nu_rot, float nu_trans, float dist, float tol,
+                                      const float* nm, const float* np, int nbr, float lambda_rot, float lambda_trans, const float* A,
+                                      float mu_rot, float mu_trans, float* out) {
+#pragma clang fp contract(off)
+    for (int i = 0; i < 7; ++i) out[i] = root[i];
+    if (tol > 0.f && dist < tol) return;
+    if (nu_rot > 0.f) {
+        float u[4];
+        for (int i = 0; i < 4; ++i) {
+            const float t = nu_rot * groot[i];
+            u[i] = root[i] - t;
+        }
+        if (lambda_rot > 0.f && nbr == 3) {
+            float m_[4], p_[4], am[4], ap[4];
+            for (int i = 0; i < 4; ++i) {
+                m_[i] = nm[i];
+                p_[i] = np[i];
+            }
+            pndf_quat_align(root, m_, am);
+            pndf_quat_align(root, p_, ap);
+            for (int i = 0; i < 4; ++i) {
+                const float sum = am[i] + ap[i];
+                const float h = 0.5f * sum;
+                const float m = h - root[i];
+                const float lm = lambda_rot * m;
+                u[i] = u[i] + lm;
+            }
+        } else if (lambda_rot > 0.f && nbr != 0) {
+            float n[4], an[4];
+            for (int i = 0; i < 4; ++i) n[i] = nbr == 1 ? nm[i] : np[i];
+            pndf_quat_align(root, n, an);
+            for (int i = 0; i < 4; ++i) {
+                const float m = an[i] - root[i];
+                const float h = 0.5f * m;
+                const float lm = lambda_rot * h;
+                u[i] = u[i] + lm;
+            }
+        }
+        if (mu_rot > 0.f) {
+            float a[4], aa[4];
+            for (int i = 0; i < 4; ++i) a[i] = A[i];
+            pndf_quat_align(root, a, aa);
+            for (int i = 0; i < 4; ++i) {
+                const float m = aa[i] - root[i];
+                const float wm = mu_rot * m;
+                u[i] = u[i] + wm;
+            }
+        }
+        (void)pndf_fk_unit(u, out);
+    }
+    if (nu_trans > 0.f)
+        for (int x = 4; x < 7; ++x) {
+            const float t = nu_trans * groot[x];
+            float u = root[x] - t;
+            if (lambda_trans > 0.f && nbr == 3) {
+                const float sum = nm[x] + np[x];
+                const float h = 0.5f * sum;
+                const float m = h - root[x];
+                const float lm = lambda_trans * m;
+                u = u + lm;
+            } else if (lambda_trans > 0.f && nbr != 0) {
+                const float n = nbr == 1 ? nm[x] : np[x];
+                const float m = n - root[x];
+                const float h = 0.5f * m;
+                const float lm = lambda_trans * h;
+                u = u + lm;
+            }
+            if (mu_trans > 0.f) {
+                const float m = A[x] - root[x];
+                const float wm = mu_trans * m;
+                u = u + wm;
+            }
+            out[x] = u;
+        }
+}
+
 // ---- Bone lengths of a pndf_project_options7 (DESIGN.md section 2j "Bone lengths"): the camera term above on a tree whose rest offsets and
 // keypoint offsets are scaled, t'_j = sigma_j t_j and o'_k = sigma_{J+k} o_k per component, and the gradient of E with respect to the
 // S = J + K scales.  Stated once beside the other terms, whose functions above stay as they are (their bits are pinned); with every scale

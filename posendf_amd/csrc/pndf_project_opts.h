@@ -536,6 +536,95 @@ inline const char* pndf_check_project_options8(const pndf_project_options* opt, 
     return nullptr;
 }
 
+// The root trajectory of a pndf_project_options9, validated: without a keypoint term (kp_target NULL or nu == 0) every weight stays 0 and
+// nothing of the root or the anchor is read or written; `named_anchor` is what the struct names either way (pndf_check_root_anchor_apart
+// refuses its overlaps).
+struct PndfRootSmooth {
+    const float* anchor = nullptr;      // [B,7], or null: no data term
+    const float* named_anchor = nullptr;
+    float lambda_rot = 0.f, lambda_trans = 0.f, mu_rot = 0.f, mu_trans = 0.f;
+    // whether a call needs the coupled form of the root's step at all: without it it is the call of the 224-byte struct
+    bool any() const { return lambda_rot > 0.f || lambda_trans > 0.f || mu_rot > 0.f || mu_trans > 0.f; }
+};
+
+// The checker of the same two entry points for all nine structs: a pndf_project_options9 brings the root's trajectory besides.  Returns
+// nullptr and fills `out`, `observed`, `tracks`, `data`, `kp`, `cam`, `len`, `vw` and `rs`, or the reason the struct is refused.  That
+// root_anchor does not overlap root or q_out is the caller's to check (pndf_check_root_anchor_apart).
+inline const char* pndf_check_project_options9(const pndf_project_options* opt, int64_t B, int nj, pndf_project_options& out,
+                                               const uint32_t*& observed, PndfTracks& tracks, PndfData& data, PndfKeypoints& kp,
+                                               PndfCameraTerm& cam, PndfLengths& len, PndfViews& vw, PndfRootSmooth& rs) {
+    rs = PndfRootSmooth();
+    if (!opt || opt->struct_size != sizeof(pndf_project_options9)) {
+        const char* why = pndf_check_project_options8(opt, B, nj, out, observed, tracks, data, kp, cam, len, vw);
+        if (why && opt && opt->struct_size != sizeof(pndf_project_options) && opt->struct_size != sizeof(pndf_project_options2) &&
+            opt->struct_size != sizeof(pndf_project_options3) && opt->struct_size != sizeof(pndf_project_options4) &&
+            opt->struct_size != sizeof(pndf_project_options5) && opt->struct_size != sizeof(pndf_project_options6) &&
+            opt->struct_size != sizeof(pndf_project_options7) && opt->struct_size != sizeof(pndf_project_options8))
+            return "pndf_project_options.struct_size is none of sizeof(pndf_project_options), sizeof(pndf_project_options2), "
+                   "sizeof(pndf_project_options3), sizeof(pndf_project_options4), sizeof(pndf_project_options5), "
+                   "sizeof(pndf_project_options6), sizeof(pndf_project_options7), sizeof(pndf_project_options8) and "
+                   "sizeof(pndf_project_options9): fill the struct with pndf_default_project_options";
+        return why;
+    }
+    const pndf_project_options9* o9 = (const pndf_project_options9*)opt;
+    // what the struct says of itself first: a refusal here has filled nothing
+    out = pndf_project_options();
+    observed = nullptr;
+    tracks = PndfTracks();
+    data = PndfData();
+    kp = PndfKeypoints();
+    cam = PndfCameraTerm();
+    len = PndfLengths();
+    for (int i = 0; i < PNDF_MAX_SCALES; ++i) len.rate[i] = 1.0f;
+    vw.V = 0;
+    auto unit = [](float v) { return v >= 0.f && v <= 1.f; };      // false for a NaN
+    const pndf_project_options6& o6 = o9->base8.base7.base6;
+    const bool rot = o9->lambda_rot > 0.f || o9->mu_rot > 0.f, trans = o9->lambda_trans > 0.f || o9->mu_trans > 0.f;
+    if (o9->reserved5 != 0u) return "pndf_project_options9.reserved5 must be 0";
+    if (!unit(o9->lambda_rot)) return "pndf_project_options9.lambda_rot must lie in [0, 1] (and not be NaN)";
+    if (!unit(o9->lambda_trans)) return "pndf_project_options9.lambda_trans must lie in [0, 1] (and not be NaN)";
+    if (!unit(o9->mu_rot)) return "pndf_project_options9.mu_rot must lie in [0, 1] (and not be NaN)";
+    if (!unit(o9->mu_trans)) return "pndf_project_options9.mu_trans must lie in [0, 1] (and not be NaN)";
+    if (o9->lambda_rot > 0.f && o6.base5.base4.base3.frames == 0)
+        return "pndf_project_options9.lambda_rot must be 0 when pndf_project_options3.frames is 0 (no tracks)";
+    if (o9->lambda_trans > 0.f && o6.base5.base4.base3.frames == 0)
+        return "pndf_project_options9.lambda_trans must be 0 when pndf_project_options3.frames is 0 (no tracks)";
+    // (a nu that is negative or not finite is base8's to refuse, below, with its own text)
+    if (o9->lambda_rot > 0.f && o6.nu_rot == 0.f) return "pndf_project_options9.lambda_rot must be 0 when pndf_project_options6.nu_rot is 0: the rotation is held";
+    if (o9->mu_rot > 0.f && o6.nu_rot == 0.f) return "pndf_project_options9.mu_rot must be 0 when pndf_project_options6.nu_rot is 0: the rotation is held";
+    if (o9->lambda_trans > 0.f && o6.nu_trans == 0.f) return "pndf_project_options9.lambda_trans must be 0 when pndf_project_options6.nu_trans is 0: the translation is held";
+    if (o9->mu_trans > 0.f && o6.nu_trans == 0.f) return "pndf_project_options9.mu_trans must be 0 when pndf_project_options6.nu_trans is 0: the translation is held";
+    if ((rot || trans) && !o6.root) return "pndf_project_options6.root must not be NULL when a lambda or mu of pndf_project_options9 is positive";
+    if ((o9->mu_rot > 0.f || o9->mu_trans > 0.f) && !o9->root_anchor)
+        return "pndf_project_options9.root_anchor must not be NULL when mu_rot or mu_trans is positive";
+    if (o9->root_anchor && !(o9->mu_rot > 0.f || o9->mu_trans > 0.f))
+        return "pndf_project_options9.root_anchor must be NULL when mu_rot and mu_trans are 0 (no data term)";
+    if ((uintptr_t)o9->root_anchor & 3) return "pndf_project_options9.root_anchor must be 4-byte aligned";
+    pndf_project_options8 base8 = o9->base8;
+    base8.base7.base6.base5.base4.base3.base2.base.struct_size = (uint32_t)sizeof(pndf_project_options8);
+    if (const char* why = pndf_check_project_options8(&base8.base7.base6.base5.base4.base3.base2.base, B, nj, out, observed, tracks, data, kp, cam, len, vw)) return why;
+    rs.named_anchor = o9->root_anchor;
+    if (kp.any()) {
+        rs.anchor = o9->root_anchor;
+        rs.lambda_rot = o9->lambda_rot;
+        rs.lambda_trans = o9->lambda_trans;
+        rs.mu_rot = o9->mu_rot;
+        rs.mu_trans = o9->mu_trans;
+    }
+    return nullptr;
+}
+
+// What the entry point adds to that checker, knowing B and the poses: every step reads root_anchor [B,7] and writes root and q_out, so it
+// may share memory with neither.  nullptr, or the reason.  The arrays are compared as the struct names them.
+inline const char* pndf_check_root_anchor_apart(const PndfRootSmooth& rs, const PndfCameraTerm& cam, const float* q_out, int64_t B, int nj) {
+    if (B <= 0 || !rs.named_anchor) return nullptr;
+    const uintptr_t r0 = (uintptr_t)rs.named_anchor, r1 = (uintptr_t)(rs.named_anchor + B * 7);
+    auto meets = [&](const float* p, int64_t floats) { return p && (uintptr_t)p < r1 && r0 < (uintptr_t)(p + floats); };
+    if (meets(cam.named_root, B * 7)) return "pndf_project_options9.root_anchor must not overlap pndf_project_options6.root: every step writes the root";
+    if (meets(q_out, B * nj * 4)) return "pndf_project_options9.root_anchor must not overlap q_out";
+    return nullptr;
+}
+
 // The host tables of validated keypoints as the step functions of pndf_fk.h take them: kp_joint and kp_offset with their defaults
 // filled in (keypoint k is joint k; zeros).  T: anything with rest [96], kpj [64] and kpo [192] -- the kernel's argument struct, the
 // host twin's local copy.

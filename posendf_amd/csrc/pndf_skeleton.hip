@@ -32,7 +32,10 @@
 //                              with the bone lengths of a pndf_project_options7 its sixth instantiation pndf_skel_enc_rev_len_kernel:
 //                              the camera term on the tree scaled by the row of the lane's group, d E / d sigma of the frame left in
 //                              S workspace rows; with the views of a pndf_project_options8 its seventh instantiation
-//                              pndf_skel_enc_rev_views_kernel: the same, with the pixels of V cameras in front of the root's frame
+//                              pndf_skel_enc_rev_views_kernel: the same, with the pixels of V cameras in front of the root's frame;
+//                              with the root trajectory of a pndf_project_options9 its eighth instantiation
+//                              pndf_skel_enc_rev_root_kernel: any of those three terms, and the root stepped out of place, coupled to
+//                              the roots of the neighbour frames and drawn towards an anchor
 //   pndf_skel_len_step_kernel  once per chunk and step behind that kernel (only when nu_len > 0): the sum of those rows over the frames
 //                              of every group in pndf_fk.h's order and the step of the scales in place
 //   pndf_skel_fill_kernel      the fill of a track from its two end frames, once per chunk in front of the steps
@@ -139,6 +142,16 @@ struct SkViewsArgs : SkLenArgs {
 };
 static_assert(sizeof(SkViewsArgs) <= 4096, "a kernel's arguments are at most 4,096 bytes");
 
+// SkViewsArgs with the root trajectory of a pndf_project_options9 (SK_PROJECT), which pndf_skel_enc_rev_root_kernel alone takes, derived
+// for the same reason.  With it `root` is the buffer the step READS (the lane's row and its neighbours') and `root_out` the one it writes.
+struct SkRootArgs : SkViewsArgs {
+    float* root_out;                 // [n][7]: the other root buffer of the Jacobi step; null: no trajectory term
+    const float* root_anchor;        // the chunk's anchor [n][7], or null (no data term)
+    float lambda_rot, lambda_trans;  // the neighbour coupling of the root's rotation / translation
+    float mu_rot, mu_trans;          // the weights of the data term towards root_anchor
+};
+static_assert(sizeof(SkRootArgs) <= 4096, "a kernel's arguments are at most 4,096 bytes");
+
 // What pndf_skel_len_step_kernel takes: the rows h [S][ld] the reverse left, the chunk's distance row and the scales to step in place
 struct SkLenStepArgs {
     float* bone_scale;        // [G][S]
@@ -231,13 +244,18 @@ extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_fwd_kernel(SkArg
 // of the lane's group and leaves d E / d sigma of the lane's frame in the rows behind the tree's; the scales step in their own kernel.
 // SK_REV_VIEWS is the instantiation of a pndf_project_options8 with views: SK_REV_LEN with pndf_fk.h's several-camera term (targets
 // [V][K][2] and confidences [V][K] per lane); the group's row of scales may be missing (all ones).
-enum { SK_REV_PLAIN = 0, SK_REV_TRACKS = 1, SK_REV_DENOISE = 2, SK_REV_FIT = 3, SK_REV_IMAGE = 4, SK_REV_LEN = 5, SK_REV_VIEWS = 6 };
+// SK_REV_ROOT is the instantiation of a pndf_project_options9 with a positive lambda or mu of the root: the term of SK_REV_IMAGE, SK_REV_LEN
+// or SK_REV_VIEWS -- a wave-uniform choice from V and bone_scale, as sk_run_chunk chooses among those kernels -- and pndf_fk.h's
+// pndf_fk_root_smooth_step from `root` to `root_out` in place of the root's step; the neighbours' and the anchor's rows are loaded inside
+// that step, behind the energy and its reverse.
+enum { SK_REV_PLAIN = 0, SK_REV_TRACKS = 1, SK_REV_DENOISE = 2, SK_REV_FIT = 3, SK_REV_IMAGE = 4, SK_REV_LEN = 5, SK_REV_VIEWS = 6, SK_REV_ROOT = 7 };
 template <int KIND, class Args>
 __device__ __forceinline__ void skel_enc_rev(const Args& e) {
     constexpr bool TRACKS = KIND == SK_REV_TRACKS;
     constexpr bool LEN = KIND == SK_REV_LEN;
     constexpr bool VIEWS = KIND == SK_REV_VIEWS;
-    constexpr bool IMAGE = KIND == SK_REV_IMAGE || LEN || VIEWS;
+    constexpr bool ROOT = KIND == SK_REV_ROOT;
+    constexpr bool IMAGE = KIND == SK_REV_IMAGE || LEN || VIEWS || ROOT;
     constexpr bool FIT = KIND == SK_REV_FIT || IMAGE;
     constexpr bool DENOISE = KIND == SK_REV_DENOISE || FIT;
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -282,7 +300,19 @@ __device__ __forceinline__ void skel_enc_rev(const Args& e) {
         if (e.root)
 #pragma unroll
             for (int i = 0; i < 7; ++i) root[i] = e.root[c * 7 + i];
-        if constexpr (VIEWS)
+        if constexpr (ROOT) {
+            if (e.V > 0)
+                energy = pndf_fk_views_energy_grad(q, e.nj, e.parent, e.rest, e.K, e.kpj, e.kpo, e.kp_target + c * (e.V * e.K * 2),
+                                                   e.kp_conf ? e.kp_conf + c * (e.V * e.K) : nullptr, e.root != nullptr, root, e.cam.rho, e.V,
+                                                   e.views, e.bone_scale ? e.bone_scale + (c / e.group) * e.S : nullptr, groot, e.fk + c, e.ld);
+            else if (e.bone_scale)
+                energy = pndf_fk_len_energy_grad(q, e.nj, e.parent, e.rest, e.K, e.kpj, e.kpo, e.kp_target + c * (e.K * (e.cam.image ? 2 : 3)),
+                                                 e.kp_conf ? e.kp_conf + c * e.K : nullptr, e.root != nullptr, root, e.cam,
+                                                 e.bone_scale + (c / e.group) * e.S, groot, e.fk + c, e.ld);
+            else
+                energy = pndf_fk_camera_energy_grad(q, e.nj, e.parent, e.rest, e.K, e.kpj, e.kpo, e.kp_target + c * (e.K * (e.cam.image ? 2 : 3)),
+                                                    e.kp_conf ? e.kp_conf + c * e.K : nullptr, e.root != nullptr, root, e.cam, groot, e.fk + c, e.ld);
+        } else if constexpr (VIEWS)
             energy = pndf_fk_views_energy_grad(q, e.nj, e.parent, e.rest, e.K, e.kpj, e.kpo, e.kp_target + c * (e.V * e.K * 2),
                                                e.kp_conf ? e.kp_conf + c * (e.V * e.K) : nullptr, e.root != nullptr, root, e.cam.rho, e.V,
                                                e.views, e.bone_scale ? e.bone_scale + (c / e.group) * e.S : nullptr, groot, e.fk + c, e.ld);
@@ -355,7 +385,16 @@ __device__ __forceinline__ void skel_enc_rev(const Args& e) {
     if (e.d_out) e.d_out[c] = dist;
     if constexpr (FIT)
         if (e.kp_energy) e.kp_energy[c] = energy;
-    if constexpr (IMAGE)
+    if constexpr (ROOT) {      // (the host launches this kernel only with a root, a positive root weight and a positive lambda or mu)
+        const int k = e.frames ? (int)(c % e.frames) : 0;
+        const int rn = e.frames ? ((k > 0 ? 1 : 0) | (k < e.frames - 1 ? 2 : 0)) : 0;
+        const float* row = e.root + c * 7;
+        float stepped[7];
+        pndf_fk_root_smooth_step(root, groot, e.nu_rot, e.nu_trans, dist, e.tol, row - 7, row + 7, rn, e.lambda_rot, e.lambda_trans,
+                                 e.root_anchor + c * 7, e.mu_rot, e.mu_trans, stepped);
+#pragma unroll
+        for (int i = 0; i < 7; ++i) e.root_out[c * 7 + i] = stepped[i];
+    } else if constexpr (IMAGE)
         if (e.root && (e.nu_rot > 0.f || e.nu_trans > 0.f)) {
             float stepped[7];
             pndf_fk_root_step(root, groot, e.nu_rot, e.nu_trans, dist, e.tol, stepped);
@@ -371,6 +410,7 @@ extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_fit_kernel(S
 extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_image_kernel(SkImageArgs e) { skel_enc_rev<SK_REV_IMAGE>(e); }
 extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_len_kernel(SkLenArgs e) { skel_enc_rev<SK_REV_LEN>(e); }
 extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_views_kernel(SkViewsArgs e) { skel_enc_rev<SK_REV_VIEWS>(e); }
+extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_root_kernel(SkRootArgs e) { skel_enc_rev<SK_REV_ROOT>(e); }
 
 // The step of the scales of a chunk (pndf_fk.h: pndf_fk_len_group_sum's order, pndf_fk_len_step).  Frames per group n <= 64: lanes own
 // (group, scale) pairs and sum their frames in order.  n > 64: one workgroup per (group, scale), lane b sums block b of 64 frames, lane 0
@@ -478,6 +518,7 @@ struct SkLayout {
     int64_t Q2;      // the second pose buffer [nc][4 J] of the out-of-place steps of a pndf_project_options3
     int64_t FK;      // the rows [24 J][nc] of the forward kinematics and its adjoints of a pndf_project_options5 (pndf_fk.h), and behind
                      // them the rows [96][nc] of d E / d sigma of a pndf_project_options7
+    int64_t ROOT;    // the second root buffer [nc][7] of the Jacobi steps of a pndf_project_options9
     int64_t total;
 };
 
@@ -504,12 +545,13 @@ SkLayout sk_layout(const pndf_skel_plan* h, int64_t B) {
     l.P[1] = c.take((int64_t)h->maxw * l.nc);
     l.Q2 = c.take(nq * l.nc);
     l.FK = c.take(((int64_t)PNDF_FK_ROWS * h->nj + PNDF_MAX_SCALES) * l.nc);      // the tree's rows, then pndf_fk_len_row's
+    l.ROOT = c.take(7 * l.nc);
     l.total = c.o;
     return l;
 }
 
 // One evaluation of a chunk of n poses at `q`: the 2 + 2 L launches (the forward alone: 1 + L and the copy of the output row)
-void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const SkViewsArgs& e, hipStream_t st) {
+void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const SkRootArgs& e, hipStream_t st) {
     const int n = (int)e.n;
     TrunkWeights w{};
     TrunkBuffers b{};
@@ -521,6 +563,7 @@ void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const S
     const SkFitArgs& fit = e;
     const SkImageArgs& image = e;
     const SkLenArgs& lengths = e;
+    const SkViewsArgs& views = e;
     hipLaunchKernelGGL(pndf_skel_enc_fwd_kernel, dim3(blocks(n)), dim3(256), 0, st, plain);
     trunk_forward(SK_GEMM, *h, w, b, st);
     if (e.mode == SK_FORWARD) {
@@ -528,7 +571,8 @@ void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const S
         return;
     }
     trunk_reverse(SK_GEMM, *h, w, b, st);      // grad_out scales the result in the encoder's reverse
-    if (e.mode == SK_PROJECT && e.kp_target && e.V > 0) hipLaunchKernelGGL(pndf_skel_enc_rev_views_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
+    if (e.mode == SK_PROJECT && e.kp_target && e.root_out) hipLaunchKernelGGL(pndf_skel_enc_rev_root_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
+    else if (e.mode == SK_PROJECT && e.kp_target && e.V > 0) hipLaunchKernelGGL(pndf_skel_enc_rev_views_kernel, dim3(blocks(n)), dim3(256), 0, st, views);
     else if (e.mode == SK_PROJECT && e.kp_target && e.bone_scale) hipLaunchKernelGGL(pndf_skel_enc_rev_len_kernel, dim3(blocks(n)), dim3(256), 0, st, lengths);
     else if (e.mode == SK_PROJECT && e.kp_target && (e.root || e.cam.image)) hipLaunchKernelGGL(pndf_skel_enc_rev_image_kernel, dim3(blocks(n)), dim3(256), 0, st, image);
     else if (e.mode == SK_PROJECT && e.kp_target) hipLaunchKernelGGL(pndf_skel_enc_rev_fit_kernel, dim3(blocks(n)), dim3(256), 0, st, fit);
@@ -537,8 +581,8 @@ void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const S
     else hipLaunchKernelGGL(pndf_skel_enc_rev_kernel, dim3(blocks(n)), dim3(256), 0, st, plain);
 }
 
-SkViewsArgs sk_args(const pndf_skel_plan* h, const SkLayout& l, float* ws, int mode) {
-    SkViewsArgs e;
+SkRootArgs sk_args(const pndf_skel_plan* h, const SkLayout& l, float* ws, int mode) {
+    SkRootArgs e;
     memset(&e, 0, sizeof(e));
     e.wenc = h->d_blob;
     e.X = ws + l.X; e.act0 = ws + l.act0; e.U0 = ws + l.U0; e.Gx = ws + l.Gx; e.dist = ws + l.dist; e.fk = ws + l.FK;
@@ -648,7 +692,7 @@ extern "C" int pndf_skel_forward(pndf_skel_handle h, const float* q, float* d, i
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     float* ws = (float*)workspace;
-    SkViewsArgs e = sk_args(h, l, ws, SK_FORWARD);
+    SkRootArgs e = sk_args(h, l, ws, SK_FORWARD);
     for (int64_t c0 = 0; c0 < B; c0 += l.nc) {
         e.n = B - c0 < l.nc ? B - c0 : l.nc;
         e.q = q + c0 * h->nj * BONE;
@@ -671,7 +715,7 @@ extern "C" int pndf_skel_forward_grad(pndf_skel_handle h, const float* q, const 
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     float* ws = (float*)workspace;
-    SkViewsArgs e = sk_args(h, l, ws, SK_GRAD);
+    SkRootArgs e = sk_args(h, l, ws, SK_GRAD);
     for (int64_t c0 = 0; c0 < B; c0 += l.nc) {
         e.n = B - c0 < l.nc ? B - c0 : l.nc;
         e.q = q + c0 * h->nj * BONE;
@@ -694,7 +738,8 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
     PndfCameraTerm cam;            // a pndf_project_options6 the camera and the root besides (image fitting): the roots per pose in device memory
     PndfLengths len;               // a pndf_project_options7 the bone lengths besides: the scales per group in device memory, the rates in host memory
     PndfViews vw;                  // a pndf_project_options8 the views besides: the table in host memory, targets [B,V,K,2] and confidences [B,V,K] in device memory
-    if (const char* why = pndf_check_project_options8(opt, B, h->nj, o, observed, tracks, data, kp, cam, len, vw)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    PndfRootSmooth rs;             // a pndf_project_options9 the root's trajectory besides: the anchor [B,7] in device memory
+    if (const char* why = pndf_check_project_options9(opt, B, h->nj, o, observed, tracks, data, kp, cam, len, vw, rs)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (steps < 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count");
     SkLayout l;
     if (B > 0 && (!q_in || !q_out)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose pointer");
@@ -708,6 +753,7 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
     if (const char* why = pndf_check_keypoints_apart(kp, q_out, B, h->nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (const char* why = pndf_check_root_apart(cam, data, kp, q_in, q_out, B, h->nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (const char* why = pndf_check_lengths_apart(len, cam, data, kp, q_in, q_out, B, h->nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (const char* why = pndf_check_root_anchor_apart(rs, cam, q_out, B, h->nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (const int rc = sk_check(h, B, workspace, workspace_bytes, l); rc != PNDF_OK || B == 0) return rc;
     PndfRange range("pndf_skel_project");
     DeviceGuard guard(h->device);
@@ -722,7 +768,7 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
         return PNDF_OK;
     }
     float* ws = (float*)workspace;
-    SkViewsArgs e = sk_args(h, l, ws, SK_PROJECT);
+    SkRootArgs e = sk_args(h, l, ws, SK_PROJECT);
     e.step_size = o.step_size; e.tol = o.tol; e.renorm = (int)o.renorm;
     e.frames = tracks.frames; e.lambda = tracks.lambda;
     e.mu = data.mu; e.flags = data.free_ends ? (uint32_t)PNDF_TRACK_FREE_ENDS : 0u;
@@ -736,6 +782,7 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
         e.V = vw.V;
         for (int i = 0; i < PNDF_FK_MAX_VIEWS * PNDF_FK_VIEW_FLOATS; ++i) e.views[i] = vw.table[i];
     }
+    if (rs.any()) { e.lambda_rot = rs.lambda_rot; e.lambda_trans = rs.lambda_trans; e.mu_rot = rs.mu_rot; e.mu_trans = rs.mu_trans; }
     SkLenStepArgs ls;
     memset(&ls, 0, sizeof(ls));
     if (len.any()) {
@@ -763,6 +810,10 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
         // q_out; step 0 reads q_in, or the buffer the fill wrote.
         float* buf[2] = {q_out + c0 * nq, tracks.frames ? ws + l.Q2 : q_out + c0 * nq};
         const float* cur = q_in + c0 * nq;
+        // With the trajectory of a pndf_project_options9 the root's step is out of place too: step s reads rbuf[s & 1] and writes the other
+        // buffer, step 0 reads the caller's rows; after an odd step count the result is copied back into them.
+        float* rbuf[2] = {cam.root ? cam.root + c0 * 7 : nullptr, ws + l.ROOT};
+        e.root_anchor = rs.anchor ? rs.anchor + c0 * 7 : nullptr;
         if (filled) {
             float* dst = buf[steps & 1];      // what step 0 does not write; q_out itself when there is no step
             hipLaunchKernelGGL(pndf_skel_fill_kernel, dim3(blocks(e.n * h->nj)), dim3(256), 0, st, cur, dst, e.n * (int64_t)h->nj, h->nj,
@@ -774,6 +825,10 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
             e.out = buf[(steps - 1 - s) & 1];
             e.d_out = (d_last && s == steps - 1) ? d_last + c0 : nullptr;
             e.kp_energy = (kp.any() && kp.energy && s == steps - 1) ? kp.energy + c0 : nullptr;
+            if (rs.any()) {
+                e.root = rbuf[s & 1];
+                e.root_out = rbuf[(s + 1) & 1];
+            }
             sk_run_chunk(h, l, ws, e, st);
             if (len.moves()) {      // behind the reverse on the same stream: the frames of this step have read the scales
                 ls.bone_scale = len.scale + (c0 / len.group) * len.S;
@@ -784,6 +839,8 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
             }
             cur = e.out;
         }
+        if (rs.any() && (steps & 1))
+            hipLaunchKernelGGL(pndf_skel_copy_kernel, dim3(blocks(e.n * 7)), dim3(256), 0, st, rbuf[1], rbuf[0], e.n * (int64_t)7);
     }
     return pndf_check_launch(h, "pndf_skel_project");
 }

@@ -15,7 +15,7 @@ import numpy as np
 # public names stay importable from here.  `torch` comes from there too: abi imports it before the library is loaded (None without it).
 from .abi import (ACT_CODES, DEBUG_EXPERIMENT_WORDS, DEBUG_EXPORTS, EXPERIMENT_WORDS, EXPORTS, INTERP_MODES, METRIC_CODES,  # noqa: F401
                   NOISE_CODES, PRECISION_CODES, RENORM_CODES, Camera, DenoiseWeights, KeypointOpts, OnlineOpts, PndfConfig, PndfError,
-                  ProjectOptions, ProjectOptions2, ProjectOptions3, ProjectOptions4, ProjectOptions5, ProjectOptions6, ProjectOptions7, ProjectOptions8, KP_IMAGE, LEN_PER_POSE, MAX_VIEWS, TRACK_FILLS, TRACK_FREE_ENDS, debug_library_path, experiment_word, load_library, torch)
+                  ProjectOptions, ProjectOptions2, ProjectOptions3, ProjectOptions4, ProjectOptions5, ProjectOptions6, ProjectOptions7, ProjectOptions8, ProjectOptions9, KP_IMAGE, LEN_PER_POSE, MAX_VIEWS, TRACK_FILLS, TRACK_FREE_ENDS, debug_library_path, experiment_word, load_library, torch)
 
 
 def stream_handle(device) -> int:
@@ -232,13 +232,41 @@ def project_options8(lib, *args, views=None, **kw):
     opt = ProjectOptions8()
     if views is not None and kw.get("image") is None:
         kw = dict(kw, image=True)
-    opt.base7 = project_options7(lib, *args, **kw)
+    opt._base7 = project_options7(lib, *args, **kw)      # (kept: it owns the rates that the copy below points to)
+    opt.base7 = opt._base7
     opt.base7.base6.base5.base4.base3.base2.base.struct_size = ctypes.sizeof(opt)
     if views is not None:
         opt._views = view_table(views)      # host memory that lives as long as the struct
         opt.views = opt._views.ctypes.data if opt._views.size else None
         opt.n_views = int(opt._views.shape[0])
     return opt
+
+
+def project_options9(lib, *args, root_smooth=None, root_anchor_ptr=None, root_data=None, **kw):
+    """pndf_project_options9 (include/posendf_amd.h): `project_options8`'s arguments, and the root's trajectory over the frames of a track --
+    `root_smooth` = (lambda_rot, lambda_trans): the coupling of a frame's root to its neighbour frames'; `root_anchor_ptr`: an observed or
+    earlier trajectory [B,7] (device memory for the skeleton unit, host memory for the twin); `root_data` = (mu_rot, mu_trans): the weights
+    of the data term towards it.  The values are checked by the library."""
+    opt = ProjectOptions9()
+    opt._base8 = project_options8(lib, *args, **kw)      # (kept: it owns the view table that the copy below points to)
+    opt.base8 = opt._base8
+    opt.base8.base7.base6.base5.base4.base3.base2.base.struct_size = ctypes.sizeof(opt)
+    opt.root_anchor = root_anchor_ptr
+    opt.lambda_rot, opt.lambda_trans = (float(v) for v in (root_smooth or (0.0, 0.0)))
+    opt.mu_rot, opt.mu_trans = (float(v) for v in (root_data or (0.0, 0.0)))
+    return opt
+
+
+_ROOT_TRACK_KEYS = ("root_smooth", "root_anchor_ptr", "root_data")
+
+
+def _root_tracked(kw):
+    """(the root-trajectory keywords of a `project` call, the rest): only when one of them says something is the 256-byte struct built"""
+    mine = {k: kw[k] for k in _ROOT_TRACK_KEYS if k in kw}
+    rest = {k: v for k, v in kw.items() if k not in _ROOT_TRACK_KEYS}
+    named = (mine.get("root_anchor_ptr") is not None or any(float(v) != 0.0 for v in (mine.get("root_smooth") or ()))
+             or any(float(v) != 0.0 for v in (mine.get("root_data") or ())))
+    return (mine if named else None), rest
 
 
 _LENGTH_KEYS = ("bone_scale_ptr", "len_rate", "len_weight", "len_prior", "len_range", "per_pose_lengths")
@@ -632,12 +660,19 @@ class SkeletonEngine(_Handle):
         the camera of a fit to 2D keypoints (through a pndf_project_options6: `project_options6`); bone_scale_ptr [G,S] in device memory,
         len_rate, len_weight, len_prior, len_range, per_pose_lengths: the bone lengths of a fit (through a pndf_project_options7:
         `project_options7`); views: the cameras of a fit to pixels seen by several views, kp_target_ptr then [B,V,K,2] and kp_conf_ptr
-        [B,V,K] (through a pndf_project_options8: `project_options8`, built only when views are given)"""
+        [B,V,K] (through a pndf_project_options8: `project_options8`, built only when views are given); root_smooth, root_anchor_ptr
+        [B,7] in device memory, root_data: the root's trajectory over the frames of a track (through a pndf_project_options9:
+        `project_options9`, built only when one of them says something)"""
         views = keypoints.pop("views", None)
+        rooted, keypoints = _root_tracked(keypoints)
         lengthed, keypoints = _lengthed(keypoints)
         imaged, keypoints = _imaged(keypoints)
         named = _keypointed(keypoints)      # (refuses an unknown keyword)
-        if views is not None:
+        if rooted is not None:
+            opt9 = project_options9(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends, views=views,
+                                    step_size=step_size, renorm=renorm, tol=tol, **keypoints, **(imaged or {}), **(lengthed or {}), **rooted)
+            opt = ctypes.byref(opt9)
+        elif views is not None:
             opt8 = project_options8(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends, views=views,
                                     step_size=step_size, renorm=renorm, tol=tol, **keypoints, **(imaged or {}), **(lengthed or {}))
             opt = ctypes.byref(opt8)
@@ -852,11 +887,19 @@ class CpuEngine(_Handle):
         SkeletonEngine.project, every pointer in host memory (pndf_project_ex_cpu with a pndf_project_options5: `project_options5`, or with
         root_ptr / root_weights / camera / rho / image a pndf_project_options6: `project_options6`, or with bone_scale_ptr / len_rate /
         len_weight / len_prior / len_range / per_pose_lengths a pndf_project_options7: `project_options7`, or with views a
-        pndf_project_options8: `project_options8`)"""
+        pndf_project_options8: `project_options8`, or with root_smooth / root_anchor_ptr / root_data a pndf_project_options9:
+        `project_options9`)"""
         views = keypoints.pop("views", None)
+        rooted, keypoints = _root_tracked(keypoints)
         lengthed, keypoints = _lengthed(keypoints)
         imaged, keypoints = _imaged(keypoints)
         named = _keypointed(keypoints)      # (refuses an unknown keyword)
+        if rooted is not None:
+            opt9 = project_options9(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends, views=views,
+                                    step_size=step_size, renorm=renorm, tol=tol, **keypoints, **(imaged or {}), **(lengthed or {}), **rooted)
+            self._check(self.lib.pndf_project_ex_cpu(self.handle, q_in_ptr, q_out_ptr, d_ptr, B, int(steps), ctypes.byref(opt9)),
+                        "pndf_project_ex_cpu")
+            return
         if views is not None:
             opt8 = project_options8(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends, views=views,
                                     step_size=step_size, renorm=renorm, tol=tol, **keypoints, **(imaged or {}), **(lengthed or {}))

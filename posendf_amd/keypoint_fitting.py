@@ -14,6 +14,9 @@ With `views` the detections are pixels [N,V,K,2] of the same frame in V calibrat
 With `fit_lengths=True` the segment lengths of the subject are unknowns too: a scale per rest offset and per keypoint offset
 (pndf_project_options7; DESIGN.md section 2j "Bone lengths").
 
+`KeypointFitting.fit_clip` is the driver for a video: `fit` per frame, then one tracked call that couples the poses and the roots along
+the clip (pndf_project_options9; DESIGN.md section 2j "Root trajectory"); `--clip T` and `--root_smooth` on the command line.
+
 `python -m posendf_amd.keypoint_fitting` reads an .npz of targets and writes the fitted poses.
 """
 from __future__ import annotations
@@ -154,11 +157,49 @@ class KeypointFitting(SamplePose):
             result += (sg.reshape(N, H, J + K)[pick, best],)
         return result
 
+    @torch.no_grad()
+    def fit_clip(self, targets, rest, frames, conf=None, clip_steps=60, smooth=0.25, root_smooth=(0.0, 0.25), root_anchor=None, root_data=(0.0, 0.0),
+                 fit_lengths=False, length_weight=0.02, length_prior=0.1, length_range=(0.5, 2.0), **fit):
+        """The driver for a video: targets [P*T,K,2] (or [P*T,K,3], or with `views` [P*T,V,K,2]) are P clips of T = `frames` consecutive
+        frames each.  Stage 1 is `fit` per frame -- the random hypotheses and the choice by energy + lam * dist, with `**fit` its
+        arguments (camera, root, root_weights, views, weight, hypotheses, ...), without bone lengths.  Stage 2 is ONE tracked call of
+        `clip_steps` steps over the chosen poses and roots: the joints coupled along the clip with `smooth`, the end frames free, the
+        roots coupled with `root_smooth` = (lambda_rot, lambda_trans) and, with `root_anchor` [P*T,7], drawn towards it with `root_data`
+        (pndf_project_options9), and with `fit_lengths` one set of scales per clip (`length_weight`, `length_prior`, `length_range` as in
+        `fit`).  The root of stage 2 is the one stage 1 returns: the `root` given, stepped, or with a `camera` or `views` and no `root`
+        the identity placement; without any of the three there is no root.  A part of the root is coupled (and drawn towards the anchor)
+        only where it moves -- there is a root and its `root_weights` entry is positive; the coupling of a held part is dropped, not
+        refused, so with the default `root_weights` = (0, 0) the defaults of this method are a call without a root trajectory.
+        Returns (pose [P*T,J,4], energy [P*T] and dist [P*T] of the last step, root [P*T,7]: the identity placement when there is none)
+        and with `fit_lengths` the scales [P,S].
+        The reference implementation has no such driver: it fits single frames.  The schedule (60 steps, smooth 0.25, the translation
+        coupled with 0.25, the rotation not) is UNTUNED: no trained skeleton model exists to tune it on."""
+        net = self.pose_prior
+        T = int(frames)
+        y = targets.to(self.device).float()
+        if T < 2 or y.shape[0] % T != 0:
+            raise ValueError(f"targets are P * T frames with T = frames >= 2, not {y.shape[0]} frames with frames = {frames}")
+        first = self.fit(y, rest, conf=conf, **fit)
+        pose = first[0]
+        placed = fit.get("camera") is not None or fit.get("root") is not None or fit.get("views") is not None
+        root = first[4] if placed else None      # (the identity placement when a camera or views came without a root)
+        step = {k: fit[k] for k in ("keypoint_joints", "keypoint_offsets", "weight", "step_size", "tol", "camera", "rho", "views", "root_weights") if k in fit}
+        moves = [root is not None and float(w) > 0.0 for w in fit.get("root_weights", (0.0, 0.0))]
+        coupled = tuple(float(v) if m else 0.0 for v, m in zip(root_smooth, moves))
+        drawn = tuple(float(v) if m and root_anchor is not None else 0.0 for v, m in zip(root_data, moves))
+        c = None if conf is None else torch.as_tensor(conf).to(self.device).float()
+        lengths = dict(scale_weight=length_weight, scale_prior=length_prior, scale_range=length_range) if fit_lengths else {}
+        out = net.fit_keypoints(pose, y, rest, steps=int(clip_steps), conf=c, frames=T, smooth=smooth, free_ends=True, renormalize=fit.get("renormalize", "unit"),
+                                return_dist=True, return_energy=True, return_root=True, return_scale=bool(fit_lengths), root=root, root_smooth=coupled,
+                                root_anchor=root_anchor if any(drawn) else None, root_data=drawn, **step, **lengths)
+        return (out[0], out[2], out[1].reshape(-1)) + tuple(out[3:])
 
-def fit_keypoint_file(posendf, keypoint_file, device="cuda:0", key="keypoints", **kwargs):
+
+def fit_keypoint_file(posendf, keypoint_file, device="cuda:0", key="keypoints", clip=0, **kwargs):
     """The targets of an .npz -- `key` [N,K,3], `rest` [J,3], and, if the file has them, `conf` [K] or [N,K], `keypoint_joints` [K],
     `keypoint_offsets` [K,3], `camera` [4] = (fx, fy, cx, cy) (then `key` is [N,K,2] pixels) and `root` [7] or [N,7] -> what
-    KeypointFitting.fit returns for them.  With `views=` among the keyword arguments `key` is [N,V,K,2]."""
+    KeypointFitting.fit returns for them.  With `views=` among the keyword arguments `key` is [N,V,K,2].  With `clip` = T the targets are
+    clips of T frames and the result is KeypointFitting.fit_clip's."""
     import numpy as np
     with np.load(keypoint_file) as f:
         y = torch.from_numpy(np.ascontiguousarray(f[key], dtype=np.float32))
@@ -174,7 +215,10 @@ def fit_keypoint_file(posendf, keypoint_file, device="cuda:0", key="keypoints", 
             opt["camera"] = tuple(float(v) for v in np.asarray(f["camera"]).reshape(-1))
         if "root" in f.files:
             opt["root"] = torch.from_numpy(np.ascontiguousarray(f["root"], dtype=np.float32))
-    return KeypointFitting(posendf, body_model=None, device=device).fit(y, rest, **opt, **kwargs)
+    driver = KeypointFitting(posendf, body_model=None, device=device)
+    if clip:
+        return driver.fit_clip(y, rest, int(clip), **opt, **kwargs)
+    return driver.fit(y, rest, **opt, **kwargs)
 
 
 def main(argv=None):
@@ -199,6 +243,12 @@ def main(argv=None):
     ap.add_argument("--views", default=None, metavar="FILE.npz",
                     help="calibration of several cameras: arrays K [V,3,3] (or [V,4] = fx, fy, cx, cy), R [V,3,3] and t [V,3], world -> camera; "
                          "keypoints are then [N,V,K,2] pixels (not with a camera in the keypoint file)")
+    ap.add_argument("--clip", type=int, default=0, metavar="T",
+                    help="the keypoints are clips of T consecutive frames each: after the fit per frame one tracked call couples the poses and the "
+                         "roots along every clip (KeypointFitting.fit_clip; schedule untuned)")
+    ap.add_argument("--root_smooth", type=float, nargs=2, default=None, metavar=("LAM_ROT", "LAM_TRANS"),
+                    help="with --clip: the coupling of a frame's root rotation / translation to its neighbour frames', each in [0, 1] (default: "
+                         "fit_clip's); a part is coupled only where its --root_weights entry is positive and there is a root or a camera")
     ap.add_argument("--lam", type=float, default=1.0, help="weight of the distance in the choice between hypotheses")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None, help="write the fitted poses (key pose), their energies (energy) and distances (dist) to this .npz")
@@ -218,10 +268,20 @@ def main(argv=None):
         import numpy as np
         with np.load(a.views) as f:
             extra["views"] = [(f["K"][v], f["R"][v], f["t"][v]) for v in range(f["R"].shape[0])]
-    pose, energy, dist, start, *root = fit_keypoint_file(net, a.keypoint_file, device=opt["train"]["device"], hypotheses=a.hypotheses, iterations=a.iterations,
-                                                         steps_per_iter=a.steps_per_iter, weight=a.weight, lam=a.lam, seed=a.seed, **extra)
-    if energy.numel():
-        print(f"median keypoint energy {float(energy.median()):.5f} (random starts: {float(start.median()):.5f}), mean dist {float(dist.mean()):.4f}")
+    if a.root_smooth is not None and not a.clip:
+        ap.error("--root_smooth needs --clip T")
+    if a.clip:
+        if a.root_smooth is not None:
+            extra["root_smooth"] = tuple(a.root_smooth)
+        pose, energy, dist, *root = fit_keypoint_file(net, a.keypoint_file, device=opt["train"]["device"], clip=a.clip, hypotheses=a.hypotheses,
+                                                      iterations=a.iterations, steps_per_iter=a.steps_per_iter, weight=a.weight, lam=a.lam, seed=a.seed, **extra)
+        if energy.numel():
+            print(f"median keypoint energy {float(energy.median()):.5f}, mean dist {float(dist.mean()):.4f} over clips of {a.clip} frames")
+    else:
+        pose, energy, dist, start, *root = fit_keypoint_file(net, a.keypoint_file, device=opt["train"]["device"], hypotheses=a.hypotheses, iterations=a.iterations,
+                                                             steps_per_iter=a.steps_per_iter, weight=a.weight, lam=a.lam, seed=a.seed, **extra)
+        if energy.numel():
+            print(f"median keypoint energy {float(energy.median()):.5f} (random starts: {float(start.median()):.5f}), mean dist {float(dist.mean()):.4f}")
     scale = [root.pop()] if a.fit_lengths else []
     if a.out:
         import numpy as np

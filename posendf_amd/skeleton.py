@@ -26,6 +26,8 @@ With `bone_scale=` / `scale_weight=` the segment lengths of the subject are unkn
 pndf_project_options7; `forward_kinematics(..., bone_scale=)` is the torch statement of the scaled tree).
 With `views=` the detections are pixels of the same frame in several calibrated cameras (a pndf_project_options8;
 `camera_project(..., views=)` is the torch statement of the pixels).
+With `root_smooth=` / `root_anchor=` / `root_data=` the roots of the frames of a track are coupled to their neighbours' and drawn towards an
+observed trajectory (a pndf_project_options9).
 Only the second order stays 21-joint: its C ABI refuses another joint count, and that refusal is pinned.
 """
 from __future__ import annotations
@@ -236,7 +238,7 @@ class SkeletonPoseNDF(PoseModel):
                       frames=None, smooth=0.0, anchor=None, data=0.0, free_ends=False, return_dist=True, return_energy=False, *, step_size=1.0,
                       renormalize=None, tol=0.0, root=None, root_weights=(0.0, 0.0), camera=None, rho=0.0, return_root=False, bone_scale=None,
                       scale_weight=0.0, scale_prior=0.0, scale_range=None, scale_rates=None, per_pose_scale=False, return_scale=False,
-                      views=None):
+                      views=None, root_smooth=(0.0, 0.0), root_anchor=None, root_data=(0.0, 0.0)):
         """Inverse kinematics under the learned prior, for the model's tree: from the start `poses` [B,J,4], `steps` projection steps that
         also descend E = 1/2 sum_k conf_k |P_k(pose) - targets_k|^2 with weight `weight` (nu), P_k = `forward_kinematics` of the pose.
         `targets` [B,K,3] are 3D detections in the roots' frame; `rest` [J,3] the offsets of the joints from their parents in the rest
@@ -279,6 +281,11 @@ class SkeletonPoseNDF(PoseModel):
         the tree, to the camera's (C = R W + t).  A view whose confidence for a keypoint is not positive, or behind which the keypoint
         lies, takes no part for it and its target is not read.  `camera=` together with `views=` is an error.  `camera_project(views=)` is
         the torch statement of the pixels.
+        The root's trajectory (pndf_project_options9; DESIGN.md section 2j "Root trajectory"): `root_smooth` = (lambda_rot, lambda_trans),
+        each in [0, 1], couples the root of every frame of a track (`frames`) to the roots of its neighbour frames as `smooth` couples
+        the joints, the end frames with their one neighbour whether or not `free_ends` is set; `root_anchor` [B,7] (where `poses` may
+        live) is an observed or earlier trajectory and `root_data` = (mu_rot, mu_trans) the weights of the data term towards it.  A part
+        needs its `root_weights` entry positive.  The defaults are the call without them, bit for bit, and UNTUNED.
         Returns poses [B,J,4], then dist [B,1] of the last iteration (`return_dist`), then the energy [B] of the last iteration, evaluated
         before its update (`return_energy`), then the final root [B,7] (`return_root`; the identity placement when none was given), then
         the final scales [G,S] (`return_scale`; ones when none were given); step options: as `project`."""
@@ -338,6 +345,17 @@ class SkeletonPoseNDF(PoseModel):
             place = place.float().expand(B, 7).contiguous().clone()
         if len(tuple(root_weights)) != 2:
             raise PndfError("root_weights is (nu_rot, nu_trans)")
+        if len(tuple(root_smooth)) != 2:
+            raise PndfError("root_smooth is (lambda_rot, lambda_trans)")
+        if len(tuple(root_data)) != 2:
+            raise PndfError("root_data is (mu_rot, mu_trans)")
+        track_anchor = None
+        if root_anchor is not None:
+            track_anchor = on_device(root_anchor, "root_anchor")
+            if not track_anchor.is_floating_point() or tuple(track_anchor.shape) != (B, 7):
+                raise PndfError(f"root_anchor is a floating-point tensor [{B},7], not {track_anchor.dtype} {list(track_anchor.shape)}")
+            track_anchor = track_anchor.float().contiguous()
+        root_tracked = track_anchor is not None or any(root_smooth) or any(root_data)
         T = int(frames or 0)
         if T == 1:
             T = 0
@@ -392,6 +410,8 @@ class SkeletonPoseNDF(PoseModel):
                         **(dict(root_ptr=place.data_ptr() if place is not None and B else None, root_weights=tuple(root_weights) if B else (0.0, 0.0), camera=camera, rho=rho)
                            if place is not None or camera is not None or rho or any(root_weights) else {}),
                         **(dict(views=vt) if vt is not None and B else {}),      # (without poses there are no targets for the views to size)
+                        **(dict(root_smooth=tuple(root_smooth) if B else (0.0, 0.0), root_data=tuple(root_data) if B else (0.0, 0.0),
+                                root_anchor_ptr=track_anchor.data_ptr() if track_anchor is not None and B else None) if root_tracked else {}),
                         **(dict(bone_scale_ptr=scales.data_ptr() if scales is not None and B else None, len_rate=rates, len_weight=scale_weight if B else 0.0,
                                 len_prior=scale_prior, len_range=None if scale_range is None else tuple(scale_range), per_pose_lengths=bool(per_pose_scale))
                            if lengthed else {}))
