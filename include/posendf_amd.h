@@ -274,7 +274,7 @@ typedef struct {
  *   o.base5.base4.base3.base2.base.struct_size = sizeof o;  o.root = placement;  o.fx = o.fy = 500.f;  o.cx = 320.f;  o.cy = 240.f;
  *   o.nu_rot = 0.02f;  o.nu_trans = 0.02f;  o.kp_flags = PNDF_KP_IMAGE;
  * Exactly the two entry points that take a pndf_project_options5 take it.  PNDF_ERR_BAD_ARG with a text that names the field, before
- * anything is launched or written: a struct_size that is none of the nine sizes, an unknown bit in kp_flags, a rho, nu_rot or nu_trans
+ * anything is launched or written: a struct_size that is none of the ten sizes, an unknown bit in kp_flags, a rho, nu_rot or nu_trans
  * that is negative or not finite, rho != 0 without PNDF_KP_IMAGE, with PNDF_KP_IMAGE an fx or fy that is not finite or <= 0 or a cx or
  * cy that is not finite, root == NULL with a positive root weight, a misaligned root, root overlapping q_out, with a positive root
  * weight root overlapping q_in, anchor, conf, kp_target, kp_conf or kp_energy; and what is refused in `base5`. */
@@ -309,7 +309,7 @@ typedef struct {
  * the 168-byte struct bit for bit and bone_scale is not written; with kp_target == NULL or nu == 0 it is the one with the 72-byte struct
  * and bone_scale is neither read nor written; steps == 0 leaves it untouched.  Exactly the two entry points that take a
  * pndf_project_options6 take it.  PNDF_ERR_BAD_ARG with a text that names the field, before anything is launched or written: a
- * struct_size that is none of the nine sizes, reserved3 != 0, an unknown bit in len_flags, a nu_len or kappa that is negative or not
+ * struct_size that is none of the ten sizes, reserved3 != 0, an unknown bit in len_flags, a nu_len or kappa that is negative or not
  * finite, a clamp that is not 0 < len_min <= len_max finite (both 0: none), a len_rate entry that is negative or not finite, bone_scale
  * == NULL with nu_len > 0, a misaligned bone_scale or len_rate, bone_scale overlapping q_out, q_in, root, anchor, conf, kp_target, kp_conf
  * or kp_energy; and what is refused in `base6`. */
@@ -341,7 +341,7 @@ typedef struct {
  * are not read.  `views` is HOST memory in both entry points, read during the call.  With views == NULL and n_views == 0 the call is the
  * one with the 208-byte struct bit for bit; with kp_target's term absent (nu == 0) it is the one with the 72-byte struct and neither the
  * targets nor the confidences are read.  Exactly the two entry points that take a pndf_project_options7 take it.  PNDF_ERR_BAD_ARG with a
- * text that names the field, before anything is launched or written: a struct_size that is none of the nine sizes, reserved4 != 0,
+ * text that names the field, before anything is launched or written: a struct_size that is none of the ten sizes, reserved4 != 0,
  * n_views outside 0 .. PNDF_FK_MAX_VIEWS, exactly one of views == NULL and n_views == 0, n_views > 0 without PNDF_KP_IMAGE or without
  * kp_target, a view whose fx or fy is not finite or <= 0, any other view entry that is not finite, a misaligned views; and what is
  * refused in `base7` (the overlap checks of kp_target and kp_conf with their extents [B,V,K,2] and [B,V,K]). */
@@ -372,7 +372,7 @@ typedef struct {
  * kp_target == NULL or nu == 0 it is the one with the 72-byte struct and neither root nor root_anchor is read or written; steps == 0
  * leaves root untouched.  After the call the result is in `root`, whatever the parity of steps.  Exactly the two entry points that take a
  * pndf_project_options8 take it.  PNDF_ERR_BAD_ARG with a text that names the field, before anything is launched or written: a
- * struct_size that is none of the nine sizes, reserved5 != 0, a lambda or mu outside [0, 1] or NaN, a positive lambda with frames == 0, a
+ * struct_size that is none of the ten sizes, reserved5 != 0, a lambda or mu outside [0, 1] or NaN, a positive lambda with frames == 0, a
  * positive lambda_rot or mu_rot with nu_rot == 0 (likewise the translation), a positive lambda or mu with root == NULL, a positive mu with
  * root_anchor == NULL, root_anchor != NULL with both mu 0, a misaligned root_anchor, root_anchor overlapping root or q_out; and what is
  * refused in `base8`. */
@@ -383,6 +383,36 @@ typedef struct {
     float mu_rot, mu_trans;        /* weight of the root's data term towards root_anchor, each in [0, 1] */
     uint64_t reserved5;            /* must be 0 */
 } pndf_project_options9;           /* 256 bytes */
+
+/* The options with moving cameras: the fit of pndf_project_options9 with a view table per pose, or per frame of a track, in place of the
+ * one table of pndf_project_options8.  `pose_views` is [B,V,16] (view_flags == 0: pose b reads block b) or [T,V,16] with T = frames
+ * (PNDF_VIEWS_PER_FRAME: pose b reads block b % T, one camera path shared by every track of the call); a row is fx, fy, cx, cy, R_v [9]
+ * row-major (world -> camera), t_v [3], as in the 224-byte struct.  The table is DEVICE memory for pndf_skel_project and HOST memory for
+ * pndf_project_ex_cpu, read by every step, and 16-byte aligned.  The term is the several-camera term of the 224-byte struct, operation
+ * for operation and in its order (pndf_fk_cams_energy_grad of csrc/pndf_fk.h), with the pose's own block, and with one rule more, which
+ * is the table's validation -- the library cannot look at values in device memory:
+ *   view v takes no part for a pose when fx > 0 && fy > 0 is false for that pose's row v.  This comes before anything else of the view:
+ *   neither kp_conf [b][v][*] nor kp_target [b][v][*] is read, and the rest of the row may hold anything.  A row of zeros or NaNs says
+ *   "no calibration for this camera in this frame".  No division by a focal length that is not positive happens.
+ * In a row whose fx and fy are positive, finite cx, cy, R_v and t_v are the CALLER's responsibility, as finite targets are.  A pose whose
+ * every view is skipped has energy 0 and takes the step of the prior alone.  With n_pose_views = V > 0: kp_target is [B,V,K,2], kp_conf
+ * [B,V,K], kp_flags must have PNDF_KP_IMAGE, base9.base8.views must be NULL; root, root_anchor, the lambdas and mus, bone_scale, masks
+ * and tracks are those of the 256-byte struct.  With pose_views == NULL, n_pose_views == 0 and view_flags == 0 the call is the one with
+ * the 256-byte struct bit for bit; without a keypoint term (kp_target == NULL or nu == 0) nothing of the table is read and the call is
+ * the one with the 72-byte struct.  Exactly the two entry points that take a pndf_project_options9 take it.  PNDF_ERR_BAD_ARG with a text
+ * that names the field, before anything is launched or written: a struct_size that is none of the ten sizes, reserved6 != 0, an unknown
+ * bit in view_flags, n_pose_views outside 0 .. PNDF_FK_MAX_VIEWS, exactly one of pose_views == NULL and n_pose_views == 0, view_flags
+ * != 0 without a table, PNDF_VIEWS_PER_FRAME with frames == 0, a pose_views that is not 16-byte aligned, pose_views together with
+ * base9.base8.views or n_views, n_pose_views > 0 without PNDF_KP_IMAGE or without kp_target, pose_views overlapping q_out, root (when a
+ * root weight is positive) or bone_scale (when nu_len > 0); and what is refused in `base9`. */
+enum { PNDF_VIEWS_PER_FRAME = 1 };     /* view_flags: pose_views is [frames,V,16], pose b reads block b % frames */
+typedef struct {
+    pndf_project_options9 base9;   /* base9.base8.base7.base6.base5.base4.base3.base2.base.struct_size = sizeof(pndf_project_options10) */
+    const float* pose_views;       /* [B,V,16] or [frames,V,16], 16-byte aligned, or NULL; DEVICE (pndf_skel_project) / HOST (pndf_project_ex_cpu) */
+    int32_t      n_pose_views;     /* V, 0 or 1 .. PNDF_FK_MAX_VIEWS */
+    uint32_t     view_flags;       /* 0 or PNDF_VIEWS_PER_FRAME */
+    uint64_t     reserved6;        /* must be 0 */
+} pndf_project_options10;          /* 280 bytes */
 
 /* pndf_project with step options.  opt == NULL means the defaults, and with the defaults the call is pndf_project bit for
  * bit.  PNDF_ERR_BAD_ARG (text in pndf_last_error; nothing is launched or written) for a struct_size other than
@@ -413,9 +443,10 @@ int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* q_out, floa
                                                                   pndf_project_options2, a pndf_project_options3, a
                                                                   pndf_project_options4, a pndf_project_options5, a
                                                                   pndf_project_options6, a pndf_project_options7, a
-                                                                  pndf_project_options8 or a pndf_project_options9,
-                                                                  `observed` / `anchor` / `conf` / `kp_*` / `root` /
-                                                                  `bone_scale` / `root_anchor` in HOST memory */
+                                                                  pndf_project_options8, a pndf_project_options9 or a
+                                                                  pndf_project_options10, `observed` / `anchor` / `conf` /
+                                                                  `kp_*` / `root` / `bone_scale` / `root_anchor` /
+                                                                  `pose_views` in HOST memory */
 const char* pndf_cpu_last_error(pndf_cpu_handle h);   /* h may be NULL: last error of a failed pndf_cpu_create */
 
 /* Host-only weight packer (what pndf_load_weights uploads); needs no device.  Output sizes in floats come

@@ -78,6 +78,12 @@
  * brings the result back into root.  The gradient's last kernel is then its eighth instantiation, pndf_skel_enc_rev_root_kernel, launched
  * only when a lambda or mu is positive; no step gains a launch.
  *
+ * Moving cameras -- a view table per pose, or per frame of a track, in place of the one table of a pndf_project_options8 -- are the same
+ * two entry points with a pndf_project_options10 (posendf_amd.h): pose_views [B,V,16] or [frames,V,16] in DEVICE memory, 16-byte aligned,
+ * read by every step.  The gradient's last kernel is then its ninth instantiation, pndf_skel_enc_rev_cams_kernel, which steps the root in
+ * place or, with a root trajectory, out of place; a row whose fx or fy is not positive switches its view off for that pose.  No step
+ * gains a launch, and the workspace is what it was.
+ *
  * Still 21-joint: the second order (posendf_amd_second_order.h) only -- pndf_so_create refuses another joint count and
  * pndf_second_order_cpu a handle of another tree, and that is pinned.  2D keypoints with a camera run for any joint tree through
  * pndf_skel_project (above); pndf_keypoint_terms_grad and pndf_lbs_* are the SMPL body model's (vertices, shape, lens of ImageFit).
@@ -136,8 +142,8 @@ int pndf_skel_forward_grad(pndf_skel_handle h, const float* q, const float* grad
  * keypoint term of weight nu to every free joint; kp_energy is E of the last iteration, evaluated before its update, as d_last is.  Or to
  * a pndf_project_options6 (root [B,7]: DEVICE memory) or a pndf_project_options7 (bone_scale [G,S]: DEVICE memory, len_rate [S]: HOST
  * memory, read during the call) or a pndf_project_options8 (views [V,16]: HOST memory, read during the call; kp_target [B,V,K,2] and
- * kp_conf [B,V,K]: DEVICE memory) or a pndf_project_options9 (root_anchor [B,7]: DEVICE memory): nine sizes in all, every other one is
- * refused. */
+ * kp_conf [B,V,K]: DEVICE memory) or a pndf_project_options9 (root_anchor [B,7]: DEVICE memory) or a pndf_project_options10 (pose_views
+ * [B,V,16] or [frames,V,16]: DEVICE memory): ten sizes in all, every other one is refused. */
 int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q_out, float* d_last, int64_t B, int steps,
                       const pndf_project_options* opt, void* workspace, int64_t workspace_bytes, void* stream);
 

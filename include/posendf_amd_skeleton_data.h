@@ -10,7 +10,7 @@
  * pndf_skel_train_batch).
  *
  * Still 21-joint: pndf_quat_topk (dist_utils.geo / euc) and the second order (completion, interpolation, motion denoising and 3D / 2D keypoint
- * fitting for J joints: pndf_skel_project with a pndf_project_options2 / 3 / 4 / 5 / 6 / 7 / 8 / 9, posendf_amd_skeleton.h).
+ * fitting for J joints: pndf_skel_project with a pndf_project_options2 / 3 / 4 / 5 / 6 / 7 / 8 / 9 / 10, posendf_amd_skeleton.h).
  */
 #ifndef POSENDF_AMD_SKELETON_DATA_H
 #define POSENDF_AMD_SKELETON_DATA_H

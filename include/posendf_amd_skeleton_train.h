@@ -11,7 +11,7 @@
  * builds, and the compute calls return the same bits.
  *
  * Still 21-joint: the second order (posendf_amd_second_order.h).  Completion, interpolation, motion denoising, 3D keypoint fitting and
- * fitting to 2D keypoints with a free root for J joints are pndf_skel_project with a pndf_project_options2 / 3 / 4 / 5 / 6 / 7 / 8 / 9
+ * fitting to 2D keypoints with a free root for J joints are pndf_skel_project with a pndf_project_options2 / 3 / 4 / 5 / 6 / 7 / 8 / 9 / 10
  * (posendf_amd_skeleton.h).  The k-NN index and the online
  * sampler for J joints, which make this trainer's data: posendf_amd_skeleton_data.h.
  */

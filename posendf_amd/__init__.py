@@ -28,7 +28,7 @@ def __getattr__(name):   # torch is imported lazily so that numpy-only users (or
     if name in ("PoseDenoising", "denoise_track_file"):
         from . import pose_denoising
         return getattr(pose_denoising, name)
-    if name in ("KeypointFitting", "fit_keypoint_file"):
+    if name in ("KeypointFitting", "fit_keypoint_file", "view_tables"):
         from . import keypoint_fitting
         return getattr(keypoint_fitting, name)
     if name in ("SkeletonPoseNDF", "SKELETONS", "skeleton_config", "forward_kinematics", "camera_project", "view_table"):
@@ -45,6 +45,6 @@ def __getattr__(name):   # torch is imported lazily so that numpy-only users (or
 
 __all__ = ["PoseNDF", "gradient", "BodyModel", "PoseIndex", "Trainer", "PoseDataset", "OnlinePoseDataset", "OnlineOptions", "sample_noisy", "ImageFit", "PerspectiveCamera", "keypoint_term", "PoseCompletion", "PoseInterpolation",
            "PoseDenoising", "denoise_track_file",
-           "KeypointFitting", "fit_keypoint_file",
+           "KeypointFitting", "fit_keypoint_file", "view_tables",
            "SkeletonPoseNDF", "SKELETONS", "skeleton_config", "forward_kinematics", "camera_project", "view_table",
            "amass_config", "load_config", "synth"]

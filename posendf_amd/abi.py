@@ -113,6 +113,20 @@ class ProjectOptions9(ctypes.Structure):
                 ("mu_rot", c_float), ("mu_trans", c_float), ("reserved5", ctypes.c_uint64)]
 
 
+VIEWS_PER_FRAME = 1                                        # PNDF_VIEWS_PER_FRAME (pndf_project_options10.view_flags)
+
+
+class ProjectOptions10(ctypes.Structure):
+    """pndf_project_options10: the options with a mask, tracks, an observation, keypoints, a camera, bone lengths, several cameras and a
+    root trajectory (`base9`, with base9.base8.base7.base6.base5.base4.base3.base2.base.struct_size = 280) and moving cameras --
+    `pose_views` a view table [B,V,16] with one block per pose, or with VIEWS_PER_FRAME in `view_flags` [frames,V,16] with one block per
+    frame of a track (device memory for the skeleton unit, host memory for the twin, 16-byte aligned; None: none), `n_pose_views` V in
+    0 .. MAX_VIEWS.  A row whose fx or fy is not positive switches its view off for that pose.  With pose_views base9.base8.views is None;
+    taken by the two entry points that take a ProjectOptions9"""
+    _fields_ = [("base9", ProjectOptions9), ("pose_views", c_void_p), ("n_pose_views", c_int32), ("view_flags", ctypes.c_uint32),
+                ("reserved6", ctypes.c_uint64)]
+
+
 class DenoiseWeights(ctypes.Structure):
     """pndf_denoise_weights: the loss weights of one outer iteration, evaluated"""
     _fields_ = [("prior_coef", c_float), ("prior_power", c_int32), ("temp_coef", c_float), ("data_coef", c_float)]
@@ -142,7 +156,7 @@ class PndfError(RuntimeError):
 _H = c_void_p                          # every handle type, and every `void* stream`
 _P = c_void_p                          # any other address: tensor data (an int from data_ptr(), or None), a callback, an out value
 _TENSORS = [POINTER(c_void_p), POINTER(c_int64), c_int]      # tensors, numel, n_tensors (host pointers in state-dict order)
-_OPT2 = c_void_p                       # `const pndf_project_options*` where it may point to a ProjectOptions, a ProjectOptions2 .. a ProjectOptions9 (byref of any)
+_OPT2 = c_void_p                       # `const pndf_project_options*` where it may point to a ProjectOptions, a ProjectOptions2 .. a ProjectOptions10 (byref of any)
 # ---- the header set, stated once: header of include/ -> {name: (restype, argtypes)} in the header's order; the headers in the order
 # they were added.  A new header is a file in include/, a table here and its declaration count in tests/test_cabi.py.
 DEBUG_HEADER = "posendf_amd_debug.h"      # the one header that lives in libposendf_amd_debug.so; every other one in the product library

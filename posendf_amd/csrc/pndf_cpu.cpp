@@ -7,8 +7,8 @@
 // SMPL table they compute what they did with the table fixed.  pndf_complete_cpu, pndf_interpolate_cpu and the second order stay 21-joint;
 // pndf_project_ex_cpu completes, interpolates, denoises and fits 3D or 2D keypoints for any joint tree (pndf_project_options2 /
 // pndf_project_options3 / pndf_project_options4 / pndf_project_options5 / pndf_project_options6), with the bone lengths as unknowns too
-// (pndf_project_options7), the pixels seen by several calibrated cameras (pndf_project_options8) and the root's trajectory over the
-// frames of a track (pndf_project_options9).
+// (pndf_project_options7), the pixels seen by several calibrated cameras (pndf_project_options8), the root's trajectory over the
+// frames of a track (pndf_project_options9) and cameras that move from pose to pose or frame to frame (pndf_project_options10).
 //
 // Layout: poses are processed in blocks of PB = 32; inside a block every activation tensor is [feature][pose] so that the
 // inner loop of a layer runs over the 32 poses of the block (contiguous floats: one or two AVX-512 / four AVX2 registers)
@@ -446,14 +446,25 @@ static void root_step_cpu(const PndfCameraTerm& cam, float* rt, const float* roo
 // d E / d sigma of this frame; the scales step in len_step_cpu once every frame of the step has read them.
 // With the views of a pndf_project_options8 (`vw`) the term is pndf_fk_views_energy_grad: targets [V][K][2] and confidences [V][K] per pose,
 // with the scales or without.  With the trajectory of a pndf_project_options9 (`tr`) the root is read from tr->src and its step
-// (pndf_fk_root_smooth_step) goes to tr->dst.
+// (pndf_fk_root_smooth_step) goes to tr->dst.  With the moving cameras of a pndf_project_options10 (`pv`) the term is
+// pndf_fk_cams_energy_grad on the block of the pose.
 static float keypoint_grad_cpu(const PndfKeypoints& kp, const KeypointTables& tb, const int* parent, int nj, const float* q, int64_t pose,
                                float* gk, const PndfCameraTerm& cam = PndfCameraTerm(), float dist = 0.f, float tol = 0.f,
                                const PndfLengths& len = PndfLengths(), float* hs = nullptr, const PndfViews& vw = PndfViews(),
-                               const RootTrack* tr = nullptr) {
+                               const RootTrack* tr = nullptr, const PndfPoseViews& pv = PndfPoseViews()) {
     float W[PNDF_FK_ROWS * MAXJ + PNDF_MAX_SCALES];
     float E;
-    if (vw.any()) {
+    if (pv.any()) {
+        float root[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, groot[7];
+        float* rt = cam.root ? cam.root + pose * 7 : nullptr;
+        if (rt) memcpy(root, tr ? tr->src + pose * 7 : rt, sizeof(root));
+        E = pndf_fk_cams_energy_grad(q, nj, parent, tb.rest, kp.K, tb.kpj, tb.kpo, kp.target + pose * pv.V * kp.K * 2,
+                                     kp.conf ? kp.conf + pose * pv.V * kp.K : nullptr, rt != nullptr, root, cam.rho, pv.V, pv.block(pose),
+                                     len.any() ? len.scale + (pose / len.group) * len.S : nullptr, groot, W, 1);
+        root_step_cpu(cam, rt, root, groot, dist, tol, pose, tr);
+        if (len.any())
+            for (int i = 0; i < len.S; ++i) hs[i] = W[pndf_fk_len_row(nj, i)];
+    } else if (vw.any()) {
         float root[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, groot[7];
         float* rt = cam.root ? cam.root + pose * 7 : nullptr;
         if (rt) memcpy(root, tr ? tr->src + pose * 7 : rt, sizeof(root));
@@ -534,7 +545,7 @@ static int project_loop_cpu(pndf_cpu_handle h, const float* q_in, const uint32_t
                             int steps, const pndf_project_options& o, const PndfData& data = PndfData(),
                             const PndfKeypoints& kp = PndfKeypoints(), const PndfCameraTerm& cam = PndfCameraTerm(),
                             const PndfLengths& len = PndfLengths(), const PndfViews& vw = PndfViews(),
-                            const PndfRootSmooth& rs = PndfRootSmooth()) {
+                            const PndfRootSmooth& rs = PndfRootSmooth(), const PndfPoseViews& pv = PndfPoseViews()) {
     const int NQ = h->nq();
     // without tracks no pose reads another's root (only the data term of a pndf_project_options9 is possible): its step is in place
     const RootTrack rtk{&rs, cam.root, cam.root, 0};
@@ -549,7 +560,7 @@ static int project_loop_cpu(pndf_cpu_handle h, const float* q_in, const uint32_t
         for (int s = 0; s < steps; ++s) {
             forward_grad_block(*h, qb, nb, nullptr, dd, dqb, true, S);
             for (int p = 0; p < nb; ++p) {
-                if (kp.any()) ee[p] = keypoint_grad_cpu(kp, tb, h->net.parent, h->net.nj, qb + p * NQ, p0 + p, gk, cam, dd[p], o.tol, len, hs, vw, tr);
+                if (kp.any()) ee[p] = keypoint_grad_cpu(kp, tb, h->net.parent, h->net.nj, qb + p * NQ, p0 + p, gk, cam, dd[p], o.tol, len, hs, vw, tr, pv);
                 if (len.moves()) len_step_cpu(len, p0 + p, hs, dd + p, o.tol);      // (without tracks every pose is its own group)
                 project_step_cpu(qb + p * NQ, dqb + p * NQ, dd[p], o, observed ? observed[p0 + p] : 0u, h->net.nj,
                                  data.anchor ? data.anchor + (p0 + p) * NQ : nullptr, data.conf ? data.conf + (p0 + p) * h->net.nj : nullptr, data.mu,
@@ -590,7 +601,8 @@ static int track_loop_cpu(pndf_cpu_handle h, const float* a, int64_t a_stride, c
                           const uint32_t* observed, float* track_out, float* d_last, int64_t P, int32_t T, int steps, float lambda,
                           const pndf_project_options& o, const PndfData& data = PndfData(), const PndfKeypoints& kp = PndfKeypoints(),
                           const PndfCameraTerm& cam = PndfCameraTerm(), const PndfLengths& len = PndfLengths(),
-                          const PndfViews& vw = PndfViews(), const PndfRootSmooth& rs = PndfRootSmooth()) {
+                          const PndfViews& vw = PndfViews(), const PndfRootSmooth& rs = PndfRootSmooth(),
+                          const PndfPoseViews& pv = PndfPoseViews()) {
     const int nj = h->net.nj;
     const int64_t nq = h->nq(), B = P * T;
     int rc = PNDF_OK;
@@ -625,7 +637,7 @@ static int track_loop_cpu(pndf_cpu_handle h, const float* a, int64_t a_stride, c
                 const uint32_t held = (nbr != 3 && !data.free_ends) ? ~0u : (observed ? observed[f] : 0u);
                 float gk[4 * MAXJ];
                 if (kp.any()) ee[f] = keypoint_grad_cpu(kp, tb, h->net.parent, nj, cur + f * nq, f, gk, cam, dd[f], o.tol, len,
-                                                        len.any() ? hs.data() + f * len.S : nullptr, vw, rs.any() ? &rtk : nullptr);
+                                                        len.any() ? hs.data() + f * len.S : nullptr, vw, rs.any() ? &rtk : nullptr, pv);
                 for (int j = 0; j < nj; ++j) {
                     const int64_t i = (f * nj + j) * 4;
                     float u[4];
@@ -669,7 +681,8 @@ extern "C" int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* 
     PndfLengths len;               // a pndf_project_options7 the bone lengths besides (host memory): one row of scales per track or per pose
     PndfViews vw;                  // a pndf_project_options8 the views besides (host memory): pixels of the same frame in several cameras
     PndfRootSmooth rs;             // a pndf_project_options9 the root's trajectory besides (host memory): the roots of a track coupled, an anchor
-    if (const char* why = pndf_check_project_options9(opt, B, h->net.nj, o, observed, tracks, data, kp, cam, len, vw, rs)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    PndfPoseViews pv;              // a pndf_project_options10 the moving cameras besides (host memory): a view table per pose or per frame
+    if (const char* why = pndf_check_project_options10(opt, B, h->net.nj, o, observed, tracks, data, kp, cam, len, vw, rs, pv)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (!tracks.frames && !observed && !data.any() && !kp.any() && !kp.energy && pndf_project_options_plain(o))
         return pndf_project_cpu(h, q_in, q_out, d_last, B, steps);
     if (int rc = check(h, q_in, B)) return rc;
@@ -679,14 +692,15 @@ extern "C" int pndf_project_ex_cpu(pndf_cpu_handle h, const float* q_in, float* 
     if (const char* why = pndf_check_root_apart(cam, data, kp, q_in, q_out, B, h->net.nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (const char* why = pndf_check_lengths_apart(len, cam, data, kp, q_in, q_out, B, h->net.nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (const char* why = pndf_check_root_anchor_apart(rs, cam, q_out, B, h->net.nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
-    if (!tracks.frames) return project_loop_cpu(h, q_in, observed, q_out, d_last, B, steps, o, data, kp, cam, len, vw, rs);
+    if (const char* why = pndf_check_pose_views_apart(pv, cam, len, q_out, B, h->net.nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (!tracks.frames) return project_loop_cpu(h, q_in, observed, q_out, d_last, B, steps, o, data, kp, cam, len, vw, rs, pv);
     if (B == 0) return PNDF_OK;
     const int64_t nq = h->nq(), T = tracks.frames;
     if ((uintptr_t)q_in < (uintptr_t)(q_out + B * nq) && (uintptr_t)q_out < (uintptr_t)(q_in + B * nq))
         return pndf_fail(h, PNDF_ERR_BAD_ARG, "q_out must not overlap q_in when pndf_project_options3.frames > 0: a step reads the neighbour "
                                               "frames of its input");
     return track_loop_cpu(h, q_in, T * nq, q_in + (T - 1) * nq, T * nq, tracks.fill, observed, q_out, d_last, B / T, (int32_t)T, steps,
-                          tracks.lambda, o, data, kp, cam, len, vw, rs);
+                          tracks.lambda, o, data, kp, cam, len, vw, rs, pv);
 }
 
 // Host twin of pndf_interpolate (include/posendf_amd_interpolation.h): track_loop_cpu on the 21-joint table; with lambda == 0 this is

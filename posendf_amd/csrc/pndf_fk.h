@@ -767,3 +767,165 @@ PNDF_HD float pndf_fk_views_energy_grad(const float* q, int nj, const int* paren
     }
     return 0.5f * acc;
 }
+
+// ---- Moving cameras of a pndf_project_options10 (DESIGN.md section 2j "Moving cameras"): the several-camera term above with a view table
+// per pose.  Stated once beside the other terms, whose functions above stay as they are (their bits are pinned).  `views` is the POSE's
+// own block [V][16], 16-byte aligned, in memory the lane reads itself (on the device: global memory, every lane another block; nothing
+// here is wave-uniform).  Everything is pndf_fk_views_keypoint / pndf_fk_views_energy_grad, operation for operation and in their order --
+// keypoints in the outer loop, views 0 .. V-1 in the inner one, the energy in that order, aW_k in view order from 0.0f -- with one rule in
+// front of a view, which is the table's validation (the host cannot look at values in device memory):
+//   a view takes no part for the pose when fx > 0 && fy > 0 is false for its row (zero, negative, NaN).  The test comes before the
+//   confidence is read: neither conf [v][*] nor Y [v][*] is read for that view, and the rest of its row may hold anything.
+// So no division by a focal length that is not positive happens.  In a row whose focal lengths are positive, finite cx, cy, R and t are
+// the CALLER's responsibility, as finite targets are.  With every block equal to one table whose focal lengths are positive the result
+// is that of the functions above with that table, bit for bit.
+// A row is fetched as four 16-byte quads per (keypoint, view): the block is not held across the keypoint loop (V = 8 would be 128
+// registers), so a pose reads its block K times per step, from the caches after the first.
+struct alignas(16) PndfFkQuad {
+    float v[4];
+};
+
+PNDF_HD void pndf_fk_cams_row(const float* row, float* vw) {
+    const PndfFkQuad* p = reinterpret_cast<const PndfFkQuad*>(row);
+    const PndfFkQuad a = p[0], b = p[1], c = p[2], d = p[3];
+    for (int i = 0; i < 4; ++i) {
+        vw[i] = a.v[i];
+        vw[4 + i] = b.v[i];
+        vw[8 + i] = c.v[i];
+        vw[12 + i] = d.v[i];
+    }
+}
+
+PNDF_HD float pndf_fk_cams_keypoint(int a, const float* o, bool scaled, float sg, int k, int K, const float* Y, const float* conf, float acc,
+                                    float rho, int V, const float* views, bool has_root, const float* Rc, const float* s, float* as,
+                                    float* AR, float* W, int64_t ld, int nj, float* h) {
+#pragma clang fp contract(off)
+    const float* Ga = W + (int64_t)pndf_fk_G(nj, a) * ld;
+    const float* pa = W + (int64_t)pndf_fk_p(nj, a) * ld;
+    float* Ma = W + (int64_t)pndf_fk_M(nj, a) * ld;
+    float* aa = W + (int64_t)pndf_fk_ap(nj, a) * ld;
+    float os[3], P[3], Wd[3], vu[3];
+    *h = 0.f;
+    for (int x = 0; x < 3; ++x) os[x] = scaled ? sg * o[x] : o[x];
+    for (int x = 0; x < 3; ++x) {
+        const float v = pndf_fk_dot3(Ga[(3 * x) * ld], os[0], Ga[(3 * x + 1) * ld], os[1], Ga[(3 * x + 2) * ld], os[2]);
+        P[x] = pa[x * ld] + v;
+        vu[x] = pndf_fk_dot3(Ga[(3 * x) * ld], o[0], Ga[(3 * x + 1) * ld], o[1], Ga[(3 * x + 2) * ld], o[2]);
+    }
+    if (has_root) {
+        for (int x = 0; x < 3; ++x) {
+            const float v = pndf_fk_dot3(Rc[3 * x], P[0], Rc[3 * x + 1], P[1], Rc[3 * x + 2], P[2]);
+            Wd[x] = v + s[x];
+        }
+    } else {
+        for (int x = 0; x < 3; ++x) Wd[x] = P[x];
+    }
+    float aW[3] = {0.f, 0.f, 0.f};
+    bool seen = false;
+    for (int v = 0; v < V; ++v) {
+        float vw[PNDF_FK_VIEW_FLOATS];
+        pndf_fk_cams_row(views + PNDF_FK_VIEW_FLOATS * v, vw);
+        if (!(vw[0] > 0.f && vw[1] > 0.f)) continue;      // no calibration for this camera and pose: nothing of the view is read
+        const float w = conf ? conf[v * K + k] : 1.0f;
+        if (!(w > 0.f)) continue;
+        float C[3];
+        for (int x = 0; x < 3; ++x) {
+            const float d = pndf_fk_dot3(vw[4 + 3 * x], Wd[0], vw[5 + 3 * x], Wd[1], vw[6 + 3 * x], Wd[2]);
+            C[x] = d + vw[13 + x];
+        }
+        if (!(C[2] > 0.f)) continue;      // behind this camera, in its plane, or NaN: no energy, no gradient from this view
+        const float* y = Y + 2 * (v * K + k);
+        const float nu = C[0] / C[2], nv = C[1] / C[2];
+        const float du = y[0] - vw[2], dv = y[1] - vw[3];
+        const float yu = du / vw[0], yv = dv / vw[1];
+        const float eu = nu - yu, ev = nv - yv;
+        float pu, pv;
+        const float ru = pndf_fk_robust(eu, rho, &pu);
+        const float rv = pndf_fk_robust(ev, rho, &pv);
+        const float rs = ru + rv;
+        const float e = w * rs;
+        acc = acc + e;
+        const float tu = pu / C[2], tv = pv / C[2];
+        const float un = pu * nu, vn = pv * nv;
+        const float sn = un + vn;
+        const float tz = -(sn / C[2]);
+        const float a0 = w * tu, a1 = w * tv, a2 = w * tz;
+        for (int x = 0; x < 3; ++x) {      // R_v^T a
+            const float d = pndf_fk_dot3(vw[4 + x], a0, vw[7 + x], a1, vw[10 + x], a2);
+            aW[x] = aW[x] + d;
+        }
+        seen = true;
+    }
+    if (!seen) return acc;
+    if (has_root)
+        for (int x = 0; x < 3; ++x) {
+            as[x] = as[x] + aW[x];
+            for (int y = 0; y < 3; ++y) {
+                const float m = aW[x] * P[y];
+                AR[3 * x + y] = AR[3 * x + y] + m;
+            }
+        }
+    float wr[3];
+    for (int x = 0; x < 3; ++x) {
+        wr[x] = has_root ? pndf_fk_dot3(Rc[x], aW[0], Rc[3 + x], aW[1], Rc[6 + x], aW[2]) : aW[x];      // R_c^T aW
+        aa[x * ld] = aa[x * ld] + wr[x];
+        for (int y = 0; y < 3; ++y) {
+            const float m = wr[x] * os[y];
+            Ma[(3 * x + y) * ld] = Ma[(3 * x + y) * ld] + m;
+        }
+    }
+    *h = pndf_fk_dot3(wr[0], vu[0], wr[1], vu[1], wr[2], vu[2]);
+    return acc;
+}
+
+// The whole term of one pose under the V views of its own block: pndf_fk_views_energy_grad's arguments and results, `views` [V][16] being
+// the pose's block.
+PNDF_HD float pndf_fk_cams_energy_grad(const float* q, int nj, const int* parent, const float* rest, int K, const int32_t* kp_joint,
+                                       const float* kp_offset, const float* Y, const float* conf, bool has_root, const float* root,
+                                       float rho, int V, const float* views, const float* sigma, float* groot, float* W, int64_t ld) {
+#pragma clang fp contract(off)
+    const bool scaled = sigma != nullptr;
+    for (int j = 0; j < nj; ++j) {
+        float ts[3];
+        for (int x = 0; x < 3; ++x) ts[x] = scaled ? sigma[j] * rest[3 * j + x] : rest[3 * j + x];
+        pndf_fk_joint(q + 4 * j, parent[j], ts, W, ld, nj, j);
+    }
+    float ch[4] = {0.f, 0.f, 0.f, 0.f}, Rc[9], s[3] = {0.f, 0.f, 0.f}, n = 0.f;
+    float as[3] = {0.f, 0.f, 0.f}, AR[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < 9; ++i) Rc[i] = 0.f;
+    if (has_root) {
+        float c[4];
+        for (int i = 0; i < 4; ++i) c[i] = root[i];
+        for (int x = 0; x < 3; ++x) s[x] = root[4 + x];
+        n = pndf_fk_unit(c, ch);
+        pndf_fk_rot(ch, Rc);
+    }
+    float acc = 0.f;
+    for (int k = 0; k < K; ++k) {
+        float h = 0.f;
+        acc = pndf_fk_cams_keypoint(kp_joint[k], kp_offset + 3 * k, scaled, scaled ? sigma[nj + k] : 1.0f, k, K, Y, conf, acc, rho, V, views,
+                                    has_root, Rc, s, as, AR, W, ld, nj, &h);
+        if (scaled) W[(int64_t)pndf_fk_len_row(nj, nj + k) * ld] = h;      // (without scales nobody reads the rows of h: they are not written)
+    }
+    for (int j = nj - 1; j >= 0; --j) {
+        const float* t = rest + 3 * j;
+        const float* aj = W + (int64_t)pndf_fk_ap(nj, j) * ld;
+        float ts[3], v[3] = {0.f, 0.f, 0.f};
+        for (int x = 0; x < 3; ++x) ts[x] = scaled ? sigma[j] * t[x] : t[x];
+        if (scaled) {
+            if (parent[j] < 0) {
+                for (int x = 0; x < 3; ++x) v[x] = t[x];
+            } else {
+                const float* Gp = W + (int64_t)pndf_fk_G(nj, parent[j]) * ld;
+                for (int x = 0; x < 3; ++x) v[x] = pndf_fk_dot3(Gp[(3 * x) * ld], t[0], Gp[(3 * x + 1) * ld], t[1], Gp[(3 * x + 2) * ld], t[2]);
+            }
+            W[(int64_t)pndf_fk_len_row(nj, j) * ld] = pndf_fk_dot3(aj[0], v[0], aj[ld], v[1], aj[2 * ld], v[2]);
+        }
+        pndf_fk_joint_rev(q + 4 * j, parent[j], ts, W, ld, nj, j);
+    }
+    if (has_root) {
+        pndf_fk_quat_adj(AR, ch, n, groot);
+        for (int x = 0; x < 3; ++x) groot[4 + x] = as[x];
+    }
+    return 0.5f * acc;
+}

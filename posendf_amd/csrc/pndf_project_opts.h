@@ -625,6 +625,107 @@ inline const char* pndf_check_root_anchor_apart(const PndfRootSmooth& rs, const 
     return nullptr;
 }
 
+// The moving cameras of a pndf_project_options10, validated as far as the host can: the table lives where the step runs (device memory
+// for the skeleton unit), so its VALUES are not looked at here -- pndf_fk_cams_keypoint switches off a view whose focal lengths are not
+// positive.  Without a keypoint term (kp_target NULL or nu == 0) `table` stays null and nothing of it is read; `named_table` is what the
+// struct names either way (pndf_check_pose_views_apart refuses its overlaps).
+struct PndfPoseViews {
+    const float* table = nullptr;      // [B,V,16], or [frames,V,16] with per_frame; null: none
+    const float* named_table = nullptr;
+    int32_t V = 0;
+    int32_t frames = 0;                // per_frame: T, pose c reads block c % T; else 0: pose c reads block c
+    bool any() const { return table != nullptr; }
+    // the block of pose number `pose` of the call
+    const float* block(int64_t pose) const { return table + (frames ? pose % frames : pose) * ((int64_t)V * 16); }
+};
+
+// The checker of the same two entry points for all ten structs: a pndf_project_options10 brings the moving cameras besides.  Returns
+// nullptr and fills `out`, `observed`, `tracks`, `data`, `kp` (with the views' count in kp.views, as a pndf_project_options8 does),
+// `cam`, `len`, `vw`, `rs` and `pv`, or the reason the struct is refused.  That pose_views does not overlap what the steps write is the
+// caller's to check (pndf_check_pose_views_apart).
+inline const char* pndf_check_project_options10(const pndf_project_options* opt, int64_t B, int nj, pndf_project_options& out,
+                                                const uint32_t*& observed, PndfTracks& tracks, PndfData& data, PndfKeypoints& kp,
+                                                PndfCameraTerm& cam, PndfLengths& len, PndfViews& vw, PndfRootSmooth& rs,
+                                                PndfPoseViews& pv) {
+    pv = PndfPoseViews();
+    if (!opt || opt->struct_size != sizeof(pndf_project_options10)) {
+        const char* why = pndf_check_project_options9(opt, B, nj, out, observed, tracks, data, kp, cam, len, vw, rs);
+        if (why && opt && opt->struct_size != sizeof(pndf_project_options) && opt->struct_size != sizeof(pndf_project_options2) &&
+            opt->struct_size != sizeof(pndf_project_options3) && opt->struct_size != sizeof(pndf_project_options4) &&
+            opt->struct_size != sizeof(pndf_project_options5) && opt->struct_size != sizeof(pndf_project_options6) &&
+            opt->struct_size != sizeof(pndf_project_options7) && opt->struct_size != sizeof(pndf_project_options8) &&
+            opt->struct_size != sizeof(pndf_project_options9))
+            return "pndf_project_options.struct_size is none of sizeof(pndf_project_options), sizeof(pndf_project_options2), "
+                   "sizeof(pndf_project_options3), sizeof(pndf_project_options4), sizeof(pndf_project_options5), "
+                   "sizeof(pndf_project_options6), sizeof(pndf_project_options7), sizeof(pndf_project_options8), "
+                   "sizeof(pndf_project_options9) and sizeof(pndf_project_options10): fill the struct with pndf_default_project_options";
+        return why;
+    }
+    const pndf_project_options10* o10 = (const pndf_project_options10*)opt;
+    // what the struct says of itself first: a refusal here has filled nothing
+    out = pndf_project_options();
+    observed = nullptr;
+    tracks = PndfTracks();
+    data = PndfData();
+    kp = PndfKeypoints();
+    cam = PndfCameraTerm();
+    len = PndfLengths();
+    for (int i = 0; i < PNDF_MAX_SCALES; ++i) len.rate[i] = 1.0f;
+    vw.V = 0;
+    for (int i = 0; i < PNDF_FK_MAX_VIEWS * 16; ++i) vw.table[i] = 0.f;
+    rs = PndfRootSmooth();
+    const pndf_project_options8& o8 = o10->base9.base8;
+    const int32_t frames = o8.base7.base6.base5.base4.base3.frames;
+    if (o10->reserved6 != 0u) return "pndf_project_options10.reserved6 must be 0";
+    if (o10->view_flags & ~(uint32_t)PNDF_VIEWS_PER_FRAME) return "pndf_project_options10.view_flags has a bit other than PNDF_VIEWS_PER_FRAME";
+    if (o10->n_pose_views < 0 || o10->n_pose_views > PNDF_FK_MAX_VIEWS) return "pndf_project_options10.n_pose_views must lie in 0 .. 8";
+    if ((uintptr_t)o10->pose_views & 15) return "pndf_project_options10.pose_views must be 16-byte aligned: a row is fetched in 16-byte quads";
+    if (!o10->pose_views && o10->n_pose_views != 0) return "pndf_project_options10.pose_views must not be NULL when n_pose_views is positive";
+    if (o10->pose_views && o10->n_pose_views == 0) return "pndf_project_options10.n_pose_views must be positive when pose_views is not NULL";
+    if (!o10->pose_views && o10->view_flags != 0u) return "pndf_project_options10.view_flags must be 0 when pose_views is NULL";
+    const bool per_frame = (o10->view_flags & PNDF_VIEWS_PER_FRAME) != 0;
+    if (per_frame && frames < 2)
+        return "pndf_project_options10.view_flags has PNDF_VIEWS_PER_FRAME, so pndf_project_options3.frames must be at least 2 (the table is [frames,V,16])";
+    if (o10->pose_views) {
+        if (o8.views || o8.n_views != 0)
+            return "pndf_project_options10.pose_views is given, so pndf_project_options8.views must be NULL and n_views 0: one table or the other";
+        if (!(o8.base7.base6.kp_flags & PNDF_KP_IMAGE)) return "pndf_project_options10.n_pose_views is positive, so pndf_project_options6.kp_flags must have PNDF_KP_IMAGE";
+        if (!o8.base7.base6.base5.kp_target) return "pndf_project_options10.n_pose_views is positive, so pndf_project_options5.kp_target must not be NULL";
+    }
+    pndf_project_options9 base9 = o10->base9;
+    base9.base8.base7.base6.base5.base4.base3.base2.base.struct_size = (uint32_t)sizeof(pndf_project_options9);
+    if (o10->pose_views) {      // the intrinsics of base6 are not read: whatever they hold is not refused
+        base9.base8.base7.base6.fx = base9.base8.base7.base6.fy = 1.f;
+        base9.base8.base7.base6.cx = base9.base8.base7.base6.cy = 0.f;
+    }
+    if (const char* why = pndf_check_project_options9(&base9.base8.base7.base6.base5.base4.base3.base2.base, B, nj, out, observed, tracks, data, kp, cam, len, vw, rs)) return why;
+    if (o10->pose_views) {
+        kp.views = o10->n_pose_views;
+        pv.named_table = o10->pose_views;
+        pv.V = o10->n_pose_views;
+        pv.frames = per_frame ? frames : 0;
+        if (kp.any()) pv.table = o10->pose_views;
+    }
+    return nullptr;
+}
+
+// What the entry point adds to that checker, knowing B and the poses: every step reads pose_views, so it may share memory with nothing
+// the steps write -- q_out, root when a root weight is positive, bone_scale when nu_len > 0.  nullptr, or the reason.  The arrays are
+// compared as the struct names them.
+inline const char* pndf_check_pose_views_apart(const PndfPoseViews& pv, const PndfCameraTerm& cam, const PndfLengths& len, const float* q_out,
+                                               int64_t B, int nj) {
+    if (B <= 0 || !pv.named_table) return nullptr;
+    const int64_t blocks = pv.frames ? pv.frames : B;
+    const uintptr_t r0 = (uintptr_t)pv.named_table, r1 = (uintptr_t)(pv.named_table + blocks * pv.V * 16);
+    auto meets = [&](const float* p, int64_t floats) { return p && (uintptr_t)p < r1 && r0 < (uintptr_t)(p + floats); };
+    if (meets(q_out, B * nj * 4)) return "pndf_project_options10.pose_views must not overlap q_out";
+    if ((cam.nu_rot > 0.f || cam.nu_trans > 0.f) && meets(cam.named_root, B * 7))
+        return "pndf_project_options10.pose_views must not overlap pndf_project_options6.root: every step writes the root";
+    if (len.nu_len > 0.f && meets(len.named_scale, len.named_floats))
+        return "pndf_project_options10.pose_views must not overlap pndf_project_options7.bone_scale: every step writes the scales";
+    return nullptr;
+}
+
 // The host tables of validated keypoints as the step functions of pndf_fk.h take them: kp_joint and kp_offset with their defaults
 // filled in (keypoint k is joint k; zeros).  T: anything with rest [96], kpj [64] and kpo [192] -- the kernel's argument struct, the
 // host twin's local copy.

@@ -35,7 +35,9 @@
 //                              pndf_skel_enc_rev_views_kernel: the same, with the pixels of V cameras in front of the root's frame;
 //                              with the root trajectory of a pndf_project_options9 its eighth instantiation
 //                              pndf_skel_enc_rev_root_kernel: any of those three terms, and the root stepped out of place, coupled to
-//                              the roots of the neighbour frames and drawn towards an anchor
+//                              the roots of the neighbour frames and drawn towards an anchor; with the moving cameras of a
+//                              pndf_project_options10 its ninth instantiation pndf_skel_enc_rev_cams_kernel: the several-camera term
+//                              on the lane's own block of a view table in device memory, the root stepped in place or out of place
 //   pndf_skel_len_step_kernel  once per chunk and step behind that kernel (only when nu_len > 0): the sum of those rows over the frames
 //                              of every group in pndf_fk.h's order and the step of the scales in place
 //   pndf_skel_fill_kernel      the fill of a track from its two end frames, once per chunk in front of the steps
@@ -152,6 +154,14 @@ struct SkRootArgs : SkViewsArgs {
 };
 static_assert(sizeof(SkRootArgs) <= 4096, "a kernel's arguments are at most 4,096 bytes");
 
+// SkRootArgs with the moving cameras of a pndf_project_options10 (SK_PROJECT), which pndf_skel_enc_rev_cams_kernel alone takes, derived
+// for the same reason.  The table is device memory: every lane fetches the rows of its own block with vector loads.
+struct SkCamsArgs : SkRootArgs {
+    const float* pose_views;         // the chunk's blocks [n][V][16], or with views_per_frame the call's [frames][V][16]; 16-byte aligned
+    int views_per_frame;             // != 0: lane c reads block c % frames; 0: block c
+};
+static_assert(sizeof(SkCamsArgs) <= 4096, "a kernel's arguments are at most 4,096 bytes");
+
 // What pndf_skel_len_step_kernel takes: the rows h [S][ld] the reverse left, the chunk's distance row and the scales to step in place
 struct SkLenStepArgs {
     float* bone_scale;        // [G][S]
@@ -248,14 +258,19 @@ extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_fwd_kernel(SkArg
 // or SK_REV_VIEWS -- a wave-uniform choice from V and bone_scale, as sk_run_chunk chooses among those kernels -- and pndf_fk.h's
 // pndf_fk_root_smooth_step from `root` to `root_out` in place of the root's step; the neighbours' and the anchor's rows are loaded inside
 // that step, behind the energy and its reverse.
-enum { SK_REV_PLAIN = 0, SK_REV_TRACKS = 1, SK_REV_DENOISE = 2, SK_REV_FIT = 3, SK_REV_IMAGE = 4, SK_REV_LEN = 5, SK_REV_VIEWS = 6, SK_REV_ROOT = 7 };
+// SK_REV_CAMS is the instantiation of a pndf_project_options10 with a view table per pose: pndf_fk.h's pndf_fk_cams_energy_grad on the
+// lane's own block (block c, or c % frames: a chunk holds whole tracks), with the scales or without, and both forms of the root's step by
+// a wave-uniform branch on root_out -- pndf_fk_root_step in place as SK_REV_VIEWS, pndf_fk_root_smooth_step out of place as SK_REV_ROOT.
+enum { SK_REV_PLAIN = 0, SK_REV_TRACKS = 1, SK_REV_DENOISE = 2, SK_REV_FIT = 3, SK_REV_IMAGE = 4, SK_REV_LEN = 5, SK_REV_VIEWS = 6, SK_REV_ROOT = 7,
+       SK_REV_CAMS = 8 };
 template <int KIND, class Args>
 __device__ __forceinline__ void skel_enc_rev(const Args& e) {
     constexpr bool TRACKS = KIND == SK_REV_TRACKS;
     constexpr bool LEN = KIND == SK_REV_LEN;
     constexpr bool VIEWS = KIND == SK_REV_VIEWS;
     constexpr bool ROOT = KIND == SK_REV_ROOT;
-    constexpr bool IMAGE = KIND == SK_REV_IMAGE || LEN || VIEWS || ROOT;
+    constexpr bool CAMS = KIND == SK_REV_CAMS;
+    constexpr bool IMAGE = KIND == SK_REV_IMAGE || LEN || VIEWS || ROOT || CAMS;
     constexpr bool FIT = KIND == SK_REV_FIT || IMAGE;
     constexpr bool DENOISE = KIND == SK_REV_DENOISE || FIT;
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -300,7 +315,13 @@ __device__ __forceinline__ void skel_enc_rev(const Args& e) {
         if (e.root)
 #pragma unroll
             for (int i = 0; i < 7; ++i) root[i] = e.root[c * 7 + i];
-        if constexpr (ROOT) {
+        if constexpr (CAMS) {
+            const int64_t blk = e.views_per_frame ? c % e.frames : c;
+            energy = pndf_fk_cams_energy_grad(q, e.nj, e.parent, e.rest, e.K, e.kpj, e.kpo, e.kp_target + c * (e.V * e.K * 2),
+                                              e.kp_conf ? e.kp_conf + c * (e.V * e.K) : nullptr, e.root != nullptr, root, e.cam.rho, e.V,
+                                              e.pose_views + blk * (e.V * PNDF_FK_VIEW_FLOATS),
+                                              e.bone_scale ? e.bone_scale + (c / e.group) * e.S : nullptr, groot, e.fk + c, e.ld);
+        } else if constexpr (ROOT) {
             if (e.V > 0)
                 energy = pndf_fk_views_energy_grad(q, e.nj, e.parent, e.rest, e.K, e.kpj, e.kpo, e.kp_target + c * (e.V * e.K * 2),
                                                    e.kp_conf ? e.kp_conf + c * (e.V * e.K) : nullptr, e.root != nullptr, root, e.cam.rho, e.V,
@@ -385,7 +406,23 @@ __device__ __forceinline__ void skel_enc_rev(const Args& e) {
     if (e.d_out) e.d_out[c] = dist;
     if constexpr (FIT)
         if (e.kp_energy) e.kp_energy[c] = energy;
-    if constexpr (ROOT) {      // (the host launches this kernel only with a root, a positive root weight and a positive lambda or mu)
+    if constexpr (CAMS) {
+        if (e.root_out) {      // (wave-uniform; set only with a root, a positive root weight and a positive lambda or mu)
+            const int k = e.frames ? (int)(c % e.frames) : 0;
+            const int rn = e.frames ? ((k > 0 ? 1 : 0) | (k < e.frames - 1 ? 2 : 0)) : 0;
+            const float* row = e.root + c * 7;
+            float stepped[7];
+            pndf_fk_root_smooth_step(root, groot, e.nu_rot, e.nu_trans, dist, e.tol, row - 7, row + 7, rn, e.lambda_rot, e.lambda_trans,
+                                     e.root_anchor + c * 7, e.mu_rot, e.mu_trans, stepped);
+#pragma unroll
+            for (int i = 0; i < 7; ++i) e.root_out[c * 7 + i] = stepped[i];
+        } else if (e.root && (e.nu_rot > 0.f || e.nu_trans > 0.f)) {
+            float stepped[7];
+            pndf_fk_root_step(root, groot, e.nu_rot, e.nu_trans, dist, e.tol, stepped);
+#pragma unroll
+            for (int i = 0; i < 7; ++i) e.root[c * 7 + i] = stepped[i];
+        }
+    } else if constexpr (ROOT) {      // (the host launches this kernel only with a root, a positive root weight and a positive lambda or mu)
         const int k = e.frames ? (int)(c % e.frames) : 0;
         const int rn = e.frames ? ((k > 0 ? 1 : 0) | (k < e.frames - 1 ? 2 : 0)) : 0;
         const float* row = e.root + c * 7;
@@ -411,6 +448,7 @@ extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_image_kernel
 extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_len_kernel(SkLenArgs e) { skel_enc_rev<SK_REV_LEN>(e); }
 extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_views_kernel(SkViewsArgs e) { skel_enc_rev<SK_REV_VIEWS>(e); }
 extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_root_kernel(SkRootArgs e) { skel_enc_rev<SK_REV_ROOT>(e); }
+extern "C" __global__ void __launch_bounds__(256) pndf_skel_enc_rev_cams_kernel(SkCamsArgs e) { skel_enc_rev<SK_REV_CAMS>(e); }
 
 // The step of the scales of a chunk (pndf_fk.h: pndf_fk_len_group_sum's order, pndf_fk_len_step).  Frames per group n <= 64: lanes own
 // (group, scale) pairs and sum their frames in order.  n > 64: one workgroup per (group, scale), lane b sums block b of 64 frames, lane 0
@@ -551,7 +589,7 @@ SkLayout sk_layout(const pndf_skel_plan* h, int64_t B) {
 }
 
 // One evaluation of a chunk of n poses at `q`: the 2 + 2 L launches (the forward alone: 1 + L and the copy of the output row)
-void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const SkRootArgs& e, hipStream_t st) {
+void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const SkCamsArgs& e, hipStream_t st) {
     const int n = (int)e.n;
     TrunkWeights w{};
     TrunkBuffers b{};
@@ -564,6 +602,7 @@ void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const S
     const SkImageArgs& image = e;
     const SkLenArgs& lengths = e;
     const SkViewsArgs& views = e;
+    const SkRootArgs& rooted = e;
     hipLaunchKernelGGL(pndf_skel_enc_fwd_kernel, dim3(blocks(n)), dim3(256), 0, st, plain);
     trunk_forward(SK_GEMM, *h, w, b, st);
     if (e.mode == SK_FORWARD) {
@@ -571,7 +610,8 @@ void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const S
         return;
     }
     trunk_reverse(SK_GEMM, *h, w, b, st);      // grad_out scales the result in the encoder's reverse
-    if (e.mode == SK_PROJECT && e.kp_target && e.root_out) hipLaunchKernelGGL(pndf_skel_enc_rev_root_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
+    if (e.mode == SK_PROJECT && e.kp_target && e.pose_views) hipLaunchKernelGGL(pndf_skel_enc_rev_cams_kernel, dim3(blocks(n)), dim3(256), 0, st, e);
+    else if (e.mode == SK_PROJECT && e.kp_target && e.root_out) hipLaunchKernelGGL(pndf_skel_enc_rev_root_kernel, dim3(blocks(n)), dim3(256), 0, st, rooted);
     else if (e.mode == SK_PROJECT && e.kp_target && e.V > 0) hipLaunchKernelGGL(pndf_skel_enc_rev_views_kernel, dim3(blocks(n)), dim3(256), 0, st, views);
     else if (e.mode == SK_PROJECT && e.kp_target && e.bone_scale) hipLaunchKernelGGL(pndf_skel_enc_rev_len_kernel, dim3(blocks(n)), dim3(256), 0, st, lengths);
     else if (e.mode == SK_PROJECT && e.kp_target && (e.root || e.cam.image)) hipLaunchKernelGGL(pndf_skel_enc_rev_image_kernel, dim3(blocks(n)), dim3(256), 0, st, image);
@@ -581,8 +621,8 @@ void sk_run_chunk(const pndf_skel_plan* h, const SkLayout& l, float* ws, const S
     else hipLaunchKernelGGL(pndf_skel_enc_rev_kernel, dim3(blocks(n)), dim3(256), 0, st, plain);
 }
 
-SkRootArgs sk_args(const pndf_skel_plan* h, const SkLayout& l, float* ws, int mode) {
-    SkRootArgs e;
+SkCamsArgs sk_args(const pndf_skel_plan* h, const SkLayout& l, float* ws, int mode) {
+    SkCamsArgs e;
     memset(&e, 0, sizeof(e));
     e.wenc = h->d_blob;
     e.X = ws + l.X; e.act0 = ws + l.act0; e.U0 = ws + l.U0; e.Gx = ws + l.Gx; e.dist = ws + l.dist; e.fk = ws + l.FK;
@@ -692,7 +732,7 @@ extern "C" int pndf_skel_forward(pndf_skel_handle h, const float* q, float* d, i
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     float* ws = (float*)workspace;
-    SkRootArgs e = sk_args(h, l, ws, SK_FORWARD);
+    SkCamsArgs e = sk_args(h, l, ws, SK_FORWARD);
     for (int64_t c0 = 0; c0 < B; c0 += l.nc) {
         e.n = B - c0 < l.nc ? B - c0 : l.nc;
         e.q = q + c0 * h->nj * BONE;
@@ -715,7 +755,7 @@ extern "C" int pndf_skel_forward_grad(pndf_skel_handle h, const float* q, const 
     DeviceGuard guard(h->device);
     if (!guard.ok) return pndf_fail(h, PNDF_ERR_HIP, "hipSetDevice failed");
     float* ws = (float*)workspace;
-    SkRootArgs e = sk_args(h, l, ws, SK_GRAD);
+    SkCamsArgs e = sk_args(h, l, ws, SK_GRAD);
     for (int64_t c0 = 0; c0 < B; c0 += l.nc) {
         e.n = B - c0 < l.nc ? B - c0 : l.nc;
         e.q = q + c0 * h->nj * BONE;
@@ -739,7 +779,8 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
     PndfLengths len;               // a pndf_project_options7 the bone lengths besides: the scales per group in device memory, the rates in host memory
     PndfViews vw;                  // a pndf_project_options8 the views besides: the table in host memory, targets [B,V,K,2] and confidences [B,V,K] in device memory
     PndfRootSmooth rs;             // a pndf_project_options9 the root's trajectory besides: the anchor [B,7] in device memory
-    if (const char* why = pndf_check_project_options9(opt, B, h->nj, o, observed, tracks, data, kp, cam, len, vw, rs)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    PndfPoseViews pv;              // a pndf_project_options10 the moving cameras besides: a table [B,V,16] or [frames,V,16] in device memory
+    if (const char* why = pndf_check_project_options10(opt, B, h->nj, o, observed, tracks, data, kp, cam, len, vw, rs, pv)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (steps < 0) return pndf_fail(h, PNDF_ERR_BAD_ARG, "negative step count");
     SkLayout l;
     if (B > 0 && (!q_in || !q_out)) return pndf_fail(h, PNDF_ERR_BAD_ARG, "null pose pointer");
@@ -754,6 +795,7 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
     if (const char* why = pndf_check_root_apart(cam, data, kp, q_in, q_out, B, h->nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (const char* why = pndf_check_lengths_apart(len, cam, data, kp, q_in, q_out, B, h->nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (const char* why = pndf_check_root_anchor_apart(rs, cam, q_out, B, h->nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
+    if (const char* why = pndf_check_pose_views_apart(pv, cam, len, q_out, B, h->nj)) return pndf_fail(h, PNDF_ERR_BAD_ARG, why);
     if (const int rc = sk_check(h, B, workspace, workspace_bytes, l); rc != PNDF_OK || B == 0) return rc;
     PndfRange range("pndf_skel_project");
     DeviceGuard guard(h->device);
@@ -768,7 +810,7 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
         return PNDF_OK;
     }
     float* ws = (float*)workspace;
-    SkRootArgs e = sk_args(h, l, ws, SK_PROJECT);
+    SkCamsArgs e = sk_args(h, l, ws, SK_PROJECT);
     e.step_size = o.step_size; e.tol = o.tol; e.renorm = (int)o.renorm;
     e.frames = tracks.frames; e.lambda = tracks.lambda;
     e.mu = data.mu; e.flags = data.free_ends ? (uint32_t)PNDF_TRACK_FREE_ENDS : 0u;
@@ -781,6 +823,10 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
     if (vw.any()) {
         e.V = vw.V;
         for (int i = 0; i < PNDF_FK_MAX_VIEWS * PNDF_FK_VIEW_FLOATS; ++i) e.views[i] = vw.table[i];
+    }
+    if (pv.any()) {
+        e.V = pv.V;
+        e.views_per_frame = pv.frames ? 1 : 0;
     }
     if (rs.any()) { e.lambda_rot = rs.lambda_rot; e.lambda_trans = rs.lambda_trans; e.mu_rot = rs.mu_rot; e.mu_trans = rs.mu_trans; }
     SkLenStepArgs ls;
@@ -814,6 +860,8 @@ extern "C" int pndf_skel_project(pndf_skel_handle h, const float* q_in, float* q
         // buffer, step 0 reads the caller's rows; after an odd step count the result is copied back into them.
         float* rbuf[2] = {cam.root ? cam.root + c0 * 7 : nullptr, ws + l.ROOT};
         e.root_anchor = rs.anchor ? rs.anchor + c0 * 7 : nullptr;
+        // A table per pose goes with the chunk; a table per frame does not: a chunk holds whole tracks, so c0 is a multiple of frames.
+        if (pv.any()) e.pose_views = pv.frames ? pv.table : pv.table + c0 * ((int64_t)pv.V * PNDF_FK_VIEW_FLOATS);
         if (filled) {
             float* dst = buf[steps & 1];      // what step 0 does not write; q_out itself when there is no step
             hipLaunchKernelGGL(pndf_skel_fill_kernel, dim3(blocks(e.n * h->nj)), dim3(256), 0, st, cur, dst, e.n * (int64_t)h->nj, h->nj,

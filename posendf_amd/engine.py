@@ -15,7 +15,7 @@ import numpy as np
 # public names stay importable from here.  `torch` comes from there too: abi imports it before the library is loaded (None without it).
 from .abi import (ACT_CODES, DEBUG_EXPERIMENT_WORDS, DEBUG_EXPORTS, EXPERIMENT_WORDS, EXPORTS, INTERP_MODES, METRIC_CODES,  # noqa: F401
                   NOISE_CODES, PRECISION_CODES, RENORM_CODES, Camera, DenoiseWeights, KeypointOpts, OnlineOpts, PndfConfig, PndfError,
-                  ProjectOptions, ProjectOptions2, ProjectOptions3, ProjectOptions4, ProjectOptions5, ProjectOptions6, ProjectOptions7, ProjectOptions8, ProjectOptions9, KP_IMAGE, LEN_PER_POSE, MAX_VIEWS, TRACK_FILLS, TRACK_FREE_ENDS, debug_library_path, experiment_word, load_library, torch)
+                  ProjectOptions, ProjectOptions2, ProjectOptions3, ProjectOptions4, ProjectOptions5, ProjectOptions6, ProjectOptions7, ProjectOptions8, ProjectOptions9, ProjectOptions10, KP_IMAGE, LEN_PER_POSE, MAX_VIEWS, TRACK_FILLS, TRACK_FREE_ENDS, VIEWS_PER_FRAME, debug_library_path, experiment_word, load_library, torch)
 
 
 def stream_handle(device) -> int:
@@ -254,6 +254,36 @@ def project_options9(lib, *args, root_smooth=None, root_anchor_ptr=None, root_da
     opt.root_anchor = root_anchor_ptr
     opt.lambda_rot, opt.lambda_trans = (float(v) for v in (root_smooth or (0.0, 0.0)))
     opt.mu_rot, opt.mu_trans = (float(v) for v in (root_data or (0.0, 0.0)))
+    return opt
+
+
+def project_options10(lib, *args, pose_views=None, views_per_frame=False, **kw):
+    """pndf_project_options10 (include/posendf_amd.h): `project_options9`'s arguments, and moving cameras -- `pose_views`: a contiguous
+    float32 view table [B,V,16] with one block per pose, or with `views_per_frame` [frames,V,16] with one block per frame of a track, as
+    a tensor in device memory for the skeleton unit or a tensor / numpy array in host memory for the twin; 16-byte aligned.  The returned
+    struct keeps the table alive.  With it kp_target_ptr is [B,V,K,2], kp_conf_ptr [B,V,K], the image flag is set and `views` stays None.
+    The shape is checked here, the rest by the library -- which cannot see the values of a table in device memory: a row whose fx or fy
+    is not positive switches its view off for that pose."""
+    opt = ProjectOptions10()
+    if pose_views is not None and kw.get("image") is None:
+        kw = dict(kw, image=True)
+    opt._base9 = project_options9(lib, *args, **kw)      # (kept: it owns what the copy below points to)
+    opt.base9 = opt._base9
+    opt.base9.base8.base7.base6.base5.base4.base3.base2.base.struct_size = ctypes.sizeof(opt)
+    if pose_views is not None:
+        table = pose_views
+        is_tensor = torch is not None and isinstance(table, torch.Tensor)
+        if not is_tensor:
+            table = np.ascontiguousarray(table, dtype=np.float32)
+        elif table.dtype != torch.float32 or not table.is_contiguous():
+            raise PndfError(f"pose_views is a contiguous float32 tensor, not {table.dtype} with strides {tuple(table.stride())}")
+        if table.ndim != 3 or table.shape[2] != 16:
+            raise PndfError(f"pose_views is [B,V,16] or [frames,V,16], not {list(table.shape)}")
+        opt._pose_views = table      # the table lives as long as the struct
+        filled = table.numel() if is_tensor else table.size
+        opt.pose_views = (table.data_ptr() if is_tensor else table.ctypes.data) if filled else None
+        opt.n_pose_views = int(table.shape[1]) if filled else 0
+        opt.view_flags = VIEWS_PER_FRAME if views_per_frame and filled else 0
     return opt
 
 
@@ -662,13 +692,21 @@ class SkeletonEngine(_Handle):
         `project_options7`); views: the cameras of a fit to pixels seen by several views, kp_target_ptr then [B,V,K,2] and kp_conf_ptr
         [B,V,K] (through a pndf_project_options8: `project_options8`, built only when views are given); root_smooth, root_anchor_ptr
         [B,7] in device memory, root_data: the root's trajectory over the frames of a track (through a pndf_project_options9:
-        `project_options9`, built only when one of them says something)"""
+        `project_options9`, built only when one of them says something); pose_views [B,V,16] or, with views_per_frame, [frames,V,16]: a
+        tensor in device memory, the cameras of a fit to pixels seen by moving views (through a pndf_project_options10:
+        `project_options10`, built only when pose_views is given)"""
         views = keypoints.pop("views", None)
+        pose_views, views_per_frame = keypoints.pop("pose_views", None), keypoints.pop("views_per_frame", False)
         rooted, keypoints = _root_tracked(keypoints)
         lengthed, keypoints = _lengthed(keypoints)
         imaged, keypoints = _imaged(keypoints)
         named = _keypointed(keypoints)      # (refuses an unknown keyword)
-        if rooted is not None:
+        if pose_views is not None:
+            opt10 = project_options10(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends, views=views,
+                                      step_size=step_size, renorm=renorm, tol=tol, pose_views=pose_views, views_per_frame=views_per_frame,
+                                      **keypoints, **(imaged or {}), **(lengthed or {}), **(rooted or {}))
+            opt = ctypes.byref(opt10)
+        elif rooted is not None:
             opt9 = project_options9(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends, views=views,
                                     step_size=step_size, renorm=renorm, tol=tol, **keypoints, **(imaged or {}), **(lengthed or {}), **rooted)
             opt = ctypes.byref(opt9)
@@ -888,12 +926,20 @@ class CpuEngine(_Handle):
         root_ptr / root_weights / camera / rho / image a pndf_project_options6: `project_options6`, or with bone_scale_ptr / len_rate /
         len_weight / len_prior / len_range / per_pose_lengths a pndf_project_options7: `project_options7`, or with views a
         pndf_project_options8: `project_options8`, or with root_smooth / root_anchor_ptr / root_data a pndf_project_options9:
-        `project_options9`)"""
+        `project_options9`, or with pose_views / views_per_frame a pndf_project_options10: `project_options10`)"""
         views = keypoints.pop("views", None)
+        pose_views, views_per_frame = keypoints.pop("pose_views", None), keypoints.pop("views_per_frame", False)
         rooted, keypoints = _root_tracked(keypoints)
         lengthed, keypoints = _lengthed(keypoints)
         imaged, keypoints = _imaged(keypoints)
         named = _keypointed(keypoints)      # (refuses an unknown keyword)
+        if pose_views is not None:
+            opt10 = project_options10(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends, views=views,
+                                      step_size=step_size, renorm=renorm, tol=tol, pose_views=pose_views, views_per_frame=views_per_frame,
+                                      **keypoints, **(imaged or {}), **(lengthed or {}), **(rooted or {}))
+            self._check(self.lib.pndf_project_ex_cpu(self.handle, q_in_ptr, q_out_ptr, d_ptr, B, int(steps), ctypes.byref(opt10)),
+                        "pndf_project_ex_cpu")
+            return
         if rooted is not None:
             opt9 = project_options9(self.lib, observed_ptr, frames, smooth, fill, anchor_ptr, conf_ptr, data, free_ends, views=views,
                                     step_size=step_size, renorm=renorm, tol=tol, **keypoints, **(imaged or {}), **(lengthed or {}), **rooted)

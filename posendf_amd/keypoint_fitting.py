@@ -10,7 +10,8 @@ starts per target and returns, per target, the hypothesis of the lowest `energy 
 With a `camera` the detections are pixels [N,K,2], and with a `root` the tree is placed in the target's frame by a rotation and a
 translation per pose that the steps move as well (pndf_project_options6; DESIGN.md section 2j "Image fitting"): a hand tracker's output.
 With `views` the detections are pixels [N,V,K,2] of the same frame in V calibrated cameras (pndf_project_options8; DESIGN.md section 2j
-"Several cameras"); `--views FILE.npz` on the command line.
+"Several cameras"); `--views FILE.npz` on the command line.  With `views` [N,V,16] the cameras move from frame to frame
+(pndf_project_options10; DESIGN.md section 2j "Moving cameras"); arrays with a leading frame dimension in FILE.npz select that form.
 With `fit_lengths=True` the segment lengths of the subject are unknowns too: a scale per rest offset and per keypoint offset
 (pndf_project_options7; DESIGN.md section 2j "Bone lengths").
 
@@ -32,16 +33,21 @@ def keypoint_energy(pose, targets, parents, rest, conf=None, keypoint_joints=Non
     confidence is not positive (zero, negative, NaN) takes no part, whatever its target holds.  With a `camera` the targets are pixels and
     the residual e is taken in normalised image coordinates, rho(e) = e^2 or (rho > 0) rho^2 e^2 / (e^2 + rho^2) summed over both axes; a
     keypoint that is not in front of the camera takes no part.  With `views` (`SkeletonPoseNDF.fit_keypoints(views=)`) the targets are
-    [...,V,K,2], the confidences [...,V,K] and the sum runs over views and keypoints"""
+    [...,V,K,2], the confidences [...,V,K] and the sum runs over views and keypoints; `views` [...,V,16] with leading dimensions is a table
+    per pose (moving cameras), in which a view whose fx or fy is not positive takes no part for that pose"""
     from .engine import view_table
     from .skeleton import camera_project, forward_kinematics
     C = camera_project(forward_kinematics(pose, parents, rest, keypoint_joints, keypoint_offsets, bone_scale), root)
     if views is not None:
-        vt = torch.as_tensor(view_table(views), dtype=C.dtype, device=C.device)
-        C = (vt[:, 4:13].reshape(-1, 1, 3, 3) @ C.unsqueeze(-3).unsqueeze(-1)).squeeze(-1) + vt[:, 13:16].unsqueeze(-2)      # [...,V,K,3]
-        front = C[..., 2] > 0
+        moving = hasattr(views, "shape") and len(views.shape) > 2
+        vt = torch.as_tensor(views if moving else view_table(views), dtype=C.dtype, device=C.device)      # [V,16], or [...,V,16]
+        C = (vt[..., 4:13].reshape(vt.shape[:-1] + (1, 3, 3)) @ C.unsqueeze(-3).unsqueeze(-1)).squeeze(-1) + vt[..., 13:16].unsqueeze(-2)      # [...,V,K,3]
+        focal = vt[..., 0:2].unsqueeze(-2)
+        on_view = ((focal[..., 0] > 0) & (focal[..., 1] > 0)).expand(C.shape[:-1])
+        focal = torch.where(on_view.unsqueeze(-1), focal, torch.ones_like(focal))
+        front = (C[..., 2] > 0) & on_view
         z = torch.where(front, C[..., 2], torch.ones_like(C[..., 2]))
-        e = C[..., :2] / z.unsqueeze(-1) - (targets - vt[:, 2:4].unsqueeze(-2)) / vt[:, 0:2].unsqueeze(-2)
+        e = C[..., :2] / z.unsqueeze(-1) - (targets - vt[..., 2:4].unsqueeze(-2)) / focal
         ee = e * e
         cost = ee if not rho else float(rho) ** 2 * ee / (ee + float(rho) ** 2)
         sq = torch.where(front, cost.sum(-1), torch.zeros_like(z))
@@ -60,6 +66,18 @@ def keypoint_energy(pose, targets, parents, rest, conf=None, keypoint_joints=Non
         on = conf > 0
         sq = torch.where(on, conf * torch.where(on, sq, torch.zeros_like(sq)), torch.zeros_like(sq))
     return 0.5 * (sq.sum((-2, -1)) if views is not None else sq.sum(-1))
+
+
+def view_tables(K, R, t):
+    """The view table [N,V,16] float32 of cameras that move from frame to frame (`SkeletonPoseNDF.fit_keypoints` with a 3-D `views`), from
+    arrays with a leading frame dimension: K [N,V,3,3] or [N,V,4] = (fx, fy, cx, cy), R [N,V,3,3] and t [N,V,3], world -> camera"""
+    import numpy as np
+    K, R, t = (np.asarray(v, dtype=np.float64) for v in (K, R, t))
+    if K.ndim == 4 and K.shape[2:] == (3, 3):
+        K = np.stack([K[..., 0, 0], K[..., 1, 1], K[..., 0, 2], K[..., 1, 2]], axis=-1)
+    if K.ndim != 3 or K.shape[2] != 4 or R.shape != K.shape[:2] + (3, 3) or t.shape != K.shape[:2] + (3,):
+        raise ValueError(f"moving views are K [N,V,3,3] or [N,V,4], R [N,V,3,3] and t [N,V,3], not {K.shape}, {R.shape}, {t.shape}")
+    return np.ascontiguousarray(np.concatenate([K, R.reshape(R.shape[:2] + (9,)), t], axis=-1), dtype=np.float32)
 
 
 class KeypointFitting(SamplePose):
@@ -94,7 +112,9 @@ class KeypointFitting(SamplePose):
         it.
         `views` (a [V,16] array or a sequence of (K, R, t): `SkeletonPoseNDF.fit_keypoints(views=)`): targets are [N,V,K,2] pixels of the
         same frame in V calibrated cameras and conf [K], [V,K] or [N,V,K]; the root places the tree in the world frame.  Not with
-        `camera`.  The weights tried for one camera are the only ones known; several views add their gradients, so start lower."""
+        `camera`.  The weights tried for one camera are the only ones known; several views add their gradients, so start lower.
+        `views` [N,V,16] (a tensor or array): a table per target, for cameras that move from frame to frame (pndf_project_options10); its
+        rows are repeated per hypothesis.  A row whose fx or fy is not positive switches its view off for that target."""
         net = self.pose_prior
         if not hasattr(net, "fit_keypoints"):
             raise TypeError(f"{type(net).__name__} has no fit_keypoints(): fitting to 3D keypoints is SkeletonPoseNDF's; a PoseNDF fits 2D "
@@ -118,6 +138,11 @@ class KeypointFitting(SamplePose):
         rt = None
         if root is not None:
             rt = torch.as_tensor(root).to(self.device).float().expand(N, 7)[:, None].expand(N, H, 7).reshape(N * H, 7).contiguous()
+        if views is not None and hasattr(views, "shape") and len(views.shape) == 3:      # a table per target: one copy per hypothesis
+            vm = torch.as_tensor(views).to(self.device).float()
+            if vm.shape[0] != N or vm.shape[1] != y.shape[1] or vm.shape[2] != 16:
+                raise ValueError(f"views with a table per target are [{N},{y.shape[1]},16], not {list(vm.shape)}")
+            views = vm[:, None].expand(N, H, vm.shape[1], 16).reshape(N * H, vm.shape[1], 16).contiguous()
         image = dict(camera=camera, rho=rho, root_weights=tuple(root_weights), **({} if views is None else dict(views=views))) if placed else {}
         c = None
         if conf is not None:
@@ -172,6 +197,8 @@ class KeypointFitting(SamplePose):
         refused, so with the default `root_weights` = (0, 0) the defaults of this method are a call without a root trajectory.
         Returns (pose [P*T,J,4], energy [P*T] and dist [P*T] of the last step, root [P*T,7]: the identity placement when there is none)
         and with `fit_lengths` the scales [P,S].
+        `views` [T,V,16] (one camera path for every clip) or [P*T,V,16] (pndf_project_options10): cameras that move from frame to frame;
+        stage 1 gets the table of every frame, stage 2 the table as given.
         The reference implementation has no such driver: it fits single frames.  The schedule (60 steps, smooth 0.25, the translation
         coupled with 0.25, the rotation not) is UNTUNED: no trained skeleton model exists to tune it on."""
         net = self.pose_prior
@@ -179,7 +206,13 @@ class KeypointFitting(SamplePose):
         y = targets.to(self.device).float()
         if T < 2 or y.shape[0] % T != 0:
             raise ValueError(f"targets are P * T frames with T = frames >= 2, not {y.shape[0]} frames with frames = {frames}")
+        views = fit.get("views")
+        if views is not None and hasattr(views, "shape") and len(views.shape) == 3 and views.shape[0] == T and y.shape[0] != T:
+            per_frame = torch.as_tensor(views).float()      # stage 1 fits single frames: every frame of every clip gets its table
+            fit = dict(fit, views=per_frame.repeat(y.shape[0] // T, 1, 1))
         first = self.fit(y, rest, conf=conf, **fit)
+        if views is not None:
+            fit = dict(fit, views=views)
         pose = first[0]
         placed = fit.get("camera") is not None or fit.get("root") is not None or fit.get("views") is not None
         root = first[4] if placed else None      # (the identity placement when a camera or views came without a root)
@@ -242,7 +275,9 @@ def main(argv=None):
                     help="fit a scale per rest offset and per keypoint offset besides (weights untuned); written to the key scale")
     ap.add_argument("--views", default=None, metavar="FILE.npz",
                     help="calibration of several cameras: arrays K [V,3,3] (or [V,4] = fx, fy, cx, cy), R [V,3,3] and t [V,3], world -> camera; "
-                         "keypoints are then [N,V,K,2] pixels (not with a camera in the keypoint file)")
+                         "keypoints are then [N,V,K,2] pixels (not with a camera in the keypoint file).  Arrays with a leading frame dimension "
+                         "-- K [N,V,3,3] (or [N,V,4]), R [N,V,3,3], t [N,V,3] -- are cameras that move from frame to frame; with --clip T, N "
+                         "is T (one path for every clip) or the number of frames")
     ap.add_argument("--clip", type=int, default=0, metavar="T",
                     help="the keypoints are clips of T consecutive frames each: after the fit per frame one tracked call couples the poses and the "
                          "roots along every clip (KeypointFitting.fit_clip; schedule untuned)")
@@ -267,7 +302,10 @@ def main(argv=None):
     if a.views:
         import numpy as np
         with np.load(a.views) as f:
-            extra["views"] = [(f["K"][v], f["R"][v], f["t"][v]) for v in range(f["R"].shape[0])]
+            if f["R"].ndim == 4:      # a leading frame dimension: cameras that move from frame to frame
+                extra["views"] = view_tables(f["K"], f["R"], f["t"])
+            else:
+                extra["views"] = [(f["K"][v], f["R"][v], f["t"][v]) for v in range(f["R"].shape[0])]
     if a.root_smooth is not None and not a.clip:
         ap.error("--root_smooth needs --clip T")
     if a.clip:

@@ -28,6 +28,7 @@ With `views=` the detections are pixels of the same frame in several calibrated 
 `camera_project(..., views=)` is the torch statement of the pixels).
 With `root_smooth=` / `root_anchor=` / `root_data=` the roots of the frames of a track are coupled to their neighbours' and drawn towards an
 observed trajectory (a pndf_project_options9).
+With a 3-D `views=` [B,V,16] or [frames,V,16] the cameras move from pose to pose or from frame to frame (a pndf_project_options10).
 Only the second order stays 21-joint: its C ABI refuses another joint count, and that refusal is pinned.
 """
 from __future__ import annotations
@@ -281,6 +282,11 @@ class SkeletonPoseNDF(PoseModel):
         the tree, to the camera's (C = R W + t).  A view whose confidence for a keypoint is not positive, or behind which the keypoint
         lies, takes no part for it and its target is not read.  `camera=` together with `views=` is an error.  `camera_project(views=)` is
         the torch statement of the pixels.
+        Moving cameras (pndf_project_options10; DESIGN.md section 2j "Moving cameras"): `views` as a 3-D tensor or array is a table per
+        pose [B,V,16], or with `frames` a table per frame of a track [frames,V,16] -- one camera path shared by every track; when B ==
+        frames the two mean the same.  It is moved to the poses' device as contiguous float32.  A row whose fx or fy is not positive
+        (zeros, NaNs) switches its view off for that pose: neither its targets nor its confidences are read.  In a row that is on,
+        finite entries are the caller's responsibility: the library cannot look at a table in device memory.
         The root's trajectory (pndf_project_options9; DESIGN.md section 2j "Root trajectory"): `root_smooth` = (lambda_rot, lambda_trans),
         each in [0, 1], couples the root of every frame of a track (`frames`) to the roots of its neighbour frames as `smooth` couples
         the joints, the end frames with their one neighbour whether or not `free_ends` is set; `root_anchor` [B,7] (where `poses` may
@@ -324,12 +330,20 @@ class SkeletonPoseNDF(PoseModel):
             raise PndfError("camera= is the one camera of a fit and views= the several: give one of them")
         if camera is not None and len(tuple(camera)) != 4:
             raise PndfError("camera is (fx, fy, cx, cy)")
-        vt = None if views is None else view_table(views)
+        mv = None      # the moving table [B,V,16] or [frames,V,16] of a pndf_project_options10
+        if views is not None and hasattr(views, "shape") and len(views.shape) == 3:
+            mv = on_device(views, "views")
+            if not mv.is_floating_point() or mv.shape[2] != 16:
+                raise PndfError(f"views with a block per pose or frame is a floating-point [N,V,16], not {mv.dtype} {list(mv.shape)}")
+        vt = None if views is None or mv is not None else view_table(views)
         V = 1 if vt is None else int(vt.shape[0])
-        if vt is not None and not 1 <= V <= MAX_VIEWS:
+        if mv is not None:
+            V = int(mv.shape[1])
+        several = vt is not None or mv is not None
+        if several and not 1 <= V <= MAX_VIEWS:
             raise PndfError(f"views are 1 .. {MAX_VIEWS} rows, not {V}")
         y = on_device(targets, "targets").float()
-        if vt is not None:
+        if several:
             if y.dim() < 3 or tuple(y.shape[-3:]) != (V, K, 2) or y.numel() != B * V * K * 2:
                 raise PndfError(f"targets are [{B},{V},{K},2] with views, not {list(y.shape)}")
             y = y.reshape(B, V, K, 2).contiguous()
@@ -359,6 +373,14 @@ class SkeletonPoseNDF(PoseModel):
         T = int(frames or 0)
         if T == 1:
             T = 0
+        per_frame = False
+        if mv is not None:
+            N = int(mv.shape[0])
+            if N != B and not (T >= 2 and N == T):
+                raise PndfError(f"views [{N},{V},16] has neither a block per pose ([{B},{V},16]) nor a block per frame of a track "
+                                f"([frames,{V},16] with frames = {T})")
+            per_frame = N != B
+            mv = mv.float().contiguous()
         S = J + K
         G = B if (per_pose_scale or T < 2) else (B // T if B % T == 0 else -1)
         lengthed = bone_scale is not None or bool(scale_weight) or bool(scale_prior) or scale_range is not None or scale_rates is not None or bool(per_pose_scale)
@@ -378,7 +400,7 @@ class SkeletonPoseNDF(PoseModel):
         c = None
         if conf is not None:
             c = on_device(conf, "conf")
-            if vt is not None:
+            if several:
                 if not c.is_floating_point() or tuple(c.shape) not in ((K,), (V, K), (B, V, K)):
                     raise PndfError(f"conf is a floating-point tensor [{K}], [{V},{K}] or [{B},{V},{K}] with views, not {c.dtype} {list(c.shape)}")
                 c = c.float().expand(B, V, K).contiguous()
@@ -410,6 +432,7 @@ class SkeletonPoseNDF(PoseModel):
                         **(dict(root_ptr=place.data_ptr() if place is not None and B else None, root_weights=tuple(root_weights) if B else (0.0, 0.0), camera=camera, rho=rho)
                            if place is not None or camera is not None or rho or any(root_weights) else {}),
                         **(dict(views=vt) if vt is not None and B else {}),      # (without poses there are no targets for the views to size)
+                        **(dict(pose_views=mv, views_per_frame=per_frame) if mv is not None and B else {}),
                         **(dict(root_smooth=tuple(root_smooth) if B else (0.0, 0.0), root_data=tuple(root_data) if B else (0.0, 0.0),
                                 root_anchor_ptr=track_anchor.data_ptr() if track_anchor is not None and B else None) if root_tracked else {}),
                         **(dict(bone_scale_ptr=scales.data_ptr() if scales is not None and B else None, len_rate=rates, len_weight=scale_weight if B else 0.0,
@@ -483,7 +506,8 @@ def camera_project(points, root=None, camera=None, views=None):
     [...,K,2] of a pinhole camera that looks along +z.  This is the statement `SkeletonPoseNDF.fit_keypoints(camera=..., root=...)`
     (csrc/pndf_fk.h) descends; use it to make targets and to read residuals.  With `views` ([V,16], or a sequence of (K or (fx, fy, cx, cy),
     R, t): `fit_keypoints(views=)`) the root places the tree in the world frame and the result is [...,V,K,2]: the pixels
-    (fx C_x / C_z + cx, fy C_y / C_z + cy) of C = R_v W + t_v in every view."""
+    (fx C_x / C_z + cx, fy C_y / C_z + cy) of C = R_v W + t_v in every view.  A `views` tensor or array with leading dimensions,
+    [...,V,16], is a table per pose (moving cameras): those dimensions broadcast against the points' and the result is [...,V,K,2]."""
     if camera is not None and views is not None:
         raise PndfError("camera= is the one camera and views= the several: give one of them")
     if points.shape[-1] != 3:
@@ -500,6 +524,15 @@ def camera_project(points, root=None, camera=None, views=None):
                          2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
                          2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], dim=-1).reshape(r.shape[:-1] + (3, 3))
         C = (R.unsqueeze(-3) @ points.unsqueeze(-1)).squeeze(-1) + s.unsqueeze(-2)
+    if views is not None and hasattr(views, "shape") and len(views.shape) > 2:
+        # moving cameras (`fit_keypoints` with a 3-D views): a table [...,V,16] whose leading dimensions broadcast against the points'
+        vt = torch.as_tensor(views, dtype=points.dtype, device=points.device)
+        if vt.shape[-1] != 16:
+            raise PndfError(f"views with leading dimensions is [...,V,16], not {tuple(vt.shape)}")
+        Rv = vt[..., 4:13].reshape(vt.shape[:-1] + (1, 3, 3))                                         # [...,V,1,3,3]
+        Cv = (Rv @ C.unsqueeze(-3).unsqueeze(-1)).squeeze(-1) + vt[..., 13:16].unsqueeze(-2)         # [...,V,K,3]
+        f, pp = vt[..., 0:2].unsqueeze(-2), vt[..., 2:4].unsqueeze(-2)
+        return f * Cv[..., :2] / Cv[..., 2:3] + pp
     if views is not None:
         vt = torch.as_tensor(view_table(views), dtype=points.dtype, device=points.device)      # [V,16]
         Cv = (vt[:, 4:13].reshape(-1, 1, 3, 3) @ C.unsqueeze(-3).unsqueeze(-1)).squeeze(-1) + vt[:, 13:16].unsqueeze(-2)      # [...,V,K,3]
